@@ -6,9 +6,12 @@
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 Inputs (uint8 NHWC images) are resident in HBM before the timed region; weights are the seeded synthetic
-stream (no real .weights ships with the reference).  `roofline` prices the dominant kernel (the fused
-implicit-GEMM conv) with HIP events recorded by the library on its own stream; `cpu_baseline` times the
-reference's own C code (oracle/_ref) on the host cores for a bounded sample.
+stream (no real .weights ships with the reference).  A plain run sets up, warms up, times --steps steps and
+prints the headline line.  --full adds the legs that take runs of their own, after the timed region:
+`roofline` prices the dominant kernel (the fused implicit-GEMM conv) with HIP events recorded by the library
+on its own stream, plus the batch-1 latency, the calibration yardsticks, `parity` against the fp32 oracle,
+`tolerance_line` and `cpu_baseline` (the reference's own C code, oracle/_ref, on the host cores for a bounded
+sample).  --dump-outputs DIR writes the box records of the last timed step as DIR/<name>.npy (float32).
 """
 import argparse
 import json
@@ -24,6 +27,23 @@ sys.path.insert(0, ROOT)
 PEAK_BF16_TFLOPS = 2500.0      # MI355X dense bf16 MFMA (MI355X_MICROARCH.md, chip-level parameters)
 PEAK_FP8_TFLOPS = 5000.0       # dense e4m3 through v_mfma_*_f8f6f4 (same table)
 PEAK_F32_TFLOPS = 157.3        # v_mfma_f32_16x16x4_f32: exact fp32 at the vector rate (same table, "Peak FP32 (matrix)")
+
+
+def dump_outputs(out_dir, boxes, counts, max_out):
+    """What a caller of the timed step receives, as float32 arrays in `out_dir`: the yolo_box records (x0, y0, x1, y1, score, cls)
+    of every image, boxes [n, max_out, 4], scores / classes [n, max_out], and counts [n].  Slots past an image's count hold
+    nothing the library promises: they are written as zeros (class -1), so that two builds compare record for record."""
+    recs = np.ascontiguousarray(boxes, dtype=np.int32).reshape(-1, max_out, 6)
+    counts = np.ascontiguousarray(counts, dtype=np.int32).reshape(recs.shape[0])
+    keep = np.arange(max_out)[None, :] < counts[:, None]
+    f = recs.view(np.float32)
+    arrays = {"boxes": np.where(keep[..., None], f[..., :4], np.float32(0)),
+              "scores": np.where(keep, f[..., 4], np.float32(0)),
+              "classes": np.where(keep, recs[..., 5], -1),
+              "counts": counts}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float32))
 
 
 def cpu_baseline(cfg_txt, flat, budget_s=25.0):
@@ -219,6 +239,12 @@ def main():
                     help="after the headline leg, time the configuration that meets north_star's IoU >= 0.999 in the same process and print it inside the "
                          "same JSON line as `tolerance_line` (rank 0, N = 1, default workload only; outside the headline's timed region)")
     ap.add_argument("--no-calibration", action="store_true", help="skip roofline.calib_tflops / clock_ghz (the register-resident MFMA yardstick, 0.4 s)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the legs that take runs of their own: `roofline` (library events per forward), the batch-1 "
+                         "latency, the calibration yardsticks, `parity`, `tolerance_line`, `cpu_baseline` and the functional exchange check of "
+                         "BENCH_BACKEND=gloo (each still subject to its --no-* / --parity-images / --tolerance option); off: the headline line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the box records of the last timed step (rank 0: the global batch when N > 1) as DIR/{boxes,scores,classes,counts}.npy, float32")
     args = ap.parse_args()
     if args.config4:
         args.size, args.global_batch = 608, args.global_batch or 64
@@ -345,8 +371,9 @@ def main():
     for i in range(args.steps):
         step()
         ev[i + 1].record(stream)
+    gathered = None
     if gather is not None:
-        gather.result()                         # the last step's exchange completes inside the timed region
+        gathered = gather.result()              # the last step's exchange completes inside the timed region
     torch.cuda.synchronize(dev)
     if G > 1:
         dist.barrier()
@@ -357,8 +384,15 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     step_ms = np.array([ev[i].elapsed_time(ev[i + 1]) for i in range(args.steps)])
+    if args.dump_outputs and rank == 0:
+        # the last timed step's records, before anything else runs on the engine: this rank's buffers, or the gathered global batch
+        if gathered is not None:
+            out_boxes, out_counts = ydist.split_flat_records_ragged(gathered, GB, max_out)
+        else:
+            out_boxes, out_counts = boxes[:n_local], counts[:n_local]
+        dump_outputs(args.dump_outputs, out_boxes.cpu().numpy(), out_counts.cpu().numpy(), max_out)
     exchange_ok = None
-    if gather is not None and backend == "gloo":
+    if args.full and gather is not None and backend == "gloo":
         # functional check of the exchange: one more step, gathered; this rank's slot must hold its own records, and the counts of all ranks
         # must be those of n_local real images followed by the zero padding of a short rank
         step(); allrec = gather.result()
@@ -374,21 +408,6 @@ def main():
         exchange_ok = bool(flag.item())
 
     if rank == 0:
-        total_ms, conv_ms = eng.time_forward(n_local, 10, conv=True)
-        # HBM bytes per forward of the conv launches: PMC counters cannot be read in-process, so this is the committed
-        # rocprofv3 measurement (tools/profile_round.sh) -- printed only when it was taken on exactly this code and tile plan
-        # (source hash), null otherwise: a stale number is never reported
-        traffic = None
-        from yolo_tensorflow_amd import buildinfo
-        for tpath in sorted(__import__("glob").glob(os.path.join(ROOT, "profiles", "r*_hbm_traffic.json")), reverse=True):
-            try:
-                tj = json.load(open(tpath))
-                if loaded and tj.get("source_hash") == buildinfo.source_hash(args.size, B, args.dtype):
-                    traffic = tj["conv_hbm_bytes_per_forward"]; break
-            except Exception:      # noqa: BLE001
-                pass
-        flops = eng.conv_flops() * n_local
-        achieved = flops / (conv_ms * 1e-3) / 1e12
         out = {
             "metric": "images_per_sec", "value": round(GB * args.steps / elapsed, 2), "unit": "img/s",
             "n_gpus": G, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
@@ -403,49 +422,68 @@ def main():
                                       "exchange (the last one is waited for inside the timed region)" % G},
             "p50_ms_per_image": round(float(np.median(step_ms)) / n_local, 5),
             "p50_ms_per_batch": round(float(np.median(step_ms)), 4),
-            "roofline": {"bound": "mfma", "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s",
-                         "frac": round(achieved / peak, 4), "traffic": traffic,
-                         "kernel": "conv_igemm_f32 (every conv launch of one forward)" if fp32 else "conv_igemm + conv_stem (every conv launch of one forward)", "flops_per_forward": flops,
-                         "kernel_ms_per_forward": round(conv_ms, 4), "forward_ms": round(total_ms, 4)},
         }
         if backend == "gloo" and (G > 1 or force_dist):
             out["backend"] = ("gloo: FUNCTIONAL multi-rank run -- %d ranks on %d GPU(s), box records exchanged through pinned host buffers; exercises the N > 1 "
                               "code path, not a scaling measurement" % (G, max(1, torch.cuda.device_count())))
-            out["exchange_check"] = exchange_ok
+            if args.full:
+                out["exchange_check"] = exchange_ok
         if hip.LIB_OVERRIDE:
             out["lib_override"] = hip.LIB_OVERRIDE          # measured through YOLO_HIP_LIB (an A/B probe build), not the in-tree library
-        if strong:      # a fixed global batch leaves each rank a small share: say which regime that share runs in, so a poor strong curve reads correctly
-            out["config"]["per_rank"] = {"images_on_rank0": n_local, "conv_frac_of_peak_on_rank0": round(achieved / peak, 4),
-                                         "regime": "launch-bound (per-launch fixed cost dominates: DESIGN.md section 6)" if achieved / peak < 0.25 else "matrix-pipe / fixed-cost mix"}
-        if G == 1 and not args.no_latency:
-            out.update(latency_b1(hip, cfg_txt, flat, args, dev, stream, fp8, fp32, fp16, x2, eng if B == 1 else None))
-        if not args.no_calibration and not fp32:
-            # the box's own yardstick, outside the timed region and AFTER the timed work (the chip is warm): what a register-resident MFMA loop
-            # sustains here and at which clock -- `frac_of_calib` is what compares between boxes (the same binary reads 9 % apart by box)
-            ct, cg = hip.calibrate(0.4, f16=fp16 or x2, device=local_rank, stream=stream.cuda_stream)
-            mult = 2.0 if fp8 and not mixed else 1.0          # (the e4m3 MFMA runs at twice the 16-bit rate the loop measures)
-            try:
-                cc = hip.calibrate_copy(0.2, device=local_rank, stream=stream.cuda_stream)
-            except Exception:      # noqa: BLE001
-                cc = None
-            out["roofline"].update({"calib_tflops": round(ct, 1), "clock_ghz": round(cg, 3), "calib_copy_gbs": round(cc, 0) if cc else None,
-                                    "frac_of_calib": round(achieved / (ct * mult), 4) if ct > 0 and not mixed else None,
-                                    "calib": "yolo_calibrate: register-resident v_mfma_f32_16x16x32 loop, 8 waves per CU, random operands, 0.4 s; clock = s_memtime / s_memrealtime; yolo_calibrate_copy: streaming 1 GiB -> 1 GiB device copy, GB/s read + written"})
-        refs, imgs_par, t_or = None, None, 0.0
-        if G == 1 and args.parity_images > 0:
-            imgs_par = images[:min(args.parity_images, n_local)].cpu().numpy()
-            t_or = time.time()
-            refs = oracle_boxes(cfg_txt.replace("yolo_store=bf16\n", "").replace("yolo_store=fp8\n", "").replace("yolo_pair=0\n", "").replace("yolo_pair=1\n", "").replace("yolo_pair_input=0\n", ""), flat, imgs_par, args.size)
-            t_or = time.time() - t_or
-            out["parity"] = parity(eng, refs, imgs_par, t_oracle=t_or)
-        if G == 1 and args.tolerance != "none" and args.dtype == "bf16" and not strong and not args.no_graph:
-            base_txt = IO.cfg_text("yolov3") if args.size == 416 else IO.with_input_size(IO.cfg_text("yolov3"), args.size)
-            try:
-                out["tolerance_line"] = tolerance_line(hip, IO, base_txt, flat, args, dev, stream, images, refs, imgs_par, args.tolerance)
-            except Exception as e:      # noqa: BLE001 -- the headline line must not depend on the extra leg
-                out["tolerance_line"] = {"dtype": args.tolerance, "error": "%s: %s" % (type(e).__name__, e)}
-        if G == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(cfg_txt, flat)
+        if strong:
+            out["config"]["per_rank"] = {"images_on_rank0": n_local}
+        if args.full:      # the legs after the timed region that take runs of their own
+            total_ms, conv_ms = eng.time_forward(n_local, 10, conv=True)
+            # HBM bytes per forward of the conv launches: PMC counters cannot be read in-process, so this is the committed
+            # rocprofv3 measurement (tools/profile_round.sh) -- printed only when it was taken on exactly this code and tile plan
+            # (source hash), null otherwise: a stale number is never reported
+            traffic = None
+            from yolo_tensorflow_amd import buildinfo
+            for tpath in sorted(__import__("glob").glob(os.path.join(ROOT, "profiles", "r*_hbm_traffic.json")), reverse=True):
+                try:
+                    tj = json.load(open(tpath))
+                    if loaded and tj.get("source_hash") == buildinfo.source_hash(args.size, B, args.dtype):
+                        traffic = tj["conv_hbm_bytes_per_forward"]; break
+                except Exception:      # noqa: BLE001
+                    pass
+            flops = eng.conv_flops() * n_local
+            achieved = flops / (conv_ms * 1e-3) / 1e12
+            out["roofline"] = {"bound": "mfma", "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s",
+                               "frac": round(achieved / peak, 4), "traffic": traffic,
+                               "kernel": "conv_igemm_f32 (every conv launch of one forward)" if fp32 else "conv_igemm + conv_stem (every conv launch of one forward)", "flops_per_forward": flops,
+                               "kernel_ms_per_forward": round(conv_ms, 4), "forward_ms": round(total_ms, 4)}
+            if strong:      # a fixed global batch leaves each rank a small share: say which regime that share runs in, so a poor strong curve reads correctly
+                out["config"]["per_rank"].update({"conv_frac_of_peak_on_rank0": round(achieved / peak, 4),
+                                                  "regime": "launch-bound (per-launch fixed cost dominates: DESIGN.md section 6)" if achieved / peak < 0.25 else "matrix-pipe / fixed-cost mix"})
+            if G == 1 and not args.no_latency:
+                out.update(latency_b1(hip, cfg_txt, flat, args, dev, stream, fp8, fp32, fp16, x2, eng if B == 1 else None))
+            if not args.no_calibration and not fp32:
+                # the box's own yardstick, outside the timed region and AFTER the timed work (the chip is warm): what a register-resident MFMA loop
+                # sustains here and at which clock -- `frac_of_calib` is what compares between boxes (the same binary reads 9 % apart by box)
+                ct, cg = hip.calibrate(0.4, f16=fp16 or x2, device=local_rank, stream=stream.cuda_stream)
+                mult = 2.0 if fp8 and not mixed else 1.0          # (the e4m3 MFMA runs at twice the 16-bit rate the loop measures)
+                try:
+                    cc = hip.calibrate_copy(0.2, device=local_rank, stream=stream.cuda_stream)
+                except Exception:      # noqa: BLE001
+                    cc = None
+                out["roofline"].update({"calib_tflops": round(ct, 1), "clock_ghz": round(cg, 3), "calib_copy_gbs": round(cc, 0) if cc else None,
+                                        "frac_of_calib": round(achieved / (ct * mult), 4) if ct > 0 and not mixed else None,
+                                        "calib": "yolo_calibrate: register-resident v_mfma_f32_16x16x32 loop, 8 waves per CU, random operands, 0.4 s; clock = s_memtime / s_memrealtime; yolo_calibrate_copy: streaming 1 GiB -> 1 GiB device copy, GB/s read + written"})
+            refs, imgs_par, t_or = None, None, 0.0
+            if G == 1 and args.parity_images > 0:
+                imgs_par = images[:min(args.parity_images, n_local)].cpu().numpy()
+                t_or = time.time()
+                refs = oracle_boxes(cfg_txt.replace("yolo_store=bf16\n", "").replace("yolo_store=fp8\n", "").replace("yolo_pair=0\n", "").replace("yolo_pair=1\n", "").replace("yolo_pair_input=0\n", ""), flat, imgs_par, args.size)
+                t_or = time.time() - t_or
+                out["parity"] = parity(eng, refs, imgs_par, t_oracle=t_or)
+            if G == 1 and args.tolerance != "none" and args.dtype == "bf16" and not strong and not args.no_graph:
+                base_txt = IO.cfg_text("yolov3") if args.size == 416 else IO.with_input_size(IO.cfg_text("yolov3"), args.size)
+                try:
+                    out["tolerance_line"] = tolerance_line(hip, IO, base_txt, flat, args, dev, stream, images, refs, imgs_par, args.tolerance)
+                except Exception as e:      # noqa: BLE001 -- the headline line must not depend on the extra leg
+                    out["tolerance_line"] = {"dtype": args.tolerance, "error": "%s: %s" % (type(e).__name__, e)}
+            if G == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(cfg_txt, flat)
         print(json.dumps(out), flush=True)
     eng.close()
     if G > 1 or force_dist:

@@ -66,7 +66,7 @@ def test_bench_force_dist_path(hiplib, capsys, monkeypatch):
         pytest.fail("torch does not see the GPU")
     monkeypatch.setenv("BENCH_FORCE_DIST", "1")
     monkeypatch.setenv("MASTER_PORT", str(30700 + os.getpid() % 1000))
-    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3", "--warmup", "2", "--no-cpu-baseline"])
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3", "--warmup", "2", "--no-cpu-baseline", "--full"])
     sys.path.insert(0, ROOT)
     import bench
     bench.main()
@@ -83,7 +83,7 @@ def test_bench_strong_scaling_and_parity_fields(hiplib, capsys, monkeypatch):
         pytest.fail("torch does not see the GPU")
     monkeypatch.setenv("BENCH_FORCE_DIST", "1")
     monkeypatch.setenv("MASTER_PORT", str(31700 + os.getpid() % 1000))
-    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3", "--warmup", "2", "--no-cpu-baseline", "--global-batch", "8", "--parity-images", "1"])
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3", "--warmup", "2", "--no-cpu-baseline", "--global-batch", "8", "--parity-images", "1", "--full"])
     sys.path.insert(0, ROOT)
     import bench
     bench.main()
@@ -110,7 +110,7 @@ def test_bench_two_ranks_one_gpu(hiplib, tmp_path):
         env.pop(k, None)
     port = str(32700 + os.getpid() % 1000)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", port,
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--global-batch", "33", "--no-tune", "--no-cpu-baseline", "--parity-images", "0"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--global-batch", "33", "--no-tune", "--no-cpu-baseline", "--parity-images", "0", "--full"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -156,6 +156,7 @@ DARKNET_PY_SYMBOLS = ["network_width", "network_height", "network_predict", "cud
 
 def test_darknet_veneer_exports_everything_darknet_py_binds():
     import ctypes as C
+    import json
     import re
     path = os.path.join(ROOT, "yolo_tensorflow_amd", "libdarknet_hip.so")
     assert os.path.exists(path), "libdarknet_hip.so is not built"
@@ -165,10 +166,9 @@ def test_darknet_veneer_exports_everything_darknet_py_binds():
     hdr = open(os.path.join(ROOT, "include", "darknet_hip.h")).read()
     for name in DARKNET_PY_SYMBOLS + ["free_network", "set_batch_network"]:
         assert re.search(r"\b%s\(" % name, hdr), "include/darknet_hip.h does not declare %s" % name
-    ref = "/root/reference/Darknet2Tensorflow/darknet-master/darknet.py"
-    if os.path.exists(ref):                       # build container only: the list above is what that file binds
-        bound = set(re.findall(r"\blib\.(\w+)", open(ref).read()))
-        assert bound == set(DARKNET_PY_SYMBOLS), bound ^ set(DARKNET_PY_SYMBOLS)
+    # the list above is what that file binds (tests/golden/darknet_py_bound_symbols.json, tools/make_golden.py gen_darknet_py_symbols)
+    bound = set(json.load(open(os.path.join(ROOT, "tests", "golden", "darknet_py_bound_symbols.json")))["lib_symbols"])
+    assert bound == set(DARKNET_PY_SYMBOLS), bound ^ set(DARKNET_PY_SYMBOLS)
 
 
 def test_draw_detection_counterpart(tmp_path):
@@ -260,3 +260,24 @@ def test_pair_closure_and_cfg_keys():
     t3 = IO.with_layer_pairs(txt, IO.pair_closure(secs, set()))
     assert "yolo_pair_input=0" in t3 and t3.count("yolo_pair=0") == 75
     assert IO.with_layer_pairs(t3, allp).count("yolo_pair") == 3                   # (idempotent: old keys are dropped; only the three heads say plain)
+
+
+def test_bench_dump_outputs_writes_the_records_a_caller_receives(tmp_path):
+    """bench.py --dump-outputs: the flat int32 yolo_box buffer of the detect step -> float32 boxes / scores / classes / counts, the slots
+    past an image's count written as zeros (class -1) whatever the buffer held there."""
+    import bench
+    from yolo_tensorflow_amd.hip import BOX_DTYPE
+    rng = np.random.default_rng(5)
+    max_out, counts = 4, np.array([2, 0, 4], np.int32)
+    recs = np.zeros((3, max_out), BOX_DTYPE)
+    for f in ("x0", "y0", "x1", "y1", "score"):
+        recs[f] = rng.random((3, max_out), dtype=np.float32)
+    recs["cls"] = rng.integers(0, 80, (3, max_out))
+    bench.dump_outputs(str(tmp_path / "d"), recs.view(np.int32).reshape(3, max_out * 6), counts, max_out)
+    got = {n: np.load(str(tmp_path / "d" / (n + ".npy"))) for n in ("boxes", "scores", "classes", "counts")}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert np.array_equal(got["counts"], counts.astype(np.float32))
+    for b, n in enumerate(counts):
+        assert np.array_equal(got["boxes"][b, :n], np.stack([recs[f][b, :n] for f in ("x0", "y0", "x1", "y1")], -1))
+        assert np.array_equal(got["scores"][b, :n], recs["score"][b, :n]) and np.array_equal(got["classes"][b, :n], recs["cls"][b, :n].astype(np.float32))
+        assert not got["boxes"][b, n:].any() and not got["scores"][b, n:].any() and (got["classes"][b, n:] == -1).all()

@@ -525,12 +525,24 @@ def gen_known_answers():
     json.dump(out, open(os.path.join(OUT, "dog_known_answers.json"), "w"), indent=1)
 
 
+def gen_darknet_py_symbols():
+    """Every symbol the reference's Python binding resolves from libdarknet.so (`lib.X` in D2T/darknet.py:49-115): the names only ->
+    tests/golden/darknet_py_bound_symbols.json, what tests/test_host.py holds libdarknet_hip.so's exports against."""
+    import json, re
+    text = open(os.path.join(REF, "Darknet2Tensorflow", "darknet-master", "darknet.py")).read()
+    names = sorted(set(re.findall(r"\blib\.(\w+)", text)))
+    json.dump({"source": "D2T/darknet.py", "lib_symbols": names}, open(os.path.join(OUT, "darknet_py_bound_symbols.json"), "w"), indent=1)
+    print("darknet.py binds", len(names), "symbols")
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     if sys.argv[1:] == ["bn_real"]:
         gen_bn_real(); sys.exit(0)
     if sys.argv[1:] == ["known_answers"]:
         gen_known_answers(); sys.exit(0)
+    if sys.argv[1:] == ["darknet_py_symbols"]:
+        gen_darknet_py_symbols(); sys.exit(0)
     stub_modules()
     gen_nms_v3()
     gen_v2_post()
@@ -540,3 +552,4 @@ if __name__ == "__main__":
     gen_mini_local()
     gen_bn_real()
     gen_known_answers()
+    gen_darknet_py_symbols()

@@ -1,7 +1,7 @@
 #!/bin/bash
 # plain (write-back) output stores + image windows: does the Infinity Cache keep a producer's tensor for its consumer when the stores are not write-through?
 cd "$(dirname "$0")/../.."
-run() { python bench.py --dtype $1 --no-cpu-baseline --no-latency --tolerance none --parity-images 0 --no-calibration 2>/dev/null | python -c "
+run() { python bench.py --full --dtype $1 --no-cpu-baseline --no-latency --tolerance none --parity-images 0 --no-calibration 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.readline()); print('$1 $3 windows=$2: %.0f img/s, step %.3f ms, conv %.3f ms' % (d['value'], d['ms_per_step'], d['roofline']['kernel_ms_per_forward']))"; }
 for lib in sc1 plain; do
