@@ -26,38 +26,8 @@
 // whole step gains 0.2 %: what the memory system no longer does, stage 1, the staging and the piece loop spend in issue slots (ablation:
 // stage 1 9, DMA issue 3, piece loop 15, staging / barriers / waits 25 us).  HBM traffic of a forward falls by 350 MB (6 %).
 #include "kernels.h"
+#include "device_common.h"
 #include <type_traits>
-
-typedef __bf16 cb_bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 cb_f16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 cb_bf16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 cb_f16x2 __attribute__((ext_vector_type(2)));
-typedef float cb_f32x2 __attribute__((ext_vector_type(2)));
-typedef float cb_f32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t cb_u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void cb_lds_void;
-typedef __attribute__((address_space(3))) char cb_lds_char;
-
-template <bool H16> __device__ __forceinline__ uint32_t cb_pk(float lo, float hi)
-{
-    if constexpr (H16) return __builtin_bit_cast(uint32_t, __builtin_convertvector(cb_f32x2{lo, hi}, cb_f16x2));      // (MODE.FP16_OVFL: an overflowing conversion saturates at +-65504)
-    else return __builtin_bit_cast(uint32_t, __builtin_convertvector(cb_f32x2{lo, hi}, cb_bf16x2));
-}
-template <bool H16> __device__ __forceinline__ float cb_lo(uint32_t w) { if constexpr (H16) return (float)__builtin_bit_cast(cb_f16x2, w)[0]; else return __builtin_bit_cast(float, w << 16); }
-template <bool H16> __device__ __forceinline__ float cb_hi(uint32_t w) { if constexpr (H16) return (float)__builtin_bit_cast(cb_f16x2, w)[1]; else return __builtin_bit_cast(float, w & 0xffff0000u); }
-__device__ __forceinline__ float cb_max(float a, float b) { float r; asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-// acc + bias, activation (slope 0.1: leaky as max(v, 0.1 v); slope 1: linear), rounded to the storage type: four channels as two packed words
-template <bool H16> __device__ __forceinline__ uint2 cb_epi(const cb_f32x4 acc, const cb_f32x4 bias, const float slope)
-{
-    cb_f32x4 v = acc + bias;
-    const cb_f32x4 t = v * slope;
-    return uint2{cb_pk<H16>(cb_max(v[0], t[0]), cb_max(v[1], t[1])), cb_pk<H16>(cb_max(v[2], t[2]), cb_max(v[3], t[3]))};
-}
-template <bool H16> __device__ __forceinline__ cb_f32x4 cb_mma(const cb_bf16x8 a, const cb_bf16x8 b, const cb_f32x4 c)
-{
-    if constexpr (H16) return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(cb_f16x8, a), __builtin_bit_cast(cb_f16x8, b), c, 0, 0, 0);
-    else return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
 
 constexpr int CB_B = 13;                               // output block edge
 constexpr int CB_T = CB_B + 2;                         // halo tile edge: 15
@@ -83,7 +53,7 @@ __global__ __launch_bounds__(64 * CB_NW) void conv_resblock_c128(const BlockArgs
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    if constexpr (H16) __builtin_amdgcn_s_setreg((0 << 11) | (23 << 6) | 1, 1);      // hwreg(HW_REG_MODE, 23, 1) = FP16_OVFL
+    if constexpr (H16) fp16_saturating_mode();      // fp16 conversions saturate
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l15 = lane & 15, lq = lane >> 4;
     const int wc = wave & 3, wp = wave >> 2;             // channel group (32 output channels of the 3x3), pixel half
@@ -97,23 +67,23 @@ __global__ __launch_bounds__(64 * CB_NW) void conv_resblock_c128(const BlockArgs
         const int row = g >> 4, piece = g & 15;
         *(uint4 *)(lw1_ + row * CB_W1PITCH + piece * 16) = *(const uint4 *)((const bf16_t *)a.w1 + (size_t)row * a.Kpad1 + piece * 8);
     }
-    cb_bf16x8 fw2[2][18];                                // [channel tile of this wave][tap * 2 + half]: K = tap * 64 + half * 32 + lq * 8 ..
+    bf16x8 fw2[2][18];                                   // [channel tile of this wave][tap * 2 + half]: K = tap * 64 + half * 32 + lq * 8 ..
 #pragma unroll
     for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
         for (int ks = 0; ks < 18; ++ks)
-            fw2[ct][ks] = *(const cb_bf16x8 *)((const bf16_t *)a.w2 + (size_t)(wc * 32 + ct * 16 + l15) * a.Kpad2 + ks * 32 + lq * 8);
+            fw2[ct][ks] = *(const bf16x8 *)((const bf16_t *)a.w2 + (size_t)(wc * 32 + ct * 16 + l15) * a.Kpad2 + ks * 32 + lq * 8);
     if (tid < CB_M) *(float *)(lb1_ + tid * 4) = a.b1[tid];
     if (tid < CB_C) *(float *)(lb2_ + tid * 4) = a.b2[tid];
 
-    __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void *)a.x, 0, 0x80000000u, 0x00020000);
-    __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc((void *)a.out, 0, 0x80000000u, 0x00020000);
+    __amdgpu_buffer_rsrc_t rx = buf_rsrc(a.x);
+    __amdgpu_buffer_rsrc_t ro = buf_rsrc(a.out);
 
     struct Blk { int n, y0, x0; };                       // image, origin of the output block
     auto blk_of = [&](int j) { const int b = (int)blockIdx.x + j * (int)gridDim.x; Blk q; q.n = b / per_img; const int r = b - q.n * per_img; q.y0 = (r / bx) * CB_B; q.x0 = (r - (r / bx) * bx) * CB_B; return q; };
     // the 15 x 15 x 128 halo tile of block `q` -> lx: 3600 16-byte pieces (225 pixels x 16), lane-linear 1 KiB per instruction; the piece at
     // LDS slot `phys` of pixel p holds global chunk phys ^ (p & 7); pixels outside the image are zero-filled by the range check
-    auto fetch_x = [&](const Blk &q, cb_lds_char *dst) {
+    auto fetch_x = [&](const Blk &q, lds_char *dst) {
         // Row by row: a tile row is 15 pixels x 256 B, contiguous in global memory and in LDS; piece id = 4 * row + part covers tile pixels
         // c = 4 * part + (lane >> 4) of that row (the 16th does not exist: those lanes stay out), chunk lane & 15 of each.  Everything but the
         // column test and the swizzle key -- (pixel & 7) = (c - row) & 7, 15 being -1 mod 8 -- is scalar.
@@ -126,20 +96,20 @@ __global__ __launch_bounds__(64 * CB_NW) void conv_resblock_c128(const BlockArgs
             const int iy = q.y0 - 1 + r, ix = q.x0 - 1 + c;
             const bool ok = (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
             const unsigned off = ok ? (unsigned)((((q.n * a.H + iy) * a.W + ix) * a.x_stride + ((chunk ^ ((c - r) & 7)) * 8)) * 2) : 0x80000000u;
-            if (c < CB_T) __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (cb_lds_void *)(dst + (r * CB_T + (id & 3) * 4) * 256), 16, off, 0, 0, 0);
+            if (c < CB_T) __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (lds_void *)(dst + (r * CB_T + (id & 3) * 4) * 256), 16, off, 0, 0, 0);
         }
     };
 
     // ---- per-lane constants of the 3x3's fragment reads: output pixel (j, l15) = raster index j * 16 + l15 of the 13 x 13 block ----
     // address of mid pixel (oy + kh, ox + kw), 32-channel half h, this lane's 16 bytes: mida[j] + ((kh * 15 + kw) * CB_MPITCH + h * 64), the
     // second term an immediate
-    typedef const __attribute__((address_space(3))) cb_bf16x8 *lds_frag_p;
+    typedef const __attribute__((address_space(3))) bf16x8 *lds_frag_p;
     uint32_t mida[CB_NJ];
 #pragma unroll
     for (int j = 0; j < CB_NJ; ++j) {
         int q = (wp * CB_NJ + j) * 16 + l15; if (q >= CB_OPIX) q = CB_OPIX - 1;     // (the last sub-tile's spare lanes repeat the last pixel: computed, not stored)
         const int oy = (q * 5042) >> 16, ox = q - oy * CB_B;         // q / 13 for q < 176
-        mida[j] = (uint32_t)(uintptr_t)(cb_lds_char *)lmid_ + (uint32_t)((oy * CB_T + ox) * CB_MPITCH + lq * 16);
+        mida[j] = (uint32_t)(uintptr_t)(lds_char *)lmid_ + (uint32_t)((oy * CB_T + ox) * CB_MPITCH + lq * 16);
         asm volatile("" : "+v"(mida[j]));
     }
 
@@ -147,28 +117,28 @@ __global__ __launch_bounds__(64 * CB_NW) void conv_resblock_c128(const BlockArgs
     // the NEXT block fills; the mid tile twice, as what stage 1 writes and (null-based: `mida` holds absolute addresses) as what stage 2
     // reads -- or hipcc, which cannot tell an LDS-DMA's target from any other LDS access, waits vmcnt(0) in front of the first LDS read
     // after every fetch: the whole latency of the prefetch, exposed.  The barriers order what the parameters hide.
-    auto block = [&](int it, const cb_lds_char *__restrict__ lx, cb_lds_char *__restrict__ lx_dma, cb_lds_char *__restrict__ lmid, const cb_lds_char *__restrict__ mid_rd,
-                     const cb_lds_char *__restrict__ lw1, const cb_lds_char *__restrict__ lb1, const cb_lds_char *__restrict__ lb2, cb_lds_char *__restrict__ lout) {
+    auto block = [&](int it, const lds_char *__restrict__ lx, lds_char *__restrict__ lx_dma, lds_char *__restrict__ lmid, const lds_char *__restrict__ mid_rd,
+                     const lds_char *__restrict__ lw1, const lds_char *__restrict__ lb1, const lds_char *__restrict__ lb2, lds_char *__restrict__ lout) {
         const Blk q = blk_of(it);
         // this block's halo tile has landed (first pass: and the 1x1 filters are written): the vector-memory queue is in order, and behind the
         // tile's LDS-DMA this thread issued the previous block's 6 shortcut loads (consumed since) and 6 stores, which may still be in flight
         static_assert((CB_OPIX * 16 + 64 * CB_NW - 1) / (64 * CB_NW) == 6, "vmcnt below counts the stores of one thread");
-        if (it > 0) __builtin_amdgcn_s_waitcnt(0x0076);  // vmcnt(6) lgkmcnt(0)  (the first tile was waited for in front of the loop)
+        if (it > 0) __builtin_amdgcn_s_waitcnt(waitcnt_imm(6, 0));  // (the first tile was waited for in front of the loop)
         __builtin_amdgcn_s_barrier();
         // ================= stage 1: mid = act1(W1 . x + b1) on the 225 halo pixels, zero outside the image =================
         // sub-tile pair (2u, 2u+1), u = wave: 8 pairs cover 16 sub-tiles (the 16th is padding rows: skipped)
         {
             const int u = wave;
-            cb_f32x4 acc[2][4];
+            f32x4 acc[2][4];
 #pragma unroll
             for (int s = 0; s < 2; ++s)
 #pragma unroll
-                for (int ct = 0; ct < 4; ++ct) acc[s][ct] = cb_f32x4{0.f, 0.f, 0.f, 0.f};
+                for (int ct = 0; ct < 4; ++ct) acc[s][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
             int p0 = (2 * u) * 16 + l15;
             asm volatile("" : "+v"(p0));
             const int p1 = p0 + 16;
             // the fragments of K-step kk + 1 (two of pixels, four of filters) are requested ahead of the MFMAs of K-step kk
-            cb_bf16x8 xf[2][2], wf[2][4];
+            bf16x8 xf[2][2], wf[2][4];
             auto frags = [&](int kk) {
                 xf[kk & 1][0] = *(lds_frag_p)(lx + p0 * 256 + (((kk * 4 + lq) ^ (p0 & 7)) << 4));
                 xf[kk & 1][1] = *(lds_frag_p)(lx + p1 * 256 + (((kk * 4 + lq) ^ (p1 & 7)) << 4));
@@ -182,8 +152,8 @@ __global__ __launch_bounds__(64 * CB_NW) void conv_resblock_c128(const BlockArgs
                 if (kk + 1 < 4) frags(kk + 1);
 #pragma unroll
                 for (int ct = 0; ct < 4; ++ct) {
-                    acc[0][ct] = cb_mma<H16>(wf[kk & 1][ct], xf[kk & 1][0], acc[0][ct]);
-                    acc[1][ct] = cb_mma<H16>(wf[kk & 1][ct], xf[kk & 1][1], acc[1][ct]);
+                    acc[0][ct] = mma16<H16>(wf[kk & 1][ct], xf[kk & 1][0], acc[0][ct]);
+                    acc[1][ct] = mma16<H16>(wf[kk & 1][ct], xf[kk & 1][1], acc[1][ct]);
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -195,26 +165,26 @@ __global__ __launch_bounds__(64 * CB_NW) void conv_resblock_c128(const BlockArgs
                 const bool inside = p < CB_TPIX && (unsigned)(q.y0 - 1 + r) < (unsigned)a.H && (unsigned)(q.x0 - 1 + col) < (unsigned)a.W;
 #pragma unroll
                 for (int ct = 0; ct < 4; ++ct) {
-                    uint2 pk = cb_epi<H16>(acc[s][ct], *(const __attribute__((address_space(3))) cb_f32x4 *)(lb1 + (ct * 16 + lq * 4) * 4), slope1);
+                    uint2 pk = leaky_pack4<H16>(acc[s][ct], *(const __attribute__((address_space(3))) f32x4 *)(lb1 + (ct * 16 + lq * 4) * 4), slope1);
                     if (!inside) pk = uint2{0u, 0u};
                     *(__attribute__((address_space(3))) uint2 *)(lmid + p * CB_MPITCH + (ct * 16 + lq * 4) * 2) = pk;
                 }
             }
         }
-        __builtin_amdgcn_s_waitcnt(0xc07f);
+        __builtin_amdgcn_s_waitcnt(waitcnt_imm(63, 0));
         __builtin_amdgcn_s_barrier();                    // the mid tile is complete; the x tile is free
         if (it + 1 < nt) fetch_x(blk_of(it + 1), lx_dma);        // lands during stage 2
         // ================= stage 2: 3x3 over the mid tile, filters in registers =================
-        cb_f32x4 acc2[2][CB_NJ];
+        f32x4 acc2[2][CB_NJ];
 #pragma unroll
         for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
-            for (int j = 0; j < CB_NJ; ++j) acc2[ct][j] = cb_f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int j = 0; j < CB_NJ; ++j) acc2[ct][j] = f32x4{0.f, 0.f, 0.f, 0.f};
         // K-step ks = tap * 2 + half.  The 6 pixel fragments of a K-step are read in three groups of 2, each one group ahead of the MFMAs that
         // consume it (the fences keep hipcc from re-ordering the software pipeline); the SIMD's other wave covers the rest of the LDS latency.
         // (Registers are the constraint: 144 of filters + 48 accumulators leave 64, and ONE spilled value is ruinous here -- scratch accesses
         //  share vmcnt with the LDS-DMA and the stores, so every reload waits for whatever of those is in flight.)
-        cb_bf16x8 fg[3][2];
+        bf16x8 fg[3][2];
         auto koff = [](int ks) { const int t = ks >> 1, h = ks & 1, kh = t / 3, kw = t - kh * 3; return (kh * CB_T + kw) * CB_MPITCH + h * 64; };
 #pragma unroll
         for (int j = 0; j < 2; ++j) fg[0][j] = *(lds_frag_p)(mid_rd + mida[j] + koff(0));
@@ -229,7 +199,7 @@ __global__ __launch_bounds__(64 * CB_NW) void conv_resblock_c128(const BlockArgs
                     for (int j = 0; j < 2; ++j) fg[gn][j] = *(lds_frag_p)(mid_rd + mida[gn * 2 + j] + koff(ksn));
                 }
 #pragma unroll
-                for (int j = 0; j < 2; ++j) { acc2[0][g * 2 + j] = cb_mma<H16>(fw2[0][ks], fg[g][j], acc2[0][g * 2 + j]); acc2[1][g * 2 + j] = cb_mma<H16>(fw2[1][ks], fg[g][j], acc2[1][g * 2 + j]); }
+                for (int j = 0; j < 2; ++j) { acc2[0][g * 2 + j] = mma16<H16>(fw2[0][ks], fg[g][j], acc2[0][g * 2 + j]); acc2[1][g * 2 + j] = mma16<H16>(fw2[1][ks], fg[g][j], acc2[1][g * 2 + j]); }
                 __builtin_amdgcn_sched_barrier(0);
             }
         // ================= epilogue =================
@@ -237,15 +207,15 @@ __global__ __launch_bounds__(64 * CB_NW) void conv_resblock_c128(const BlockArgs
         // (x at the pixels and channels it stores below) are requested in between, as soon as half the accumulators are dead -- their
         // latency runs under the second half and the barrier
         auto stage_out = [&](int ct) {
-            const cb_f32x4 bv = *(const __attribute__((address_space(3))) cb_f32x4 *)(lb2 + (wc * 32 + ct * 16 + lq * 4) * 4);
+            const f32x4 bv = *(const __attribute__((address_space(3))) f32x4 *)(lb2 + (wc * 32 + ct * 16 + lq * 4) * 4);
 #pragma unroll
             for (int j = 0; j < CB_NJ; ++j)
                 if (wp * CB_NJ + j < CB_OSUB)                // (wave-uniform: the second half has one idle slot)
-                    *(__attribute__((address_space(3))) uint2 *)(lout + ((wp * CB_NJ + j) * 16 + l15) * CB_OPITCH + (wc * 32 + ct * 16 + lq * 4) * 2) = cb_epi<H16>(acc2[ct][j], bv, slope2);
+                    *(__attribute__((address_space(3))) uint2 *)(lout + ((wp * CB_NJ + j) * 16 + l15) * CB_OPITCH + (wc * 32 + ct * 16 + lq * 4) * 2) = leaky_pack4<H16>(acc2[ct][j], bv, slope2);
         };
         stage_out(0);
         constexpr int NPIECE = (CB_OPIX * 16 + 64 * CB_NW - 1) / (64 * CB_NW);
-        cb_u32x4 rsv[NPIECE];
+        u32x4_t rsv[NPIECE];
 #pragma unroll
         for (int k = 0; k < NPIECE; ++k) {
             int g = tid + k * 64 * CB_NW;
@@ -256,7 +226,7 @@ __global__ __launch_bounds__(64 * CB_NW) void conv_resblock_c128(const BlockArgs
             rsv[k] = __builtin_amdgcn_raw_buffer_load_b128(rx, (px < CB_OPIX && q.y0 + oy < a.H && q.x0 + ox < a.W) ? (pix * a.x_stride + piece * 8) * 2 : 0x80000000u, 0, 0);
         }
         stage_out(1);
-        __builtin_amdgcn_s_waitcnt(0xc07f);
+        __builtin_amdgcn_s_waitcnt(waitcnt_imm(63, 0));
         __builtin_amdgcn_s_barrier();                    // staged tile complete (and every wave is done with the mid tile)
         // 169 pixels x 16 pieces of 16 bytes: piece g of thread tid + 256 k; the shortcut is x at the same pixel and channels
 #pragma unroll
@@ -267,16 +237,16 @@ __global__ __launch_bounds__(64 * CB_NW) void conv_resblock_c128(const BlockArgs
             const int oy = (px * 5042) >> 16, ox = px - oy * CB_B;
             const bool ok = px < CB_OPIX && q.y0 + oy < a.H && q.x0 + ox < a.W;
             const unsigned pix = (unsigned)((q.n * a.H + q.y0 + oy) * a.W + q.x0 + ox);
-            const cb_u32x4 r = rsv[k];
-            cb_u32x4 o = *(const __attribute__((address_space(3))) cb_u32x4 *)(lout + (px < CB_OPIX ? px : 0) * CB_OPITCH + piece * 16);
+            const u32x4_t r = rsv[k];
+            u32x4_t o = *(const __attribute__((address_space(3))) u32x4_t *)(lout + (px < CB_OPIX ? px : 0) * CB_OPITCH + piece * 16);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = cb_pk<H16>(cb_lo<H16>(o[e]) + cb_lo<H16>(r[e]), cb_hi<H16>(o[e]) + cb_hi<H16>(r[e]));
+            for (int e = 0; e < 4; ++e) o[e] = pack16x2<H16>(unpack16_lo<H16>(o[e]) + unpack16_lo<H16>(r[e]), unpack16_hi<H16>(o[e]) + unpack16_hi<H16>(r[e]));
             __builtin_amdgcn_raw_buffer_store_b128(o, ro, ok ? (pix * a.out_stride + piece * 8) * 2 : 0x80000000u, 0, OUT_STORE_AUX);
         }
     };
-    if (nt > 0) fetch_x(blk_of(0), (cb_lds_char *)lx_);
-    __builtin_amdgcn_s_waitcnt(0x0070);                  // vmcnt(0) lgkmcnt(0): the first halo tile has landed, the 1x1 filters are written
-    for (int it = 0; it < nt; ++it) block(it, (const cb_lds_char *)lx_, (cb_lds_char *)lx_, (cb_lds_char *)lmid_, (const cb_lds_char *)(uintptr_t)0, (const cb_lds_char *)lw1_, (const cb_lds_char *)lb1_, (const cb_lds_char *)lb2_, (cb_lds_char *)lout_);
+    if (nt > 0) fetch_x(blk_of(0), (lds_char *)lx_);
+    __builtin_amdgcn_s_waitcnt(waitcnt_imm(0, 0));       // the first halo tile has landed, the 1x1 filters are written
+    for (int it = 0; it < nt; ++it) block(it, (const lds_char *)lx_, (lds_char *)lx_, (lds_char *)lmid_, (const lds_char *)(uintptr_t)0, (const lds_char *)lw1_, (const lds_char *)lb1_, (const lds_char *)lb2_, (lds_char *)lout_);
 #endif
 }
 

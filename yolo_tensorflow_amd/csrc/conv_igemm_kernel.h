@@ -2,14 +2,10 @@
 // configurations) and conv_halo13.hip (halo-staged 3x3 configurations) so the two sets of instantiations compile in parallel.
 #pragma once
 #include "kernels.h"
+#include "device_common.h"
 #include "halo_perm_tables.h"
 #include <type_traits>
 #include <utility>
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) void lds_void;
 
 __device__ __forceinline__ uint32_t f32_to_bf16_rn(float f)
 {
@@ -17,66 +13,23 @@ __device__ __forceinline__ uint32_t f32_to_bf16_rn(float f)
     return (uint32_t)__builtin_bit_cast(uint16_t, b);
 }
 __device__ __forceinline__ float bf16_bits_to_f32(uint32_t b) { return __builtin_bit_cast(float, b << 16); }
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-// two floats -> packed bf16 pair (lo | hi << 16) in ONE v_cvt_pk_bf16_f32 (same RNE as f32_to_bf16_rn)
-__device__ __forceinline__ uint32_t f32x2_to_bf16x2(float lo, float hi)
-{
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2_t{lo, hi}, bf16x2_t));
-}
-// ---- 16-bit storage type of the EB = 2 kernels: bf16 (8-bit significand) or, H16 = true, IEEE fp16 (11-bit significand; same MFMA
-//      rate, v_mfma_f32_16x16x32_f16).  Values beyond fp16's range saturate at +-65504 on the way to memory. ----
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
-#define F16_MAX 65504.0f
-// The saturation is the hardware's: the fp16 kernels set MODE.FP16_OVFL (fp16_saturating_mode below), under which a conversion that
-// overflows yields +-65504 instead of an infinity -- two v_med3_f32 per stored pair less than clamping in fp32 first (that clamp was the
-// 3-4 % fp16 cost against bf16).
-__device__ __forceinline__ void fp16_saturating_mode() { __builtin_amdgcn_s_setreg((0 << 11) | (23 << 6) | 1, 1); }      // hwreg(HW_REG_MODE, 23, 1) = FP16_OVFL
-template <bool H16> __device__ __forceinline__ uint32_t pack16x2(float lo, float hi)
-{
-    if constexpr (H16) return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2_t{lo, hi}, f16x2_t));       // RNE, saturating (FP16_OVFL)
-    else return f32x2_to_bf16x2(lo, hi);
-}
-template <bool H16> __device__ __forceinline__ float unpack16_lo(uint32_t w)
-{
-    if constexpr (H16) return (float)__builtin_bit_cast(f16x2_t, w)[0]; else return __builtin_bit_cast(float, w << 16);
-}
-template <bool H16> __device__ __forceinline__ float unpack16_hi(uint32_t w)
-{
-    if constexpr (H16) return (float)__builtin_bit_cast(f16x2_t, w)[1]; else return __builtin_bit_cast(float, w & 0xffff0000u);
-}
-template <bool H16> __device__ __forceinline__ f32x4 mma16(const bf16x8 a, const bf16x8 b, const f32x4 c)
-{
-    if constexpr (H16) return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-    else return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
 // Split-fp16 pairs in the epilogues, on the mixed-precision FMA (round 6): `v_fma_mix_f32` reads an f16 half as one of its operands, so
 // hi + lo of a pair is ONE instruction per value (two conversions and an add before), and `v_fma_mixlo/hi_f16` forms f16(v - hi) into a half
 // of the destination in one (conversion, subtraction, conversion before).  Same values bit for bit: fp32(hi) * 1 + fp32(lo) and v - fp32(hi)
 // are exact in fp32 for a pair made by the split, the one rounding is the final one to f16 (RNE, as v_cvt_pk_f16_f32).
 __device__ __forceinline__ void pair_join2(uint32_t H, uint32_t L, float &a, float &b)
 {
-#ifdef PAIR_NO_MIX          // (probe builds: the conversions and separate add / subtract of rounds 4-5, for the same-box A/B)
-    a = unpack16_lo<true>(H) + unpack16_lo<true>(L); b = unpack16_hi<true>(H) + unpack16_hi<true>(L); return;
-#endif
     asm("v_fma_mix_f32 %0, %1, 1.0, %2 op_sel_hi:[1,0,1]" : "=v"(a) : "v"(H), "v"(L));
     asm("v_fma_mix_f32 %0, %1, 1.0, %2 op_sel:[1,0,1] op_sel_hi:[1,0,1]" : "=v"(b) : "v"(H), "v"(L));
 }
 __device__ __forceinline__ void pair_split2(float a, float b, uint32_t &H, uint32_t &L)
 {
     H = __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2_t{a, b}, f16x2_t));       // RNE, saturating (FP16_OVFL)
-#ifdef PAIR_NO_MIX
-    L = pack16x2<true>(a - unpack16_lo<true>(H), b - unpack16_hi<true>(H)); return;
-#endif
     uint32_t l;
     asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(l) : "v"(H), "v"(a));
     asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(l) : "v"(H), "v"(b));
     L = l;
 }
-// max(a, b) for finite operands without the sNaN-quieting v_max the compiler puts in front of fmaxf (one instruction, not two)
-__device__ __forceinline__ float vmax_f32(float a, float b) { float r; asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 // two floats -> two OCP e4m3 codes (RNE, saturating at +-448) merged into the low / high half of `old`
 template <bool HI> __device__ __forceinline__ uint32_t f32x2_to_fp8(float a, float b, uint32_t old)
 {
@@ -89,14 +42,8 @@ __device__ __forceinline__ int fast_div(int n, uint32_t mul, uint32_t shift)
     return shift == 255 ? n : (int)(__umulhi((uint32_t)n, mul) >> shift);
 }
 
-// probe knobs of the pair K loop (tools/probe/ab): fragment read-ahead in first uses, stagger of a SIMD's two waves in 1/64 MFMA-steps
-#ifndef PAIR_PD
-#define PAIR_PD 4
-#endif
-#ifndef PAIR_SLEEP
-#define PAIR_SLEEP 48
-#endif
-template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+// pair K loop: fragment read-ahead in first uses, stagger of a SIMD's two waves in 1/64 MFMA-steps (other values measured within 0.4 %)
+constexpr int PAIR_PD = 4, PAIR_SLEEP = 48;
 // counted wait with a wave-uniform run-time count (the immediate has to be a constant: a scalar branch ladder)
 template <int MAXN> __device__ __forceinline__ void wait_vmcnt_rt(int n)
 {
@@ -108,10 +55,8 @@ template <int MAXN> __device__ __forceinline__ void wait_vmcnt_rt(int n)
     default: wait_vmcnt<0>(); break;
     }
 }
-__device__ __forceinline__ void block_barrier() { asm volatile("s_barrier" ::: "memory"); }
 
-#define OOB_OFFSET 0x80000000u                  // >= num_records of every descriptor below -> DMA writes zeros
-#define BUF_RECORDS 0x80000000u
+#define OOB_OFFSET 0x80000000u                  // >= num_records of every descriptor below (buf_rsrc) -> DMA writes zeros
 
 // UNI: Cin_pad is a multiple of 64, so all 8 chunks of a K-step belong to one tap (scalar tap cursor).
 // otherwise (Cin_pad = 8, 16, 32, ...): the chunks of one K-step span several taps, tap cursor is per lane.
@@ -289,8 +234,8 @@ __global__ __launch_bounds__(64 * (WP * WC + NL)) void conv_igemm(const ConvArgs
     // Buffer descriptors.  The activation base is moved back by (W+1) pixels so that the offset of tap (0,0) of a
     // border pixel (one row up, one column left) is still >= 0.
     const int shift = HALO ? 0 : (a.W + 1) * a.in_stride * EB;      // bytes (the halo form only forms in-image offsets)
-    __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void *)((const char *)a.in - shift), 0, BUF_RECORDS, 0x00020000);
-    __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void *)a.wt, 0, BUF_RECORDS, 0x00020000);
+    __amdgpu_buffer_rsrc_t rx = buf_rsrc((const char *)a.in - shift);
+    __amdgpu_buffer_rsrc_t rw = buf_rsrc(a.wt);
 
     // ---- per-lane constants: wave w fills row groups w, w+NW, ...; inside a group lane l fills LDS slot
     //      (row l>>3, physical chunk l&7), i.e. logical K-chunk (l&7) ^ (row&7) of that row ----
@@ -799,7 +744,7 @@ __global__ __launch_bounds__(64 * (WP * WC + NL)) void conv_igemm(const ConvArgs
     auto tile_rsrc = [&](const void *p) -> __amdgpu_buffer_rsrc_t {
         const unsigned long long v = (unsigned long long)p;
         const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-        return __builtin_amdgcn_make_buffer_rsrc((void *)(((unsigned long long)hi << 32) | lo), 0, BUF_RECORDS, 0x00020000);
+        return buf_rsrc((const void *)(((unsigned long long)hi << 32) | lo));
     };
     // byte offset (from the tile origin, channel tile ct) of 16-byte piece c of the tile -- row-major, `cpr` pieces of `cpp` channels
     // per row, pixel stride `sb` bytes -- or OOB_OFFSET when the piece is not stored; also returns the piece's row and position

@@ -15,32 +15,7 @@
 //              everything outside the image are out-of-range requests: zeros).
 //   epilogue   bias, activation, rounding -> LDS (272-B rows) -> 16-byte pieces -> global (write-through, kernels.h OUT_STORE_AUX)
 #include "kernels.h"
-
-typedef __bf16 s2_bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 s2_f16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 s2_bf16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 s2_f16x2 __attribute__((ext_vector_type(2)));
-typedef float s2_f32x2 __attribute__((ext_vector_type(2)));
-typedef float s2_f32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void s2_lds_void;
-
-template <bool H16> __device__ __forceinline__ uint32_t s2_pk(float lo, float hi)
-{
-    if constexpr (H16) return __builtin_bit_cast(uint32_t, __builtin_convertvector(s2_f32x2{lo, hi}, s2_f16x2));      // (MODE.FP16_OVFL: saturating)
-    else return __builtin_bit_cast(uint32_t, __builtin_convertvector(s2_f32x2{lo, hi}, s2_bf16x2));
-}
-__device__ __forceinline__ float s2_max(float a, float b) { float r; asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-template <bool H16> __device__ __forceinline__ uint2 s2_epi(const s2_f32x4 acc, const s2_f32x4 bias, const float slope)
-{
-    s2_f32x4 v = acc + bias;
-    const s2_f32x4 t = v * slope;
-    return uint2{s2_pk<H16>(s2_max(v[0], t[0]), s2_max(v[1], t[1])), s2_pk<H16>(s2_max(v[2], t[2]), s2_max(v[3], t[3]))};
-}
-template <bool H16> __device__ __forceinline__ s2_f32x4 s2_mma(const s2_bf16x8 a, const s2_bf16x8 b, const s2_f32x4 c)
-{
-    if constexpr (H16) return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(s2_f16x8, a), __builtin_bit_cast(s2_f16x8, b), c, 0, 0, 0);
-    else return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
+#include "device_common.h"
 
 constexpr int S2_T = 8;                                  // output tile edge
 constexpr int S2_WIN = 2 * S2_T + 1;                     // input window edge: 17
@@ -60,26 +35,26 @@ __global__ __launch_bounds__(64 * S2_NW) void conv_s2_c64_c128(const HaloArgs a)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    if constexpr (H16) __builtin_amdgcn_s_setreg((0 << 11) | (23 << 6) | 1, 1);      // hwreg(HW_REG_MODE, 23, 1) = FP16_OVFL: fp16 conversions saturate
+    if constexpr (H16) fp16_saturating_mode();      // fp16 conversions saturate
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l15 = lane & 15, lq = lane >> 4;
     const int grp = wave & 3, half = wave >> 2;                  // channel group (32 output channels), pixel half (sub-tiles 2 half, 2 half + 1)
     // this wave's filters: 2 channel tiles x 18 K-slices (tap * 2 + channel half), rows K-contiguous with k = tap * 64 + c
-    s2_bf16x8 fw[2][18];
+    bf16x8 fw[2][18];
 #pragma unroll
     for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
         for (int ks = 0; ks < 18; ++ks)
-            fw[ct][ks] = *(const s2_bf16x8 *)((const bf16_t *)a.w + (size_t)(grp * 32 + ct * 16 + l15) * a.Kpad + ks * 32 + lq * 8);
-    s2_f32x4 bv[2];
+            fw[ct][ks] = *(const bf16x8 *)((const bf16_t *)a.w + (size_t)(grp * 32 + ct * 16 + l15) * a.Kpad + ks * 32 + lq * 8);
+    f32x4 bv[2];
 #pragma unroll
-    for (int ct = 0; ct < 2; ++ct) bv[ct] = *(const s2_f32x4 *)(a.b + grp * 32 + ct * 16 + lq * 4);
+    for (int ct = 0; ct < 2; ++ct) bv[ct] = *(const f32x4 *)(a.b + grp * 32 + ct * 16 + lq * 4);
     const float slope = a.act == ACT_LEAKY ? 0.1f : 1.f;
 
     const int Ho = (a.H - 1) / 2 + 1, Wo = (a.W - 1) / 2 + 1;
     const int tiles_x = (Wo + S2_T - 1) / S2_T, tiles_y = (Ho + S2_T - 1) / S2_T;
     const int per_img = tiles_x * tiles_y, ntiles = a.N * per_img;
-    __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc((void *)a.in, 0, 0x80000000u, 0x00020000);
+    __amdgpu_buffer_rsrc_t rin = buf_rsrc(a.in);
 
     // the pieces this lane requests for every tile: LDS slot g = (wave + 8 k) * 64 + lane is piece g % 9 of window pixel g / 9
     unsigned rel[S2_KMAX]; int wyx[S2_KMAX];                     // byte offset from the window's first pixel; window row | column << 8 (-1: no request)
@@ -103,7 +78,7 @@ __global__ __launch_bounds__(64 * S2_NW) void conv_s2_c64_c128(const HaloArgs a)
             if (c < S2_CHUNKS) {
                 const int wy = wyx[k] & 0xff, wx = (wyx[k] >> 8) & 0xff;
                 const bool ok = wyx[k] >= 0 && tile < ntiles && (unsigned)(iy0 + wy) < (unsigned)a.H && (unsigned)(ix0 + wx) < (unsigned)a.W;
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rin, (s2_lds_void *)(dst + c * 1024), 16, ok ? base + rel[k] : 0x80000000u, 0, 0, 0);
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rin, (lds_void *)(dst + c * 1024), 16, ok ? base + rel[k] : 0x80000000u, 0, 0, 0);
             }
         }
     };
@@ -124,11 +99,11 @@ __global__ __launch_bounds__(64 * S2_NW) void conv_s2_c64_c128(const HaloArgs a)
         const int n = tile / per_img, tr = tile - n * per_img;
         const int ty = tr / tiles_x, tx = tr - ty * tiles_x;
         const int oy0 = ty * S2_T, ox0 = tx * S2_T;
-        s2_f32x4 acc[2][2];
+        f32x4 acc[2][2];
 #pragma unroll
         for (int sb = 0; sb < 2; ++sb)
 #pragma unroll
-            for (int ct = 0; ct < 2; ++ct) acc[sb][ct] = s2_f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int ct = 0; ct < 2; ++ct) acc[sb][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int t = 0; t < 9; ++t) {
             const int kh = t / 3, kw = t - kh * 3;
@@ -138,9 +113,9 @@ __global__ __launch_bounds__(64 * S2_NW) void conv_s2_c64_c128(const HaloArgs a)
                 const int coff = ((hh * 4 + lq) ^ swz) << 4;
 #pragma unroll
                 for (int sb = 0; sb < 2; ++sb) {
-                    const s2_bf16x8 x = *(const s2_bf16x8 *)(in_cur + pb[sb] + (kh * S2_WIN + kw) * S2_PITCH + coff);
+                    const bf16x8 x = *(const bf16x8 *)(in_cur + pb[sb] + (kh * S2_WIN + kw) * S2_PITCH + coff);
 #pragma unroll
-                    for (int ct = 0; ct < 2; ++ct) acc[sb][ct] = s2_mma<H16>(fw[ct][t * 2 + hh], x, acc[sb][ct]);
+                    for (int ct = 0; ct < 2; ++ct) acc[sb][ct] = mma16<H16>(fw[ct][t * 2 + hh], x, acc[sb][ct]);
                 }
             }
         }
@@ -148,10 +123,10 @@ __global__ __launch_bounds__(64 * S2_NW) void conv_s2_c64_c128(const HaloArgs a)
         for (int sb = 0; sb < 2; ++sb)
 #pragma unroll
             for (int ct = 0; ct < 2; ++ct)
-                *(uint2 *)(lo + ((2 * half + sb) * 16 + l15) * S2_OPITCH + (grp * 32 + ct * 16 + lq * 4) * 2) = s2_epi<H16>(acc[sb][ct], bv[ct], slope);
+                *(uint2 *)(lo + ((2 * half + sb) * 16 + l15) * S2_OPITCH + (grp * 32 + ct * 16 + lq * 4) * 2) = leaky_pack4<H16>(acc[sb][ct], bv[ct], slope);
         // staged tile complete, every wave done with this tile's window; the next tile's window (requested a tile ago) must have landed.
         // Younger than its pieces in this wave's queue: the previous tile's two stores and the pieces requested at the top of this tile
-        if (wave == 0) __builtin_amdgcn_s_waitcnt(0x0078); else __builtin_amdgcn_s_waitcnt(0x0077);
+        if (wave == 0) __builtin_amdgcn_s_waitcnt(waitcnt_imm(8, 0)); else __builtin_amdgcn_s_waitcnt(waitcnt_imm(7, 0));
         __builtin_amdgcn_s_barrier();
 #pragma unroll
         for (int it = 0; it < S2_T * S2_T * 16 / (64 * S2_NW); ++it) {
@@ -163,7 +138,7 @@ __global__ __launch_bounds__(64 * S2_NW) void conv_s2_c64_c128(const HaloArgs a)
             out_store16_at(a.out, so, o.x, o.y, o.z, o.w);
         }
         // the next tile writes `lo` only after its own pre-store barrier and re-fills this tile's window slot at its top
-        __builtin_amdgcn_s_waitcnt(0xc07f);
+        __builtin_amdgcn_s_waitcnt(waitcnt_imm(63, 0));
         __builtin_amdgcn_s_barrier();
     };
 
@@ -172,7 +147,7 @@ __global__ __launch_bounds__(64 * S2_NW) void conv_s2_c64_c128(const HaloArgs a)
     const int G = gridDim.x;
     fetch_in(tile, inb);
     fetch_in(tile + G, inb + S2_IN_BYTES);
-    __builtin_amdgcn_s_waitcnt(0x0070);
+    __builtin_amdgcn_s_waitcnt(waitcnt_imm(0, 0));
     __builtin_amdgcn_s_barrier();
     for (int slot = 0; tile < ntiles; tile += G, slot = slot == 2 ? 0 : slot + 1) {
         const int fill = slot == 0 ? 2 : slot - 1;               // (slot + 2) % 3

@@ -20,38 +20,10 @@
 // leaves LDS, so that layer never re-reads its 177 MB input.
 // Workgroups are persistent (one 8-wave workgroup per CU) so the filter fragments (144 VGPRs of layer 1 in a consumer wave) are loaded once per wave.
 #include "kernels.h"
+#include "device_common.h"
 #include <type_traits>
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 // Both kernels are VALU-issue-bound (two waves per SIMD, ~4 cycles per instruction): the epilogues are written for instruction count.
-typedef __bf16 st_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float st_f32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 st_f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 st_f16x8 __attribute__((ext_vector_type(8)));
-// two floats -> packed 16-bit pair (lo | hi << 16), RNE: bf16 (one v_cvt_pk_bf16_f32) or, H16, fp16 saturating at +-65504 (MODE.FP16_OVFL, set at the top of the H16 kernels)
-template <bool H16> __device__ __forceinline__ uint32_t stem_pk(float lo, float hi)
-{
-    if constexpr (H16) return __builtin_bit_cast(uint32_t, __builtin_convertvector(st_f32x2{lo, hi}, st_f16x2));      // (the H16 kernels run with MODE.FP16_OVFL: an overflowing conversion saturates)
-    else return __builtin_bit_cast(uint32_t, __builtin_convertvector(st_f32x2{lo, hi}, st_bf16x2));
-}
-template <bool H16> __device__ __forceinline__ float stem_lo(uint32_t w) { if constexpr (H16) return (float)__builtin_bit_cast(st_f16x2, w)[0]; else return __builtin_bit_cast(float, w << 16); }
-template <bool H16> __device__ __forceinline__ float stem_hi(uint32_t w) { if constexpr (H16) return (float)__builtin_bit_cast(st_f16x2, w)[1]; else return __builtin_bit_cast(float, w & 0xffff0000u); }
-// max for finite operands as ONE instruction (fmaxf is preceded by an sNaN-quieting v_max)
-__device__ __forceinline__ float stem_max(float a, float b) { float r; asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-// acc + bias, activation (slope 0.1: leaky as max(v, 0.1 v); slope 1: linear), rounded to bf16: four channels as two packed words
-template <bool H16> __device__ __forceinline__ uint2 stem_epi(const f32x4 acc, const f32x4 bias, const float slope)
-{
-    f32x4 v = acc + bias;
-    const f32x4 t = v * slope;
-    return uint2{stem_pk<H16>(stem_max(v[0], t[0]), stem_max(v[1], t[1])), stem_pk<H16>(stem_max(v[2], t[2]), stem_max(v[3], t[3]))};
-}
-template <bool H16> __device__ __forceinline__ f32x4 stem_mma(const bf16x8 a, const bf16x8 b, const f32x4 c)
-{
-    if constexpr (H16) return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(st_f16x8, a), __builtin_bit_cast(st_f16x8, b), c, 0, 0, 0);
-    else return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
 
 constexpr int ST_TH = 8, ST_TW = 16;                 // layer-1 output tile
 constexpr int ST_LH = 2 * ST_TH + 1, ST_LW = 2 * ST_TW + 1;   // layer-0 pixels it needs: 17 x 33
@@ -64,8 +36,6 @@ constexpr int ST_OUT_BYTES = ST_TH * ST_TW * ST_OPITCH;       // 18432
 
 
 constexpr int ST_NW = 8;                             // waves per workgroup == ST_TH
-typedef __attribute__((address_space(3))) void st_lds_void;
-typedef __attribute__((address_space(3))) char lds_char;
 constexpr int ST_IH = ST_LH + 2, ST_IW = ST_LW + 2;          // input pixels a tile needs: 19 x 35
 constexpr int ST_INPIX = ST_IH * ST_IW;                      // 665
 constexpr int ST_INCHUNKS = (ST_INPIX + 63) / 64;            // 64-pixel LDS-DMA pieces: 11
@@ -100,7 +70,7 @@ __global__ __launch_bounds__(64 * ST_NW) void conv_stem_c32_c64(const StemArgs a
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    if constexpr (H16) __builtin_amdgcn_s_setreg((0 << 11) | (23 << 6) | 1, 1);      // hwreg(HW_REG_MODE, 23, 1) = FP16_OVFL: fp16 conversions saturate
+    if constexpr (H16) fp16_saturating_mode();      // fp16 conversions saturate
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l15 = lane & 15, lq = lane >> 4;
     const int sub = wave & 3;                                    // index among the four waves of this wave's role
@@ -174,7 +144,7 @@ __global__ __launch_bounds__(64 * ST_NW) void conv_stem_c32_c64(const StemArgs a
                         const int s_r = ((n * a.H + iy) * a.W + ix0) * 3;    // first byte the row needs
                         const bool ok = g < ST_RAW_DW && (unsigned)iy < (unsigned)a.H;
                         const unsigned off = ok ? (unsigned)((s_r & ~3) + 4 * d) : 0x80000000u;      // (a negative offset is out of range too: zeros)
-                        __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (st_lds_void *)(dst + c * 256), 4, off, 0, 0, 0);
+                        __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (lds_void *)(dst + c * 256), 4, off, 0, 0, 0);
                     }
                 }
             } else {
@@ -188,7 +158,7 @@ __global__ __launch_bounds__(64 * ST_NW) void conv_stem_c32_c64(const StemArgs a
                         const int iy = iy0 + ry, ix = ix0 + rxx;
                         const bool ok = q < ST_INPIX && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
                         const unsigned off = ok ? (unsigned)(((n * a.H + iy) * a.W + ix) * a.in_stride) * 2u : 0x80000000u;
-                        __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (st_lds_void *)(dst + c * 1024), 16, off, 0, 0, 0);
+                        __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (lds_void *)(dst + c * 1024), 16, off, 0, 0, 0);
                     }
                 }
             }
@@ -242,7 +212,7 @@ __global__ __launch_bounds__(64 * ST_NW) void conv_stem_c32_c64(const StemArgs a
                         for (int i = 0; i < 2; ++i) {
                             acc[u][i] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                            for (int kk = 0; kk < 3; ++kk) acc[u][i] = stem_mma<H16>(fw0[i][kk], fx[u][kk], acc[u][i]);
+                            for (int kk = 0; kk < 3; ++kk) acc[u][i] = mma16<H16>(fw0[i][kk], fx[u][kk], acc[u][i]);
                         }
 #pragma unroll
                     for (int u = 0; u < 3; ++u) {
@@ -252,7 +222,7 @@ __global__ __launch_bounds__(64 * ST_NW) void conv_stem_c32_c64(const StemArgs a
                         else zero = !(((unsigned)(gy0 + (lyx[j] & 0xff)) < (unsigned)a.H) & ((unsigned)(gx0 + (lyx[j] >> 8)) < (unsigned)a.W));
 #pragma unroll
                         for (int i = 0; i < 2; ++i) {
-                            uint2 pk = stem_epi<H16>(acc[u][i], b0v[i], slope0);
+                            uint2 pk = leaky_pack4<H16>(acc[u][i], b0v[i], slope0);
                             if (!INT || j == NG - 1) { pk.x = zero ? 0u : pk.x; pk.y = zero ? 0u : pk.y; }
                             *(lds_u2_p)(l0 + wr + j * 64 * ST_PITCH + i * 32) = pk;
                         }
@@ -272,12 +242,12 @@ __global__ __launch_bounds__(64 * ST_NW) void conv_stem_c32_c64(const StemArgs a
         };
         static_assert(ST_GROUPS % 12 == 0, "phase A: whole groups per producer wave, three at a time");
         if constexpr (U8) { fetch(pf, (lds_char *)raw0); advance(pf); }
-        __builtin_amdgcn_s_waitcnt(0x0070);
+        __builtin_amdgcn_s_waitcnt(waitcnt_imm(0, 0));
         __builtin_amdgcn_s_barrier();
         for (int i = -2; i <= nt; ++i) {                         // (one step past the last tile: the consumers drain it there)
             if (i & 1) produce(i, (lds_char *)(U8 ? raw0 : pix1), (const lds_char *)(uintptr_t)0, (lds_char *)(uintptr_t)0);
             else produce(i, (lds_char *)(U8 ? raw1 : pix0), (const lds_char *)(uintptr_t)ST_IN_BYTES, (lds_char *)(uintptr_t)ST_L0_BYTES);
-            __builtin_amdgcn_s_waitcnt(0x0070);                  // vmcnt(0) lgkmcnt(0): the fetched input has landed, the layer-0 tile is written
+            __builtin_amdgcn_s_waitcnt(waitcnt_imm(0, 0));       // the fetched input has landed, the layer-0 tile is written
             __builtin_amdgcn_s_barrier();
         }
     } else {
@@ -309,7 +279,7 @@ __global__ __launch_bounds__(64 * ST_NW) void conv_stem_c32_c64(const StemArgs a
                     float v0 = __fmul_rn((float)(x & 0xffu), a.in_scale), v1 = __fmul_rn((float)((x >> 8) & 0xffu), a.in_scale), v2 = __fmul_rn((float)((x >> 16) & 0xffu), a.in_scale);
                     if (a.in_mul != 1.0f || a.in_add != 0.0f) { v0 = __fadd_rn(__fmul_rn(v0, a.in_mul), a.in_add); v1 = __fadd_rn(__fmul_rn(v1, a.in_mul), a.in_add); v2 = __fadd_rn(__fmul_rn(v2, a.in_mul), a.in_add); }
                     const bool ok = (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
-                    *(uint4 *)(pix + p * 16) = ok ? uint4{stem_pk<H16>(v0, v1), stem_pk<H16>(v2, 0.f), 0u, 0u} : uint4{0u, 0u, 0u, 0u};
+                    *(uint4 *)(pix + p * 16) = ok ? uint4{pack16x2<H16>(v0, v1), pack16x2<H16>(v2, 0.f), 0u, 0u} : uint4{0u, 0u, 0u, 0u};
                 }
             }
         };
@@ -321,9 +291,8 @@ __global__ __launch_bounds__(64 * ST_NW) void conv_stem_c32_c64(const StemArgs a
         // then overwrites the staged rows.  One straight-line block: stores that must not happen (no previous tile, pixels past the
         // image) go to an out-of-range buffer offset instead of around a branch.  (Same box: 131.9 -> 129.2 us against the plain
         // sequence -- the step is bound by what the two waves of a SIMD can issue and by LDS traffic, ~340 KB per tile, not by stalls.)
-        __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc((void *)a.out, 0, 0x80000000u, 0x00020000);
-        __amdgpu_buffer_rsrc_t ro2 = __builtin_amdgcn_make_buffer_rsrc((void *)(a.w2 ? a.out2 : a.out), 0, 0x80000000u, 0x00020000);
-        typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+        __amdgpu_buffer_rsrc_t ro = buf_rsrc(a.out);
+        __amdgpu_buffer_rsrc_t ro2 = buf_rsrc(a.w2 ? a.out2 : a.out);
         char *const lrow = lo + (2 * sub) * ST_TW * ST_OPITCH;           // this wave's 32 staged pixels
         char *const lrow2 = lo2 + (2 * sub) * ST_TW * ST_O2PITCH;
         int pn = 0, poy0 = 0, pox0 = 0;                                  // image and origin (this wave's rows) of the previous tile
@@ -357,7 +326,7 @@ __global__ __launch_bounds__(64 * ST_NW) void conv_stem_c32_c64(const StemArgs a
                 float v0 = __fmul_rn((float)(x & 0xffu), a.in_scale), v1 = __fmul_rn((float)((x >> 8) & 0xffu), a.in_scale), v2 = __fmul_rn((float)((x >> 16) & 0xffu), a.in_scale);
                 if (a.in_mul != 1.0f || a.in_add != 0.0f) { v0 = __fadd_rn(__fmul_rn(v0, a.in_mul), a.in_add); v1 = __fadd_rn(__fmul_rn(v1, a.in_mul), a.in_add); v2 = __fadd_rn(__fmul_rn(v2, a.in_mul), a.in_add); }
                 const bool ok = (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
-                if (cv && p < ST_INPIX) *(uint4 *)(pix + p * 16) = ok ? uint4{stem_pk<H16>(v0, v1), stem_pk<H16>(v2, 0.f), 0u, 0u} : uint4{0u, 0u, 0u, 0u};
+                if (cv && p < ST_INPIX) *(uint4 *)(pix + p * 16) = ok ? uint4{pack16x2<H16>(v0, v1), pack16x2<H16>(v2, 0.f), 0u, 0u} : uint4{0u, 0u, 0u, 0u};
             };
             const char *xb = l0 + ((4 * sub) * ST_LW + 2 * l15) * ST_PITCH + lq * 16;
             u32x4_t sd[2];
@@ -370,7 +339,7 @@ __global__ __launch_bounds__(64 * ST_NW) void conv_stem_c32_c64(const StemArgs a
             };
             auto tail_mma = [&]() {
 #pragma unroll
-                for (int r = 0; r < 2; ++r) { acc2[r][0] = stem_mma<H16>(tw_[0], tx_[r], acc2[r][0]); acc2[r][1] = stem_mma<H16>(tw_[1], tx_[r], acc2[r][1]); }
+                for (int r = 0; r < 2; ++r) { acc2[r][0] = mma16<H16>(tw_[0], tx_[r], acc2[r][0]); acc2[r][1] = mma16<H16>(tw_[1], tx_[r], acc2[r][1]); }
             };
             // The wave's two tile rows one after the other (16 accumulator registers at a time, not 32): 18 steps of four MFMAs; the first
             // row's epilogue rides with the second row's taps.
@@ -378,7 +347,7 @@ __global__ __launch_bounds__(64 * ST_NW) void conv_stem_c32_c64(const StemArgs a
             auto epilogue = [&](int r, int c0) {
 #pragma unroll
                 for (int ct = c0; ct < c0 + 2; ++ct)
-                    *(uint2 *)(lr + (r * ST_TW + l15) * ST_OPITCH + (ct * 16 + lq * 4) * 2) = stem_epi<H16>(accr[r][ct], *(const f32x4 *)(lw2_ + ST_W2_BYTES + ST_B2_BYTES + (ct * 16 + lq * 4) * 4), slope1);
+                    *(uint2 *)(lr + (r * ST_TW + l15) * ST_OPITCH + (ct * 16 + lq * 4) * 2) = leaky_pack4<H16>(accr[r][ct], *(const f32x4 *)(lw2_ + ST_W2_BYTES + ST_B2_BYTES + (ct * 16 + lq * 4) * 4), slope1);
             };
             bf16x8 xn = *(const bf16x8 *)xb;                             // fragment of the next step
 #pragma unroll
@@ -404,7 +373,7 @@ __global__ __launch_bounds__(64 * ST_NW) void conv_stem_c32_c64(const StemArgs a
                     for (int q = 0; q < 2; ++q)
 #pragma unroll
                         for (int k = 0; k < 2; ++k)
-                            *(uint2 *)(lr2 + (q * ST_TW + l15) * ST_O2PITCH + (k * 16 + lq * 4) * 2) = stem_epi<H16>(acc2[q][k], *(const f32x4 *)(lw2_ + ST_W2_BYTES + (k * 16 + lq * 4) * 4), slope2);
+                            *(uint2 *)(lr2 + (q * ST_TW + l15) * ST_O2PITCH + (k * 16 + lq * 4) * 2) = leaky_pack4<H16>(acc2[q][k], *(const f32x4 *)(lw2_ + ST_W2_BYTES + (k * 16 + lq * 4) * 4), slope2);
                 }
                 if (h == 8) { sd[0] = *(const u32x4_t *)(lr2 + (lane >> 2) * ST_O2PITCH + (lane & 3) * 16); sd[1] = *(const u32x4_t *)(lr2 + ((lane + 64) >> 2) * ST_O2PITCH + (lane & 3) * 16); }
                 if (h == 9) { __builtin_amdgcn_raw_buffer_store_b128(sd[0], ro2, piece2_off(0), 0, OUT_STORE_AUX); __builtin_amdgcn_raw_buffer_store_b128(sd[1], ro2, piece2_off(1), 0, OUT_STORE_AUX); }
@@ -417,20 +386,20 @@ __global__ __launch_bounds__(64 * ST_NW) void conv_stem_c32_c64(const StemArgs a
                 const bf16x8 x = xn;
                 if (h + 1 < 18) { const int r1 = (h + 1) / 9, t1 = h + 1 - r1 * 9, kh1 = t1 / 3, kw1 = t1 - kh1 * 3; xn = *(const bf16x8 *)(xb + ((kh1 + 2 * r1) * ST_LW + kw1) * ST_PITCH); }
 #pragma unroll
-                for (int ct = 0; ct < 4; ++ct) accr[r][ct] = stem_mma<H16>(fw1[ct][t], x, t == 0 ? f32x4{0.f, 0.f, 0.f, 0.f} : accr[r][ct]);
+                for (int ct = 0; ct < 4; ++ct) accr[r][ct] = mma16<H16>(fw1[ct][t], x, t == 0 ? f32x4{0.f, 0.f, 0.f, 0.f} : accr[r][ct]);
                 __builtin_amdgcn_sched_barrier(0);
             }
             // ---- epilogue of the second row: with the first row's, it replaces the previous tile's staged rows ----
             epilogue(1, 0); epilogue(1, 2);
             pn = n; poy0 = ty * ST_TH + 2 * sub; pox0 = tx * ST_TW;
         };
-        __builtin_amdgcn_s_waitcnt(0x0070);
+        __builtin_amdgcn_s_waitcnt(waitcnt_imm(0, 0));
         __builtin_amdgcn_s_barrier();
         for (int i = -2; i <= nt; ++i) {
             if (i >= 0) { if (i & 1) consume_p(i, l01, raw1, pix1, lrow, lrow2, lw2); else consume_p(i, l00, raw0, pix0, lrow, lrow2, lw2); advance(pi); }
             else if constexpr (U8) { if (i + 2 < nt) { if (i & 1) convert_raw(pc, raw1, pix1); else convert_raw(pc, raw0, pix0); } }
             advance(pc);
-            __builtin_amdgcn_s_waitcnt(0xc07f);                  // lgkmcnt(0): the records are written, the layer-0 tile is read
+            __builtin_amdgcn_s_waitcnt(waitcnt_imm(63, 0));      // the records are written, the layer-0 tile is read
             __builtin_amdgcn_s_barrier();
         }
     }
@@ -461,7 +430,7 @@ __global__ __launch_bounds__(64 * ST_NW) void conv_halo_c32_c64(const HaloArgs a
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    if constexpr (H16) __builtin_amdgcn_s_setreg((0 << 11) | (23 << 6) | 1, 1);      // hwreg(HW_REG_MODE, 23, 1) = FP16_OVFL: fp16 conversions saturate
+    if constexpr (H16) fp16_saturating_mode();      // fp16 conversions saturate
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l15 = lane & 15, lq = lane >> 4;
     bf16x8 fw[4][9];
@@ -477,8 +446,8 @@ __global__ __launch_bounds__(64 * ST_NW) void conv_halo_c32_c64(const HaloArgs a
 
     const int tiles_x = (a.W + ST_TW - 1) / ST_TW, tiles_y = (a.H + ST_TH - 1) / ST_TH;
     const int per_img = tiles_x * tiles_y, ntiles = a.N * per_img;
-    __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc((void *)a.in, 0, 0x80000000u, 0x00020000);
-    __amdgpu_buffer_rsrc_t rres = __builtin_amdgcn_make_buffer_rsrc((void *)(a.res ? a.res : a.in), 0, 0x80000000u, 0x00020000);
+    __amdgpu_buffer_rsrc_t rin = buf_rsrc(a.in);
+    __amdgpu_buffer_rsrc_t rres = buf_rsrc(a.res ? a.res : a.in);
 
     auto fetch_in = [&](int tile, char *dst) {
         const int n = tile / per_img, tr = tile - n * per_img;
@@ -496,7 +465,7 @@ __global__ __launch_bounds__(64 * ST_NW) void conv_halo_c32_c64(const HaloArgs a
                 const int sc = pc ^ (2 * ((px >> 2) & 1));       // source chunk that belongs in this physical slot
                 const bool ok = px < HL_INPIX && tile < ntiles && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
                 const unsigned off = ok ? (unsigned)(((n * a.H + iy) * a.W + ix) * a.in_stride + sc * 8) * 2u : 0x80000000u;
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rin, (st_lds_void *)(dst + c * 1024), 16, off, 0, 0, 0);
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rin, (lds_void *)(dst + c * 1024), 16, off, 0, 0, 0);
             }
         }
     };
@@ -510,7 +479,7 @@ __global__ __launch_bounds__(64 * ST_NW) void conv_halo_c32_c64(const HaloArgs a
             const int oy = ty * ST_TH + (px >> 4), ox = tx * ST_TW + (px & 15);
             const bool ok = tile < ntiles && oy < a.H && ox < a.W;
             const unsigned off = ok ? (unsigned)(((n * a.H + oy) * a.W + ox) * a.res_stride + pc * 8) * 2u : 0x80000000u;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rres, (st_lds_void *)(dst + (wave + ST_NW * k) * 1024), 16, off, 0, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rres, (lds_void *)(dst + (wave + ST_NW * k) * 1024), 16, off, 0, 0, 0);
         }
     };
 
@@ -533,18 +502,18 @@ __global__ __launch_bounds__(64 * ST_NW) void conv_halo_c32_c64(const HaloArgs a
             const int p = (wave + kh) * HL_IW + l15 + kw;        // input-tile pixel of this lane for this tap
             const bf16x8 x = *(const bf16x8 *)(in_cur + p * 64 + ((lq ^ (2 * ((p >> 2) & 1))) << 4));
 #pragma unroll
-            for (int ct = 0; ct < 4; ++ct) acc[ct] = stem_mma<H16>(fw[ct][t], x, acc[ct]);
+            for (int ct = 0; ct < 4; ++ct) acc[ct] = mma16<H16>(fw[ct][t], x, acc[ct]);
         }
 #pragma unroll
         for (int ct = 0; ct < 4; ++ct) {
-            *(uint2 *)(lo + (wave * ST_TW + l15) * ST_OPITCH + (ct * 16 + lq * 4) * 2) = stem_epi<H16>(acc[ct], bv[ct], slope);
+            *(uint2 *)(lo + (wave * ST_TW + l15) * ST_OPITCH + (ct * 16 + lq * 4) * 2) = leaky_pack4<H16>(acc[ct], bv[ct], slope);
         }
         // staged tile complete, every wave done with this tile's input; the next tile's input and this tile's shortcut (requested one
         // and two tiles ago) must have landed.  Younger than the next tile's input pieces in this wave's queue: the next tile's shortcut
         // pieces, the previous tile's two stores, the pieces requested at the top of this tile -- they may stay in flight (the first
         // tile has no stores behind it; the start-up wait below has landed its tiles anyway)
-        if (has_res) { if (wave < 4) __builtin_amdgcn_s_waitcnt(0x0078); else __builtin_amdgcn_s_waitcnt(0x0077); }
-        else { if (wave < 4) __builtin_amdgcn_s_waitcnt(0x0074); else __builtin_amdgcn_s_waitcnt(0x0073); }
+        if (has_res) { if (wave < 4) __builtin_amdgcn_s_waitcnt(waitcnt_imm(8, 0)); else __builtin_amdgcn_s_waitcnt(waitcnt_imm(7, 0)); }
+        else { if (wave < 4) __builtin_amdgcn_s_waitcnt(waitcnt_imm(4, 0)); else __builtin_amdgcn_s_waitcnt(waitcnt_imm(3, 0)); }
         __builtin_amdgcn_s_barrier();
 #pragma unroll
         for (int it = 0; it < ST_TH * ST_TW * 8 / (64 * ST_NW); ++it) {
@@ -557,9 +526,9 @@ __global__ __launch_bounds__(64 * ST_NW) void conv_halo_c32_c64(const HaloArgs a
                 uint32_t ov[4] = {o.x, o.y, o.z, o.w}, rv[4] = {r.x, r.y, r.z, r.w};
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
-                    const float lo_ = stem_lo<H16>(ov[q]) + stem_lo<H16>(rv[q]);
-                    const float hi_ = stem_hi<H16>(ov[q]) + stem_hi<H16>(rv[q]);
-                    ov[q] = stem_pk<H16>(lo_, hi_);
+                    const float lo_ = unpack16_lo<H16>(ov[q]) + unpack16_lo<H16>(rv[q]);
+                    const float hi_ = unpack16_hi<H16>(ov[q]) + unpack16_hi<H16>(rv[q]);
+                    ov[q] = pack16x2<H16>(lo_, hi_);
                 }
                 o = uint4{ov[0], ov[1], ov[2], ov[3]};
             }
@@ -570,7 +539,7 @@ __global__ __launch_bounds__(64 * ST_NW) void conv_halo_c32_c64(const HaloArgs a
         }
         // the next tile writes `lo` only after its own pre-store barrier, and re-fills this tile's input / shortcut slots at its top:
         // every thread must be past the reads above first
-        __builtin_amdgcn_s_waitcnt(0xc07f);
+        __builtin_amdgcn_s_waitcnt(waitcnt_imm(63, 0));
         __builtin_amdgcn_s_barrier();
     };
 
@@ -579,7 +548,7 @@ __global__ __launch_bounds__(64 * ST_NW) void conv_halo_c32_c64(const HaloArgs a
     const int G = gridDim.x;
     fetch_in(tile, inb); if (has_res) fetch_res(tile, resb);
     fetch_in(tile + G, inb + HL_IN_BYTES); if (has_res) fetch_res(tile + G, resb + HL_RES_BYTES);
-    __builtin_amdgcn_s_waitcnt(0x0070);
+    __builtin_amdgcn_s_waitcnt(waitcnt_imm(0, 0));
     __builtin_amdgcn_s_barrier();
     for (int slot = 0; tile < ntiles; tile += G, slot = slot == 2 ? 0 : slot + 1) {
         const int fill = slot == 0 ? 2 : slot - 1;               // (slot + 2) % 3

@@ -199,10 +199,6 @@ struct BlockArgs {
 };
 bool conv_resblock_ok(const BlockArgs &a);
 hipError_t launch_conv_resblock(const BlockArgs &a, hipStream_t s);
-// the same block at C = 64, Cmid = 32 (darknet-53's first residual block, 208 x 208 at 416 x 416): conv_block64.hip, two workgroups per CU,
-// shortcut from the x tile in LDS
-bool conv_resblock64_ok(const BlockArgs &a);
-hipError_t launch_conv_resblock64(const BlockArgs &a, hipStream_t s);
 // exact-fp32 MFMA conv (config 2); same argument meaning, in/wt/res are float
 hipError_t launch_conv_f32(const ConvArgs &a, hipStream_t s);
 

@@ -228,25 +228,18 @@ int build_plan(yolo_ctx *c, const std::vector<Section> &secs)
     //  kernels: what counts is the type of the tensors a kernel touches, not the context's)
     const bool ctx16 = c->half_like() || c->dtype == YOLO_FP8 || c->split();        // (a split-fp16 network: where the tensors a fused kernel touches are PLAIN fp16 -- mixed plans)
     auto is16 = [](int dt) { return dt == DT_BF16 || dt == DT_F16; };
-    // fused residual block (conv_block.hip, conv_block64.hip): a 1x1 conv C -> C/2 read only by the 3x3 conv C/2 -> C that follows, whose folded
-    // shortcut source is the 1x1's own input, on a grid that is (nearly) whole 13 x 13 blocks: C = 128, darknet-53's 104 x 104 stage at
-    // 416 x 416, and (round 5) C = 64, its first residual block at 208 x 208 -- found BEFORE the stem's 1x1 tail and the halo-staged 32 -> 64
-    // form, which would otherwise take those two layers
+    // fused residual block (conv_block.hip): a 1x1 conv 128 -> 64 read only by the 3x3 conv 64 -> 128 that follows, whose folded shortcut
+    // source is the 1x1's own input, on a grid that is (nearly) whole 13 x 13 blocks: darknet-53's 104 x 104 stage at 416 x 416
     if (ctx16 && !c->keep_layers && !getenv("YOLO_NO_RESBLOCK"))
         for (int i = 1; i + 1 < NL; ++i) {
             Layer &A = c->layers[i], &B = c->layers[i + 1];
-            const bool c128 = A.cin == 128 && A.filters == 64 && B.cin == 64 && B.filters == 128;
-            // (C = 64: built and bit-identical, but SLOWER than what it replaces -- 130 us against 107 for the halo-staged 32 -> 64 conv, the stem no
-            //  faster without its 1x1 tail: the block is instruction-issue-bound, ~800 instructions per wave and block for 62 MFMAs, docs/NOTEBOOK.md
-            //  round 5 -- so it is opt-in: YOLO_RESBLOCK64=1)
-            const bool c64 = A.cin == 64 && A.filters == 32 && B.cin == 32 && B.filters == 64 && getenv("YOLO_RESBLOCK64") && !getenv("YOLO_NO_RESBLOCK64");
             if (A.type == L_CONV && B.type == L_CONV && !A.fc && !B.fc && !A.head && !B.head && uses[i] == 1 && B.in[0] == i && A.in[0] >= 0 &&
-                A.size == 1 && A.stride == 1 && A.pad == 0 && (c128 || c64) && A.residual_from < -1 &&
+                A.size == 1 && A.stride == 1 && A.pad == 0 && A.cin == 128 && A.filters == 64 && B.cin == 64 && B.filters == 128 && A.residual_from < -1 &&
                 B.size == 3 && B.stride == 1 && B.pad == 1 && B.residual_from == A.in[0] &&
                 ((long)((B.H + 12) / 13) * ((B.W + 12) / 13) * 169 * 100 <= (long)B.H * B.W * 115) && A.in_dt == B.in_dt && (A.in_dt == DT_BF16 || A.in_dt == DT_F16) && A.store_dt == A.in_dt && B.store_dt == A.in_dt &&
                 c->layers[A.in[0]].store_dt == A.in_dt && !A.pair && !B.pair && !c->pair_of(A.in[0])) { A.blk_skip = true; B.blk = true; }
         }
-    if (ctx16 && !c->keep_layers && NL >= 2 && !getenv("YOLO_NO_STEM") && (double)c->max_batch * c->in_h * c->in_w * 8 * 2 < 2147483648.0) {
+    if (ctx16 && !c->keep_layers && NL >= 2 && (double)c->max_batch * c->in_h * c->in_w * 8 * 2 < 2147483648.0) {
         const Layer &A = c->layers[0], &B = c->layers[1];
         if (A.type == L_CONV && B.type == L_CONV && uses[0] == 1 && B.in[0] == 0 && A.size == 3 && A.stride == 1 && A.pad == 1 && A.cin == 3 &&
             A.filters == 32 && B.size == 3 && B.stride == 2 && B.pad == 1 && B.filters == 64 && !A.head && !B.head && B.residual_from < -1 &&
@@ -255,7 +248,7 @@ int build_plan(yolo_ctx *c, const std::vector<Section> &secs)
             if (NL >= 3) {
                 const Layer &T = c->layers[2];
                 if (T.type == L_CONV && !T.fc && T.in[0] == 1 && T.size == 1 && T.stride == 1 && T.pad == 0 && T.filters == 32 && !T.head && T.residual_from < -1 &&
-                    T.in_dt == A.in_dt && T.store_dt == A.in_dt && !T.blk_skip && !T.pair)        // (blk_skip: the fused first residual block computes it)
+                    T.in_dt == A.in_dt && T.store_dt == A.in_dt && !T.pair)
                     c->layers[2].stem_tail = true;
             }
         }
@@ -282,7 +275,7 @@ int build_plan(yolo_ctx *c, const std::vector<Section> &secs)
         }
     // 1x1 convs that can ride in their producer's epilogue: conv i (bf16, 128 or 256 output channels, optionally with its
     // fused shortcut) read by a 1x1/s1 conv with half as many filters
-    if (ctx16 && !c->keep_layers && !getenv("YOLO_NO_TAIL")) {
+    if (ctx16 && !c->keep_layers) {
         for (int i = 0; i + 1 < NL; ++i) {
             Layer &P = c->layers[i];
             if (P.type != L_CONV || P.fc || P.head || P.stem || P.stem_skip || P.stem_tail || P.blk || P.s2 || P.halo || (P.filters != 128 && P.filters != 256)) continue;      // (fixed kernels host no tail: run_layer would skip the 1x1)
@@ -297,7 +290,7 @@ int build_plan(yolo_ctx *c, const std::vector<Section> &secs)
             // round 5: a detection head (1x1, <= 256 filters, fp32 out, linear) as the tail of the 256-channel 3x3 in front of it when nobody else
             // reads that conv (darknet-53's 52 x 52 head): the head tensor is formed from the tile in LDS, bit-identical to the stand-alone launch
             else if (T.type == L_CONV && !T.fc && T.head && T.in[0] == o && uses[o] == 1 && T.size == 1 && T.stride == 1 && T.pad == 0 && P.filters == 256 && T.filters <= 256 &&
-                     P.size == 3 && P.residual_from < -1 && T.act == ACT_LINEAR && T.in_dt == P.in_dt && (T.in_dt == DT_BF16 || T.in_dt == DT_F16) && !getenv("YOLO_NO_HEAD_TAIL") && j + 1 < NL && c->layers[j + 1].type == L_YOLO) { P.tail_layer = j; T.fused_into = i; }
+                     P.size == 3 && P.residual_from < -1 && T.act == ACT_LINEAR && T.in_dt == P.in_dt && (T.in_dt == DT_BF16 || T.in_dt == DT_F16) && j + 1 < NL && c->layers[j + 1].type == L_YOLO) { P.tail_layer = j; T.fused_into = i; }
         }
     }
     // storage assignment: st_of[i] = storage holding layer i's output
