@@ -109,6 +109,27 @@ typedef struct yolo_box {
     int32_t cls;
 } yolo_box;
 
+/* One image of a ragged batch (yolo_*_images_*): a uint8 RGB [h][w][3] image at byte `offset` of one packed buffer (16 bytes). */
+typedef struct yolo_image_desc {
+    uint64_t offset;
+    int32_t h, w;
+} yolo_image_desc;
+/* How a native-size image is fitted into the S x S network input (each bit-identical, per pixel, to the single-image path named). */
+enum yolo_fit {
+    YOLO_FIT_STRETCH = 0,      /* /255, then TF legacy bilinear stretch (yolo_forward_image_u8; D2T/YOLO_V3_convert...py:106-111) */
+    YOLO_FIT_LETTERBOX = 1,    /* darknet letterbox_image: darknet's (float)p/255., aspect-preserving resize_image, 0.5 fill, centred
+                                * (yolo_forward_letterbox_chw on the same image converted on the host, DN/image.c:960-981) */
+    YOLO_FIT_CV2 = 2,          /* V2 preprocess_image: cv2.resize INTER_LINEAR, then /225 (yolo_op_resize_cv2, V2/utils.py:13-27), RGB in */
+    YOLO_FIT_CV2_BGR = 3       /* the same on a BGR image: the RGB swap of cv2.cvtColor(.., COLOR_BGR2RGB) first */
+};
+/* Units of the records yolo_detect_images_* returns.
+ * NETWORK: as yolo_postprocess returns them for an image at network size (STRETCH / CV2: normalised or network pixels by the decode;
+ * LETTERBOX: un-letterboxed boxes normalised to the source image, darknet's relative = 1).
+ * SOURCE_PIXELS: in the source image's pixels -- STRETCH / CV2: the kept records scaled after NMS (`convert_to_original_size`,
+ * V3/YOLO_V3_inference.py:55-57, V3/convert_ckpt_and_inference.py:43-45); LETTERBOX: relative = 0; YOLO_NMS_PER_CLASS: the image's
+ * (h, w) is V2's `image_shape` (V2/utils.py:30-43). */
+enum yolo_box_units { YOLO_UNITS_NETWORK = 0, YOLO_UNITS_SOURCE_PIXELS = 1 };
+
 /* ---- lifecycle ------------------------------------------------------------------------------ */
 /* Parses the topology, plans buffers on `device`.  On failure returns NULL and writes a message to
  * err (if non-NULL).  Replaces load_network's cfg half (DN/parser.c:730-875). */
@@ -168,12 +189,40 @@ int yolo_forward_image_u8(yolo_ctx *ctx, const uint8_t *image, int h, int w, int
 int yolo_forward_letterbox_chw(yolo_ctx *ctx, const float *image_chw, int w, int h, int loc,
                                float *detections_out, int out_loc);
 
+/* A ragged batch of native-size uint8 RGB images in ONE device step: `pixels` holds n images packed in one buffer of `bytes` bytes (at
+ * `loc`; YOLO_HOST: staged with one host-to-device copy), descs[n] (host memory) where each one lies.  One launch fits every image
+ * into the network input (`fit`, enum yolo_fit), then as yolo_forward with n images.  YOLO_ERR_INVALID before any launch when n is
+ * outside 1..max_batch, a descriptor has h < 1 or w < 1 or ends past `bytes`, `bytes` >= 2^32, or a letterboxed image would be less
+ * than one pixel wide or high. */
+int yolo_forward_images_u8(yolo_ctx *ctx, const uint8_t *pixels, size_t bytes, const yolo_image_desc *descs, int n, int fit, int loc,
+                           float *detections_out, int out_loc);
+/* The same + threshold + NMS with each image's geometry (enum yolo_box_units): boxes_out [n * max_out], counts_out [n] at out_loc.
+ * LETTERBOX un-letterboxes every box for its image before NMS, darknet's order (networks with a [detection] head:
+ * YOLO_ERR_UNSUPPORTED, darknet v1 does not letterbox). */
+int yolo_detect_images_u8(yolo_ctx *ctx, const uint8_t *pixels, size_t bytes, const yolo_image_desc *descs, int n, int fit, int loc,
+                          float score_thr, float iou_thr, int max_out, int nms_mode, int select_mode, int units,
+                          yolo_box *boxes_out, int32_t *counts_out, int out_loc);
+/* yolo_detect_images_u8 replayed from a HIP graph, as yolo_detect_graph: `pixels`, boxes_out and counts_out are device pointers, descs
+ * host memory.  The graph is keyed on the buffer pointer, `bytes`, n and the modes -- NOT on the image sizes or offsets: every call
+ * validates the descriptors on the host and copies them into the context's device table on the context stream before the launch, so
+ * one captured graph serves batches whose image sizes change from call to call. */
+int yolo_detect_images_graph(yolo_ctx *ctx, const uint8_t *pixels, size_t bytes, const yolo_image_desc *descs, int n, int fit,
+                             float score_thr, float iou_thr, int max_out, int nms_mode, int select_mode, int units,
+                             yolo_box *boxes_out, int32_t *counts_out);
+/* The value one source byte `value` (0..255) contributes to a fit's arithmetic before interpolation: STRETCH value / 255.0f, LETTERBOX
+ * darknet's (float)value/255. (a double division rounded to float, DN/image.c load_image_stb), CV2 the byte itself.  Host-side; the
+ * device evaluates the same expression. */
+float yolo_fit_unit_value(int fit, int value);
+
 /* darknet's get_network_boxes on the device (DN/network.c:536-567 = num_detections + fill_network_boxes ->
  * get_yolo_detections DN/yolo_layer.c:316-343 / get_region_detections DN/region_layer.c:364-437 (softmax heads, no tree),
  * then correct_yolo_boxes DN/yolo_layer.c:247-273) over image 0 of the last forward: boxes above `thresh`, compacted in
  * darknet's order, un-letterboxed for a w x h source image.  records: host [cap][5 + classes] = x, y, w, h, objectness,
  * prob[classes]; *count = number of detections (may exceed cap; cap = 0 / records = NULL: count only = num_detections). */
 int yolo_darknet_boxes(yolo_ctx *ctx, int w, int h, float thresh, int relative, float *records, int cap, int *count);
+/* The same over image `image` of the last forward (0 <= image < its batch): e.g. the letterboxed batch of yolo_forward_images_u8,
+ * each image with its own w x h.  yolo_darknet_boxes is yolo_darknet_boxes_at(ctx, 0, ...). */
+int yolo_darknet_boxes_at(yolo_ctx *ctx, int image, int w, int h, float thresh, int relative, float *records, int cap, int *count);
 /* What darknet's network_predict returns (DN/network.c:497-508, net->output): the LAST layer's output of image 0 in darknet's
  * own layout -- for a [yolo] / [region] layer the planar [anchors * (5 + classes)][grid * grid] tensor with that layer's
  * activations applied (DN/yolo_layer.c:143-152, DN/region_layer.c:160-186).  host buffer of yolo_last_layer_size() floats. */

@@ -137,42 +137,58 @@ hipError_t launch_preprocess(const void *img, int fmt, int n, int hw, float scal
     return hipGetLastError();
 }
 
+// ---- per-pixel arithmetic of the three image fits, shared by the single-image kernels and the batched k_fit_images.  `at(y, x, c)`
+//      returns what the fit reads at a source pixel: the byte as a float for the stretch and cv2 forms, the 0..1 value for the letterbox
+//      (a planar float image, or a byte through fit_unit_value).  Restated operation for operation from the reference; this file is
+//      compiled with -ffp-contract=off, so every caller rounds the same. ----
+
 // legacy TF bilinear (no half-pixel offset): src = dst * (in/out); value/255 first (D2T _input_process)
-template <typename T>
-__global__ void k_resize_u8(const uint8_t *img, int h, int w, int so, T *out, int out_stride, int out_c, float post_scale, float post_add)
+template <class At>
+__device__ __forceinline__ void px_stretch(const At &at, int h, int w, int so, int oy, int ox, float post_scale, float post_add, float *v)
 {
-    int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= so * so) return;
-    int oy = p / so, ox = p - oy * so;
     const float hs = (float)h / (float)so, ws = (float)w / (float)so;
     float fy = (float)oy * hs, fx = (float)ox * ws;
     int y0 = (int)floorf(fy), x0 = (int)floorf(fx);
     int y1 = min(y0 + 1, h - 1), x1 = min(x0 + 1, w - 1);
     float yl = fy - (float)y0, xl = fx - (float)x0;
-    float v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-        float tl = (float)img[((size_t)y0 * w + x0) * 3 + c] / 255.0f;
-        float tr = (float)img[((size_t)y0 * w + x1) * 3 + c] / 255.0f;
-        float bl = (float)img[((size_t)y1 * w + x0) * 3 + c] / 255.0f;
-        float br = (float)img[((size_t)y1 * w + x1) * 3 + c] / 255.0f;
+        float tl = at(y0, x0, c) / 255.0f;
+        float tr = at(y0, x1, c) / 255.0f;
+        float bl = at(y1, x0, c) / 255.0f;
+        float br = at(y1, x1, c) / 255.0f;
         float top = tl + (tr - tl) * xl;
         float bot = bl + (br - bl) * xl;
         v[c] = top + (bot - top) * yl;
         if (post_scale != 1.0f) v[c] *= post_scale;
         if (post_add != 0.0f) v[c] += post_add;
     }
-    if (out_c >= 8) Elt<T>::store8(out + (size_t)p * out_stride, v);
-    else
-        for (int c = 0; c < out_c; ++c) Elt<T>::store1(out + (size_t)p * out_stride + c, v[c]);
 }
 
-hipError_t launch_resize_u8(const uint8_t *img, int h, int w, int s_out, void *out, int out_dt, int out_stride,
-                            int out_c, hipStream_t s, float post_scale, float post_add)
+// darknet letterbox_image (DN/image.c:960-981) of one output pixel: aspect-preserving resize_image (DN/image.c:1347-1393: horizontal
+// pass then vertical pass, scales (in-1)/(out-1), last column / row copied) embedded at the centre of a 0.5-filled canvas.  Operation
+// order of the two passes is kept: part = (1-dx)*a + dx*b, then (1-dy)*p0 (+ dy*p1).
+template <class At>
+__device__ __forceinline__ void px_letterbox(const At &at, int iw, int ih, int new_w, int new_h, int off_x, int off_y, int oy, int ox, float *v)
 {
-    size_t np = (size_t)s_out * s_out;
-    WITH_DT(out_dt, hipLaunchKernelGGL(k_resize_u8<T>, grid_for(np), dim3(256), 0, s, img, h, w, s_out, (T *)out, out_stride, out_c, post_scale, post_add));
-    return hipGetLastError();
+    const int r = oy - off_y, c = ox - off_x;
+    v[0] = v[1] = v[2] = 0.5f;
+    if ((unsigned)r < (unsigned)new_h && (unsigned)c < (unsigned)new_w) {
+        const float w_scale = (float)(iw - 1) / (float)(new_w - 1), h_scale = (float)(ih - 1) / (float)(new_h - 1);
+        const float sy = (float)r * h_scale; const int iy = (int)sy; const float dy = sy - (float)iy;
+        const bool last_c = c == new_w - 1 || iw == 1, last_r = r == new_h - 1 || ih == 1;
+        const float sx = (float)c * w_scale; const int ix = (int)sx; const float dx = sx - (float)ix;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            auto part = [&](int row) {
+                if (last_c) return at(row, iw - 1, k);
+                return (1 - dx) * at(row, ix, k) + dx * at(row, ix + 1, k);
+            };
+            float val = (1 - dy) * part(iy);
+            if (!last_r) val = val + dy * part(iy + 1);
+            v[k] = val;
+        }
+    }
 }
 
 // `cv2.resize(image_float32, (ow, oh))` as V2/utils.py:13-27 calls it (INTER_LINEAR on a float32 image, after BGR -> RGB) followed by the
@@ -180,13 +196,11 @@ hipError_t launch_resize_u8(const uint8_t *img, int h, int w, int s_out, void *o
 //   fx = (float)((dx + 0.5) * (double)(src_w / dst_w as 1 / (dst_w / src_w)) - 0.5); sx = floor(fx); fx -= sx;
 //   sx < 0 -> (sx, fx) = (0, 0);  sx >= src_w - 1 -> (sx, fx) = (src_w - 1, 0);     likewise in y,
 // a horizontal pass S[sx] * (1 - fx) + S[sx + 1] * fx on both rows, then the vertical one R0 * (1 - fy) + R1 * fy (separately rounded
-// float operations: this file is compiled with -ffp-contract=off).  cv2 is absent here: parity unpinned, oracle.resize_cv2_linear is the
-// same closed form.  swap_rb: output channel c reads input channel 2 - c (cv2.cvtColor(..., COLOR_BGR2RGB)).
-__global__ void k_resize_cv2_u8(const uint8_t *img, int h, int w, int oh, int ow, int swap_rb, float divisor, float *out)
+// float operations).  cv2 is absent here: parity unpinned, oracle.resize_cv2_linear is the same closed form.  swap_rb: output channel c
+// reads input channel 2 - c (cv2.cvtColor(..., COLOR_BGR2RGB)).
+template <class At>
+__device__ __forceinline__ void px_cv2(const At &at, int h, int w, int oh, int ow, int dy, int dx, int swap_rb, float divisor, float *v)
 {
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= oh * ow) return;
-    const int dy = p / ow, dx = p - dy * ow;
     const double scale_x = 1.0 / ((double)ow / (double)w), scale_y = 1.0 / ((double)oh / (double)h);
     float fx = (float)(((double)dx + 0.5) * scale_x - 0.5), fy = (float)(((double)dy + 0.5) * scale_y - 0.5);
     int sx = (int)floorf(fx), sy = (int)floorf(fy);
@@ -200,11 +214,54 @@ __global__ void k_resize_cv2_u8(const uint8_t *img, int h, int w, int oh, int ow
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         const int ci = swap_rb ? 2 - c : c;
-        const float p00 = (float)img[((size_t)sy * w + sx) * 3 + ci], p01 = (float)img[((size_t)sy * w + sx1) * 3 + ci];
-        const float p10 = (float)img[((size_t)sy1 * w + sx) * 3 + ci], p11 = (float)img[((size_t)sy1 * w + sx1) * 3 + ci];
+        const float p00 = at(sy, sx, ci), p01 = at(sy, sx1, ci);
+        const float p10 = at(sy1, sx, ci), p11 = at(sy1, sx1, ci);
         const float r0 = p00 * a0 + p01 * a1, r1 = p10 * a0 + p11 * a1;
-        out[(size_t)p * 3 + c] = (r0 * b0 + r1 * b1) / divisor;
+        v[c] = (r0 * b0 + r1 * b1) / divisor;
     }
+}
+
+// source readers of the single-image kernels: a uint8 HWC image, a planar float [3][h][w] image
+struct AtU8 {
+    const uint8_t *img; int w;
+    __device__ __forceinline__ float operator()(int y, int x, int c) const { return (float)img[((size_t)y * w + x) * 3 + c]; }
+};
+struct AtPlanar {
+    const float *img; int w, h;
+    __device__ __forceinline__ float operator()(int y, int x, int k) const { return img[(size_t)k * w * h + (size_t)y * w + x]; }
+};
+
+template <typename T>
+__global__ void k_resize_u8(const uint8_t *img, int h, int w, int so, T *out, int out_stride, int out_c, float post_scale, float post_add)
+{
+    int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= so * so) return;
+    int oy = p / so, ox = p - oy * so;
+    float v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    px_stretch(AtU8{img, w}, h, w, so, oy, ox, post_scale, post_add, v);
+    if (out_c >= 8) Elt<T>::store8(out + (size_t)p * out_stride, v);
+    else
+        for (int c = 0; c < out_c; ++c) Elt<T>::store1(out + (size_t)p * out_stride + c, v[c]);
+}
+
+hipError_t launch_resize_u8(const uint8_t *img, int h, int w, int s_out, void *out, int out_dt, int out_stride,
+                            int out_c, hipStream_t s, float post_scale, float post_add)
+{
+    size_t np = (size_t)s_out * s_out;
+    WITH_DT(out_dt, hipLaunchKernelGGL(k_resize_u8<T>, grid_for(np), dim3(256), 0, s, img, h, w, s_out, (T *)out, out_stride, out_c, post_scale, post_add));
+    return hipGetLastError();
+}
+
+// cv2.resize of one uint8 image to fp32 [oh][ow][3] (px_cv2 above)
+__global__ void k_resize_cv2_u8(const uint8_t *img, int h, int w, int oh, int ow, int swap_rb, float divisor, float *out)
+{
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= oh * ow) return;
+    const int dy = p / ow, dx = p - dy * ow;
+    float v[3];
+    px_cv2(AtU8{img, w}, h, w, oh, ow, dy, dx, swap_rb, divisor, v);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) out[(size_t)p * 3 + c] = v[c];
 }
 hipError_t launch_resize_cv2_u8(const uint8_t *img, int h, int w, int oh, int ow, int swap_rb, float divisor, float *out, hipStream_t s)
 {
@@ -528,43 +585,82 @@ hipError_t launch_add_split(const void *a, int a_stride, const void *b, int b_st
     return hipGetLastError();
 }
 
-// ---- darknet letterbox_image (DN/image.c:960-981) fused with the layout change: a planar float image of any size ->
-//      aspect-preserving resize_image (DN/image.c:1347-1393: horizontal pass then vertical pass, scales (in-1)/(out-1),
-//      last column / row copied) embedded at the centre of a 0.5-filled S x S canvas, written as the 8-channel
-//      network input.  Operation order of the two passes is kept: part = (1-dx)*a + dx*b, then (1-dy)*p0 (+ dy*p1). ----
+// ---- darknet letterbox_image (DN/image.c:960-981) fused with the layout change: a planar float image of any size -> px_letterbox,
+//      written as the 8-channel network input ----
 template <typename T>
 __global__ void k_letterbox_chw(const float *img, int iw, int ih, int S, int new_w, int new_h, int off_x, int off_y, T *out, int out_stride)
 {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= S * S) return;
     const int oy = p / S, ox = p - oy * S;
-    const int r = oy - off_y, c = ox - off_x;
     float v[8] = {0.5f, 0.5f, 0.5f, 0, 0, 0, 0, 0};
-    if ((unsigned)r < (unsigned)new_h && (unsigned)c < (unsigned)new_w) {
-        const float w_scale = (float)(iw - 1) / (float)(new_w - 1), h_scale = (float)(ih - 1) / (float)(new_h - 1);
-        const float sy = (float)r * h_scale; const int iy = (int)sy; const float dy = sy - (float)iy;
-        const bool last_c = c == new_w - 1 || iw == 1, last_r = r == new_h - 1 || ih == 1;
-        const float sx = (float)c * w_scale; const int ix = (int)sx; const float dx = sx - (float)ix;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const float *pl = img + (size_t)k * iw * ih;
-            auto part = [&](int row) {
-                if (last_c) return pl[(size_t)row * iw + (iw - 1)];
-                return (1 - dx) * pl[(size_t)row * iw + ix] + dx * pl[(size_t)row * iw + ix + 1];
-            };
-            float val = (1 - dy) * part(iy);
-            if (!last_r) val = val + dy * part(iy + 1);
-            v[k] = val;
-        }
-    }
+    px_letterbox(AtPlanar{img, iw, ih}, iw, ih, new_w, new_h, off_x, off_y, oy, ox, v);
     Elt<T>::store8(out + (size_t)p * out_stride, v);
 }
 hipError_t launch_letterbox_chw(const float *img, int iw, int ih, int S, void *out, int out_dt, int out_stride, hipStream_t s)
 {
     int new_w, new_h;
-    if (((float)S / iw) < ((float)S / ih)) { new_w = S; new_h = (ih * S) / iw; } else { new_h = S; new_w = (iw * S) / ih; }
+    letterbox_dims(S, S, iw, ih, &new_w, &new_h);
     if (new_w < 1 || new_h < 1) return hipErrorInvalidValue;
     WITH_DT(out_dt, hipLaunchKernelGGL(k_letterbox_chw<T>, grid_for((size_t)S * S), dim3(256), 0, s, img, iw, ih, S, new_w, new_h, (S - new_w) / 2, (S - new_h) / 2, (T *)out, out_stride));
+    return hipGetLastError();
+}
+
+// ---- ragged batch fit (yolo_forward_images_u8): native-size uint8 RGB images packed in one HWC buffer, described by a device table of
+//      {offset, h, w}, fitted into the network input [n][S][S][out_stride] by ONE launch: grid (pixel tiles) x (images), one output pixel
+//      per lane, the 16-byte output pixel (8 channels: 3 real + 5 zero) stored as one vector.  Per pixel, each fit is the single-image
+//      kernel's arithmetic (px_stretch / px_letterbox / px_cv2), so a batched image equals the same image run alone, bit for bit.
+//      Source bytes are read through a buffer descriptor whose size is the packed buffer's byte count: a descriptor that pointed past
+//      the end would read zeros, never another allocation (the host validates every descriptor before the launch anyway).
+struct AtPacked {
+    __amdgpu_buffer_rsrc_t rsrc; unsigned base; int w, fit;
+    __device__ __forceinline__ float operator()(int y, int x, int c) const
+    {
+        const unsigned v = (unsigned)__builtin_amdgcn_raw_buffer_load_b8(rsrc, base + ((unsigned)y * (unsigned)w + (unsigned)x) * 3u + (unsigned)c, 0, 0);
+        // STRETCH and CV2 read the byte as a float (the /255 and /225 are part of px_stretch / px_cv2); LETTERBOX reads darknet's 0..1 value
+        return fit == FIT_LETTERBOX ? fit_unit_value(FIT_LETTERBOX, v) : (float)v;
+    }
+};
+
+template <typename T, int FIT>
+__global__ __launch_bounds__(256) void k_fit_images(const uint8_t *pixels, unsigned bytes, const ImgDesc *descs, int S, T *out, int out_stride,
+                                                    float post_mul, float post_add)
+{
+    const int img = blockIdx.y;
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= S * S) return;
+    const ImgDesc d = descs[img];
+    const int oy = p / S, ox = p - oy * S;
+    const AtPacked at{__builtin_amdgcn_make_buffer_rsrc((void *)pixels, 0, bytes, 0x00020000), (unsigned)d.offset, d.w, FIT};
+    float v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (FIT == FIT_STRETCH) px_stretch(at, d.h, d.w, S, oy, ox, post_mul, post_add, v);
+    else {
+        if (FIT == FIT_LETTERBOX) {
+            int new_w, new_h;
+            letterbox_dims(S, S, d.w, d.h, &new_w, &new_h);
+            px_letterbox(at, d.w, d.h, new_w, new_h, (S - new_w) / 2, (S - new_h) / 2, oy, ox, v);
+        } else px_cv2(at, d.h, d.w, S, S, oy, ox, FIT == FIT_CV2_BGR, 225.0f, v);
+        // YOLOv1's `x * 2 - 1` ([net] yolo_input_mul / yolo_input_add), as px_stretch applies it
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            if (post_mul != 1.0f) v[c] *= post_mul;
+            if (post_add != 0.0f) v[c] += post_add;
+        }
+    }
+    Elt<T>::store8(out + ((size_t)img * S * S + p) * out_stride, v);
+}
+
+hipError_t launch_fit_images(const uint8_t *pixels, size_t bytes, const ImgDesc *d_descs, int n, int fit, int S, void *out, int out_dt,
+                             int out_stride, float post_mul, float post_add, hipStream_t s)
+{
+    if (n < 1 || S < 1 || bytes > 0xffffffffull || fit < FIT_STRETCH || fit > FIT_CV2_BGR) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((S * S + 255) / 256), (unsigned)n);
+#define FIT_LAUNCH(F) WITH_DT(out_dt, hipLaunchKernelGGL((k_fit_images<T, F>), grid, dim3(256), 0, s, pixels, (unsigned)bytes, d_descs, S, (T *)out, out_stride, post_mul, post_add))
+    if (fit == FIT_STRETCH) FIT_LAUNCH(FIT_STRETCH);
+    else if (fit == FIT_LETTERBOX) FIT_LAUNCH(FIT_LETTERBOX);
+    else if (fit == FIT_CV2) FIT_LAUNCH(FIT_CV2);
+    else FIT_LAUNCH(FIT_CV2_BGR);
+#undef FIT_LAUNCH
     return hipGetLastError();
 }
 
@@ -576,25 +672,8 @@ __global__ void k_letterbox_planar(const float *img, int iw, int ih, int W, int 
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= W * H) return;
     const int oy = p / W, ox = p - oy * W;
-    const int r = oy - off_y, c = ox - off_x;
-    float v[3] = {0.5f, 0.5f, 0.5f};
-    if ((unsigned)r < (unsigned)new_h && (unsigned)c < (unsigned)new_w) {
-        const float w_scale = (float)(iw - 1) / (float)(new_w - 1), h_scale = (float)(ih - 1) / (float)(new_h - 1);
-        const float sy = (float)r * h_scale; const int iy = (int)sy; const float dy = sy - (float)iy;
-        const bool last_c = c == new_w - 1 || iw == 1, last_r = r == new_h - 1 || ih == 1;
-        const float sx = (float)c * w_scale; const int ix = (int)sx; const float dx = sx - (float)ix;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const float *pl = img + (size_t)k * iw * ih;
-            auto part = [&](int row) {
-                if (last_c) return pl[(size_t)row * iw + (iw - 1)];
-                return (1 - dx) * pl[(size_t)row * iw + ix] + dx * pl[(size_t)row * iw + ix + 1];
-            };
-            float val = (1 - dy) * part(iy);
-            if (!last_r) val = val + dy * part(iy + 1);
-            v[k] = val;
-        }
-    }
+    float v[3];
+    px_letterbox(AtPlanar{img, iw, ih}, iw, ih, new_w, new_h, off_x, off_y, oy, ox, v);
 #pragma unroll
     for (int k = 0; k < 3; ++k) out[(size_t)k * W * H + p] = v[k];
 }

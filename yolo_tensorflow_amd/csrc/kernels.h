@@ -209,6 +209,26 @@ hipError_t launch_resize_u8(const uint8_t *img, int h, int w, int s_out, void *o
                             int out_stride, int out_c, hipStream_t s, float post_scale = 1.0f, float post_add = 0.0f);
 // cv2.resize (INTER_LINEAR, float32) of a uint8 [h,w,3] image to fp32 [oh,ow,3], optional BGR -> RGB, then / divisor (V2/utils.py:13-27)
 hipError_t launch_resize_cv2_u8(const uint8_t *img, int h, int w, int oh, int ow, int swap_rb, float divisor, float *out, hipStream_t s);
+// ragged batch of native-size uint8 RGB images (yolo_forward_images_u8): one packed HWC buffer, one descriptor per image (the layout of
+// yolo_image_desc, include/yolo_hip.h), all fitted into the network input [n][S][S][out_stride] in ONE launch.  fit: FIT_* below.
+struct ImgDesc { unsigned long long offset; int h, w; };
+enum { FIT_STRETCH = 0, FIT_LETTERBOX = 1, FIT_CV2 = 2, FIT_CV2_BGR = 3 };
+// source pixels are read through a buffer descriptor of `bytes` bytes (< 2^32, checked by the caller with every descriptor)
+hipError_t launch_fit_images(const uint8_t *pixels, size_t bytes, const ImgDesc *d_descs, int n, int fit, int S, void *out, int out_dt,
+                             int out_stride, float post_mul, float post_add, hipStream_t s);
+// darknet's letterbox_image geometry (DN/image.c:960-966): the aspect-preserving size of a w x h image inside netw x neth
+__host__ __device__ inline void letterbox_dims(int netw, int neth, int w, int h, int *new_w, int *new_h)
+{
+    if (((float)netw / w) < ((float)neth / h)) { *new_w = netw; *new_h = (h * netw) / w; } else { *new_h = neth; *new_w = (w * neth) / h; }
+}
+// the value one source byte contributes before any interpolation: STRETCH value / 255.0f (TF's convert_image_dtype), LETTERBOX darknet's
+// loader `(float)data / 255.` -- a DOUBLE division rounded to float (DN/image.c load_image_stb) --, CV2 the byte itself (/ 225 comes last)
+__host__ __device__ inline float fit_unit_value(int fit, unsigned v)
+{
+    if (fit == FIT_STRETCH) return (float)v / 255.0f;
+    if (fit == FIT_LETTERBOX) return (float)((double)v / 255.);
+    return (float)v;
+}
 hipError_t launch_upsample2x(const TView &in, const TView &out, int bilinear, hipStream_t s);
 hipError_t launch_maxpool(const TView &in, const TView &out, int size, int stride, int pad, hipStream_t s);
 hipError_t launch_reorg(const TView &in, const TView &out, int stride, int darknet, hipStream_t s);
@@ -275,6 +295,12 @@ struct PostArgs {
     // needs the workspace srow [n*rows].  nullptr: not reported
     int *rows_out; int *srow;
     unsigned *zero_word;                // optional: a device word this launch resets to 0 (the lean decode's list counter)
+    // optional per-image source geometry (yolo_detect_images_*): nullptr keeps the single-shape path above.  fit FIT_LETTERBOX: every
+    // candidate box is un-letterboxed for its image (correct_yolo_boxes) before NMS, in source pixels unless geom_relative; the other
+    // fits: NMS runs in network space and, with geom_pixels, the kept records are scaled to the image afterwards (a separate launch).
+    // NMS_PER_CLASS with geom_pixels: the image's (h, w) is V2's image_shape.
+    const ImgDesc *geom; int geom_fit, geom_pixels, geom_relative, net_size;
+    int geom_net_pixels;                // 1: the decoded boxes are in network-input pixels (DECODE_PIXEL [yolo] heads), 0: normalised
 };
 hipError_t launch_postprocess(const PostArgs &a, hipStream_t s);
 hipError_t launch_letterbox_chw(const float *img, int iw, int ih, int S, void *out, int out_dt, int out_stride, hipStream_t s);

@@ -578,6 +578,49 @@ __device__ __forceinline__ float iou_numpy_v3(float4 a, float4 b)
     return inter / (a1 + a2 - inter + 1e-05f);
 }
 
+// correct_yolo_boxes / correct_region_boxes (DN/yolo_layer.c:247-273 = DN/region_layer.c:336-362) of attribute k (0 x, 1 y, 2 w, 3 h) of
+// one box: undo the letterbox of a w x h source image (aspect-preserving size new_w x new_h) inside netw x neth; relative = 0 scales to
+// source pixels.  Operation for operation darknet's (float and double mixed as there); k_darknet_boxes and the letterboxed detect path
+// (cand_box) both call it, so the two round alike.
+__device__ __forceinline__ float dn_correct(int k, float p, int netw, int neth, int new_w, int new_h, int w, int h, int relative)
+{
+    float v;
+    if (k == 0) { v = (p - (netw - new_w) / 2. / netw) / ((float)new_w / netw); if (!relative) v *= w; }
+    else if (k == 1) { v = (p - (neth - new_h) / 2. / neth) / ((float)new_h / neth); if (!relative) v *= h; }
+    else if (k == 2) { v = p; v *= (float)netw / new_w; if (!relative) v *= w; }
+    else { v = p; v *= (float)neth / new_h; if (!relative) v *= h; }
+    return v;
+}
+
+// the box a candidate row enters NMS with.  A letterboxed image's row is un-letterboxed first (darknet's order: get_network_boxes, then
+// do_nms_sort).  Then (cx,cy,w,h) for darknet / given corners; YOLOv1's swapped extents (see the general path below); corners
+// otherwise (V3/YOLOV3.py:348-351); V2's int pixel boxes last (V2/utils.py:32-43: scale to the image, truncate to int32, clip)
+__device__ __forceinline__ float4 cand_box(const PostArgs &a, int img, int row, int img_h, int img_w)
+{
+    const float *p = a.box4 ? a.box4 + ((size_t)img * a.rows + row) * 4 : a.det + ((size_t)img * a.rows + row) * a.attrs;
+    float q0 = p[0], q1 = p[1], q2 = p[2], q3 = p[3];
+    if (a.geom && a.geom_fit == FIT_LETTERBOX) {
+        const ImgDesc d = a.geom[img];
+        int new_w, new_h;
+        letterbox_dims(a.net_size, a.net_size, d.w, d.h, &new_w, &new_h);
+        q0 = dn_correct(0, q0, a.net_size, a.net_size, new_w, new_h, d.w, d.h, a.geom_relative);
+        q1 = dn_correct(1, q1, a.net_size, a.net_size, new_w, new_h, d.w, d.h, a.geom_relative);
+        q2 = dn_correct(2, q2, a.net_size, a.net_size, new_w, new_h, d.w, d.h, a.geom_relative);
+        q3 = dn_correct(3, q3, a.net_size, a.net_size, new_w, new_h, d.w, d.h, a.geom_relative);
+    }
+    float4 b;
+    if (a.nms_mode == 2 || a.corners_in) b = float4{q0, q1, q2, q3};
+    else if (a.nms_mode == 4) { float w2 = 0.5f * q2, h2 = 0.5f * q3; b = float4{q0 - h2, q1 - w2, q0 + h2, q1 + w2}; }
+    else { float w2 = q2 * 0.5f, h2 = q3 * 0.5f; b = float4{q0 - w2, q1 - h2, q0 + w2, q1 + h2}; }
+    if (a.nms_mode == 1 && img_w > 0) {
+        int x0 = (int)(b.x * (float)img_w), y0 = (int)(b.y * (float)img_h);
+        int x1 = (int)(b.z * (float)img_w), y1 = (int)(b.w * (float)img_h);
+        x0 = max(x0, 0); y0 = max(y0, 0); x1 = min(x1, img_w - 1); y1 = min(y1, img_h - 1);
+        b = float4{(float)x0, (float)y0, (float)x1, (float)y1};
+    }
+    return b;
+}
+
 #define NMS_THREADS 1024
 #define SORT_LDS 4096
 
@@ -591,7 +634,8 @@ static_assert(NMS_POOL >= SORT_LDS + 512, "the general path's keys + alive bitse
 __global__ __launch_bounds__(NMS_THREADS) void k_nms_image(const PostArgs a)
 {
     float4 *sbox = a.sbox; int *slabel = a.slabel; float *sscore = a.sscore;
-    const int img_h = a.img_h, img_w = a.img_w;
+    int img_h = a.img_h, img_w = a.img_w;
+    if (a.geom && a.geom_pixels && a.nms_mode == 1) { img_h = a.geom[blockIdx.x].h; img_w = a.geom[blockIdx.x].w; }      // V2's image_shape = this image's
     __shared__ unsigned long long pool[NMS_POOL];
     unsigned long long *const skeys = pool;
     unsigned int *const alive = (unsigned int *)(pool + SORT_LDS);      // bitset for up to 32768 candidates (general path)
@@ -680,18 +724,7 @@ __global__ __launch_bounds__(NMS_THREADS) void k_nms_image(const PostArgs a)
             rank += __shfl_xor(rank, 1); rank += __shfl_xor(rank, 2); rank += __shfl_xor(rank, 4);
             if (ci < M && part == 0) {
                 const int row = cand[ci];
-                const float *p = a.box4 ? a.box4 + ((size_t)img * a.rows + row) * 4 : a.det + ((size_t)img * a.rows + row) * a.attrs;
-                float4 bx;
-                if (a.nms_mode == 2 || a.corners_in) bx = float4{p[0], p[1], p[2], p[3]};      // (cx,cy,w,h) for darknet; given corners
-                else if (a.nms_mode == 4) { float w2 = 0.5f * p[2], h2 = 0.5f * p[3]; bx = float4{p[0] - h2, p[1] - w2, p[0] + h2, p[1] + w2}; }      // YOLOv1's swapped extents, see below
-                else { float w2 = p[2] * 0.5f, h2 = p[3] * 0.5f; bx = float4{p[0] - w2, p[1] - h2, p[0] + w2, p[1] + h2}; }                          // V3/YOLOV3.py:348-351
-                if (a.nms_mode == 1 && img_w > 0) {            // V2/utils.py:32-43: scale to the image, truncate to int32, clip
-                    int x0 = (int)(bx.x * (float)img_w), y0 = (int)(bx.y * (float)img_h);
-                    int x1 = (int)(bx.z * (float)img_w), y1 = (int)(bx.w * (float)img_h);
-                    x0 = max(x0, 0); y0 = max(y0, 0); x1 = min(x1, img_w - 1); y1 = min(y1, img_h - 1);
-                    bx = float4{(float)x0, (float)y0, (float)x1, (float)y1};
-                }
-                lbox[rank] = bx; llabel[rank] = labels[row]; lscore[rank] = scores[row]; lrow[rank] = row;
+                lbox[rank] = cand_box(a, img, row, img_h, img_w); llabel[rank] = labels[row]; lscore[rank] = scores[row]; lrow[rank] = row;
             }
         }
         __syncthreads();
@@ -814,25 +847,7 @@ __global__ __launch_bounds__(NMS_THREADS) void k_nms_image(const PostArgs a)
     // (4) gather candidates in sorted order
     for (int i = tid; i < M; i += NMS_THREADS) {
         int row = cand[(unsigned int)(keys[i] & (a.nms_mode == 3 ? 0x7fffu : 0xffffffffu))];
-        const float *p = a.box4 ? a.box4 + ((size_t)img * a.rows + row) * 4 : a.det + ((size_t)img * a.rows + row) * a.attrs;
-        float4 b;
-        if (a.nms_mode == 2 || a.corners_in) b = float4{p[0], p[1], p[2], p[3]};       // (cx,cy,w,h) for darknet; given corners
-        else if (a.nms_mode == 4) {
-            // YOLOv1's quirk (V1/YOLO_V1_Inference.py:259-262): `_boxes` = [y - w/2, x - h/2, y + w/2, x + h/2] handed over as
-            // [ymin, xmin, ymax, xmax] -- the vertical extent is built from the WIDTH and the horizontal one from the HEIGHT
-            float w2 = 0.5f * p[2], h2 = 0.5f * p[3];
-            b = float4{p[0] - h2, p[1] - w2, p[0] + h2, p[1] + w2};
-        } else {
-            float w2 = p[2] * 0.5f, h2 = p[3] * 0.5f;                                      // V3/YOLOV3.py:348-351
-            b = float4{p[0] - w2, p[1] - h2, p[0] + w2, p[1] + h2};
-        }
-        if (a.nms_mode == 1 && img_w > 0) {
-            // V2/utils.py:32-43: scale to the image, truncate to int32, clip to [0, w-1] x [0, h-1]
-            int x0 = (int)(b.x * (float)img_w), y0 = (int)(b.y * (float)img_h);
-            int x1 = (int)(b.z * (float)img_w), y1 = (int)(b.w * (float)img_h);
-            x0 = max(x0, 0); y0 = max(y0, 0); x1 = min(x1, img_w - 1); y1 = min(y1, img_h - 1);
-            b = float4{(float)x0, (float)y0, (float)x1, (float)y1};
-        }
+        const float4 b = cand_box(a, img, row, img_h, img_w);
         sbox[i] = b; slabel[i] = labels[row]; sscore[i] = scores[row];
         if (srow) srow[i] = row;
     }
@@ -944,11 +959,29 @@ __global__ __launch_bounds__(NMS_THREADS) void k_nms_image(const PostArgs a)
     if (tid == 0) a.counts_out[img] = min(s_kept, a.max_out);
 }
 
+// the kept records of a stretched image, scaled to its source pixels after NMS: `convert_to_original_size` of the reference's V3 scripts,
+// box * original_size for normalised boxes (V3/YOLO_V3_inference.py:55-57) and box * (original_size / size) for network-pixel boxes
+// (V3/convert_ckpt_and_inference.py:43-45), both float64 in numpy: evaluated in double here and rounded once
+__global__ void k_records_to_source(BoxOut *out, const int *counts, int max_out, const ImgDesc *geom, int net_size, int net_pixels)
+{
+    const int img = blockIdx.x, k = threadIdx.x;
+    const int cnt = min(counts[img], max_out);
+    const ImgDesc d = geom[img];
+    const double rx = net_pixels ? (double)d.w / (double)net_size : (double)d.w, ry = net_pixels ? (double)d.h / (double)net_size : (double)d.h;
+    for (int r = k; r < cnt; r += blockDim.x) {
+        BoxOut &b = out[(size_t)img * max_out + r];
+        b.x0 = (float)((double)b.x0 * rx); b.y0 = (float)((double)b.y0 * ry);
+        b.x1 = (float)((double)b.x1 * rx); b.y1 = (float)((double)b.y1 * ry);
+    }
+}
+
 hipError_t launch_postprocess(const PostArgs &a, hipStream_t s)
 {
     size_t nrows = (size_t)a.n * a.rows;
     if (!a.scores_ready) launch_score_rows(a.det, nrows, a.attrs, a.scores, a.labels, s, a.nms_mode == 3);
     hipLaunchKernelGGL(k_nms_image, dim3(a.n), dim3(NMS_THREADS), 0, s, a);
+    if (a.geom && a.geom_pixels && a.geom_fit != FIT_LETTERBOX && a.nms_mode != 1)
+        hipLaunchKernelGGL(k_records_to_source, dim3(a.n), dim3(64), 0, s, (BoxOut *)a.boxes_out, (const int *)a.counts_out, a.max_out, a.geom, a.net_size, a.geom_net_pixels);
     return hipGetLastError();
 }
 
@@ -1092,7 +1125,7 @@ __global__ __launch_bounds__(1024) void k_darknet_boxes(const DnBoxesArgs a)
     const int n = count < a.cap ? count : a.cap;
     const int netw = a.netw, neth = a.neth, w = a.w, h = a.h;
     int new_w, new_h;
-    if (((float)netw / w) < ((float)neth / h)) { new_w = netw; new_h = (h * netw) / w; } else { new_h = neth; new_w = (w * neth) / h; }
+    letterbox_dims(netw, neth, w, h, &new_w, &new_h);
     // which head a row belongs to decides the gating
     for (long idx = tid; idx < (long)n * a.attrs; idx += 1024) {
         const int rec = (int)(idx / a.attrs), k = (int)(idx - (long)rec * a.attrs);
@@ -1119,10 +1152,7 @@ __global__ __launch_bounds__(1024) void k_darknet_boxes(const DnBoxesArgs a)
         const float obj_raw = p[4];
         const float objectness = kind == 1 ? (obj_raw > a.thresh ? obj_raw : 0.f) : obj_raw;
         float v;
-        if (k == 0) { v = (p[0] - (netw - new_w) / 2. / netw) / ((float)new_w / netw); if (!a.relative) v *= w; }
-        else if (k == 1) { v = (p[1] - (neth - new_h) / 2. / neth) / ((float)new_h / neth); if (!a.relative) v *= h; }
-        else if (k == 2) { v = p[2]; v *= (float)netw / new_w; if (!a.relative) v *= w; }
-        else if (k == 3) { v = p[3]; v *= (float)neth / new_h; if (!a.relative) v *= h; }
+        if (k < 4) v = dn_correct(k, p[k], netw, neth, new_w, new_h, w, h, a.relative);
         else if (k == 4) v = objectness;
         else { const float prob = obj_raw * p[k]; v = (objectness != 0.f && prob > a.thresh) ? prob : 0.f; }
         a.rec[idx] = v;

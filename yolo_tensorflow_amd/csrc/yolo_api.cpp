@@ -36,9 +36,10 @@ void yolo_destroy(yolo_ctx *c)
     for (void *p : c->phys) if (p) hipFree(p);
     for (auto &L : c->layers) { if (L.d_w) hipFree(L.d_w); if (L.d_b) hipFree(L.d_b); if (L.d_sc) hipFree(L.d_sc); if (L.d_wf) hipFree(L.d_wf); if (L.d_obj) hipFree(L.d_obj); }
     void *ptrs[] = {c->input.ptr, c->d_zeros, c->d_stage, c->d_det, c->d_scores, c->d_labels, c->d_cand, c->d_keys, c->d_sbox, c->d_slabel, c->d_sscore, c->d_boxes, c->d_counts,
-                    c->d_dn_rec, c->d_dn_src, c->d_dn_count, c->d_dn_last, c->d_box4, c->s2d.ptr, c->d_srow, c->d_rows, c->d_lean_list, c->d_lean_cnt, c->d_f32a, c->d_f32b};
+                    c->d_dn_rec, c->d_dn_src, c->d_dn_count, c->d_dn_last, c->d_box4, c->s2d.ptr, c->d_srow, c->d_rows, c->d_lean_list, c->d_lean_cnt, c->d_f32a, c->d_f32b, c->d_descs, c->d_pix};
     for (void *p : ptrs) if (p) hipFree(p);
     if (c->gexec) hipGraphExecDestroy(c->gexec);
+    if (c->gexec_img) hipGraphExecDestroy(c->gexec_img);
     if (c->own_stream && c->stream) hipStreamDestroy(c->stream);
     delete c;
 }
@@ -84,8 +85,14 @@ double yolo_conv_bytes(const yolo_ctx *c, int n)
 // ---- darknet-flavoured views of the last forward (image 0), used by the veneer libdarknet_hip.so ----
 int yolo_darknet_boxes(yolo_ctx *c, int w, int h, float thresh, int relative, float *records, int cap, int *count)
 {
+    return yolo_darknet_boxes_at(c, 0, w, h, thresh, relative, records, cap, count);
+}
+
+int yolo_darknet_boxes_at(yolo_ctx *c, int image, int w, int h, float thresh, int relative, float *records, int cap, int *count)
+{
     if (!c || !count) return YOLO_ERR_INVALID;
     if (c->last_n < 1 || !c->det_valid) return fail(c, YOLO_ERR_STATE, "yolo_darknet_boxes needs a yolo_forward* pass first");
+    if (image < 0 || image >= c->last_n) return fail(c, YOLO_ERR_INVALID, "image %d outside the last forward's batch of %d", image, c->last_n);
     if (w < 1 || h < 1 || cap < 0 || (cap > 0 && !records)) return fail(c, YOLO_ERR_INVALID, "bad image size / capacity");
     HIPCK(c, hipSetDevice(c->device));
     if (!c->d_dn_rec) {
@@ -94,14 +101,14 @@ int yolo_darknet_boxes(yolo_ctx *c, int w, int h, float thresh, int relative, fl
         HIPCK(c, hipMalloc((void **)&c->d_dn_count, 4));
     }
     DnBoxesArgs a; memset(&a, 0, sizeof a);
-    a.det = c->d_det; a.attrs = c->attrs;
+    a.det = c->d_det + (size_t)image * c->rows * c->attrs; a.attrs = c->attrs;
     for (size_t li = 0; li < c->layers.size(); ++li) {
         const Layer &L = c->layers[li];
         if (L.type != L_YOLO && L.type != L_REGION && L.type != L_DETECT) continue;
         if (a.nheads == 8) return fail(c, YOLO_ERR_UNSUPPORTED, "more than 8 heads");
         if (L.type == L_DETECT) {
             if (a.nheads) return fail(c, YOLO_ERR_UNSUPPORTED, "a [detection] head next to other heads");
-            a.raw = (const float *)c->layers[li - 1].out.ptr; a.side = L.side; a.classes = L.classes; a.sqr = L.sqr;
+            a.raw = (const float *)c->layers[li - 1].out.ptr + (size_t)image * c->layers[li - 1].out.stride; a.side = L.side; a.classes = L.classes; a.sqr = L.sqr;
             a.kind[0] = 2; a.grid[0] = L.side; a.na[0] = L.na; a.off[0] = L.row_off; a.nheads = 1;
             continue;
         }

@@ -104,6 +104,13 @@ struct yolo_ctx {
     // yolo_detect_graph state
     struct GKey { const void *img; int n, fmt; float scale, st, it; int mo, nm, sm; void *bo, *co; } gkey{};
     hipGraphExec_t gexec = nullptr; int gstate = 0;      // 0: next call eager, 1: next call captures, 2: replay, -1: capture unsupported
+    // ragged batches of native-size images (yolo_*_images_*): descriptor table [max_batch] (device), staging of a host packed buffer, the
+    // geometry the last such forward ran with (what the box mapping of its postprocess reads), and yolo_detect_images_graph's state (the
+    // same states as above; its key holds no image size or offset: those live in d_descs, rewritten before every launch)
+    ImgDesc *d_descs = nullptr; void *d_pix = nullptr; size_t pix_cap = 0;
+    int geom_fit = -1, geom_n = 0;
+    struct GKeyImages { const void *pix; size_t bytes; int n, fit, units; float st, it; int mo, nm, sm; void *bo, *co; } gkey_img;
+    hipGraphExec_t gexec_img = nullptr; int gstate_img = 0;
     bool weights_loaded = false;
     int scores_mode = -1;                 // what d_scores/d_labels hold: 0 max(obj*cls) from the decode, 1 objectness, -1 nothing
     size_t weights_count = 0;
@@ -135,7 +142,11 @@ int fail(yolo_ctx *c, int code, const char *fmt, ...);
 inline int roundup(int x, int m) { return (x + m - 1) / m * m; }
 inline int pair_width(int C) { return 2 * roundup(C, 32); }      // elements per pixel of an interleaved split-fp16 pair tensor of C channels (32 hi | 32 lo per group)
 inline int gran_of(int dt) { return dt == DT_FP8 ? 16 : 8; }      // channels per 16-byte piece (8 for fp32 tensors too)
-inline void drop_graph(yolo_ctx *c) { if (c->gexec) { hipGraphExecDestroy(c->gexec); c->gexec = nullptr; } if (c->gstate > 0) c->gstate = 0; }      // a plan / parameter change: the captured detect step must not be replayed
+inline void drop_graph(yolo_ctx *c)      // a plan / parameter / buffer change: no captured detect step may be replayed
+{
+    if (c->gexec) { hipGraphExecDestroy(c->gexec); c->gexec = nullptr; } if (c->gstate > 0) c->gstate = 0;
+    if (c->gexec_img) { hipGraphExecDestroy(c->gexec_img); c->gexec_img = nullptr; } if (c->gstate_img > 0) c->gstate_img = 0;
+}
 
 // yolo_pack.cpp
 uint16_t f2bf(float f);
@@ -160,8 +171,10 @@ int stage_in(yolo_ctx *c, const void *images, int n, int fmt, int loc, float sca
 int run_network(yolo_ctx *c, int n, bool lean = false);
 int copy_out(yolo_ctx *c, void *dst, const void *src, size_t bytes, int loc);
 int post_args_ok(yolo_ctx *c, int max_out, int nms_mode, int select_mode);
+struct PostGeom { int fit, pixels; };      // per-image box mapping of a ragged batch (yolo_box_units), over c->d_descs
 int post(yolo_ctx *c, const float *det, int n, int rows, int attrs, float score_thr, float iou_thr, int max_out,
-         int nms_mode, int select_mode, int img_h, int img_w, int scores_ready, yolo_box *boxes_out, int32_t *counts_out, int out_loc, int32_t *rows_out = nullptr);
+         int nms_mode, int select_mode, int img_h, int img_w, int scores_ready, yolo_box *boxes_out, int32_t *counts_out, int out_loc, int32_t *rows_out = nullptr,
+         const PostGeom *geom = nullptr);
 // yolo_ops.cpp
 extern thread_local std::string g_op_err;
 TView make_view(void *p, int n, int h, int w, int c, int stride, int dt);

@@ -196,7 +196,7 @@ int yolo_set_act_scales(yolo_ctx *c, const float *scales, int n)
     c->user_scale.assign(scales, scales + n);
     resolve_scales(c);
     c->weights_loaded = false;           // filters absorb the input scales: they have to be packed again
-    if (c->gexec) { hipGraphExecDestroy(c->gexec); c->gexec = nullptr; } if (c->gstate > 0) c->gstate = 0;
+    drop_graph(c);
     return YOLO_OK;
 }
 

@@ -421,6 +421,7 @@ int allocate(yolo_ctx *c)
     }
     c->stage_bytes = (size_t)c->max_batch * c->in_h * c->in_w * 3 * 4;
     HIPCK(c, hipMalloc(&c->d_stage, c->stage_bytes));
+    HIPCK(c, hipMalloc((void **)&c->d_descs, (size_t)c->max_batch * sizeof(ImgDesc)));      // ragged batches: one descriptor per image
     size_t nr = (size_t)c->max_batch * c->rows;
     HIPCK(c, hipMalloc((void **)&c->d_det, nr * c->attrs * 4));
     HIPCK(c, hipMalloc((void **)&c->d_box4, nr * 16));

@@ -309,14 +309,14 @@ int copy_out(yolo_ctx *c, void *dst, const void *src, size_t bytes, int loc)
 }
 
 int post(yolo_ctx *c, const float *det, int n, int rows, int attrs, float score_thr, float iou_thr, int max_out,
-         int nms_mode, int select_mode, int img_h, int img_w, int scores_ready, yolo_box *boxes_out, int32_t *counts_out, int out_loc, int32_t *rows_out)
+         int nms_mode, int select_mode, int img_h, int img_w, int scores_ready, yolo_box *boxes_out, int32_t *counts_out, int out_loc, int32_t *rows_out,
+         const PostGeom *geom)
 {
     if (int r = post_args_ok(c, max_out, nms_mode, select_mode)) return r;
     size_t need = (size_t)n * max_out;
     if ((int)need > c->boxes_cap) {
         // a captured detect graph holds the old pointer (memset, NMS writes, D2D copy): it must not be replayed
-        if (c->gexec) { hipGraphExecDestroy(c->gexec); c->gexec = nullptr; }
-        if (c->gstate > 0) c->gstate = 0;
+        drop_graph(c);
         HIPCK(c, hipStreamSynchronize(c->stream));
         if (c->d_boxes) HIPCK(c, hipFree(c->d_boxes));
         if (c->d_rows) HIPCK(c, hipFree(c->d_rows));
@@ -335,6 +335,13 @@ int post(yolo_ctx *c, const float *det, int n, int rows, int attrs, float score_
     if (direct_c) p.counts_out = (int *)counts_out;
     if (rows_out) { p.srow = c->d_srow; p.rows_out = out_loc != YOLO_HOST ? (int *)rows_out : c->d_rows; }
     if (c->lean_cnt_dirty) p.zero_word = c->d_lean_cnt;
+    if (geom) {
+        p.geom = c->d_descs; p.geom_fit = geom->fit; p.geom_pixels = geom->pixels; p.net_size = c->in_h;
+        // a letterboxed box leaves darknet's correction in source pixels, unless V2's per-class NMS scales it to the image itself
+        p.geom_relative = !(geom->pixels && nms_mode != YOLO_NMS_PER_CLASS);
+        p.geom_net_pixels = c->decode == YOLO_DECODE_PIXEL;          // [region] / [detection] heads always decode normalised boxes
+        for (auto &L : c->layers) if (L.type == L_REGION || L.type == L_DETECT) p.geom_net_pixels = 0;
+    }
     HIPCK(c, launch_postprocess(p, c->stream));
     c->lean_cnt_dirty = false;
     if (rows_out && out_loc == YOLO_HOST) { int r = copy_out(c, rows_out, c->d_rows, need * 4, out_loc); if (r) return r; }
@@ -409,10 +416,9 @@ int yolo_forward_letterbox_chw(yolo_ctx *c, const float *image_chw, int w, int h
     return YOLO_OK;
 }
 
-int yolo_postprocess_rows(yolo_ctx *c, int n, float score_thr, float iou_thr, int max_out, int nms_mode, int select_mode,
-                          yolo_box *boxes_out, int32_t *counts_out, int32_t *rows_out, int out_loc)
+static int postprocess_impl(yolo_ctx *c, int n, float score_thr, float iou_thr, int max_out, int nms_mode, int select_mode,
+                            yolo_box *boxes_out, int32_t *counts_out, int32_t *rows_out, int out_loc, const PostGeom *geom)
 {
-    if (!c) return YOLO_ERR_INVALID;
     if (n < 1 || n > c->last_n) return fail(c, YOLO_ERR_STATE, "postprocess of %d images but the last forward ran %d", n, c->last_n);
     HIPCK(c, hipSetDevice(c->device));
     const int want = nms_mode == YOLO_NMS_NUMPY_V3 ? 1 : 0;
@@ -423,7 +429,14 @@ int yolo_postprocess_rows(yolo_ctx *c, int n, float score_thr, float iou_thr, in
     const int ready = c->scores_mode == want;
     c->scores_mode = want;
     return post(c, c->d_det, n, c->rows, c->attrs, score_thr, iou_thr, max_out, nms_mode, select_mode,
-                nms_mode == YOLO_NMS_PER_CLASS ? c->in_h : 0, nms_mode == YOLO_NMS_PER_CLASS ? c->in_w : 0, ready, boxes_out, counts_out, out_loc, rows_out);
+                nms_mode == YOLO_NMS_PER_CLASS ? c->in_h : 0, nms_mode == YOLO_NMS_PER_CLASS ? c->in_w : 0, ready, boxes_out, counts_out, out_loc, rows_out, geom);
+}
+
+int yolo_postprocess_rows(yolo_ctx *c, int n, float score_thr, float iou_thr, int max_out, int nms_mode, int select_mode,
+                          yolo_box *boxes_out, int32_t *counts_out, int32_t *rows_out, int out_loc)
+{
+    if (!c) return YOLO_ERR_INVALID;
+    return postprocess_impl(c, n, score_thr, iou_thr, max_out, nms_mode, select_mode, boxes_out, counts_out, rows_out, out_loc, nullptr);
 }
 
 int yolo_postprocess(yolo_ctx *c, int n, float score_thr, float iou_thr, int max_out, int nms_mode, int select_mode,
@@ -478,6 +491,144 @@ int yolo_detect_graph(yolo_ctx *c, const void *images, int n, int fmt, float sca
     c->lean = nms_mode != YOLO_NMS_NUMPY_V3 && c->lean_ok; c->det_valid = !c->lean; c->lean_thr = score_thr;
     c->last_n = n; c->scores_mode = nms_mode == YOLO_NMS_NUMPY_V3 ? 1 : 0;
     return YOLO_OK;
+}
+
+// ---- ragged batches of native-size images: one fit launch over a descriptor table, then the ordinary forward; the box mapping of the
+//      postprocess reads the same table ("Ragged batches") ----
+static_assert(sizeof(ImgDesc) == sizeof(yolo_image_desc) && sizeof(yolo_image_desc) == 16, "yolo_image_desc is the device table's row");
+
+// everything a ragged batch is refused for, before any launch
+static int images_check(yolo_ctx *c, const void *pixels, size_t bytes, const yolo_image_desc *descs, int n, int fit)
+{
+    if (!c->weights_loaded) return fail(c, YOLO_ERR_STATE, "forward of images before weights were loaded");
+    if (n < 1 || n > c->max_batch) return fail(c, YOLO_ERR_INVALID, "batch %d outside 1..%d", n, c->max_batch);
+    if (!pixels || !descs) return fail(c, YOLO_ERR_INVALID, "pixels / descs == NULL");
+    if (fit < YOLO_FIT_STRETCH || fit > YOLO_FIT_CV2_BGR) return fail(c, YOLO_ERR_INVALID, "bad fit %d", fit);
+    if (bytes < 3 || bytes > 0xffffffffull) return fail(c, YOLO_ERR_INVALID, "packed buffer of %zu bytes (3 .. 2^32 - 1)", bytes);
+    for (int i = 0; i < n; ++i) {
+        const yolo_image_desc &d = descs[i];
+        if (d.h < 1 || d.w < 1) return fail(c, YOLO_ERR_INVALID, "image %d: %d x %d", i, (int)d.h, (int)d.w);
+        const uint64_t need = (uint64_t)d.h * (uint64_t)d.w * 3u;
+        if (d.offset > bytes || need > bytes - d.offset)
+            return fail(c, YOLO_ERR_INVALID, "image %d: %d x %d x 3 bytes at offset %llu end past the %zu-byte buffer", i, (int)d.h, (int)d.w, (unsigned long long)d.offset, bytes);
+        if (fit == YOLO_FIT_LETTERBOX) {
+            int nw, nh; letterbox_dims(c->in_w, c->in_h, d.w, d.h, &nw, &nh);
+            if (nw < 1 || nh < 1) return fail(c, YOLO_ERR_INVALID, "image %d: %d x %d letterboxes to less than one pixel", i, (int)d.h, (int)d.w);
+        }
+    }
+    return YOLO_OK;
+}
+
+static int detect_images_check(yolo_ctx *c, int fit, int max_out, int nms_mode, int select_mode, int units)
+{
+    if (int r = post_args_ok(c, max_out, nms_mode, select_mode)) return r;
+    if (units != YOLO_UNITS_NETWORK && units != YOLO_UNITS_SOURCE_PIXELS) return fail(c, YOLO_ERR_INVALID, "bad units %d", units);
+    if (fit == YOLO_FIT_LETTERBOX)
+        for (auto &L : c->layers) if (L.type == L_DETECT) return fail(c, YOLO_ERR_UNSUPPORTED, "letterbox box mapping of a [detection] head (darknet v1 does not letterbox)");
+    return YOLO_OK;
+}
+
+// the device step of a checked batch: (descriptor upload,) fit, network.  pixels: device memory
+static int images_step(yolo_ctx *c, const uint8_t *pixels, size_t bytes, const yolo_image_desc *descs, int n, int fit, bool upload, bool lean, float score_thr)
+{
+    c->lean_thr = score_thr;
+    if (upload) HIPCK(c, hipMemcpyAsync(c->d_descs, descs, (size_t)n * sizeof(ImgDesc), hipMemcpyHostToDevice, c->stream));
+    c->stem_u8 = nullptr;                // the fused stem reads the fitted input
+    if (c->in_pair) {
+        HIPCK(c, launch_fit_images(pixels, bytes, c->d_descs, n, fit, c->in_h, c->d_f32a, DT_F32, 8, c->in_mul, c->in_add, c->stream));
+        HIPCK(c, launch_split_from_f32(c->d_f32a, 8, c->input.ptr, 24, 8, (size_t)n * c->in_h * c->in_w, c->stream, PAIR_B3));
+    } else HIPCK(c, launch_fit_images(pixels, bytes, c->d_descs, n, fit, c->in_h, c->input.ptr, c->input.dt, 8, c->in_mul, c->in_add, c->stream));
+    if (int r = run_network(c, n, lean)) return r;
+    c->geom_fit = fit; c->geom_n = n;
+    return YOLO_OK;
+}
+
+static int forward_images_impl(yolo_ctx *c, const uint8_t *pixels, size_t bytes, const yolo_image_desc *descs, int n, int fit, int loc,
+                               float *det_out, int out_loc, bool lean, float score_thr)
+{
+    if (int r = images_check(c, pixels, bytes, descs, n, fit)) return r;
+    HIPCK(c, hipSetDevice(c->device));
+    const uint8_t *src = pixels;
+    if (loc == YOLO_HOST) {              // one host-to-device copy of the packed buffer (grown, never shrunk)
+        if (bytes > c->pix_cap) {
+            HIPCK(c, hipStreamSynchronize(c->stream));
+            if (c->d_pix) HIPCK(c, hipFree(c->d_pix));
+            c->d_pix = nullptr; c->pix_cap = 0;
+            HIPCK(c, hipMalloc(&c->d_pix, bytes)); c->pix_cap = bytes;
+        }
+        HIPCK(c, hipMemcpyAsync(c->d_pix, pixels, bytes, hipMemcpyHostToDevice, c->stream));
+        src = (const uint8_t *)c->d_pix;
+    }
+    if (int r = images_step(c, src, bytes, descs, n, fit, true, lean && !det_out, score_thr)) return r;
+    if (det_out) return copy_out(c, det_out, c->d_det, (size_t)n * c->rows * c->attrs * 4, out_loc);
+    return YOLO_OK;
+}
+
+int yolo_forward_images_u8(yolo_ctx *c, const uint8_t *pixels, size_t bytes, const yolo_image_desc *descs, int n, int fit, int loc,
+                           float *det_out, int out_loc)
+{
+    if (!c) return YOLO_ERR_INVALID;
+    return forward_images_impl(c, pixels, bytes, descs, n, fit, loc, det_out, out_loc, false, 0.f);
+}
+
+int yolo_detect_images_u8(yolo_ctx *c, const uint8_t *pixels, size_t bytes, const yolo_image_desc *descs, int n, int fit, int loc,
+                          float score_thr, float iou_thr, int max_out, int nms_mode, int select_mode, int units,
+                          yolo_box *boxes_out, int32_t *counts_out, int out_loc)
+{
+    if (!c) return YOLO_ERR_INVALID;
+    if (int r = detect_images_check(c, fit, max_out, nms_mode, select_mode, units)) return r;
+    if (int r = forward_images_impl(c, pixels, bytes, descs, n, fit, loc, nullptr, YOLO_DEVICE, nms_mode != YOLO_NMS_NUMPY_V3, score_thr)) return r;
+    const PostGeom g{fit, units == YOLO_UNITS_SOURCE_PIXELS};
+    return postprocess_impl(c, n, score_thr, iou_thr, max_out, nms_mode, select_mode, boxes_out, counts_out, nullptr, out_loc, &g);
+}
+
+int yolo_detect_images_graph(yolo_ctx *c, const uint8_t *pixels, size_t bytes, const yolo_image_desc *descs, int n, int fit,
+                             float score_thr, float iou_thr, int max_out, int nms_mode, int select_mode, int units,
+                             yolo_box *boxes_out, int32_t *counts_out)
+{
+    if (!c) return YOLO_ERR_INVALID;
+    if (!pixels || !boxes_out || !counts_out) return fail(c, YOLO_ERR_INVALID, "yolo_detect_images_graph needs device pointers for pixels, boxes_out and counts_out");
+    if (int r = detect_images_check(c, fit, max_out, nms_mode, select_mode, units)) return r;
+    if (int r = images_check(c, pixels, bytes, descs, n, fit)) return r;
+    yolo_ctx::GKeyImages k; memset(&k, 0, sizeof k);
+    k.pix = pixels; k.bytes = bytes; k.n = n; k.fit = fit; k.units = units; k.st = score_thr; k.it = iou_thr; k.mo = max_out; k.nm = nms_mode; k.sm = select_mode;
+    k.bo = (void *)boxes_out; k.co = (void *)counts_out;
+    if (memcmp(&k, &c->gkey_img, sizeof k) != 0) {
+        if (c->gexec_img) { hipGraphExecDestroy(c->gexec_img); c->gexec_img = nullptr; }
+        c->gkey_img = k; if (c->gstate_img >= 0) c->gstate_img = 0;
+    }
+    HIPCK(c, hipSetDevice(c->device));
+    // this call's sizes and offsets: into the device table, on the context stream, ahead of the step that reads them (never captured)
+    HIPCK(c, hipMemcpyAsync(c->d_descs, descs, (size_t)n * sizeof(ImgDesc), hipMemcpyHostToDevice, c->stream));
+    const PostGeom g{fit, units == YOLO_UNITS_SOURCE_PIXELS};
+    const bool lean = nms_mode != YOLO_NMS_NUMPY_V3;
+    auto eager = [&]() -> int {
+        if (int r = images_step(c, pixels, bytes, descs, n, fit, false, lean, score_thr)) return r;
+        return postprocess_impl(c, n, score_thr, iou_thr, max_out, nms_mode, select_mode, boxes_out, counts_out, nullptr, YOLO_DEVICE, &g);
+    };
+    if (c->gstate_img <= 0) { int r = eager(); if (r == YOLO_OK && c->gstate_img == 0) c->gstate_img = 1; return r; }
+    if (c->gstate_img == 1) {
+        hipGraph_t gr = nullptr;
+        if (hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) { (void)hipGetLastError(); c->gstate_img = -1; return eager(); }
+        int r = eager();
+        hipError_t e = hipStreamEndCapture(c->stream, &gr);
+        if (r != YOLO_OK || e != hipSuccess || !gr) { (void)hipGetLastError(); if (gr) hipGraphDestroy(gr); c->gstate_img = -1; return r ? r : eager(); }
+        e = hipGraphInstantiate(&c->gexec_img, gr, nullptr, nullptr, 0);
+        hipGraphDestroy(gr);
+        if (e != hipSuccess) { (void)hipGetLastError(); c->gexec_img = nullptr; c->gstate_img = -1; return eager(); }
+        c->gstate_img = 2;
+    }
+    if (c->lean_cnt_dirty) { HIPCK(c, hipMemsetAsync(c->d_lean_cnt, 0, 16, c->stream)); c->lean_cnt_dirty = false; }      // see yolo_detect_graph
+    HIPCK(c, hipGraphLaunch(c->gexec_img, c->stream));
+    c->lean = lean && c->lean_ok; c->det_valid = !c->lean; c->lean_thr = score_thr;
+    c->last_n = n; c->scores_mode = nms_mode == YOLO_NMS_NUMPY_V3 ? 1 : 0; c->stem_u8 = nullptr; c->geom_fit = fit; c->geom_n = n;
+    return YOLO_OK;
+}
+
+float yolo_fit_unit_value(int fit, int value)
+{
+    if (fit < YOLO_FIT_STRETCH || fit > YOLO_FIT_CV2_BGR || value < 0 || value > 255) return NAN;
+    return fit_unit_value(fit, (unsigned)value);
 }
 
 // the timing entry points' events: destroyed on every return path
@@ -659,7 +810,7 @@ int yolo_autotune(yolo_ctx *c, int n, int iters)
             L.tail_on = b.second >= 0; L.tile_cfg = b.second >= 0 ? b.second : base_cfg[i];
         }
     }
-    if (c->gexec) { hipGraphExecDestroy(c->gexec); c->gexec = nullptr; } if (c->gstate > 0) c->gstate = 0;
+    drop_graph(c);
     return YOLO_OK;
 }
 
@@ -691,7 +842,7 @@ int yolo_set_tile_configs(yolo_ctx *c, const int32_t *cfgs)
         }
         c->layers[i].tile_cfg = v; c->layers[i].tail_on = tail;
     }
-    if (c->gexec) { hipGraphExecDestroy(c->gexec); c->gexec = nullptr; } if (c->gstate > 0) c->gstate = 0;
+    drop_graph(c);
     return YOLO_OK;
 }
 

@@ -22,7 +22,7 @@ class _Detector:
     flags = None
     select_mode = hip.SELECT_GT
 
-    def __init__(self, weights_file, verbose=False, dtype=hip.BF16, device=0, weights=None, max_output_size=None):
+    def __init__(self, weights_file, verbose=False, dtype=hip.BF16, device=0, weights=None, max_output_size=None, max_batch=1):
         f = self.flags
         self.verbose = verbose
         self.threshold, self.iou_threshold = f.conf_threshold, f.iou_threshold
@@ -33,7 +33,8 @@ class _Detector:
         text = IO.cfg_text(self.cfg)
         if self.input_size != int(IO.parse_cfg(text)[0]["width"]):
             text = IO.with_input_size(text, self.input_size)
-        self.engine = hip.Engine(text, max_batch=1, dtype=dtype, semantics=hip.SEM_TF, decode=hip.DECODE_RATIO, device=device)
+        self.max_batch = max_batch
+        self.engine = hip.Engine(text, max_batch=max_batch, dtype=dtype, semantics=hip.SEM_TF, decode=hip.DECODE_RATIO, device=device)
         if weights is not None:
             self.engine.set_weights(weights)
         else:
@@ -59,6 +60,19 @@ class _Detector:
                                     nms_mode=hip.NMS_TF, select_mode=self.select_mode)[0]
         boxes = np.stack([r["x0"], r["y0"], r["x1"], r["y1"]], -1).reshape(-1, 4)
         return r["score"], boxes, r["cls"]
+
+    def detect_from_images(self, images):
+        """A list of RGB uint8 [H,W,3] images of any sizes -> [(scores, boxes, classes)] per image, exactly what detect_from_image
+        returns for each (normalised boxes, as `detected_boxes:0`); the images run max_batch at a time, each chunk as ONE device step
+        (stretch fit, threshold and NMS of the whole chunk: Engine.detect_images)."""
+        out = []
+        for i in range(0, len(images), self.max_batch):
+            chunk = [np.ascontiguousarray(im, dtype=np.uint8) for im in images[i:i + self.max_batch]]
+            for r in self.engine.detect_images(chunk, fit=hip.FIT_STRETCH, units=hip.UNITS_NETWORK, score_thr=self.threshold,
+                                               iou_thr=self.iou_threshold, max_out=self.max_output_size, nms_mode=hip.NMS_TF,
+                                               select_mode=self.select_mode):
+                out.append((r["score"], np.stack([r["x0"], r["y0"], r["x1"], r["y1"]], -1).reshape(-1, 4), r["cls"]))
+        return out
 
     def detect_from_file(self, image_file, imshow=False, deteted_boxes_file="boxes.txt", detected_image_file=None):
         """(sic: `deteted_boxes_file` is the reference's spelling.)  Reads the image with PIL instead of OpenCV and

@@ -22,8 +22,16 @@ HOST, DEVICE = 0, 1
 IMG_U8, IMG_F32, IMG_F32_CHW = 0, 1, 2
 NMS_TF, NMS_PER_CLASS, NMS_DARKNET, NMS_NUMPY_V3, NMS_TF_V1 = 0, 1, 2, 3, 4
 SELECT_GT, SELECT_GE = 0, 1
+FIT_STRETCH, FIT_LETTERBOX, FIT_CV2, FIT_CV2_BGR = 0, 1, 2, 3
+UNITS_NETWORK, UNITS_SOURCE_PIXELS = 0, 1
 
 BOX_DTYPE = np.dtype([("x0", "<f4"), ("y0", "<f4"), ("x1", "<f4"), ("y1", "<f4"), ("score", "<f4"), ("cls", "<i4")])
+# yolo_image_desc: one image of a ragged batch, a uint8 RGB [h][w][3] image at byte `offset` of one packed buffer
+DESC_DTYPE = np.dtype([("offset", "<u8"), ("h", "<i4"), ("w", "<i4")])
+
+
+class ImageDesc(C.Structure):
+    _fields_ = [("offset", C.c_uint64), ("h", C.c_int32), ("w", C.c_int32)]
 
 EXPORTS = [
     "yolo_create", "yolo_destroy", "yolo_last_error", "yolo_load_darknet_weights", "yolo_set_weights",
@@ -34,6 +42,7 @@ EXPORTS = [
     "yolo_darknet_boxes", "yolo_last_layer_size", "yolo_last_layer_output", "yolo_op_letterbox",
     "yolo_op_maxpool", "yolo_op_resize_u8", "yolo_op_detections_boxes", "yolo_op_nms_detections", "yolo_forward_letterbox_chw", "yolo_op_decode", "yolo_op_postprocess",
     "yolo_postprocess_rows", "yolo_op_postprocess_rows", "yolo_last_layer_output_batch", "yolo_head_raw", "yolo_calibrate", "yolo_calibrate_copy", "yolo_op_resize_cv2",
+    "yolo_forward_images_u8", "yolo_detect_images_u8", "yolo_detect_images_graph", "yolo_fit_unit_value", "yolo_darknet_boxes_at",
 ]
 # include/yolo_dist.h: the image-sharded detect step
 DIST_EXPORTS = ["yolo_shard_bounds", "yolo_dist_flat_words", "yolo_dist_split_records", "yolo_dist_unique_id", "yolo_dist_create",
@@ -112,6 +121,12 @@ def load_library():
     l.yolo_calibrate.argtypes = [I, P, I, C.c_double, FP, FP]
     l.yolo_calibrate_copy.argtypes = [I, P, C.c_double, FP]
     l.yolo_op_resize_cv2.argtypes = [P, I, I, I, I, I, F, P, I]
+    SZ = C.c_size_t
+    l.yolo_forward_images_u8.argtypes = [P, P, SZ, P, I, I, I, P, I]
+    l.yolo_detect_images_u8.argtypes = [P, P, SZ, P, I, I, I, F, F, I, I, I, I, P, P, I]
+    l.yolo_detect_images_graph.argtypes = [P, P, SZ, P, I, I, F, F, I, I, I, I, P, P]
+    l.yolo_fit_unit_value.argtypes = [I, I]; l.yolo_fit_unit_value.restype = F
+    l.yolo_darknet_boxes_at.argtypes = [P, I, I, I, F, I, P, I, P]
     l.yolo_shard_bounds.argtypes = [I, I, I, C.POINTER(I), C.POINTER(I)]
     l.yolo_dist_flat_words.argtypes = [I, I]; l.yolo_dist_flat_words.restype = C.c_size_t
     l.yolo_dist_split_records.argtypes = [P, I, I, I, P, P]
@@ -149,6 +164,41 @@ def _op_check(rc, what):
 
 _warned_legacy = False
 HIP_STREAM_LEGACY = 1     # hipStreamLegacy: the explicit handle of the legacy NULL stream (hip_runtime_api.h)
+
+
+def pack_images(images):
+    """A list of uint8 RGB [h, w, 3] arrays of any sizes -> (packed uint8 buffer, DESC_DTYPE descriptors): the images back to back in
+    list order, each C-contiguous, offset = bytes of the images before it.  Pure host code; what yolo_*_images_* read."""
+    arrs = []
+    for i, im in enumerate(images):
+        a = np.ascontiguousarray(im)
+        if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.shape[0] < 1 or a.shape[1] < 1:
+            raise YoloError("image %d: need a uint8 [h, w, 3] array, got %s %s" % (i, a.dtype, a.shape))
+        arrs.append(a)
+    if not arrs:
+        raise YoloError("pack_images: no images")
+    descs = np.zeros(len(arrs), dtype=DESC_DTYPE)
+    off = 0
+    for i, a in enumerate(arrs):
+        descs[i] = (off, a.shape[0], a.shape[1])
+        off += a.size
+    buf = np.empty(off, dtype=np.uint8)
+    for a, d in zip(arrs, descs):
+        buf[int(d["offset"]):int(d["offset"]) + a.size] = a.reshape(-1)
+    return buf, descs
+
+
+def _descs(descs):
+    d = np.ascontiguousarray(descs)
+    if d.dtype != DESC_DTYPE:
+        d = np.ascontiguousarray(np.asarray(descs), dtype=DESC_DTYPE)
+    return d
+
+
+def fit_unit_value(fit, value):
+    """What one source byte contributes to a fit's arithmetic before interpolation (yolo_fit_unit_value): host evaluation of the
+    expression the fit kernel evaluates."""
+    return load_library().yolo_fit_unit_value(fit, value)
 
 
 def _stream_handle(stream):
@@ -345,6 +395,66 @@ class Engine:
         fmt = IMG_U8 if str(images.dtype).endswith("uint8") else IMG_F32
         self._check(self.lib.yolo_detect_graph(self.ctx, p, int(images.shape[0]), fmt, scale, score_thr, iou_thr, max_out,
                                                nms_mode, select_mode, bp, cp), "yolo_detect_graph")
+
+    # ---- ragged batches of native-size images ----
+    def _packed(self, images):
+        if isinstance(images, tuple):
+            buf, descs = images
+        else:
+            buf, descs = pack_images(images)
+        descs = _descs(descs)
+        p, loc = _ptr(buf)
+        nbytes = int(buf.numel()) if hasattr(buf, "numel") else int(buf.nbytes)
+        return buf, descs, p, loc, nbytes
+
+    def forward_images(self, images, fit=FIT_STRETCH, want_detections=True):
+        """A list of uint8 RGB [h, w, 3] images of any sizes (or a (buffer, descs) pair from pack_images, the buffer on the host or
+        the device) -> fitted on the device in one launch (`fit`), then forward.  Returns the decoded tensor [n, rows, attrs]."""
+        buf, descs, p, loc, nbytes = self._packed(images)
+        n = len(descs)
+        self._order_after_producer(buf)
+        det = np.empty((n, self.rows, self.attrs), dtype=np.float32) if want_detections else None
+        self._check(self.lib.yolo_forward_images_u8(self.ctx, p, nbytes, descs.ctypes.data, n, fit, loc,
+                                                    det.ctypes.data if det is not None else None, HOST), "yolo_forward_images_u8")
+        return det
+
+    def detect_images(self, images, fit=FIT_STRETCH, units=UNITS_NETWORK, score_thr=0.5, iou_thr=0.5, max_out=20, nms_mode=NMS_TF,
+                      select_mode=SELECT_GT):
+        """forward_images + threshold + NMS with each image's own geometry (yolo_detect_images_u8) -> list of BOX_DTYPE arrays."""
+        buf, descs, p, loc, nbytes = self._packed(images)
+        n = len(descs)
+        self._order_after_producer(buf)
+        boxes = np.zeros((n, max_out), dtype=BOX_DTYPE); counts = np.zeros(n, dtype=np.int32)
+        self._check(self.lib.yolo_detect_images_u8(self.ctx, p, nbytes, descs.ctypes.data, n, fit, loc, score_thr, iou_thr, max_out,
+                                                   nms_mode, select_mode, units, boxes.ctypes.data, counts.ctypes.data, HOST),
+                    "yolo_detect_images_u8")
+        return [boxes[i, :counts[i]].copy() for i in range(n)]
+
+    def detect_images_graph(self, pixels_dev, descs, boxes_out, counts_out, fit=FIT_STRETCH, units=UNITS_NETWORK, score_thr=0.5,
+                            iou_thr=0.5, max_out=20, nms_mode=NMS_TF, select_mode=SELECT_GT, nbytes=None):
+        """yolo_detect_images_graph: pixels_dev a device uint8 tensor holding the packed images, descs (host) where each one lies this
+        call; boxes_out / counts_out device tensors.  One captured graph serves every call with the same buffers and modes, whatever
+        the image sizes."""
+        p, loc = _ptr(pixels_dev); bp, bl = _ptr(boxes_out); cp, cl = _ptr(counts_out)
+        if loc != DEVICE or bl != DEVICE or cl != DEVICE:
+            raise YoloError("detect_images_graph needs device-resident buffers")
+        descs = _descs(descs)
+        if nbytes is None:
+            nbytes = int(pixels_dev.numel())
+        self._order_after_producer(pixels_dev, boxes_out, counts_out)
+        self._check(self.lib.yolo_detect_images_graph(self.ctx, p, nbytes, descs.ctypes.data, len(descs), fit, score_thr, iou_thr,
+                                                      max_out, nms_mode, select_mode, units, bp, cp), "yolo_detect_images_graph")
+
+    def darknet_boxes(self, image, w, h, thresh=0.5, relative=1, cap=None):
+        """darknet's get_network_boxes over image `image` of the last forward (yolo_darknet_boxes_at) -> records [count, 5 + classes]
+        (x, y, w, h, objectness, prob[classes]), un-letterboxed for a w x h source image."""
+        cnt = C.c_int(0)
+        self._check(self.lib.yolo_darknet_boxes_at(self.ctx, image, w, h, thresh, relative, None, 0, C.byref(cnt)), "yolo_darknet_boxes_at")
+        cap = cnt.value if cap is None else cap
+        rec = np.zeros((max(cap, 1), self.attrs), dtype=np.float32)
+        self._check(self.lib.yolo_darknet_boxes_at(self.ctx, image, w, h, thresh, relative, rec.ctypes.data, cap, C.byref(cnt)),
+                    "yolo_darknet_boxes_at")
+        return rec[:min(cnt.value, cap)]
 
     def synchronize(self):
         self._check(self.lib.yolo_synchronize(self.ctx), "yolo_synchronize")
