@@ -335,6 +335,30 @@ int yolo_op_postprocess_rows(const float *det, int n, int rows, int attrs, float
                              int max_out, int nms_mode, int select_mode, yolo_box *boxes_out,
                              int32_t *counts_out, int32_t *rows_out, int device);
 
+/* ---- classifier networks (darknet.py `classify`, D2T/darknet.py:117-123) ------------------------------------------------------
+ * A cfg without a detection head whose output layer -- the last layer that is not [cost] -- is a [softmax] plans a CLASSIFIER
+ * context: [avgpool] (global), [softmax] (keys groups, temperature) and [cost] (identity) are served in the fp32, bf16, fp16 and
+ * split-fp16 configurations; the logits stay fp32.  For such a context yolo_num_rows / yolo_num_attrs are 0, yolo_last_layer_output*
+ * returns the probabilities, and the detection entry points (yolo_postprocess*, yolo_detect*, yolo_head_raw, yolo_darknet_boxes*)
+ * return YOLO_ERR_INVALID. */
+/* outputs of the [softmax] layer of a classifier context; for a detector, attrs - 5 */
+int yolo_num_classes(const yolo_ctx *ctx);
+/* yolo_forward's image arguments, then the tail.  top_k == 0: probs_out receives the n x classes probability matrix (classes_out
+ * is not written).  0 < top_k <= min(32, classes), a [softmax] with groups=1: the [softmax] launch itself selects, and only n x top_k
+ * records are copied: classes_out / probs_out [n][top_k], probability descending, equal probabilities by ascending class (the order
+ * of classify()'s stable sort by -prob).  out_loc: where classes_out / probs_out live. */
+int yolo_classify(yolo_ctx *ctx, const void *images, int n, int fmt, int loc, float scale, int top_k,
+                  int32_t *classes_out, float *probs_out, int out_loc);
+/* ... over a ragged batch of native-size images through the one-launch fit of yolo_forward_images_u8 */
+int yolo_classify_images_u8(yolo_ctx *ctx, const uint8_t *pixels, size_t bytes, const yolo_image_desc *descs, int n, int fit, int loc,
+                            int top_k, int32_t *classes_out, float *probs_out, int out_loc);
+/* darknet's [avgpool] on x [n,h,w,c] fp32 stored as `dtype` (YOLO_FP32 / BF16 / FP16 / FP16X2) first: out [n,c] fp32 */
+int yolo_op_avgpool(const float *x, int n, int h, int w, int c, int dtype, float *out, int device);
+/* darknet's [softmax] on x [n][len] fp32, `groups` equal runs per row: probs_out [n][len]; top_k > 0 (groups == 1, <= 32): also
+ * classes_out / topk_probs_out [n][top_k] from the same launch (else NULL) */
+int yolo_op_softmax(const float *x, int n, int len, int groups, float temperature, int top_k, float *probs_out,
+                    int32_t *classes_out, float *topk_probs_out, int device);
+
 #ifdef __cplusplus
 }
 #endif

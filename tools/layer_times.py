@@ -1,5 +1,5 @@
-"""Per-layer device time of a configuration at its committed tile plan: python tools/layer_times.py [dtype=bf16] [batch=32] [size=416]
-Prints layer, shape, tile configuration, microseconds, GFLOP and algorithmic TFLOP/s; sums per class of layer."""
+"""Per-layer device time of a configuration at its committed tile plan: python tools/layer_times.py [dtype=bf16] [batch=32] [size=416] [cfg=yolov3]
+(cfg: any shipped topology, e.g. darknet53 at 256 for the classifier and its tail launches).  Prints layer, shape, tile configuration, microseconds, GFLOP and algorithmic TFLOP/s; sums per class of layer."""
 import os, sys, json
 import numpy as np
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
@@ -8,12 +8,13 @@ from yolo_tensorflow_amd import hip, darknet_io as IO
 dtype = sys.argv[1] if len(sys.argv) > 1 else "bf16"
 B = int(sys.argv[2]) if len(sys.argv) > 2 else 32
 size = int(sys.argv[3]) if len(sys.argv) > 3 else 416
-txt = IO.with_input_size(IO.cfg_text("yolov3"), size); secs = IO.parse_cfg(txt); sh = IO.layer_shapes(secs)
+name = sys.argv[4] if len(sys.argv) > 4 else "yolov3"
+txt = IO.with_input_size(IO.cfg_text(name), size); secs = IO.parse_cfg(txt); sh = IO.layer_shapes(secs)
 DT = {"bf16": hip.BF16, "fp16": hip.FP16, "fp16x2": hip.FP16X2, "fp8": hip.FP8, "fp32": hip.FP32}[dtype]
 eng = hip.Engine(txt, max_batch=B, dtype=DT); eng.set_weights(IO.synth_weights(secs, 0))
 img = np.random.default_rng(0).integers(0, 256, (B, size, size, 3), dtype=np.uint8)
 eng.forward(img, want_detections=False)
-pf = os.environ.get("PLAN") or os.path.join(ROOT, "yolo_tensorflow_amd", "tuned", "yolov3_%d_b%d_%s.json" % (size, B, "bf16" if dtype == "fp16" else dtype))
+pf = os.environ.get("PLAN") or os.path.join(ROOT, "yolo_tensorflow_amd", "tuned", "%s_%d_b%d_%s.json" % (name, size, B, "bf16" if dtype == "fp16" else dtype))
 plan = [-1] * eng.num_layers
 if os.path.exists(pf):
     plan = json.load(open(pf))["cfgs"]; eng.set_tile_configs(plan)

@@ -7,6 +7,9 @@ reference's layer tables and TF graph builders:
   yolov3-tiny     D2T/YOLO_V3_Tiny_convert_darkenet_to_Tensorflow.py:376-465 (anchors :29)
   yolov2          V2/yolov2.txt:2-32   == V2/model_darknet19_slim.py:119-200 (anchors V2/config.py:7-11)
   yolov2-tiny-voc D2T/YOLO_V2_Tiny_Voc_convert_darkenet_to_Tensorflow.py:162-225
+  darknet19 / darknet53
+                  the classifiers those two backbones are (cfg layers 0-22 of yolov2 / 0-74 of yolov3, same tables) with the tail the
+                  reference's parser reads: [avgpool] (DN/parser.c:493-507), [softmax] (:268-280), 1000 classes, 256 x 256
   yolov1          V1/YOLO_V1_Inference.py:124-210 (`_build_network`: 24 bias convs, 7x7/2 first, four SAME pools, CHW flatten,
                   FC 50176 -> 512 -> 4096 -> 1470) + :213-270 ([detection]: side 7, 2 boxes, 20 classes, sqrt sizes); the two
                   `yolo_input_*` keys of [net] state its input normalisation (x/255)*2-1 (:67-71) for the HIP planner (darknet ignores them)
@@ -80,6 +83,18 @@ class Cfg:
         return self._sec("detection", classes=classes, coords=4, rescore=1, side=side, num=num, softmax=0, sqrt=1,
                          jitter=.2, object_scale=1, noobject_scale=.5, class_scale=1, coord_scale=5)
 
+    def avgpool(self):
+        return self._sec("avgpool")
+
+    def softmax(self, groups=1, temperature=None):
+        kv = {"groups": groups}
+        if temperature is not None:
+            kv["temperature"] = temperature
+        return self._sec("softmax", **kv)
+
+    def cost(self):
+        return self._sec("cost")        # (type defaults to sse, DN/parser.c:419)
+
     def text(self):
         return "\n".join(self.lines)
 
@@ -90,8 +105,8 @@ V2_ANCHORS = [(0.57273, 0.677385), (1.87446, 2.06253), (3.33843, 5.47434), (7.88
 V2_TINY_VOC_ANCHORS = [(1.08, 1.19), (3.42, 4.41), (6.63, 11.38), (9.42, 5.11), (16.62, 10.52)]
 
 
-def yolov3(size=416, classes=80):
-    c = Cfg(size)
+def darknet53_backbone(c):
+    """cfg layers 0-74 of yolov3: the stem conv and the five residual stages; -> the two layers the detector routes back to."""
     c.conv(32, 3)
 
     def stage(filters, blocks):
@@ -105,6 +120,12 @@ def yolov3(size=416, classes=80):
     stage(512, 8)
     route_2 = c.n - 1           # 61
     stage(1024, 4)
+    return route_1, route_2
+
+
+def yolov3(size=416, classes=80):
+    c = Cfg(size)
+    route_1, route_2 = darknet53_backbone(c)
 
     def yolo_block(f):
         for _ in range(2):
@@ -143,8 +164,8 @@ def yolov3_tiny(size=416, classes=80):
     return c.text()
 
 
-def yolov2(size=416, classes=80):
-    c = Cfg(size)
+def darknet19_backbone(c):
+    """cfg layers 0-22 of yolov2: the eighteen backbone convs and their five pools; -> the layer the detector's passthrough reads."""
     c.conv(32, 3); c.maxpool()
     c.conv(64, 3); c.maxpool()
     c.conv(128, 3); c.conv(64, 1); c.conv(128, 3); c.maxpool()
@@ -153,6 +174,12 @@ def yolov2(size=416, classes=80):
     sc = c.conv(512, 3)         # 16
     c.maxpool()
     c.conv(1024, 3); c.conv(512, 1); c.conv(1024, 3); c.conv(512, 1); c.conv(1024, 3)
+    return sc
+
+
+def yolov2(size=416, classes=80):
+    c = Cfg(size)
+    sc = darknet19_backbone(c)
     c.conv(1024, 3)
     main = c.conv(1024, 3)      # 24
     c.route(sc)
@@ -207,6 +234,27 @@ def yolov1_tiny(size=448, classes=20):
     return c.text()
 
 
+def darknet53(size=256, classes=1000):
+    """The ImageNet classifier the yolov3 backbone was trained as: layers 0-74, global average pool, a 1x1 conv to the classes
+    (linear, no batch norm) and the softmax."""
+    c = Cfg(size)
+    darknet53_backbone(c)
+    c.avgpool()
+    c.conv(classes, 1, bn=False, act="linear")
+    c.softmax()
+    return c.text()
+
+
+def darknet19(size=256, classes=1000):
+    """... and the yolov2 backbone's: layers 0-22, the 1x1 conv to the classes on the last feature map, global average pool, softmax."""
+    c = Cfg(size)
+    darknet19_backbone(c)
+    c.conv(classes, 1, bn=False, act="linear")
+    c.avgpool()
+    c.softmax()
+    return c.text()
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     files = {
@@ -214,6 +262,7 @@ def main():
         "yolov3.cfg": yolov3(416), "yolov3-608.cfg": yolov3(608),
         "yolov3-tiny.cfg": yolov3_tiny(416),
         "yolov2.cfg": yolov2(416), "yolov2-tiny-voc.cfg": yolov2_tiny_voc(416),
+        "darknet19.cfg": darknet19(256), "darknet53.cfg": darknet53(256),
     }
     for name, text in files.items():
         with open(os.path.join(OUT, name), "w") as f:

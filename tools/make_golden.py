@@ -13,6 +13,9 @@ Runs only in the build container (it reads /root/reference and oracle/_ref); the
                      an input image, EVERY layer output, and the boxes after get_network_boxes /
                      do_nms_sort -- produced by the reference's own C code compiled CPU-only
                      (oracle/Makefile -> oracle/_ref/libdarknet_ref.so)
+  mini_cls53.npz / mini_cls19.npz
+                     two small classifier topologies ([avgpool], [softmax], [cost]; darknet-53's and darknet-19's tail order), every
+                     layer output and the probability vector, from the same compiled reference
   yolov3_bn_real.npz / yolov2_bn_real.npz
                      the COMPLETE batch-norm vectors (beta, gamma, rolling mean, rolling variance) of every
                      batch-normalised conv of yolov3.weights / yolov2.weights, and the first l.n filter
@@ -468,6 +471,50 @@ def gen_mini(name, cfg, classes, nms_thresh=0.3, thresh=0.15):
     net.close()
 
 
+def _conv(filters, size, stride=1, bn=True, act="leaky"):
+    return "[convolutional]\n%sfilters=%d\nsize=%d\nstride=%d\npad=1\nactivation=%s\n\n" % ("batch_normalize=1\n" if bn else "", filters, size, stride, act)
+
+
+_CLS_NET = "[net]\nbatch=1\nwidth=64\nheight=64\nchannels=3\n\n"
+# darknet-53's tail order: ... -> [avgpool] -> 1x1 conv to the classes -> [softmax] (here with groups and a temperature) -> [cost]
+MINI_CLS53 = (_CLS_NET + _conv(8, 3) + _conv(16, 3, 2) + _conv(8, 1) + _conv(16, 3) + "[shortcut]\nfrom=-3\nactivation=linear\n\n" + _conv(32, 3, 2) +
+              "[avgpool]\n\n" + _conv(24, 1, bn=False, act="linear") + "[softmax]\ngroups=2\ntemperature=2\n\n[cost]\n")
+# darknet-19's: ... -> 1x1 conv to the classes -> [avgpool] -> [softmax]
+MINI_CLS19 = (_CLS_NET + _conv(8, 3) + "[maxpool]\nsize=2\nstride=2\n\n" + _conv(16, 3) + _conv(8, 1) + _conv(16, 3) + "[shortcut]\nfrom=-3\nactivation=linear\n\n" +
+              "[maxpool]\nsize=2\nstride=2\n\n" + _conv(32, 3) + _conv(24, 1, bn=False, act="linear") + "[avgpool]\n\n[softmax]\ngroups=1\n")
+
+
+def gen_mini_cls():
+    """Two small classifier topologies, one of each tail order, through the compiled reference (avgpool_layer.c, softmax_layer.c,
+    cost_layer.c): every layer output and the vector network_predict returns (the last layer that is not [cost]).  The last conv's
+    parameters are scaled so that the reference's logits reach +-5: the probabilities must not be a near-uniform distribution."""
+    from oracle import darknet_ref as D
+    from yolo_tensorflow_amd import darknet_io as IO
+    for name, cfg, seed, logit_layer in (("mini_cls53", MINI_CLS53, 21, 7), ("mini_cls19", MINI_CLS19, 23, 8)):
+        secs = IO.parse_cfg(cfg)
+        flat = IO.synth_weights(secs, seed=seed)
+        last = IO.conv_specs(secs)[-1]
+        tail = last["filters"] * (1 + last["cin"] * last["size"] ** 2)          # bias + filters of the (linear, bias-only) last conv
+        img = np.random.default_rng(seed + 1).integers(0, 256, (64, 64, 3), dtype=np.uint8)
+        x = img.astype(np.float32) / np.float32(255.0)
+        net = D.RefNet(cfg, flat, 0, 2)
+        net.predict(x)
+        factor = np.float32(round(5.0 / float(np.abs(net.layer_output_nhwc(logit_layer)).max()), 2))
+        net.close()
+        flat[-tail:] *= factor
+        net = D.RefNet(cfg, flat, 0, 2)
+        net.predict(x)
+        data = {"cfg": np.array(cfg), "weights": flat, "image_u8": img, "header": np.array([0, 2])}
+        for i in range(net.n):
+            data["layer_%02d" % i] = np.asarray(net.layer_output_nhwc(i), dtype=np.float32)
+        out_layer = max(i for i in range(net.n) if secs[i + 1]["type"] != "cost")
+        data["output"] = np.asarray(data["layer_%02d" % out_layer], dtype=np.float32).reshape(-1)
+        data["max_abs_logit"] = np.float32(np.abs(data["layer_%02d" % logit_layer]).max())
+        np.savez_compressed(os.path.join(OUT, name + ".npz"), **data)
+        print(name, "layers", net.n, "max|logit|", float(data["max_abs_logit"]), "p max/min", float(data["output"].max()), float(data["output"].min()))
+        net.close()
+
+
 def gen_bn_real():
     """D2T/log.txt is the reference's stdout of two detect runs (yolov2 then yolov3) with the printf block of DN/parser.c:1176-1228
     enabled: per batch-normalised conv five lines of numbers (beta, gamma, rolling mean, rolling variance -- l.n values each -- and the
@@ -550,6 +597,7 @@ if __name__ == "__main__":
     gen_mini("mini_v2", MINI_V2, 5)
     gen_mini_v1()
     gen_mini_local()
+    gen_mini_cls()
     gen_bn_real()
     gen_known_answers()
     gen_darknet_py_symbols()

@@ -1,0 +1,48 @@
+"""Classifier networks (darknet-19, darknet-53, any cfg that ends in [softmax]): "Darknet weights in, top classes out".
+
+Counterpart of what the reference's ctypes binding does with such a network (`classify`, D2T/darknet.py:117-123: predict, pair every
+probability with its name, sort by -prob), with the pooling, the softmax and the selection of the top classes on the device: uint8
+images of any sizes are fitted to the network input in one launch, and only `top` records per image come back."""
+import numpy as np
+from . import hip, darknet_io as IO
+
+
+class Classifier:
+    def __init__(self, cfg_or_name, weights_file=None, dtype=hip.BF16, max_batch=1, names=None, device=0, fit=hip.FIT_STRETCH, seed=0):
+        """cfg_or_name: a shipped topology ('darknet19', 'darknet53'), a cfg file path, or cfg text.  weights_file: a darknet
+        `.weights` file; None loads darknet_io's seeded synthetic parameters (`seed`).  names: a list of class names or the path of a
+        file with one name per line; without it the class index stands in for the name."""
+        text = cfg_or_name if "[net]" in cfg_or_name or "[network]" in cfg_or_name else IO.cfg_text(cfg_or_name)
+        self.engine = hip.Engine(text, max_batch=max_batch, dtype=dtype, semantics=hip.SEM_DARKNET, device=device)
+        if self.engine.rows != 0:
+            self.engine.close()
+            raise hip.YoloError("Classifier: the cfg describes a detector (it has a detection head)")
+        if weights_file is not None:
+            self.engine.load_weights(weights_file)
+        else:
+            self.engine.set_weights(IO.synth_weights(IO.parse_cfg(text), seed=seed))
+        self.max_batch, self.fit = max_batch, fit
+        self.num_classes = self.engine.num_classes
+        if isinstance(names, str):
+            with open(names) as fh:
+                names = [line.rstrip("\r\n") for line in fh]
+        self.names = list(names) if names is not None else None
+
+    def _name(self, k):
+        return self.names[k] if self.names is not None and 0 <= k < len(self.names) else int(k)
+
+    def classify_from_images(self, images, top=5):
+        """images: a list of RGB uint8 [h, w, 3] arrays of any sizes -> per image [(name_or_index, prob), ...], `top` entries,
+        probability descending."""
+        out = []
+        for lo in range(0, len(images), self.max_batch):
+            cls, probs = self.engine.classify_images(images[lo:lo + self.max_batch], fit=self.fit, top_k=top)
+            for c, p in zip(cls, probs):
+                out.append([(self._name(int(k)), float(q)) for k, q in zip(c, p)])
+        return out
+
+    def classify_from_image(self, image, top=5):
+        return self.classify_from_images([np.ascontiguousarray(image, dtype=np.uint8)], top=top)[0]
+
+    def close(self):
+        self.engine.close()

@@ -103,7 +103,8 @@ void set_batch_network(network *net, int b)
     yolo_destroy(prev);
 }
 
-// `input`: batch x planar [3][h][w] at network size.  Returns net->output: the last layer's output of every image of the batch,
+// `input`: batch x planar [3][h][w] at network size.  Returns net->output: the last layer's output of every image of the batch
+// (a classifier cfg: the probabilities of its [softmax] layer, what darknet.py's classify() reads),
 // image after image (batch * outputs floats, DN/network.c:497-508), see include/darknet_hip.h.
 float *network_predict(network *net, float *input)
 {
@@ -130,6 +131,7 @@ detection *make_network_boxes(network *net, float thresh, int *num)
 {
     if (num) *num = 0;
     if (!net || !net->have) return nullptr;
+    if (net->rows == 0) return (detection *)calloc(1, sizeof(detection));      // a classifier: no boxes (DN/network.c:510-524 counts the detection layers)
     int count = 0;
     if (yolo_darknet_boxes(net->ctx, net->w, net->h, thresh, 1, nullptr, 0, &count) != YOLO_OK) { fprintf(stderr, "darknet_hip: %s\n", yolo_last_error(net->ctx)); return nullptr; }
     const int C = net->attrs - 5;
@@ -146,6 +148,7 @@ detection *get_network_boxes(network *net, int w, int h, float thresh, float hie
     (void)hier; (void)map;
     if (num) *num = 0;
     if (!net || !net->have) return nullptr;
+    if (net->rows == 0) return (detection *)calloc(1, sizeof(detection));      // a classifier: no boxes
     const int A = net->attrs, C = A - 5;
     net->rec.resize((size_t)net->rows * A);
     int count = 0;

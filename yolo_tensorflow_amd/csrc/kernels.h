@@ -248,6 +248,27 @@ hipError_t launch_split_to_f32(const void *in, int in_stride, int Cp, float *out
 hipError_t launch_upsample2x_pair(const TView &in, const TView &out, int bilinear, hipStream_t s);      // 2x upsample of an interleaved pair tensor (join, fp32 lerp, split) in one launch
 hipError_t launch_add_split(const void *a, int a_stride, const void *b, int b_stride, void *out, int out_stride, int Cp, size_t npix, hipStream_t s);      // shortcut on interleaved pair tensors
 
+// ---- classifier tail (cls_ops.hip) ---------------------------------------------------------------
+// darknet's [avgpool] (always global, DN/avgpool_layer.c:40-55): in [n, h, w, c] -> out [n, 1, 1, c] in the same tensor form (bf16 /
+// fp16 / fp32, or interleaved split-fp16 pairs with in_pair); fp32 sums, then / (h * w).  Both views may be channel windows.
+hipError_t launch_avgpool(const TView &in, bool in_pair, const TView &out, hipStream_t s);
+#define CLS_SOFTMAX_MAX 8192          // logits of one softmax group (staged in LDS once)
+#define CLS_TOPK_MAX 32
+// darknet's [softmax] (DN/blas.c:305-321) over x [n][x_stride] fp32, `groups` runs of `len` logits per image -> probs [n][p_stride];
+// top_k > 0 (groups == 1): the same launch also writes the top_k best of every image to cls / topk_probs [n][top_k], probability
+// descending, equal probabilities by ascending class (the order of a stable sort by -prob); slots past `len`: class -1, probability 0
+struct SoftmaxArgs {
+    const float *x; int x_stride;
+    int n, groups, len; float temperature;
+    float *probs; int p_stride;
+    int top_k; int *cls; float *topk_probs;
+};
+hipError_t launch_softmax_topk(const SoftmaxArgs &a, hipStream_t s);
+// [avgpool] of an fp32 tensor followed by [softmax] in ONE launch (a.x / a.x_stride are not read: the logits are the pooled `in`);
+// the pooled vector is also written to pooled [n][pooled_stride]
+bool avgpool_softmax_ok(const TView &in, const SoftmaxArgs &a);
+hipError_t launch_avgpool_softmax(const TView &in, float *pooled, int pooled_stride, const SoftmaxArgs &a, hipStream_t s);
+
 // ---- head decode + postprocess (post_ops.hip) ---------------------------------------------------
 struct DecodeArgs {
     const float *raw; int raw_stride;   // [n, g*g, raw_stride] fp32 head conv output

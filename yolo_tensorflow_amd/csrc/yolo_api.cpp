@@ -36,7 +36,7 @@ void yolo_destroy(yolo_ctx *c)
     for (void *p : c->phys) if (p) hipFree(p);
     for (auto &L : c->layers) { if (L.d_w) hipFree(L.d_w); if (L.d_b) hipFree(L.d_b); if (L.d_sc) hipFree(L.d_sc); if (L.d_wf) hipFree(L.d_wf); if (L.d_obj) hipFree(L.d_obj); }
     void *ptrs[] = {c->input.ptr, c->d_zeros, c->d_stage, c->d_det, c->d_scores, c->d_labels, c->d_cand, c->d_keys, c->d_sbox, c->d_slabel, c->d_sscore, c->d_boxes, c->d_counts,
-                    c->d_dn_rec, c->d_dn_src, c->d_dn_count, c->d_dn_last, c->d_box4, c->s2d.ptr, c->d_srow, c->d_rows, c->d_lean_list, c->d_lean_cnt, c->d_f32a, c->d_f32b, c->d_descs, c->d_pix};
+                    c->d_dn_rec, c->d_dn_src, c->d_dn_count, c->d_dn_last, c->d_box4, c->s2d.ptr, c->d_srow, c->d_rows, c->d_lean_list, c->d_lean_cnt, c->d_f32a, c->d_f32b, c->d_descs, c->d_pix, c->d_cls_idx, c->d_cls_prob};
     for (void *p : ptrs) if (p) hipFree(p);
     if (c->gexec) hipGraphExecDestroy(c->gexec);
     if (c->gexec_img) hipGraphExecDestroy(c->gexec_img);
@@ -51,6 +51,7 @@ size_t yolo_weights_count(const yolo_ctx *c) { return c ? c->weights_count : 0; 
 int yolo_input_size(const yolo_ctx *c, int *h, int *w, int *ch) { if (!c) return YOLO_ERR_INVALID; if (h) *h = c->in_h; if (w) *w = c->in_w; if (ch) *ch = c->in_c; return YOLO_OK; }
 int yolo_num_rows(const yolo_ctx *c) { return c ? c->rows : YOLO_ERR_INVALID; }
 int yolo_num_attrs(const yolo_ctx *c) { return c ? c->attrs : YOLO_ERR_INVALID; }
+int yolo_num_classes(const yolo_ctx *c) { return !c ? YOLO_ERR_INVALID : c->cls_layer >= 0 ? c->layers[c->cls_layer].C : c->attrs - 5; }
 int yolo_num_layers(const yolo_ctx *c) { return c ? (int)c->layers.size() : YOLO_ERR_INVALID; }
 int yolo_head_geometry(const yolo_ctx *c, int head, int *kind, int *grid, int *anchors, int *row_offset)
 {
@@ -91,6 +92,7 @@ int yolo_darknet_boxes(yolo_ctx *c, int w, int h, float thresh, int relative, fl
 int yolo_darknet_boxes_at(yolo_ctx *c, int image, int w, int h, float thresh, int relative, float *records, int cap, int *count)
 {
     if (!c || !count) return YOLO_ERR_INVALID;
+    if (int r = need_detector(c, "yolo_darknet_boxes")) return r;
     if (c->last_n < 1 || !c->det_valid) return fail(c, YOLO_ERR_STATE, "yolo_darknet_boxes needs a yolo_forward* pass first");
     if (image < 0 || image >= c->last_n) return fail(c, YOLO_ERR_INVALID, "image %d outside the last forward's batch of %d", image, c->last_n);
     if (w < 1 || h < 1 || cap < 0 || (cap > 0 && !records)) return fail(c, YOLO_ERR_INVALID, "bad image size / capacity");
@@ -130,6 +132,7 @@ int yolo_darknet_boxes_at(yolo_ctx *c, int image, int w, int h, float thresh, in
 size_t yolo_last_layer_size(const yolo_ctx *c)
 {
     if (!c) return 0;
+    if (c->cls_layer >= 0) return (size_t)c->layers[c->cls_layer].C;      // the [softmax] layer's probabilities
     for (int i = (int)c->layers.size() - 1; i >= 0; --i) {
         const Layer &L = c->layers[i];
         if (L.type == L_DETECT) return (size_t)L.side * L.side * (L.classes + 5 * L.na);      // the layer copies its input (DN/detection_layer.c:50-57)
@@ -143,7 +146,13 @@ int yolo_last_layer_output_batch(yolo_ctx *c, int n, float *out, size_t out_floa
     if (!c || !out) return YOLO_ERR_INVALID;
     if (c->last_n < 1) return fail(c, YOLO_ERR_STATE, "yolo_last_layer_output before a forward pass");
     if (n < 1 || n > c->last_n) return fail(c, YOLO_ERR_INVALID, "yolo_last_layer_output of %d images but the last forward ran %d", n, c->last_n);
-    const int li = (int)c->layers.size() - 1;
+    if (c->cls_layer >= 0) {             // a classifier: the dense [n][classes] probabilities of its [softmax] layer
+        const Layer &S = c->layers[c->cls_layer];
+        if (out_floats < (size_t)n * S.C) return fail(c, YOLO_ERR_INVALID, "output buffer too small (%zu < %zu floats)", out_floats, (size_t)n * S.C);
+        HIPCK(c, hipSetDevice(c->device));
+        return copy_out(c, out, S.out.ptr, (size_t)n * S.C * 4, YOLO_HOST);
+    }
+    const int li = output_layer(c);
     if (li < 1 || (c->layers[li].type != L_YOLO && c->layers[li].type != L_REGION && c->layers[li].type != L_DETECT))
         return fail(c, YOLO_ERR_UNSUPPORTED, "the last layer is not a detection head");
     const Layer &L = c->layers[li]; const Layer &P = c->layers[li - 1];
@@ -172,6 +181,7 @@ int yolo_last_layer_output(yolo_ctx *c, float *out, size_t out_floats) { return 
 int yolo_head_raw(yolo_ctx *c, int head, int n, float *out, size_t out_floats)
 {
     if (!c || !out || head < 0) return YOLO_ERR_INVALID;
+    if (int r = need_detector(c, "yolo_head_raw")) return r;
     if (c->last_n < 1 || n < 1 || n > c->last_n) return fail(c, YOLO_ERR_STATE, "yolo_head_raw of %d images but the last forward ran %d", n, c->last_n);
     int k = 0;
     for (size_t li = 1; li < c->layers.size(); ++li) {

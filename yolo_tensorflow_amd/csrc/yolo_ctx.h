@@ -18,7 +18,7 @@
 
 namespace yolo_impl {
 
-enum LType { L_CONV, L_SHORTCUT, L_ROUTE, L_UPSAMPLE, L_MAXPOOL, L_REORG, L_YOLO, L_REGION, L_DETECT, L_LOCAL };
+enum LType { L_CONV, L_SHORTCUT, L_ROUTE, L_UPSAMPLE, L_MAXPOOL, L_REORG, L_YOLO, L_REGION, L_DETECT, L_LOCAL, L_AVGPOOL, L_SOFTMAX };
 
 struct Section { std::string type; std::map<std::string, std::string> kv; };
 
@@ -63,6 +63,9 @@ struct Layer {
     // head
     int na = 0, classes = 0, row_off = 0;
     std::vector<float> anchors;          // masked, in reference units
+    // classifier tail: [softmax] keys; an [avgpool] whose fp32 input is pooled inside the launch of the [softmax] behind it (cls_ops.hip);
+    // `cost`: a [cost] section (inference identity, never the network's output)
+    int groups = 1; float temperature = 1.f; bool pool_fused = false; bool cost = false;
     // storage
     int storage = -1; int ch_off = 0;    // view = storage buffer + channel offset
     TView out;
@@ -90,6 +93,9 @@ struct yolo_ctx {
     const uint8_t *stem_u8 = nullptr; float stem_scale = 1.f; int stem_u8_n = 0;      // uint8 image (of stem_u8_n images) the fused stem reads itself (no conversion launch), or nullptr: c->input.  May be the CALLER's buffer: only valid for a pass over <= stem_u8_n images while the caller keeps it (yolo_time_*)
     float in_mul = 1.f, in_add = 0.f;     // input normalisation after the /255: v * in_mul + in_add ([net] yolo_input_mul / yolo_input_add)
     float *d_det = nullptr; int rows = 0, attrs = 0;
+    // classifier context: no detection head, the output layer (the last one that is not [cost]) is a [softmax].  cls_layer: that layer
+    // (-1: a detector); cls_topk: what the next forward's [softmax] launch selects (yolo_classify*), into d_cls_idx / d_cls_prob [max_batch][32]
+    int cls_layer = -1, cls_topk = 0; int *d_cls_idx = nullptr; float *d_cls_prob = nullptr;
     // lean detect path (yolo_detect*): the decode writes scores, labels and the four box numbers of every row, not the tensor
     bool lean_cnt_dirty = false;
     void *d_lean_list = nullptr; unsigned *d_lean_cnt = nullptr;      // lean decode: list of the boxes that pass the objectness pre-filter + its counters
@@ -170,6 +176,8 @@ int run_layer(yolo_ctx *c, int i, int n);
 int stage_in(yolo_ctx *c, const void *images, int n, int fmt, int loc, float scale);
 int run_network(yolo_ctx *c, int n, bool lean = false);
 int copy_out(yolo_ctx *c, void *dst, const void *src, size_t bytes, int loc);
+int output_layer(const yolo_ctx *c);      // the network's output: the last layer that is not [cost] (DN/network.c:699-706)
+int need_detector(yolo_ctx *c, const char *what);      // YOLO_ERR_INVALID with a message for a classifier context
 int post_args_ok(yolo_ctx *c, int max_out, int nms_mode, int select_mode);
 struct PostGeom { int fit, pixels; };      // per-image box mapping of a ragged batch (yolo_box_units), over c->d_descs
 int post(yolo_ctx *c, const float *det, int n, int rows, int attrs, float score_thr, float iou_thr, int max_out,

@@ -189,6 +189,54 @@ int yolo_op_upsample2x(const float *x, int n, int h, int w, int c, int semantics
 int yolo_op_reorg(const float *x, int n, int h, int w, int c, int stride, int semantics, float *out, int device) { return ew_op(1, x, n, h, w, c, stride, semantics, 0, out, device); }
 int yolo_op_maxpool(const float *x, int n, int h, int w, int c, int size, int stride, float *out, int device) { return ew_op(2, x, n, h, w, c, size, stride, 0, out, device); }
 
+int yolo_op_avgpool(const float *x, int n, int h, int w, int c, int dtype, float *out, int device)
+{
+    if (!x || !out || n < 1 || h < 1 || w < 1 || c < 1) { g_op_err = "avgpool: bad arguments"; return YOLO_ERR_INVALID; }
+    if (dtype != YOLO_FP32 && dtype != YOLO_BF16 && dtype != YOLO_FP16 && dtype != YOLO_FP16X2) { g_op_err = "avgpool: dtype (fp32, bf16, fp16 or fp16x2)"; return YOLO_ERR_UNSUPPORTED; }
+    OpScope S(device); if (S.rc) { g_op_err = "avgpool: no HIP device"; return S.rc; }
+    const size_t npix = (size_t)n * h * w;
+    float *d_o32 = (float *)S.alloc((size_t)n * c * 4);
+    bool ok;
+    if (dtype == YOLO_FP16X2) {          // fp32 padded to whole 32-channel groups -> interleaved pairs -> pool -> joined again
+        const int cp = roundup(c, 32);
+        float *d_x32 = (float *)S.alloc(npix * cp * 4), *d_j = (float *)S.alloc((size_t)n * cp * 4);
+        void *d_x = S.alloc(npix * 2 * cp * 2), *d_o = S.alloc((size_t)n * 2 * cp * 2);
+        if (S.rc) { g_op_err = "avgpool: allocation failed"; return S.rc; }
+        ok = S.ok(hipMemcpy2DAsync(d_x32, (size_t)cp * 4, x, (size_t)c * 4, (size_t)c * 4, npix, hipMemcpyHostToDevice, S.s));
+        ok = ok && S.ok(launch_split_from_f32(d_x32, cp, d_x, 2 * cp, cp, npix, S.s));
+        ok = ok && S.ok(launch_avgpool(make_view(d_x, n, h, w, c, 2 * cp, DT_F16), true, make_view(d_o, n, 1, 1, c, 2 * cp, DT_F16), S.s));
+        ok = ok && S.ok(launch_split_to_f32(d_o, 2 * cp, cp, d_j, cp, (size_t)n, S.s));
+        ok = ok && S.ok(launch_to_f32(make_view(d_j, n, 1, 1, c, cp, DT_F32), d_o32, S.s));
+    } else {
+        const int dt = dtype == YOLO_FP32 ? DT_F32 : dtype == YOLO_FP16 ? DT_F16 : DT_BF16, cs = roundup(c, 8);
+        float *d_x32 = (float *)S.upload(x, npix * c * 4);
+        void *d_x = S.alloc(npix * cs * dt_size(dt)), *d_o = S.alloc((size_t)n * cs * dt_size(dt));
+        if (S.rc) { g_op_err = "avgpool: allocation failed"; return S.rc; }
+        ok = S.ok(launch_from_f32(d_x32, make_view(d_x, n, h, w, c, cs, dt), S.s));
+        ok = ok && S.ok(launch_avgpool(make_view(d_x, n, h, w, c, cs, dt), false, make_view(d_o, n, 1, 1, c, cs, dt), S.s));
+        ok = ok && S.ok(launch_to_f32(make_view(d_o, n, 1, 1, c, cs, dt), d_o32, S.s));
+    }
+    if (!ok) { g_op_err = "avgpool: " + S.err; return S.rc; }
+    return S.download(out, d_o32, (size_t)n * c * 4);
+}
+
+int yolo_op_softmax(const float *x, int n, int len, int groups, float temperature, int top_k, float *probs_out,
+                    int32_t *classes_out, float *topk_probs_out, int device)
+{
+    if (!x || !probs_out || n < 1 || len < 1 || groups < 1 || len % groups || !(temperature > 0.f)) { g_op_err = "softmax: bad arguments"; return YOLO_ERR_INVALID; }
+    if (len / groups > CLS_SOFTMAX_MAX) { g_op_err = "softmax: more than 8192 logits in a group"; return YOLO_ERR_UNSUPPORTED; }
+    if (top_k < 0 || top_k > CLS_TOPK_MAX || (top_k > 0 && (groups != 1 || !classes_out || !topk_probs_out))) { g_op_err = "softmax: top_k needs 1..32, groups == 1 and both output arrays"; return YOLO_ERR_INVALID; }
+    OpScope S(device); if (S.rc) { g_op_err = "softmax: no HIP device"; return S.rc; }
+    SoftmaxArgs a; memset(&a, 0, sizeof a);
+    a.x = (const float *)S.upload(x, (size_t)n * len * 4); a.x_stride = len; a.n = n; a.groups = groups; a.len = len / groups; a.temperature = temperature;
+    a.probs = (float *)S.alloc((size_t)n * len * 4); a.p_stride = len; a.top_k = top_k;
+    a.cls = (int *)S.alloc((size_t)n * CLS_TOPK_MAX * 4); a.topk_probs = (float *)S.alloc((size_t)n * CLS_TOPK_MAX * 4);
+    if (S.rc) { g_op_err = "softmax: allocation failed"; return S.rc; }
+    if (!S.ok(launch_softmax_topk(a, S.s))) { g_op_err = "softmax: " + S.err; return S.rc; }
+    if (top_k > 0) { S.download(classes_out, a.cls, (size_t)n * top_k * 4); S.download(topk_probs_out, a.topk_probs, (size_t)n * top_k * 4); }
+    return S.download(probs_out, a.probs, (size_t)n * len * 4);
+}
+
 int yolo_op_resize_u8(const uint8_t *img, int h, int w, int s, float post_scale, float *out, int device)
 {
     if (!img || !out || h < 1 || w < 1 || s < 1) return YOLO_ERR_INVALID;

@@ -189,6 +189,26 @@ int build_plan(yolo_ctx *c, const std::vector<Section> &secs)
             if (c->attrs && c->attrs != 5 + L.classes) return fail(c, YOLO_ERR_UNSUPPORTED, "heads with different class counts");
             c->attrs = 5 + L.classes; L.row_off = c->rows; c->rows += H * W * L.na;
             c->layers[i - 1].head = true;
+        } else if (s.type == "avgpool") {
+            // always global (DN/avgpool_layer.c:40-55): H x W x C -> 1 x 1 x C, stored in the form of its input
+            if (c->dtype == YOLO_FP8) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [avgpool] is not served in the fp8 configuration", i);
+            L.type = L_AVGPOOL; H = 1; W = 1;
+        } else if (s.type == "softmax") {
+            // DN/parser.c:268-280: groups, temperature; per image and group e = exp(x / temp - max / temp), p = e / sum (DN/blas.c:305-321)
+            if (c->dtype == YOLO_FP8) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [softmax] is not served in the fp8 configuration", i);
+            if (s.kv.count("tree")) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [softmax] with tree= (hierarchical softmax) is not served", i);
+            if (opt_i(s, "spatial", 0)) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [softmax] with spatial=1 is not served", i);
+            L.type = L_SOFTMAX; L.groups = opt_i(s, "groups", 1); L.temperature = (float)atof(opt_s(s, "temperature", "1").c_str());
+            if (H != 1 || W != 1) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [softmax] over a %d x %d map (it must follow an [avgpool] or a [connected] layer)", i, H, W);
+            if (L.groups < 1 || C % L.groups) return fail(c, YOLO_ERR_INVALID, "layer %d: [softmax] groups=%d does not divide its %d inputs", i, L.groups, C);
+            if (!(L.temperature > 0.f)) return fail(c, YOLO_ERR_INVALID, "layer %d: [softmax] temperature must be > 0", i);
+            if (C / L.groups > CLS_SOFTMAX_MAX) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [softmax] group of %d logits (at most %d)", i, C / L.groups, CLS_SOFTMAX_MAX);
+            // the logits are never rounded to 16 bits: the conv that reaches this layer directly, or through one [avgpool], writes fp32
+            int p = i - 1;
+            if (p >= 0 && c->layers[p].type == L_AVGPOOL) p = c->layers[p].in[0];
+            if (p >= 0 && c->layers[p].type == L_CONV) c->layers[p].head = true;
+        } else if (s.type == "cost") {
+            L.type = L_ROUTE; L.cost = true;         // inference: identity (DN/cost_layer.c: forward returns without a truth)
         } else {
             return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: section [%s] is outside the inference hot path", i, s.type.c_str());
         }
@@ -205,7 +225,26 @@ int build_plan(yolo_ctx *c, const std::vector<Section> &secs)
         }
     }
     for (int i = 0; i < NL; ++i) if (c->layers[i].head) c->layers[i].pair = false;        // heads are fp32
-    if (c->rows == 0) return fail(c, YOLO_ERR_INVALID, "cfg has no [yolo] / [region] / [detection] head");
+    // classifier tail: an [avgpool] of an fp32 logit map stays fp32 and is pooled inside the [softmax] launch behind it; a [softmax] reads fp32
+    for (int i = 0; i < NL; ++i) {
+        Layer &L = c->layers[i];
+        const int j = L.in.empty() ? -1 : L.in[0];
+        if (L.type == L_AVGPOOL && (c->dtype == YOLO_FP32 || (j >= 0 && c->layers[j].head))) {
+            L.pair = false; L.store_dt = DT_F32;
+            L.pool_fused = i + 1 < NL && c->layers[i + 1].type == L_SOFTMAX && L.C <= CLS_SOFTMAX_MAX && !getenv("YOLO_NO_POOL_FUSE");
+        }
+        if (L.type == L_SOFTMAX) {
+            L.pair = false; L.store_dt = DT_F32;
+            if (!(c->dtype == YOLO_FP32 || (j >= 0 && (c->layers[j].head || (c->layers[j].type == L_AVGPOOL && c->layers[j].store_dt == DT_F32)))))
+                return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [softmax] must follow a [convolutional] / [connected] layer, directly or through one [avgpool] (fp32 logits)", i);
+        }
+    }
+    if (c->rows == 0) {          // no detection head: a classifier when the output layer (the last one that is not [cost]) is a [softmax]
+        int o = NL - 1;
+        while (o >= 0 && c->layers[o].cost) --o;
+        if (o < 0 || c->layers[o].type != L_SOFTMAX) return fail(c, YOLO_ERR_INVALID, "cfg has no [yolo] / [region] / [detection] head");
+        c->cls_layer = o;
+    }
     c->in_mul = (float)atof(opt_s(net, "yolo_input_mul", "1").c_str()); c->in_add = (float)atof(opt_s(net, "yolo_input_add", "0").c_str());
     if (c->rows > 32768) return fail(c, YOLO_ERR_UNSUPPORTED, "more than 32768 candidates per image");
 
@@ -305,7 +344,8 @@ int build_plan(yolo_ctx *c, const std::vector<Section> &secs)
             //  concatenation like any other tensor; element offset 2 x the channel offset)
             const int gran = L.pair ? 32 : gran_of(L.store_dt);
             bool ok = j >= 0 && place_route[j] < 0 && c->layers[j].type != L_ROUTE && !c->layers[j].head &&
-                      c->layers[j].type != L_YOLO && c->layers[j].type != L_REGION && c->layers[j].type != L_DETECT && (cj % gran == 0) && (off % gran == 0);
+                      c->layers[j].type != L_YOLO && c->layers[j].type != L_REGION && c->layers[j].type != L_DETECT && (cj % gran == 0) && (off % gran == 0) &&
+                      c->layers[j].type != L_SOFTMAX && !c->layers[j].cost && !(c->layers[j].type == L_AVGPOOL && c->layers[j].store_dt != L.store_dt);
             // a fused-away conv's real producer is the conv; the shortcut layer itself is what gets placed
             if (ok && c->layers[j].type == L_CONV && j + 1 < NL && c->layers[j + 1].noop && c->layers[j + 1].type == L_SHORTCUT) ok = false;
             if (ok) { place_route[j] = i; place_off[j] = L.pair ? 2 * off : off; }
@@ -330,6 +370,7 @@ int build_plan(yolo_ctx *c, const std::vector<Section> &secs)
         if (L.type == L_ROUTE && L.in.size() == 1) { L.noop = true; int j = L.in[0]; if (j < 0) return fail(c, YOLO_ERR_UNSUPPORTED, "route to network input"); L.storage = c->layers[j].storage; L.ch_off = c->layers[j].ch_off; continue; }
         if (L.type == L_ROUTE) continue;
         if (L.stem_skip || L.pstem_skip) { L.noop = true; continue; }               // lives in LDS only
+        if (L.type == L_SOFTMAX) { L.storage = new_storage(L.C, DT_F32, (size_t)c->max_batch, true); continue; }      // dense [n][C] probabilities
         if (place_route[i] >= 0) { L.storage = c->layers[place_route[i]].storage; L.ch_off = place_off[i]; }
         else if (L.head) L.storage = new_storage(roundup(L.C, 4), DT_F32, (size_t)c->max_batch * L.H * L.W, true);
         else L.storage = new_storage(L.pair ? pair_width(L.C) : roundup(L.C, gran_of(L.store_dt)), L.store_dt, (size_t)c->max_batch * L.H * L.W, c->keep_layers);
@@ -423,7 +464,11 @@ int allocate(yolo_ctx *c)
     HIPCK(c, hipMalloc(&c->d_stage, c->stage_bytes));
     HIPCK(c, hipMalloc((void **)&c->d_descs, (size_t)c->max_batch * sizeof(ImgDesc)));      // ragged batches: one descriptor per image
     size_t nr = (size_t)c->max_batch * c->rows;
-    HIPCK(c, hipMalloc((void **)&c->d_det, nr * c->attrs * 4));
+    if (c->cls_layer >= 0) {             // a classifier has no candidate rows: the detection workspace is one element each
+        nr = 1;
+        HIPCK(c, hipMalloc((void **)&c->d_cls_idx, (size_t)c->max_batch * CLS_TOPK_MAX * 4)); HIPCK(c, hipMalloc((void **)&c->d_cls_prob, (size_t)c->max_batch * CLS_TOPK_MAX * 4));
+    }
+    HIPCK(c, hipMalloc((void **)&c->d_det, nr * (c->attrs ? c->attrs : 1) * 4));
     HIPCK(c, hipMalloc((void **)&c->d_box4, nr * 16));
     HIPCK(c, hipMalloc(&c->d_lean_list, nr * 16)); HIPCK(c, hipMalloc((void **)&c->d_lean_cnt, 16)); HIPCK(c, hipMemsetAsync(c->d_lean_cnt, 0, 16, c->stream));
     c->lean_ok = true;                  // every head a [yolo] head the cell-per-wave decode serves

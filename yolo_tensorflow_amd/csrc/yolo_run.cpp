@@ -202,6 +202,27 @@ int run_layer(yolo_ctx *c, int i, int n)
     case L_UPSAMPLE: if (L.pair) { if (getenv("YOLO_PAIR_UPSAMPLE_VIA_F32")) { if (int r = via_f32(c, L, n, 0)) return r; } else HIPCK(c, launch_upsample2x_pair(nview(view_of(c, L.in[0])), nview(L.out), c->semantics == YOLO_SEM_TF, s)); break; } HIPCK(c, launch_upsample2x(nview(view_of(c, L.in[0])), nview(L.out), c->semantics == YOLO_SEM_TF, s)); break;
     case L_MAXPOOL: if (L.pair) { if (int r = via_f32(c, L, n, 1)) return r; break; } HIPCK(c, launch_maxpool(nview(view_of(c, L.in[0])), nview(L.out), L.psize, L.pstride, L.ppad, s)); break;
     case L_REORG: if (L.pair) { if (int r = via_f32(c, L, n, 2)) return r; break; } HIPCK(c, launch_reorg(nview(view_of(c, L.in[0])), nview(L.out), L.pstride, c->semantics == YOLO_SEM_DARKNET, s)); break;
+    case L_AVGPOOL: {
+        if (L.pool_fused) break;             // pooled inside the [softmax] launch that follows
+        const TView in = nview(view_of(c, L.in[0]));
+        HIPCK(c, launch_avgpool(in, c->pair_of(L.in[0]) && in.dt == DT_F16, nview(L.out), s));
+        break; }
+    case L_SOFTMAX: {
+        SoftmaxArgs a; memset(&a, 0, sizeof a);
+        a.n = n; a.groups = L.groups; a.len = L.C / L.groups; a.temperature = L.temperature; a.probs = (float *)L.out.ptr; a.p_stride = L.out.stride;
+        a.top_k = i == c->cls_layer ? c->cls_topk : 0; a.cls = c->d_cls_idx; a.topk_probs = c->d_cls_prob;      // (yolo_classify*: the output layer also selects)
+        const Layer &P = c->layers[L.in[0]];
+        if (P.type == L_AVGPOOL && P.pool_fused) {
+            const TView in = nview(view_of(c, P.in[0]));
+            if (!avgpool_softmax_ok(in, a)) return fail(c, YOLO_ERR_STATE, "layer %d: the fused [avgpool] + [softmax] launch does not apply to this plan", i);
+            HIPCK(c, launch_avgpool_softmax(in, (float *)P.out.ptr, P.out.stride, a, s));
+        } else {
+            const TView in = view_of(c, L.in[0]);
+            if (in.dt != DT_F32) return fail(c, YOLO_ERR_STATE, "layer %d: [softmax] input is not fp32", i);
+            a.x = (const float *)in.ptr; a.x_stride = in.stride;
+            HIPCK(c, launch_softmax_topk(a, s));
+        }
+        break; }
     case L_DETECT: {
         const Layer &P = c->layers[i - 1];
         HIPCK(c, launch_decode_v1((const float *)P.out.ptr, P.out.stride, n, L.side, L.na, L.classes, L.sqr, c->d_det, c->rows, L.row_off,
@@ -294,8 +315,22 @@ int run_network(yolo_ctx *c, int n, bool lean)
     return YOLO_OK;
 }
 
+int output_layer(const yolo_ctx *c)
+{
+    int o = (int)c->layers.size() - 1;
+    while (o >= 0 && c->layers[o].cost) --o;
+    return o;
+}
+
+int need_detector(yolo_ctx *c, const char *what)
+{
+    if (c->cls_layer >= 0) return fail(c, YOLO_ERR_INVALID, "%s: the network is a classifier (its output layer is a [softmax], it has no detection head); use yolo_classify*", what);
+    return YOLO_OK;
+}
+
 int post_args_ok(yolo_ctx *c, int max_out, int nms_mode, int select_mode)
 {
+    if (int r = need_detector(c, "threshold + NMS")) return r;
     if (max_out < 1) return fail(c, YOLO_ERR_INVALID, "max_out < 1");
     if (nms_mode < 0 || nms_mode > 4 || select_mode < 0 || select_mode > 1) return fail(c, YOLO_ERR_INVALID, "bad nms/select mode");
     return YOLO_OK;
@@ -419,6 +454,7 @@ int yolo_forward_letterbox_chw(yolo_ctx *c, const float *image_chw, int w, int h
 static int postprocess_impl(yolo_ctx *c, int n, float score_thr, float iou_thr, int max_out, int nms_mode, int select_mode,
                             yolo_box *boxes_out, int32_t *counts_out, int32_t *rows_out, int out_loc, const PostGeom *geom)
 {
+    if (int r = need_detector(c, "yolo_postprocess")) return r;
     if (n < 1 || n > c->last_n) return fail(c, YOLO_ERR_STATE, "postprocess of %d images but the last forward ran %d", n, c->last_n);
     HIPCK(c, hipSetDevice(c->device));
     const int want = nms_mode == YOLO_NMS_NUMPY_V3 ? 1 : 0;
@@ -623,6 +659,48 @@ int yolo_detect_images_graph(yolo_ctx *c, const uint8_t *pixels, size_t bytes, c
     c->lean = lean && c->lean_ok; c->det_valid = !c->lean; c->lean_thr = score_thr;
     c->last_n = n; c->scores_mode = nms_mode == YOLO_NMS_NUMPY_V3 ? 1 : 0; c->stem_u8 = nullptr; c->geom_fit = fit; c->geom_n = n;
     return YOLO_OK;
+}
+
+// ---- classifier contexts: forward + tail; the [softmax] launch of the output layer selects the top_k itself (run_layer) ----
+static int classify_check(yolo_ctx *c, int top_k, const int32_t *classes_out, const float *probs_out)
+{
+    if (c->cls_layer < 0) return fail(c, YOLO_ERR_INVALID, "yolo_classify: the network is a detector (its output layer is not a [softmax])");
+    const Layer &L = c->layers[c->cls_layer];
+    if (top_k < 0 || top_k > CLS_TOPK_MAX || top_k > L.C) return fail(c, YOLO_ERR_INVALID, "top_k %d outside 0..%d", top_k, L.C < CLS_TOPK_MAX ? L.C : CLS_TOPK_MAX);
+    if (top_k > 0 && L.groups != 1) return fail(c, YOLO_ERR_INVALID, "top_k needs a [softmax] with groups=1 (this one has groups=%d)", L.groups);
+    if (!probs_out || (top_k > 0 && !classes_out)) return fail(c, YOLO_ERR_INVALID, "classes_out / probs_out == NULL");
+    return YOLO_OK;
+}
+
+static int classify_out(yolo_ctx *c, int n, int top_k, int32_t *classes_out, float *probs_out, int out_loc)
+{
+    const Layer &L = c->layers[c->cls_layer];
+    if (top_k == 0) return copy_out(c, probs_out, L.out.ptr, (size_t)n * L.C * 4, out_loc);
+    if (int r = copy_out(c, classes_out, c->d_cls_idx, (size_t)n * top_k * 4, out_loc)) return r;
+    return copy_out(c, probs_out, c->d_cls_prob, (size_t)n * top_k * 4, out_loc);
+}
+
+int yolo_classify(yolo_ctx *c, const void *images, int n, int fmt, int loc, float scale, int top_k, int32_t *classes_out, float *probs_out, int out_loc)
+{
+    if (!c) return YOLO_ERR_INVALID;
+    if (int r = classify_check(c, top_k, classes_out, probs_out)) return r;
+    c->cls_topk = top_k;
+    const int r = forward_impl(c, images, n, fmt, loc, scale, nullptr, YOLO_DEVICE, false);
+    c->cls_topk = 0;
+    if (r) return r;
+    return classify_out(c, n, top_k, classes_out, probs_out, out_loc);
+}
+
+int yolo_classify_images_u8(yolo_ctx *c, const uint8_t *pixels, size_t bytes, const yolo_image_desc *descs, int n, int fit, int loc, int top_k,
+                            int32_t *classes_out, float *probs_out, int out_loc)
+{
+    if (!c) return YOLO_ERR_INVALID;
+    if (int r = classify_check(c, top_k, classes_out, probs_out)) return r;
+    c->cls_topk = top_k;
+    const int r = forward_images_impl(c, pixels, bytes, descs, n, fit, loc, nullptr, YOLO_DEVICE, false, 0.f);
+    c->cls_topk = 0;
+    if (r) return r;
+    return classify_out(c, n, top_k, classes_out, probs_out, out_loc);
 }
 
 float yolo_fit_unit_value(int fit, int value)

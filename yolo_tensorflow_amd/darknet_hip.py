@@ -1,7 +1,7 @@
 """Counterpart of the reference's `darknet.py` (D2T/darknet.py:20-142), named darknet_hip to keep the two apart: the same ctypes
 declarations (BOX, DETECTION, IMAGE, METADATA) and every name that file binds (`load_net`, `load_meta`, `load_image`,
 `predict_image`, `get_network_boxes`, `make_network_boxes`, `do_nms_obj`, `do_nms_sort`, `free_detections`, `free_ptrs`,
-`letterbox_image`, `rgbgr_image`, `set_gpu`, `reset_rnn`, `detect`), bound to `libdarknet_hip.so` (include/darknet_hip.h)
+`letterbox_image`, `rgbgr_image`, `set_gpu`, `reset_rnn`, `classify`, `detect`), bound to `libdarknet_hip.so` (include/darknet_hip.h)
 instead of `./libdarknet.so`.
 
 Differences a caller sees: `load_image` decodes binary PPM / PGM only (the reference's stb JPEG decoding, D2T/darknet.py:105,
@@ -118,6 +118,24 @@ def predict_image(net, im):
     if not out:
         raise YoloError("network_predict_image failed")
     return out
+
+
+def classify(net, meta, im):
+    """D2T/darknet.py:117-123: the network's probabilities for `im` (an IMAGE, or an RGB HWC array) as [(name, prob)] over
+    `meta.classes`, sorted by -prob (Python's sort is stable: equal probabilities stay in class order).  `meta`: a METADATA
+    (load_meta) or the class-name list."""
+    if not isinstance(im, IMAGE):
+        im = array_to_image(im)
+    out = predict_image(net, im)
+    if isinstance(meta, METADATA):
+        names = [meta.names[i] for i in range(meta.classes)]
+    else:
+        names = list(meta)
+    res = []
+    for i in range(len(names)):
+        res.append((names[i], out[i]))
+    res = sorted(res, key=lambda x: -x[1])
+    return res
 
 
 def detect(net, names, image, thresh=.5, hier_thresh=.5, nms=.45):

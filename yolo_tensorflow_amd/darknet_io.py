@@ -17,8 +17,8 @@ CFG_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "cfg")
 
 
 def cfg_text(name):
-    """Text of a shipped topology ('yolov3', 'yolov3-608', 'yolov3-tiny', 'yolov2', 'yolov2-tiny-voc', 'yolov1', 'yolov1-tiny')
-    or of a cfg file path."""
+    """Text of a shipped topology ('yolov3', 'yolov3-608', 'yolov3-tiny', 'yolov2', 'yolov2-tiny-voc', 'yolov1', 'yolov1-tiny', and the
+    classifiers 'darknet19', 'darknet53') or of a cfg file path."""
     path = name if os.path.exists(name) else os.path.join(CFG_DIR, name + ".cfg")
     with open(path) as f:
         return f.read()
@@ -176,7 +176,9 @@ def layer_shapes(secs):
             H, W, C = ((H - 1) if pad else (H - k)) // st + 1, ((W - 1) if pad else (W - k)) // st + 1, int(s["filters"])
         elif t == "detection":
             H = W = int(s.get("side", 7))
-        elif t not in ("shortcut", "yolo", "region", "dropout"):
+        elif t == "avgpool":                 # always global (DN/avgpool_layer.c:40-55)
+            H = W = 1
+        elif t not in ("shortcut", "yolo", "region", "dropout", "softmax", "cost"):
             raise ValueError("unsupported layer type [%s]" % t)
         shapes.append((t, H, W, C, cin))
     return shapes

@@ -43,6 +43,7 @@ EXPORTS = [
     "yolo_op_maxpool", "yolo_op_resize_u8", "yolo_op_detections_boxes", "yolo_op_nms_detections", "yolo_forward_letterbox_chw", "yolo_op_decode", "yolo_op_postprocess",
     "yolo_postprocess_rows", "yolo_op_postprocess_rows", "yolo_last_layer_output_batch", "yolo_head_raw", "yolo_calibrate", "yolo_calibrate_copy", "yolo_op_resize_cv2",
     "yolo_forward_images_u8", "yolo_detect_images_u8", "yolo_detect_images_graph", "yolo_fit_unit_value", "yolo_darknet_boxes_at",
+    "yolo_num_classes", "yolo_classify", "yolo_classify_images_u8", "yolo_op_avgpool", "yolo_op_softmax",
 ]
 # include/yolo_dist.h: the image-sharded detect step
 DIST_EXPORTS = ["yolo_shard_bounds", "yolo_dist_flat_words", "yolo_dist_split_records", "yolo_dist_unique_id", "yolo_dist_create",
@@ -84,7 +85,7 @@ def load_library():
     l.yolo_export.argtypes = [P, C.c_char_p]
     l.yolo_create_from_file.argtypes = [C.c_char_p, I, I, P, I, C.c_char_p, C.c_size_t]; l.yolo_create_from_file.restype = P
     l.yolo_input_size.argtypes = [P, C.POINTER(I), C.POINTER(I), C.POINTER(I)]
-    for n in ("yolo_num_rows", "yolo_num_attrs", "yolo_num_layers", "yolo_synchronize"):
+    for n in ("yolo_num_rows", "yolo_num_attrs", "yolo_num_layers", "yolo_synchronize", "yolo_num_classes"):
         getattr(l, n).argtypes = [P]
     l.yolo_conv_flops.argtypes = [P]; l.yolo_conv_flops.restype = D
     l.yolo_conv_bytes.argtypes = [P, I]; l.yolo_conv_bytes.restype = D
@@ -127,6 +128,10 @@ def load_library():
     l.yolo_detect_images_graph.argtypes = [P, P, SZ, P, I, I, F, F, I, I, I, I, P, P]
     l.yolo_fit_unit_value.argtypes = [I, I]; l.yolo_fit_unit_value.restype = F
     l.yolo_darknet_boxes_at.argtypes = [P, I, I, I, F, I, P, I, P]
+    l.yolo_classify.argtypes = [P, P, I, I, I, F, I, P, P, I]
+    l.yolo_classify_images_u8.argtypes = [P, P, SZ, P, I, I, I, I, P, P, I]
+    l.yolo_op_avgpool.argtypes = [P, I, I, I, I, I, P, I]
+    l.yolo_op_softmax.argtypes = [P, I, I, I, F, I, P, P, P, I]
     l.yolo_shard_bounds.argtypes = [I, I, I, C.POINTER(I), C.POINTER(I)]
     l.yolo_dist_flat_words.argtypes = [I, I]; l.yolo_dist_flat_words.restype = C.c_size_t
     l.yolo_dist_split_records.argtypes = [P, I, I, I, P, P]
@@ -445,6 +450,42 @@ class Engine:
         self._check(self.lib.yolo_detect_images_graph(self.ctx, p, nbytes, descs.ctypes.data, len(descs), fit, score_thr, iou_thr,
                                                       max_out, nms_mode, select_mode, units, bp, cp), "yolo_detect_images_graph")
 
+    # ---- classifier networks (a cfg whose output layer is a [softmax]) ----
+    @property
+    def num_classes(self):
+        """Outputs of the [softmax] layer of a classifier; for a detector, attrs - 5 (yolo_num_classes)."""
+        return self.lib.yolo_num_classes(self.ctx)
+
+    def _classify_result(self, n, top_k):
+        if top_k:
+            return np.full((n, top_k), -1, dtype=np.int32), np.zeros((n, top_k), dtype=np.float32)
+        return None, np.zeros((n, max(self.num_classes, 0)), dtype=np.float32)
+
+    def classify(self, images, top_k=5, scale=1.0 / 255.0):
+        """images as for `forward`.  top_k > 0: -> (classes int32 [n, top_k], probs float32 [n, top_k]), probability descending, equal
+        probabilities by ascending class -- selected on the device, only these records are copied; top_k == 0: -> the whole
+        probability matrix float32 [n, num_classes]."""
+        p, loc = _ptr(images)
+        self._last_image = images if loc == DEVICE else None
+        self._order_after_producer(images)
+        n = int(images.shape[0])
+        fmt = IMG_U8 if str(images.dtype).endswith("uint8") else IMG_F32
+        cls, probs = self._classify_result(n, top_k)
+        self._check(self.lib.yolo_classify(self.ctx, p, n, fmt, loc, scale, top_k, cls.ctypes.data if top_k else None, probs.ctypes.data, HOST),
+                    "yolo_classify")
+        return (cls, probs) if top_k else probs
+
+    def classify_images(self, images, fit=FIT_STRETCH, top_k=5):
+        """`classify` over a list of uint8 RGB [h, w, 3] images of any sizes (or a (buffer, descs) pair from pack_images), fitted on
+        the device in one launch (yolo_classify_images_u8)."""
+        buf, descs, p, loc, nbytes = self._packed(images)
+        n = len(descs)
+        self._order_after_producer(buf)
+        cls, probs = self._classify_result(n, top_k)
+        self._check(self.lib.yolo_classify_images_u8(self.ctx, p, nbytes, descs.ctypes.data, n, fit, loc, top_k,
+                                                     cls.ctypes.data if top_k else None, probs.ctypes.data, HOST), "yolo_classify_images_u8")
+        return (cls, probs) if top_k else probs
+
     def darknet_boxes(self, image, w, h, thresh=0.5, relative=1, cap=None):
         """darknet's get_network_boxes over image `image` of the last forward (yolo_darknet_boxes_at) -> records [count, 5 + classes]
         (x, y, w, h, objectness, prob[classes]), un-letterboxed for a w x h source image."""
@@ -558,6 +599,25 @@ def op_maxpool(x, size=2, stride=2, device=0):
     out = np.empty((n, (h + 2 * pad) // stride, (w + 2 * pad) // stride, c), dtype=np.float32)
     _op_check(load_library().yolo_op_maxpool(x.ctypes.data, n, h, w, c, size, stride, out.ctypes.data, device), "yolo_op_maxpool")
     return out
+
+
+def op_avgpool(x, dtype=FP32, device=0):
+    """darknet's (global) [avgpool] of x [n, h, w, c], stored as `dtype` first -> [n, c] float32."""
+    x = _f32(x); n, h, w, c = x.shape
+    out = np.empty((n, c), dtype=np.float32)
+    _op_check(load_library().yolo_op_avgpool(x.ctypes.data, n, h, w, c, dtype, out.ctypes.data, device), "yolo_op_avgpool")
+    return out
+
+
+def op_softmax(x, groups=1, temperature=1.0, top_k=0, device=0):
+    """darknet's [softmax] of x [n, len] -> probs [n, len]; top_k > 0: -> (probs, classes int32 [n, top_k], top probs [n, top_k]) from
+    the same launch."""
+    x = _f32(x); n, ln = x.shape
+    probs = np.empty((n, ln), dtype=np.float32)
+    cls = np.full((n, max(top_k, 1)), -1, dtype=np.int32); tkp = np.zeros((n, max(top_k, 1)), dtype=np.float32)
+    _op_check(load_library().yolo_op_softmax(x.ctypes.data, n, ln, groups, float(temperature), top_k, probs.ctypes.data,
+                                             cls.ctypes.data if top_k else None, tkp.ctypes.data if top_k else None, device), "yolo_op_softmax")
+    return (probs, cls, tkp) if top_k else probs
 
 
 def op_resize_u8(img, size, post_scale=1.0, device=0):
