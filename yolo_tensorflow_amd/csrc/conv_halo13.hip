@@ -1,20 +1,16 @@
 // Halo-staged instantiations of the implicit-GEMM conv kernel (conv_igemm_kernel.h, HALO = true): 3x3 / stride 1 / pad 1 layers
 // whose spatial size is a multiple of 13 -- every residual-block 3x3 conv of a 416x416 darknet-53 (104, 52, 26, 13) --, or (round 5) tiles
-// into 10 x 19 blocks / 5 x 19 strips: the 76 / 38 / 19 grids of the 608x608 network (tile configurations 54..56).
+// into 10 x 19 blocks / 5 x 19 strips: the 76 / 38 / 19 grids of the 608x608 network.  Which ids are halo forms, and their blocks: conv_cfgs.h.
 // Replaces the same reference chain as conv_igemm.hip (DN/convolutional_layer.c:445-485; slim.conv2d V3/yolo_v3.py:47-60).
 #include "conv_igemm_kernel.h"
 
 static bool halo_ok(const ConvArgs &a, int bh, int bw);
 bool conv_halo13_ok(const ConvArgs &a) { return halo_ok(a, HALO_B, HALO_B); }
-// block shape of a halo configuration (ids: conv_igemm.hip's tables)
-static void halo_cfg_block(int cfg, int &bh, int &bw) { bh = bw = HALO_B; if (cfg == 54 || cfg == 55) { bh = 10; bw = 19; } else if (cfg == 56) { bh = 5; bw = 19; } }
 bool conv_halo_cfg_ok(const ConvArgs &a, int cfg)
 {
-    int bh, bw; halo_cfg_block(cfg, bh, bw);
-    if (bh != HALO_B && (a.in_dt == DT_FP8 || a.split)) return false;      // the rectangular blocks are instantiated for bf16 / fp16 storage
-    if (a.pairk && !(a.split && (cfg == 40 || cfg == 41 || cfg == 43 || cfg == 57 || cfg == 58))) return false;      // pair K loop: the free-running forms writing pairs
-    if ((cfg == 57 || cfg == 58) && !a.pairk) return false;                    // (one wave per SIMD: instantiated for the pair K loop only)
-    return halo_ok(a, bh, bw);
+    // instantiated for the conv's storage family (the rectangular blocks: bf16 / fp16 storage; pair K loop: the free-running forms writing
+    // pairs, 57 / 58 for it alone), and the layer tiles into the configuration's blocks
+    return conv_cfg_is_halo(cfg) && conv_cfg_instantiated(a, cfg) && halo_ok(a, kCfgs[cfg].bh, kCfgs[cfg].bw);
 }
 static bool halo_ok(const ConvArgs &a, int bh, int bw)
 {
@@ -35,7 +31,7 @@ static bool halo_ok(const ConvArgs &a, int bh, int bw)
 template <int WC, int TC, int NL, int EB, bool FREE = false, int NS = 2, bool H16 = false, bool SPLIT = false, int BH = HALO_B, int BW = HALO_B, bool HEADT = false, bool PAIRK = false>
 static hipError_t launch_h(const ConvArgs &a, hipStream_t s)
 {
-    if (a.tail_f32 && !HEADT) return hipErrorInvalidValue;        // a head as the tail runs on the HEADT instantiations (tile configurations 40 and 54)
+    if (a.tail_f32 && !HEADT) return hipErrorInvalidValue;        // a head as the tail runs on the HEADT instantiations (head_tail in the table)
     constexpr int WP = 1, TP = (BH * BW + 15) / 16, BK = 64, BC = WC * TC * 16;
     const long blocks = (long)a.N * ((a.H + BH - 1) / BH) * ((a.W + BW - 1) / BW);
     const long tiles = blocks * ((a.Cout + BC - 1) / BC);
@@ -67,63 +63,35 @@ hipError_t launch_conv_halo13_diag(const ConvArgs &a, hipStream_t s, int variant
     return variant == 1 ? launch_diag<4, 4>(a, s) : launch_diag<8, 2>(a, s);
 }
 
+// halo configuration ID (conv_cfgs.h): the tile shape comes from the table, operand size / storage form / tail kind / K loop from the conv
+template <int ID, int EB, bool H16 = false, bool SPLIT = false, bool HEADT = false, bool PAIRK = false>
+static hipError_t launch_hid(const ConvArgs &a, hipStream_t s)
+{
+    constexpr ConvCfg c = kCfgs[ID];
+    static_assert(c.halo && c.wp == 1 && c.bk == 64 && c.tp == (c.bh * c.bw + 15) / 16, "halo form: one wave row over the block's sub-tiles");
+    return launch_h<c.wc, c.tc, c.nl, EB, c.free, c.ns, H16, SPLIT, c.bh, c.bw, HEADT, PAIRK>(a, s);
+}
+// 16-bit storage: a detection head as the fused tail has its own instantiation where the table says so
+template <int ID, bool H16>
+static hipError_t launch_hid16(const ConvArgs &a, hipStream_t s)
+{
+    if constexpr (kCfgs[ID].head_tail) if (a.tail_f32) return launch_hid<ID, 2, H16, false, true>(a, s);
+    return launch_hid<ID, 2, H16>(a, s);
+}
+
 hipError_t launch_conv_halo13(const ConvArgs &a, int cfg, hipStream_t s)
 {
     if (!conv_halo_cfg_ok(a, cfg)) return hipErrorInvalidValue;
-    const bool f8 = a.in_dt == DT_FP8;
-    // round 5: free-running forms on 10 x 19 blocks (12 sub-tiles: 76 x 76 and 38 x 38 grids) and 5 x 19 strips (6 sub-tiles: 19 x 19), bf16 / fp16
-    if (cfg >= 54 && cfg <= 56) {
-        if (f8 || a.split) return hipErrorInvalidValue;
-        const bool h = a.in_dt == DT_F16;
-        if (h && a.out_dt != DT_F16) return hipErrorInvalidValue;
-        switch (cfg) {
-        case 54: if (a.tail_f32) return h ? launch_h<8, 2, 0, 2, true, 2, true, false, 10, 19, true>(a, s) : launch_h<8, 2, 0, 2, true, 2, false, false, 10, 19, true>(a, s);
-                 return h ? launch_h<8, 2, 0, 2, true, 2, true, false, 10, 19>(a, s) : launch_h<8, 2, 0, 2, true, 2, false, false, 10, 19>(a, s);
-        case 55: return h ? launch_h<8, 1, 0, 2, true, 3, true, false, 10, 19>(a, s) : launch_h<8, 1, 0, 2, true, 3, false, false, 10, 19>(a, s);
-        default: return h ? launch_h<8, 1, 0, 2, true, 3, true, false, 5, 19>(a, s) : launch_h<8, 1, 0, 2, true, 3, false, false, 5, 19>(a, s);
-        }
-    }
     if (a.split) {        // split fp16 storage (YOLO_FP16X2): the free-running forms with the two-pass epilogue
         if (a.in_dt != DT_F16 || a.out_dt != DT_F16 || a.w2) return hipErrorInvalidValue;
         if (a.pairk)          // pairs in, pairs out: the pair K loop (three products per K-step row pair)
-            switch (cfg) {
-            case 40: return launch_h<8, 2, 0, 2, true, 2, true, true, HALO_B, HALO_B, false, true>(a, s);
-            case 41: return launch_h<8, 1, 0, 2, true, 2, true, true, HALO_B, HALO_B, false, true>(a, s);
-            case 43: return launch_h<8, 1, 0, 2, true, 3, true, true, HALO_B, HALO_B, false, true>(a, s);
-            case 57: return launch_h<4, 4, 0, 2, true, 2, true, true, HALO_B, HALO_B, false, true>(a, s);
-            case 58: return launch_h<4, 2, 0, 2, true, 2, true, true, HALO_B, HALO_B, false, true>(a, s);
-            default: return hipErrorInvalidValue;
-            }
-        switch (cfg) {          // plain fp16 in, pairs out (mixed plans)
-        case 40: return launch_h<8, 2, 0, 2, true, 2, true, true>(a, s);
-        case 41: return launch_h<8, 1, 0, 2, true, 2, true, true>(a, s);
-        case 43: return launch_h<8, 1, 0, 2, true, 3, true, true>(a, s);
-        default: return hipErrorInvalidValue;
-        }
+            return cfg_dispatch(CfgsHaloPairK{}, cfg, [&](auto id) { return launch_hid<decltype(id)::value, 2, true, true, false, true>(a, s); });
+        return cfg_dispatch(CfgsHaloSplit{}, cfg, [&](auto id) { return launch_hid<decltype(id)::value, 2, true, true>(a, s); });          // plain fp16 in, pairs out (mixed plans)
     }
+    if (a.in_dt == DT_FP8) return cfg_dispatch(CfgsHaloFp8{}, cfg, [&](auto id) { return launch_hid<decltype(id)::value, 1>(a, s); });
     if (a.in_dt == DT_F16) {
         if (a.out_dt != DT_F16) return hipErrorInvalidValue;
-        switch (cfg) {
-        case 36: return launch_h<8, 2, 0, 2, false, 2, true>(a, s);
-        case 37: return launch_h<8, 2, 4, 2, false, 2, true>(a, s);
-        case 38: return launch_h<4, 2, 4, 2, false, 2, true>(a, s);
-        case 39: return launch_h<4, 2, 0, 2, false, 2, true>(a, s);
-        case 40: return a.tail_f32 ? launch_h<8, 2, 0, 2, true, 2, true, false, HALO_B, HALO_B, true>(a, s) : launch_h<8, 2, 0, 2, true, 2, true>(a, s);
-        case 41: return launch_h<8, 1, 0, 2, true, 2, true>(a, s);
-        case 42: return launch_h<4, 2, 0, 2, true, 2, true>(a, s);
-        case 43: return launch_h<8, 1, 0, 2, true, 3, true>(a, s);
-        default: return hipErrorInvalidValue;
-        }
+        return cfg_dispatch(CfgsHalo16{}, cfg, [&](auto id) { return launch_hid16<decltype(id)::value, true>(a, s); });
     }
-    switch (cfg) {
-    case 36: return f8 ? launch_h<8, 2, 0, 1>(a, s) : launch_h<8, 2, 0, 2>(a, s);
-    case 37: return f8 ? launch_h<8, 2, 4, 1>(a, s) : launch_h<8, 2, 4, 2>(a, s);
-    case 38: return f8 ? launch_h<4, 2, 4, 1>(a, s) : launch_h<4, 2, 4, 2>(a, s);
-    case 39: return f8 ? launch_h<4, 2, 0, 1>(a, s) : launch_h<4, 2, 0, 2>(a, s);
-    case 40: return f8 ? launch_h<8, 2, 0, 1, true>(a, s) : a.tail_f32 ? launch_h<8, 2, 0, 2, true, 2, false, false, HALO_B, HALO_B, true>(a, s) : launch_h<8, 2, 0, 2, true>(a, s);
-    case 41: return f8 ? launch_h<8, 1, 0, 1, true>(a, s) : launch_h<8, 1, 0, 2, true>(a, s);
-    case 42: return f8 ? launch_h<4, 2, 0, 1, true>(a, s) : launch_h<4, 2, 0, 2, true>(a, s);
-    case 43: return f8 ? launch_h<8, 1, 0, 1, true, 3>(a, s) : launch_h<8, 1, 0, 2, true, 3>(a, s);
-    default: return hipErrorInvalidValue;
-    }
+    return cfg_dispatch(CfgsHalo16{}, cfg, [&](auto id) { return launch_hid16<decltype(id)::value, false>(a, s); });
 }

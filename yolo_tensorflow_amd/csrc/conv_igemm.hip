@@ -170,103 +170,34 @@ hipError_t launch_conv_c8_direct(const ConvArgs &a, hipStream_t s)
 }
 
 // ---------------------------------------------------------------------------------------------
-// Tile configurations: (waves along pixels, waves along channels, 16-px tiles per wave, 16-ch tiles per wave, LDS
-// stages, K-step).  Pixel-tile heights that are not powers of two exist so the autotuner can make the tile count a
-// near multiple of 256 CUs x resident workgroups (wave quantisation), e.g. 176 px for M = 32 * 26 * 26.
-// BK = 32 halves the staging LDS (three or four workgroups per CU) and makes Cin = 32 layers uniform-tap; measured it
-// only pays on the early, short-K layers -- on the deep 3x3 layers the extra barriers cost more than the occupancy
-// buys (0.066 vs 0.053 ms) -- so only a few BK = 32 shapes are kept.
-#define CONV_CFGS(X)                                                                                   \
-    X(0, 2, 2, 4, 4, 2, 64, 0)  X(1, 2, 2, 4, 4, 3, 64, 0)  X(2, 2, 2, 2, 4, 2, 64, 0)  X(3, 2, 2, 2, 4, 3, 64, 0)    \
-    X(4, 4, 1, 4, 2, 2, 64, 0)  X(5, 4, 1, 4, 2, 3, 64, 0)  X(6, 2, 2, 4, 2, 2, 64, 0)  X(7, 2, 2, 4, 2, 3, 64, 0)    \
-    X(8, 4, 1, 4, 4, 2, 64, 0)  X(9, 4, 1, 4, 4, 3, 64, 0)  X(10, 4, 2, 4, 4, 2, 64, 0) X(11, 4, 2, 4, 4, 3, 64, 0)   \
-    X(12, 2, 4, 4, 4, 2, 64, 0) X(13, 2, 4, 4, 4, 3, 64, 0) X(14, 2, 2, 2, 2, 2, 64, 0) X(15, 2, 2, 2, 2, 4, 64, 0)   \
-    X(16, 1, 4, 11, 2, 2, 64, 0) X(17, 1, 4, 11, 4, 2, 64, 0) X(18, 1, 4, 11, 1, 2, 64, 0) X(19, 1, 4, 10, 2, 2, 64, 0) \
-    X(20, 1, 4, 12, 2, 2, 64, 0) X(21, 1, 4, 9, 2, 2, 64, 0) X(22, 1, 4, 13, 2, 2, 64, 0) X(23, 1, 4, 6, 2, 2, 64, 0)  \
-    X(24, 1, 4, 7, 2, 2, 64, 0)                                                                            \
-    X(25, 1, 4, 11, 2, 2, 32, 0) X(26, 2, 2, 4, 2, 2, 32, 0)  X(27, 4, 1, 4, 2, 2, 32, 0)  X(28, 4, 1, 4, 4, 2, 32, 0)  \
-    X(29, 2, 2, 2, 2, 2, 32, 0)  X(30, 2, 2, 2, 4, 2, 32, 0)                                                \
-    X(31, 1, 8, 11, 2, 2, 64, 4) X(32, 1, 8, 11, 2, 2, 64, 0)                                              \
-    X(33, 1, 4, 11, 2, 3, 64, 0) X(34, 1, 4, 6, 2, 3, 64, 0)                                              \
-    X(35, 2, 4, 3, 4, 2, 64, 0)
-// halo-staged 3x3 configurations (conv_halo13.hip; same columns): one 13x13 pixel block x (wc * tc * 16) channels per workgroup
-#define CONV_CFGS_HALO(X)                                                                              \
-    X(36, 1, 8, 11, 2, 2, 64, 0) X(37, 1, 8, 11, 2, 2, 64, 4) X(38, 1, 4, 11, 2, 2, 64, 4) X(39, 1, 4, 11, 2, 2, 64, 0)   \
-    X(40, 1, 8, 11, 2, 2, 64, 0) X(41, 1, 8, 11, 1, 2, 64, 0) X(42, 1, 4, 11, 2, 2, 64, 0)        /* 40-: free-running waves */ \
-    X(43, 1, 8, 11, 1, 3, 64, 0)
-// round 4 (ids follow the halo block: a configuration's id is its index in kCfgs): whole-Cout tiles for the stand-alone 1x1 layers
-// (every activation row enters ONE CU) and small-batch shapes.  (No tile wider than 256 channels: filters and bias are padded to
-// multiples of 256 rows, cout_pad.)
-#define CONV_CFGS_B(X)                                                                                 \
-    X(44, 1, 8, 6, 2, 2, 64, 0) X(45, 1, 8, 6, 2, 3, 64, 0) X(46, 2, 4, 3, 4, 2, 64, 0) X(47, 2, 4, 2, 4, 2, 64, 0)    \
-    X(48, 2, 4, 3, 2, 2, 64, 0) X(49, 2, 4, 4, 2, 3, 64, 0) X(50, 1, 8, 4, 2, 3, 64, 0) X(51, 2, 4, 2, 2, 3, 64, 0)    \
-    X(52, 2, 4, 3, 2, 3, 64, 0) X(53, 2, 4, 3, 2, 4, 64, 0)
-// (Tried and dropped, round 4: the free-running halo form with ONE wave per SIMD -- four waves of 176 x 64, 40 % fewer LDS bytes per FLOP
-// than eight of 176 x 32, whose stamped K loop needs 1 708 cycles per K-step against 1 862.  In the network it LOSES: 26x26 layers 0.412 ms
-// against 0.387 for the eleven of them, 52x52 0.495 against 0.460, 13x13 0.307 against 0.289 -- set-up and epilogue are serial in a wave,
-// and with nobody else on the SIMD nothing runs under them.)
-
-// split fp16 storage (YOLO_FP16X2): the tile shapes instantiated with the two-pass epilogue
-#define CONV_CFGS_SPLIT(X)                                                                             \
-    X(0, 2, 2, 4, 4, 2, 64, 0)  X(2, 2, 2, 2, 4, 2, 64, 0)  X(3, 2, 2, 2, 4, 3, 64, 0)  X(4, 4, 1, 4, 2, 2, 64, 0)    \
-    X(6, 2, 2, 4, 2, 2, 64, 0)  X(7, 2, 2, 4, 2, 3, 64, 0)  X(8, 4, 1, 4, 4, 2, 64, 0)  X(14, 2, 2, 2, 2, 2, 64, 0)   \
-    X(15, 2, 2, 2, 2, 4, 64, 0) X(16, 1, 4, 11, 2, 2, 64, 0) X(23, 1, 4, 6, 2, 2, 64, 0) X(33, 1, 4, 11, 2, 3, 64, 0) \
-    X(34, 1, 4, 6, 2, 3, 64, 0) X(49, 2, 4, 4, 2, 3, 64, 0) X(45, 1, 8, 6, 2, 3, 64, 0) X(52, 2, 4, 3, 2, 3, 64, 0)                    \
-    X(25, 1, 4, 11, 2, 2, 32, 0) X(26, 2, 2, 4, 2, 2, 32, 0) X(27, 4, 1, 4, 2, 2, 32, 0) X(28, 4, 1, 4, 4, 2, 32, 0)    /* 64-byte rows: 3 x 32 = 96 input 'channels' are uniform-tap */
-#define CONV_CFGS_SPLIT_HALO(X) X(40, 1, 8, 11, 2, 2, 64, 0) X(41, 1, 8, 11, 1, 2, 64, 0) X(43, 1, 8, 11, 1, 3, 64, 0)
-bool conv_cfg_split_ok(int cfg)
-{
-    switch (cfg) {
-#define X(id, wp, wc, tp, tc, ns, bk, nl) case id: return true;
-        CONV_CFGS_SPLIT(X) CONV_CFGS_SPLIT_HALO(X)
-#undef X
-    default: return false;
-    }
-}
-
-// round 5: free-running halo forms on rectangular blocks (conv_halo13.hip): 10 x 19 (12 sub-tiles) x 256 / 128 channels, 5 x 19 (6 sub-tiles) x 128
-// -- the 608 x 608 network's 76 / 38 / 19 grids tile into them exactly, 256 workgroups each at 8 images per GPU
-#define CONV_CFGS_HALO_R(X) X(54, 1, 8, 12, 2, 2, 64, 0) X(55, 1, 8, 12, 1, 3, 64, 0) X(56, 1, 8, 6, 1, 3, 64, 0)
-struct CfgDesc { int id, wp, wc, tp, tc, ns, bk, nl, halo; };
-#define X(id, wp, wc, tp, tc, ns, bk, nl) {id, wp, wc, tp, tc, ns, bk, nl, 0},
-#define XH(id, wp, wc, tp, tc, ns, bk, nl) {id, wp, wc, tp, tc, ns, bk, nl, 1},
-// round 6: free-running 13 x 13-block halo forms with ONE wave per SIMD, for the pair K loop (conv_halo13.hip, split-fp16 only): four waves of
-// 176 x 64 (57) / 176 x 32 (58) read every pixel fragment four times per K-step instead of eight -- 42 % fewer LDS bytes per MFMA in a loop whose
-// LDS reads (1 952 cycles per K-step) sit just under its MFMAs (2 112)
-#define CONV_CFGS_HALO_P(X) X(57, 1, 4, 11, 4, 2, 64, 0) X(58, 1, 4, 11, 2, 2, 64, 0)
-static const CfgDesc kCfgs[] = {CONV_CFGS(X) CONV_CFGS_HALO(XH) CONV_CFGS_B(X) CONV_CFGS_HALO_R(XH) CONV_CFGS_HALO_P(XH)};
-#undef X
-#undef XH
-int conv_num_cfgs() { return (int)(sizeof(kCfgs) / sizeof(kCfgs[0])); }
-bool conv_cfg_is_halo(int cfg) { return cfg >= 0 && cfg < conv_num_cfgs() && kCfgs[cfg].halo; }
+// Tile configurations: the table and the families' id lists are conv_cfgs.h
+int conv_num_cfgs() { return kNumCfgs; }
+bool conv_cfg_is_halo(int cfg) { return cfg >= 0 && cfg < kNumCfgs && kCfgs[cfg].halo; }
 bool conv_cfg_tail_ok(int cfg, int cout, bool fp8, bool head)
 {
-    if (cfg < 0 || cfg >= conv_num_cfgs()) return false;
-    const CfgDesc &c = kCfgs[cfg];
+    if (cfg < 0 || cfg >= kNumCfgs) return false;
+    const ConvCfg &c = kCfgs[cfg];
     const int bc = c.wc * c.tc * 16;
-    if (head) return !fp8 && (cfg == 40 || cfg == 54) && cout == 256;      // a head as the tail: the free-running 176 x 256 / 10 x 19 x 256 halo forms have a HEADT instantiation
-    return c.wp == 1 && c.wc == 8 && (fp8 ? bc == 256 : c.nl == 0 && (bc == 256 || bc == 128)) && bc == cout;      // (as TAIL_OK in the kernel)
+    if (head) return !fp8 && c.head_tail && cout == 256;      // a head as the tail: the free-running 176 x 256 / 10 x 19 x 256 halo forms have a HEADT instantiation
+    return conv_tail_shape(c.wp, c.wc, bc, c.nl, fp8 ? 1 : 2) && bc == cout;
 }
 const char *conv_cfg_name(int cfg)
 {
-    static char names[64][32];
-    if (cfg < 0 || cfg >= conv_num_cfgs()) return cfg == CONV_CFG_DIRECT ? "direct_c8" : "?";
-    const CfgDesc &c = kCfgs[cfg];
-    if (c.id >= 57) { snprintf(names[cfg], sizeof names[cfg], "f176c%d_w4_pair", c.wc * c.tc * 16); return names[cfg]; }
-    if (c.id >= 54) { snprintf(names[cfg], sizeof names[cfg], "f%sc%d_s%d", c.tp == 12 ? "10x19" : "5x19", c.wc * c.tc * 16, c.ns); return names[cfg]; }
-    snprintf(names[cfg], sizeof names[cfg], "%s%dc%d_s%d_k%d%s%d", c.halo ? (c.id >= 40 ? "f" : "h") : "p", c.wp * c.tp * 16, c.wc * c.tc * 16, c.ns, c.bk, c.nl ? "_L" : "_w", c.nl ? c.nl : c.wp * c.wc);
-    return names[cfg];
-}
-
-int conv_pick_cfg(const ConvArgs &a)
-{
-    if (conv_c8_direct_ok(a)) return CONV_CFG_DIRECT;
-    const long M = (long)a.N * a.Ho * a.Wo;
-    if (a.Cout <= 32) return 4;
-    if (a.Cout <= 64) return M >= 65536 ? 8 : 6;
-    const long tiles128 = ((M + 127) / 128) * ((a.Cout + 127) / 128);
-    if (tiles128 < 512) return M < 8192 && tiles128 < 128 ? 14 : 2;
-    return 0;
+    struct Names {
+        char s[kNumCfgs][32];
+        Names()
+        {
+            for (const ConvCfg &c : kCfgs) {
+                const int bp = c.wp * c.tp * 16, bc = c.wc * c.tc * 16;
+                if (c.halo && !CfgsHalo16::has(c.id)) snprintf(s[c.id], sizeof s[c.id], "f%dc%d_w%d_pair", bp, bc, c.wp * c.wc);      // the pair K loop's own forms
+                else if (c.halo && (c.bh != HALO_B || c.bw != HALO_B)) snprintf(s[c.id], sizeof s[c.id], "f%dx%dc%d_s%d", c.bh, c.bw, bc, c.ns);
+                else snprintf(s[c.id], sizeof s[c.id], "%s%dc%d_s%d_k%d%s%d", c.halo ? (c.free ? "f" : "h") : "p", bp, bc, c.ns, c.bk, c.nl ? "_L" : "_w", c.nl ? c.nl : c.wp * c.wc);
+            }
+        }
+    };
+    static const Names names;
+    if (cfg < 0 || cfg >= kNumCfgs) return cfg == CONV_CFG_DIRECT ? "direct_c8" : "?";
+    return names.s[cfg];
 }
 
 template <int WP, int WC, int TP, int TC, int NS, int BK, int NL, bool UNI, int EB, bool H16 = false, bool SPLIT = false>
@@ -295,6 +226,14 @@ static hipError_t launch_t(const ConvArgs &a, hipStream_t s)
     return (a.Cin_pad % BKE) == 0 ? launch_u<WP, WC, TP, TC, NS, BK, NL, true, EB, H16, SPLIT>(a, s) : launch_u<WP, WC, TP, TC, NS, BK, NL, false, EB, H16, SPLIT>(a, s);
 }
 
+// tile configuration ID with EB-byte operands
+template <int ID, int EB, bool H16 = false, bool SPLIT = false>
+static hipError_t launch_id(const ConvArgs &a, hipStream_t s)
+{
+    constexpr ConvCfg c = kCfgs[ID];
+    return launch_t<c.wp, c.wc, c.tp, c.tc, c.ns, c.bk, c.nl, EB, H16, SPLIT>(a, s);
+}
+
 hipError_t launch_conv_bf16(const ConvArgs &a, int cfg, hipStream_t s)
 {
     // (16-bit storage: bf16, or fp16 -- the same tile table, the same kernels with the other MFMA and conversions)
@@ -306,62 +245,19 @@ hipError_t launch_conv_bf16(const ConvArgs &a, int cfg, hipStream_t s)
         // split fp16 storage (YOLO_FP16X2), PLAIN input (or the network input's three blocks): fp16 operands, the ordinary K loop, 16-bit
         // outputs written as interleaved pairs (fp32 head outputs as ever); a subset of the tile table is instantiated
         if (a.in_dt != DT_F16 || (a.out_dt != DT_F16 && a.out_dt != DT_F32) || a.w2 || (a.res && a.out_dt == DT_F32)) return hipErrorInvalidValue;
-        switch (cfg) {
-#define X(id, wp, wc, tp, tc, ns, bk, nl) case id: return launch_t<wp, wc, tp, tc, ns, bk, nl, 2, true, true>(a, s);
-            CONV_CFGS_SPLIT(X)
-#undef X
-#define X(id, wp, wc, tp, tc, ns, bk, nl) case id: return launch_conv_halo13(a, id, s);
-            CONV_CFGS_SPLIT_HALO(X)
-#undef X
-        default: return hipErrorInvalidValue;
-        }
+        if (CfgsHaloSplit::has(cfg)) return launch_conv_halo13(a, cfg, s);
+        return cfg_dispatch(CfgsSplit{}, cfg, [&](auto id) { return launch_id<decltype(id)::value, 2, true, true>(a, s); });
     }
     if (cfg == CONV_CFG_DIRECT) return conv_c8_direct_ok(a) ? launch_conv_c8_direct(a, s) : hipErrorInvalidValue;
-    if (a.in_dt == DT_F16)
-        switch (cfg) {
-#define X(id, wp, wc, tp, tc, ns, bk, nl) case id: return launch_t<wp, wc, tp, tc, ns, bk, nl, 2, true>(a, s);
-            CONV_CFGS(X) CONV_CFGS_B(X)
-#undef X
-        default: break;
-        }
-    switch (cfg) {
-#define X(id, wp, wc, tp, tc, ns, bk, nl) case id: return launch_t<wp, wc, tp, tc, ns, bk, nl, 2>(a, s);
-        CONV_CFGS(X) CONV_CFGS_B(X)
-#undef X
-#define X(id, wp, wc, tp, tc, ns, bk, nl) case id: return launch_conv_halo13(a, id, s);
-        CONV_CFGS_HALO(X) CONV_CFGS_HALO_R(X) CONV_CFGS_HALO_P(X)
-#undef X
-    default: return hipErrorInvalidValue;
-    }
+    if (conv_cfg_is_halo(cfg)) return launch_conv_halo13(a, cfg, s);
+    if (a.in_dt == DT_F16) return cfg_dispatch(Cfgs16{}, cfg, [&](auto id) { return launch_id<decltype(id)::value, 2, true>(a, s); });
+    return cfg_dispatch(Cfgs16{}, cfg, [&](auto id) { return launch_id<decltype(id)::value, 2>(a, s); });
 }
 
-// fp8 operands: the same tile ids, restricted to the two-stage 128-B-row symmetric shapes that the bf16 tuning kept
-#define CONV_CFGS_FP8(X)                                                                                     \
-    X(0, 2, 2, 4, 4, 2, 64, 0)  X(2, 2, 2, 2, 4, 2, 64, 0)  X(4, 4, 1, 4, 2, 2, 64, 0)  X(6, 2, 2, 4, 2, 2, 64, 0)    \
-    X(8, 4, 1, 4, 4, 2, 64, 0)  X(12, 2, 4, 4, 4, 2, 64, 0) X(14, 2, 2, 2, 2, 2, 64, 0) X(16, 1, 4, 11, 2, 2, 64, 0)  \
-    X(17, 1, 4, 11, 4, 2, 64, 0) X(19, 1, 4, 10, 2, 2, 64, 0) X(20, 1, 4, 12, 2, 2, 64, 0) X(23, 1, 4, 6, 2, 2, 64, 0) \
-    X(32, 1, 8, 11, 2, 2, 64, 0) X(31, 1, 8, 11, 2, 2, 64, 4) X(33, 1, 4, 11, 2, 3, 64, 0) X(34, 1, 4, 6, 2, 3, 64, 0) \
-    X(45, 1, 8, 6, 2, 3, 64, 0) X(48, 2, 4, 3, 2, 2, 64, 0) X(49, 2, 4, 4, 2, 3, 64, 0) X(51, 2, 4, 2, 2, 3, 64, 0)      /* round 4: the 8-wave / 3-stage shapes */
-bool conv_cfg_fp8_ok(int cfg)
-{
-    switch (cfg) {
-#define X(id, wp, wc, tp, tc, ns, bk, nl) case id: return true;
-        CONV_CFGS_FP8(X)
-        CONV_CFGS_HALO(X)
-#undef X
-    default: return false;
-    }
-}
+// fp8 operands: the same tile ids, the kernel on the e4m3 MFMA
 hipError_t launch_conv_fp8(const ConvArgs &a, int cfg, hipStream_t s)
 {
     if (a.in_dt != DT_FP8) return hipErrorInvalidValue;
-    switch (cfg) {
-#define X(id, wp, wc, tp, tc, ns, bk, nl) case id: return launch_t<wp, wc, tp, tc, ns, bk, nl, 1>(a, s);
-        CONV_CFGS_FP8(X)
-#undef X
-#define X(id, wp, wc, tp, tc, ns, bk, nl) case id: return launch_conv_halo13(a, id, s);
-        CONV_CFGS_HALO(X)
-#undef X
-    default: return hipErrorInvalidValue;
-    }
+    if (CfgsHaloFp8::has(cfg)) return launch_conv_halo13(a, cfg, s);
+    return cfg_dispatch(CfgsFp8{}, cfg, [&](auto id) { return launch_id<decltype(id)::value, 1>(a, s); });
 }

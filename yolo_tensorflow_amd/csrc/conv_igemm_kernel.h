@@ -2,6 +2,7 @@
 // configurations) and conv_halo13.hip (halo-staged 3x3 configurations) so the two sets of instantiations compile in parallel.
 #pragma once
 #include "kernels.h"
+#include "conv_cfgs.h"
 #include "device_common.h"
 #include "halo_perm_tables.h"
 #include <type_traits>
@@ -398,11 +399,8 @@ __global__ __launch_bounds__(64 * (WP * WC + NL)) void conv_igemm(const ConvArgs
 
     const int KT = a.Kpad / BKE;
     // fused 1x1 tail (see the epilogue): one channel tile covers the whole output (BC == Cout, checked by the host), the
-    // consumer waves split the C2 = BC / 2 tail channels 16 apiece
-    // (8-wave shapes only: in the 4-wave 176x128 shapes the extra live registers push the kernel past 256 VGPRs and cost the
-    // second resident workgroup per CU -- measured slower overall even where the pair itself got faster)
-    // (bf16: not in the role-split shapes -- the tail's addresses, hoisted above the K loop, push their 168-VGPR budget into spills)
-    constexpr bool TAIL_OK = !SPLIT && WP == 1 && NC == 8 && (EB == 2 ? NL == 0 && (BC == 256 || BC == 128) : BC == 256);
+    // consumer waves split the C2 = BC / 2 tail channels 16 apiece (which shapes, and why: conv_tail_shape)
+    constexpr bool TAIL_OK = !SPLIT && conv_tail_shape(WP, WC, BC, NL, EB);
     // (Tried and dropped: placing one LDS-DMA of the next stage behind every MFMA group with sched_group_barrier instead of
     // issuing the whole stage first.  A/B on one MI355X box, YOLOv3-416 batch 32: 2 % SLOWER in both bf16 (3.48 vs 3.40 ms)
     // and fp8 (2.39 vs 2.34 ms) -- a DMA blocks its wave's issue for ~60 cycles wherever it is placed, and the MFMA pipe
@@ -1238,7 +1236,7 @@ constexpr size_t conv_lds_bytes()
     constexpr int RG = 64 / (BK * 2 / 16);
     constexpr int LA = ((BP + RG - 1) / RG + NW - 1) / NW, LB = ((BC + RG - 1) / RG + NW - 1) / NW;
     constexpr size_t stage = (size_t)(LA + LB) * NW * RG * (BK * 2);
-    constexpr bool tail = WP == 1 && WC == 8 && (BC == 256 || BC == 128); // TAIL_OK shapes also stage the tail's [BP][BC/2] tile
+    constexpr bool tail = conv_tail_shape(WP, WC, BC, 0, 2);      // tail shapes also stage the tail's [BP][BC/2] tile (one LDS size per tile shape: sized by the 16-bit rule, loader waves or not)
     constexpr size_t lds0 = HALO ? (size_t)2 * halo_apieces(BH, BW) * 1024 + (size_t)NS * LB * NW * RG * (BK * 2) : (size_t)NS * stage, ldso = (size_t)BP * (BC * 2 + 16) + (tail ? (size_t)BP * (BC + 16) : 0);
     return lds0 > ldso ? lds0 : ldso;
 }

@@ -7,37 +7,6 @@
 #include "conv_igemm_kernel.h"
 #include <cstdlib>
 
-// tile shapes (ids and columns: conv_igemm.hip's table) instantiated with the pair K loop and the SPLIT epilogue (pairs in, pairs or an
-// fp32 head out) ...
-#define CONV_CFGS_PAIRK(X)                                                                             \
-    X(0, 2, 2, 4, 4, 2, 64, 0)  X(2, 2, 2, 2, 4, 2, 64, 0)  X(3, 2, 2, 2, 4, 3, 64, 0)  X(4, 4, 1, 4, 2, 2, 64, 0)    \
-    X(6, 2, 2, 4, 2, 2, 64, 0)  X(7, 2, 2, 4, 2, 3, 64, 0)  X(8, 4, 1, 4, 4, 2, 64, 0)  X(14, 2, 2, 2, 2, 2, 64, 0)   \
-    X(15, 2, 2, 2, 2, 4, 64, 0) X(16, 1, 4, 11, 2, 2, 64, 0) X(23, 1, 4, 6, 2, 2, 64, 0) X(33, 1, 4, 11, 2, 3, 64, 0) \
-    X(34, 1, 4, 6, 2, 3, 64, 0) X(49, 2, 4, 4, 2, 3, 64, 0) X(45, 1, 8, 6, 2, 3, 64, 0) X(52, 2, 4, 3, 2, 3, 64, 0)
-// ... and with the ordinary fp16 epilogue (pairs in, PLAIN fp16 out: the boundaries of a mixed plan)
-#define CONV_CFGS_PAIRK_PLAIN(X)                                                                       \
-    X(0, 2, 2, 4, 4, 2, 64, 0)  X(2, 2, 2, 2, 4, 2, 64, 0)  X(4, 4, 1, 4, 2, 2, 64, 0)  X(6, 2, 2, 4, 2, 2, 64, 0)    \
-    X(8, 4, 1, 4, 4, 2, 64, 0)  X(14, 2, 2, 2, 2, 2, 64, 0) X(16, 1, 4, 11, 2, 2, 64, 0) X(33, 1, 4, 11, 2, 3, 64, 0)      /* (every id split_default_cfg can return is here) */
-
-bool conv_cfg_pairk_ok(int cfg, bool split_out)
-{
-    if (split_out) {
-        if (cfg == 40 || cfg == 41 || cfg == 43 || cfg == 57 || cfg == 58) return true;      // the free-running halo forms (conv_halo13.hip)
-        switch (cfg) {
-#define X(id, wp, wc, tp, tc, ns, bk, nl) case id: return true;
-            CONV_CFGS_PAIRK(X)
-#undef X
-        default: return false;
-        }
-    }
-    switch (cfg) {
-#define X(id, wp, wc, tp, tc, ns, bk, nl) case id: return true;
-        CONV_CFGS_PAIRK_PLAIN(X)
-#undef X
-    default: return false;
-    }
-}
-
 template <int WP, int WC, int TP, int TC, int NS, bool SPLIT>
 static hipError_t launch_p(const ConvArgs &a, hipStream_t s)
 {
@@ -55,26 +24,26 @@ static hipError_t launch_p(const ConvArgs &a, hipStream_t s)
     return hipGetLastError();
 }
 
+// tile configuration ID (ids and columns: conv_cfgs.h) with the pair K loop and the SPLIT epilogue (pairs in, pairs or an fp32 head out), or
+// with the ordinary fp16 epilogue (pairs in, PLAIN fp16 out: the boundaries of a mixed plan)
+template <int ID, bool SPLIT>
+static hipError_t launch_pid(const ConvArgs &a, hipStream_t s)
+{
+    constexpr ConvCfg c = kCfgs[ID];
+    static_assert(c.bk == 64 && c.nl == 0, "pair K loop: 128-byte rows, no loader waves");
+    return launch_p<c.wp, c.wc, c.tp, c.tc, c.ns, SPLIT>(a, s);
+}
+
 hipError_t launch_conv_pair(const ConvArgs &a, int cfg, hipStream_t s)
 {
     if (!a.pairk || a.in_dt != DT_F16 || (a.out_dt != DT_F16 && a.out_dt != DT_F32) || a.w2) return hipErrorInvalidValue;
     if (a.split) {
         if (a.res && a.out_dt == DT_F32) return hipErrorInvalidValue;
-        if (conv_cfg_is_halo(cfg)) return launch_conv_halo13(a, cfg, s);
-        switch (cfg) {
-#define X(id, wp, wc, tp, tc, ns, bk, nl) case id: return launch_p<wp, wc, tp, tc, ns, true>(a, s);
-            CONV_CFGS_PAIRK(X)
-#undef X
-        default: return hipErrorInvalidValue;
-        }
+        if (CfgsHaloPairK::has(cfg)) return launch_conv_halo13(a, cfg, s);
+        return cfg_dispatch(CfgsPairK{}, cfg, [&](auto id) { return launch_pid<decltype(id)::value, true>(a, s); });
     }
     if (a.out_dt != DT_F16) return hipErrorInvalidValue;          // (an fp32 head of a split network runs on the SPLIT instantiations: a.split is set for it)
-    switch (cfg) {
-#define X(id, wp, wc, tp, tc, ns, bk, nl) case id: return launch_p<wp, wc, tp, tc, ns, false>(a, s);
-        CONV_CFGS_PAIRK_PLAIN(X)
-#undef X
-    default: return hipErrorInvalidValue;
-    }
+    return cfg_dispatch(CfgsPairKPlain{}, cfg, [&](auto id) { return launch_pid<decltype(id)::value, false>(a, s); });
 }
 
 // ---------------------------------------------------------------------------------------------

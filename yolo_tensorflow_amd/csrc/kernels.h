@@ -1,4 +1,5 @@
-// Internal launcher interface between the host planner (yolo_api.cpp) and the gfx950 kernels.
+// Internal launcher interface between the host side (planner yolo_plan.cpp, launch sequence yolo_run.cpp, tile selection yolo_tune.cpp, operators
+// yolo_ops.cpp) and the gfx950 kernels.
 #pragma once
 // Cache policy of the conv kernels' OUTPUT stores (aux operand of buffer_store on gfx950: 0 plain write-back, 2 nt, 16 sc1, 17 sc0 sc1).
 // Round 5: sc1 -- write-through to memory as the epilogue runs, instead of leaving up to 32 MB of dirty lines for the end-of-kernel L2
@@ -122,25 +123,24 @@ inline ConvArgs conv_tile_magic(const ConvArgs &a0, int BC, int bh, int bw = 0)
 
 // opt a kernel in to more than 64 KiB of dynamic LDS, once per (device, kernel) -- the attribute is per device
 hipError_t conv_opt_in_lds(const void *kernel, size_t lds_bytes);
-// bf16 MFMA implicit-GEMM conv.  cfg in [0, conv_num_cfgs()); returns hipError.
+// bf16 MFMA implicit-GEMM conv.  cfg in [0, conv_num_cfgs()) (the tile table: conv_cfgs.h); returns hipError.
 #define CONV_CFG_DIRECT 1000          // first-layer direct kernel (Cin padded 3 -> 8), outside the tile table
 bool conv_c8_direct_ok(const ConvArgs &a);
 int conv_num_cfgs();
 const char *conv_cfg_name(int cfg);
-// rough preference used when no autotune ran
-int conv_pick_cfg(const ConvArgs &a);
+// Tile selection (yolo_tune.cpp), the ONE rule behind the forward, the autotuner, the plan loader and the single-operator entry points:
+int conv_default_cfg(const ConvArgs &a);                 // rough preference used when no autotune ran (an id every storage family instantiates, or DIRECT)
+bool conv_cfg_runs(const ConvArgs &a, int cfg);          // would the launcher of a's storage family accept (a, cfg)?
+int conv_resolve_cfg(const ConvArgs &a, int planned);    // the id a layer planned with `planned` (-1: none) launches
 hipError_t launch_conv_bf16(const ConvArgs &a, int cfg, hipStream_t s);
 // halo-staged 3x3 / stride 1 form (conv_halo13.hip): bf16 or fp8 operands, spatial size a multiple of 13, whole 128-byte channel chunks
-bool conv_halo13_ok(const ConvArgs &a);                  // the 13 x 13-block halo forms (tile configurations 36..43)
-bool conv_halo_cfg_ok(const ConvArgs &a, int cfg);       // ... and the block shape of halo configuration `cfg` (round 5: 10 x 19 and 5 x 19 blocks, 54..56)
+bool conv_halo13_ok(const ConvArgs &a);                  // the 13 x 13-block halo forms
+bool conv_halo_cfg_ok(const ConvArgs &a, int cfg);       // halo configuration `cfg`: instantiated for a's storage family, and its block shape fits the layer
 bool conv_cfg_is_halo(int cfg);
 hipError_t launch_conv_halo13(const ConvArgs &a, int cfg, hipStream_t s);
 hipError_t launch_conv_halo13_diag(const ConvArgs &a, hipStream_t s, int variant = 0);   // 0: eight waves of 176 x 32 (the shipped shape), 1: four waves of 176 x 64      // stamped free-running 176x256 build (tools only)
 bool conv_cfg_tail_ok(int cfg, int cout, bool fp8, bool head = false);      // can tile configuration `cfg` run the fused 1x1 tail for a conv with `cout` channels
-// fp8 (e4m3 x e4m3 -> fp32, v_mfma_f32_16x16x128_f8f6f4) variant of the same kernel; only the 128-B-row tile configs
-bool conv_cfg_fp8_ok(int cfg);
-bool conv_cfg_split_ok(int cfg);      // tile configurations instantiated for split fp16 storage (YOLO_FP16X2)
-bool conv_cfg_pairk_ok(int cfg, bool split_out);      // ... and for a conv that READS interleaved pairs (pair K loop), writing pairs / plain fp16 or an fp32 head
+// a conv that READS interleaved pairs (pair K loop), writing pairs / plain fp16 or an fp32 head
 hipError_t launch_conv_pair(const ConvArgs &a, int cfg, hipStream_t s);
 // first layer of a split-fp16 network (image in three blocks hi | lo | hi -> interleaved pairs): the direct kernel, no LDS (conv_pair.hip)
 // fused conv0 + conv1 of a split-fp16 network (conv_stem_pair.hip): image in three blocks -> conv1's interleaved pairs, conv0 never materialised
@@ -156,6 +156,7 @@ bool conv_stem_pair_ok(const StemPairArgs &a);
 hipError_t launch_conv_stem_pair(const StemPairArgs &a, hipStream_t s);
 bool conv_c8_direct_pair_ok(const ConvArgs &a);
 hipError_t launch_conv_c8_direct_pair(const ConvArgs &a, hipStream_t s);      // the tiled pair-K-loop instantiations (conv_pair.hip); the halo ones: launch_conv_halo13
+// fp8 (e4m3 x e4m3 -> fp32, v_mfma_f32_16x16x128_f8f6f4) variant of the same kernel; only the 128-B-row tile configs
 hipError_t launch_conv_fp8(const ConvArgs &a, int cfg, hipStream_t s);
 hipError_t launch_conv_diag(const ConvArgs &a, hipStream_t s);   // stamped diagnostic build of p176c128_s2 (tools only)
 // fused stem: conv 3x3/s1 (3 -> 32) + conv 3x3/s2 (32 -> 64), bf16 (conv_stem.hip)

@@ -1,6 +1,6 @@
 // Private to libyolo_hip.so's host side: the planned network (layers, storage pool, context) and the functions its translation
 // units share.  yolo_plan.cpp: darknet-cfg parser, planner, buffer pool.  yolo_pack.cpp: BN fold, filter packing, fp8 scales, weight
-// stream / export artifact.  yolo_run.cpp: launch sequence, detect graph, timing, tile autotuner.  yolo_api.cpp: create / destroy,
+// stream / export artifact.  yolo_run.cpp: launch sequence, detect graph, timing.  yolo_tune.cpp: tile selection rule, autotuner, tile plan.  yolo_api.cpp: create / destroy,
 // introspection, darknet-flavoured views.  yolo_ops.cpp: single-operator entry points.
 #pragma once
 #include "../../include/yolo_hip.h"

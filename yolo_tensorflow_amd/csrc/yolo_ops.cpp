@@ -59,8 +59,8 @@ static int op_conv2d_split(const float *x, int n, int h, int w, int cin, const f
     a.N = n; a.H = h; a.W = w; a.Cin_pad = L.cin_pad; a.Ho = ho; a.Wo = wo; a.Cout = cout;
     a.ksize = k; a.stride = stride; a.pad = L.pad; a.Kpad = L.kpad; a.kchunk = conv_kchunk(L.cin_pad, DT_F16); a.act = act; a.zeros = d_z;
     conv_finalize(a);
-    int cfg = tile_cfg >= 0 ? tile_cfg : 6;
-    if (!conv_cfg_pairk_ok(cfg, true) || (conv_cfg_is_halo(cfg) && !conv_halo_cfg_ok(a, cfg))) { g_op_err = "conv2d (fp16x2): tile config not instantiated for split storage / not applicable to this shape"; return YOLO_ERR_UNSUPPORTED; }
+    const int cfg = tile_cfg >= 0 ? tile_cfg : 6;
+    if (!conv_cfg_runs(a, cfg)) { g_op_err = "conv2d (fp16x2): tile config not instantiated for split storage / not applicable to this shape"; return YOLO_ERR_UNSUPPORTED; }
     // the shortcut: fused into the conv's epilogue, or (YOLO_SPLIT_UNFUSED, the parity tests' A/B) as the separate launch a keep_layers plan makes
     void *d_r = nullptr;
     if (residual) {
@@ -119,7 +119,8 @@ int yolo_op_conv2d(const float *x, int n, int h, int w, int cin, const float *w_
     a.res = d_r; a.res_stride = cstride; a.N = n; a.H = h; a.W = w; a.Cin_pad = L.cin_pad; a.Ho = ho; a.Wo = wo; a.Cout = cout;
     a.ksize = k; a.stride = stride; a.pad = L.pad; a.Kpad = L.kpad; a.kchunk = conv_kchunk(L.cin_pad, dt); a.act = act; a.zeros = d_z;
     conv_finalize(a);
-    if (conv_cfg_is_halo(tile_cfg) && (f32 || !conv_halo_cfg_ok(a, tile_cfg))) { g_op_err = "conv2d: tile config not applicable to this shape (halo-staged form: 3x3, stride 1, size a multiple of 13, whole channel chunks)"; return YOLO_ERR_UNSUPPORTED; }
+    const int cfg = tile_cfg >= 0 ? tile_cfg : conv_default_cfg(a);
+    if (conv_cfg_is_halo(cfg) && (f32 || !conv_cfg_runs(a, cfg))) { g_op_err = "conv2d: tile config not applicable to this shape (halo-staged form: 3x3, stride 1, size a multiple of 13, whole channel chunks)"; return YOLO_ERR_UNSUPPORTED; }
     hipError_t e;
     if (dt != DT_F32 && dt != DT_F16 && getenv("YOLO_CONV_DIAG") && a.Cin_pad % (dt == DT_FP8 ? 128 : 64) == 0) {
         // developer diagnostic: phase cycle sums of the stamped p176c128_s2 build (YOLO_CONV_DIAG=free: of the free-running halo form
@@ -154,9 +155,7 @@ int yolo_op_conv2d(const float *x, int n, int h, int w, int cin, const float *w_
                 sum[6], sum[7], sum[8], sum[9], sum[10], sum[11]);
         if (a.w2) fprintf(stderr, "diag: fused 1x1 tail: barrier %.0f  fragments + MFMA + pack %.0f  barrier %.0f (then the tail's stores, in `store drain`)\n", sum[12], sum[13], sum[14]);
     } else
-        e = f32 ? launch_conv_f32(a, S.s)
-                : dt == DT_FP8 ? launch_conv_fp8(a, tile_cfg >= 0 ? tile_cfg : conv_pick_cfg(a), S.s)
-                               : launch_conv_bf16(a, tile_cfg >= 0 ? tile_cfg : conv_pick_cfg(a), S.s);
+        e = f32 ? launch_conv_f32(a, S.s) : dt == DT_FP8 ? launch_conv_fp8(a, cfg, S.s) : launch_conv_bf16(a, cfg, S.s);
     if (!S.ok(e)) { g_op_err = "conv2d launch: " + S.err; return S.rc; }
     if (!S.ok(launch_to_f32(make_view(d_o, n, ho, wo, cout, cstride, dt), d_o32, S.s))) { g_op_err = S.err; return S.rc; }
     S.download(out, d_o32, (size_t)n * ho * wo * cout * 4);

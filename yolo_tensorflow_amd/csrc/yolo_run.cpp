@@ -1,5 +1,4 @@
-// Launch sequence of libyolo_hip.so: layer -> kernel launch, input staging, threshold + NMS, the captured detect step, layer timing and
-// the in-situ tile autotuner.
+// Launch sequence of libyolo_hip.so: layer -> kernel launch, input staging, threshold + NMS, the captured detect step and layer timing.
 #include "yolo_ctx.h"
 
 namespace yolo_impl {
@@ -49,20 +48,6 @@ ConvArgs conv_args(const yolo_ctx *c, const Layer &L, int n)
     if (L.s2d7) { a.in = c->s2d.ptr; a.in_stride = 32; a.H = c->s2d.h; a.W = c->s2d.w; a.ksize = 4; a.stride = 1; a.pad = 2; }   // see pack_s2d7
     conv_finalize(a);
     return a;
-}
-
-// split fp16: the untuned choice among the instantiated shapes (conv_cfg_split_ok)
-static int split_default_cfg(const ConvArgs &a)
-{
-    // the image layer: the direct pair kernel wherever it applies -- and ONLY it (its K grouping differs from the tiled kernel's: were both
-    // selectable, a tuned plan would no longer be the built-in plan bit for bit)
-    if (conv_c8_direct_pair_ok(a)) return CONV_CFG_DIRECT;
-    const long M = (long)a.N * a.Ho * a.Wo;
-    if (a.Cout <= 32) return 4;
-    if (a.Cout <= 64) return M >= 65536 ? 8 : 6;
-    const long tiles128 = ((M + 127) / 128) * ((a.Cout + 127) / 128);
-    if (tiles128 < 512) return M < 8192 && tiles128 < 128 ? 14 : 2;
-    return 0;
 }
 
 // split fp16: a layer that moves or interpolates values runs in fp32 between a join (hi + lo) and a split
@@ -153,26 +138,10 @@ int run_layer(yolo_ctx *c, int i, int n)
             h.res = a.res; h.out = a.out; h.out_stride = a.out_stride; h.N = n; h.H = in.h; h.W = in.w; h.dt = L.in_dt;
             if (conv_s2_ok(h)) { HIPCK(c, launch_conv_s2(h, s)); break; }
         }
-        if (a.split || a.pairk) {
-            auto inst = [&](int cfg) { return a.pairk ? conv_cfg_pairk_ok(cfg, a.split != 0) : conv_cfg_split_ok(cfg); };
-            int cfg = L.tile_cfg >= 0 && inst(L.tile_cfg) ? L.tile_cfg : split_default_cfg(a);
-            if (conv_c8_direct_pair_ok(a)) cfg = CONV_CFG_DIRECT;          // the image layer: the direct pair kernel, whatever the plan says
-            if (conv_cfg_is_halo(cfg) && (!conv_halo_cfg_ok(a, cfg) || a.out_dt == DT_F32)) cfg = split_default_cfg(a);
-            HIPCK(c, launch_conv_bf16(a, cfg, s));
-        }
-        else if (c->dtype == YOLO_FP32) { HIPCK(c, launch_conv_f32(a, s)); }
-        else if (L.in_dt == DT_FP8) {
-            int cfg = L.tile_cfg >= 0 && conv_cfg_fp8_ok(L.tile_cfg) ? L.tile_cfg : conv_pick_cfg(a);
-            if (conv_cfg_is_halo(cfg) && !conv_halo_cfg_ok(a, cfg)) cfg = conv_pick_cfg(a);      // e.g. a smaller batch window or another input size
-            if (a.w2 && !conv_cfg_tail_ok(cfg, a.Cout, a.in_dt == DT_FP8, a.tail_f32 != 0)) return fail(c, YOLO_ERR_STATE, "layer %d: tile config %d cannot run the fused 1x1 tail", i, cfg);
-            HIPCK(c, launch_conv_fp8(a, cfg, s));
-        } else {
-            int cfg = L.tile_cfg >= 0 ? L.tile_cfg : conv_pick_cfg(a);
-            if (cfg == CONV_CFG_DIRECT && !conv_c8_direct_ok(a)) cfg = conv_pick_cfg(a);
-            if (conv_cfg_is_halo(cfg) && !conv_halo_cfg_ok(a, cfg)) cfg = conv_pick_cfg(a);
-            if (a.w2 && !conv_cfg_tail_ok(cfg, a.Cout, a.in_dt == DT_FP8, a.tail_f32 != 0)) return fail(c, YOLO_ERR_STATE, "layer %d: tile config %d cannot run the fused 1x1 tail", i, cfg);
-            HIPCK(c, launch_conv_bf16(a, cfg, s));
-        }
+        if (c->dtype == YOLO_FP32) { HIPCK(c, launch_conv_f32(a, s)); break; }
+        const int cfg = conv_resolve_cfg(a, L.tile_cfg);
+        if (a.w2 && !a.split && !a.pairk && !conv_cfg_tail_ok(cfg, a.Cout, a.in_dt == DT_FP8, a.tail_f32 != 0)) return fail(c, YOLO_ERR_STATE, "layer %d: tile config %d cannot run the fused 1x1 tail", i, cfg);
+        HIPCK(c, a.in_dt == DT_FP8 ? launch_conv_fp8(a, cfg, s) : launch_conv_bf16(a, cfg, s));
         break; }
     case L_SHORTCUT:
         if (!L.noop && L.pair) {
@@ -770,157 +739,6 @@ int yolo_time_layers(yolo_ctx *c, int n, int iters, float *ms_out)
     }
     for (int i = 0; i < NL; ++i) ms_out[i] = (float)(acc[i] / iters);
     c->last_n = n;
-    return YOLO_OK;
-}
-
-// Tile selection is measured IN SITU: every candidate configuration is timed inside the real layer sequence (per-layer
-// events around a full forward), not as the same kernel launched back to back.  Back-to-back timing flatters
-// configurations that live off a warm L2: in the real sequence each layer's filters come cold from HBM (124 MB of
-// filters and up to 350 MB of activations pass through the 32 MB of L2 / 256 MB of Infinity Cache between two uses), and
-// the deep, filter-heavy layers ran 0.069 ms in the network against 0.050 ms in isolation.
-int yolo_autotune(yolo_ctx *c, int n, int iters)
-{
-    if (!c) return YOLO_ERR_INVALID;
-    if (!c->weights_loaded) return fail(c, YOLO_ERR_STATE, "weights not loaded");
-    if (c->dtype == YOLO_FP32) return YOLO_OK;
-    if (n < 1 || n > c->max_batch || iters < 1) return fail(c, YOLO_ERR_INVALID, "bad n/iters");
-    HIPCK(c, hipSetDevice(c->device));
-    const int NL = (int)c->layers.size();
-    auto shape_key = [&](const Layer &L) {
-        ConvArgs a = conv_args(c, L, n);
-        char key[128]; snprintf(key, sizeof key, "%d_%d_%d_%d_%d_%d_%d%d_%d%d%d", a.H, a.W, a.Cin_pad, a.Cout, a.ksize, a.stride, a.in_dt, a.out_dt, a.res != nullptr, a.split, a.pairk);
-        return std::string(key);
-    };
-    auto valid = [&](const Layer &L, int cfg) {
-        if (fixed_kernel(L)) return false;                     // fused stem: nothing to choose
-        ConvArgs a = conv_args(c, L, n);
-        if (a.split && conv_c8_direct_pair_ok(a)) return cfg == CONV_CFG_DIRECT;
-        if (cfg == CONV_CFG_DIRECT) return !a.split && conv_c8_direct_ok(a);
-        if (a.pairk) return conv_cfg_pairk_ok(cfg, a.split != 0) && (!conv_cfg_is_halo(cfg) || (conv_halo_cfg_ok(a, cfg) && a.out_dt != DT_F32));
-        if (a.split) return conv_cfg_split_ok(cfg) && (!conv_cfg_is_halo(cfg) || (conv_halo_cfg_ok(a, cfg) && a.out_dt != DT_F32));
-        if (a.in_dt == DT_FP8) return conv_cfg_fp8_ok(cfg);
-        return true;
-    };
-    for (auto &L : c->layers) L.tail_on = false;
-    std::vector<int> fallback(NL, -1);
-    for (int i = 0; i < NL; ++i) if (c->layers[i].type == L_CONV && !fixed_kernel(c->layers[i])) { ConvArgs a = conv_args(c, c->layers[i], n); fallback[i] = (a.split || a.pairk) ? split_default_cfg(a) : conv_pick_cfg(a); }
-    std::map<std::string, std::map<int, double>> score;          // shape -> cfg -> summed ms over the layers of that shape
-    std::vector<float> ms(NL);
-    for (int ci = 0; ci <= conv_num_cfgs(); ++ci) {
-        const int cfg = ci == conv_num_cfgs() ? CONV_CFG_DIRECT : ci;
-        bool any = false;
-        for (int i = 0; i < NL; ++i) {
-            Layer &L = c->layers[i];
-            if (L.type != L_CONV) continue;
-            const bool ok = valid(L, cfg);
-            L.tile_cfg = ok ? cfg : fallback[i]; any |= ok;
-        }
-        if (!any) continue;
-        // a configuration a layer cannot launch (LDS / 2 GiB window) must not abort the pass: probe once
-        for (int i = 0; i < NL; ++i) {
-            Layer &L = c->layers[i];
-            if (L.type != L_CONV || L.tile_cfg != cfg || fixed_kernel(L)) continue;
-            ConvArgs a = conv_args(c, L, n);
-            hipError_t e = a.in_dt == DT_FP8 ? launch_conv_fp8(a, cfg, c->stream) : launch_conv_bf16(a, cfg, c->stream);
-            if (e != hipSuccess) { (void)hipGetLastError(); L.tile_cfg = fallback[i]; }
-        }
-        int r = yolo_time_layers(c, n, iters, ms.data()); if (r) return r;
-        for (int i = 0; i < NL; ++i) {
-            const Layer &L = c->layers[i];
-            if (L.type == L_CONV && L.tile_cfg == cfg && !fixed_kernel(L)) score[shape_key(L)][cfg] += ms[i];
-        }
-        if (getenv("YOLO_TUNE_VERBOSE")) {
-            std::map<std::string, double> seen;
-            for (int i = 0; i < NL; ++i) if (c->layers[i].type == L_CONV && c->layers[i].tile_cfg == cfg && !fixed_kernel(c->layers[i])) seen[shape_key(c->layers[i])] = score[shape_key(c->layers[i])][cfg];
-            for (auto &kv : seen) fprintf(stderr, "tune %s cfg %d %-16s %.4f ms (sum over the layers of this shape, in situ)\n", kv.first.c_str(), cfg, conv_cfg_name(cfg), kv.second);
-        }
-    }
-    for (int i = 0; i < NL; ++i) {
-        Layer &L = c->layers[i];
-        if (L.type != L_CONV || fixed_kernel(L)) continue;
-        auto it = score.find(shape_key(L));
-        int best = fallback[i]; double bt = 1e30;
-        if (it != score.end()) for (auto &kv : it->second) if (kv.second < bt) { bt = kv.second; best = kv.first; }
-        L.tile_cfg = best;
-    }
-    // second pass: fold 1x1 convs into their producers where that beats the best unfused pair.  Base = the plan just
-    // chosen; candidate = every tail-capable tile shape on all producers at once; decided per producer shape.
-    {
-        int r = yolo_time_layers(c, n, iters, ms.data()); if (r) return r;
-        std::vector<float> base(ms);
-        std::vector<int> base_cfg(NL, -1);
-        for (int i = 0; i < NL; ++i) base_cfg[i] = c->layers[i].tile_cfg;
-        std::map<std::string, std::pair<double, int>> best;         // producer shape (+ kind of tail) -> (pair time, cfg), cfg -1 = unfused
-        auto tail_key = [&](const Layer &L) { return shape_key(L) + (c->layers[L.tail_layer].head ? "_head" : ""); };      // (a head as the tail: another set of configurations can host it)
-        for (int i = 0; i < NL; ++i) {
-            const Layer &L = c->layers[i];
-            if (L.type != L_CONV || L.tail_layer < 0) continue;
-            auto &b = best[tail_key(L)];
-            if (b.second == 0 && b.first == 0) b = {0.0, -1};
-            b.first += base[i] + base[L.tail_layer];
-        }
-        for (int cfg = 0; cfg < conv_num_cfgs(); ++cfg) {
-            bool any = false;
-            for (int i = 0; i < NL; ++i) {
-                Layer &L = c->layers[i];
-                if (L.type != L_CONV || L.tail_layer < 0) continue;
-                bool ok = conv_cfg_tail_ok(cfg, L.filters, L.in_dt == DT_FP8, c->layers[L.tail_layer].head) && c->layers[L.tail_layer].in_dt == L.in_dt && valid(L, cfg);      // (valid: e.g. a shape the e4m3 table does not instantiate)
-                if (ok && conv_cfg_is_halo(cfg)) { ConvArgs a = conv_args(c, L, n); ok = conv_halo_cfg_ok(a, cfg); }
-                L.tile_cfg = ok ? cfg : base_cfg[i]; L.tail_on = ok; any |= ok;
-            }
-            if (!any) continue;
-            r = yolo_time_layers(c, n, iters, ms.data()); if (r) return r;
-            std::map<std::string, double> t;
-            for (int i = 0; i < NL; ++i) {
-                const Layer &L = c->layers[i];
-                if (L.type == L_CONV && L.tail_layer >= 0 && L.tail_on) t[tail_key(L)] += ms[i] + ms[L.tail_layer];
-            }
-            for (auto &kv : t) {
-                auto &b = best[kv.first];
-                if (getenv("YOLO_TUNE_VERBOSE")) fprintf(stderr, "tune-tail %s cfg %d %-16s fused pair %.4f ms (unfused best so far %.4f)\n", kv.first.c_str(), cfg, conv_cfg_name(cfg), kv.second, b.first);
-                if (kv.second < b.first) b = {kv.second, cfg};
-            }
-        }
-        for (int i = 0; i < NL; ++i) {
-            Layer &L = c->layers[i];
-            if (L.type != L_CONV || L.tail_layer < 0) continue;
-            const auto &b = best[tail_key(L)];
-            L.tail_on = b.second >= 0; L.tile_cfg = b.second >= 0 ? b.second : base_cfg[i];
-        }
-    }
-    drop_graph(c);
-    return YOLO_OK;
-}
-
-int yolo_get_tile_configs(const yolo_ctx *c, int32_t *cfgs)
-{
-    if (!c || !cfgs) return YOLO_ERR_INVALID;
-    // a conv whose plan folds the following 1x1 conv into its epilogue is reported as cfg + 10000
-    for (size_t i = 0; i < c->layers.size(); ++i) {
-        const Layer &L = c->layers[i];
-        cfgs[i] = L.type == L_CONV ? (L.tail_on && L.tile_cfg >= 0 ? L.tile_cfg + 10000 : L.tile_cfg) : -1;
-    }
-    return YOLO_OK;
-}
-
-int yolo_set_tile_configs(yolo_ctx *c, const int32_t *cfgs)
-{
-    if (!c || !cfgs) return YOLO_ERR_INVALID;
-    for (size_t i = 0; i < c->layers.size(); ++i) {
-        if (c->layers[i].type != L_CONV) continue;
-        int v = cfgs[i]; bool tail = false;
-        if (v >= 10000) { v -= 10000; tail = true; }
-        if (v != -1 && v != CONV_CFG_DIRECT && (v < 0 || v >= conv_num_cfgs())) return fail(c, YOLO_ERR_INVALID, "layer %zu: tile config %d out of range", i, v);
-        if (tail && (c->layers[i].tail_layer < 0 || !conv_cfg_tail_ok(v, c->layers[i].filters, c->layers[i].in_dt == DT_FP8, c->layers[c->layers[i].tail_layer].head) || c->layers[c->layers[i].tail_layer].in_dt != c->layers[i].in_dt))
-            return fail(c, YOLO_ERR_INVALID, "layer %zu: plan asks for a fused 1x1 tail this layer / tile config cannot run", i);
-        if (tail && fixed_kernel(c->layers[i])) return fail(c, YOLO_ERR_INVALID, "layer %zu runs a fixed kernel (stem / conv3 / block / stride-2): it hosts no fused 1x1 tail", i);
-        if (tail && conv_cfg_is_halo(v)) {
-            ConvArgs a = conv_args(c, c->layers[i], c->max_batch);
-            if (!conv_halo_cfg_ok(a, v)) return fail(c, YOLO_ERR_INVALID, "layer %zu: the halo-staged tile config %d does not apply to this layer, so it cannot carry the fused 1x1 tail", i, v);
-        }
-        c->layers[i].tile_cfg = v; c->layers[i].tail_on = tail;
-    }
-    drop_graph(c);
     return YOLO_OK;
 }
 
