@@ -186,15 +186,16 @@ def test_resize_u8_legacy_bilinear(hiplib):
         np.testing.assert_allclose(got, ref, rtol=0, atol=2e-6)      # same op order; a 1-ulp slack on the scale factor
 
 
+@pytest.mark.parametrize("classes", [80, 100])      # 255 channels: one wave per cell; 315 (> 256): one wave per box, two 64-lane passes
 @pytest.mark.parametrize("mode", ["ratio", "pixel"])
-def test_decode_yolo(hiplib, mode):
+def test_decode_yolo(hiplib, mode, classes):
     rng = np.random.default_rng(15)
     anchors = [(116, 90), (156, 198), (373, 326)]
     for g in (13, 26):
-        raw = (rng.standard_normal((2, g, g, 255)) * 2).astype(np.float32)
+        raw = (rng.standard_normal((2, g, g, 3 * (5 + classes))) * 2).astype(np.float32)
         fn = R.detection_layer_ratio if mode == "ratio" else R.detection_layer_pixel
         ref = fn(raw, anchors, (32 * g, 32 * g))
-        got = hiplib.op_decode(raw, anchors, 80, 32 * g, hiplib.DECODE_RATIO if mode == "ratio" else hiplib.DECODE_PIXEL)
+        got = hiplib.op_decode(raw, anchors, classes, 32 * g, hiplib.DECODE_RATIO if mode == "ratio" else hiplib.DECODE_PIXEL)
         # expf/sigmoid differ from numpy's by a few ulp
         np.testing.assert_allclose(got, ref, rtol=3e-6, atol=1e-7)
 

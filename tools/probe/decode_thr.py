@@ -1,5 +1,5 @@
 """Developer probe: whole-step time of the graph-replayed detect path at several score thresholds (what the objectness pre-filter of the
-lean decode lets through), with the one-launch multi-head decode (default) and with the per-head launches (YOLO_NO_LEAN_MULTI=1)."""
+lean decode lets through)."""
 import os, sys, json
 import numpy as np, torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))

@@ -292,7 +292,7 @@ struct LeanArgs {
     long total;                          // boxes of all heads: n * sum(g * g * na)
     int n, classes, img_size, mode, rows_total;
     float *box4; float reject_below;
-    uint4 *list; unsigned *list_count; unsigned list_cap;      // boxes that pass the objectness pre-filter (descriptor each); list_count[0] = entries, [1] = phase-2 workgroups done (both zero between launches)
+    uint4 *list; unsigned *list_count; unsigned list_cap;      // boxes that pass the objectness pre-filter (descriptor each); *list_count = entries, zero between launches
 };
 hipError_t launch_decode_lean(const LeanArgs &a, float *scores, int *labels, hipStream_t s);
 // scores/labels (nullable): per-row max_k(obj*cls_k) and its first argmax, written alongside the decode
@@ -325,6 +325,8 @@ struct PostArgs {
     int geom_net_pixels;                // 1: the decoded boxes are in network-input pixels (DECODE_PIXEL [yolo] heads), 0: normalised
 };
 hipError_t launch_postprocess(const PostArgs &a, hipStream_t s);
+// row S on its own: score = max_k(obj * cls_k), label = first arg-max, of nrows decoded rows (objectness_mode: V3/yolo_v3.py:385,397)
+void launch_score_rows(const float *det, size_t nrows, int attrs, float *scores, int *labels, hipStream_t s, int objectness_mode = 0);
 hipError_t launch_letterbox_chw(const float *img, int iw, int ih, int S, void *out, int out_dt, int out_stride, hipStream_t s);
 hipError_t launch_nms_dets(const float4 *boxes, float *prob, float *objectness, int n, int classes, float thresh, int by_obj, hipStream_t s);
 // darknet get_network_boxes on the device (post_ops.hip): ordered compaction + letterbox correction of one image's decoded rows

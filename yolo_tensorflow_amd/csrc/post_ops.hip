@@ -2,7 +2,7 @@
 // the head tensor to the host, DN/yolo_layer.c:347-362, and runs DN/box.c on the CPU; the TF scripts run
 // tf.boolean_mask / tf.image.non_max_suppression or pure-numpy loops, V3/yolo_v3.py:376-420).
 //
-//   k_decode_yolo / k_decode_region : rows D3 / D2 -- raw head conv output -> [n, rows, 5+C] fp32
+//   k_decode_yolo* / k_decode_region: rows D3 / D2 -- raw head conv output -> [n, rows, 5+C] fp32
 //   k_score_rows                    : row S        -- score = max_k(obj*cls_k), label = first argmax
 //   k_nms_image (1 workgroup/image) : rows S+N     -- order-preserving threshold compaction, sort by
 //                                     score (ties: lower row first), greedy suppression, top max_out
@@ -23,8 +23,21 @@ __device__ __forceinline__ float sigmoid_fast(float x)
     const float e = __builtin_amdgcn_exp2f(-x * 1.44269504088896340736f);
     return __builtin_amdgcn_rcpf(1.0f + e);
 }
-void launch_score_rows(const float *det, size_t nrows, int attrs, float *scores, int *labels, hipStream_t s, int objectness_mode = 0);
 
+// Attribute k (0 x, 1 y, 2 w, 3 h) of a [yolo] box, the ONE place this arithmetic is written (`_detection_layer`, V3/yolo_v3.py:111-159, and
+// `_ratio_detection_layer`, V3/YOLOV3.py:168-238): x raw value, (cx, cy) grid cell, anchor = the box's (w, h) pair pre-divided by the
+// stride on the host, G grid size, S stride.  mode 0 divides by G, the pixel mode multiplies by S: not interchangeable without
+// contraction, and the operand order is the reference's.
+__device__ __forceinline__ float yolo_box_attr(int k, float x, int cx, int cy, const float *anchor, float G, float S, int mode)
+{
+    const float t = k < 2 ? sigmoidf_(x) + (float)(k == 0 ? cx : cy) : expf(x) * anchor[k - 2];
+    return mode == 0 ? t / G : t * S;
+}
+// One more class score of a box, taken in ascending class order: the strict > keeps the first maximum (argmax's choice)
+__device__ __forceinline__ void first_max(float &best, int &label, float sc, int k)
+{
+    if (sc > best) { best = sc; label = k; }
+}
 // wave-wide (value, first index) arg-max over lanes; every lane returns the result
 __device__ __forceinline__ void wave_argmax(float &v, int &idx)
 {
@@ -74,44 +87,61 @@ __global__ __launch_bounds__(256) void k_decode_yolo(const DecodeArgs a, float *
         for (int u = 0; u < U; ++u) {
             if (b0 + u >= total) break;
             const int an = an_[u], cell = cell_[u];
-            float r0;
-            if (lane < 2) {
-                const float off = (float)(lane == 0 ? cell % a.g : cell / a.g);
-                const float sg = sigmoidf_(v0[u]) + off;
-                r0 = a.mode == 0 ? sg / G : sg * S;
-            } else if (lane < 4) {
-                const float e = expf(v0[u]) * a.anchors[2 * an + (lane - 2)];   // anchors pre-divided by stride on the host
-                r0 = a.mode == 0 ? e / G : e * S;
-            } else {
-                r0 = sigmoid_fast(v0[u]);
-            }
+            const float r0 = lane < 4 ? yolo_box_attr(lane, v0[u], cell % a.g, cell / a.g, a.anchors + 2 * an, G, S, a.mode) : sigmoid_fast(v0[u]);
             const float r1 = sigmoid_fast(v1[u]);
             if (lane < attrs) dst[u][lane] = r0;
             if (two && lane + 64 < attrs) dst[u][lane + 64] = r1;
             const float obj = __shfl(r0, 4);
             float best = -INFINITY; int bi = 0x7fffffff;
             if (lane >= 5 && lane < attrs) { best = obj * r0; bi = lane - 5; }
-            if (two && lane + 64 < attrs) { const float sc = obj * r1; if (sc > best) { best = sc; bi = lane + 59; } }
+            if (two && lane + 64 < attrs) first_max(best, bi, obj * r1, lane + 59);
             wave_argmax(best, bi);
             if (lane == 0 && scores) { scores[rowi[u]] = best; labels[rowi[u]] = bi; }
         }
     }
 }
 
-// wave-wide maximum on the vector ALU only (DPP row operations, no LDS traffic): lane 63 ends up with the maximum of all
-// 64 lanes, which is broadcast with a readlane
+// Reductions on the vector ALU only (DPP row operations, no LDS traffic).  dpp<CTRL, ROWS>(v): v of the lane the DPP control selects, in
+// the rows of ROWS (the other rows keep their own v).
+template <int CTRL, int ROWS = 0xF, typename T>
+__device__ __forceinline__ T dpp(T v)
+{
+    const int i = __builtin_bit_cast(int, v);
+    return __builtin_bit_cast(T, __builtin_amdgcn_update_dpp(i, i, CTRL, ROWS, 0xF, false));
+}
+// the ladder: every lane ends up with op over the 16 lanes of its DPP row
+template <typename T, typename Op>
+__device__ __forceinline__ T row_reduce_dpp(T v, Op op)
+{
+    v = op(v, dpp<0xB1>(v));       // quad_perm [1,0,3,2]
+    v = op(v, dpp<0x4E>(v));       // quad_perm [2,3,0,1]
+    v = op(v, dpp<0x124>(v));      // row_ror:4
+    v = op(v, dpp<0x128>(v));      // row_ror:8
+    return v;
+}
+__device__ __forceinline__ float row_max_dpp(float v) { return row_reduce_dpp(v, [](float x, float y) { return fmaxf(x, y); }); }
+__device__ __forceinline__ int row_min_dpp(int v) { return row_reduce_dpp(v, [](int x, int y) { return min(x, y); }); }
+// wave-wide maximum: lane 63 ends up with the maximum of all 64 lanes, which is broadcast with a readlane
 __device__ __forceinline__ float wave_max_dpp(float v)
 {
-#define DPP_MAX(ctrl, rmask)                                                                                      \
-    v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, v), __builtin_bit_cast(int, v), ctrl, rmask, 0xF, false)))
-    DPP_MAX(0xB1, 0xF);      // quad_perm [1,0,3,2]
-    DPP_MAX(0x4E, 0xF);      // quad_perm [2,3,0,1]
-    DPP_MAX(0x124, 0xF);     // row_ror:4
-    DPP_MAX(0x128, 0xF);     // row_ror:8   -> every lane holds its row's (16 lanes) maximum
-    DPP_MAX(0x142, 0xA);     // row_bcast:15 into rows 1 and 3
-    DPP_MAX(0x143, 0xC);     // row_bcast:31 into rows 2 and 3
-#undef DPP_MAX
+    v = row_max_dpp(v);
+    v = fmaxf(v, dpp<0x142, 0xA>(v));      // row_bcast:15 into rows 1 and 3
+    v = fmaxf(v, dpp<0x143, 0xC>(v));      // row_bcast:31 into rows 2 and 3
     return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
+}
+
+// Ordered compaction, the step every workgroup-wide form shares: the position of this thread among the flagged threads of a 1024-thread
+// workgroup (thread order), and their number.  One barrier; `wcnt` (LDS, a word per wave) may be rewritten only after a later barrier.
+__device__ __forceinline__ int block_rank(bool flag, int *wcnt, int &total)
+{
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const unsigned long long m = __ballot(flag);
+    if (lane == 0) wcnt[wv] = __popcll(m);
+    __syncthreads();
+    int pre = 0; total = 0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) { const int cnt = wcnt[k]; if (k < wv) pre += cnt; total += cnt; }
+    return pre + __popcll(m & ((1ull << lane) - 1ull));
 }
 
 // Same decode, one wave per grid CELL (all `na` boxes of a pixel = na*(5+C) <= 256 contiguous floats on both sides):
@@ -175,14 +205,7 @@ __global__ __launch_bounds__(256) void k_decode_yolo_cell(const DecodeArgs a, fl
         if (merged) {
 #pragma unroll
             for (int r = 0; r < R; ++r) if (spec_[r]) { xs = x[r]; ks = k_[r]; ans = an_[r]; }
-            float vs = 0.f;
-            if (ks < 2) {
-                const float sg = sigmoidf_(xs) + (float)(ks == 0 ? cx : cy);
-                vs = a.mode == 0 ? sg / G : sg * S;
-            } else if (ks < 4) {
-                const float e = expf(xs) * a.anchors[2 * ans + (ks - 2)];       // anchors pre-divided by stride on the host
-                vs = a.mode == 0 ? e / G : e * S;
-            }
+            const float vs = ks < 4 ? yolo_box_attr(ks, xs, cx, cy, a.anchors + 2 * ans, G, S, a.mode) : 0.f;
 #pragma unroll
             for (int r = 0; r < R; ++r) {
                 v[r] = spec_[r] ? vs : sigmoid_fast(x[r]);
@@ -192,16 +215,7 @@ __global__ __launch_bounds__(256) void k_decode_yolo_cell(const DecodeArgs a, fl
         } else {
 #pragma unroll
             for (int r = 0; r < R; ++r) {
-                const int k = k_[r];
-                if (k < 2) {
-                    const float sg = sigmoidf_(x[r]) + (float)(k == 0 ? cx : cy);
-                    v[r] = a.mode == 0 ? sg / G : sg * S;
-                } else if (k < 4) {
-                    const float e = expf(x[r]) * a.anchors[2 * an_[r] + (k - 2)];
-                    v[r] = a.mode == 0 ? e / G : e * S;
-                } else {
-                    v[r] = sigmoid_fast(x[r]);
-                }
+                v[r] = k_[r] < 4 ? yolo_box_attr(k_[r], x[r], cx, cy, a.anchors + 2 * an_[r], G, S, a.mode) : sigmoid_fast(x[r]);
                 if (dst) { if (ok_[r]) dst[lane + 64 * r] = v[r]; }
                 else if (spec_[r]) dst4[an_[r] * 4 + k_[r]] = v[r];
             }
@@ -238,83 +252,22 @@ __global__ __launch_bounds__(256) void k_decode_yolo_cell(const DecodeArgs a, fl
     }
 }
 
-// Lean decode, objectness first.  When the caller only wants boxes above a score threshold (yolo_detect*: no decoded tensor), a box
-// whose objectness is below the threshold cannot pass whatever its classes say (score = objectness x class probability), and with
-// trained -- or the synthetic -- weights that is 95+ % of the 10647 boxes of an image.  Phase 1: one LANE per box reads just the
-// objectness logit (one 128-byte line of the cell's 1020 bytes per box) and settles every box below the threshold with its score
-// reported as the objectness itself, exactly as the cell-per-wave kernel does.  Phase 2: the lanes whose boxes remain decode them
-// themselves -- the same arithmetic, the same first-maximum label.  The cell-per-wave kernel spent
-// ~400 instructions per cell on boxes that were then thrown away (the 52x52 head: 45 us; this form: the objectness lines + a few
-// per cent of the boxes).
-__global__ __launch_bounds__(256) void k_decode_yolo_lean(const DecodeArgs a, float *scores, int *labels)
-{
-    const int attrs = 5 + a.classes;
-    const int lane = threadIdx.x & 63;
-    const long wave = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const long nwaves = ((long)gridDim.x * blockDim.x) >> 6;
-    const int gg = a.g * a.g;
-    const long total = (long)a.n * gg * a.na;
-    const int stride = a.img_size / a.g;
-    const float G = (float)a.g, S = (float)stride;
-    for (long base = wave * 64; base < total; base += nwaves * 64) {
-        const long box = base + lane;
-        const bool valid = box < total;
-        const unsigned ubox = valid ? (unsigned)box : 0u;
-        const unsigned cidx = ubox / (unsigned)a.na; const int an = (int)(ubox - cidx * (unsigned)a.na);      // cell index over n * g * g
-        const unsigned b = cidx / (unsigned)gg; const int cell = (int)(cidx - b * (unsigned)gg);
-        const size_t row = (size_t)b * a.rows_total + a.row_off + (size_t)cell * a.na + an;
-        const float obj = sigmoid_fast(a.raw[(size_t)cidx * a.raw_stride + an * attrs + 4]);
-        const bool pass = valid && !(obj < a.reject_below);
-        if (valid && !pass) { scores[row] = obj; labels[row] = 0; }
-        if (pass) {
-            // this lane decodes its own box: the attribute loads of the passing lanes are independent of each other (memory-level
-            // parallelism whatever the pass rate -- the synthetic weights let a quarter of the boxes through, trained ones far fewer);
-            // a cooperative wave-per-box loop here was latency-bound at 1-2 us per passing box
-            const float *src = a.raw + (size_t)cidx * a.raw_stride + an * attrs;
-            const float g0 = src[0], g1 = src[1], g2 = src[2], g3 = src[3];
-            float best = -INFINITY; int label = 0;
-            for (int k = 0; k < a.classes; ++k) {                   // ascending: the first maximum wins, like the wave kernels' ballot
-                const float sc = obj * sigmoid_fast(src[5 + k]);
-                if (sc > best) { best = sc; label = k; }
-            }
-            const float sx = sigmoidf_(g0) + (float)(cell % a.g), sy = sigmoidf_(g1) + (float)(cell / a.g);
-            const float ew = expf(g2) * a.anchors[2 * an], eh = expf(g3) * a.anchors[2 * an + 1];      // anchors pre-divided by stride on the host
-            float4 o;
-            o.x = a.mode == 0 ? sx / G : sx * S; o.y = a.mode == 0 ? sy / G : sy * S;
-            o.z = a.mode == 0 ? ew / G : ew * S; o.w = a.mode == 0 ? eh / G : eh * S;
-            *(float4 *)(a.box4 + row * 4) = o;
-            scores[row] = best; labels[row] = label;
-        }
-    }
-}
-
-// The same for every head of the network in one launch, with a cooperative second phase.  Phase 1 as above (one lane per box reads
-// the objectness logit).  Phase 2: the boxes that remain are taken four at a time, one per 16-lane row of the wave: the row reads the
-// box's 5 + C attributes as coalesced 64-byte runs (the lane-per-box loop walked 340 bytes per lane, 85 dependent-address loads each,
-// with the other lanes of the wave idle), scores them, and reduces maximum and first arg-max inside the row with DPP row operations.
-// Same arithmetic per element as k_decode_yolo_lean, same first-maximum label: bit-identical scores, labels and boxes.
-__device__ __forceinline__ float row_max_dpp(float v)         // maximum over the 16 lanes of a DPP row, in every lane of the row
-{
-#define DPP_MAXR(ctrl) v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, v), __builtin_bit_cast(int, v), ctrl, 0xF, 0xF, false)))
-    DPP_MAXR(0xB1); DPP_MAXR(0x4E); DPP_MAXR(0x124); DPP_MAXR(0x128);
-#undef DPP_MAXR
-    return v;
-}
-__device__ __forceinline__ int row_min_dpp(int v)
-{
-#define DPP_MINR(ctrl) v = min(v, __builtin_amdgcn_update_dpp(v, v, ctrl, 0xF, 0xF, false))
-    DPP_MINR(0xB1); DPP_MINR(0x4E); DPP_MINR(0x124); DPP_MINR(0x128);
-#undef DPP_MINR
-    return v;
-}
+// Lean decode, objectness first, for every head of the network in one launch.  When the caller only wants boxes above a score threshold
+// (yolo_detect*: no decoded tensor), a box whose objectness is below the threshold cannot pass whatever its classes say (score = objectness
+// x class probability), and with trained -- or the synthetic -- weights that is 95+ % of the 10647 boxes of an image.  Phase 1: one LANE
+// per box reads just the objectness logit and settles every box below the threshold with its score reported as the objectness itself,
+// exactly as the cell-per-wave kernel does (which spent ~400 instructions per cell on boxes that were then thrown away: 45 us for the
+// 52x52 head).  Phase 2: the boxes that remain are taken four at a time, one per 16-lane row of the wave: the row reads the box's 5 + C
+// attributes as coalesced 64-byte runs (a lane-per-box loop walked 340 bytes per lane, 85 dependent-address loads each, with the other
+// lanes of the wave idle), scores them, and reduces maximum and first arg-max inside the row with DPP row operations.  Same arithmetic per
+// element as the cell-per-wave kernel (yolo_box_attr, sigmoid_fast), same first-maximum label: bit-identical scores, labels and boxes.
 // Phase 1: one lane per box.  Boxes below the threshold are settled here; the others are appended to a list (one atomic per wave) that
 // phase 2 spreads over the whole chip -- the passing boxes cluster (an anchor, an image), and a wave that had to finish its own 64
 // boxes four at a time was the kernel's tail: 49 us for 14 000 boxes, 5 us without them.
 __global__ __launch_bounds__(1024) void k_decode_yolo_lean_p1(const LeanArgs a, float *scores, int *labels)
 {
-    __shared__ unsigned wcnt[16], s_base;
+    __shared__ int wcnt[16]; __shared__ unsigned s_base;
     const int attrs = 5 + a.classes;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     for (long base = (long)blockIdx.x * 1024; base < a.total; base += (long)gridDim.x * 1024) {      // (block-uniform trip count: barriers inside)
         const long box = base + threadIdx.x;
         const bool valid = box < a.total;
@@ -336,22 +289,18 @@ __global__ __launch_bounds__(1024) void k_decode_yolo_lean_p1(const LeanArgs a, 
         const bool pass = valid && !(obj < a.reject_below);
         if (valid && !pass) { scores[row] = obj; labels[row] = 0; }
         // one atomic per WORKGROUP and step (all of them hit one word: ~11 ns each, whoever issues them): wave counts through LDS
-        const unsigned long long m = __ballot(pass);
-        if (lane == 0) wcnt[wv] = (unsigned)__popcll(m);
+        int tot;
+        const int rank = block_rank(pass, wcnt, tot);
+        if (threadIdx.x == 0 && tot) s_base = atomicAdd(a.list_count, (unsigned)tot);
         __syncthreads();
-        unsigned pre = 0, tot = 0;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) { const unsigned cnt = wcnt[k]; if (k < wv) pre += cnt; tot += cnt; }
-        if (threadIdx.x == 0 && tot) s_base = atomicAdd(a.list_count, tot);
-        __syncthreads();
-        const unsigned slot = s_base + pre + (unsigned)__popcll(m & ((1ull << lane) - 1ull));
+        const unsigned slot = s_base + (unsigned)rank;
         // cell < 2^24 (grid <= 4096), anchor < 16, head < 4
         if (pass && slot < a.list_cap) a.list[slot] = uint4{eoff, row, (unsigned)cell | ((unsigned)an << 24) | ((unsigned)hd << 28), __float_as_uint(obj)};
     }
 }
 // Phase 2: one 16-lane row per listed box, grid-stride.  The row reads the box's 5 + C attributes as coalesced 64-byte runs, all loads
 // issued before the first use, scores them and reduces maximum and first arg-max inside the row with DPP row operations -- the same
-// arithmetic per element as k_decode_yolo_lean, the same first-maximum label: bit-identical scores, labels and boxes.  
+// arithmetic per element as the cell-per-wave kernel, the same first-maximum label: bit-identical scores, labels and boxes.
 __global__ __launch_bounds__(256) void k_decode_yolo_lean_p2(const LeanArgs a, float *scores, int *labels)
 {
     const int attrs = 5 + a.classes;
@@ -377,23 +326,12 @@ __global__ __launch_bounds__(256) void k_decode_yolo_lean_p2(const LeanArgs a, f
 #pragma unroll
         for (int t = 0; t < 8; ++t) {                                    // ascending k inside a lane: a strict > keeps the first maximum
             const int k = l15 + 16 * t;
-            if (act && k >= 5 && k < attrs) { const float sc = r_obj * sigmoid_fast(vv[t]); if (sc > best) { best = sc; label = k - 5; } }
+            if (act && k >= 5 && k < attrs) first_max(best, label, r_obj * sigmoid_fast(vv[t]), k - 5);
         }
         const float rbest = row_max_dpp(best);
         const int rlabel = row_min_dpp(best == rbest ? label : 0x7fffffff);      // lowest class index holding the maximum
         if (act && l15 < 4) {
-            const int stride = a.img_size / r_g;
-            const float G = (float)r_g, S = (float)stride;
-            float o;
-            if (l15 < 2) { const float sg = sigmoidf_(g_raw) + (float)(l15 == 0 ? r_cell % r_g : r_cell / r_g); o = a.mode == 0 ? sg / G : sg * S; }
-            else {
-                float anc = a.h[0].anchors[0];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) if (r_hd == k) anc = a.h[k].anchors[2 * r_an + (l15 - 2)];
-                const float e = expf(g_raw) * anc;                   // anchors pre-divided by stride on the host
-                o = a.mode == 0 ? e / G : e * S;
-            }
-            a.box4[(size_t)r_row * 4 + l15] = o;
+            a.box4[(size_t)r_row * 4 + l15] = yolo_box_attr(l15, g_raw, r_cell % r_g, r_cell / r_g, a.h[r_hd].anchors + 2 * r_an, (float)r_g, (float)(a.img_size / r_g), a.mode);
             if (l15 == 0) { scores[r_row] = rbest; labels[r_row] = rlabel; }
         }
     }
@@ -469,14 +407,8 @@ hipError_t launch_decode_v1(const float *raw, int raw_stride, int n, int side, i
 
 hipError_t launch_decode(const DecodeArgs &a, float *scores, int *labels, hipStream_t s)
 {
-    // the lean form (no decoded tensor) exists in the objectness-first and cell-per-wave kernels only
+    // the lean form (no decoded tensor) of a single head exists in the cell-per-wave kernel only
     if (!a.det && (a.region || !a.box4 || !scores || a.na * (5 + a.classes) > 256 || a.raw_stride < a.na * (5 + a.classes))) return hipErrorInvalidValue;
-    if (!a.det && a.reject_below > 0.f && 5 + a.classes <= 128) {
-        const size_t total = (size_t)a.n * a.g * a.g * a.na;
-        size_t blocks = (total + 255) / 256; if (blocks > 256 * 8) blocks = 256 * 8;
-        hipLaunchKernelGGL(k_decode_yolo_lean, dim3((unsigned)blocks), dim3(256), 0, s, a, scores, labels);
-        return hipGetLastError();
-    }
     if (a.region) {
         size_t total = (size_t)a.n * a.g * a.g * a.na;
         hipLaunchKernelGGL(k_decode_region, dim3((unsigned)((total + 127) / 128)), dim3(128), 0, s, a);
@@ -517,8 +449,7 @@ __global__ __launch_bounds__(256) void k_score_rows(const float *det, size_t nro
         float best = -INFINITY; int bi = 0x7fffffff;
         for (int k = lane; k < attrs - 5; k += 64) {
             // objectness_mode (V3/yolo_v3.py:385,397): gate on obj alone, class = argmax of the raw class scores
-            float sc = objectness_mode ? p[5 + k] : obj * p[5 + k];
-            if (sc > best) { best = sc; bi = k; }
+            first_max(best, bi, objectness_mode ? p[5 + k] : obj * p[5 + k], k);
         }
         wave_argmax(best, bi);
         if (lane == 0) { scores[r] = objectness_mode ? obj : best; labels[r] = bi; }
@@ -631,206 +562,202 @@ __device__ __forceinline__ float4 cand_box(const PostArgs &a, int img, int row, 
 #define NMS_POOL (NMS_FAST /*keys*/ + 2 * NMS_FAST /*boxes*/ + NMS_FAST / 2 * 3 /*label, score, row*/ + NMS_FAST * (NMS_FAST / 64) /*matrix*/)
 static_assert(NMS_POOL >= SORT_LDS + 512, "the general path's keys + alive bitset fit the pool");
 
-__global__ __launch_bounds__(NMS_THREADS) void k_nms_image(const PostArgs a)
+// one image's views of the workspace and of the result, and the workgroup's LDS
+struct NmsImage {
+    int img, img_h, img_w;
+    const float *scores; const int *labels;                          // [rows]
+    int *cand; unsigned long long *gkeys;                            // [rows], [rows_pow2]
+    float4 *sbox; int *slabel; float *sscore; int *srow;             // sorted candidates in global memory (general paths); srow only with rows_out
+    BoxOut *out; int *rows_out;                                      // [max_out]; rows_out may be null
+    unsigned long long *pool; int *wave_cnt, *s_base, *s_cur, *s_kept;
+    // the fast paths' carving of the pool: sorted candidates and the suppression bit matrix
+    __device__ float4 *lbox() const { return (float4 *)(pool + NMS_FAST); }
+    __device__ int *llabel() const { return (int *)(pool + 3 * NMS_FAST); }
+    __device__ float *lscore() const { return (float *)(llabel() + NMS_FAST); }
+    __device__ int *lrow() const { return llabel() + 2 * NMS_FAST; }
+    __device__ unsigned long long *mat() const { return pool + 3 * NMS_FAST + NMS_FAST / 2 * 3; }
+    __device__ unsigned int *alive() const { return (unsigned int *)(pool + SORT_LDS); }      // bitset for up to 32768 candidates (general paths)
+};
+
+// Sort key of candidate i (row `row`): descending score, ascending candidate index; the numpy-V3 flavour: per class (ascending), then
+// objectness descending, then candidate index
+__device__ __forceinline__ unsigned long long nms_key(const PostArgs &a, const NmsImage &c, int row, int i)
 {
-    float4 *sbox = a.sbox; int *slabel = a.slabel; float *sscore = a.sscore;
-    int img_h = a.img_h, img_w = a.img_w;
-    if (a.geom && a.geom_pixels && a.nms_mode == 1) { img_h = a.geom[blockIdx.x].h; img_w = a.geom[blockIdx.x].w; }      // V2's image_shape = this image's
-    __shared__ unsigned long long pool[NMS_POOL];
-    unsigned long long *const skeys = pool;
-    unsigned int *const alive = (unsigned int *)(pool + SORT_LDS);      // bitset for up to 32768 candidates (general path)
-    __shared__ int wave_cnt[NMS_THREADS / 64];
-    __shared__ int s_base, s_cur, s_kept;
+    unsigned int u = __float_as_uint(c.scores[row]);
+    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);       // monotone map of float order
+    if (a.nms_mode == 3) return ((unsigned long long)(c.labels[row] & 0x3ff) << 47) | ((unsigned long long)(~u) << 15) | (unsigned int)(i & 0x7fff);
+    return ((unsigned long long)(~u) << 32) | (unsigned int)i;
+}
+// word w of the alive set before any suppression: candidates 0 .. M-1
+template <typename W>
+__device__ __forceinline__ W alive_init(int w, int M)
+{
+    constexpr int B = 8 * (int)sizeof(W);
+    const int lo = w * B;
+    return lo >= M ? (W)0 : (M - lo >= B) ? ~(W)0 : (W)(((W)1 << (M - lo)) - 1);
+}
+// does the kept candidate i remove the later candidate j (of the sorted arrays box / label)?  The three flavours of the greedy scheme:
+// TF's / YOLOv1's (class-blind), darknet's and V2's numpy one (per class; V2 on int pixel boxes with a float64 ratio and the reference's
+// `!(v < thr)`).  CLASS_BLIND: the caller has established that the flavour is one of the first two
+template <bool CLASS_BLIND = false>
+__device__ __forceinline__ bool nms_kills(const PostArgs &a, const float4 *box, const int *label, int i, int j)
+{
+    const float4 bi = box[i], bj = box[j];
+    if (CLASS_BLIND || a.nms_mode == 0 || a.nms_mode == 4) return iou_tf(bi, bj) > a.iou_thr;
+    if (a.nms_mode == 2) return label[j] == label[i] && iou_darknet(bi, bj) > a.iou_thr;
+    const double v = iou_v2np(int4{(int)bi.x, (int)bi.y, (int)bi.z, (int)bi.w}, int4{(int)bj.x, (int)bj.y, (int)bj.z, (int)bj.w});
+    return label[j] == label[i] && !(v < (double)a.iou_thr);
+}
+// record `kept` = sorted candidate i (box b) of the arrays given
+__device__ __forceinline__ void nms_emit(const NmsImage &c, int kept, float4 b, const float *score, const int *label, const int *row, int i)
+{
+    c.out[kept] = BoxOut{b.x, b.y, b.z, b.w, score[i], label[i]};
+    if (c.rows_out) c.rows_out[kept] = row[i];
+}
 
-    const int img = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const float *scores = a.scores + (size_t)img * a.rows;
-    const int *labels = a.labels + (size_t)img * a.rows;
-    int *cand = a.cand + (size_t)img * a.rows;
-    unsigned long long *gkeys = a.keys + (size_t)img * a.rows_pow2;
-    sbox += (size_t)img * a.rows; slabel += (size_t)img * a.rows; sscore += (size_t)img * a.rows;
-    BoxOut *out = (BoxOut *)a.boxes_out + (size_t)img * a.max_out;
-
-    // unused record slots read as zeros (this replaces a memset node in front of every launch); the kept boxes are written by thread
-    // 0 after later barriers
-    for (int k = tid; k < a.max_out * (int)(sizeof(BoxOut) / 4); k += NMS_THREADS) ((unsigned *)out)[k] = 0u;
-    int *const rows_out = a.rows_out ? a.rows_out + (size_t)img * a.max_out : nullptr;
-    int *const srow = a.rows_out ? a.srow + (size_t)img * a.rows : nullptr;      // row of every sorted candidate
-    if (rows_out) for (int k = tid; k < a.max_out; k += NMS_THREADS) rows_out[k] = -1;
-    if (a.zero_word && img == 0 && tid == 0) *a.zero_word = 0u;      // the lean decode's list counter, for the next step
-    // (1) order-preserving compaction of rows whose score passes the threshold (tf.boolean_mask order).  Every wave owns a contiguous run
-    // of rows and keeps the ballots of its 64-row steps in LDS: two barriers in all (one per 1024 rows made this phase a third of the
-    // kernel: a barrier of sixteen waves costs ~0.4 us)
+// (1) order-preserving compaction of rows whose score passes the threshold (tf.boolean_mask order) into c.cand; returns their number.
+// Every wave owns a contiguous run of rows and keeps the ballots of its 64-row steps in LDS: two barriers in all (one per 1024 rows made
+// this phase a third of the kernel: a barrier of sixteen waves costs ~0.4 us)
+__device__ __forceinline__ int nms_threshold_compact(const PostArgs &a, const NmsImage &c)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int per_wave = ((a.rows + NMS_THREADS - 1) / NMS_THREADS) * 64;          // rows per wave, a multiple of 64 (<= 2048)
     const int steps = per_wave / 64;                                               // <= 32
-    unsigned long long *const wmask = pool + wv * 32;                              // this wave's ballots (the pool is free until the keys are built)
-    {
-        int cnt = 0;
-        const int r_lo = wv * per_wave;
-        // eight steps' loads in flight at a time (one load per step, each waited for by its ballot, was a chain of a dozen memory round trips)
-        for (int s0 = 0; s0 < steps; s0 += 8) {
-            float sv[8];
+    unsigned long long *const wmask = c.pool + wv * 32;                            // this wave's ballots (the pool is free until the keys are built)
+    const int r_lo = wv * per_wave;
+    int cnt = 0;
+    // eight steps' loads in flight at a time (one load per step, each waited for by its ballot, was a chain of a dozen memory round trips)
+    for (int s0 = 0; s0 < steps; s0 += 8) {
+        float sv[8];
 #pragma unroll
-            for (int u = 0; u < 8; ++u) { const int r = r_lo + (s0 + u) * 64 + lane; sv[u] = (s0 + u < steps && r < a.rows) ? scores[r] : -INFINITY; }
+        for (int u = 0; u < 8; ++u) { const int r = r_lo + (s0 + u) * 64 + lane; sv[u] = (s0 + u < steps && r < a.rows) ? c.scores[r] : -INFINITY; }
 #pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                if (s0 + u >= steps) break;
-                const int r = r_lo + (s0 + u) * 64 + lane;
-                const bool f = r < a.rows && (a.select_mode == 0 ? (sv[u] > a.score_thr) : (sv[u] >= a.score_thr));
-                const unsigned long long m = __ballot(f);
-                if (lane == 0) wmask[s0 + u] = m;
-                cnt += __popcll(m);
-            }
+        for (int u = 0; u < 8; ++u) {
+            if (s0 + u >= steps) break;
+            const int r = r_lo + (s0 + u) * 64 + lane;
+            const bool f = r < a.rows && (a.select_mode == 0 ? (sv[u] > a.score_thr) : (sv[u] >= a.score_thr));
+            const unsigned long long m = __ballot(f);
+            if (lane == 0) wmask[s0 + u] = m;
+            cnt += __popcll(m);
         }
-        if (lane == 0) wave_cnt[wv] = cnt;
     }
+    if (lane == 0) c.wave_cnt[wv] = cnt;
     __syncthreads();
-    {
-        int pre = 0, tot = 0;
-        for (int i = 0; i < NMS_THREADS / 64; ++i) { const int c = wave_cnt[i]; if (i < wv) pre += c; tot += c; }
-        const int r_lo = wv * per_wave;
-        for (int st = 0; st < steps; ++st) {
-            const unsigned long long m = wmask[st];
-            if ((m >> lane) & 1ull) cand[pre + __popcll(m & ((1ull << lane) - 1ull))] = r_lo + st * 64 + lane;
-            pre += __popcll(m);
-        }
-        if (tid == 0) s_base = tot;
+    int pre = 0, tot = 0;
+    for (int i = 0; i < NMS_THREADS / 64; ++i) { const int n = c.wave_cnt[i]; if (i < wv) pre += n; tot += n; }
+    for (int st = 0; st < steps; ++st) {
+        const unsigned long long m = wmask[st];
+        if ((m >> lane) & 1ull) c.cand[pre + __popcll(m & ((1ull << lane) - 1ull))] = r_lo + st * 64 + lane;
+        pre += __popcll(m);
     }
+    if (tid == 0) *c.s_base = tot;
     __syncthreads();
-    int M = s_base;
-    if (M <= NMS_FAST && a.nms_mode != 3) {
-        // ---- fast path: everything in LDS, five barriers (the general path pays two per kept box and ~40 for its sort).  Phase times at
-        //      ~150 candidates, 32 images (kernel trace, one MI355X): launch 4 us, compaction 2.5, keys + rank + gather 5, bit matrix 14, scan 5:
-        //      the matrix evaluates every later pair although a kept box is rare -- a lazily evaluated row per kept box is the next step.
-        //      Same keys, same gather arithmetic, same IoU functions and the same greedy
-        //      order as the general path below: identical records. ----
-        unsigned long long *const keys = pool;                                                  // [NMS_FAST]
-        float4 *const lbox = (float4 *)(pool + NMS_FAST);                                       // [NMS_FAST] sorted candidates
-        int *const llabel = (int *)(pool + 3 * NMS_FAST); float *const lscore = (float *)(llabel + NMS_FAST); int *const lrow = llabel + 2 * NMS_FAST;
-        unsigned long long *const mat = pool + 3 * NMS_FAST + NMS_FAST / 2 * 3;                 // [M][W] suppression bits
-        // (the barrier above also retired the ballots that shared the pool with the keys)
-        if (tid < M) {
-            unsigned int u = __float_as_uint(scores[cand[tid]]);
-            u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);       // monotone map of float order
-            keys[tid] = ((unsigned long long)(~u) << 32) | (unsigned int)tid;      // descending score, ascending candidate index
-        }
-        __syncthreads();
-        // rank sort: the keys are distinct, so a key's position is the number of smaller keys.  Eight lanes share a candidate (each
-        // counts an eighth of the keys; three shuffles add the parts up), two passes of the 1024 threads cover 256 candidates
-        for (int c0 = 0; c0 < M; c0 += NMS_THREADS / 8) {
-            const int ci = c0 + (tid >> 3), part = tid & 7;
-            const unsigned long long mykey = ci < M ? keys[ci] : 0ull;
-            int rank = 0;
-            for (int j = part; j < M; j += 8) rank += keys[j] < mykey ? 1 : 0;
-            rank += __shfl_xor(rank, 1); rank += __shfl_xor(rank, 2); rank += __shfl_xor(rank, 4);
-            if (ci < M && part == 0) {
-                const int row = cand[ci];
-                lbox[rank] = cand_box(a, img, row, img_h, img_w); llabel[rank] = labels[row]; lscore[rank] = scores[row]; lrow[rank] = row;
-            }
-        }
-        __syncthreads();
-        if (a.nms_mode == 1 && M > 400) M = 400;           // V2 numpy flavour keeps only the 400 best before NMS (bboxes_sort top_k, V2/utils.py:146-151)
-        const int W = (M + 63) >> 6;
-        // The flavours that stop at max_out kept boxes (TF's, YOLOv1's) need the suppression row of a KEPT box only, and kept boxes are
-        // few: one wave walks the candidates in order and forms the row of each box it keeps on the spot -- lane b evaluates the pair
-        // (i, 64 w + b), the ballot is the word -- instead of all M W words up front (14 of the kernel's 30 us for ~150 candidates, of which
-        // 20 rows were ever read).  Same pairs, same IoU function, same greedy order: identical records.
-        if ((a.nms_mode == 0 || a.nms_mode == 4) && a.max_out <= 64) {
-            if (wv == 0) {
-                unsigned long long al = 0;                   // lane w holds word w of the alive set
-                if (lane < W) { const int lo = lane * 64; al = (M - lo >= 64) ? ~0ull : ((1ull << (M - lo)) - 1ull); }
-                int kept = 0;
-                for (int w = 0; w < W && kept < a.max_out; ++w) {
-                    while (kept < a.max_out) {
-                        const unsigned long long cw = __shfl(al, w);      // (wave-uniform)
-                        if (!cw) break;
-                        const int i = 64 * w + (int)__builtin_ctzll(cw);
-                        const float4 bc = lbox[i];
-                        if (lane == 0) {
-                            out[kept] = BoxOut{bc.x, bc.y, bc.z, bc.w, lscore[i], llabel[i]};
-                            if (rows_out) rows_out[kept] = lrow[i];
-                        }
-                        ++kept;
-                        for (int ww = w; ww < W; ++ww) {
-                            const int j = 64 * ww + lane;
-                            const bool kill = j > i && j < M && iou_tf(bc, lbox[j < M ? j : i]) > a.iou_thr;
-                            unsigned long long bits = __ballot(kill);
-                            if (ww == w) bits |= 1ull << (i & 63);
-                            if (lane == ww) al &= ~bits;
-                        }
-                    }
-                }
-                if (lane == 0) a.counts_out[img] = kept;
-            }
-            return;
-        }
-        // suppression bits: word (i, w) bit b set <=> candidate i, when kept, removes the later candidate j = 64 w + b.  One wave per
-        // word: lane b evaluates the pair (i, 64 w + b), the ballot IS the word
-        for (int e = wv; e < M * W; e += NMS_THREADS / 64) {
-            const int i = e / W, w = e - i * W;
-            unsigned long long bits = 0;
-            if (64 * w + 63 > i) {                           // (wave-uniform)
-                const int j = 64 * w + lane;
-                bool kill = false;
-                if (j > i && j < M) {
-                    const float4 bc = lbox[i], bj = lbox[j];
-                    if (a.nms_mode == 0 || a.nms_mode == 4) kill = iou_tf(bc, bj) > a.iou_thr;
-                    else if (a.nms_mode == 2) kill = llabel[j] == llabel[i] && iou_darknet(bc, bj) > a.iou_thr;
-                    else {
-                        const double v = iou_v2np(int4{(int)bc.x, (int)bc.y, (int)bc.z, (int)bc.w}, int4{(int)bj.x, (int)bj.y, (int)bj.z, (int)bj.w});
-                        kill = llabel[j] == llabel[i] && !(v < (double)a.iou_thr);
-                    }
-                }
-                bits = __ballot(kill);
-            }
-            if (lane == 0) mat[e] = bits;
-        }
-        __syncthreads();
-        // greedy scan by ONE wave: lane w holds word w of the alive set
-        if (wv == 0) {
-            unsigned long long al = 0;
-            if (lane < W) { const int lo = lane * 64; al = (M - lo >= 64) ? ~0ull : ((1ull << (M - lo)) - 1ull); }
-            int kept = 0;
-            const bool capped = a.nms_mode == 0 || a.nms_mode == 4;
-            for (int w = 0; w < W; ++w) {
-                while (true) {
-                    const unsigned long long cw = __shfl(al, w);          // (wave-uniform)
-                    if (!cw || (capped && kept >= a.max_out)) break;
-                    const int i = 64 * w + (int)__builtin_ctzll(cw);
-                    if (kept < a.max_out && lane == 0) {
-                        const float4 bc = lbox[i];
-                        out[kept] = BoxOut{bc.x, bc.y, bc.z, bc.w, lscore[i], llabel[i]};
-                        if (rows_out) rows_out[kept] = lrow[i];
-                    }
-                    ++kept;
-                    unsigned long long kill = lane < W ? mat[i * W + lane] : 0ull;
-                    if (lane == w) kill |= 1ull << (i & 63);
-                    al &= ~kill;
-                }
-                if (capped && kept >= a.max_out) break;
-            }
-            if (lane == 0) a.counts_out[img] = min(kept, a.max_out);
-        }
-        return;
-    }
-    // V2 numpy flavour keeps only the 400 best before NMS (bboxes_sort top_k, V2/utils.py:146-151)
-    int P = 1; while (P < M) P <<= 1;
-    const bool in_lds = P <= SORT_LDS;
-    unsigned long long *keys = in_lds ? skeys : gkeys;
+    return *c.s_base;
+}
 
-    // (2) keys: descending score, ascending candidate index
-    for (int i = tid; i < P; i += NMS_THREADS) {
-        unsigned long long k = ~0ull;
-        if (i < M) {
-            unsigned int u = __float_as_uint(scores[cand[i]]);
-            u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);       // monotone map of float order
-            k = ((unsigned long long)(~u) << 32) | (unsigned int)i;
-            if (a.nms_mode == 3)       // per class (ascending), then objectness descending, then candidate index
-                k = ((unsigned long long)(labels[cand[i]] & 0x3ff) << 47) | ((unsigned long long)(~u) << 15) | (unsigned int)(i & 0x7fff);
+// ---- fast paths (M <= NMS_FAST): everything in LDS, five barriers (the general path pays two per kept box and ~40 for its sort).  Phase
+//      times at ~150 candidates, 32 images (kernel trace, one MI355X): launch 4 us, compaction 2.5, keys + rank + gather 5, bit matrix 14,
+//      scan 5.  Same keys, same gather arithmetic, same nms_kills and the same greedy order as the general path: identical records. ----
+// keys, rank sort and gather of the M candidates into the LDS arrays (two barriers)
+__device__ __forceinline__ void nms_sort_lds(const PostArgs &a, const NmsImage &c, int M)
+{
+    const int tid = threadIdx.x;
+    unsigned long long *const keys = c.pool;                                                // [NMS_FAST]
+    // (the compaction's last barrier also retired the ballots that shared the pool with the keys)
+    if (tid < M) keys[tid] = nms_key(a, c, c.cand[tid], tid);
+    __syncthreads();
+    // rank sort: the keys are distinct, so a key's position is the number of smaller keys.  Eight lanes share a candidate (each
+    // counts an eighth of the keys; three shuffles add the parts up), two passes of the 1024 threads cover 256 candidates
+    for (int c0 = 0; c0 < M; c0 += NMS_THREADS / 8) {
+        const int ci = c0 + (tid >> 3), part = tid & 7;
+        const unsigned long long mykey = ci < M ? keys[ci] : 0ull;
+        int rank = 0;
+        for (int j = part; j < M; j += 8) rank += keys[j] < mykey ? 1 : 0;
+        rank += __shfl_xor(rank, 1); rank += __shfl_xor(rank, 2); rank += __shfl_xor(rank, 4);
+        if (ci < M && part == 0) {
+            const int row = c.cand[ci];
+            c.lbox()[rank] = cand_box(a, c.img, row, c.img_h, c.img_w); c.llabel()[rank] = c.labels[row]; c.lscore()[rank] = c.scores[row]; c.lrow()[rank] = row;
         }
-        keys[i] = k;
     }
     __syncthreads();
-    // (3) bitonic sort, ascending
+}
+// The flavours that stop at max_out kept boxes (TF's, YOLOv1's) need the suppression row of a KEPT box only, and kept boxes are few: one
+// wave walks the candidates in order and forms the row of each box it keeps on the spot -- lane b evaluates the pair (i, 64 w + b), the
+// ballot is the word -- instead of all M W words up front (14 of the kernel's 30 us for ~150 candidates, of which 20 rows were ever read)
+__device__ __forceinline__ void nms_lazy(const PostArgs &a, const NmsImage &c, int M)
+{
+    const int lane = threadIdx.x & 63, W = (M + 63) >> 6;
+    if (threadIdx.x >> 6) return;
+    const float4 *const lbox = c.lbox();
+    unsigned long long al = alive_init<unsigned long long>(lane, M);      // lane w holds word w of the alive set
+    int kept = 0;
+    for (int w = 0; w < W && kept < a.max_out; ++w) {
+        while (kept < a.max_out) {
+            const unsigned long long cw = __shfl(al, w);      // (wave-uniform)
+            if (!cw) break;
+            const int i = 64 * w + (int)__builtin_ctzll(cw);
+            const float4 bc = lbox[i];
+            if (lane == 0) nms_emit(c, kept, bc, c.lscore(), c.llabel(), c.lrow(), i);
+            ++kept;
+            for (int ww = w; ww < W; ++ww) {
+                const int j = 64 * ww + lane;
+                const bool kill = j > i && j < M && nms_kills<true>(a, lbox, nullptr, i, j < M ? j : i);
+                unsigned long long bits = __ballot(kill);
+                if (ww == w) bits |= 1ull << (i & 63);
+                if (lane == ww) al &= ~bits;
+            }
+        }
+    }
+    if (lane == 0) a.counts_out[c.img] = kept;
+}
+// Suppression bit matrix, then a greedy scan by one wave (one barrier)
+__device__ __forceinline__ void nms_matrix(const PostArgs &a, const NmsImage &c, int M)
+{
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, W = (M + 63) >> 6;
+    const float4 *const lbox = c.lbox(); const int *const llabel = c.llabel();
+    unsigned long long *const mat = c.mat();                                                // [M][W]
+    // word (i, w) bit b set <=> candidate i, when kept, removes the later candidate j = 64 w + b.  One wave per word: lane b evaluates
+    // the pair (i, 64 w + b), the ballot IS the word
+    for (int e = wv; e < M * W; e += NMS_THREADS / 64) {
+        const int i = e / W, w = e - i * W;
+        unsigned long long bits = 0;
+        if (64 * w + 63 > i) {                           // (wave-uniform)
+            const int j = 64 * w + lane;
+            bits = __ballot(j > i && j < M && nms_kills(a, lbox, llabel, i, j));
+        }
+        if (lane == 0) mat[e] = bits;
+    }
+    __syncthreads();
+    if (wv) return;
+    unsigned long long al = alive_init<unsigned long long>(lane, M);      // lane w holds word w of the alive set
+    int kept = 0;
+    const bool capped = a.nms_mode == 0 || a.nms_mode == 4;
+    for (int w = 0; w < W; ++w) {
+        while (true) {
+            const unsigned long long cw = __shfl(al, w);          // (wave-uniform)
+            if (!cw || (capped && kept >= a.max_out)) break;
+            const int i = 64 * w + (int)__builtin_ctzll(cw);
+            if (kept < a.max_out && lane == 0) nms_emit(c, kept, lbox[i], c.lscore(), llabel, c.lrow(), i);
+            ++kept;
+            unsigned long long kill = lane < W ? mat[i * W + lane] : 0ull;
+            if (lane == w) kill |= 1ull << (i & 63);
+            al &= ~kill;
+        }
+        if (capped && kept >= a.max_out) break;
+    }
+    if (lane == 0) a.counts_out[c.img] = min(kept, a.max_out);
+}
+
+// ---- general paths (any M): keys + bitonic sort in LDS (or in global memory above SORT_LDS), the sorted candidates in global memory,
+//      the alive bitset in LDS.  Returns M after V2's top-400 cut. ----
+__device__ __forceinline__ int nms_sort_global(const PostArgs &a, const NmsImage &c, int M)
+{
+    const int tid = threadIdx.x;
+    int P = 1; while (P < M) P <<= 1;
+    unsigned long long *const keys = P <= SORT_LDS ? c.pool : c.gkeys;
+    for (int i = tid; i < P; i += NMS_THREADS) keys[i] = i < M ? nms_key(a, c, c.cand[i], i) : ~0ull;
+    __syncthreads();
+    // bitonic sort, ascending
     for (int k = 2; k <= P; k <<= 1)
         for (int j = k >> 1; j > 0; j >>= 1) {
             for (int i = tid; i < P; i += NMS_THREADS) {
@@ -843,84 +770,81 @@ __global__ __launch_bounds__(NMS_THREADS) void k_nms_image(const PostArgs a)
             }
             __syncthreads();
         }
-    if (a.nms_mode == 1 && M > 400) M = 400;
-    // (4) gather candidates in sorted order
+    if (a.nms_mode == 1 && M > 400) M = 400;           // V2 numpy flavour keeps only the 400 best before NMS (bboxes_sort top_k, V2/utils.py:146-151)
+    // gather candidates in sorted order
     for (int i = tid; i < M; i += NMS_THREADS) {
-        int row = cand[(unsigned int)(keys[i] & (a.nms_mode == 3 ? 0x7fffu : 0xffffffffu))];
-        const float4 b = cand_box(a, img, row, img_h, img_w);
-        sbox[i] = b; slabel[i] = labels[row]; sscore[i] = scores[row];
-        if (srow) srow[i] = row;
+        int row = c.cand[(unsigned int)(keys[i] & (a.nms_mode == 3 ? 0x7fffu : 0xffffffffu))];
+        c.sbox[i] = cand_box(a, c.img, row, c.img_h, c.img_w); c.slabel[i] = c.labels[row]; c.sscore[i] = c.scores[row];
+        if (c.srow) c.srow[i] = row;
     }
-    for (int i = tid; i < 1024; i += NMS_THREADS) {
-        int lo = i * 32;
-        unsigned int bits = 0;
-        if (lo < M) bits = (M - lo >= 32) ? 0xffffffffu : ((1u << (M - lo)) - 1u);
-        alive[i] = bits;
-    }
-    if (tid == 0) { s_cur = -1; s_kept = 0; }
+    for (int i = tid; i < 1024; i += NMS_THREADS) c.alive()[i] = alive_init<unsigned int>(i, M);
+    if (tid == 0) { *c.s_cur = -1; *c.s_kept = 0; }
     __syncthreads();
-
-    if (a.nms_mode == 3) {
-        // Reference numpy NMS (V3/yolo_v3.py:376-420), class by class over the sorted list.  The reference filters
-        // `cls_scores` with indices taken on `cls_boxes[1:]` (:414-418), so after every round each survivor
-        // inherits the score of the element that preceded it in the current list -- reproduced here.
+    return M;
+}
+// Reference numpy NMS (V3/yolo_v3.py:376-420), class by class over the sorted list.  The reference filters `cls_scores` with indices
+// taken on `cls_boxes[1:]` (:414-418), so after every round each survivor inherits the score of the element that preceded it in the
+// current list -- reproduced here.
+__device__ __forceinline__ void nms_numpy_v3(const PostArgs &a, const NmsImage &c, int M)
+{
+    const int tid = threadIdx.x;
+    unsigned int *const alive = c.alive();
+    __syncthreads();
+    int *list = c.cand;                             // compacted alive positions (cand is free after the gather)
+    float *tmp = (float *)c.gkeys;                  // scratch for the shifted scores (keys are free as well)
+    __shared__ int s_seg_end;
+    int seg = 0;
+    while (seg < M) {
+        if (tid == 0) { int e = seg + 1; const int lc = c.slabel[seg]; while (e < M && c.slabel[e] == lc) ++e; s_seg_end = e; }
         __syncthreads();
-        int *list = cand;                               // compacted alive positions (cand is free after the gather)
-        float *tmp = (float *)gkeys;                    // scratch for the shifted scores (keys are free as well)
-        __shared__ int s_seg_end;
-        int seg = 0;
-        while (seg < M) {
-            if (tid == 0) { int e = seg + 1; const int lc = slabel[seg]; while (e < M && slabel[e] == lc) ++e; s_seg_end = e; }
+        const int seg_end = s_seg_end;
+        while (true) {
+            // compact the alive positions of this class segment, in order
+            if (tid == 0) *c.s_base = 0;
             __syncthreads();
-            const int seg_end = s_seg_end;
-            while (true) {
-                // compact the alive positions of this class segment, in order
-                if (tid == 0) s_base = 0;
+            for (int r0 = seg; r0 < seg_end; r0 += NMS_THREADS) {
+                const int j = r0 + tid;
+                const bool f = j < seg_end && ((alive[j >> 5] >> (j & 31)) & 1u);
+                int tot;
+                const int rank = block_rank(f, c.wave_cnt, tot);
+                const int base = *c.s_base;
+                if (f) list[base + rank] = j;
                 __syncthreads();
-                for (int r0 = seg; r0 < seg_end; r0 += NMS_THREADS) {
-                    int j = r0 + tid;
-                    bool f = j < seg_end && ((alive[j >> 5] >> (j & 31)) & 1u);
-                    unsigned long long m = __ballot(f);
-                    if (lane == 0) wave_cnt[wv] = __popcll(m);
-                    __syncthreads();
-                    int pre = 0, tot = 0;
-                    for (int i = 0; i < NMS_THREADS / 64; ++i) { int c = wave_cnt[i]; if (i < wv) pre += c; tot += c; }
-                    int base = s_base;
-                    if (f) list[base + pre + __popcll(m & ((1ull << lane) - 1))] = j;
-                    __syncthreads();
-                    if (tid == 0) s_base = base + tot;
-                    __syncthreads();
-                }
-                const int len = s_base;
-                if (len == 0) break;
-                const int head = list[0];
-                const float4 bh = sbox[head];
-                const int kept = s_kept;
-                if (tid == 0) {
-                    if (kept < a.max_out) { out[kept] = BoxOut{bh.x, bh.y, bh.z, bh.w, sscore[head], slabel[head]}; if (rows_out) rows_out[kept] = srow[head]; }
-                    s_kept = kept + 1;
-                    atomicAnd(&alive[head >> 5], ~(1u << (head & 31)));
-                }
-                for (int m2 = 1 + tid; m2 < len; m2 += NMS_THREADS) {
-                    const int j = list[m2];
-                    if (iou_numpy_v3(bh, sbox[j]) < a.iou_thr) tmp[j] = sscore[list[m2 - 1]];     // survivor: shifted score
-                    else atomicAnd(&alive[j >> 5], ~(1u << (j & 31)));
-                }
-                __syncthreads();
-                for (int m2 = 1 + tid; m2 < len; m2 += NMS_THREADS) {
-                    const int j = list[m2];
-                    if ((alive[j >> 5] >> (j & 31)) & 1u) sscore[j] = tmp[j];
-                }
+                if (tid == 0) *c.s_base = base + tot;
                 __syncthreads();
             }
-            seg = seg_end;
+            const int len = *c.s_base;
+            if (len == 0) break;
+            const int head = list[0];
+            const float4 bh = c.sbox[head];
+            const int kept = *c.s_kept;
+            if (tid == 0) {
+                if (kept < a.max_out) nms_emit(c, kept, bh, c.sscore, c.slabel, c.srow, head);
+                *c.s_kept = kept + 1;
+                atomicAnd(&alive[head >> 5], ~(1u << (head & 31)));
+            }
+            for (int m2 = 1 + tid; m2 < len; m2 += NMS_THREADS) {
+                const int j = list[m2];
+                if (iou_numpy_v3(bh, c.sbox[j]) < a.iou_thr) tmp[j] = c.sscore[list[m2 - 1]];     // survivor: shifted score
+                else atomicAnd(&alive[j >> 5], ~(1u << (j & 31)));
+            }
+            __syncthreads();
+            for (int m2 = 1 + tid; m2 < len; m2 += NMS_THREADS) {
+                const int j = list[m2];
+                if ((alive[j >> 5] >> (j & 31)) & 1u) c.sscore[j] = tmp[j];
+            }
             __syncthreads();
         }
-        if (tid == 0) a.counts_out[img] = min(s_kept, a.max_out);
-        return;
+        seg = seg_end;
+        __syncthreads();
     }
-
-    // (5) greedy: the best alive candidate is kept and suppresses every later one it overlaps
+    if (tid == 0) a.counts_out[c.img] = min(*c.s_kept, a.max_out);
+}
+// greedy: the best alive candidate is kept and suppresses every later one it overlaps (two barriers per kept box)
+__device__ __forceinline__ void nms_general(const PostArgs &a, const NmsImage &c, int M)
+{
+    const int tid = threadIdx.x;
+    unsigned int *const alive = c.alive();
     int pos = 0;
     while (true) {
         if (tid == 0) {
@@ -930,33 +854,58 @@ __global__ __launch_bounds__(NMS_THREADS) void k_nms_image(const PostArgs a)
                 if (wd == (pos >> 5)) bits &= ~((1u << (pos & 31)) - 1u);
                 if (bits) { cur = wd * 32 + __ffs(bits) - 1; break; }
             }
-            s_cur = cur;
+            *c.s_cur = cur;
         }
         __syncthreads();
-        const int cur = s_cur, kept = s_kept;
+        const int cur = *c.s_cur, kept = *c.s_kept;
         if (cur < 0 || ((a.nms_mode == 0 || a.nms_mode == 4) && kept >= a.max_out)) break;
-        const float4 bc = sbox[cur];
-        const int lc = slabel[cur];
         if (tid == 0) {
-            if (kept < a.max_out) { out[kept] = BoxOut{bc.x, bc.y, bc.z, bc.w, sscore[cur], lc}; if (rows_out) rows_out[kept] = srow[cur]; }
-            s_kept = kept + 1;
+            if (kept < a.max_out) nms_emit(c, kept, c.sbox[cur], c.sscore, c.slabel, c.srow, cur);
+            *c.s_kept = kept + 1;
         }
         for (int j = cur + 1 + tid; j < M; j += NMS_THREADS) {
             if (!((alive[j >> 5] >> (j & 31)) & 1u)) continue;
-            bool kill;
-            if (a.nms_mode == 0 || a.nms_mode == 4) kill = iou_tf(bc, sbox[j]) > a.iou_thr;
-            else if (a.nms_mode == 2) kill = slabel[j] == lc && iou_darknet(bc, sbox[j]) > a.iou_thr;
-            else {
-                float4 bj = sbox[j];
-                double v = iou_v2np(int4{(int)bc.x, (int)bc.y, (int)bc.z, (int)bc.w}, int4{(int)bj.x, (int)bj.y, (int)bj.z, (int)bj.w});
-                kill = slabel[j] == lc && !(v < (double)a.iou_thr);
-            }
-            if (kill) atomicAnd(&alive[j >> 5], ~(1u << (j & 31)));
+            if (nms_kills(a, c.sbox, c.slabel, cur, j)) atomicAnd(&alive[j >> 5], ~(1u << (j & 31)));
         }
         pos = cur + 1;
         __syncthreads();
     }
-    if (tid == 0) a.counts_out[img] = min(s_kept, a.max_out);
+    if (tid == 0) a.counts_out[c.img] = min(*c.s_kept, a.max_out);
+}
+
+__global__ __launch_bounds__(NMS_THREADS) void k_nms_image(const PostArgs a)
+{
+    __shared__ unsigned long long pool[NMS_POOL];
+    __shared__ int wave_cnt[NMS_THREADS / 64];
+    __shared__ int s_base, s_cur, s_kept;
+    const int img = blockIdx.x, tid = threadIdx.x;
+    const size_t r0 = (size_t)img * a.rows, o0 = (size_t)img * a.max_out;
+    NmsImage c;
+    c.img = img; c.img_h = a.img_h; c.img_w = a.img_w;
+    if (a.geom && a.geom_pixels && a.nms_mode == 1) { c.img_h = a.geom[img].h; c.img_w = a.geom[img].w; }      // V2's image_shape = this image's
+    c.scores = a.scores + r0; c.labels = a.labels + r0; c.cand = a.cand + r0; c.gkeys = a.keys + (size_t)img * a.rows_pow2;
+    c.sbox = a.sbox + r0; c.slabel = a.slabel + r0; c.sscore = a.sscore + r0;
+    c.srow = a.rows_out ? a.srow + r0 : nullptr;                       // row of every sorted candidate
+    c.out = (BoxOut *)a.boxes_out + o0; c.rows_out = a.rows_out ? a.rows_out + o0 : nullptr;
+    c.pool = pool; c.wave_cnt = wave_cnt; c.s_base = &s_base; c.s_cur = &s_cur; c.s_kept = &s_kept;
+
+    // unused record slots read as zeros (this replaces a memset node in front of every launch); the kept boxes are written by thread
+    // 0 after later barriers
+    for (int k = tid; k < a.max_out * (int)(sizeof(BoxOut) / 4); k += NMS_THREADS) ((unsigned *)c.out)[k] = 0u;
+    if (c.rows_out) for (int k = tid; k < a.max_out; k += NMS_THREADS) c.rows_out[k] = -1;
+    if (a.zero_word && img == 0 && tid == 0) *a.zero_word = 0u;      // the lean decode's list counter, for the next step
+
+    int M = nms_threshold_compact(a, c);
+    if (M <= NMS_FAST && a.nms_mode != 3) {
+        nms_sort_lds(a, c, M);
+        if (a.nms_mode == 1 && M > 400) M = 400;           // V2 numpy flavour keeps only the 400 best before NMS (bboxes_sort top_k, V2/utils.py:146-151)
+        if ((a.nms_mode == 0 || a.nms_mode == 4) && a.max_out <= 64) nms_lazy(a, c, M);
+        else nms_matrix(a, c, M);
+        return;
+    }
+    M = nms_sort_global(a, c, M);
+    if (a.nms_mode == 3) nms_numpy_v3(a, c, M);
+    else nms_general(a, c, M);
 }
 
 // the kept records of a stretched image, scaled to its source pixels after NMS: `convert_to_original_size` of the reference's V3 scripts,
@@ -1080,7 +1029,7 @@ __global__ __launch_bounds__(1024) void k_darknet_boxes(const DnBoxesArgs a)
 {
     __shared__ int s_wave[16];
     __shared__ int s_base;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tid = threadIdx.x;
     if (tid == 0) s_base = 0;
     __syncthreads();
     for (int hd = 0; hd < a.nheads; ++hd) {
@@ -1106,12 +1055,9 @@ __global__ __launch_bounds__(1024) void k_darknet_boxes(const DnBoxesArgs a)
             for (int r0 = 0; r0 < rows; r0 += 1024) {
                 const int r = r0 + tid;
                 const bool keep = r < rows && a.det[(size_t)(a.off[hd] + r) * a.attrs + 4] > a.thresh;
-                const unsigned long long m = __ballot(keep);
-                if (lane == 0) s_wave[wv] = __popcll(m);
-                __syncthreads();
-                int before = s_base, total = 0;
-                for (int k = 0; k < 16; ++k) { if (k < wv) before += s_wave[k]; total += s_wave[k]; }
-                if (keep) { const int pos = before + __popcll(m & ((1ull << lane) - 1ull)); if (pos < a.cap) a.src[pos] = a.off[hd] + r; }
+                int total;
+                const int rank = block_rank(keep, s_wave, total), pos = s_base + rank;
+                if (keep && pos < a.cap) a.src[pos] = a.off[hd] + r;
                 __syncthreads();
                 if (tid == 0) s_base += total;
                 __syncthreads();

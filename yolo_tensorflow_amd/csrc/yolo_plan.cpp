@@ -470,7 +470,7 @@ int allocate(yolo_ctx *c)
     }
     HIPCK(c, hipMalloc((void **)&c->d_det, nr * (c->attrs ? c->attrs : 1) * 4));
     HIPCK(c, hipMalloc((void **)&c->d_box4, nr * 16));
-    HIPCK(c, hipMalloc(&c->d_lean_list, nr * 16)); HIPCK(c, hipMalloc((void **)&c->d_lean_cnt, 16)); HIPCK(c, hipMemsetAsync(c->d_lean_cnt, 0, 16, c->stream));
+    HIPCK(c, hipMalloc(&c->d_lean_list, nr * 16)); HIPCK(c, hipMalloc((void **)&c->d_lean_cnt, 4)); HIPCK(c, hipMemsetAsync(c->d_lean_cnt, 0, 4, c->stream));
     c->lean_ok = true;                  // every head a [yolo] head the cell-per-wave decode serves
     for (auto &L : c->layers) {
         if (L.type == L_REGION || L.type == L_DETECT) c->lean_ok = false;

@@ -198,7 +198,7 @@ int run_layer(yolo_ctx *c, int i, int n)
                                   c->d_scores, c->d_labels, s));
         break; }
     case L_YOLO: case L_REGION: {
-        if (c->lean && c->lean_thr > 0.f && c->lean_heads >= 1 && c->lean_heads <= 4 && !getenv("YOLO_NO_LEAN_MULTI")) {
+        if (c->lean && c->lean_thr > 0.f && c->lean_heads >= 1 && c->lean_heads <= 4) {
             // lean detect path: every [yolo] head is decoded by ONE launch, issued at the last head (the head tensors keep their own buffers)
             bool later_head = false;
             for (size_t k = i + 1; k < c->layers.size(); ++k) later_head |= c->layers[k].type == L_YOLO;
@@ -219,7 +219,7 @@ int run_layer(yolo_ctx *c, int i, int n)
             la.box4 = c->d_box4; la.reject_below = c->lean_thr; la.list = (uint4 *)c->d_lean_list; la.list_count = c->d_lean_cnt; la.list_cap = (unsigned)((size_t)c->max_batch * c->rows);
             // the list counter must be zero: the NMS launch of the previous detect call resets it; if none ran since the last decode
             // (a failed call in between), a memset does
-            if (c->lean_cnt_dirty) HIPCK(c, hipMemsetAsync(c->d_lean_cnt, 0, 16, s));
+            if (c->lean_cnt_dirty) HIPCK(c, hipMemsetAsync(c->d_lean_cnt, 0, 4, s));
             c->lean_cnt_dirty = true;
             HIPCK(c, launch_decode_lean(la, c->d_scores, c->d_labels, s));
             break;
@@ -489,7 +489,7 @@ int yolo_detect_graph(yolo_ctx *c, const void *images, int n, int fmt, float sca
     }
     // the captured step holds no reset of the lean decode's list counter (its NMS node leaves it at zero): a step that failed between
     // its decode and its NMS since then left it set
-    if (c->lean_cnt_dirty) { HIPCK(c, hipMemsetAsync(c->d_lean_cnt, 0, 16, c->stream)); c->lean_cnt_dirty = false; }
+    if (c->lean_cnt_dirty) { HIPCK(c, hipMemsetAsync(c->d_lean_cnt, 0, 4, c->stream)); c->lean_cnt_dirty = false; }
     HIPCK(c, hipGraphLaunch(c->gexec, c->stream));
     // the replay leaves the context exactly as the eager call it was captured from would (run_network / forward_impl): a later
     // yolo_postprocess / yolo_darknet_boxes must see that the decoded tensor was (not) written and which threshold pruned the scores
@@ -623,7 +623,7 @@ int yolo_detect_images_graph(yolo_ctx *c, const uint8_t *pixels, size_t bytes, c
         if (e != hipSuccess) { (void)hipGetLastError(); c->gexec_img = nullptr; c->gstate_img = -1; return eager(); }
         c->gstate_img = 2;
     }
-    if (c->lean_cnt_dirty) { HIPCK(c, hipMemsetAsync(c->d_lean_cnt, 0, 16, c->stream)); c->lean_cnt_dirty = false; }      // see yolo_detect_graph
+    if (c->lean_cnt_dirty) { HIPCK(c, hipMemsetAsync(c->d_lean_cnt, 0, 4, c->stream)); c->lean_cnt_dirty = false; }      // see yolo_detect_graph
     HIPCK(c, hipGraphLaunch(c->gexec_img, c->stream));
     c->lean = lean && c->lean_ok; c->det_valid = !c->lean; c->lean_thr = score_thr;
     c->last_n = n; c->scores_mode = nms_mode == YOLO_NMS_NUMPY_V3 ? 1 : 0; c->stem_u8 = nullptr; c->geom_fit = fit; c->geom_n = n;
