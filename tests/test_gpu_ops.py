@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 from conftest import golden
 from oracle import yolo_ref as R
+from oracle import postprocess_ref as P
 
 pytestmark = pytest.mark.gpu
 
@@ -279,6 +280,12 @@ def test_postprocess_darknet_per_class(hiplib):
         want = sorted((float(kept[i, labels[i]]), int(labels[i])) for i in range(len(idx)) if kept[i, labels[i]] > 0)
         have = sorted((float(s), int(c)) for s, c in zip(got[b]["score"], got[b]["cls"]))
         assert have == want and len(have) > 0
+        # the complete records, (cx, cy, w, h) as darknet keeps them, in the device's order: score descending, ties to the lower row
+        rec, _ = P.postprocess_records(det[b], 0.5, 0.45, 400, P.NMS_DARKNET, P.SELECT_GT)
+        assert len(rec) == len(want) and np.array_equal(got[b], rec)
+        alive = kept[np.arange(len(idx)), labels] > 0
+        order = np.argsort(-scores, kind="stable")
+        assert np.array_equal(np.stack([got[b]["x0"], got[b]["y0"], got[b]["x1"], got[b]["y1"]], -1), det[b, idx[order][alive[order]], :4])
 
 
 def test_postprocess_v2_numpy_flavour(hiplib):
