@@ -267,7 +267,9 @@ int yolo_synchronize(yolo_ctx *ctx);
 
 /* ---- introspection / measurement ------------------------------------------------------------ */
 /* Copies layer `index`'s output of the last forward as fp32 NHWC [n,H,W,C] to host (needs
- * keep_layers=1).  dims_out receives H,W,C.  Head (yolo/region) layers return the raw conv tensor. */
+ * keep_layers=1; without it only a conv layer's own tensor that still sits in its buffer after the
+ * forward -- launched, no folded shortcut, buffer not reused by a later layer -- is served, anything else is
+ * YOLO_ERR_STATE).  dims_out receives H,W,C.  Head (yolo/region) layers return the raw conv tensor. */
 int yolo_layer_output(yolo_ctx *ctx, int index, int n, float *out, size_t out_floats, int *dims_out);
 /* Times `iters` forwards of batch n on the context stream with HIP events:
  * total_ms = wall per forward; conv_ms = the conv launches' share of it (all layers minus all-but-conv, bulk-timed)

@@ -189,6 +189,18 @@ hipError_t launch_conv_halo(const HaloArgs &a, hipStream_t s);
 // 3x3 / stride 2 / pad 1, 64 -> 128 channels, 16-bit storage, no shortcut (conv_s2.hip): same arguments (H, W: the INPUT size; k = tap*64 + ci)
 bool conv_s2_ok(const HaloArgs &a);
 hipError_t launch_conv_s2(const HaloArgs &a, hipStream_t s);
+// conv 3x3/s1 32 -> 64 + shortcut and the 3x3/s2 64 -> 128 conv that reads it, in one launch (conv_c3s2.hip): the tensor between them is never stored
+struct C3S2Args {
+    const void *in; int in_stride;            // [N,H,W,>=32]: input of the 3x3/s1 conv
+    const void *w3; const float *b3; int Kpad3, act3;         // 3x3/s1: [64 pad][Kpad3], k = tap*32 + ci
+    const void *res; int res_stride;          // shortcut source [N,H,W,>=64]
+    const void *w5; const float *b5; int Kpad5, act5;         // 3x3/s2: [128 pad][Kpad5], k = tap*64 + ci
+    void *out; int out_stride;                // [N,(H-1)/2+1,(W-1)/2+1,>=128]
+    int N, H, W;                              // size of the tensor between the two convs
+    int dt;                                   // DT_BF16 or DT_F16
+};
+bool conv_c3s2_ok(const C3S2Args &a);
+hipError_t launch_conv_c3s2(const C3S2Args &a, hipStream_t s);
 // fused residual block x + act2(conv3x3(act1(conv1x1(x)))), 128 -> 64 -> 128 channels, 16-bit storage (conv_block.hip)
 struct BlockArgs {
     const void *x; int x_stride;              // [N,H,W,>=128]: input of the 1x1 and source of the shortcut

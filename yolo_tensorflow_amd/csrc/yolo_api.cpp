@@ -76,8 +76,8 @@ double yolo_conv_bytes(const yolo_ctx *c, int n)
     for (auto &L : c->layers) if (L.type == L_CONV) {
         TView in = view_of(c, L.in[0]);
         const double ie = (double)dt_size(L.in_dt), oe = (double)dt_size(L.out.dt);
-        if (!L.stem && !L.stem_tail && !L.blk) b += (double)n * in.h * in.w * L.cin * ie;         // the fused stem / residual block keep these inputs in LDS
-        if (!L.stem_skip && !L.blk_skip && !L.pstem_skip) b += (double)n * L.H * L.W * L.filters * oe;
+        if (!L.stem && !L.stem_tail && !L.blk && !L.c3s2) b += (double)n * in.h * in.w * L.cin * ie;         // the fused stem / residual block / conv3 + stride-2 launch keep these inputs in LDS
+        if (!L.stem_skip && !L.blk_skip && !L.pstem_skip && !L.c3s2_skip) b += (double)n * L.H * L.W * L.filters * oe;
         b += (double)L.filters * L.cin * L.size * L.size * ie;
     }
     return b;
@@ -205,9 +205,15 @@ int yolo_synchronize(yolo_ctx *c) { if (!c) return YOLO_ERR_INVALID; HIPCK(c, hi
 int yolo_layer_output(yolo_ctx *c, int index, int n, float *out, size_t out_floats, int *dims_out)
 {
     if (!c) return YOLO_ERR_INVALID;
-    if (!c->keep_layers) return fail(c, YOLO_ERR_STATE, "yolo_layer_output needs keep_layers=1");
     if (index < 0 || index >= (int)c->layers.size() || n < 1 || n > c->last_n) return fail(c, YOLO_ERR_INVALID, "bad layer index / n");
     const Layer &L = c->layers[index];
+    if (!c->keep_layers) {
+        // the production plan pools its buffers and keeps fused-away tensors in LDS: only a conv that launches, writes its own tensor and
+        // whose buffer no later tensor takes over still holds its output after the forward
+        bool kept = L.type == L_CONV && L.storage >= 0 && L.residual_from < -1 && !L.stem_skip && !L.pstem_skip && !L.blk_skip && !L.c3s2_skip;
+        if (kept) for (const Storage &o : c->storages) if (&o != &c->storages[L.storage] && o.phys == c->storages[L.storage].phys && o.def > c->storages[L.storage].def) kept = false;
+        if (!kept) return fail(c, YOLO_ERR_STATE, "yolo_layer_output needs keep_layers=1 (without it: only a conv layer's own tensor whose buffer no later layer reuses)");
+    }
     if (dims_out) { dims_out[0] = L.H; dims_out[1] = L.W; dims_out[2] = L.C; }
     size_t need = (size_t)n * L.H * L.W * L.C;
     if (!out) return YOLO_OK;

@@ -45,6 +45,8 @@ struct Layer {
     bool stem_tail = false;                 // ... and this 1x1 conv (layer 2) is computed by that launch too
     bool halo = false;                      // 3x3/s1, 32 -> 64 channels: halo-staged kernel instead of the tiled one
     bool s2 = false;                        // 3x3/s2, 64 -> 128 channels: window-staged kernel with register-resident filters (conv_s2.hip)
+    bool c3s2_skip = false, c3s2 = false;   // conv3 + its folded shortcut + the stride-2 conv behind them in one launch (conv_c3s2.hip): this 3x3/s1 conv is computed inside
+                                            // the launch of the stride-2 conv two layers on / this stride-2 conv launches both; both keep their halo / s2 marks (the fall-back)
     // [connected] (YOLOv1's fully connected head, V1/YOLO_V1_Inference.py:196-206; DN/connected_layer.c:151): a 1x1 conv over the
     // producer's tensor flattened to one pixel per image; fc_h/w/c = the producer's geometry (darknet / the TF graph flatten CHW)
     bool fc = false; int fc_h = 0, fc_w = 0, fc_c = 0;

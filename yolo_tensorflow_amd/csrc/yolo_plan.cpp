@@ -312,6 +312,15 @@ int build_plan(yolo_ctx *c, const std::vector<Section> &secs)
                 L.filters == 128 && L.residual_from < -1 && is16(L.in_dt) && L.store_dt == L.in_dt && !L.pair && !c->pair_of(L.in[0]) && !getenv("YOLO_NO_S2"))
                 L.s2 = true;
         }
+    // conv3 + shortcut + stride-2 conv in one launch (conv_c3s2.hip): a halo conv whose folded shortcut output (layer i + 1) is read by
+    // the s2 conv at i + 2 and by nobody else -- that tensor then never leaves LDS.  Both layers keep their own marks: the two kernels
+    // are the fall-back where the fused launch's 32-bit windows do not hold the batch
+    if (ctx16 && !c->keep_layers && !getenv("YOLO_NO_C3S2"))
+        for (int i = 1; i + 2 < NL; ++i) {
+            Layer &A = c->layers[i], &S = c->layers[i + 1], &B = c->layers[i + 2];
+            if (A.halo && B.s2 && A.residual_from >= 0 && S.type == L_SHORTCUT && S.noop && uses[i] == 1 && uses[i + 1] == 1 && B.in[0] == i + 1 && A.in[0] >= 0 &&
+                A.in_dt == B.in_dt && c->layers[A.residual_from].C == 64) { A.c3s2_skip = true; B.c3s2 = true; }
+        }
     // 1x1 convs that can ride in their producer's epilogue: conv i (bf16, 128 or 256 output channels, optionally with its
     // fused shortcut) read by a 1x1/s1 conv with half as many filters
     if (ctx16 && !c->keep_layers) {
@@ -392,6 +401,10 @@ int build_plan(yolo_ctx *c, const std::vector<Section> &secs)
         if (!L.noop) { Storage &s = c->storages[L.storage]; s.def = std::min(s.def, L.fused_into >= 0 ? L.fused_into : i); s.last = std::max(s.last, i); }
         for (int j : L.in) if (j >= 0 && c->layers[j].storage >= 0) { Storage &s = c->storages[c->layers[j].storage]; s.last = std::max(s.last, i); }
         if (L.type == L_CONV && L.residual_from >= 0) { Storage &s = c->storages[c->layers[L.residual_from].storage]; s.last = std::max(s.last, i); }
+        if (L.c3s2) {           // this launch reads what the 3x3/s1 conv two layers back reads: its input and its shortcut source live until here
+            const Layer &A = c->layers[i - 2];
+            for (int j : {A.in[0], A.residual_from}) if (j >= 0 && c->layers[j].storage >= 0) { Storage &s = c->storages[c->layers[j].storage]; s.last = std::max(s.last, i); }
+        }
     }
     // greedy pooled assignment
     std::vector<int> free_list;
@@ -520,6 +533,6 @@ int allocate(yolo_ctx *c)
     return YOLO_OK;
 }
 
-bool fixed_kernel(const Layer &L) { return L.stem || L.stem_skip || L.stem_tail || L.halo || L.s2 || L.blk || L.blk_skip || L.pstem || L.pstem_skip; }
+bool fixed_kernel(const Layer &L) { return L.stem || L.stem_skip || L.stem_tail || L.halo || L.s2 || L.blk || L.blk_skip || L.pstem || L.pstem_skip || L.c3s2 || L.c3s2_skip; }
 
 }  // namespace yolo_impl

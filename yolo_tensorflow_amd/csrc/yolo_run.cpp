@@ -121,6 +121,20 @@ int run_layer(yolo_ctx *c, int i, int n)
                 break;
             }
         }
+        if (L.c3s2_skip || L.c3s2) {
+            // conv3 + shortcut (c3s2_skip) are computed inside the stride-2 conv's launch; were the batch window ever beyond the kernel's
+            // 32-bit offsets, both run as the layers they are (halo / s2 below)
+            const Layer &A = L.c3s2 ? c->layers[i - 2] : L, &B = L.c3s2 ? L : c->layers[i + 2];
+            const TView x = view_of(c, A.in[0]), r = view_of(c, A.residual_from);
+            C3S2Args t; memset(&t, 0, sizeof t);
+            t.in = x.ptr; t.in_stride = x.stride; t.w3 = A.d_w; t.b3 = A.d_b; t.Kpad3 = A.kpad; t.act3 = A.act; t.res = r.ptr; t.res_stride = r.stride;
+            t.w5 = B.d_w; t.b5 = B.d_b; t.Kpad5 = B.kpad; t.act5 = B.act; t.out = B.out.ptr; t.out_stride = B.out.stride;
+            t.N = n; t.H = A.H; t.W = A.W; t.dt = B.in_dt;
+            if (conv_c3s2_ok(t)) {
+                if (L.c3s2) HIPCK(c, launch_conv_c3s2(t, s));
+                break;
+            }
+        }
         ConvArgs a = conv_args(c, L, n);
         if (L.tail_on && !a.w2) return fail(c, YOLO_ERR_STATE, "layer %d: the plan folds the 1x1 conv %d into this layer, but its filters are not available in the producer's operand type", i, L.tail_layer);
         if (L.s2d7) HIPCK(c, launch_reorg(nview(c->input), nview(c->s2d), 2, 0, s));      // tf.space_to_depth order: (dy, dx, channel)
