@@ -10,7 +10,12 @@
  * Differences a caller can observe:
  *   - load_image_color decodes binary PPM / PGM only (the reference uses the vendored stb_image for JPEG / PNG);
  *   - do_nms_* leave the array order unchanged (the reference qsorts it in place);
- *   - [region] heads are served in their softmax form (no tree / map / mask coefficients), hier_thresh and map are ignored;
+ *   - [region] heads are served in their softmax form or with a softmax tree (`tree=`, YOLO9000): get_network_boxes honours
+ *     hier_thresh and map for the latter (no mask coefficients, no background=1).  A tree head follows the reference's GPU path,
+ *     temperature 1: its CPU path divides by a temperature parse_region never sets (DN/region_layer.c:179, DN/blas.c:314);
+ *   - get_network_boxes is idempotent.  The reference's hierarchy_predictions multiplies the layer output in place, so its second
+ *     call after one network_predict compounds the class probabilities of a tree head;
+ *   - a get_network_boxes `map` needs a head of at least 200 classes (the reference writes past prob[] otherwise): NULL is returned;
  *   - network_predict* return net->output for networks whose last layer is a [yolo] / [region] / [detection] head (every
  *     topology the reference's detectors use); precision is bf16 unless DARKNET_HIP_DTYPE=fp32 is set in the environment;
  *   - get_network_boxes reports the first image of a batch, as the reference does. */

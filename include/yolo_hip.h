@@ -361,6 +361,40 @@ int yolo_op_avgpool(const float *x, int n, int h, int w, int c, int dtype, float
 int yolo_op_softmax(const float *x, int n, int len, int groups, float temperature, int top_k, float *probs_out,
                     int32_t *classes_out, float *topk_probs_out, int device);
 
+/* ---- hierarchical softmax: darknet's softmax trees (`tree=` on a [region] or [softmax] section; YOLO9000, the tree classifiers) ----
+ * The tree file is opened as darknet opens it (relative to the working directory) when the context is created; an export artifact
+ * embeds it.  A [region] head with a tree decodes ABSOLUTE class probabilities (hierarchy_predictions, DN/tree.c:37-51) into the
+ * detection tensor; yolo_postprocess* / yolo_detect* score a box with its objectness and label it with hierarchy_top_prediction
+ * (DN/tree.c:53-81) at the context's hier_thresh.  A [softmax] layer with a tree outputs CONDITIONAL probabilities, as
+ * network_predict does. */
+enum yolo_hierarchy_mode { YOLO_HIER_CONDITIONAL = 0, YOLO_HIER_ABSOLUTE = 1, YOLO_HIER_LEAVES = 2 };
+/* hier_thresh of yolo_postprocess*, yolo_detect* and yolo_darknet_boxes* on a network with a tree head; default 0.5 (darknet.py's).
+ * No effect on other networks. */
+int yolo_set_hier_thresh(yolo_ctx *ctx, float hier_thresh);
+/* what yolo_classify* returns (and selects its top-k over) for a tree classifier: the conditional probabilities (default), the
+ * absolute ones (hierarchy_predictions), or the absolute ones with every inner node zeroed (only_leaves). */
+int yolo_set_hierarchy_mode(yolo_ctx *ctx, int mode);
+/* get_network_boxes with a `map` (DN/region_layer.c:415-420): yolo_darknet_boxes_at whose class columns are prob[j < 200] =
+ * objectness * absolute[map200[j]] gated by thresh, zeros beyond; map200 == NULL: yolo_darknet_boxes_at.  YOLO_ERR_INVALID for a
+ * head of fewer than 200 classes (the reference writes past prob[] there) or a map entry that is not a class. */
+int yolo_darknet_boxes_map(yolo_ctx *ctx, int image, int w, int h, float thresh, int relative, const int32_t *map200, float *records, int cap, int *count);
+/* The network's tree (the [region] head's, else the last [softmax] layer's that has one): node and group counts (0, 0: no tree) and,
+ * where a pointer is given, a copy of parent / child / leaf [nodes] and group_offset / group_size [groups] as DN/tree.c builds them. */
+int yolo_tree_geometry(const yolo_ctx *ctx, int32_t *nodes, int32_t *groups, int32_t *parent, int32_t *child, int32_t *group_offset,
+                       int32_t *group_size, int32_t *leaf);
+/* The same for a tree file, without a context or a device.  YOLO_ERR_INVALID with a message that names the line for a file that
+ * cannot be opened, a parent that is not below its own index, children that are not one contiguous run, a first parent other than -1. */
+int yolo_tree_read(const char *path, int32_t *nodes, int32_t *groups, int32_t *parent, int32_t *child, int32_t *group_offset, int32_t *group_size,
+                   int32_t *leaf, char *err, size_t err_len);
+/* Parse and plan a cfg for `dtype` without a device, with the defaults of a zeroed yolo_config (TF semantics, ratio decode, no
+ * keep_layers, batch 1): the planner's status and message, or YOLO_OK.  What only a device can tell (memory, the per-context
+ * batch limit) is not checked. */
+int yolo_plan_check(const char *cfg_text, int dtype, char *err, size_t err_len);
+/* single operators: x [n][len] fp32 logits, one softmax per group of the tree at tree_path, `mode` a yolo_hierarchy_mode -> out [n][len];
+ * hierarchy_top_prediction of n rows of raw logits (temperature 1) walking down from the root -> labels_out [n] */
+int yolo_op_tree_softmax(const float *x, int n, int len, const char *tree_path, float temperature, int mode, float *out, int device);
+int yolo_op_tree_top(const float *x_logits, int n, const char *tree_path, float hier_thresh, int32_t *labels_out, int device);
+
 #ifdef __cplusplus
 }
 #endif

@@ -255,7 +255,53 @@ def darknet19(size=256, classes=1000):
     return c.text()
 
 
+def synthetic_tree(nodes=9418, roots=10, seed=0, max_group=120):
+    """A seeded tree in darknet's file format (DN/tree.c:83-139: `name parent` lines, the children of a node one contiguous run, a
+    parent below its own index): the reference ships no 9k.tree.  Breadth-first: every run of siblings is appended whole, its size
+    drawn from a skewed distribution as WordNet's are (most nodes have few children, a few have many)."""
+    import random
+    rng = random.Random(seed)
+    parent = [-1] * roots
+    queue = list(range(roots))
+    while len(parent) < nodes and queue:
+        p = queue.pop(0)
+        if rng.random() < 0.35 and len(queue) > 2:
+            continue                                    # a leaf
+        k = min(nodes - len(parent), 1 + int(rng.paretovariate(1.1)) if rng.random() < 0.9 else rng.randint(20, max_group))
+        k = min(k, max_group)
+        queue.extend(range(len(parent), len(parent) + k))
+        parent.extend([p] * k)
+    while len(parent) < nodes:                          # the queue ran dry: hang the rest under the last node as one run
+        parent.append(len(parent) - 1) if parent[-1] != len(parent) - 2 else parent.append(parent[-1])
+    return "".join("n%05d %d\n" % (i, q) for i, q in enumerate(parent))
+
+
+YOLO9000_ANCHORS = [(0.77871, 1.14074), (3.00525, 4.31277), (9.22725, 9.61974)]
+
+
+def yolo9000(size=544, classes=9418, tree="9k.tree"):
+    """A YOLO9000-shaped detector (the other half of the YOLOv2 paper): the darknet-19 backbone, a 1x1 head of 3 x (5 + classes)
+    channels and a [region] layer whose class scores are a softmax tree (DN/region_layer.c:171-181).  At 544 x 544 the grid is
+    17 x 17.  `tree` names the tree file, opened relative to the working directory like darknet does."""
+    c = Cfg(size)
+    darknet19_backbone(c)
+    c.conv(len(YOLO9000_ANCHORS) * (5 + classes), 1, bn=False, act="linear")
+    c._sec("region", anchors=",  ".join(f"{a},{b}" for a, b in YOLO9000_ANCHORS), bias_match=1, classes=classes, coords=4,
+           num=len(YOLO9000_ANCHORS), softmax=1, tree=tree, jitter=.2, rescore=1, object_scale=5, noobject_scale=1, class_scale=1,
+           coord_scale=1, absolute=1, thresh=.6, random=0)
+    return c.text()
+
+
 def main():
+    import sys
+    if len(sys.argv) > 2 and sys.argv[1] == "--yolo9000":      # python tools/make_cfgs.py --yolo9000 DIR: yolo9000.cfg + its seeded tree
+        os.makedirs(sys.argv[2], exist_ok=True)
+        with open(os.path.join(sys.argv[2], "9k.tree"), "w") as f:
+            f.write(synthetic_tree())
+        with open(os.path.join(sys.argv[2], "yolo9000.cfg"), "w") as f:
+            f.write(yolo9000())
+        print("wrote yolo9000.cfg and 9k.tree (synthetic) to", sys.argv[2])
+        return
     os.makedirs(OUT, exist_ok=True)
     files = {
         "yolov1.cfg": yolov1(448), "yolov1-tiny.cfg": yolov1_tiny(448),

@@ -8,10 +8,12 @@ from . import hip, darknet_io as IO
 
 
 class Classifier:
-    def __init__(self, cfg_or_name, weights_file=None, dtype=hip.BF16, max_batch=1, names=None, device=0, fit=hip.FIT_STRETCH, seed=0):
+    def __init__(self, cfg_or_name, weights_file=None, dtype=hip.BF16, max_batch=1, names=None, device=0, fit=hip.FIT_STRETCH, seed=0, hierarchy=None):
         """cfg_or_name: a shipped topology ('darknet19', 'darknet53'), a cfg file path, or cfg text.  weights_file: a darknet
         `.weights` file; None loads darknet_io's seeded synthetic parameters (`seed`).  names: a list of class names or the path of a
-        file with one name per line; without it the class index stands in for the name."""
+        file with one name per line; without it the class index stands in for the name.  hierarchy (a [softmax] with tree=): None
+        returns the conditional probabilities network_predict gives, "absolute" the products along the path to the root
+        (hierarchy_predictions), "leaves" those with every inner node zeroed -- what darknet's classifier apps rank."""
         text = cfg_or_name if "[net]" in cfg_or_name or "[network]" in cfg_or_name else IO.cfg_text(cfg_or_name)
         self.engine = hip.Engine(text, max_batch=max_batch, dtype=dtype, semantics=hip.SEM_DARKNET, device=device)
         if self.engine.rows != 0:
@@ -21,6 +23,8 @@ class Classifier:
             self.engine.load_weights(weights_file)
         else:
             self.engine.set_weights(IO.synth_weights(IO.parse_cfg(text), seed=seed))
+        if hierarchy is not None:
+            self.engine.set_hierarchy_mode(hierarchy)
         self.max_batch, self.fit = max_batch, fit
         self.num_classes = self.engine.num_classes
         if isinstance(names, str):

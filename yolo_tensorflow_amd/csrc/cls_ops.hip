@@ -2,6 +2,7 @@
 // their output: DN/avgpool_layer.c:40-55, DN/blas.c:305-321, D2T/darknet.py:117-123).  Memory- and latency-bound: plain HIP, wave64,
 // 16-byte loads, fp32 arithmetic throughout, fixed reduction orders (a launch gives the same bits every time).
 #include "kernels.h"
+#include "wave_ops.h"
 #include <math.h>
 
 namespace {
@@ -99,8 +100,7 @@ __global__ __launch_bounds__(AP_NT) void k_avgpool(const void *in, int in_stride
 // ---- block-wide collectives (any whole number of waves up to 16; every lane gets the result; fixed order) ----
 __device__ __forceinline__ float block_max(float m, float *red)
 {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    m = wave_max(m);
     const int nw = blockDim.x >> 6;
     __syncthreads();
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
@@ -111,8 +111,7 @@ __device__ __forceinline__ float block_max(float m, float *red)
 }
 __device__ __forceinline__ float block_sum(float s, float *red)
 {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o, 64);
+    s = wave_sum(s);
     const int nw = blockDim.x >> 6;
     __syncthreads();
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
@@ -121,23 +120,6 @@ __device__ __forceinline__ float block_sum(float s, float *red)
     for (int w = 1; w < nw; ++w) r += red[w];
     return r;
 }
-// the order of classify()'s stable sort by -prob: larger probability first, equal probabilities by ascending index; index -1: nothing
-__device__ __forceinline__ bool ranks_before(float p2, int i2, float p1, int i1) { return i2 >= 0 && (i1 < 0 || p2 > p1 || (p2 == p1 && i2 < i1)); }
-__device__ __forceinline__ void block_best(float &p, int &i, float *red_p, int *red_i)
-{
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        const float p2 = __shfl_xor(p, o, 64); const int i2 = __shfl_xor(i, o, 64);
-        if (ranks_before(p2, i2, p, i)) { p = p2; i = i2; }
-    }
-    const int nw = blockDim.x >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) { red_p[threadIdx.x >> 6] = p; red_i[threadIdx.x >> 6] = i; }
-    __syncthreads();
-    p = red_p[0]; i = red_i[0];
-    for (int w = 1; w < nw; ++w) if (ranks_before(red_p[w], red_i[w], p, i)) { p = red_p[w]; i = red_i[w]; }
-}
-
 // softmax of the `len` logits in LDS at v (DN/blas.c:305-321: e = exp(x / temp - max / temp), p = e / sum), probabilities to
 // probs[0 .. len) and left in v; then, top_k > 0, the top_k best (probability descending, index ascending) to cls / tkp.
 // Called by every thread of the block.

@@ -145,14 +145,17 @@ detection *make_network_boxes(network *net, float thresh, int *num)
 // surviving boxes cross PCIe and are copied into darknet's structs here.
 detection *get_network_boxes(network *net, int w, int h, float thresh, float hier, int *map, int relative, int *num)
 {
-    (void)hier; (void)map;
     if (num) *num = 0;
     if (!net || !net->have) return nullptr;
     if (net->rows == 0) return (detection *)calloc(1, sizeof(detection));      // a classifier: no boxes
     const int A = net->attrs, C = A - 5;
     net->rec.resize((size_t)net->rows * A);
     int count = 0;
-    if (yolo_darknet_boxes(net->ctx, w, h, thresh, relative, net->rec.data(), net->rows, &count) != YOLO_OK) {
+    // `hier` and `map` are what a [region] head with a softmax tree reads (DN/region_layer.c:412-424); other heads ignore both
+    int32_t tree_nodes = 0;
+    yolo_tree_geometry(net->ctx, &tree_nodes, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    if (tree_nodes > 0 && yolo_set_hier_thresh(net->ctx, hier) != YOLO_OK) { fprintf(stderr, "darknet_hip: %s\n", yolo_last_error(net->ctx)); return nullptr; }
+    if (yolo_darknet_boxes_map(net->ctx, 0, w, h, thresh, relative, tree_nodes > 0 ? map : nullptr, net->rec.data(), net->rows, &count) != YOLO_OK) {
         fprintf(stderr, "darknet_hip: %s\n", yolo_last_error(net->ctx)); return nullptr;
     }
     detection *dets = (detection *)calloc(count > 0 ? count : 1, sizeof(detection));

@@ -282,6 +282,40 @@ hipError_t launch_softmax_topk(const SoftmaxArgs &a, hipStream_t s);
 bool avgpool_softmax_ok(const TView &in, const SoftmaxArgs &a);
 hipError_t launch_avgpool_softmax(const TView &in, float *pooled, int pooled_stride, const SoftmaxArgs &a, hipStream_t s);
 
+// ---- hierarchical softmax: darknet's softmax trees (tree_ops.hip; DN/tree.c, DN/softmax_layer.c:41-48, DN/region_layer.c:171-181) ----
+// A tree on the device.  parent / child / leaf [n], goff / gsize [groups] as DN/tree.c:83-139 builds them; order [groups]: the groups
+// sorted by depth (the root group first), lvl [levels + 1]: where each depth begins in `order`.  A group's parent node lies in a
+// shallower group, so a pass over `order` level by level forms every absolute probability as cond[j] * abs[parent[j]] exactly.
+struct TreeDev { int n, groups, levels; const int *parent, *child, *goff, *gsize, *leaf, *order, *lvl; };
+// where the n logits of row r lie: x + (r / na) * cell_stride + (r % na) * an_stride + off (a dense matrix: na 1, cell_stride = its
+// row stride; a [region] head's raw tensor: one cell per pixel, na boxes of 5 + classes values each, off 5)
+struct TreeRows { const float *x; size_t rows; int na, cell_stride, an_stride, off; };
+enum { TREE_CONDITIONAL = 0, TREE_ABSOLUTE = 1, TREE_LEAVES = 2 };
+// one softmax per group with e = exp(x / t - max / t) (DN/blas.c:305-321) -> out [rows][out_stride]; mode TREE_ABSOLUTE: then
+// hierarchy_predictions (DN/tree.c:37-51), TREE_LEAVES: with only_leaves.  top_k > 0: the best top_k of every row (the order of
+// launch_softmax_topk) to cls / topk_probs [rows][top_k]
+hipError_t launch_tree_softmax(const TreeDev &t, const TreeRows &x, float temperature, int mode, float *out, int out_stride,
+                               int top_k, int *cls, float *topk_probs, hipStream_t s);
+// hierarchy_top_prediction (DN/tree.c:53-81) of every row, walking down from the root over the raw logits: per step one group's
+// softmax (temperature 1), scaled by the parent's absolute probability.  labels [rows]
+hipError_t launch_tree_top(const TreeDev &t, const TreeRows &x, float hier_thresh, int *labels, hipStream_t s);
+struct DecodeArgs;
+// [region] head with a tree, full form: det rows (x, y, w, h, objectness, ABSOLUTE class probabilities)
+hipError_t launch_decode_region_tree(const DecodeArgs &a, const TreeDev &t, hipStream_t s);
+// ... its rows scored from those absolute probabilities: scores[row] = objectness, labels[row] = hierarchy_top_prediction;
+// det / scores / labels are [nrows] consecutive rows
+hipError_t launch_tree_score_rows(const float *det, size_t nrows, int attrs, const TreeDev &t, float hier_thresh, float *scores, int *labels, hipStream_t s);
+// ... descent form (yolo_detect*): box4, scores, labels of every row straight from the raw head tensor, no decoded tensor; the tree is
+// walked for the boxes whose objectness reaches a.reject_below only (the others: label 0)
+hipError_t launch_decode_region_tree_lean(const DecodeArgs &a, const TreeDev &t, float hier_thresh, float *scores, int *labels, hipStream_t s);
+// get_region_detections with a tree (DN/region_layer.c:412-424) over the records launch_darknet_boxes wrote (rec [count][attrs], src:
+// the decoded row of each): the class columns become zeros but prob[top prediction] = objectness > thresh ? objectness : 0, or,
+// with map (200 device ints), prob[j < 200] = objectness * abs[map[j]] gated by thresh
+hipError_t launch_darknet_tree_probs(const float *det, int attrs, const TreeDev &t, float thresh, float hier_thresh, const int *map200,
+                                     float *rec, const int *src, const int *count, int cap, hipStream_t s);
+// the tree form of launch_head_darknet_layout's region branch: conditional probabilities, planar
+hipError_t launch_head_darknet_layout_tree(const float *raw, int raw_stride, int cells, int na, int classes, const TreeDev &t, float *out, hipStream_t s);
+
 // ---- head decode + postprocess (post_ops.hip) ---------------------------------------------------
 struct DecodeArgs {
     const float *raw; int raw_stride;   // [n, g*g, raw_stride] fp32 head conv output
@@ -296,6 +330,26 @@ struct DecodeArgs {
                                         // (score = objectness * class probability <= objectness): its class work is skipped and its
                                         // score is reported as the objectness itself.  -inf: every box is scored
 };
+#ifdef __HIPCC__
+// Box and objectness of one [region] box, the ONE place this arithmetic is written (V2/decode.py:13-47; k_decode_region and its tree
+// twins): p the box's 5 + classes raw values, o (cx, cy, w, h, objectness) normalised by the grid size g
+__device__ __forceinline__ float region_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
+__device__ __forceinline__ float region_box_attr(int k, const float *p, int cell, int g, const float *anchor_wh)
+{
+    const float G = (float)g;
+    if (k == 0) return ((float)(cell % g) + region_sigmoid(p[0])) / G;
+    if (k == 1) return ((float)(cell / g) + region_sigmoid(p[1])) / G;
+    if (k == 2) return (anchor_wh[0] * expf(p[2])) / G;
+    if (k == 3) return (anchor_wh[1] * expf(p[3])) / G;
+    return region_sigmoid(p[4]);
+}
+// Attribute k < 5 of a box in darknet's layer-output layout (DN/yolo_layer.c:143-152, DN/region_layer.c:163-173): the logistic,
+// 1. / (1. + exp(-x)) in double like DN/activations.h:38, on x, y and objectness; w and h stay raw
+__device__ __forceinline__ float darknet_layout_box_attr(int k, const float *p)
+{
+    return (k == 2 || k == 3) ? p[k] : (float)(1. / (1. + exp(-(double)p[k])));
+}
+#endif
 // Lean decode of up to four [yolo] heads in ONE launch (yolo_detect*: the decodes of a three-scale network are three short,
 // latency-bound launches otherwise; the head tensors keep their own buffers, so the early heads can wait for the last one)
 struct LeanHead { const float *raw; const float *obj; int raw_stride, g, na, row_off; long box_begin; float anchors[2 * 16]; };      // obj: compact objectness-logit plane [n * g * g][na] written by the head conv, or nullptr (read from raw)

@@ -10,6 +10,7 @@
 // Built with -ffp-contract=off: every IoU is evaluated with the reference's operation order in fp32
 // (or fp64 for the V2 numpy flavour) so the kept set is bit-identical to the oracle on equal inputs.
 #include "kernels.h"
+#include "wave_ops.h"
 #include <math.h>
 
 struct BoxOut { float x0, y0, x1, y1, score; int cls; };
@@ -32,21 +33,6 @@ __device__ __forceinline__ float yolo_box_attr(int k, float x, int cx, int cy, c
 {
     const float t = k < 2 ? sigmoidf_(x) + (float)(k == 0 ? cx : cy) : expf(x) * anchor[k - 2];
     return mode == 0 ? t / G : t * S;
-}
-// One more class score of a box, taken in ascending class order: the strict > keeps the first maximum (argmax's choice)
-__device__ __forceinline__ void first_max(float &best, int &label, float sc, int k)
-{
-    if (sc > best) { best = sc; label = k; }
-}
-// wave-wide (value, first index) arg-max over lanes; every lane returns the result
-__device__ __forceinline__ void wave_argmax(float &v, int &idx)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        float ov = __shfl_xor(v, off);
-        int oi = __shfl_xor(idx, off);
-        if (ov > v || (ov == v && oi < idx)) { v = ov; idx = oi; }
-    }
 }
 
 // ---- D3 (+S): `_detection_layer` (V3/yolo_v3.py:111-159) / `_ratio_detection_layer` (V3/YOLOV3.py:168-238),
@@ -359,12 +345,8 @@ __global__ void k_decode_region(const DecodeArgs a)
     int cell = (int)(t % (a.g * a.g)); int b = (int)(t / (a.g * a.g));
     const float *p = a.raw + ((size_t)b * a.g * a.g + cell) * a.raw_stride + an * attrs;
     float *o = a.det + ((size_t)b * a.rows_total + a.row_off + (size_t)cell * a.na + an) * attrs;
-    const float G = (float)a.g;
-    o[0] = ((float)(cell % a.g) + sigmoidf_(p[0])) / G;
-    o[1] = ((float)(cell / a.g) + sigmoidf_(p[1])) / G;
-    o[2] = (a.anchors[2 * an] * expf(p[2])) / G;
-    o[3] = (a.anchors[2 * an + 1] * expf(p[3])) / G;
-    o[4] = sigmoidf_(p[4]);
+#pragma unroll
+    for (int k = 0; k < 5; ++k) o[k] = region_box_attr(k, p, cell, a.g, a.anchors + 2 * an);
     float mx = -INFINITY;
     for (int k = 0; k < a.classes; ++k) mx = fmaxf(mx, p[5 + k]);
     float sum = 0.f;
@@ -1123,10 +1105,10 @@ __global__ void k_head_darknet_layout(const float *raw, int raw_stride, int cell
     const int cell = r / na, n = r - cell * na, attrs = 5 + classes;
     const float *p = raw + (size_t)cell * raw_stride + n * attrs;
     float *o = out + (size_t)n * attrs * cells + cell;
-    auto lg = [](float x) { return (float)(1. / (1. + exp(-(double)x))); };
-    o[0] = lg(p[0]); o[(size_t)cells] = lg(p[1]); o[(size_t)2 * cells] = p[2]; o[(size_t)3 * cells] = p[3]; o[(size_t)4 * cells] = lg(p[4]);
+#pragma unroll
+    for (int k = 0; k < 5; ++k) o[(size_t)k * cells] = darknet_layout_box_attr(k, p);
     if (!region) {
-        for (int k = 0; k < classes; ++k) o[(size_t)(5 + k) * cells] = lg(p[5 + k]);
+        for (int k = 0; k < classes; ++k) o[(size_t)(5 + k) * cells] = darknet_layout_box_attr(0, p + 5 + k);
     } else {
         // softmax (DN/blas.c:305-321, temperature 1): largest first, exp(x - largest), normalised by the running sum
         float largest = -3.402823466e+38f;

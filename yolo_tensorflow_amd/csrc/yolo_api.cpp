@@ -38,6 +38,8 @@ void yolo_destroy(yolo_ctx *c)
     void *ptrs[] = {c->input.ptr, c->d_zeros, c->d_stage, c->d_det, c->d_scores, c->d_labels, c->d_cand, c->d_keys, c->d_sbox, c->d_slabel, c->d_sscore, c->d_boxes, c->d_counts,
                     c->d_dn_rec, c->d_dn_src, c->d_dn_count, c->d_dn_last, c->d_box4, c->s2d.ptr, c->d_srow, c->d_rows, c->d_lean_list, c->d_lean_cnt, c->d_f32a, c->d_f32b, c->d_descs, c->d_pix, c->d_cls_idx, c->d_cls_prob};
     for (void *p : ptrs) if (p) hipFree(p);
+    for (auto &t : c->trees) free_tree(t);
+    if (c->d_map200) hipFree(c->d_map200);
     if (c->gexec) hipGraphExecDestroy(c->gexec);
     if (c->gexec_img) hipGraphExecDestroy(c->gexec_img);
     if (c->own_stream && c->stream) hipStreamDestroy(c->stream);
@@ -91,7 +93,18 @@ int yolo_darknet_boxes(yolo_ctx *c, int w, int h, float thresh, int relative, fl
 
 int yolo_darknet_boxes_at(yolo_ctx *c, int image, int w, int h, float thresh, int relative, float *records, int cap, int *count)
 {
+    return yolo_darknet_boxes_map(c, image, w, h, thresh, relative, nullptr, records, cap, count);
+}
+
+int yolo_darknet_boxes_map(yolo_ctx *c, int image, int w, int h, float thresh, int relative, const int32_t *map200, float *records, int cap, int *count)
+{
     if (!c || !count) return YOLO_ERR_INVALID;
+    if (map200) {
+        // DN/region_layer.c:415-420 reads exactly 200 entries and writes prob[0 .. 200): with fewer classes the reference writes past prob[]
+        if (c->tree_head < 0) return fail(c, YOLO_ERR_INVALID, "yolo_darknet_boxes_map: the network has no [region] head with a tree");
+        if (c->attrs - 5 < 200) return fail(c, YOLO_ERR_INVALID, "yolo_darknet_boxes_map: a map has 200 entries and the head only %d classes", c->attrs - 5);
+        for (int j = 0; j < 200; ++j) if (map200[j] < 0 || map200[j] >= c->attrs - 5) return fail(c, YOLO_ERR_INVALID, "yolo_darknet_boxes_map: map[%d] = %d is not a class", j, (int)map200[j]);
+    }
     if (int r = need_detector(c, "yolo_darknet_boxes")) return r;
     if (c->last_n < 1 || !c->det_valid) return fail(c, YOLO_ERR_STATE, "yolo_darknet_boxes needs a yolo_forward* pass first");
     if (image < 0 || image >= c->last_n) return fail(c, YOLO_ERR_INVALID, "image %d outside the last forward's batch of %d", image, c->last_n);
@@ -121,6 +134,15 @@ int yolo_darknet_boxes_at(yolo_ctx *c, int image, int w, int h, float thresh, in
     a.cap = cap < c->rows ? cap : c->rows;
     a.rec = a.cap > 0 ? c->d_dn_rec : nullptr; a.src = c->d_dn_src; a.count = c->d_dn_count;
     HIPCK(c, launch_darknet_boxes(a, c->stream));
+    if (c->tree_head >= 0 && a.rec) {
+        // the class columns of a softmax-tree head (DN/region_layer.c:412-424), over the records just written
+        if (map200) {
+            if (!c->d_map200) HIPCK(c, hipMalloc((void **)&c->d_map200, 200 * 4));
+            HIPCK(c, hipMemcpyAsync(c->d_map200, map200, 200 * 4, hipMemcpyHostToDevice, c->stream));
+        }
+        HIPCK(c, launch_darknet_tree_probs(a.det, c->attrs, c->trees[c->layers[c->tree_head].tree].dev, thresh, c->hier_thresh, map200 ? c->d_map200 : nullptr,
+                                           a.rec, a.src, a.count, a.cap, c->stream));
+    }
     int n = 0;
     HIPCK(c, hipMemcpyAsync(&n, c->d_dn_count, 4, hipMemcpyDeviceToHost, c->stream)); HIPCK(c, hipStreamSynchronize(c->stream));
     *count = n;
@@ -169,7 +191,8 @@ int yolo_last_layer_output_batch(yolo_ctx *c, int n, float *out, size_t out_floa
     }
     const size_t cells = (size_t)L.H * L.W;
     for (int b = 0; b < n; ++b)
-        HIPCK(c, launch_head_darknet_layout((const float *)P.out.ptr + (size_t)b * cells * P.out.stride, P.out.stride, (int)cells, L.na, L.classes, L.type == L_REGION, c->d_dn_last + (size_t)b * per, c->stream));
+        if (L.tree >= 0) HIPCK(c, launch_head_darknet_layout_tree((const float *)P.out.ptr + (size_t)b * cells * P.out.stride, P.out.stride, (int)cells, L.na, L.classes, c->trees[L.tree].dev, c->d_dn_last + (size_t)b * per, c->stream));
+        else HIPCK(c, launch_head_darknet_layout((const float *)P.out.ptr + (size_t)b * cells * P.out.stride, P.out.stride, (int)cells, L.na, L.classes, L.type == L_REGION, c->d_dn_last + (size_t)b * per, c->stream));
     HIPCK(c, hipMemcpyAsync(out, c->d_dn_last, need * 4, hipMemcpyDeviceToHost, c->stream)); HIPCK(c, hipStreamSynchronize(c->stream));
     return YOLO_OK;
 }

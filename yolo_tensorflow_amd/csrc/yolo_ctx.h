@@ -68,9 +68,18 @@ struct Layer {
     // classifier tail: [softmax] keys; an [avgpool] whose fp32 input is pooled inside the launch of the [softmax] behind it (cls_ops.hip);
     // `cost`: a [cost] section (inference identity, never the network's output)
     int groups = 1; float temperature = 1.f; bool pool_fused = false; bool cost = false;
+    int tree = -1;                       // [region] / [softmax] with tree=: index into yolo_ctx::trees (hierarchical softmax), else -1
     // storage
     int storage = -1; int ch_off = 0;    // view = storage buffer + channel offset
     TView out;
+};
+
+// a softmax tree (DN/tree.c:83-139 read_tree): the file's text (kept for the export artifact), its arrays, and their device copy
+struct Tree {
+    std::string path, text;
+    int n = 0, groups = 0, levels = 0;
+    std::vector<int> parent, child, goff, gsize, leaf, order, lvl;      // order / lvl: see TreeDev (kernels.h)
+    int *d_all = nullptr; TreeDev dev{};
 };
 
 struct Storage { int def = 1 << 30, last = -1; size_t bytes = 0; int phys = -1; int stride = 0; int dt = DT_BF16; bool persistent = false; };
@@ -96,8 +105,9 @@ struct yolo_ctx {
     float in_mul = 1.f, in_add = 0.f;     // input normalisation after the /255: v * in_mul + in_add ([net] yolo_input_mul / yolo_input_add)
     float *d_det = nullptr; int rows = 0, attrs = 0;
     // classifier context: no detection head, the output layer (the last one that is not [cost]) is a [softmax].  cls_layer: that layer
-    // (-1: a detector); cls_topk: what the next forward's [softmax] launch selects (yolo_classify*), into d_cls_idx / d_cls_prob [max_batch][32]
-    int cls_layer = -1, cls_topk = 0; int *d_cls_idx = nullptr; float *d_cls_prob = nullptr;
+    // (-1: a detector); cls_topk: what the next forward's [softmax] launch selects (yolo_classify*), into d_cls_idx / d_cls_prob [max_batch][32];
+    // cls_mode: the form (TREE_*) a tree classifier's output layer writes during that forward
+    int cls_layer = -1, cls_topk = 0, cls_mode = 0; int *d_cls_idx = nullptr; float *d_cls_prob = nullptr;
     // lean detect path (yolo_detect*): the decode writes scores, labels and the four box numbers of every row, not the tensor
     bool lean_cnt_dirty = false;
     void *d_lean_list = nullptr; unsigned *d_lean_cnt = nullptr;      // lean decode: list of the boxes that pass the objectness pre-filter + its counter (one word)
@@ -119,6 +129,11 @@ struct yolo_ctx {
     int geom_fit = -1, geom_n = 0;
     struct GKeyImages { const void *pix; size_t bytes; int n, fit, units; float st, it; int mo, nm, sm; void *bo, *co; } gkey_img;
     hipGraphExec_t gexec_img = nullptr; int gstate_img = 0;
+    // hierarchical softmax ("Softmax trees"): the trees of the cfg's tree= keys; tree_head: the [region] layer that has one
+    // (-1: none); hier_thresh: yolo_set_hier_thresh; hierarchy_mode: yolo_set_hierarchy_mode; tree_full: YOLO_TREE_FULL forces the full
+    // decode in yolo_detect*; lean_hier: the hier_thresh the last descent-form decode labelled its rows with
+    std::vector<Tree> trees; int tree_head = -1; float hier_thresh = 0.5f, lean_hier = 0.f; int hierarchy_mode = 0; bool tree_full = false;
+    int *d_map200 = nullptr;
     bool weights_loaded = false;
     int scores_mode = -1;                 // what d_scores/d_labels hold: 0 max(obj*cls) from the decode, 1 objectness, -1 nothing
     size_t weights_count = 0;
@@ -166,6 +181,15 @@ float h2f(uint16_t h);
 void resolve_scales(yolo_ctx *c);
 void channel_scales(const yolo_ctx *c, int idx, std::vector<float> &out);
 int tail_fragments(yolo_ctx *c);
+// yolo_tree.cpp
+int parse_tree(const std::string &text, Tree &t, std::string &err);      // YOLO_OK or YOLO_ERR_INVALID with a message that names the line
+int load_tree(const std::string &path, Tree &t, std::string &err);        // ... from the artifact being read (g_tree_texts) or the file, as darknet opens it
+std::vector<int> pack_tree(const Tree &t, size_t at[7]);      // the seven arrays of TreeDev in one buffer; at[k]: where array k begins
+TreeDev tree_dev(const Tree &t, const int *base, const size_t at[7]);
+int upload_tree(yolo_ctx *c, Tree &t);
+void free_tree(Tree &t);
+int score_tree_rows(yolo_ctx *c, int n);      // full form: d_scores / d_labels of the n images' decoded rows at the context's hier_thresh
+extern thread_local const std::vector<std::pair<std::string, std::string>> *g_tree_texts;      // (path, text) of the trees an artifact embeds, while it is loaded
 // yolo_plan.cpp
 bool parse_cfg(const char *text, std::vector<Section> &out, std::string &err);
 int build_plan(yolo_ctx *c, const std::vector<Section> &secs);

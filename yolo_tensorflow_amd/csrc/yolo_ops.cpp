@@ -17,6 +17,19 @@ thread_local std::string g_op_err;
 
 TView make_view(void *p, int n, int h, int w, int c, int stride, int dt) { TView v; v.ptr = p; v.n = n; v.h = h; v.w = w; v.c = c; v.stride = stride; v.dt = dt; return v; }
 
+// a tree for the single operators: read, checked against the row length (len < 0: any), uploaded into the scope
+static int op_tree(OpScope &S, const char *what, const char *tree_path, int len, Tree &t)
+{
+    std::string err;
+    if (int r = load_tree(tree_path ? tree_path : "", t, err)) { g_op_err = std::string(what) + ": " + err; return r; }
+    if (len >= 0 && t.n != len) { g_op_err = std::string(what) + ": the tree has " + std::to_string(t.n) + " nodes, the rows " + std::to_string(len) + " values"; return YOLO_ERR_INVALID; }
+    size_t at[7];
+    const std::vector<int> all = pack_tree(t, at);
+    const int *d = (const int *)S.upload(all.data(), all.size() * 4);
+    if (S.rc) { g_op_err = std::string(what) + ": allocation failed"; return S.rc; }
+    t.dev = tree_dev(t, d, at);
+    return YOLO_OK;
+}
 
 }  // namespace yolo_impl
 
@@ -234,6 +247,30 @@ int yolo_op_softmax(const float *x, int n, int len, int groups, float temperatur
     if (!S.ok(launch_softmax_topk(a, S.s))) { g_op_err = "softmax: " + S.err; return S.rc; }
     if (top_k > 0) { S.download(classes_out, a.cls, (size_t)n * top_k * 4); S.download(topk_probs_out, a.topk_probs, (size_t)n * top_k * 4); }
     return S.download(probs_out, a.probs, (size_t)n * len * 4);
+}
+
+int yolo_op_tree_softmax(const float *x, int n, int len, const char *tree_path, float temperature, int mode, float *out, int device)
+{
+    if (!x || !out || n < 1 || len < 1 || !(temperature > 0.f) || mode < YOLO_HIER_CONDITIONAL || mode > YOLO_HIER_LEAVES) { g_op_err = "tree_softmax: bad arguments"; return YOLO_ERR_INVALID; }
+    OpScope S(device); if (S.rc) { g_op_err = "tree_softmax: no HIP device"; return S.rc; }
+    Tree t; if (int r = op_tree(S, "tree_softmax", tree_path, len, t)) return r;
+    TreeRows rows{(const float *)S.upload(x, (size_t)n * len * 4), (size_t)n, 1, len, 0, 0};
+    float *d_o = (float *)S.alloc((size_t)n * len * 4);
+    if (S.rc) { g_op_err = "tree_softmax: allocation failed"; return S.rc; }
+    if (!S.ok(launch_tree_softmax(t.dev, rows, temperature, mode, d_o, len, 0, nullptr, nullptr, S.s))) { g_op_err = "tree_softmax: " + S.err; return S.rc; }
+    return S.download(out, d_o, (size_t)n * len * 4);
+}
+
+int yolo_op_tree_top(const float *x_logits, int n, const char *tree_path, float hier_thresh, int32_t *labels_out, int device)
+{
+    if (!x_logits || !labels_out || n < 1) { g_op_err = "tree_top: bad arguments"; return YOLO_ERR_INVALID; }
+    OpScope S(device); if (S.rc) { g_op_err = "tree_top: no HIP device"; return S.rc; }
+    Tree t; if (int r = op_tree(S, "tree_top", tree_path, -1, t)) return r;
+    TreeRows rows{(const float *)S.upload(x_logits, (size_t)n * t.n * 4), (size_t)n, 1, t.n, 0, 0};
+    int *d_l = (int *)S.alloc((size_t)n * 4);
+    if (S.rc) { g_op_err = "tree_top: allocation failed"; return S.rc; }
+    if (!S.ok(launch_tree_top(t.dev, rows, hier_thresh, d_l, S.s))) { g_op_err = "tree_top: " + S.err; return S.rc; }
+    return S.download(labels_out, d_l, (size_t)n * 4);
 }
 
 int yolo_op_resize_u8(const uint8_t *img, int h, int w, int s, float post_scale, float *out, int device)

@@ -297,6 +297,7 @@ int yolo_load_darknet_weights(yolo_ctx *c, const char *path, int header_ints)
 namespace {
 struct ArtHeader { char magic[8]; uint32_t version, dtype, semantics, decode, n_layers, num_cfgs, cfg_len, reserved; };
 const char kArtMagic[8] = {'Y', 'O', 'L', 'O', 'H', 'I', 'P', '1'};
+const uint32_t kArtHasTrees = 1;         // ArtHeader::reserved, bit 0: the softmax trees of the cfg's tree= keys follow the tile plan (0: the layout every artifact had before)
 const uint32_t kArtVersion = 3;          // 3: split-fp16 filters packed for the interleaved pair layout (round 6); 2: filters packed chunk-major (conv_kchunk); 1: tap-major
 uint64_t fnv1a(uint64_t h, const void *p, size_t n) { const uint8_t *b = (const uint8_t *)p; for (size_t i = 0; i < n; ++i) { h ^= b[i]; h *= 1099511628211ull; } return h; }
 struct ArtWriter {
@@ -321,9 +322,12 @@ int yolo_export(yolo_ctx *c, const char *path)
     ArtHeader hd; memset(&hd, 0, sizeof hd); memcpy(hd.magic, kArtMagic, 8);
     hd.version = kArtVersion; hd.dtype = c->dtype; hd.semantics = c->semantics; hd.decode = c->decode; hd.n_layers = NL;
     hd.num_cfgs = (uint32_t)conv_num_cfgs(); hd.cfg_len = (uint32_t)c->cfg_text.size();
+    hd.reserved = c->trees.empty() ? 0 : kArtHasTrees;
     w.put(&hd, sizeof hd); w.put(c->cfg_text.data(), c->cfg_text.size());
     std::vector<float> sc(c->user_scale); sc.resize(NL, 1.f); w.put(sc.data(), NL * 4);
     std::vector<int32_t> plan(NL); yolo_get_tile_configs(c, plan.data()); w.put(plan.data(), NL * 4);
+    // softmax trees (only where the cfg has tree= keys: a network without one writes what it always wrote): path and text of each
+    for (auto &t : c->trees) { const uint32_t len[2] = {(uint32_t)t.path.size(), (uint32_t)t.text.size()}; w.put(len, sizeof len); w.put(t.path.data(), t.path.size()); w.put(t.text.data(), t.text.size()); }
     std::vector<uint8_t> buf;
     for (auto &L : c->layers) {
         if (L.type != L_CONV && L.type != L_LOCAL) continue;
@@ -355,11 +359,28 @@ yolo_ctx *yolo_create_from_file(const char *path, int max_batch, int device, voi
     std::string cfg_text(hd.cfg_len, '\0'); r.get(&cfg_text[0], hd.cfg_len);
     std::vector<float> sc(hd.n_layers); r.get(sc.data(), (size_t)hd.n_layers * 4);
     std::vector<int32_t> plan(hd.n_layers); r.get(plan.data(), (size_t)hd.n_layers * 4);
+    // the trees the cfg names, in section order: read here, handed to the planner in place of the files (load_tree)
+    std::vector<std::pair<std::string, std::string>> trees;
+    {
+        std::vector<Section> secs; std::string perr;
+        if (parse_cfg(cfg_text.c_str(), secs, perr))
+            for (size_t i = 1; i < secs.size() && r.ok; ++i) {
+                if ((secs[i].type != "region" && secs[i].type != "softmax") || !secs[i].kv.count("tree")) continue;
+                // written before trees were served (the [region] head ran as a flat softmax): no tree blobs to read, and not what this cfg means now
+                if (!(hd.reserved & kArtHasTrees)) { fclose(f); return bail(nullptr, "the artifact's cfg names a softmax tree but the artifact carries none (exported before trees were served): export it again"); }
+                uint32_t len[2] = {0, 0}; r.get(len, sizeof len);
+                if (!r.ok || len[0] > (1u << 16) || len[1] > (1u << 26)) { r.ok = false; break; }
+                std::string path(len[0], '\0'), text(len[1], '\0'); r.get(&path[0], len[0]); r.get(&text[0], len[1]);
+                trees.emplace_back(path, text);
+            }
+    }
     if (!r.ok) { fclose(f); return bail(nullptr, "truncated artifact"); }
     yolo_config cfg; memset(&cfg, 0, sizeof cfg);
     cfg.struct_size = sizeof cfg; cfg.cfg_text = cfg_text.c_str(); cfg.max_batch = max_batch; cfg.dtype = (int)hd.dtype; cfg.semantics = (int)hd.semantics;
     cfg.decode = (int)hd.decode; cfg.device = device; cfg.keep_layers = keep_layers; cfg.stream = stream;
+    g_tree_texts = &trees;
     yolo_ctx *c = yolo_create(&cfg, err, err_len);
+    g_tree_texts = nullptr;
     if (!c) { fclose(f); return nullptr; }
     if (c->layers.size() != hd.n_layers) { fclose(f); return bail(c, "artifact layer count does not match its own cfg"); }
     if (c->dtype == YOLO_FP8 && yolo_set_act_scales(c, sc.data(), (int)hd.n_layers) != YOLO_OK) { fclose(f); return bail(c, c->err); }

@@ -47,6 +47,20 @@ std::vector<float> opt_list(const Section &s, const char *k)
     return v;
 }
 
+// The descent form of a tree head is the default of yolo_detect* only once it is measured as not slower than the full form on the
+// YOLO9000 shape (tools/tree_decode_rate.py); until then the full form is
+#define TREE_DESCENT_DEFAULT 0
+
+// tree= of layer i: read and checked (yolo_tree.cpp), its size against the `want` values the layer has
+static int plan_tree(yolo_ctx *c, int i, const char *section, const std::string &path, int want, const char *of)
+{
+    Tree t; std::string err;
+    if (int r = load_tree(path, t, err)) return fail(c, r, "layer %d: [%s] %s", i, section, err.c_str());
+    if (t.n != want) return fail(c, YOLO_ERR_INVALID, "layer %d: [%s] tree '%s' has %d nodes but the layer has %d %s", i, section, path.c_str(), t.n, want, of);
+    c->trees.push_back(std::move(t)); c->layers[i].tree = (int)c->trees.size() - 1;
+    return YOLO_OK;
+}
+
 TView view_of(const yolo_ctx *c, int idx) { return idx < 0 ? c->input : c->layers[idx].out; }
 
 int build_plan(yolo_ctx *c, const std::vector<Section> &secs)
@@ -187,6 +201,15 @@ int build_plan(yolo_ctx *c, const std::vector<Section> &secs)
             if (C != L.na * (5 + L.classes)) return fail(c, YOLO_ERR_INVALID, "layer %d: head expects %d channels, conv gives %d", i, L.na * (5 + L.classes), C);
             if (H != W) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: non-square grid", i);
             if (c->attrs && c->attrs != 5 + L.classes) return fail(c, YOLO_ERR_UNSUPPORTED, "heads with different class counts");
+            if (L.type == L_REGION && s.kv.count("tree")) {
+                // [region] with a softmax tree (YOLO9000, DN/region_layer.c:171-181): the tree takes precedence over softmax=1
+                if (opt_i(s, "background", 0)) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [region] tree= with background=1 is not served", i);
+                if (opt_i(s, "coords", 4) != 4) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [region] tree= with coords != 4 is not served", i);
+                if (s.kv.count("map")) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [region] tree= with map= in the cfg is not served (pass the map to yolo_darknet_boxes_map)", i);
+                if (c->rows) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: a [region] head with a tree must be the network's only head", i);
+                if (int r = plan_tree(c, i, "region", opt_s(s, "tree", ""), L.classes, "classes")) return r;
+                c->tree_head = i;
+            } else if (c->tree_head >= 0) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: a [region] head with a tree must be the network's only head", i);
             c->attrs = 5 + L.classes; L.row_off = c->rows; c->rows += H * W * L.na;
             c->layers[i - 1].head = true;
         } else if (s.type == "avgpool") {
@@ -196,13 +219,18 @@ int build_plan(yolo_ctx *c, const std::vector<Section> &secs)
         } else if (s.type == "softmax") {
             // DN/parser.c:268-280: groups, temperature; per image and group e = exp(x / temp - max / temp), p = e / sum (DN/blas.c:305-321)
             if (c->dtype == YOLO_FP8) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [softmax] is not served in the fp8 configuration", i);
-            if (s.kv.count("tree")) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [softmax] with tree= (hierarchical softmax) is not served", i);
             if (opt_i(s, "spatial", 0)) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [softmax] with spatial=1 is not served", i);
             L.type = L_SOFTMAX; L.groups = opt_i(s, "groups", 1); L.temperature = (float)atof(opt_s(s, "temperature", "1").c_str());
             if (H != 1 || W != 1) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [softmax] over a %d x %d map (it must follow an [avgpool] or a [connected] layer)", i, H, W);
-            if (L.groups < 1 || C % L.groups) return fail(c, YOLO_ERR_INVALID, "layer %d: [softmax] groups=%d does not divide its %d inputs", i, L.groups, C);
             if (!(L.temperature > 0.f)) return fail(c, YOLO_ERR_INVALID, "layer %d: [softmax] temperature must be > 0", i);
+            if (s.kv.count("tree")) {
+                // hierarchical softmax (DN/softmax_layer.c:41-48): one softmax per group of the tree, whatever `groups` says
+                if (int r = plan_tree(c, i, "softmax", opt_s(s, "tree", ""), C, "inputs")) return r;
+                L.groups = 1;
+            } else {
+            if (L.groups < 1 || C % L.groups) return fail(c, YOLO_ERR_INVALID, "layer %d: [softmax] groups=%d does not divide its %d inputs", i, L.groups, C);
             if (C / L.groups > CLS_SOFTMAX_MAX) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [softmax] group of %d logits (at most %d)", i, C / L.groups, CLS_SOFTMAX_MAX);
+            }
             // the logits are never rounded to 16 bits: the conv that reaches this layer directly, or through one [avgpool], writes fp32
             int p = i - 1;
             if (p >= 0 && c->layers[p].type == L_AVGPOOL) p = c->layers[p].in[0];
@@ -231,7 +259,7 @@ int build_plan(yolo_ctx *c, const std::vector<Section> &secs)
         const int j = L.in.empty() ? -1 : L.in[0];
         if (L.type == L_AVGPOOL && (c->dtype == YOLO_FP32 || (j >= 0 && c->layers[j].head))) {
             L.pair = false; L.store_dt = DT_F32;
-            L.pool_fused = i + 1 < NL && c->layers[i + 1].type == L_SOFTMAX && L.C <= CLS_SOFTMAX_MAX && !getenv("YOLO_NO_POOL_FUSE");
+            L.pool_fused = i + 1 < NL && c->layers[i + 1].type == L_SOFTMAX && c->layers[i + 1].tree < 0 && L.C <= CLS_SOFTMAX_MAX && !getenv("YOLO_NO_POOL_FUSE");
         }
         if (L.type == L_SOFTMAX) {
             L.pair = false; L.store_dt = DT_F32;
@@ -484,11 +512,16 @@ int allocate(yolo_ctx *c)
     HIPCK(c, hipMalloc((void **)&c->d_det, nr * (c->attrs ? c->attrs : 1) * 4));
     HIPCK(c, hipMalloc((void **)&c->d_box4, nr * 16));
     HIPCK(c, hipMalloc(&c->d_lean_list, nr * 16)); HIPCK(c, hipMalloc((void **)&c->d_lean_cnt, 4)); HIPCK(c, hipMemsetAsync(c->d_lean_cnt, 0, 4, c->stream));
+    for (auto &t : c->trees) if (int r = upload_tree(c, t)) return r;
     c->lean_ok = true;                  // every head a [yolo] head the cell-per-wave decode serves
     for (auto &L : c->layers) {
         if (L.type == L_REGION || L.type == L_DETECT) c->lean_ok = false;
         if (L.type == L_YOLO && L.na * (5 + L.classes) > 256) c->lean_ok = false;
     }
+    // ... or the one [region] head with a tree: its descent form writes scores, labels and box4.  Which form yolo_detect* takes:
+    // YOLO_TREE_FULL forces the full decode, YOLO_TREE_DESCENT the descent; otherwise TREE_DESCENT_DEFAULT (NOTEBOOK, "Softmax trees")
+    c->tree_full = getenv("YOLO_TREE_FULL") ? true : getenv("YOLO_TREE_DESCENT") ? false : !TREE_DESCENT_DEFAULT;
+    if (c->tree_head >= 0) c->lean_ok = !c->tree_full;
     c->lean_heads = 0;
     if (c->lean_ok) {
         int classes = -1; bool same = true;

@@ -195,6 +195,16 @@ int run_layer(yolo_ctx *c, int i, int n)
         a.n = n; a.groups = L.groups; a.len = L.C / L.groups; a.temperature = L.temperature; a.probs = (float *)L.out.ptr; a.p_stride = L.out.stride;
         a.top_k = i == c->cls_layer ? c->cls_topk : 0; a.cls = c->d_cls_idx; a.topk_probs = c->d_cls_prob;      // (yolo_classify*: the output layer also selects)
         const Layer &P = c->layers[L.in[0]];
+        if (L.tree >= 0) {
+            // hierarchical softmax: conditional probabilities are the layer's output (what network_predict returns); the output layer of
+            // a classify call writes the form yolo_set_hierarchy_mode selected and takes its top-k from it
+            const TView in = view_of(c, L.in[0]);
+            if (in.dt != DT_F32) return fail(c, YOLO_ERR_STATE, "layer %d: [softmax] input is not fp32", i);
+            const TreeRows rows{(const float *)in.ptr, (size_t)n, 1, in.stride, 0, 0};
+            HIPCK(c, launch_tree_softmax(c->trees[L.tree].dev, rows, L.temperature, i == c->cls_layer ? c->cls_mode : TREE_CONDITIONAL, a.probs, a.p_stride,
+                                         a.top_k, a.cls, a.topk_probs, s));
+            break;
+        }
         if (P.type == L_AVGPOOL && P.pool_fused) {
             const TView in = nview(view_of(c, P.in[0]));
             if (!avgpool_softmax_ok(in, a)) return fail(c, YOLO_ERR_STATE, "layer %d: the fused [avgpool] + [softmax] launch does not apply to this plan", i);
@@ -212,6 +222,20 @@ int run_layer(yolo_ctx *c, int i, int n)
                                   c->d_scores, c->d_labels, s));
         break; }
     case L_YOLO: case L_REGION: {
+        if (L.tree >= 0) {
+            // [region] with a softmax tree.  Full form: the decoded tensor with absolute class probabilities (scored at postprocess time,
+            // with the hier_thresh of that moment); descent form (yolo_detect*): box4, scores, labels straight from the raw tensor
+            DecodeArgs d; memset(&d, 0, sizeof d);
+            const Layer &P = c->layers[i - 1];
+            d.raw = (const float *)P.out.ptr; d.raw_stride = P.out.stride; d.n = n; d.g = L.H; d.na = L.na; d.classes = L.classes;
+            d.img_size = c->in_h; d.mode = c->decode; d.region = 1;
+            for (int k = 0; k < 2 * L.na; ++k) d.anchors[k] = L.anchors[k];
+            d.det = c->lean ? nullptr : c->d_det; d.box4 = c->lean ? c->d_box4 : nullptr; d.rows_total = c->rows; d.row_off = L.row_off;
+            d.reject_below = c->lean ? c->lean_thr : -INFINITY;
+            if (c->lean) { HIPCK(c, launch_decode_region_tree_lean(d, c->trees[L.tree].dev, c->hier_thresh, c->d_scores, c->d_labels, s)); c->lean_hier = c->hier_thresh; }
+            else HIPCK(c, launch_decode_region_tree(d, c->trees[L.tree].dev, s));
+            break;
+        }
         if (c->lean && c->lean_thr > 0.f && c->lean_heads >= 1 && c->lean_heads <= 4) {
             // lean detect path: every [yolo] head is decoded by ONE launch, issued at the last head (the head tensors keep their own buffers)
             bool later_head = false;
@@ -440,6 +464,17 @@ static int postprocess_impl(yolo_ctx *c, int n, float score_thr, float iou_thr, 
     if (int r = need_detector(c, "yolo_postprocess")) return r;
     if (n < 1 || n > c->last_n) return fail(c, YOLO_ERR_STATE, "postprocess of %d images but the last forward ran %d", n, c->last_n);
     HIPCK(c, hipSetDevice(c->device));
+    if (c->tree_head >= 0) {
+        // a softmax-tree head: score = objectness, label = hierarchy_top_prediction at the context's hier_thresh.  After a full decode
+        // the rows are scored here; after the descent form they already are
+        if (nms_mode == YOLO_NMS_NUMPY_V3) return fail(c, YOLO_ERR_UNSUPPORTED, "YOLO_NMS_NUMPY_V3 over a softmax-tree head");
+        if (!c->det_valid && (score_thr < c->lean_thr || c->hier_thresh != c->lean_hier))
+            return fail(c, YOLO_ERR_STATE, "the last forward ran through yolo_detect* with score threshold %g and hier_thresh %g; other values need yolo_forward", c->lean_thr, c->lean_hier);
+        if (c->det_valid) if (int r = score_tree_rows(c, n)) return r;
+        c->scores_mode = 2;
+        return post(c, c->d_det, n, c->rows, c->attrs, score_thr, iou_thr, max_out, nms_mode, select_mode,
+                    nms_mode == YOLO_NMS_PER_CLASS ? c->in_h : 0, nms_mode == YOLO_NMS_PER_CLASS ? c->in_w : 0, 1, boxes_out, counts_out, out_loc, rows_out, geom);
+    }
     const int want = nms_mode == YOLO_NMS_NUMPY_V3 ? 1 : 0;
     if (!c->det_valid && score_thr < c->lean_thr)
         return fail(c, YOLO_ERR_STATE, "the last forward ran through yolo_detect* with score threshold %g and pruned the scores below it; a lower threshold needs yolo_forward", c->lean_thr);
@@ -667,9 +702,9 @@ int yolo_classify(yolo_ctx *c, const void *images, int n, int fmt, int loc, floa
 {
     if (!c) return YOLO_ERR_INVALID;
     if (int r = classify_check(c, top_k, classes_out, probs_out)) return r;
-    c->cls_topk = top_k;
+    c->cls_topk = top_k; c->cls_mode = c->hierarchy_mode;
     const int r = forward_impl(c, images, n, fmt, loc, scale, nullptr, YOLO_DEVICE, false);
-    c->cls_topk = 0;
+    c->cls_topk = 0; c->cls_mode = 0;
     if (r) return r;
     return classify_out(c, n, top_k, classes_out, probs_out, out_loc);
 }
@@ -679,9 +714,9 @@ int yolo_classify_images_u8(yolo_ctx *c, const uint8_t *pixels, size_t bytes, co
 {
     if (!c) return YOLO_ERR_INVALID;
     if (int r = classify_check(c, top_k, classes_out, probs_out)) return r;
-    c->cls_topk = top_k;
+    c->cls_topk = top_k; c->cls_mode = c->hierarchy_mode;
     const int r = forward_images_impl(c, pixels, bytes, descs, n, fit, loc, nullptr, YOLO_DEVICE, false, 0.f);
-    c->cls_topk = 0;
+    c->cls_topk = 0; c->cls_mode = 0;
     if (r) return r;
     return classify_out(c, n, top_k, classes_out, probs_out, out_loc);
 }

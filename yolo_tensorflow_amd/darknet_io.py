@@ -144,6 +144,57 @@ def parse_cfg(text):
     return secs
 
 
+def read_tree(path):
+    """darknet's softmax-tree file (DN/tree.c:83-139 read_tree), the twin of the library's reader (csrc/yolo_tree.cpp): one
+    `name parent` line per node; a group is a maximal run of consecutive lines with the same parent, child[parent] the index of that
+    run, leaf[i] true when nobody names i as parent.  `path` is opened as darknet opens it, relative to the working directory.
+    -> dict(n, groups, names, parent, child, group, group_offset, group_size, leaf) with int32 arrays.  ValueError, naming the line,
+    for what the library refuses too: a parent that is not below its own index, children that are not one contiguous run, a first
+    parent other than -1."""
+    import numpy as np
+    try:
+        with open(path, "r") as fh:
+            lines = fh.read().split("\n")
+    except OSError:
+        raise ValueError("tree file '%s' cannot be opened" % path)
+    if lines and lines[-1] == "":
+        lines.pop()
+    names, parent, child, group, goff, gsize = [], [], [], [], [], []
+    last = -1
+    for no, line in enumerate(lines, 1):
+        tok = line.split()
+        if not tok:
+            raise ValueError("tree file '%s': tree line %d: no node name" % (path, no))
+        try:
+            par = int(tok[1]) if len(tok) > 1 else -1
+        except ValueError:
+            par = -1
+        i = len(parent)
+        if i == 0 and par != -1:
+            raise ValueError("tree file '%s': tree line %d: the first node must be a root (parent -1), it names parent %d" % (path, no, par))
+        if par < -1 or par >= i:
+            raise ValueError("tree file '%s': tree line %d: parent %d is not below the node's own index %d" % (path, no, par, i))
+        if i == 0 or par != last:
+            if i > 0 and (par < 0 or child[par] >= 0):
+                raise ValueError("tree file '%s': tree line %d: the children of %s are not one contiguous run"
+                                 % (path, no, "the root" if par < 0 else "node %d" % par))
+            goff.append(i); gsize.append(0)
+            if par >= 0:
+                child[par] = len(goff) - 1
+            last = par
+        names.append(tok[0]); parent.append(par); child.append(-1); group.append(len(goff) - 1)
+        gsize[-1] += 1
+    if not parent:
+        raise ValueError("tree file '%s': tree line 1: the file has no nodes" % path)
+    leaf = [1] * len(parent)
+    for q in parent:
+        if q >= 0:
+            leaf[q] = 0
+    a = lambda v: np.asarray(v, dtype=np.int32)
+    return dict(n=len(parent), groups=len(goff), names=names, parent=a(parent), child=a(child), group=a(group),
+                group_offset=a(goff), group_size=a(gsize), leaf=a(leaf))
+
+
 def layer_shapes(secs):
     """[(type, H, W, C_out, C_in)] per layer, darknet shape rules (DN/parser.c:730-875)."""
     net = secs[0]

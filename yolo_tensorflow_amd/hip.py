@@ -44,7 +44,11 @@ EXPORTS = [
     "yolo_postprocess_rows", "yolo_op_postprocess_rows", "yolo_last_layer_output_batch", "yolo_head_raw", "yolo_calibrate", "yolo_calibrate_copy", "yolo_op_resize_cv2",
     "yolo_forward_images_u8", "yolo_detect_images_u8", "yolo_detect_images_graph", "yolo_fit_unit_value", "yolo_darknet_boxes_at",
     "yolo_num_classes", "yolo_classify", "yolo_classify_images_u8", "yolo_op_avgpool", "yolo_op_softmax",
+    "yolo_set_hier_thresh", "yolo_set_hierarchy_mode", "yolo_darknet_boxes_map", "yolo_tree_geometry", "yolo_tree_read", "yolo_plan_check",
+    "yolo_op_tree_softmax", "yolo_op_tree_top",
 ]
+HIER_CONDITIONAL, HIER_ABSOLUTE, HIER_LEAVES = 0, 1, 2
+_HIER_MODES = {None: HIER_CONDITIONAL, "conditional": HIER_CONDITIONAL, "absolute": HIER_ABSOLUTE, "leaves": HIER_LEAVES}
 # include/yolo_dist.h: the image-sharded detect step
 DIST_EXPORTS = ["yolo_shard_bounds", "yolo_dist_flat_words", "yolo_dist_split_records", "yolo_dist_unique_id", "yolo_dist_create",
                 "yolo_dist_detect", "yolo_dist_detect_async", "yolo_dist_destroy"]
@@ -132,6 +136,14 @@ def load_library():
     l.yolo_classify_images_u8.argtypes = [P, P, SZ, P, I, I, I, I, P, P, I]
     l.yolo_op_avgpool.argtypes = [P, I, I, I, I, I, P, I]
     l.yolo_op_softmax.argtypes = [P, I, I, I, F, I, P, P, P, I]
+    l.yolo_set_hier_thresh.argtypes = [P, F]
+    l.yolo_set_hierarchy_mode.argtypes = [P, I]
+    l.yolo_darknet_boxes_map.argtypes = [P, I, I, I, F, I, P, P, I, P]
+    l.yolo_tree_geometry.argtypes = [P, P, P, P, P, P, P, P]
+    l.yolo_tree_read.argtypes = [C.c_char_p, P, P, P, P, P, P, P, C.c_char_p, SZ]
+    l.yolo_plan_check.argtypes = [C.c_char_p, I, C.c_char_p, SZ]
+    l.yolo_op_tree_softmax.argtypes = [P, I, I, C.c_char_p, F, I, P, I]
+    l.yolo_op_tree_top.argtypes = [P, I, C.c_char_p, F, P, I]
     l.yolo_shard_bounds.argtypes = [I, I, I, C.POINTER(I), C.POINTER(I)]
     l.yolo_dist_flat_words.argtypes = [I, I]; l.yolo_dist_flat_words.restype = C.c_size_t
     l.yolo_dist_split_records.argtypes = [P, I, I, I, P, P]
@@ -385,13 +397,55 @@ class Engine:
         self._check(self.lib.yolo_last_layer_output_batch(self.ctx, n, out.ctypes.data, out.size), "yolo_last_layer_output_batch")
         return out
 
-    def detect(self, images, scale=1.0 / 255.0, **kw):
+    # ---- softmax trees (a [region] or [softmax] section with tree=) ----
+    def set_hier_thresh(self, hier_thresh):
+        """hier_thresh of postprocess / detect* / darknet_boxes on a network with a tree head (yolo_set_hier_thresh; default 0.5)."""
+        self._check(self.lib.yolo_set_hier_thresh(self.ctx, float(hier_thresh)), "yolo_set_hier_thresh")
+
+    def set_hierarchy_mode(self, mode):
+        """What classify* returns for a tree classifier: None / "conditional", "absolute" or "leaves" (yolo_set_hierarchy_mode)."""
+        self._check(self.lib.yolo_set_hierarchy_mode(self.ctx, _HIER_MODES[mode] if mode in _HIER_MODES else int(mode)), "yolo_set_hierarchy_mode")
+
+    def tree_geometry(self):
+        """The network's softmax tree -> dict(n, groups, parent, child, group_offset, group_size, leaf), or None without one."""
+        n, g = C.c_int32(0), C.c_int32(0)
+        self._check(self.lib.yolo_tree_geometry(self.ctx, C.byref(n), C.byref(g), None, None, None, None, None), "yolo_tree_geometry")
+        if n.value == 0:
+            return None
+        a = {k: np.zeros(n.value if k in ("parent", "child", "leaf") else g.value, dtype=np.int32) for k in ("parent", "child", "group_offset", "group_size", "leaf")}
+        self._check(self.lib.yolo_tree_geometry(self.ctx, None, None, a["parent"].ctypes.data, a["child"].ctypes.data, a["group_offset"].ctypes.data,
+                                                a["group_size"].ctypes.data, a["leaf"].ctypes.data), "yolo_tree_geometry")
+        a.update(n=n.value, groups=g.value)
+        return a
+
+    def detect(self, images, scale=1.0 / 255.0, hier_thresh=None, **kw):
+        """forward, then postprocess(**kw).  hier_thresh (networks with a tree head): None leaves the context's value alone."""
+        if hier_thresh is not None:
+            self.set_hier_thresh(hier_thresh)
         self.forward(images, scale=scale, want_detections=False)
         return self.postprocess(int(images.shape[0]), **kw)
 
+    def detect_fused(self, images, scale=1.0 / 255.0, hier_thresh=None, **kw):
+        """yolo_detect: forward + threshold + NMS as one call that never materialises the decoded tensor (the lean decode of [yolo]
+        heads, the descent form of a tree head); records to the host.  Keywords as for postprocess."""
+        if hier_thresh is not None:
+            self.set_hier_thresh(hier_thresh)
+        p, loc = _ptr(images)
+        self._last_image = images if loc == DEVICE else None
+        self._order_after_producer(images)
+        n = int(images.shape[0])
+        fmt = IMG_U8 if str(images.dtype).endswith("uint8") else IMG_F32
+        a = dict(score_thr=0.5, iou_thr=0.5, max_out=20, nms_mode=NMS_TF, select_mode=SELECT_GT); a.update(kw)
+        boxes = np.zeros((n, a["max_out"]), dtype=BOX_DTYPE); counts = np.zeros(n, dtype=np.int32)
+        self._check(self.lib.yolo_detect(self.ctx, p, n, fmt, loc, scale, a["score_thr"], a["iou_thr"], a["max_out"], a["nms_mode"], a["select_mode"],
+                                         boxes.ctypes.data, counts.ctypes.data, HOST), "yolo_detect")
+        return [boxes[i, :counts[i]].copy() for i in range(n)]
+
     def detect_graph(self, images, boxes_out, counts_out, scale=1.0 / 255.0, score_thr=0.5, iou_thr=0.5, max_out=20,
-                     nms_mode=NMS_TF, select_mode=SELECT_GT):
+                     nms_mode=NMS_TF, select_mode=SELECT_GT, hier_thresh=None):
         """Device-resident detect replayed from a HIP graph (images / boxes_out / counts_out: device tensors)."""
+        if hier_thresh is not None:
+            self.set_hier_thresh(hier_thresh)
         p, loc = _ptr(images); bp, bl = _ptr(boxes_out); cp, cl = _ptr(counts_out)
         if loc != DEVICE or bl != DEVICE or cl != DEVICE:
             raise YoloError("detect_graph needs device-resident buffers")
@@ -424,8 +478,10 @@ class Engine:
         return det
 
     def detect_images(self, images, fit=FIT_STRETCH, units=UNITS_NETWORK, score_thr=0.5, iou_thr=0.5, max_out=20, nms_mode=NMS_TF,
-                      select_mode=SELECT_GT):
+                      select_mode=SELECT_GT, hier_thresh=None):
         """forward_images + threshold + NMS with each image's own geometry (yolo_detect_images_u8) -> list of BOX_DTYPE arrays."""
+        if hier_thresh is not None:
+            self.set_hier_thresh(hier_thresh)
         buf, descs, p, loc, nbytes = self._packed(images)
         n = len(descs)
         self._order_after_producer(buf)
@@ -436,10 +492,12 @@ class Engine:
         return [boxes[i, :counts[i]].copy() for i in range(n)]
 
     def detect_images_graph(self, pixels_dev, descs, boxes_out, counts_out, fit=FIT_STRETCH, units=UNITS_NETWORK, score_thr=0.5,
-                            iou_thr=0.5, max_out=20, nms_mode=NMS_TF, select_mode=SELECT_GT, nbytes=None):
+                            iou_thr=0.5, max_out=20, nms_mode=NMS_TF, select_mode=SELECT_GT, nbytes=None, hier_thresh=None):
         """yolo_detect_images_graph: pixels_dev a device uint8 tensor holding the packed images, descs (host) where each one lies this
         call; boxes_out / counts_out device tensors.  One captured graph serves every call with the same buffers and modes, whatever
         the image sizes."""
+        if hier_thresh is not None:
+            self.set_hier_thresh(hier_thresh)
         p, loc = _ptr(pixels_dev); bp, bl = _ptr(boxes_out); cp, cl = _ptr(counts_out)
         if loc != DEVICE or bl != DEVICE or cl != DEVICE:
             raise YoloError("detect_images_graph needs device-resident buffers")
@@ -486,14 +544,21 @@ class Engine:
                                                      cls.ctypes.data if top_k else None, probs.ctypes.data, HOST), "yolo_classify_images_u8")
         return (cls, probs) if top_k else probs
 
-    def darknet_boxes(self, image, w, h, thresh=0.5, relative=1, cap=None):
+    def darknet_boxes(self, image, w, h, thresh=0.5, relative=1, cap=None, hier_thresh=None, map200=None):
         """darknet's get_network_boxes over image `image` of the last forward (yolo_darknet_boxes_at) -> records [count, 5 + classes]
-        (x, y, w, h, objectness, prob[classes]), un-letterboxed for a w x h source image."""
+        (x, y, w, h, objectness, prob[classes]), un-letterboxed for a w x h source image.  A tree head: hier_thresh (None: the
+        context's), map200 the 200 class indices of the `map` form (yolo_darknet_boxes_map)."""
+        if hier_thresh is not None:
+            self.set_hier_thresh(hier_thresh)
+        m = None if map200 is None else np.ascontiguousarray(map200, dtype=np.int32)
+        if m is not None and m.size != 200:
+            raise YoloError("map200 needs exactly 200 entries")
+        mp = None if m is None else m.ctypes.data
         cnt = C.c_int(0)
-        self._check(self.lib.yolo_darknet_boxes_at(self.ctx, image, w, h, thresh, relative, None, 0, C.byref(cnt)), "yolo_darknet_boxes_at")
+        self._check(self.lib.yolo_darknet_boxes_map(self.ctx, image, w, h, thresh, relative, mp, None, 0, C.byref(cnt)), "yolo_darknet_boxes_at")
         cap = cnt.value if cap is None else cap
         rec = np.zeros((max(cap, 1), self.attrs), dtype=np.float32)
-        self._check(self.lib.yolo_darknet_boxes_at(self.ctx, image, w, h, thresh, relative, rec.ctypes.data, cap, C.byref(cnt)),
+        self._check(self.lib.yolo_darknet_boxes_map(self.ctx, image, w, h, thresh, relative, mp, rec.ctypes.data, cap, C.byref(cnt)),
                     "yolo_darknet_boxes_at")
         return rec[:min(cnt.value, cap)]
 
@@ -618,6 +683,43 @@ def op_softmax(x, groups=1, temperature=1.0, top_k=0, device=0):
     _op_check(load_library().yolo_op_softmax(x.ctypes.data, n, ln, groups, float(temperature), top_k, probs.ctypes.data,
                                              cls.ctypes.data if top_k else None, tkp.ctypes.data if top_k else None, device), "yolo_op_softmax")
     return (probs, cls, tkp) if top_k else probs
+
+
+def tree_read(path):
+    """The library's reader of a darknet tree file (yolo_tree_read; no device needed) -> dict(n, groups, parent, child, group_offset,
+    group_size, leaf); YoloError with the library's message for a file it refuses."""
+    lib = load_library()
+    n, g = C.c_int32(0), C.c_int32(0)
+    err = C.create_string_buffer(512)
+    rc = lib.yolo_tree_read(os.fsencode(path), C.byref(n), C.byref(g), None, None, None, None, None, err, 512)
+    if rc != 0:
+        raise YoloError("yolo_tree_read failed (%d): %s" % (rc, err.value.decode()))
+    a = {k: np.zeros(n.value if k in ("parent", "child", "leaf") else g.value, dtype=np.int32) for k in ("parent", "child", "group_offset", "group_size", "leaf")}
+    lib.yolo_tree_read(os.fsencode(path), None, None, a["parent"].ctypes.data, a["child"].ctypes.data, a["group_offset"].ctypes.data,
+                       a["group_size"].ctypes.data, a["leaf"].ctypes.data, err, 512)
+    a.update(n=n.value, groups=g.value)
+    return a
+
+
+def plan_check(cfg_text, dtype=BF16):
+    """Parse and plan a cfg without a device (yolo_plan_check) -> (status, message); status 0: it plans."""
+    err = C.create_string_buffer(1024)
+    rc = load_library().yolo_plan_check(cfg_text.encode(), dtype, err, 1024)
+    return rc, err.value.decode()
+
+
+def op_tree_softmax(x, tree_path, temperature=1.0, mode=HIER_CONDITIONAL, device=0):
+    """x [n, len] logits -> [n, len]: one softmax per group of the tree (mode 0), the absolute probabilities (1), leaves only (2)."""
+    x = _f32(x); out = np.empty_like(x)
+    _op_check(load_library().yolo_op_tree_softmax(x.ctypes.data, x.shape[0], x.shape[1], os.fsencode(tree_path), temperature, mode, out.ctypes.data, device), "yolo_op_tree_softmax")
+    return out
+
+
+def op_tree_top(x, tree_path, hier_thresh=0.5, device=0):
+    """x [n, nodes] raw logits -> int32 [n]: hierarchy_top_prediction of every row, walked from the root (the descent kernel)."""
+    x = _f32(x); out = np.empty(x.shape[0], dtype=np.int32)
+    _op_check(load_library().yolo_op_tree_top(x.ctypes.data, x.shape[0], os.fsencode(tree_path), hier_thresh, out.ctypes.data, device), "yolo_op_tree_top")
+    return out
 
 
 def op_resize_u8(img, size, post_scale=1.0, device=0):
