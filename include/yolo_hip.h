@@ -390,6 +390,12 @@ int yolo_tree_read(const char *path, int32_t *nodes, int32_t *groups, int32_t *p
  * keep_layers, batch 1): the planner's status and message, or YOLO_OK.  What only a device can tell (memory, the per-context
  * batch limit) is not checked. */
 int yolo_plan_check(const char *cfg_text, int dtype, char *err, size_t err_len);
+/* The plan itself, as text, for `max_batch` and `keep_layers` (the other defaults as above): one line per layer --
+ *   <index> <section> kernel=<tiled|halo|s2|-> fused=<none|stem|pair-stem|resblock|c3s2> launcher=<layer that issues the fused launch, -1>
+ *   residual_from=<folded shortcut source, -2> tail_layer=<1x1 conv that can ride in this conv's epilogue, -1> storage=<index, -1>
+ *   phys=<pooled buffer> def=<first writer> last=<last reader>
+ * -- then `buffers <count> bytes <total>`.  YOLO_ERR_INVALID with the size needed when `out` is too small. */
+int yolo_plan_table(const char *cfg_text, int dtype, int max_batch, int keep_layers, char *out, size_t out_len, char *err, size_t err_len);
 /* single operators: x [n][len] fp32 logits, one softmax per group of the tree at tree_path, `mode` a yolo_hierarchy_mode -> out [n][len];
  * hierarchy_top_prediction of n rows of raw logits (temperature 1) walking down from the root -> labels_out [n] */
 int yolo_op_tree_softmax(const float *x, int n, int len, const char *tree_path, float temperature, int mode, float *out, int device);

@@ -75,11 +75,11 @@ double yolo_conv_bytes(const yolo_ctx *c, int n)
 {
     if (!c) return 0;
     double b = 0;
-    for (auto &L : c->layers) if (L.type == L_CONV) {
-        TView in = view_of(c, L.in[0]);
-        const double ie = (double)dt_size(L.in_dt), oe = (double)dt_size(L.out.dt);
-        if (!L.stem && !L.stem_tail && !L.blk && !L.c3s2) b += (double)n * in.h * in.w * L.cin * ie;         // the fused stem / residual block / conv3 + stride-2 launch keep these inputs in LDS
-        if (!L.stem_skip && !L.blk_skip && !L.pstem_skip && !L.c3s2_skip) b += (double)n * L.H * L.W * L.filters * oe;
+    for (int i = 0; i < (int)c->layers.size(); ++i) if (c->layers[i].type == L_CONV) {
+        const Layer &L = c->layers[i];
+        const TView in = view_of(c, L.in[0]); const double ie = (double)dt_size(L.in_dt), oe = (double)dt_size(L.out.dt);
+        if (!input_never_loaded(L, i)) b += (double)n * in.h * in.w * L.cin * ie;         // the fused stem / residual block / conv3 + stride-2 launch keep these inputs in LDS
+        if (!never_stored(L, i)) b += (double)n * L.H * L.W * L.filters * oe;
         b += (double)L.filters * L.cin * L.size * L.size * ie;
     }
     return b;
@@ -233,7 +233,7 @@ int yolo_layer_output(yolo_ctx *c, int index, int n, float *out, size_t out_floa
     if (!c->keep_layers) {
         // the production plan pools its buffers and keeps fused-away tensors in LDS: only a conv that launches, writes its own tensor and
         // whose buffer no later tensor takes over still holds its output after the forward
-        bool kept = L.type == L_CONV && L.storage >= 0 && L.residual_from < -1 && !L.stem_skip && !L.pstem_skip && !L.blk_skip && !L.c3s2_skip;
+        bool kept = L.type == L_CONV && L.storage >= 0 && L.residual_from < -1 && !never_stored(L, index);
         if (kept) for (const Storage &o : c->storages) if (&o != &c->storages[L.storage] && o.phys == c->storages[L.storage].phys && o.def > c->storages[L.storage].def) kept = false;
         if (!kept) return fail(c, YOLO_ERR_STATE, "yolo_layer_output needs keep_layers=1 (without it: only a conv layer's own tensor whose buffer no later layer reuses)");
     }

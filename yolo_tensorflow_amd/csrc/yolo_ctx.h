@@ -19,6 +19,9 @@
 namespace yolo_impl {
 
 enum LType { L_CONV, L_SHORTCUT, L_ROUTE, L_UPSAMPLE, L_MAXPOOL, L_REORG, L_YOLO, L_REGION, L_DETECT, L_LOCAL, L_AVGPOOL, L_SOFTMAX };
+enum ConvKernel { K_TILED, K_HALO, K_S2 };      // a conv's own kernel: the tiled family (fp32 / direct / pair form picked by dtype), conv_halo_c32_c64 (3x3/s1, 32 -> 64), conv_s2_c64_c128 (3x3/s2, 64 -> 128)
+// the fused launch a conv is a member of, {members} -> launcher: conv_stem.hip {0, 1, optionally the 1x1 conv 2} -> 1; conv_stem_pair.hip (split-fp16) {0, 1} -> 1; conv_block.hip {1x1 i, 3x3 i + 1} -> i + 1; conv_c3s2.hip {conv3 i, stride-2 conv i + 2} -> i + 2 (both keep K_HALO / K_S2, the fall-back)
+enum FuseKind { F_NONE, F_STEM, F_PSTEM, F_RESBLOCK, F_C3S2 };
 
 struct Section { std::string type; std::map<std::string, std::string> kv; };
 
@@ -39,14 +42,9 @@ struct Layer {
     int residual_from = -2;              // >= -1: fused shortcut source
     bool head = false;                   // conv feeding a yolo/region layer: fp32 output
     float *d_obj = nullptr;              // ... feeding a [yolo] layer (bf16 / fp8 networks): compact plane of its objectness logits [max_batch * H * W][anchors]
-    bool stem_skip = false, stem = false;   // fused stem (conv_stem.hip): layer 0 is never materialised, layer 1 launches both
-    bool pstem_skip = false, pstem = false; // ... the same fusion in a split-fp16 network (conv_stem_pair.hip): image pairs -> conv1's pairs in one launch
-    bool blk_skip = false, blk = false;     // fused residual block (conv_block.hip): this 1x1 conv is computed inside the launch of the 3x3 conv that follows / this 3x3 conv launches both
-    bool stem_tail = false;                 // ... and this 1x1 conv (layer 2) is computed by that launch too
-    bool halo = false;                      // 3x3/s1, 32 -> 64 channels: halo-staged kernel instead of the tiled one
-    bool s2 = false;                        // 3x3/s2, 64 -> 128 channels: window-staged kernel with register-resident filters (conv_s2.hip)
-    bool c3s2_skip = false, c3s2 = false;   // conv3 + its folded shortcut + the stride-2 conv behind them in one launch (conv_c3s2.hip): this 3x3/s1 conv is computed inside
-                                            // the launch of the stride-2 conv two layers on / this stride-2 conv launches both; both keep their halo / s2 marks (the fall-back)
+    int kernel = K_TILED;                // its own kernel: what it runs when it issues a launch of its own.  This and the next line: written by the planner's marking passes only, read through the predicates below
+    int fused = F_NONE, launcher = -1;   // the fused launch it is a member of, and the layer that issues that launch
+    int fuse_n = 0; bool fuse_ok = false;      // run state (run_conv), on the launcher of a group that may fall back: does its kernel take batch fuse_n (0: not asked yet)?  Valid for the plan's life: the answer depends on n and plan-fixed geometry only
     // [connected] (YOLOv1's fully connected head, V1/YOLO_V1_Inference.py:196-206; DN/connected_layer.c:151): a 1x1 conv over the
     // producer's tensor flattened to one pixel per image; fc_h/w/c = the producer's geometry (darknet / the TF graph flatten CHW)
     bool fc = false; int fc_h = 0, fc_w = 0, fc_c = 0;
@@ -171,6 +169,15 @@ inline void drop_graph(yolo_ctx *c)      // a plan / parameter / buffer change: 
     if (c->gexec_img) { hipGraphExecDestroy(c->gexec_img); c->gexec_img = nullptr; } if (c->gstate_img > 0) c->gstate_img = 0;
 }
 
+// ---- what a conv layer's (kernel, fused, launcher) mean: the only places that enumerate fused kinds; `i` = the layer's own index.  Where two of the old lists disagreed: NOTEBOOK 2026-10-18 ----
+inline bool fused_may_fall_back(const Layer &L) { return L.fused == F_RESBLOCK || L.fused == F_C3S2; }      // to its members' own kernels, where the fused launch's 32-bit windows do not hold the batch; the stems cannot (layer 0 has no storage) and refuse
+inline bool never_stored(const Layer &L, int i) { return L.fused != F_NONE && i < L.launcher; }      // the tensor stays in LDS in the fused plan: every member in front of its launcher
+inline bool input_never_loaded(const Layer &L, int i) { return L.fused != F_NONE && L.fused != F_PSTEM && i >= L.launcher; }      // (yolo_conv_bytes) the pair stem's layer 1 is left out: not intended, kept (the bench's roofline line)
+inline bool fixed_kernel(const Layer &L) { return L.kernel != K_TILED || L.fused != F_NONE; }      // nothing for the tile tuner to choose, no 1x1 tail to host
+inline bool window_check_skipped(const Layer &L, int i) { return L.fused != F_NONE && (!fused_may_fall_back(L) || (L.fused == F_RESBLOCK && i < L.launcher)); }      // by allocate()'s 2 GiB check.  A resblock's inner 1x1 should be checked like the other members of groups that may fall back: not intended, kept, unreachable in darknet-53
+inline bool rides_as_tail(const yolo_ctx *c, const Layer &L) { return L.fused_into >= 0 && c->layers[L.fused_into].tail_on; }      // computed in its producer's epilogue (tail_on is toggled after planning)
+inline bool issues_launch(const yolo_ctx *c, int i) { const Layer &L = c->layers[i]; return (L.fused == F_NONE || L.launcher == i) && !rides_as_tail(c, L); }      // in the fused plan (the members of a group that fell back do so too)
+
 // yolo_pack.cpp
 uint16_t f2bf(float f);
 uint16_t f2h(float f);
@@ -195,7 +202,6 @@ bool parse_cfg(const char *text, std::vector<Section> &out, std::string &err);
 int build_plan(yolo_ctx *c, const std::vector<Section> &secs);
 int allocate(yolo_ctx *c);
 TView view_of(const yolo_ctx *c, int idx);
-bool fixed_kernel(const Layer &L);      // layers whose kernel is fixed by a fusion (nothing for the tile tuner to choose)
 // yolo_run.cpp
 ConvArgs conv_args(const yolo_ctx *c, const Layer &L, int n);
 int run_layer(yolo_ctx *c, int i, int n);

@@ -304,19 +304,19 @@ int build_plan(yolo_ctx *c, const std::vector<Section> &secs)
                 A.size == 1 && A.stride == 1 && A.pad == 0 && A.cin == 128 && A.filters == 64 && B.cin == 64 && B.filters == 128 && A.residual_from < -1 &&
                 B.size == 3 && B.stride == 1 && B.pad == 1 && B.residual_from == A.in[0] &&
                 ((long)((B.H + 12) / 13) * ((B.W + 12) / 13) * 169 * 100 <= (long)B.H * B.W * 115) && A.in_dt == B.in_dt && (A.in_dt == DT_BF16 || A.in_dt == DT_F16) && A.store_dt == A.in_dt && B.store_dt == A.in_dt &&
-                c->layers[A.in[0]].store_dt == A.in_dt && !A.pair && !B.pair && !c->pair_of(A.in[0])) { A.blk_skip = true; B.blk = true; }
+                c->layers[A.in[0]].store_dt == A.in_dt && !A.pair && !B.pair && !c->pair_of(A.in[0])) { A.fused = B.fused = F_RESBLOCK; A.launcher = B.launcher = i + 1; }
         }
     if (ctx16 && !c->keep_layers && NL >= 2 && (double)c->max_batch * c->in_h * c->in_w * 8 * 2 < 2147483648.0) {
         const Layer &A = c->layers[0], &B = c->layers[1];
         if (A.type == L_CONV && B.type == L_CONV && uses[0] == 1 && B.in[0] == 0 && A.size == 3 && A.stride == 1 && A.pad == 1 && A.cin == 3 &&
             A.filters == 32 && B.size == 3 && B.stride == 2 && B.pad == 1 && B.filters == 64 && !A.head && !B.head && B.residual_from < -1 &&
             is16(A.in_dt) && A.store_dt == A.in_dt && B.in_dt == A.in_dt && B.store_dt == A.in_dt && !c->in_pair && !A.pair && !B.pair) {        // (layer 0 reads the staged image, which is kept in its operand type)
-            c->layers[0].stem_skip = true; c->layers[1].stem = true;
+            for (int k = 0; k < 2; ++k) { c->layers[k].fused = F_STEM; c->layers[k].launcher = 1; }
             if (NL >= 3) {
                 const Layer &T = c->layers[2];
                 if (T.type == L_CONV && !T.fc && T.in[0] == 1 && T.size == 1 && T.stride == 1 && T.pad == 0 && T.filters == 32 && !T.head && T.residual_from < -1 &&
                     T.in_dt == A.in_dt && T.store_dt == A.in_dt && !T.pair)
-                    c->layers[2].stem_tail = true;
+                    { c->layers[2].fused = F_STEM; c->layers[2].launcher = 1; }
             }
         }
     }
@@ -326,35 +326,31 @@ int build_plan(yolo_ctx *c, const std::vector<Section> &secs)
         if (A.type == L_CONV && B.type == L_CONV && uses[0] == 1 && B.in[0] == 0 && A.size == 3 && A.stride == 1 && A.pad == 1 && A.cin == 3 && A.bn == B.bn &&
             (A.filters == 32) && B.size == 3 && B.stride == 2 && B.pad == 1 && B.filters == 64 && !A.head && !B.head && A.residual_from < -1 && B.residual_from < -1 &&
             A.pair && B.pair && c->in_h % 2 == 0 && c->in_w % 2 == 0 && A.kpad >= 216 && B.kpad == 576) {
-            c->layers[0].pstem_skip = true; c->layers[1].pstem = true;
+            for (int k = 0; k < 2; ++k) { c->layers[k].fused = F_PSTEM; c->layers[k].launcher = 1; }
         }
     }
     if (ctx16 && !getenv("YOLO_NO_HALO"))
         for (int i = 1; i < NL; ++i) {
             Layer &L = c->layers[i];
-            if (L.type == L_CONV && !L.head && !L.stem && !L.stem_skip && !L.stem_tail && !L.blk && L.size == 3 && L.stride == 1 && L.pad == 1 && L.cin == 32 && L.filters == 64 &&
-                is16(L.in_dt) && L.store_dt == L.in_dt && (L.residual_from < 0 || c->layers[L.residual_from].store_dt == L.in_dt) && !L.pair && !c->pair_of(L.in[0]))
-                L.halo = true;
+            if (L.type != L_CONV || L.head || L.fused != F_NONE || L.size != 3 || L.pad != 1 || !is16(L.in_dt) || L.store_dt != L.in_dt || L.pair || c->pair_of(L.in[0])) continue;
+            if (L.stride == 1 && L.cin == 32 && L.filters == 64 && (L.residual_from < 0 || c->layers[L.residual_from].store_dt == L.in_dt)) L.kernel = K_HALO;
             // darknet-53's 64 -> 128 downsampling conv: window-staged, filters in registers (conv_s2.hip)
-            if (L.type == L_CONV && !L.head && !L.stem && !L.stem_skip && !L.stem_tail && !L.blk && !L.blk_skip && L.size == 3 && L.stride == 2 && L.pad == 1 && L.cin == 64 &&
-                L.filters == 128 && L.residual_from < -1 && is16(L.in_dt) && L.store_dt == L.in_dt && !L.pair && !c->pair_of(L.in[0]) && !getenv("YOLO_NO_S2"))
-                L.s2 = true;
+            if (L.stride == 2 && L.cin == 64 && L.filters == 128 && L.residual_from < -1 && !getenv("YOLO_NO_S2")) L.kernel = K_S2;
         }
-    // conv3 + shortcut + stride-2 conv in one launch (conv_c3s2.hip): a halo conv whose folded shortcut output (layer i + 1) is read by
-    // the s2 conv at i + 2 and by nobody else -- that tensor then never leaves LDS.  Both layers keep their own marks: the two kernels
-    // are the fall-back where the fused launch's 32-bit windows do not hold the batch
+    // conv3 + shortcut + stride-2 conv in one launch (conv_c3s2.hip): a halo conv whose folded shortcut output (layer i + 1) is read by the s2 conv at i + 2 and by
+    // nobody else -- that tensor then never leaves LDS.  Both layers keep their own kernels: the fall-back where the fused launch's 32-bit windows do not hold the batch
     if (ctx16 && !c->keep_layers && !getenv("YOLO_NO_C3S2"))
         for (int i = 1; i + 2 < NL; ++i) {
             Layer &A = c->layers[i], &S = c->layers[i + 1], &B = c->layers[i + 2];
-            if (A.halo && B.s2 && A.residual_from >= 0 && S.type == L_SHORTCUT && S.noop && uses[i] == 1 && uses[i + 1] == 1 && B.in[0] == i + 1 && A.in[0] >= 0 &&
-                A.in_dt == B.in_dt && c->layers[A.residual_from].C == 64) { A.c3s2_skip = true; B.c3s2 = true; }
+            if (A.kernel == K_HALO && B.kernel == K_S2 && A.residual_from >= 0 && S.type == L_SHORTCUT && S.noop && uses[i] == 1 && uses[i + 1] == 1 && B.in[0] == i + 1 && A.in[0] >= 0 &&
+                A.in_dt == B.in_dt && c->layers[A.residual_from].C == 64) { A.fused = B.fused = F_C3S2; A.launcher = B.launcher = i + 2; }
         }
     // 1x1 convs that can ride in their producer's epilogue: conv i (bf16, 128 or 256 output channels, optionally with its
     // fused shortcut) read by a 1x1/s1 conv with half as many filters
     if (ctx16 && !c->keep_layers) {
         for (int i = 0; i + 1 < NL; ++i) {
             Layer &P = c->layers[i];
-            if (P.type != L_CONV || P.fc || P.head || P.stem || P.stem_skip || P.stem_tail || P.blk || P.s2 || P.halo || (P.filters != 128 && P.filters != 256)) continue;      // (fixed kernels host no tail: run_layer would skip the 1x1)
+            if (P.type != L_CONV || P.fc || P.head || fixed_kernel(P) || (P.filters != 128 && P.filters != 256)) continue;      // (fixed kernels host no tail: run_conv would skip the 1x1)
             if (c->split() && (P.pair || c->pair_of(P.in[0]))) continue;       // (split-fp16 networks: the tail rides on plain fp16 layers only)
             int o = i;
             if (P.residual_from >= -1) o = i + 1;            // its shortcut was folded into it: consumers read layer i+1
@@ -362,7 +358,7 @@ int build_plan(yolo_ctx *c, const std::vector<Section> &secs)
             if (j >= NL) continue;
             Layer &T = c->layers[j];
             if (T.type == L_CONV && !T.fc && T.in[0] == o && T.size == 1 && T.stride == 1 && T.pad == 0 && T.filters * 2 == P.filters && !T.head &&
-                T.residual_from < -1 && !T.stem_tail && !T.blk_skip && T.in_dt == P.in_dt && !T.pair) { P.tail_layer = j; T.fused_into = i; }      // (same operand type: the tail runs on the producer's MFMA)
+                T.residual_from < -1 && issues_launch(c, j) && T.in_dt == P.in_dt && !T.pair) { P.tail_layer = j; T.fused_into = i; }      // (same operand type: the tail runs on the producer's MFMA)
             // round 5: a detection head (1x1, <= 256 filters, fp32 out, linear) as the tail of the 256-channel 3x3 in front of it when nobody else
             // reads that conv (darknet-53's 52 x 52 head): the head tensor is formed from the tile in LDS, bit-identical to the stand-alone launch
             else if (T.type == L_CONV && !T.fc && T.head && T.in[0] == o && uses[o] == 1 && T.size == 1 && T.stride == 1 && T.pad == 0 && P.filters == 256 && T.filters <= 256 &&
@@ -406,7 +402,7 @@ int build_plan(yolo_ctx *c, const std::vector<Section> &secs)
         if (L.type == L_YOLO || L.type == L_REGION || L.type == L_DETECT) { L.noop = true; L.storage = c->layers[i - 1].storage; L.ch_off = c->layers[i - 1].ch_off; continue; }
         if (L.type == L_ROUTE && L.in.size() == 1) { L.noop = true; int j = L.in[0]; if (j < 0) return fail(c, YOLO_ERR_UNSUPPORTED, "route to network input"); L.storage = c->layers[j].storage; L.ch_off = c->layers[j].ch_off; continue; }
         if (L.type == L_ROUTE) continue;
-        if (L.stem_skip || L.pstem_skip) { L.noop = true; continue; }               // lives in LDS only
+        if (never_stored(L, i) && !fused_may_fall_back(L)) { L.noop = true; continue; }               // lives in LDS only; a group that may fall back keeps its members' storage
         if (L.type == L_SOFTMAX) { L.storage = new_storage(L.C, DT_F32, (size_t)c->max_batch, true); continue; }      // dense [n][C] probabilities
         if (place_route[i] >= 0) { L.storage = c->layers[place_route[i]].storage; L.ch_off = place_off[i]; }
         else if (L.head) L.storage = new_storage(roundup(L.C, 4), DT_F32, (size_t)c->max_batch * L.H * L.W, true);
@@ -426,13 +422,11 @@ int build_plan(yolo_ctx *c, const std::vector<Section> &secs)
     for (int i = 0; i < NL; ++i) {
         Layer &L = c->layers[i];
         if (L.storage < 0) continue;
-        if (!L.noop) { Storage &s = c->storages[L.storage]; s.def = std::min(s.def, L.fused_into >= 0 ? L.fused_into : i); s.last = std::max(s.last, i); }
+        if (!L.noop) { Storage &s = c->storages[L.storage]; s.def = std::min(s.def, L.fused_into >= 0 ? L.fused_into : i); s.last = std::max(s.last, i); }      // (whichever way tail_on is toggled later)
         for (int j : L.in) if (j >= 0 && c->layers[j].storage >= 0) { Storage &s = c->storages[c->layers[j].storage]; s.last = std::max(s.last, i); }
         if (L.type == L_CONV && L.residual_from >= 0) { Storage &s = c->storages[c->layers[L.residual_from].storage]; s.last = std::max(s.last, i); }
-        if (L.c3s2) {           // this launch reads what the 3x3/s1 conv two layers back reads: its input and its shortcut source live until here
-            const Layer &A = c->layers[i - 2];
-            for (int j : {A.in[0], A.residual_from}) if (j >= 0 && c->layers[j].storage >= 0) { Storage &s = c->storages[c->layers[j].storage]; s.last = std::max(s.last, i); }
-        }
+        if (never_stored(L, i))           // its group's launch reads what this layer reads: its input and its shortcut source live until the launcher
+            for (int j : {L.in[0], L.residual_from}) if (j >= 0 && c->layers[j].storage >= 0) { Storage &s = c->storages[c->layers[j].storage]; s.last = std::max(s.last, L.launcher); }
     }
     // greedy pooled assignment
     std::vector<int> free_list;
@@ -556,7 +550,7 @@ int allocate(yolo_ctx *c)
     if (c->dtype != YOLO_FP32)
         for (size_t i = 0; i < c->layers.size(); ++i) {
             const Layer &L = c->layers[i];
-            if (L.type != L_CONV || L.fc || L.s2d7 || L.stem_skip || L.stem || L.stem_tail || L.blk_skip || L.pstem_skip || L.pstem) continue;     // (fused layers: their launch checks its own windows)
+            if (L.type != L_CONV || L.fc || L.s2d7 || window_check_skipped(L, (int)i)) continue;     // (fused layers: their launch checks its own windows)
             const TView in = view_of(c, L.in[0]);
             const double per_image = (double)in.h * in.w * in.stride * dt_size(L.in_dt), slack = 2.0 * (in.w + 1) * in.stride * dt_size(L.in_dt);
             if (per_image * c->max_batch + slack >= 2147483648.0)
@@ -565,7 +559,5 @@ int allocate(yolo_ctx *c)
         }
     return YOLO_OK;
 }
-
-bool fixed_kernel(const Layer &L) { return L.stem || L.stem_skip || L.stem_tail || L.halo || L.s2 || L.blk || L.blk_skip || L.pstem || L.pstem_skip || L.c3s2 || L.c3s2_skip; }
 
 }  // namespace yolo_impl

@@ -72,91 +72,144 @@ static int via_f32(yolo_ctx *c, const Layer &L, int n, int kind)
     return YOLO_OK;
 }
 
+// ---- one builder per argument struct of the fused / fixed launches, each called once per launch.  `l`: the group's launcher ----
+static StemPairArgs stem_pair_args(const yolo_ctx *c, int l, int n)          // split-fp16: conv0 + conv1 in one launch (conv_stem_pair.hip)
+{
+    const Layer &A = c->layers[0], &L = c->layers[l]; StemPairArgs t; memset(&t, 0, sizeof t);
+    t.in = c->input.ptr; t.w0 = A.d_w; t.b0 = A.d_b; t.Kpad0 = A.kpad; t.C0 = A.filters; t.act0 = A.act;
+    t.in_u8 = c->stem_u8; t.in_scale = c->stem_scale; t.in_mul = c->in_mul; t.in_add = c->in_add;
+    t.w1 = L.d_w; t.b1 = L.d_b; t.Kpad1 = L.kpad; t.act1 = L.act;
+    t.out = L.out.ptr; t.out_stride = L.out.stride; t.N = n; t.H = A.H; t.W = A.W; t.Ho = L.H; t.Wo = L.W;
+    return t;
+}
+static StemArgs stem_args(const yolo_ctx *c, int l, int n)
+{
+    const Layer &A = c->layers[0], &L = c->layers[l]; StemArgs t; memset(&t, 0, sizeof t);
+    t.in = c->input.ptr; t.in_stride = c->input.stride;
+    t.in_u8 = c->stem_u8; t.in_scale = c->stem_scale; t.in_mul = c->in_mul; t.in_add = c->in_add;
+    t.w0 = A.d_w; t.b0 = A.d_b; t.Kpad0 = A.kpad; t.C0 = A.filters; t.act0 = A.act;
+    t.w1 = L.d_w; t.b1 = L.d_b; t.Kpad1 = L.kpad; t.C1 = L.filters; t.act1 = L.act;
+    if (l + 1 < (int)c->layers.size() && c->layers[l + 1].fused == L.fused) { const Layer &T = c->layers[l + 1];          // the group's third member: the 1x1 conv behind conv1
+        t.w2 = T.d_w; t.b2 = T.d_b; t.Kpad2 = T.kpad; t.C2 = T.filters; t.act2 = T.act; t.out2 = T.out.ptr; t.out2_stride = T.out.stride;
+    }
+    t.out = L.out.ptr; t.out_stride = L.out.stride; t.N = n; t.H = A.H; t.W = A.W; t.Ho = L.H; t.Wo = L.W; t.zeros = c->d_zeros; t.dt = L.in_dt;
+    return t;
+}
+static BlockArgs block_args(const yolo_ctx *c, int l, int n)          // fused residual block: the 1x1 (A) is computed inside the 3x3's (B) launch
+{
+    const Layer &A = c->layers[l - 1], &B = c->layers[l]; const TView x = view_of(c, A.in[0]); BlockArgs b; memset(&b, 0, sizeof b);
+    b.x = x.ptr; b.x_stride = x.stride; b.w1 = A.d_w; b.b1 = A.d_b; b.Kpad1 = A.kpad; b.act1 = A.act;
+    b.w2 = B.d_w; b.b2 = B.d_b; b.Kpad2 = B.kpad; b.act2 = B.act; b.out = B.out.ptr; b.out_stride = B.out.stride;
+    b.N = n; b.H = B.H; b.W = B.W; b.C = B.filters; b.Cmid = A.filters; b.dt = B.in_dt;
+    return b;
+}
+static C3S2Args c3s2_args(const yolo_ctx *c, int l, int n)          // conv3 + shortcut (A) are computed inside the stride-2 conv's (B) launch
+{
+    const Layer &A = c->layers[l - 2], &B = c->layers[l]; const TView x = view_of(c, A.in[0]), r = view_of(c, A.residual_from); C3S2Args t; memset(&t, 0, sizeof t);
+    t.in = x.ptr; t.in_stride = x.stride; t.w3 = A.d_w; t.b3 = A.d_b; t.Kpad3 = A.kpad; t.act3 = A.act; t.res = r.ptr; t.res_stride = r.stride;
+    t.w5 = B.d_w; t.b5 = B.d_b; t.Kpad5 = B.kpad; t.act5 = B.act; t.out = B.out.ptr; t.out_stride = B.out.stride;
+    t.N = n; t.H = A.H; t.W = A.W; t.dt = B.in_dt;
+    return t;
+}
+static HaloArgs halo_args(const ConvArgs &a, const Layer &L, int n)      // for conv_halo_c32_c64 and conv_s2_c64_c128.  H, W: the input's, which are the output's of the 3x3/s1/pad-1 halo conv; res / res_stride: 0 for K_S2 (it folds no shortcut)
+{
+    HaloArgs h; memset(&h, 0, sizeof h);
+    h.in = a.in; h.in_stride = a.in_stride; h.w = a.wt; h.b = a.bias; h.Kpad = a.Kpad; h.Cin = L.cin; h.Cout = L.filters; h.act = L.act;
+    h.res = a.res; h.res_stride = a.res_stride; h.out = a.out; h.out_stride = a.out_stride; h.N = n; h.H = a.H; h.W = a.W; h.dt = L.in_dt;
+    return h;
+}
+
+static bool fused_launch_applies(yolo_ctx *c, const Layer &L, int n)      // at batch n (no group: no)?  A group that may fall back asks its kernel once per batch size and keeps the answer on its launcher: every member takes the same branch
+{
+    if (!fused_may_fall_back(L)) return L.fused != F_NONE;
+    Layer &G = c->layers[L.launcher]; const int l = L.launcher;
+    if (G.fuse_n != n) { G.fuse_ok = L.fused == F_RESBLOCK ? conv_resblock_ok(block_args(c, l, n)) : conv_c3s2_ok(c3s2_args(c, l, n)); G.fuse_n = n; }
+    return G.fuse_ok;
+}
+
+static int run_conv(yolo_ctx *c, int i, int n)
+{
+    Layer &L = c->layers[i];
+    hipStream_t s = c->stream;
+    auto nview = [&](TView v) { v.n = n; return v; };
+    if (fused_launch_applies(c, L, n)) {          // computed inside its group's launch, which the launcher issues
+        if (i == L.launcher) switch (L.fused) {
+        case F_STEM: { StemArgs t = stem_args(c, i, n); HIPCK(c, launch_conv_stem(t, s)); break; }
+        case F_PSTEM: { StemPairArgs t = stem_pair_args(c, i, n); if (c->input.stride != 24 || !conv_stem_pair_ok(t)) return fail(c, YOLO_ERR_STATE, "layer %d: the fused split-fp16 stem does not apply to this plan", i);
+            HIPCK(c, launch_conv_stem_pair(t, s)); break; }
+        case F_RESBLOCK: { BlockArgs b = block_args(c, i, n); HIPCK(c, launch_conv_resblock(b, s)); break; }
+        case F_C3S2: { C3S2Args t = c3s2_args(c, i, n); HIPCK(c, launch_conv_c3s2(t, s)); break; }
+        }
+        return YOLO_OK;
+    }
+    if (rides_as_tail(c, L)) return YOLO_OK;        // computed in the producer's epilogue
+    ConvArgs a = conv_args(c, L, n);
+    if (L.tail_on && !a.w2) return fail(c, YOLO_ERR_STATE, "layer %d: the plan folds the 1x1 conv %d into this layer, but its filters are not available in the producer's operand type", i, L.tail_layer);
+    if (L.s2d7) HIPCK(c, launch_reorg(nview(c->input), nview(c->s2d), 2, 0, s));      // tf.space_to_depth order: (dy, dx, channel)
+    if (L.kernel != K_TILED) {          // input tile (K_HALO, conv_stem.hip) / window (K_S2, conv_s2.hip) staged once in LDS; a window over 2 GiB (very large batches): the tiled kernel below checks its own
+        HaloArgs h = halo_args(a, L, n);
+        if (L.kernel == K_HALO && conv_halo_ok(h)) { HIPCK(c, launch_conv_halo(h, s)); return YOLO_OK; }
+        if (L.kernel == K_S2 && conv_s2_ok(h)) { HIPCK(c, launch_conv_s2(h, s)); return YOLO_OK; }
+    }
+    if (c->dtype == YOLO_FP32) { HIPCK(c, launch_conv_f32(a, s)); return YOLO_OK; }
+    const int cfg = conv_resolve_cfg(a, L.tile_cfg);
+    if (a.w2 && !a.split && !a.pairk && !conv_cfg_tail_ok(cfg, a.Cout, a.in_dt == DT_FP8, a.tail_f32 != 0)) return fail(c, YOLO_ERR_STATE, "layer %d: tile config %d cannot run the fused 1x1 tail", i, cfg);
+    HIPCK(c, a.in_dt == DT_FP8 ? launch_conv_fp8(a, cfg, s) : launch_conv_bf16(a, cfg, s));
+    return YOLO_OK;
+}
+
+static int run_decode(yolo_ctx *c, int i, int n)
+{
+    const Layer &L = c->layers[i];
+    hipStream_t s = c->stream;
+    if (L.tree < 0 && c->lean && c->lean_thr > 0.f && c->lean_heads >= 1 && c->lean_heads <= 4) {
+        // lean detect path: every [yolo] head is decoded by ONE launch, issued at the last head (the head tensors keep their own buffers)
+        bool later_head = false;
+        for (size_t k = i + 1; k < c->layers.size(); ++k) later_head |= c->layers[k].type == L_YOLO;
+        if (later_head) return YOLO_OK;
+        LeanArgs la; memset(&la, 0, sizeof la);
+        long begin = 0;
+        for (size_t k = 0; k < c->layers.size(); ++k) {
+            const Layer &Y = c->layers[k];
+            if (Y.type != L_YOLO) continue;
+            const Layer &P = c->layers[k - 1];
+            LeanHead &h = la.h[la.nheads++];
+            h.raw = (const float *)P.out.ptr; h.obj = P.d_obj; h.raw_stride = P.out.stride; h.g = Y.H; h.na = Y.na; h.row_off = Y.row_off; h.box_begin = begin;
+            const int stride = c->in_h / Y.H;
+            for (int q = 0; q < 2 * Y.na; ++q) h.anchors[q] = (float)(1.0 * (double)Y.anchors[q] / (double)stride);
+            begin += (long)n * Y.H * Y.W * Y.na;
+        }
+        la.total = begin; la.n = n; la.classes = L.classes; la.img_size = c->in_h; la.mode = c->decode; la.rows_total = c->rows;
+        la.box4 = c->d_box4; la.reject_below = c->lean_thr; la.list = (uint4 *)c->d_lean_list; la.list_count = c->d_lean_cnt; la.list_cap = (unsigned)((size_t)c->max_batch * c->rows);
+        // the list counter must be zero: the NMS launch of the previous detect call resets it; if none ran since the last decode
+        // (a failed call in between), a memset does
+        if (c->lean_cnt_dirty) HIPCK(c, hipMemsetAsync(c->d_lean_cnt, 0, 4, s));
+        c->lean_cnt_dirty = true;
+        HIPCK(c, launch_decode_lean(la, c->d_scores, c->d_labels, s));
+        return YOLO_OK;
+    }
+    const Layer &P = c->layers[i - 1];
+    DecodeArgs d; memset(&d, 0, sizeof d);          // one fill for the three decode launches below
+    d.raw = (const float *)P.out.ptr; d.raw_stride = P.out.stride; d.n = n; d.g = L.H; d.na = L.na; d.classes = L.classes;
+    d.img_size = c->in_h; d.mode = c->decode; d.region = L.type == L_REGION;
+    const int stride = c->in_h / L.H;
+    for (int k = 0; k < 2 * L.na; ++k) d.anchors[k] = L.type == L_YOLO ? (float)(1.0 * (double)L.anchors[k] / (double)stride) : L.anchors[k];
+    d.det = c->lean ? nullptr : c->d_det; d.box4 = c->lean ? c->d_box4 : nullptr; d.rows_total = c->rows; d.row_off = L.row_off;
+    d.reject_below = c->lean ? c->lean_thr : -INFINITY;
+    // [region] with a softmax tree.  Full form: the decoded tensor with absolute class probabilities (scored at postprocess time, with the hier_thresh of that moment); descent form (yolo_detect*): box4, scores, labels straight from the raw tensor
+    if (L.tree < 0) HIPCK(c, launch_decode(d, c->d_scores, c->d_labels, s));
+    else if (c->lean) { HIPCK(c, launch_decode_region_tree_lean(d, c->trees[L.tree].dev, c->hier_thresh, c->d_scores, c->d_labels, s)); c->lean_hier = c->hier_thresh; }
+    else HIPCK(c, launch_decode_region_tree(d, c->trees[L.tree].dev, s));
+    return YOLO_OK;
+}
+
 int run_layer(yolo_ctx *c, int i, int n)
 {
     Layer &L = c->layers[i];
     hipStream_t s = c->stream;
     auto nview = [&](TView v) { v.n = n; return v; };
     switch (L.type) {
-    case L_CONV: {
-        if (L.stem_skip || L.stem_tail || L.pstem_skip) break;
-        if (L.pstem) {           // split-fp16: conv0 + conv1 in one launch (conv_stem_pair.hip)
-            const Layer &A = c->layers[0];
-            StemPairArgs t; memset(&t, 0, sizeof t);
-            t.in = c->input.ptr; t.w0 = A.d_w; t.b0 = A.d_b; t.Kpad0 = A.kpad; t.C0 = A.filters; t.act0 = A.act;
-            t.in_u8 = c->stem_u8; t.in_scale = c->stem_scale; t.in_mul = c->in_mul; t.in_add = c->in_add;
-            t.w1 = L.d_w; t.b1 = L.d_b; t.Kpad1 = L.kpad; t.act1 = L.act;
-            t.out = L.out.ptr; t.out_stride = L.out.stride; t.N = n; t.H = A.H; t.W = A.W; t.Ho = L.H; t.Wo = L.W;
-            if (c->input.stride != 24 || !conv_stem_pair_ok(t)) return fail(c, YOLO_ERR_STATE, "layer %d: the fused split-fp16 stem does not apply to this plan", i);
-            HIPCK(c, launch_conv_stem_pair(t, s));
-            break;
-        }
-        if (L.fused_into >= 0 && c->layers[L.fused_into].tail_on) break;        // computed in the producer's epilogue
-        if (L.stem) {
-            const Layer &A = c->layers[0];
-            StemArgs t; memset(&t, 0, sizeof t);
-            t.in = c->input.ptr; t.in_stride = c->input.stride;
-            t.in_u8 = c->stem_u8; t.in_scale = c->stem_scale; t.in_mul = c->in_mul; t.in_add = c->in_add;
-            t.w0 = A.d_w; t.b0 = A.d_b; t.Kpad0 = A.kpad; t.C0 = A.filters; t.act0 = A.act;
-            t.w1 = L.d_w; t.b1 = L.d_b; t.Kpad1 = L.kpad; t.C1 = L.filters; t.act1 = L.act;
-            if (i + 1 < (int)c->layers.size() && c->layers[i + 1].stem_tail) {
-                const Layer &T = c->layers[i + 1];
-                t.w2 = T.d_w; t.b2 = T.d_b; t.Kpad2 = T.kpad; t.C2 = T.filters; t.act2 = T.act; t.out2 = T.out.ptr; t.out2_stride = T.out.stride;
-            }
-            t.out = L.out.ptr; t.out_stride = L.out.stride; t.N = n; t.H = A.H; t.W = A.W; t.Ho = L.H; t.Wo = L.W; t.zeros = c->d_zeros; t.dt = L.in_dt;
-            HIPCK(c, launch_conv_stem(t, s));
-            break;
-        }
-        if (L.blk_skip || L.blk) {
-            // fused residual block: the 1x1 (blk_skip) is computed inside the 3x3's launch; were the batch window ever beyond the
-            // kernel's 32-bit offsets, both run as ordinary layers
-            const Layer &A = L.blk ? c->layers[i - 1] : L, &B = L.blk ? L : c->layers[i + 1];
-            const TView x = view_of(c, A.in[0]);
-            BlockArgs b; memset(&b, 0, sizeof b);
-            b.x = x.ptr; b.x_stride = x.stride; b.w1 = A.d_w; b.b1 = A.d_b; b.Kpad1 = A.kpad; b.act1 = A.act;
-            b.w2 = B.d_w; b.b2 = B.d_b; b.Kpad2 = B.kpad; b.act2 = B.act; b.out = B.out.ptr; b.out_stride = B.out.stride;
-            b.N = n; b.H = B.H; b.W = B.W; b.C = B.filters; b.Cmid = A.filters; b.dt = B.in_dt;
-            if (conv_resblock_ok(b)) {
-                if (L.blk) HIPCK(c, launch_conv_resblock(b, s));
-                break;
-            }
-        }
-        if (L.c3s2_skip || L.c3s2) {
-            // conv3 + shortcut (c3s2_skip) are computed inside the stride-2 conv's launch; were the batch window ever beyond the kernel's
-            // 32-bit offsets, both run as the layers they are (halo / s2 below)
-            const Layer &A = L.c3s2 ? c->layers[i - 2] : L, &B = L.c3s2 ? L : c->layers[i + 2];
-            const TView x = view_of(c, A.in[0]), r = view_of(c, A.residual_from);
-            C3S2Args t; memset(&t, 0, sizeof t);
-            t.in = x.ptr; t.in_stride = x.stride; t.w3 = A.d_w; t.b3 = A.d_b; t.Kpad3 = A.kpad; t.act3 = A.act; t.res = r.ptr; t.res_stride = r.stride;
-            t.w5 = B.d_w; t.b5 = B.d_b; t.Kpad5 = B.kpad; t.act5 = B.act; t.out = B.out.ptr; t.out_stride = B.out.stride;
-            t.N = n; t.H = A.H; t.W = A.W; t.dt = B.in_dt;
-            if (conv_c3s2_ok(t)) {
-                if (L.c3s2) HIPCK(c, launch_conv_c3s2(t, s));
-                break;
-            }
-        }
-        ConvArgs a = conv_args(c, L, n);
-        if (L.tail_on && !a.w2) return fail(c, YOLO_ERR_STATE, "layer %d: the plan folds the 1x1 conv %d into this layer, but its filters are not available in the producer's operand type", i, L.tail_layer);
-        if (L.s2d7) HIPCK(c, launch_reorg(nview(c->input), nview(c->s2d), 2, 0, s));      // tf.space_to_depth order: (dy, dx, channel)
-        if (L.halo) {          // small-Cin 3x3: input tile staged once in LDS (conv_stem.hip)
-            HaloArgs h; memset(&h, 0, sizeof h);
-            h.in = a.in; h.in_stride = a.in_stride; h.w = a.wt; h.b = a.bias; h.Kpad = a.Kpad; h.Cin = L.cin; h.Cout = L.filters; h.act = L.act;
-            h.res = a.res; h.res_stride = a.res_stride; h.out = a.out; h.out_stride = a.out_stride; h.N = n; h.H = L.H; h.W = L.W; h.dt = L.in_dt;
-            if (conv_halo_ok(h)) { HIPCK(c, launch_conv_halo(h, s)); break; }
-            // window over 2 GiB (very large batches): the tiled kernel below checks its own window
-        }
-        if (L.s2) {            // 3x3/s2 64 -> 128: window staged once in LDS, filters in registers (conv_s2.hip)
-            HaloArgs h; memset(&h, 0, sizeof h);
-            const TView in = view_of(c, L.in[0]);
-            h.in = a.in; h.in_stride = a.in_stride; h.w = a.wt; h.b = a.bias; h.Kpad = a.Kpad; h.Cin = L.cin; h.Cout = L.filters; h.act = L.act;
-            h.res = a.res; h.out = a.out; h.out_stride = a.out_stride; h.N = n; h.H = in.h; h.W = in.w; h.dt = L.in_dt;
-            if (conv_s2_ok(h)) { HIPCK(c, launch_conv_s2(h, s)); break; }
-        }
-        if (c->dtype == YOLO_FP32) { HIPCK(c, launch_conv_f32(a, s)); break; }
-        const int cfg = conv_resolve_cfg(a, L.tile_cfg);
-        if (a.w2 && !a.split && !a.pairk && !conv_cfg_tail_ok(cfg, a.Cout, a.in_dt == DT_FP8, a.tail_f32 != 0)) return fail(c, YOLO_ERR_STATE, "layer %d: tile config %d cannot run the fused 1x1 tail", i, cfg);
-        HIPCK(c, a.in_dt == DT_FP8 ? launch_conv_fp8(a, cfg, s) : launch_conv_bf16(a, cfg, s));
-        break; }
+    case L_CONV: return run_conv(c, i, n);
     case L_SHORTCUT:
         if (!L.noop && L.pair) {
             HIPCK(c, launch_add_split(view_of(c, L.in[0]).ptr, view_of(c, L.in[0]).stride, view_of(c, L.in[1]).ptr, view_of(c, L.in[1]).stride, L.out.ptr, L.out.stride, roundup(L.C, 32), (size_t)n * L.H * L.W, s));
@@ -221,58 +274,7 @@ int run_layer(yolo_ctx *c, int i, int n)
         HIPCK(c, launch_decode_v1((const float *)P.out.ptr, P.out.stride, n, L.side, L.na, L.classes, L.sqr, c->d_det, c->rows, L.row_off,
                                   c->d_scores, c->d_labels, s));
         break; }
-    case L_YOLO: case L_REGION: {
-        if (L.tree >= 0) {
-            // [region] with a softmax tree.  Full form: the decoded tensor with absolute class probabilities (scored at postprocess time,
-            // with the hier_thresh of that moment); descent form (yolo_detect*): box4, scores, labels straight from the raw tensor
-            DecodeArgs d; memset(&d, 0, sizeof d);
-            const Layer &P = c->layers[i - 1];
-            d.raw = (const float *)P.out.ptr; d.raw_stride = P.out.stride; d.n = n; d.g = L.H; d.na = L.na; d.classes = L.classes;
-            d.img_size = c->in_h; d.mode = c->decode; d.region = 1;
-            for (int k = 0; k < 2 * L.na; ++k) d.anchors[k] = L.anchors[k];
-            d.det = c->lean ? nullptr : c->d_det; d.box4 = c->lean ? c->d_box4 : nullptr; d.rows_total = c->rows; d.row_off = L.row_off;
-            d.reject_below = c->lean ? c->lean_thr : -INFINITY;
-            if (c->lean) { HIPCK(c, launch_decode_region_tree_lean(d, c->trees[L.tree].dev, c->hier_thresh, c->d_scores, c->d_labels, s)); c->lean_hier = c->hier_thresh; }
-            else HIPCK(c, launch_decode_region_tree(d, c->trees[L.tree].dev, s));
-            break;
-        }
-        if (c->lean && c->lean_thr > 0.f && c->lean_heads >= 1 && c->lean_heads <= 4) {
-            // lean detect path: every [yolo] head is decoded by ONE launch, issued at the last head (the head tensors keep their own buffers)
-            bool later_head = false;
-            for (size_t k = i + 1; k < c->layers.size(); ++k) later_head |= c->layers[k].type == L_YOLO;
-            if (later_head) break;
-            LeanArgs la; memset(&la, 0, sizeof la);
-            long begin = 0;
-            for (size_t k = 0; k < c->layers.size(); ++k) {
-                const Layer &Y = c->layers[k];
-                if (Y.type != L_YOLO) continue;
-                const Layer &P = c->layers[k - 1];
-                LeanHead &h = la.h[la.nheads++];
-                h.raw = (const float *)P.out.ptr; h.obj = P.d_obj; h.raw_stride = P.out.stride; h.g = Y.H; h.na = Y.na; h.row_off = Y.row_off; h.box_begin = begin;
-                const int stride = c->in_h / Y.H;
-                for (int q = 0; q < 2 * Y.na; ++q) h.anchors[q] = (float)(1.0 * (double)Y.anchors[q] / (double)stride);
-                begin += (long)n * Y.H * Y.W * Y.na;
-            }
-            la.total = begin; la.n = n; la.classes = L.classes; la.img_size = c->in_h; la.mode = c->decode; la.rows_total = c->rows;
-            la.box4 = c->d_box4; la.reject_below = c->lean_thr; la.list = (uint4 *)c->d_lean_list; la.list_count = c->d_lean_cnt; la.list_cap = (unsigned)((size_t)c->max_batch * c->rows);
-            // the list counter must be zero: the NMS launch of the previous detect call resets it; if none ran since the last decode
-            // (a failed call in between), a memset does
-            if (c->lean_cnt_dirty) HIPCK(c, hipMemsetAsync(c->d_lean_cnt, 0, 4, s));
-            c->lean_cnt_dirty = true;
-            HIPCK(c, launch_decode_lean(la, c->d_scores, c->d_labels, s));
-            break;
-        }
-        DecodeArgs d; memset(&d, 0, sizeof d);
-        const Layer &P = c->layers[i - 1];
-        d.raw = (const float *)P.out.ptr; d.raw_stride = P.out.stride; d.n = n; d.g = L.H; d.na = L.na; d.classes = L.classes;
-        d.img_size = c->in_h; d.mode = c->decode; d.region = L.type == L_REGION;
-        const int stride = c->in_h / L.H;
-        for (int k = 0; k < 2 * L.na; ++k)
-            d.anchors[k] = L.type == L_YOLO ? (float)(1.0 * (double)L.anchors[k] / (double)stride) : L.anchors[k];
-        d.det = c->lean ? nullptr : c->d_det; d.box4 = c->lean ? c->d_box4 : nullptr; d.rows_total = c->rows; d.row_off = L.row_off;
-        d.reject_below = c->lean ? c->lean_thr : -INFINITY;
-        HIPCK(c, launch_decode(d, c->d_scores, c->d_labels, s));
-        break; }
+    case L_YOLO: case L_REGION: return run_decode(c, i, n);
     }
     return YOLO_OK;
 }
@@ -289,7 +291,7 @@ int stage_in(yolo_ctx *c, const void *images, int n, int fmt, int loc, float sca
     }
     // uint8 images of a network whose first layers run as the fused stem: the stem converts the pixels itself (conv_stem.hip, U8 form)
     c->stem_u8 = nullptr;
-    if (fmt == YOLO_IMG_U8 && c->layers.size() > 1 && (c->layers[1].stem || c->layers[1].pstem) && (double)npix * 3 < 2147483648.0 && ((size_t)src & 3) == 0) {
+    if (fmt == YOLO_IMG_U8 && c->layers.size() > 1 && never_stored(c->layers[0], 0) && (double)npix * 3 < 2147483648.0 && ((size_t)src & 3) == 0) {
         c->stem_u8 = (const uint8_t *)src; c->stem_scale = scale; c->stem_u8_n = n;
         return YOLO_OK;
     }

@@ -44,7 +44,7 @@ EXPORTS = [
     "yolo_postprocess_rows", "yolo_op_postprocess_rows", "yolo_last_layer_output_batch", "yolo_head_raw", "yolo_calibrate", "yolo_calibrate_copy", "yolo_op_resize_cv2",
     "yolo_forward_images_u8", "yolo_detect_images_u8", "yolo_detect_images_graph", "yolo_fit_unit_value", "yolo_darknet_boxes_at",
     "yolo_num_classes", "yolo_classify", "yolo_classify_images_u8", "yolo_op_avgpool", "yolo_op_softmax",
-    "yolo_set_hier_thresh", "yolo_set_hierarchy_mode", "yolo_darknet_boxes_map", "yolo_tree_geometry", "yolo_tree_read", "yolo_plan_check",
+    "yolo_set_hier_thresh", "yolo_set_hierarchy_mode", "yolo_darknet_boxes_map", "yolo_tree_geometry", "yolo_tree_read", "yolo_plan_check", "yolo_plan_table",
     "yolo_op_tree_softmax", "yolo_op_tree_top",
 ]
 HIER_CONDITIONAL, HIER_ABSOLUTE, HIER_LEAVES = 0, 1, 2
@@ -142,6 +142,7 @@ def load_library():
     l.yolo_tree_geometry.argtypes = [P, P, P, P, P, P, P, P]
     l.yolo_tree_read.argtypes = [C.c_char_p, P, P, P, P, P, P, P, C.c_char_p, SZ]
     l.yolo_plan_check.argtypes = [C.c_char_p, I, C.c_char_p, SZ]
+    l.yolo_plan_table.argtypes = [C.c_char_p, I, I, I, C.c_char_p, SZ, C.c_char_p, SZ]
     l.yolo_op_tree_softmax.argtypes = [P, I, I, C.c_char_p, F, I, P, I]
     l.yolo_op_tree_top.argtypes = [P, I, C.c_char_p, F, P, I]
     l.yolo_shard_bounds.argtypes = [I, I, I, C.POINTER(I), C.POINTER(I)]
@@ -706,6 +707,15 @@ def plan_check(cfg_text, dtype=BF16):
     err = C.create_string_buffer(1024)
     rc = load_library().yolo_plan_check(cfg_text.encode(), dtype, err, 1024)
     return rc, err.value.decode()
+
+
+def plan_table(cfg_text, dtype=BF16, max_batch=1, keep_layers=False):
+    """The plan of a cfg without a device (yolo_plan_table) -> (status, text): one line per layer (own kernel, fused launch and its
+    launcher, folded shortcut, 1x1 tail, storage, buffer, first writer, last reader) and the buffer total; the planner's message when
+    it refuses."""
+    out, err = C.create_string_buffer(1 << 18), C.create_string_buffer(1024)
+    rc = load_library().yolo_plan_table(cfg_text.encode(), dtype, max_batch, int(keep_layers), out, len(out), err, 1024)
+    return rc, (err if rc else out).value.decode()
 
 
 def op_tree_softmax(x, tree_path, temperature=1.0, mode=HIER_CONDITIONAL, device=0):
