@@ -356,6 +356,19 @@ int yolo_classify_images_u8(yolo_ctx *ctx, const uint8_t *pixels, size_t bytes, 
                             int top_k, int32_t *classes_out, float *probs_out, int out_loc);
 /* darknet's [avgpool] on x [n,h,w,c] fp32 stored as `dtype` (YOLO_FP32 / BF16 / FP16 / FP16X2) first: out [n,c] fp32 */
 int yolo_op_avgpool(const float *x, int n, int h, int w, int c, int dtype, float *out, int device);
+/* Activations: the names DN/activations.c get_activation accepts.  YOLO_ACT_LINEAR .. YOLO_ACT_RELIE are the slope family, max(v, v * slope)
+ * in every conv epilogue; the others are applied by a kernel of their own behind the layer's launch ("Activations"). */
+enum yolo_activation { YOLO_ACT_LINEAR = 0, YOLO_ACT_LEAKY = 1, YOLO_ACT_RELU = 2, YOLO_ACT_RELIE = 3, YOLO_ACT_LOGISTIC = 4, YOLO_ACT_LOGGY = 5,
+                       YOLO_ACT_ELU = 6, YOLO_ACT_RAMP = 7, YOLO_ACT_TANH = 8, YOLO_ACT_PLSE = 9, YOLO_ACT_STAIR = 10, YOLO_ACT_HARDTAN = 11, YOLO_ACT_LHTAN = 12 };
+/* the code of an activation name as a cfg spells it, -1 for a name darknet does not know (the mapping the planner uses) */
+int yolo_activation_code(const char *name);
+/* out = act(x), x and out [n,h,w,c] fp32; x is stored as `dtype` (YOLO_FP32 / BF16 / FP16 / FP16X2) first and the result is rounded to it */
+int yolo_op_activate(const float *x, int n, int h, int w, int c, int act, int dtype, float *out, int device);
+/* darknet's [shortcut] (DN/blas.c:68-92 shortcut_cpu, then the activation): out [n,h2,w2,c2] = act(x + gather(from)), x [n,h2,w2,c2] the
+ * layer's input, from [n,h1,w1,c1]: the first min(c1, c2) channels, sampled with stride w1 / w2 (or written to every (w2 / w1)-th
+ * position), both integer divisions raised to 1.  Stored as `dtype` first, rounded to it once.  FP16X2: c1 and c2 multiples of 32. */
+int yolo_op_shortcut(const float *x, int n, int h2, int w2, int c2, const float *from, int h1, int w1, int c1, int act, int dtype,
+                     float *out, int device);
 /* darknet's [softmax] on x [n][len] fp32, `groups` equal runs per row: probs_out [n][len]; top_k > 0 (groups == 1, <= 32): also
  * classes_out / topk_probs_out [n][top_k] from the same launch (else NULL) */
 int yolo_op_softmax(const float *x, int n, int len, int groups, float temperature, int top_k, float *probs_out,

@@ -10,6 +10,10 @@ reference's layer tables and TF graph builders:
   darknet19 / darknet53
                   the classifiers those two backbones are (cfg layers 0-22 of yolov2 / 0-74 of yolov3, same tables) with the tail the
                   reference's parser reads: [avgpool] (DN/parser.c:493-507), [softmax] (:268-280), 1000 classes, 256 x 256
+  resnet18 / 34 / 50 / 101 / 152, vgg-16
+                  written from the architectures (He et al. 2015, Simonyan & Zisserman 2014) in the layer vocabulary of darknet's own model
+                  zoo: see resnet() and vgg16() below.  What they need of the reference is its general [shortcut] (DN/blas.c:68-92) and
+                  the activations of DN/activations.h
   yolov1          V1/YOLO_V1_Inference.py:124-210 (`_build_network`: 24 bias convs, 7x7/2 first, four SAME pools, CHW flatten,
                   FC 50176 -> 512 -> 4096 -> 1470) + :213-270 ([detection]: side 7, 2 boxes, 20 classes, sqrt sizes); the two
                   `yolo_input_*` keys of [net] state its input normalisation (x/255)*2-1 (:67-71) for the HIP planner (darknet ignores them)
@@ -46,8 +50,8 @@ class Cfg:
         kv.update(filters=filters, size=size, stride=stride, pad=1, activation=act)
         return self._sec("convolutional", **kv)
 
-    def shortcut(self, frm):
-        return self._sec("shortcut", **{"from": frm, "activation": "linear"})
+    def shortcut(self, frm, act="linear"):
+        return self._sec("shortcut", **{"from": frm, "activation": act})
 
     def route(self, *layers):
         return self._sec("route", layers=",".join(str(l) for l in layers))
@@ -255,6 +259,48 @@ def darknet19(size=256, classes=1000):
     return c.text()
 
 
+RESNET_BLOCKS = {18: (2, 2, 2, 2), 34: (3, 4, 6, 3), 50: (3, 4, 6, 3), 101: (3, 4, 23, 3), 152: (3, 8, 36, 3)}
+
+
+def resnet(depth, size=256, classes=1000):
+    """ResNet-18/34 (basic blocks: 3x3, 3x3, `from=-3`) and ResNet-50/101/152 (bottlenecks: 1x1, 3x3, 1x1 to four times the width,
+    `from=-4`) as darknet spells them: a 7x7/2 stem of 64 filters and a 2/2 max-pool, four stages of 64, 128, 256, 512 filters whose
+    first block (from the second stage on) has stride 2 on its 3x3 conv, every conv batch-normalised and leaky but the last of a block,
+    which is linear, and `[shortcut] activation=leaky` closing the block.  There are no projection convs: the first block of a stage
+    adds a tensor with fewer channels -- and, from the second stage on, twice the size --, which darknet's shortcut defines as the
+    first min(c1, c2) channels sampled with stride w1 / w2.  Tail: a 1x1 conv to the classes, [avgpool], [softmax]."""
+    c = Cfg(size)
+    c.conv(64, 7, stride=2); c.maxpool()
+    bottleneck = depth >= 50
+    for stage, blocks in enumerate(RESNET_BLOCKS[depth]):
+        f = 64 << stage
+        for b in range(blocks):
+            st = 2 if stage > 0 and b == 0 else 1
+            if bottleneck:
+                c.conv(f, 1); c.conv(f, 3, stride=st); c.conv(4 * f, 1, act="linear"); c.shortcut(-4, act="leaky")
+            else:
+                c.conv(f, 3, stride=st); c.conv(f, 3, act="linear"); c.shortcut(-3, act="leaky")
+    c.conv(classes, 1, bn=False, act="linear")
+    c.avgpool()
+    c.softmax()
+    return c.text()
+
+
+def vgg16(size=224, classes=1000):
+    """VGG-16 (configuration D): thirteen 3x3 convs with bias and relu in five groups of 64 .. 512 filters, a 2/2 max-pool behind each
+    group, then [connected] 4096, 4096 (relu, with dropout) and the classes (linear), [softmax]."""
+    c = Cfg(size)
+    for f, n in ((64, 2), (128, 2), (256, 3), (512, 3), (512, 3)):
+        for _ in range(n):
+            c.conv(f, 3, bn=False, act="relu")
+        c.maxpool()
+    c.connected(4096, act="relu"); c.dropout()
+    c.connected(4096, act="relu"); c.dropout()
+    c.connected(classes, act="linear")
+    c.softmax()
+    return c.text()
+
+
 def synthetic_tree(nodes=9418, roots=10, seed=0, max_group=120):
     """A seeded tree in darknet's file format (DN/tree.c:83-139: `name parent` lines, the children of a node one contiguous run, a
     parent below its own index): the reference ships no 9k.tree.  Breadth-first: every run of siblings is appended whole, its size
@@ -309,7 +355,10 @@ def main():
         "yolov3-tiny.cfg": yolov3_tiny(416),
         "yolov2.cfg": yolov2(416), "yolov2-tiny-voc.cfg": yolov2_tiny_voc(416),
         "darknet19.cfg": darknet19(256), "darknet53.cfg": darknet53(256),
+        # cfg/zoo/: classifiers of darknet's model zoo that are no YOLO backbone (cfg/ itself is the set tests/golden/plan_tables.json pins)
+        "zoo/resnet18.cfg": resnet(18), "zoo/resnet50.cfg": resnet(50), "zoo/vgg-16.cfg": vgg16(),
     }
+    os.makedirs(os.path.join(OUT, "zoo"), exist_ok=True)
     for name, text in files.items():
         with open(os.path.join(OUT, name), "w") as f:
             f.write("# generated by tools/make_cfgs.py -- do not edit\n" + text)

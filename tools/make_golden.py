@@ -13,6 +13,9 @@ Runs only in the build container (it reads /root/reference and oracle/_ref); the
                      an input image, EVERY layer output, and the boxes after get_network_boxes /
                      do_nms_sort -- produced by the reference's own C code compiled CPU-only
                      (oracle/Makefile -> oracle/_ref/libdarknet_ref.so)
+  mini_resnet.npz / mini_resnet_30.npz
+                    a ResNet in miniature (general [shortcut] forms, activations outside the slope family) at 32 x 32 and 30 x 30:
+                    three images each, every layer's output from the compiled reference
   mini_cls53.npz / mini_cls19.npz
                      two small classifier topologies ([avgpool], [softmax], [cost]; darknet-53's and darknet-19's tail order), every
                      layer output and the probability vector, from the same compiled reference
@@ -515,6 +518,57 @@ def gen_mini_cls():
         net.close()
 
 
+def mini_resnet_cfg(size=32, mul=1):
+    """A ResNet in miniature, one block per form of the general [shortcut] (DN/blas.c:68-92) and a sample of the activations outside
+    the conv epilogues' slope family: a relu stem and a 2/2 max-pool; a bottleneck whose `from` tensor has fewer channels (16 -> 32); a
+    matched one closed by relu; one whose 3x3 conv has stride 2, so that `from` is both larger and narrower (32 -> 64); one with
+    logistic and tanh convs under an elu shortcut; a linear 1x1 conv to 24 classes, [avgpool], [softmax].  size=30 makes the pooled map
+    15 x 15 and the strided block's output 8 x 8: stride = 15 / 8 = 1, the top-left 8 x 8 of `from` is added unstrided.  `mul` scales
+    the channel counts (2: multiples of 32, what split-fp16 pairs need)."""
+    m = mul
+    sc = lambda act: "[shortcut]\nfrom=-4\nactivation=%s\n\n" % act
+    return ("[net]\nbatch=1\nwidth=%d\nheight=%d\nchannels=3\n\n" % (size, size) + _conv(16 * m, 3, act="relu") + "[maxpool]\nsize=2\nstride=2\n\n" +
+            _conv(8 * m, 1) + _conv(8 * m, 3) + _conv(32 * m, 1, act="linear") + sc("leaky") +
+            _conv(8 * m, 1) + _conv(8 * m, 3) + _conv(32 * m, 1, act="linear") + sc("relu") +
+            _conv(16 * m, 1) + _conv(16 * m, 3, 2) + _conv(64 * m, 1, act="linear") + sc("leaky") +
+            _conv(16 * m, 1, act="logistic") + _conv(16 * m, 3, act="tanh") + _conv(64 * m, 1, act="linear") + sc("elu") +
+            _conv(24, 1, bn=False, act="linear") + "[avgpool]\n\n[softmax]\ngroups=1\n")
+
+
+def gen_mini_resnet():
+    """mini_resnet_cfg at 32 x 32 and at 30 x 30 through the compiled reference (shortcut_layer.c, blas.c shortcut_cpu, activations.h):
+    cfg text, weights, three images and every layer's output for each of them.  The last conv is scaled as gen_mini_cls does."""
+    from oracle import darknet_ref as D
+    from yolo_tensorflow_amd import darknet_io as IO
+    for name, size, seed in (("mini_resnet", 32, 31), ("mini_resnet_30", 30, 33)):      # (one archive each: three images x every layer is 0.9 MB of floats that do not compress)
+        cfg = mini_resnet_cfg(size)
+        secs = IO.parse_cfg(cfg)
+        flat = IO.synth_weights(secs, seed=seed)
+        last = IO.conv_specs(secs)[-1]
+        tail = last["filters"] * (1 + last["cin"] * last["size"] ** 2)
+        imgs = np.random.default_rng(seed + 1).integers(0, 256, (3, size, size, 3), dtype=np.uint8)
+        x = imgs.astype(np.float32) / np.float32(255.0)
+        logit_layer = len(secs) - 4
+        net = D.RefNet(cfg, flat, 0, 2)
+        net.predict(x[0])
+        factor = np.float32(round(5.0 / float(np.abs(net.layer_output_nhwc(logit_layer)).max()), 2))
+        net.close()
+        flat[-tail:] *= factor
+        net = D.RefNet(cfg, flat, 0, 2)
+        outs = [[] for _ in range(net.n)]
+        for b in range(3):
+            net.predict(x[b])
+            for i in range(net.n):
+                outs[i].append(np.asarray(net.layer_output_nhwc(i), dtype=np.float32).reshape(-1) if secs[i + 1]["type"] in ("avgpool", "softmax") else np.asarray(net.layer_output_nhwc(i), dtype=np.float32)[0])
+        data = {"cfg": np.array(cfg), "weights": flat, "images_u8": imgs, "logit_layer": np.int32(logit_layer)}
+        for i in range(net.n):
+            data["layer_%02d" % i] = np.stack(outs[i])
+        data["max_abs_logit"] = np.float32(np.abs(data["layer_%02d" % logit_layer]).max())
+        print(name, "layers", net.n, "max|logit|", float(data["max_abs_logit"]), "p max", float(data["layer_%02d" % (net.n - 1)].max()))
+        net.close()
+        np.savez_compressed(os.path.join(OUT, name + ".npz"), **data)
+
+
 def gen_bn_real():
     """D2T/log.txt is the reference's stdout of two detect runs (yolov2 then yolov3) with the printf block of DN/parser.c:1176-1228
     enabled: per batch-normalised conv five lines of numbers (beta, gamma, rolling mean, rolling variance -- l.n values each -- and the
@@ -588,6 +642,8 @@ if __name__ == "__main__":
         gen_bn_real(); sys.exit(0)
     if sys.argv[1:] == ["known_answers"]:
         gen_known_answers(); sys.exit(0)
+    if sys.argv[1:] == ["mini_resnet"]:
+        gen_mini_resnet(); sys.exit(0)
     if sys.argv[1:] == ["darknet_py_symbols"]:
         gen_darknet_py_symbols(); sys.exit(0)
     stub_modules()
@@ -598,6 +654,7 @@ if __name__ == "__main__":
     gen_mini_v1()
     gen_mini_local()
     gen_mini_cls()
+    gen_mini_resnet()
     gen_bn_real()
     gen_known_answers()
     gen_darknet_py_symbols()

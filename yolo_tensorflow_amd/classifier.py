@@ -1,4 +1,4 @@
-"""Classifier networks (darknet-19, darknet-53, any cfg that ends in [softmax]): "Darknet weights in, top classes out".
+"""Classifier networks (darknet-19, darknet-53, ResNet-18 .. 152, VGG-16, any cfg that ends in [softmax]): "Darknet weights in, top classes out".
 
 Counterpart of what the reference's ctypes binding does with such a network (`classify`, D2T/darknet.py:117-123: predict, pair every
 probability with its name, sort by -prob), with the pooling, the softmax and the selection of the top classes on the device: uint8
@@ -9,7 +9,8 @@ from . import hip, darknet_io as IO
 
 class Classifier:
     def __init__(self, cfg_or_name, weights_file=None, dtype=hip.BF16, max_batch=1, names=None, device=0, fit=hip.FIT_STRETCH, seed=0, hierarchy=None):
-        """cfg_or_name: a shipped topology ('darknet19', 'darknet53'), a cfg file path, or cfg text.  weights_file: a darknet
+        """cfg_or_name: a shipped topology ('darknet19', 'darknet53', 'resnet18', 'resnet50', 'vgg-16'), a cfg file path, or cfg text
+        (a ResNet's [shortcut] layers with fewer or larger `from` tensors and any of darknet's thirteen activations are served).  weights_file: a darknet
         `.weights` file; None loads darknet_io's seeded synthetic parameters (`seed`).  names: a list of class names or the path of a
         file with one name per line; without it the class index stands in for the name.  hierarchy (a [softmax] with tree=): None
         returns the conditional probabilities network_predict gives, "absolute" the products along the path to the root

@@ -58,7 +58,7 @@ __global__ __launch_bounds__(64 * CB_NW) void conv_resblock_c128(const BlockArgs
     const int l15 = lane & 15, lq = lane >> 4;
     const int wc = wave & 3, wp = wave >> 2;             // channel group (32 output channels of the 3x3), pixel half
     char *const lx_ = smem, *const lmid_ = lx_ + CB_X_BYTES, *const lw1_ = lmid_ + CB_MID_BYTES, *const lb1_ = lw1_ + CB_W1_BYTES, *const lb2_ = lb1_ + CB_B1_BYTES, *const lout_ = lb2_ + CB_B2_BYTES;
-    const float slope1 = a.act1 == ACT_LEAKY ? 0.1f : 1.f, slope2 = a.act2 == ACT_LEAKY ? 0.1f : 1.f;
+    const float slope1 = act_slope(a.act1), slope2 = act_slope(a.act2);
     const int bx = (a.W + CB_B - 1) / CB_B, by = (a.H + CB_B - 1) / CB_B, per_img = bx * by, nblocks = a.N * per_img;      // (ragged blocks on the bottom / right edge: their pixels past the image are computed on zeros and never stored)
     const int nt = (nblocks - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;
 

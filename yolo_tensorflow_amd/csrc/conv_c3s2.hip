@@ -73,7 +73,7 @@ __global__ __launch_bounds__(64 * CS_NW) void conv_c3s2_c32_c64_c128(const C3S2A
         f32x4 bv[4];
 #pragma unroll
         for (int ct = 0; ct < 4; ++ct) bv[ct] = *(const f32x4 *)(a.b3 + ct * 16 + lq * 4);
-        const float slope = a.act3 == ACT_LEAKY ? 0.1f : 1.f;
+        const float slope = act_slope(a.act3);
         __amdgpu_buffer_rsrc_t rin = buf_rsrc(a.in);
         __amdgpu_buffer_rsrc_t rres = buf_rsrc(a.res);
 
@@ -198,7 +198,7 @@ __global__ __launch_bounds__(64 * CS_NW) void conv_c3s2_c32_c64_c128(const C3S2A
         f32x4 bv[2];
 #pragma unroll
         for (int ct = 0; ct < 2; ++ct) bv[ct] = *(const f32x4 *)(a.b5 + grp * 32 + ct * 16 + lq * 4);
-        const float slope = a.act5 == ACT_LEAKY ? 0.1f : 1.f;
+        const float slope = act_slope(a.act5);
         const int ctid = tid - 256;
         // LDS byte offset of this lane's window pixel for tap (0, 0), per sub-tile (two output rows of 8 pixels); the tap adds (kh * 17 + kw) * 144
         int pb[2];

@@ -5,6 +5,7 @@
 // on gfx950), so the result differs from the fp32 reference only by summation order.
 // A K-step is 32 floats (128 B per tile row); lane l feeds A[row l&15][k = l>>4], B[k = l>>4][col l&15].
 #include "kernels.h"
+#include "device_common.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -111,9 +112,11 @@ __global__ __launch_bounds__(64 * WP * WC) void conv_igemm_f32(const ConvArgs a)
             const int m = pt * BP + (wpi * TP + j) * 16 + l15;
             if (m >= M) continue;
             float v[4] = {acc[i][j][0] + bv.x, acc[i][j][1] + bv.y, acc[i][j][2] + bv.z, acc[i][j][3] + bv.w};
-            if (a.act == ACT_LEAKY)
+            if (a.act != ACT_LINEAR) {          // max(v, v * slope) == v > 0 ? v : slope * v for 0 <= slope < 1, signed zeros and NaN included
+                const float slope = act_slope(a.act);
 #pragma unroll
-                for (int q = 0; q < 4; ++q) v[q] = v[q] > 0.f ? v[q] : 0.1f * v[q];
+                for (int q = 0; q < 4; ++q) v[q] = fmaxf(v[q], slope * v[q]);
+            }
             if (res) {
                 const float4 rv = *(const float4 *)(res + (size_t)m * a.res_stride + ch);
                 v[0] += rv.x; v[1] += rv.y; v[2] += rv.z; v[3] += rv.w;

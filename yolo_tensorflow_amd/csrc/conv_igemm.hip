@@ -125,9 +125,11 @@ __global__ __launch_bounds__(256) void conv_c8_3x3_direct(const ConvArgs a)
 #pragma unroll
                 for (int i = 0; i < TC; ++i) {
                     float v[4] = {acc[i][0] + bv[i].x, acc[i][1] + bv[i].y, acc[i][2] + bv[i].z, acc[i][3] + bv[i].w};
-                    if (a.act == ACT_LEAKY)
+                    if (a.act != ACT_LINEAR) {
+                        const float slope = act_slope(a.act);
 #pragma unroll
-                        for (int q = 0; q < 4; ++q) v[q] = fmaxf(v[q], 0.1f * v[q]);     // == v > 0 ? v : 0.1 v
+                        for (int q = 0; q < 4; ++q) v[q] = fmaxf(v[q], slope * v[q]);     // leaky: == v > 0 ? v : 0.1 v
+                    }
                     uint2 pk;
                     pk.x = pack16x2<H16>(v[0], v[1]);
                     pk.y = pack16x2<H16>(v[2], v[3]);

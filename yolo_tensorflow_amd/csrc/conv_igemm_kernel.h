@@ -786,7 +786,7 @@ __global__ __launch_bounds__(64 * (WP * WC + NL)) void conv_igemm(const ConvArgs
         f32x4 bvs[TC];
 #pragma unroll
         for (int i = 0; i < TC; ++i) bvs[i] = is_consumer ? *(const f32x4 *)(a.bias + ct * BC + (wci * TC + i) * 16 + lq * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
-        const float slope = a.act == ACT_LEAKY ? 0.1f : 1.0f;
+        const float slope = act_slope(a.act);
         auto split8 = [](const float *v, u32x4_t &H, u32x4_t &L) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) { uint32_t h, l; pair_split2(v[2 * q], v[2 * q + 1], h, l); H[q] = h; L[q] = l; }
@@ -905,7 +905,7 @@ __global__ __launch_bounds__(64 * (WP * WC + NL)) void conv_igemm(const ConvArgs
         // (Tried and dropped, round 3: converting the accumulators to packed bf16 in registers BEFORE this barrier, so that only the LDS
         // writes remain behind it.  The stamped build moved 1 300 cycles in front of the barrier and took 100 off the phase behind it: that
         // phase is the LDS store path -- 176 ds_write_b64 per wave pair at ~12 cycles each -- not the arithmetic; the step got 1.7 % slower.)
-        const float slope = a.act == ACT_LEAKY ? 0.1f : 1.0f;
+        const float slope = act_slope(a.act);
         {
             if (is_consumer)
 #pragma unroll
@@ -1019,9 +1019,10 @@ __global__ __launch_bounds__(64 * (WP * WC + NL)) void conv_igemm(const ConvArgs
                             acc2 = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fw2q[kk], x, acc2, 0, 0, 0, 0, 0, 0);
                         }
                         float v[4] = {acc2[0] * s2v.x + b2v.x, acc2[1] * s2v.y + b2v.y, acc2[2] * s2v.z + b2v.z, acc2[3] * s2v.w + b2v.w};
-                        if (a.act2 == ACT_LEAKY) {
+                        if (a.act2 != ACT_LINEAR) {
+                            const float slope2 = act_slope(a.act2);
 #pragma unroll
-                            for (int q = 0; q < 4; ++q) v[q] = fmaxf(v[q], 0.1f * v[q]);
+                            for (int q = 0; q < 4; ++q) v[q] = fmaxf(v[q], slope2 * v[q]);
                         }
 #pragma unroll
                         for (int q = 0; q < 4; ++q) v[q] = bf16_bits_to_f32(f32_to_bf16_rn(v[q])) * a.out2_inv_scale;
@@ -1085,7 +1086,7 @@ __global__ __launch_bounds__(64 * (WP * WC + NL)) void conv_igemm(const ConvArgs
                 block_barrier();                                   // tile (with the shortcut added) complete in LDS
                 if (DIAG) te4 = stamp();
                 if (is_consumer) {
-                    const float slope2 = a.act2 == ACT_LEAKY ? 0.1f : 1.0f;
+                    const float slope2 = act_slope(a.act2);
                     f32x4 b2v[T2W];
 #pragma unroll
                     for (int t = 0; t < T2W; ++t) b2v[t] = *(const f32x4 *)(a.b2 + (t2g * T2W + t) * 16 + lq * 4);
@@ -1202,9 +1203,10 @@ __global__ __launch_bounds__(64 * (WP * WC + NL)) void conv_igemm(const ConvArgs
                 float v[4];
                 if (EB == 1) { v[0] = acc[i][j][0] * sv.x + bv.x; v[1] = acc[i][j][1] * sv.y + bv.y; v[2] = acc[i][j][2] * sv.z + bv.z; v[3] = acc[i][j][3] * sv.w + bv.w; }
                 else { v[0] = acc[i][j][0] + bv.x; v[1] = acc[i][j][1] + bv.y; v[2] = acc[i][j][2] + bv.z; v[3] = acc[i][j][3] + bv.w; }
-                if (a.act == ACT_LEAKY) {
+                if (a.act != ACT_LINEAR) {
+                    const float slope = act_slope(a.act);
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) v[q] = fmaxf(v[q], 0.1f * v[q]);     // == v > 0 ? v : 0.1 v
+                    for (int q = 0; q < 4; ++q) v[q] = fmaxf(v[q], slope * v[q]);     // leaky: == v > 0 ? v : 0.1 v
                 }
                 float *o = (float *)a.out + (size_t)m * a.out_stride + ch;
                 if (oq >= 0) a.obj_out[(size_t)m * a.obj_na + oan] = oq == 0 ? v[0] : oq == 1 ? v[1] : oq == 2 ? v[2] : v[3];

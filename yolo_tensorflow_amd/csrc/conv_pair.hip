@@ -82,7 +82,7 @@ __global__ __launch_bounds__(256) void conv_c8_3x3_direct_pair(const ConvArgs a)
     float4 bv[TC];
 #pragma unroll
     for (int i = 0; i < TC; ++i) bv[i] = *(const float4 *)(a.bias + i * 16 + lq * 4);
-    const float slope = a.act == ACT_LEAKY ? 0.1f : 1.0f;
+    const float slope = act_slope(a.act);
     const int HoWo = a.Ho * a.Wo;
     constexpr int U = 2;                        // 16-pixel tiles in flight per wave
     const long groups = (tiles + U - 1) / U;

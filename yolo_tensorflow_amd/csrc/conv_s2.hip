@@ -49,7 +49,7 @@ __global__ __launch_bounds__(64 * S2_NW) void conv_s2_c64_c128(const HaloArgs a)
     f32x4 bv[2];
 #pragma unroll
     for (int ct = 0; ct < 2; ++ct) bv[ct] = *(const f32x4 *)(a.b + grp * 32 + ct * 16 + lq * 4);
-    const float slope = a.act == ACT_LEAKY ? 0.1f : 1.f;
+    const float slope = act_slope(a.act);
 
     const int Ho = (a.H - 1) / 2 + 1, Wo = (a.W - 1) / 2 + 1;
     const int tiles_x = (Wo + S2_T - 1) / S2_T, tiles_y = (Ho + S2_T - 1) / S2_T;

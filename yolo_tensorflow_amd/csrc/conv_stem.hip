@@ -74,7 +74,7 @@ __global__ __launch_bounds__(64 * ST_NW) void conv_stem_c32_c64(const StemArgs a
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l15 = lane & 15, lq = lane >> 4;
     const int sub = wave & 3;                                    // index among the four waves of this wave's role
-    const float slope0 = a.act0 == ACT_LEAKY ? 0.1f : 1.f, slope1 = a.act1 == ACT_LEAKY ? 0.1f : 1.f, slope2 = a.act2 == ACT_LEAKY ? 0.1f : 1.f;
+    const float slope0 = act_slope(a.act0), slope1 = act_slope(a.act1), slope2 = act_slope(a.act2);
 
     const int tiles_x = (a.Wo + ST_TW - 1) / ST_TW, tiles_y = (a.Ho + ST_TH - 1) / ST_TH;
     const int per_img = tiles_x * tiles_y, ntiles = a.N * per_img;
@@ -442,7 +442,7 @@ __global__ __launch_bounds__(64 * ST_NW) void conv_halo_c32_c64(const HaloArgs a
     f32x4 bv[4];
 #pragma unroll
     for (int ct = 0; ct < 4; ++ct) bv[ct] = *(const f32x4 *)(a.b + ct * 16 + lq * 4);
-    const float slope = a.act == ACT_LEAKY ? 0.1f : 1.f;
+    const float slope = act_slope(a.act);
 
     const int tiles_x = (a.W + ST_TW - 1) / ST_TW, tiles_y = (a.H + ST_TH - 1) / ST_TH;
     const int per_img = tiles_x * tiles_y, ntiles = a.N * per_img;

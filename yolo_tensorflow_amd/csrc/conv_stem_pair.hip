@@ -52,7 +52,7 @@ __global__ __launch_bounds__(512) void conv_stem_pair_pc(const StemPairArgs a)
         n = tile / (ty_n * tx_n); const int r = tile - n * ty_n * tx_n; const int ty = r / tx_n;
         oy0 = ty * PC_TH; ox0 = (r - ty * tx_n) * PC_TW;
     };
-    const float slope0 = a.act0 == ACT_LEAKY ? 0.1f : 1.0f, slope1 = a.act1 == ACT_LEAKY ? 0.1f : 1.0f;
+    const float slope0 = act_slope(a.act0), slope1 = act_slope(a.act1);
     const int first = blockIdx.x;
     const int count = first < tiles ? (tiles - first + G - 1) / G : 0;       // this workgroup's tiles: first, first + G, ...
 

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "kernels.h"
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
@@ -46,6 +47,11 @@ template <bool H16> __device__ __forceinline__ f32x4 mma16(const bf16x8 a, const
 }
 // max(a, b) for finite operands without the sNaN-quieting v_max the compiler puts in front of fmaxf (one instruction, not two)
 __device__ __forceinline__ float vmax_f32(float a, float b) { float r; asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+// The slope s of a slope-family activation (kernels.h): every conv epilogue evaluates max(v, v * s) -- linear 1, leaky 0.1, relie 0.01, relu 0.
+// relu: the reference's x * (x > 0) (DN/activations.h:34) gives -0 for a negative x and so does max(v, 0 * v) = max(v, -0); +-0 and NaN pass
+// through in both; +inf: 0 * inf is NaN and v_max returns its other operand, +inf, as the reference does.  -inf alone differs: the reference's
+// -inf * 0 is NaN, max(-inf, NaN) is -inf.  Any other code (the planner never hands one to a conv) is linear.
+__host__ __device__ __forceinline__ float act_slope(int act) { return act == ACT_LEAKY ? 0.1f : act == ACT_RELU ? 0.f : act == ACT_RELIE ? 0.01f : 1.f; }
 // acc + bias, activation (slope 0.1: leaky as max(v, 0.1 v); slope 1: linear), rounded to the storage type: four channels as two packed words
 template <bool H16> __device__ __forceinline__ uint2 leaky_pack4(const f32x4 acc, const f32x4 bias, const float slope)
 {

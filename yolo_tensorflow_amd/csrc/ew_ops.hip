@@ -4,6 +4,7 @@
 // One thread moves an 8-channel granule (16 B of bf16, 32 B of fp32) so global accesses are 16-B vectors
 // and consecutive lanes touch consecutive addresses along the channel axis.
 #include "kernels.h"
+#include "device_common.h"
 #include <math.h>
 
 template <typename T> struct Elt;
@@ -585,6 +586,160 @@ hipError_t launch_add_split(const void *a, int a_stride, const void *b, int b_st
     return hipGetLastError();
 }
 
+// ---- activations and the general [shortcut] (DN/activations.h, DN/blas.c:68-92 shortcut_cpu) ----
+// One value through activation `act`.  The slope family is the conv epilogues' max(v, v * slope) (act_slope: a float product where the
+// reference's .1 * x is a double one).  Every other formula is evaluated as DN/activations.h writes it, operation for operation and in the
+// reference's types -- its constants and its exp are double, so the arithmetic here is double and the result is rounded to float once, as the
+// C compiler rounds the reference's return value.  (A float expf would leave loggy and tanh a few units of 2^-24 off near 0, where the
+// result is the small difference of numbers close to 1.)  None of this is on a network's hot path.
+__device__ __forceinline__ float act_apply(float x, int act)
+{
+    switch (act) {
+    case ACT_LINEAR: return x;
+    case ACT_LEAKY: case ACT_RELU: case ACT_RELIE: return fmaxf(x, x * act_slope(act));
+    case ACT_LOGISTIC: return (float)(1. / (1. + exp((double)-x)));
+    case ACT_LOGGY: return (float)(2. / (1. + exp((double)-x)) - 1);
+    case ACT_ELU: return (float)((double)((float)(x >= 0) * x) + (double)(x < 0) * (exp((double)x) - 1));
+    case ACT_RAMP: return (float)((double)(x * (float)(x > 0)) + .1 * (double)x);
+    case ACT_TANH: { const double e = exp((double)(2 * x)); return (float)((e - 1) / (e + 1)); }
+    case ACT_PLSE:
+        if (x < -4) return (float)(.01 * (double)(x + 4));
+        if (x > 4) return (float)(.01 * (double)(x - 4) + 1);
+        return (float)(.125 * (double)x + .5);
+    case ACT_STAIR: {
+        const int n = (int)floor((double)x);
+        if (n % 2 == 0) return (float)floor((double)x / 2.);
+        return (float)((double)(x - (float)n) + floor((double)x / 2.));
+    }
+    case ACT_HARDTAN: return x < -1 ? -1.f : x > 1 ? 1.f : x;
+    case ACT_LHTAN:
+        if (x < 0) return (float)(.001 * (double)x);
+        if (x > 1) return (float)(.001 * (double)(x - 1) + 1);
+        return x;
+    }
+    return x;
+}
+
+// k_activate: x = act(x) in place on the C real channels of a view (channels C .. of the last granule keep their zeros); one 16-byte granule
+// per lane: 8 channels of a 16-bit tensor, 4 of an fp32 one (an fp32 head's pixel stride is a multiple of 4 only).  G = channels per granule.
+template <typename T, int G>
+__global__ void k_activate(T *x, int xs, size_t npix, int C, int cg, int act)
+{
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= npix * cg) return;
+    const size_t p = idx / cg; const int g = (int)(idx - p * cg);
+    T *q = x + p * xs + g * G;
+    if constexpr (G == 4) {
+        float4 v = *(const float4 *)q;
+        float r[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) if (g * 4 + i < C) r[i] = act_apply(r[i], act);
+        *(float4 *)q = float4{r[0], r[1], r[2], r[3]};
+    } else {
+        float r[8];
+        Elt<T>::load8(q, r);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) if (g * 8 + i < C) r[i] = act_apply(r[i], act);
+        Elt<T>::store8(q, r);
+    }
+}
+// ... on an interleaved split-fp16 pair tensor: join, activate, split again
+__global__ void k_activate_pair(f16_t *x, int xs, size_t npix, int C, int Cp, int act)
+{
+    const int c8 = Cp / 8;
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= npix * c8) return;
+    const size_t p = idx / c8; const int g = (int)(idx - p * c8);
+    f16_t *q = x + p * xs + pair_hi_off(g, Cp, PAIR_ILV);
+    float r[8]; join8(q, 32, r);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) if (g * 8 + i < C) r[i] = act_apply(r[i], act);
+    put_split8(q, Cp, PAIR_ILV, r);
+}
+hipError_t launch_activate(const TView &x, bool pair, int act, hipStream_t s)
+{
+    if (act < 0 || act >= ACT_COUNT || x.dt == DT_FP8) return hipErrorInvalidValue;
+    if (act == ACT_LINEAR) return hipSuccess;
+    const size_t npix = (size_t)x.n * x.h * x.w;
+    if (pair) {
+        const int Cp = (x.c + 31) / 32 * 32;
+        if (x.dt != DT_F16 || x.stride < 2 * Cp) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(k_activate_pair, grid_for(npix * (Cp / 8)), dim3(256), 0, s, (f16_t *)x.ptr, x.stride, npix, x.c, Cp, act);
+    } else if (x.dt == DT_F32) {
+        const int cg = (x.c + 3) / 4;
+        if (x.stride < cg * 4 || x.stride % 4) return hipErrorInvalidValue;
+        hipLaunchKernelGGL((k_activate<float, 4>), grid_for(npix * cg), dim3(256), 0, s, (float *)x.ptr, x.stride, npix, x.c, cg, act);
+    } else {
+        const int cg = (x.c + 7) / 8;
+        if (x.stride < cg * 8 || x.stride % 8) return hipErrorInvalidValue;
+        if (x.dt == DT_F16) hipLaunchKernelGGL((k_activate<f16_t, 8>), grid_for(npix * cg), dim3(256), 0, s, (f16_t *)x.ptr, x.stride, npix, x.c, cg, act);
+        else hipLaunchKernelGGL((k_activate<bf16_t, 8>), grid_for(npix * cg), dim3(256), 0, s, (bf16_t *)x.ptr, x.stride, npix, x.c, cg, act);
+    }
+    return hipGetLastError();
+}
+
+// The geometry of shortcut_cpu, restated literally: (w1, h1, c1) the `from` tensor, (w2, h2, c2) the layer's input = output.
+__host__ __device__ inline ShortcutGeom shortcut_geom_of(int w1, int h1, int c1, int w2, int h2, int c2)
+{
+    ShortcutGeom g;
+    g.stride = w1 / w2; g.sample = w2 / w1;
+    g.ok = g.stride == h1 / h2 && g.sample == h2 / h1;
+    if (g.stride < 1) g.stride = 1;
+    if (g.sample < 1) g.sample = 1;
+    g.minw = w1 < w2 ? w1 : w2; g.minh = h1 < h2 ? h1 : h2; g.minc = c1 < c2 ? c1 : c2;
+    return g;
+}
+ShortcutGeom shortcut_geom(int w1, int h1, int c1, int w2, int h2, int c2) { return shortcut_geom_of(w1, h1, c1, w2, h2, c2); }
+
+// k_shortcut: out = act(a + gather(b)) in one launch, rounded to the storage type once.  a, out: [n, h2, w2, c2]; b (`from`): [n, h1, w1, c1].
+// Output position (y, x), channel k receives b[(y / sample) * stride, (x / sample) * stride, k] when k < minc, y and x are multiples of
+// `sample` and y / sample < minh, x / sample < minw -- shortcut_cpu's loop read from the output's side; everywhere else the value passes
+// through without an add (a + 0 would turn a -0 into +0).  One 8-channel granule per lane; the lanes at and beyond minc of the granule that
+// straddles it are masked.  PAIR: interleaved split-fp16 pairs (c1, c2 multiples of 32, so no granule straddles minc).
+template <typename T, bool PAIR>
+__global__ void k_shortcut(const T *a, int as, const T *b, int bs, T *o, int os, int n, int h2, int w2, int c2, int h1, int w1, ShortcutGeom sg, int act)
+{
+    const int c8 = PAIR ? ((c2 + 31) / 32 * 32) / 8 : (c2 + 7) / 8;
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (size_t)n * h2 * w2 * c8) return;
+    const int g = (int)(idx % c8); size_t p = idx / c8;
+    const int x = (int)(p % w2); const size_t row = p / w2;
+    const int y = (int)(row % h2), img = (int)(row / h2);
+    const int off = PAIR ? pair_hi_off(g, c8 * 8, PAIR_ILV) : g * 8;
+    float v[8];
+    if constexpr (PAIR) join8((const f16_t *)a + p * as + off, 32, v); else Elt<T>::load8(a + p * as + off, v);
+    const int j = y / sg.sample, i = x / sg.sample;
+    if (g * 8 < sg.minc && j * sg.sample == y && i * sg.sample == x && j < sg.minh && i < sg.minw) {
+        const size_t q = ((size_t)img * h1 + (size_t)j * sg.stride) * w1 + (size_t)i * sg.stride;
+        float u[8];
+        if constexpr (PAIR) join8((const f16_t *)b + q * bs + off, 32, u); else Elt<T>::load8(b + q * bs + off, u);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) if (g * 8 + k < sg.minc) v[k] = v[k] + u[k];
+    }
+    if (act != ACT_LINEAR) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) if (g * 8 + k < c2) v[k] = act_apply(v[k], act);
+    }
+    if constexpr (PAIR) put_split8((f16_t *)o + p * os + off, c8 * 8, PAIR_ILV, v); else Elt<T>::store8(o + p * os + off, v);
+}
+hipError_t launch_shortcut(const TView &a, const TView &b, const TView &out, bool pair, int act, hipStream_t s)
+{
+    const ShortcutGeom sg = shortcut_geom_of(b.w, b.h, b.c, a.w, a.h, a.c);
+    if (!sg.ok || act < 0 || act >= ACT_COUNT || a.dt != b.dt || a.dt != out.dt || a.dt == DT_FP8 || a.n != b.n || out.h != a.h || out.w != a.w || out.c != a.c) return hipErrorInvalidValue;
+    if (pair) {
+        const int cp2 = (a.c + 31) / 32 * 32;
+        if (a.dt != DT_F16 || a.c % 32 || b.c % 32 || a.stride < 2 * cp2 || out.stride < 2 * cp2 || b.stride < 2 * b.c) return hipErrorInvalidValue;
+        hipLaunchKernelGGL((k_shortcut<f16_t, true>), grid_for((size_t)a.n * a.h * a.w * (cp2 / 8)), dim3(256), 0, s, (const f16_t *)a.ptr, a.stride, (const f16_t *)b.ptr, b.stride,
+                           (f16_t *)out.ptr, out.stride, a.n, a.h, a.w, a.c, b.h, b.w, sg, act);
+        return hipGetLastError();
+    }
+    const int c8 = (a.c + 7) / 8;
+    if (a.stride < c8 * 8 || out.stride < c8 * 8 || b.stride < (b.c + 7) / 8 * 8) return hipErrorInvalidValue;      // whole granules are read and written
+    WITH_DT(a.dt, hipLaunchKernelGGL((k_shortcut<T, false>), grid_for((size_t)a.n * a.h * a.w * c8), dim3(256), 0, s, (const T *)a.ptr, a.stride, (const T *)b.ptr, b.stride,
+                                     (T *)out.ptr, out.stride, a.n, a.h, a.w, a.c, b.h, b.w, sg, act));
+    return hipGetLastError();
+}
+
 // ---- darknet letterbox_image (DN/image.c:960-981) fused with the layout change: a planar float image of any size -> px_letterbox,
 //      written as the 8-channel network input ----
 template <typename T>
@@ -721,7 +876,7 @@ __global__ __launch_bounds__(256) void k_local(const T *in, int in_stride, const
         for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
         if (lane == 0) {
             float v = acc + bias[(size_t)loc * F + f];
-            if (act == ACT_LEAKY) v = v > 0.f ? v : 0.1f * v;
+            if (act != ACT_LINEAR) v = fmaxf(v, v * act_slope(act));          // == v > 0 ? v : slope * v
             Elt<T>::store1(out + ((size_t)b * Ho * Wo + loc) * out_stride + f, v);
         }
     }

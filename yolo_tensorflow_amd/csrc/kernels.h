@@ -49,7 +49,13 @@ struct TView {
     int dt = DT_BF16;        // element type (DT_*)
 };
 
-enum { ACT_LINEAR = 0, ACT_LEAKY = 1 };
+// Activations: the set DN/activations.c get_activation accepts (the codes are YOLO_ACT_* of include/yolo_hip.h).  The SLOPE FAMILY --
+// linear 1, leaky 0.1, relu 0, relie 0.01 -- is max(v, v * act_slope(act)) in every conv epilogue (device_common.h); the others never enter a
+// conv kernel: the planner gives such a layer a linear epilogue and a post-activation (Layer::post_act), applied by k_activate (ew_ops.hip)
+enum { ACT_LINEAR = 0, ACT_LEAKY = 1, ACT_RELU = 2, ACT_RELIE = 3, ACT_LOGISTIC = 4, ACT_LOGGY = 5, ACT_ELU = 6, ACT_RAMP = 7, ACT_TANH = 8,
+       ACT_PLSE = 9, ACT_STAIR = 10, ACT_HARDTAN = 11, ACT_LHTAN = 12, ACT_COUNT = 13 };
+inline bool act_is_slope(int act) { return act == ACT_LINEAR || act == ACT_LEAKY || act == ACT_RELU || act == ACT_RELIE; }
+int act_from_name(const char *name);          // the code of a darknet activation name, -1 for a name get_activation does not know (yolo_ops.cpp; the planner and yolo_activation_code share it)
 
 struct ConvArgs {
     const void *in; int in_stride;       // elements per input pixel; Cin_pad channels are readable
@@ -248,6 +254,15 @@ hipError_t launch_reorg(const TView &in, const TView &out, int stride, int darkn
 // out = (a * sa + b * sb) * so   (the scales are the fp8 tensor scales; 1 for bf16 / fp32)
 hipError_t launch_add(const TView &a, const TView &b, const TView &out, hipStream_t s, float sa = 1.f, float sb = 1.f, float so = 1.f);
 hipError_t launch_copy(const TView &in, const TView &out, hipStream_t s);
+// x = act(x) in place on the view's real channels (k_activate; any of ACT_*, fp32 / bf16 / fp16 or, `pair`, interleaved split-fp16 pairs): the
+// post-activation of a layer whose activation is outside the slope family
+hipError_t launch_activate(const TView &x, bool pair, int act, hipStream_t s);
+// darknet's general [shortcut] (DN/blas.c:68-92 shortcut_cpu + activate_array) in one launch (k_shortcut): out = act(a + gather(b)), a / out
+// [n, h2, w2, c2] the layer's input and output, b [n, h1, w1, c1] the `from` tensor.  shortcut_geom restates shortcut_cpu's integers: stride
+// = w1 / w2 and sample = w2 / w1 (integer divisions, each raised to 1), the minima, and ok = the reference's two assertions
+struct ShortcutGeom { int stride, sample, minw, minh, minc; bool ok; };
+ShortcutGeom shortcut_geom(int w1, int h1, int c1, int w2, int h2, int c2);
+hipError_t launch_shortcut(const TView &a, const TView &b, const TView &out, bool pair, int act, hipStream_t s);
 // [local] (locally connected, DN/local_layer.c): w [locations][filters][k][k][C] in the tensors' type, bias [locations][filters] fp32
 hipError_t launch_local(const TView &in, const TView &out, const void *w, const float *bias, int k, int stride, int pad, int act, hipStream_t s);
 hipError_t launch_to_f32(const TView &in, float *out, hipStream_t s, float scale = 1.f);   // dense NHWC fp32 copy (* scale)

@@ -30,7 +30,9 @@ struct Layer {
     int H = 0, W = 0, C = 0;             // logical output geometry
     std::vector<int> in;                 // producer layer indices (-1 = network input)
     // conv
-    int filters = 0, size = 0, stride = 1, pad = 0, bn = 0, act = ACT_LINEAR;
+    int filters = 0, size = 0, stride = 1, pad = 0, bn = 0, act = ACT_LINEAR;      // act: the activation of the layer's own kernel -- a conv / [connected] / [local]: slope family only; a [shortcut]: any
+    int post_act = ACT_LINEAR;           // conv / [connected] / [local] with an activation outside the slope family: applied in place on the output by k_activate after the layer's launch
+    bool general = false;                // [shortcut]: a `from` tensor of another shape, or an activation -- runs as k_shortcut, never folded
     int cin = 0, cin_pad = 0, kpad = 0, cout_pad = 0;
     void *d_w = nullptr; float *d_b = nullptr; float *d_sc = nullptr;   // filters, bias, fp8 per-channel dequant scale
     void *d_wf = nullptr;                   // bf16 1x1 conv that can ride in its producer's epilogue: its filters in MFMA-fragment order (tail_fragments)

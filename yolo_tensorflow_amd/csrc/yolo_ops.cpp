@@ -33,7 +33,74 @@ static int op_tree(OpScope &S, const char *what, const char *tree_path, int len,
 
 }  // namespace yolo_impl
 
+// darknet's activation names (DN/activations.c get_activation) in the order of ACT_* / YOLO_ACT_*
+int act_from_name(const char *name)
+{
+    static const char *const names[ACT_COUNT] = {"linear", "leaky", "relu", "relie", "logistic", "loggy", "elu", "ramp", "tanh", "plse", "stair", "hardtan", "lhtan"};
+    for (int k = 0; name && k < ACT_COUNT; ++k) if (!strcmp(name, names[k])) return k;
+    return -1;
+}
+
 extern "C" {
+
+int yolo_activation_code(const char *name) { return act_from_name(name); }
+
+// the storage forms of yolo_op_activate / yolo_op_shortcut: a dense fp32 host tensor -> the device view of `dtype` (fp16x2: interleaved pairs of
+// whole 32-channel groups) and back
+namespace {
+struct OpTensor { void *d = nullptr; TView v; int cp = 0; bool pair = false; };
+bool op_tensor(OpScope &S, const float *host, int n, int h, int w, int c, int dtype, OpTensor &t)
+{
+    const size_t npix = (size_t)n * h * w;
+    t.pair = dtype == YOLO_FP16X2;
+    const int dt = dtype == YOLO_FP32 ? DT_F32 : dtype == YOLO_BF16 ? DT_BF16 : DT_F16;
+    t.cp = roundup(c, t.pair ? 32 : 8);
+    const int stride = t.pair ? 2 * t.cp : t.cp;
+    t.d = S.alloc(npix * stride * dt_size(dt));
+    t.v = make_view(t.d, n, h, w, c, stride, dt);
+    if (!host) return !S.rc;
+    float *d32 = (float *)S.alloc(npix * t.cp * 4);
+    if (S.rc) return false;
+    if (!S.ok(hipMemcpy2DAsync(d32, (size_t)t.cp * 4, host, (size_t)c * 4, (size_t)c * 4, npix, hipMemcpyHostToDevice, S.s))) return false;
+    if (t.pair) return S.ok(launch_split_from_f32(d32, t.cp, t.d, stride, t.cp, npix, S.s));
+    TView dst = t.v; dst.c = t.cp;
+    return S.ok(launch_from_f32(d32, dst, S.s));
+}
+int op_tensor_out(OpScope &S, const OpTensor &t, float *host)
+{
+    const size_t npix = (size_t)t.v.n * t.v.h * t.v.w;
+    float *d32 = (float *)S.alloc(npix * t.cp * 4);
+    if (S.rc) return S.rc;
+    TView all = t.v; all.c = t.cp;
+    if (!S.ok(t.pair ? launch_split_to_f32(t.d, t.v.stride, t.cp, d32, t.cp, npix, S.s) : launch_to_f32(all, d32, S.s))) return S.rc;
+    if (hipMemcpy2DAsync(host, (size_t)t.v.c * 4, d32, (size_t)t.cp * 4, (size_t)t.v.c * 4, npix, hipMemcpyDeviceToHost, S.s) != hipSuccess || hipStreamSynchronize(S.s) != hipSuccess) S.rc = YOLO_ERR_HIP;
+    return S.rc;
+}
+bool op_dtype_ok(int dtype) { return dtype == YOLO_FP32 || dtype == YOLO_BF16 || dtype == YOLO_FP16 || dtype == YOLO_FP16X2; }
+}  // namespace
+
+int yolo_op_activate(const float *x, int n, int h, int w, int c, int act, int dtype, float *out, int device)
+{
+    if (!x || !out || n < 1 || h < 1 || w < 1 || c < 1 || act < 0 || act >= ACT_COUNT) { g_op_err = "activate: bad arguments"; return YOLO_ERR_INVALID; }
+    if (!op_dtype_ok(dtype)) { g_op_err = "activate: dtype (fp32, bf16, fp16 or fp16x2)"; return YOLO_ERR_UNSUPPORTED; }
+    OpScope S(device); if (S.rc) { g_op_err = "activate: no HIP device"; return S.rc; }
+    OpTensor t;
+    if (!op_tensor(S, x, n, h, w, c, dtype, t) || !S.ok(launch_activate(t.v, t.pair, act, S.s)) || op_tensor_out(S, t, out)) { g_op_err = "activate: " + (S.err.empty() ? std::string("allocation or copy failed") : S.err); return S.rc ? S.rc : YOLO_ERR_HIP; }
+    return YOLO_OK;
+}
+
+int yolo_op_shortcut(const float *x, int n, int h2, int w2, int c2, const float *from, int h1, int w1, int c1, int act, int dtype, float *out, int device)
+{
+    if (!x || !from || !out || n < 1 || h1 < 1 || w1 < 1 || c1 < 1 || h2 < 1 || w2 < 1 || c2 < 1 || act < 0 || act >= ACT_COUNT) { g_op_err = "shortcut: bad arguments"; return YOLO_ERR_INVALID; }
+    if (!op_dtype_ok(dtype)) { g_op_err = "shortcut: dtype (fp32, bf16, fp16 or fp16x2)"; return YOLO_ERR_UNSUPPORTED; }
+    if (!shortcut_geom(w1, h1, c1, w2, h2, c2).ok) { g_op_err = "shortcut: darknet requires w1 / w2 == h1 / h2 and w2 / w1 == h2 / h1"; return YOLO_ERR_UNSUPPORTED; }
+    if (dtype == YOLO_FP16X2 && (c1 % 32 || c2 % 32)) { g_op_err = "shortcut (fp16x2): channel counts must be multiples of 32"; return YOLO_ERR_UNSUPPORTED; }
+    OpScope S(device); if (S.rc) { g_op_err = "shortcut: no HIP device"; return S.rc; }
+    OpTensor a, b, o;
+    if (!op_tensor(S, x, n, h2, w2, c2, dtype, a) || !op_tensor(S, from, n, h1, w1, c1, dtype, b) || !op_tensor(S, nullptr, n, h2, w2, c2, dtype, o) ||
+        !S.ok(launch_shortcut(a.v, b.v, o.v, a.pair, act, S.s)) || op_tensor_out(S, o, out)) { g_op_err = "shortcut: " + (S.err.empty() ? std::string("allocation or copy failed") : S.err); return S.rc ? S.rc : YOLO_ERR_HIP; }
+    return YOLO_OK;
+}
 
 // ---- single operators -----------------------------------------------------------------------
 // yolo_op_conv2d for dtype YOLO_FP16X2: x (and the residual) enter as interleaved split-fp16 pairs (32 hi | 32 lo per 32-channel group), the

@@ -61,6 +61,22 @@ static int plan_tree(yolo_ctx *c, int i, const char *section, const std::string 
     return YOLO_OK;
 }
 
+// activation= of layer i (DN/parser.c: `logistic` where a [convolutional] / [connected] / [local] section names none, `linear` for a
+// [shortcut]), the ONE place a name becomes a code.  A [shortcut] keeps any of them in L.act (k_shortcut applies it).  The other layers keep
+// a slope-family activation in L.act, their kernel's own epilogue; any other one leaves the epilogue linear and becomes L.post_act, applied
+// in place on the layer's output by k_activate.
+static int plan_activation(yolo_ctx *c, int i, const Section &s, const char *dflt, bool shortcut)
+{
+    Layer &L = c->layers[i];
+    const std::string name = opt_s(s, "activation", dflt);
+    const int code = act_from_name(name.c_str());
+    if (code < 0) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: activation '%s' unsupported", i, name.c_str());
+    if (shortcut || act_is_slope(code)) { L.act = code; return YOLO_OK; }
+    if (c->dtype == YOLO_FP8) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: activation '%s' is not served in the fp8 configuration", i, name.c_str());
+    L.act = ACT_LINEAR; L.post_act = code;
+    return YOLO_OK;
+}
+
 TView view_of(const yolo_ctx *c, int idx) { return idx < 0 ? c->input : c->layers[idx].out; }
 
 int build_plan(yolo_ctx *c, const std::vector<Section> &secs)
@@ -77,6 +93,8 @@ int build_plan(yolo_ctx *c, const std::vector<Section> &secs)
     // split-fp16 networks: per-tensor storage form (mixed plans): pairs unless a [convolutional] section says yolo_pair=0
     // ([net] yolo_pair_input for the image); layers that move data inherit, both operands of a shortcut / all inputs of a route must agree
     c->in_pair = c->split() && opt_i(net, "yolo_pair_input", 1) != 0;
+    // (a 7x7 / stride 2 first conv reads the 2x2 space-to-depth of the image, which is kept as plain fp16: such a network's input is never pairs)
+    if (c->in_pair && NL >= 1 && secs[1].type == "convolutional" && opt_i(secs[1], "size", 1) == 7 && opt_i(secs[1], "stride", 1) == 2) c->in_pair = false;
     for (int i = 0; i < NL; ++i) {
         const Section &s = secs[i + 1]; Layer &L = c->layers[i];
         L.in = {i - 1};
@@ -85,9 +103,7 @@ int build_plan(yolo_ctx *c, const std::vector<Section> &secs)
             L.type = L_CONV; L.filters = opt_i(s, "filters", 1); L.size = opt_i(s, "size", 1); L.stride = opt_i(s, "stride", 1);
             L.pad = opt_i(s, "pad", 0) ? L.size / 2 : opt_i(s, "padding", 0);
             L.bn = opt_i(s, "batch_normalize", 0);
-            std::string act = opt_s(s, "activation", "logistic");
-            if (act == "leaky") L.act = ACT_LEAKY; else if (act == "linear") L.act = ACT_LINEAR;
-            else return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: activation '%s' unsupported", i, act.c_str());
+            if (int r = plan_activation(c, i, s, "logistic", false)) return r;
             if (L.size == 7 && L.stride == 2 && L.pad == 3 && i == 0 && C == 3 && H % 2 == 0 && W % 2 == 0 && c->dtype != YOLO_FP8) L.s2d7 = true;
             else if (L.size != 1 && L.size != 3) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: conv size %d unsupported on the device path", i, L.size);
             // fp8 mode: the first conv still reads the bf16 image (3 real channels padded to 8) with bf16 filters; a conv reads its
@@ -118,9 +134,7 @@ int build_plan(yolo_ctx *c, const std::vector<Section> &secs)
             if (opt_i(s, "batch_normalize", 0)) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: batch-normalised [connected]", i);
             L.type = L_CONV; L.fc = true; L.fc_h = H; L.fc_w = W; L.fc_c = C;
             L.filters = opt_i(s, "output", 1); L.size = 1; L.stride = 1; L.pad = 0; L.bn = 0;
-            std::string act = opt_s(s, "activation", "logistic");
-            if (act == "leaky") L.act = ACT_LEAKY; else if (act == "linear") L.act = ACT_LINEAR;
-            else return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: activation '%s' unsupported", i, act.c_str());
+            if (int r = plan_activation(c, i, s, "logistic", false)) return r;
             L.in_dt = c->act_dt(); L.store_dt = c->act_dt();
             if ((long)H * W * C > (1L << 24)) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [connected] input too large", i);
             L.cin = H * W * C; L.cin_pad = roundup(L.cin, 8); L.kpad = roundup(L.cin_pad, 64); L.cout_pad = roundup(L.filters, 256);
@@ -134,9 +148,7 @@ int build_plan(yolo_ctx *c, const std::vector<Section> &secs)
             if (L.pad != 0 && L.pad != 1) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [local] pad must be 0 or 1", i);
             // pad=1 pads by ONE pixel whatever the size (DN/local_layer.c:103 im2col) while the output size assumes size / 2 (:10-24): they only agree for 3x3
             if (L.pad == 1 && L.size != 3) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [local] with pad=1 needs size=3 (darknet's own output size and im2col disagree otherwise)", i);
-            std::string act = opt_s(s, "activation", "logistic");
-            if (act == "leaky") L.act = ACT_LEAKY; else if (act == "linear") L.act = ACT_LINEAR;
-            else return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: activation '%s' unsupported", i, act.c_str());
+            if (int r = plan_activation(c, i, s, "logistic", false)) return r;
             if (C % 8) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [local] needs a producer with a multiple of 8 channels", i);
             L.cin = C; L.cin_pad = C; L.in_dt = c->act_dt(); L.store_dt = c->act_dt();
             const int ho = ((L.pad ? H - 1 : H - L.size)) / L.stride + 1, wo = ((L.pad ? W - 1 : W - L.size)) / L.stride + 1;
@@ -153,15 +165,22 @@ int build_plan(yolo_ctx *c, const std::vector<Section> &secs)
             if (C != L.side * L.side * (L.classes + L.na * 5)) return fail(c, YOLO_ERR_INVALID, "layer %d: [detection] expects %d inputs, got %d", i, L.side * L.side * (L.classes + L.na * 5), C);
             if (c->attrs && c->attrs != 5 + L.classes) return fail(c, YOLO_ERR_UNSUPPORTED, "heads with different class counts");
             c->attrs = 5 + L.classes; L.row_off = c->rows; c->rows += L.side * L.side * L.na;
+            if (c->layers[i - 1].post_act != ACT_LINEAR) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: the layer in front of a [detection] head needs a linear, leaky, relu or relie activation", i - 1);
             c->layers[i - 1].head = true;
             H = L.side; W = L.side;
         } else if (s.type == "shortcut") {
             L.type = L_SHORTCUT; int f = opt_i(s, "from", -1); f = f < 0 ? i + f : f;
             if (f < 0 || f >= i) return fail(c, YOLO_ERR_INVALID, "layer %d: bad shortcut from", i);
             L.in = {i - 1, f};
-            if (opt_s(s, "activation", "linear") != "linear") return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: shortcut activation", i);
-            int h2, w2, c2; dims(f, h2, w2, c2);
-            if (h2 != H || w2 != W || c2 != C) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: shortcut shape mismatch", i);
+            if (int r = plan_activation(c, i, s, "linear", true)) return r;
+            // the general form (DN/blas.c:68-92 shortcut_cpu): a `from` tensor of another channel count or size, or an activation.  (w1, h1,
+            // c1) = the `from` tensor, (w2, h2, c2) = this layer's input and output; the reference asserts what is checked here
+            int h1, w1, c1; dims(f, h1, w1, c1);
+            L.general = h1 != H || w1 != W || c1 != C || L.act != ACT_LINEAR;
+            if (!shortcut_geom(w1, h1, c1, W, H, C).ok)
+                return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: shortcut of a %d x %d tensor (layer %d) into a %d x %d one: darknet requires w1 / w2 == h1 / h2 and w2 / w1 == h2 / h1", i, w1, h1, f, W, H);
+            if (L.general && c->dtype == YOLO_FP8)
+                return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: a [shortcut] with an activation or a `from` tensor of another shape is not served in the fp8 configuration", i);
         } else if (s.type == "route") {
             L.type = L_ROUTE; L.in.clear();
             std::vector<float> ls = opt_list(s, "layers");
@@ -211,6 +230,7 @@ int build_plan(yolo_ctx *c, const std::vector<Section> &secs)
                 c->tree_head = i;
             } else if (c->tree_head >= 0) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: a [region] head with a tree must be the network's only head", i);
             c->attrs = 5 + L.classes; L.row_off = c->rows; c->rows += H * W * L.na;
+            if (c->layers[i - 1].post_act != ACT_LINEAR) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: the conv in front of a [yolo] / [region] head needs a linear, leaky, relu or relie activation", i - 1);
             c->layers[i - 1].head = true;
         } else if (s.type == "avgpool") {
             // always global (DN/avgpool_layer.c:40-55): H x W x C -> 1 x 1 x C, stored in the form of its input
@@ -249,6 +269,8 @@ int build_plan(yolo_ctx *c, const std::vector<Section> &secs)
             if (c->split() && !L.in.empty() && L.type != L_YOLO && L.type != L_REGION && L.type != L_DETECT) {
                 L.pair = c->pair_of(L.in[0]);
                 for (int j : L.in) if (c->pair_of(j) != L.pair) return fail(c, YOLO_ERR_INVALID, "layer %d: operands stored in different forms (yolo_pair): a %s needs pairs or plain fp16 throughout", i, L.type == L_ROUTE ? "route" : L.type == L_SHORTCUT ? "shortcut" : "layer");
+                // pairs are interleaved per 32-channel group: the general shortcut's channel boundary (minc) must fall between groups
+                if (L.type == L_SHORTCUT && L.general && L.pair) { int h1, w1, c1; dims(L.in[1], h1, w1, c1); if (L.C % 32 || c1 % 32) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: a [shortcut] with an activation or a `from` tensor of another shape, on split-fp16 pairs, needs channel counts that are multiples of 32 (%d and %d)", i, L.C, c1); }
             }
         }
     }
@@ -281,9 +303,9 @@ int build_plan(yolo_ctx *c, const std::vector<Section> &secs)
     for (int i = 0; i < NL; ++i) for (int j : c->layers[i].in) if (j >= 0) uses[j]++;
     for (int i = 0; i < NL; ++i) {
         Layer &L = c->layers[i];
-        if (L.type == L_SHORTCUT && !c->keep_layers) {
+        if (L.type == L_SHORTCUT && !L.general && !c->keep_layers) {          // the general form (k_shortcut) is never folded
             Layer &P = c->layers[i - 1];
-            if (P.type == L_CONV && uses[i - 1] == 1 && !P.head && L.in[1] != i - 1 && (L.in[1] < 0 || c->layers[L.in[1]].store_dt == P.store_dt)) {
+            if (P.type == L_CONV && P.post_act == ACT_LINEAR && uses[i - 1] == 1 && !P.head && L.in[1] != i - 1 && (L.in[1] < 0 || c->layers[L.in[1]].store_dt == P.store_dt)) {
                 if (c->pair_of(L.in[1]) != P.pair) return fail(c, YOLO_ERR_INVALID, "layer %d: the conv in front of this shortcut and its other operand are stored in different forms (yolo_pair)", i);
                 P.residual_from = L.in[1]; L.noop = true;
             }
@@ -295,12 +317,15 @@ int build_plan(yolo_ctx *c, const std::vector<Section> &secs)
     //  kernels: what counts is the type of the tensors a kernel touches, not the context's)
     const bool ctx16 = c->half_like() || c->dtype == YOLO_FP8 || c->split();        // (a split-fp16 network: where the tensors a fused kernel touches are PLAIN fp16 -- mixed plans)
     auto is16 = [](int dt) { return dt == DT_BF16 || dt == DT_F16; };
+    // a layer with a post-activation runs its own plain launch, then k_activate: it is no member of a fused launch, neither end of a 1x1 tail,
+    // and keeps the tiled kernel.  Every marking pass below asks this of each layer it marks
+    auto plain = [&](const Layer &X) { return X.post_act == ACT_LINEAR; };
     // fused residual block (conv_block.hip): a 1x1 conv 128 -> 64 read only by the 3x3 conv 64 -> 128 that follows, whose folded shortcut
     // source is the 1x1's own input, on a grid that is (nearly) whole 13 x 13 blocks: darknet-53's 104 x 104 stage at 416 x 416
     if (ctx16 && !c->keep_layers && !getenv("YOLO_NO_RESBLOCK"))
         for (int i = 1; i + 1 < NL; ++i) {
             Layer &A = c->layers[i], &B = c->layers[i + 1];
-            if (A.type == L_CONV && B.type == L_CONV && !A.fc && !B.fc && !A.head && !B.head && uses[i] == 1 && B.in[0] == i && A.in[0] >= 0 &&
+            if (A.type == L_CONV && B.type == L_CONV && plain(A) && plain(B) && !A.fc && !B.fc && !A.head && !B.head && uses[i] == 1 && B.in[0] == i && A.in[0] >= 0 &&
                 A.size == 1 && A.stride == 1 && A.pad == 0 && A.cin == 128 && A.filters == 64 && B.cin == 64 && B.filters == 128 && A.residual_from < -1 &&
                 B.size == 3 && B.stride == 1 && B.pad == 1 && B.residual_from == A.in[0] &&
                 ((long)((B.H + 12) / 13) * ((B.W + 12) / 13) * 169 * 100 <= (long)B.H * B.W * 115) && A.in_dt == B.in_dt && (A.in_dt == DT_BF16 || A.in_dt == DT_F16) && A.store_dt == A.in_dt && B.store_dt == A.in_dt &&
@@ -308,13 +333,13 @@ int build_plan(yolo_ctx *c, const std::vector<Section> &secs)
         }
     if (ctx16 && !c->keep_layers && NL >= 2 && (double)c->max_batch * c->in_h * c->in_w * 8 * 2 < 2147483648.0) {
         const Layer &A = c->layers[0], &B = c->layers[1];
-        if (A.type == L_CONV && B.type == L_CONV && uses[0] == 1 && B.in[0] == 0 && A.size == 3 && A.stride == 1 && A.pad == 1 && A.cin == 3 &&
+        if (A.type == L_CONV && B.type == L_CONV && plain(A) && plain(B) && uses[0] == 1 && B.in[0] == 0 && A.size == 3 && A.stride == 1 && A.pad == 1 && A.cin == 3 &&
             A.filters == 32 && B.size == 3 && B.stride == 2 && B.pad == 1 && B.filters == 64 && !A.head && !B.head && B.residual_from < -1 &&
             is16(A.in_dt) && A.store_dt == A.in_dt && B.in_dt == A.in_dt && B.store_dt == A.in_dt && !c->in_pair && !A.pair && !B.pair) {        // (layer 0 reads the staged image, which is kept in its operand type)
             for (int k = 0; k < 2; ++k) { c->layers[k].fused = F_STEM; c->layers[k].launcher = 1; }
             if (NL >= 3) {
                 const Layer &T = c->layers[2];
-                if (T.type == L_CONV && !T.fc && T.in[0] == 1 && T.size == 1 && T.stride == 1 && T.pad == 0 && T.filters == 32 && !T.head && T.residual_from < -1 &&
+                if (T.type == L_CONV && plain(T) && !T.fc && T.in[0] == 1 && T.size == 1 && T.stride == 1 && T.pad == 0 && T.filters == 32 && !T.head && T.residual_from < -1 &&
                     T.in_dt == A.in_dt && T.store_dt == A.in_dt && !T.pair)
                     { c->layers[2].fused = F_STEM; c->layers[2].launcher = 1; }
             }
@@ -323,7 +348,7 @@ int build_plan(yolo_ctx *c, const std::vector<Section> &secs)
     // split-fp16: conv0 + conv1 on pairs in one launch (conv_stem_pair.hip) -- both tensors pairs, the image in its three blocks
     if (c->split() && !c->keep_layers && NL >= 2 && c->in_pair && !getenv("YOLO_NO_PAIR_STEM")) {
         const Layer &A = c->layers[0], &B = c->layers[1];
-        if (A.type == L_CONV && B.type == L_CONV && uses[0] == 1 && B.in[0] == 0 && A.size == 3 && A.stride == 1 && A.pad == 1 && A.cin == 3 && A.bn == B.bn &&
+        if (A.type == L_CONV && B.type == L_CONV && plain(A) && plain(B) && uses[0] == 1 && B.in[0] == 0 && A.size == 3 && A.stride == 1 && A.pad == 1 && A.cin == 3 && A.bn == B.bn &&
             (A.filters == 32) && B.size == 3 && B.stride == 2 && B.pad == 1 && B.filters == 64 && !A.head && !B.head && A.residual_from < -1 && B.residual_from < -1 &&
             A.pair && B.pair && c->in_h % 2 == 0 && c->in_w % 2 == 0 && A.kpad >= 216 && B.kpad == 576) {
             for (int k = 0; k < 2; ++k) { c->layers[k].fused = F_PSTEM; c->layers[k].launcher = 1; }
@@ -332,7 +357,7 @@ int build_plan(yolo_ctx *c, const std::vector<Section> &secs)
     if (ctx16 && !getenv("YOLO_NO_HALO"))
         for (int i = 1; i < NL; ++i) {
             Layer &L = c->layers[i];
-            if (L.type != L_CONV || L.head || L.fused != F_NONE || L.size != 3 || L.pad != 1 || !is16(L.in_dt) || L.store_dt != L.in_dt || L.pair || c->pair_of(L.in[0])) continue;
+            if (L.type != L_CONV || !plain(L) || L.head || L.fused != F_NONE || L.size != 3 || L.pad != 1 || !is16(L.in_dt) || L.store_dt != L.in_dt || L.pair || c->pair_of(L.in[0])) continue;
             if (L.stride == 1 && L.cin == 32 && L.filters == 64 && (L.residual_from < 0 || c->layers[L.residual_from].store_dt == L.in_dt)) L.kernel = K_HALO;
             // darknet-53's 64 -> 128 downsampling conv: window-staged, filters in registers (conv_s2.hip)
             if (L.stride == 2 && L.cin == 64 && L.filters == 128 && L.residual_from < -1 && !getenv("YOLO_NO_S2")) L.kernel = K_S2;
@@ -350,18 +375,18 @@ int build_plan(yolo_ctx *c, const std::vector<Section> &secs)
     if (ctx16 && !c->keep_layers) {
         for (int i = 0; i + 1 < NL; ++i) {
             Layer &P = c->layers[i];
-            if (P.type != L_CONV || P.fc || P.head || fixed_kernel(P) || (P.filters != 128 && P.filters != 256)) continue;      // (fixed kernels host no tail: run_conv would skip the 1x1)
+            if (P.type != L_CONV || !plain(P) || P.fc || P.head || fixed_kernel(P) || (P.filters != 128 && P.filters != 256)) continue;      // (fixed kernels host no tail: run_conv would skip the 1x1)
             if (c->split() && (P.pair || c->pair_of(P.in[0]))) continue;       // (split-fp16 networks: the tail rides on plain fp16 layers only)
             int o = i;
             if (P.residual_from >= -1) o = i + 1;            // its shortcut was folded into it: consumers read layer i+1
             const int j = o + 1;
             if (j >= NL) continue;
             Layer &T = c->layers[j];
-            if (T.type == L_CONV && !T.fc && T.in[0] == o && T.size == 1 && T.stride == 1 && T.pad == 0 && T.filters * 2 == P.filters && !T.head &&
+            if (T.type == L_CONV && plain(T) && !T.fc && T.in[0] == o && T.size == 1 && T.stride == 1 && T.pad == 0 && T.filters * 2 == P.filters && !T.head &&
                 T.residual_from < -1 && issues_launch(c, j) && T.in_dt == P.in_dt && !T.pair) { P.tail_layer = j; T.fused_into = i; }      // (same operand type: the tail runs on the producer's MFMA)
             // round 5: a detection head (1x1, <= 256 filters, fp32 out, linear) as the tail of the 256-channel 3x3 in front of it when nobody else
             // reads that conv (darknet-53's 52 x 52 head): the head tensor is formed from the tile in LDS, bit-identical to the stand-alone launch
-            else if (T.type == L_CONV && !T.fc && T.head && T.in[0] == o && uses[o] == 1 && T.size == 1 && T.stride == 1 && T.pad == 0 && P.filters == 256 && T.filters <= 256 &&
+            else if (T.type == L_CONV && plain(T) && !T.fc && T.head && T.in[0] == o && uses[o] == 1 && T.size == 1 && T.stride == 1 && T.pad == 0 && P.filters == 256 && T.filters <= 256 &&
                      P.size == 3 && P.residual_from < -1 && T.act == ACT_LINEAR && T.in_dt == P.in_dt && (T.in_dt == DT_BF16 || T.in_dt == DT_F16) && j + 1 < NL && c->layers[j + 1].type == L_YOLO) { P.tail_layer = j; T.fused_into = i; }
         }
     }
@@ -485,7 +510,7 @@ int allocate(yolo_ctx *c)
     HIPCK(c, hipMalloc(&c->d_zeros, 4096)); HIPCK(c, hipMemsetAsync(c->d_zeros, 0, 4096, c->stream));
     for (size_t i = 0; i < c->layers.size(); ++i) {
         const Layer &L = c->layers[i];
-        if (L.s2d7 && c->split()) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %zu: a 7x7 / stride 2 first conv is not served in the split-fp16 configuration", i);
+        if (L.s2d7 && c->in_pair) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %zu: a 7x7 / stride 2 first conv does not read an image stored as split-fp16 pairs", i);
         if (L.s2d7) {
             c->s2d = c->input; c->s2d.h = c->in_h / 2; c->s2d.w = c->in_w / 2; c->s2d.c = 32; c->s2d.stride = 32;
             HIPCK(c, hipMalloc(&c->s2d.ptr, (size_t)c->max_batch * c->s2d.h * c->s2d.w * 32 * dt_size(c->s2d.dt)));

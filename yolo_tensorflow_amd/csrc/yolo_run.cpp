@@ -209,9 +209,14 @@ int run_layer(yolo_ctx *c, int i, int n)
     hipStream_t s = c->stream;
     auto nview = [&](TView v) { v.n = n; return v; };
     switch (L.type) {
-    case L_CONV: return run_conv(c, i, n);
+    case L_CONV:
+        if (int r = run_conv(c, i, n)) return r;
+        if (L.post_act != ACT_LINEAR) HIPCK(c, launch_activate(nview(L.out), L.pair, L.post_act, s));
+        break;
     case L_SHORTCUT:
-        if (!L.noop && L.pair) {
+        if (L.general) {          // DN/blas.c:68-92 + the layer's activation, one launch
+            HIPCK(c, launch_shortcut(nview(view_of(c, L.in[0])), nview(view_of(c, L.in[1])), nview(L.out), L.pair, L.act, s));
+        } else if (!L.noop && L.pair) {
             HIPCK(c, launch_add_split(view_of(c, L.in[0]).ptr, view_of(c, L.in[0]).stride, view_of(c, L.in[1]).ptr, view_of(c, L.in[1]).stride, L.out.ptr, L.out.stride, roundup(L.C, 32), (size_t)n * L.H * L.W, s));
         } else if (!L.noop) {
             float sa = 1.f, sb = 1.f, so = 1.f;
@@ -234,7 +239,10 @@ int run_layer(yolo_ctx *c, int i, int n)
             HIPCK(c, launch_copy(src, dst, s));
         }
         break;
-    case L_LOCAL: HIPCK(c, launch_local(nview(view_of(c, L.in[0])), nview(L.out), L.d_w, L.d_b, L.size, L.stride, L.pad, L.act, s)); break;
+    case L_LOCAL:
+        HIPCK(c, launch_local(nview(view_of(c, L.in[0])), nview(L.out), L.d_w, L.d_b, L.size, L.stride, L.pad, L.act, s));
+        if (L.post_act != ACT_LINEAR) HIPCK(c, launch_activate(nview(L.out), false, L.post_act, s));
+        break;
     case L_UPSAMPLE: if (L.pair) { if (getenv("YOLO_PAIR_UPSAMPLE_VIA_F32")) { if (int r = via_f32(c, L, n, 0)) return r; } else HIPCK(c, launch_upsample2x_pair(nview(view_of(c, L.in[0])), nview(L.out), c->semantics == YOLO_SEM_TF, s)); break; } HIPCK(c, launch_upsample2x(nview(view_of(c, L.in[0])), nview(L.out), c->semantics == YOLO_SEM_TF, s)); break;
     case L_MAXPOOL: if (L.pair) { if (int r = via_f32(c, L, n, 1)) return r; break; } HIPCK(c, launch_maxpool(nview(view_of(c, L.in[0])), nview(L.out), L.psize, L.pstride, L.ppad, s)); break;
     case L_REORG: if (L.pair) { if (int r = via_f32(c, L, n, 2)) return r; break; } HIPCK(c, launch_reorg(nview(view_of(c, L.in[0])), nview(L.out), L.pstride, c->semantics == YOLO_SEM_DARKNET, s)); break;

@@ -18,8 +18,11 @@ CFG_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "cfg")
 
 def cfg_text(name):
     """Text of a shipped topology ('yolov3', 'yolov3-608', 'yolov3-tiny', 'yolov2', 'yolov2-tiny-voc', 'yolov1', 'yolov1-tiny', and the
-    classifiers 'darknet19', 'darknet53') or of a cfg file path."""
+    classifiers 'darknet19', 'darknet53', 'resnet18', 'resnet50', 'vgg-16') or of a cfg file path.  tools/make_cfgs.py generates them,
+    and ResNet-34 / 101 / 152 on request (`resnet(depth)`)."""
     path = name if os.path.exists(name) else os.path.join(CFG_DIR, name + ".cfg")
+    if not os.path.exists(path) and os.path.exists(os.path.join(CFG_DIR, "zoo", name + ".cfg")):
+        path = os.path.join(CFG_DIR, "zoo", name + ".cfg")          # cfg/zoo/: the classifiers of darknet's model zoo beyond the two YOLO backbones
     with open(path) as f:
         return f.read()
 

@@ -45,7 +45,7 @@ EXPORTS = [
     "yolo_forward_images_u8", "yolo_detect_images_u8", "yolo_detect_images_graph", "yolo_fit_unit_value", "yolo_darknet_boxes_at",
     "yolo_num_classes", "yolo_classify", "yolo_classify_images_u8", "yolo_op_avgpool", "yolo_op_softmax",
     "yolo_set_hier_thresh", "yolo_set_hierarchy_mode", "yolo_darknet_boxes_map", "yolo_tree_geometry", "yolo_tree_read", "yolo_plan_check", "yolo_plan_table",
-    "yolo_op_tree_softmax", "yolo_op_tree_top",
+    "yolo_op_tree_softmax", "yolo_op_tree_top", "yolo_activation_code", "yolo_op_activate", "yolo_op_shortcut",
 ]
 HIER_CONDITIONAL, HIER_ABSOLUTE, HIER_LEAVES = 0, 1, 2
 _HIER_MODES = {None: HIER_CONDITIONAL, "conditional": HIER_CONDITIONAL, "absolute": HIER_ABSOLUTE, "leaves": HIER_LEAVES}
@@ -145,6 +145,9 @@ def load_library():
     l.yolo_plan_table.argtypes = [C.c_char_p, I, I, I, C.c_char_p, SZ, C.c_char_p, SZ]
     l.yolo_op_tree_softmax.argtypes = [P, I, I, C.c_char_p, F, I, P, I]
     l.yolo_op_tree_top.argtypes = [P, I, C.c_char_p, F, P, I]
+    l.yolo_activation_code.argtypes = [C.c_char_p]
+    l.yolo_op_activate.argtypes = [P, I, I, I, I, I, I, P, I]
+    l.yolo_op_shortcut.argtypes = [P, I, I, I, I, P, I, I, I, I, I, P, I]
     l.yolo_shard_bounds.argtypes = [I, I, I, C.POINTER(I), C.POINTER(I)]
     l.yolo_dist_flat_words.argtypes = [I, I]; l.yolo_dist_flat_words.restype = C.c_size_t
     l.yolo_dist_split_records.argtypes = [P, I, I, I, P, P]
@@ -672,6 +675,41 @@ def op_avgpool(x, dtype=FP32, device=0):
     x = _f32(x); n, h, w, c = x.shape
     out = np.empty((n, c), dtype=np.float32)
     _op_check(load_library().yolo_op_avgpool(x.ctypes.data, n, h, w, c, dtype, out.ctypes.data, device), "yolo_op_avgpool")
+    return out
+
+
+ACTIVATIONS = ("linear", "leaky", "relu", "relie", "logistic", "loggy", "elu", "ramp", "tanh", "plse", "stair", "hardtan", "lhtan")
+
+
+def activation_code(name):
+    """The library's code of a darknet activation name (yolo_activation_code, the planner's mapping); YoloError for a name darknet does
+    not know.  An int passes through."""
+    if isinstance(name, (int, np.integer)):
+        return int(name)
+    code = load_library().yolo_activation_code(str(name).encode())
+    if code < 0:
+        raise YoloError("unknown activation '%s'" % name)
+    return code
+
+
+def op_activate(x, activation, dtype=FP32, device=0):
+    """act(x) of x [n, h, w, c] by the kernel behind a layer whose activation is outside the conv epilogues' slope family (k_activate);
+    x is stored as `dtype` first and the result is rounded to it -> float32 [n, h, w, c]."""
+    x = _f32(x); n, h, w, c = x.shape
+    out = np.empty_like(x)
+    _op_check(load_library().yolo_op_activate(x.ctypes.data, n, h, w, c, activation_code(activation), dtype, out.ctypes.data, device), "yolo_op_activate")
+    return out
+
+
+def op_shortcut(x, frm, activation="linear", dtype=FP32, device=0):
+    """darknet's [shortcut]: act(x + gather(frm)), x [n, h2, w2, c2] the layer's input, frm [n, h1, w1, c1] the `from` tensor (the first
+    min(c1, c2) channels, stride w1 // w2 or sample w2 // w1 as shortcut_cpu computes them), stored as `dtype` first -> float32 like x."""
+    x = _f32(x); frm = _f32(frm); n, h2, w2, c2 = x.shape; n1, h1, w1, c1 = frm.shape
+    if n1 != n:
+        raise ValueError("op_shortcut: batch sizes differ")
+    out = np.empty_like(x)
+    _op_check(load_library().yolo_op_shortcut(x.ctypes.data, n, h2, w2, c2, frm.ctypes.data, h1, w1, c1, activation_code(activation), dtype,
+                                              out.ctypes.data, device), "yolo_op_shortcut")
     return out
 
 
