@@ -69,9 +69,9 @@ enum yolo_decode { YOLO_DECODE_RATIO = 0, YOLO_DECODE_PIXEL = 1 };
  * V3/yolo_v3.py:111-159 (input pixels).  Region (v2) heads are always normalised (V2/decode.py:13). */
 enum yolo_location { YOLO_HOST = 0, YOLO_DEVICE = 1 };
 enum yolo_image_format {
-    YOLO_IMG_U8 = 0,           /* uint8  [n,S,S,3] already at network size */
-    YOLO_IMG_F32 = 1,          /* float32 [n,S,S,3] already at network size */
-    YOLO_IMG_F32_CHW = 2       /* float32 [n,3,S,S] planar: darknet's `image` layout (DN/image.c get_pixel) */
+    YOLO_IMG_U8 = 0,           /* uint8  [n,H,W,3] already at network size ([net] height x width) */
+    YOLO_IMG_F32 = 1,          /* float32 [n,H,W,3] already at network size */
+    YOLO_IMG_F32_CHW = 2       /* float32 [n,3,H,W] planar: darknet's `image` layout (DN/image.c get_pixel) */
 };
 enum yolo_nms_mode {
     YOLO_NMS_TF = 0,           /* tf.image.non_max_suppression: class-agnostic, `>` iou, top max_out (row N1) */
@@ -164,14 +164,18 @@ int yolo_input_size(const yolo_ctx *ctx, int *height, int *width, int *channels)
 int yolo_num_rows(const yolo_ctx *ctx);      /* candidates per image: 10647 @416 v3, 845 v2 */
 int yolo_num_attrs(const yolo_ctx *ctx);     /* 5 + classes */
 int yolo_num_layers(const yolo_ctx *ctx);
-/* detection head number `head` (0-based, cfg order): kind 0 = [yolo], 1 = [region]; grid side; anchors per cell; first row of
- * this head in the decoded tensor (rows are cell-major, anchor inner).  YOLO_ERR_INVALID past the last head. */
+/* detection head number `head` (0-based, cfg order): kind 0 = [yolo], 1 = [region], 2 = [detection]; grid rows and columns; anchors
+ * per cell; first row of this head in the decoded tensor (rows are cell-major, cell = row * grid_w + col, anchor inner).
+ * YOLO_ERR_INVALID past the last head. */
+int yolo_head_geometry_hw(const yolo_ctx *ctx, int head, int *kind, int *grid_h, int *grid_w, int *anchors, int *row_offset);
+/* the same for a head whose grid is square (grid = its side).  A head of a network with width != height has two sides:
+ * YOLO_ERR_UNSUPPORTED, use yolo_head_geometry_hw. */
 int yolo_head_geometry(const yolo_ctx *ctx, int head, int *kind, int *grid, int *anchors, int *row_offset);
 double yolo_conv_flops(const yolo_ctx *ctx); /* 2*k*k*Cin*Cout*Ho*Wo summed (DN/convolutional_layer.c:325), per image */
 double yolo_conv_bytes(const yolo_ctx *ctx, int n); /* algorithmic HBM bytes of the conv stack for n images */
 
 /* ---- hot path ------------------------------------------------------------------------------- */
-/* images: [n,S,S,3] in `fmt`, at `loc`; each value is multiplied by `scale` on the way in
+/* images: [n,H,W,3] ([net] height x width) in `fmt`, at `loc`; each value is multiplied by `scale` on the way in
  * (1/255 for the `inputs / 255` of V3/yolo_v3.py:215, 1 for pre-normalised input).  Runs the conv stack
  * and the head decode; the decoded tensor [n, rows, attrs] (V3/yolo_v3.py:266) stays resident and, when
  * detections_out != NULL, is also copied there (fp32, at out_loc).  Asynchronous on the context stream
@@ -224,7 +228,7 @@ int yolo_darknet_boxes(yolo_ctx *ctx, int w, int h, float thresh, int relative, 
  * each image with its own w x h.  yolo_darknet_boxes is yolo_darknet_boxes_at(ctx, 0, ...). */
 int yolo_darknet_boxes_at(yolo_ctx *ctx, int image, int w, int h, float thresh, int relative, float *records, int cap, int *count);
 /* What darknet's network_predict returns (DN/network.c:497-508, net->output): the LAST layer's output of image 0 in darknet's
- * own layout -- for a [yolo] / [region] layer the planar [anchors * (5 + classes)][grid * grid] tensor with that layer's
+ * own layout -- for a [yolo] / [region] layer the planar [anchors * (5 + classes)][grid_h * grid_w] tensor with that layer's
  * activations applied (DN/yolo_layer.c:143-152, DN/region_layer.c:160-186).  host buffer of yolo_last_layer_size() floats. */
 size_t yolo_last_layer_size(const yolo_ctx *ctx);
 int yolo_last_layer_output(yolo_ctx *ctx, float *out, size_t out_floats);
@@ -307,7 +311,9 @@ int yolo_op_conv_num_cfgs(void);
 int yolo_op_upsample2x(const float *x, int n, int h, int w, int c, int semantics, float *out, int device);
 int yolo_op_reorg(const float *x, int n, int h, int w, int c, int stride, int semantics, float *out, int device);
 int yolo_op_maxpool(const float *x, int n, int h, int w, int c, int size, int stride, float *out, int device);
-/* legacy-bilinear stretch of one uint8 image to [s,s,3] fp32: (value/255 then resize) * post_scale. */
+/* legacy-bilinear stretch of one uint8 image to [out_h,out_w,3] fp32: (value/255 then resize) * post_scale. */
+int yolo_op_resize_u8_hw(const uint8_t *img, int h, int w, int out_h, int out_w, float post_scale, float *out, int device);
+/* ... to [s,s,3]: the out_h == out_w call of the same kernel */
 int yolo_op_resize_u8(const uint8_t *img, int h, int w, int s, float post_scale, float *out, int device);
 /* V2/utils.py:13-27 `preprocess_image`'s arithmetic on the device: cv2.resize(float32 image, (ow, oh)) -- INTER_LINEAR, half-pixel centres,
  * restated from OpenCV's published CV_32F linear resize -- of one uint8 [h,w,3] image, optionally after BGR -> RGB (swap_rb), then
@@ -315,7 +321,11 @@ int yolo_op_resize_u8(const uint8_t *img, int h, int w, int s, float post_scale,
 int yolo_op_resize_cv2(const uint8_t *img, int h, int w, int oh, int ow, int swap_rb, float divisor, float *out, int device);
 /* `detections_boxes` (V3/yolo_v3.py:329-347): (cx,cy,w,h,...) -> (x0,y0,x1,y1,...) over [n,rows,attrs] fp32 */
 int yolo_op_detections_boxes(const float *det, int n, int rows, int attrs, float *out, int device);
-/* head decode of raw [n,g,g,na*(5+classes)] fp32: yolo (logistic) or region (softmax) */
+/* head decode of raw [n,gh,gw,na*(5+classes)] fp32 (gh grid rows, gw columns) of a network input of img_h x img_w: yolo (logistic) or
+ * region (softmax).  x and w follow the columns / the width, y and h the rows / the height; per-axis strides img_w / gw and img_h / gh */
+int yolo_op_decode_hw(const float *raw, int n, int gh, int gw, int na, int classes, const float *anchors_wh,
+                      int img_h, int img_w, int decode, int region, float *out, int device);
+/* ... of raw [n,g,g,na*(5+classes)]: the gh == gw call of the same kernels */
 int yolo_op_decode(const float *raw, int n, int g, int na, int classes, const float *anchors_wh,
                    int img_size, int decode, int region, float *out, int device);
 /* threshold + NMS over det [n,rows,attrs] fp32.  nms_mode bits 8..19 / 20..31 carry image height / width for

@@ -19,6 +19,9 @@ Runs only in the build container (it reads /root/reference and oracle/_ref); the
   mini_cls53.npz / mini_cls19.npz
                      two small classifier topologies ([avgpool], [softmax], [cost]; darknet-53's and darknet-19's tail order), every
                      layer output and the probability vector, from the same compiled reference
+  mini_v3_rect.npz / mini_v2_rect.npz / mini_cls_rect.npz / mini_v3_rect_letterbox.npz
+                     the minis at width != height (64 high x 96 wide, 96 x 64, 64 x 96): layers and boxes as above; the letterbox file holds
+                     the reference's own letterbox_image of three source images and its corrected boxes at each image's size
   yolov3_bn_real.npz / yolov2_bn_real.npz
                      the COMPLETE batch-norm vectors (beta, gamma, rolling mean, rolling variance) of every
                      batch-normalised conv of yolov3.weights / yolov2.weights, and the first l.n filter
@@ -636,6 +639,135 @@ def gen_darknet_py_symbols():
     print("darknet.py binds", len(names), "symbols")
 
 
+# ---- rectangular networks (width != height): the same minis at another [net] size, through the same compiled reference ----
+def _rect_cfg(cfg, height, width):
+    from yolo_tensorflow_amd import darknet_io as IO
+    return IO.with_input_size(cfg, (height, width))
+
+
+def _head_counts(net, secs, thresh, classes):
+    """Boxes whose objectness exceeds `thresh`, per [yolo] / [region] layer, from the layer's own output (planar, logistic applied)."""
+    counts = []
+    for i in range(net.n):
+        if secs[i + 1]["type"] not in ("yolo", "region"):
+            continue
+        o = net.layer_output_nhwc(i)[0]
+        counts.append(int((o[..., 4::5 + classes] > thresh).sum()))
+    return counts
+
+
+def gen_mini_rect(name, cfg, classes, height, width, nms_thresh=0.3, thresh=0.15, letterbox=False):
+    """gen_mini at height x width.  The image seed is the first from 11 on for which every head has a box above thresh, there are at
+    least 8 boxes in all, and do_nms_sort suppresses at least one box and leaves at least one (thresholds are never lowered).
+    letterbox: also the reference's own letterbox_image of three float CHW source images (wider than, taller than and of the network's
+    aspect) and get_network_boxes at each image's (w, h), relative=1 -- written to <name>_letterbox.npz (the committed-file size limit)."""
+    import ctypes as C
+    from oracle import darknet_ref as D
+    from yolo_tensorflow_amd import darknet_io as IO
+    cfg = _rect_cfg(cfg, height, width)
+    secs = IO.parse_cfg(cfg)
+    flat = IO.synth_weights(secs, seed=7, obj_bias=0.5)
+    mj, mn = IO.default_header(secs)
+    net = D.RefNet(cfg, flat, mj, mn)
+    assert (net.h, net.w) == (height, width)
+    for seed in range(11, 200):
+        img = np.random.default_rng(seed).integers(0, 256, (height, width, 3), dtype=np.uint8)
+        x = img.astype(np.float32) / np.float32(255.0)
+        net.predict(x)
+        layers = [net.layer_output_nhwc(i).astype(np.float32) for i in range(net.n)]
+        heads = _head_counts(net, secs, thresh, classes)
+        bb, obj, pr = net.boxes(thresh, None, classes)
+        net.predict(x)
+        bb2, obj2, pr2 = net.boxes(thresh, nms_thresh, classes)
+        before, after = int((pr > 0).sum()), int((pr2 > 0).sum())
+        if min(heads) >= 1 and len(bb) >= 8 and 0 < after < before:
+            break
+    else:
+        raise SystemExit(name + ": no image seed meets the fixture conditions")
+    data = {"cfg": np.array(cfg), "weights": flat, "image_u8": img, "header": np.array([mj, mn])}
+    for i, o in enumerate(layers):
+        data["layer_%02d" % i] = o
+    data["boxes_raw"], data["obj_raw"], data["prob_raw"] = bb, obj, pr
+    data["boxes_nms"], data["obj_nms"], data["prob_nms"] = bb2, obj2, pr2
+    data["thresh"] = np.float32(thresh); data["nms"] = np.float32(nms_thresh)
+    np.savez_compressed(os.path.join(OUT, name + ".npz"), **data)
+    print(name, "image seed", seed, "layers", net.n, "boxes", len(bb), "per head", heads, "nonzero probs before/after nms", before, after)
+    if letterbox:
+        class IMAGE(C.Structure):
+            _fields_ = [("w", C.c_int), ("h", C.c_int), ("c", C.c_int), ("data", C.POINTER(C.c_float))]
+        l = D.lib()
+        l.letterbox_image.argtypes = [IMAGE, C.c_int, C.c_int]; l.letterbox_image.restype = IMAGE
+        l.free_image.argtypes = [IMAGE]
+        lb = {"thresh": np.float32(thresh), "nms": np.float32(nms_thresh)}
+        for k, (ih, iw) in enumerate(((37, 80), (50, 37), (32, 48))):
+            for sseed in range(31 + 100 * k, 31 + 100 * k + 100):
+                src = np.ascontiguousarray(np.random.default_rng(sseed).random((3, ih, iw), dtype=np.float32))
+                im = IMAGE(iw, ih, 3, src.ctypes.data_as(C.POINTER(C.c_float)))
+                boxed = l.letterbox_image(im, net.w, net.h)
+                inp = np.ctypeslib.as_array(boxed.data, shape=(3, net.h, net.w)).copy()
+                l.free_image(boxed)
+                net.predict(np.transpose(inp, (1, 2, 0)))
+                num = C.c_int(0)
+                dets = l.get_network_boxes(net.net, iw, ih, thresh, .5, None, 1, C.byref(num))
+                n = num.value
+                bbk = np.zeros((n, 4), np.float32); objk = np.zeros(n, np.float32); prk = np.zeros((n, classes), np.float32)
+                for i in range(n):
+                    d = dets[i]
+                    bbk[i] = (d.bbox.x, d.bbox.y, d.bbox.w, d.bbox.h); objk[i] = d.objectness
+                    prk[i] = np.ctypeslib.as_array(d.prob, shape=(classes,))
+                l.do_nms_sort(dets, n, classes, nms_thresh)
+                prn = np.zeros((n, classes), np.float32); bbn = np.zeros((n, 4), np.float32)
+                for i in range(n):
+                    prn[i] = np.ctypeslib.as_array(dets[i].prob, shape=(classes,))
+                    bbn[i] = (dets[i].bbox.x, dets[i].bbox.y, dets[i].bbox.w, dets[i].bbox.h)
+                l.free_detections(dets, n)
+                b4, a4 = int((prk > 0).sum()), int((prn > 0).sum())
+                if min(_head_counts(net, secs, thresh, classes)) >= 1 and n >= 8 and 0 < a4 < b4:
+                    break
+            else:
+                raise SystemExit(name + ": no source seed meets the fixture conditions for %d x %d" % (ih, iw))
+            lb["src_%d" % k], lb["input_%d" % k] = src, inp
+            lb["boxes_%d" % k], lb["obj_%d" % k], lb["prob_%d" % k], lb["prob_nms_%d" % k], lb["boxes_nms_%d" % k] = bbk, objk, prk, prn, bbn
+            print(name, "letterbox source %d x %d seed %d: boxes %d, nonzero probs before/after nms %d %d" % (ih, iw, sseed, n, b4, a4))
+        np.savez_compressed(os.path.join(OUT, name + "_letterbox.npz"), **lb)
+    net.close()
+
+
+def gen_mini_cls_rect():
+    """gen_mini_cls's darknet-19 mini at 64 high x 96 wide: every layer output and the softmax vector."""
+    from oracle import darknet_ref as D
+    from yolo_tensorflow_amd import darknet_io as IO
+    cfg, seed, logit_layer = _rect_cfg(MINI_CLS19, 64, 96), 23, 8
+    secs = IO.parse_cfg(cfg)
+    flat = IO.synth_weights(secs, seed=seed)
+    last = IO.conv_specs(secs)[-1]
+    tail = last["filters"] * (1 + last["cin"] * last["size"] ** 2)
+    img = np.random.default_rng(seed + 1).integers(0, 256, (64, 96, 3), dtype=np.uint8)
+    x = img.astype(np.float32) / np.float32(255.0)
+    net = D.RefNet(cfg, flat, 0, 2)
+    net.predict(x)
+    factor = np.float32(round(5.0 / float(np.abs(net.layer_output_nhwc(logit_layer)).max()), 2))
+    net.close()
+    flat[-tail:] *= factor
+    net = D.RefNet(cfg, flat, 0, 2)
+    net.predict(x)
+    data = {"cfg": np.array(cfg), "weights": flat, "image_u8": img, "header": np.array([0, 2])}
+    for i in range(net.n):
+        data["layer_%02d" % i] = np.asarray(net.layer_output_nhwc(i), dtype=np.float32)
+    out_layer = max(i for i in range(net.n) if secs[i + 1]["type"] != "cost")
+    data["output"] = np.asarray(data["layer_%02d" % out_layer], dtype=np.float32).reshape(-1)
+    data["max_abs_logit"] = np.float32(np.abs(data["layer_%02d" % logit_layer]).max())
+    np.savez_compressed(os.path.join(OUT, "mini_cls_rect.npz"), **data)
+    print("mini_cls_rect layers", net.n, "max|logit|", float(data["max_abs_logit"]), "p max/min", float(data["output"].max()), float(data["output"].min()))
+    net.close()
+
+
+def gen_rect():
+    gen_mini_rect("mini_v3_rect", MINI_V3, 4, 64, 96, letterbox=True)
+    gen_mini_rect("mini_v2_rect", MINI_V2, 5, 96, 64)
+    gen_mini_cls_rect()
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     if sys.argv[1:] == ["bn_real"]:
@@ -646,6 +778,8 @@ if __name__ == "__main__":
         gen_mini_resnet(); sys.exit(0)
     if sys.argv[1:] == ["darknet_py_symbols"]:
         gen_darknet_py_symbols(); sys.exit(0)
+    if sys.argv[1:] == ["rect"]:
+        gen_rect(); sys.exit(0)
     stub_modules()
     gen_nms_v3()
     gen_v2_post()
@@ -655,6 +789,7 @@ if __name__ == "__main__":
     gen_mini_local()
     gen_mini_cls()
     gen_mini_resnet()
+    gen_rect()
     gen_bn_real()
     gen_known_answers()
     gen_darknet_py_symbols()

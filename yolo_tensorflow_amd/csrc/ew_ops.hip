@@ -145,9 +145,9 @@ hipError_t launch_preprocess(const void *img, int fmt, int n, int hw, float scal
 
 // legacy TF bilinear (no half-pixel offset): src = dst * (in/out); value/255 first (D2T _input_process)
 template <class At>
-__device__ __forceinline__ void px_stretch(const At &at, int h, int w, int so, int oy, int ox, float post_scale, float post_add, float *v)
+__device__ __forceinline__ void px_stretch(const At &at, int h, int w, int oh, int ow, int oy, int ox, float post_scale, float post_add, float *v)
 {
-    const float hs = (float)h / (float)so, ws = (float)w / (float)so;
+    const float hs = (float)h / (float)oh, ws = (float)w / (float)ow;
     float fy = (float)oy * hs, fx = (float)ox * ws;
     int y0 = (int)floorf(fy), x0 = (int)floorf(fx);
     int y1 = min(y0 + 1, h - 1), x1 = min(x0 + 1, w - 1);
@@ -233,23 +233,23 @@ struct AtPlanar {
 };
 
 template <typename T>
-__global__ void k_resize_u8(const uint8_t *img, int h, int w, int so, T *out, int out_stride, int out_c, float post_scale, float post_add)
+__global__ void k_resize_u8(const uint8_t *img, int h, int w, int oh, int ow, T *out, int out_stride, int out_c, float post_scale, float post_add)
 {
     int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= so * so) return;
-    int oy = p / so, ox = p - oy * so;
+    if (p >= oh * ow) return;
+    int oy = p / ow, ox = p - oy * ow;
     float v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    px_stretch(AtU8{img, w}, h, w, so, oy, ox, post_scale, post_add, v);
+    px_stretch(AtU8{img, w}, h, w, oh, ow, oy, ox, post_scale, post_add, v);
     if (out_c >= 8) Elt<T>::store8(out + (size_t)p * out_stride, v);
     else
         for (int c = 0; c < out_c; ++c) Elt<T>::store1(out + (size_t)p * out_stride + c, v[c]);
 }
 
-hipError_t launch_resize_u8(const uint8_t *img, int h, int w, int s_out, void *out, int out_dt, int out_stride,
+hipError_t launch_resize_u8(const uint8_t *img, int h, int w, int out_h, int out_w, void *out, int out_dt, int out_stride,
                             int out_c, hipStream_t s, float post_scale, float post_add)
 {
-    size_t np = (size_t)s_out * s_out;
-    WITH_DT(out_dt, hipLaunchKernelGGL(k_resize_u8<T>, grid_for(np), dim3(256), 0, s, img, h, w, s_out, (T *)out, out_stride, out_c, post_scale, post_add));
+    size_t np = (size_t)out_h * out_w;
+    WITH_DT(out_dt, hipLaunchKernelGGL(k_resize_u8<T>, grid_for(np), dim3(256), 0, s, img, h, w, out_h, out_w, (T *)out, out_stride, out_c, post_scale, post_add));
     return hipGetLastError();
 }
 
@@ -743,26 +743,26 @@ hipError_t launch_shortcut(const TView &a, const TView &b, const TView &out, boo
 // ---- darknet letterbox_image (DN/image.c:960-981) fused with the layout change: a planar float image of any size -> px_letterbox,
 //      written as the 8-channel network input ----
 template <typename T>
-__global__ void k_letterbox_chw(const float *img, int iw, int ih, int S, int new_w, int new_h, int off_x, int off_y, T *out, int out_stride)
+__global__ void k_letterbox_chw(const float *img, int iw, int ih, int net_h, int net_w, int new_w, int new_h, int off_x, int off_y, T *out, int out_stride)
 {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= S * S) return;
-    const int oy = p / S, ox = p - oy * S;
+    if (p >= net_h * net_w) return;
+    const int oy = p / net_w, ox = p - oy * net_w;
     float v[8] = {0.5f, 0.5f, 0.5f, 0, 0, 0, 0, 0};
     px_letterbox(AtPlanar{img, iw, ih}, iw, ih, new_w, new_h, off_x, off_y, oy, ox, v);
     Elt<T>::store8(out + (size_t)p * out_stride, v);
 }
-hipError_t launch_letterbox_chw(const float *img, int iw, int ih, int S, void *out, int out_dt, int out_stride, hipStream_t s)
+hipError_t launch_letterbox_chw(const float *img, int iw, int ih, int net_h, int net_w, void *out, int out_dt, int out_stride, hipStream_t s)
 {
     int new_w, new_h;
-    letterbox_dims(S, S, iw, ih, &new_w, &new_h);
+    letterbox_dims(net_w, net_h, iw, ih, &new_w, &new_h);
     if (new_w < 1 || new_h < 1) return hipErrorInvalidValue;
-    WITH_DT(out_dt, hipLaunchKernelGGL(k_letterbox_chw<T>, grid_for((size_t)S * S), dim3(256), 0, s, img, iw, ih, S, new_w, new_h, (S - new_w) / 2, (S - new_h) / 2, (T *)out, out_stride));
+    WITH_DT(out_dt, hipLaunchKernelGGL(k_letterbox_chw<T>, grid_for((size_t)net_h * net_w), dim3(256), 0, s, img, iw, ih, net_h, net_w, new_w, new_h, (net_w - new_w) / 2, (net_h - new_h) / 2, (T *)out, out_stride));
     return hipGetLastError();
 }
 
 // ---- ragged batch fit (yolo_forward_images_u8): native-size uint8 RGB images packed in one HWC buffer, described by a device table of
-//      {offset, h, w}, fitted into the network input [n][S][S][out_stride] by ONE launch: grid (pixel tiles) x (images), one output pixel
+//      {offset, h, w}, fitted into the network input [n][net_h][net_w][out_stride] by ONE launch: grid (pixel tiles) x (images), one output pixel
 //      per lane, the 16-byte output pixel (8 channels: 3 real + 5 zero) stored as one vector.  Per pixel, each fit is the single-image
 //      kernel's arithmetic (px_stretch / px_letterbox / px_cv2), so a batched image equals the same image run alone, bit for bit.
 //      Source bytes are read through a buffer descriptor whose size is the packed buffer's byte count: a descriptor that pointed past
@@ -778,23 +778,23 @@ struct AtPacked {
 };
 
 template <typename T, int FIT>
-__global__ __launch_bounds__(256) void k_fit_images(const uint8_t *pixels, unsigned bytes, const ImgDesc *descs, int S, T *out, int out_stride,
+__global__ __launch_bounds__(256) void k_fit_images(const uint8_t *pixels, unsigned bytes, const ImgDesc *descs, int net_h, int net_w, T *out, int out_stride,
                                                     float post_mul, float post_add)
 {
     const int img = blockIdx.y;
     const int p = blockIdx.x * 256 + threadIdx.x;
-    if (p >= S * S) return;
+    if (p >= net_h * net_w) return;
     const ImgDesc d = descs[img];
-    const int oy = p / S, ox = p - oy * S;
+    const int oy = p / net_w, ox = p - oy * net_w;
     const AtPacked at{__builtin_amdgcn_make_buffer_rsrc((void *)pixels, 0, bytes, 0x00020000), (unsigned)d.offset, d.w, FIT};
     float v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (FIT == FIT_STRETCH) px_stretch(at, d.h, d.w, S, oy, ox, post_mul, post_add, v);
+    if (FIT == FIT_STRETCH) px_stretch(at, d.h, d.w, net_h, net_w, oy, ox, post_mul, post_add, v);
     else {
         if (FIT == FIT_LETTERBOX) {
             int new_w, new_h;
-            letterbox_dims(S, S, d.w, d.h, &new_w, &new_h);
-            px_letterbox(at, d.w, d.h, new_w, new_h, (S - new_w) / 2, (S - new_h) / 2, oy, ox, v);
-        } else px_cv2(at, d.h, d.w, S, S, oy, ox, FIT == FIT_CV2_BGR, 225.0f, v);
+            letterbox_dims(net_w, net_h, d.w, d.h, &new_w, &new_h);
+            px_letterbox(at, d.w, d.h, new_w, new_h, (net_w - new_w) / 2, (net_h - new_h) / 2, oy, ox, v);
+        } else px_cv2(at, d.h, d.w, net_h, net_w, oy, ox, FIT == FIT_CV2_BGR, 225.0f, v);
         // YOLOv1's `x * 2 - 1` ([net] yolo_input_mul / yolo_input_add), as px_stretch applies it
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
@@ -802,15 +802,15 @@ __global__ __launch_bounds__(256) void k_fit_images(const uint8_t *pixels, unsig
             if (post_add != 0.0f) v[c] += post_add;
         }
     }
-    Elt<T>::store8(out + ((size_t)img * S * S + p) * out_stride, v);
+    Elt<T>::store8(out + ((size_t)img * net_h * net_w + p) * out_stride, v);
 }
 
-hipError_t launch_fit_images(const uint8_t *pixels, size_t bytes, const ImgDesc *d_descs, int n, int fit, int S, void *out, int out_dt,
+hipError_t launch_fit_images(const uint8_t *pixels, size_t bytes, const ImgDesc *d_descs, int n, int fit, int net_h, int net_w, void *out, int out_dt,
                              int out_stride, float post_mul, float post_add, hipStream_t s)
 {
-    if (n < 1 || S < 1 || bytes > 0xffffffffull || fit < FIT_STRETCH || fit > FIT_CV2_BGR) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)((S * S + 255) / 256), (unsigned)n);
-#define FIT_LAUNCH(F) WITH_DT(out_dt, hipLaunchKernelGGL((k_fit_images<T, F>), grid, dim3(256), 0, s, pixels, (unsigned)bytes, d_descs, S, (T *)out, out_stride, post_mul, post_add))
+    if (n < 1 || net_h < 1 || net_w < 1 || (size_t)net_h * net_w > 0x7fffffffull || bytes > 0xffffffffull || fit < FIT_STRETCH || fit > FIT_CV2_BGR) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((net_h * net_w + 255) / 256), (unsigned)n);
+#define FIT_LAUNCH(F) WITH_DT(out_dt, hipLaunchKernelGGL((k_fit_images<T, F>), grid, dim3(256), 0, s, pixels, (unsigned)bytes, d_descs, net_h, net_w, (T *)out, out_stride, post_mul, post_add))
     if (fit == FIT_STRETCH) FIT_LAUNCH(FIT_STRETCH);
     else if (fit == FIT_LETTERBOX) FIT_LAUNCH(FIT_LETTERBOX);
     else if (fit == FIT_CV2) FIT_LAUNCH(FIT_CV2);

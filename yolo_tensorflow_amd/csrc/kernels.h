@@ -224,16 +224,16 @@ hipError_t launch_conv_f32(const ConvArgs &a, hipStream_t s);
 // ---- memory-bound operators (ew_ops.hip) ------------------------------------------------------
 hipError_t launch_preprocess(const void *img, int fmt /*0 u8, 1 f32*/, int n, int hw, float scale,
                              void *out, int out_dt, int out_stride, hipStream_t s, float post_mul = 1.0f, float post_add = 0.0f);
-hipError_t launch_resize_u8(const uint8_t *img, int h, int w, int s_out, void *out, int out_dt,
+hipError_t launch_resize_u8(const uint8_t *img, int h, int w, int out_h, int out_w, void *out, int out_dt,
                             int out_stride, int out_c, hipStream_t s, float post_scale = 1.0f, float post_add = 0.0f);
 // cv2.resize (INTER_LINEAR, float32) of a uint8 [h,w,3] image to fp32 [oh,ow,3], optional BGR -> RGB, then / divisor (V2/utils.py:13-27)
 hipError_t launch_resize_cv2_u8(const uint8_t *img, int h, int w, int oh, int ow, int swap_rb, float divisor, float *out, hipStream_t s);
 // ragged batch of native-size uint8 RGB images (yolo_forward_images_u8): one packed HWC buffer, one descriptor per image (the layout of
-// yolo_image_desc, include/yolo_hip.h), all fitted into the network input [n][S][S][out_stride] in ONE launch.  fit: FIT_* below.
+// yolo_image_desc, include/yolo_hip.h), all fitted into the network input [n][net_h][net_w][out_stride] in ONE launch.  fit: FIT_* below.
 struct ImgDesc { unsigned long long offset; int h, w; };
 enum { FIT_STRETCH = 0, FIT_LETTERBOX = 1, FIT_CV2 = 2, FIT_CV2_BGR = 3 };
 // source pixels are read through a buffer descriptor of `bytes` bytes (< 2^32, checked by the caller with every descriptor)
-hipError_t launch_fit_images(const uint8_t *pixels, size_t bytes, const ImgDesc *d_descs, int n, int fit, int S, void *out, int out_dt,
+hipError_t launch_fit_images(const uint8_t *pixels, size_t bytes, const ImgDesc *d_descs, int n, int fit, int net_h, int net_w, void *out, int out_dt,
                              int out_stride, float post_mul, float post_add, hipStream_t s);
 // darknet's letterbox_image geometry (DN/image.c:960-966): the aspect-preserving size of a w x h image inside netw x neth
 __host__ __device__ inline void letterbox_dims(int netw, int neth, int w, int h, int *new_w, int *new_h)
@@ -333,10 +333,10 @@ hipError_t launch_head_darknet_layout_tree(const float *raw, int raw_stride, int
 
 // ---- head decode + postprocess (post_ops.hip) ---------------------------------------------------
 struct DecodeArgs {
-    const float *raw; int raw_stride;   // [n, g*g, raw_stride] fp32 head conv output
-    int n, g, na, classes;
-    float anchors[2 * 16];              // pixels (yolo) or grid units (region), masked order
-    int img_size;
+    const float *raw; int raw_stride;   // [n, gh*gw, raw_stride] fp32 head conv output, cell = row * gw + col
+    int n, gh, gw, na, classes;         // grid rows x columns
+    float anchors[2 * 16];              // yolo: (w / stride_x, h / stride_y); region: grid units; masked order
+    int img_h, img_w;                   // network input; per-axis strides img_w / gw, img_h / gh
     int mode;                           // yolo_decode
     int region;                         // 1: softmax/region head
     float *det; int rows_total; int row_off;   // det [n, rows_total, 5+classes]; nullptr: the decoded tensor is not materialised ...
@@ -347,15 +347,16 @@ struct DecodeArgs {
 };
 #ifdef __HIPCC__
 // Box and objectness of one [region] box, the ONE place this arithmetic is written (V2/decode.py:13-47; k_decode_region and its tree
-// twins): p the box's 5 + classes raw values, o (cx, cy, w, h, objectness) normalised by the grid size g
+// twins; on a gh x gw grid DN/region_layer.c get_region_box): p the box's 5 + classes raw values, o (cx, cy, w, h, objectness), x and w
+// normalised by the grid's columns gw, y and h by its rows gh
 __device__ __forceinline__ float region_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
-__device__ __forceinline__ float region_box_attr(int k, const float *p, int cell, int g, const float *anchor_wh)
+__device__ __forceinline__ float region_box_attr(int k, const float *p, int cell, int gw, int gh, const float *anchor_wh)
 {
-    const float G = (float)g;
-    if (k == 0) return ((float)(cell % g) + region_sigmoid(p[0])) / G;
-    if (k == 1) return ((float)(cell / g) + region_sigmoid(p[1])) / G;
-    if (k == 2) return (anchor_wh[0] * expf(p[2])) / G;
-    if (k == 3) return (anchor_wh[1] * expf(p[3])) / G;
+    const float GW = (float)gw, GH = (float)gh;
+    if (k == 0) return ((float)(cell % gw) + region_sigmoid(p[0])) / GW;
+    if (k == 1) return ((float)(cell / gw) + region_sigmoid(p[1])) / GH;
+    if (k == 2) return (anchor_wh[0] * expf(p[2])) / GW;
+    if (k == 3) return (anchor_wh[1] * expf(p[3])) / GH;
     return region_sigmoid(p[4]);
 }
 // Attribute k < 5 of a box in darknet's layer-output layout (DN/yolo_layer.c:143-152, DN/region_layer.c:163-173): the logistic,
@@ -367,11 +368,11 @@ __device__ __forceinline__ float darknet_layout_box_attr(int k, const float *p)
 #endif
 // Lean decode of up to four [yolo] heads in ONE launch (yolo_detect*: the decodes of a three-scale network are three short,
 // latency-bound launches otherwise; the head tensors keep their own buffers, so the early heads can wait for the last one)
-struct LeanHead { const float *raw; const float *obj; int raw_stride, g, na, row_off; long box_begin; float anchors[2 * 16]; };      // obj: compact objectness-logit plane [n * g * g][na] written by the head conv, or nullptr (read from raw)
+struct LeanHead { const float *raw; const float *obj; int raw_stride, gh, gw, na, row_off; long box_begin; float sx, sy; float anchors[2 * 16]; };      // obj: compact objectness-logit plane [n * gh * gw][na] written by the head conv, or nullptr (read from raw); sx, sy: the strides img_w / gw, img_h / gh (integer divisions) as floats
 struct LeanArgs {
     int nheads; LeanHead h[4];
-    long total;                          // boxes of all heads: n * sum(g * g * na)
-    int n, classes, img_size, mode, rows_total;
+    long total;                          // boxes of all heads: n * sum(gh * gw * na)
+    int n, classes, mode, rows_total;
     float *box4; float reject_below;
     uint4 *list; unsigned *list_count; unsigned list_cap;      // boxes that pass the objectness pre-filter (descriptor each); *list_count = entries, zero between launches
 };
@@ -402,18 +403,18 @@ struct PostArgs {
     // candidate box is un-letterboxed for its image (correct_yolo_boxes) before NMS, in source pixels unless geom_relative; the other
     // fits: NMS runs in network space and, with geom_pixels, the kept records are scaled to the image afterwards (a separate launch).
     // NMS_PER_CLASS with geom_pixels: the image's (h, w) is V2's image_shape.
-    const ImgDesc *geom; int geom_fit, geom_pixels, geom_relative, net_size;
+    const ImgDesc *geom; int geom_fit, geom_pixels, geom_relative, netw, neth;
     int geom_net_pixels;                // 1: the decoded boxes are in network-input pixels (DECODE_PIXEL [yolo] heads), 0: normalised
 };
 hipError_t launch_postprocess(const PostArgs &a, hipStream_t s);
 // row S on its own: score = max_k(obj * cls_k), label = first arg-max, of nrows decoded rows (objectness_mode: V3/yolo_v3.py:385,397)
 void launch_score_rows(const float *det, size_t nrows, int attrs, float *scores, int *labels, hipStream_t s, int objectness_mode = 0);
-hipError_t launch_letterbox_chw(const float *img, int iw, int ih, int S, void *out, int out_dt, int out_stride, hipStream_t s);
+hipError_t launch_letterbox_chw(const float *img, int iw, int ih, int net_h, int net_w, void *out, int out_dt, int out_stride, hipStream_t s);
 hipError_t launch_nms_dets(const float4 *boxes, float *prob, float *objectness, int n, int classes, float thresh, int by_obj, hipStream_t s);
 // darknet get_network_boxes on the device (post_ops.hip): ordered compaction + letterbox correction of one image's decoded rows
 struct DnBoxesArgs {
     const float *det; int attrs;          // decoded rows of ONE image [rows][attrs]
-    int nheads, kind[8], grid[8], na[8], off[8];   // per head: 0 yolo / 1 region, grid size, anchors, first row
+    int nheads, kind[8], cells[8], na[8], off[8];   // per head: 0 yolo / 1 region, grid cells (rows x columns), anchors, first row
     float thresh; int w, h, netw, neth, relative;
     // kind 2, a [detection] head (get_detection_detections, DN/detection_layer.c:225-254): every one of the side * side * num boxes,
     // straight from the layer's input vector (= its output in inference): raw [classes | confidences | boxes]

@@ -27,11 +27,13 @@ __device__ __forceinline__ float sigmoid_fast(float x)
 
 // Attribute k (0 x, 1 y, 2 w, 3 h) of a [yolo] box, the ONE place this arithmetic is written (`_detection_layer`, V3/yolo_v3.py:111-159, and
 // `_ratio_detection_layer`, V3/YOLOV3.py:168-238): x raw value, (cx, cy) grid cell, anchor = the box's (w, h) pair pre-divided by the
-// stride on the host, G grid size, S stride.  mode 0 divides by G, the pixel mode multiplies by S: not interchangeable without
-// contraction, and the operand order is the reference's.
-__device__ __forceinline__ float yolo_box_attr(int k, float x, int cx, int cy, const float *anchor, float G, float S, int mode)
+// stride on the host, (GW, GH) grid columns and rows, (SX, SY) the strides along x and y: x and w take GW / SX, y and h GH / SY (one value
+// each on a square network).  mode 0 divides by G, the pixel mode multiplies by S: not interchangeable without contraction, and the
+// operand order is the reference's.
+__device__ __forceinline__ float yolo_box_attr(int k, float x, int cx, int cy, const float *anchor, float GW, float GH, float SX, float SY, int mode)
 {
     const float t = k < 2 ? sigmoidf_(x) + (float)(k == 0 ? cx : cy) : expf(x) * anchor[k - 2];
+    const float G = (k & 1) ? GH : GW, S = (k & 1) ? SY : SX;
     return mode == 0 ? t / G : t * S;
 }
 
@@ -45,10 +47,9 @@ __global__ __launch_bounds__(256) void k_decode_yolo(const DecodeArgs a, float *
     const int lane = threadIdx.x & 63;
     const long wave = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const long nwaves = ((long)gridDim.x * blockDim.x) >> 6;
-    const long total = (long)a.n * a.g * a.g * a.na;
-    const int stride = a.img_size / a.g;
-    const float G = (float)a.g, S = (float)stride;
-    const int gg = a.g * a.g;
+    const int gg = a.gh * a.gw;
+    const long total = (long)a.n * gg * a.na;
+    const float GW = (float)a.gw, GH = (float)a.gh, SX = (float)(a.img_w / a.gw), SY = (float)(a.img_h / a.gh);
     constexpr int U = 4;                       // boxes in flight per wave (memory-level parallelism)
     const bool two = attrs > 64;               // second 64-attribute pass needed (attrs <= 128 is enforced by the launcher)
     for (long b0 = wave * U; b0 < total; b0 += nwaves * U) {
@@ -73,7 +74,7 @@ __global__ __launch_bounds__(256) void k_decode_yolo(const DecodeArgs a, float *
         for (int u = 0; u < U; ++u) {
             if (b0 + u >= total) break;
             const int an = an_[u], cell = cell_[u];
-            const float r0 = lane < 4 ? yolo_box_attr(lane, v0[u], cell % a.g, cell / a.g, a.anchors + 2 * an, G, S, a.mode) : sigmoid_fast(v0[u]);
+            const float r0 = lane < 4 ? yolo_box_attr(lane, v0[u], cell % a.gw, cell / a.gw, a.anchors + 2 * an, GW, GH, SX, SY, a.mode) : sigmoid_fast(v0[u]);
             const float r1 = sigmoid_fast(v1[u]);
             if (lane < attrs) dst[u][lane] = r0;
             if (two && lane + 64 < attrs) dst[u][lane + 64] = r1;
@@ -142,10 +143,9 @@ __global__ __launch_bounds__(256) void k_decode_yolo_cell(const DecodeArgs a, fl
     const int lane = threadIdx.x & 63;
     const long wave = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const long nwaves = ((long)gridDim.x * blockDim.x) >> 6;
-    const int gg = a.g * a.g;
+    const int gg = a.gh * a.gw;
     const long total = (long)a.n * gg;
-    const int stride = a.img_size / a.g;
-    const float G = (float)a.g, S = (float)stride;
+    const float GW = (float)a.gw, GH = (float)a.gh, SX = (float)(a.img_w / a.gw), SY = (float)(a.img_h / a.gh);
     // per-lane channel decomposition, constant over the cells
     int an_[R], k_[R]; bool ok_[R];
 #pragma unroll
@@ -172,7 +172,7 @@ __global__ __launch_bounds__(256) void k_decode_yolo_cell(const DecodeArgs a, fl
     for (long p = wave; p < total; p += nwaves) {
         const unsigned up = (unsigned)__builtin_amdgcn_readfirstlane((int)p);
         const int b = (int)(up / (unsigned)gg), cell = (int)(up - (unsigned)b * gg);
-        const int cy = cell / a.g, cx = cell - cy * a.g;
+        const int cy = cell / a.gw, cx = cell - cy * a.gw;
         const size_t row0 = (size_t)b * a.rows_total + a.row_off + (size_t)cell * a.na;
         float *dst = a.det ? a.det + row0 * attrs : nullptr;
         float *dst4 = a.box4 ? a.box4 + row0 * 4 : nullptr;            // lean form: geometry only (the caller wants boxes, not the tensor)
@@ -191,7 +191,7 @@ __global__ __launch_bounds__(256) void k_decode_yolo_cell(const DecodeArgs a, fl
         if (merged) {
 #pragma unroll
             for (int r = 0; r < R; ++r) if (spec_[r]) { xs = x[r]; ks = k_[r]; ans = an_[r]; }
-            const float vs = ks < 4 ? yolo_box_attr(ks, xs, cx, cy, a.anchors + 2 * ans, G, S, a.mode) : 0.f;
+            const float vs = ks < 4 ? yolo_box_attr(ks, xs, cx, cy, a.anchors + 2 * ans, GW, GH, SX, SY, a.mode) : 0.f;
 #pragma unroll
             for (int r = 0; r < R; ++r) {
                 v[r] = spec_[r] ? vs : sigmoid_fast(x[r]);
@@ -201,7 +201,7 @@ __global__ __launch_bounds__(256) void k_decode_yolo_cell(const DecodeArgs a, fl
         } else {
 #pragma unroll
             for (int r = 0; r < R; ++r) {
-                v[r] = k_[r] < 4 ? yolo_box_attr(k_[r], x[r], cx, cy, a.anchors + 2 * an_[r], G, S, a.mode) : sigmoid_fast(x[r]);
+                v[r] = k_[r] < 4 ? yolo_box_attr(k_[r], x[r], cx, cy, a.anchors + 2 * an_[r], GW, GH, SX, SY, a.mode) : sigmoid_fast(x[r]);
                 if (dst) { if (ok_[r]) dst[lane + 64 * r] = v[r]; }
                 else if (spec_[r]) dst4[an_[r] * 4 + k_[r]] = v[r];
             }
@@ -261,12 +261,11 @@ __global__ __launch_bounds__(1024) void k_decode_yolo_lean_p1(const LeanArgs a, 
 #pragma unroll
         for (int k = 1; k < 4; ++k) if (k < a.nheads && box >= a.h[k].box_begin) hd = k;
         // per-lane head parameters (the four heads' descriptors sit in the kernel arguments: scalar selects)
-        const float *raw = a.h[0].raw, *objp = a.h[0].obj; int raw_stride = a.h[0].raw_stride, g = a.h[0].g, na = a.h[0].na, row_off = a.h[0].row_off; long bb = a.h[0].box_begin;
+        const float *raw = a.h[0].raw, *objp = a.h[0].obj; int raw_stride = a.h[0].raw_stride, gg = a.h[0].gh * a.h[0].gw, na = a.h[0].na, row_off = a.h[0].row_off; long bb = a.h[0].box_begin;
 #pragma unroll
-        for (int k = 1; k < 4; ++k) if (hd == k) { raw = a.h[k].raw; objp = a.h[k].obj; raw_stride = a.h[k].raw_stride; g = a.h[k].g; na = a.h[k].na; row_off = a.h[k].row_off; bb = a.h[k].box_begin; }
-        const int gg = g * g;
+        for (int k = 1; k < 4; ++k) if (hd == k) { raw = a.h[k].raw; objp = a.h[k].obj; raw_stride = a.h[k].raw_stride; gg = a.h[k].gh * a.h[k].gw; na = a.h[k].na; row_off = a.h[k].row_off; bb = a.h[k].box_begin; }
         const unsigned ubox = valid ? (unsigned)(box - bb) : 0u;
-        const unsigned cidx = ubox / (unsigned)na; const int an = (int)(ubox - cidx * (unsigned)na);      // cell index over n * g * g
+        const unsigned cidx = ubox / (unsigned)na; const int an = (int)(ubox - cidx * (unsigned)na);      // cell index over n * gh * gw
         const unsigned b = cidx / (unsigned)gg; const int cell = (int)(cidx - b * (unsigned)gg);
         const unsigned row = b * (unsigned)a.rows_total + (unsigned)row_off + (unsigned)cell * (unsigned)na + (unsigned)an;
         const unsigned eoff = cidx * (unsigned)raw_stride + (unsigned)(an * attrs);              // element offset of the box in its head tensor
@@ -300,9 +299,9 @@ __global__ __launch_bounds__(256) void k_decode_yolo_lean_p2(const LeanArgs a, f
         const uint4 d = act ? a.list[idx] : uint4{0, 0, 0, 0};
         const unsigned r_eoff = d.x, r_row = d.y; const int r_cell = (int)(d.z & 0xffffffu), r_an = (int)((d.z >> 24) & 15u), r_hd = (int)(d.z >> 28);
         const float r_obj = __uint_as_float(d.w);
-        const float *r_raw = a.h[0].raw; int r_g = a.h[0].g;
+        const float *r_raw = a.h[0].raw; int r_gw = a.h[0].gw, r_gh = a.h[0].gh; float r_sx = a.h[0].sx, r_sy = a.h[0].sy;
 #pragma unroll
-        for (int k = 1; k < 4; ++k) if (r_hd == k) { r_raw = a.h[k].raw; r_g = a.h[k].g; }
+        for (int k = 1; k < 4; ++k) if (r_hd == k) { r_raw = a.h[k].raw; r_gw = a.h[k].gw; r_gh = a.h[k].gh; r_sx = a.h[k].sx; r_sy = a.h[k].sy; }
         const float *src = r_raw + r_eoff;
         float vv[8];
 #pragma unroll
@@ -317,7 +316,7 @@ __global__ __launch_bounds__(256) void k_decode_yolo_lean_p2(const LeanArgs a, f
         const float rbest = row_max_dpp(best);
         const int rlabel = row_min_dpp(best == rbest ? label : 0x7fffffff);      // lowest class index holding the maximum
         if (act && l15 < 4) {
-            a.box4[(size_t)r_row * 4 + l15] = yolo_box_attr(l15, g_raw, r_cell % r_g, r_cell / r_g, a.h[r_hd].anchors + 2 * r_an, (float)r_g, (float)(a.img_size / r_g), a.mode);
+            a.box4[(size_t)r_row * 4 + l15] = yolo_box_attr(l15, g_raw, r_cell % r_gw, r_cell / r_gw, a.h[r_hd].anchors + 2 * r_an, (float)r_gw, (float)r_gh, r_sx, r_sy, a.mode);
             if (l15 == 0) { scores[r_row] = rbest; labels[r_row] = rlabel; }
         }
     }
@@ -339,14 +338,15 @@ __global__ void k_decode_region(const DecodeArgs a)
 {
     const int attrs = 5 + a.classes;
     size_t box = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t total = (size_t)a.n * a.g * a.g * a.na;
+    const int gg = a.gh * a.gw;
+    const size_t total = (size_t)a.n * gg * a.na;
     if (box >= total) return;
     int an = (int)(box % a.na); size_t t = box / a.na;
-    int cell = (int)(t % (a.g * a.g)); int b = (int)(t / (a.g * a.g));
-    const float *p = a.raw + ((size_t)b * a.g * a.g + cell) * a.raw_stride + an * attrs;
+    int cell = (int)(t % gg); int b = (int)(t / gg);
+    const float *p = a.raw + ((size_t)b * gg + cell) * a.raw_stride + an * attrs;
     float *o = a.det + ((size_t)b * a.rows_total + a.row_off + (size_t)cell * a.na + an) * attrs;
 #pragma unroll
-    for (int k = 0; k < 5; ++k) o[k] = region_box_attr(k, p, cell, a.g, a.anchors + 2 * an);
+    for (int k = 0; k < 5; ++k) o[k] = region_box_attr(k, p, cell, a.gw, a.gh, a.anchors + 2 * an);
     float mx = -INFINITY;
     for (int k = 0; k < a.classes; ++k) mx = fmaxf(mx, p[5 + k]);
     float sum = 0.f;
@@ -389,14 +389,15 @@ hipError_t launch_decode_v1(const float *raw, int raw_stride, int n, int side, i
 
 hipError_t launch_decode(const DecodeArgs &a, float *scores, int *labels, hipStream_t s)
 {
+    if (a.gh < 1 || a.gw < 1) return hipErrorInvalidValue;
     // the lean form (no decoded tensor) of a single head exists in the cell-per-wave kernel only
     if (!a.det && (a.region || !a.box4 || !scores || a.na * (5 + a.classes) > 256 || a.raw_stride < a.na * (5 + a.classes))) return hipErrorInvalidValue;
     if (a.region) {
-        size_t total = (size_t)a.n * a.g * a.g * a.na;
+        size_t total = (size_t)a.n * a.gh * a.gw * a.na;
         hipLaunchKernelGGL(k_decode_region, dim3((unsigned)((total + 127) / 128)), dim3(128), 0, s, a);
         if (scores) {
             // region heads are tiny (845 rows/image): score them with the generic row kernel
-            const size_t rows = (size_t)a.g * a.g * a.na;
+            const size_t rows = (size_t)a.gh * a.gw * a.na;
             for (int b = 0; b < a.n; ++b)
                 launch_score_rows(a.det + ((size_t)b * a.rows_total + a.row_off) * (5 + a.classes), rows, 5 + a.classes,
                                   scores + (size_t)b * a.rows_total + a.row_off, labels + (size_t)b * a.rows_total + a.row_off, s);
@@ -404,13 +405,13 @@ hipError_t launch_decode(const DecodeArgs &a, float *scores, int *labels, hipStr
     } else {
         const int nch = a.na * (5 + a.classes);
         if (nch <= 256 && a.raw_stride >= nch) {                   // one wave per cell (every shipped topology)
-            size_t cells = (size_t)a.n * a.g * a.g;
+            size_t cells = (size_t)a.n * a.gh * a.gw;
             size_t blocks = (cells + 3) / 4; if (blocks > 256 * 8) blocks = 256 * 8;    // persistent: 8 workgroups per CU
             if (nch <= 128) hipLaunchKernelGGL(k_decode_yolo_cell<2>, dim3((unsigned)blocks), dim3(256), 0, s, a, scores, labels);
             else hipLaunchKernelGGL(k_decode_yolo_cell<4>, dim3((unsigned)blocks), dim3(256), 0, s, a, scores, labels);
             return hipGetLastError();
         }
-        size_t total = (size_t)a.n * a.g * a.g * a.na;             // four boxes per wave per step, grid-stride
+        size_t total = (size_t)a.n * a.gh * a.gw * a.na;           // four boxes per wave per step, grid-stride
         if (5 + a.classes > 128) return hipErrorInvalidValue;
         size_t blocks = (total + 15) / 16; if (blocks > (1u << 20)) blocks = 1u << 20;   // one step per wave: latency-bound otherwise
         hipLaunchKernelGGL(k_decode_yolo, dim3((unsigned)blocks), dim3(256), 0, s, a, scores, labels);
@@ -515,11 +516,11 @@ __device__ __forceinline__ float4 cand_box(const PostArgs &a, int img, int row, 
     if (a.geom && a.geom_fit == FIT_LETTERBOX) {
         const ImgDesc d = a.geom[img];
         int new_w, new_h;
-        letterbox_dims(a.net_size, a.net_size, d.w, d.h, &new_w, &new_h);
-        q0 = dn_correct(0, q0, a.net_size, a.net_size, new_w, new_h, d.w, d.h, a.geom_relative);
-        q1 = dn_correct(1, q1, a.net_size, a.net_size, new_w, new_h, d.w, d.h, a.geom_relative);
-        q2 = dn_correct(2, q2, a.net_size, a.net_size, new_w, new_h, d.w, d.h, a.geom_relative);
-        q3 = dn_correct(3, q3, a.net_size, a.net_size, new_w, new_h, d.w, d.h, a.geom_relative);
+        letterbox_dims(a.netw, a.neth, d.w, d.h, &new_w, &new_h);
+        q0 = dn_correct(0, q0, a.netw, a.neth, new_w, new_h, d.w, d.h, a.geom_relative);
+        q1 = dn_correct(1, q1, a.netw, a.neth, new_w, new_h, d.w, d.h, a.geom_relative);
+        q2 = dn_correct(2, q2, a.netw, a.neth, new_w, new_h, d.w, d.h, a.geom_relative);
+        q3 = dn_correct(3, q3, a.netw, a.neth, new_w, new_h, d.w, d.h, a.geom_relative);
     }
     float4 b;
     if (a.nms_mode == 2 || a.corners_in) b = float4{q0, q1, q2, q3};
@@ -893,12 +894,12 @@ __global__ __launch_bounds__(NMS_THREADS) void k_nms_image(const PostArgs a)
 // the kept records of a stretched image, scaled to its source pixels after NMS: `convert_to_original_size` of the reference's V3 scripts,
 // box * original_size for normalised boxes (V3/YOLO_V3_inference.py:55-57) and box * (original_size / size) for network-pixel boxes
 // (V3/convert_ckpt_and_inference.py:43-45), both float64 in numpy: evaluated in double here and rounded once
-__global__ void k_records_to_source(BoxOut *out, const int *counts, int max_out, const ImgDesc *geom, int net_size, int net_pixels)
+__global__ void k_records_to_source(BoxOut *out, const int *counts, int max_out, const ImgDesc *geom, int netw, int neth, int net_pixels)
 {
     const int img = blockIdx.x, k = threadIdx.x;
     const int cnt = min(counts[img], max_out);
     const ImgDesc d = geom[img];
-    const double rx = net_pixels ? (double)d.w / (double)net_size : (double)d.w, ry = net_pixels ? (double)d.h / (double)net_size : (double)d.h;
+    const double rx = net_pixels ? (double)d.w / (double)netw : (double)d.w, ry = net_pixels ? (double)d.h / (double)neth : (double)d.h;
     for (int r = k; r < cnt; r += blockDim.x) {
         BoxOut &b = out[(size_t)img * max_out + r];
         b.x0 = (float)((double)b.x0 * rx); b.y0 = (float)((double)b.y0 * ry);
@@ -912,7 +913,7 @@ hipError_t launch_postprocess(const PostArgs &a, hipStream_t s)
     if (!a.scores_ready) launch_score_rows(a.det, nrows, a.attrs, a.scores, a.labels, s, a.nms_mode == 3);
     hipLaunchKernelGGL(k_nms_image, dim3(a.n), dim3(NMS_THREADS), 0, s, a);
     if (a.geom && a.geom_pixels && a.geom_fit != FIT_LETTERBOX && a.nms_mode != 1)
-        hipLaunchKernelGGL(k_records_to_source, dim3(a.n), dim3(64), 0, s, (BoxOut *)a.boxes_out, (const int *)a.counts_out, a.max_out, a.geom, a.net_size, a.geom_net_pixels);
+        hipLaunchKernelGGL(k_records_to_source, dim3(a.n), dim3(64), 0, s, (BoxOut *)a.boxes_out, (const int *)a.counts_out, a.max_out, a.geom, a.netw, a.neth, a.geom_net_pixels);
     return hipGetLastError();
 }
 
@@ -1015,7 +1016,7 @@ __global__ __launch_bounds__(1024) void k_darknet_boxes(const DnBoxesArgs a)
     if (tid == 0) s_base = 0;
     __syncthreads();
     for (int hd = 0; hd < a.nheads; ++hd) {
-        const int cells = a.grid[hd] * a.grid[hd], rows = cells * a.na[hd];
+        const int cells = a.cells[hd], rows = cells * a.na[hd];
         if (a.kind[hd] == 2) {
             // [detection]: no selection, no reordering -- box i * num + n of the layer is record i * num + n
             const int base = s_base;

@@ -146,8 +146,9 @@ __device__ __forceinline__ RegionBox region_box_of(const DecodeArgs &a, size_t b
 {
     RegionBox b;
     b.an = (int)(box % a.na); const size_t c = box / a.na;
-    b.cell = (int)(c % ((size_t)a.g * a.g)); const size_t img = c / ((size_t)a.g * a.g);
-    b.p = a.raw + (img * a.g * a.g + b.cell) * (size_t)a.raw_stride + (size_t)b.an * (5 + a.classes);
+    const size_t gg = (size_t)a.gh * a.gw;
+    b.cell = (int)(c % gg); const size_t img = c / gg;
+    b.p = a.raw + (img * gg + b.cell) * (size_t)a.raw_stride + (size_t)b.an * (5 + a.classes);
     b.row = img * a.rows_total + a.row_off + (size_t)b.cell * a.na + b.an;
     return b;
 }
@@ -156,7 +157,7 @@ __global__ __launch_bounds__(TR_NT) void k_decode_region_tree(const DecodeArgs a
 {
     const RegionBox b = region_box_of(a, blockIdx.x);
     float *o = a.det + b.row * (size_t)(5 + a.classes);
-    if (threadIdx.x < 5) o[threadIdx.x] = region_box_attr(threadIdx.x, b.p, b.cell, a.g, a.anchors + 2 * b.an);
+    if (threadIdx.x < 5) o[threadIdx.x] = region_box_attr(threadIdx.x, b.p, b.cell, a.gw, a.gh, a.anchors + 2 * b.an);
     row_tree_probs(t, b.p + 5, 1.f, TREE_ABSOLUTE, o + 5, 1);
 }
 
@@ -173,11 +174,11 @@ __global__ __launch_bounds__(TR_NT) void k_tree_score_rows(const float *det, siz
 __global__ __launch_bounds__(TR_NT) void k_decode_region_tree_lean(const DecodeArgs a, const TreeDev t, float thresh, float *scores, int *labels)
 {
     const int lane = threadIdx.x & 63;
-    const size_t box = (size_t)blockIdx.x * TR_NW + (threadIdx.x >> 6), total = (size_t)a.n * a.g * a.g * a.na;
+    const size_t box = (size_t)blockIdx.x * TR_NW + (threadIdx.x >> 6), total = (size_t)a.n * a.gh * a.gw * a.na;
     if (box >= total) return;
     const RegionBox b = region_box_of(a, box);
-    if (lane < 4) a.box4[b.row * 4 + lane] = region_box_attr(lane, b.p, b.cell, a.g, a.anchors + 2 * b.an);
-    const float obj = region_box_attr(4, b.p, b.cell, a.g, a.anchors + 2 * b.an);
+    if (lane < 4) a.box4[b.row * 4 + lane] = region_box_attr(lane, b.p, b.cell, a.gw, a.gh, a.anchors + 2 * b.an);
+    const float obj = region_box_attr(4, b.p, b.cell, a.gw, a.gh, a.anchors + 2 * b.an);
     int j = 0;
     if (obj >= a.reject_below) j = wave_tree_top_raw(t, b.p + 5, thresh, lane);      // (wave-uniform: every lane holds the same objectness)
     if (lane == 0) { scores[b.row] = obj; labels[b.row] = j; }
@@ -235,14 +236,14 @@ hipError_t launch_tree_top(const TreeDev &t, const TreeRows &x, float hier_thres
 
 static bool region_tree_args_ok(const DecodeArgs &a, const TreeDev &t)
 {
-    const size_t total = (size_t)a.n * a.g * a.g * a.na;
-    return tree_ok(t) && a.raw && a.region && t.n == a.classes && a.n >= 1 && a.g >= 1 && a.na >= 1 && a.na <= 16 && a.raw_stride >= a.na * (5 + a.classes) && total <= 0x7fffffffull;
+    const size_t total = (size_t)a.n * a.gh * a.gw * a.na;
+    return tree_ok(t) && a.raw && a.region && t.n == a.classes && a.n >= 1 && a.gh >= 1 && a.gw >= 1 && a.na >= 1 && a.na <= 16 && a.raw_stride >= a.na * (5 + a.classes) && total <= 0x7fffffffull;
 }
 
 hipError_t launch_decode_region_tree(const DecodeArgs &a, const TreeDev &t, hipStream_t s)
 {
     if (!region_tree_args_ok(a, t) || !a.det) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_decode_region_tree, dim3((unsigned)((size_t)a.n * a.g * a.g * a.na)), dim3(TR_NT), 0, s, a, t);
+    hipLaunchKernelGGL(k_decode_region_tree, dim3((unsigned)((size_t)a.n * a.gh * a.gw * a.na)), dim3(TR_NT), 0, s, a, t);
     return hipGetLastError();
 }
 
@@ -256,7 +257,7 @@ hipError_t launch_tree_score_rows(const float *det, size_t nrows, int attrs, con
 hipError_t launch_decode_region_tree_lean(const DecodeArgs &a, const TreeDev &t, float hier_thresh, float *scores, int *labels, hipStream_t s)
 {
     if (!region_tree_args_ok(a, t) || !a.box4 || !scores || !labels) return hipErrorInvalidValue;
-    const size_t total = (size_t)a.n * a.g * a.g * a.na;
+    const size_t total = (size_t)a.n * a.gh * a.gw * a.na;
     hipLaunchKernelGGL(k_decode_region_tree_lean, dim3((unsigned)((total + TR_NW - 1) / TR_NW)), dim3(TR_NT), 0, s, a, t, hier_thresh, scores, labels);
     return hipGetLastError();
 }

@@ -55,7 +55,7 @@ int yolo_num_rows(const yolo_ctx *c) { return c ? c->rows : YOLO_ERR_INVALID; }
 int yolo_num_attrs(const yolo_ctx *c) { return c ? c->attrs : YOLO_ERR_INVALID; }
 int yolo_num_classes(const yolo_ctx *c) { return !c ? YOLO_ERR_INVALID : c->cls_layer >= 0 ? c->layers[c->cls_layer].C : c->attrs - 5; }
 int yolo_num_layers(const yolo_ctx *c) { return c ? (int)c->layers.size() : YOLO_ERR_INVALID; }
-int yolo_head_geometry(const yolo_ctx *c, int head, int *kind, int *grid, int *anchors, int *row_offset)
+int yolo_head_geometry_hw(const yolo_ctx *c, int head, int *kind, int *grid_h, int *grid_w, int *anchors, int *row_offset)
 {
     if (!c || head < 0) return YOLO_ERR_INVALID;
     int k = 0;
@@ -63,12 +63,21 @@ int yolo_head_geometry(const yolo_ctx *c, int head, int *kind, int *grid, int *a
         if (L.type != L_YOLO && L.type != L_REGION && L.type != L_DETECT) continue;
         if (k++ != head) continue;
         if (kind) *kind = L.type == L_REGION ? 1 : L.type == L_DETECT ? 2 : 0;
-        if (grid) *grid = L.H;
+        if (grid_h) *grid_h = L.H;
+        if (grid_w) *grid_w = L.W;
         if (anchors) *anchors = L.na;
         if (row_offset) *row_offset = L.row_off;
         return YOLO_OK;
     }
     return YOLO_ERR_INVALID;             // no such head
+}
+int yolo_head_geometry(const yolo_ctx *c, int head, int *kind, int *grid, int *anchors, int *row_offset)
+{
+    int gh = 0, gw = 0;
+    if (int r = yolo_head_geometry_hw(c, head, kind, &gh, &gw, anchors, row_offset)) return r;
+    if (gh != gw) return fail(const_cast<yolo_ctx *>(c), YOLO_ERR_UNSUPPORTED, "yolo_head_geometry: head %d has a %d x %d grid; use yolo_head_geometry_hw", head, gh, gw);
+    if (grid) *grid = gh;
+    return YOLO_OK;
 }
 double yolo_conv_flops(const yolo_ctx *c) { return c ? c->conv_flops : 0; }
 double yolo_conv_bytes(const yolo_ctx *c, int n)
@@ -124,11 +133,11 @@ int yolo_darknet_boxes_map(yolo_ctx *c, int image, int w, int h, float thresh, i
         if (L.type == L_DETECT) {
             if (a.nheads) return fail(c, YOLO_ERR_UNSUPPORTED, "a [detection] head next to other heads");
             a.raw = (const float *)c->layers[li - 1].out.ptr + (size_t)image * c->layers[li - 1].out.stride; a.side = L.side; a.classes = L.classes; a.sqr = L.sqr;
-            a.kind[0] = 2; a.grid[0] = L.side; a.na[0] = L.na; a.off[0] = L.row_off; a.nheads = 1;
+            a.kind[0] = 2; a.cells[0] = L.side * L.side; a.na[0] = L.na; a.off[0] = L.row_off; a.nheads = 1;
             continue;
         }
         if (a.raw) return fail(c, YOLO_ERR_UNSUPPORTED, "a [detection] head next to other heads");
-        a.kind[a.nheads] = L.type == L_REGION; a.grid[a.nheads] = L.H; a.na[a.nheads] = L.na; a.off[a.nheads] = L.row_off; ++a.nheads;
+        a.kind[a.nheads] = L.type == L_REGION; a.cells[a.nheads] = L.H * L.W; a.na[a.nheads] = L.na; a.off[a.nheads] = L.row_off; ++a.nheads;
     }
     a.thresh = thresh; a.w = w; a.h = h; a.netw = c->in_w; a.neth = c->in_h; a.relative = relative;
     a.cap = cap < c->rows ? cap : c->rows;
@@ -199,7 +208,7 @@ int yolo_last_layer_output_batch(yolo_ctx *c, int n, float *out, size_t out_floa
 
 int yolo_last_layer_output(yolo_ctx *c, float *out, size_t out_floats) { return yolo_last_layer_output_batch(c, 1, out, out_floats); }
 
-// The raw tensor a detection head decodes: the head conv's fp32 output [n, grid, grid, anchors * (5 + classes)] (what the reference's
+// The raw tensor a detection head decodes: the head conv's fp32 output [n, grid_h, grid_w, anchors * (5 + classes)] (what the reference's
 // graph builders return before any decode: V2/model_darknet19_slim.py:198-200, V3/yolo_v3.py:239-263 `predictions`).
 int yolo_head_raw(yolo_ctx *c, int head, int n, float *out, size_t out_floats)
 {

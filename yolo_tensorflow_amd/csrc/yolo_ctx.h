@@ -97,10 +97,10 @@ struct yolo_ctx {
     std::vector<Layer> layers;
     std::vector<Storage> storages;
     std::vector<void *> phys; std::vector<size_t> phys_bytes;
-    TView input;                          // [n, S, S, 8]
+    TView input;                          // [n, in_h, in_w, 8]
     void *d_zeros = nullptr;
     void *d_stage = nullptr; size_t stage_bytes = 0;     // host->device image staging
-    TView s2d;                            // [n, S/2, S/2, 32]: space-to-depth of the input for a 7x7/2 first conv
+    TView s2d;                            // [n, in_h/2, in_w/2, 32]: space-to-depth of the input for a 7x7/2 first conv
     const uint8_t *stem_u8 = nullptr; float stem_scale = 1.f; int stem_u8_n = 0;      // uint8 image (of stem_u8_n images) the fused stem reads itself (no conversion launch), or nullptr: c->input.  May be the CALLER's buffer: only valid for a pass over <= stem_u8_n images while the caller keeps it (yolo_time_*)
     float in_mul = 1.f, in_add = 0.f;     // input normalisation after the /255: v * in_mul + in_add ([net] yolo_input_mul / yolo_input_add)
     float *d_det = nullptr; int rows = 0, attrs = 0;

@@ -340,14 +340,19 @@ int yolo_op_tree_top(const float *x_logits, int n, const char *tree_path, float 
     return S.download(labels_out, d_l, (size_t)n * 4);
 }
 
+int yolo_op_resize_u8_hw(const uint8_t *img, int h, int w, int out_h, int out_w, float post_scale, float *out, int device)
+{
+    if (!img || !out || h < 1 || w < 1 || out_h < 1 || out_w < 1 || (size_t)out_h * out_w > 0x7fffffffull) return YOLO_ERR_INVALID;
+    OpScope S(device); if (S.rc) return S.rc;
+    uint8_t *d_i = (uint8_t *)S.upload(img, (size_t)h * w * 3); float *d_o = (float *)S.alloc((size_t)out_h * out_w * 3 * 4);
+    if (S.rc) return S.rc;
+    if (!S.ok(launch_resize_u8(d_i, h, w, out_h, out_w, d_o, 1, 3, 3, S.s, post_scale))) { g_op_err = S.err; return S.rc; }
+    return S.download(out, d_o, (size_t)out_h * out_w * 3 * 4);
+}
+
 int yolo_op_resize_u8(const uint8_t *img, int h, int w, int s, float post_scale, float *out, int device)
 {
-    if (!img || !out || h < 1 || w < 1 || s < 1) return YOLO_ERR_INVALID;
-    OpScope S(device); if (S.rc) return S.rc;
-    uint8_t *d_i = (uint8_t *)S.upload(img, (size_t)h * w * 3); float *d_o = (float *)S.alloc((size_t)s * s * 3 * 4);
-    if (S.rc) return S.rc;
-    if (!S.ok(launch_resize_u8(d_i, h, w, s, d_o, 1, 3, 3, S.s, post_scale))) { g_op_err = S.err; return S.rc; }
-    return S.download(out, d_o, (size_t)s * s * 3 * 4);
+    return yolo_op_resize_u8_hw(img, h, w, s, s, post_scale, out, device);
 }
 
 int yolo_op_resize_cv2(const uint8_t *img, int h, int w, int oh, int ow, int swap_rb, float divisor, float *out, int device)
@@ -370,21 +375,27 @@ int yolo_op_letterbox(const float *image_chw, int iw, int ih, int w, int h, int 
     return S.download(out_chw, d_o, (size_t)w * h * 3 * 4);
 }
 
-int yolo_op_decode(const float *raw, int n, int g, int na, int classes, const float *anchors_wh, int img_size, int decode,
-                   int region, float *out, int device)
+int yolo_op_decode_hw(const float *raw, int n, int gh, int gw, int na, int classes, const float *anchors_wh, int img_h, int img_w, int decode,
+                      int region, float *out, int device)
 {
-    if (!raw || !out || !anchors_wh || na < 1 || na > 16) return YOLO_ERR_INVALID;
+    if (!raw || !out || !anchors_wh || na < 1 || na > 16 || gh < 1 || gw < 1) return YOLO_ERR_INVALID;
     OpScope S(device); if (S.rc) return S.rc;
-    const int attrs = 5 + classes; const size_t cnt = (size_t)n * g * g * na * attrs;
+    const int attrs = 5 + classes; const size_t cnt = (size_t)n * gh * gw * na * attrs;
     float *d_r = (float *)S.upload(raw, cnt * 4), *d_o = (float *)S.alloc(cnt * 4);
     if (S.rc) return S.rc;
     DecodeArgs d; memset(&d, 0, sizeof d);
-    d.raw = d_r; d.raw_stride = na * attrs; d.n = n; d.g = g; d.na = na; d.classes = classes; d.img_size = img_size; d.mode = decode; d.region = region;
-    const int stride = img_size / g;
-    for (int k = 0; k < 2 * na; ++k) d.anchors[k] = region ? anchors_wh[k] : (float)(1.0 * (double)anchors_wh[k] / (double)stride);
-    d.det = d_o; d.rows_total = g * g * na; d.row_off = 0; d.reject_below = -INFINITY;
+    d.raw = d_r; d.raw_stride = na * attrs; d.n = n; d.gh = gh; d.gw = gw; d.na = na; d.classes = classes; d.img_h = img_h; d.img_w = img_w; d.mode = decode; d.region = region;
+    const int stride[2] = {img_w / gw, img_h / gh};          // along x (anchor widths), along y (anchor heights)
+    for (int k = 0; k < 2 * na; ++k) d.anchors[k] = region ? anchors_wh[k] : (float)(1.0 * (double)anchors_wh[k] / (double)stride[k & 1]);
+    d.det = d_o; d.rows_total = gh * gw * na; d.row_off = 0; d.reject_below = -INFINITY;
     if (!S.ok(launch_decode(d, nullptr, nullptr, S.s))) { g_op_err = S.err; return S.rc; }
     return S.download(out, d_o, cnt * 4);
+}
+
+int yolo_op_decode(const float *raw, int n, int g, int na, int classes, const float *anchors_wh, int img_size, int decode,
+                   int region, float *out, int device)
+{
+    return yolo_op_decode_hw(raw, n, g, g, na, classes, anchors_wh, img_size, img_size, decode, region, out, device);
 }
 
 int yolo_op_detections_boxes(const float *det, int n, int rows, int attrs, float *out, int device)

@@ -83,8 +83,8 @@ int build_plan(yolo_ctx *c, const std::vector<Section> &secs)
 {
     const Section &net = secs[0];
     c->in_h = opt_i(net, "height", 0); c->in_w = opt_i(net, "width", 0); c->in_c = opt_i(net, "channels", 3);
-    if (c->in_h <= 0 || c->in_w != c->in_h || c->in_c != 3)
-        return fail(c, YOLO_ERR_UNSUPPORTED, "cfg: need square input with 3 channels (got %dx%dx%d)", c->in_w, c->in_h, c->in_c);
+    if (c->in_h <= 0 || c->in_w <= 0 || c->in_c != 3)
+        return fail(c, YOLO_ERR_UNSUPPORTED, "cfg: need an input of positive height and width with 3 channels (got %dx%dx%d)", c->in_w, c->in_h, c->in_c);
     const int NL = (int)secs.size() - 1;
     c->layers.resize(NL);
     int H = c->in_h, W = c->in_w, C = c->in_c;
@@ -218,7 +218,6 @@ int build_plan(yolo_ctx *c, const std::vector<Section> &secs)
             if (L.na > 16) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: more than 16 anchors", i);
             if (i == 0 || c->layers[i - 1].type != L_CONV) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: head must follow a conv", i);
             if (C != L.na * (5 + L.classes)) return fail(c, YOLO_ERR_INVALID, "layer %d: head expects %d channels, conv gives %d", i, L.na * (5 + L.classes), C);
-            if (H != W) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: non-square grid", i);
             if (c->attrs && c->attrs != 5 + L.classes) return fail(c, YOLO_ERR_UNSUPPORTED, "heads with different class counts");
             if (L.type == L_REGION && s.kv.count("tree")) {
                 // [region] with a softmax tree (YOLO9000, DN/region_layer.c:171-181): the tree takes precedence over softmax=1

@@ -174,12 +174,13 @@ static int run_decode(yolo_ctx *c, int i, int n)
             if (Y.type != L_YOLO) continue;
             const Layer &P = c->layers[k - 1];
             LeanHead &h = la.h[la.nheads++];
-            h.raw = (const float *)P.out.ptr; h.obj = P.d_obj; h.raw_stride = P.out.stride; h.g = Y.H; h.na = Y.na; h.row_off = Y.row_off; h.box_begin = begin;
-            const int stride = c->in_h / Y.H;
-            for (int q = 0; q < 2 * Y.na; ++q) h.anchors[q] = (float)(1.0 * (double)Y.anchors[q] / (double)stride);
+            h.raw = (const float *)P.out.ptr; h.obj = P.d_obj; h.raw_stride = P.out.stride; h.gh = Y.H; h.gw = Y.W; h.na = Y.na; h.row_off = Y.row_off; h.box_begin = begin;
+            const int stride[2] = {c->in_w / Y.W, c->in_h / Y.H};          // along x (anchor widths), along y (anchor heights)
+            h.sx = (float)stride[0]; h.sy = (float)stride[1];
+            for (int q = 0; q < 2 * Y.na; ++q) h.anchors[q] = (float)(1.0 * (double)Y.anchors[q] / (double)stride[q & 1]);
             begin += (long)n * Y.H * Y.W * Y.na;
         }
-        la.total = begin; la.n = n; la.classes = L.classes; la.img_size = c->in_h; la.mode = c->decode; la.rows_total = c->rows;
+        la.total = begin; la.n = n; la.classes = L.classes; la.mode = c->decode; la.rows_total = c->rows;
         la.box4 = c->d_box4; la.reject_below = c->lean_thr; la.list = (uint4 *)c->d_lean_list; la.list_count = c->d_lean_cnt; la.list_cap = (unsigned)((size_t)c->max_batch * c->rows);
         // the list counter must be zero: the NMS launch of the previous detect call resets it; if none ran since the last decode
         // (a failed call in between), a memset does
@@ -190,10 +191,10 @@ static int run_decode(yolo_ctx *c, int i, int n)
     }
     const Layer &P = c->layers[i - 1];
     DecodeArgs d; memset(&d, 0, sizeof d);          // one fill for the three decode launches below
-    d.raw = (const float *)P.out.ptr; d.raw_stride = P.out.stride; d.n = n; d.g = L.H; d.na = L.na; d.classes = L.classes;
-    d.img_size = c->in_h; d.mode = c->decode; d.region = L.type == L_REGION;
-    const int stride = c->in_h / L.H;
-    for (int k = 0; k < 2 * L.na; ++k) d.anchors[k] = L.type == L_YOLO ? (float)(1.0 * (double)L.anchors[k] / (double)stride) : L.anchors[k];
+    d.raw = (const float *)P.out.ptr; d.raw_stride = P.out.stride; d.n = n; d.gh = L.H; d.gw = L.W; d.na = L.na; d.classes = L.classes;
+    d.img_h = c->in_h; d.img_w = c->in_w; d.mode = c->decode; d.region = L.type == L_REGION;
+    const int stride[2] = {c->in_w / L.W, c->in_h / L.H};          // along x (anchor widths), along y (anchor heights)
+    for (int k = 0; k < 2 * L.na; ++k) d.anchors[k] = L.type == L_YOLO ? (float)(1.0 * (double)L.anchors[k] / (double)stride[k & 1]) : L.anchors[k];
     d.det = c->lean ? nullptr : c->d_det; d.box4 = c->lean ? c->d_box4 : nullptr; d.rows_total = c->rows; d.row_off = L.row_off;
     d.reject_below = c->lean ? c->lean_thr : -INFINITY;
     // [region] with a softmax tree.  Full form: the decoded tensor with absolute class probabilities (scored at postprocess time, with the hier_thresh of that moment); descent form (yolo_detect*): box4, scores, labels straight from the raw tensor
@@ -388,7 +389,7 @@ int post(yolo_ctx *c, const float *det, int n, int rows, int attrs, float score_
     if (rows_out) { p.srow = c->d_srow; p.rows_out = out_loc != YOLO_HOST ? (int *)rows_out : c->d_rows; }
     if (c->lean_cnt_dirty) p.zero_word = c->d_lean_cnt;
     if (geom) {
-        p.geom = c->d_descs; p.geom_fit = geom->fit; p.geom_pixels = geom->pixels; p.net_size = c->in_h;
+        p.geom = c->d_descs; p.geom_fit = geom->fit; p.geom_pixels = geom->pixels; p.netw = c->in_w; p.neth = c->in_h;
         // a letterboxed box leaves darknet's correction in source pixels, unless V2's per-class NMS scales it to the image itself
         p.geom_relative = !(geom->pixels && nms_mode != YOLO_NMS_PER_CLASS);
         p.geom_net_pixels = c->decode == YOLO_DECODE_PIXEL;          // [region] / [detection] heads always decode normalised boxes
@@ -437,8 +438,8 @@ int yolo_forward_image_u8(yolo_ctx *c, const uint8_t *image, int h, int w, int l
         HIPCK(c, hipMemcpyAsync(tmp, image, (size_t)h * w * 3, hipMemcpyHostToDevice, c->stream)); src = (const uint8_t *)tmp;
     }
     c->stem_u8 = nullptr;
-    hipError_t e = c->in_pair ? launch_resize_u8(src, h, w, c->in_h, c->d_f32a, DT_F32, 8, 8, c->stream, c->in_mul, c->in_add)
-                              : launch_resize_u8(src, h, w, c->in_h, c->input.ptr, c->input.dt, 8, 8, c->stream, c->in_mul, c->in_add);
+    hipError_t e = c->in_pair ? launch_resize_u8(src, h, w, c->in_h, c->in_w, c->d_f32a, DT_F32, 8, 8, c->stream, c->in_mul, c->in_add)
+                              : launch_resize_u8(src, h, w, c->in_h, c->in_w, c->input.ptr, c->input.dt, 8, 8, c->stream, c->in_mul, c->in_add);
     if (e == hipSuccess && c->in_pair) e = launch_split_from_f32(c->d_f32a, 8, c->input.ptr, 24, 8, (size_t)c->in_h * c->in_w, c->stream, PAIR_B3);
     int r = e == hipSuccess ? run_network(c, 1) : fail(c, YOLO_ERR_HIP, "resize: %s", hipGetErrorString(e));
     if (tmp) { hipStreamSynchronize(c->stream); hipFree(tmp); }
@@ -459,7 +460,7 @@ int yolo_forward_letterbox_chw(yolo_ctx *c, const float *image_chw, int w, int h
         HIPCK(c, hipMemcpyAsync(tmp, image_chw, (size_t)h * w * 3 * 4, hipMemcpyHostToDevice, c->stream)); src = (const float *)tmp;
     }
     c->stem_u8 = nullptr;
-    hipError_t e = c->in_pair ? launch_letterbox_chw(src, w, h, c->in_h, c->d_f32a, DT_F32, 8, c->stream) : launch_letterbox_chw(src, w, h, c->in_h, c->input.ptr, c->input.dt, 8, c->stream);
+    hipError_t e = c->in_pair ? launch_letterbox_chw(src, w, h, c->in_h, c->in_w, c->d_f32a, DT_F32, 8, c->stream) : launch_letterbox_chw(src, w, h, c->in_h, c->in_w, c->input.ptr, c->input.dt, 8, c->stream);
     if (e == hipSuccess && c->in_pair) e = launch_split_from_f32(c->d_f32a, 8, c->input.ptr, 24, 8, (size_t)c->in_h * c->in_w, c->stream, PAIR_B3);
     int r = e == hipSuccess ? run_network(c, 1) : fail(c, YOLO_ERR_HIP, "letterbox: %s", hipGetErrorString(e));
     if (tmp) { hipStreamSynchronize(c->stream); hipFree(tmp); }
@@ -599,9 +600,9 @@ static int images_step(yolo_ctx *c, const uint8_t *pixels, size_t bytes, const y
     if (upload) HIPCK(c, hipMemcpyAsync(c->d_descs, descs, (size_t)n * sizeof(ImgDesc), hipMemcpyHostToDevice, c->stream));
     c->stem_u8 = nullptr;                // the fused stem reads the fitted input
     if (c->in_pair) {
-        HIPCK(c, launch_fit_images(pixels, bytes, c->d_descs, n, fit, c->in_h, c->d_f32a, DT_F32, 8, c->in_mul, c->in_add, c->stream));
+        HIPCK(c, launch_fit_images(pixels, bytes, c->d_descs, n, fit, c->in_h, c->in_w, c->d_f32a, DT_F32, 8, c->in_mul, c->in_add, c->stream));
         HIPCK(c, launch_split_from_f32(c->d_f32a, 8, c->input.ptr, 24, 8, (size_t)n * c->in_h * c->in_w, c->stream, PAIR_B3));
-    } else HIPCK(c, launch_fit_images(pixels, bytes, c->d_descs, n, fit, c->in_h, c->input.ptr, c->input.dt, 8, c->in_mul, c->in_add, c->stream));
+    } else HIPCK(c, launch_fit_images(pixels, bytes, c->d_descs, n, fit, c->in_h, c->in_w, c->input.ptr, c->input.dt, 8, c->in_mul, c->in_add, c->stream));
     if (int r = run_network(c, n, lean)) return r;
     c->geom_fit = fit; c->geom_n = n;
     return YOLO_OK;

@@ -197,6 +197,11 @@ int yolo_plan_table(const char *cfg_text, int dtype, int max_batch, int keep_lay
         size_t total = 0; for (size_t b : c.phys_bytes) total += b;
         snprintf(line, sizeof line, "buffers %zu bytes %zu\n", c.phys_bytes.size(), total);
         text += line;
+        if (c.in_h != c.in_w) {          // a rectangular network only (the table of a square one is pinned byte for byte): its input, every head's grid, the candidate rows per image
+            snprintf(line, sizeof line, "input %dx%d", c.in_h, c.in_w); text += line;
+            for (size_t i = 0; i < c.layers.size(); ++i) { const Layer &L = c.layers[i]; if (L.type == L_YOLO || L.type == L_REGION || L.type == L_DETECT) { snprintf(line, sizeof line, " head %zu grid %dx%d anchors %d", i, L.H, L.W, L.na); text += line; } }
+            snprintf(line, sizeof line, " rows %d\n", c.rows); text += line;
+        }
         if (!out || text.size() + 1 > out_len) r = fail(&c, YOLO_ERR_INVALID, "yolo_plan_table: the table needs %zu bytes", text.size() + 1);
     }
     if (out && out_len) snprintf(out, out_len, "%s", r ? "" : text.c_str());

@@ -28,12 +28,13 @@ def cfg_text(name):
 
 
 def with_input_size(text, size):
-    """Same topology at another square input size (kernels are shape-generic in H,W; darknet
+    """Same topology at another input size: `size` an int (square) or (height, width) (kernels are shape-generic in H,W; darknet
     `resize_network`, DN/network.c:358-438)."""
+    h, w = (size, size) if isinstance(size, int) else (int(size[0]), int(size[1]))
     out = []
     for line in text.splitlines():
         key = line.split("=")[0].strip()
-        out.append(f"{key}={size}" if key in ("width", "height") else line)
+        out.append(f"{key}={w if key == 'width' else h}" if key in ("width", "height") else line)
     return "\n".join(out)
 
 

@@ -35,7 +35,7 @@ class ImageDesc(C.Structure):
 
 EXPORTS = [
     "yolo_create", "yolo_destroy", "yolo_last_error", "yolo_load_darknet_weights", "yolo_set_weights",
-    "yolo_weights_count", "yolo_set_act_scales", "yolo_export", "yolo_create_from_file", "yolo_input_size", "yolo_num_rows", "yolo_num_attrs", "yolo_num_layers", "yolo_head_geometry",
+    "yolo_weights_count", "yolo_set_act_scales", "yolo_export", "yolo_create_from_file", "yolo_input_size", "yolo_num_rows", "yolo_num_attrs", "yolo_num_layers", "yolo_head_geometry", "yolo_head_geometry_hw", "yolo_op_decode_hw", "yolo_op_resize_u8_hw",
     "yolo_conv_flops", "yolo_conv_bytes", "yolo_forward", "yolo_forward_image_u8", "yolo_postprocess",
     "yolo_detect", "yolo_detect_graph", "yolo_synchronize", "yolo_layer_output", "yolo_time_forward", "yolo_time_layers",
     "yolo_autotune", "yolo_get_tile_configs", "yolo_set_tile_configs", "yolo_op_conv2d", "yolo_op_conv_num_cfgs", "yolo_op_upsample2x", "yolo_op_reorg",
@@ -86,6 +86,7 @@ def load_library():
     l.yolo_weights_count.argtypes = [P]; l.yolo_weights_count.restype = C.c_size_t
     l.yolo_set_act_scales.argtypes = [P, P, I]
     l.yolo_head_geometry.argtypes = [P, I, P, P, P, P]
+    l.yolo_head_geometry_hw.argtypes = [P, I, P, P, P, P, P]
     l.yolo_export.argtypes = [P, C.c_char_p]
     l.yolo_create_from_file.argtypes = [C.c_char_p, I, I, P, I, C.c_char_p, C.c_size_t]; l.yolo_create_from_file.restype = P
     l.yolo_input_size.argtypes = [P, C.POINTER(I), C.POINTER(I), C.POINTER(I)]
@@ -110,10 +111,12 @@ def load_library():
     l.yolo_op_reorg.argtypes = [P, I, I, I, I, I, I, P, I]
     l.yolo_op_maxpool.argtypes = [P, I, I, I, I, I, I, P, I]
     l.yolo_op_resize_u8.argtypes = [P, I, I, I, F, P, I]
+    l.yolo_op_resize_u8_hw.argtypes = [P, I, I, I, I, F, P, I]
     l.yolo_op_detections_boxes.argtypes = [P, I, I, I, P, I]
     l.yolo_op_nms_detections.argtypes = [P, P, P, I, I, F, I, I]
     l.yolo_forward_letterbox_chw.argtypes = [P, P, I, I, I, P, I]
     l.yolo_op_decode.argtypes = [P, I, I, I, I, P, I, I, I, P, I]
+    l.yolo_op_decode_hw.argtypes = [P, I, I, I, I, I, P, I, I, I, I, P, I]
     l.yolo_darknet_boxes.argtypes = [P, I, I, F, I, P, I, P]
     l.yolo_last_layer_size.argtypes = [P]; l.yolo_last_layer_size.restype = C.c_size_t
     l.yolo_last_layer_output.argtypes = [P, P, C.c_size_t]
@@ -260,7 +263,8 @@ class Engine:
             raise YoloError("yolo_create: " + err.value.decode())
         h, w, ch = C.c_int(), C.c_int(), C.c_int()
         self.lib.yolo_input_size(self.ctx, C.byref(h), C.byref(w), C.byref(ch))
-        self.size = h.value
+        self.size = h.value                        # the input's height; input_hw: both sides
+        self.input_hw = (h.value, w.value)
         self.rows = self.lib.yolo_num_rows(self.ctx)
         self.attrs = self.lib.yolo_num_attrs(self.ctx)
         self.num_layers = self.lib.yolo_num_layers(self.ctx)
@@ -282,6 +286,7 @@ class Engine:
         h, w, ch = C.c_int(), C.c_int(), C.c_int()
         self.lib.yolo_input_size(self.ctx, C.byref(h), C.byref(w), C.byref(ch))
         self.size = h.value
+        self.input_hw = (h.value, w.value)
         self.rows = self.lib.yolo_num_rows(self.ctx); self.attrs = self.lib.yolo_num_attrs(self.ctx)
         self.num_layers = self.lib.yolo_num_layers(self.ctx); self.max_batch = max_batch; self.dtype = None
         self._own_stream = not stream
@@ -337,7 +342,7 @@ class Engine:
 
     # ---- hot path ----
     def forward(self, images, scale=1.0 / 255.0, want_detections=True, n=None, fmt=None, out=None):
-        """images: uint8 or float32 [n,S,S,3] (numpy, torch host/device tensor, or raw device pointer with
+        """images: uint8 or float32 [n,in_h,in_w,3] (input_hw; numpy, torch host/device tensor, or raw device pointer with
         n and fmt given).  Returns the decoded tensor [n, rows, attrs] (numpy) unless out/want_detections say otherwise."""
         p, loc = _ptr(images)
         # a device uint8 image may be read IN PLACE by the fused stem, also by a later time_forward / time_layers / autotune pass
@@ -385,11 +390,17 @@ class Engine:
             return recs, [rows[i, :counts[i]].copy() for i in range(n)]
         return recs
 
+    def head_geometry(self, head):
+        """Detection head `head` (cfg order) -> dict(kind, grid_h, grid_w, anchors, row_offset) (yolo_head_geometry_hw): kind 0 [yolo],
+        1 [region], 2 [detection]; rows of the decoded tensor are cell-major (cell = row * grid_w + col), the anchor inner."""
+        kind, gh, gw, na, off = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        self._check(self.lib.yolo_head_geometry_hw(self.ctx, head, C.byref(kind), C.byref(gh), C.byref(gw), C.byref(na), C.byref(off)), "yolo_head_geometry_hw")
+        return {"kind": kind.value, "grid_h": gh.value, "grid_w": gw.value, "anchors": na.value, "row_offset": off.value}
+
     def head_raw(self, head, n):
-        """Raw fp32 tensor [n, grid, grid, anchors * (5 + classes)] that detection head `head` decodes (yolo_head_raw)."""
-        kind, grid, na, off = C.c_int(), C.c_int(), C.c_int(), C.c_int()
-        self._check(self.lib.yolo_head_geometry(self.ctx, head, C.byref(kind), C.byref(grid), C.byref(na), C.byref(off)), "yolo_head_geometry")
-        out = np.empty((n, grid.value, grid.value, na.value * self.attrs), dtype=np.float32)
+        """Raw fp32 tensor [n, grid_h, grid_w, anchors * (5 + classes)] that detection head `head` decodes (yolo_head_raw)."""
+        g = self.head_geometry(head)
+        out = np.empty((n, g["grid_h"], g["grid_w"], g["anchors"] * self.attrs), dtype=np.float32)
         self._check(self.lib.yolo_head_raw(self.ctx, head, n, out.ctypes.data, out.size), "yolo_head_raw")
         return out
 
@@ -777,12 +788,29 @@ def op_resize_u8(img, size, post_scale=1.0, device=0):
     return out
 
 
+def op_resize_u8_hw(img, out_hw, post_scale=1.0, device=0):
+    """yolo_op_resize_u8_hw: the legacy-bilinear stretch of one uint8 [h,w,3] image to [out_h,out_w,3] float32."""
+    img = np.ascontiguousarray(img, dtype=np.uint8)
+    oh, ow = int(out_hw[0]), int(out_hw[1])
+    out = np.empty((oh, ow, 3), dtype=np.float32)
+    _op_check(load_library().yolo_op_resize_u8_hw(img.ctypes.data, img.shape[0], img.shape[1], oh, ow, post_scale, out.ctypes.data, device), "yolo_op_resize_u8_hw")
+    return out
+
+
 def op_resize_cv2(img, out_hw, swap_rb=True, divisor=225.0, device=0):
     """yolo_op_resize_cv2: `cv2.resize(image.astype(float32)[, BGR -> RGB], (w, h)) / divisor` of one uint8 [h,w,3] image -> [oh,ow,3] float32."""
     img = np.ascontiguousarray(img, dtype=np.uint8)
     out = np.empty((int(out_hw[0]), int(out_hw[1]), 3), dtype=np.float32)
     _op_check(load_library().yolo_op_resize_cv2(img.ctypes.data, img.shape[0], img.shape[1], int(out_hw[0]), int(out_hw[1]), 1 if swap_rb else 0,
                                                 float(divisor), out.ctypes.data, device), "yolo_op_resize_cv2")
+    return out
+
+
+def op_letterbox(image_chw, w, h, embed=True, device=0):
+    """yolo_op_letterbox: darknet's letterbox_image (embed) or resize_image of a planar float [3, ih, iw] image -> [3, h, w]."""
+    img = _f32(image_chw)
+    out = np.empty((3, int(h), int(w)), dtype=np.float32)
+    _op_check(load_library().yolo_op_letterbox(img.ctypes.data, img.shape[2], img.shape[1], int(w), int(h), 1 if embed else 0, out.ctypes.data, device), "yolo_op_letterbox")
     return out
 
 
@@ -808,6 +836,17 @@ def op_decode(raw, anchors, classes, img_size, decode=DECODE_RATIO, region=False
     out = np.empty((n, g * g * na, 5 + classes), dtype=np.float32)
     _op_check(load_library().yolo_op_decode(raw.ctypes.data, n, g, na, classes, anchors.ctypes.data, img_size, decode,
                                             1 if region else 0, out.ctypes.data, device), "yolo_op_decode")
+    return out
+
+
+def op_decode_hw(raw, anchors, classes, img_hw, decode=DECODE_RATIO, region=False, device=0):
+    """yolo_op_decode_hw: raw [n, gh, gw, na * (5 + classes)] of a network input of img_hw = (height, width) -> [n, gh * gw * na, 5 + classes]."""
+    raw = _f32(raw); n, gh, gw = raw.shape[0], raw.shape[1], raw.shape[2]
+    anchors = _f32(anchors).reshape(-1)
+    na = anchors.size // 2
+    out = np.empty((n, gh * gw * na, 5 + classes), dtype=np.float32)
+    _op_check(load_library().yolo_op_decode_hw(raw.ctypes.data, n, gh, gw, na, classes, anchors.ctypes.data, int(img_hw[0]), int(img_hw[1]), decode,
+                                               1 if region else 0, out.ctypes.data, device), "yolo_op_decode_hw")
     return out
 
 
