@@ -424,6 +424,42 @@ int yolo_plan_table(const char *cfg_text, int dtype, int max_batch, int keep_lay
 int yolo_op_tree_softmax(const float *x, int n, int len, const char *tree_path, float temperature, int mode, float *out, int device);
 int yolo_op_tree_top(const float *x_logits, int n, const char *tree_path, float hier_thresh, int32_t *labels_out, int device);
 
+
+/* ---- dense-prediction ("map") networks: segmentation masks, heat maps, U-Net-shaped cfgs (the reference: examples/segmenter.c, which
+ * calls network_predict and then get_network_image) ------------------------------------------------------------------------------
+ * Served sections: [deconvolutional] (DN/deconvolutional_layer.c; 1 <= size <= 7, 1 <= stride <= 4, 0 <= padding < size, pad=1 meaning
+ * size / 2, a positive output; fp32, bf16 and fp16 configurations), [logistic], [activation] (any of the thirteen names), [l2norm], and
+ * with darknet semantics [upsample] with stride 1..8 and scale.  A cfg whose [net] section says `yolo_output=map` (darknet ignores the
+ * key) and that has no detection head plans a MAP context: its output is the image-shaped tensor of the last layer that is not [cost],
+ * kept in fp32.  For such a context yolo_num_rows / yolo_num_attrs are 0, yolo_last_layer_output* returns the map planar (CHW per image,
+ * what darknet's net->output holds), and the detection and classification entry points return YOLO_ERR_INVALID with a message that says
+ * `map network`; the calls below return the same on a detector or a classifier. */
+int yolo_output_map_geometry(yolo_ctx *ctx, int *h, int *w, int *c);
+/* the map of images 0..n-1 of the last forward: NHWC fp32 [n][h][w][c], host */
+int yolo_output_map(yolo_ctx *ctx, int n, float *out, size_t out_floats);
+/* per map pixel of those images the arg-max over the channels, the lowest index winning a tie; 255 where the maximum is < thresh.
+ * labels_u8 [n][h][w], host.  YOLO_ERR_UNSUPPORTED for a map of more than 255 channels. */
+int yolo_label_map(yolo_ctx *ctx, int n, float thresh, uint8_t *labels_u8);
+/* A ragged batch of native-size images (host: `pixels` packed as for yolo_forward_images_u8, ending where its last image ends): one fit
+ * launch and one forward, then one kernel that writes image i's labels AT THAT IMAGE'S OWN SIZE, [h_i][w_i] uint8 at labels_u8 +
+ * label_offsets[i] (NULL: back to back in image order; with offsets, the bytes between the images are zeroed).  Each native pixel takes
+ * its map pixel by nearest lookup through the fit, in integers: pixel x of an image w wide, fitted to new_w columns at offset dx of a
+ * net_w-wide input, with a map_w-wide map, reads column floor(((2x + 1) new_w + 2 w dx) map_w / (2 w net_w)), clamped to map_w - 1; the
+ * same for y.  YOLO_FIT_LETTERBOX: new_w, new_h, dx, dy are darknet's letterbox_image integers; every other fit: new_w = net_w, dx = 0. */
+int yolo_segment_images_u8(yolo_ctx *ctx, const uint8_t *pixels, const yolo_image_desc *descs, int n, int fit, float thresh,
+                           uint8_t *labels_u8, const uint64_t *label_offsets);
+/* single operators.  deconv2d: x [n,h,w,cin] fp32 NHWC, w_iohw [cin][cout][size][size] (the order of darknet's weight files), bias [cout]
+ * or NULL, act a yolo_activation, dtype YOLO_FP32 / BF16 / FP16 (the operands are stored as it first), out_f32 != 0: the fp32 store of a
+ * 16-bit kernel (a map network's output layer); out [n, (h-1) stride + size - 2 padding, ..., cout] fp32 */
+int yolo_op_deconv2d(const float *x, int n, int h, int w, int cin, const float *w_iohw, const float *bias, int size, int stride, int padding,
+                     int cout, int act, int dtype, int out_f32, float *out, int device);
+/* [l2norm]: per pixel x / sqrtf(sum over the channels of x^2); an all-zero pixel is NaN, as in the reference */
+int yolo_op_l2norm(const float *x, int n, int h, int w, int c, int dtype, float *out, int device);
+/* darknet's [upsample]: nearest, out = scale * in, stride 1..8; out [n, h stride, w stride, c] */
+int yolo_op_upsample(const float *x, int n, int h, int w, int c, int stride, float scale, int dtype, float *out, int device);
+/* yolo_label_map's kernel on a host map [n,h,w,c] fp32: labels_out [n,h,w] */
+int yolo_op_label_map(const float *map, int n, int h, int w, int c, float thresh, uint8_t *labels_out, int device);
+
 #ifdef __cplusplus
 }
 #endif

@@ -90,6 +90,14 @@ class Cfg:
     def avgpool(self):
         return self._sec("avgpool")
 
+    def deconv(self, filters, size, stride, padding, bn=True, act="leaky"):
+        kv = {"batch_normalize": 1} if bn else {}
+        kv.update(filters=filters, size=size, stride=stride, padding=padding, activation=act)
+        return self._sec("deconvolutional", **kv)
+
+    def logistic(self):
+        return self._sec("logistic")
+
     def softmax(self, groups=1, temperature=None):
         kv = {"groups": groups}
         if temperature is not None:
@@ -338,8 +346,38 @@ def yolo9000(size=544, classes=9418, tree="9k.tree"):
     return c.text()
 
 
+def unet(size=416, classes=21, base=32):
+    """A U-Net-shaped map network ([net] yolo_output=map; darknet ignores the key): four 3x3 conv pairs going down by stride-2 convs
+    (base .. 8 x base channels), three 4/2/1 [deconvolutional] layers going up, each concatenated with the encoder tensor of its size
+    (the skip connections) and followed by a 3x3 conv, a linear 1x1 conv to `classes` maps at the input's size and [logistic].  For rate
+    measurements (tools/segmenter_rate.py); no trained weights exist for it."""
+    c = Cfg(size, extra=["yolo_output=map"])
+    skips = []
+    ch = base
+    c.conv(ch, 3); skips.append(c.conv(ch, 3))
+    for _ in range(3):
+        ch *= 2
+        c.conv(ch, 3, stride=2); last = c.conv(ch, 3)
+        skips.append(last)
+    skips.pop()                     # the bottleneck itself is no skip
+    for skip in reversed(skips):
+        ch //= 2
+        d = c.deconv(ch, 4, 2, 1)
+        c.route(d, skip)
+        c.conv(ch, 3)
+    c.conv(classes, 1, bn=False, act="linear")
+    c.logistic()
+    return c.text()
+
+
 def main():
     import sys
+    if len(sys.argv) > 2 and sys.argv[1] == "--unet":          # python tools/make_cfgs.py --unet DIR: unet.cfg at 416 x 416
+        os.makedirs(sys.argv[2], exist_ok=True)
+        with open(os.path.join(sys.argv[2], "unet.cfg"), "w") as f:
+            f.write(unet() + "\n")
+        print("wrote unet.cfg to", sys.argv[2])
+        return
     if len(sys.argv) > 2 and sys.argv[1] == "--yolo9000":      # python tools/make_cfgs.py --yolo9000 DIR: yolo9000.cfg + its seeded tree
         os.makedirs(sys.argv[2], exist_ok=True)
         with open(os.path.join(sys.argv[2], "9k.tree"), "w") as f:

@@ -572,6 +572,81 @@ def gen_mini_resnet():
         np.savez_compressed(os.path.join(OUT, name + ".npz"), **data)
 
 
+def _deconv(filters, size, stride, padding, bn=True, act="leaky"):
+    return "[deconvolutional]\n%sfilters=%d\nsize=%d\nstride=%d\npadding=%d\nactivation=%s\n\n" % ("batch_normalize=1\n" if bn else "", filters, size, stride, padding, act)
+
+
+def mini_unet_cfg(height=12, width=20):
+    """A U-Net in miniature, a map network ([net] yolo_output=map): two stride-2 convs down, a batch-normalised 4/2/1 deconv up whose output is
+    concatenated with the encoder's tensor of that size (the skip connection: both write into windows of the concat buffer), a conv, a
+    2/2/0 deconv with a tanh (a post-activation), a [shortcut] back to the first conv (not folded), [l2norm], darknet's [upsample] with
+    a scale, a linear 3/1/1 deconv to six classes and [logistic].  The INPUT is 12 high x 20 wide -- half of the 24 x 40 first planned:
+    at that size three images x every layer are 2.4 MB of floats that do not compress, and a committed fixture stays under 1 MB (the
+    input was shrunk, not the layer list).  The [upsample] doubles the size again, so the MAP is 24 x 40 x 6: that is what the (24, 40)
+    of the tests are."""
+    return ("[net]\nbatch=1\nwidth=%d\nheight=%d\nchannels=3\nyolo_output=map\n\n" % (width, height) + _conv(16, 3) + _conv(24, 3, 2) + _conv(40, 3, 2) +
+            _deconv(24, 4, 2, 1) + "[route]\nlayers=-1,1\n\n" + _conv(24, 3) + _deconv(16, 2, 2, 0, bn=False, act="tanh") +
+            "[shortcut]\nfrom=0\nactivation=linear\n\n[l2norm]\n\n[upsample]\nstride=2\nscale=0.5\n\n" + _deconv(6, 3, 1, 1, bn=False, act="linear") + "[logistic]\n")
+
+
+def mini_deconv_odd_cfg(height=10, width=14):
+    """The deconv shapes the U-Net leaves out, on a 10 x 14 input taken down to 3 x 4 first: 3/2/1 (phases of unequal tap counts, an odd output
+    extent: 5 x 7), an [activation] elu, 5/3/2 (13 x 19) and 1/2/0 (stride > size: three of four phases have no tap; 25 x 37)."""
+    return ("[net]\nbatch=1\nwidth=%d\nheight=%d\nchannels=3\nyolo_output=map\n\n" % (width, height) + _conv(8, 3, 2) + _conv(16, 3, 2) +
+            _deconv(12, 3, 2, 1) + "[activation]\nactivation=elu\n\n" + _deconv(8, 5, 3, 2, act="relu") + _deconv(6, 1, 2, 0, bn=False, act="linear"))
+
+
+MARGIN_TOL = 5e-4          # the fp32 bound of the network tests, as a share of the output tensor's scale
+
+
+def gen_mini_unet():
+    """mini_unet_cfg and mini_deconv_odd_cfg through the compiled reference (deconvolutional_layer.c, l2norm_layer.c, upsample_layer.c,
+    logistic_layer.c, activation_layer.c), the recipe of gen_mini_resnet: cfg text, weights, three images, every layer's output for each
+    of them (separate predicts).  Per image also `margin`, the difference of the two largest channels of every output pixel, `argmax`,
+    and `tight_share`, the share of pixels whose margin is below 2 x MARGIN_TOL x the output's scale -- the pixels a label comparison
+    must leave out; it is asserted to be at most 2 %."""
+    from oracle import darknet_ref as D
+    from yolo_tensorflow_amd import darknet_io as IO
+    for name, cfg, hw, seed in (("mini_unet", mini_unet_cfg(), (12, 20), 51), ("mini_deconv_odd", mini_deconv_odd_cfg(), (10, 14), 53)):
+        secs = IO.parse_cfg(cfg)
+        flat = IO.synth_weights(secs, seed=seed)
+        imgs = np.random.default_rng(seed + 1).integers(0, 256, (3, hw[0], hw[1], 3), dtype=np.uint8)
+        x = imgs.astype(np.float32) / np.float32(255.0)
+        if name == "mini_unet":
+            # the class deconv reads unit-norm pixels halved by the [upsample]: its filters are scaled until the reference's logits reach +-4
+            # and its biases shrunk, as gen_mini_cls scales its class conv -- the labels must not be one class everywhere
+            last = IO.conv_specs(secs)[-1]
+            nw = last["filters"] * last["cin"] * last["size"] ** 2
+            flat[-nw - last["filters"]:-nw] *= np.float32(0.2)
+            net = D.RefNet(cfg, flat, 0, 2)
+            net.predict(x[0])
+            factor = np.float32(round(4.0 / float(np.abs(net.layer_output_nhwc(net.n - 2)).max()), 2))
+            net.close()
+            flat[-nw:] *= factor
+        net = D.RefNet(cfg, flat, 0, 2)
+        outs = [[] for _ in range(net.n)]
+        for b in range(3):
+            net.predict(x[b])
+            for i in range(net.n):
+                outs[i].append(np.asarray(net.layer_output_nhwc(i), dtype=np.float32)[0])
+        data = {"cfg": np.array(cfg), "weights": flat, "images_u8": imgs}
+        for i in range(net.n):
+            data["layer_%02d" % i] = np.stack(outs[i])
+        out = data["layer_%02d" % (net.n - 1)]
+        top2 = np.sort(out, axis=-1)[..., -2:]
+        scale = float(np.abs(out).max())
+        data["margin"] = (top2[..., 1] - top2[..., 0]).astype(np.float32)
+        data["argmax"] = np.argmax(out, axis=-1).astype(np.uint8)
+        data["scale"] = np.float32(scale)
+        data["tight_share"] = (data["margin"] < 2 * MARGIN_TOL * scale).reshape(3, -1).mean(axis=1).astype(np.float32)
+        print(name, "layers", net.n, "map", out.shape[1:], "scale %.3f" % scale, "tight share per image", data["tight_share"],
+              "labels used", np.unique(data["argmax"]).tolist())
+        assert float(data["tight_share"].max()) <= 0.02, "too many near-ties: change the seed, not the cap"
+        net.close()
+        np.savez_compressed(os.path.join(OUT, name + ".npz"), **data)
+        print(name, os.path.getsize(os.path.join(OUT, name + ".npz")), "bytes")
+
+
 def gen_bn_real():
     """D2T/log.txt is the reference's stdout of two detect runs (yolov2 then yolov3) with the printf block of DN/parser.c:1176-1228
     enabled: per batch-normalised conv five lines of numbers (beta, gamma, rolling mean, rolling variance -- l.n values each -- and the
@@ -776,6 +851,8 @@ if __name__ == "__main__":
         gen_known_answers(); sys.exit(0)
     if sys.argv[1:] == ["mini_resnet"]:
         gen_mini_resnet(); sys.exit(0)
+    if sys.argv[1:] == ["mini_unet"]:
+        gen_mini_unet(); sys.exit(0)
     if sys.argv[1:] == ["darknet_py_symbols"]:
         gen_darknet_py_symbols(); sys.exit(0)
     if sys.argv[1:] == ["rect"]:
@@ -789,6 +866,7 @@ if __name__ == "__main__":
     gen_mini_local()
     gen_mini_cls()
     gen_mini_resnet()
+    gen_mini_unet()
     gen_rect()
     gen_bn_real()
     gen_known_answers()

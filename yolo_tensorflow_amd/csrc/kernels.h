@@ -221,6 +221,70 @@ hipError_t launch_conv_resblock(const BlockArgs &a, hipStream_t s);
 // exact-fp32 MFMA conv (config 2); same argument meaning, in/wt/res are float
 hipError_t launch_conv_f32(const ConvArgs &a, hipStream_t s);
 
+// ---- transposed convolution (deconv.hip; DN/deconvolutional_layer.c) ------------------------------------------------------------
+// out[f, iy * s - p + kh, ix * s - p + kw] += sum_ci w[ci, f, kh, kw] * in[ci, iy, ix], computed as a GATHER: the output splits into s x s
+// PHASES ((oy + p) mod s, (ox + p) mod s); phase (py, px) is an implicit GEMM over the taps kh = py + ty * s < size, kw = px + tx * s < size,
+// reading iy = (oy + p) / s - ty, ix = (ox + p) / s - tx (rows and columns outside the input contribute nothing).  Per phase the filters
+// are packed [cout_pad][kp], k = (ty * taps(px) + tx) * Cin_pad + ci, kp = that K rounded up to 32; a phase without taps (stride > size)
+// has kp = 0 and its pixels are act(bias).  No atomics, no col buffer, no zero-fill pass.
+#define DECONV_MAX_SIZE 7
+#define DECONV_MAX_STRIDE 4
+#define DECONV_CO_TILE 32            // output channels per workgroup: cout_pad is a multiple of it
+struct DeconvArgs {
+    const void *in; int in_stride;       // elements per input pixel; Cin_pad channels are readable
+    const void *wt;                      // the phases' filter blocks back to back, in the operand type (in_dt)
+    const float *bias;                   // [cout_pad] fp32 (BN folded)
+    void *out; int out_stride; int out_dt, in_dt;      // out_dt: in_dt, or DT_F32 (a "head": the map network's output)
+    int N, H, W, Cin_pad, Ho, Wo, Cout;
+    int Cstore;                          // channels written per pixel: Cout rounded up to the output's granule (zeros past Cout), a multiple of 4
+    int size, stride, pad, act;          // act: slope family only
+    int cout_pad;
+    int woff[DECONV_MAX_STRIDE * DECONV_MAX_STRIDE], kp[DECONV_MAX_STRIDE * DECONV_MAX_STRIDE];      // per phase py * stride + px: element offset of its block in wt, its padded K
+};
+__host__ __device__ inline int deconv_taps(int p, int size, int stride) { return p < size ? (size - p + stride - 1) / stride : 0; }
+// fills woff / kp for (size, stride, Cin_pad, cout_pad); returns the elements of all blocks together
+inline size_t deconv_layout(DeconvArgs &a)
+{
+    size_t off = 0;
+    for (int py = 0; py < a.stride; ++py) for (int px = 0; px < a.stride; ++px) {
+        const int k = deconv_taps(py, a.size, a.stride) * deconv_taps(px, a.size, a.stride) * a.Cin_pad;
+        a.kp[py * a.stride + px] = (k + 31) / 32 * 32; a.woff[py * a.stride + px] = (int)off;
+        off += (size_t)a.cout_pad * a.kp[py * a.stride + px];
+    }
+    return off;
+}
+inline bool deconv_served(int size, int stride, int pad, int h, int w)
+{
+    return size >= 1 && size <= DECONV_MAX_SIZE && stride >= 1 && stride <= DECONV_MAX_STRIDE && pad >= 0 && pad < size &&
+           (h - 1) * stride + size - 2 * pad >= 1 && (w - 1) * stride + size - 2 * pad >= 1;
+}
+// 16-bit operands: v_mfma_f32_16x16x32_{bf16,f16}, fp32 accumulators; fp32 operands: plain FMAs
+hipError_t launch_deconv(const DeconvArgs &a, hipStream_t s);
+
+// ---- the small layers of a dense-prediction network and the map outputs (map_ops.hip) ----------
+// [l2norm] (DN/blas.c:126-144): per pixel, over the channels, x / sqrtf(sum x^2); an all-zero pixel is 0 / 0 = NaN, as in the reference
+hipError_t launch_l2norm(const TView &in, const TView &out, hipStream_t s);
+// darknet's [upsample] (DN/blas.c:334-349): nearest, out[y][x] = scale * in[y / stride][x / stride]
+hipError_t launch_upsample_nearest(const TView &in, const TView &out, int stride, float scale, hipStream_t s);
+hipError_t launch_scale(const TView &x, float scale, hipStream_t s);          // x *= scale in place on the real channels
+hipError_t launch_copy_channels(const TView &in, const TView &out, hipStream_t s);      // out = in, element by element: any channel count, any strides
+// per map pixel the arg-max over the c <= 255 channels of an fp32 map (the lowest index wins a tie), 255 where the maximum is < thresh
+hipError_t launch_label_map(const float *map, int stride, size_t npix, int c, float thresh, uint8_t *labels, hipStream_t s);
+// The map pixel a native pixel takes, along one axis: native coordinate x of an image `w` wide, fitted to new_w columns at offset dx of
+// a net_w-wide input, with a map_w-wide map: floor(((2x + 1) new_w + 2 w dx) map_w / (2 w net_w)), clamped to map_w - 1 (64-bit integers)
+__host__ __device__ inline int map_coord(int x, int w, int new_w, int dx, int net_w, int map_w)
+{
+    const long long num = ((2LL * x + 1) * new_w + 2LL * w * dx) * map_w, den = 2LL * w * net_w;
+    const long long m = num / den;
+    return m > map_w - 1 ? map_w - 1 : (int)m;
+}
+struct ImgDesc;
+// labels of a ragged batch at every image's OWN size: image i's h x w labels at labels + label_off[i], each native pixel taking its map
+// pixel through the fit (map_coord; FIT_LETTERBOX: darknet's letterbox_image integers, the other fits: the stretch)
+hipError_t launch_segment_labels(const float *map, int stride, int map_h, int map_w, int c, float thresh, const ImgDesc *descs, const unsigned long long *label_off,
+                                 int n, int fit, int net_h, int net_w, uint8_t *labels, hipStream_t s);
+hipError_t launch_nhwc_to_chw(const float *in, float *out, int n, int hw, int c, hipStream_t s);      // dense fp32 [n][hw][c] -> [n][c][hw]
+
 // ---- memory-bound operators (ew_ops.hip) ------------------------------------------------------
 hipError_t launch_preprocess(const void *img, int fmt /*0 u8, 1 f32*/, int n, int hw, float scale,
                              void *out, int out_dt, int out_stride, hipStream_t s, float post_mul = 1.0f, float post_add = 0.0f);

@@ -3,6 +3,48 @@
 // artifact), yolo_run.cpp (forward / detect / timing / tile plans), yolo_ops.cpp (single operators).
 #include "yolo_ctx.h"
 
+namespace yolo_impl {
+
+int need_map(yolo_ctx *c, const char *what)
+{
+    if (c->map_layer < 0) return fail(c, YOLO_ERR_INVALID, "%s: the network is not a map network (a %s; [net] yolo_output=map declares one)", what, c->cls_layer >= 0 ? "classifier" : "detector");
+    return YOLO_OK;
+}
+
+// the map of the last forward's first n images as dense fp32 NHWC in d_map_f32 (room for max_batch images, twice: the planar copy of
+// yolo_last_layer_output* lies behind it)
+int map_to_f32(yolo_ctx *c, int n)
+{
+    const Layer &M = c->layers[c->map_layer];
+    const size_t cap = 2 * (size_t)c->max_batch * M.H * M.W * M.C;
+    if (c->map_f32_cap < cap) { HIPCK(c, hipMalloc((void **)&c->d_map_f32, cap * 4)); c->map_f32_cap = cap; }
+    TView v = M.out; v.n = n;
+    HIPCK(c, launch_to_f32(v, c->d_map_f32, c->stream));
+    return YOLO_OK;
+}
+
+// the map as fp32 rows for the label kernels: the layer's own tensor where it is fp32 (every map a conv or deconv reaches), else the dense copy
+int map_f32_view(yolo_ctx *c, int n, const float **map, int *stride)
+{
+    const Layer &M = c->layers[c->map_layer];
+    if (M.out.dt == DT_F32) { *map = (const float *)M.out.ptr; *stride = M.out.stride; return YOLO_OK; }
+    if (int r = map_to_f32(c, n)) return r;
+    *map = c->d_map_f32; *stride = M.C;
+    return YOLO_OK;
+}
+
+int map_labels_room(yolo_ctx *c, size_t bytes)
+{
+    if (bytes <= c->map_labels_cap) return YOLO_OK;
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    if (c->d_map_labels) HIPCK(c, hipFree(c->d_map_labels));
+    c->d_map_labels = nullptr; c->map_labels_cap = 0;
+    HIPCK(c, hipMalloc((void **)&c->d_map_labels, bytes)); c->map_labels_cap = bytes;
+    return YOLO_OK;
+}
+
+}  // namespace yolo_impl
+
 extern "C" {
 
 yolo_ctx *yolo_create(const yolo_config *cfg, char *err, size_t err_len)
@@ -36,7 +78,7 @@ void yolo_destroy(yolo_ctx *c)
     for (void *p : c->phys) if (p) hipFree(p);
     for (auto &L : c->layers) { if (L.d_w) hipFree(L.d_w); if (L.d_b) hipFree(L.d_b); if (L.d_sc) hipFree(L.d_sc); if (L.d_wf) hipFree(L.d_wf); if (L.d_obj) hipFree(L.d_obj); }
     void *ptrs[] = {c->input.ptr, c->d_zeros, c->d_stage, c->d_det, c->d_scores, c->d_labels, c->d_cand, c->d_keys, c->d_sbox, c->d_slabel, c->d_sscore, c->d_boxes, c->d_counts,
-                    c->d_dn_rec, c->d_dn_src, c->d_dn_count, c->d_dn_last, c->d_box4, c->s2d.ptr, c->d_srow, c->d_rows, c->d_lean_list, c->d_lean_cnt, c->d_f32a, c->d_f32b, c->d_descs, c->d_pix, c->d_cls_idx, c->d_cls_prob};
+                    c->d_dn_rec, c->d_dn_src, c->d_dn_count, c->d_dn_last, c->d_box4, c->s2d.ptr, c->d_srow, c->d_rows, c->d_lean_list, c->d_lean_cnt, c->d_f32a, c->d_f32b, c->d_descs, c->d_pix, c->d_cls_idx, c->d_cls_prob, c->d_map_f32, c->d_map_labels, c->d_label_off};
     for (void *p : ptrs) if (p) hipFree(p);
     for (auto &t : c->trees) free_tree(t);
     if (c->d_map200) hipFree(c->d_map200);
@@ -164,6 +206,7 @@ size_t yolo_last_layer_size(const yolo_ctx *c)
 {
     if (!c) return 0;
     if (c->cls_layer >= 0) return (size_t)c->layers[c->cls_layer].C;      // the [softmax] layer's probabilities
+    if (c->map_layer >= 0) { const Layer &M = c->layers[c->map_layer]; return (size_t)M.H * M.W * M.C; }      // the map, planar
     for (int i = (int)c->layers.size() - 1; i >= 0; --i) {
         const Layer &L = c->layers[i];
         if (L.type == L_DETECT) return (size_t)L.side * L.side * (L.classes + 5 * L.na);      // the layer copies its input (DN/detection_layer.c:50-57)
@@ -182,6 +225,15 @@ int yolo_last_layer_output_batch(yolo_ctx *c, int n, float *out, size_t out_floa
         if (out_floats < (size_t)n * S.C) return fail(c, YOLO_ERR_INVALID, "output buffer too small (%zu < %zu floats)", out_floats, (size_t)n * S.C);
         HIPCK(c, hipSetDevice(c->device));
         return copy_out(c, out, S.out.ptr, (size_t)n * S.C * 4, YOLO_HOST);
+    }
+    if (c->map_layer >= 0) {             // a map network: planar CHW per image, what darknet's net->output holds
+        const Layer &M = c->layers[c->map_layer];
+        const size_t per = (size_t)M.H * M.W * M.C;
+        if (out_floats < per * n) return fail(c, YOLO_ERR_INVALID, "output buffer too small (%zu < %zu floats)", out_floats, per * n);
+        HIPCK(c, hipSetDevice(c->device));
+        if (int r = map_to_f32(c, n)) return r;
+        HIPCK(c, launch_nhwc_to_chw(c->d_map_f32, c->d_map_f32 + (size_t)c->max_batch * per, n, M.H * M.W, M.C, c->stream));
+        return copy_out(c, out, c->d_map_f32 + (size_t)c->max_batch * per, per * n * 4, YOLO_HOST);
     }
     const int li = output_layer(c);
     if (li < 1 || (c->layers[li].type != L_YOLO && c->layers[li].type != L_REGION && c->layers[li].type != L_DETECT))
@@ -230,6 +282,45 @@ int yolo_head_raw(yolo_ctx *c, int head, int n, float *out, size_t out_floats)
         return YOLO_OK;
     }
     return fail(c, YOLO_ERR_INVALID, "no detection head %d", head);
+}
+
+// ---- map networks ([net] yolo_output=map) ----
+int yolo_output_map_geometry(yolo_ctx *c, int *h, int *w, int *ch)
+{
+    if (!c) return YOLO_ERR_INVALID;
+    if (int r = need_map(c, "yolo_output_map_geometry")) return r;
+    const Layer &M = c->layers[c->map_layer];
+    if (h) *h = M.H; if (w) *w = M.W; if (ch) *ch = M.C;
+    return YOLO_OK;
+}
+
+int yolo_output_map(yolo_ctx *c, int n, float *out, size_t out_floats)
+{
+    if (!c || !out) return YOLO_ERR_INVALID;
+    if (int r = need_map(c, "yolo_output_map")) return r;
+    if (c->last_n < 1 || n < 1 || n > c->last_n) return fail(c, YOLO_ERR_STATE, "yolo_output_map of %d images but the last forward ran %d", n, c->last_n);
+    const Layer &M = c->layers[c->map_layer];
+    const size_t need = (size_t)n * M.H * M.W * M.C;
+    if (out_floats < need) return fail(c, YOLO_ERR_INVALID, "output buffer too small (%zu < %zu floats)", out_floats, need);
+    HIPCK(c, hipSetDevice(c->device));
+    if (int r = map_to_f32(c, n)) return r;
+    return copy_out(c, out, c->d_map_f32, need * 4, YOLO_HOST);
+}
+
+int yolo_label_map(yolo_ctx *c, int n, float thresh, uint8_t *labels_u8)
+{
+    if (!c || !labels_u8) return YOLO_ERR_INVALID;
+    if (int r = need_map(c, "yolo_label_map")) return r;
+    if (c->last_n < 1 || n < 1 || n > c->last_n) return fail(c, YOLO_ERR_STATE, "yolo_label_map of %d images but the last forward ran %d", n, c->last_n);
+    const Layer &M = c->layers[c->map_layer];
+    if (M.C > 255) return fail(c, YOLO_ERR_UNSUPPORTED, "yolo_label_map: a map of %d channels (uint8 labels hold at most 255 classes; 255 itself means `below thresh`)", M.C);
+    HIPCK(c, hipSetDevice(c->device));
+    const size_t npix = (size_t)n * M.H * M.W;
+    const float *map = nullptr; int map_stride = 0;
+    if (int r = map_f32_view(c, n, &map, &map_stride)) return r;
+    if (int r = map_labels_room(c, npix)) return r;
+    HIPCK(c, launch_label_map(map, map_stride, npix, M.C, thresh, c->d_map_labels, c->stream));
+    return copy_out(c, labels_u8, c->d_map_labels, npix, YOLO_HOST);
 }
 
 int yolo_synchronize(yolo_ctx *c) { if (!c) return YOLO_ERR_INVALID; HIPCK(c, hipStreamSynchronize(c->stream)); return YOLO_OK; }

@@ -18,7 +18,8 @@
 
 namespace yolo_impl {
 
-enum LType { L_CONV, L_SHORTCUT, L_ROUTE, L_UPSAMPLE, L_MAXPOOL, L_REORG, L_YOLO, L_REGION, L_DETECT, L_LOCAL, L_AVGPOOL, L_SOFTMAX };
+enum LType { L_CONV, L_SHORTCUT, L_ROUTE, L_UPSAMPLE, L_MAXPOOL, L_REORG, L_YOLO, L_REGION, L_DETECT, L_LOCAL, L_AVGPOOL, L_SOFTMAX,
+             L_DECONV, L_ACTIVATE, L_L2NORM };      // [deconvolutional]; [logistic] / [activation]: k_activate over the producer's tensor; [l2norm]
 enum ConvKernel { K_TILED, K_HALO, K_S2 };      // a conv's own kernel: the tiled family (fp32 / direct / pair form picked by dtype), conv_halo_c32_c64 (3x3/s1, 32 -> 64), conv_s2_c64_c128 (3x3/s2, 64 -> 128)
 // the fused launch a conv is a member of, {members} -> launcher: conv_stem.hip {0, 1, optionally the 1x1 conv 2} -> 1; conv_stem_pair.hip (split-fp16) {0, 1} -> 1; conv_block.hip {1x1 i, 3x3 i + 1} -> i + 1; conv_c3s2.hip {conv3 i, stride-2 conv i + 2} -> i + 2 (both keep K_HALO / K_S2, the fall-back)
 enum FuseKind { F_NONE, F_STEM, F_PSTEM, F_RESBLOCK, F_C3S2 };
@@ -62,6 +63,10 @@ struct Layer {
     std::vector<int> copy_offsets;
     // pool / upsample / reorg
     int psize = 0, pstride = 0, ppad = 0;
+    float up_scale = 1.f;                // [upsample] scale= (DN/upsample_layer.c: out = scale * in)
+    // [logistic] / [activation] (L_ACTIVATE; the activation is L.act): `inplace` = the layer aliases its producer's tensor and is ONE k_activate launch over it (nobody
+    // else reads that tensor and nobody asked to keep it); else it copies into a tensor of its own first
+    bool inplace = false;
     // head
     int na = 0, classes = 0, row_off = 0;
     std::vector<float> anchors;          // masked, in reference units
@@ -108,6 +113,10 @@ struct yolo_ctx {
     // (-1: a detector); cls_topk: what the next forward's [softmax] launch selects (yolo_classify*), into d_cls_idx / d_cls_prob [max_batch][32];
     // cls_mode: the form (TREE_*) a tree classifier's output layer writes during that forward
     int cls_layer = -1, cls_topk = 0, cls_mode = 0; int *d_cls_idx = nullptr; float *d_cls_prob = nullptr;
+    // map context ([net] yolo_output=map): no detection head, no [softmax]; the output is the image-shaped tensor of map_layer, the last layer
+    // that is not [cost] (-1: not a map network).  d_map_f32: its dense fp32 copy (+ the planar one of yolo_last_layer_output*), d_map_labels:
+    // uint8 labels of yolo_label_map / yolo_segment_images_u8, d_label_off: where each image's labels begin (yolo_segment_images_u8)
+    int map_layer = -1; float *d_map_f32 = nullptr; size_t map_f32_cap = 0; uint8_t *d_map_labels = nullptr; size_t map_labels_cap = 0; unsigned long long *d_label_off = nullptr;
     // lean detect path (yolo_detect*): the decode writes scores, labels and the four box numbers of every row, not the tensor
     bool lean_cnt_dirty = false;
     void *d_lean_list = nullptr; unsigned *d_lean_cnt = nullptr;      // lean decode: list of the boxes that pass the objectness pre-filter + its counter (one word)
@@ -186,6 +195,8 @@ uint16_t f2h(float f);
 uint8_t f2e4m3(float f);
 void pack_conv(const Layer &L, const float *bn_or_bias, const float *w_oihw, int wdt, const float *in_scale,
                std::vector<uint8_t> &wbuf, std::vector<float> &bias, std::vector<float> &osc, int semantics = YOLO_SEM_TF, int split = 0);      // split: 0 plain, 1 pair input in three blocks (the image), 2 interleaved pair input
+// [deconvolutional]: w_iohw [cin][filters][k][k] (darknet's order) -> the per-phase blocks of DeconvArgs, batch norm folded as pack_conv folds it
+void pack_deconv(const Layer &L, const float *bn_or_bias, const float *w_iohw, int wdt, std::vector<uint8_t> &wbuf, std::vector<float> &bias, int semantics = YOLO_SEM_TF);
 float h2f(uint16_t h);
 void resolve_scales(yolo_ctx *c);
 void channel_scales(const yolo_ctx *c, int idx, std::vector<float> &out);
@@ -206,17 +217,23 @@ int allocate(yolo_ctx *c);
 TView view_of(const yolo_ctx *c, int idx);
 // yolo_run.cpp
 ConvArgs conv_args(const yolo_ctx *c, const Layer &L, int n);
+DeconvArgs deconv_geometry(int size, int stride, int pad, int h, int w, int cin_pad, int filters, int act, int in_dt);      // everything of DeconvArgs but pointers, strides, N, out_dt, Cstore
 int run_layer(yolo_ctx *c, int i, int n);
 int stage_in(yolo_ctx *c, const void *images, int n, int fmt, int loc, float scale);
 int run_network(yolo_ctx *c, int n, bool lean = false);
 int copy_out(yolo_ctx *c, void *dst, const void *src, size_t bytes, int loc);
 int output_layer(const yolo_ctx *c);      // the network's output: the last layer that is not [cost] (DN/network.c:699-706)
-int need_detector(yolo_ctx *c, const char *what);      // YOLO_ERR_INVALID with a message for a classifier context
+int need_detector(yolo_ctx *c, const char *what);      // YOLO_ERR_INVALID with a message for a classifier or a map context
 int post_args_ok(yolo_ctx *c, int max_out, int nms_mode, int select_mode);
 struct PostGeom { int fit, pixels; };      // per-image box mapping of a ragged batch (yolo_box_units), over c->d_descs
 int post(yolo_ctx *c, const float *det, int n, int rows, int attrs, float score_thr, float iou_thr, int max_out,
          int nms_mode, int select_mode, int img_h, int img_w, int scores_ready, yolo_box *boxes_out, int32_t *counts_out, int out_loc, int32_t *rows_out = nullptr,
          const PostGeom *geom = nullptr);
+// yolo_api.cpp: map networks
+int need_map(yolo_ctx *c, const char *what);      // YOLO_ERR_INVALID with a message for a detector or a classifier context
+int map_to_f32(yolo_ctx *c, int n);
+int map_f32_view(yolo_ctx *c, int n, const float **map, int *stride);
+int map_labels_room(yolo_ctx *c, size_t bytes);
 // yolo_ops.cpp
 extern thread_local std::string g_op_err;
 TView make_view(void *p, int n, int h, int w, int c, int stride, int dt);

@@ -243,6 +243,72 @@ int yolo_op_conv2d(const float *x, int n, int h, int w, int cin, const float *w_
     return S.rc;
 }
 
+// darknet's [deconvolutional] on host tensors: x [n,h,w,cin] fp32 NHWC, w_iohw [cin][cout][size][size] (the order of darknet's weight files), bias
+// [cout] or NULL.  The operands are stored as `dtype` first; out_f32 != 0: the fp32 ("head") store of a 16-bit kernel.  An activation
+// outside the slope family runs as the planner plans it: a linear epilogue, then k_activate on the output.
+int yolo_op_deconv2d(const float *x, int n, int h, int w, int cin, const float *w_iohw, const float *bias, int size, int stride, int padding,
+                     int cout, int act, int dtype, int out_f32, float *out, int device)
+{
+    if (!x || !w_iohw || !out || n < 1 || h < 1 || w < 1 || cin < 1 || cout < 1 || act < 0 || act >= ACT_COUNT) { g_op_err = "deconv2d: bad arguments"; return YOLO_ERR_INVALID; }
+    if (dtype != YOLO_FP32 && dtype != YOLO_BF16 && dtype != YOLO_FP16) { g_op_err = "deconv2d: dtype (fp32, bf16 or fp16; the fp8 and split-fp16 configurations do not serve [deconvolutional])"; return YOLO_ERR_UNSUPPORTED; }
+    if (!deconv_served(size, stride, padding, h, w)) { g_op_err = "deconv2d: served are 1 <= size <= 7, 1 <= stride <= 4, 0 <= padding < size and a positive output"; return YOLO_ERR_UNSUPPORTED; }
+    OpScope S(device); if (S.rc) { g_op_err = "deconv2d: no HIP device"; return S.rc; }
+    const int dt = dtype == YOLO_FP32 ? DT_F32 : dtype == YOLO_FP16 ? DT_F16 : DT_BF16, odt = (out_f32 || dt == DT_F32) ? DT_F32 : dt;
+    Layer L; L.type = L_DECONV; L.filters = cout; L.size = size; L.stride = stride; L.pad = padding; L.bn = 0; L.in_dt = dt;
+    L.cin = cin; L.cin_pad = roundup(cin, 8); L.cout_pad = roundup(cout, DECONV_CO_TILE);
+    DeconvArgs a = deconv_geometry(size, stride, padding, h, w, L.cin_pad, cout, act_is_slope(act) ? act : ACT_LINEAR, dt);
+    std::vector<float> b0(cout, 0.f); if (bias) memcpy(b0.data(), bias, (size_t)cout * 4);
+    std::vector<uint8_t> wbuf; std::vector<float> bv; pack_deconv(L, b0.data(), w_iohw, dt, wbuf, bv);
+    const int cs = roundup(cout, odt == DT_F32 && dt != DT_F32 ? 4 : 8);
+    const size_t pin = (size_t)n * h * w, pout = (size_t)n * a.Ho * a.Wo;
+    void *d_w = S.upload(wbuf.data(), wbuf.size()); float *d_b = (float *)S.upload(bv.data(), bv.size() * 4);
+    float *d_x32 = (float *)S.upload(x, pin * cin * 4);
+    void *d_x = S.alloc(pin * L.cin_pad * dt_size(dt)), *d_o = S.alloc(pout * cs * dt_size(odt)); float *d_o32 = (float *)S.alloc(pout * cout * 4);
+    if (S.rc) { g_op_err = "deconv2d: allocation failed"; return S.rc; }
+    if (!S.ok(launch_from_f32(d_x32, make_view(d_x, n, h, w, cin, L.cin_pad, dt), S.s))) { g_op_err = S.err; return S.rc; }
+    a.in = d_x; a.in_stride = L.cin_pad; a.wt = d_w; a.bias = d_b; a.out = d_o; a.out_stride = cs; a.out_dt = odt; a.N = n; a.Cstore = cs;
+    const TView vo = make_view(d_o, n, a.Ho, a.Wo, cout, cs, odt);
+    if (!S.ok(launch_deconv(a, S.s))) { g_op_err = "deconv2d launch: " + S.err; return S.rc; }
+    if (!act_is_slope(act) && !S.ok(launch_activate(vo, false, act, S.s))) { g_op_err = "deconv2d activation: " + S.err; return S.rc; }
+    if (!S.ok(launch_to_f32(vo, d_o32, S.s))) { g_op_err = S.err; return S.rc; }
+    S.download(out, d_o32, pout * cout * 4);
+    if (S.rc) g_op_err = "deconv2d: " + std::string(hipGetErrorString(hipGetLastError()));
+    return S.rc;
+}
+
+int yolo_op_l2norm(const float *x, int n, int h, int w, int c, int dtype, float *out, int device)
+{
+    if (!x || !out || n < 1 || h < 1 || w < 1 || c < 1) { g_op_err = "l2norm: bad arguments"; return YOLO_ERR_INVALID; }
+    if (dtype != YOLO_FP32 && dtype != YOLO_BF16 && dtype != YOLO_FP16) { g_op_err = "l2norm: dtype (fp32, bf16 or fp16)"; return YOLO_ERR_UNSUPPORTED; }
+    OpScope S(device); if (S.rc) { g_op_err = "l2norm: no HIP device"; return S.rc; }
+    OpTensor a, o;
+    if (!op_tensor(S, x, n, h, w, c, dtype, a) || !op_tensor(S, nullptr, n, h, w, c, dtype, o) || !S.ok(launch_l2norm(a.v, o.v, S.s)) || op_tensor_out(S, o, out)) { g_op_err = "l2norm: " + (S.err.empty() ? std::string("allocation or copy failed") : S.err); return S.rc ? S.rc : YOLO_ERR_HIP; }
+    return YOLO_OK;
+}
+
+int yolo_op_upsample(const float *x, int n, int h, int w, int c, int stride, float scale, int dtype, float *out, int device)
+{
+    if (!x || !out || n < 1 || h < 1 || w < 1 || c < 1) { g_op_err = "upsample: bad arguments"; return YOLO_ERR_INVALID; }
+    if (stride < 1 || stride > 8) { g_op_err = "upsample: stride (1..8; a stride below 1 is darknet's reverse mode, which is not served)"; return YOLO_ERR_UNSUPPORTED; }
+    if (dtype != YOLO_FP32 && dtype != YOLO_BF16 && dtype != YOLO_FP16) { g_op_err = "upsample: dtype (fp32, bf16 or fp16)"; return YOLO_ERR_UNSUPPORTED; }
+    OpScope S(device); if (S.rc) { g_op_err = "upsample: no HIP device"; return S.rc; }
+    OpTensor a, o;
+    if (!op_tensor(S, x, n, h, w, c, dtype, a) || !op_tensor(S, nullptr, n, h * stride, w * stride, c, dtype, o) || !S.ok(launch_upsample_nearest(a.v, o.v, stride, scale, S.s)) || op_tensor_out(S, o, out)) { g_op_err = "upsample: " + (S.err.empty() ? std::string("allocation or copy failed") : S.err); return S.rc ? S.rc : YOLO_ERR_HIP; }
+    return YOLO_OK;
+}
+
+int yolo_op_label_map(const float *map, int n, int h, int w, int c, float thresh, uint8_t *labels_out, int device)
+{
+    if (!map || !labels_out || n < 1 || h < 1 || w < 1 || c < 1) { g_op_err = "label_map: bad arguments"; return YOLO_ERR_INVALID; }
+    if (c > 255) { g_op_err = "label_map: a map of " + std::to_string(c) + " channels (uint8 labels hold at most 255 classes; 255 itself means `below thresh`)"; return YOLO_ERR_UNSUPPORTED; }
+    OpScope S(device); if (S.rc) { g_op_err = "label_map: no HIP device"; return S.rc; }
+    const size_t npix = (size_t)n * h * w;
+    const float *d_m = (const float *)S.upload(map, npix * c * 4); uint8_t *d_l = (uint8_t *)S.alloc(npix);
+    if (S.rc) { g_op_err = "label_map: allocation failed"; return S.rc; }
+    if (!S.ok(launch_label_map(d_m, c, npix, c, thresh, d_l, S.s))) { g_op_err = "label_map: " + S.err; return S.rc; }
+    return S.download(labels_out, d_l, npix);
+}
+
 static int ew_op(int kind, const float *x, int n, int h, int w, int c, int p0, int p1, int p2, float *out, int device)
 {
     if (!x || !out || c % 8) { g_op_err = "op: bad arguments (channels must be a multiple of 8)"; return YOLO_ERR_INVALID; }

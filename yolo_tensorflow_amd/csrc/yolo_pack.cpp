@@ -123,6 +123,34 @@ void pack_conv(const Layer &L, const float *bn_or_bias, const float *w_oihw, int
     }
 }
 
+// [deconvolutional]: batch norm folded as pack_conv folds it, then one filter block per output phase (DeconvArgs, kernels.h): phase
+// (py, px) holds the taps kh = py + ty * stride, kw = px + tx * stride as rows [cout_pad][kp], k = (ty * taps(px) + tx) * cin_pad + ci
+void pack_deconv(const Layer &L, const float *bn_or_bias, const float *w_iohw, int wdt, std::vector<uint8_t> &wbuf, std::vector<float> &bias, int semantics)
+{
+    const int n = L.filters, k = L.size, cin = L.cin, st = L.stride;
+    bias.assign(L.cout_pad, 0.f);
+    std::vector<float> scale(n, 1.f);
+    if (L.bn) {
+        const float *beta = bn_or_bias, *gamma = beta + n, *mean = gamma + n, *var = mean + n;
+        for (int o = 0; o < n; ++o) {
+            const float s = semantics == YOLO_SEM_DARKNET ? gamma[o] / (sqrtf(var[o]) + 1e-6f) : gamma[o] / sqrtf(var[o] + 1e-5f);
+            scale[o] = s; bias[o] = beta[o] - mean[o] * s;
+        }
+    } else for (int o = 0; o < n; ++o) bias[o] = bn_or_bias[o];
+    DeconvArgs g; memset(&g, 0, sizeof g); g.size = k; g.stride = st; g.Cin_pad = L.cin_pad; g.cout_pad = L.cout_pad;
+    const size_t es = dt_size(wdt), total = deconv_layout(g);
+    wbuf.assign(total * es, 0);
+    for (int kh = 0; kh < k; ++kh) for (int kw = 0; kw < k; ++kw) {
+        const int py = kh % st, px = kw % st, phase = py * st + px, tap = (kh / st) * deconv_taps(px, k, st) + kw / st;
+        for (int o = 0; o < n; ++o) for (int ci = 0; ci < cin; ++ci) {
+            const float v = w_iohw[(((size_t)ci * n + o) * k + kh) * k + kw] * scale[o];
+            const size_t idx = (size_t)g.woff[phase] + (size_t)o * g.kp[phase] + (size_t)tap * L.cin_pad + ci;
+            if (wdt == DT_F32) memcpy(&wbuf[idx * 4], &v, 4);
+            else { const uint16_t b = wdt == DT_F16 ? f2h(v) : f2bf(v); memcpy(&wbuf[idx * 2], &b, 2); }
+        }
+    }
+}
+
 // fp8: scale of the tensor each layer's view holds, and per-input-channel scales of a conv
 void resolve_scales(yolo_ctx *c)
 {
@@ -232,6 +260,14 @@ int yolo_set_weights(yolo_ctx *c, const float *flat, size_t n)
             HIPCK(c, hipMemcpy(L.d_b, b.data(), b.size() * 4, hipMemcpyHostToDevice));
             continue;
         }
+        if (L.type == L_DECONV) {          // the file: as a conv's, [bias | beta gamma mean var] then cin * filters * size^2 filters (DN/parser.c load_convolutional_weights)
+            const float *params = p; p += (size_t)L.filters * (L.bn ? 4 : 1);
+            const float *w = p; p += (size_t)L.cin * L.filters * L.size * L.size;
+            pack_deconv(L, params, w, L.in_dt, wbuf, bias, c->semantics);
+            HIPCK(c, hipMemcpy(L.d_w, wbuf.data(), wbuf.size(), hipMemcpyHostToDevice));
+            HIPCK(c, hipMemcpy(L.d_b, bias.data(), bias.size() * 4, hipMemcpyHostToDevice));
+            continue;
+        }
         if (L.type != L_CONV) continue;
         const float *params = p; p += (size_t)L.filters * (L.bn ? 4 : 1);
         const float *w = p; p += (size_t)L.filters * L.cin * L.size * L.size;
@@ -330,7 +366,7 @@ int yolo_export(yolo_ctx *c, const char *path)
     for (auto &t : c->trees) { const uint32_t len[2] = {(uint32_t)t.path.size(), (uint32_t)t.text.size()}; w.put(len, sizeof len); w.put(t.path.data(), t.path.size()); w.put(t.text.data(), t.text.size()); }
     std::vector<uint8_t> buf;
     for (auto &L : c->layers) {
-        if (L.type != L_CONV && L.type != L_LOCAL) continue;
+        if (L.type != L_CONV && L.type != L_LOCAL && L.type != L_DECONV) continue;
         uint64_t sz[3] = {(uint64_t)L.cout_pad * L.kpad * dt_size(L.in_dt), (uint64_t)L.cout_pad, L.d_sc ? (uint64_t)L.cout_pad : 0};
         if (L.type == L_LOCAL) { sz[0] = (uint64_t)L.H * L.W * L.filters * L.size * L.size * L.cin * dt_size(L.in_dt); sz[1] = (uint64_t)L.H * L.W * L.filters; sz[2] = 0; }
         w.put(sz, sizeof sz);
@@ -386,7 +422,7 @@ yolo_ctx *yolo_create_from_file(const char *path, int max_batch, int device, voi
     if (c->dtype == YOLO_FP8 && yolo_set_act_scales(c, sc.data(), (int)hd.n_layers) != YOLO_OK) { fclose(f); return bail(c, c->err); }
     std::vector<uint8_t> buf;
     for (auto &L : c->layers) {
-        if (L.type != L_CONV && L.type != L_LOCAL) continue;
+        if (L.type != L_CONV && L.type != L_LOCAL && L.type != L_DECONV) continue;
         uint64_t sz[3]; r.get(sz, sizeof sz);
         uint64_t want[3] = {(uint64_t)L.cout_pad * L.kpad * dt_size(L.in_dt), (uint64_t)L.cout_pad, L.d_sc ? (uint64_t)L.cout_pad : 0};
         if (L.type == L_LOCAL) { want[0] = (uint64_t)L.H * L.W * L.filters * L.size * L.size * L.cin * dt_size(L.in_dt); want[1] = (uint64_t)L.H * L.W * L.filters; want[2] = 0; }

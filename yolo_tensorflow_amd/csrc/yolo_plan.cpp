@@ -195,9 +195,43 @@ int build_plan(yolo_ctx *c, const std::vector<Section> &secs)
                 C += c2;
             }
         } else if (s.type == "upsample") {
-            L.type = L_UPSAMPLE; L.pstride = opt_i(s, "stride", 2);
-            if (L.pstride != 2) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: upsample stride %d", i, L.pstride);
-            H *= 2; W *= 2;
+            // TF semantics: the 2x bilinear closed form only.  darknet semantics (DN/upsample_layer.c): nearest, any stride 1..8; a stride
+            // below 1 is darknet's reverse mode, which is not served.  scale= (out = scale * in) in both
+            L.type = L_UPSAMPLE; L.pstride = opt_i(s, "stride", 2); L.up_scale = (float)atof(opt_s(s, "scale", "1").c_str());
+            if (c->semantics == YOLO_SEM_DARKNET ? (L.pstride < 1 || L.pstride > 8) : L.pstride != 2) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: upsample stride %d", i, L.pstride);
+            if ((L.pstride != 2 || L.up_scale != 1.f) && (c->dtype == YOLO_FP8 || c->split()))
+                return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [upsample] with a stride other than 2 or a scale is not served in the fp8 / split-fp16 configurations", i);
+            H *= L.pstride; W *= L.pstride;
+        } else if (s.type == "deconvolutional") {
+            // transposed convolution (DN/deconvolutional_layer.c, DN/parser.c:151-174): its own kernel (deconv.hip), never a member of a fused
+            // launch, neither end of a 1x1 tail, and a [shortcut] behind it is not folded into it -- every marking pass asks for L_CONV
+            if (c->dtype == YOLO_FP8) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [deconvolutional] is not served in the fp8 configuration", i);
+            if (c->split()) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [deconvolutional] is not served in the split-fp16 configuration", i);
+            L.type = L_DECONV; L.filters = opt_i(s, "filters", 1); L.size = opt_i(s, "size", 1); L.stride = opt_i(s, "stride", 1);
+            L.pad = opt_i(s, "pad", 0) ? L.size / 2 : opt_i(s, "padding", 0);
+            L.bn = opt_i(s, "batch_normalize", 0);
+            if (L.size < 1 || L.size > DECONV_MAX_SIZE) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: deconv size %d (1..%d are served)", i, L.size, DECONV_MAX_SIZE);
+            if (L.stride < 1 || L.stride > DECONV_MAX_STRIDE) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: deconv stride %d (1..%d are served)", i, L.stride, DECONV_MAX_STRIDE);
+            if (L.pad < 0 || L.pad >= L.size) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: deconv padding %d must be below its size %d", i, L.pad, L.size);
+            if (L.filters < 1) return fail(c, YOLO_ERR_INVALID, "layer %d: deconv filters %d", i, L.filters);
+            const int ho = (H - 1) * L.stride + L.size - 2 * L.pad, wo = (W - 1) * L.stride + L.size - 2 * L.pad;
+            if (ho < 1 || wo < 1) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: deconv output %d x %d is not positive", i, wo, ho);
+            if (int r = plan_activation(c, i, s, "logistic", false)) return r;
+            L.in_dt = c->act_dt(); L.store_dt = c->act_dt();
+            L.cin = C; L.cin_pad = roundup(C, 8); L.cout_pad = roundup(L.filters, DECONV_CO_TILE);
+            { DeconvArgs g; memset(&g, 0, sizeof g); g.size = L.size; g.stride = L.stride; g.Cin_pad = L.cin_pad; g.cout_pad = L.cout_pad; L.kpad = (int)(deconv_layout(g) / L.cout_pad); }      // (the K of all phases together: cout_pad * kpad elements of filters)
+            c->conv_flops += 2.0 * L.size * L.size * L.cin * L.filters * (double)H * W;
+            c->weights_count += (size_t)L.filters * (L.bn ? 4 : 1) + (size_t)L.cin * L.filters * L.size * L.size;
+            H = ho; W = wo; C = L.filters;
+        } else if (s.type == "logistic" || s.type == "activation") {
+            // DN/logistic_layer.c, DN/activation_layer.c: activate_array over a copy of the input -- here k_activate over the producer's tensor
+            if (c->dtype == YOLO_FP8) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [%s] is not served in the fp8 configuration", i, s.type.c_str());
+            L.type = L_ACTIVATE;
+            if (s.type == "logistic") L.act = ACT_LOGISTIC;
+            else if (int r = plan_activation(c, i, s, "linear", true)) return r;
+        } else if (s.type == "l2norm") {
+            if (c->dtype == YOLO_FP8 || c->split()) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [l2norm] is not served in the fp8 / split-fp16 configurations", i);
+            L.type = L_L2NORM;
         } else if (s.type == "maxpool") {
             L.type = L_MAXPOOL; L.pstride = opt_i(s, "stride", 1); L.psize = opt_i(s, "size", L.pstride);
             L.ppad = opt_i(s, "padding", (L.psize - 1) / 2);
@@ -260,7 +294,7 @@ int build_plan(yolo_ctx *c, const std::vector<Section> &secs)
             return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: section [%s] is outside the inference hot path", i, s.type.c_str());
         }
         L.H = H; L.W = W; L.C = C;
-        if (L.type != L_CONV && L.type != L_LOCAL) {
+        if (L.type != L_CONV && L.type != L_LOCAL && L.type != L_DECONV) {
             // layers that move data keep the type of what they move; their operands must agree
             int dt = -1;
             for (int j : L.in) { const int dj = j < 0 ? c->act_dt() : c->layers[j].store_dt; if (dt >= 0 && dj != dt && (L.type == L_ROUTE || L.type == L_SHORTCUT)) return fail(c, YOLO_ERR_INVALID, "layer %d: operands stored in different types (yolo_store): a %s needs one type", i, L.type == L_ROUTE ? "route" : "shortcut"); if (dt < 0) dt = dj; }
@@ -288,11 +322,26 @@ int build_plan(yolo_ctx *c, const std::vector<Section> &secs)
                 return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [softmax] must follow a [convolutional] / [connected] layer, directly or through one [avgpool] (fp32 logits)", i);
         }
     }
+    // the third kind is declared, [net] yolo_output=map: the output is the image-shaped tensor of the last layer that is not [cost]
+    const std::string out_kind = opt_s(net, "yolo_output", "");
+    if (!out_kind.empty() && out_kind != "map") return fail(c, YOLO_ERR_INVALID, "cfg: yolo_output=%s (the one value is `map`)", out_kind.c_str());
+    if (!out_kind.empty() && c->rows) return fail(c, YOLO_ERR_INVALID, "cfg: yolo_output=map on a network with a [yolo] / [region] / [detection] head");
     if (c->rows == 0) {          // no detection head: a classifier when the output layer (the last one that is not [cost]) is a [softmax]
         int o = NL - 1;
         while (o >= 0 && c->layers[o].cost) --o;
+        if (!out_kind.empty()) {
+            if (o < 0 || c->layers[o].type == L_SOFTMAX) return fail(c, YOLO_ERR_INVALID, "cfg: yolo_output=map on a network whose output layer is a [softmax] (a classifier)");
+            c->map_layer = o;
+            // the map is never rounded to 16 bits: the computing layer that reaches it directly or through [logistic] / [activation] layers writes
+            // fp32, and so do those (the `head` flag, as for logits)
+            int p = o;
+            while (p >= 0 && c->layers[p].type == L_ACTIVATE) { c->layers[p].head = true; c->layers[p].pair = false; p = c->layers[p].in[0]; }
+            if (p >= 0 && (c->layers[p].type == L_CONV || c->layers[p].type == L_DECONV)) { c->layers[p].head = true; c->layers[p].pair = false; }
+            else for (int q = o; q >= 0 && q != p; q = c->layers[q].in[0]) c->layers[q].head = false;      // (nothing computes in front of them: they keep their producer's type)
+        } else {
         if (o < 0 || c->layers[o].type != L_SOFTMAX) return fail(c, YOLO_ERR_INVALID, "cfg has no [yolo] / [region] / [detection] head");
         c->cls_layer = o;
+        }
     }
     c->in_mul = (float)atof(opt_s(net, "yolo_input_mul", "1").c_str()); c->in_add = (float)atof(opt_s(net, "yolo_input_add", "0").c_str());
     if (c->rows > 32768) return fail(c, YOLO_ERR_UNSUPPORTED, "more than 32768 candidates per image");
@@ -389,6 +438,20 @@ int build_plan(yolo_ctx *c, const std::vector<Section> &secs)
                      P.size == 3 && P.residual_from < -1 && T.act == ACT_LINEAR && T.in_dt == P.in_dt && (T.in_dt == DT_BF16 || T.in_dt == DT_F16) && j + 1 < NL && c->layers[j + 1].type == L_YOLO) { P.tail_layer = j; T.fused_into = i; }
         }
     }
+    // [logistic] / [activation]: one k_activate launch over the producer's own tensor where this layer is that tensor's only reader, nobody asked
+    // to keep every layer, and neither tensor is a window of a concatenation; else a tensor of its own, copied first
+    for (int i = 0; i < NL; ++i) {
+        Layer &L = c->layers[i];
+        if (L.type != L_ACTIVATE) continue;
+        const int j = L.in[0];
+        bool routed = false;
+        for (int r = i + 1; r < NL; ++r) if (c->layers[r].type == L_ROUTE && c->layers[r].in.size() >= 2) for (int q : c->layers[r].in) routed |= q == i;
+        if (j >= 0 && c->layers[j].head != L.head) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [logistic] / [activation] of a detection head's fp32 tensor", i);
+        if (j < 0 || c->keep_layers || routed || uses[j] != 1) continue;
+        const Layer &P = c->layers[j];
+        L.inplace = (P.type == L_CONV || P.type == L_DECONV || P.type == L_LOCAL || P.type == L_SHORTCUT || P.type == L_L2NORM || P.type == L_UPSAMPLE || P.type == L_MAXPOOL ||
+                     P.type == L_ACTIVATE) && !never_stored(P, j);
+    }
     // storage assignment: st_of[i] = storage holding layer i's output
     std::vector<int> place_route(NL, -1), place_off(NL, 0);
     for (int i = 0; i < NL; ++i) {
@@ -428,6 +491,7 @@ int build_plan(yolo_ctx *c, const std::vector<Section> &secs)
         if (L.type == L_ROUTE) continue;
         if (never_stored(L, i) && !fused_may_fall_back(L)) { L.noop = true; continue; }               // lives in LDS only; a group that may fall back keeps its members' storage
         if (L.type == L_SOFTMAX) { L.storage = new_storage(L.C, DT_F32, (size_t)c->max_batch, true); continue; }      // dense [n][C] probabilities
+        if (L.type == L_ACTIVATE && L.inplace) { L.storage = c->layers[L.in[0]].storage; L.ch_off = c->layers[L.in[0]].ch_off; continue; }
         if (place_route[i] >= 0) { L.storage = c->layers[place_route[i]].storage; L.ch_off = place_off[i]; }
         else if (L.head) L.storage = new_storage(roundup(L.C, 4), DT_F32, (size_t)c->max_batch * L.H * L.W, true);
         else L.storage = new_storage(L.pair ? pair_width(L.C) : roundup(L.C, gran_of(L.store_dt)), L.store_dt, (size_t)c->max_batch * L.H * L.W, c->keep_layers);
@@ -523,8 +587,8 @@ int allocate(yolo_ctx *c)
     HIPCK(c, hipMalloc(&c->d_stage, c->stage_bytes));
     HIPCK(c, hipMalloc((void **)&c->d_descs, (size_t)c->max_batch * sizeof(ImgDesc)));      // ragged batches: one descriptor per image
     size_t nr = (size_t)c->max_batch * c->rows;
-    if (c->cls_layer >= 0) {             // a classifier has no candidate rows: the detection workspace is one element each
-        nr = 1;
+    if (c->rows == 0) nr = 1;            // a classifier or a map network has no candidate rows: the detection workspace is one element each
+    if (c->cls_layer >= 0) {
         HIPCK(c, hipMalloc((void **)&c->d_cls_idx, (size_t)c->max_batch * CLS_TOPK_MAX * 4)); HIPCK(c, hipMalloc((void **)&c->d_cls_prob, (size_t)c->max_batch * CLS_TOPK_MAX * 4));
     }
     HIPCK(c, hipMalloc((void **)&c->d_det, nr * (c->attrs ? c->attrs : 1) * 4));
@@ -552,7 +616,7 @@ int allocate(yolo_ctx *c)
     HIPCK(c, hipMalloc((void **)&c->d_sbox, nr * 16)); HIPCK(c, hipMalloc((void **)&c->d_slabel, nr * 4)); HIPCK(c, hipMalloc((void **)&c->d_sscore, nr * 4));
     HIPCK(c, hipMalloc((void **)&c->d_counts, (size_t)c->max_batch * 4));
     // filters
-    for (auto &L : c->layers) if (L.type == L_CONV) {
+    for (auto &L : c->layers) if (L.type == L_CONV || L.type == L_DECONV) {
         size_t wb = (size_t)L.cout_pad * L.kpad * dt_size(L.in_dt);
         HIPCK(c, hipMalloc(&L.d_w, wb)); HIPCK(c, hipMemsetAsync(L.d_w, 0, wb, c->stream));
         HIPCK(c, hipMalloc((void **)&L.d_b, (size_t)L.cout_pad * 4)); HIPCK(c, hipMemsetAsync(L.d_b, 0, (size_t)L.cout_pad * 4, c->stream));

@@ -50,6 +50,26 @@ ConvArgs conv_args(const yolo_ctx *c, const Layer &L, int n)
     return a;
 }
 
+DeconvArgs deconv_geometry(int size, int stride, int pad, int h, int w, int cin_pad, int filters, int act, int in_dt)
+{
+    DeconvArgs a; memset(&a, 0, sizeof a);
+    a.size = size; a.stride = stride; a.pad = pad; a.H = h; a.W = w; a.Cin_pad = cin_pad; a.Cout = filters; a.act = act; a.in_dt = in_dt;
+    a.Ho = (h - 1) * stride + size - 2 * pad; a.Wo = (w - 1) * stride + size - 2 * pad;
+    a.cout_pad = roundup(filters, DECONV_CO_TILE);
+    deconv_layout(a);
+    return a;
+}
+
+static DeconvArgs deconv_args(const yolo_ctx *c, const Layer &L, int n)
+{
+    const TView in = view_of(c, L.in[0]);
+    DeconvArgs a = deconv_geometry(L.size, L.stride, L.pad, in.h, in.w, L.cin_pad, L.filters, L.act, L.in_dt);
+    a.in = in.ptr; a.in_stride = in.stride; a.wt = L.d_w; a.bias = L.d_b; a.out = L.out.ptr; a.out_stride = L.out.stride; a.out_dt = L.out.dt; a.N = n;
+    // zeros in the channels past the filters, up to the granule of the output's type (a window of a concat buffer holds whole granules)
+    a.Cstore = std::min(L.out.stride, roundup(L.filters, L.out.dt == DT_F32 && L.head ? 4 : 8));
+    return a;
+}
+
 // split fp16: a layer that moves or interpolates values runs in fp32 between a join (hi + lo) and a split
 static int via_f32(yolo_ctx *c, const Layer &L, int n, int kind)
 {
@@ -244,7 +264,30 @@ int run_layer(yolo_ctx *c, int i, int n)
         HIPCK(c, launch_local(nview(view_of(c, L.in[0])), nview(L.out), L.d_w, L.d_b, L.size, L.stride, L.pad, L.act, s));
         if (L.post_act != ACT_LINEAR) HIPCK(c, launch_activate(nview(L.out), false, L.post_act, s));
         break;
-    case L_UPSAMPLE: if (L.pair) { if (getenv("YOLO_PAIR_UPSAMPLE_VIA_F32")) { if (int r = via_f32(c, L, n, 0)) return r; } else HIPCK(c, launch_upsample2x_pair(nview(view_of(c, L.in[0])), nview(L.out), c->semantics == YOLO_SEM_TF, s)); break; } HIPCK(c, launch_upsample2x(nview(view_of(c, L.in[0])), nview(L.out), c->semantics == YOLO_SEM_TF, s)); break;
+    case L_DECONV:
+        HIPCK(c, launch_deconv(deconv_args(c, L, n), s));
+        if (L.post_act != ACT_LINEAR) HIPCK(c, launch_activate(nview(L.out), false, L.post_act, s));
+        break;
+    case L_ACTIVATE: {
+        TView out = nview(L.out);
+        if (!L.inplace) {          // a tensor of its own (keep_layers, a second reader of the producer, a concat window): copied first
+            // whole granules: the channels C .. of the last one are the producer's zeros, not what the pooled buffer's last tenant left there
+            // (a consumer multiplies them by zero filters, and 0 * Inf is NaN)
+            TView src = nview(view_of(c, L.in[0])), dst = out;
+            src.c = dst.c = L.pair ? pair_width(L.C) : std::min(std::min(src.stride, dst.stride), roundup(L.C, out.dt == DT_F32 && L.head ? 4 : 8));
+            HIPCK(c, launch_copy_channels(src, dst, s));
+        }
+        HIPCK(c, launch_activate(out, L.pair, L.act, s));
+        break; }
+    case L_L2NORM: HIPCK(c, launch_l2norm(nview(view_of(c, L.in[0])), nview(L.out), s)); break;
+    case L_UPSAMPLE:
+        if (L.pstride != 2 || L.up_scale != 1.f) {          // (never pairs: the planner refuses these in the split-fp16 configuration)
+            if (c->semantics == YOLO_SEM_DARKNET) { HIPCK(c, launch_upsample_nearest(nview(view_of(c, L.in[0])), nview(L.out), L.pstride, L.up_scale, s)); break; }
+            HIPCK(c, launch_upsample2x(nview(view_of(c, L.in[0])), nview(L.out), 1, s));
+            HIPCK(c, launch_scale(nview(L.out), L.up_scale, s));
+            break;
+        }
+        if (L.pair) { if (getenv("YOLO_PAIR_UPSAMPLE_VIA_F32")) { if (int r = via_f32(c, L, n, 0)) return r; } else HIPCK(c, launch_upsample2x_pair(nview(view_of(c, L.in[0])), nview(L.out), c->semantics == YOLO_SEM_TF, s)); break; } HIPCK(c, launch_upsample2x(nview(view_of(c, L.in[0])), nview(L.out), c->semantics == YOLO_SEM_TF, s)); break;
     case L_MAXPOOL: if (L.pair) { if (int r = via_f32(c, L, n, 1)) return r; break; } HIPCK(c, launch_maxpool(nview(view_of(c, L.in[0])), nview(L.out), L.psize, L.pstride, L.ppad, s)); break;
     case L_REORG: if (L.pair) { if (int r = via_f32(c, L, n, 2)) return r; break; } HIPCK(c, launch_reorg(nview(view_of(c, L.in[0])), nview(L.out), L.pstride, c->semantics == YOLO_SEM_DARKNET, s)); break;
     case L_AVGPOOL: {
@@ -342,6 +385,7 @@ int output_layer(const yolo_ctx *c)
 
 int need_detector(yolo_ctx *c, const char *what)
 {
+    if (c->map_layer >= 0) return fail(c, YOLO_ERR_INVALID, "%s: the network is a map network ([net] yolo_output=map: its output is an image-shaped tensor, it has no detection head); use yolo_output_map / yolo_label_map / yolo_segment_images_u8", what);
     if (c->cls_layer >= 0) return fail(c, YOLO_ERR_INVALID, "%s: the network is a classifier (its output layer is a [softmax], it has no detection head); use yolo_classify*", what);
     return YOLO_OK;
 }
@@ -693,6 +737,7 @@ int yolo_detect_images_graph(yolo_ctx *c, const uint8_t *pixels, size_t bytes, c
 // ---- classifier contexts: forward + tail; the [softmax] launch of the output layer selects the top_k itself (run_layer) ----
 static int classify_check(yolo_ctx *c, int top_k, const int32_t *classes_out, const float *probs_out)
 {
+    if (c->map_layer >= 0) return fail(c, YOLO_ERR_INVALID, "yolo_classify: the network is a map network ([net] yolo_output=map); use yolo_output_map / yolo_label_map");
     if (c->cls_layer < 0) return fail(c, YOLO_ERR_INVALID, "yolo_classify: the network is a detector (its output layer is not a [softmax])");
     const Layer &L = c->layers[c->cls_layer];
     if (top_k < 0 || top_k > CLS_TOPK_MAX || top_k > L.C) return fail(c, YOLO_ERR_INVALID, "top_k %d outside 0..%d", top_k, L.C < CLS_TOPK_MAX ? L.C : CLS_TOPK_MAX);
@@ -730,6 +775,38 @@ int yolo_classify_images_u8(yolo_ctx *c, const uint8_t *pixels, size_t bytes, co
     c->cls_topk = 0; c->cls_mode = 0;
     if (r) return r;
     return classify_out(c, n, top_k, classes_out, probs_out, out_loc);
+}
+
+// ---- map contexts: the ragged native-size path.  One fit launch and one forward, as yolo_detect_images_u8, then ONE kernel that writes every
+//      image's labels at that image's own size (launch_segment_labels) ----
+int yolo_segment_images_u8(yolo_ctx *c, const uint8_t *pixels, const yolo_image_desc *descs, int n, int fit, float thresh, uint8_t *labels_u8,
+                           const uint64_t *label_offsets)
+{
+    if (!c) return YOLO_ERR_INVALID;
+    if (int r = need_map(c, "yolo_segment_images_u8")) return r;
+    if (!labels_u8) return fail(c, YOLO_ERR_INVALID, "labels_u8 == NULL");
+    const Layer &M = c->layers[c->map_layer];
+    if (M.C > 255) return fail(c, YOLO_ERR_UNSUPPORTED, "yolo_segment_images_u8: a map of %d channels (uint8 labels hold at most 255 classes)", M.C);
+    if (!descs || n < 1 || n > c->max_batch) return fail(c, YOLO_ERR_INVALID, "batch %d outside 1..%d", n, c->max_batch);
+    // the packed buffer ends where its last image ends; the labels lie back to back in image order unless the caller places them
+    size_t bytes = 0, total = 0;
+    std::vector<unsigned long long> off(n);
+    for (int i = 0; i < n; ++i) {
+        if (descs[i].h < 1 || descs[i].w < 1) return fail(c, YOLO_ERR_INVALID, "image %d: %d x %d", i, (int)descs[i].h, (int)descs[i].w);
+        const size_t px = (size_t)descs[i].h * (size_t)descs[i].w;
+        bytes = std::max(bytes, (size_t)descs[i].offset + px * 3);
+        off[i] = label_offsets ? label_offsets[i] : total;
+        total = std::max(total, (size_t)off[i] + px);
+    }
+    if (int r = forward_images_impl(c, pixels, bytes, descs, n, fit, YOLO_HOST, nullptr, YOLO_DEVICE, false, 0.f)) return r;
+    if (!c->d_label_off) HIPCK(c, hipMalloc((void **)&c->d_label_off, (size_t)c->max_batch * 8));
+    HIPCK(c, hipMemcpyAsync(c->d_label_off, off.data(), (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+    const float *map = nullptr; int map_stride = 0;
+    if (int r = map_f32_view(c, n, &map, &map_stride)) return r;
+    if (int r = map_labels_room(c, total)) return r;
+    if (label_offsets) HIPCK(c, hipMemsetAsync(c->d_map_labels, 0, total, c->stream));          // (gaps a caller's placement leaves)
+    HIPCK(c, launch_segment_labels(map, map_stride, M.H, M.W, M.C, thresh, c->d_descs, c->d_label_off, n, fit, c->in_h, c->in_w, c->d_map_labels, c->stream));
+    return copy_out(c, labels_u8, c->d_map_labels, total, YOLO_HOST);          // (synchronises: `off` outlives its asynchronous copy)
 }
 
 float yolo_fit_unit_value(int fit, int value)

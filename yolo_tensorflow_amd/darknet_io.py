@@ -210,6 +210,10 @@ def layer_shapes(secs):
             k, st = int(s["size"]), int(s.get("stride", 1))
             pad = k // 2 if int(s.get("pad", 0)) else int(s.get("padding", 0))
             H, W, C = (H + 2 * pad - k) // st + 1, (W + 2 * pad - k) // st + 1, int(s["filters"])
+        elif t == "deconvolutional":         # transposed convolution (DN/deconvolutional_layer.c:67-68)
+            k, st = int(s.get("size", 1)), int(s.get("stride", 1))
+            pad = k // 2 if int(s.get("pad", 0)) else int(s.get("padding", 0))
+            H, W, C = (H - 1) * st + k - 2 * pad, (W - 1) * st + k - 2 * pad, int(s["filters"])
         elif t == "maxpool":
             st = int(s.get("stride", 1)); k = int(s.get("size", st))
             pad = int(s.get("padding", (k - 1) // 2))
@@ -233,22 +237,22 @@ def layer_shapes(secs):
             H = W = int(s.get("side", 7))
         elif t == "avgpool":                 # always global (DN/avgpool_layer.c:40-55)
             H = W = 1
-        elif t not in ("shortcut", "yolo", "region", "dropout", "softmax", "cost"):
+        elif t not in ("shortcut", "yolo", "region", "dropout", "softmax", "cost", "logistic", "activation", "l2norm"):
             raise ValueError("unsupported layer type [%s]" % t)
         shapes.append((t, H, W, C, cin))
     return shapes
 
 
 def conv_specs(secs):
-    """Per parameterised layer in file order ([convolutional], and [connected] as a 1x1 conv over the flattened producer):
-    dict(filters, size, cin, bn, head, index)."""
+    """Per parameterised layer in file order ([convolutional], [deconvolutional] -- the same parameter counts, its filters stored
+    [cin][filters][size][size] --, and [connected] as a 1x1 conv over the flattened producer): dict(filters, size, cin, bn, head, index)."""
     shapes = layer_shapes(secs)
     layers = secs[1:]
     out = []
     for i, s in enumerate(layers):
         head = i + 1 < len(layers) and layers[i + 1]["type"] in ("yolo", "region", "detection")
-        if s["type"] == "convolutional":
-            out.append(dict(filters=int(s["filters"]), size=int(s["size"]), cin=shapes[i][4],
+        if s["type"] in ("convolutional", "deconvolutional"):
+            out.append(dict(filters=int(s["filters"]), size=int(s.get("size", 1)), cin=shapes[i][4],
                             bn=int(s.get("batch_normalize", 0)), head=head, index=i))
         elif s["type"] == "connected":
             out.append(dict(filters=int(s["output"]), size=1, cin=shapes[i][4], bn=0, head=head, index=i))
@@ -336,6 +340,19 @@ def synth_weights(secs, seed=0, obj_bias=-0.75, stats="benign"):
                 parts.append(b)
                 parts.append(rng.normal(0, np.sqrt(1.0 / (k * k * cin * max(cur, 1e-6))), n * cin * k * k))
                 cur = 1.0 + 1.0
+        elif t == "deconvolutional":
+            # an output pixel sums size^2 / stride^2 taps of cin channels on average (a phase without taps sums none): filters
+            # ~ N(0, 2 / that count), the rolling variance of a batch-normalised layer what they produce -- the conv recipe above
+            n, k, st, cin = int(s["filters"]), int(s.get("size", 1)), int(s.get("stride", 1)), shapes[i][4]
+            fan = max(k * k / float(st * st), 1.0) * cin
+            if int(s.get("batch_normalize", 0)):
+                pre_var = 2.0 * cur
+                parts += [rng.normal(0, .1, n), rng.uniform(.8, 1.2, n), rng.normal(0, .1 * np.sqrt(pre_var), n), pre_var * rng.uniform(.8, 1.25, n)]
+                parts.append(rng.normal(0, np.sqrt(2.0 / fan), cin * n * k * k))
+                cur = 1.01 * (0.505 if s.get("activation", "logistic") == "leaky" else 1.0)
+            else:
+                parts += [rng.normal(0, .5, n), rng.normal(0, np.sqrt(1.0 / (fan * max(cur, 1e-6))), cin * n * k * k)]
+                cur = 1.0 + 0.25
         elif t == "local":
             n, k, cin = int(s["filters"]), int(s["size"]), shapes[i][4]
             loc = shapes[i][1] * shapes[i][2]

@@ -46,6 +46,7 @@ EXPORTS = [
     "yolo_num_classes", "yolo_classify", "yolo_classify_images_u8", "yolo_op_avgpool", "yolo_op_softmax",
     "yolo_set_hier_thresh", "yolo_set_hierarchy_mode", "yolo_darknet_boxes_map", "yolo_tree_geometry", "yolo_tree_read", "yolo_plan_check", "yolo_plan_table",
     "yolo_op_tree_softmax", "yolo_op_tree_top", "yolo_activation_code", "yolo_op_activate", "yolo_op_shortcut",
+    "yolo_output_map_geometry", "yolo_output_map", "yolo_label_map", "yolo_segment_images_u8", "yolo_op_deconv2d", "yolo_op_l2norm", "yolo_op_upsample", "yolo_op_label_map",
 ]
 HIER_CONDITIONAL, HIER_ABSOLUTE, HIER_LEAVES = 0, 1, 2
 _HIER_MODES = {None: HIER_CONDITIONAL, "conditional": HIER_CONDITIONAL, "absolute": HIER_ABSOLUTE, "leaves": HIER_LEAVES}
@@ -151,6 +152,14 @@ def load_library():
     l.yolo_activation_code.argtypes = [C.c_char_p]
     l.yolo_op_activate.argtypes = [P, I, I, I, I, I, I, P, I]
     l.yolo_op_shortcut.argtypes = [P, I, I, I, I, P, I, I, I, I, I, P, I]
+    l.yolo_output_map_geometry.argtypes = [P, C.POINTER(I), C.POINTER(I), C.POINTER(I)]
+    l.yolo_output_map.argtypes = [P, I, P, SZ]
+    l.yolo_label_map.argtypes = [P, I, F, P]
+    l.yolo_segment_images_u8.argtypes = [P, P, P, I, I, F, P, P]
+    l.yolo_op_deconv2d.argtypes = [P, I, I, I, I, P, P, I, I, I, I, I, I, I, P, I]
+    l.yolo_op_l2norm.argtypes = [P, I, I, I, I, I, P, I]
+    l.yolo_op_upsample.argtypes = [P, I, I, I, I, I, F, I, P, I]
+    l.yolo_op_label_map.argtypes = [P, I, I, I, I, F, P, I]
     l.yolo_shard_bounds.argtypes = [I, I, I, C.POINTER(I), C.POINTER(I)]
     l.yolo_dist_flat_words.argtypes = [I, I]; l.yolo_dist_flat_words.restype = C.c_size_t
     l.yolo_dist_split_records.argtypes = [P, I, I, I, P, P]
@@ -559,6 +568,40 @@ class Engine:
                                                      cls.ctypes.data if top_k else None, probs.ctypes.data, HOST), "yolo_classify_images_u8")
         return (cls, probs) if top_k else probs
 
+    # ---- map networks ([net] yolo_output=map): segmentation masks, heat maps ----
+    def map_geometry(self):
+        """(h, w, c) of the output map (yolo_output_map_geometry); YoloError on a detector or a classifier."""
+        h, w, ch = C.c_int(), C.c_int(), C.c_int()
+        self._check(self.lib.yolo_output_map_geometry(self.ctx, C.byref(h), C.byref(w), C.byref(ch)), "yolo_output_map_geometry")
+        return h.value, w.value, ch.value
+
+    def output_map(self, n):
+        """The map of images 0..n-1 of the last forward (forward / forward_images with want_detections=False): [n, h, w, c] float32."""
+        out = np.empty((n,) + self.map_geometry(), dtype=np.float32)
+        self._check(self.lib.yolo_output_map(self.ctx, n, out.ctypes.data, out.size), "yolo_output_map")
+        return out
+
+    def label_map(self, n, thresh=0.5):
+        """Per map pixel of those images the arg-max over the channels (the lowest index wins a tie), 255 where the maximum is below
+        thresh: [n, h, w] uint8 (yolo_label_map)."""
+        h, w, _ = self.map_geometry()
+        out = np.empty((n, h, w), dtype=np.uint8)
+        self._check(self.lib.yolo_label_map(self.ctx, n, float(thresh), out.ctypes.data), "yolo_label_map")
+        return out
+
+    def segment_images(self, images, fit=FIT_LETTERBOX, thresh=0.5):
+        """images: a list of uint8 RGB [h_i, w_i, 3] arrays of any sizes -> a list of [h_i, w_i] uint8 label arrays, each at its image's own
+        size: one fit launch, one forward, one label kernel (yolo_segment_images_u8; include/yolo_hip.h states the pixel mapping)."""
+        buf, descs = pack_images(images)
+        d = _descs(descs)
+        sizes = [int(q["h"]) * int(q["w"]) for q in d]
+        labels = np.empty(sum(sizes), dtype=np.uint8)
+        self._check(self.lib.yolo_segment_images_u8(self.ctx, buf.ctypes.data, d.ctypes.data, len(d), fit, float(thresh), labels.ctypes.data, None), "yolo_segment_images_u8")
+        out, lo = [], 0
+        for q, sz in zip(d, sizes):
+            out.append(labels[lo:lo + sz].reshape(int(q["h"]), int(q["w"])).copy()); lo += sz
+        return out
+
     def darknet_boxes(self, image, w, h, thresh=0.5, relative=1, cap=None, hier_thresh=None, map200=None):
         """darknet's get_network_boxes over image `image` of the last forward (yolo_darknet_boxes_at) -> records [count, 5 + classes]
         (x, y, w, h, objectness, prob[classes]), un-letterboxed for a w x h source image.  A tree head: hier_thresh (None: the
@@ -721,6 +764,46 @@ def op_shortcut(x, frm, activation="linear", dtype=FP32, device=0):
     out = np.empty_like(x)
     _op_check(load_library().yolo_op_shortcut(x.ctypes.data, n, h2, w2, c2, frm.ctypes.data, h1, w1, c1, activation_code(activation), dtype,
                                               out.ctypes.data, device), "yolo_op_shortcut")
+    return out
+
+
+def op_deconv2d(x, w_iohw, bias=None, stride=1, padding=0, activation="linear", dtype=BF16, out_f32=False, device=0):
+    """darknet's [deconvolutional] (yolo_op_deconv2d): x [n, h, w, cin], w_iohw [cin, cout, size, size] (the weight file's order) ->
+    [n, (h - 1) stride + size - 2 padding, ..., cout] float32.  out_f32: the fp32 store of a 16-bit kernel."""
+    x = _f32(x); w_iohw = _f32(w_iohw)
+    n, h, w, cin = x.shape
+    if w_iohw.ndim != 4 or w_iohw.shape[0] != cin or w_iohw.shape[2] != w_iohw.shape[3]:
+        raise YoloError("op_deconv2d: filters must be [cin, cout, size, size]")
+    cout, size = w_iohw.shape[1], w_iohw.shape[2]
+    b = _f32(bias) if bias is not None else None
+    ho, wo = (h - 1) * stride + size - 2 * padding, (w - 1) * stride + size - 2 * padding
+    out = np.empty((n, max(ho, 0), max(wo, 0), cout), dtype=np.float32)
+    _op_check(load_library().yolo_op_deconv2d(x.ctypes.data, n, h, w, cin, w_iohw.ctypes.data, b.ctypes.data if b is not None else None, size, stride, padding,
+                                              cout, activation_code(activation), dtype, 1 if out_f32 else 0, out.ctypes.data, device), "yolo_op_deconv2d")
+    return out
+
+
+def op_l2norm(x, dtype=FP32, device=0):
+    """[l2norm]: per pixel x / sqrt(sum over the channels of x^2) (yolo_op_l2norm)."""
+    x = _f32(x); n, h, w, c = x.shape
+    out = np.empty_like(x)
+    _op_check(load_library().yolo_op_l2norm(x.ctypes.data, n, h, w, c, dtype, out.ctypes.data, device), "yolo_op_l2norm")
+    return out
+
+
+def op_upsample(x, stride=2, scale=1.0, dtype=FP32, device=0):
+    """darknet's [upsample]: nearest, out = scale * in (yolo_op_upsample)."""
+    x = _f32(x); n, h, w, c = x.shape
+    out = np.empty((n, h * max(stride, 0), w * max(stride, 0), c), dtype=np.float32)
+    _op_check(load_library().yolo_op_upsample(x.ctypes.data, n, h, w, c, stride, float(scale), dtype, out.ctypes.data, device), "yolo_op_upsample")
+    return out
+
+
+def op_label_map(m, thresh=0.5, device=0):
+    """[n, h, w, c] float32 map -> [n, h, w] uint8 labels: arg-max over the channels, 255 where the maximum is below thresh (yolo_op_label_map)."""
+    m = _f32(m); n, h, w, c = m.shape
+    out = np.empty((n, h, w), dtype=np.uint8)
+    _op_check(load_library().yolo_op_label_map(m.ctypes.data, n, h, w, c, float(thresh), out.ctypes.data, device), "yolo_op_label_map")
     return out
 
 

@@ -1,0 +1,54 @@
+"""Dense-prediction networks (segmentation masks, heat maps, any U-Net-shaped cfg with `yolo_output=map` in [net]): "Darknet weights in,
+maps and label images out".
+
+Counterpart of the reference's examples/segmenter.c `predict_segmenter`, which letterboxes an image, calls network_predict and reads the
+prediction back with get_network_image.  Here uint8 images of any sizes are fitted to the network input in one launch, the map stays
+on the device in fp32, and `segment_from_images` returns every image's labels AT ITS OWN SIZE (the reference only ever shows the
+letterboxed prediction; the native-pixel -> map-pixel rule is this project's own, include/yolo_hip.h yolo_segment_images_u8)."""
+import numpy as np
+from . import hip, darknet_io as IO
+
+_FITS = {"letterbox": hip.FIT_LETTERBOX, "stretch": hip.FIT_STRETCH}
+
+
+class Segmenter:
+    def __init__(self, cfg, weights=None, max_batch=1, dtype=hip.BF16, fit="letterbox", device=0, seed=0):
+        """cfg: a cfg file path or cfg text with `yolo_output=map` in its [net] section.  weights: a darknet `.weights` file or a flat
+        float32 parameter stream; None loads darknet_io's seeded synthetic parameters (`seed`).  fit: "letterbox" (darknet's
+        letterbox_image) or "stretch", or a hip.FIT_* code."""
+        text = cfg if "[net]" in cfg or "[network]" in cfg else IO.cfg_text(cfg)
+        self.engine = hip.Engine(text, max_batch=max_batch, dtype=dtype, semantics=hip.SEM_DARKNET, device=device)
+        try:
+            self.map_hwc = self.engine.map_geometry()
+        except hip.YoloError:
+            self.engine.close()
+            raise
+        if weights is None:
+            self.engine.set_weights(IO.synth_weights(IO.parse_cfg(text), seed=seed))
+        elif isinstance(weights, str):
+            self.engine.load_weights(weights)
+        else:
+            self.engine.set_weights(weights)
+        self.max_batch = max_batch
+        self.fit = _FITS[fit] if isinstance(fit, str) else int(fit)
+        self.num_classes = self.map_hwc[2]
+
+    def predict_from_images(self, images):
+        """images: a list of RGB uint8 [h, w, 3] arrays of any sizes -> a list of [map_h, map_w, c] float32 maps (of the fitted input)."""
+        out = []
+        for lo in range(0, len(images), self.max_batch):
+            chunk = images[lo:lo + self.max_batch]
+            self.engine.forward_images(chunk, fit=self.fit, want_detections=False)
+            out.extend(m.copy() for m in self.engine.output_map(len(chunk)))
+        return out
+
+    def segment_from_images(self, images, thresh=0.5):
+        """-> a list of [h_i, w_i] uint8 label arrays, each at its image's own size: the arg-max channel of the map pixel the native pixel
+        falls on, 255 where that maximum is below `thresh`."""
+        out = []
+        for lo in range(0, len(images), self.max_batch):
+            out.extend(self.engine.segment_images(images[lo:lo + self.max_batch], fit=self.fit, thresh=thresh))
+        return out
+
+    def close(self):
+        self.engine.close()
