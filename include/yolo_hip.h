@@ -417,7 +417,11 @@ int yolo_plan_check(const char *cfg_text, int dtype, char *err, size_t err_len);
  *   <index> <section> kernel=<tiled|halo|s2|-> fused=<none|stem|pair-stem|resblock|c3s2> launcher=<layer that issues the fused launch, -1>
  *   residual_from=<folded shortcut source, -2> tail_layer=<1x1 conv that can ride in this conv's epilogue, -1> storage=<index, -1>
  *   phys=<pooled buffer> def=<first writer> last=<last reader>
- * -- then `buffers <count> bytes <total>`.  YOLO_ERR_INVALID with the size needed when `out` is too small. */
+ * -- then `buffers <count> bytes <total>`.  YOLO_ERR_INVALID with the size needed when `out` is too small.
+ * A [convolutional] section with groups > 1 runs the grouped kernel and prints, as a [deconvolutional] section does, kernel=- fused=none
+ * launcher=-1 residual_from=-2 tail_layer=-1: it is no member of a fused launch, hosts no folded [shortcut] and no 1x1 tail.  The planner
+ * refuses (YOLO_ERR_INVALID) groups that do not divide the input channels or the filters, and (YOLO_ERR_UNSUPPORTED) a grouped section in
+ * the fp8 and split-fp16 configurations, as the first layer, or directly in front of a [yolo] / [region] / [detection] head. */
 int yolo_plan_table(const char *cfg_text, int dtype, int max_batch, int keep_layers, char *out, size_t out_len, char *err, size_t err_len);
 /* single operators: x [n][len] fp32 logits, one softmax per group of the tree at tree_path, `mode` a yolo_hierarchy_mode -> out [n][len];
  * hierarchy_top_prediction of n rows of raw logits (temperature 1) walking down from the root -> labels_out [n] */
@@ -453,6 +457,12 @@ int yolo_segment_images_u8(yolo_ctx *ctx, const uint8_t *pixels, const yolo_imag
  * 16-bit kernel (a map network's output layer); out [n, (h-1) stride + size - 2 padding, ..., cout] fp32 */
 int yolo_op_deconv2d(const float *x, int n, int h, int w, int cin, const float *w_iohw, const float *bias, int size, int stride, int padding,
                      int cout, int act, int dtype, int out_f32, float *out, int device);
+/* darknet's [convolutional] with groups= (DN/convolutional_layer.c:458-471): group g reads the input channels g cin/groups .. and writes the output
+ * channels g cout/groups ..  x [n,h,w,cin] fp32 NHWC, w_oihw [cout][cin/groups][size][size] (the order of darknet's weight files), bias [cout] or NULL;
+ * 1 <= size <= 7, 1 <= stride <= 4, 0 <= padding < size; groups >= 1 divides cin and cout (1 runs the same kernel with one group: a direct comparison
+ * against yolo_op_conv2d); dtype and out_f32 as for yolo_op_deconv2d; out [n, (h + 2 padding - size) / stride + 1, ..., cout] fp32 */
+int yolo_op_conv2d_grouped(const float *x, int n, int h, int w, int cin, const float *w_oihw, const float *bias, int size, int stride, int padding,
+                           int cout, int groups, int act, int dtype, int out_f32, float *out, int device);
 /* [l2norm]: per pixel x / sqrtf(sum over the channels of x^2); an all-zero pixel is NaN, as in the reference */
 int yolo_op_l2norm(const float *x, int n, int h, int w, int c, int dtype, float *out, int device);
 /* darknet's [upsample]: nearest, out = scale * in, stride 1..8; out [n, h stride, w stride, c] */

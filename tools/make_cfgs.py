@@ -10,7 +10,7 @@ reference's layer tables and TF graph builders:
   darknet19 / darknet53
                   the classifiers those two backbones are (cfg layers 0-22 of yolov2 / 0-74 of yolov3, same tables) with the tail the
                   reference's parser reads: [avgpool] (DN/parser.c:493-507), [softmax] (:268-280), 1000 classes, 256 x 256
-  resnet18 / 34 / 50 / 101 / 152, vgg-16
+  resnet18 / 34 / 50 / 101 / 152, resnext50 / 101 / 152, vgg-16
                   written from the architectures (He et al. 2015, Simonyan & Zisserman 2014) in the layer vocabulary of darknet's own model
                   zoo: see resnet() and vgg16() below.  What they need of the reference is its general [shortcut] (DN/blas.c:68-92) and
                   the activations of DN/activations.h
@@ -43,11 +43,13 @@ class Cfg:
         self.n += 1
         return self.n - 1
 
-    def conv(self, filters, size, stride=1, bn=True, act="leaky"):
+    def conv(self, filters, size, stride=1, bn=True, act="leaky", groups=1):
         kv = {}
         if bn:
             kv["batch_normalize"] = 1
         kv.update(filters=filters, size=size, stride=stride, pad=1, activation=act)
+        if groups != 1:
+            kv["groups"] = groups            # DN/parser.c:184
         return self._sec("convolutional", **kv)
 
     def shortcut(self, frm, act="linear"):
@@ -294,6 +296,50 @@ def resnet(depth, size=256, classes=1000):
     return c.text()
 
 
+def resnext(depth, size=256, classes=1000, groups=32):
+    """ResNeXt-50/101/152 (32x4d; Xie et al. 2016) as darknet's model zoo spells them: resnet()'s stem, stages and tail, with bottlenecks
+    of 1x1 / 3x3 groups=32 / 1x1 linear + [shortcut] whose inner width is twice ResNet's: 128/256, 256/512, 512/1024, 1024/2048."""
+    c = Cfg(size)
+    c.conv(64, 7, stride=2); c.maxpool()
+    for stage, blocks in enumerate(RESNET_BLOCKS[depth]):
+        f = 128 << stage
+        for b in range(blocks):
+            st = 2 if stage > 0 and b == 0 else 1
+            c.conv(f, 1); c.conv(f, 3, stride=st, groups=groups); c.conv(2 * f, 1, act="linear"); c.shortcut(-4, act="leaky")
+    c.conv(classes, 1, bn=False, act="linear")
+    c.avgpool()
+    c.softmax()
+    return c.text()
+
+
+def dw_yolo(size=416, classes=80):
+    """A depthwise-separable detector in the shape of yolov3_tiny(), for rate runs (no trained weights exist for it): the dense 3x3 first
+    conv stays, every later 3x3 conv becomes a depthwise 3x3 (groups = its input channels) followed by a pointwise 1x1 to the filters;
+    the two head convs are ordinary 1x1 convs."""
+    c = Cfg(size)
+    ch = [16]
+
+    def sep(f):
+        c.conv(ch[0], 3, groups=ch[0]); ch[0] = f
+        return c.conv(f, 1)
+    c.conv(16, 3); c.maxpool()
+    for f in (32, 64, 128):
+        sep(f); c.maxpool()
+    route_1 = sep(256)
+    c.maxpool()
+    sep(512)
+    c.maxpool(2, 1)
+    sep(1024)
+    route_2 = c.conv(256, 1); ch[0] = 256
+    sep(512)
+    nout = 3 * (5 + classes)
+    c.conv(nout, 1, bn=False, act="linear"); c.yolo([3, 4, 5], V3_TINY_ANCHORS, classes)
+    c.route(route_2); c.conv(128, 1); up = c.upsample(); c.route(up, route_1); ch[0] = 128 + 256
+    sep(256)
+    c.conv(nout, 1, bn=False, act="linear"); c.yolo([0, 1, 2], V3_TINY_ANCHORS, classes)
+    return c.text()
+
+
 def vgg16(size=224, classes=1000):
     """VGG-16 (configuration D): thirteen 3x3 convs with bias and relu in five groups of 64 .. 512 filters, a 2/2 max-pool behind each
     group, then [connected] 4096, 4096 (relu, with dropout) and the classes (linear), [softmax]."""
@@ -378,6 +424,19 @@ def main():
             f.write(unet() + "\n")
         print("wrote unet.cfg to", sys.argv[2])
         return
+    if len(sys.argv) > 2 and sys.argv[1] == "--dw-yolo":       # python tools/make_cfgs.py --dw-yolo DIR: dw-yolo.cfg, a depthwise-separable yolov3-tiny
+        os.makedirs(sys.argv[2], exist_ok=True)
+        with open(os.path.join(sys.argv[2], "dw-yolo.cfg"), "w") as f:
+            f.write(dw_yolo() + "\n")
+        print("wrote dw-yolo.cfg to", sys.argv[2])
+        return
+    if len(sys.argv) > 2 and sys.argv[1] == "--resnext":       # python tools/make_cfgs.py --resnext DIR: the 101 and 152 depths (50 is shipped in cfg/zoo)
+        os.makedirs(sys.argv[2], exist_ok=True)
+        for depth in (101, 152):
+            with open(os.path.join(sys.argv[2], "resnext%d.cfg" % depth), "w") as f:
+                f.write(resnext(depth) + "\n")
+        print("wrote resnext101.cfg and resnext152.cfg to", sys.argv[2])
+        return
     if len(sys.argv) > 2 and sys.argv[1] == "--yolo9000":      # python tools/make_cfgs.py --yolo9000 DIR: yolo9000.cfg + its seeded tree
         os.makedirs(sys.argv[2], exist_ok=True)
         with open(os.path.join(sys.argv[2], "9k.tree"), "w") as f:
@@ -395,6 +454,7 @@ def main():
         "darknet19.cfg": darknet19(256), "darknet53.cfg": darknet53(256),
         # cfg/zoo/: classifiers of darknet's model zoo that are no YOLO backbone (cfg/ itself is the set tests/golden/plan_tables.json pins)
         "zoo/resnet18.cfg": resnet(18), "zoo/resnet50.cfg": resnet(50), "zoo/vgg-16.cfg": vgg16(),
+        "zoo/resnext50.cfg": resnext(50),
     }
     os.makedirs(os.path.join(OUT, "zoo"), exist_ok=True)
     for name, text in files.items():

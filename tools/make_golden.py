@@ -16,6 +16,10 @@ Runs only in the build container (it reads /root/reference and oracle/_ref); the
   mini_resnet.npz / mini_resnet_30.npz
                     a ResNet in miniature (general [shortcut] forms, activations outside the slope family) at 32 x 32 and 30 x 30:
                     three images each, every layer's output from the compiled reference
+  mini_grouped.npz / mini_dw_v3.npz
+                    [convolutional] sections with groups= (ResNeXt-style bottlenecks, depthwise and pointwise pairs, a grouped 5x5, a
+                    grouped class conv): a classifier with three images and every layer's output, and a two-head depthwise-separable
+                    [yolo] detector with its boxes, from the compiled reference
   mini_cls53.npz / mini_cls19.npz
                      two small classifier topologies ([avgpool], [softmax], [cost]; darknet-53's and darknet-19's tail order), every
                      layer output and the probability vector, from the same compiled reference
@@ -647,6 +651,78 @@ def gen_mini_unet():
         print(name, os.path.getsize(os.path.join(OUT, name + ".npz")), "bytes")
 
 
+def _gconv(filters, size, groups, stride=1, bn=True, act="leaky"):
+    return "[convolutional]\n%sfilters=%d\nsize=%d\nstride=%d\npad=1\ngroups=%d\nactivation=%s\n\n" % ("batch_normalize=1\n" if bn else "", filters, size, stride, groups, act)
+
+
+def mini_grouped_cfg(size=32):
+    """A classifier whose [convolutional] sections carry groups= (DN/parser.c:184, DN/convolutional_layer.c:458-471), one layer per shape the
+    grouped kernel's bundle rule distinguishes: a relu stem (16) and a 2/2 max-pool; a bottleneck 1x1 16 -> 3x3 groups=4 16 -> 1x1 32 linear
+    + leaky shortcut; one whose 3x3 is groups=8 with stride 2, its shortcut from the larger, narrower tensor; a depthwise 3x3 (groups =
+    channels) and its pointwise 1x1; a depthwise stride-2 3x3 with bias and tanh (a post-activation); a grouped 5x5, groups=2; a [route] that
+    concatenates that layer's output with the tensor it read (two grouped convs store into windows of one buffer); a grouped 1x1, groups=2,
+    to 24 classes (the fp32 store), [avgpool], [softmax]."""
+    sc = lambda act: "[shortcut]\nfrom=-4\nactivation=%s\n\n" % act
+    return ("[net]\nbatch=1\nwidth=%d\nheight=%d\nchannels=3\n\n" % (size, size) + _conv(16, 3, act="relu") + "[maxpool]\nsize=2\nstride=2\n\n" +
+            _conv(16, 1) + _gconv(16, 3, 4) + _conv(32, 1, act="linear") + sc("leaky") +
+            _conv(16, 1) + _gconv(16, 3, 8, stride=2) + _conv(64, 1, act="linear") + sc("leaky") +
+            _gconv(64, 3, 64) + _conv(32, 1) +
+            _gconv(32, 3, 32, stride=2, bn=False, act="tanh") +
+            _gconv(32, 5, 2) + "[route]\nlayers=-1,-2\n\n" +
+            _gconv(24, 1, 2, bn=False, act="linear") + "[avgpool]\n\n[softmax]\ngroups=1\n")
+
+
+MINI_DW_V3 = ("[net]\nbatch=1\nwidth=64\nheight=64\nchannels=3\n\n" + _conv(8, 3) + _gconv(8, 3, 8, stride=2) + _conv(16, 1) + _gconv(16, 3, 16) + _conv(16, 1, act="linear") +
+              "[shortcut]\nfrom=-3\nactivation=linear\n\n" + _gconv(16, 3, 16, stride=2) + _conv(32, 1) + "[maxpool]\nsize=2\nstride=2\n\n" + _gconv(32, 3, 32) + _conv(16, 1) +
+              _conv(27, 1, bn=False, act="linear") + "[yolo]\nmask=3,4,5\nanchors=4,5,  8,6,  10,14,  20,18,  30,40,  50,44\nclasses=4\nnum=6\n\n" +
+              "[route]\nlayers=-3\n\n" + _conv(8, 1) + "[upsample]\nstride=2\n\n[route]\nlayers=-1,7\n\n" + _gconv(40, 3, 40) + _conv(24, 1) +
+              _conv(27, 1, bn=False, act="linear") + "[yolo]\nmask=0,1,2\nanchors=4,5,  8,6,  10,14,  20,18,  30,40,  50,44\nclasses=4\nnum=6\n")
+
+TOL16_BF16 = 3e-2          # the bf16 bound of the classifier tests, as a share of the largest logit
+
+
+def gen_mini_grouped():
+    """mini_grouped_cfg through the compiled reference (convolutional_layer.c with l.groups), the recipe of gen_mini_resnet: cfg text,
+    weights, three images, every layer's output for each (separate predicts); the class conv scaled until the reference's logits reach
+    +-5.  Asserted: on every image the two largest pooled logits differ by more than twice the bf16 bound, so that a top-1 comparison
+    holds for all three.  And mini_dw_v3: a two-head [yolo] detector on a depthwise-separable backbone, through gen_mini."""
+    from oracle import darknet_ref as D
+    from yolo_tensorflow_amd import darknet_io as IO
+    name, size, seed = "mini_grouped", 32, 61
+    cfg = mini_grouped_cfg(size)
+    secs = IO.parse_cfg(cfg)
+    flat = IO.synth_weights(secs, seed=seed)
+    last = IO.conv_specs(secs)[-1]
+    tail = last["filters"] * (1 + (last["cin"] // last["groups"]) * last["size"] ** 2)
+    imgs = np.random.default_rng(seed + 1).integers(0, 256, (3, size, size, 3), dtype=np.uint8)
+    x = imgs.astype(np.float32) / np.float32(255.0)
+    logit_layer = len(secs) - 4
+    net = D.RefNet(cfg, flat, 0, 2)
+    net.predict(x[0])
+    factor = np.float32(round(5.0 / float(np.abs(net.layer_output_nhwc(logit_layer)).max()), 2))
+    net.close()
+    flat[-tail:] *= factor
+    net = D.RefNet(cfg, flat, 0, 2)
+    outs = [[] for _ in range(net.n)]
+    for b in range(3):
+        net.predict(x[b])
+        for i in range(net.n):
+            outs[i].append(np.asarray(net.layer_output_nhwc(i), dtype=np.float32).reshape(-1) if secs[i + 1]["type"] in ("avgpool", "softmax") else np.asarray(net.layer_output_nhwc(i), dtype=np.float32)[0])
+    data = {"cfg": np.array(cfg), "weights": flat, "images_u8": imgs, "logit_layer": np.int32(logit_layer)}
+    for i in range(net.n):
+        data["layer_%02d" % i] = np.stack(outs[i])
+    data["max_abs_logit"] = np.float32(np.abs(data["layer_%02d" % logit_layer]).max())
+    pooled = data["layer_%02d" % (net.n - 2)]
+    top2 = np.sort(pooled, axis=-1)[:, -2:]
+    data["top1_margin"] = (top2[:, 1] - top2[:, 0]).astype(np.float32)
+    print(name, "layers", net.n, "max|logit|", float(data["max_abs_logit"]), "pooled max", float(np.abs(pooled).max()), "top-1 margins", data["top1_margin"], "p max", float(data["layer_%02d" % (net.n - 1)].max()))
+    assert float(data["top1_margin"].min()) > 2 * TOL16_BF16 * float(np.abs(pooled).max()), "a top-1 margin below twice the bf16 bound: change the seed, not the rule"
+    net.close()
+    np.savez_compressed(os.path.join(OUT, name + ".npz"), **data)
+    print(name, os.path.getsize(os.path.join(OUT, name + ".npz")), "bytes")
+    gen_mini("mini_dw_v3", MINI_DW_V3, 4)
+
+
 def gen_bn_real():
     """D2T/log.txt is the reference's stdout of two detect runs (yolov2 then yolov3) with the printf block of DN/parser.c:1176-1228
     enabled: per batch-normalised conv five lines of numbers (beta, gamma, rolling mean, rolling variance -- l.n values each -- and the
@@ -853,6 +929,8 @@ if __name__ == "__main__":
         gen_mini_resnet(); sys.exit(0)
     if sys.argv[1:] == ["mini_unet"]:
         gen_mini_unet(); sys.exit(0)
+    if sys.argv[1:] == ["mini_grouped"]:
+        gen_mini_grouped(); sys.exit(0)
     if sys.argv[1:] == ["darknet_py_symbols"]:
         gen_darknet_py_symbols(); sys.exit(0)
     if sys.argv[1:] == ["rect"]:
@@ -867,6 +945,7 @@ if __name__ == "__main__":
     gen_mini_cls()
     gen_mini_resnet()
     gen_mini_unet()
+    gen_mini_grouped()
     gen_rect()
     gen_bn_real()
     gen_known_answers()

@@ -9,7 +9,7 @@ from . import hip, darknet_io as IO
 
 class Classifier:
     def __init__(self, cfg_or_name, weights_file=None, dtype=hip.BF16, max_batch=1, names=None, device=0, fit=hip.FIT_STRETCH, seed=0, hierarchy=None):
-        """cfg_or_name: a shipped topology ('darknet19', 'darknet53', 'resnet18', 'resnet50', 'vgg-16'), a cfg file path, or cfg text
+        """cfg_or_name: a shipped topology ('darknet19', 'darknet53', 'resnet18', 'resnet50', 'resnext50', 'vgg-16'), a cfg file path, or cfg text
         (a ResNet's [shortcut] layers with fewer or larger `from` tensors and any of darknet's thirteen activations are served).  weights_file: a darknet
         `.weights` file; None loads darknet_io's seeded synthetic parameters (`seed`).  names: a list of class names or the path of a
         file with one name per line; without it the class index stands in for the name.  hierarchy (a [softmax] with tree=): None

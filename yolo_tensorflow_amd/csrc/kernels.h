@@ -261,6 +261,49 @@ inline bool deconv_served(int size, int stride, int pad, int h, int w)
 // 16-bit operands: v_mfma_f32_16x16x32_{bf16,f16}, fp32 accumulators; fp32 operands: plain FMAs
 hipError_t launch_deconv(const DeconvArgs &a, hipStream_t s);
 
+// ---- grouped convolution (gconv.hip; [convolutional] with groups > 1, DN/convolutional_layer.c:458-471) ---------------------------
+// Group g reads the input channels g * cg .. (cg = C / groups) and writes the output channels g * m .. (m = Cout / groups); the file
+// holds the filters [Cout][cg][size][size].  The packer merges t = max(8 / gcd(cg, 8), 16 / gcd(m, 16)) <= 16 consecutive groups into
+// a BUNDLE: its kc = t * cg input channels are whole 8-channel granules, contiguous in NHWC, its mb = t * m output channels whole 16-row
+// MFMA tiles.  Per bundle the filters are a block-diagonal matrix [mb][kp], k = tap * kc + (channel in the bundle), tap = ky * size + kx,
+// kp = size^2 * kc rounded up to 32; everything off the diagonal, and the rows and columns of the groups a trailing bundle lacks, is zero.
+// The bundles lie back to back: nb * mb rows in all (>= Cout; the bias has as many entries).  fp32 operands (in_dt == DT_F32) are not
+// bundled: the same nb * mb rows, row o = its group's own filters [tap][cg] (kc = cg, kp = size^2 * cg).
+#define GCONV_MAX_SIZE 7
+#define GCONV_MAX_STRIDE 4
+#define GCONV_CO_TILE 32             // output channels of a bundle per wave: a bundle of more is cut into pieces of this size
+#define GCONV_PT 2                   // 16-pixel tiles per wave: one filter fragment feeds this many MFMAs
+struct GConvArgs {
+    const void *in; int in_stride;       // elements per input pixel; the channels up to C rounded up to 8 are readable and finite
+    const void *wt;                      // the bundles' filter blocks back to back, in the operand type (in_dt)
+    const float *bias;                   // [nb * mb] fp32 (BN folded)
+    void *out; int out_stride; int out_dt, in_dt;      // out_dt: in_dt, or DT_F32 (a "head": logits, a map network's output)
+    int N, H, W, C, Ho, Wo, Cout;
+    int Cstore;                          // channels written per pixel: Cout rounded up to the output's granule (zeros past Cout), a multiple of 4
+    int size, stride, pad, act;          // act: slope family only
+    int groups, cg, m, t, nb, kc, mb, kp;      // the bundle layout (gconv_layout)
+};
+// fills cg .. kp from (C, Cout, groups, size, in_dt); returns the elements of all blocks together
+inline size_t gconv_layout(GConvArgs &a)
+{
+    a.cg = a.C / a.groups; a.m = a.Cout / a.groups;
+    int tc, tm;          // the smallest power of two tc with tc * cg a multiple of 8, tm with tm * m a multiple of 16
+    for (tc = 1; (tc * a.cg) % 8; tc *= 2) {}
+    for (tm = 1; (tm * a.m) % 16; tm *= 2) {}
+    a.t = tc > tm ? tc : tm;
+    a.nb = (a.groups + a.t - 1) / a.t; a.kc = a.t * a.cg; a.mb = a.t * a.m;
+    a.kp = (a.size * a.size * a.kc + 31) / 32 * 32;
+    if (a.in_dt == DT_F32) { a.kc = a.cg; a.kp = a.size * a.size * a.cg; }          // fp32: no bundling, row o holds [tap][cg] of its own group
+    return (size_t)a.nb * a.mb * a.kp;
+}
+inline bool gconv_served(int size, int stride, int pad, int h, int w)
+{
+    return size >= 1 && size <= GCONV_MAX_SIZE && stride >= 1 && stride <= GCONV_MAX_STRIDE && pad >= 0 && pad < size &&
+           h + 2 * pad >= size && w + 2 * pad >= size;
+}
+// 16-bit operands: v_mfma_f32_16x16x32_{bf16,f16} over the bundles, fp32 accumulators; fp32 operands: plain FMAs over the group's own channels
+hipError_t launch_gconv(const GConvArgs &a, hipStream_t s);
+
 // ---- the small layers of a dense-prediction network and the map outputs (map_ops.hip) ----------
 // [l2norm] (DN/blas.c:126-144): per pixel, over the channels, x / sqrtf(sum x^2); an all-zero pixel is 0 / 0 = NaN, as in the reference
 hipError_t launch_l2norm(const TView &in, const TView &out, hipStream_t s);

@@ -19,7 +19,8 @@
 namespace yolo_impl {
 
 enum LType { L_CONV, L_SHORTCUT, L_ROUTE, L_UPSAMPLE, L_MAXPOOL, L_REORG, L_YOLO, L_REGION, L_DETECT, L_LOCAL, L_AVGPOOL, L_SOFTMAX,
-             L_DECONV, L_ACTIVATE, L_L2NORM };      // [deconvolutional]; [logistic] / [activation]: k_activate over the producer's tensor; [l2norm]
+             L_DECONV, L_ACTIVATE, L_L2NORM,        // [deconvolutional]; [logistic] / [activation]: k_activate over the producer's tensor; [l2norm]
+             L_GCONV };                             // [convolutional] with groups > 1 (gconv.hip); Layer::groups
 enum ConvKernel { K_TILED, K_HALO, K_S2 };      // a conv's own kernel: the tiled family (fp32 / direct / pair form picked by dtype), conv_halo_c32_c64 (3x3/s1, 32 -> 64), conv_s2_c64_c128 (3x3/s2, 64 -> 128)
 // the fused launch a conv is a member of, {members} -> launcher: conv_stem.hip {0, 1, optionally the 1x1 conv 2} -> 1; conv_stem_pair.hip (split-fp16) {0, 1} -> 1; conv_block.hip {1x1 i, 3x3 i + 1} -> i + 1; conv_c3s2.hip {conv3 i, stride-2 conv i + 2} -> i + 2 (both keep K_HALO / K_S2, the fall-back)
 enum FuseKind { F_NONE, F_STEM, F_PSTEM, F_RESBLOCK, F_C3S2 };
@@ -197,6 +198,8 @@ void pack_conv(const Layer &L, const float *bn_or_bias, const float *w_oihw, int
                std::vector<uint8_t> &wbuf, std::vector<float> &bias, std::vector<float> &osc, int semantics = YOLO_SEM_TF, int split = 0);      // split: 0 plain, 1 pair input in three blocks (the image), 2 interleaved pair input
 // [deconvolutional]: w_iohw [cin][filters][k][k] (darknet's order) -> the per-phase blocks of DeconvArgs, batch norm folded as pack_conv folds it
 void pack_deconv(const Layer &L, const float *bn_or_bias, const float *w_iohw, int wdt, std::vector<uint8_t> &wbuf, std::vector<float> &bias, int semantics = YOLO_SEM_TF);
+// [convolutional] with groups > 1: w_oihw [filters][cin / groups][k][k] -> the block-diagonal bundles of GConvArgs, batch norm folded as pack_conv folds it
+void pack_gconv(const Layer &L, const float *bn_or_bias, const float *w_oihw, int wdt, std::vector<uint8_t> &wbuf, std::vector<float> &bias, int semantics = YOLO_SEM_TF);
 float h2f(uint16_t h);
 void resolve_scales(yolo_ctx *c);
 void channel_scales(const yolo_ctx *c, int idx, std::vector<float> &out);
@@ -218,6 +221,7 @@ TView view_of(const yolo_ctx *c, int idx);
 // yolo_run.cpp
 ConvArgs conv_args(const yolo_ctx *c, const Layer &L, int n);
 DeconvArgs deconv_geometry(int size, int stride, int pad, int h, int w, int cin_pad, int filters, int act, int in_dt);      // everything of DeconvArgs but pointers, strides, N, out_dt, Cstore
+GConvArgs gconv_geometry(int size, int stride, int pad, int h, int w, int cin, int filters, int groups, int act, int in_dt);      // the same of GConvArgs
 int run_layer(yolo_ctx *c, int i, int n);
 int stage_in(yolo_ctx *c, const void *images, int n, int fmt, int loc, float scale);
 int run_network(yolo_ctx *c, int n, bool lean = false);

@@ -151,6 +151,35 @@ void pack_deconv(const Layer &L, const float *bn_or_bias, const float *w_iohw, i
     }
 }
 
+// [convolutional] with groups > 1: batch norm folded as pack_conv folds it, then the bundle layout (GConvArgs, kernels.h): filter o of group
+// g = o / m lies in bundle g / t as row o (the bundles' rows are the output channels in order), its channel ci of tap (ky, kx) at column
+// (ky * size + kx) * kc + (g % t) * cg + ci; every other entry of the row is zero.  fp32: no bundling, column (ky * size + kx) * cg + ci
+void pack_gconv(const Layer &L, const float *bn_or_bias, const float *w_oihw, int wdt, std::vector<uint8_t> &wbuf, std::vector<float> &bias, int semantics)
+{
+    const int n = L.filters, k = L.size;
+    GConvArgs g; memset(&g, 0, sizeof g); g.C = L.cin; g.Cout = n; g.groups = L.groups; g.size = k; g.in_dt = wdt;
+    const size_t es = dt_size(wdt), total = gconv_layout(g);
+    bias.assign((size_t)g.nb * g.mb, 0.f);
+    std::vector<float> scale(n, 1.f);
+    if (L.bn) {
+        const float *beta = bn_or_bias, *gamma = beta + n, *mean = gamma + n, *var = mean + n;
+        for (int o = 0; o < n; ++o) {
+            const float s = semantics == YOLO_SEM_DARKNET ? gamma[o] / (sqrtf(var[o]) + 1e-6f) : gamma[o] / sqrtf(var[o] + 1e-5f);
+            scale[o] = s; bias[o] = beta[o] - mean[o] * s;
+        }
+    } else for (int o = 0; o < n; ++o) bias[o] = bn_or_bias[o];
+    wbuf.assign(total * es, 0);
+    for (int o = 0; o < n; ++o) {
+        const int gi = wdt == DT_F32 ? 0 : (o / g.m) % g.t;          // (fp32 rows hold the group's own channels only)
+        for (int ci = 0; ci < g.cg; ++ci) for (int tap = 0; tap < k * k; ++tap) {
+            const float v = w_oihw[((size_t)o * g.cg + ci) * k * k + tap] * scale[o];
+            const size_t idx = (size_t)o * g.kp + (size_t)tap * g.kc + gi * g.cg + ci;
+            if (wdt == DT_F32) memcpy(&wbuf[idx * 4], &v, 4);
+            else { const uint16_t b = wdt == DT_F16 ? f2h(v) : f2bf(v); memcpy(&wbuf[idx * 2], &b, 2); }
+        }
+    }
+}
+
 // fp8: scale of the tensor each layer's view holds, and per-input-channel scales of a conv
 void resolve_scales(yolo_ctx *c)
 {
@@ -268,6 +297,14 @@ int yolo_set_weights(yolo_ctx *c, const float *flat, size_t n)
             HIPCK(c, hipMemcpy(L.d_b, bias.data(), bias.size() * 4, hipMemcpyHostToDevice));
             continue;
         }
+        if (L.type == L_GCONV) {           // the file: [bias | beta gamma mean var] then filters * (cin / groups) * size^2 filters (DN/parser.c load_convolutional_weights: l.nweights)
+            const float *params = p; p += (size_t)L.filters * (L.bn ? 4 : 1);
+            const float *w = p; p += (size_t)L.filters * (L.cin / L.groups) * L.size * L.size;
+            pack_gconv(L, params, w, L.in_dt, wbuf, bias, c->semantics);
+            HIPCK(c, hipMemcpy(L.d_w, wbuf.data(), wbuf.size(), hipMemcpyHostToDevice));
+            HIPCK(c, hipMemcpy(L.d_b, bias.data(), bias.size() * 4, hipMemcpyHostToDevice));
+            continue;
+        }
         if (L.type != L_CONV) continue;
         const float *params = p; p += (size_t)L.filters * (L.bn ? 4 : 1);
         const float *w = p; p += (size_t)L.filters * L.cin * L.size * L.size;
@@ -366,7 +403,7 @@ int yolo_export(yolo_ctx *c, const char *path)
     for (auto &t : c->trees) { const uint32_t len[2] = {(uint32_t)t.path.size(), (uint32_t)t.text.size()}; w.put(len, sizeof len); w.put(t.path.data(), t.path.size()); w.put(t.text.data(), t.text.size()); }
     std::vector<uint8_t> buf;
     for (auto &L : c->layers) {
-        if (L.type != L_CONV && L.type != L_LOCAL && L.type != L_DECONV) continue;
+        if (L.type != L_CONV && L.type != L_LOCAL && L.type != L_DECONV && L.type != L_GCONV) continue;
         uint64_t sz[3] = {(uint64_t)L.cout_pad * L.kpad * dt_size(L.in_dt), (uint64_t)L.cout_pad, L.d_sc ? (uint64_t)L.cout_pad : 0};
         if (L.type == L_LOCAL) { sz[0] = (uint64_t)L.H * L.W * L.filters * L.size * L.size * L.cin * dt_size(L.in_dt); sz[1] = (uint64_t)L.H * L.W * L.filters; sz[2] = 0; }
         w.put(sz, sizeof sz);
@@ -422,7 +459,7 @@ yolo_ctx *yolo_create_from_file(const char *path, int max_batch, int device, voi
     if (c->dtype == YOLO_FP8 && yolo_set_act_scales(c, sc.data(), (int)hd.n_layers) != YOLO_OK) { fclose(f); return bail(c, c->err); }
     std::vector<uint8_t> buf;
     for (auto &L : c->layers) {
-        if (L.type != L_CONV && L.type != L_LOCAL && L.type != L_DECONV) continue;
+        if (L.type != L_CONV && L.type != L_LOCAL && L.type != L_DECONV && L.type != L_GCONV) continue;
         uint64_t sz[3]; r.get(sz, sizeof sz);
         uint64_t want[3] = {(uint64_t)L.cout_pad * L.kpad * dt_size(L.in_dt), (uint64_t)L.cout_pad, L.d_sc ? (uint64_t)L.cout_pad : 0};
         if (L.type == L_LOCAL) { want[0] = (uint64_t)L.H * L.W * L.filters * L.size * L.size * L.cin * dt_size(L.in_dt); want[1] = (uint64_t)L.H * L.W * L.filters; want[2] = 0; }

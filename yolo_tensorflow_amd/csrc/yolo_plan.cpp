@@ -99,7 +99,33 @@ int build_plan(yolo_ctx *c, const std::vector<Section> &secs)
         const Section &s = secs[i + 1]; Layer &L = c->layers[i];
         L.in = {i - 1};
         if (!c->split() && (s.kv.count("yolo_pair") || net.kv.count("yolo_pair_input"))) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: yolo_pair is a key of split-fp16 networks (YOLO_FP16X2)", i);
-        if (s.type == "convolutional") {
+        if (s.type == "convolutional" && opt_i(s, "groups", 1) != 1) {
+            // grouped convolution (DN/parser.c:184, DN/convolutional_layer.c:458-471): a layer kind of its own with its own kernel (gconv.hip).  Like
+            // [deconvolutional] it is never a member of a fused launch, neither end of a 1x1 tail, no host of a folded [shortcut] and nothing for
+            // the tile tuner to choose -- every marking pass asks for L_CONV
+            L.groups = opt_i(s, "groups", 1);
+            if (L.groups < 1) return fail(c, YOLO_ERR_INVALID, "layer %d: [convolutional] groups=%d", i, L.groups);
+            if (c->dtype == YOLO_FP8) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [convolutional] with groups=%d is not served in the fp8 configuration", i, L.groups);
+            if (c->split()) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [convolutional] with groups=%d is not served in the split-fp16 configuration", i, L.groups);
+            if (i == 0) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [convolutional] with groups=%d as the network's first layer is not served (the image is read by the dense kernels only)", i, L.groups);
+            L.type = L_GCONV; L.filters = opt_i(s, "filters", 1); L.size = opt_i(s, "size", 1); L.stride = opt_i(s, "stride", 1);
+            L.pad = opt_i(s, "pad", 0) ? L.size / 2 : opt_i(s, "padding", 0);
+            L.bn = opt_i(s, "batch_normalize", 0);
+            if (L.filters < 1) return fail(c, YOLO_ERR_INVALID, "layer %d: conv filters %d", i, L.filters);
+            if (C % L.groups) return fail(c, YOLO_ERR_INVALID, "layer %d: groups=%d does not divide the %d input channels", i, L.groups, C);
+            if (L.filters % L.groups) return fail(c, YOLO_ERR_INVALID, "layer %d: groups=%d does not divide filters=%d", i, L.groups, L.filters);
+            if (L.size < 1 || L.size > GCONV_MAX_SIZE) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: grouped conv size %d (1..%d are served)", i, L.size, GCONV_MAX_SIZE);
+            if (L.stride < 1 || L.stride > GCONV_MAX_STRIDE) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: grouped conv stride %d (1..%d are served)", i, L.stride, GCONV_MAX_STRIDE);
+            if (L.pad < 0 || L.pad >= L.size) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: grouped conv padding %d must be below its size %d", i, L.pad, L.size);
+            if (H + 2 * L.pad < L.size || W + 2 * L.pad < L.size) return fail(c, YOLO_ERR_INVALID, "layer %d: grouped conv larger than its padded input", i);
+            if (int r = plan_activation(c, i, s, "logistic", false)) return r;
+            L.in_dt = c->act_dt(); L.store_dt = c->act_dt();
+            L.cin = C; L.cin_pad = roundup(C, 8);
+            { GConvArgs g; memset(&g, 0, sizeof g); g.C = C; g.Cout = L.filters; g.groups = L.groups; g.size = L.size; g.in_dt = L.in_dt; gconv_layout(g); L.kpad = g.kp; L.cout_pad = g.nb * g.mb; }      // cout_pad * kpad elements of filters
+            H = (H + 2 * L.pad - L.size) / L.stride + 1; W = (W + 2 * L.pad - L.size) / L.stride + 1; C = L.filters;
+            c->conv_flops += 2.0 * L.size * L.size * (L.cin / L.groups) * L.filters * (double)H * W;      // DN/convolutional_layer.c:201, :325: c / groups
+            c->weights_count += (size_t)L.filters * (L.bn ? 4 : 1) + (size_t)L.filters * (L.cin / L.groups) * L.size * L.size;
+        } else if (s.type == "convolutional") {
             L.type = L_CONV; L.filters = opt_i(s, "filters", 1); L.size = opt_i(s, "size", 1); L.stride = opt_i(s, "stride", 1);
             L.pad = opt_i(s, "pad", 0) ? L.size / 2 : opt_i(s, "padding", 0);
             L.bn = opt_i(s, "batch_normalize", 0);
@@ -161,6 +187,7 @@ int build_plan(yolo_ctx *c, const std::vector<Section> &secs)
         } else if (s.type == "detection") {
             L.type = L_DETECT; L.classes = opt_i(s, "classes", 1); L.na = opt_i(s, "num", 1); L.side = opt_i(s, "side", 7); L.sqr = opt_i(s, "sqrt", 0);
             if (opt_i(s, "coords", 4) != 4 || opt_i(s, "softmax", 0)) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [detection] with coords != 4 or softmax", i);
+            if (i > 0 && c->layers[i - 1].type == L_GCONV) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: a [convolutional] with groups=%d directly in front of a [detection] head is not served ([detection] must follow a [connected] layer)", i - 1, c->layers[i - 1].groups);
             if (i == 0 || !c->layers[i - 1].fc) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [detection] must follow a [connected] layer", i);
             if (C != L.side * L.side * (L.classes + L.na * 5)) return fail(c, YOLO_ERR_INVALID, "layer %d: [detection] expects %d inputs, got %d", i, L.side * L.side * (L.classes + L.na * 5), C);
             if (c->attrs && c->attrs != 5 + L.classes) return fail(c, YOLO_ERR_UNSUPPORTED, "heads with different class counts");
@@ -250,6 +277,7 @@ int build_plan(yolo_ctx *c, const std::vector<Section> &secs)
             else L.anchors.assign(an.begin(), an.begin() + 2 * total);
             L.na = (int)L.anchors.size() / 2;
             if (L.na > 16) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: more than 16 anchors", i);
+            if (i > 0 && c->layers[i - 1].type == L_GCONV) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: a [convolutional] with groups=%d directly in front of a [%s] head is not served (the head's objectness plane and lean decode belong to the dense kernels; put a dense 1x1 conv in between)", i - 1, c->layers[i - 1].groups, s.type.c_str());
             if (i == 0 || c->layers[i - 1].type != L_CONV) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: head must follow a conv", i);
             if (C != L.na * (5 + L.classes)) return fail(c, YOLO_ERR_INVALID, "layer %d: head expects %d channels, conv gives %d", i, L.na * (5 + L.classes), C);
             if (c->attrs && c->attrs != 5 + L.classes) return fail(c, YOLO_ERR_UNSUPPORTED, "heads with different class counts");
@@ -287,14 +315,14 @@ int build_plan(yolo_ctx *c, const std::vector<Section> &secs)
             // the logits are never rounded to 16 bits: the conv that reaches this layer directly, or through one [avgpool], writes fp32
             int p = i - 1;
             if (p >= 0 && c->layers[p].type == L_AVGPOOL) p = c->layers[p].in[0];
-            if (p >= 0 && c->layers[p].type == L_CONV) c->layers[p].head = true;
+            if (p >= 0 && (c->layers[p].type == L_CONV || c->layers[p].type == L_GCONV)) c->layers[p].head = true;
         } else if (s.type == "cost") {
             L.type = L_ROUTE; L.cost = true;         // inference: identity (DN/cost_layer.c: forward returns without a truth)
         } else {
             return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: section [%s] is outside the inference hot path", i, s.type.c_str());
         }
         L.H = H; L.W = W; L.C = C;
-        if (L.type != L_CONV && L.type != L_LOCAL && L.type != L_DECONV) {
+        if (L.type != L_CONV && L.type != L_LOCAL && L.type != L_DECONV && L.type != L_GCONV) {
             // layers that move data keep the type of what they move; their operands must agree
             int dt = -1;
             for (int j : L.in) { const int dj = j < 0 ? c->act_dt() : c->layers[j].store_dt; if (dt >= 0 && dj != dt && (L.type == L_ROUTE || L.type == L_SHORTCUT)) return fail(c, YOLO_ERR_INVALID, "layer %d: operands stored in different types (yolo_store): a %s needs one type", i, L.type == L_ROUTE ? "route" : "shortcut"); if (dt < 0) dt = dj; }
@@ -336,7 +364,7 @@ int build_plan(yolo_ctx *c, const std::vector<Section> &secs)
             // fp32, and so do those (the `head` flag, as for logits)
             int p = o;
             while (p >= 0 && c->layers[p].type == L_ACTIVATE) { c->layers[p].head = true; c->layers[p].pair = false; p = c->layers[p].in[0]; }
-            if (p >= 0 && (c->layers[p].type == L_CONV || c->layers[p].type == L_DECONV)) { c->layers[p].head = true; c->layers[p].pair = false; }
+            if (p >= 0 && (c->layers[p].type == L_CONV || c->layers[p].type == L_DECONV || c->layers[p].type == L_GCONV)) { c->layers[p].head = true; c->layers[p].pair = false; }
             else for (int q = o; q >= 0 && q != p; q = c->layers[q].in[0]) c->layers[q].head = false;      // (nothing computes in front of them: they keep their producer's type)
         } else {
         if (o < 0 || c->layers[o].type != L_SOFTMAX) return fail(c, YOLO_ERR_INVALID, "cfg has no [yolo] / [region] / [detection] head");
@@ -449,7 +477,7 @@ int build_plan(yolo_ctx *c, const std::vector<Section> &secs)
         if (j >= 0 && c->layers[j].head != L.head) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [logistic] / [activation] of a detection head's fp32 tensor", i);
         if (j < 0 || c->keep_layers || routed || uses[j] != 1) continue;
         const Layer &P = c->layers[j];
-        L.inplace = (P.type == L_CONV || P.type == L_DECONV || P.type == L_LOCAL || P.type == L_SHORTCUT || P.type == L_L2NORM || P.type == L_UPSAMPLE || P.type == L_MAXPOOL ||
+        L.inplace = (P.type == L_CONV || P.type == L_DECONV || P.type == L_GCONV || P.type == L_LOCAL || P.type == L_SHORTCUT || P.type == L_L2NORM || P.type == L_UPSAMPLE || P.type == L_MAXPOOL ||
                      P.type == L_ACTIVATE) && !never_stored(P, j);
     }
     // storage assignment: st_of[i] = storage holding layer i's output
@@ -616,7 +644,7 @@ int allocate(yolo_ctx *c)
     HIPCK(c, hipMalloc((void **)&c->d_sbox, nr * 16)); HIPCK(c, hipMalloc((void **)&c->d_slabel, nr * 4)); HIPCK(c, hipMalloc((void **)&c->d_sscore, nr * 4));
     HIPCK(c, hipMalloc((void **)&c->d_counts, (size_t)c->max_batch * 4));
     // filters
-    for (auto &L : c->layers) if (L.type == L_CONV || L.type == L_DECONV) {
+    for (auto &L : c->layers) if (L.type == L_CONV || L.type == L_DECONV || L.type == L_GCONV) {
         size_t wb = (size_t)L.cout_pad * L.kpad * dt_size(L.in_dt);
         HIPCK(c, hipMalloc(&L.d_w, wb)); HIPCK(c, hipMemsetAsync(L.d_w, 0, wb, c->stream));
         HIPCK(c, hipMalloc((void **)&L.d_b, (size_t)L.cout_pad * 4)); HIPCK(c, hipMemsetAsync(L.d_b, 0, (size_t)L.cout_pad * 4, c->stream));

@@ -70,6 +70,24 @@ static DeconvArgs deconv_args(const yolo_ctx *c, const Layer &L, int n)
     return a;
 }
 
+GConvArgs gconv_geometry(int size, int stride, int pad, int h, int w, int cin, int filters, int groups, int act, int in_dt)
+{
+    GConvArgs a; memset(&a, 0, sizeof a);
+    a.size = size; a.stride = stride; a.pad = pad; a.H = h; a.W = w; a.C = cin; a.Cout = filters; a.groups = groups; a.act = act; a.in_dt = in_dt;
+    a.Ho = (h + 2 * pad - size) / stride + 1; a.Wo = (w + 2 * pad - size) / stride + 1;
+    gconv_layout(a);
+    return a;
+}
+
+static GConvArgs gconv_args(const yolo_ctx *c, const Layer &L, int n)
+{
+    const TView in = view_of(c, L.in[0]);
+    GConvArgs a = gconv_geometry(L.size, L.stride, L.pad, in.h, in.w, L.cin, L.filters, L.groups, L.act, L.in_dt);
+    a.in = in.ptr; a.in_stride = in.stride; a.wt = L.d_w; a.bias = L.d_b; a.out = L.out.ptr; a.out_stride = L.out.stride; a.out_dt = L.out.dt; a.N = n;
+    a.Cstore = std::min(L.out.stride, roundup(L.filters, L.out.dt == DT_F32 && L.head ? 4 : 8));      // zeros past the filters, as deconv_args
+    return a;
+}
+
 // split fp16: a layer that moves or interpolates values runs in fp32 between a join (hi + lo) and a split
 static int via_f32(yolo_ctx *c, const Layer &L, int n, int kind)
 {
@@ -268,6 +286,10 @@ int run_layer(yolo_ctx *c, int i, int n)
         HIPCK(c, launch_deconv(deconv_args(c, L, n), s));
         if (L.post_act != ACT_LINEAR) HIPCK(c, launch_activate(nview(L.out), false, L.post_act, s));
         break;
+    case L_GCONV:
+        HIPCK(c, launch_gconv(gconv_args(c, L, n), s));
+        if (L.post_act != ACT_LINEAR) HIPCK(c, launch_activate(nview(L.out), false, L.post_act, s));
+        break;
     case L_ACTIVATE: {
         TView out = nview(L.out);
         if (!L.inplace) {          // a tensor of its own (keep_layers, a second reader of the producer, a concat window): copied first
@@ -356,13 +378,13 @@ int stage_in(yolo_ctx *c, const void *images, int n, int fmt, int loc, float sca
     return YOLO_OK;
 }
 
-// the layer sequence of one forward.  `skip_conv`: the timing pass that runs everything but the convs; `ev`: per-layer events
+// the layer sequence of one forward.  `skip_conv`: the timing pass that runs everything but the convs (dense and grouped: conv_flops counts both); `ev`: per-layer events
 // (yolo_time_layers)
 static int run_layers(yolo_ctx *c, int n, bool skip_conv = false, std::vector<hipEvent_t> *ev = nullptr)
 {
     const int NL = (int)c->layers.size();
     for (int i = 0; i < NL; ++i) {
-        if (!(skip_conv && c->layers[i].type == L_CONV)) { int r = run_layer(c, i, n); if (r) return r; }
+        if (!(skip_conv && (c->layers[i].type == L_CONV || c->layers[i].type == L_GCONV))) { int r = run_layer(c, i, n); if (r) return r; }
         if (ev) HIPCK(c, hipEventRecord((*ev)[i + 1], c->stream));
     }
     return YOLO_OK;

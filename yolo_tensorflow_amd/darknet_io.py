@@ -18,7 +18,7 @@ CFG_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "cfg")
 
 def cfg_text(name):
     """Text of a shipped topology ('yolov3', 'yolov3-608', 'yolov3-tiny', 'yolov2', 'yolov2-tiny-voc', 'yolov1', 'yolov1-tiny', and the
-    classifiers 'darknet19', 'darknet53', 'resnet18', 'resnet50', 'vgg-16') or of a cfg file path.  tools/make_cfgs.py generates them,
+    classifiers 'darknet19', 'darknet53', 'resnet18', 'resnet50', 'resnext50', 'vgg-16') or of a cfg file path.  tools/make_cfgs.py generates them,
     and ResNet-34 / 101 / 152 on request (`resnet(depth)`)."""
     path = name if os.path.exists(name) else os.path.join(CFG_DIR, name + ".cfg")
     if not os.path.exists(path) and os.path.exists(os.path.join(CFG_DIR, "zoo", name + ".cfg")):
@@ -127,7 +127,7 @@ def bf16_flop_share(secs):
     for i, s in enumerate(L):
         if s["type"] != "convolutional":
             continue
-        f = 2.0 * int(s["size"]) ** 2 * shapes[i][4] * shapes[i][3] * shapes[i][1] * shapes[i][2]
+        f = 2.0 * int(s["size"]) ** 2 * (shapes[i][4] // int(s.get("groups", 1))) * shapes[i][3] * shapes[i][1] * shapes[i][2]
         tot += f
         if i == 0 or is16(i - 1):
             b16 += f
@@ -245,7 +245,9 @@ def layer_shapes(secs):
 
 def conv_specs(secs):
     """Per parameterised layer in file order ([convolutional], [deconvolutional] -- the same parameter counts, its filters stored
-    [cin][filters][size][size] --, and [connected] as a 1x1 conv over the flattened producer): dict(filters, size, cin, bn, head, index)."""
+    [cin][filters][size][size] --, and [connected] as a 1x1 conv over the flattened producer): dict(filters, size, cin, groups, bn, head, index).
+    `cin` is the producer's channel count; a [convolutional] section with groups= holds filters * (cin / groups) * size^2 filter values,
+    [filters][cin / groups][size][size] (DN/convolutional_layer.c:201)."""
     shapes = layer_shapes(secs)
     layers = secs[1:]
     out = []
@@ -253,6 +255,7 @@ def conv_specs(secs):
         head = i + 1 < len(layers) and layers[i + 1]["type"] in ("yolo", "region", "detection")
         if s["type"] in ("convolutional", "deconvolutional"):
             out.append(dict(filters=int(s["filters"]), size=int(s.get("size", 1)), cin=shapes[i][4],
+                            groups=int(s.get("groups", 1)) if s["type"] == "convolutional" else 1,
                             bn=int(s.get("batch_normalize", 0)), head=head, index=i))
         elif s["type"] == "connected":
             out.append(dict(filters=int(s["output"]), size=1, cin=shapes[i][4], bn=0, head=head, index=i))
@@ -265,7 +268,7 @@ def weights_count(secs):
     n = 0
     for c in conv_specs(secs):
         loc = c.get("locations", 1)
-        n += c["filters"] * loc * (4 if c["bn"] else 1) + loc * c["filters"] * c["cin"] * c["size"] ** 2
+        n += c["filters"] * loc * (4 if c["bn"] else 1) + loc * c["filters"] * (c["cin"] // c.get("groups", 1)) * c["size"] ** 2
     return n
 
 
@@ -316,7 +319,7 @@ def synth_weights(secs, seed=0, obj_bias=-0.75, stats="benign"):
     for i, s in enumerate(layers):
         t = s["type"]
         if t == "convolutional":
-            n, k, cin = int(s["filters"]), int(s["size"]), shapes[i][4]
+            n, k, cin = int(s["filters"]), int(s["size"]), shapes[i][4] // int(s.get("groups", 1))      # fan-in: a group's own channels
             head = i + 1 < len(layers) and layers[i + 1]["type"] in ("yolo", "region")
             if int(s.get("batch_normalize", 0)):
                 pre_var = 2.0 * cur                                   # k*k*cin * (2/(k*k*cin)) * E[x^2]
@@ -461,14 +464,19 @@ def synth_weights_log(secs, seed=0, obj_bias=-0.75, real=None):
             ci += 1
             n, k, cin = int(s["filters"]), int(s["size"]), shapes[i][4]
             head = i + 1 < len(layers) and layers[i + 1]["type"] in ("yolo", "region")
+            # the input moments as every filter sees them, [1 or n][cin]: all channels, or with groups= its own group's
+            G = int(s.get("groups", 1))
+            cin //= G
+            rows = np.arange(n) // (n // G) if G > 1 else [0]
+            pm, pv = pm.reshape(G, cin)[rows], pv.reshape(G, cin)[rows]
             w = rng.normal(0, 1.0, (n, cin, k * k))
             ex2 = pv + pm * pm
             if int(s.get("batch_normalize", 0)) and real is not None:
                 r = real[ci]
                 target = np.maximum(r["var"].astype(np.float64), 1e-30)
-                unit_var = (w * w * pv[None, :, None]).sum((1, 2))
+                unit_var = (w * w * pv[:, :, None]).sum((1, 2))
                 w *= np.sqrt(target / np.maximum(unit_var, 1e-30))[:, None, None]
-                rmean = (w * pm[None, :, None]).sum((1, 2))
+                rmean = (w * pm[:, :, None]).sum((1, 2))
                 gamma, beta = r["gamma"].astype(np.float64), r["beta"].astype(np.float64)
                 parts += [beta, gamma, rmean, target, w.reshape(-1)]
                 std = np.abs(gamma) * np.sqrt(target / (target + 1e-5))
@@ -479,9 +487,9 @@ def synth_weights_log(secs, seed=0, obj_bias=-0.75, real=None):
                 target = np.exp(rng.uniform(np.log(lo), np.log(hi), n))
                 tiny = rng.random(n) < 0.03
                 target[tiny] = np.exp(rng.uniform(np.log(8e-4), np.log(1e-2), int(tiny.sum())))
-                unit_var = (w * w * pv[None, :, None]).sum((1, 2))
+                unit_var = (w * w * pv[:, :, None]).sum((1, 2))
                 w *= np.sqrt(target / np.maximum(unit_var, 1e-30))[:, None, None]
-                rmean = (w * pm[None, :, None]).sum((1, 2))                                  # what the conv produces on average
+                rmean = (w * pm[:, :, None]).sum((1, 2))                                  # what the conv produces on average
                 rvar = target * rng.uniform(0.9, 1.1, n)                                     # running average vs this batch
                 gamma = np.exp(rng.normal(0.25, 0.45, n)); gamma = np.clip(gamma, 0.0017, 4.7)
                 gamma *= np.where(rng.random(n) < 0.06, -1.0, 1.0)
@@ -501,10 +509,10 @@ def synth_weights_log(secs, seed=0, obj_bias=-0.75, real=None):
                         b[:, 0:4] = rng.normal(0, .5, (na, 4))
                         b[:, 4] = obj_bias + rng.normal(0, .5, na)
                         b = b.reshape(-1)
-                w *= np.sqrt(1.0 / np.maximum((ex2[None, :, None] * np.ones((1, 1, k * k))).sum(), 1e-30))
+                w *= np.sqrt(1.0 / np.maximum((ex2[:, :, None] * np.ones((1, 1, k * k))).sum((1, 2)), 1e-30))[:, None, None]
                 parts += [b, w.reshape(-1)]
-                m1, m2 = b + (w * pm[None, :, None]).sum((1, 2)), None
-                v_out = (w * w * pv[None, :, None]).sum((1, 2))
+                m1, m2 = b + (w * pm[:, :, None]).sum((1, 2)), None
+                v_out = (w * w * pv[:, :, None]).sum((1, 2))
                 m2 = v_out + m1 * m1
             mean[i] = m1; var[i] = np.maximum(m2 - m1 * m1, 1e-12)
         elif t == "shortcut":
@@ -607,7 +615,7 @@ def pair_flop_share(secs, pair):
     tot = three = 0.0
     for i, s in enumerate(secs[1:]):
         if s["type"] == "convolutional":
-            f = 2.0 * int(s["size"]) ** 2 * shapes[i][4] * int(s["filters"]) * shapes[i][1] * shapes[i][2]
+            f = 2.0 * int(s["size"]) ** 2 * (shapes[i][4] // int(s.get("groups", 1))) * int(s["filters"]) * shapes[i][1] * shapes[i][2]
             tot += f; three += f if pair.get(i - 1, False) else 0.0
     return three / tot
 
