@@ -159,7 +159,8 @@ def test_conv_fp32_exact_path(hiplib, shape):
 
 def test_upsample(hiplib):
     rng = np.random.default_rng(12)
-    for shape in ((2, 13, 13, 256), (1, 26, 26, 128), (1, 1, 1, 8), (3, 5, 7, 16)):
+    # (the last three: channel counts that are no multiples of 8 -- the last granule of a pixel is ragged -- on odd and non-square extents)
+    for shape in ((2, 13, 13, 256), (1, 26, 26, 128), (1, 1, 1, 8), (3, 5, 7, 16), (2, 7, 5, 20), (1, 1, 1, 3), (3, 15, 22, 12)):
         x = R.to_bf16(rng.standard_normal(shape).astype(np.float32))
         # TF bilinear `_upsample`: same fp32 lerp order as the oracle, rounded once to bf16 -> bit-exact
         assert np.array_equal(hiplib.op_upsample2x(x, hiplib.SEM_TF), R.to_bf16(R.upsample_tf(x)))
@@ -176,6 +177,19 @@ def test_reorg_and_maxpool(hiplib):
         if shape[1] % 2 == 0:
             assert np.array_equal(hiplib.op_maxpool(x, 2, 2), R.max_pool(x, 2, 2))
         assert np.array_equal(hiplib.op_maxpool(x, 2, 1), R.max_pool(x, 2, 1))     # 'SAME' stride-1 pool, -inf padding
+    # ragged channel counts (no multiples of 8), odd and non-square extents: 2/2, 2/1, 3/2, 3/1 with darknet's default padding (size - 1) / 2
+    # (3/1 pads by 1 on each side and keeps (h + 2) x (w + 2) outputs: its last row and column see no input at all and are -inf in both)
+    for shape in ((2, 7, 5, 20), (1, 1, 1, 3), (3, 15, 22, 12)):
+        x = R.to_bf16(rng.standard_normal(shape).astype(np.float32))
+        for size, stride in ((2, 2), (2, 1), (3, 2), (3, 1)):
+            if (shape[1] + 2 * ((size - 1) // 2)) // stride < 1:
+                continue          # (1 x 1 under a 2/2 pool: no output pixel)
+            got, want = hiplib.op_maxpool(x, size, stride), R.max_pool(x, size, stride, (size - 1) // 2)
+            assert got.shape == want.shape and np.array_equal(got, want), (shape, size, stride)
+    # reorg of 20 channels: block (dy, dx) of space_to_depth begins at channel (dy * 2 + dx) * 20, in the middle of a granule
+    x = R.to_bf16(rng.standard_normal((2, 6, 10, 20)).astype(np.float32))
+    assert np.array_equal(hiplib.op_reorg(x, 2, hiplib.SEM_TF), R.space_to_depth(x, 2))
+    assert np.array_equal(hiplib.op_reorg(x, 2, hiplib.SEM_DARKNET), R.reorg_darknet(x, 2))
 
 
 def test_resize_u8_legacy_bilinear(hiplib):

@@ -26,6 +26,10 @@ Runs only in the build container (it reads /root/reference and oracle/_ref); the
   mini_v3_rect.npz / mini_v2_rect.npz / mini_cls_rect.npz / mini_v3_rect_letterbox.npz
                      the minis at width != height (64 high x 96 wide, 96 x 64, 64 x 96): layers and boxes as above; the letterbox file holds
                      the reference's own letterbox_image of three source images and its corrected boxes at each image's size
+  mini_edges.npz
+                    the layers that move data and the dense conv's geometry keys at ragged channel counts (a map network, 15 high x 22
+                    wide: pad=0, padding=2, stride 3, five max-pool geometries, reorg, a concatenation at channel offset 20): three
+                    images, every layer's output from the compiled reference; written with fixed member dates, so it regenerates byte for byte
   yolov3_bn_real.npz / yolov2_bn_real.npz
                      the COMPLETE batch-norm vectors (beta, gamma, rolling mean, rolling variance) of every
                      batch-normalised conv of yolov3.weights / yolov2.weights, and the first l.n filter
@@ -913,6 +917,94 @@ def gen_mini_cls_rect():
     net.close()
 
 
+def _econv(filters, size, stride=1, pad=None, padding=None, bn=False, act="leaky"):
+    """a [convolutional] section with its geometry keys spelled out: pad=1 (size / 2), or pad=0 and a literal padding="""
+    geo = "pad=1\n" if pad else "pad=0\n" + ("padding=%d\n" % padding if padding is not None else "")
+    return "[convolutional]\n%sfilters=%d\nsize=%d\nstride=%d\n%sactivation=%s\n\n" % ("batch_normalize=1\n" if bn else "", filters, size, stride, geo, act)
+
+
+def _pool(size, stride, padding=None):
+    return "[maxpool]\nsize=%d\nstride=%d\n%s\n" % (size, stride, "padding=%d\n" % padding if padding is not None else "")
+
+
+def mini_edges_cfg(height=15, width=22):
+    """The layers that move data and the dense conv's geometry keys at the edges the planner accepts: a map network on a 15 high x 22 wide
+    input whose channel counts are no multiples of 8 or 4 where a layer allows it (3 -> 20 -> 12 -> 27 -> 20).  Layer by layer (H x W x C):
+      0 conv 3x3 pad=0 ("valid"), bn                      13 x 20 x 20
+      1 maxpool 2/2 on odd extents                          6 x 10 x 20
+      2 maxpool 3/2 padding=0                               3 x  5 x 20
+      3 conv 1x1, bn                                        3 x  5 x 12
+      4 route 0 (one input)                                13 x 20 x 20
+      5 conv 3x3 pad=0 padding=2, bias: windows of padding 15 x 22 x 12
+      6 maxpool 3/2 (padding 1)                             8 x 12 x 12
+      7 conv 3x3 pad=0 padding=2 stride=2, bias, linear     5 x  7 x 27
+      8 maxpool 2/1                                         5 x  7 x 27
+      9 conv 3x3 stride=2 pad=1, bn                         3 x  4 x 20
+     10 upsample 2                                          6 x  8 x 20
+     11 conv 3x3 pad=1, bias, leaky                         6 x  8 x 20
+     12 shortcut from 10 (identity; layer 11 is read again by 15, so no plan folds the add into the conv)
+     13 reorg 2                                             3 x  4 x 80
+     14 conv 3x3 pad=0 ("valid"), bias                       1 x  2 x 12
+     15 route 11 (one input)                                6 x  8 x 20
+     16 maxpool 3/1 padding=0                               6 x  8 x 20
+     17 route 5 (one input)                                15 x 22 x 12
+     18 conv 3x3 stride=3 pad=0 padding=2, bias             6 x  8 x 12
+     19 route 16, 18: 20 + 12 channels, the second at channel offset 20
+     20 conv 3x3 pad=1 to 6 channels, bias, linear: the map 6 x 8 x 6
+    Every pool has padding < min(size, stride): no window lies wholly outside its tensor (there darknet writes -FLT_MAX, the device -inf).
+    No 1x1 conv here has a padding or a stride: the reference's forward_convolutional_layer hands a 1x1 conv's input to gemm without im2col
+    (DN/convolutional_layer.c:468), as if stride were 1 and padding 0 -- with padding=1 it reads past its input (two runs of this generator
+    gave two answers), with stride=2 it reads the wrong pixels.  Those two layers are tested on the device against the convolution's
+    definition instead (tests/test_gpu_edges.py)."""
+    return ("[net]\nbatch=1\nwidth=%d\nheight=%d\nchannels=3\nyolo_output=map\n\n" % (width, height) +
+            _econv(20, 3, pad=0, bn=True) + _pool(2, 2) + _pool(3, 2, 0) + _econv(12, 1, pad=0, bn=True) + "[route]\nlayers=0\n\n" +
+            _econv(12, 3, padding=2) + _pool(3, 2) + _econv(27, 3, stride=2, padding=2, act="linear") + _pool(2, 1) + _econv(20, 3, stride=2, pad=1, bn=True) +
+            "[upsample]\nstride=2\n\n" + _econv(20, 3, pad=1) + "[shortcut]\nfrom=-2\nactivation=linear\n\n[reorg]\nstride=2\n\n" + _econv(12, 3, pad=0) +
+            "[route]\nlayers=11\n\n" + _pool(3, 1, 0) + "[route]\nlayers=5\n\n" + _econv(12, 3, stride=3, padding=2) + "[route]\nlayers=16,18\n\n" +
+            _econv(6, 3, pad=1, act="linear"))
+
+
+def save_npz_reproducibly(path, data):
+    """np.savez_compressed with a fixed member date: the same arrays give the same bytes"""
+    import zipfile
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as z:
+        for key, val in data.items():
+            info = zipfile.ZipInfo(key + ".npy", date_time=(1980, 1, 1, 0, 0, 0)); info.compress_type = zipfile.ZIP_DEFLATED; info.external_attr = 0o644 << 16
+            with z.open(info, "w") as f:
+                np.lib.format.write_array(f, np.asanyarray(val), allow_pickle=False)
+
+
+def gen_edges():
+    """mini_edges_cfg through the compiled reference (maxpool_layer.c, upsample_layer.c, reorg_layer.c, route_layer.c, shortcut_layer.c and
+    convolutional_layer.c with pad=0 / padding= / stride), the recipe of gen_mini_unet: cfg text, weights (filters bf16-exact), three images,
+    every layer's output for each of them (separate predicts), `max_abs` per layer."""
+    from oracle import darknet_ref as D
+    from yolo_tensorflow_amd import darknet_io as IO
+    name, cfg, hw, seed = "mini_edges", mini_edges_cfg(), (15, 22), 71
+    secs = IO.parse_cfg(cfg)
+    flat = IO.bf16_exact_filters(secs, IO.synth_weights(secs, seed=seed))
+    imgs = np.random.default_rng(seed + 1).integers(0, 256, (3, hw[0], hw[1], 3), dtype=np.uint8)
+    x = imgs.astype(np.float32) / np.float32(255.0)
+    net = D.RefNet(cfg, flat, 0, 2)
+    outs = [[] for _ in range(net.n)]
+    for b in range(3):
+        net.predict(x[b])
+        for i in range(net.n):
+            outs[i].append(np.asarray(net.layer_output_nhwc(i), dtype=np.float32)[0])
+    data = {"cfg": np.array(cfg), "weights": flat, "images_u8": imgs}
+    for i in range(net.n):
+        data["layer_%02d" % i] = np.stack(outs[i])
+    data["max_abs"] = np.array([np.abs(data["layer_%02d" % i]).max() for i in range(net.n)], dtype=np.float32)
+    shapes = IO.layer_shapes(secs)
+    for i in range(net.n):
+        assert data["layer_%02d" % i].shape[1:] == shapes[i][1:4], (i, data["layer_%02d" % i].shape, shapes[i])
+        assert np.isfinite(data["layer_%02d" % i]).all() and np.abs(data["layer_%02d" % i]).max() < 1e30, "layer %d holds -FLT_MAX: a pool window wholly outside its tensor" % i
+    net.close()
+    path = os.path.join(OUT, name + ".npz")
+    save_npz_reproducibly(path, data)
+    print(name, "layers", len(shapes), "map", data["layer_%02d" % (len(shapes) - 1)].shape[1:], "max_abs", np.round(data["max_abs"], 3).tolist(), os.path.getsize(path), "bytes")
+
+
 def gen_rect():
     gen_mini_rect("mini_v3_rect", MINI_V3, 4, 64, 96, letterbox=True)
     gen_mini_rect("mini_v2_rect", MINI_V2, 5, 96, 64)
@@ -935,6 +1027,8 @@ if __name__ == "__main__":
         gen_darknet_py_symbols(); sys.exit(0)
     if sys.argv[1:] == ["rect"]:
         gen_rect(); sys.exit(0)
+    if sys.argv[1:] == ["edges"]:
+        gen_edges(); sys.exit(0)
     stub_modules()
     gen_nms_v3()
     gen_v2_post()
@@ -947,6 +1041,7 @@ if __name__ == "__main__":
     gen_mini_unet()
     gen_mini_grouped()
     gen_rect()
+    gen_edges()
     gen_bn_real()
     gen_known_answers()
     gen_darknet_py_symbols()

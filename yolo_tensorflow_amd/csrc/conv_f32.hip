@@ -102,10 +102,13 @@ __global__ __launch_bounds__(64 * WP * WC) void conv_igemm_f32(const ConvArgs a)
     }
 
     const float *__restrict__ res = (const float *)a.res;
+    // channels Cout .. of the last 8-channel granule are stored as zeros (as the 16-bit epilogues store whole granules): the layers that
+    // move granules read them, and a pooled buffer's last tenant may have left anything there
+    const int cstore = min(a.out_stride, (a.Cout + 7) & ~7);
 #pragma unroll
     for (int i = 0; i < TC; ++i) {
         const int ch = ct * BC + (wci * TC + i) * 16 + lq * 4;
-        if (ch >= a.Cout) continue;
+        if (ch >= cstore) continue;
         const float4 bv = *(const float4 *)(a.bias + ch);
 #pragma unroll
         for (int j = 0; j < TP; ++j) {
@@ -117,13 +120,13 @@ __global__ __launch_bounds__(64 * WP * WC) void conv_igemm_f32(const ConvArgs a)
 #pragma unroll
                 for (int q = 0; q < 4; ++q) v[q] = fmaxf(v[q], slope * v[q]);
             }
-            if (res) {
+            if (res && ch < a.Cout) {
                 const float4 rv = *(const float4 *)(res + (size_t)m * a.res_stride + ch);
                 v[0] += rv.x; v[1] += rv.y; v[2] += rv.z; v[3] += rv.w;
             }
             float *o = (float *)a.out + (size_t)m * a.out_stride + ch;
             if (ch + 3 < a.Cout) *(float4 *)o = float4{v[0], v[1], v[2], v[3]};
-            else for (int q = 0; q < 4; ++q) if (ch + q < a.Cout) o[q] = v[q];
+            else for (int q = 0; q < 4; ++q) if (ch + q < cstore) o[q] = ch + q < a.Cout ? v[q] : 0.f;
         }
     }
 }

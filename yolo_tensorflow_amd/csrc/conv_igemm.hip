@@ -222,7 +222,7 @@ template <int WP, int WC, int TP, int TC, int NS, int BK, int NL, int EB, bool H
 static hipError_t launch_t(const ConvArgs &a, hipStream_t s)
 {
     // 32-bit buffer offsets: the activation window must stay below 2 GiB
-    if (((double)a.N * a.H * a.W * a.in_stride + 2.0 * (a.W + 1) * a.in_stride) * EB >= 2147483648.0) return hipErrorInvalidValue;
+    if (((double)a.N * a.H * a.W * a.in_stride + ((a.pad > 1 ? a.pad : 1) + 1.0) * (a.W + 1) * a.in_stride) * EB >= 2147483648.0) return hipErrorInvalidValue;
     constexpr int BKE = BK * 2 / EB;
     if (a.Kpad % BKE) return hipErrorInvalidValue;
     return (a.Cin_pad % BKE) == 0 ? launch_u<WP, WC, TP, TC, NS, BK, NL, true, EB, H16, SPLIT>(a, s) : launch_u<WP, WC, TP, TC, NS, BK, NL, false, EB, H16, SPLIT>(a, s);

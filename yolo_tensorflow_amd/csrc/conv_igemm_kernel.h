@@ -232,9 +232,11 @@ __global__ __launch_bounds__(64 * (WP * WC + NL)) void conv_igemm(const ConvArgs
         bn = fast_div(pt, a.bpi_mul, a.bpi_shift); const int r = pt - bn * bpi; by = fast_div(r, a.bpr_mul, a.bpr_shift); bx = r - by * bpr;
     }
 
-    // Buffer descriptors.  The activation base is moved back by (W+1) pixels so that the offset of tap (0,0) of a
-    // border pixel (one row up, one column left) is still >= 0.
-    const int shift = HALO ? 0 : (a.W + 1) * a.in_stride * EB;      // bytes (the halo form only forms in-image offsets)
+    // Buffer descriptors.  The activation base is moved back by `lead` = pad x (W+1) pixels (at least one W+1) so that the offset
+    // of tap (0,0) of a border pixel (pad rows up, pad columns left) is still >= 0: a negative one would wrap past num_records
+    // and the DMA would write zeros for taps that are inside the image.
+    const int lead = (a.pad > 1 ? a.pad : 1) * (a.W + 1);           // pixels
+    const int shift = HALO ? 0 : lead * a.in_stride * EB;           // bytes (the halo form only forms in-image offsets)
     __amdgpu_buffer_rsrc_t rx = buf_rsrc((const char *)a.in - shift);
     __amdgpu_buffer_rsrc_t rw = buf_rsrc(a.wt);
 
@@ -290,8 +292,8 @@ __global__ __launch_bounds__(64 * (WP * WC + NL)) void conv_igemm(const ConvArgs
             const int prow = (wid + i * NW) * RG + rl;
             const int m = pt * BP + prow;
             const bool ok = m < M && prow < BP;
-            // (the descriptor base sits (W + 1) pixels before the tensor, see `shift`)
-            rowoff[i] = (unsigned)((m + a.W + 1) * a.in_stride) * (unsigned)EB + (UNI ? (unsigned)(chunk * EPC * EB) : 0u);
+            // (the descriptor base sits `lead` pixels before the tensor, see `shift`)
+            rowoff[i] = (unsigned)((m + lead) * a.in_stride) * (unsigned)EB + (UNI ? (unsigned)(chunk * EPC * EB) : 0u);
             tapmask[i] = ok ? 1u : 0u;
         }
     }
@@ -309,7 +311,7 @@ __global__ __launch_bounds__(64 * (WP * WC + NL)) void conv_igemm(const ConvArgs
                 const int oy = fast_div(rem, a.wo_mul, a.wo_shift);
                 const int ox = rem - oy * a.Wo;
                 const int iy0 = oy * a.stride - a.pad, ix0 = ox * a.stride - a.pad;
-                off = (unsigned)(((n * a.H + iy0) * a.W + ix0 + a.W + 1) * a.in_stride) * (unsigned)EB;
+                off = (unsigned)(((n * a.H + iy0) * a.W + ix0 + lead) * a.in_stride) * (unsigned)EB;
                 if (a.ksize == 3) {
                     unsigned ry = 0, cx = 0;
 #pragma unroll

@@ -12,7 +12,7 @@ static hipError_t launch_p(const ConvArgs &a, hipStream_t s)
 {
     constexpr int BK = 64, BP = WP * TP * 16, BC = WC * TC * 16;
     // 32-bit buffer offsets: the activation window must stay below 2 GiB; whole 32-channel groups
-    if (((double)a.N * a.H * a.W * a.in_stride + 2.0 * (a.W + 1) * a.in_stride) * 2 >= 2147483648.0) return hipErrorInvalidValue;
+    if (((double)a.N * a.H * a.W * a.in_stride + ((a.pad > 1 ? a.pad : 1) + 1.0) * (a.W + 1) * a.in_stride) * 2 >= 2147483648.0) return hipErrorInvalidValue;
     if (a.Kpad % 64 || a.Cin_pad % 64 || a.kchunk != 64) return hipErrorInvalidValue;
     const long M = (long)a.N * a.Ho * a.Wo;
     const long tiles = ((M + BP - 1) / BP) * ((a.Cout + BC - 1) / BC);

@@ -2,12 +2,18 @@
 // upsample (row U), max-pool (row M), space-to-depth / darknet reorg (row R), residual add and strided
 // copies (rows B, Rt when they cannot be fused into a conv epilogue), dtype conversion for introspection.
 // One thread moves an 8-channel granule (16 B of bf16, 32 B of fp32) so global accesses are 16-B vectors
-// and consecutive lanes touch consecutive addresses along the channel axis.
+// and consecutive lanes touch consecutive addresses along the channel axis.  A tensor of C channels has ceil(C / 8) granules: its pixel
+// stride is a multiple of 8, and the channels C .. of the last granule are zeros that every layer stores again (a consumer multiplies
+// them by zero filters; a stale Inf or NaN there would not survive that).
 #include "kernels.h"
 #include "device_common.h"
 #include <math.h>
+#include <algorithm>
 
 #include "elt.h"
+
+// do `c` channels fit both pixel strides as whole 8-channel granules?
+static inline bool granules_ok(int c, int stride_a, int stride_b) { const int c8 = (c + 7) / 8; return c >= 1 && stride_a >= c8 * 8 && stride_b >= c8 * 8; }
 
 // ---- row P: uint8/float image at network size -> 8-channel (3 real + 5 zero) activation ---------
 template <typename T>
@@ -208,14 +214,17 @@ __global__ void k_upsample2x(const T *in, int is, T *out, int os, int n, int h, 
 
 hipError_t launch_upsample2x(const TView &in, const TView &out, int bilinear, hipStream_t s)
 {
-    size_t total = (size_t)in.n * 4 * in.h * in.w * (in.c / 8);
-    WITH_DT(in.dt, hipLaunchKernelGGL(k_upsample2x<T>, grid_for(total), dim3(256), 0, s, (const T *)in.ptr, in.stride, (T *)out.ptr, out.stride, in.n, in.h, in.w, in.c / 8, bilinear));
+    if (in.dt != out.dt || !granules_ok(in.c, in.stride, out.stride)) return hipErrorInvalidValue;
+    const int c8 = (in.c + 7) / 8;
+    size_t total = (size_t)in.n * 4 * in.h * in.w * c8;
+    WITH_DT(in.dt, hipLaunchKernelGGL(k_upsample2x<T>, grid_for(total), dim3(256), 0, s, (const T *)in.ptr, in.stride, (T *)out.ptr, out.stride, in.n, in.h, in.w, c8, bilinear));
     return hipGetLastError();
 }
 
-// ---- row M: max-pool, window origin -pad, out-of-range = -inf (DN/maxpool_layer.c:79-111 == TF) ----
+// ---- row M: max-pool, window origin -pad, out-of-range = -inf (DN/maxpool_layer.c:79-111 == TF); the lanes at and beyond channel `c` of
+//      the last granule are stored as zeros whatever the window held ----
 template <typename T>
-__global__ void k_maxpool(const T *in, int is, T *out, int os, int n, int h, int w, int ho, int wo, int c8,
+__global__ void k_maxpool(const T *in, int is, T *out, int os, int n, int h, int w, int ho, int wo, int c8, int c,
                           int size, int stride, int pad)
 {
     size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -237,13 +246,19 @@ __global__ void k_maxpool(const T *in, int is, T *out, int os, int n, int h, int
                 for (int i = 0; i < 8; ++i) m[i] = v[i] > m[i] ? v[i] : m[i];
             }
         }
+    if (g * 8 + 8 > c) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) if (g * 8 + i >= c) m[i] = 0.f;
+    }
     Elt<T>::store8(out + (((size_t)b * ho + oy) * wo + ox) * os + g * 8, m);
 }
 
 hipError_t launch_maxpool(const TView &in, const TView &out, int size, int stride, int pad, hipStream_t s)
 {
-    size_t total = (size_t)out.n * out.h * out.w * (in.c / 8);
-    WITH_DT(in.dt, hipLaunchKernelGGL(k_maxpool<T>, grid_for(total), dim3(256), 0, s, (const T *)in.ptr, in.stride, (T *)out.ptr, out.stride, in.n, in.h, in.w, out.h, out.w, in.c / 8, size, stride, pad));
+    if (in.dt != out.dt || !granules_ok(in.c, in.stride, out.stride) || size < 1 || stride < 1 || pad < 0) return hipErrorInvalidValue;
+    const int c8 = (in.c + 7) / 8;
+    size_t total = (size_t)out.n * out.h * out.w * c8;
+    WITH_DT(in.dt, hipLaunchKernelGGL(k_maxpool<T>, grid_for(total), dim3(256), 0, s, (const T *)in.ptr, in.stride, (T *)out.ptr, out.stride, in.n, in.h, in.w, out.h, out.w, c8, in.c, size, stride, pad));
     return hipGetLastError();
 }
 
@@ -264,15 +279,40 @@ __global__ void k_space_to_depth(const T *in, int is, T *out, int os, int n, int
     Elt<T>::store8(out + (((size_t)b * (h / st) + oy) * (w / st) + ox) * os + oc, v);
 }
 
-// Darknet: with x,out as NCHW flat buffers of the *input* geometry (w,h,c): out[in_index] = x[out_index]
-// (DN/blas.c:9-30, forward=0), the result then reinterpreted as [c*s*s, h/s, w/s].
+// ... for a channel count that is no multiple of 8 (block (dy, dx) begins at channel (dy * st + dx) * c, not at a granule): one output
+// element per lane; the channels c * st * st .. cw of an output pixel are stored as zeros
 template <typename T>
-__global__ void k_reorg_darknet(const T *in, int is, T *out, int os, int n, int h, int w, int c, int st)
+__global__ void k_space_to_depth_elems(const T *in, int is, T *out, int os, int n, int h, int w, int c, int st, int cw)
 {
     size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    size_t per = (size_t)h * w * c;
+    const int ho = h / st, wo = w / st;
+    if (idx >= (size_t)n * ho * wo * cw) return;
+    const int co = (int)(idx % cw); size_t p = idx / cw;
+    const int ox = (int)(p % wo); p /= wo;
+    const int oy = (int)(p % ho), b = (int)(p / ho);
+    float v = 0.f;
+    if (co < c * st * st) {
+        const int blk = co / c, ch = co - blk * c, dy = blk / st, dx = blk - dy * st;
+        v = Elt<T>::load1(in + (((size_t)b * h + oy * st + dy) * w + ox * st + dx) * is + ch);
+    }
+    Elt<T>::store1(out + (((size_t)b * ho + oy) * wo + ox) * os + co, v);
+}
+
+// Darknet: with x,out as NCHW flat buffers of the *input* geometry (w,h,c): out[in_index] = x[out_index]
+// (DN/blas.c:9-30, forward=0), the result then reinterpreted as [c*s*s, h/s, w/s].  `cw` >= c*s*s: the channels of an output pixel that
+// are stored; those past c*s*s (t >= h*w*c below) as zeros.
+template <typename T>
+__global__ void k_reorg_darknet(const T *in, int is, T *out, int os, int n, int h, int w, int c, int st, int cw)
+{
+    size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    size_t per = (size_t)(h / st) * (w / st) * cw;
     if (idx >= per * n) return;
     int b = (int)(idx / per); int t = (int)(idx - (size_t)b * per);      // t = in_index
+    if (t >= h * w * c) {
+        const int wz = w / st, hz = h / st;
+        Elt<T>::store1(out + (((size_t)b * hz + (t / wz) % hz) * wz + t % wz) * os + t / (wz * hz), 0.f);
+        return;
+    }
     int i = t % w, j = (t / w) % h, k = t / (w * h);
     int out_c = c / (st * st);
     int c2 = k % out_c, off = k / out_c;
@@ -289,12 +329,18 @@ __global__ void k_reorg_darknet(const T *in, int is, T *out, int os, int n, int 
 
 hipError_t launch_reorg(const TView &in, const TView &out, int stride, int darknet, hipStream_t s)
 {
-    if (!darknet) {
+    if (in.dt != out.dt || stride < 1 || in.c < 1 || in.h % stride || in.w % stride || in.stride < in.c) return hipErrorInvalidValue;
+    const int co = in.c * stride * stride, cw = std::min(out.stride, (co + 7) / 8 * 8);      // the stored channels of an output pixel: whole granules
+    if (out.stride < co || (size_t)in.h * in.w * in.c + (size_t)in.h * in.w * 8 > 0x7fffffffull) return hipErrorInvalidValue;
+    const size_t elems = (size_t)in.n * (in.h / stride) * (in.w / stride) * cw;
+    if (!darknet && in.c % 8 == 0) {
         size_t total = (size_t)in.n * in.h * in.w * (in.c / 8);
         WITH_DT(in.dt, hipLaunchKernelGGL(k_space_to_depth<T>, grid_for(total), dim3(256), 0, s, (const T *)in.ptr, in.stride, (T *)out.ptr, out.stride, in.n, in.h, in.w, in.c / 8, stride));
+    } else if (!darknet) {
+        WITH_DT(in.dt, hipLaunchKernelGGL(k_space_to_depth_elems<T>, grid_for(elems), dim3(256), 0, s, (const T *)in.ptr, in.stride, (T *)out.ptr, out.stride, in.n, in.h, in.w, in.c, stride, cw));
     } else {
-        size_t total = (size_t)in.n * in.h * in.w * in.c;
-        WITH_DT(in.dt, hipLaunchKernelGGL(k_reorg_darknet<T>, grid_for(total), dim3(256), 0, s, (const T *)in.ptr, in.stride, (T *)out.ptr, out.stride, in.n, in.h, in.w, in.c, stride));
+        if (in.c < stride * stride) return hipErrorInvalidValue;      // reorg_cpu divides by c / (stride * stride)
+        WITH_DT(in.dt, hipLaunchKernelGGL(k_reorg_darknet<T>, grid_for(elems), dim3(256), 0, s, (const T *)in.ptr, in.stride, (T *)out.ptr, out.stride, in.n, in.h, in.w, in.c, stride, cw));
     }
     return hipGetLastError();
 }
@@ -315,7 +361,8 @@ __global__ void k_add(const T *a, int as, const T *b, int bs, T *o, int os, size
 }
 hipError_t launch_add(const TView &a, const TView &b, const TView &out, hipStream_t s, float sa, float sb, float so)
 {
-    size_t npix = (size_t)a.n * a.h * a.w; int c8 = a.c / 8;
+    if (a.dt != b.dt || a.dt != out.dt || !granules_ok(a.c, a.stride, b.stride) || !granules_ok(a.c, out.stride, out.stride)) return hipErrorInvalidValue;
+    size_t npix = (size_t)a.n * a.h * a.w; int c8 = (a.c + 7) / 8;
     WITH_DT(a.dt, hipLaunchKernelGGL(k_add<T>, grid_for(npix * c8), dim3(256), 0, s, (const T *)a.ptr, a.stride, (const T *)b.ptr, b.stride, (T *)out.ptr, out.stride, npix, c8, sa, sb, so));
     return hipGetLastError();
 }
@@ -332,7 +379,8 @@ __global__ void k_copy(const T *a, int as, T *o, int os, size_t npix, int c8)
 }
 hipError_t launch_copy(const TView &in, const TView &out, hipStream_t s)
 {
-    size_t npix = (size_t)in.n * in.h * in.w; int c8 = in.c / 8;
+    if (in.dt != out.dt || !granules_ok(in.c, in.stride, out.stride)) return hipErrorInvalidValue;
+    size_t npix = (size_t)in.n * in.h * in.w; int c8 = (in.c + 7) / 8;
     WITH_DT(in.dt, hipLaunchKernelGGL(k_copy<T>, grid_for(npix * c8), dim3(256), 0, s, (const T *)in.ptr, in.stride, (T *)out.ptr, out.stride, npix, c8));
     return hipGetLastError();
 }

@@ -310,7 +310,7 @@ hipError_t launch_l2norm(const TView &in, const TView &out, hipStream_t s);
 // darknet's [upsample] (DN/blas.c:334-349): nearest, out[y][x] = scale * in[y / stride][x / stride]
 hipError_t launch_upsample_nearest(const TView &in, const TView &out, int stride, float scale, hipStream_t s);
 hipError_t launch_scale(const TView &x, float scale, hipStream_t s);          // x *= scale in place on the real channels
-hipError_t launch_copy_channels(const TView &in, const TView &out, hipStream_t s);      // out = in, element by element: any channel count, any strides
+hipError_t launch_copy_channels(const TView &in, const TView &out, hipStream_t s, int zero_to = 0);      // out = in, element by element: any channel count, any strides, any channel offset; channels in.c .. zero_to of out: zeros
 // per map pixel the arg-max over the c <= 255 channels of an fp32 map (the lowest index wins a tie), 255 where the maximum is < thresh
 hipError_t launch_label_map(const float *map, int stride, size_t npix, int c, float thresh, uint8_t *labels, hipStream_t s);
 // The map pixel a native pixel takes, along one axis: native coordinate x of an image `w` wide, fitted to new_w columns at offset dx of

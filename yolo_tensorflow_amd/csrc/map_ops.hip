@@ -76,18 +76,21 @@ hipError_t launch_scale(const TView &x, float scale, hipStream_t s)
 }
 
 template <typename T>
-__global__ void k_copy_channels(const T *in, int is, T *out, int os, size_t npix, int C)
+__global__ void k_copy_channels(const T *in, int is, T *out, int os, size_t npix, int C, int Cw)
 {
     const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= npix * C) return;
-    const size_t p = idx / C; const int c = (int)(idx - p * C);
-    out[p * os + c] = in[p * is + c];
+    if (idx >= npix * Cw) return;
+    const size_t p = idx / Cw; const int c = (int)(idx - p * Cw);
+    if (c < C) out[p * os + c] = in[p * is + c];
+    else Elt<T>::store1(out + p * os + c, 0.f);
 }
-hipError_t launch_copy_channels(const TView &in, const TView &out, hipStream_t s)
+// `zero_to` > in.c: channels in.c .. zero_to of every output pixel are stored as zeros (the tail of a concatenation's last granule)
+hipError_t launch_copy_channels(const TView &in, const TView &out, hipStream_t s, int zero_to)
 {
-    if (in.dt != out.dt || in.c != out.c || in.stride < in.c || out.stride < out.c) return hipErrorInvalidValue;
+    const int cw = std::max(in.c, zero_to);
+    if (in.dt != out.dt || in.c != out.c || in.c < 1 || in.stride < in.c || out.stride < cw) return hipErrorInvalidValue;
     const size_t npix = (size_t)in.n * in.h * in.w;
-    WITH_DT(in.dt, hipLaunchKernelGGL(k_copy_channels<T>, grid_for(npix * in.c), dim3(256), 0, s, (const T *)in.ptr, in.stride, (T *)out.ptr, out.stride, npix, in.c));
+    WITH_DT(in.dt, hipLaunchKernelGGL(k_copy_channels<T>, grid_for(npix * cw), dim3(256), 0, s, (const T *)in.ptr, in.stride, (T *)out.ptr, out.stride, npix, in.c, cw));
     return hipGetLastError();
 }
 

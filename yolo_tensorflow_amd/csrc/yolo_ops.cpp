@@ -345,24 +345,28 @@ int yolo_op_label_map(const float *map, int n, int h, int w, int c, float thresh
 
 static int ew_op(int kind, const float *x, int n, int h, int w, int c, int p0, int p1, int p2, float *out, int device)
 {
-    if (!x || !out || c % 8) { g_op_err = "op: bad arguments (channels must be a multiple of 8)"; return YOLO_ERR_INVALID; }
-    OpScope S(device); if (S.rc) { g_op_err = "op: no HIP device"; return S.rc; }
+    // any channel count: the tensors are stored as the planner stores them, bf16 with the pixel stride rounded up to whole 8-channel granules
+    if (!x || !out || n < 1 || h < 1 || w < 1 || c < 1) { g_op_err = "op: bad arguments"; return YOLO_ERR_INVALID; }
     int ho = h, wo = w, co = c;
     if (kind == 0) { ho = 2 * h; wo = 2 * w; }
-    else if (kind == 1) { ho = h / p0; wo = w / p0; co = c * p0 * p0; }
-    else { int pad = (p0 - 1) / 2; ho = (h + 2 * pad) / p1; wo = (w + 2 * pad) / p1; }
-    float *d_x32 = (float *)S.upload(x, (size_t)n * h * w * c * 4);
-    void *d_x = S.alloc((size_t)n * h * w * c * 2), *d_o = S.alloc((size_t)n * ho * wo * co * 2);
-    float *d_o32 = (float *)S.alloc((size_t)n * ho * wo * co * 4);
-    if (S.rc) return S.rc;
-    TView vi = make_view(d_x, n, h, w, c, c, 0), vo = make_view(d_o, n, ho, wo, co, co, 0);
-    bool ok = S.ok(launch_from_f32(d_x32, vi, S.s));
-    if (ok && kind == 0) ok = S.ok(launch_upsample2x(vi, vo, p0 == YOLO_SEM_TF, S.s));
-    if (ok && kind == 1) ok = S.ok(launch_reorg(vi, vo, p0, p1 == YOLO_SEM_DARKNET, S.s));
-    if (ok && kind == 2) ok = S.ok(launch_maxpool(vi, vo, p0, p1, (p0 - 1) / 2, S.s));
-    if (ok) ok = S.ok(launch_to_f32(vo, d_o32, S.s));
-    if (!ok) { g_op_err = S.err; return S.rc; }
-    return S.download(out, d_o32, (size_t)n * ho * wo * co * 4);
+    else if (kind == 1) {
+        if (p0 < 1 || h % p0 || w % p0) { g_op_err = "reorg: the stride must divide height and width"; return YOLO_ERR_INVALID; }
+        if (p1 == YOLO_SEM_DARKNET && c < p0 * p0) { g_op_err = "reorg: darknet semantics need at least stride^2 channels"; return YOLO_ERR_INVALID; }
+        ho = h / p0; wo = w / p0; co = c * p0 * p0;
+    }
+    else {
+        if (p0 < 1 || p1 < 1) { g_op_err = "maxpool: size and stride must be positive"; return YOLO_ERR_INVALID; }
+        int pad = (p0 - 1) / 2; ho = (h + 2 * pad) / p1; wo = (w + 2 * pad) / p1;
+        if (ho < 1 || wo < 1) { g_op_err = "maxpool: no output pixel"; return YOLO_ERR_INVALID; }
+    }
+    OpScope S(device); if (S.rc) { g_op_err = "op: no HIP device"; return S.rc; }
+    OpTensor a, o;
+    bool ok = op_tensor(S, x, n, h, w, c, YOLO_BF16, a) && op_tensor(S, nullptr, n, ho, wo, co, YOLO_BF16, o);
+    if (ok && kind == 0) ok = S.ok(launch_upsample2x(a.v, o.v, p0 == YOLO_SEM_TF, S.s));
+    if (ok && kind == 1) ok = S.ok(launch_reorg(a.v, o.v, p0, p1 == YOLO_SEM_DARKNET, S.s));
+    if (ok && kind == 2) ok = S.ok(launch_maxpool(a.v, o.v, p0, p1, (p0 - 1) / 2, S.s));
+    if (!ok || op_tensor_out(S, o, out)) { g_op_err = "op: " + (S.err.empty() ? std::string("allocation or copy failed") : S.err); return S.rc ? S.rc : YOLO_ERR_HIP; }
+    return YOLO_OK;
 }
 int yolo_op_upsample2x(const float *x, int n, int h, int w, int c, int semantics, float *out, int device) { return ew_op(0, x, n, h, w, c, semantics, 0, 0, out, device); }
 int yolo_op_reorg(const float *x, int n, int h, int w, int c, int stride, int semantics, float *out, int device) { return ew_op(1, x, n, h, w, c, stride, semantics, 0, out, device); }

@@ -132,6 +132,10 @@ int build_plan(yolo_ctx *c, const std::vector<Section> &secs)
             if (int r = plan_activation(c, i, s, "logistic", false)) return r;
             if (L.size == 7 && L.stride == 2 && L.pad == 3 && i == 0 && C == 3 && H % 2 == 0 && W % 2 == 0 && c->dtype != YOLO_FP8) L.s2d7 = true;
             else if (L.size != 1 && L.size != 3) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: conv size %d unsupported on the device path", i, L.size);
+            // padding= is taken literally when pad=0, and any stride: the tiled kernels serve both; what has no output pixel is refused
+            if (L.filters < 1) return fail(c, YOLO_ERR_INVALID, "layer %d: conv filters %d", i, L.filters);
+            if (L.stride < 1 || L.pad < 0) return fail(c, YOLO_ERR_INVALID, "layer %d: conv stride %d, padding %d", i, L.stride, L.pad);
+            if (H + 2 * L.pad < L.size || W + 2 * L.pad < L.size) return fail(c, YOLO_ERR_INVALID, "layer %d: conv larger than its padded input (%d x %d with padding %d under a size %d conv)", i, W, H, L.pad, L.size);
             // fp8 mode: the first conv still reads the bf16 image (3 real channels padded to 8) with bf16 filters; a conv reads its
             // producer's tensor in the type that tensor is stored in (cfg key `yolo_store=bf16` on a [convolutional] section of an fp8
             // network keeps that layer's output -- and what is derived from it without arithmetic -- in bf16: mixed-precision plans)
@@ -262,10 +266,14 @@ int build_plan(yolo_ctx *c, const std::vector<Section> &secs)
         } else if (s.type == "maxpool") {
             L.type = L_MAXPOOL; L.pstride = opt_i(s, "stride", 1); L.psize = opt_i(s, "size", L.pstride);
             L.ppad = opt_i(s, "padding", (L.psize - 1) / 2);
+            if (L.pstride < 1 || L.psize < 1 || L.ppad < 0) return fail(c, YOLO_ERR_INVALID, "layer %d: [maxpool] size %d, stride %d, padding %d", i, L.psize, L.pstride, L.ppad);
             H = (H + 2 * L.ppad) / L.pstride; W = (W + 2 * L.ppad) / L.pstride;
+            if (H < 1 || W < 1) return fail(c, YOLO_ERR_INVALID, "layer %d: [maxpool] with stride %d leaves no output pixel", i, L.pstride);
         } else if (s.type == "reorg") {
             L.type = L_REORG; L.pstride = opt_i(s, "stride", 1);
-            if (H % L.pstride || W % L.pstride) return fail(c, YOLO_ERR_INVALID, "layer %d: reorg stride", i);
+            if (L.pstride < 1 || H % L.pstride || W % L.pstride) return fail(c, YOLO_ERR_INVALID, "layer %d: reorg stride", i);
+            // darknet's reorg_cpu takes channel indices modulo c / stride^2 (DN/blas.c:9-30): with fewer channels than stride^2 it divides by zero
+            if (c->semantics == YOLO_SEM_DARKNET && C < L.pstride * L.pstride) return fail(c, YOLO_ERR_INVALID, "layer %d: [reorg] with stride %d needs at least %d channels in darknet semantics (its producer has %d)", i, L.pstride, L.pstride * L.pstride, C);
             H /= L.pstride; W /= L.pstride; C *= L.pstride * L.pstride;
         } else if (s.type == "yolo" || s.type == "region") {
             L.type = s.type == "yolo" ? L_YOLO : L_REGION;
@@ -331,6 +339,8 @@ int build_plan(yolo_ctx *c, const std::vector<Section> &secs)
                 L.pair = c->pair_of(L.in[0]);
                 for (int j : L.in) if (c->pair_of(j) != L.pair) return fail(c, YOLO_ERR_INVALID, "layer %d: operands stored in different forms (yolo_pair): a %s needs pairs or plain fp16 throughout", i, L.type == L_ROUTE ? "route" : L.type == L_SHORTCUT ? "shortcut" : "layer");
                 // pairs are interleaved per 32-channel group: the general shortcut's channel boundary (minc) must fall between groups
+                // ... and a [reorg] scrambles channels across them: whole groups in, whole groups out (via_f32)
+                if (L.type == L_REORG && L.pair) { int h1, w1, c1; dims(L.in[0], h1, w1, c1); if (c1 % 32 || L.C % 32) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: a [reorg] of split-fp16 pairs needs a channel count that is a multiple of 32 (%d)", i, c1); }
                 if (L.type == L_SHORTCUT && L.general && L.pair) { int h1, w1, c1; dims(L.in[1], h1, w1, c1); if (L.C % 32 || c1 % 32) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: a [shortcut] with an activation or a `from` tensor of another shape, on split-fp16 pairs, needs channel counts that are multiples of 32 (%d and %d)", i, L.C, c1); }
             }
         }
@@ -497,7 +507,15 @@ int build_plan(yolo_ctx *c, const std::vector<Section> &secs)
             // a fused-away conv's real producer is the conv; the shortcut layer itself is what gets placed
             if (ok && c->layers[j].type == L_CONV && j + 1 < NL && c->layers[j + 1].noop && c->layers[j + 1].type == L_SHORTCUT) ok = false;
             if (ok) { place_route[j] = i; place_off[j] = L.pair ? 2 * off : off; }
-            else { L.copy_inputs.push_back(j); L.copy_offsets.push_back(off); }
+            else {
+                // a copied source (run_layer): granule by granule, or element by element at a channel offset that is no multiple of 8; what the
+                // copy kernels do not serve is refused here, not at the first forward
+                const int dj = j < 0 ? c->act_dt() : (c->layers[j].head && c->dtype != YOLO_FP32) ? DT_F32 : c->layers[j].store_dt;
+                if (dj != L.store_dt) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [route] of layer %d, whose tensor is stored in another type (an fp32 head, map or classifier tensor), is not served", i, j);
+                if (L.pair && (cj % 32 || off % 32)) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [route] copies the %d channels of layer %d to channel offset %d: on split-fp16 pairs a copied source needs whole 32-channel groups", i, cj, j, off);
+                if (L.store_dt == DT_FP8 && (cj % 8 || off % 8)) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [route] copies the %d channels of layer %d to channel offset %d: in the fp8 configuration a copied source needs multiples of 8", i, cj, j, off);
+                L.copy_inputs.push_back(j); L.copy_offsets.push_back(off);
+            }
             off += cj;
         }
     }
@@ -668,7 +686,7 @@ int allocate(yolo_ctx *c)
             const Layer &L = c->layers[i];
             if (L.type != L_CONV || L.fc || L.s2d7 || window_check_skipped(L, (int)i)) continue;     // (fused layers: their launch checks its own windows)
             const TView in = view_of(c, L.in[0]);
-            const double per_image = (double)in.h * in.w * in.stride * dt_size(L.in_dt), slack = 2.0 * (in.w + 1) * in.stride * dt_size(L.in_dt);
+            const double per_image = (double)in.h * in.w * in.stride * dt_size(L.in_dt), slack = (std::max(L.pad, 1) + 1.0) * (in.w + 1) * in.stride * dt_size(L.in_dt);
             if (per_image * c->max_batch + slack >= 2147483648.0)
                 return fail(c, YOLO_ERR_UNSUPPORTED, "max_batch %d: layer %zu reads %.0f bytes per image%s, and a conv's whole-batch input must stay below 2 GiB (32-bit buffer offsets): at most %d images per context",
                             c->max_batch, i, per_image, c->split() ? " (split fp16 pairs: 2 x the channels)" : "", (int)((2147483648.0 - slack - 1) / per_image));

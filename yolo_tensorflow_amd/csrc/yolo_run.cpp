@@ -103,7 +103,7 @@ static int via_f32(yolo_ctx *c, const Layer &L, int n, int kind)
     else if (kind == 1) HIPCK(c, launch_maxpool(a, b, L.psize, L.pstride, L.ppad, s));
     else {          // reorg scrambles channels: it runs on the LOGICAL channel counts (the padding of a pair tensor is not part of it)
         a.c = in.c; b.c = L.C;
-        if (in.c % 32 || L.C % 32) return fail(c, YOLO_ERR_UNSUPPORTED, "reorg of a pair tensor of %d channels (whole 32-channel groups only)", in.c);
+        if (in.c % 32 || L.C % 32) return fail(c, YOLO_ERR_STATE, "internal: reorg of a pair tensor of %d channels (the planner refuses all but whole 32-channel groups)", in.c);
         HIPCK(c, launch_reorg(a, b, L.pstride, c->semantics == YOLO_SEM_DARKNET, s));
     }
     HIPCK(c, launch_split_from_f32(c->d_f32b, cpo, L.out.ptr, L.out.stride, cpo, pout, s));
@@ -267,15 +267,20 @@ int run_layer(yolo_ctx *c, int i, int n)
         for (size_t k = 0; k < L.copy_inputs.size(); ++k) {
             TView src = nview(view_of(c, L.copy_inputs[k])); TView dst = nview(L.out);
             dst.ptr = (char *)dst.ptr + (size_t)L.copy_offsets[k] * dt_size(dst.dt); dst.c = src.c;
-            if (src.c % 8) return fail(c, YOLO_ERR_UNSUPPORTED, "route copy of %d channels", src.c);
-            if (L.pair) {        // interleaved pairs: the source's 2 * Cp elements at twice the channel offset (whole 32-channel groups)
-                if (src.c % 32 || L.copy_offsets[k] % 32) return fail(c, YOLO_ERR_UNSUPPORTED, "route copy of a pair tensor: %d channels at offset %d (whole 32-channel groups only)", src.c, L.copy_offsets[k]);
+            if (L.pair) {        // interleaved pairs: the source's 2 * Cp elements at twice the channel offset (whole 32-channel groups: the planner refuses the rest)
+                if (src.c % 32 || L.copy_offsets[k] % 32) return fail(c, YOLO_ERR_STATE, "internal: route copy of a pair tensor: %d channels at offset %d", src.c, L.copy_offsets[k]);
                 TView dv = nview(L.out);
                 dv.ptr = (char *)L.out.ptr + (size_t)2 * L.copy_offsets[k] * 2; dv.c = 2 * src.c; src.c = 2 * src.c;
                 HIPCK(c, launch_copy(src, dv, s));
                 continue;
             }
-            HIPCK(c, launch_copy(src, dst, s));
+            // a source at a whole-granule offset is copied granule by granule (the zeros behind a ragged channel count come along and end the
+            // concatenation's last granule, or are overwritten by the next source's copy); at any other offset element by element, and the last
+            // source then writes the zeros up to the end of the granule itself
+            if (L.copy_offsets[k] % 8 == 0 && dst.dt != DT_FP8) { HIPCK(c, launch_copy(src, dst, s)); continue; }
+            if (dst.dt == DT_FP8) { if (src.c % 8) return fail(c, YOLO_ERR_STATE, "internal: route copy of %d e4m3 channels", src.c); HIPCK(c, launch_copy(src, dst, s)); continue; }
+            const int end = L.copy_offsets[k] + src.c;
+            HIPCK(c, launch_copy_channels(src, dst, s, end == L.C ? std::min(L.out.stride, roundup(L.C, 8)) - L.copy_offsets[k] : 0));
         }
         break;
     case L_LOCAL:

@@ -388,6 +388,23 @@ def synth_weights(secs, seed=0, obj_bias=-0.75, stats="benign"):
     return np.concatenate(parts).astype(np.float32)
 
 
+def bf16_exact_filters(secs, flat, floor=2.0 ** -10):
+    """The stream with every FILTER value (not the biases or batch-norm vectors) rounded to bf16 (nearest even) and kept at or above `floor`
+    in magnitude, so that it is exact in fp16 as well (no fp16 subnormal): a bias-only conv on such filters and a stored input has one
+    rounding, the output's.  [convolutional] sections without groups only."""
+    flat = np.array(flat, dtype=np.float32); at = 0
+    for s in conv_specs(secs):
+        at += s["filters"] * (4 if s["bn"] else 1)
+        n = s["filters"] * s["cin"] * s["size"] ** 2
+        u = flat[at:at + n].view(np.uint32).astype(np.uint64)
+        w = (((u + 0x7fff + ((u >> 16) & 1)) >> 16) << 16).astype(np.uint32).view(np.float32)
+        flat[at:at + n] = np.where(np.abs(w) < floor, np.where(w < 0, -floor, floor), w).astype(np.float32)
+        at += n
+    if at != flat.size:
+        raise ValueError("bf16_exact_filters: the stream does not match the cfg")
+    return flat
+
+
 def _leaky_moments(mean, std, slope):
     """(E[f(y)], E[f(y)^2]) for y ~ N(mean, std^2) and f = leaky ReLU with `slope` (slope 1: identity); arrays per channel."""
     from math import pi
