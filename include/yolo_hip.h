@@ -299,6 +299,11 @@ int yolo_autotune(yolo_ctx *ctx, int n, int iters);
  * tuned plan can be persisted by the caller.  cfgs has yolo_num_layers() entries. */
 int yolo_get_tile_configs(const yolo_ctx *ctx, int32_t *cfgs);
 int yolo_set_tile_configs(yolo_ctx *ctx, const int32_t *cfgs);
+/* The tile configuration every layer would launch at batch n (1..max_batch) under the plan as it stands, into out[yolo_num_layers()]:
+ * yolo_set_tile_configs stores any in-range id, and a layer whose id does not apply to it (another storage type's, a halo-staged form
+ * its size does not tile into) runs its default instead.  -1: not a tunable layer (no [convolutional] section, a fixed kernel, a 1x1
+ * conv computed in its producer's epilogue, an fp32 network).  Read-only: no device call, no state changed. */
+int yolo_resolved_tile_configs(const yolo_ctx *ctx, int n, int32_t *out);
 
 /* ---- single operators on host buffers (parity tests call the production kernels through these) - */
 /* x [n,h,w,cin] fp32 NHWC, w_hwio [k,k,cin,cout], bias [cout] (or NULL), residual [n,ho,wo,cout] or NULL.

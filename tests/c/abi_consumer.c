@@ -16,6 +16,8 @@ int main(void)
     char err[256] = "";
     CHECK(yolo_create(NULL, err, sizeof err) == NULL && strstr(err, "yolo_config"));
     CHECK(yolo_op_conv_num_cfgs() > 40);
+    int32_t resolved[1];
+    CHECK(yolo_resolved_tile_configs(NULL, 1, resolved) == YOLO_ERR_INVALID);
 
     /* world 3, batch 8: 3 + 3 + 2 */
     int first = -1, count = -1, sum = 0;

@@ -21,11 +21,14 @@ SPLIT_CFGS = (0, 2, 3, 4, 6, 7, 8, 14, 15, 16, 23, 33, 34, 45, 49, 52)       # (
 SPLIT_HALO = (40, 41, 43, 57, 58)          # (57, 58: round 6, one wave per SIMD)
 
 
-def _emu_conv(x, w, b, stride, act, res=None):
+def _emu_conv(x, w, b, stride, act, res=None, pad=None, f32_out=False):
+    """pad: zero padding each side (None: size / 2); f32_out: an fp32 output (a head, a map) is not split (test_gpu_tile_matrix.py)"""
     xh, xl = R.split_f16(x); wh, wl = R.split_f16(w)
-    y = R.conv2d_nhwc(xh, wh, stride) + R.conv2d_nhwc(xl, wh, stride) + R.conv2d_nhwc(xh, wl, stride) + b
+    y = R.conv2d_nhwc(xh, wh, stride, pad) + R.conv2d_nhwc(xl, wh, stride, pad) + R.conv2d_nhwc(xh, wl, stride, pad) + b
     if act:
         y = R.leaky_relu(y)
+    if f32_out:
+        return y.astype(np.float32)
     h, l = R.split_f16(y.astype(np.float32))
     if res is not None:
         rh, rl = R.split_f16(res)

@@ -36,12 +36,13 @@ def _codes_close(got, want, scale, what, min_same=0.997, operands=()):
     return same
 
 
-def _conv_ref(x, w, b, stride, residual):
+def _conv_ref(x, w, b, stride, residual, pad=None, leaky=True):
+    """pad: zero padding each side (None: size / 2); leaky=False: a linear conv (test_gpu_tile_matrix.py: the cfg's padding= and activation)"""
     xq = R.to_fp8_e4m3(x)
     amax = np.abs(w).max(axis=(0, 1, 2)); osc = np.where(amax > 0, amax / np.float32(448), np.float32(1)).astype(np.float32)
     wq = R.to_fp8_e4m3(w / osc[None, None, None, :])
-    v = (R.conv2d_nhwc(xq, wq, stride).astype(np.float64) * osc + b.astype(np.float64)).astype(np.float32)
-    q = R.to_fp8_e4m3(R.to_bf16(R.leaky_relu(v)))
+    v = (R.conv2d_nhwc(xq, wq, stride, pad).astype(np.float64) * osc + b.astype(np.float64)).astype(np.float32)
+    q = R.to_fp8_e4m3(R.to_bf16(R.leaky_relu(v) if leaky else v))
     return (q, ()) if residual is None else (R.to_fp8_e4m3(q + R.to_fp8_e4m3(residual)), (q, residual))
 
 
@@ -55,9 +56,17 @@ def test_fp8_conv_operator(hiplib, n, h, cin, cout, k, stride, res):
     ho = (h + 2 * (k // 2) - k) // stride + 1
     r = rng.normal(0, 1, (n, ho, ho, cout)).astype(np.float32) if res else None
     want, operands = _conv_ref(x, w, b, stride, r)
-    for cfg in (-1, 0, 16, 17, 23, 32):
-        got = hiplib.op_conv2d(x, w, b, stride=stride, act=1, residual=r, dtype=hiplib.FP8, tile_cfg=cfg)
+    ran = []
+    for cfg in [-1] + list(range(hiplib.op_conv_num_cfgs())):          # every id the operator accepts for e4m3 operands; it errors on the rest
+        try:
+            got = hiplib.op_conv2d(x, w, b, stride=stride, act=1, residual=r, dtype=hiplib.FP8, tile_cfg=cfg)
+        except hiplib.YoloError:
+            continue
         _codes_close(got, want, 1.0, "cfg %d" % cfg, operands=operands)
+        ran.append(cfg)
+    # csrc/conv_cfgs.h: CfgsFp8, every one of them; CfgsHaloFp8 (36..43) where the shape is 3x3 / stride 1 on whole 128-channel chunks over 13 x 13 blocks
+    assert [c for c in ran if not 36 <= c <= 43] == [-1, 0, 2, 4, 6, 8, 12, 14, 16, 17, 19, 20, 23, 31, 32, 33, 34, 45, 48, 49, 51], ran
+    assert [c for c in ran if 36 <= c <= 43] == (list(range(36, 44)) if (k, stride, h % 13, cin % 128) == (3, 1, 0, 0) else []), ran
 
 
 def test_fp8_saturates_and_keeps_zero(hiplib):

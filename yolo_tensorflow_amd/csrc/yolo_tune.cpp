@@ -157,6 +157,20 @@ int yolo_get_tile_configs(const yolo_ctx *c, int32_t *cfgs)
     return YOLO_OK;
 }
 
+// What run_conv would launch at batch n under the plan as it stands: yolo_set_tile_configs stores any in-range id, and a layer whose id
+// does not run (another storage family's, a halo form that does not fit) falls back to its default without a word.  No device call, no state.
+int yolo_resolved_tile_configs(const yolo_ctx *c, int n, int32_t *out)
+{
+    if (!c || !out || n < 1 || n > c->max_batch) return YOLO_ERR_INVALID;
+    for (size_t i = 0; i < c->layers.size(); ++i) {
+        const Layer &L = c->layers[i];
+        // -1: no [convolutional] layer, a fixed kernel (stem / block / conv3 / stride-2), a 1x1 computed in its producer's epilogue, fp32 (no tile ids)
+        const bool tiled = L.type == L_CONV && !fixed_kernel(L) && !rides_as_tail(c, L) && c->dtype != YOLO_FP32;
+        out[i] = tiled ? conv_resolve_cfg(conv_args(c, L, n), L.tile_cfg) : -1;
+    }
+    return YOLO_OK;
+}
+
 int yolo_set_tile_configs(yolo_ctx *c, const int32_t *cfgs)
 {
     if (!c || !cfgs) return YOLO_ERR_INVALID;
@@ -168,8 +182,10 @@ int yolo_set_tile_configs(yolo_ctx *c, const int32_t *cfgs)
         if (tail && (c->layers[i].tail_layer < 0 || !conv_cfg_tail_ok(v, c->layers[i].filters, c->layers[i].in_dt == DT_FP8, c->layers[c->layers[i].tail_layer].head) || c->layers[c->layers[i].tail_layer].in_dt != c->layers[i].in_dt))
             return fail(c, YOLO_ERR_INVALID, "layer %zu: plan asks for a fused 1x1 tail this layer / tile config cannot run", i);
         if (tail && fixed_kernel(c->layers[i])) return fail(c, YOLO_ERR_INVALID, "layer %zu runs a fixed kernel (stem / conv3 / block / stride-2): it hosts no fused 1x1 tail", i);
-        if (tail && conv_cfg_is_halo(v) && !conv_cfg_runs(conv_args(c, c->layers[i], c->max_batch), v))
-            return fail(c, YOLO_ERR_INVALID, "layer %zu: the halo-staged tile config %d does not apply to this layer, so it cannot carry the fused 1x1 tail", i, v);
+        // (any id, not the halo forms alone: with a tiled id its storage family does not instantiate -- 44 and 50 on e4m3 operands -- the layer
+        // would fall back to its default id, which hosts no tail, and the forward would refuse the plan)
+        if (tail && !conv_cfg_runs(conv_args(c, c->layers[i], c->max_batch), v))
+            return fail(c, YOLO_ERR_INVALID, "layer %zu: tile config %d does not run on this layer (its storage type does not instantiate it, or a halo-staged form does not fit), so it cannot carry the fused 1x1 tail", i, v);
         c->layers[i].tile_cfg = v; c->layers[i].tail_on = tail;
     }
     drop_graph(c);

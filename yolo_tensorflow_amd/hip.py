@@ -38,7 +38,7 @@ EXPORTS = [
     "yolo_weights_count", "yolo_set_act_scales", "yolo_export", "yolo_create_from_file", "yolo_input_size", "yolo_num_rows", "yolo_num_attrs", "yolo_num_layers", "yolo_head_geometry", "yolo_head_geometry_hw", "yolo_op_decode_hw", "yolo_op_resize_u8_hw",
     "yolo_conv_flops", "yolo_conv_bytes", "yolo_forward", "yolo_forward_image_u8", "yolo_postprocess",
     "yolo_detect", "yolo_detect_graph", "yolo_synchronize", "yolo_layer_output", "yolo_time_forward", "yolo_time_layers",
-    "yolo_autotune", "yolo_get_tile_configs", "yolo_set_tile_configs", "yolo_op_conv2d", "yolo_op_conv_num_cfgs", "yolo_op_upsample2x", "yolo_op_reorg",
+    "yolo_autotune", "yolo_get_tile_configs", "yolo_set_tile_configs", "yolo_resolved_tile_configs", "yolo_op_conv2d", "yolo_op_conv_num_cfgs", "yolo_op_upsample2x", "yolo_op_reorg",
     "yolo_darknet_boxes", "yolo_last_layer_size", "yolo_last_layer_output", "yolo_op_letterbox",
     "yolo_op_maxpool", "yolo_op_resize_u8", "yolo_op_detections_boxes", "yolo_op_nms_detections", "yolo_forward_letterbox_chw", "yolo_op_decode", "yolo_op_postprocess",
     "yolo_postprocess_rows", "yolo_op_postprocess_rows", "yolo_last_layer_output_batch", "yolo_head_raw", "yolo_calibrate", "yolo_calibrate_copy", "yolo_op_resize_cv2",
@@ -107,6 +107,7 @@ def load_library():
     l.yolo_autotune.argtypes = [P, I, I]
     l.yolo_get_tile_configs.argtypes = [P, P]
     l.yolo_set_tile_configs.argtypes = [P, P]
+    l.yolo_resolved_tile_configs.argtypes = [P, I, P]
     l.yolo_op_conv2d.argtypes = [P, I, I, I, I, P, P, I, I, I, I, P, P, I, I, I]
     l.yolo_op_conv_num_cfgs.argtypes = []
     l.yolo_op_upsample2x.argtypes = [P, I, I, I, I, I, P, I]
@@ -662,6 +663,12 @@ class Engine:
         if cfgs.size != self.num_layers:
             raise YoloError("need %d tile configs, got %d" % (self.num_layers, cfgs.size))
         self._check(self.lib.yolo_set_tile_configs(self.ctx, cfgs.ctypes.data), "yolo_set_tile_configs")
+
+    def resolved_tile_configs(self, n):
+        """the id every layer would launch at batch n under the current plan (-1: not a tunable conv layer); see include/yolo_hip.h"""
+        out = np.full(self.num_layers, -1, dtype=np.int32)
+        self._check(self.lib.yolo_resolved_tile_configs(self.ctx, n, out.ctypes.data), "yolo_resolved_tile_configs")
+        return out
 
 
 # ---- single operators (host buffers in, host buffers out; production kernels underneath) ----------
