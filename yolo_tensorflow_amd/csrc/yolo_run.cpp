@@ -368,9 +368,11 @@ int stage_in(yolo_ctx *c, const void *images, int n, int fmt, int loc, float sca
         HIPCK(c, hipMemcpyAsync(c->d_stage, images, npix * 3 * (fmt == YOLO_IMG_U8 ? 1 : 4), hipMemcpyHostToDevice, c->stream));
         src = c->d_stage;
     }
-    // uint8 images of a network whose first layers run as the fused stem: the stem converts the pixels itself (conv_stem.hip, U8 form)
+    // uint8 images of a network whose first layers run as the fused stem: the stem converts the pixels itself (conv_stem.hip, U8 form).
+    // That form gathers the raw rows in aligned dwords through a descriptor that ends with the image tensor: a batch whose byte count is no
+    // multiple of 4 (odd width x odd height x odd n) would lose its last 1-3 bytes to the range check, so it takes the conversion launch
     c->stem_u8 = nullptr;
-    if (fmt == YOLO_IMG_U8 && c->layers.size() > 1 && never_stored(c->layers[0], 0) && (double)npix * 3 < 2147483648.0 && ((size_t)src & 3) == 0) {
+    if (fmt == YOLO_IMG_U8 && c->layers.size() > 1 && never_stored(c->layers[0], 0) && (double)npix * 3 < 2147483648.0 && ((size_t)src & 3) == 0 && (npix * 3) % 4 == 0) {
         c->stem_u8 = (const uint8_t *)src; c->stem_scale = scale; c->stem_u8_n = n;
         return YOLO_OK;
     }
