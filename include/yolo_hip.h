@@ -428,6 +428,12 @@ int yolo_plan_check(const char *cfg_text, int dtype, char *err, size_t err_len);
  * refuses (YOLO_ERR_INVALID) groups that do not divide the input channels or the filters, and (YOLO_ERR_UNSUPPORTED) a grouped section in
  * the fp8 and split-fp16 configurations, as the first layer, or directly in front of a [yolo] / [region] / [detection] head. */
 int yolo_plan_table(const char *cfg_text, int dtype, int max_batch, int keep_layers, char *out, size_t out_len, char *err, size_t err_len);
+/* Everything the planner writes, as text, with the calling convention of yolo_plan_table: one `layer <index> <section> name=value ...` line per
+ * layer (geometry, conv keys, padded sizes, types and pair form, fusion marks, route copies, head and classifier keys, storage and channel
+ * offset), one `storage <index> def= last= bytes= phys= stride= dt= persistent=` line per storage, then one `context ...` line (input, rows,
+ * attrs, the kind of network, normalisation, weights_count, conv_flops, phys_bytes[]).  Enumerations print as their numbers, floats and the
+ * conv_flops double as %a.  The text is meant to be compared, not parsed: tests/test_plan_dump.py pins its SHA-256 per cfg. */
+int yolo_plan_dump(const char *cfg_text, int dtype, int max_batch, int keep_layers, char *out, size_t out_len, char *err, size_t err_len);
 /* single operators: x [n][len] fp32 logits, one softmax per group of the tree at tree_path, `mode` a yolo_hierarchy_mode -> out [n][len];
  * hierarchy_top_prediction of n rows of raw logits (temperature 1) walking down from the root -> labels_out [n] */
 int yolo_op_tree_softmax(const float *x, int n, int len, const char *tree_path, float temperature, int mode, float *out, int device);

@@ -1,5 +1,5 @@
 // Private to libyolo_hip.so's host side: the planned network (layers, storage pool, context) and the functions its translation
-// units share.  yolo_plan.cpp: darknet-cfg parser, planner, buffer pool.  yolo_pack.cpp: BN fold, filter packing, fp8 scales, weight
+// units share.  yolo_plan.cpp: darknet-cfg parser, planner, buffer pool, the plan queries that need no device.  yolo_pack.cpp: BN fold, filter packing, fp8 scales, weight
 // stream / export artifact.  yolo_run.cpp: launch sequence, detect graph, timing.  yolo_tune.cpp: tile selection rule, autotuner, tile plan.  yolo_api.cpp: create / destroy,
 // introspection, darknet-flavoured views.  yolo_ops.cpp: single-operator entry points.
 #pragma once
@@ -180,6 +180,10 @@ inline void drop_graph(yolo_ctx *c)      // a plan / parameter / buffer change: 
     if (c->gexec) { hipGraphExecDestroy(c->gexec); c->gexec = nullptr; } if (c->gstate > 0) c->gstate = 0;
     if (c->gexec_img) { hipGraphExecDestroy(c->gexec_img); c->gexec_img = nullptr; } if (c->gstate_img > 0) c->gstate_img = 0;
 }
+
+// ---- layer kinds the planner asks for by more than one name ----
+inline bool computes(const Layer &L) { return L.type == L_CONV || L.type == L_DECONV || L.type == L_GCONV; }      // has filters and an MFMA kernel ([connected] is an L_CONV; [local] is not among them)
+inline bool is_head_layer(const Layer &L) { return L.type == L_YOLO || L.type == L_REGION || L.type == L_DETECT; }      // a detection head: no tensor of its own, an alias of the conv in front of it
 
 // ---- what a conv layer's (kernel, fused, launcher) mean: the only places that enumerate fused kinds; `i` = the layer's own index.  Where two of the old lists disagreed: NOTEBOOK 2026-10-18 ----
 inline bool fused_may_fall_back(const Layer &L) { return L.fused == F_RESBLOCK || L.fused == F_C3S2; }      // to its members' own kernels, where the fused launch's 32-bit windows do not hold the batch; the stems cannot (layer 0 has no storage) and refuse

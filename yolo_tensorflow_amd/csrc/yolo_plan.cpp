@@ -2,13 +2,22 @@
 //
 // What the reference does with a Python graph builder + tf.Session (V3/yolo_v3.py:195-267,
 // D2T/YOLO_V3_convert_darkenet_to_Tensorflow.py:435-545) or with parse_network_cfg + forward_network
-// (DN/parser.c:730-875, DN/network.c:188-211) is done here once at yolo_create():
-//   * shapes are inferred, every layer gets a view into a small pool of HBM buffers (liveness-based
-//     reuse so consecutive layers recycle the same few allocations and stay in L2 / Infinity Cache);
-//   * route/concat is never executed: producers are planned to write straight into a channel window of
-//     the concat buffer (DN/route_layer.c:74-89 and tf.concat V3/yolo_v3.py:247,259 become strides);
-//   * `shortcut` after a conv is folded into that conv's epilogue (V3/yolo_v3.py:54-60);
-//   * batch-norm is folded into the filters at weight-load time.
+// (DN/parser.c:730-875, DN/network.c:188-211) is done here once at yolo_create(), by build_plan(): a sequence of file-static steps, each
+// with a header that says what it reads from the steps before it and what it writes.  In order:
+//   1. parse_sections: [net], then one parser per section kind (section_table) over a cursor of the running geometry; after each layer
+//      inherit_form gives a layer that moves data the type and pair form of what it moves.  Shapes, types, padded sizes, totals;
+//   2. heads_to_fp32, classifier_tail, network_kind (detector / classifier / map), input_norm_and_row_limit;
+//   3. count_uses, fold_shortcuts: `shortcut` after a conv is folded into that conv's epilogue (V3/yolo_v3.py:54-60);
+//   4. the marking passes -- mark_resblocks, mark_stem, mark_pair_stem, mark_halo_and_s2, mark_c3s2, mark_tails -- which choose a conv's
+//      own kernel, the fused launch it is a member of and the 1x1 conv that rides in its epilogue.  Their order matters: the comment in
+//      build_plan() says why;
+//   5. storage: decide_inplace; place_route_sources (route/concat is never executed: producers write straight into a channel window of the
+//      concat buffer -- DN/route_layer.c:74-89 and tf.concat V3/yolo_v3.py:247,259 become strides); create_storages;
+//      redirect_folded_convs; compute_liveness; assign_pool (liveness-based reuse of a small pool of HBM buffers, so consecutive layers
+//      recycle the same few allocations and stay in L2 / Infinity Cache).
+// allocate() then turns the pool into device memory.  Batch-norm is folded into the filters at weight-load time (yolo_pack.cpp).
+// The planner needs no device: yolo_plan_check / yolo_plan_table / yolo_plan_dump at the end of this file run it alone, and
+// tests/test_plan_table.py and tests/test_plan_dump.py pin what it writes.
 #include "yolo_ctx.h"
 
 namespace yolo_impl {
@@ -79,7 +88,356 @@ static int plan_activation(yolo_ctx *c, int i, const Section &s, const char *dfl
 
 TView view_of(const yolo_ctx *c, int idx) { return idx < 0 ? c->input : c->layers[idx].out; }
 
-int build_plan(yolo_ctx *c, const std::vector<Section> &secs)
+// ---- section parsing: one function per section kind, found by name in section_table -----------------------------------------
+// Every parser reads: the cursor (what layer i receives), the layers in front of i.  Writes: its own Layer's keys, in_dt / store_dt / pair where
+// the layer computes, the cursor (what it produces), c->rows / attrs / conv_flops / weights_count / trees / tree_head, `head` on its producer.
+
+// the running geometry while the sections are read: on entry what layer i receives, on return what it produces
+struct Cursor {
+    yolo_ctx *c; int i, H, W, C;
+    void dims(int idx, int &h, int &w, int &ch) const { if (idx < 0) { h = c->in_h; w = c->in_w; ch = c->in_c; } else { h = c->layers[idx].H; w = c->layers[idx].W; ch = c->layers[idx].C; } }
+};
+
+// the keys the three convolution kinds share (DN/parser.c: pad=1 means size / 2, else padding= is taken literally)
+static void read_conv_keys(const Section &s, Layer &L)
+{
+    L.filters = opt_i(s, "filters", 1); L.size = opt_i(s, "size", 1); L.stride = opt_i(s, "stride", 1);
+    L.pad = opt_i(s, "pad", 0) ? L.size / 2 : opt_i(s, "padding", 0);
+    L.bn = opt_i(s, "batch_normalize", 0);
+}
+// ... their output geometry, (H + 2p - k) / s + 1, and what they add to the context's totals: `cin_g` input channels per filter over an h x w grid
+static void conv_out(Cursor &k, const Layer &L) { k.H = (k.H + 2 * L.pad - L.size) / L.stride + 1; k.W = (k.W + 2 * L.pad - L.size) / L.stride + 1; k.C = L.filters; }
+static void conv_totals(yolo_ctx *c, const Layer &L, int cin_g, int h, int w)
+{
+    c->conv_flops += 2.0 * L.size * L.size * cin_g * L.filters * (double)h * w;
+    c->weights_count += (size_t)L.filters * (L.bn ? 4 : 1) + (size_t)L.filters * cin_g * L.size * L.size;
+}
+
+// grouped convolution (DN/parser.c:184, DN/convolutional_layer.c:458-471): a layer kind of its own with its own kernel (gconv.hip).  Like
+// [deconvolutional] it is never a member of a fused launch, neither end of a 1x1 tail, no host of a folded [shortcut] and nothing for
+// the tile tuner to choose -- every marking pass asks for L_CONV
+static int parse_grouped_conv(Cursor &k, const Section &s, Layer &L)
+{
+    yolo_ctx *c = k.c; const int i = k.i;
+    L.groups = opt_i(s, "groups", 1);
+    if (L.groups < 1) return fail(c, YOLO_ERR_INVALID, "layer %d: [convolutional] groups=%d", i, L.groups);
+    if (c->dtype == YOLO_FP8) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [convolutional] with groups=%d is not served in the fp8 configuration", i, L.groups);
+    if (c->split()) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [convolutional] with groups=%d is not served in the split-fp16 configuration", i, L.groups);
+    if (i == 0) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [convolutional] with groups=%d as the network's first layer is not served (the image is read by the dense kernels only)", i, L.groups);
+    L.type = L_GCONV; read_conv_keys(s, L);
+    if (L.filters < 1) return fail(c, YOLO_ERR_INVALID, "layer %d: conv filters %d", i, L.filters);
+    if (k.C % L.groups) return fail(c, YOLO_ERR_INVALID, "layer %d: groups=%d does not divide the %d input channels", i, L.groups, k.C);
+    if (L.filters % L.groups) return fail(c, YOLO_ERR_INVALID, "layer %d: groups=%d does not divide filters=%d", i, L.groups, L.filters);
+    if (L.size < 1 || L.size > GCONV_MAX_SIZE) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: grouped conv size %d (1..%d are served)", i, L.size, GCONV_MAX_SIZE);
+    if (L.stride < 1 || L.stride > GCONV_MAX_STRIDE) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: grouped conv stride %d (1..%d are served)", i, L.stride, GCONV_MAX_STRIDE);
+    if (L.pad < 0 || L.pad >= L.size) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: grouped conv padding %d must be below its size %d", i, L.pad, L.size);
+    if (k.H + 2 * L.pad < L.size || k.W + 2 * L.pad < L.size) return fail(c, YOLO_ERR_INVALID, "layer %d: grouped conv larger than its padded input", i);
+    if (int r = plan_activation(c, i, s, "logistic", false)) return r;
+    L.in_dt = c->act_dt(); L.store_dt = c->act_dt();
+    L.cin = k.C; L.cin_pad = roundup(k.C, 8);
+    { GConvArgs g; memset(&g, 0, sizeof g); g.C = k.C; g.Cout = L.filters; g.groups = L.groups; g.size = L.size; g.in_dt = L.in_dt; gconv_layout(g); L.kpad = g.kp; L.cout_pad = g.nb * g.mb; }      // cout_pad * kpad elements of filters
+    conv_out(k, L);
+    conv_totals(c, L, L.cin / L.groups, k.H, k.W);      // DN/convolutional_layer.c:201, :325: c / groups
+    return YOLO_OK;
+}
+
+static int parse_convolutional(Cursor &k, const Section &s, Layer &L)
+{
+    if (opt_i(s, "groups", 1) != 1) return parse_grouped_conv(k, s, L);
+    yolo_ctx *c = k.c; const int i = k.i;
+    L.type = L_CONV; read_conv_keys(s, L);
+    if (int r = plan_activation(c, i, s, "logistic", false)) return r;
+    if (L.size == 7 && L.stride == 2 && L.pad == 3 && i == 0 && k.C == 3 && k.H % 2 == 0 && k.W % 2 == 0 && c->dtype != YOLO_FP8) L.s2d7 = true;
+    else if (L.size != 1 && L.size != 3) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: conv size %d unsupported on the device path", i, L.size);
+    // padding= is taken literally when pad=0, and any stride: the tiled kernels serve both; what has no output pixel is refused
+    if (L.filters < 1) return fail(c, YOLO_ERR_INVALID, "layer %d: conv filters %d", i, L.filters);
+    if (L.stride < 1 || L.pad < 0) return fail(c, YOLO_ERR_INVALID, "layer %d: conv stride %d, padding %d", i, L.stride, L.pad);
+    if (k.H + 2 * L.pad < L.size || k.W + 2 * L.pad < L.size) return fail(c, YOLO_ERR_INVALID, "layer %d: conv larger than its padded input (%d x %d with padding %d under a size %d conv)", i, k.W, k.H, L.pad, L.size);
+    // fp8 mode: the first conv still reads the bf16 image (3 real channels padded to 8) with bf16 filters; a conv reads its
+    // producer's tensor in the type that tensor is stored in (cfg key `yolo_store=bf16` on a [convolutional] section of an fp8
+    // network keeps that layer's output -- and what is derived from it without arithmetic -- in bf16: mixed-precision plans)
+    L.in_dt = c->dtype == YOLO_FP8 ? (i == 0 ? DT_BF16 : c->layers[i - 1].store_dt) : c->act_dt();
+    L.store_dt = c->act_dt();
+    const std::string st = opt_s(s, "yolo_store", "");
+    if (!st.empty()) {
+        if (c->dtype != YOLO_FP8) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: yolo_store is a key of fp8 networks (mixed e4m3 / bf16 plans)", i);
+        if (st == "bf16") L.store_dt = DT_BF16; else if (st == "fp8") L.store_dt = DT_FP8;
+        else return fail(c, YOLO_ERR_INVALID, "layer %d: yolo_store=%s (bf16 or fp8)", i, st.c_str());
+    }
+    L.cin = k.C; L.cin_pad = roundup(k.C, L.in_dt == DT_FP8 ? 16 : 8);
+    // the conv kernel's view of a pair tensor: a layer output is interleaved per 32-channel group, 2 * roundup(C, 32) elements per
+    // pixel and tap (pair K loop); the network input keeps the three blocks hi | lo | hi of its 8 padded channels (plain K loop)
+    if (c->pair_of(i - 1)) L.cin_pad = i - 1 < 0 ? 3 * roundup(k.C, 8) : pair_width(k.C);
+    L.pair = c->split() && opt_i(s, "yolo_pair", 1) != 0;
+    L.kpad = roundup(L.size * L.size * L.cin_pad, L.in_dt == DT_FP8 ? 128 : 64); L.cout_pad = roundup(L.filters, 256);
+    if (L.s2d7) { L.cin_pad = 32; L.kpad = 16 * 32; }          // 4x4 taps x (2x2 positions x 8 padded channels)
+    conv_out(k, L);
+    conv_totals(c, L, L.cin, k.H, k.W);
+    return YOLO_OK;
+}
+
+// transposed convolution (DN/deconvolutional_layer.c, DN/parser.c:151-174): its own kernel (deconv.hip), never a member of a fused
+// launch, neither end of a 1x1 tail, and a [shortcut] behind it is not folded into it -- every marking pass asks for L_CONV
+static int parse_deconvolutional(Cursor &k, const Section &s, Layer &L)
+{
+    yolo_ctx *c = k.c; const int i = k.i;
+    if (c->dtype == YOLO_FP8) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [deconvolutional] is not served in the fp8 configuration", i);
+    if (c->split()) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [deconvolutional] is not served in the split-fp16 configuration", i);
+    L.type = L_DECONV; read_conv_keys(s, L);
+    if (L.size < 1 || L.size > DECONV_MAX_SIZE) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: deconv size %d (1..%d are served)", i, L.size, DECONV_MAX_SIZE);
+    if (L.stride < 1 || L.stride > DECONV_MAX_STRIDE) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: deconv stride %d (1..%d are served)", i, L.stride, DECONV_MAX_STRIDE);
+    if (L.pad < 0 || L.pad >= L.size) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: deconv padding %d must be below its size %d", i, L.pad, L.size);
+    if (L.filters < 1) return fail(c, YOLO_ERR_INVALID, "layer %d: deconv filters %d", i, L.filters);
+    const int ho = (k.H - 1) * L.stride + L.size - 2 * L.pad, wo = (k.W - 1) * L.stride + L.size - 2 * L.pad;
+    if (ho < 1 || wo < 1) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: deconv output %d x %d is not positive", i, wo, ho);
+    if (int r = plan_activation(c, i, s, "logistic", false)) return r;
+    L.in_dt = c->act_dt(); L.store_dt = c->act_dt();
+    L.cin = k.C; L.cin_pad = roundup(k.C, 8); L.cout_pad = roundup(L.filters, DECONV_CO_TILE);
+    { DeconvArgs g; memset(&g, 0, sizeof g); g.size = L.size; g.stride = L.stride; g.Cin_pad = L.cin_pad; g.cout_pad = L.cout_pad; L.kpad = (int)(deconv_layout(g) / L.cout_pad); }      // (the K of all phases together: cout_pad * kpad elements of filters)
+    conv_totals(c, L, L.cin, k.H, k.W);      // (over the INPUT grid: every input pixel meets every tap)
+    k.H = ho; k.W = wo; k.C = L.filters;
+    return YOLO_OK;
+}
+
+static int parse_connected(Cursor &k, const Section &s, Layer &L)
+{
+    yolo_ctx *c = k.c; const int i = k.i;
+    if (c->dtype == YOLO_FP8 || c->split()) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [connected] is not served in the fp8 / split-fp16 configurations", i);
+    if (opt_i(s, "batch_normalize", 0)) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: batch-normalised [connected]", i);
+    L.type = L_CONV; L.fc = true; L.fc_h = k.H; L.fc_w = k.W; L.fc_c = k.C;
+    L.filters = opt_i(s, "output", 1); L.size = 1; L.stride = 1; L.pad = 0; L.bn = 0;
+    if (int r = plan_activation(c, i, s, "logistic", false)) return r;
+    L.in_dt = c->act_dt(); L.store_dt = c->act_dt();
+    if ((long)k.H * k.W * k.C > (1L << 24)) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [connected] input too large", i);
+    L.cin = k.H * k.W * k.C; L.cin_pad = roundup(L.cin, 8); L.kpad = roundup(L.cin_pad, 64); L.cout_pad = roundup(L.filters, 256);
+    c->conv_flops += 2.0 * L.cin * L.filters;
+    c->weights_count += (size_t)L.filters + (size_t)L.filters * L.cin;
+    k.H = 1; k.W = 1; k.C = L.filters;
+    return YOLO_OK;
+}
+
+// locally connected (DN/local_layer.c; darknet's own yolov1.cfg): `pad` is a flag AND the im2col pad amount (:10-24, :103)
+static int parse_local(Cursor &k, const Section &s, Layer &L)
+{
+    yolo_ctx *c = k.c; const int i = k.i;
+    if (c->dtype == YOLO_FP8 || c->split()) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [local] is not served in the fp8 / split-fp16 configurations", i);
+    L.type = L_LOCAL; L.filters = opt_i(s, "filters", 1); L.size = opt_i(s, "size", 1); L.stride = opt_i(s, "stride", 1); L.pad = opt_i(s, "pad", 0);
+    if (L.pad != 0 && L.pad != 1) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [local] pad must be 0 or 1", i);
+    // pad=1 pads by ONE pixel whatever the size (DN/local_layer.c:103 im2col) while the output size assumes size / 2 (:10-24): they only agree for 3x3
+    if (L.pad == 1 && L.size != 3) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [local] with pad=1 needs size=3 (darknet's own output size and im2col disagree otherwise)", i);
+    if (int r = plan_activation(c, i, s, "logistic", false)) return r;
+    if (k.C % 8) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [local] needs a producer with a multiple of 8 channels", i);
+    L.cin = k.C; L.cin_pad = k.C; L.in_dt = c->act_dt(); L.store_dt = c->act_dt();
+    const int ho = ((L.pad ? k.H - 1 : k.H - L.size)) / L.stride + 1, wo = ((L.pad ? k.W - 1 : k.W - L.size)) / L.stride + 1;
+    if (ho < 1 || wo < 1) return fail(c, YOLO_ERR_INVALID, "layer %d: [local] larger than its input", i);
+    k.H = ho; k.W = wo; k.C = L.filters;
+    c->conv_flops += 2.0 * L.size * L.size * L.cin * L.filters * (double)k.H * k.W;
+    c->weights_count += (size_t)L.filters * k.H * k.W + (size_t)k.H * k.W * L.filters * L.cin * L.size * L.size;
+    return YOLO_OK;
+}
+
+// [dropout] (DN/dropout_layer.c:38-40) and [cost] (DN/cost_layer.c: forward returns without a truth): the identity at inference
+static int parse_identity(Cursor &, const Section &s, Layer &L) { L.type = L_ROUTE; L.cost = s.type == "cost"; return YOLO_OK; }
+
+static int parse_detection(Cursor &k, const Section &s, Layer &L)
+{
+    yolo_ctx *c = k.c; const int i = k.i;
+    L.type = L_DETECT; L.classes = opt_i(s, "classes", 1); L.na = opt_i(s, "num", 1); L.side = opt_i(s, "side", 7); L.sqr = opt_i(s, "sqrt", 0);
+    if (opt_i(s, "coords", 4) != 4 || opt_i(s, "softmax", 0)) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [detection] with coords != 4 or softmax", i);
+    if (i > 0 && c->layers[i - 1].type == L_GCONV) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: a [convolutional] with groups=%d directly in front of a [detection] head is not served ([detection] must follow a [connected] layer)", i - 1, c->layers[i - 1].groups);
+    if (i == 0 || !c->layers[i - 1].fc) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [detection] must follow a [connected] layer", i);
+    if (k.C != L.side * L.side * (L.classes + L.na * 5)) return fail(c, YOLO_ERR_INVALID, "layer %d: [detection] expects %d inputs, got %d", i, L.side * L.side * (L.classes + L.na * 5), k.C);
+    if (c->attrs && c->attrs != 5 + L.classes) return fail(c, YOLO_ERR_UNSUPPORTED, "heads with different class counts");
+    c->attrs = 5 + L.classes; L.row_off = c->rows; c->rows += L.side * L.side * L.na;
+    if (c->layers[i - 1].post_act != ACT_LINEAR) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: the layer in front of a [detection] head needs a linear, leaky, relu or relie activation", i - 1);
+    c->layers[i - 1].head = true;
+    k.H = L.side; k.W = L.side;
+    return YOLO_OK;
+}
+
+static int parse_shortcut(Cursor &k, const Section &s, Layer &L)
+{
+    yolo_ctx *c = k.c; const int i = k.i;
+    L.type = L_SHORTCUT; int f = opt_i(s, "from", -1); f = f < 0 ? i + f : f;
+    if (f < 0 || f >= i) return fail(c, YOLO_ERR_INVALID, "layer %d: bad shortcut from", i);
+    L.in = {i - 1, f};
+    if (int r = plan_activation(c, i, s, "linear", true)) return r;
+    // the general form (DN/blas.c:68-92 shortcut_cpu): a `from` tensor of another channel count or size, or an activation.  (w1, h1,
+    // c1) = the `from` tensor, (w2, h2, c2) = this layer's input and output; the reference asserts what is checked here
+    int h1, w1, c1; k.dims(f, h1, w1, c1);
+    L.general = h1 != k.H || w1 != k.W || c1 != k.C || L.act != ACT_LINEAR;
+    if (!shortcut_geom(w1, h1, c1, k.W, k.H, k.C).ok)
+        return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: shortcut of a %d x %d tensor (layer %d) into a %d x %d one: darknet requires w1 / w2 == h1 / h2 and w2 / w1 == h2 / h1", i, w1, h1, f, k.W, k.H);
+    if (L.general && c->dtype == YOLO_FP8)
+        return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: a [shortcut] with an activation or a `from` tensor of another shape is not served in the fp8 configuration", i);
+    return YOLO_OK;
+}
+
+static int parse_route(Cursor &k, const Section &s, Layer &L)
+{
+    yolo_ctx *c = k.c; const int i = k.i;
+    L.type = L_ROUTE; L.in.clear();
+    std::vector<float> ls = opt_list(s, "layers");
+    if (ls.empty()) return fail(c, YOLO_ERR_INVALID, "layer %d: route without layers", i);
+    k.C = 0;
+    for (float v : ls) {
+        int l = (int)v; l = l < 0 ? i + l : l;
+        if (l < 0 || l >= i) return fail(c, YOLO_ERR_INVALID, "layer %d: bad route index", i);
+        L.in.push_back(l);
+        int h2, w2, c2; k.dims(l, h2, w2, c2);
+        if (L.in.size() == 1) { k.H = h2; k.W = w2; } else if (h2 != k.H || w2 != k.W) return fail(c, YOLO_ERR_INVALID, "layer %d: route spatial mismatch", i);
+        k.C += c2;
+    }
+    return YOLO_OK;
+}
+
+// TF semantics: the 2x bilinear closed form only.  darknet semantics (DN/upsample_layer.c): nearest, any stride 1..8; a stride
+// below 1 is darknet's reverse mode, which is not served.  scale= (out = scale * in) in both
+static int parse_upsample(Cursor &k, const Section &s, Layer &L)
+{
+    yolo_ctx *c = k.c; const int i = k.i;
+    L.type = L_UPSAMPLE; L.pstride = opt_i(s, "stride", 2); L.up_scale = (float)atof(opt_s(s, "scale", "1").c_str());
+    if (c->semantics == YOLO_SEM_DARKNET ? (L.pstride < 1 || L.pstride > 8) : L.pstride != 2) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: upsample stride %d", i, L.pstride);
+    if ((L.pstride != 2 || L.up_scale != 1.f) && (c->dtype == YOLO_FP8 || c->split()))
+        return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [upsample] with a stride other than 2 or a scale is not served in the fp8 / split-fp16 configurations", i);
+    k.H *= L.pstride; k.W *= L.pstride;
+    return YOLO_OK;
+}
+
+// [logistic] / [activation] (DN/logistic_layer.c, DN/activation_layer.c): activate_array over a copy of the input -- here k_activate over the producer's tensor
+static int parse_activate(Cursor &k, const Section &s, Layer &L)
+{
+    yolo_ctx *c = k.c; const int i = k.i;
+    if (c->dtype == YOLO_FP8) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [%s] is not served in the fp8 configuration", i, s.type.c_str());
+    L.type = L_ACTIVATE;
+    if (s.type == "logistic") L.act = ACT_LOGISTIC;
+    else if (int r = plan_activation(c, i, s, "linear", true)) return r;
+    return YOLO_OK;
+}
+
+static int parse_l2norm(Cursor &k, const Section &, Layer &L)
+{
+    if (k.c->dtype == YOLO_FP8 || k.c->split()) return fail(k.c, YOLO_ERR_UNSUPPORTED, "layer %d: [l2norm] is not served in the fp8 / split-fp16 configurations", k.i);
+    L.type = L_L2NORM;
+    return YOLO_OK;
+}
+
+static int parse_maxpool(Cursor &k, const Section &s, Layer &L)
+{
+    yolo_ctx *c = k.c; const int i = k.i;
+    L.type = L_MAXPOOL; L.pstride = opt_i(s, "stride", 1); L.psize = opt_i(s, "size", L.pstride);
+    L.ppad = opt_i(s, "padding", (L.psize - 1) / 2);
+    if (L.pstride < 1 || L.psize < 1 || L.ppad < 0) return fail(c, YOLO_ERR_INVALID, "layer %d: [maxpool] size %d, stride %d, padding %d", i, L.psize, L.pstride, L.ppad);
+    k.H = (k.H + 2 * L.ppad) / L.pstride; k.W = (k.W + 2 * L.ppad) / L.pstride;
+    if (k.H < 1 || k.W < 1) return fail(c, YOLO_ERR_INVALID, "layer %d: [maxpool] with stride %d leaves no output pixel", i, L.pstride);
+    return YOLO_OK;
+}
+
+static int parse_reorg(Cursor &k, const Section &s, Layer &L)
+{
+    yolo_ctx *c = k.c; const int i = k.i;
+    L.type = L_REORG; L.pstride = opt_i(s, "stride", 1);
+    if (L.pstride < 1 || k.H % L.pstride || k.W % L.pstride) return fail(c, YOLO_ERR_INVALID, "layer %d: reorg stride", i);
+    // darknet's reorg_cpu takes channel indices modulo c / stride^2 (DN/blas.c:9-30): with fewer channels than stride^2 it divides by zero
+    if (c->semantics == YOLO_SEM_DARKNET && k.C < L.pstride * L.pstride) return fail(c, YOLO_ERR_INVALID, "layer %d: [reorg] with stride %d needs at least %d channels in darknet semantics (its producer has %d)", i, L.pstride, L.pstride * L.pstride, k.C);
+    k.H /= L.pstride; k.W /= L.pstride; k.C *= L.pstride * L.pstride;
+    return YOLO_OK;
+}
+
+// [yolo] / [region]: the anchors (masked for [yolo]), the rows the head adds, `head` on the conv in front of it
+static int parse_head(Cursor &k, const Section &s, Layer &L)
+{
+    yolo_ctx *c = k.c; const int i = k.i;
+    L.type = s.type == "yolo" ? L_YOLO : L_REGION;
+    L.classes = opt_i(s, "classes", 20);
+    std::vector<float> an = opt_list(s, "anchors"), mask = opt_list(s, "mask");
+    int total = opt_i(s, "num", 1);
+    if ((int)an.size() < 2 * total) return fail(c, YOLO_ERR_INVALID, "layer %d: anchors/num mismatch", i);
+    if (L.type == L_YOLO && !mask.empty()) { for (float m : mask) { int a = (int)m; if (a < 0 || a >= total) return fail(c, YOLO_ERR_INVALID, "layer %d: mask", i); L.anchors.push_back(an[2 * a]); L.anchors.push_back(an[2 * a + 1]); } }
+    else L.anchors.assign(an.begin(), an.begin() + 2 * total);
+    L.na = (int)L.anchors.size() / 2;
+    if (L.na > 16) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: more than 16 anchors", i);
+    if (i > 0 && c->layers[i - 1].type == L_GCONV) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: a [convolutional] with groups=%d directly in front of a [%s] head is not served (the head's objectness plane and lean decode belong to the dense kernels; put a dense 1x1 conv in between)", i - 1, c->layers[i - 1].groups, s.type.c_str());
+    if (i == 0 || c->layers[i - 1].type != L_CONV) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: head must follow a conv", i);
+    if (k.C != L.na * (5 + L.classes)) return fail(c, YOLO_ERR_INVALID, "layer %d: head expects %d channels, conv gives %d", i, L.na * (5 + L.classes), k.C);
+    if (c->attrs && c->attrs != 5 + L.classes) return fail(c, YOLO_ERR_UNSUPPORTED, "heads with different class counts");
+    if (L.type == L_REGION && s.kv.count("tree")) {
+        // [region] with a softmax tree (YOLO9000, DN/region_layer.c:171-181): the tree takes precedence over softmax=1
+        if (opt_i(s, "background", 0)) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [region] tree= with background=1 is not served", i);
+        if (opt_i(s, "coords", 4) != 4) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [region] tree= with coords != 4 is not served", i);
+        if (s.kv.count("map")) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [region] tree= with map= in the cfg is not served (pass the map to yolo_darknet_boxes_map)", i);
+        if (c->rows) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: a [region] head with a tree must be the network's only head", i);
+        if (int r = plan_tree(c, i, "region", opt_s(s, "tree", ""), L.classes, "classes")) return r;
+        c->tree_head = i;
+    } else if (c->tree_head >= 0) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: a [region] head with a tree must be the network's only head", i);
+    c->attrs = 5 + L.classes; L.row_off = c->rows; c->rows += k.H * k.W * L.na;
+    if (c->layers[i - 1].post_act != ACT_LINEAR) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: the conv in front of a [yolo] / [region] head needs a linear, leaky, relu or relie activation", i - 1);
+    c->layers[i - 1].head = true;
+    return YOLO_OK;
+}
+
+// always global (DN/avgpool_layer.c:40-55): H x W x C -> 1 x 1 x C, stored in the form of its input
+static int parse_avgpool(Cursor &k, const Section &, Layer &L)
+{
+    if (k.c->dtype == YOLO_FP8) return fail(k.c, YOLO_ERR_UNSUPPORTED, "layer %d: [avgpool] is not served in the fp8 configuration", k.i);
+    L.type = L_AVGPOOL; k.H = 1; k.W = 1;
+    return YOLO_OK;
+}
+
+// DN/parser.c:268-280: groups, temperature; per image and group e = exp(x / temp - max / temp), p = e / sum (DN/blas.c:305-321)
+static int parse_softmax(Cursor &k, const Section &s, Layer &L)
+{
+    yolo_ctx *c = k.c; const int i = k.i;
+    if (c->dtype == YOLO_FP8) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [softmax] is not served in the fp8 configuration", i);
+    if (opt_i(s, "spatial", 0)) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [softmax] with spatial=1 is not served", i);
+    L.type = L_SOFTMAX; L.groups = opt_i(s, "groups", 1); L.temperature = (float)atof(opt_s(s, "temperature", "1").c_str());
+    if (k.H != 1 || k.W != 1) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [softmax] over a %d x %d map (it must follow an [avgpool] or a [connected] layer)", i, k.H, k.W);
+    if (!(L.temperature > 0.f)) return fail(c, YOLO_ERR_INVALID, "layer %d: [softmax] temperature must be > 0", i);
+    if (s.kv.count("tree")) {
+        // hierarchical softmax (DN/softmax_layer.c:41-48): one softmax per group of the tree, whatever `groups` says
+        if (int r = plan_tree(c, i, "softmax", opt_s(s, "tree", ""), k.C, "inputs")) return r;
+        L.groups = 1;
+    } else {
+        if (L.groups < 1 || k.C % L.groups) return fail(c, YOLO_ERR_INVALID, "layer %d: [softmax] groups=%d does not divide its %d inputs", i, L.groups, k.C);
+        if (k.C / L.groups > CLS_SOFTMAX_MAX) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [softmax] group of %d logits (at most %d)", i, k.C / L.groups, CLS_SOFTMAX_MAX);
+    }
+    // the logits are never rounded to 16 bits: the conv that reaches this layer directly, or through one [avgpool], writes fp32
+    int p = i - 1;
+    if (p >= 0 && c->layers[p].type == L_AVGPOOL) p = c->layers[p].in[0];
+    if (p >= 0 && (c->layers[p].type == L_CONV || c->layers[p].type == L_GCONV)) c->layers[p].head = true;      // (not L_DECONV: not computes())
+    return YOLO_OK;
+}
+
+static const struct { const char *name; int (*parse)(Cursor &, const Section &, Layer &); } section_table[] = {
+    {"convolutional", parse_convolutional}, {"connected", parse_connected}, {"local", parse_local}, {"dropout", parse_identity}, {"detection", parse_detection},
+    {"shortcut", parse_shortcut}, {"route", parse_route}, {"upsample", parse_upsample}, {"deconvolutional", parse_deconvolutional},
+    {"logistic", parse_activate}, {"activation", parse_activate}, {"l2norm", parse_l2norm}, {"maxpool", parse_maxpool}, {"reorg", parse_reorg},
+    {"yolo", parse_head}, {"region", parse_head}, {"avgpool", parse_avgpool}, {"softmax", parse_softmax}, {"cost", parse_identity},
+};
+
+// After each section: a layer that moves data keeps the type and the pair form of what it moves, and its operands must agree.
+// Reads store_dt / pair of the layers in L.in, L.general; writes L.store_dt, L.pair
+static int inherit_form(const Cursor &k, Layer &L)
+{
+    yolo_ctx *c = k.c; const int i = k.i;
+    if (computes(L) || L.type == L_LOCAL) return YOLO_OK;
+    int dt = -1;
+    for (int j : L.in) { const int dj = j < 0 ? c->act_dt() : c->layers[j].store_dt; if (dt >= 0 && dj != dt && (L.type == L_ROUTE || L.type == L_SHORTCUT)) return fail(c, YOLO_ERR_INVALID, "layer %d: operands stored in different types (yolo_store): a %s needs one type", i, L.type == L_ROUTE ? "route" : "shortcut"); if (dt < 0) dt = dj; }
+    L.store_dt = dt >= 0 ? dt : c->act_dt();
+    if (c->split() && !L.in.empty() && !is_head_layer(L)) {
+        L.pair = c->pair_of(L.in[0]);
+        for (int j : L.in) if (c->pair_of(j) != L.pair) return fail(c, YOLO_ERR_INVALID, "layer %d: operands stored in different forms (yolo_pair): a %s needs pairs or plain fp16 throughout", i, L.type == L_ROUTE ? "route" : L.type == L_SHORTCUT ? "shortcut" : "layer");
+        // pairs are interleaved per 32-channel group: the general shortcut's channel boundary (minc) must fall between groups
+        // ... and a [reorg] scrambles channels across them: whole groups in, whole groups out (via_f32)
+        if (L.type == L_REORG && L.pair) { int h1, w1, c1; k.dims(L.in[0], h1, w1, c1); if (c1 % 32 || L.C % 32) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: a [reorg] of split-fp16 pairs needs a channel count that is a multiple of 32 (%d)", i, c1); }
+        if (L.type == L_SHORTCUT && L.general && L.pair) { int h1, w1, c1; k.dims(L.in[1], h1, w1, c1); if (L.C % 32 || c1 % 32) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: a [shortcut] with an activation or a `from` tensor of another shape, on split-fp16 pairs, needs channel counts that are multiples of 32 (%d and %d)", i, L.C, c1); }
+    }
+    return YOLO_OK;
+}
+
+// [net] keys of the input, the layer array, the pair form of the image; then every section through section_table and inherit_form.
+// Writes in_h / in_w / in_c / in_pair, the totals, and per layer everything the parsers and inherit_form write plus in[] and H / W / C
+static int parse_sections(yolo_ctx *c, const std::vector<Section> &secs)
 {
     const Section &net = secs[0];
     c->in_h = opt_i(net, "height", 0); c->in_w = opt_i(net, "width", 0); c->in_c = opt_i(net, "channels", 3);
@@ -87,266 +445,35 @@ int build_plan(yolo_ctx *c, const std::vector<Section> &secs)
         return fail(c, YOLO_ERR_UNSUPPORTED, "cfg: need an input of positive height and width with 3 channels (got %dx%dx%d)", c->in_w, c->in_h, c->in_c);
     const int NL = (int)secs.size() - 1;
     c->layers.resize(NL);
-    int H = c->in_h, W = c->in_w, C = c->in_c;
-    auto dims = [&](int idx, int &h, int &w, int &ch) { if (idx < 0) { h = c->in_h; w = c->in_w; ch = c->in_c; } else { h = c->layers[idx].H; w = c->layers[idx].W; ch = c->layers[idx].C; } };
     c->rows = 0; c->attrs = 0; c->conv_flops = 0; c->weights_count = 0;
     // split-fp16 networks: per-tensor storage form (mixed plans): pairs unless a [convolutional] section says yolo_pair=0
     // ([net] yolo_pair_input for the image); layers that move data inherit, both operands of a shortcut / all inputs of a route must agree
     c->in_pair = c->split() && opt_i(net, "yolo_pair_input", 1) != 0;
     // (a 7x7 / stride 2 first conv reads the 2x2 space-to-depth of the image, which is kept as plain fp16: such a network's input is never pairs)
     if (c->in_pair && NL >= 1 && secs[1].type == "convolutional" && opt_i(secs[1], "size", 1) == 7 && opt_i(secs[1], "stride", 1) == 2) c->in_pair = false;
-    for (int i = 0; i < NL; ++i) {
-        const Section &s = secs[i + 1]; Layer &L = c->layers[i];
-        L.in = {i - 1};
-        if (!c->split() && (s.kv.count("yolo_pair") || net.kv.count("yolo_pair_input"))) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: yolo_pair is a key of split-fp16 networks (YOLO_FP16X2)", i);
-        if (s.type == "convolutional" && opt_i(s, "groups", 1) != 1) {
-            // grouped convolution (DN/parser.c:184, DN/convolutional_layer.c:458-471): a layer kind of its own with its own kernel (gconv.hip).  Like
-            // [deconvolutional] it is never a member of a fused launch, neither end of a 1x1 tail, no host of a folded [shortcut] and nothing for
-            // the tile tuner to choose -- every marking pass asks for L_CONV
-            L.groups = opt_i(s, "groups", 1);
-            if (L.groups < 1) return fail(c, YOLO_ERR_INVALID, "layer %d: [convolutional] groups=%d", i, L.groups);
-            if (c->dtype == YOLO_FP8) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [convolutional] with groups=%d is not served in the fp8 configuration", i, L.groups);
-            if (c->split()) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [convolutional] with groups=%d is not served in the split-fp16 configuration", i, L.groups);
-            if (i == 0) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [convolutional] with groups=%d as the network's first layer is not served (the image is read by the dense kernels only)", i, L.groups);
-            L.type = L_GCONV; L.filters = opt_i(s, "filters", 1); L.size = opt_i(s, "size", 1); L.stride = opt_i(s, "stride", 1);
-            L.pad = opt_i(s, "pad", 0) ? L.size / 2 : opt_i(s, "padding", 0);
-            L.bn = opt_i(s, "batch_normalize", 0);
-            if (L.filters < 1) return fail(c, YOLO_ERR_INVALID, "layer %d: conv filters %d", i, L.filters);
-            if (C % L.groups) return fail(c, YOLO_ERR_INVALID, "layer %d: groups=%d does not divide the %d input channels", i, L.groups, C);
-            if (L.filters % L.groups) return fail(c, YOLO_ERR_INVALID, "layer %d: groups=%d does not divide filters=%d", i, L.groups, L.filters);
-            if (L.size < 1 || L.size > GCONV_MAX_SIZE) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: grouped conv size %d (1..%d are served)", i, L.size, GCONV_MAX_SIZE);
-            if (L.stride < 1 || L.stride > GCONV_MAX_STRIDE) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: grouped conv stride %d (1..%d are served)", i, L.stride, GCONV_MAX_STRIDE);
-            if (L.pad < 0 || L.pad >= L.size) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: grouped conv padding %d must be below its size %d", i, L.pad, L.size);
-            if (H + 2 * L.pad < L.size || W + 2 * L.pad < L.size) return fail(c, YOLO_ERR_INVALID, "layer %d: grouped conv larger than its padded input", i);
-            if (int r = plan_activation(c, i, s, "logistic", false)) return r;
-            L.in_dt = c->act_dt(); L.store_dt = c->act_dt();
-            L.cin = C; L.cin_pad = roundup(C, 8);
-            { GConvArgs g; memset(&g, 0, sizeof g); g.C = C; g.Cout = L.filters; g.groups = L.groups; g.size = L.size; g.in_dt = L.in_dt; gconv_layout(g); L.kpad = g.kp; L.cout_pad = g.nb * g.mb; }      // cout_pad * kpad elements of filters
-            H = (H + 2 * L.pad - L.size) / L.stride + 1; W = (W + 2 * L.pad - L.size) / L.stride + 1; C = L.filters;
-            c->conv_flops += 2.0 * L.size * L.size * (L.cin / L.groups) * L.filters * (double)H * W;      // DN/convolutional_layer.c:201, :325: c / groups
-            c->weights_count += (size_t)L.filters * (L.bn ? 4 : 1) + (size_t)L.filters * (L.cin / L.groups) * L.size * L.size;
-        } else if (s.type == "convolutional") {
-            L.type = L_CONV; L.filters = opt_i(s, "filters", 1); L.size = opt_i(s, "size", 1); L.stride = opt_i(s, "stride", 1);
-            L.pad = opt_i(s, "pad", 0) ? L.size / 2 : opt_i(s, "padding", 0);
-            L.bn = opt_i(s, "batch_normalize", 0);
-            if (int r = plan_activation(c, i, s, "logistic", false)) return r;
-            if (L.size == 7 && L.stride == 2 && L.pad == 3 && i == 0 && C == 3 && H % 2 == 0 && W % 2 == 0 && c->dtype != YOLO_FP8) L.s2d7 = true;
-            else if (L.size != 1 && L.size != 3) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: conv size %d unsupported on the device path", i, L.size);
-            // padding= is taken literally when pad=0, and any stride: the tiled kernels serve both; what has no output pixel is refused
-            if (L.filters < 1) return fail(c, YOLO_ERR_INVALID, "layer %d: conv filters %d", i, L.filters);
-            if (L.stride < 1 || L.pad < 0) return fail(c, YOLO_ERR_INVALID, "layer %d: conv stride %d, padding %d", i, L.stride, L.pad);
-            if (H + 2 * L.pad < L.size || W + 2 * L.pad < L.size) return fail(c, YOLO_ERR_INVALID, "layer %d: conv larger than its padded input (%d x %d with padding %d under a size %d conv)", i, W, H, L.pad, L.size);
-            // fp8 mode: the first conv still reads the bf16 image (3 real channels padded to 8) with bf16 filters; a conv reads its
-            // producer's tensor in the type that tensor is stored in (cfg key `yolo_store=bf16` on a [convolutional] section of an fp8
-            // network keeps that layer's output -- and what is derived from it without arithmetic -- in bf16: mixed-precision plans)
-            L.in_dt = c->dtype == YOLO_FP8 ? (i == 0 ? DT_BF16 : c->layers[i - 1].store_dt) : c->act_dt();
-            L.store_dt = c->act_dt();
-            {
-                const std::string st = opt_s(s, "yolo_store", "");
-                if (!st.empty()) {
-                    if (c->dtype != YOLO_FP8) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: yolo_store is a key of fp8 networks (mixed e4m3 / bf16 plans)", i);
-                    if (st == "bf16") L.store_dt = DT_BF16; else if (st == "fp8") L.store_dt = DT_FP8;
-                    else return fail(c, YOLO_ERR_INVALID, "layer %d: yolo_store=%s (bf16 or fp8)", i, st.c_str());
-                }
-            }
-            L.cin = C; L.cin_pad = roundup(C, L.in_dt == DT_FP8 ? 16 : 8);
-            // the conv kernel's view of a pair tensor: a layer output is interleaved per 32-channel group, 2 * roundup(C, 32) elements per
-            // pixel and tap (pair K loop); the network input keeps the three blocks hi | lo | hi of its 8 padded channels (plain K loop)
-            if (c->pair_of(i - 1)) L.cin_pad = i - 1 < 0 ? 3 * roundup(C, 8) : pair_width(C);
-            L.pair = c->split() && opt_i(s, "yolo_pair", 1) != 0;
-            L.kpad = roundup(L.size * L.size * L.cin_pad, L.in_dt == DT_FP8 ? 128 : 64); L.cout_pad = roundup(L.filters, 256);
-            if (L.s2d7) { L.cin_pad = 32; L.kpad = 16 * 32; }          // 4x4 taps x (2x2 positions x 8 padded channels)
-            H = (H + 2 * L.pad - L.size) / L.stride + 1; W = (W + 2 * L.pad - L.size) / L.stride + 1; C = L.filters;
-            c->conv_flops += 2.0 * L.size * L.size * L.cin * L.filters * (double)H * W;
-            c->weights_count += (size_t)L.filters * (L.bn ? 4 : 1) + (size_t)L.filters * L.cin * L.size * L.size;
-        } else if (s.type == "connected") {
-            if (c->dtype == YOLO_FP8 || c->split()) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [connected] is not served in the fp8 / split-fp16 configurations", i);
-            if (opt_i(s, "batch_normalize", 0)) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: batch-normalised [connected]", i);
-            L.type = L_CONV; L.fc = true; L.fc_h = H; L.fc_w = W; L.fc_c = C;
-            L.filters = opt_i(s, "output", 1); L.size = 1; L.stride = 1; L.pad = 0; L.bn = 0;
-            if (int r = plan_activation(c, i, s, "logistic", false)) return r;
-            L.in_dt = c->act_dt(); L.store_dt = c->act_dt();
-            if ((long)H * W * C > (1L << 24)) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [connected] input too large", i);
-            L.cin = H * W * C; L.cin_pad = roundup(L.cin, 8); L.kpad = roundup(L.cin_pad, 64); L.cout_pad = roundup(L.filters, 256);
-            c->conv_flops += 2.0 * L.cin * L.filters;
-            c->weights_count += (size_t)L.filters + (size_t)L.filters * L.cin;
-            H = 1; W = 1; C = L.filters;
-        } else if (s.type == "local") {
-            // locally connected (DN/local_layer.c; darknet's own yolov1.cfg): `pad` is a flag AND the im2col pad amount (:10-24, :103)
-            if (c->dtype == YOLO_FP8 || c->split()) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [local] is not served in the fp8 / split-fp16 configurations", i);
-            L.type = L_LOCAL; L.filters = opt_i(s, "filters", 1); L.size = opt_i(s, "size", 1); L.stride = opt_i(s, "stride", 1); L.pad = opt_i(s, "pad", 0);
-            if (L.pad != 0 && L.pad != 1) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [local] pad must be 0 or 1", i);
-            // pad=1 pads by ONE pixel whatever the size (DN/local_layer.c:103 im2col) while the output size assumes size / 2 (:10-24): they only agree for 3x3
-            if (L.pad == 1 && L.size != 3) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [local] with pad=1 needs size=3 (darknet's own output size and im2col disagree otherwise)", i);
-            if (int r = plan_activation(c, i, s, "logistic", false)) return r;
-            if (C % 8) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [local] needs a producer with a multiple of 8 channels", i);
-            L.cin = C; L.cin_pad = C; L.in_dt = c->act_dt(); L.store_dt = c->act_dt();
-            const int ho = ((L.pad ? H - 1 : H - L.size)) / L.stride + 1, wo = ((L.pad ? W - 1 : W - L.size)) / L.stride + 1;
-            if (ho < 1 || wo < 1) return fail(c, YOLO_ERR_INVALID, "layer %d: [local] larger than its input", i);
-            H = ho; W = wo; C = L.filters;
-            c->conv_flops += 2.0 * L.size * L.size * L.cin * L.filters * (double)H * W;
-            c->weights_count += (size_t)L.filters * H * W + (size_t)H * W * L.filters * L.cin * L.size * L.size;
-        } else if (s.type == "dropout") {
-            L.type = L_ROUTE;                       // inference: identity (DN/dropout_layer.c:38-40)
-        } else if (s.type == "detection") {
-            L.type = L_DETECT; L.classes = opt_i(s, "classes", 1); L.na = opt_i(s, "num", 1); L.side = opt_i(s, "side", 7); L.sqr = opt_i(s, "sqrt", 0);
-            if (opt_i(s, "coords", 4) != 4 || opt_i(s, "softmax", 0)) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [detection] with coords != 4 or softmax", i);
-            if (i > 0 && c->layers[i - 1].type == L_GCONV) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: a [convolutional] with groups=%d directly in front of a [detection] head is not served ([detection] must follow a [connected] layer)", i - 1, c->layers[i - 1].groups);
-            if (i == 0 || !c->layers[i - 1].fc) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [detection] must follow a [connected] layer", i);
-            if (C != L.side * L.side * (L.classes + L.na * 5)) return fail(c, YOLO_ERR_INVALID, "layer %d: [detection] expects %d inputs, got %d", i, L.side * L.side * (L.classes + L.na * 5), C);
-            if (c->attrs && c->attrs != 5 + L.classes) return fail(c, YOLO_ERR_UNSUPPORTED, "heads with different class counts");
-            c->attrs = 5 + L.classes; L.row_off = c->rows; c->rows += L.side * L.side * L.na;
-            if (c->layers[i - 1].post_act != ACT_LINEAR) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: the layer in front of a [detection] head needs a linear, leaky, relu or relie activation", i - 1);
-            c->layers[i - 1].head = true;
-            H = L.side; W = L.side;
-        } else if (s.type == "shortcut") {
-            L.type = L_SHORTCUT; int f = opt_i(s, "from", -1); f = f < 0 ? i + f : f;
-            if (f < 0 || f >= i) return fail(c, YOLO_ERR_INVALID, "layer %d: bad shortcut from", i);
-            L.in = {i - 1, f};
-            if (int r = plan_activation(c, i, s, "linear", true)) return r;
-            // the general form (DN/blas.c:68-92 shortcut_cpu): a `from` tensor of another channel count or size, or an activation.  (w1, h1,
-            // c1) = the `from` tensor, (w2, h2, c2) = this layer's input and output; the reference asserts what is checked here
-            int h1, w1, c1; dims(f, h1, w1, c1);
-            L.general = h1 != H || w1 != W || c1 != C || L.act != ACT_LINEAR;
-            if (!shortcut_geom(w1, h1, c1, W, H, C).ok)
-                return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: shortcut of a %d x %d tensor (layer %d) into a %d x %d one: darknet requires w1 / w2 == h1 / h2 and w2 / w1 == h2 / h1", i, w1, h1, f, W, H);
-            if (L.general && c->dtype == YOLO_FP8)
-                return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: a [shortcut] with an activation or a `from` tensor of another shape is not served in the fp8 configuration", i);
-        } else if (s.type == "route") {
-            L.type = L_ROUTE; L.in.clear();
-            std::vector<float> ls = opt_list(s, "layers");
-            if (ls.empty()) return fail(c, YOLO_ERR_INVALID, "layer %d: route without layers", i);
-            C = 0;
-            for (float v : ls) {
-                int l = (int)v; l = l < 0 ? i + l : l;
-                if (l < 0 || l >= i) return fail(c, YOLO_ERR_INVALID, "layer %d: bad route index", i);
-                L.in.push_back(l);
-                int h2, w2, c2; dims(l, h2, w2, c2);
-                if (L.in.size() == 1) { H = h2; W = w2; } else if (h2 != H || w2 != W) return fail(c, YOLO_ERR_INVALID, "layer %d: route spatial mismatch", i);
-                C += c2;
-            }
-        } else if (s.type == "upsample") {
-            // TF semantics: the 2x bilinear closed form only.  darknet semantics (DN/upsample_layer.c): nearest, any stride 1..8; a stride
-            // below 1 is darknet's reverse mode, which is not served.  scale= (out = scale * in) in both
-            L.type = L_UPSAMPLE; L.pstride = opt_i(s, "stride", 2); L.up_scale = (float)atof(opt_s(s, "scale", "1").c_str());
-            if (c->semantics == YOLO_SEM_DARKNET ? (L.pstride < 1 || L.pstride > 8) : L.pstride != 2) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: upsample stride %d", i, L.pstride);
-            if ((L.pstride != 2 || L.up_scale != 1.f) && (c->dtype == YOLO_FP8 || c->split()))
-                return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [upsample] with a stride other than 2 or a scale is not served in the fp8 / split-fp16 configurations", i);
-            H *= L.pstride; W *= L.pstride;
-        } else if (s.type == "deconvolutional") {
-            // transposed convolution (DN/deconvolutional_layer.c, DN/parser.c:151-174): its own kernel (deconv.hip), never a member of a fused
-            // launch, neither end of a 1x1 tail, and a [shortcut] behind it is not folded into it -- every marking pass asks for L_CONV
-            if (c->dtype == YOLO_FP8) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [deconvolutional] is not served in the fp8 configuration", i);
-            if (c->split()) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [deconvolutional] is not served in the split-fp16 configuration", i);
-            L.type = L_DECONV; L.filters = opt_i(s, "filters", 1); L.size = opt_i(s, "size", 1); L.stride = opt_i(s, "stride", 1);
-            L.pad = opt_i(s, "pad", 0) ? L.size / 2 : opt_i(s, "padding", 0);
-            L.bn = opt_i(s, "batch_normalize", 0);
-            if (L.size < 1 || L.size > DECONV_MAX_SIZE) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: deconv size %d (1..%d are served)", i, L.size, DECONV_MAX_SIZE);
-            if (L.stride < 1 || L.stride > DECONV_MAX_STRIDE) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: deconv stride %d (1..%d are served)", i, L.stride, DECONV_MAX_STRIDE);
-            if (L.pad < 0 || L.pad >= L.size) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: deconv padding %d must be below its size %d", i, L.pad, L.size);
-            if (L.filters < 1) return fail(c, YOLO_ERR_INVALID, "layer %d: deconv filters %d", i, L.filters);
-            const int ho = (H - 1) * L.stride + L.size - 2 * L.pad, wo = (W - 1) * L.stride + L.size - 2 * L.pad;
-            if (ho < 1 || wo < 1) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: deconv output %d x %d is not positive", i, wo, ho);
-            if (int r = plan_activation(c, i, s, "logistic", false)) return r;
-            L.in_dt = c->act_dt(); L.store_dt = c->act_dt();
-            L.cin = C; L.cin_pad = roundup(C, 8); L.cout_pad = roundup(L.filters, DECONV_CO_TILE);
-            { DeconvArgs g; memset(&g, 0, sizeof g); g.size = L.size; g.stride = L.stride; g.Cin_pad = L.cin_pad; g.cout_pad = L.cout_pad; L.kpad = (int)(deconv_layout(g) / L.cout_pad); }      // (the K of all phases together: cout_pad * kpad elements of filters)
-            c->conv_flops += 2.0 * L.size * L.size * L.cin * L.filters * (double)H * W;
-            c->weights_count += (size_t)L.filters * (L.bn ? 4 : 1) + (size_t)L.cin * L.filters * L.size * L.size;
-            H = ho; W = wo; C = L.filters;
-        } else if (s.type == "logistic" || s.type == "activation") {
-            // DN/logistic_layer.c, DN/activation_layer.c: activate_array over a copy of the input -- here k_activate over the producer's tensor
-            if (c->dtype == YOLO_FP8) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [%s] is not served in the fp8 configuration", i, s.type.c_str());
-            L.type = L_ACTIVATE;
-            if (s.type == "logistic") L.act = ACT_LOGISTIC;
-            else if (int r = plan_activation(c, i, s, "linear", true)) return r;
-        } else if (s.type == "l2norm") {
-            if (c->dtype == YOLO_FP8 || c->split()) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [l2norm] is not served in the fp8 / split-fp16 configurations", i);
-            L.type = L_L2NORM;
-        } else if (s.type == "maxpool") {
-            L.type = L_MAXPOOL; L.pstride = opt_i(s, "stride", 1); L.psize = opt_i(s, "size", L.pstride);
-            L.ppad = opt_i(s, "padding", (L.psize - 1) / 2);
-            if (L.pstride < 1 || L.psize < 1 || L.ppad < 0) return fail(c, YOLO_ERR_INVALID, "layer %d: [maxpool] size %d, stride %d, padding %d", i, L.psize, L.pstride, L.ppad);
-            H = (H + 2 * L.ppad) / L.pstride; W = (W + 2 * L.ppad) / L.pstride;
-            if (H < 1 || W < 1) return fail(c, YOLO_ERR_INVALID, "layer %d: [maxpool] with stride %d leaves no output pixel", i, L.pstride);
-        } else if (s.type == "reorg") {
-            L.type = L_REORG; L.pstride = opt_i(s, "stride", 1);
-            if (L.pstride < 1 || H % L.pstride || W % L.pstride) return fail(c, YOLO_ERR_INVALID, "layer %d: reorg stride", i);
-            // darknet's reorg_cpu takes channel indices modulo c / stride^2 (DN/blas.c:9-30): with fewer channels than stride^2 it divides by zero
-            if (c->semantics == YOLO_SEM_DARKNET && C < L.pstride * L.pstride) return fail(c, YOLO_ERR_INVALID, "layer %d: [reorg] with stride %d needs at least %d channels in darknet semantics (its producer has %d)", i, L.pstride, L.pstride * L.pstride, C);
-            H /= L.pstride; W /= L.pstride; C *= L.pstride * L.pstride;
-        } else if (s.type == "yolo" || s.type == "region") {
-            L.type = s.type == "yolo" ? L_YOLO : L_REGION;
-            L.classes = opt_i(s, "classes", 20);
-            std::vector<float> an = opt_list(s, "anchors"), mask = opt_list(s, "mask");
-            int total = opt_i(s, "num", 1);
-            if ((int)an.size() < 2 * total) return fail(c, YOLO_ERR_INVALID, "layer %d: anchors/num mismatch", i);
-            if (L.type == L_YOLO && !mask.empty()) { for (float m : mask) { int k = (int)m; if (k < 0 || k >= total) return fail(c, YOLO_ERR_INVALID, "layer %d: mask", i); L.anchors.push_back(an[2 * k]); L.anchors.push_back(an[2 * k + 1]); } }
-            else L.anchors.assign(an.begin(), an.begin() + 2 * total);
-            L.na = (int)L.anchors.size() / 2;
-            if (L.na > 16) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: more than 16 anchors", i);
-            if (i > 0 && c->layers[i - 1].type == L_GCONV) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: a [convolutional] with groups=%d directly in front of a [%s] head is not served (the head's objectness plane and lean decode belong to the dense kernels; put a dense 1x1 conv in between)", i - 1, c->layers[i - 1].groups, s.type.c_str());
-            if (i == 0 || c->layers[i - 1].type != L_CONV) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: head must follow a conv", i);
-            if (C != L.na * (5 + L.classes)) return fail(c, YOLO_ERR_INVALID, "layer %d: head expects %d channels, conv gives %d", i, L.na * (5 + L.classes), C);
-            if (c->attrs && c->attrs != 5 + L.classes) return fail(c, YOLO_ERR_UNSUPPORTED, "heads with different class counts");
-            if (L.type == L_REGION && s.kv.count("tree")) {
-                // [region] with a softmax tree (YOLO9000, DN/region_layer.c:171-181): the tree takes precedence over softmax=1
-                if (opt_i(s, "background", 0)) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [region] tree= with background=1 is not served", i);
-                if (opt_i(s, "coords", 4) != 4) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [region] tree= with coords != 4 is not served", i);
-                if (s.kv.count("map")) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [region] tree= with map= in the cfg is not served (pass the map to yolo_darknet_boxes_map)", i);
-                if (c->rows) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: a [region] head with a tree must be the network's only head", i);
-                if (int r = plan_tree(c, i, "region", opt_s(s, "tree", ""), L.classes, "classes")) return r;
-                c->tree_head = i;
-            } else if (c->tree_head >= 0) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: a [region] head with a tree must be the network's only head", i);
-            c->attrs = 5 + L.classes; L.row_off = c->rows; c->rows += H * W * L.na;
-            if (c->layers[i - 1].post_act != ACT_LINEAR) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: the conv in front of a [yolo] / [region] head needs a linear, leaky, relu or relie activation", i - 1);
-            c->layers[i - 1].head = true;
-        } else if (s.type == "avgpool") {
-            // always global (DN/avgpool_layer.c:40-55): H x W x C -> 1 x 1 x C, stored in the form of its input
-            if (c->dtype == YOLO_FP8) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [avgpool] is not served in the fp8 configuration", i);
-            L.type = L_AVGPOOL; H = 1; W = 1;
-        } else if (s.type == "softmax") {
-            // DN/parser.c:268-280: groups, temperature; per image and group e = exp(x / temp - max / temp), p = e / sum (DN/blas.c:305-321)
-            if (c->dtype == YOLO_FP8) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [softmax] is not served in the fp8 configuration", i);
-            if (opt_i(s, "spatial", 0)) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [softmax] with spatial=1 is not served", i);
-            L.type = L_SOFTMAX; L.groups = opt_i(s, "groups", 1); L.temperature = (float)atof(opt_s(s, "temperature", "1").c_str());
-            if (H != 1 || W != 1) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [softmax] over a %d x %d map (it must follow an [avgpool] or a [connected] layer)", i, H, W);
-            if (!(L.temperature > 0.f)) return fail(c, YOLO_ERR_INVALID, "layer %d: [softmax] temperature must be > 0", i);
-            if (s.kv.count("tree")) {
-                // hierarchical softmax (DN/softmax_layer.c:41-48): one softmax per group of the tree, whatever `groups` says
-                if (int r = plan_tree(c, i, "softmax", opt_s(s, "tree", ""), C, "inputs")) return r;
-                L.groups = 1;
-            } else {
-            if (L.groups < 1 || C % L.groups) return fail(c, YOLO_ERR_INVALID, "layer %d: [softmax] groups=%d does not divide its %d inputs", i, L.groups, C);
-            if (C / L.groups > CLS_SOFTMAX_MAX) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [softmax] group of %d logits (at most %d)", i, C / L.groups, CLS_SOFTMAX_MAX);
-            }
-            // the logits are never rounded to 16 bits: the conv that reaches this layer directly, or through one [avgpool], writes fp32
-            int p = i - 1;
-            if (p >= 0 && c->layers[p].type == L_AVGPOOL) p = c->layers[p].in[0];
-            if (p >= 0 && (c->layers[p].type == L_CONV || c->layers[p].type == L_GCONV)) c->layers[p].head = true;
-        } else if (s.type == "cost") {
-            L.type = L_ROUTE; L.cost = true;         // inference: identity (DN/cost_layer.c: forward returns without a truth)
-        } else {
-            return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: section [%s] is outside the inference hot path", i, s.type.c_str());
-        }
-        L.H = H; L.W = W; L.C = C;
-        if (L.type != L_CONV && L.type != L_LOCAL && L.type != L_DECONV && L.type != L_GCONV) {
-            // layers that move data keep the type of what they move; their operands must agree
-            int dt = -1;
-            for (int j : L.in) { const int dj = j < 0 ? c->act_dt() : c->layers[j].store_dt; if (dt >= 0 && dj != dt && (L.type == L_ROUTE || L.type == L_SHORTCUT)) return fail(c, YOLO_ERR_INVALID, "layer %d: operands stored in different types (yolo_store): a %s needs one type", i, L.type == L_ROUTE ? "route" : "shortcut"); if (dt < 0) dt = dj; }
-            L.store_dt = dt >= 0 ? dt : c->act_dt();
-            if (c->split() && !L.in.empty() && L.type != L_YOLO && L.type != L_REGION && L.type != L_DETECT) {
-                L.pair = c->pair_of(L.in[0]);
-                for (int j : L.in) if (c->pair_of(j) != L.pair) return fail(c, YOLO_ERR_INVALID, "layer %d: operands stored in different forms (yolo_pair): a %s needs pairs or plain fp16 throughout", i, L.type == L_ROUTE ? "route" : L.type == L_SHORTCUT ? "shortcut" : "layer");
-                // pairs are interleaved per 32-channel group: the general shortcut's channel boundary (minc) must fall between groups
-                // ... and a [reorg] scrambles channels across them: whole groups in, whole groups out (via_f32)
-                if (L.type == L_REORG && L.pair) { int h1, w1, c1; dims(L.in[0], h1, w1, c1); if (c1 % 32 || L.C % 32) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: a [reorg] of split-fp16 pairs needs a channel count that is a multiple of 32 (%d)", i, c1); }
-                if (L.type == L_SHORTCUT && L.general && L.pair) { int h1, w1, c1; dims(L.in[1], h1, w1, c1); if (L.C % 32 || c1 % 32) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: a [shortcut] with an activation or a `from` tensor of another shape, on split-fp16 pairs, needs channel counts that are multiples of 32 (%d and %d)", i, L.C, c1); }
-            }
-        }
+    Cursor k{c, 0, c->in_h, c->in_w, c->in_c};
+    for (k.i = 0; k.i < NL; ++k.i) {
+        const Section &s = secs[k.i + 1]; Layer &L = c->layers[k.i];
+        L.in = {k.i - 1};
+        if (!c->split() && (s.kv.count("yolo_pair") || net.kv.count("yolo_pair_input"))) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: yolo_pair is a key of split-fp16 networks (YOLO_FP16X2)", k.i);
+        const auto *e = std::find_if(std::begin(section_table), std::end(section_table), [&](const auto &t) { return s.type == t.name; });
+        if (e == std::end(section_table)) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: section [%s] is outside the inference hot path", k.i, s.type.c_str());
+        if (int r = e->parse(k, s, L)) return r;
+        L.H = k.H; L.W = k.W; L.C = k.C;
+        if (int r = inherit_form(k, L)) return r;
     }
-    for (int i = 0; i < NL; ++i) if (c->layers[i].head) c->layers[i].pair = false;        // heads are fp32
-    // classifier tail: an [avgpool] of an fp32 logit map stays fp32 and is pooled inside the [softmax] launch behind it; a [softmax] reads fp32
+    return YOLO_OK;
+}
+
+// ---- after the sections, in this order (each reads what the ones above it wrote) ----------------------------------------------
+// heads are fp32.  Reads head; writes pair
+static void heads_to_fp32(yolo_ctx *c) { for (Layer &L : c->layers) if (L.head) L.pair = false; }
+
+// classifier tail: an [avgpool] of an fp32 logit map stays fp32 and is pooled inside the [softmax] launch behind it; a [softmax] reads fp32.
+// Reads head (of the producer), tree, C; writes pair, store_dt, pool_fused
+static int classifier_tail(yolo_ctx *c)
+{
+    const int NL = (int)c->layers.size();
     for (int i = 0; i < NL; ++i) {
         Layer &L = c->layers[i];
         const int j = L.in.empty() ? -1 : L.in[0];
@@ -360,124 +487,189 @@ int build_plan(yolo_ctx *c, const std::vector<Section> &secs)
                 return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [softmax] must follow a [convolutional] / [connected] layer, directly or through one [avgpool] (fp32 logits)", i);
         }
     }
-    // the third kind is declared, [net] yolo_output=map: the output is the image-shaped tensor of the last layer that is not [cost]
+    return YOLO_OK;
+}
+
+// the kind of network: a detector (rows > 0), else a map where [net] yolo_output=map declares one (the image-shaped tensor of the last layer
+// that is not [cost]), else a classifier (that layer is a [softmax]).  Reads rows, cost, type; writes map_layer / cls_layer, head and pair along the map chain
+static int network_kind(yolo_ctx *c, const Section &net)
+{
     const std::string out_kind = opt_s(net, "yolo_output", "");
     if (!out_kind.empty() && out_kind != "map") return fail(c, YOLO_ERR_INVALID, "cfg: yolo_output=%s (the one value is `map`)", out_kind.c_str());
     if (!out_kind.empty() && c->rows) return fail(c, YOLO_ERR_INVALID, "cfg: yolo_output=map on a network with a [yolo] / [region] / [detection] head");
-    if (c->rows == 0) {          // no detection head: a classifier when the output layer (the last one that is not [cost]) is a [softmax]
-        int o = NL - 1;
-        while (o >= 0 && c->layers[o].cost) --o;
-        if (!out_kind.empty()) {
-            if (o < 0 || c->layers[o].type == L_SOFTMAX) return fail(c, YOLO_ERR_INVALID, "cfg: yolo_output=map on a network whose output layer is a [softmax] (a classifier)");
-            c->map_layer = o;
-            // the map is never rounded to 16 bits: the computing layer that reaches it directly or through [logistic] / [activation] layers writes
-            // fp32, and so do those (the `head` flag, as for logits)
-            int p = o;
-            while (p >= 0 && c->layers[p].type == L_ACTIVATE) { c->layers[p].head = true; c->layers[p].pair = false; p = c->layers[p].in[0]; }
-            if (p >= 0 && (c->layers[p].type == L_CONV || c->layers[p].type == L_DECONV || c->layers[p].type == L_GCONV)) { c->layers[p].head = true; c->layers[p].pair = false; }
-            else for (int q = o; q >= 0 && q != p; q = c->layers[q].in[0]) c->layers[q].head = false;      // (nothing computes in front of them: they keep their producer's type)
-        } else {
+    if (c->rows) return YOLO_OK;
+    int o = (int)c->layers.size() - 1;
+    while (o >= 0 && c->layers[o].cost) --o;
+    if (out_kind.empty()) {
         if (o < 0 || c->layers[o].type != L_SOFTMAX) return fail(c, YOLO_ERR_INVALID, "cfg has no [yolo] / [region] / [detection] head");
         c->cls_layer = o;
-        }
+        return YOLO_OK;
     }
+    if (o < 0 || c->layers[o].type == L_SOFTMAX) return fail(c, YOLO_ERR_INVALID, "cfg: yolo_output=map on a network whose output layer is a [softmax] (a classifier)");
+    c->map_layer = o;
+    // the map is never rounded to 16 bits: the computing layer that reaches it directly or through [logistic] / [activation] layers writes
+    // fp32, and so do those (the `head` flag, as for logits)
+    int p = o;
+    while (p >= 0 && c->layers[p].type == L_ACTIVATE) { c->layers[p].head = true; c->layers[p].pair = false; p = c->layers[p].in[0]; }
+    if (p >= 0 && computes(c->layers[p])) { c->layers[p].head = true; c->layers[p].pair = false; }
+    else for (int q = o; q >= 0 && q != p; q = c->layers[q].in[0]) c->layers[q].head = false;      // (nothing computes in front of them: they keep their producer's type)
+    return YOLO_OK;
+}
+
+// [net] normalisation keys and the row limit.  Reads rows; writes in_mul, in_add
+static int input_norm_and_row_limit(yolo_ctx *c, const Section &net)
+{
     c->in_mul = (float)atof(opt_s(net, "yolo_input_mul", "1").c_str()); c->in_add = (float)atof(opt_s(net, "yolo_input_add", "0").c_str());
     if (c->rows > 32768) return fail(c, YOLO_ERR_UNSUPPORTED, "more than 32768 candidates per image");
+    return YOLO_OK;
+}
 
-    // ---- use counts, shortcut fusion, concat placement ----
-    std::vector<int> uses(NL, 0);
-    for (int i = 0; i < NL; ++i) for (int j : c->layers[i].in) if (j >= 0) uses[j]++;
-    for (int i = 0; i < NL; ++i) {
+// how many layers read each layer's tensor (a [shortcut] reads two, a [route] all it names)
+static std::vector<int> count_uses(const yolo_ctx *c)
+{
+    std::vector<int> uses(c->layers.size(), 0);
+    for (const Layer &L : c->layers) for (int j : L.in) if (j >= 0) uses[j]++;
+    return uses;
+}
+
+// `shortcut` after a conv is folded into that conv's epilogue (V3/yolo_v3.py:54-60); the general form (k_shortcut) is never folded.
+// Reads general, post_act, head, store_dt, pair, uses; writes residual_from on the conv, noop on the [shortcut]
+static int fold_shortcuts(yolo_ctx *c, const std::vector<int> &uses)
+{
+    if (c->keep_layers) return YOLO_OK;
+    for (int i = 0; i < (int)c->layers.size(); ++i) {
         Layer &L = c->layers[i];
-        if (L.type == L_SHORTCUT && !L.general && !c->keep_layers) {          // the general form (k_shortcut) is never folded
-            Layer &P = c->layers[i - 1];
-            if (P.type == L_CONV && P.post_act == ACT_LINEAR && uses[i - 1] == 1 && !P.head && L.in[1] != i - 1 && (L.in[1] < 0 || c->layers[L.in[1]].store_dt == P.store_dt)) {
-                if (c->pair_of(L.in[1]) != P.pair) return fail(c, YOLO_ERR_INVALID, "layer %d: the conv in front of this shortcut and its other operand are stored in different forms (yolo_pair)", i);
-                P.residual_from = L.in[1]; L.noop = true;
-            }
+        if (L.type != L_SHORTCUT || L.general) continue;
+        Layer &P = c->layers[i - 1];
+        if (P.type == L_CONV && P.post_act == ACT_LINEAR && uses[i - 1] == 1 && !P.head && L.in[1] != i - 1 && (L.in[1] < 0 || c->layers[L.in[1]].store_dt == P.store_dt)) {
+            if (c->pair_of(L.in[1]) != P.pair) return fail(c, YOLO_ERR_INVALID, "layer %d: the conv in front of this shortcut and its other operand are stored in different forms (yolo_pair)", i);
+            P.residual_from = L.in[1]; L.noop = true;
         }
     }
-    // fused stem: conv0 (3x3/s1, 3 -> 32) read only by conv1 (3x3/s2, 32 -> 64), bf16, nothing asking for layer 0's tensor
-    // (the stem and halo kernels address their input with 32-bit buffer offsets: the whole-batch window must stay under 2 GiB)
-    // (an e4m3 network whose first layers are stored in a 16-bit type -- a mixed plan, yolo_store=bf16 -- runs them through the same fused
-    //  kernels: what counts is the type of the tensors a kernel touches, not the context's)
-    const bool ctx16 = c->half_like() || c->dtype == YOLO_FP8 || c->split();        // (a split-fp16 network: where the tensors a fused kernel touches are PLAIN fp16 -- mixed plans)
-    auto is16 = [](int dt) { return dt == DT_BF16 || dt == DT_F16; };
-    // a layer with a post-activation runs its own plain launch, then k_activate: it is no member of a fused launch, neither end of a 1x1 tail,
-    // and keeps the tiled kernel.  Every marking pass below asks this of each layer it marks
-    auto plain = [&](const Layer &X) { return X.post_act == ACT_LINEAR; };
-    // fused residual block (conv_block.hip): a 1x1 conv 128 -> 64 read only by the 3x3 conv 64 -> 128 that follows, whose folded shortcut
-    // source is the 1x1's own input, on a grid that is (nearly) whole 13 x 13 blocks: darknet-53's 104 x 104 stage at 416 x 416
-    if (ctx16 && !c->keep_layers && !getenv("YOLO_NO_RESBLOCK"))
-        for (int i = 1; i + 1 < NL; ++i) {
-            Layer &A = c->layers[i], &B = c->layers[i + 1];
-            if (A.type == L_CONV && B.type == L_CONV && plain(A) && plain(B) && !A.fc && !B.fc && !A.head && !B.head && uses[i] == 1 && B.in[0] == i && A.in[0] >= 0 &&
-                A.size == 1 && A.stride == 1 && A.pad == 0 && A.cin == 128 && A.filters == 64 && B.cin == 64 && B.filters == 128 && A.residual_from < -1 &&
-                B.size == 3 && B.stride == 1 && B.pad == 1 && B.residual_from == A.in[0] &&
-                ((long)((B.H + 12) / 13) * ((B.W + 12) / 13) * 169 * 100 <= (long)B.H * B.W * 115) && A.in_dt == B.in_dt && (A.in_dt == DT_BF16 || A.in_dt == DT_F16) && A.store_dt == A.in_dt && B.store_dt == A.in_dt &&
-                c->layers[A.in[0]].store_dt == A.in_dt && !A.pair && !B.pair && !c->pair_of(A.in[0])) { A.fused = B.fused = F_RESBLOCK; A.launcher = B.launcher = i + 1; }
-        }
-    if (ctx16 && !c->keep_layers && NL >= 2 && (double)c->max_batch * c->in_h * c->in_w * 8 * 2 < 2147483648.0) {
-        const Layer &A = c->layers[0], &B = c->layers[1];
-        if (A.type == L_CONV && B.type == L_CONV && plain(A) && plain(B) && uses[0] == 1 && B.in[0] == 0 && A.size == 3 && A.stride == 1 && A.pad == 1 && A.cin == 3 &&
-            A.filters == 32 && B.size == 3 && B.stride == 2 && B.pad == 1 && B.filters == 64 && !A.head && !B.head && B.residual_from < -1 &&
-            is16(A.in_dt) && A.store_dt == A.in_dt && B.in_dt == A.in_dt && B.store_dt == A.in_dt && !c->in_pair && !A.pair && !B.pair) {        // (layer 0 reads the staged image, which is kept in its operand type)
-            for (int k = 0; k < 2; ++k) { c->layers[k].fused = F_STEM; c->layers[k].launcher = 1; }
-            if (NL >= 3) {
-                const Layer &T = c->layers[2];
-                if (T.type == L_CONV && plain(T) && !T.fc && T.in[0] == 1 && T.size == 1 && T.stride == 1 && T.pad == 0 && T.filters == 32 && !T.head && T.residual_from < -1 &&
-                    T.in_dt == A.in_dt && T.store_dt == A.in_dt && !T.pair)
-                    { c->layers[2].fused = F_STEM; c->layers[2].launcher = 1; }
-            }
-        }
+    return YOLO_OK;
+}
+
+// ---- marking passes: each writes kernel / fused / launcher / tail_layer / fused_into of the layers it marks, nothing else ------------------
+// One name per phrase the passes repeat.  A predicate stands only where the text it replaced was exactly its body; where the passes differ
+// in what they ask (the stems ask no !fc, the pair stem asks no operand type, ...) they still differ.
+static inline bool is16(int dt) { return dt == DT_BF16 || dt == DT_F16; }
+// a layer with a post-activation runs its own plain launch, then k_activate: it is no member of a fused launch, neither end of a 1x1 tail,
+// and keeps the tiled kernel.  Every marking pass asks this of each layer it marks
+static inline bool plain(const Layer &X) { return X.post_act == ACT_LINEAR; }
+static inline bool plain_conv(const Layer &X) { return X.type == L_CONV && plain(X) && !X.head; }      // a dense conv ([connected] included) that is plain and no head
+static inline bool plain_conv_no_fc(const Layer &X) { return plain_conv(X) && !X.fc; }                  // ... and no [connected] layer
+static inline bool conv_is(const Layer &X, int size, int stride, int pad) { return X.size == size && X.stride == stride && X.pad == pad; }
+static inline bool hosts_shortcut(const Layer &X) { return X.residual_from >= -1; }                     // a [shortcut] was folded into it (-1: of the image)
+static inline bool plain16(const Layer &X) { return is16(X.in_dt) && X.store_dt == X.in_dt && !X.pair; }      // stored in its 16-bit operand type, not pairs
+static inline bool like16(const Layer &X, const Layer &A) { return X.in_dt == A.in_dt && X.store_dt == A.in_dt && !X.pair; }      // reads and stores A's operand type, not pairs
+// the context may hold 16-bit tensors at all: a 16-bit network, an e4m3 one with bf16 islands (yolo_store=bf16), a split-fp16 one with plain
+// fp16 islands (yolo_pair=0) -- what counts is the type of the tensors a kernel touches, not the context's
+static inline bool ctx16(const yolo_ctx *c) { return c->half_like() || c->dtype == YOLO_FP8 || c->split(); }
+
+// fused residual block (conv_block.hip): a 1x1 conv 128 -> 64 read only by the 3x3 conv 64 -> 128 that follows, whose folded shortcut
+// source is the 1x1's own input, on a grid that is (nearly) whole 13 x 13 blocks: darknet-53's 104 x 104 stage at 416 x 416.
+// Reads residual_from (fold_shortcuts)
+static void mark_resblocks(yolo_ctx *c, const std::vector<int> &uses)
+{
+    const int NL = (int)c->layers.size();
+    if (!(ctx16(c) && !c->keep_layers && !getenv("YOLO_NO_RESBLOCK"))) return;
+    for (int i = 1; i + 1 < NL; ++i) {
+        Layer &A = c->layers[i], &B = c->layers[i + 1];
+        if (plain_conv_no_fc(A) && plain_conv_no_fc(B) && uses[i] == 1 && B.in[0] == i && A.in[0] >= 0 &&
+            conv_is(A, 1, 1, 0) && A.cin == 128 && A.filters == 64 && B.cin == 64 && B.filters == 128 && !hosts_shortcut(A) &&
+            conv_is(B, 3, 1, 1) && B.residual_from == A.in[0] &&
+            ((long)((B.H + 12) / 13) * ((B.W + 12) / 13) * 169 * 100 <= (long)B.H * B.W * 115) && plain16(A) && like16(B, A) &&
+            c->layers[A.in[0]].store_dt == A.in_dt && !c->pair_of(A.in[0])) { A.fused = B.fused = F_RESBLOCK; A.launcher = B.launcher = i + 1; }
     }
-    // split-fp16: conv0 + conv1 on pairs in one launch (conv_stem_pair.hip) -- both tensors pairs, the image in its three blocks
-    if (c->split() && !c->keep_layers && NL >= 2 && c->in_pair && !getenv("YOLO_NO_PAIR_STEM")) {
-        const Layer &A = c->layers[0], &B = c->layers[1];
-        if (A.type == L_CONV && B.type == L_CONV && plain(A) && plain(B) && uses[0] == 1 && B.in[0] == 0 && A.size == 3 && A.stride == 1 && A.pad == 1 && A.cin == 3 && A.bn == B.bn &&
-            (A.filters == 32) && B.size == 3 && B.stride == 2 && B.pad == 1 && B.filters == 64 && !A.head && !B.head && A.residual_from < -1 && B.residual_from < -1 &&
-            A.pair && B.pair && c->in_h % 2 == 0 && c->in_w % 2 == 0 && A.kpad >= 216 && B.kpad == 576) {
-            for (int k = 0; k < 2; ++k) { c->layers[k].fused = F_PSTEM; c->layers[k].launcher = 1; }
-        }
+}
+
+// fused stem (conv_stem.hip): conv0 (3x3/s1, 3 -> 32) read only by conv1 (3x3/s2, 32 -> 64), 16-bit, nothing asking for layer 0's tensor;
+// optionally the 1x1 conv 64 -> 32 behind them.  (The stem and halo kernels address their input with 32-bit buffer offsets: the
+// whole-batch window must stay under 2 GiB.)  Layer 0 reads the staged image, which is kept in its operand type
+static void mark_stem(yolo_ctx *c, const std::vector<int> &uses)
+{
+    const int NL = (int)c->layers.size();
+    if (!(ctx16(c) && !c->keep_layers && NL >= 2 && (double)c->max_batch * c->in_h * c->in_w * 8 * 2 < 2147483648.0)) return;
+    const Layer &A = c->layers[0], &B = c->layers[1];
+    if (!(plain_conv(A) && plain_conv(B) && uses[0] == 1 && B.in[0] == 0 && conv_is(A, 3, 1, 1) && A.cin == 3 &&
+          A.filters == 32 && conv_is(B, 3, 2, 1) && B.filters == 64 && !hosts_shortcut(B) && plain16(A) && like16(B, A) && !c->in_pair)) return;
+    for (int m = 0; m < 2; ++m) { c->layers[m].fused = F_STEM; c->layers[m].launcher = 1; }
+    if (NL < 3) return;
+    const Layer &T = c->layers[2];
+    if (plain_conv_no_fc(T) && T.in[0] == 1 && conv_is(T, 1, 1, 0) && T.filters == 32 && !hosts_shortcut(T) && like16(T, A)) { c->layers[2].fused = F_STEM; c->layers[2].launcher = 1; }
+}
+
+// split-fp16: conv0 + conv1 on pairs in one launch (conv_stem_pair.hip) -- both tensors pairs, the image in its three blocks
+static void mark_pair_stem(yolo_ctx *c, const std::vector<int> &uses)
+{
+    if (!(c->split() && !c->keep_layers && c->layers.size() >= 2 && c->in_pair && !getenv("YOLO_NO_PAIR_STEM"))) return;
+    const Layer &A = c->layers[0], &B = c->layers[1];
+    if (plain_conv(A) && plain_conv(B) && uses[0] == 1 && B.in[0] == 0 && conv_is(A, 3, 1, 1) && A.cin == 3 && A.bn == B.bn &&
+        (A.filters == 32) && conv_is(B, 3, 2, 1) && B.filters == 64 && !hosts_shortcut(A) && !hosts_shortcut(B) &&
+        A.pair && B.pair && c->in_h % 2 == 0 && c->in_w % 2 == 0 && A.kpad >= 216 && B.kpad == 576)
+        for (int m = 0; m < 2; ++m) { c->layers[m].fused = F_PSTEM; c->layers[m].launcher = 1; }
+}
+
+// a conv's own fixed kernel: conv_halo_c32_c64 (3x3/s1, 32 -> 64, with or without a folded shortcut) and darknet-53's 64 -> 128
+// downsampling conv, window-staged with its filters in registers (conv_s2.hip).  Reads fused (both stems), residual_from
+static void mark_halo_and_s2(yolo_ctx *c)
+{
+    if (!(ctx16(c) && !getenv("YOLO_NO_HALO"))) return;
+    for (int i = 1; i < (int)c->layers.size(); ++i) {
+        Layer &L = c->layers[i];
+        if (!plain_conv(L) || L.fused != F_NONE || L.size != 3 || L.pad != 1 || !plain16(L) || c->pair_of(L.in[0])) continue;
+        if (L.stride == 1 && L.cin == 32 && L.filters == 64 && (L.residual_from < 0 || c->layers[L.residual_from].store_dt == L.in_dt)) L.kernel = K_HALO;
+        if (L.stride == 2 && L.cin == 64 && L.filters == 128 && !hosts_shortcut(L) && !getenv("YOLO_NO_S2")) L.kernel = K_S2;
     }
-    if (ctx16 && !getenv("YOLO_NO_HALO"))
-        for (int i = 1; i < NL; ++i) {
-            Layer &L = c->layers[i];
-            if (L.type != L_CONV || !plain(L) || L.head || L.fused != F_NONE || L.size != 3 || L.pad != 1 || !is16(L.in_dt) || L.store_dt != L.in_dt || L.pair || c->pair_of(L.in[0])) continue;
-            if (L.stride == 1 && L.cin == 32 && L.filters == 64 && (L.residual_from < 0 || c->layers[L.residual_from].store_dt == L.in_dt)) L.kernel = K_HALO;
-            // darknet-53's 64 -> 128 downsampling conv: window-staged, filters in registers (conv_s2.hip)
-            if (L.stride == 2 && L.cin == 64 && L.filters == 128 && L.residual_from < -1 && !getenv("YOLO_NO_S2")) L.kernel = K_S2;
-        }
-    // conv3 + shortcut + stride-2 conv in one launch (conv_c3s2.hip): a halo conv whose folded shortcut output (layer i + 1) is read by the s2 conv at i + 2 and by
-    // nobody else -- that tensor then never leaves LDS.  Both layers keep their own kernels: the fall-back where the fused launch's 32-bit windows do not hold the batch
-    if (ctx16 && !c->keep_layers && !getenv("YOLO_NO_C3S2"))
-        for (int i = 1; i + 2 < NL; ++i) {
-            Layer &A = c->layers[i], &S = c->layers[i + 1], &B = c->layers[i + 2];
-            if (A.kernel == K_HALO && B.kernel == K_S2 && A.residual_from >= 0 && S.type == L_SHORTCUT && S.noop && uses[i] == 1 && uses[i + 1] == 1 && B.in[0] == i + 1 && A.in[0] >= 0 &&
-                A.in_dt == B.in_dt && c->layers[A.residual_from].C == 64) { A.fused = B.fused = F_C3S2; A.launcher = B.launcher = i + 2; }
-        }
-    // 1x1 convs that can ride in their producer's epilogue: conv i (bf16, 128 or 256 output channels, optionally with its
-    // fused shortcut) read by a 1x1/s1 conv with half as many filters
-    if (ctx16 && !c->keep_layers) {
-        for (int i = 0; i + 1 < NL; ++i) {
-            Layer &P = c->layers[i];
-            if (P.type != L_CONV || !plain(P) || P.fc || P.head || fixed_kernel(P) || (P.filters != 128 && P.filters != 256)) continue;      // (fixed kernels host no tail: run_conv would skip the 1x1)
-            if (c->split() && (P.pair || c->pair_of(P.in[0]))) continue;       // (split-fp16 networks: the tail rides on plain fp16 layers only)
-            int o = i;
-            if (P.residual_from >= -1) o = i + 1;            // its shortcut was folded into it: consumers read layer i+1
-            const int j = o + 1;
-            if (j >= NL) continue;
-            Layer &T = c->layers[j];
-            if (T.type == L_CONV && plain(T) && !T.fc && T.in[0] == o && T.size == 1 && T.stride == 1 && T.pad == 0 && T.filters * 2 == P.filters && !T.head &&
-                T.residual_from < -1 && issues_launch(c, j) && T.in_dt == P.in_dt && !T.pair) { P.tail_layer = j; T.fused_into = i; }      // (same operand type: the tail runs on the producer's MFMA)
-            // round 5: a detection head (1x1, <= 256 filters, fp32 out, linear) as the tail of the 256-channel 3x3 in front of it when nobody else
-            // reads that conv (darknet-53's 52 x 52 head): the head tensor is formed from the tile in LDS, bit-identical to the stand-alone launch
-            else if (T.type == L_CONV && plain(T) && !T.fc && T.head && T.in[0] == o && uses[o] == 1 && T.size == 1 && T.stride == 1 && T.pad == 0 && P.filters == 256 && T.filters <= 256 &&
-                     P.size == 3 && P.residual_from < -1 && T.act == ACT_LINEAR && T.in_dt == P.in_dt && (T.in_dt == DT_BF16 || T.in_dt == DT_F16) && j + 1 < NL && c->layers[j + 1].type == L_YOLO) { P.tail_layer = j; T.fused_into = i; }
-        }
+}
+
+// conv3 + shortcut + stride-2 conv in one launch (conv_c3s2.hip): a halo conv whose folded shortcut output (layer i + 1) is read by the s2 conv at i + 2 and by
+// nobody else -- that tensor then never leaves LDS.  Both layers keep their own kernels: the fall-back where the fused launch's 32-bit windows do not hold the batch.
+// Reads kernel (mark_halo_and_s2), residual_from and noop (fold_shortcuts)
+static void mark_c3s2(yolo_ctx *c, const std::vector<int> &uses)
+{
+    const int NL = (int)c->layers.size();
+    if (!(ctx16(c) && !c->keep_layers && !getenv("YOLO_NO_C3S2"))) return;
+    for (int i = 1; i + 2 < NL; ++i) {
+        Layer &A = c->layers[i], &S = c->layers[i + 1], &B = c->layers[i + 2];
+        if (A.kernel == K_HALO && B.kernel == K_S2 && A.residual_from >= 0 && S.type == L_SHORTCUT && S.noop && uses[i] == 1 && uses[i + 1] == 1 && B.in[0] == i + 1 && A.in[0] >= 0 &&
+            A.in_dt == B.in_dt && c->layers[A.residual_from].C == 64) { A.fused = B.fused = F_C3S2; A.launcher = B.launcher = i + 2; }
     }
-    // [logistic] / [activation]: one k_activate launch over the producer's own tensor where this layer is that tensor's only reader, nobody asked
-    // to keep every layer, and neither tensor is a window of a concatenation; else a tensor of its own, copied first
+}
+
+// 1x1 convs that can ride in their producer's epilogue: conv i (16-bit, 128 or 256 output channels, optionally with its fused shortcut) read
+// by a 1x1/s1 conv with half as many filters.  Reads kernel / fused / launcher of every layer (fixed_kernel, issues_launch), residual_from
+static void mark_tails(yolo_ctx *c, const std::vector<int> &uses)
+{
+    const int NL = (int)c->layers.size();
+    if (!(ctx16(c) && !c->keep_layers)) return;
+    for (int i = 0; i + 1 < NL; ++i) {
+        Layer &P = c->layers[i];
+        if (!plain_conv_no_fc(P) || fixed_kernel(P) || (P.filters != 128 && P.filters != 256)) continue;      // (fixed kernels host no tail: run_conv would skip the 1x1)
+        if (c->split() && (P.pair || c->pair_of(P.in[0]))) continue;       // (split-fp16 networks: the tail rides on plain fp16 layers only)
+        const int o = hosts_shortcut(P) ? i + 1 : i;            // its shortcut was folded into it: consumers read layer i+1
+        const int j = o + 1;
+        if (j >= NL) continue;
+        Layer &T = c->layers[j];
+        if (plain_conv_no_fc(T) && T.in[0] == o && conv_is(T, 1, 1, 0) && T.filters * 2 == P.filters &&
+            !hosts_shortcut(T) && issues_launch(c, j) && T.in_dt == P.in_dt && !T.pair) { P.tail_layer = j; T.fused_into = i; }      // (same operand type: the tail runs on the producer's MFMA)
+        // a detection head (1x1, <= 256 filters, fp32 out, linear) as the tail of the 256-channel 3x3 in front of it when nobody else
+        // reads that conv (darknet-53's 52 x 52 head): the head tensor is formed from the tile in LDS, bit-identical to the stand-alone launch
+        else if (T.type == L_CONV && plain(T) && !T.fc && T.head && T.in[0] == o && uses[o] == 1 && conv_is(T, 1, 1, 0) && P.filters == 256 && T.filters <= 256 &&
+                 P.size == 3 && !hosts_shortcut(P) && T.act == ACT_LINEAR && T.in_dt == P.in_dt && is16(T.in_dt) && j + 1 < NL && c->layers[j + 1].type == L_YOLO) { P.tail_layer = j; T.fused_into = i; }
+    }
+}
+
+// ---- storage steps ----------------------------------------------------------------------------------------------------------
+// elements per pixel of a layer's own tensor (a head's fp32 tensor and a [softmax]'s dense rows have their own widths)
+static int storage_width(const Layer &L) { return L.pair ? pair_width(L.C) : roundup(L.C, gran_of(L.store_dt)); }
+
+// [logistic] / [activation]: one k_activate launch over the producer's own tensor where this layer is that tensor's only reader, nobody asked
+// to keep every layer, and neither tensor is a window of a concatenation; else a tensor of its own, copied first.
+// Reads head (network_kind), fused / launcher (never_stored), uses; writes inplace
+static int decide_inplace(yolo_ctx *c, const std::vector<int> &uses)
+{
+    const int NL = (int)c->layers.size();
     for (int i = 0; i < NL; ++i) {
         Layer &L = c->layers[i];
         if (L.type != L_ACTIVATE) continue;
@@ -487,26 +679,36 @@ int build_plan(yolo_ctx *c, const std::vector<Section> &secs)
         if (j >= 0 && c->layers[j].head != L.head) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [logistic] / [activation] of a detection head's fp32 tensor", i);
         if (j < 0 || c->keep_layers || routed || uses[j] != 1) continue;
         const Layer &P = c->layers[j];
-        L.inplace = (P.type == L_CONV || P.type == L_DECONV || P.type == L_GCONV || P.type == L_LOCAL || P.type == L_SHORTCUT || P.type == L_L2NORM || P.type == L_UPSAMPLE || P.type == L_MAXPOOL ||
+        L.inplace = (computes(P) || P.type == L_LOCAL || P.type == L_SHORTCUT || P.type == L_L2NORM || P.type == L_UPSAMPLE || P.type == L_MAXPOOL ||
                      P.type == L_ACTIVATE) && !never_stored(P, j);
     }
-    // storage assignment: st_of[i] = storage holding layer i's output
-    std::vector<int> place_route(NL, -1), place_off(NL, 0);
+    return YOLO_OK;
+}
+
+// route/concat is never executed where its sources can write straight into a channel window of the concatenation: route[j] = the [route]
+// layer j writes into (-1: none), off[j] = at which element offset
+struct Placement { std::vector<int> route, off; };
+
+// Reads store_dt, pair, head, cost, noop (fold_shortcuts); writes `at`, copy_inputs / copy_offsets of the routes whose sources must be copied
+static int place_route_sources(yolo_ctx *c, Placement &at)
+{
+    const int NL = (int)c->layers.size();
+    at.route.assign(NL, -1); at.off.assign(NL, 0);
     for (int i = 0; i < NL; ++i) {
         Layer &L = c->layers[i];
         if (L.type != L_ROUTE || L.in.size() < 2) continue;
         int off = 0;
         for (int j : L.in) {
             int cj = j < 0 ? c->in_c : c->layers[j].C;
-            // (pair tensors, round 6: interleaved per 32-channel group, so a source of whole groups at a whole-group offset is a window of the
+            // (pair tensors: interleaved per 32-channel group, so a source of whole groups at a whole-group offset is a window of the
             //  concatenation like any other tensor; element offset 2 x the channel offset)
             const int gran = L.pair ? 32 : gran_of(L.store_dt);
-            bool ok = j >= 0 && place_route[j] < 0 && c->layers[j].type != L_ROUTE && !c->layers[j].head &&
-                      c->layers[j].type != L_YOLO && c->layers[j].type != L_REGION && c->layers[j].type != L_DETECT && (cj % gran == 0) && (off % gran == 0) &&
+            bool ok = j >= 0 && at.route[j] < 0 && c->layers[j].type != L_ROUTE && !c->layers[j].head &&
+                      !is_head_layer(c->layers[j]) && (cj % gran == 0) && (off % gran == 0) &&
                       c->layers[j].type != L_SOFTMAX && !c->layers[j].cost && !(c->layers[j].type == L_AVGPOOL && c->layers[j].store_dt != L.store_dt);
             // a fused-away conv's real producer is the conv; the shortcut layer itself is what gets placed
             if (ok && c->layers[j].type == L_CONV && j + 1 < NL && c->layers[j + 1].noop && c->layers[j + 1].type == L_SHORTCUT) ok = false;
-            if (ok) { place_route[j] = i; place_off[j] = L.pair ? 2 * off : off; }
+            if (ok) { at.route[j] = i; at.off[j] = L.pair ? 2 * off : off; }
             else {
                 // a copied source (run_layer): granule by granule, or element by element at a channel offset that is no multiple of 8; what the
                 // copy kernels do not serve is refused here, not at the first forward
@@ -519,54 +721,72 @@ int build_plan(yolo_ctx *c, const std::vector<Section> &secs)
             off += cj;
         }
     }
-    auto new_storage = [&](int stride, int dt, size_t pixels, bool persistent) {
-        Storage s; s.stride = stride; s.dt = dt; s.bytes = pixels * (size_t)stride * dt_size(dt); s.persistent = persistent;
-        c->storages.push_back(s); return (int)c->storages.size() - 1;
-    };
-    // routes first (so producers can point into them)
+    return YOLO_OK;
+}
+
+static int new_storage(yolo_ctx *c, int stride, int dt, size_t pixels, bool persistent)
+{
+    Storage s; s.stride = stride; s.dt = dt; s.bytes = pixels * (size_t)stride * dt_size(dt); s.persistent = persistent;
+    c->storages.push_back(s); return (int)c->storages.size() - 1;
+}
+
+// every layer gets a view: a storage of its own, a window of a concatenation, or an alias of its producer's.  Concatenations first, so
+// producers can point into them.  Reads `at`, inplace, head, fused / launcher; writes storages, storage / ch_off, noop
+static int create_storages(yolo_ctx *c, const Placement &at)
+{
+    const int NL = (int)c->layers.size();
+    const size_t n = (size_t)c->max_batch;
+    for (Layer &L : c->layers)
+        if (L.type == L_ROUTE && L.in.size() >= 2) { L.storage = new_storage(c, storage_width(L), L.store_dt, n * L.H * L.W, c->keep_layers); L.ch_off = 0; }
     for (int i = 0; i < NL; ++i) {
         Layer &L = c->layers[i];
-        if (L.type == L_ROUTE && L.in.size() >= 2) {
-            L.storage = new_storage(L.pair ? pair_width(L.C) : roundup(L.C, gran_of(L.store_dt)), L.store_dt, (size_t)c->max_batch * L.H * L.W, c->keep_layers); L.ch_off = 0;
-        }
-    }
-    for (int i = 0; i < NL; ++i) {
-        Layer &L = c->layers[i];
-        if (L.type == L_YOLO || L.type == L_REGION || L.type == L_DETECT) { L.noop = true; L.storage = c->layers[i - 1].storage; L.ch_off = c->layers[i - 1].ch_off; continue; }
+        if (is_head_layer(L)) { L.noop = true; L.storage = c->layers[i - 1].storage; L.ch_off = c->layers[i - 1].ch_off; continue; }
         if (L.type == L_ROUTE && L.in.size() == 1) { L.noop = true; int j = L.in[0]; if (j < 0) return fail(c, YOLO_ERR_UNSUPPORTED, "route to network input"); L.storage = c->layers[j].storage; L.ch_off = c->layers[j].ch_off; continue; }
         if (L.type == L_ROUTE) continue;
         if (never_stored(L, i) && !fused_may_fall_back(L)) { L.noop = true; continue; }               // lives in LDS only; a group that may fall back keeps its members' storage
-        if (L.type == L_SOFTMAX) { L.storage = new_storage(L.C, DT_F32, (size_t)c->max_batch, true); continue; }      // dense [n][C] probabilities
+        if (L.type == L_SOFTMAX) { L.storage = new_storage(c, L.C, DT_F32, n, true); continue; }      // dense [n][C] probabilities
         if (L.type == L_ACTIVATE && L.inplace) { L.storage = c->layers[L.in[0]].storage; L.ch_off = c->layers[L.in[0]].ch_off; continue; }
-        if (place_route[i] >= 0) { L.storage = c->layers[place_route[i]].storage; L.ch_off = place_off[i]; }
-        else if (L.head) L.storage = new_storage(roundup(L.C, 4), DT_F32, (size_t)c->max_batch * L.H * L.W, true);
-        else L.storage = new_storage(L.pair ? pair_width(L.C) : roundup(L.C, gran_of(L.store_dt)), L.store_dt, (size_t)c->max_batch * L.H * L.W, c->keep_layers);
+        if (at.route[i] >= 0) { L.storage = c->layers[at.route[i]].storage; L.ch_off = at.off[i]; }
+        else if (L.head) L.storage = new_storage(c, roundup(L.C, 4), DT_F32, n * L.H * L.W, true);
+        else L.storage = new_storage(c, storage_width(L), L.store_dt, n * L.H * L.W, c->keep_layers);
     }
-    // a conv whose shortcut was fused writes the shortcut layer's tensor
-    for (int i = 0; i + 1 < NL; ++i) {
+    return YOLO_OK;
+}
+
+// a conv whose shortcut was folded writes the shortcut layer's tensor: its own storage slot is unused (unless it is a window of a
+// concatenation).  Reads residual_from, `at`; writes storage / ch_off of the conv, bytes of its former storage
+static void redirect_folded_convs(yolo_ctx *c, const Placement &at)
+{
+    for (int i = 0; i + 1 < (int)c->layers.size(); ++i) {
         Layer &L = c->layers[i];
-        if (L.type == L_CONV && L.residual_from >= -1) {
-            // its own storage slot is unused: redirect to the shortcut's
-            Storage &mine = c->storages[L.storage];
-            if (place_route[i] < 0) mine.bytes = 0;
-            L.storage = c->layers[i + 1].storage; L.ch_off = c->layers[i + 1].ch_off;
-        }
+        if (L.type != L_CONV || !hosts_shortcut(L)) continue;
+        if (at.route[i] < 0) c->storages[L.storage].bytes = 0;
+        L.storage = c->layers[i + 1].storage; L.ch_off = c->layers[i + 1].ch_off;
     }
-    // liveness: def = first writer, last = last reader of any view
-    for (int i = 0; i < NL; ++i) {
+}
+
+// liveness: def = first writer, last = last reader of any view of a storage.  Reads storage, noop, fused_into, residual_from, fused / launcher
+static void compute_liveness(yolo_ctx *c)
+{
+    auto read_at = [&](int j, int when) { if (j >= 0 && c->layers[j].storage >= 0) { Storage &s = c->storages[c->layers[j].storage]; s.last = std::max(s.last, when); } };
+    for (int i = 0; i < (int)c->layers.size(); ++i) {
         Layer &L = c->layers[i];
         if (L.storage < 0) continue;
         if (!L.noop) { Storage &s = c->storages[L.storage]; s.def = std::min(s.def, L.fused_into >= 0 ? L.fused_into : i); s.last = std::max(s.last, i); }      // (whichever way tail_on is toggled later)
-        for (int j : L.in) if (j >= 0 && c->layers[j].storage >= 0) { Storage &s = c->storages[c->layers[j].storage]; s.last = std::max(s.last, i); }
+        for (int j : L.in) read_at(j, i);
         if (L.type == L_CONV && L.residual_from >= 0) { Storage &s = c->storages[c->layers[L.residual_from].storage]; s.last = std::max(s.last, i); }
         if (never_stored(L, i))           // its group's launch reads what this layer reads: its input and its shortcut source live until the launcher
-            for (int j : {L.in[0], L.residual_from}) if (j >= 0 && c->layers[j].storage >= 0) { Storage &s = c->storages[c->layers[j].storage]; s.last = std::max(s.last, L.launcher); }
+            for (int j : {L.in[0], L.residual_from}) read_at(j, L.launcher);
     }
-    // greedy pooled assignment
+}
+
+// greedy pooled assignment in layer order: a storage takes the largest free buffer when it is first written, gives it back after its last
+// reader; persistent ones get a buffer of their own.  Reads def / last / bytes / persistent; writes phys, phys_bytes
+static void assign_pool(yolo_ctx *c)
+{
     std::vector<int> free_list;
-    for (int i = 0; i < NL; ++i) {
-        for (size_t k = 0; k < c->storages.size(); ++k) {
-            Storage &s = c->storages[k];
+    for (int i = 0; i < (int)c->layers.size(); ++i) {
+        for (Storage &s : c->storages) {
             if (s.def != i || s.bytes == 0) continue;
             int pick = -1;
             if (!s.persistent) {
@@ -576,11 +796,50 @@ int build_plan(yolo_ctx *c, const std::vector<Section> &secs)
             if (pick >= 0) { s.phys = free_list[pick]; free_list.erase(free_list.begin() + pick); c->phys_bytes[s.phys] = std::max(c->phys_bytes[s.phys], s.bytes); }
             else { s.phys = (int)c->phys_bytes.size(); c->phys_bytes.push_back(s.bytes); }
         }
-        for (size_t k = 0; k < c->storages.size(); ++k) {
-            Storage &s = c->storages[k];
+        for (Storage &s : c->storages)
             if (s.last == i && s.phys >= 0 && !s.persistent) free_list.push_back(s.phys);
-        }
     }
+}
+
+// The planner: the order below is the order the steps depend on each other in (see the headers of the steps for what each reads).
+int build_plan(yolo_ctx *c, const std::vector<Section> &secs)
+{
+    const Section &net = secs[0];
+    if (int r = parse_sections(c, secs)) return r;
+    heads_to_fp32(c);
+    if (int r = classifier_tail(c)) return r;
+    if (int r = network_kind(c, net)) return r;
+    if (int r = input_norm_and_row_limit(c, net)) return r;
+    const std::vector<int> uses = count_uses(c);
+    if (int r = fold_shortcuts(c, uses)) return r;
+    // Marking passes.  What their order must respect:
+    //   * all of them run after fold_shortcuts: they test residual_from (and mark_c3s2 the [shortcut]'s noop), and after network_kind, which sets
+    //     `head` along a map chain;
+    //   * mark_resblocks, mark_stem and mark_pair_stem do not read each other's marks.  No layer can be claimed twice: a resblock starts at
+    //     layer >= 1 with a 1x1 conv of 128 channels, the stems own layers 0 and 1 (3x3) and a 1x1 of 64 -> 32 at layer 2; the stem needs
+    //     !in_pair and the pair stem in_pair;
+    //   * mark_halo_and_s2 runs after all three: it leaves the members of a fused launch alone (`fused != F_NONE`);
+    //   * mark_c3s2 runs after mark_halo_and_s2: it joins layers by their `kernel` (K_HALO at i, K_S2 at i + 2).  It does not ask `fused`: it
+    //     can only meet layers mark_halo_and_s2 marked, which were in no fused launch;
+    //   * mark_tails runs last: fixed_kernel() of the host asks `kernel` and `fused`, issues_launch() of the 1x1 asks `fused` / `launcher`
+    //     (tail_on is false throughout planning, so rides_as_tail() is);
+    //   * decide_inplace and create_storages run after every marking pass: never_stored() asks `fused` / `launcher`; compute_liveness reads
+    //     fused_into, so it runs after mark_tails.
+    mark_resblocks(c, uses);
+    mark_stem(c, uses);
+    mark_pair_stem(c, uses);
+    mark_halo_and_s2(c);
+    mark_c3s2(c, uses);
+    mark_tails(c, uses);
+    // Storage: in-place activations before placement and creation (an in-place layer aliases its producer); placement before creation
+    // (producers point into the concatenations); the redirect after creation; liveness over the final views; then the pool.
+    if (int r = decide_inplace(c, uses)) return r;
+    Placement at;
+    if (int r = place_route_sources(c, at)) return r;
+    if (int r = create_storages(c, at)) return r;
+    redirect_folded_convs(c, at);
+    compute_liveness(c);
+    assign_pool(c);
     return YOLO_OK;
 }
 
@@ -695,3 +954,92 @@ int allocate(yolo_ctx *c)
 }
 
 }  // namespace yolo_impl
+
+// ---- the planner without a device: yolo_plan_check, yolo_plan_table, yolo_plan_dump -----------------------------------------------
+// cfg text -> sections and plan in a context that never sees a device; the message of a refusal is left in c.err
+static int plan_text(yolo_ctx &c, std::vector<Section> &secs, const char *cfg_text, int dtype, int max_batch, int keep_layers)
+{
+    c.dtype = dtype; c.max_batch = max_batch; c.keep_layers = keep_layers;
+    std::string perr;
+    if (max_batch < 1) { c.err = "max_batch < 1"; return YOLO_ERR_INVALID; }
+    if (!parse_cfg(cfg_text, secs, perr)) { c.err = perr; return YOLO_ERR_INVALID; }
+    return build_plan(&c, secs);
+}
+// ... and the text and the message handed back: the text must fit `out`
+static int plan_text_out(yolo_ctx &c, int r, const std::string &text, const char *who, const char *what, char *out, size_t out_len, char *err, size_t err_len)
+{
+    if (r == YOLO_OK && (!out || text.size() + 1 > out_len)) r = fail(&c, YOLO_ERR_INVALID, "%s: the %s needs %zu bytes", who, what, text.size() + 1);
+    if (out && out_len) snprintf(out, out_len, "%s", r ? "" : text.c_str());
+    if (err && err_len) snprintf(err, err_len, "%s", r ? c.err.c_str() : "");
+    return r;
+}
+
+extern "C" {
+
+int yolo_plan_check(const char *cfg_text, int dtype, char *err, size_t err_len)
+{
+    yolo_ctx c; std::vector<Section> secs;
+    const int r = plan_text(c, secs, cfg_text, dtype, 1, 0);
+    if (err && err_len) snprintf(err, err_len, "%s", r ? c.err.c_str() : "");
+    return r;
+}
+
+int yolo_plan_table(const char *cfg_text, int dtype, int max_batch, int keep_layers, char *out, size_t out_len, char *err, size_t err_len)
+{
+    yolo_ctx c; std::vector<Section> secs; std::string text;
+    const int r = plan_text(c, secs, cfg_text, dtype, max_batch, keep_layers);
+    static const char *const kernels[] = {"tiled", "halo", "s2"}, *const kinds[] = {"none", "stem", "pair-stem", "resblock", "c3s2"};      // ConvKernel, FuseKind
+    char line[256];
+    for (size_t i = 0; r == YOLO_OK && i < c.layers.size(); ++i) {
+        const Layer &L = c.layers[i];
+        const Storage *st = L.storage >= 0 ? &c.storages[L.storage] : nullptr;
+        snprintf(line, sizeof line, "%zu %s kernel=%s fused=%s launcher=%d residual_from=%d tail_layer=%d storage=%d phys=%d def=%d last=%d\n", i, secs[i + 1].type.c_str(),
+                 L.type == L_CONV ? kernels[L.kernel] : "-", kinds[L.fused], L.launcher, L.residual_from, L.tail_layer, L.storage, st ? st->phys : -1, st ? st->def : -1, st ? st->last : -1);
+        text += line;
+    }
+    if (r == YOLO_OK) {
+        size_t total = 0; for (size_t b : c.phys_bytes) total += b;
+        snprintf(line, sizeof line, "buffers %zu bytes %zu\n", c.phys_bytes.size(), total);
+        text += line;
+        if (c.in_h != c.in_w) {          // a rectangular network only (the table of a square one is pinned byte for byte): its input, every head's grid, the candidate rows per image
+            snprintf(line, sizeof line, "input %dx%d", c.in_h, c.in_w); text += line;
+            for (size_t i = 0; i < c.layers.size(); ++i) { const Layer &L = c.layers[i]; if (is_head_layer(L)) { snprintf(line, sizeof line, " head %zu grid %dx%d anchors %d", i, L.H, L.W, L.na); text += line; } }
+            snprintf(line, sizeof line, " rows %d\n", c.rows); text += line;
+        }
+    }
+    return plan_text_out(c, r, text, "yolo_plan_table", "table", out, out_len, err, err_len);
+}
+
+int yolo_plan_dump(const char *cfg_text, int dtype, int max_batch, int keep_layers, char *out, size_t out_len, char *err, size_t err_len)
+{
+    yolo_ctx c; std::vector<Section> secs; std::string text;
+    int r = plan_text(c, secs, cfg_text, dtype, max_batch, keep_layers);
+    char buf[512];
+    auto put = [&](const char *fmt, ...) { va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap); text += buf; };
+    auto ints = [&](const char *name, const std::vector<int> &v) { put(" %s=[", name); for (size_t k = 0; k < v.size(); ++k) put(k ? ",%d" : "%d", v[k]); text += "]"; };
+    for (size_t i = 0; r == YOLO_OK && i < c.layers.size(); ++i) {
+        const Layer &L = c.layers[i];
+        put("layer %zu %s type=%d H=%d W=%d C=%d", i, secs[i + 1].type.c_str(), (int)L.type, L.H, L.W, L.C); ints("in", L.in);
+        put(" filters=%d size=%d stride=%d pad=%d bn=%d act=%d post_act=%d general=%d", L.filters, L.size, L.stride, L.pad, L.bn, L.act, L.post_act, (int)L.general);
+        put(" cin=%d cin_pad=%d kpad=%d cout_pad=%d in_dt=%d store_dt=%d pair=%d", L.cin, L.cin_pad, L.kpad, L.cout_pad, L.in_dt, L.store_dt, (int)L.pair);
+        put(" residual_from=%d head=%d kernel=%d fused=%d launcher=%d", L.residual_from, (int)L.head, L.kernel, L.fused, L.launcher);
+        put(" fc=%d fc_h=%d fc_w=%d fc_c=%d s2d7=%d side=%d sqr=%d", (int)L.fc, L.fc_h, L.fc_w, L.fc_c, (int)L.s2d7, L.side, L.sqr);
+        put(" tail_layer=%d fused_into=%d noop=%d", L.tail_layer, L.fused_into, (int)L.noop); ints("copy_inputs", L.copy_inputs); ints("copy_offsets", L.copy_offsets);
+        put(" psize=%d pstride=%d ppad=%d up_scale=%a inplace=%d", L.psize, L.pstride, L.ppad, (double)L.up_scale, (int)L.inplace);
+        put(" na=%d classes=%d row_off=%d anchors=[", L.na, L.classes, L.row_off); for (size_t k = 0; k < L.anchors.size(); ++k) put(k ? ",%a" : "%a", (double)L.anchors[k]);
+        put("] groups=%d temperature=%a pool_fused=%d cost=%d tree=%d storage=%d ch_off=%d\n", L.groups, (double)L.temperature, (int)L.pool_fused, (int)L.cost, L.tree, L.storage, L.ch_off);
+    }
+    for (size_t k = 0; r == YOLO_OK && k < c.storages.size(); ++k) {
+        const Storage &s = c.storages[k];
+        put("storage %zu def=%d last=%d bytes=%zu phys=%d stride=%d dt=%d persistent=%d\n", k, s.def, s.last, s.bytes, s.phys, s.stride, s.dt, (int)s.persistent);
+    }
+    if (r == YOLO_OK) {
+        put("context in_h=%d in_w=%d in_c=%d in_pair=%d rows=%d attrs=%d cls_layer=%d map_layer=%d tree_head=%d in_mul=%a in_add=%a weights_count=%zu conv_flops=%a phys_bytes=[",
+            c.in_h, c.in_w, c.in_c, (int)c.in_pair, c.rows, c.attrs, c.cls_layer, c.map_layer, c.tree_head, (double)c.in_mul, (double)c.in_add, c.weights_count, c.conv_flops);
+        for (size_t k = 0; k < c.phys_bytes.size(); ++k) put(k ? ",%zu" : "%zu", c.phys_bytes[k]);
+        text += "]\n";
+    }
+    return plan_text_out(c, r, text, "yolo_plan_dump", "dump", out, out_len, err, err_len);
+}
+
+}  // extern "C"

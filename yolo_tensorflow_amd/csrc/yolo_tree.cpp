@@ -165,48 +165,4 @@ int yolo_tree_geometry(const yolo_ctx *c, int32_t *nodes, int32_t *groups, int32
     return YOLO_OK;
 }
 
-int yolo_plan_check(const char *cfg_text, int dtype, char *err, size_t err_len)
-{
-    yolo_ctx c; c.dtype = dtype; c.max_batch = 1;
-    std::vector<Section> secs; std::string perr;
-    int r = YOLO_OK;
-    if (!parse_cfg(cfg_text, secs, perr)) { c.err = perr; r = YOLO_ERR_INVALID; }
-    else r = build_plan(&c, secs);
-    if (err && err_len) snprintf(err, err_len, "%s", r ? c.err.c_str() : "");
-    return r;
-}
-
-int yolo_plan_table(const char *cfg_text, int dtype, int max_batch, int keep_layers, char *out, size_t out_len, char *err, size_t err_len)
-{
-    yolo_ctx c; c.dtype = dtype; c.max_batch = max_batch; c.keep_layers = keep_layers;
-    std::vector<Section> secs; std::string perr, text;
-    int r = YOLO_OK;
-    if (max_batch < 1) { c.err = "max_batch < 1"; r = YOLO_ERR_INVALID; }
-    else if (!parse_cfg(cfg_text, secs, perr)) { c.err = perr; r = YOLO_ERR_INVALID; }
-    else r = build_plan(&c, secs);
-    static const char *const kernels[] = {"tiled", "halo", "s2"}, *const kinds[] = {"none", "stem", "pair-stem", "resblock", "c3s2"};      // ConvKernel, FuseKind
-    char line[256];
-    for (size_t i = 0; r == YOLO_OK && i < c.layers.size(); ++i) {
-        const Layer &L = c.layers[i];
-        const Storage *st = L.storage >= 0 ? &c.storages[L.storage] : nullptr;
-        snprintf(line, sizeof line, "%zu %s kernel=%s fused=%s launcher=%d residual_from=%d tail_layer=%d storage=%d phys=%d def=%d last=%d\n", i, secs[i + 1].type.c_str(),
-                 L.type == L_CONV ? kernels[L.kernel] : "-", kinds[L.fused], L.launcher, L.residual_from, L.tail_layer, L.storage, st ? st->phys : -1, st ? st->def : -1, st ? st->last : -1);
-        text += line;
-    }
-    if (r == YOLO_OK) {
-        size_t total = 0; for (size_t b : c.phys_bytes) total += b;
-        snprintf(line, sizeof line, "buffers %zu bytes %zu\n", c.phys_bytes.size(), total);
-        text += line;
-        if (c.in_h != c.in_w) {          // a rectangular network only (the table of a square one is pinned byte for byte): its input, every head's grid, the candidate rows per image
-            snprintf(line, sizeof line, "input %dx%d", c.in_h, c.in_w); text += line;
-            for (size_t i = 0; i < c.layers.size(); ++i) { const Layer &L = c.layers[i]; if (L.type == L_YOLO || L.type == L_REGION || L.type == L_DETECT) { snprintf(line, sizeof line, " head %zu grid %dx%d anchors %d", i, L.H, L.W, L.na); text += line; } }
-            snprintf(line, sizeof line, " rows %d\n", c.rows); text += line;
-        }
-        if (!out || text.size() + 1 > out_len) r = fail(&c, YOLO_ERR_INVALID, "yolo_plan_table: the table needs %zu bytes", text.size() + 1);
-    }
-    if (out && out_len) snprintf(out, out_len, "%s", r ? "" : text.c_str());
-    if (err && err_len) snprintf(err, err_len, "%s", r ? c.err.c_str() : "");
-    return r;
-}
-
 }  // extern "C"

@@ -44,7 +44,7 @@ EXPORTS = [
     "yolo_postprocess_rows", "yolo_op_postprocess_rows", "yolo_last_layer_output_batch", "yolo_head_raw", "yolo_calibrate", "yolo_calibrate_copy", "yolo_op_resize_cv2",
     "yolo_forward_images_u8", "yolo_detect_images_u8", "yolo_detect_images_graph", "yolo_fit_unit_value", "yolo_darknet_boxes_at",
     "yolo_num_classes", "yolo_classify", "yolo_classify_images_u8", "yolo_op_avgpool", "yolo_op_softmax",
-    "yolo_set_hier_thresh", "yolo_set_hierarchy_mode", "yolo_darknet_boxes_map", "yolo_tree_geometry", "yolo_tree_read", "yolo_plan_check", "yolo_plan_table",
+    "yolo_set_hier_thresh", "yolo_set_hierarchy_mode", "yolo_darknet_boxes_map", "yolo_tree_geometry", "yolo_tree_read", "yolo_plan_check", "yolo_plan_table", "yolo_plan_dump",
     "yolo_op_tree_softmax", "yolo_op_tree_top", "yolo_activation_code", "yolo_op_activate", "yolo_op_shortcut",
     "yolo_output_map_geometry", "yolo_output_map", "yolo_label_map", "yolo_segment_images_u8", "yolo_op_deconv2d", "yolo_op_l2norm", "yolo_op_upsample", "yolo_op_label_map",
     "yolo_op_conv2d_grouped",
@@ -149,6 +149,7 @@ def load_library():
     l.yolo_tree_read.argtypes = [C.c_char_p, P, P, P, P, P, P, P, C.c_char_p, SZ]
     l.yolo_plan_check.argtypes = [C.c_char_p, I, C.c_char_p, SZ]
     l.yolo_plan_table.argtypes = [C.c_char_p, I, I, I, C.c_char_p, SZ, C.c_char_p, SZ]
+    l.yolo_plan_dump.argtypes = [C.c_char_p, I, I, I, C.c_char_p, SZ, C.c_char_p, SZ]
     l.yolo_op_tree_softmax.argtypes = [P, I, I, C.c_char_p, F, I, P, I]
     l.yolo_op_tree_top.argtypes = [P, I, C.c_char_p, F, P, I]
     l.yolo_activation_code.argtypes = [C.c_char_p]
@@ -872,6 +873,14 @@ def plan_table(cfg_text, dtype=BF16, max_batch=1, keep_layers=False):
     it refuses."""
     out, err = C.create_string_buffer(1 << 18), C.create_string_buffer(1024)
     rc = load_library().yolo_plan_table(cfg_text.encode(), dtype, max_batch, int(keep_layers), out, len(out), err, 1024)
+    return rc, (err if rc else out).value.decode()
+
+
+def plan_dump(cfg_text, dtype=BF16, max_batch=1, keep_layers=False):
+    """Every field the planner writes, without a device (yolo_plan_dump) -> (status, text): a line per layer, a line per storage and
+    the context's line; the planner's message when it refuses."""
+    out, err = C.create_string_buffer(1 << 20), C.create_string_buffer(1024)
+    rc = load_library().yolo_plan_dump(cfg_text.encode(), dtype, max_batch, int(keep_layers), out, len(out), err, 1024)
     return rc, (err if rc else out).value.decode()
 
 
