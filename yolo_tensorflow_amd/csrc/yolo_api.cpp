@@ -82,8 +82,7 @@ void yolo_destroy(yolo_ctx *c)
     for (void *p : ptrs) if (p) hipFree(p);
     for (auto &t : c->trees) free_tree(t);
     if (c->d_map200) hipFree(c->d_map200);
-    if (c->gexec) hipGraphExecDestroy(c->gexec);
-    if (c->gexec_img) hipGraphExecDestroy(c->gexec_img);
+    drop_graph(c);
     if (c->own_stream && c->stream) hipStreamDestroy(c->stream);
     delete c;
 }

@@ -1,6 +1,7 @@
 // Private to libyolo_hip.so's host side: the planned network (layers, storage pool, context) and the functions its translation
 // units share.  yolo_plan.cpp: darknet-cfg parser, planner, buffer pool, the plan queries that need no device.  yolo_pack.cpp: BN fold, filter packing, fp8 scales, weight
-// stream / export artifact.  yolo_run.cpp: launch sequence, detect graph, timing.  yolo_tune.cpp: tile selection rule, autotuner, tile plan.  yolo_api.cpp: create / destroy,
+// stream / export artifact.  yolo_run.cpp: launch sequence, input staging (input_fill_dst / input_filled), the two captured detect steps (graph_step over
+// yolo_ctx::graph), what a forward leaves (forward_done), timing.  yolo_tune.cpp: tile selection rule, autotuner, tile plan.  yolo_api.cpp: create / destroy,
 // introspection, darknet-flavoured views.  yolo_ops.cpp: single-operator entry points.
 #pragma once
 #include "../../include/yolo_hip.h"
@@ -129,16 +130,14 @@ struct yolo_ctx {
     int *d_srow = nullptr, *d_rows = nullptr;      // rows_out support: row of every sorted candidate [max_batch * rows], staging [boxes_cap]
     // darknet-flavoured outputs (yolo_darknet_boxes / yolo_last_layer_output): records, row list, count, last layer's planar output
     float *d_dn_rec = nullptr; int *d_dn_src = nullptr; int *d_dn_count = nullptr; float *d_dn_last = nullptr; size_t dn_last_cap = 0;
-    // yolo_detect_graph state
-    struct GKey { const void *img; int n, fmt; float scale, st, it; int mo, nm, sm; void *bo, *co; } gkey{};
-    hipGraphExec_t gexec = nullptr; int gstate = 0;      // 0: next call eager, 1: next call captures, 2: replay, -1: capture unsupported
+    // the captured detect steps (graph_step, yolo_run.cpp): graph[0] yolo_detect_graph's, graph[1] yolo_detect_images_graph's -- one each: a caller that alternates the two recaptures neither.
+    // key: every argument the captured launches hold, both entry points' in one struct (memset to zero before it is filled: memcmp compares it; no image size or offset: those live in d_descs, rewritten before every launch)
+    struct GraphKey { const void *src; size_t bytes; int n, fmt, fit, units; float scale, st, it; int mo, nm, sm; void *bo, *co; };
+    struct GraphStep { GraphKey key; hipGraphExec_t exec; int state; } graph[2] = {};      // state 0: next call eager, 1: next call captures, 2: replay, -1: capture unsupported (sticky)
     // ragged batches of native-size images (yolo_*_images_*): descriptor table [max_batch] (device), staging of a host packed buffer, the
-    // geometry the last such forward ran with (what the box mapping of its postprocess reads), and yolo_detect_images_graph's state (the
-    // same states as above; its key holds no image size or offset: those live in d_descs, rewritten before every launch)
+    // geometry the last such forward ran with (what the box mapping of its postprocess reads)
     ImgDesc *d_descs = nullptr; void *d_pix = nullptr; size_t pix_cap = 0;
     int geom_fit = -1, geom_n = 0;
-    struct GKeyImages { const void *pix; size_t bytes; int n, fit, units; float st, it; int mo, nm, sm; void *bo, *co; } gkey_img;
-    hipGraphExec_t gexec_img = nullptr; int gstate_img = 0;
     // hierarchical softmax ("Softmax trees"): the trees of the cfg's tree= keys; tree_head: the [region] layer that has one
     // (-1: none); hier_thresh: yolo_set_hier_thresh; hierarchy_mode: yolo_set_hierarchy_mode; tree_full: YOLO_TREE_FULL forces the full
     // decode in yolo_detect*; lean_hier: the hier_thresh the last descent-form decode labelled its rows with
@@ -177,8 +176,7 @@ inline int pair_width(int C) { return 2 * roundup(C, 32); }      // elements per
 inline int gran_of(int dt) { return dt == DT_FP8 ? 16 : 8; }      // channels per 16-byte piece (8 for fp32 tensors too)
 inline void drop_graph(yolo_ctx *c)      // a plan / parameter / buffer change: no captured detect step may be replayed
 {
-    if (c->gexec) { hipGraphExecDestroy(c->gexec); c->gexec = nullptr; } if (c->gstate > 0) c->gstate = 0;
-    if (c->gexec_img) { hipGraphExecDestroy(c->gexec_img); c->gexec_img = nullptr; } if (c->gstate_img > 0) c->gstate_img = 0;
+    for (auto &g : c->graph) { if (g.exec) { hipGraphExecDestroy(g.exec); g.exec = nullptr; } if (g.state > 0) g.state = 0; }
 }
 
 // ---- layer kinds the planner asks for by more than one name ----
@@ -228,7 +226,7 @@ DeconvArgs deconv_geometry(int size, int stride, int pad, int h, int w, int cin_
 GConvArgs gconv_geometry(int size, int stride, int pad, int h, int w, int cin, int filters, int groups, int act, int in_dt);      // the same of GConvArgs
 int run_layer(yolo_ctx *c, int i, int n);
 int stage_in(yolo_ctx *c, const void *images, int n, int fmt, int loc, float scale);
-int run_network(yolo_ctx *c, int n, bool lean = false);
+int run_network(yolo_ctx *c, int n, bool lean = false, int fit = -1);      // fit >= 0: the input is a fitted ragged batch (forward_done records its geometry)
 int copy_out(yolo_ctx *c, void *dst, const void *src, size_t bytes, int loc);
 int output_layer(const yolo_ctx *c);      // the network's output: the last layer that is not [cost] (DN/network.c:699-706)
 int need_detector(yolo_ctx *c, const char *what);      // YOLO_ERR_INVALID with a message for a classifier or a map context

@@ -1,4 +1,4 @@
-// Launch sequence of libyolo_hip.so: layer -> kernel launch, input staging, threshold + NMS, the captured detect step and layer timing.
+// Launch sequence of libyolo_hip.so: layer -> kernel launch, input staging, threshold + NMS, the captured detect steps and layer timing.
 #include "yolo_ctx.h"
 
 namespace yolo_impl {
@@ -60,13 +60,16 @@ DeconvArgs deconv_geometry(int size, int stride, int pad, int h, int w, int cin_
     return a;
 }
 
+static TView nview(int n, TView v) { v.n = n; return v; }      // a tensor's view at this call's batch
+// channels a layer that computes `ch` of them stores: zeros in the channels past them, up to the granule of the output's type (a window of a concat buffer holds whole granules)
+static int store_width(const Layer &L, int ch) { return std::min(L.out.stride, roundup(ch, L.out.dt == DT_F32 && L.head ? 4 : 8)); }
+
 static DeconvArgs deconv_args(const yolo_ctx *c, const Layer &L, int n)
 {
     const TView in = view_of(c, L.in[0]);
     DeconvArgs a = deconv_geometry(L.size, L.stride, L.pad, in.h, in.w, L.cin_pad, L.filters, L.act, L.in_dt);
     a.in = in.ptr; a.in_stride = in.stride; a.wt = L.d_w; a.bias = L.d_b; a.out = L.out.ptr; a.out_stride = L.out.stride; a.out_dt = L.out.dt; a.N = n;
-    // zeros in the channels past the filters, up to the granule of the output's type (a window of a concat buffer holds whole granules)
-    a.Cstore = std::min(L.out.stride, roundup(L.filters, L.out.dt == DT_F32 && L.head ? 4 : 8));
+    a.Cstore = store_width(L, L.filters);
     return a;
 }
 
@@ -84,12 +87,12 @@ static GConvArgs gconv_args(const yolo_ctx *c, const Layer &L, int n)
     const TView in = view_of(c, L.in[0]);
     GConvArgs a = gconv_geometry(L.size, L.stride, L.pad, in.h, in.w, L.cin, L.filters, L.groups, L.act, L.in_dt);
     a.in = in.ptr; a.in_stride = in.stride; a.wt = L.d_w; a.bias = L.d_b; a.out = L.out.ptr; a.out_stride = L.out.stride; a.out_dt = L.out.dt; a.N = n;
-    a.Cstore = std::min(L.out.stride, roundup(L.filters, L.out.dt == DT_F32 && L.head ? 4 : 8));      // zeros past the filters, as deconv_args
+    a.Cstore = store_width(L, L.filters);
     return a;
 }
 
 // split fp16: a layer that moves or interpolates values runs in fp32 between a join (hi + lo) and a split
-static int via_f32(yolo_ctx *c, const Layer &L, int n, int kind)
+static int via_f32(yolo_ctx *c, const Layer &L, int n)
 {
     hipStream_t s = c->stream;
     const TView in = view_of(c, L.in[0]);
@@ -99,9 +102,10 @@ static int via_f32(yolo_ctx *c, const Layer &L, int n, int kind)
     HIPCK(c, launch_split_to_f32(in.ptr, in.stride, cpi, c->d_f32a, cpi, pin, s));
     TView a; a.ptr = c->d_f32a; a.n = n; a.h = in.h; a.w = in.w; a.c = cpi; a.stride = cpi; a.dt = DT_F32;
     TView b; b.ptr = c->d_f32b; b.n = n; b.h = L.H; b.w = L.W; b.c = cpo; b.stride = cpo; b.dt = DT_F32;
-    if (kind == 0) HIPCK(c, launch_upsample2x(a, b, c->semantics == YOLO_SEM_TF, s));
-    else if (kind == 1) HIPCK(c, launch_maxpool(a, b, L.psize, L.pstride, L.ppad, s));
-    else {          // reorg scrambles channels: it runs on the LOGICAL channel counts (the padding of a pair tensor is not part of it)
+    switch (L.type) {
+    case L_UPSAMPLE: HIPCK(c, launch_upsample2x(a, b, c->semantics == YOLO_SEM_TF, s)); break;
+    case L_MAXPOOL: HIPCK(c, launch_maxpool(a, b, L.psize, L.pstride, L.ppad, s)); break;
+    default:          // L_REORG.  It scrambles channels: it runs on the LOGICAL channel counts (the padding of a pair tensor is not part of it)
         a.c = in.c; b.c = L.C;
         if (in.c % 32 || L.C % 32) return fail(c, YOLO_ERR_STATE, "internal: reorg of a pair tensor of %d channels (the planner refuses all but whole 32-channel groups)", in.c);
         HIPCK(c, launch_reorg(a, b, L.pstride, c->semantics == YOLO_SEM_DARKNET, s));
@@ -169,7 +173,6 @@ static int run_conv(yolo_ctx *c, int i, int n)
 {
     Layer &L = c->layers[i];
     hipStream_t s = c->stream;
-    auto nview = [&](TView v) { v.n = n; return v; };
     if (fused_launch_applies(c, L, n)) {          // computed inside its group's launch, which the launcher issues
         if (i == L.launcher) switch (L.fused) {
         case F_STEM: { StemArgs t = stem_args(c, i, n); HIPCK(c, launch_conv_stem(t, s)); break; }
@@ -183,7 +186,7 @@ static int run_conv(yolo_ctx *c, int i, int n)
     if (rides_as_tail(c, L)) return YOLO_OK;        // computed in the producer's epilogue
     ConvArgs a = conv_args(c, L, n);
     if (L.tail_on && !a.w2) return fail(c, YOLO_ERR_STATE, "layer %d: the plan folds the 1x1 conv %d into this layer, but its filters are not available in the producer's operand type", i, L.tail_layer);
-    if (L.s2d7) HIPCK(c, launch_reorg(nview(c->input), nview(c->s2d), 2, 0, s));      // tf.space_to_depth order: (dy, dx, channel)
+    if (L.s2d7) HIPCK(c, launch_reorg(nview(n, c->input), nview(n, c->s2d), 2, 0, s));      // tf.space_to_depth order: (dy, dx, channel)
     if (L.kernel != K_TILED) {          // input tile (K_HALO, conv_stem.hip) / window (K_S2, conv_s2.hip) staged once in LDS; a window over 2 GiB (very large batches): the tiled kernel below checks its own
         HaloArgs h = halo_args(a, L, n);
         if (L.kernel == K_HALO && conv_halo_ok(h)) { HIPCK(c, launch_conv_halo(h, s)); return YOLO_OK; }
@@ -194,6 +197,12 @@ static int run_conv(yolo_ctx *c, int i, int n)
     if (a.w2 && !a.split && !a.pairk && !conv_cfg_tail_ok(cfg, a.Cout, a.in_dt == DT_FP8, a.tail_f32 != 0)) return fail(c, YOLO_ERR_STATE, "layer %d: tile config %d cannot run the fused 1x1 tail", i, cfg);
     HIPCK(c, a.in_dt == DT_FP8 ? launch_conv_fp8(a, cfg, s) : launch_conv_bf16(a, cfg, s));
     return YOLO_OK;
+}
+
+static void yolo_anchors(const yolo_ctx *c, const Layer &Y, float *out)      // a [yolo] head's anchors in cells: pixels over the head's stride
+{
+    const int stride[2] = {c->in_w / Y.W, c->in_h / Y.H};          // along x (anchor widths), along y (anchor heights)
+    for (int k = 0; k < 2 * Y.na; ++k) out[k] = (float)(1.0 * (double)Y.anchors[k] / (double)stride[k & 1]);
 }
 
 static int run_decode(yolo_ctx *c, int i, int n)
@@ -213,9 +222,7 @@ static int run_decode(yolo_ctx *c, int i, int n)
             const Layer &P = c->layers[k - 1];
             LeanHead &h = la.h[la.nheads++];
             h.raw = (const float *)P.out.ptr; h.obj = P.d_obj; h.raw_stride = P.out.stride; h.gh = Y.H; h.gw = Y.W; h.na = Y.na; h.row_off = Y.row_off; h.box_begin = begin;
-            const int stride[2] = {c->in_w / Y.W, c->in_h / Y.H};          // along x (anchor widths), along y (anchor heights)
-            h.sx = (float)stride[0]; h.sy = (float)stride[1];
-            for (int q = 0; q < 2 * Y.na; ++q) h.anchors[q] = (float)(1.0 * (double)Y.anchors[q] / (double)stride[q & 1]);
+            h.sx = (float)(c->in_w / Y.W); h.sy = (float)(c->in_h / Y.H); yolo_anchors(c, Y, h.anchors);
             begin += (long)n * Y.H * Y.W * Y.na;
         }
         la.total = begin; la.n = n; la.classes = L.classes; la.mode = c->decode; la.rows_total = c->rows;
@@ -231,8 +238,8 @@ static int run_decode(yolo_ctx *c, int i, int n)
     DecodeArgs d; memset(&d, 0, sizeof d);          // one fill for the three decode launches below
     d.raw = (const float *)P.out.ptr; d.raw_stride = P.out.stride; d.n = n; d.gh = L.H; d.gw = L.W; d.na = L.na; d.classes = L.classes;
     d.img_h = c->in_h; d.img_w = c->in_w; d.mode = c->decode; d.region = L.type == L_REGION;
-    const int stride[2] = {c->in_w / L.W, c->in_h / L.H};          // along x (anchor widths), along y (anchor heights)
-    for (int k = 0; k < 2 * L.na; ++k) d.anchors[k] = L.type == L_YOLO ? (float)(1.0 * (double)L.anchors[k] / (double)stride[k & 1]) : L.anchors[k];
+    if (L.type == L_YOLO) yolo_anchors(c, L, d.anchors);
+    else std::copy(L.anchors.begin(), L.anchors.begin() + 2 * L.na, d.anchors);          // [region]: already in cells
     d.det = c->lean ? nullptr : c->d_det; d.box4 = c->lean ? c->d_box4 : nullptr; d.rows_total = c->rows; d.row_off = L.row_off;
     d.reject_below = c->lean ? c->lean_thr : -INFINITY;
     // [region] with a softmax tree.  Full form: the decoded tensor with absolute class probabilities (scored at postprocess time, with the hier_thresh of that moment); descent form (yolo_detect*): box4, scores, labels straight from the raw tensor
@@ -246,30 +253,29 @@ int run_layer(yolo_ctx *c, int i, int n)
 {
     Layer &L = c->layers[i];
     hipStream_t s = c->stream;
-    auto nview = [&](TView v) { v.n = n; return v; };
     switch (L.type) {
     case L_CONV:
         if (int r = run_conv(c, i, n)) return r;
-        if (L.post_act != ACT_LINEAR) HIPCK(c, launch_activate(nview(L.out), L.pair, L.post_act, s));
+        if (L.post_act != ACT_LINEAR) HIPCK(c, launch_activate(nview(n, L.out), L.pair, L.post_act, s));
         break;
     case L_SHORTCUT:
         if (L.general) {          // DN/blas.c:68-92 + the layer's activation, one launch
-            HIPCK(c, launch_shortcut(nview(view_of(c, L.in[0])), nview(view_of(c, L.in[1])), nview(L.out), L.pair, L.act, s));
+            HIPCK(c, launch_shortcut(nview(n, view_of(c, L.in[0])), nview(n, view_of(c, L.in[1])), nview(n, L.out), L.pair, L.act, s));
         } else if (!L.noop && L.pair) {
             HIPCK(c, launch_add_split(view_of(c, L.in[0]).ptr, view_of(c, L.in[0]).stride, view_of(c, L.in[1]).ptr, view_of(c, L.in[1]).stride, L.out.ptr, L.out.stride, roundup(L.C, 32), (size_t)n * L.H * L.W, s));
         } else if (!L.noop) {
             float sa = 1.f, sb = 1.f, so = 1.f;
             if (c->dtype == YOLO_FP8) { sa = c->eff_scale[L.in[0]]; sb = c->eff_scale[L.in[1]]; so = 1.f / c->eff_scale[i]; }
-            HIPCK(c, launch_add(nview(view_of(c, L.in[0])), nview(view_of(c, L.in[1])), nview(L.out), s, sa, sb, so));
+            HIPCK(c, launch_add(nview(n, view_of(c, L.in[0])), nview(n, view_of(c, L.in[1])), nview(n, L.out), s, sa, sb, so));
         }
         break;
     case L_ROUTE:
         for (size_t k = 0; k < L.copy_inputs.size(); ++k) {
-            TView src = nview(view_of(c, L.copy_inputs[k])); TView dst = nview(L.out);
+            TView src = nview(n, view_of(c, L.copy_inputs[k])); TView dst = nview(n, L.out);
             dst.ptr = (char *)dst.ptr + (size_t)L.copy_offsets[k] * dt_size(dst.dt); dst.c = src.c;
             if (L.pair) {        // interleaved pairs: the source's 2 * Cp elements at twice the channel offset (whole 32-channel groups: the planner refuses the rest)
                 if (src.c % 32 || L.copy_offsets[k] % 32) return fail(c, YOLO_ERR_STATE, "internal: route copy of a pair tensor: %d channels at offset %d", src.c, L.copy_offsets[k]);
-                TView dv = nview(L.out);
+                TView dv = nview(n, L.out);
                 dv.ptr = (char *)L.out.ptr + (size_t)2 * L.copy_offsets[k] * 2; dv.c = 2 * src.c; src.c = 2 * src.c;
                 HIPCK(c, launch_copy(src, dv, s));
                 continue;
@@ -284,43 +290,52 @@ int run_layer(yolo_ctx *c, int i, int n)
         }
         break;
     case L_LOCAL:
-        HIPCK(c, launch_local(nview(view_of(c, L.in[0])), nview(L.out), L.d_w, L.d_b, L.size, L.stride, L.pad, L.act, s));
-        if (L.post_act != ACT_LINEAR) HIPCK(c, launch_activate(nview(L.out), false, L.post_act, s));
+        HIPCK(c, launch_local(nview(n, view_of(c, L.in[0])), nview(n, L.out), L.d_w, L.d_b, L.size, L.stride, L.pad, L.act, s));
+        if (L.post_act != ACT_LINEAR) HIPCK(c, launch_activate(nview(n, L.out), false, L.post_act, s));
         break;
     case L_DECONV:
         HIPCK(c, launch_deconv(deconv_args(c, L, n), s));
-        if (L.post_act != ACT_LINEAR) HIPCK(c, launch_activate(nview(L.out), false, L.post_act, s));
+        if (L.post_act != ACT_LINEAR) HIPCK(c, launch_activate(nview(n, L.out), false, L.post_act, s));
         break;
     case L_GCONV:
         HIPCK(c, launch_gconv(gconv_args(c, L, n), s));
-        if (L.post_act != ACT_LINEAR) HIPCK(c, launch_activate(nview(L.out), false, L.post_act, s));
+        if (L.post_act != ACT_LINEAR) HIPCK(c, launch_activate(nview(n, L.out), false, L.post_act, s));
         break;
     case L_ACTIVATE: {
-        TView out = nview(L.out);
+        TView out = nview(n, L.out);
         if (!L.inplace) {          // a tensor of its own (keep_layers, a second reader of the producer, a concat window): copied first
             // whole granules: the channels C .. of the last one are the producer's zeros, not what the pooled buffer's last tenant left there
             // (a consumer multiplies them by zero filters, and 0 * Inf is NaN)
-            TView src = nview(view_of(c, L.in[0])), dst = out;
-            src.c = dst.c = L.pair ? pair_width(L.C) : std::min(std::min(src.stride, dst.stride), roundup(L.C, out.dt == DT_F32 && L.head ? 4 : 8));
+            TView src = nview(n, view_of(c, L.in[0])), dst = out;
+            src.c = dst.c = L.pair ? pair_width(L.C) : std::min(src.stride, store_width(L, L.C));
             HIPCK(c, launch_copy_channels(src, dst, s));
         }
         HIPCK(c, launch_activate(out, L.pair, L.act, s));
         break; }
-    case L_L2NORM: HIPCK(c, launch_l2norm(nview(view_of(c, L.in[0])), nview(L.out), s)); break;
+    case L_L2NORM: HIPCK(c, launch_l2norm(nview(n, view_of(c, L.in[0])), nview(n, L.out), s)); break;
     case L_UPSAMPLE:
         if (L.pstride != 2 || L.up_scale != 1.f) {          // (never pairs: the planner refuses these in the split-fp16 configuration)
-            if (c->semantics == YOLO_SEM_DARKNET) { HIPCK(c, launch_upsample_nearest(nview(view_of(c, L.in[0])), nview(L.out), L.pstride, L.up_scale, s)); break; }
-            HIPCK(c, launch_upsample2x(nview(view_of(c, L.in[0])), nview(L.out), 1, s));
-            HIPCK(c, launch_scale(nview(L.out), L.up_scale, s));
+            if (c->semantics == YOLO_SEM_DARKNET) { HIPCK(c, launch_upsample_nearest(nview(n, view_of(c, L.in[0])), nview(n, L.out), L.pstride, L.up_scale, s)); break; }
+            HIPCK(c, launch_upsample2x(nview(n, view_of(c, L.in[0])), nview(n, L.out), 1, s));
+            HIPCK(c, launch_scale(nview(n, L.out), L.up_scale, s));
             break;
         }
-        if (L.pair) { if (getenv("YOLO_PAIR_UPSAMPLE_VIA_F32")) { if (int r = via_f32(c, L, n, 0)) return r; } else HIPCK(c, launch_upsample2x_pair(nview(view_of(c, L.in[0])), nview(L.out), c->semantics == YOLO_SEM_TF, s)); break; } HIPCK(c, launch_upsample2x(nview(view_of(c, L.in[0])), nview(L.out), c->semantics == YOLO_SEM_TF, s)); break;
-    case L_MAXPOOL: if (L.pair) { if (int r = via_f32(c, L, n, 1)) return r; break; } HIPCK(c, launch_maxpool(nview(view_of(c, L.in[0])), nview(L.out), L.psize, L.pstride, L.ppad, s)); break;
-    case L_REORG: if (L.pair) { if (int r = via_f32(c, L, n, 2)) return r; break; } HIPCK(c, launch_reorg(nview(view_of(c, L.in[0])), nview(L.out), L.pstride, c->semantics == YOLO_SEM_DARKNET, s)); break;
+        if (L.pair && getenv("YOLO_PAIR_UPSAMPLE_VIA_F32")) { if (int r = via_f32(c, L, n)) return r; }
+        else if (L.pair) HIPCK(c, launch_upsample2x_pair(nview(n, view_of(c, L.in[0])), nview(n, L.out), c->semantics == YOLO_SEM_TF, s));
+        else HIPCK(c, launch_upsample2x(nview(n, view_of(c, L.in[0])), nview(n, L.out), c->semantics == YOLO_SEM_TF, s));
+        break;
+    case L_MAXPOOL:          // (split fp16: no pair form of the pool and the reorg)
+        if (L.pair) { if (int r = via_f32(c, L, n)) return r; }
+        else HIPCK(c, launch_maxpool(nview(n, view_of(c, L.in[0])), nview(n, L.out), L.psize, L.pstride, L.ppad, s));
+        break;
+    case L_REORG:
+        if (L.pair) { if (int r = via_f32(c, L, n)) return r; }
+        else HIPCK(c, launch_reorg(nview(n, view_of(c, L.in[0])), nview(n, L.out), L.pstride, c->semantics == YOLO_SEM_DARKNET, s));
+        break;
     case L_AVGPOOL: {
         if (L.pool_fused) break;             // pooled inside the [softmax] launch that follows
-        const TView in = nview(view_of(c, L.in[0]));
-        HIPCK(c, launch_avgpool(in, c->pair_of(L.in[0]) && in.dt == DT_F16, nview(L.out), s));
+        const TView in = nview(n, view_of(c, L.in[0]));
+        HIPCK(c, launch_avgpool(in, c->pair_of(L.in[0]) && in.dt == DT_F16, nview(n, L.out), s));
         break; }
     case L_SOFTMAX: {
         SoftmaxArgs a; memset(&a, 0, sizeof a);
@@ -338,7 +353,7 @@ int run_layer(yolo_ctx *c, int i, int n)
             break;
         }
         if (P.type == L_AVGPOOL && P.pool_fused) {
-            const TView in = nview(view_of(c, P.in[0]));
+            const TView in = nview(n, view_of(c, P.in[0]));
             if (!avgpool_softmax_ok(in, a)) return fail(c, YOLO_ERR_STATE, "layer %d: the fused [avgpool] + [softmax] launch does not apply to this plan", i);
             HIPCK(c, launch_avgpool_softmax(in, (float *)P.out.ptr, P.out.stride, a, s));
         } else {
@@ -358,6 +373,14 @@ int run_layer(yolo_ctx *c, int i, int n)
     return YOLO_OK;
 }
 
+// ---- input staging.  Every site that writes the network input does: auto [dst, dt] = input_fill_dst(c); its own fill launch into dst (8 channels per pixel); input_filled(c, pixels) ----
+static std::pair<void *, int> input_fill_dst(yolo_ctx *c)      // (pointer, element type).  Split fp16: the fill writes the image in fp32 (exact for uint8 pixels x scale up to fp32 rounding), input_filled splits it into pairs
+{
+    c->stem_u8 = nullptr;          // from here on the fused stem reads the filled input, not a caller's uint8 image: ahead of the fill launch, so also when that launch is refused
+    using P = std::pair<void *, int>; return c->in_pair ? P(c->d_f32a, DT_F32) : P(c->input.ptr, c->input.dt);
+}
+static hipError_t input_filled(yolo_ctx *c, size_t npix) { return c->in_pair ? launch_split_from_f32(c->d_f32a, 8, c->input.ptr, 24, 8, npix, c->stream, PAIR_B3) : hipSuccess; }
+
 int stage_in(yolo_ctx *c, const void *images, int n, int fmt, int loc, float scale)
 {
     if (n < 1 || n > c->max_batch) return fail(c, YOLO_ERR_INVALID, "batch %d outside 1..%d", n, c->max_batch);
@@ -371,22 +394,17 @@ int stage_in(yolo_ctx *c, const void *images, int n, int fmt, int loc, float sca
     // uint8 images of a network whose first layers run as the fused stem: the stem converts the pixels itself (conv_stem.hip, U8 form).
     // That form gathers the raw rows in aligned dwords through a descriptor that ends with the image tensor: a batch whose byte count is no
     // multiple of 4 (odd width x odd height x odd n) would lose its last 1-3 bytes to the range check, so it takes the conversion launch
-    c->stem_u8 = nullptr;
     if (fmt == YOLO_IMG_U8 && c->layers.size() > 1 && never_stored(c->layers[0], 0) && (double)npix * 3 < 2147483648.0 && ((size_t)src & 3) == 0 && (npix * 3) % 4 == 0) {
         c->stem_u8 = (const uint8_t *)src; c->stem_scale = scale; c->stem_u8_n = n;
         return YOLO_OK;
     }
-    if (c->in_pair) {        // the image in fp32 (exact for uint8 pixels x scale up to fp32 rounding), then split pairs
-        HIPCK(c, launch_preprocess(src, fmt, n, c->in_h * c->in_w, scale, c->d_f32a, DT_F32, 8, c->stream, c->in_mul, c->in_add));
-        HIPCK(c, launch_split_from_f32(c->d_f32a, 8, c->input.ptr, 24, 8, npix, c->stream, PAIR_B3));
-        return YOLO_OK;
-    }
-    HIPCK(c, launch_preprocess(src, fmt, n, c->in_h * c->in_w, scale, c->input.ptr, c->input.dt, 8, c->stream, c->in_mul, c->in_add));
+    auto [dst, dt] = input_fill_dst(c);
+    HIPCK(c, launch_preprocess(src, fmt, n, c->in_h * c->in_w, scale, dst, dt, 8, c->stream, c->in_mul, c->in_add));
+    HIPCK(c, input_filled(c, npix));
     return YOLO_OK;
 }
 
-// the layer sequence of one forward.  `skip_conv`: the timing pass that runs everything but the convs (dense and grouped: conv_flops counts both); `ev`: per-layer events
-// (yolo_time_layers)
+// the layer sequence of one forward.  `skip_conv`: the timing pass that runs everything but the convs (dense and grouped: conv_flops counts both); `ev`: per-layer events (yolo_time_layers)
 static int run_layers(yolo_ctx *c, int n, bool skip_conv = false, std::vector<hipEvent_t> *ev = nullptr)
 {
     const int NL = (int)c->layers.size();
@@ -397,11 +415,19 @@ static int run_layers(yolo_ctx *c, int n, bool skip_conv = false, std::vector<hi
     return YOLO_OK;
 }
 
-int run_network(yolo_ctx *c, int n, bool lean)
+// What a finished forward of n images leaves for yolo_postprocess* / yolo_darknet_boxes*.  lean: the decode wrote scores, labels and box4, not the tensor; scores_mode: what d_scores holds now (< 0: left as it is); fit >= 0: the input was a ragged batch fitted that way
+static void forward_done(yolo_ctx *c, int n, bool lean, int scores_mode = 0, int fit = -1)
 {
-    c->lean = lean && c->lean_ok;
-    { int r = run_layers(c, n); if (r) { c->lean = false; return r; } }
-    c->last_n = n; c->scores_mode = 0; c->det_valid = !c->lean;
+    c->lean = lean && c->lean_ok; c->det_valid = !c->lean; c->last_n = n;
+    if (scores_mode >= 0) c->scores_mode = scores_mode;
+    if (fit >= 0) { c->geom_fit = fit; c->geom_n = n; }
+}
+
+int run_network(yolo_ctx *c, int n, bool lean, int fit)
+{
+    c->lean = lean && c->lean_ok;          // (run_decode reads it)
+    if (int r = run_layers(c, n)) { c->lean = false; return r; }
+    forward_done(c, n, lean, 0, fit);
     return YOLO_OK;
 }
 
@@ -490,8 +516,7 @@ static int forward_impl(yolo_ctx *c, const void *images, int n, int fmt, int loc
     HIPCK(c, hipSetDevice(c->device));
     int r = stage_in(c, images, n, fmt, loc, scale); if (r) return r;
     r = run_network(c, n, lean && !det_out); if (r) return r;
-    if (det_out) return copy_out(c, det_out, c->d_det, (size_t)n * c->rows * c->attrs * 4, out_loc);
-    return YOLO_OK;
+    return det_out ? copy_out(c, det_out, c->d_det, (size_t)n * c->rows * c->attrs * 4, out_loc) : YOLO_OK;
 }
 
 int yolo_forward(yolo_ctx *c, const void *images, int n, int fmt, int loc, float scale, float *det_out, int out_loc)
@@ -499,47 +524,39 @@ int yolo_forward(yolo_ctx *c, const void *images, int n, int fmt, int loc, float
     return forward_impl(c, images, n, fmt, loc, scale, det_out, out_loc, false);
 }
 
-int yolo_forward_image_u8(yolo_ctx *c, const uint8_t *image, int h, int w, int loc, float *det_out, int out_loc)
+// One image at its own size -> the network input (`fill`, which `fill_name` names in the message) -> forward -> the decoded tensor.  `name`: the entry point.
+// A host image gets a device copy of its own for the call, freed once the stream has drained -- also when the fill or the forward failed
+typedef hipError_t (*FillOne)(yolo_ctx *c, const void *src, int h, int w, void *dst, int dt);
+static int forward_one(yolo_ctx *c, const char *name, const char *fill_name, FillOne fill, const void *image, int h, int w, size_t bytes, int loc, float *det_out, int out_loc)
 {
     if (!c) return YOLO_ERR_INVALID;
-    if (!c->weights_loaded) return fail(c, YOLO_ERR_STATE, "yolo_forward_image_u8 before weights were loaded");
+    if (!c->weights_loaded) return fail(c, YOLO_ERR_STATE, "%s before weights were loaded", name);
     if (!image || h < 1 || w < 1) return fail(c, YOLO_ERR_INVALID, "bad image");
     HIPCK(c, hipSetDevice(c->device));
-    const uint8_t *src = image; void *tmp = nullptr;
+    const void *src = image; void *tmp = nullptr;
     if (loc == YOLO_HOST) {
-        HIPCK(c, hipMalloc(&tmp, (size_t)h * w * 3));
-        HIPCK(c, hipMemcpyAsync(tmp, image, (size_t)h * w * 3, hipMemcpyHostToDevice, c->stream)); src = (const uint8_t *)tmp;
+        HIPCK(c, hipMalloc(&tmp, bytes));
+        HIPCK(c, hipMemcpyAsync(tmp, image, bytes, hipMemcpyHostToDevice, c->stream)); src = tmp;
     }
-    c->stem_u8 = nullptr;
-    hipError_t e = c->in_pair ? launch_resize_u8(src, h, w, c->in_h, c->in_w, c->d_f32a, DT_F32, 8, 8, c->stream, c->in_mul, c->in_add)
-                              : launch_resize_u8(src, h, w, c->in_h, c->in_w, c->input.ptr, c->input.dt, 8, 8, c->stream, c->in_mul, c->in_add);
-    if (e == hipSuccess && c->in_pair) e = launch_split_from_f32(c->d_f32a, 8, c->input.ptr, 24, 8, (size_t)c->in_h * c->in_w, c->stream, PAIR_B3);
-    int r = e == hipSuccess ? run_network(c, 1) : fail(c, YOLO_ERR_HIP, "resize: %s", hipGetErrorString(e));
+    auto [dst, dt] = input_fill_dst(c);
+    hipError_t e = fill(c, src, h, w, dst, dt);
+    if (e == hipSuccess) e = input_filled(c, (size_t)c->in_h * c->in_w);
+    int r = e == hipSuccess ? run_network(c, 1) : fail(c, YOLO_ERR_HIP, "%s: %s", fill_name, hipGetErrorString(e));
     if (tmp) { hipStreamSynchronize(c->stream); hipFree(tmp); }
     if (r) return r;
-    if (det_out) return copy_out(c, det_out, c->d_det, (size_t)c->rows * c->attrs * 4, out_loc);
-    return YOLO_OK;
+    return det_out ? copy_out(c, det_out, c->d_det, (size_t)c->rows * c->attrs * 4, out_loc) : YOLO_OK;
+}
+
+int yolo_forward_image_u8(yolo_ctx *c, const uint8_t *image, int h, int w, int loc, float *det_out, int out_loc)
+{
+    const FillOne fill = [](yolo_ctx *c, const void *src, int h, int w, void *dst, int dt) { return launch_resize_u8((const uint8_t *)src, h, w, c->in_h, c->in_w, dst, dt, 8, 8, c->stream, c->in_mul, c->in_add); };
+    return forward_one(c, "yolo_forward_image_u8", "resize", fill, image, h, w, (size_t)h * w * 3, loc, det_out, out_loc);
 }
 
 int yolo_forward_letterbox_chw(yolo_ctx *c, const float *image_chw, int w, int h, int loc, float *det_out, int out_loc)
 {
-    if (!c) return YOLO_ERR_INVALID;
-    if (!c->weights_loaded) return fail(c, YOLO_ERR_STATE, "yolo_forward_letterbox_chw before weights were loaded");
-    if (!image_chw || h < 1 || w < 1) return fail(c, YOLO_ERR_INVALID, "bad image");
-    HIPCK(c, hipSetDevice(c->device));
-    const float *src = image_chw; void *tmp = nullptr;
-    if (loc == YOLO_HOST) {
-        HIPCK(c, hipMalloc(&tmp, (size_t)h * w * 3 * 4));
-        HIPCK(c, hipMemcpyAsync(tmp, image_chw, (size_t)h * w * 3 * 4, hipMemcpyHostToDevice, c->stream)); src = (const float *)tmp;
-    }
-    c->stem_u8 = nullptr;
-    hipError_t e = c->in_pair ? launch_letterbox_chw(src, w, h, c->in_h, c->in_w, c->d_f32a, DT_F32, 8, c->stream) : launch_letterbox_chw(src, w, h, c->in_h, c->in_w, c->input.ptr, c->input.dt, 8, c->stream);
-    if (e == hipSuccess && c->in_pair) e = launch_split_from_f32(c->d_f32a, 8, c->input.ptr, 24, 8, (size_t)c->in_h * c->in_w, c->stream, PAIR_B3);
-    int r = e == hipSuccess ? run_network(c, 1) : fail(c, YOLO_ERR_HIP, "letterbox: %s", hipGetErrorString(e));
-    if (tmp) { hipStreamSynchronize(c->stream); hipFree(tmp); }
-    if (r) return r;
-    if (det_out) return copy_out(c, det_out, c->d_det, (size_t)c->rows * c->attrs * 4, out_loc);
-    return YOLO_OK;
+    const FillOne fill = [](yolo_ctx *c, const void *src, int h, int w, void *dst, int dt) { return launch_letterbox_chw((const float *)src, w, h, c->in_h, c->in_w, dst, dt, 8, c->stream); };
+    return forward_one(c, "yolo_forward_letterbox_chw", "letterbox", fill, image_chw, h, w, (size_t)h * w * 3 * 4, loc, det_out, out_loc);
 }
 
 static int postprocess_impl(yolo_ctx *c, int n, float score_thr, float iou_thr, int max_out, int nms_mode, int select_mode,
@@ -592,42 +609,51 @@ int yolo_detect(yolo_ctx *c, const void *images, int n, int fmt, int loc, float 
     return yolo_postprocess(c, n, score_thr, iou_thr, max_out, nms_mode, select_mode, boxes_out, counts_out, out_loc);
 }
 
+// ---- the captured detect step (yolo_ctx::graph).  One call of step `g` with the checked arguments `k`: the first call with a key runs `eager` (forward + threshold + NMS from k), the second
+//      captures it, later ones replay; a stream that cannot be captured stays eager (-1).  *replayed: a graph launch ran, so what an eager call writes on the host is the caller's to write (forward_done) ----
+using GraphKey = yolo_ctx::GraphKey;
+typedef int (*GraphEager)(yolo_ctx *c, const GraphKey &k);
+static int graph_step(yolo_ctx *c, yolo_ctx::GraphStep &g, const GraphKey &k, GraphEager eager, bool *replayed)
+{
+    if (memcmp(&k, &g.key, sizeof k) != 0) {
+        if (g.exec) { hipGraphExecDestroy(g.exec); g.exec = nullptr; }
+        g.key = k; if (g.state >= 0) g.state = 0;
+    }
+    if (g.state <= 0) { int r = eager(c, k); if (r == YOLO_OK && g.state == 0) g.state = 1; return r; }
+    HIPCK(c, hipSetDevice(c->device));
+    if (g.state == 1) {
+        hipGraph_t gr = nullptr;
+        if (hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) { (void)hipGetLastError(); g.state = -1; return eager(c, k); }
+        int r = eager(c, k);
+        hipError_t e = hipStreamEndCapture(c->stream, &gr);
+        if (r != YOLO_OK || e != hipSuccess || !gr) { (void)hipGetLastError(); if (gr) hipGraphDestroy(gr); g.state = -1; return r ? r : eager(c, k); }
+        e = hipGraphInstantiate(&g.exec, gr, nullptr, nullptr, 0);
+        hipGraphDestroy(gr);
+        if (e != hipSuccess) { (void)hipGetLastError(); g.exec = nullptr; g.state = -1; return eager(c, k); }
+        g.state = 2;
+    }
+    // the captured step holds no reset of the lean decode's list counter (its NMS node leaves it at zero): a step that failed between its decode and its NMS since then left it set
+    if (c->lean_cnt_dirty) { HIPCK(c, hipMemsetAsync(c->d_lean_cnt, 0, 4, c->stream)); c->lean_cnt_dirty = false; }
+    HIPCK(c, hipGraphLaunch(g.exec, c->stream));
+    *replayed = true;
+    return YOLO_OK;
+}
+
 int yolo_detect_graph(yolo_ctx *c, const void *images, int n, int fmt, float scale, float score_thr, float iou_thr, int max_out,
                       int nms_mode, int select_mode, yolo_box *boxes_out, int32_t *counts_out)
 {
     if (!c) return YOLO_ERR_INVALID;
     if (!images || !boxes_out || !counts_out) return fail(c, YOLO_ERR_INVALID, "yolo_detect_graph needs device pointers for images, boxes_out and counts_out");
-    yolo_ctx::GKey k{images, n, fmt, scale, score_thr, iou_thr, max_out, nms_mode, select_mode, (void *)boxes_out, (void *)counts_out};
-    if (memcmp(&k, &c->gkey, sizeof k) != 0) {
-        if (c->gexec) { hipGraphExecDestroy(c->gexec); c->gexec = nullptr; }
-        c->gkey = k; if (c->gstate >= 0) c->gstate = 0;
-    }
     if (int r = post_args_ok(c, max_out, nms_mode, select_mode)) return r;
-    auto eager = [&]() -> int {
-        int r = forward_impl(c, images, n, fmt, YOLO_DEVICE, scale, nullptr, YOLO_DEVICE, nms_mode != YOLO_NMS_NUMPY_V3, score_thr); if (r) return r;
-        return yolo_postprocess(c, n, score_thr, iou_thr, max_out, nms_mode, select_mode, boxes_out, counts_out, YOLO_DEVICE);
+    GraphKey k; memset(&k, 0, sizeof k);
+    k.src = images; k.n = n; k.fmt = fmt; k.scale = scale; k.st = score_thr; k.it = iou_thr; k.mo = max_out; k.nm = nms_mode; k.sm = select_mode; k.bo = boxes_out; k.co = counts_out;
+    const GraphEager eager = [](yolo_ctx *c, const GraphKey &k) -> int {
+        int r = forward_impl(c, k.src, k.n, k.fmt, YOLO_DEVICE, k.scale, nullptr, YOLO_DEVICE, k.nm != YOLO_NMS_NUMPY_V3, k.st); if (r) return r;
+        return yolo_postprocess(c, k.n, k.st, k.it, k.mo, k.nm, k.sm, (yolo_box *)k.bo, (int32_t *)k.co, YOLO_DEVICE);
     };
-    if (c->gstate <= 0) { int r = eager(); if (r == YOLO_OK && c->gstate == 0) c->gstate = 1; return r; }
-    HIPCK(c, hipSetDevice(c->device));
-    if (c->gstate == 1) {
-        hipGraph_t g = nullptr;
-        if (hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) { (void)hipGetLastError(); c->gstate = -1; return eager(); }
-        int r = eager();
-        hipError_t e = hipStreamEndCapture(c->stream, &g);
-        if (r != YOLO_OK || e != hipSuccess || !g) { (void)hipGetLastError(); if (g) hipGraphDestroy(g); c->gstate = -1; return r ? r : eager(); }
-        e = hipGraphInstantiate(&c->gexec, g, nullptr, nullptr, 0);
-        hipGraphDestroy(g);
-        if (e != hipSuccess) { (void)hipGetLastError(); c->gexec = nullptr; c->gstate = -1; return eager(); }
-        c->gstate = 2;
-    }
-    // the captured step holds no reset of the lean decode's list counter (its NMS node leaves it at zero): a step that failed between
-    // its decode and its NMS since then left it set
-    if (c->lean_cnt_dirty) { HIPCK(c, hipMemsetAsync(c->d_lean_cnt, 0, 4, c->stream)); c->lean_cnt_dirty = false; }
-    HIPCK(c, hipGraphLaunch(c->gexec, c->stream));
-    // the replay leaves the context exactly as the eager call it was captured from would (run_network / forward_impl): a later
-    // yolo_postprocess / yolo_darknet_boxes must see that the decoded tensor was (not) written and which threshold pruned the scores
-    c->lean = nms_mode != YOLO_NMS_NUMPY_V3 && c->lean_ok; c->det_valid = !c->lean; c->lean_thr = score_thr;
-    c->last_n = n; c->scores_mode = nms_mode == YOLO_NMS_NUMPY_V3 ? 1 : 0;
+    bool replayed = false;
+    if (int r = graph_step(c, c->graph[0], k, eager, &replayed)) return r;
+    if (replayed) { c->lean_thr = score_thr; forward_done(c, n, nms_mode != YOLO_NMS_NUMPY_V3, nms_mode == YOLO_NMS_NUMPY_V3 ? 1 : 0); }      // (not stem_u8: kept, NOTEBOOK 2026-10-19)
     return YOLO_OK;
 }
 
@@ -671,14 +697,10 @@ static int images_step(yolo_ctx *c, const uint8_t *pixels, size_t bytes, const y
 {
     c->lean_thr = score_thr;
     if (upload) HIPCK(c, hipMemcpyAsync(c->d_descs, descs, (size_t)n * sizeof(ImgDesc), hipMemcpyHostToDevice, c->stream));
-    c->stem_u8 = nullptr;                // the fused stem reads the fitted input
-    if (c->in_pair) {
-        HIPCK(c, launch_fit_images(pixels, bytes, c->d_descs, n, fit, c->in_h, c->in_w, c->d_f32a, DT_F32, 8, c->in_mul, c->in_add, c->stream));
-        HIPCK(c, launch_split_from_f32(c->d_f32a, 8, c->input.ptr, 24, 8, (size_t)n * c->in_h * c->in_w, c->stream, PAIR_B3));
-    } else HIPCK(c, launch_fit_images(pixels, bytes, c->d_descs, n, fit, c->in_h, c->in_w, c->input.ptr, c->input.dt, 8, c->in_mul, c->in_add, c->stream));
-    if (int r = run_network(c, n, lean)) return r;
-    c->geom_fit = fit; c->geom_n = n;
-    return YOLO_OK;
+    auto [dst, dt] = input_fill_dst(c);
+    HIPCK(c, launch_fit_images(pixels, bytes, c->d_descs, n, fit, c->in_h, c->in_w, dst, dt, 8, c->in_mul, c->in_add, c->stream));
+    HIPCK(c, input_filled(c, (size_t)n * c->in_h * c->in_w));
+    return run_network(c, n, lean, fit);
 }
 
 static int forward_images_impl(yolo_ctx *c, const uint8_t *pixels, size_t bytes, const yolo_image_desc *descs, int n, int fit, int loc,
@@ -698,8 +720,7 @@ static int forward_images_impl(yolo_ctx *c, const uint8_t *pixels, size_t bytes,
         src = (const uint8_t *)c->d_pix;
     }
     if (int r = images_step(c, src, bytes, descs, n, fit, true, lean && !det_out, score_thr)) return r;
-    if (det_out) return copy_out(c, det_out, c->d_det, (size_t)n * c->rows * c->attrs * 4, out_loc);
-    return YOLO_OK;
+    return det_out ? copy_out(c, det_out, c->d_det, (size_t)n * c->rows * c->attrs * 4, out_loc) : YOLO_OK;
 }
 
 int yolo_forward_images_u8(yolo_ctx *c, const uint8_t *pixels, size_t bytes, const yolo_image_desc *descs, int n, int fit, int loc,
@@ -728,38 +749,19 @@ int yolo_detect_images_graph(yolo_ctx *c, const uint8_t *pixels, size_t bytes, c
     if (!pixels || !boxes_out || !counts_out) return fail(c, YOLO_ERR_INVALID, "yolo_detect_images_graph needs device pointers for pixels, boxes_out and counts_out");
     if (int r = detect_images_check(c, fit, max_out, nms_mode, select_mode, units)) return r;
     if (int r = images_check(c, pixels, bytes, descs, n, fit)) return r;
-    yolo_ctx::GKeyImages k; memset(&k, 0, sizeof k);
-    k.pix = pixels; k.bytes = bytes; k.n = n; k.fit = fit; k.units = units; k.st = score_thr; k.it = iou_thr; k.mo = max_out; k.nm = nms_mode; k.sm = select_mode;
-    k.bo = (void *)boxes_out; k.co = (void *)counts_out;
-    if (memcmp(&k, &c->gkey_img, sizeof k) != 0) {
-        if (c->gexec_img) { hipGraphExecDestroy(c->gexec_img); c->gexec_img = nullptr; }
-        c->gkey_img = k; if (c->gstate_img >= 0) c->gstate_img = 0;
-    }
+    GraphKey k; memset(&k, 0, sizeof k);
+    k.src = pixels; k.bytes = bytes; k.n = n; k.fit = fit; k.units = units; k.st = score_thr; k.it = iou_thr; k.mo = max_out; k.nm = nms_mode; k.sm = select_mode; k.bo = boxes_out; k.co = counts_out;
     HIPCK(c, hipSetDevice(c->device));
     // this call's sizes and offsets: into the device table, on the context stream, ahead of the step that reads them (never captured)
     HIPCK(c, hipMemcpyAsync(c->d_descs, descs, (size_t)n * sizeof(ImgDesc), hipMemcpyHostToDevice, c->stream));
-    const PostGeom g{fit, units == YOLO_UNITS_SOURCE_PIXELS};
-    const bool lean = nms_mode != YOLO_NMS_NUMPY_V3;
-    auto eager = [&]() -> int {
-        if (int r = images_step(c, pixels, bytes, descs, n, fit, false, lean, score_thr)) return r;
-        return postprocess_impl(c, n, score_thr, iou_thr, max_out, nms_mode, select_mode, boxes_out, counts_out, nullptr, YOLO_DEVICE, &g);
+    const GraphEager eager = [](yolo_ctx *c, const GraphKey &k) -> int {
+        if (int r = images_step(c, (const uint8_t *)k.src, k.bytes, nullptr, k.n, k.fit, false, k.nm != YOLO_NMS_NUMPY_V3, k.st)) return r;
+        const PostGeom g{k.fit, k.units == YOLO_UNITS_SOURCE_PIXELS};
+        return postprocess_impl(c, k.n, k.st, k.it, k.mo, k.nm, k.sm, (yolo_box *)k.bo, (int32_t *)k.co, nullptr, YOLO_DEVICE, &g);
     };
-    if (c->gstate_img <= 0) { int r = eager(); if (r == YOLO_OK && c->gstate_img == 0) c->gstate_img = 1; return r; }
-    if (c->gstate_img == 1) {
-        hipGraph_t gr = nullptr;
-        if (hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) { (void)hipGetLastError(); c->gstate_img = -1; return eager(); }
-        int r = eager();
-        hipError_t e = hipStreamEndCapture(c->stream, &gr);
-        if (r != YOLO_OK || e != hipSuccess || !gr) { (void)hipGetLastError(); if (gr) hipGraphDestroy(gr); c->gstate_img = -1; return r ? r : eager(); }
-        e = hipGraphInstantiate(&c->gexec_img, gr, nullptr, nullptr, 0);
-        hipGraphDestroy(gr);
-        if (e != hipSuccess) { (void)hipGetLastError(); c->gexec_img = nullptr; c->gstate_img = -1; return eager(); }
-        c->gstate_img = 2;
-    }
-    if (c->lean_cnt_dirty) { HIPCK(c, hipMemsetAsync(c->d_lean_cnt, 0, 4, c->stream)); c->lean_cnt_dirty = false; }      // see yolo_detect_graph
-    HIPCK(c, hipGraphLaunch(c->gexec_img, c->stream));
-    c->lean = lean && c->lean_ok; c->det_valid = !c->lean; c->lean_thr = score_thr;
-    c->last_n = n; c->scores_mode = nms_mode == YOLO_NMS_NUMPY_V3 ? 1 : 0; c->stem_u8 = nullptr; c->geom_fit = fit; c->geom_n = n;
+    bool replayed = false;
+    if (int r = graph_step(c, c->graph[1], k, eager, &replayed)) return r;
+    if (replayed) { c->lean_thr = score_thr; c->stem_u8 = nullptr; forward_done(c, n, nms_mode != YOLO_NMS_NUMPY_V3, nms_mode == YOLO_NMS_NUMPY_V3 ? 1 : 0, fit); }
     return YOLO_OK;
 }
 
@@ -880,7 +882,7 @@ int yolo_time_forward(yolo_ctx *c, int n, int iters, float *total_ms, float *con
             float ms = 0; HIPCK(c, hipEventElapsedTime(&ms, e0, e1)); (pass == 0 ? all_ms : rest_ms) = ms / iters;
         }
         *conv_ms = all_ms - rest_ms;
-        c->last_n = n; c->scores_mode = 0; c->det_valid = true;
+        forward_done(c, n, false);
     }
     return YOLO_OK;
 }
@@ -892,19 +894,19 @@ int yolo_time_layers(yolo_ctx *c, int n, int iters, float *ms_out)
     if (n < 1 || n > c->max_batch || iters < 1) return fail(c, YOLO_ERR_INVALID, "bad n/iters");
     HIPCK(c, hipSetDevice(c->device));
     const int NL = (int)c->layers.size();
-    c->lean = false; c->det_valid = true;
+    c->lean = false; c->det_valid = true;      // (det_valid ahead of the passes, so also when one fails: kept, NOTEBOOK 2026-10-19)
     if (c->stem_u8 && n > c->stem_u8_n) c->stem_u8 = nullptr;      // see yolo_time_forward
     EventSet evs(NL + 1); if (!evs.ok) return fail(c, YOLO_ERR_HIP, "hipEventCreate failed");
     std::vector<hipEvent_t> &ev = evs.e;
     std::vector<double> acc(NL, 0.0);
     for (int it = 0; it < iters; ++it) {
         HIPCK(c, hipEventRecord(ev[0], c->stream));
-        for (int i = 0; i < NL; ++i) { int r = run_layer(c, i, n); if (r) return r; HIPCK(c, hipEventRecord(ev[i + 1], c->stream)); }
+        if (int r = run_layers(c, n, false, &ev)) return r;
         HIPCK(c, hipStreamSynchronize(c->stream));
         for (int i = 0; i < NL; ++i) { float ms = 0; HIPCK(c, hipEventElapsedTime(&ms, ev[i], ev[i + 1])); acc[i] += ms; }
     }
     for (int i = 0; i < NL; ++i) ms_out[i] = (float)(acc[i] / iters);
-    c->last_n = n;
+    forward_done(c, n, false, -1);          // scores_mode is left as it was
     return YOLO_OK;
 }
 
