@@ -312,6 +312,13 @@ int yolo_resolved_tile_configs(const yolo_ctx *ctx, int n, int32_t *out);
 int yolo_op_conv2d(const float *x, int n, int h, int w, int cin, const float *w_hwio, const float *bias,
                    int k, int stride, int cout, int act, const float *residual, float *out,
                    int dtype, int tile_cfg, int device);
+/* ... with an explicit `padding` (darknet's padding= key; yolo_op_conv2d is padding = k / 2): k 1..11, any stride >= 1, out
+ * [n, (h + 2 padding - k) / stride + 1, ..., cout], in fp32, bf16 and fp16; the fp8 and split-fp16 kernels keep k = 1 and 3 with
+ * padding k / 2.  A conv of more than 25 taps runs the tile configurations that have the row / column tap-mask form only: a forced
+ * tile_cfg without it is YOLO_ERR_UNSUPPORTED. */
+int yolo_op_conv2d_pad(const float *x, int n, int h, int w, int cin, const float *w_hwio, const float *bias,
+                       int k, int stride, int padding, int cout, int act, const float *residual, float *out,
+                       int dtype, int tile_cfg, int device);
 int yolo_op_conv_num_cfgs(void);
 int yolo_op_upsample2x(const float *x, int n, int h, int w, int c, int semantics, float *out, int device);
 int yolo_op_reorg(const float *x, int n, int h, int w, int c, int stride, int semantics, float *out, int device);

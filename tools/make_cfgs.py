@@ -355,6 +355,24 @@ def vgg16(size=224, classes=1000):
     return c.text()
 
 
+def alexnet(size=227, classes=1000):
+    """AlexNet (Krizhevsky et al. 2012) as one tower, the way darknet's model zoo spells it: 96 x 11x11 / 4 without padding, 256 x 5x5,
+    384, 384, 256 x 3x3, all with bias and relu, a 3/2 max-pool without padding behind the first, the second and the last conv (227 ->
+    55 -> 27 -> 13 -> 6), then [connected] 4096, 4096 (relu, with dropout) and the classes (linear), [softmax]."""
+    c = Cfg(size)
+    pool = lambda: c._sec("maxpool", size=3, stride=2, padding=0)
+    c._sec("convolutional", filters=96, size=11, stride=4, pad=0, activation="relu"); pool()
+    c.conv(256, 5, bn=False, act="relu"); pool()
+    c.conv(384, 3, bn=False, act="relu")
+    c.conv(384, 3, bn=False, act="relu")
+    c.conv(256, 3, bn=False, act="relu"); pool()
+    c.connected(4096, act="relu"); c.dropout()
+    c.connected(4096, act="relu"); c.dropout()
+    c.connected(classes, act="linear")
+    c.softmax()
+    return c.text()
+
+
 def synthetic_tree(nodes=9418, roots=10, seed=0, max_group=120):
     """A seeded tree in darknet's file format (DN/tree.c:83-139: `name parent` lines, the children of a node one contiguous run, a
     parent below its own index): the reference ships no 9k.tree.  Breadth-first: every run of siblings is appended whole, its size
@@ -454,7 +472,7 @@ def main():
         "darknet19.cfg": darknet19(256), "darknet53.cfg": darknet53(256),
         # cfg/zoo/: classifiers of darknet's model zoo that are no YOLO backbone (cfg/ itself is the set tests/golden/plan_tables.json pins)
         "zoo/resnet18.cfg": resnet(18), "zoo/resnet50.cfg": resnet(50), "zoo/vgg-16.cfg": vgg16(),
-        "zoo/resnext50.cfg": resnext(50),
+        "zoo/resnext50.cfg": resnext(50), "zoo/alexnet.cfg": alexnet(),
     }
     os.makedirs(os.path.join(OUT, "zoo"), exist_ok=True)
     for name, text in files.items():

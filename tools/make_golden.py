@@ -727,6 +727,62 @@ def gen_mini_grouped():
     gen_mini("mini_dw_v3", MINI_DW_V3, 4)
 
 
+def _wconv(filters, size, stride=1, pad="pad=1", bn=True, act="leaky"):
+    return "[convolutional]\n%sfilters=%d\nsize=%d\nstride=%d\n%s\nactivation=%s\n\n" % ("batch_normalize=1\n" if bn else "", filters, size, stride, pad, act)
+
+
+def mini_wide_cfg(width=43, height=35):
+    """A small rectangular, odd-sized classifier of dense convs whose size is neither 1 nor 3: an 11x11 / 4 relu stem without padding and
+    without batch norm on the image (AlexNet's first layer); a 5x5 (the last size one validity bit per tap holds); a 7x7 with a linear
+    epilogue and a leaky [shortcut] from the 5x5 layer behind it; a 6x6 / 2 (even, strided); a 2x2 with padding=0; a 9x9 over a tensor
+    smaller than the filter; a [route] that concatenates the last two (the 9x9 and the 2x2 store into windows of one buffer); a 1x1 to
+    10 classes (the fp32 store), [avgpool], [softmax]."""
+    return ("[net]\nbatch=1\nwidth=%d\nheight=%d\nchannels=3\n\n" % (width, height) + _wconv(16, 11, 4, "pad=0", bn=False, act="relu") +
+            _wconv(16, 5) + _wconv(16, 7, act="linear") + "[shortcut]\nfrom=-2\nactivation=leaky\n\n" +
+            _wconv(24, 6, 2) + _wconv(8, 2, 1, "pad=0\npadding=0") + _wconv(16, 9) + "[route]\nlayers=-1,-2\n\n" +
+            _wconv(10, 1, bn=False, act="linear") + "[avgpool]\n\n[softmax]\ngroups=1\n")
+
+
+def gen_mini_wide():
+    """mini_wide_cfg through the compiled reference, the recipe of gen_mini_grouped: cfg text, weights, three images, every layer's output
+    for each (separate predicts); the class conv scaled until the reference's logits reach +-5.  Asserted: on every image the two largest
+    pooled logits differ by more than twice the bf16 bound."""
+    from oracle import darknet_ref as D
+    from yolo_tensorflow_amd import darknet_io as IO
+    name, width, height, seed = "mini_wide", 43, 35, 73
+    cfg = mini_wide_cfg(width, height)
+    secs = IO.parse_cfg(cfg)
+    flat = IO.synth_weights(secs, seed=seed)
+    last = IO.conv_specs(secs)[-1]
+    tail = last["filters"] * (1 + last["cin"] * last["size"] ** 2)
+    imgs = np.random.default_rng(seed + 1).integers(0, 256, (3, height, width, 3), dtype=np.uint8)
+    x = imgs.astype(np.float32) / np.float32(255.0)
+    logit_layer = len(secs) - 4
+    net = D.RefNet(cfg, flat, 0, 2)
+    net.predict(x[0])
+    factor = np.float32(round(5.0 / float(np.abs(net.layer_output_nhwc(logit_layer)).max()), 2))
+    net.close()
+    flat[-tail:] *= factor
+    net = D.RefNet(cfg, flat, 0, 2)
+    outs = [[] for _ in range(net.n)]
+    for b in range(3):
+        net.predict(x[b])
+        for i in range(net.n):
+            outs[i].append(np.asarray(net.layer_output_nhwc(i), dtype=np.float32).reshape(-1) if secs[i + 1]["type"] in ("avgpool", "softmax") else np.asarray(net.layer_output_nhwc(i), dtype=np.float32)[0])
+    data = {"cfg": np.array(cfg), "weights": flat, "images_u8": imgs, "logit_layer": np.int32(logit_layer)}
+    for i in range(net.n):
+        data["layer_%02d" % i] = np.stack(outs[i])
+    data["max_abs_logit"] = np.float32(np.abs(data["layer_%02d" % logit_layer]).max())
+    pooled = data["layer_%02d" % (net.n - 2)]
+    top2 = np.sort(pooled, axis=-1)[:, -2:]
+    data["top1_margin"] = (top2[:, 1] - top2[:, 0]).astype(np.float32)
+    print(name, "layers", net.n, "max|logit|", float(data["max_abs_logit"]), "pooled max", float(np.abs(pooled).max()), "top-1 margins", data["top1_margin"], "p max", float(data["layer_%02d" % (net.n - 1)].max()))
+    assert float(data["top1_margin"].min()) > 2 * TOL16_BF16 * float(np.abs(pooled).max()), "a top-1 margin below twice the bf16 bound: change the seed, not the rule"
+    net.close()
+    np.savez_compressed(os.path.join(OUT, name + ".npz"), **data)
+    print(name, os.path.getsize(os.path.join(OUT, name + ".npz")), "bytes")
+
+
 def gen_bn_real():
     """D2T/log.txt is the reference's stdout of two detect runs (yolov2 then yolov3) with the printf block of DN/parser.c:1176-1228
     enabled: per batch-normalised conv five lines of numbers (beta, gamma, rolling mean, rolling variance -- l.n values each -- and the
@@ -1023,6 +1079,8 @@ if __name__ == "__main__":
         gen_mini_unet(); sys.exit(0)
     if sys.argv[1:] == ["mini_grouped"]:
         gen_mini_grouped(); sys.exit(0)
+    if sys.argv[1:] == ["mini_wide"]:
+        gen_mini_wide(); sys.exit(0)
     if sys.argv[1:] == ["darknet_py_symbols"]:
         gen_darknet_py_symbols(); sys.exit(0)
     if sys.argv[1:] == ["rect"]:
@@ -1040,6 +1098,7 @@ if __name__ == "__main__":
     gen_mini_resnet()
     gen_mini_unet()
     gen_mini_grouped()
+    gen_mini_wide()
     gen_rect()
     gen_edges()
     gen_bn_real()

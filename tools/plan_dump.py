@@ -22,6 +22,9 @@ sys.path.insert(0, ROOT)
 from yolo_tensorflow_amd import hip, darknet_io as IO  # noqa: E402
 
 FIXTURE = os.path.join(ROOT, "tests", "golden", "plan_dumps.json")
+# cfgs added after the fixture was recorded whose plans the recording commit could not form (it refused dense convs of a size other than 1 and
+# 3): nothing recorded there could pin them, tests/test_wide_host.py pins their geometry instead
+UNPINNED = ("zoo/alexnet", "golden/mini_wide")
 PLANNER_RC = (0, -1, -6)          # YOLO_OK, YOLO_ERR_INVALID, YOLO_ERR_UNSUPPORTED: all build_plan returns for a cfg whose tree file opens
 
 
@@ -39,6 +42,8 @@ def combinations(tmp_dir):
     yield from T.combinations(texts)
     zoo = {"zoo/" + os.path.basename(p)[:-4]: open(p).read() for p in sorted(glob.glob(os.path.join(IO.CFG_DIR, "zoo", "*.cfg")))}
     for name in sorted(zoo):
+        if name in UNPINNED:
+            continue
         for dt in T.DTYPES:
             for keep in (0, 1):
                 for mb in (1, 32):
@@ -48,6 +53,8 @@ def combinations(tmp_dir):
             if "cfg" not in z.files:
                 continue
             text = str(z["cfg"])
+        if "golden/" + os.path.basename(p)[:-4] in UNPINNED:
+            continue
         for dt in T.DTYPES:
             for keep in (0, 1):
                 yield "golden/%s/%s/keep%d/b1" % (os.path.basename(p)[:-4], dt, keep), text, T.DTYPES[dt], 1, keep, None

@@ -88,14 +88,19 @@ using CfgsPairK = CfgList<0, 2, 3, 4, 6, 7, 8, 14, 15, 16, 23, 33, 34, 45, 49, 5
 using CfgsHaloPairK = CfgList<40, 41, 43, 57, 58>;
 // ... and writing PLAIN fp16 (the boundaries of a mixed plan); no halo form
 using CfgsPairKPlain = CfgList<0, 2, 4, 6, 8, 14, 16, 33>;
+// 16-bit storage, convs of more than 25 taps (conv_is_wide): the instantiations with row / column tap masks (WIDE, conv_wide.hip) -- every id
+// conv_default_cfg returns, and the 176-pixel shape
+using CfgsWide16 = CfgList<0, 2, 4, 6, 8, 14, 16>;
 
 template <int... I> constexpr bool cfgs_are(CfgList<I...>, bool halo) { return ((I >= 0 && I < kNumCfgs && kCfgs[I].halo == halo) && ...); }
-static_assert(cfgs_are(Cfgs16{}, false) && cfgs_are(CfgsFp8{}, false) && cfgs_are(CfgsSplit{}, false) && cfgs_are(CfgsPairK{}, false) && cfgs_are(CfgsPairKPlain{}, false), "tiled lists hold tiled ids");
+static_assert(cfgs_are(Cfgs16{}, false) && cfgs_are(CfgsFp8{}, false) && cfgs_are(CfgsSplit{}, false) && cfgs_are(CfgsPairK{}, false) && cfgs_are(CfgsPairKPlain{}, false) && cfgs_are(CfgsWide16{}, false), "tiled lists hold tiled ids");
 static_assert(cfgs_are(CfgsHalo16{}, true) && cfgs_are(CfgsHaloFp8{}, true) && cfgs_are(CfgsHaloSplit{}, true) && cfgs_are(CfgsHaloPairK{}, true), "halo lists hold halo ids");
 
 // is `cfg` instantiated for the storage family of conv `a`
 inline bool conv_cfg_instantiated(const ConvArgs &a, int cfg)
 {
+    // more than 25 taps: only the instantiations with row / column masks read the right taps, and only plain 16-bit storage has them
+    if (conv_is_wide(a)) return (a.in_dt == DT_BF16 || a.in_dt == DT_F16) && !a.split && !a.pairk && CfgsWide16::has(cfg);
     if (a.in_dt == DT_FP8) return CfgsFp8::has(cfg) || CfgsHaloFp8::has(cfg);
     if (a.pairk) return a.split ? CfgsPairK::has(cfg) || CfgsHaloPairK::has(cfg) : CfgsPairKPlain::has(cfg);
     if (a.split) return CfgsSplit::has(cfg) || CfgsHaloSplit::has(cfg);

@@ -241,6 +241,7 @@ hipError_t launch_conv_bf16(const ConvArgs &a, int cfg, hipStream_t s)
     // (16-bit storage: bf16, or fp16 -- the same tile table, the same kernels with the other MFMA and conversions)
     if (a.in_dt != DT_BF16 && a.in_dt != DT_F16) return hipErrorInvalidValue;
     if (a.in_dt == DT_F16 && a.out_dt != DT_F16 && a.out_dt != DT_F32) return hipErrorInvalidValue;
+    if (conv_is_wide(a)) return launch_conv_wide(a, cfg, s);          // more than 25 taps: the row / column mask instantiations or nothing (conv_wide.hip)
     if (cfg == CONV_CFG_DIRECT && a.split) return launch_conv_c8_direct_pair(a, s);      // the first layer of a split-fp16 network: direct kernel (conv_pair.hip)
     if (a.pairk) return launch_conv_pair(a, cfg, s);          // the input is an interleaved pair tensor: the pair K loop (conv_pair.hip, conv_halo13.hip)
     if (a.split) {
@@ -259,7 +260,7 @@ hipError_t launch_conv_bf16(const ConvArgs &a, int cfg, hipStream_t s)
 // fp8 operands: the same tile ids, the kernel on the e4m3 MFMA
 hipError_t launch_conv_fp8(const ConvArgs &a, int cfg, hipStream_t s)
 {
-    if (a.in_dt != DT_FP8) return hipErrorInvalidValue;
+    if (a.in_dt != DT_FP8 || conv_is_wide(a)) return hipErrorInvalidValue;
     if (CfgsHaloFp8::has(cfg)) return launch_conv_halo13(a, cfg, s);
     return cfg_dispatch(CfgsFp8{}, cfg, [&](auto id) { return launch_id<decltype(id)::value, 1>(a, s); });
 }

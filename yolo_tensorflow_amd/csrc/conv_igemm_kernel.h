@@ -145,7 +145,12 @@ constexpr bool halo_div_ok(int bw) { for (unsigned r = 0; r < 256; ++r) if (((r 
 // K-step and accumulator tile THREE products, W_hi x_hi + W_lo x_hi + W_hi x_lo, from the same four fragment reads that feed two in the
 // plain loop.  (Rounds 4-5 stored hi | lo | hi against W_hi | W_hi | W_lo and ran the plain loop over 3 x Cin: 1.5 x the activation bytes,
 // LDS traffic, barriers and waits of this form for the same matrix work.)
-template <int WP, int WC, int TP, int TC, int NS, int BK, bool UNI, int NL = 0, bool DIAG = false, int EB = 2, bool HALO = false, bool FREE = false, bool H16 = false, bool SPLIT = false, int BH = HALO_B, int BW = HALO_B, bool HEADT = false, bool PAIRK = false>
+// WIDE (tiled form only): convs of more than 25 taps (6x6 .. 11x11, CONV_MAX_SIZE).  One bit per tap no longer fits the 32-bit word a row
+// group carries, but validity is separable -- tap (kh, kw) lies inside the image iff row kh and column kw both do -- so the word holds two
+// masks instead: bits 0..15 the rows, bits 16..31 the columns (sizes up to 16).  A K-step asks for the two bits of its tap at once,
+// (mask & need) == need; a K-step past the last tap (K padding) asks for bit 15, which no mask of a size up to CONV_MAX_SIZE holds.
+// The per-lane cursor carries (kh, kw) along with the tap instead of dividing.  Every other instantiation is untouched by the switch.
+template <int WP, int WC, int TP, int TC, int NS, int BK, bool UNI, int NL = 0, bool DIAG = false, int EB = 2, bool HALO = false, bool FREE = false, bool H16 = false, bool SPLIT = false, int BH = HALO_B, int BW = HALO_B, bool HEADT = false, bool PAIRK = false, bool WIDE = false>
 __global__ __launch_bounds__(64 * (WP * WC + NL)) void conv_igemm(const ConvArgs a)
 {
 #if defined(__HIP_DEVICE_COMPILE__)   // the host pass only needs the launch stub (hipcc drops the stub of a
@@ -185,6 +190,7 @@ __global__ __launch_bounds__(64 * (WP * WC + NL)) void conv_igemm(const ConvArgs
     constexpr int FSTAGE = BCL * RB;                            // halo form: bytes of one filter stage
     static_assert(!HALO || LAH <= 9, "a halo tile is fetched during the nine taps of the previous chunk");
     static_assert(!FREE || (HALO && NL == 0 && LB * RG == TC * 16), "free-running form: every wave fetches its own filter rows");
+    static_assert(!WIDE || (!HALO && !PAIRK && !SPLIT && !DIAG && EB == 2), "row / column tap masks: the tiled 16-bit form");
 
     if constexpr (H16) fp16_saturating_mode();
     extern __shared__ __attribute__((aligned(16))) char smem[];   // [NS][ BP rows | BC rows ][128 B]
@@ -294,6 +300,7 @@ __global__ __launch_bounds__(64 * (WP * WC + NL)) void conv_igemm(const ConvArgs
             const bool ok = m < M && prow < BP;
             // (the descriptor base sits `lead` pixels before the tensor, see `shift`)
             rowoff[i] = (unsigned)((m + lead) * a.in_stride) * (unsigned)EB + (UNI ? (unsigned)(chunk * EPC * EB) : 0u);
+            if constexpr (WIDE) tapmask[i] = ok ? 0x10001u : 0u; else
             tapmask[i] = ok ? 1u : 0u;
         }
     }
@@ -312,7 +319,14 @@ __global__ __launch_bounds__(64 * (WP * WC + NL)) void conv_igemm(const ConvArgs
                 const int ox = rem - oy * a.Wo;
                 const int iy0 = oy * a.stride - a.pad, ix0 = ox * a.stride - a.pad;
                 off = (unsigned)(((n * a.H + iy0) * a.W + ix0 + lead) * a.in_stride) * (unsigned)EB;
-                if (a.ksize == 3) {
+                if constexpr (WIDE) {
+                    unsigned ry = 0, cx = 0;
+                    for (int d = 0; d < a.ksize; ++d) {
+                        ry |= ((unsigned)(iy0 + d) < (unsigned)a.H ? 1u : 0u) << d;
+                        cx |= ((unsigned)(ix0 + d) < (unsigned)a.W ? 1u : 0u) << d;
+                    }
+                    mask = ry | (cx << 16);
+                } else if (a.ksize == 3) {
                     unsigned ry = 0, cx = 0;
 #pragma unroll
                     for (int d = 0; d < 3; ++d) {
@@ -345,6 +359,8 @@ __global__ __launch_bounds__(64 * (WP * WC + NL)) void conv_igemm(const ConvArgs
     int v_kc = chunk * EPC, v_tap = 0;                  // !UNI
     if (!UNI)
         while (v_kc >= a.Cin_pad) { v_kc -= a.Cin_pad; ++v_tap; }
+    int v_kh = 0, v_kw = 0;                             // !UNI, WIDE: (kh, kw) of v_tap, stepped with it (no division per K-step)
+    if constexpr (WIDE && !UNI) { v_kh = v_tap / a.ksize; v_kw = v_tap - v_kh * a.ksize; }
     int s_wk = 0;                                       // byte offset of the K-step in a filter row
     auto stage = [&](char *sbase, const bool with_w = true) {
         char *dx = sbase + wid * 1024;
@@ -356,11 +372,19 @@ __global__ __launch_bounds__(64 * (WP * WC + NL)) void conv_igemm(const ConvArgs
             // hit the CU's vector L1 instead of going back to L2 (with tap-outermost order the reuse distance was a whole
             // tap, 4-8 K-steps).
             const unsigned tapbit = s_cb < a.Cin_pad ? 1u << s_tap : 0u;
+            // WIDE: the row bit and the column bit of the tap, both needed; K padding asks for a bit no mask holds (sizes <= 11: bits 11..15 are never set)
+            unsigned need = 0;
+            if constexpr (WIDE) need = s_cb < a.Cin_pad ? (1u << s_kh) | (0x10000u << s_kw) : 0x8000u;
             const int soff = ((s_kh * a.W + s_kw) * a.in_stride + s_cb + s_kb) * EB;
 #pragma unroll
             for (int i = 0; i < LA; ++i) {
+                if constexpr (WIDE) {
+                    const unsigned vo = (tapmask[i] & need) == need ? rowoff[i] : OOB_OFFSET;
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (lds_void *)(dx + i * NW * 1024), 16, vo, soff, 0, 0);
+                } else {
                 const unsigned vo = (tapmask[i] & tapbit) ? rowoff[i] : OOB_OFFSET;
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (lds_void *)(dx + i * NW * 1024), 16, vo, soff, 0, 0);
+                }
             }
             // branch-free cursor update (a branch here would split the K-step into basic blocks and keep the scheduler
             // from placing these loads between the MFMAs)
@@ -373,17 +397,31 @@ __global__ __launch_bounds__(64 * (WP * WC + NL)) void conv_igemm(const ConvArgs
             s_tap = w3 ? 0 : s_tap; s_kh = w3 ? 0 : s_kh; s_cb += w3 ? a.kchunk : 0;
         } else {
             int kh = 0, kw = 0;
+            if constexpr (WIDE) { kh = v_kh; kw = v_kw; }
+            else {
             if (a.ksize == 3) { kh = (v_tap * 11) >> 5; kw = v_tap - kh * 3; }
             else if (a.ksize != 1) { kh = v_tap / a.ksize; kw = v_tap - kh * a.ksize; }
+            }
             const unsigned tapbit = v_tap < KK ? 1u << v_tap : 0u;
+            unsigned need = 0;
+            if constexpr (WIDE) need = v_tap < KK ? (1u << kh) | (0x10000u << kw) : 0x8000u;
             const unsigned delta = (unsigned)((kh * a.W + kw) * a.in_stride + v_kc) * (unsigned)EB;
 #pragma unroll
             for (int i = 0; i < LA; ++i) {
+                if constexpr (WIDE) {
+                    const unsigned vo = (tapmask[i] & need) == need ? rowoff[i] + delta : OOB_OFFSET;
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (lds_void *)(dx + i * NW * 1024), 16, vo, 0, 0, 0);
+                } else {
                 const unsigned vo = (tapmask[i] & tapbit) ? rowoff[i] + delta : OOB_OFFSET;
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (lds_void *)(dx + i * NW * 1024), 16, vo, 0, 0, 0);
+                }
             }
             v_kc += BKE;
+            if constexpr (WIDE) {
+                while (v_kc >= a.Cin_pad) { v_kc -= a.Cin_pad; ++v_tap; ++v_kw; if (v_kw == a.ksize) { v_kw = 0; ++v_kh; } }
+            } else {
             while (v_kc >= a.Cin_pad) { v_kc -= a.Cin_pad; ++v_tap; }
+            }
         }
         if (with_w) {
 #pragma unroll

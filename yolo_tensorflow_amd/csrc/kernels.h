@@ -127,6 +127,15 @@ inline ConvArgs conv_tile_magic(const ConvArgs &a0, int BC, int bh, int bw = 0)
     return a;
 }
 
+// Dense [convolutional] sizes served (bf16, fp16, fp32).  Up to 25 taps (5x5) the tiled 16-bit kernel carries one validity bit per tap; a
+// conv of more taps is WIDE: it runs the instantiations that carry a row mask and a column mask instead (conv_wide.hip)
+#define CONV_MAX_SIZE 11
+inline bool conv_is_wide(const ConvArgs &a) { return a.ksize * a.ksize > 25; }
+inline bool conv_served(int size, int stride, int pad, int h, int w)
+{
+    return size >= 1 && size <= CONV_MAX_SIZE && stride >= 1 && pad >= 0 && h + 2 * pad >= size && w + 2 * pad >= size;
+}
+hipError_t launch_conv_wide(const ConvArgs &a, int cfg, hipStream_t s);          // 16-bit storage, conv_is_wide(a), cfg in CfgsWide16
 // opt a kernel in to more than 64 KiB of dynamic LDS, once per (device, kernel) -- the attribute is per device
 hipError_t conv_opt_in_lds(const void *kernel, size_t lds_bytes);
 // bf16 MFMA implicit-GEMM conv.  cfg in [0, conv_num_cfgs()) (the tile table: conv_cfgs.h); returns hipError.

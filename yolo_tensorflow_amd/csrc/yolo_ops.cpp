@@ -159,16 +159,20 @@ static int op_conv2d_split(const float *x, int n, int h, int w, int cin, const f
 
 int yolo_op_conv_num_cfgs(void) { return conv_num_cfgs(); }
 
-int yolo_op_conv2d(const float *x, int n, int h, int w, int cin, const float *w_hwio, const float *bias, int k, int stride,
-                   int cout, int act, const float *residual, float *out, int dtype, int tile_cfg, int device)
+// the dense conv on host tensors with an explicit padding (yolo_op_conv2d: padding = k / 2): k 1..CONV_MAX_SIZE in fp32, bf16 and fp16; the
+// e4m3 and split-fp16 kernels keep k = 1 and 3 with padding k / 2
+static int op_conv2d_any(const float *x, int n, int h, int w, int cin, const float *w_hwio, const float *bias, int k, int stride, int padding,
+                         int cout, int act, const float *residual, float *out, int dtype, int tile_cfg, int device)
 {
-    if (!x || !w_hwio || !out || n < 1 || (k != 1 && k != 3) || stride < 1) { g_op_err = "conv2d: bad arguments"; return YOLO_ERR_INVALID; }
+    if (!x || !w_hwio || !out || n < 1 || h < 1 || w < 1 || cin < 1 || cout < 1) { g_op_err = "conv2d: bad arguments"; return YOLO_ERR_INVALID; }
+    if (!conv_served(k, stride, padding, h, w)) { g_op_err = "conv2d: served are 1 <= size <= " + std::to_string(CONV_MAX_SIZE) + ", stride >= 1, padding >= 0 and a filter no larger than the padded input"; return YOLO_ERR_UNSUPPORTED; }
+    if ((dtype == YOLO_FP16X2 || dtype == YOLO_FP8) && ((k != 1 && k != 3) || padding != k / 2)) { g_op_err = "conv2d: the fp8 and split-fp16 configurations serve sizes 1 and 3 with padding size / 2 only"; return YOLO_ERR_UNSUPPORTED; }
     if (dtype == YOLO_FP16X2) return op_conv2d_split(x, n, h, w, cin, w_hwio, bias, k, stride, cout, act, residual, out, tile_cfg, device);
     OpScope S(device); if (S.rc) { g_op_err = "conv2d: no HIP device"; return S.rc; }
     // dtype YOLO_FP8: x, residual and the result are e4m3 tensors of scale 1 (the inputs are quantised here first)
     const bool f32 = dtype == YOLO_FP32; const int dt = f32 ? DT_F32 : dtype == YOLO_FP8 ? DT_FP8 : dtype == YOLO_FP16 ? DT_F16 : DT_BF16; const size_t es = dt_size(dt);
     const int gr = dt == DT_FP8 ? 16 : 8;
-    Layer L; L.type = L_CONV; L.filters = cout; L.size = k; L.stride = stride; L.pad = k / 2; L.bn = 0; L.act = act; L.in_dt = dt;
+    Layer L; L.type = L_CONV; L.filters = cout; L.size = k; L.stride = stride; L.pad = padding; L.bn = 0; L.act = act; L.in_dt = dt;
     L.cin = cin; L.cin_pad = roundup(cin, gr); L.kpad = roundup(k * k * L.cin_pad, dt == DT_FP8 ? 128 : 64); L.cout_pad = roundup(cout, 256);
     const int ho = (h + 2 * L.pad - k) / stride + 1, wo = (w + 2 * L.pad - k) / stride + 1;
     // HWIO -> OIHW for the common packer
@@ -201,6 +205,7 @@ int yolo_op_conv2d(const float *x, int n, int h, int w, int cin, const float *w_
     conv_finalize(a);
     const int cfg = tile_cfg >= 0 ? tile_cfg : conv_default_cfg(a);
     if (conv_cfg_is_halo(cfg) && (f32 || !conv_cfg_runs(a, cfg))) { g_op_err = "conv2d: tile config not applicable to this shape (halo-staged form: 3x3, stride 1, size a multiple of 13, whole channel chunks)"; return YOLO_ERR_UNSUPPORTED; }
+    if (!f32 && conv_is_wide(a) && !conv_cfg_runs(a, cfg)) { g_op_err = "conv2d: tile config " + std::to_string(cfg) + " has no form for convs of more than 25 taps (row / column tap masks)"; return YOLO_ERR_UNSUPPORTED; }
     hipError_t e;
     if (dt != DT_F32 && dt != DT_F16 && getenv("YOLO_CONV_DIAG") && a.Cin_pad % (dt == DT_FP8 ? 128 : 64) == 0) {
         // developer diagnostic: phase cycle sums of the stamped p176c128_s2 build (YOLO_CONV_DIAG=free: of the free-running halo form
@@ -241,6 +246,18 @@ int yolo_op_conv2d(const float *x, int n, int h, int w, int cin, const float *w_
     S.download(out, d_o32, (size_t)n * ho * wo * cout * 4);
     if (S.rc) g_op_err = "conv2d: " + std::string(hipGetErrorString(hipGetLastError()));
     return S.rc;
+}
+
+int yolo_op_conv2d(const float *x, int n, int h, int w, int cin, const float *w_hwio, const float *bias, int k, int stride,
+                   int cout, int act, const float *residual, float *out, int dtype, int tile_cfg, int device)
+{
+    return op_conv2d_any(x, n, h, w, cin, w_hwio, bias, k, stride, k / 2, cout, act, residual, out, dtype, tile_cfg, device);
+}
+
+int yolo_op_conv2d_pad(const float *x, int n, int h, int w, int cin, const float *w_hwio, const float *bias, int k, int stride, int padding,
+                       int cout, int act, const float *residual, float *out, int dtype, int tile_cfg, int device)
+{
+    return op_conv2d_any(x, n, h, w, cin, w_hwio, bias, k, stride, padding, cout, act, residual, out, dtype, tile_cfg, device);
 }
 
 // darknet's [deconvolutional] on host tensors: x [n,h,w,cin] fp32 NHWC, w_iohw [cin][cout][size][size] (the order of darknet's weight files), bias

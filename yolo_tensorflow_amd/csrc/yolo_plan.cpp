@@ -145,10 +145,18 @@ static int parse_convolutional(Cursor &k, const Section &s, Layer &L)
 {
     if (opt_i(s, "groups", 1) != 1) return parse_grouped_conv(k, s, L);
     yolo_ctx *c = k.c; const int i = k.i;
+    // (the variable: A/B of the dense kernels against the grouped kernel run with one group, tools/wide_conv_rate.py -- wherever that kernel serves the layer)
+    if (getenv("YOLO_DENSE_AS_GROUPED") && i > 0 && opt_i(s, "size", 1) > 3 && opt_i(s, "size", 1) <= GCONV_MAX_SIZE && c->dtype != YOLO_FP8 && !c->split()) return parse_grouped_conv(k, s, L);
     L.type = L_CONV; read_conv_keys(s, L);
     if (int r = plan_activation(c, i, s, "logistic", false)) return r;
     if (L.size == 7 && L.stride == 2 && L.pad == 3 && i == 0 && k.C == 3 && k.H % 2 == 0 && k.W % 2 == 0 && c->dtype != YOLO_FP8) L.s2d7 = true;
-    else if (L.size != 1 && L.size != 3) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: conv size %d unsupported on the device path", i, L.size);
+    else if (L.size != 1 && L.size != 3) {
+        // any size 1..CONV_MAX_SIZE in bf16, fp16 and fp32 (up to 25 taps: one validity bit per tap; more: row / column masks, conv_wide.hip;
+        // fp32: per-tap bounds tests).  The e4m3 kernels and the pair K loop (uniform taps only) keep sizes 1 and 3
+        if (c->dtype == YOLO_FP8) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: conv size %d unsupported on the device path", i, L.size);
+        if (L.size < 1 || L.size > CONV_MAX_SIZE) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: conv size %d (1..%d are served)", i, L.size, CONV_MAX_SIZE);
+        if (c->split()) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: conv size %d is not served in the split-fp16 configuration (sizes 1 and 3, and a 7x7 / stride 2 first layer)", i, L.size);
+    }
     // padding= is taken literally when pad=0, and any stride: the tiled kernels serve both; what has no output pixel is refused
     if (L.filters < 1) return fail(c, YOLO_ERR_INVALID, "layer %d: conv filters %d", i, L.filters);
     if (L.stride < 1 || L.pad < 0) return fail(c, YOLO_ERR_INVALID, "layer %d: conv stride %d, padding %d", i, L.stride, L.pad);

@@ -3,8 +3,8 @@
 #include "yolo_ctx.h"
 #include "conv_cfgs.h"
 
-template <int... I> static constexpr bool in_every_family(CfgList<I...>) { return ((Cfgs16::has(I) && CfgsFp8::has(I) && CfgsSplit::has(I) && CfgsPairK::has(I) && CfgsPairKPlain::has(I)) && ...); }
-static_assert(in_every_family(CfgList<0, 2, 4, 6, 8, 14>{}), "every id conv_default_cfg returns is instantiated for every storage family");
+template <int... I> static constexpr bool in_every_family(CfgList<I...>) { return ((Cfgs16::has(I) && CfgsFp8::has(I) && CfgsSplit::has(I) && CfgsPairK::has(I) && CfgsPairKPlain::has(I) && CfgsWide16::has(I)) && ...); }
+static_assert(in_every_family(CfgList<0, 2, 4, 6, 8, 14>{}), "every id conv_default_cfg returns is instantiated for every storage family, and with row / column tap masks (a conv of more than 25 taps runs no other form)");
 
 int conv_default_cfg(const ConvArgs &a)
 {

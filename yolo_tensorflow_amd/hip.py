@@ -47,7 +47,7 @@ EXPORTS = [
     "yolo_set_hier_thresh", "yolo_set_hierarchy_mode", "yolo_darknet_boxes_map", "yolo_tree_geometry", "yolo_tree_read", "yolo_plan_check", "yolo_plan_table", "yolo_plan_dump",
     "yolo_op_tree_softmax", "yolo_op_tree_top", "yolo_activation_code", "yolo_op_activate", "yolo_op_shortcut",
     "yolo_output_map_geometry", "yolo_output_map", "yolo_label_map", "yolo_segment_images_u8", "yolo_op_deconv2d", "yolo_op_l2norm", "yolo_op_upsample", "yolo_op_label_map",
-    "yolo_op_conv2d_grouped",
+    "yolo_op_conv2d_grouped", "yolo_op_conv2d_pad",
 ]
 HIER_CONDITIONAL, HIER_ABSOLUTE, HIER_LEAVES = 0, 1, 2
 _HIER_MODES = {None: HIER_CONDITIONAL, "conditional": HIER_CONDITIONAL, "absolute": HIER_ABSOLUTE, "leaves": HIER_LEAVES}
@@ -109,6 +109,7 @@ def load_library():
     l.yolo_set_tile_configs.argtypes = [P, P]
     l.yolo_resolved_tile_configs.argtypes = [P, I, P]
     l.yolo_op_conv2d.argtypes = [P, I, I, I, I, P, P, I, I, I, I, P, P, I, I, I]
+    l.yolo_op_conv2d_pad.argtypes = [P, I, I, I, I, P, P, I, I, I, I, I, P, P, I, I, I]
     l.yolo_op_conv_num_cfgs.argtypes = []
     l.yolo_op_upsample2x.argtypes = [P, I, I, I, I, I, P, I]
     l.yolo_op_reorg.argtypes = [P, I, I, I, I, I, I, P, I]
@@ -677,16 +678,25 @@ def _f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
 
 
-def op_conv2d(x, w_hwio, bias=None, stride=1, act=0, residual=None, dtype=BF16, tile_cfg=-1, device=0):
+def op_conv2d(x, w_hwio, bias=None, stride=1, act=0, residual=None, dtype=BF16, tile_cfg=-1, device=0, padding=None):
+    """the dense conv on host tensors: x [n, h, w, cin], w_hwio [k, k, cin, cout], k 1..11.  padding=None: k // 2 (darknet's pad=1); an
+    explicit padding, or a k other than 1 and 3, goes through yolo_op_conv2d_pad"""
     l = load_library()
     x = _f32(x); w = _f32(w_hwio)
     n, h, wd, cin = x.shape
     k, _, _, cout = w.shape
-    pad = k // 2
+    pad = k // 2 if padding is None else int(padding)
     ho, wo = (h + 2 * pad - k) // stride + 1, (wd + 2 * pad - k) // stride + 1
+    if ho < 1 or wo < 1 or pad < 0:
+        raise YoloError("op_conv2d: a %d x %d filter with padding %d over a %d x %d input leaves no output pixel" % (k, k, pad, wd, h))
     out = np.empty((n, ho, wo, cout), dtype=np.float32)
     b = _f32(bias) if bias is not None else None
     r = _f32(residual) if residual is not None else None
+    if padding is not None or k not in (1, 3):
+        rc = l.yolo_op_conv2d_pad(x.ctypes.data, n, h, wd, cin, w.ctypes.data, b.ctypes.data if b is not None else None, k, stride, pad,
+                                  cout, act, r.ctypes.data if r is not None else None, out.ctypes.data, dtype, tile_cfg, device)
+        _op_check(rc, "yolo_op_conv2d_pad")
+        return out
     rc = l.yolo_op_conv2d(x.ctypes.data, n, h, wd, cin, w.ctypes.data, b.ctypes.data if b is not None else None, k, stride,
                           cout, act, r.ctypes.data if r is not None else None, out.ctypes.data, dtype, tile_cfg, device)
     _op_check(rc, "yolo_op_conv2d")
