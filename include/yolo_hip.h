@@ -269,6 +269,21 @@ int yolo_detect_graph(yolo_ctx *ctx, const void *images, int n, int fmt, float s
 
 int yolo_synchronize(yolo_ctx *ctx);
 
+/* ---- recurrent networks: [rnn] / [gru] / [lstm] layers carry state from one call to the next ---------------------
+ * One yolo_forward* / yolo_detect* / yolo_classify* call is ONE TIME STEP (darknet after set_batch_network(net, 1) with
+ * time_steps=1): batch index b of every call is stream b, a call with n images advances streams 0 .. n-1 and leaves streams
+ * n .. max_batch-1 as they were.  Every state is zero at yolo_create and is no part of an export artifact.  A call that is
+ * refused changes no state; yolo_time_forward / yolo_time_layers / yolo_autotune hand the states back as they found them; the
+ * captured steps (yolo_detect_graph, yolo_detect_images_graph) hold the state update.  The state tensors are numbered in layer
+ * order: an [rnn] or [gru] layer has one (its state, `output` floats per stream), an [lstm] layer two (h, then the cell c).
+ * Values are exchanged as fp32: h of an [rnn] / [lstm] is kept in the network's storage type (it is a matrix operand), so
+ * yolo_set_state rounds it as the kernels do and yolo_get_state -> yolo_set_state reproduces the next step bit for bit. */
+int yolo_num_state_tensors(const yolo_ctx *ctx);                 /* 0: the network is a pure function of the batch */
+int yolo_state_geometry(const yolo_ctx *ctx, int k, int *layer, size_t *floats_per_stream);
+int yolo_get_state(yolo_ctx *ctx, int k, int stream, float *out, size_t out_floats);        /* host fp32, exactly floats_per_stream */
+int yolo_set_state(yolo_ctx *ctx, int k, int stream, const float *in, size_t in_floats);
+int yolo_reset_state(yolo_ctx *ctx, int stream);                 /* darknet's reset_network_state(net, b); stream < 0: every stream */
+
 /* ---- introspection / measurement ------------------------------------------------------------ */
 /* Copies layer `index`'s output of the last forward as fp32 NHWC [n,H,W,C] to host (needs
  * keep_layers=1; without it only a conv layer's own tensor that still sits in its buffer after the

@@ -106,6 +106,23 @@ class Cfg:
             kv["temperature"] = temperature
         return self._sec("softmax", **kv)
 
+    def crnn(self, hidden, output, act="leaky", bn=True, shortcut=False):          # DN/parser.c:207-220
+        kv = {"batch_normalize": 1} if bn else {}
+        kv.update(hidden_filters=hidden, output_filters=output, activation=act)
+        if shortcut:
+            kv["shortcut"] = 1
+        return self._sec("crnn", **kv)
+
+    def gru(self, output, tanh=True, bn=False):                                      # DN/parser.c:236-245
+        kv = {"batch_normalize": 1} if bn else {}
+        kv.update(output=output, tanh=int(tanh))
+        return self._sec("gru", **kv)
+
+    def lstm(self, output, bn=False):                                                # DN/parser.c:247-255
+        kv = {"batch_normalize": 1} if bn else {}
+        kv.update(output=output)
+        return self._sec("lstm", **kv)
+
     def cost(self):
         return self._sec("cost")        # (type defaults to sse, DN/parser.c:419)
 
@@ -175,6 +192,42 @@ def yolov3_tiny(size=416, classes=80):
     c.route(route_2); c.conv(128, 1); up = c.upsample(); c.route(up, route_1)
     c.conv(256, 3)
     c.conv(nout, 1, bn=False, act="linear"); c.yolo([0, 1, 2], V3_TINY_ANCHORS, classes)
+    return c.text()
+
+
+def yolov3_tiny_video(size=416, classes=80, recurrent=True):
+    """yolov3-tiny with a [crnn] ahead of each head: the detector keeps a state map per head from frame to frame (recurrent=False: the
+    same network with a 3x3 conv in the [crnn]'s place, for rate comparisons)"""
+    c = Cfg(size)
+    for f in (16, 32, 64, 128):
+        c.conv(f, 3); c.maxpool()
+    route_1 = c.conv(256, 3)
+    c.maxpool()
+    c.conv(512, 3)
+    c.maxpool(2, 1)
+    c.conv(1024, 3)
+    route_2 = c.conv(256, 1)
+    c.conv(512, 3)
+    c.crnn(256, 512) if recurrent else c.conv(512, 3)
+    nout = 3 * (5 + classes)
+    c.conv(nout, 1, bn=False, act="linear"); c.yolo([3, 4, 5], V3_TINY_ANCHORS, classes)
+    c.route(route_2); c.conv(128, 1); up = c.upsample(); c.route(up, route_1)
+    c.conv(256, 3)
+    c.crnn(128, 256) if recurrent else c.conv(256, 3)
+    c.conv(nout, 1, bn=False, act="linear"); c.yolo([0, 1, 2], V3_TINY_ANCHORS, classes)
+    return c.text()
+
+
+def darknet19_video(size=256, classes=1000, recurrent=True):
+    """darknet19's features, pooled, then a [gru] of 1024 units over the frames of a stream, a [connected] layer to the classes and
+    [softmax] (the per-frame features + recurrent layer of the reference's examples/rnn_vid.c); recurrent=False: without the [gru]"""
+    c = Cfg(size)
+    darknet19_backbone(c)
+    c.avgpool()
+    if recurrent:
+        c.gru(1024)
+    c.connected(classes, act="linear")
+    c.softmax()
     return c.text()
 
 
@@ -441,6 +494,15 @@ def main():
         with open(os.path.join(sys.argv[2], "unet.cfg"), "w") as f:
             f.write(unet() + "\n")
         print("wrote unet.cfg to", sys.argv[2])
+        return
+    if len(sys.argv) > 2 and sys.argv[1] == "--video":         # python tools/make_cfgs.py --video DIR: the two recurrent cfgs of the rate measurements and their twins without the recurrent layers
+        os.makedirs(sys.argv[2], exist_ok=True)
+        files = {"yolov3-tiny-crnn.cfg": yolov3_tiny_video(), "yolov3-tiny-conv.cfg": yolov3_tiny_video(recurrent=False),
+                 "darknet19-gru.cfg": darknet19_video(), "darknet19-fc.cfg": darknet19_video(recurrent=False)}
+        for name, text in files.items():
+            with open(os.path.join(sys.argv[2], name), "w") as f:
+                f.write(text + "\n")
+        print("wrote", ", ".join(files), "to", sys.argv[2])
         return
     if len(sys.argv) > 2 and sys.argv[1] == "--dw-yolo":       # python tools/make_cfgs.py --dw-yolo DIR: dw-yolo.cfg, a depthwise-separable yolov3-tiny
         os.makedirs(sys.argv[2], exist_ok=True)

@@ -30,6 +30,10 @@ Runs only in the build container (it reads /root/reference and oracle/_ref); the
                     the layers that move data and the dense conv's geometry keys at ragged channel counts (a map network, 15 high x 22
                     wide: pad=0, padding=2, stride 3, five max-pool geometries, reorg, a concatenation at channel offset 20): three
                     images, every layer's output from the compiled reference; written with fixed member dates, so it regenerates byte for byte
+  mini_seq.npz / mini_crnn.npz
+                    recurrent networks ([rnn], [gru], [lstm] behind a conv stack, a classifier; two [crnn] layers in front of a [yolo] head):
+                    ONE live network of the compiled reference over 5 frames, every layer's output after each frame (mini_crnn: the boxes too), and
+                    drift16_*: the stand-off of the 16-bit-rounded host restatement (tests/test_recurrent_host.py) per frame and layer
   yolov3_bn_real.npz / yolov2_bn_real.npz
                      the COMPLETE batch-norm vectors (beta, gamma, rolling mean, rolling variance) of every
                      batch-normalised conv of yolov3.weights / yolov2.weights, and the first l.n filter
@@ -1061,6 +1065,123 @@ def gen_edges():
     print(name, "layers", len(shapes), "map", data["layer_%02d" % (len(shapes) - 1)].shape[1:], "max_abs", np.round(data["max_abs"], 3).tolist(), os.path.getsize(path), "bytes")
 
 
+def mini_seq_cfg():
+    """Recurrent layers behind a small conv stack: 32 x 32 x 3 -> 4 x 4 x 16 -> [connected] 64, then two [rnn] (batch-normalised leaky; logistic with
+    shortcut=1), two [gru] (batch-normalised with tanh=1; plain), two [lstm] (batch-normalised; plain), a batch-normalised [connected] to 10
+    classes and [softmax]."""
+    return ("[net]\nbatch=1\nwidth=32\nheight=32\nchannels=3\ntime_steps=1\n\n" + _conv(8, 3, 2) + "[maxpool]\nsize=2\nstride=2\n\n" + _conv(16, 3, 2) +
+            "[connected]\noutput=64\nactivation=leaky\n\n"
+            "[rnn]\noutput=40\nactivation=leaky\nbatch_normalize=1\n\n[rnn]\noutput=40\nshortcut=1\n\n"
+            "[gru]\noutput=48\ntanh=1\nbatch_normalize=1\n\n[gru]\noutput=24\n\n"
+            "[lstm]\noutput=40\nbatch_normalize=1\n\n[lstm]\noutput=24\n\n"
+            "[connected]\noutput=10\nbatch_normalize=1\nactivation=linear\n\n[softmax]\n")
+
+
+def mini_crnn_cfg():
+    """A detector with temporal context: 32 x 32 x 3 -> 3x3/2 conv -> 2x2 max-pool (8 x 8) -> a batch-normalised leaky [crnn] whose 20 hidden channels are
+    no multiple of 8 -> a relu [crnn] with shortcut=1 -> a linear 1x1 conv to 18 channels -> [yolo] with one class and three anchors.
+    In front of all that stands one 3x3/1 conv at full size, for the reference's sake: darknet sizes the im2col workspace all layers share from
+    the layers' own workspace_size, make_crnn_layer sets none, and the [crnn] convs' 46 KB columns would overrun the 27 KB the 3x3/2 conv over
+    3 channels asks for (the reference then corrupts its heap); a 32 x 32 conv asks for 110 KB."""
+    return ("[net]\nbatch=1\nwidth=32\nheight=32\nchannels=3\ntime_steps=1\n\n" + _conv(8, 3) + _conv(8, 3, 2) + "[maxpool]\nsize=2\nstride=2\n\n"
+            "[crnn]\nhidden_filters=20\noutput_filters=24\nactivation=leaky\nbatch_normalize=1\n\n"
+            "[crnn]\nhidden_filters=16\noutput_filters=16\nactivation=relu\nshortcut=1\n\n" + _conv(18, 1, bn=False, act="linear") +
+            "[yolo]\nmask=0,1,2\nanchors=4,5,  8,6,  10,14\nclasses=1\nnum=3\n")
+
+
+def gen_recurrent(seed=93):
+    gen_mini_seq(seed)
+    gen_mini_crnn()
+
+
+def gen_mini_crnn(seed=57, thresh=0.7):
+    """mini_crnn_cfg through the compiled reference (crnn_layer.c): one live network over T = 5 frames, every layer's output and the boxes
+    get_network_boxes returns after each of them; drift16_* as in mini_seq.npz."""
+    import importlib.util
+    from oracle import darknet_ref as D
+    from yolo_tensorflow_amd import darknet_io as IO
+    spec = importlib.util.spec_from_file_location("test_recurrent_host", os.path.join(ROOT, "tests", "test_recurrent_host.py"))
+    sys.path.insert(0, os.path.join(ROOT, "tests")); RH = importlib.util.module_from_spec(spec); spec.loader.exec_module(RH)
+    name, cfg, steps = "mini_crnn", mini_crnn_cfg(), 5
+    secs = IO.parse_cfg(cfg)
+    flat = IO.synth_weights(secs, seed=seed, obj_bias=0.5)
+    imgs = np.random.default_rng(seed + 1).integers(0, 256, (steps, 32, 32, 3), dtype=np.uint8)
+    x = imgs.astype(np.float32) / np.float32(255.0)
+    shapes = IO.layer_shapes(secs)
+    net = D.RefNet(cfg, flat, 0, 2)
+    outs = [[] for _ in range(net.n)]
+    data = {"cfg": np.array(cfg), "weights": flat, "images_u8": imgs, "thresh": np.float32(thresh)}
+    for t in range(steps):
+        net.predict(x[t])
+        for i in range(net.n):
+            outs[i].append(np.asarray(net.layer_output_nhwc(i), dtype=np.float32).reshape(-1))
+        bb, obj, pr = net.boxes(thresh, None, 1)
+        data["boxes_%d" % t], data["obj_%d" % t], data["prob_%d" % t] = bb, obj, pr
+    net.close()
+    for i, o in enumerate(outs):
+        o = np.stack(o); assert np.isfinite(o).all()
+        data["layer_%02d" % i] = o.reshape((steps,) + tuple(shapes[i][1:4])) if secs[i + 1]["type"] != "yolo" else o
+    nl = len(outs) - 1          # (the [yolo] layer's own output is the reference's activated copy: not compared)
+    for tag, store in (("bf16", RH.bf16), ("fp16", RH.fp16)):
+        sim = RH.run_frames(cfg, flat, imgs, store)
+        data["drift16_" + tag] = np.array([[RH.standoff(sim[t][i], data["layer_%02d" % i][t]) for i in range(nl)] for t in range(steps)], dtype=np.float64)
+    exact = RH.run_frames(cfg, flat, imgs)
+    worst = max(RH.standoff(exact[t][i], data["layer_%02d" % i][t]) for t in range(steps) for i in range(nl))
+    path = os.path.join(OUT, name + ".npz")
+    save_npz_reproducibly(path, data)
+    print(name, "layers", len(outs), "boxes per frame", [len(data["boxes_%d" % t]) for t in range(steps)], "restatement stand-off %.2e" % worst,
+          "drift bf16 %.3g fp16 %.3g" % (data["drift16_bf16"].max(), data["drift16_fp16"].max()), os.path.getsize(path), "bytes")
+
+
+def gen_mini_seq(seed=93):
+    """mini_seq_cfg through the compiled reference (rnn_layer.c, gru_layer.c, lstm_layer.c, connected_layer.c with batch norm): ONE network kept
+    alive over T = 5 distinct frames, every layer's output after each of them, the top class per frame.  drift16_bf16 / drift16_fp16 [T][layers]:
+    how far the host restatement (tests/test_recurrent_host.py) stands off from those outputs, as a share of each tensor's largest value, when
+    it rounds operands and stored tensors to that type where the device does -- the yardstick of the 16-bit device tests at steps 2..5."""
+    import importlib.util
+    from oracle import darknet_ref as D
+    from yolo_tensorflow_amd import darknet_io as IO
+    spec = importlib.util.spec_from_file_location("test_recurrent_host", os.path.join(ROOT, "tests", "test_recurrent_host.py"))
+    sys.path.insert(0, os.path.join(ROOT, "tests")); RH = importlib.util.module_from_spec(spec); spec.loader.exec_module(RH)
+    name, cfg, steps = "mini_seq", mini_seq_cfg(), 5
+    secs = IO.parse_cfg(cfg)
+    flat = IO.synth_weights(secs, seed=seed)
+    imgs = np.random.default_rng(seed + 1).integers(0, 256, (steps, 32, 32, 3), dtype=np.uint8)
+    x = imgs.astype(np.float32) / np.float32(255.0)
+    # the class layer's rows are scaled until the reference's logits reach +-4 over the sequence: the probabilities must not be near-uniform
+    last = IO.conv_specs(secs)[-1]
+    tail = IO.connected_floats(last["cin"], last["filters"], 1)
+    def run(weights):
+        net = D.RefNet(cfg, weights, 0, 2)
+        outs = [[] for _ in range(net.n)]
+        for t in range(steps):
+            net.predict(x[t])
+            for i in range(net.n):
+                outs[i].append(np.asarray(net.layer_output_nhwc(i), dtype=np.float32).reshape(-1))
+        net.close()
+        return [np.stack(o) for o in outs]
+    logits = run(flat)[-2]
+    nw = last["filters"] * last["cin"]
+    flat[-tail + last["filters"]:-tail + last["filters"] + nw] *= np.float32(round(4.0 / float(np.abs(logits).max()), 2))      # (the rows; batch norm renormalises them unless the variance is kept)
+    flat[-last["filters"]:] *= np.float32(0.05)          # ... so the rolling variance is shrunk with them
+    outs = run(flat)
+    shapes = IO.layer_shapes(secs)
+    data = {"cfg": np.array(cfg), "weights": flat, "images_u8": imgs}
+    for i, o in enumerate(outs):
+        data["layer_%02d" % i] = o.reshape((steps,) + tuple(shapes[i][1:4]))          # (layer_output_nhwc: image-shaped layers come as HWC; the rest are 1 x 1 x C)
+        assert np.isfinite(o).all()
+    data["top"] = np.argmax(outs[-1], axis=1).astype(np.int32)
+    for tag, store in (("bf16", RH.bf16), ("fp16", RH.fp16)):
+        sim = RH.run_frames(cfg, flat, imgs, store)
+        data["drift16_" + tag] = np.array([[RH.standoff(sim[t][i], data["layer_%02d" % i][t]) for i in range(len(outs))] for t in range(steps)], dtype=np.float64)
+    exact = RH.run_frames(cfg, flat, imgs)
+    worst = max(RH.standoff(exact[t][i], data["layer_%02d" % i][t]) for t in range(steps) for i in range(len(outs)))
+    path = os.path.join(OUT, name + ".npz")
+    save_npz_reproducibly(path, data)
+    print(name, "layers", len(outs), "top", data["top"].tolist(), "p max", np.round(outs[-1].max(axis=1), 3).tolist(), "restatement stand-off %.2e" % worst,
+          "drift bf16 %.3g fp16 %.3g" % (data["drift16_bf16"].max(), data["drift16_fp16"].max()), os.path.getsize(path), "bytes")
+
+
 def gen_rect():
     gen_mini_rect("mini_v3_rect", MINI_V3, 4, 64, 96, letterbox=True)
     gen_mini_rect("mini_v2_rect", MINI_V2, 5, 96, 64)
@@ -1087,6 +1208,8 @@ if __name__ == "__main__":
         gen_rect(); sys.exit(0)
     if sys.argv[1:] == ["edges"]:
         gen_edges(); sys.exit(0)
+    if sys.argv[1:] == ["recurrent"]:
+        gen_recurrent(); sys.exit(0)
     stub_modules()
     gen_nms_v3()
     gen_v2_post()
@@ -1101,6 +1224,7 @@ if __name__ == "__main__":
     gen_mini_wide()
     gen_rect()
     gen_edges()
+    gen_recurrent()
     gen_bn_real()
     gen_known_answers()
     gen_darknet_py_symbols()

@@ -90,7 +90,11 @@ network *load_network(char *cfg, char *weights, int clear)
 void free_network(network *net) { if (!net) return; if (net->ctx) yolo_destroy(net->ctx); delete net; }
 int network_width(network *net) { return net ? net->w : 0; }
 int network_height(network *net) { return net ? net->h : 0; }
-void reset_rnn(network *net) { (void)net; }                                          /* DN/network.c:85: no recurrent state here */
+// network_predict carries the state of [crnn] / [rnn] / [gru] / [lstm] layers from call to call by itself (one call, one time step); these zero it.
+// (Both go through a file-local function: a process that also holds libdarknet itself resolves an exported name to whichever library came first)
+static void reset_stream(network *net, int b) { if (net && net->ctx && yolo_reset_state(net->ctx, b) != YOLO_OK) fprintf(stderr, "darknet_hip: %s\n", yolo_last_error(net->ctx)); }
+void reset_network_state(network *net, int b) { reset_stream(net, b); }              /* DN/network.c:69 */
+void reset_rnn(network *net) { reset_stream(net, 0); }                               /* DN/network.c:85 */
 
 // DN/network.c:339-356 resizes every layer for `b` images; here the plan is rebuilt for that batch (weights are re-read)
 void set_batch_network(network *net, int b)

@@ -313,6 +313,42 @@ inline bool gconv_served(int size, int stride, int pad, int h, int w)
 // 16-bit operands: v_mfma_f32_16x16x32_{bf16,f16} over the bundles, fp32 accumulators; fp32 operands: plain FMAs over the group's own channels
 hipError_t launch_gconv(const GConvArgs &a, hipStream_t s);
 
+// ---- recurrent layers [rnn] / [gru] / [lstm] (rnn_ops.hip): the stacked gate GEMM with the gate arithmetic in its epilogue ----------
+// One launch computes acc[row][stream] = W[row][:] . [x | h][stream][:] for every row of a layer's stacked weight matrix and every stream
+// (batch index) of the call, then the step arithmetic of `mode` on the accumulators.  The WEIGHTS are the MFMA A operand, the G gates of
+// one unit interleaved along M (row = unit * G + gate), so the four consecutive rows a lane's accumulator holds ((lane >> 4) * 4 + j,
+// column lane & 15) are all gates of one unit (G = 4), of two units (G = 2) or four units (G = 1): the epilogue needs no exchange.  The
+// activations [x | h] are the B operand, concatenated along K: Kx = roundup(x_len, 32) columns of x, then Kh = roundup(h_len, 32) of h; a
+// column at or past x_len / h_len reads as zero.  The products over x and over h are kept in two accumulators (an [rnn] activates each
+// before the sum; the gates add them, as the reference adds the two sublayers' outputs); bx / bh [Mp] are their biases (batch norm folded).
+// w is stored in fragment order, [M tile][K step][lane][8]: element j of lane l in K step kk of M tile mt is W[mt * 16 + (l & 15)][kk * 32 +
+// (l >> 4) * 8 + j] (recur_pack_index) -- a wave's load of one A fragment is one contiguous piece, 16-bit or fp32 alike (the fp32 kernel
+// contracts k = (l >> 4) * 8 + j in its j-th v_mfma_f32_16x16x4_f32).  Four waves of a workgroup split the K steps and reduce through LDS.
+// Modes (u: unit, n: stream; sig the logistic function; state tensors [max_batch][s_stride], the columns past `units` stay zero):
+//   RK_RNN_STATE  G 1  h_new[n][u] = (shortcut ? h[n][u] : 0) + act(x-part + bx) + act(h-part + bh)                 (storage type)
+//   RK_DENSE      G 1  out[n][u] = act(x-part + bx): the [rnn]'s output sublayer over h_new; no h part
+//   RK_GRU_GATES  G 2  rows z, r: z[n][u] = sig(.) (fp32), rh[n][u] = sig(.) * h32[n][u]                          (storage type)
+//   RK_GRU_BLEND  G 1  t = (tanh_ ? tanh : sig)(x-part + rh-part); h' = z * h32 + (1 - z) * t -> h32 (fp32), hs (storage type), out
+//   RK_LSTM       G 4  rows i, f, o, g: c = sig(f) * c + sig(i) * tanh(g) in place (fp32); h' = sig(o) * tanh(c) -> h_new (storage type), out
+// No launch writes a tensor that another workgroup of the same launch reads as an operand: h_new becomes h by a copy after the layer's
+// last launch (yolo_run.cpp); RK_GRU_BLEND reads x and rh only, so it writes hs -- the h operand of RK_GRU_GATES -- itself.
+enum { RK_RNN_STATE = 0, RK_DENSE = 1, RK_GRU_GATES = 2, RK_GRU_BLEND = 3, RK_LSTM = 4 };
+inline int recur_gates(int mode) { return mode == RK_LSTM ? 4 : mode == RK_GRU_GATES ? 2 : 1; }
+inline int recur_rows(int mode, int units) { const int g = recur_gates(mode); return (g * ((units + 7) / 8 * 8) + 15) / 16 * 16; }      // Mp: whole 16-row tiles over whole 8-unit granules of the output
+inline size_t recur_pack_index(int row, int k, int ksteps) { return ((((size_t)(row >> 4) * ksteps + (k >> 5)) * 64 + (((k >> 3) & 3) << 4 | (row & 15))) << 3) | (size_t)(k & 7); }
+struct RecurArgs {
+    int mode, dt;                          // RK_*; operand (storage) type DT_BF16 / DT_F16 / DT_F32: of w, x, h, rh, h_new, hs
+    const void *w; const float *bx, *bh;   // [Mp * (Kx + Kh)] in fragment order; [Mp] each
+    const void *x; int x_stride, x_len;    // [n][x_stride], x_len <= x_stride valid elements per stream (both multiples of 8)
+    const void *h; int h_stride, h_len;    // the same for the second part of K (null / 0: none)
+    int Kx, Kh, units, n;
+    int act, shortcut, tanh_;
+    float *c, *h32, *z;                    // fp32 [max_batch][s_stride]: LSTM cell; GRU state; GRU update gate
+    void *rh, *h_new, *hs; int s_stride;
+    void *out; int out_stride, out_dt;     // [n][out_stride]; the columns units .. min(out_stride, roundup(units, 8)) are written as zeros
+};
+hipError_t launch_recur(const RecurArgs &a, hipStream_t s);
+
 // ---- the small layers of a dense-prediction network and the map outputs (map_ops.hip) ----------
 // [l2norm] (DN/blas.c:126-144): per pixel, over the channels, x / sqrtf(sum x^2); an all-zero pixel is 0 / 0 = NaN, as in the reference
 hipError_t launch_l2norm(const TView &in, const TView &out, hipStream_t s);

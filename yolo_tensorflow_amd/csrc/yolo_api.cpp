@@ -77,6 +77,9 @@ void yolo_destroy(yolo_ctx *c)
     if (c->stream) hipStreamSynchronize(c->stream);
     for (void *p : c->phys) if (p) hipFree(p);
     for (auto &L : c->layers) { if (L.d_w) hipFree(L.d_w); if (L.d_b) hipFree(L.d_b); if (L.d_sc) hipFree(L.d_sc); if (L.d_wf) hipFree(L.d_wf); if (L.d_obj) hipFree(L.d_obj); }
+    for (auto &L : c->layers) for (void *p : {L.d_w2, (void *)L.d_b2, L.d_h, L.d_hn, L.d_rh, (void *)L.d_h32, (void *)L.d_z, (void *)L.d_c}) if (p) hipFree(p);
+    for (auto &L : c->layers) for (auto &S : L.sub) { if (S.d_w) hipFree(S.d_w); if (S.d_b) hipFree(S.d_b); }
+    if (c->d_state_keep) hipFree(c->d_state_keep);
     void *ptrs[] = {c->input.ptr, c->d_zeros, c->d_stage, c->d_det, c->d_scores, c->d_labels, c->d_cand, c->d_keys, c->d_sbox, c->d_slabel, c->d_sscore, c->d_boxes, c->d_counts,
                     c->d_dn_rec, c->d_dn_src, c->d_dn_count, c->d_dn_last, c->d_box4, c->s2d.ptr, c->d_srow, c->d_rows, c->d_lean_list, c->d_lean_cnt, c->d_f32a, c->d_f32b, c->d_descs, c->d_pix, c->d_cls_idx, c->d_cls_prob, c->d_map_f32, c->d_map_labels, c->d_label_off};
     for (void *p : ptrs) if (p) hipFree(p);
@@ -320,6 +323,81 @@ int yolo_label_map(yolo_ctx *c, int n, float thresh, uint8_t *labels_u8)
     if (int r = map_labels_room(c, npix)) return r;
     HIPCK(c, launch_label_map(map, map_stride, npix, M.C, thresh, c->d_map_labels, c->stream));
     return copy_out(c, labels_u8, c->d_map_labels, npix, YOLO_HOST);
+}
+
+// ---- recurrent networks: the state tensors of [rnn] / [gru] / [lstm] layers, one row of `floats_per_stream` values per stream (batch index) ----
+int yolo_num_state_tensors(const yolo_ctx *c) { return c ? (int)c->states.size() : YOLO_ERR_INVALID; }
+
+// values of one stream's state tensor: the units of an [rnn] / [gru] / [lstm]; H * W * hidden_filters of a [crnn], in the tensors' own order (pixel, then channel)
+static size_t state_values(const Layer &L) { return L.type == L_CRNN ? (size_t)L.H * L.W * L.cin : (size_t)L.filters; }
+
+int yolo_state_geometry(const yolo_ctx *c, int k, int *layer, size_t *floats_per_stream)
+{
+    if (!c || k < 0 || k >= (int)c->states.size()) return YOLO_ERR_INVALID;
+    if (layer) *layer = c->states[k].layer;
+    if (floats_per_stream) *floats_per_stream = state_values(c->layers[c->states[k].layer]);
+    return YOLO_OK;
+}
+
+// where state tensor k of `stream` lives: the fp32 tensor that holds it exactly (*f32: an [lstm]'s cell, a [gru]'s state) and / or its copy in the
+// operand type (*op: every h)
+static int state_rows(yolo_ctx *c, const char *who, int k, int stream, size_t floats, float **f32, void **op, Layer **layer)
+{
+    if (k < 0 || k >= (int)c->states.size()) return fail(c, YOLO_ERR_INVALID, "%s: state tensor %d outside 0..%d", who, k, (int)c->states.size() - 1);
+    if (stream < 0 || stream >= c->max_batch) return fail(c, YOLO_ERR_INVALID, "%s: stream %d outside 0..%d", who, stream, c->max_batch - 1);
+    Layer &L = c->layers[c->states[k].layer];
+    if (floats != state_values(L)) return fail(c, YOLO_ERR_INVALID, "%s: state tensor %d holds %zu floats per stream, not %zu", who, k, state_values(L), floats);
+    const size_t row = (size_t)stream * state_elems(c, L);
+    *f32 = L.type == L_CRNN ? nullptr : c->states[k].cell ? L.d_c + row : L.rkind == RECUR_GRU ? L.d_h32 + row : nullptr;
+    *op = c->states[k].cell ? nullptr : (char *)L.d_h + row * dt_size(L.in_dt);
+    *layer = &L;
+    return YOLO_OK;
+}
+
+int yolo_get_state(yolo_ctx *c, int k, int stream, float *out, size_t out_floats)
+{
+    if (!c || !out) return YOLO_ERR_INVALID;
+    float *f32; void *op; Layer *L;
+    if (int r = state_rows(c, "yolo_get_state", k, stream, out_floats, &f32, &op, &L)) return r;
+    HIPCK(c, hipSetDevice(c->device)); HIPCK(c, hipStreamSynchronize(c->stream));
+    // (a [crnn]'s map: `width` channels per pixel out of a pitch of whole granules; the other states: one row)
+    const size_t es = dt_size(L->in_dt), width = L->type == L_CRNN ? (size_t)L->cin : out_floats, pitch = L->type == L_CRNN ? (size_t)roundup(L->cin, 8) : out_floats, rows = out_floats / width;
+    if (f32 || L->in_dt == DT_F32) { HIPCK(c, hipMemcpy2D(out, width * 4, f32 ? (void *)f32 : op, pitch * 4, width * 4, rows, hipMemcpyDeviceToHost)); return YOLO_OK; }
+    std::vector<uint16_t> raw(out_floats);
+    HIPCK(c, hipMemcpy2D(raw.data(), width * es, op, pitch * es, width * es, rows, hipMemcpyDeviceToHost));
+    for (size_t j = 0; j < out_floats; ++j) { if (L->in_dt == DT_F16) out[j] = h2f(raw[j]); else { const uint32_t u = (uint32_t)raw[j] << 16; memcpy(&out[j], &u, 4); } }
+    return YOLO_OK;
+}
+
+int yolo_set_state(yolo_ctx *c, int k, int stream, const float *in, size_t in_floats)
+{
+    if (!c || !in) return YOLO_ERR_INVALID;
+    float *f32; void *op; Layer *L;
+    if (int r = state_rows(c, "yolo_set_state", k, stream, in_floats, &f32, &op, &L)) return r;
+    HIPCK(c, hipSetDevice(c->device)); HIPCK(c, hipStreamSynchronize(c->stream));
+    if (f32) HIPCK(c, hipMemcpy(f32, in, in_floats * 4, hipMemcpyHostToDevice));
+    if (!op) return YOLO_OK;
+    const size_t es = dt_size(L->in_dt), width = L->type == L_CRNN ? (size_t)L->cin : in_floats, pitch = L->type == L_CRNN ? (size_t)roundup(L->cin, 8) : in_floats, rows = in_floats / width;
+    if (L->in_dt == DT_F32) { HIPCK(c, hipMemcpy2D(op, pitch * 4, in, width * 4, width * 4, rows, hipMemcpyHostToDevice)); return YOLO_OK; }
+    std::vector<uint16_t> raw(in_floats);          // rounded as the kernels round what they store
+    for (size_t j = 0; j < in_floats; ++j) raw[j] = L->in_dt == DT_F16 ? f2h(in[j]) : f2bf(in[j]);
+    HIPCK(c, hipMemcpy2D(op, pitch * es, raw.data(), width * es, width * es, rows, hipMemcpyHostToDevice));
+    return YOLO_OK;
+}
+
+// reset_network_state(net, b) (DN/network.c:69): the states of one stream, or of all (stream < 0), back to zero
+int yolo_reset_state(yolo_ctx *c, int stream)
+{
+    if (!c) return YOLO_ERR_INVALID;
+    if (stream >= c->max_batch) return fail(c, YOLO_ERR_INVALID, "yolo_reset_state: stream %d outside 0..%d (-1: all)", stream, c->max_batch - 1);
+    HIPCK(c, hipSetDevice(c->device));
+    for (Layer &L : c->layers) {
+        if (!has_state(L)) continue;
+        const size_t ss = state_elems(c, L), first = stream < 0 ? 0 : (size_t)stream * ss, ne = stream < 0 ? (size_t)c->max_batch * ss : ss, es = dt_size(L.in_dt);
+        HIPCK(c, hipMemsetAsync((char *)L.d_h + first * es, 0, ne * es, c->stream));
+        for (float *p : {L.d_h32, L.d_c}) if (p) HIPCK(c, hipMemsetAsync(p + first, 0, ne * 4, c->stream));
+    }
+    return YOLO_OK;
 }
 
 int yolo_synchronize(yolo_ctx *c) { if (!c) return YOLO_ERR_INVALID; HIPCK(c, hipStreamSynchronize(c->stream)); return YOLO_OK; }

@@ -21,7 +21,9 @@ namespace yolo_impl {
 
 enum LType { L_CONV, L_SHORTCUT, L_ROUTE, L_UPSAMPLE, L_MAXPOOL, L_REORG, L_YOLO, L_REGION, L_DETECT, L_LOCAL, L_AVGPOOL, L_SOFTMAX,
              L_DECONV, L_ACTIVATE, L_L2NORM,        // [deconvolutional]; [logistic] / [activation]: k_activate over the producer's tensor; [l2norm]
-             L_GCONV };                             // [convolutional] with groups > 1 (gconv.hip); Layer::groups
+             L_GCONV,                               // [convolutional] with groups > 1 (gconv.hip); Layer::groups
+             L_RECUR,                               // [rnn] / [gru] / [lstm] (rnn_ops.hip); Layer::rkind
+             L_CRNN };                              // [crnn]: three 3x3 convs around a state map, run by the dense conv kernels; Layer::sub
 enum ConvKernel { K_TILED, K_HALO, K_S2 };      // a conv's own kernel: the tiled family (fp32 / direct / pair form picked by dtype), conv_halo_c32_c64 (3x3/s1, 32 -> 64), conv_s2_c64_c128 (3x3/s2, 64 -> 128)
 // the fused launch a conv is a member of, {members} -> launcher: conv_stem.hip {0, 1, optionally the 1x1 conv 2} -> 1; conv_stem_pair.hip (split-fp16) {0, 1} -> 1; conv_block.hip {1x1 i, 3x3 i + 1} -> i + 1; conv_c3s2.hip {conv3 i, stride-2 conv i + 2} -> i + 2 (both keep K_HALO / K_S2, the fall-back)
 enum FuseKind { F_NONE, F_STEM, F_PSTEM, F_RESBLOCK, F_C3S2 };
@@ -76,6 +78,18 @@ struct Layer {
     // `cost`: a [cost] section (inference identity, never the network's output)
     int groups = 1; float temperature = 1.f; bool pool_fused = false; bool cost = false;
     int tree = -1;                       // [region] / [softmax] with tree=: index into yolo_ctx::trees (hierarchical softmax), else -1
+    // [rnn] / [gru] / [lstm] (L_RECUR; DESIGN.md "Recurrent layers"): `filters` units over the flattened producer (fc_h / fc_w / fc_c its geometry, cin = their
+    // product, as a [connected] layer reads it); act: an [rnn]'s activation, any code (its kernel applies it).  One stacked matrix per launch: d_w / d_b
+    // the first launch's (RK_RNN_STATE, RK_GRU_GATES, RK_LSTM), d_w2 / d_b2 the second's (RK_DENSE, RK_GRU_BLEND); d_b / d_b2 hold bx then bh.  The state of
+    // max_batch streams lives in allocations of the layer's own, outside the pool (zero at yolo_create): d_h the state as the MFMA operand (storage type),
+    // d_hn what the step writes before it becomes d_h, d_h32 / d_z / d_rh a [gru]'s fp32 state, update gate and r * h, d_c an [lstm]'s fp32 cell
+    int rkind = 0, rshortcut = 0, rtanh = 0;      // RECUR_*; [rnn] / [crnn] shortcut=; [gru] tanh=
+    // [crnn] (L_CRNN, DN/crnn_layer.c): sub = its input, self and output convs (3x3 / stride 1 / pad 1, L_CONV layers of their own with filters and bias, seen by
+    // no marking pass); `filters` = output_filters, cin = hidden_filters.  Its state map [max_batch][H][W][roundup(hidden, 8)] is d_h, in the storage type (conv_self
+    // reads it); d_rh holds [state +] act(conv_in(x)), d_hn the new state until the step's last read of the old one is issued
+    std::vector<Layer> sub;
+    void *d_w2 = nullptr; float *d_b2 = nullptr;
+    void *d_h = nullptr, *d_hn = nullptr, *d_rh = nullptr; float *d_h32 = nullptr, *d_z = nullptr, *d_c = nullptr;
     // storage
     int storage = -1; int ch_off = 0;    // view = storage buffer + channel offset
     TView out;
@@ -88,6 +102,10 @@ struct Tree {
     std::vector<int> parent, child, goff, gsize, leaf, order, lvl;      // order / lvl: see TreeDev (kernels.h)
     int *d_all = nullptr; TreeDev dev{};
 };
+
+enum { RECUR_RNN = 0, RECUR_GRU = 1, RECUR_LSTM = 2 };
+// one state tensor of a recurrent layer as yolo_get_state / yolo_set_state number them (layer order; an [lstm]: h, then c)
+struct StateRef { int layer; bool cell; };
 
 struct Storage { int def = 1 << 30, last = -1; size_t bytes = 0; int phys = -1; int stride = 0; int dt = DT_BF16; bool persistent = false; };
 
@@ -148,6 +166,8 @@ struct yolo_ctx {
     size_t weights_count = 0;
     double conv_flops = 0;
     int last_n = 0;
+    std::vector<StateRef> states;         // the state tensors of the recurrent layers (empty: a pure function of the batch)
+    void *d_state_keep = nullptr;         // the timing entry points' copy of every state, handed back when they return (state_keep / state_restore)
     // fp8 scheme: stored value = e4m3(real / scale).  user_scale[i] is what yolo_set_act_scales gave for
     // layer i (1 by default); eff_scale[i] is the scale of the tensor layer i's view holds (inherited through
     // upsample / maxpool / reorg / single-input route; NaN for multi-input routes, which are per channel).
@@ -180,7 +200,8 @@ inline void drop_graph(yolo_ctx *c)      // a plan / parameter / buffer change: 
 }
 
 // ---- layer kinds the planner asks for by more than one name ----
-inline bool computes(const Layer &L) { return L.type == L_CONV || L.type == L_DECONV || L.type == L_GCONV; }      // has filters and an MFMA kernel ([connected] is an L_CONV; [local] is not among them)
+inline bool computes(const Layer &L) { return L.type == L_CONV || L.type == L_DECONV || L.type == L_GCONV || L.type == L_RECUR || L.type == L_CRNN; }      // has filters and an MFMA kernel ([connected] is an L_CONV; [local] is not among them)
+inline bool has_state(const Layer &L) { return L.type == L_RECUR || L.type == L_CRNN; }
 inline bool is_head_layer(const Layer &L) { return L.type == L_YOLO || L.type == L_REGION || L.type == L_DETECT; }      // a detection head: no tensor of its own, an alias of the conv in front of it
 
 // ---- what a conv layer's (kernel, fused, launcher) mean: the only places that enumerate fused kinds; `i` = the layer's own index.  Where two of the old lists disagreed: NOTEBOOK 2026-10-18 ----
@@ -206,6 +227,16 @@ float h2f(uint16_t h);
 void resolve_scales(yolo_ctx *c);
 void channel_scales(const yolo_ctx *c, int idx, std::vector<float> &out);
 int tail_fragments(yolo_ctx *c);
+// recurrent layers: the sublayers of layer L in file order -- {inputs, 1 for a sublayer over the state} per sublayer -- and the floats one holds
+int recur_sublayers(const Layer &L, int subs[8]);
+inline size_t connected_floats(int inputs, int outputs, int bn) { return (size_t)outputs * (1 + (size_t)inputs + (bn ? 3 : 0)); }
+struct RecurGeom { int mode[2], Mp[2], Kx[2], Kh[2], x_len, s_stride, launches; };      // of a planned (and, for x_len, allocated) layer: its one or two launches
+RecurGeom recur_geom(const yolo_ctx *c, const Layer &L);
+size_t recur_blob_bytes(const yolo_ctx *c, const Layer &L, int k);      // k = 0..3: d_w, d_b, d_w2, d_b2 (0: none)
+size_t state_elems(const yolo_ctx *c, const Layer &L);      // elements of one stream's state tensor as stored (padded): roundup(units, 8), a [crnn]: H * W * roundup(hidden, 8)
+// yolo_run.cpp: states across forwards of the library's own
+int state_keep(yolo_ctx *c);
+int state_restore(yolo_ctx *c);
 // yolo_tree.cpp
 int parse_tree(const std::string &text, Tree &t, std::string &err);      // YOLO_OK or YOLO_ERR_INVALID with a message that names the line
 int load_tree(const std::string &path, Tree &t, std::string &err);        // ... from the artifact being read (g_tree_texts) or the file, as darknet opens it

@@ -180,6 +180,75 @@ void pack_gconv(const Layer &L, const float *bn_or_bias, const float *w_oihw, in
     }
 }
 
+// one [connected] sublayer of the weight stream (DN/parser.c load_connected_weights: biases, weights [outputs][inputs], then scales, rolling mean,
+// rolling variance when batch-normalised) with its batch norm folded into the rows and the bias (DN/connected_layer.c:161 -> batchnorm_layer.c: the
+// rolling statistics, scale, then the biases), by pack_conv's rule.  Returns the stream behind it
+static const float *read_connected(const float *p, int inputs, int outputs, int bn, int semantics, std::vector<float> &w, std::vector<float> &b)
+{
+    const float *bias = p, *wf = p + outputs;
+    p += (size_t)outputs * (1 + (size_t)inputs);
+    w.assign(wf, wf + (size_t)outputs * inputs); b.assign(bias, bias + outputs);
+    if (!bn) return p;
+    const float *gamma = p, *mean = p + outputs, *var = p + 2 * (size_t)outputs;
+    for (int o = 0; o < outputs; ++o) {
+        const float sc = semantics == YOLO_SEM_DARKNET ? gamma[o] / (sqrtf(var[o]) + 1e-6f) : gamma[o] / sqrtf(var[o] + 1e-5f);
+        for (int j = 0; j < inputs; ++j) w[(size_t)o * inputs + j] *= sc;
+        b[o] = bias[o] - mean[o] * sc;
+    }
+    return p + 3 * (size_t)outputs;
+}
+
+// [rnn] / [gru] / [lstm]: the sublayers of the stream -> the stacked matrices of the layer's launches (RecurArgs, kernels.h), in fragment order, and
+// their bias pairs.  A sublayer over the layer's input has its columns moved from darknet's CHW flattening to the tensor's [pixel][stride] order
+static int pack_recurrent(yolo_ctx *c, Layer &L, const float *&p)
+{
+    const RecurGeom g = recur_geom(c, L);
+    const int U = L.filters, hw = L.fc_h * L.fc_w, xs = hw ? g.x_len / hw : 0;
+    int subs[8]; const int ns = recur_sublayers(L, subs);
+    std::vector<float> w[8], b[8];
+    for (int q = 0; q < ns; ++q) p = read_connected(p, subs[q] ? U : L.cin, U, L.bn, c->semantics, w[q], b[q]);
+    // per launch and gate: the sublayer over the x part and the one over the h part of K (-1: none)
+    int G[2] = {recur_gates(g.mode[0]), recur_gates(g.mode[1])}, sx[2][4] = {}, sh[2][4] = {};
+    if (L.rkind == RECUR_LSTM) for (int t = 0; t < 4; ++t) { sx[0][t] = 4 + t; sh[0][t] = t; }          // rows i f o g: ui uf uo ug over x, wi wf wo wg over h
+    if (L.rkind == RECUR_GRU) { sx[0][0] = 3; sh[0][0] = 0; sx[0][1] = 4; sh[0][1] = 1; sx[1][0] = 5; sh[1][0] = 2; }      // rows z r: uz ur | wz wr; then uh | wh over r * h
+    if (L.rkind == RECUR_RNN) { sx[0][0] = 0; sh[0][0] = 1; sx[1][0] = 2; sh[1][0] = -1; }          // input | self; then output over the new state
+    void *dw[2] = {L.d_w, L.d_w2}; float *db[2] = {L.d_b, L.d_b2};
+    const size_t es = dt_size(L.in_dt);
+    for (int q = 0; q < g.launches; ++q) {
+        const int K = g.Kx[q] + g.Kh[q], KS = K / 32;
+        std::vector<uint8_t> wbuf((size_t)g.Mp[q] * K * es, 0); std::vector<float> bias((size_t)2 * g.Mp[q], 0.f);
+        auto put = [&](int row, int k, float v) {
+            const size_t idx = recur_pack_index(row, k, KS);
+            if (L.in_dt == DT_F32) memcpy(&wbuf[idx * 4], &v, 4);
+            else { const uint16_t h = L.in_dt == DT_F16 ? f2h(v) : f2bf(v); memcpy(&wbuf[idx * 2], &h, 2); }
+        };
+        const bool x_is_input = !(L.rkind == RECUR_RNN && q == 1);
+        for (int u = 0; u < U; ++u) for (int t = 0; t < G[q]; ++t) {
+            const int row = u * G[q] + t, a = sx[q][t], hpart = sh[q][t];
+            bias[row] = b[a][u];
+            if (x_is_input) { for (int ch = 0; ch < L.fc_c; ++ch) for (int px = 0; px < hw; ++px) put(row, px * xs + ch, w[a][(size_t)u * L.cin + (size_t)ch * hw + px]); }
+            else for (int j = 0; j < U; ++j) put(row, j, w[a][(size_t)u * U + j]);
+            if (hpart < 0) continue;
+            bias[g.Mp[q] + row] = b[hpart][u];
+            for (int j = 0; j < U; ++j) put(row, g.Kx[q] + j, w[hpart][(size_t)u * U + j]);
+        }
+        HIPCK(c, hipMemcpy(dw[q], wbuf.data(), wbuf.size(), hipMemcpyHostToDevice));
+        HIPCK(c, hipMemcpy(db[q], bias.data(), bias.size() * 4, hipMemcpyHostToDevice));
+    }
+    return YOLO_OK;
+}
+
+// the parameter blobs of a layer with state, in the order an artifact holds them: an [rnn] / [gru] / [lstm]'s stacked matrix and bias pair per launch,
+// a [crnn]'s filters and bias per conv.  Returns how many (at most 6)
+static int state_layer_blobs(const yolo_ctx *c, const Layer &L, void *ptr[6], uint64_t bytes[6])
+{
+    int n = 0;
+    if (L.type == L_CRNN) { for (const Layer &S : L.sub) { ptr[n] = S.d_w; bytes[n++] = (uint64_t)S.cout_pad * S.kpad * dt_size(S.in_dt); ptr[n] = S.d_b; bytes[n++] = (uint64_t)S.cout_pad * 4; } return n; }
+    void *all[4] = {L.d_w, L.d_b, L.d_w2, L.d_b2};
+    for (int k = 0; k < 4; ++k) if (const size_t b = recur_blob_bytes(c, L, k)) { ptr[n] = all[k]; bytes[n++] = b; }
+    return n;
+}
+
 // fp8: scale of the tensor each layer's view holds, and per-input-channel scales of a conv
 void resolve_scales(yolo_ctx *c)
 {
@@ -305,9 +374,26 @@ int yolo_set_weights(yolo_ctx *c, const float *flat, size_t n)
             HIPCK(c, hipMemcpy(L.d_b, bias.data(), bias.size() * 4, hipMemcpyHostToDevice));
             continue;
         }
+        if (L.type == L_RECUR) { if (int rc = pack_recurrent(c, L, p)) return rc; continue; }
+        if (L.type == L_CRNN) {          // input, self, output: three convs in a conv's own file layout
+            for (Layer &S : L.sub) {
+                const float *params = p; p += (size_t)S.filters * (S.bn ? 4 : 1);
+                const float *w = p; p += (size_t)S.filters * S.cin * 9;
+                pack_conv(S, params, w, S.in_dt, nullptr, wbuf, bias, osc, c->semantics, 0);
+                HIPCK(c, hipMemcpy(S.d_w, wbuf.data(), wbuf.size(), hipMemcpyHostToDevice));
+                HIPCK(c, hipMemcpy(S.d_b, bias.data(), bias.size() * 4, hipMemcpyHostToDevice));
+            }
+            continue;
+        }
         if (L.type != L_CONV) continue;
         const float *params = p; p += (size_t)L.filters * (L.bn ? 4 : 1);
         const float *w = p; p += (size_t)L.filters * L.cin * L.size * L.size;
+        std::vector<float> fcbn;
+        if (L.fc && L.bn) {          // a batch-normalised [connected]: biases, weights, scales, rolling mean, rolling variance -> pack_conv's beta gamma mean var | weights
+            const size_t F = L.filters, nw = F * L.cin;
+            fcbn.assign(params, params + F); fcbn.insert(fcbn.end(), params + F + nw, params + 4 * F + nw); fcbn.insert(fcbn.end(), params + F, params + F + nw);
+            params = fcbn.data(); w = fcbn.data() + 4 * F;
+        }
         std::vector<float> in_sc;
         if (L.in_dt == DT_FP8) {
             channel_scales(c, L.in[0], in_sc);
@@ -403,6 +489,16 @@ int yolo_export(yolo_ctx *c, const char *path)
     for (auto &t : c->trees) { const uint32_t len[2] = {(uint32_t)t.path.size(), (uint32_t)t.text.size()}; w.put(len, sizeof len); w.put(t.path.data(), t.path.size()); w.put(t.text.data(), t.text.size()); }
     std::vector<uint8_t> buf;
     for (auto &L : c->layers) {
+        if (has_state(L)) {          // the parameter blobs of its launches, each behind its byte count (no state: an artifact holds parameters)
+            void *ptr[6]; uint64_t bytes[6]; const int nb = state_layer_blobs(c, L, ptr, bytes);
+            w.put(bytes, (size_t)nb * 8);
+            for (int k = 0; k < nb; ++k) {
+                buf.resize(bytes[k]);
+                if (hipMemcpy(buf.data(), ptr[k], bytes[k], hipMemcpyDeviceToHost) != hipSuccess) { fclose(f); return fail(c, YOLO_ERR_HIP, "export: device read failed"); }
+                w.put(buf.data(), bytes[k]);
+            }
+            continue;
+        }
         if (L.type != L_CONV && L.type != L_LOCAL && L.type != L_DECONV && L.type != L_GCONV) continue;
         uint64_t sz[3] = {(uint64_t)L.cout_pad * L.kpad * dt_size(L.in_dt), (uint64_t)L.cout_pad, L.d_sc ? (uint64_t)L.cout_pad : 0};
         if (L.type == L_LOCAL) { sz[0] = (uint64_t)L.H * L.W * L.filters * L.size * L.size * L.cin * dt_size(L.in_dt); sz[1] = (uint64_t)L.H * L.W * L.filters; sz[2] = 0; }
@@ -459,6 +555,17 @@ yolo_ctx *yolo_create_from_file(const char *path, int max_batch, int device, voi
     if (c->dtype == YOLO_FP8 && yolo_set_act_scales(c, sc.data(), (int)hd.n_layers) != YOLO_OK) { fclose(f); return bail(c, c->err); }
     std::vector<uint8_t> buf;
     for (auto &L : c->layers) {
+        if (has_state(L)) {
+            void *ptr[6]; uint64_t bytes[6], got[6]; const int nb = state_layer_blobs(c, L, ptr, bytes);
+            r.get(got, (size_t)nb * 8);
+            if (!r.ok || memcmp(got, bytes, (size_t)nb * 8) != 0) { fclose(f); return bail(c, "artifact parameters do not fit the topology (truncated file or different packing)"); }
+            for (int k = 0; k < nb; ++k) {
+                buf.resize(bytes[k]); r.get(buf.data(), bytes[k]);
+                if (!r.ok) { fclose(f); return bail(c, "truncated artifact"); }
+                if (hipMemcpy(ptr[k], buf.data(), bytes[k], hipMemcpyHostToDevice) != hipSuccess) { fclose(f); return bail(c, "artifact upload failed"); }
+            }
+            continue;
+        }
         if (L.type != L_CONV && L.type != L_LOCAL && L.type != L_DECONV && L.type != L_GCONV) continue;
         uint64_t sz[3]; r.get(sz, sizeof sz);
         uint64_t want[3] = {(uint64_t)L.cout_pad * L.kpad * dt_size(L.in_dt), (uint64_t)L.cout_pad, L.d_sc ? (uint64_t)L.cout_pad : 0};

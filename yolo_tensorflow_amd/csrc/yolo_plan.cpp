@@ -211,15 +211,41 @@ static int parse_connected(Cursor &k, const Section &s, Layer &L)
 {
     yolo_ctx *c = k.c; const int i = k.i;
     if (c->dtype == YOLO_FP8 || c->split()) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [connected] is not served in the fp8 / split-fp16 configurations", i);
-    if (opt_i(s, "batch_normalize", 0)) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: batch-normalised [connected]", i);
     L.type = L_CONV; L.fc = true; L.fc_h = k.H; L.fc_w = k.W; L.fc_c = k.C;
-    L.filters = opt_i(s, "output", 1); L.size = 1; L.stride = 1; L.pad = 0; L.bn = 0;
+    // batch_normalize=1 (DN/connected_layer.c:161: gemm, the rolling statistics, scale, bias): folded into the rows and the bias when the weights are packed, as a conv's
+    L.filters = opt_i(s, "output", 1); L.size = 1; L.stride = 1; L.pad = 0; L.bn = opt_i(s, "batch_normalize", 0) != 0;
+    if (L.filters < 1) return fail(c, YOLO_ERR_INVALID, "layer %d: [connected] output=%d", i, L.filters);
     if (int r = plan_activation(c, i, s, "logistic", false)) return r;
     L.in_dt = c->act_dt(); L.store_dt = c->act_dt();
     if ((long)k.H * k.W * k.C > (1L << 24)) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [connected] input too large", i);
     L.cin = k.H * k.W * k.C; L.cin_pad = roundup(L.cin, 8); L.kpad = roundup(L.cin_pad, 64); L.cout_pad = roundup(L.filters, 256);
     c->conv_flops += 2.0 * L.cin * L.filters;
-    c->weights_count += (size_t)L.filters + (size_t)L.filters * L.cin;
+    c->weights_count += connected_floats(L.cin, L.filters, L.bn);
+    k.H = 1; k.W = 1; k.C = L.filters;
+    return YOLO_OK;
+}
+
+// [rnn] / [gru] / [lstm] (DN/parser.c:222-255): `output` units over the flattened producer, which they read as a [connected] layer does; one call
+// of the library is one time step (darknet after set_batch_network(net, 1) with time_steps=1), batch index b is stream b.  Their sublayers are
+// [connected] layers (file order: recur_sublayers); which launches they become: recur_geom.  fp8 / split-fp16: refused by parse_sections
+static bool is_recurrent(const std::string &t) { return t == "rnn" || t == "gru" || t == "lstm" || t == "crnn"; }
+static int parse_recurrent(Cursor &k, const Section &s, Layer &L)
+{
+    yolo_ctx *c = k.c; const int i = k.i;
+    L.type = L_RECUR; L.rkind = s.type == "rnn" ? RECUR_RNN : s.type == "gru" ? RECUR_GRU : RECUR_LSTM;
+    L.filters = opt_i(s, "output", 1); L.size = 1; L.stride = 1; L.pad = 0; L.bn = opt_i(s, "batch_normalize", 0) != 0;
+    if (L.filters < 1) return fail(c, YOLO_ERR_INVALID, "layer %d: [%s] output=%d", i, s.type.c_str(), L.filters);
+    if (L.rkind == RECUR_RNN) {          // any activation: the kernel's epilogue applies it to each product before the sum
+        const std::string name = opt_s(s, "activation", "logistic");
+        L.act = act_from_name(name.c_str()); L.rshortcut = opt_i(s, "shortcut", 0) != 0;
+        if (L.act < 0) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: activation '%s' unsupported", i, name.c_str());
+    }
+    if (L.rkind == RECUR_GRU) L.rtanh = opt_i(s, "tanh", 0) != 0;
+    if ((long)k.H * k.W * k.C > (1L << 24)) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [%s] input too large", i, s.type.c_str());
+    L.fc_h = k.H; L.fc_w = k.W; L.fc_c = k.C; L.cin = k.H * k.W * k.C;
+    L.in_dt = c->act_dt(); L.store_dt = c->act_dt();
+    int subs[8]; const int ns = recur_sublayers(L, subs);
+    for (int q = 0; q < ns; ++q) { const int inputs = subs[q] ? L.filters : L.cin; c->conv_flops += 2.0 * inputs * L.filters; c->weights_count += connected_floats(inputs, L.filters, L.bn); }
     k.H = 1; k.W = 1; k.C = L.filters;
     return YOLO_OK;
 }
@@ -241,6 +267,37 @@ static int parse_local(Cursor &k, const Section &s, Layer &L)
     k.H = ho; k.W = wo; k.C = L.filters;
     c->conv_flops += 2.0 * L.size * L.size * L.cin * L.filters * (double)k.H * k.W;
     c->weights_count += (size_t)L.filters * k.H * k.W + (size_t)k.H * k.W * L.filters * L.cin * L.size * L.size;
+    return YOLO_OK;
+}
+
+// [crnn] (DN/crnn_layer.c:29-130, DN/parser.c:207-220): state' = [shortcut ? state : 0] + act(conv_in(x)) + act(conv_self(state)), out = act(conv_out(state')),
+// three 3x3 / stride 1 / pad 1 convs with the section's activation and batch norm.  Planned as three launches of the dense conv kernels through
+// their own selection rule (run_crnn): conv_in with the old state as its epilogue's residual (shortcut=1), conv_self with conv_in's result as its
+// residual, conv_out.  The residual is added behind the activation: with an activation the conv epilogue does not apply itself (logistic, the section's
+// default, tanh, ...) each conv is followed by k_activate and, where it sums, an add launch
+static int parse_crnn(Cursor &k, const Section &s, Layer &L)
+{
+    yolo_ctx *c = k.c; const int i = k.i;
+    const int hidden = opt_i(s, "hidden_filters", 1), output = opt_i(s, "output_filters", 1);
+    if (hidden < 1 || output < 1) return fail(c, YOLO_ERR_INVALID, "layer %d: [crnn] hidden_filters=%d output_filters=%d", i, hidden, output);
+    // DN/parser.c:215 hands make_crnn_layer (w, h) where it takes (h, w): the reference's own layer is only meaningful on a square map
+    if (k.H != k.W) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [crnn] over a %d x %d map: the reference builds the layer with height and width exchanged, so only a square map is served", i, k.W, k.H);
+    if (i == 0) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [crnn] as the network's first layer is not served", i);
+    L.type = L_CRNN; L.filters = output; L.cin = hidden; L.size = 3; L.stride = 1; L.pad = 1; L.bn = opt_i(s, "batch_normalize", 0) != 0; L.rshortcut = opt_i(s, "shortcut", 0) != 0;
+    const std::string name = opt_s(s, "activation", "logistic");
+    L.act = act_from_name(name.c_str());
+    if (L.act < 0) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: activation '%s' unsupported", i, name.c_str());
+    L.in_dt = c->act_dt(); L.store_dt = c->act_dt();
+    const int cins[3] = {k.C, hidden, hidden}, couts[3] = {hidden, hidden, output};
+    L.sub.assign(3, Layer());
+    for (int q = 0; q < 3; ++q) {
+        Layer &S = L.sub[q];
+        S.type = L_CONV; S.filters = couts[q]; S.size = 3; S.stride = 1; S.pad = 1; S.bn = L.bn; S.act = L.act; S.in_dt = S.store_dt = c->act_dt();
+        S.cin = cins[q]; S.cin_pad = roundup(S.cin, 8); S.kpad = roundup(9 * S.cin_pad, 64); S.cout_pad = roundup(S.filters, 256);
+        S.H = k.H; S.W = k.W; S.C = S.filters;
+        conv_totals(c, S, S.cin, k.H, k.W);
+    }
+    k.C = output;
     return YOLO_OK;
 }
 
@@ -412,7 +469,7 @@ static int parse_softmax(Cursor &k, const Section &s, Layer &L)
     // the logits are never rounded to 16 bits: the conv that reaches this layer directly, or through one [avgpool], writes fp32
     int p = i - 1;
     if (p >= 0 && c->layers[p].type == L_AVGPOOL) p = c->layers[p].in[0];
-    if (p >= 0 && (c->layers[p].type == L_CONV || c->layers[p].type == L_GCONV)) c->layers[p].head = true;      // (not L_DECONV: not computes())
+    if (p >= 0 && (c->layers[p].type == L_CONV || c->layers[p].type == L_GCONV || c->layers[p].type == L_RECUR)) c->layers[p].head = true;      // (not L_DECONV)
     return YOLO_OK;
 }
 
@@ -421,6 +478,7 @@ static const struct { const char *name; int (*parse)(Cursor &, const Section &, 
     {"shortcut", parse_shortcut}, {"route", parse_route}, {"upsample", parse_upsample}, {"deconvolutional", parse_deconvolutional},
     {"logistic", parse_activate}, {"activation", parse_activate}, {"l2norm", parse_l2norm}, {"maxpool", parse_maxpool}, {"reorg", parse_reorg},
     {"yolo", parse_head}, {"region", parse_head}, {"avgpool", parse_avgpool}, {"softmax", parse_softmax}, {"cost", parse_identity},
+    {"rnn", parse_recurrent}, {"gru", parse_recurrent}, {"lstm", parse_recurrent}, {"crnn", parse_crnn},
 };
 
 // After each section: a layer that moves data keeps the type and the pair form of what it moves, and its operands must agree.
@@ -452,6 +510,10 @@ static int parse_sections(yolo_ctx *c, const std::vector<Section> &secs)
     if (c->in_h <= 0 || c->in_w <= 0 || c->in_c != 3)
         return fail(c, YOLO_ERR_UNSUPPORTED, "cfg: need an input of positive height and width with 3 channels (got %dx%dx%d)", c->in_w, c->in_h, c->in_c);
     const int NL = (int)secs.size() - 1;
+    // a recurrent layer is served in the bf16, fp16 and fp32 configurations: refused here, by its own name, ahead of whatever else of such a network the
+    // configuration refuses.  ([net] time_steps is read and ignored: one call is one step)
+    for (int i = 0; i < NL && (c->dtype == YOLO_FP8 || c->split()); ++i)
+        if (is_recurrent(secs[i + 1].type)) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [%s] is not served in the %s configuration", i, secs[i + 1].type.c_str(), c->split() ? "split-fp16" : "fp8");
     c->layers.resize(NL);
     c->rows = 0; c->attrs = 0; c->conv_flops = 0; c->weights_count = 0;
     // split-fp16 networks: per-tensor storage form (mixed plans): pairs unless a [convolutional] section says yolo_pair=0
@@ -848,7 +910,45 @@ int build_plan(yolo_ctx *c, const std::vector<Section> &secs)
     redirect_folded_convs(c, at);
     compute_liveness(c);
     assign_pool(c);
+    // the recurrent layers' state tensors, in layer order (yolo_get_state): none of them is a member of the pool above
+    c->states.clear();
+    for (int i = 0; i < (int)c->layers.size(); ++i) if (has_state(c->layers[i])) { c->states.push_back({i, false}); if (c->layers[i].type == L_RECUR && c->layers[i].rkind == RECUR_LSTM) c->states.push_back({i, true}); }
     return YOLO_OK;
+}
+
+// ---- recurrent layers: sublayers, launches, parameter blobs ----------------------------------------------------------------------------
+// file order of the [connected] sublayers (DN/parser.c:1281-1314): 1 = over the state (`output` inputs), 0 = over the layer's input
+int recur_sublayers(const Layer &L, int subs[8])
+{
+    static const int rnn[3] = {0, 1, 1}, gru[6] = {1, 1, 1, 0, 0, 0}, lstm[8] = {1, 1, 1, 1, 0, 0, 0, 0};      // input self output | wz wr wh uz ur uh | wi wf wo wg ui uf uo ug
+    const int n = L.rkind == RECUR_RNN ? 3 : L.rkind == RECUR_GRU ? 6 : 8;
+    std::copy(L.rkind == RECUR_RNN ? rnn : L.rkind == RECUR_GRU ? gru : lstm, (L.rkind == RECUR_RNN ? rnn : L.rkind == RECUR_GRU ? gru : lstm) + n, subs);
+    return n;
+}
+
+// elements per pixel of the tensor layer idx's view lies in (-1: the network input); valid once create_storages ran
+static int stride_of(const yolo_ctx *c, int idx) { return idx < 0 ? (c->in_pair ? 24 : 8) : c->layers[idx].storage >= 0 ? c->storages[c->layers[idx].storage].stride : 0; }
+
+RecurGeom recur_geom(const yolo_ctx *c, const Layer &L)
+{
+    RecurGeom g; memset(&g, 0, sizeof g);
+    g.x_len = L.fc_h * L.fc_w * stride_of(c, L.in[0]); g.s_stride = roundup(L.filters, 8);
+    const int kx = roundup(g.x_len, 32), kh = roundup(g.s_stride, 32);
+    g.launches = L.rkind == RECUR_LSTM ? 1 : 2;
+    g.mode[0] = L.rkind == RECUR_RNN ? RK_RNN_STATE : L.rkind == RECUR_GRU ? RK_GRU_GATES : RK_LSTM; g.Kx[0] = kx; g.Kh[0] = kh;
+    if (L.rkind == RECUR_RNN) { g.mode[1] = RK_DENSE; g.Kx[1] = kh; g.Kh[1] = 0; }          // the output sublayer over the new state
+    if (L.rkind == RECUR_GRU) { g.mode[1] = RK_GRU_BLEND; g.Kx[1] = kx; g.Kh[1] = kh; }      // [x | r * h]
+    for (int q = 0; q < g.launches; ++q) g.Mp[q] = recur_rows(g.mode[q], L.filters);
+    return g;
+}
+
+size_t state_elems(const yolo_ctx *, const Layer &L) { return L.type == L_CRNN ? (size_t)L.H * L.W * roundup(L.cin, 8) : (size_t)roundup(L.filters, 8); }
+
+size_t recur_blob_bytes(const yolo_ctx *c, const Layer &L, int k)
+{
+    const RecurGeom g = recur_geom(c, L); const int q = k >> 1;
+    if (q >= g.launches) return 0;
+    return k & 1 ? (size_t)2 * g.Mp[q] * 4 : (size_t)g.Mp[q] * (g.Kx[q] + g.Kh[q]) * dt_size(L.in_dt);
 }
 
 int allocate(yolo_ctx *c)
@@ -935,6 +1035,39 @@ int allocate(yolo_ctx *c)
         HIPCK(c, hipMalloc((void **)&L.d_b, (size_t)L.cout_pad * 4)); HIPCK(c, hipMemsetAsync(L.d_b, 0, (size_t)L.cout_pad * 4, c->stream));
         if (L.in_dt == DT_FP8) { HIPCK(c, hipMalloc((void **)&L.d_sc, (size_t)L.cout_pad * 4)); HIPCK(c, hipMemsetAsync(L.d_sc, 0, (size_t)L.cout_pad * 4, c->stream)); }
     }
+    size_t keep_bytes = 0;
+    for (size_t i = 0; i < c->layers.size(); ++i) {
+        Layer &L = c->layers[i];
+        if (L.type != L_CRNN) continue;
+        const TView in = view_of(c, L.in[0]);
+        if (!in.ptr || in.dt != L.in_dt || c->pair_of(L.in[0])) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %zu: [crnn] needs a producer stored in the network's own type (not an fp32 head, map or classifier tensor)", i);
+        for (Layer &S : L.sub) {
+            const size_t wb = (size_t)S.cout_pad * S.kpad * dt_size(S.in_dt);
+            HIPCK(c, hipMalloc(&S.d_w, wb)); HIPCK(c, hipMemsetAsync(S.d_w, 0, wb, c->stream));
+            HIPCK(c, hipMalloc((void **)&S.d_b, (size_t)S.cout_pad * 4)); HIPCK(c, hipMemsetAsync(S.d_b, 0, (size_t)S.cout_pad * 4, c->stream));
+        }
+        const size_t bytes = (size_t)c->max_batch * state_elems(c, L) * dt_size(L.in_dt);          // (+ a tail the conv kernels' 16-byte pieces may touch, as the pool's buffers have)
+        for (void **p : {&L.d_h, &L.d_hn, &L.d_rh}) { HIPCK(c, hipMalloc(p, bytes + 256)); HIPCK(c, hipMemsetAsync(*p, 0, bytes + 256, c->stream)); }
+        keep_bytes += (size_t)c->max_batch * state_elems(c, L) * 8;
+    }
+    for (size_t i = 0; i < c->layers.size(); ++i) {
+        Layer &L = c->layers[i];
+        if (L.type != L_RECUR) continue;
+        const TView in = view_of(c, L.in[0]);
+        if (!in.ptr || in.dt != L.in_dt || in.stride % 8 || c->pair_of(L.in[0]))
+            return fail(c, YOLO_ERR_UNSUPPORTED, "layer %zu: a recurrent layer needs a producer stored in the network's own type (not an fp32 head, map or classifier tensor)", i);
+        void **blob[4] = {&L.d_w, (void **)&L.d_b, &L.d_w2, (void **)&L.d_b2};
+        for (int k = 0; k < 4; ++k) if (const size_t b = recur_blob_bytes(c, L, k)) { HIPCK(c, hipMalloc(blob[k], b)); HIPCK(c, hipMemsetAsync(*blob[k], 0, b, c->stream)); }
+        // state: max_batch streams of s_stride elements each, zero (the columns past the units stay zero for good: the kernels read them as operands)
+        const size_t ne = (size_t)c->max_batch * roundup(L.filters, 8), es = dt_size(L.in_dt);
+        auto zeroed = [&](void **p, size_t bytes) { hipError_t e = hipMalloc(p, bytes); return e != hipSuccess ? e : hipMemsetAsync(*p, 0, bytes, c->stream); };
+        HIPCK(c, zeroed(&L.d_h, ne * es));
+        if (L.rkind != RECUR_GRU) HIPCK(c, zeroed(&L.d_hn, ne * es));
+        if (L.rkind == RECUR_GRU) { HIPCK(c, zeroed(&L.d_rh, ne * es)); HIPCK(c, zeroed((void **)&L.d_h32, ne * 4)); HIPCK(c, zeroed((void **)&L.d_z, ne * 4)); }
+        if (L.rkind == RECUR_LSTM) HIPCK(c, zeroed((void **)&L.d_c, ne * 4));
+        keep_bytes += ne * 8;          // (state_keep: d_h and the layer's fp32 tensor, if it has one)
+    }
+    if (keep_bytes) HIPCK(c, hipMalloc(&c->d_state_keep, keep_bytes));
     for (auto &L : c->layers) if (L.type == L_LOCAL) {
         const size_t wn = (size_t)L.H * L.W * L.filters * L.size * L.size * L.cin;
         HIPCK(c, hipMalloc(&L.d_w, wn * dt_size(L.in_dt))); HIPCK(c, hipMalloc((void **)&L.d_b, (size_t)L.H * L.W * L.filters * 4));
@@ -1036,6 +1169,17 @@ int yolo_plan_dump(const char *cfg_text, int dtype, int max_batch, int keep_laye
         put(" psize=%d pstride=%d ppad=%d up_scale=%a inplace=%d", L.psize, L.pstride, L.ppad, (double)L.up_scale, (int)L.inplace);
         put(" na=%d classes=%d row_off=%d anchors=[", L.na, L.classes, L.row_off); for (size_t k = 0; k < L.anchors.size(); ++k) put(k ? ",%a" : "%a", (double)L.anchors[k]);
         put("] groups=%d temperature=%a pool_fused=%d cost=%d tree=%d storage=%d ch_off=%d\n", L.groups, (double)L.temperature, (int)L.pool_fused, (int)L.cost, L.tree, L.storage, L.ch_off);
+        if (L.type == L_RECUR) {          // (a line of its own, on the new layer kind only: the dump of every other cfg is pinned byte for byte)
+            const RecurGeom g = recur_geom(&c, L);
+            put("recurrent %zu kind=%s units=%d inputs=%d shortcut=%d tanh=%d x_len=%d s_stride=%d launches=%d", i, secs[i + 1].type.c_str(), L.filters, L.cin, L.rshortcut, L.rtanh, g.x_len, g.s_stride, g.launches);
+            for (int q = 0; q < g.launches; ++q) put(" launch%d=[mode=%d rows=%d kx=%d kh=%d]", q, g.mode[q], g.Mp[q], g.Kx[q], g.Kh[q]);
+            put(" state=own(%s)\n", L.rkind == RECUR_LSTM ? "h,c" : "h");
+        }
+        if (L.type == L_CRNN) {
+            put("recurrent %zu kind=crnn hidden=%d output=%d shortcut=%d launches=3", i, L.cin, L.filters, L.rshortcut);
+            for (int q = 0; q < 3; ++q) put(" conv%d=[cin=%d cin_pad=%d kpad=%d filters=%d cout_pad=%d bn=%d act=%d]", q, L.sub[q].cin, L.sub[q].cin_pad, L.sub[q].kpad, L.sub[q].filters, L.sub[q].cout_pad, L.sub[q].bn, L.sub[q].act);
+            put(" state=own(%dx%dx%d)\n", L.H, L.W, L.cin);
+        }
     }
     for (size_t k = 0; r == YOLO_OK && k < c.storages.size(); ++k) {
         const Storage &s = c.storages[k];

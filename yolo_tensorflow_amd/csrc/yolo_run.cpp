@@ -199,6 +199,83 @@ static int run_conv(yolo_ctx *c, int i, int n)
     return YOLO_OK;
 }
 
+// [rnn] / [gru] / [lstm]: one time step of streams 0 .. n - 1 in the layer's one or two launches (RecurArgs, kernels.h; recur_geom), then the copy that
+// makes the new state the state.  Streams n .. max_batch - 1 are not touched
+static int run_recurrent(yolo_ctx *c, int i, int n)
+{
+    const Layer &L = c->layers[i]; hipStream_t s = c->stream;
+    const RecurGeom g = recur_geom(c, L); const TView in = view_of(c, L.in[0]);
+    RecurArgs a; memset(&a, 0, sizeof a);
+    a.dt = L.in_dt; a.units = L.filters; a.n = n; a.act = L.act; a.shortcut = L.rshortcut; a.tanh_ = L.rtanh;
+    a.s_stride = g.s_stride; a.c = L.d_c; a.h32 = L.d_h32; a.z = L.d_z; a.rh = L.d_rh; a.h_new = L.d_hn; a.hs = L.d_h;
+    a.out = L.out.ptr; a.out_stride = L.out.stride; a.out_dt = L.out.dt;
+    a.mode = g.mode[0]; a.w = L.d_w; a.bx = L.d_b; a.bh = L.d_b + g.Mp[0];
+    a.x = in.ptr; a.x_stride = g.x_len; a.x_len = g.x_len; a.Kx = g.Kx[0];          // the flattened producer: one "pixel" of fc_h * fc_w * stride elements per stream
+    a.h = L.d_h; a.h_stride = g.s_stride; a.h_len = g.s_stride; a.Kh = g.Kh[0];
+    HIPCK(c, launch_recur(a, s));
+    if (g.launches == 2) {
+        a.mode = g.mode[1]; a.w = L.d_w2; a.bx = L.d_b2; a.bh = L.d_b2 + g.Mp[1]; a.Kx = g.Kx[1]; a.Kh = g.Kh[1];
+        if (L.rkind == RECUR_RNN) { a.x = L.d_hn; a.x_stride = a.x_len = g.s_stride; a.h = nullptr; a.h_stride = a.h_len = 0; }      // the output sublayer over the new state
+        else a.h = L.d_rh;                                                                                                          // [x | r * h]
+        HIPCK(c, launch_recur(a, s));
+    }
+    // every launch that reads the old state as an operand has been issued: the new one takes its place.  A copy, not a swap of pointers: a
+    // captured step holds both
+    if (L.d_hn) HIPCK(c, hipMemcpyAsync(L.d_h, L.d_hn, (size_t)n * g.s_stride * dt_size(L.in_dt), hipMemcpyDeviceToDevice, s));
+    return YOLO_OK;
+}
+
+// [crnn]: its three convs through the dense conv kernels' own selection rule; the epilogue's residual sums the state (run after the activation, as a
+// folded [shortcut] is) where the activation is of the slope family, else k_activate and an add launch behind the conv do.  in -> d_rh = [state +] act(conv_in(x)); state -> d_hn = d_rh + act(conv_self(state)); d_hn -> out = act(conv_out(state')); then the
+// copy that makes the new state the state: both reads of the old one have been issued by then
+static int run_crnn(yolo_ctx *c, int i, int n)
+{
+    const Layer &L = c->layers[i]; hipStream_t s = c->stream;
+    const TView in = view_of(c, L.in[0]);
+    TView st; st.n = n; st.h = L.H; st.w = L.W; st.c = L.cin; st.stride = roundup(L.cin, 8); st.dt = L.in_dt; st.ptr = L.d_h;
+    TView mid = st, nw = st; mid.ptr = L.d_rh; nw.ptr = L.d_hn;
+    const TView *ins[3] = {&in, &st, &nw}, *res[3] = {L.rshortcut ? &st : nullptr, &mid, nullptr}, *outs[3] = {&mid, &nw, &L.out};
+    const bool post = !act_is_slope(L.act);          // an activation the conv epilogue does not apply (the section's default, logistic, is one)
+    for (int q = 0; q < 3; ++q) {
+        const Layer &S = L.sub[q];
+        ConvArgs a; memset(&a, 0, sizeof a);
+        a.in = ins[q]->ptr; a.in_stride = ins[q]->stride; a.wt = S.d_w; a.bias = S.d_b; a.out = outs[q]->ptr; a.out_stride = outs[q]->stride; a.out_dt = outs[q]->dt; a.in_dt = S.in_dt;
+        a.out_inv_scale = 1.f; a.res_scale = 1.f; a.mid_scale = 1.f; a.mid_inv_scale = 1.f;
+        if (res[q] && !post) { a.res = res[q]->ptr; a.res_stride = res[q]->stride; }
+        a.N = n; a.H = L.H; a.W = L.W; a.Cin_pad = S.cin_pad; a.Ho = L.H; a.Wo = L.W; a.Cout = S.filters;
+        a.ksize = 3; a.stride = 1; a.pad = 1; a.Kpad = S.kpad; a.kchunk = conv_kchunk(S.cin_pad, S.in_dt); a.act = post ? ACT_LINEAR : S.act; a.zeros = c->d_zeros;
+        conv_finalize(a);
+        if (c->dtype == YOLO_FP32) HIPCK(c, launch_conv_f32(a, s));
+        else HIPCK(c, launch_conv_bf16(a, conv_resolve_cfg(a, -1), s));
+        if (post) {          // as a conv layer with such an activation: a linear epilogue, k_activate in place; then the sum the epilogue could not take
+            TView o = *outs[q]; o.n = n;
+            HIPCK(c, launch_activate(o, false, L.act, s));
+            if (res[q]) HIPCK(c, launch_add(o, *res[q], o, s));
+        }
+    }
+    HIPCK(c, hipMemcpyAsync(L.d_h, L.d_hn, (size_t)n * state_elems(c, L) * dt_size(L.in_dt), hipMemcpyDeviceToDevice, s));
+    return YOLO_OK;
+}
+
+// ---- states across forwards of the library's own (yolo_time_forward, yolo_time_layers and through them yolo_autotune): kept before, handed back after.
+//      Per recurrent layer 8 bytes per element of d_state_keep: the operand-type state, then the layer's fp32 tensor ([gru] state, [lstm] cell) ----
+static int state_move(yolo_ctx *c, bool restore)
+{
+    char *k = (char *)c->d_state_keep;
+    for (Layer &L : c->layers) {
+        if (!has_state(L)) continue;
+        const size_t ne = (size_t)c->max_batch * state_elems(c, L), es = dt_size(L.in_dt);
+        float *f32 = L.type == L_CRNN ? nullptr : L.rkind == RECUR_GRU ? L.d_h32 : L.d_c;
+        HIPCK(c, restore ? hipMemcpyAsync(L.d_h, k, ne * es, hipMemcpyDeviceToDevice, c->stream) : hipMemcpyAsync(k, L.d_h, ne * es, hipMemcpyDeviceToDevice, c->stream));
+        if (f32) HIPCK(c, restore ? hipMemcpyAsync(f32, k + ne * 4, ne * 4, hipMemcpyDeviceToDevice, c->stream) : hipMemcpyAsync(k + ne * 4, f32, ne * 4, hipMemcpyDeviceToDevice, c->stream));
+        k += ne * 8;
+    }
+    return YOLO_OK;
+}
+int state_keep(yolo_ctx *c) { return c->states.empty() ? YOLO_OK : state_move(c, false); }
+int state_restore(yolo_ctx *c) { return c->states.empty() ? YOLO_OK : state_move(c, true); }
+namespace { struct StateGuard { yolo_ctx *c; ~StateGuard() { state_restore(c); } }; }      // hands the states back on every return path
+
 static void yolo_anchors(const yolo_ctx *c, const Layer &Y, float *out)      // a [yolo] head's anchors in cells: pixels over the head's stride
 {
     const int stride[2] = {c->in_w / Y.W, c->in_h / Y.H};          // along x (anchor widths), along y (anchor heights)
@@ -369,6 +446,8 @@ int run_layer(yolo_ctx *c, int i, int n)
                                   c->d_scores, c->d_labels, s));
         break; }
     case L_YOLO: case L_REGION: return run_decode(c, i, n);
+    case L_RECUR: return run_recurrent(c, i, n);
+    case L_CRNN: return run_crnn(c, i, n);
     }
     return YOLO_OK;
 }
@@ -862,6 +941,8 @@ int yolo_time_forward(yolo_ctx *c, int n, int iters, float *total_ms, float *con
     HIPCK(c, hipSetDevice(c->device));
     EventSet evs(2); if (!evs.ok) return fail(c, YOLO_ERR_HIP, "hipEventCreate failed");
     hipEvent_t e0 = evs.e[0], e1 = evs.e[1];
+    if (int r = state_keep(c)) return r;          // the passes below are steps of no stream: every state is handed back as it was found
+    StateGuard guard{c};
     c->lean = false;
     if (c->stem_u8 && n > c->stem_u8_n) c->stem_u8 = nullptr;      // the staged uint8 buffer holds fewer images: the stem reads c->input instead
     if (total_ms) {
@@ -898,6 +979,8 @@ int yolo_time_layers(yolo_ctx *c, int n, int iters, float *ms_out)
     if (c->stem_u8 && n > c->stem_u8_n) c->stem_u8 = nullptr;      // see yolo_time_forward
     EventSet evs(NL + 1); if (!evs.ok) return fail(c, YOLO_ERR_HIP, "hipEventCreate failed");
     std::vector<hipEvent_t> &ev = evs.e;
+    if (int r = state_keep(c)) return r;          // see yolo_time_forward
+    StateGuard guard{c};
     std::vector<double> acc(NL, 0.0);
     for (int it = 0; it < iters; ++it) {
         HIPCK(c, hipEventRecord(ev[0], c->stream));

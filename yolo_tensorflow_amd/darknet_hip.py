@@ -54,6 +54,7 @@ _PROTOTYPES = {
     "make_network_boxes": (C.POINTER(DETECTION), [C.c_void_p, C.c_float, C.POINTER(C.c_int)]),
     "free_ptrs": (None, [C.POINTER(C.c_void_p), C.c_int]),
     "reset_rnn": (None, [C.c_void_p]),
+    "reset_network_state": (None, [C.c_void_p, C.c_int]),
     "set_batch_network": (None, [C.c_void_p, C.c_int]),
     "letterbox_image": (IMAGE, [IMAGE, C.c_int, C.c_int]),
     "get_metadata": (METADATA, [C.c_char_p]),

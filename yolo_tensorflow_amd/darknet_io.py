@@ -230,6 +230,11 @@ def layer_shapes(secs):
         elif t == "connected":               # flattens its producer (CHW order, DN/connected_layer.c:151) to `output` values
             cin = H * W * C
             H, W, C = 1, 1, int(s["output"])
+        elif t == "crnn":                    # three 3x3 / 1 / 1 convs around a state map of hidden_filters channels (DN/crnn_layer.c)
+            C = int(s["output_filters"])
+        elif t in RECURRENT:                 # [rnn] / [gru] / [lstm]: read their producer as [connected] does, `output` values per time step
+            cin = H * W * C
+            H, W, C = 1, 1, int(s["output"])
         elif t == "local":                   # locally connected: unshared filters per output location (DN/local_layer.c:10-24)
             k, st, pad = int(s["size"]), int(s.get("stride", 1)), int(s.get("pad", 0))
             H, W, C = ((H - 1) if pad else (H - k)) // st + 1, ((W - 1) if pad else (W - k)) // st + 1, int(s["filters"])
@@ -241,6 +246,40 @@ def layer_shapes(secs):
             raise ValueError("unsupported layer type [%s]" % t)
         shapes.append((t, H, W, C, cin))
     return shapes
+
+
+# the [connected] sublayers of a recurrent layer in file order (DN/parser.c:1281-1314): "h" = over the state (`output` inputs), "x" = over the layer's input
+RECURRENT = {"rnn": "xhh",               # input, self, output
+             "gru": "hhhxxx",            # wz wr wh uz ur uh
+             "lstm": "hhhhxxxx"}         # wi wf wo wg ui uf uo ug
+
+
+def connected_floats(inputs, outputs, bn):
+    """one [connected] (sub)layer in a weight stream: biases, weights [outputs][inputs], then scales, rolling mean, rolling variance when batch-normalised"""
+    return outputs * (1 + inputs + (3 if bn else 0))
+
+
+def recurrent_specs(secs):
+    """Per [rnn] / [gru] / [lstm] layer: dict(index, type, inputs, outputs, bn, subs) -- subs the (inputs, outputs) of its sublayers in file order."""
+    shapes = layer_shapes(secs)
+    out = []
+    for i, s in enumerate(secs[1:]):
+        if s["type"] in RECURRENT:
+            cin, n = shapes[i][4], int(s["output"])
+            out.append(dict(index=i, type=s["type"], inputs=cin, outputs=n, bn=int(s.get("batch_normalize", 0)),
+                            subs=[(cin if k == "x" else n, n) for k in RECURRENT[s["type"]]]))
+    return out
+
+
+def crnn_specs(secs):
+    """Per [crnn] layer: dict(index, bn, convs) -- convs the (cin, filters) of its input, self and output convs (3x3), each stored as a [convolutional] layer is."""
+    shapes = layer_shapes(secs)
+    out = []
+    for i, s in enumerate(secs[1:]):
+        if s["type"] == "crnn":
+            hid, n = int(s["hidden_filters"]), int(s["output_filters"])
+            out.append(dict(index=i, bn=int(s.get("batch_normalize", 0)), convs=[(shapes[i][4], hid), (hid, hid), (hid, n)]))
+    return out
 
 
 def conv_specs(secs):
@@ -258,7 +297,8 @@ def conv_specs(secs):
                             groups=int(s.get("groups", 1)) if s["type"] == "convolutional" else 1,
                             bn=int(s.get("batch_normalize", 0)), head=head, index=i))
         elif s["type"] == "connected":
-            out.append(dict(filters=int(s["output"]), size=1, cin=shapes[i][4], bn=0, head=head, index=i))
+            # (batch-normalised: the same count as a conv's, but biases, weights, scales, rolling mean, rolling variance in the file)
+            out.append(dict(filters=int(s["output"]), size=1, cin=shapes[i][4], bn=int(s.get("batch_normalize", 0)), head=head, index=i))
         elif s["type"] == "local":           # biases [filters * locations], weights [locations][filters][cin][k][k] (DN/parser.c:1315-1320)
             out.append(dict(filters=int(s["filters"]), size=int(s["size"]), cin=shapes[i][4], bn=0, head=False, index=i, locations=shapes[i][1] * shapes[i][2]))
     return out
@@ -269,6 +309,10 @@ def weights_count(secs):
     for c in conv_specs(secs):
         loc = c.get("locations", 1)
         n += c["filters"] * loc * (4 if c["bn"] else 1) + loc * c["filters"] * (c["cin"] // c.get("groups", 1)) * c["size"] ** 2
+    for r in recurrent_specs(secs):
+        n += sum(connected_floats(i, o, r["bn"]) for i, o in r["subs"])
+    for r in crnn_specs(secs):
+        n += sum(f * (4 if r["bn"] else 1) + f * cin * 9 for cin, f in r["convs"])
     return n
 
 
@@ -371,9 +415,29 @@ def synth_weights(secs, seed=0, obj_bias=-0.75, stats="benign"):
                                     np.stack([rng.uniform(.1, .9, S * S * B), rng.uniform(.1, .9, S * S * B),
                                               rng.uniform(.3, .8, S * S * B), rng.uniform(.3, .8, S * S * B)], -1).reshape(-1)])
                 parts += [b, rng.normal(0, 0.05 * np.sqrt(1.0 / (cin * max(cur, 1e-6))), n * cin)]
+            elif int(s.get("batch_normalize", 0)):
+                parts += _connected_parts(rng, cin, n, cur, True)
             else:
                 parts += [rng.normal(0, .1, n), rng.normal(0, np.sqrt(2.0 / (cin * max(cur, 1e-6))), n * cin)]
             cur = 1.0 + 0.01 if s.get("activation", "logistic") != "leaky" else 1.01
+        elif t == "crnn":
+            # three convs by the conv recipe above; the state map's second moment is taken as that of two activated conv outputs
+            bn = int(s.get("batch_normalize", 0)); leaky = 0.505 if s.get("activation", "logistic") == "leaky" else 1.0
+            hid, n = int(s["hidden_filters"]), int(s["output_filters"])
+            for cin, f, m in ((shapes[i][4], hid, cur), (hid, hid, 2.0 * leaky), (hid, n, 2.0 * leaky)):
+                if bn:
+                    pre_var = 2.0 * m
+                    parts += [rng.normal(0, .1, f), rng.uniform(.8, 1.2, f), rng.normal(0, .1 * np.sqrt(pre_var), f), pre_var * rng.uniform(.8, 1.25, f),
+                              rng.normal(0, np.sqrt(2.0 / (9 * cin)), f * cin * 9)]
+                else:
+                    parts += [rng.normal(0, .1, f), rng.normal(0, np.sqrt(1.0 / (9 * cin * max(m, 1e-6))), f * cin * 9)]
+            cur = 1.01 * leaky
+        elif t in RECURRENT:
+            # every sublayer a [connected] layer of its own; the state's second moment is taken as 1/4 (gated values lie in -1 .. 1)
+            n, cin, bn = int(s["output"]), shapes[i][4], int(s.get("batch_normalize", 0))
+            for k in RECURRENT[t]:
+                parts += _connected_parts(rng, cin if k == "x" else n, n, cur if k == "x" else 0.25, bn)
+            cur = 0.25
         elif t == "shortcut":
             f = int(s["from"]); f = f if f >= 0 else i + f
             # leaky outputs have a positive mean, so residual branches add coherently: use the fully
@@ -386,6 +450,15 @@ def synth_weights(secs, seed=0, obj_bias=-0.75, stats="benign"):
             cur = sum(m2[l] * shapes[l][3] for l in ls) / tot
         m2.append(cur)
     return np.concatenate(parts).astype(np.float32)
+
+
+def _connected_parts(rng, cin, n, cur, bn):
+    """one [connected] (sub)layer of synth_weights, in file order; batch-normalised: the conv recipe (rolling variance = what the rows produce)"""
+    if not bn:
+        return [rng.normal(0, .1, n), rng.normal(0, np.sqrt(2.0 / (cin * max(cur, 1e-6))), n * cin)]
+    pre_var = 2.0 * cur
+    return [rng.normal(0, .1, n), rng.normal(0, np.sqrt(2.0 / cin), n * cin), rng.uniform(.8, 1.2, n),
+            rng.normal(0, .1 * np.sqrt(pre_var), n), pre_var * rng.uniform(.8, 1.25, n)]
 
 
 def bf16_exact_filters(secs, flat, floor=2.0 ** -10):

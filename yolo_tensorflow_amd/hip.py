@@ -48,6 +48,7 @@ EXPORTS = [
     "yolo_op_tree_softmax", "yolo_op_tree_top", "yolo_activation_code", "yolo_op_activate", "yolo_op_shortcut",
     "yolo_output_map_geometry", "yolo_output_map", "yolo_label_map", "yolo_segment_images_u8", "yolo_op_deconv2d", "yolo_op_l2norm", "yolo_op_upsample", "yolo_op_label_map",
     "yolo_op_conv2d_grouped", "yolo_op_conv2d_pad",
+    "yolo_num_state_tensors", "yolo_state_geometry", "yolo_get_state", "yolo_set_state", "yolo_reset_state",
 ]
 HIER_CONDITIONAL, HIER_ABSOLUTE, HIER_LEAVES = 0, 1, 2
 _HIER_MODES = {None: HIER_CONDITIONAL, "conditional": HIER_CONDITIONAL, "absolute": HIER_ABSOLUTE, "leaves": HIER_LEAVES}
@@ -165,6 +166,11 @@ def load_library():
     l.yolo_op_l2norm.argtypes = [P, I, I, I, I, I, P, I]
     l.yolo_op_upsample.argtypes = [P, I, I, I, I, I, F, I, P, I]
     l.yolo_op_label_map.argtypes = [P, I, I, I, I, F, P, I]
+    l.yolo_num_state_tensors.argtypes = [P]
+    l.yolo_state_geometry.argtypes = [P, I, C.POINTER(I), C.POINTER(SZ)]
+    l.yolo_get_state.argtypes = [P, I, I, P, SZ]
+    l.yolo_set_state.argtypes = [P, I, I, P, SZ]
+    l.yolo_reset_state.argtypes = [P, I]
     l.yolo_shard_bounds.argtypes = [I, I, I, C.POINTER(I), C.POINTER(I)]
     l.yolo_dist_flat_words.argtypes = [I, I]; l.yolo_dist_flat_words.restype = C.c_size_t
     l.yolo_dist_split_records.argtypes = [P, I, I, I, P, P]
@@ -627,6 +633,30 @@ class Engine:
 
     def synchronize(self):
         self._check(self.lib.yolo_synchronize(self.ctx), "yolo_synchronize")
+
+    # ---- recurrent networks ([rnn] / [gru] / [lstm]): one call is one time step, batch index b is stream b (include/yolo_hip.h) ----
+    @property
+    def num_state_tensors(self):
+        return self.lib.yolo_num_state_tensors(self.ctx)
+
+    def state_geometry(self, k):
+        """(layer index, floats per stream) of state tensor k"""
+        layer, n = C.c_int(0), C.c_size_t(0)
+        self._check(self.lib.yolo_state_geometry(self.ctx, k, C.byref(layer), C.byref(n)), "yolo_state_geometry")
+        return layer.value, n.value
+
+    def state(self, k, stream):
+        out = np.empty(self.state_geometry(k)[1], dtype=np.float32)
+        self._check(self.lib.yolo_get_state(self.ctx, k, stream, out.ctypes.data, out.size), "yolo_get_state")
+        return out
+
+    def set_state(self, k, stream, values):
+        v = np.ascontiguousarray(values, dtype=np.float32).reshape(-1)
+        self._check(self.lib.yolo_set_state(self.ctx, k, stream, v.ctypes.data, v.size), "yolo_set_state")
+
+    def reset_state(self, stream=None):
+        """zero the states of one stream, or of every stream (darknet's reset_network_state)"""
+        self._check(self.lib.yolo_reset_state(self.ctx, -1 if stream is None else int(stream)), "yolo_reset_state")
 
     # ---- introspection / measurement ----
     def layer_output(self, index, n):
