@@ -120,7 +120,12 @@ enum yolo_fit {
     YOLO_FIT_LETTERBOX = 1,    /* darknet letterbox_image: darknet's (float)p/255., aspect-preserving resize_image, 0.5 fill, centred
                                 * (yolo_forward_letterbox_chw on the same image converted on the host, DN/image.c:960-981) */
     YOLO_FIT_CV2 = 2,          /* V2 preprocess_image: cv2.resize INTER_LINEAR, then /225 (yolo_op_resize_cv2, V2/utils.py:13-27), RGB in */
-    YOLO_FIT_CV2_BGR = 3       /* the same on a BGR image: the RGB swap of cv2.cvtColor(.., COLOR_BGR2RGB) first */
+    YOLO_FIT_CV2_BGR = 3,      /* the same on a BGR image: the RGB swap of cv2.cvtColor(.., COLOR_BGR2RGB) first */
+    YOLO_FIT_CENTER_CROP = 4   /* darknet's classifier validation (DN/examples/classifier.c:635-636): darknet's (float)p/255., resize_min(im, net_w) -- the
+                                * shorter side becomes the network WIDTH, integer divisions, no resize where the size does not change --, then crop_image
+                                * of net_w x net_h from the centre, coordinates clamped (the edge is replicated, no fill; DN/image.c:857-875, :997-1011).
+                                * The forward and classify entry points take it; yolo_detect_images_* and yolo_segment_images_u8 return
+                                * YOLO_ERR_UNSUPPORTED: boxes and labels cannot be mapped back through a crop that discards part of the image */
 };
 /* Units of the records yolo_detect_images_* returns.
  * NETWORK: as yolo_postprocess returns them for an image at network size (STRETCH / CV2: normalised or network pixels by the decode;
@@ -196,8 +201,8 @@ int yolo_forward_letterbox_chw(yolo_ctx *ctx, const float *image_chw, int w, int
 /* A ragged batch of native-size uint8 RGB images in ONE device step: `pixels` holds n images packed in one buffer of `bytes` bytes (at
  * `loc`; YOLO_HOST: staged with one host-to-device copy), descs[n] (host memory) where each one lies.  One launch fits every image
  * into the network input (`fit`, enum yolo_fit), then as yolo_forward with n images.  YOLO_ERR_INVALID before any launch when n is
- * outside 1..max_batch, a descriptor has h < 1 or w < 1 or ends past `bytes`, `bytes` >= 2^32, or a letterboxed image would be less
- * than one pixel wide or high. */
+ * outside 1..max_batch, a descriptor has h < 1 or w < 1 or ends past `bytes`, `bytes` >= 2^32, a letterboxed image would be less
+ * than one pixel wide or high, or (YOLO_FIT_CENTER_CROP) an image's longer side times the network width does not fit an int. */
 int yolo_forward_images_u8(yolo_ctx *ctx, const uint8_t *pixels, size_t bytes, const yolo_image_desc *descs, int n, int fit, int loc,
                            float *detections_out, int out_loc);
 /* The same + threshold + NMS with each image's geometry (enum yolo_box_units): boxes_out [n * max_out], counts_out [n] at out_loc.
@@ -213,8 +218,8 @@ int yolo_detect_images_u8(yolo_ctx *ctx, const uint8_t *pixels, size_t bytes, co
 int yolo_detect_images_graph(yolo_ctx *ctx, const uint8_t *pixels, size_t bytes, const yolo_image_desc *descs, int n, int fit,
                              float score_thr, float iou_thr, int max_out, int nms_mode, int select_mode, int units,
                              yolo_box *boxes_out, int32_t *counts_out);
-/* The value one source byte `value` (0..255) contributes to a fit's arithmetic before interpolation: STRETCH value / 255.0f, LETTERBOX
- * darknet's (float)value/255. (a double division rounded to float, DN/image.c load_image_stb), CV2 the byte itself.  Host-side; the
+/* The value one source byte `value` (0..255) contributes to a fit's arithmetic before interpolation: STRETCH value / 255.0f, LETTERBOX and
+ * CENTER_CROP darknet's (float)value/255. (a double division rounded to float, DN/image.c load_image_stb), CV2 the byte itself.  Host-side; the
  * device evaluates the same expression. */
 float yolo_fit_unit_value(int fit, int value);
 
@@ -498,6 +503,10 @@ int yolo_op_conv2d_grouped(const float *x, int n, int h, int w, int cin, const f
                            int cout, int groups, int act, int dtype, int out_f32, float *out, int device);
 /* [l2norm]: per pixel x / sqrtf(sum over the channels of x^2); an all-zero pixel is NaN, as in the reference */
 int yolo_op_l2norm(const float *x, int n, int h, int w, int c, int dtype, float *out, int device);
+/* [normalization] / [lrn] (DN/normalization_layer.c:66-95) over the channels of every pixel: out[k] = x[k] * (kappa + alpha * (W(k) - g))^(-beta), W(k) the sum of
+ * x[j]^2 over k - (size - 1) / 2 <= j <= k + size / 2 inside the tensor, g = x[size / 2]^2 -- the channel the reference's running sum never adds -- or 0 where
+ * size / 2 == c.  1 <= size <= 17 and size / 2 <= c, else YOLO_ERR_UNSUPPORTED / YOLO_ERR_INVALID; a negative base is NaN, as in the reference */
+int yolo_op_lrn(const float *x, int n, int h, int w, int c, int size, float alpha, float beta, float kappa, int dtype, float *out, int device);
 /* darknet's [upsample]: nearest, out = scale * in, stride 1..8; out [n, h stride, w stride, c] */
 int yolo_op_upsample(const float *x, int n, int h, int w, int c, int stride, float scale, int dtype, float *out, int device);
 /* yolo_label_map's kernel on a host map [n,h,w,c] fp32: labels_out [n,h,w] */

@@ -426,6 +426,26 @@ def alexnet(size=227, classes=1000):
     return c.text()
 
 
+def alexnet_lrn(size=256, crop=227, classes=1000):
+    """The 2012 network as Caffe-era zoos carry it: `alexnet` above behind a leading [crop] of the 256 x 256 input to 227 x 227 (darknet's own
+    classifier cfgs begin that way; flip / angle / saturation / exposure act while training only), with local response normalisation
+    ([normalization] size=5 alpha=0.0001 beta=0.75 kappa=2) behind the max-pool of the first and of the second conv."""
+    c = Cfg(size)
+    pool = lambda: c._sec("maxpool", size=3, stride=2, padding=0)
+    lrn = lambda: c._sec("normalization", size=5, alpha=0.0001, beta=0.75, kappa=2)
+    c._sec("crop", crop_height=crop, crop_width=crop, flip=1, angle=0, saturation=1, exposure=1)
+    c._sec("convolutional", filters=96, size=11, stride=4, pad=0, activation="relu"); pool(); lrn()
+    c.conv(256, 5, bn=False, act="relu"); pool(); lrn()
+    c.conv(384, 3, bn=False, act="relu")
+    c.conv(384, 3, bn=False, act="relu")
+    c.conv(256, 3, bn=False, act="relu"); pool()
+    c.connected(4096, act="relu"); c.dropout()
+    c.connected(4096, act="relu"); c.dropout()
+    c.connected(classes, act="linear")
+    c.softmax()
+    return c.text()
+
+
 def synthetic_tree(nodes=9418, roots=10, seed=0, max_group=120):
     """A seeded tree in darknet's file format (DN/tree.c:83-139: `name parent` lines, the children of a node one contiguous run, a
     parent below its own index): the reference ships no 9k.tree.  Breadth-first: every run of siblings is appended whole, its size
@@ -487,6 +507,9 @@ def unet(size=416, classes=21, base=32):
     return c.text()
 
 
+HEADER = "# generated by tools/make_cfgs.py -- do not edit\n"
+
+
 def main():
     import sys
     if len(sys.argv) > 2 and sys.argv[1] == "--unet":          # python tools/make_cfgs.py --unet DIR: unet.cfg at 416 x 416
@@ -510,7 +533,13 @@ def main():
             f.write(dw_yolo() + "\n")
         print("wrote dw-yolo.cfg to", sys.argv[2])
         return
-    if len(sys.argv) > 2 and sys.argv[1] == "--resnext":       # python tools/make_cfgs.py --resnext DIR: the 101 and 152 depths (50 is shipped in cfg/zoo)
+    if len(sys.argv) > 2 and sys.argv[1] == "--alexnet-lrn":   # python tools/make_cfgs.py --alexnet-lrn DIR: alexnet-lrn.cfg, the file shipped as cfg/zoo/alexnet-lrn.cfg
+        os.makedirs(sys.argv[2], exist_ok=True)
+        with open(os.path.join(sys.argv[2], "alexnet-lrn.cfg"), "w") as f:
+            f.write(HEADER + alexnet_lrn())
+        print("wrote alexnet-lrn.cfg to", sys.argv[2])
+        return
+    if len(sys.argv) > 2 and sys.argv[1] == "--resnext":     # python tools/make_cfgs.py --resnext DIR: the 101 and 152 depths (50 is shipped in cfg/zoo)
         os.makedirs(sys.argv[2], exist_ok=True)
         for depth in (101, 152):
             with open(os.path.join(sys.argv[2], "resnext%d.cfg" % depth), "w") as f:
@@ -534,12 +563,12 @@ def main():
         "darknet19.cfg": darknet19(256), "darknet53.cfg": darknet53(256),
         # cfg/zoo/: classifiers of darknet's model zoo that are no YOLO backbone (cfg/ itself is the set tests/golden/plan_tables.json pins)
         "zoo/resnet18.cfg": resnet(18), "zoo/resnet50.cfg": resnet(50), "zoo/vgg-16.cfg": vgg16(),
-        "zoo/resnext50.cfg": resnext(50), "zoo/alexnet.cfg": alexnet(),
+        "zoo/resnext50.cfg": resnext(50), "zoo/alexnet.cfg": alexnet(), "zoo/alexnet-lrn.cfg": alexnet_lrn(),
     }
     os.makedirs(os.path.join(OUT, "zoo"), exist_ok=True)
     for name, text in files.items():
         with open(os.path.join(OUT, name), "w") as f:
-            f.write("# generated by tools/make_cfgs.py -- do not edit\n" + text)
+            f.write(HEADER + text)
         print("wrote", name)
 
 

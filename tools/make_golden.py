@@ -34,6 +34,10 @@ Runs only in the build container (it reads /root/reference and oracle/_ref); the
                     recurrent networks ([rnn], [gru], [lstm] behind a conv stack, a classifier; two [crnn] layers in front of a [yolo] head):
                     ONE live network of the compiled reference over 5 frames, every layer's output after each frame (mini_crnn: the boxes too), and
                     drift16_*: the stand-off of the 16-bit-rounded host restatement (tests/test_recurrent_host.py) per frame and layer
+  mini_lrn.npz / lrn_crop_cases.npz
+                    [crop] and [normalization]: a classifier that opens with a [crop] and has two LRN layers (three images, every layer), eleven
+                    stand-alone [normalization] shapes behind a 1x1 conv, four [crop] networks, and six uint8 images through the reference's
+                    resize_min + crop_image (the classifier's validation preprocessing); fixed member dates
   yolov3_bn_real.npz / yolov2_bn_real.npz
                      the COMPLETE batch-norm vectors (beta, gamma, rolling mean, rolling variance) of every
                      batch-normalised conv of yolov3.weights / yolov2.weights, and the first l.n filter
@@ -1182,6 +1186,141 @@ def gen_mini_seq(seed=93):
           "drift bf16 %.3g fp16 %.3g" % (data["drift16_bf16"].max(), data["drift16_fp16"].max()), os.path.getsize(path), "bytes")
 
 
+def _lrn(size=None, alpha=None, beta=None, kappa=None):
+    keys = [("size", size), ("alpha", alpha), ("beta", beta), ("kappa", kappa)]
+    return "[normalization]\n" + "".join("%s=%s\n" % (k, v) for k, v in keys if v is not None) + "\n"
+
+
+def _crop(height, width, noadjust=False):
+    return "[crop]\ncrop_height=%d\ncrop_width=%d\nflip=1\nangle=0\nsaturation=1\nexposure=1\n%s\n" % (height, width, "noadjust=1\n" if noadjust else "")
+
+
+def mini_lrn_cfg(height=20, width=26):
+    """AlexNet's opening in miniature: a leading [crop] of the 20 high x 26 wide input to 16 x 21 (odd differences), a 3x3 conv to 13 filters, [normalization]
+    size=5 with darknet's defaults, a 2/2 max-pool, a 3x3 conv to 24 filters, [normalization] size=4 alpha=0.05 kappa=1.5 -- an even window, whose two reaches
+    differ, and an alpha at which the channel the reference's running sum never adds is a tenth of the sum --, a 1x1 conv to 10 classes, [avgpool], [softmax]."""
+    return ("[net]\nbatch=1\nwidth=%d\nheight=%d\nchannels=3\n\n" % (width, height) + _crop(16, 21) + _conv(13, 3, bn=False) + _lrn(size=5) +
+            "[maxpool]\nsize=2\nstride=2\n\n" + _conv(24, 3, bn=False) + _lrn(size=4, alpha=0.05, kappa=1.5) + _conv(10, 1, bn=False, act="linear") + "[avgpool]\n\n[softmax]\ngroups=1\n")
+
+
+LRN_CASES = [(7, 5), (13, 6), (9, 3), (5, 1), (3, 5), (2, 5), (2, 4), (96, 5), (520, 5), (24, 16)]          # (channels, size): tests/test_lrn_crop_host.py says why each
+LRN_BETA_CASE = (11, 5, 0.6)          # ... and one whose beta is not the default: the kernel's other power
+LRN_ALPHA, LRN_KAPPA = 0.05, 1.5
+CROP_CASES = [("odd", 11, 14, 8, 9, False, 0), ("noadjust", 11, 14, 8, 9, True, 0), ("whole", 11, 14, 11, 14, False, 0), ("conv20", 11, 14, 8, 9, False, 20)]      # (name, H, W, crop_h, crop_w, noadjust, channels of a 3x3 conv in front)
+# (name, network h, w, image h, w): darknet's validation fit, resize_min(im, net_w) then the centred crop_image
+FIT_CASES = [("landscape", 16, 16, 20, 33), ("portrait", 16, 16, 37, 19), ("same", 16, 16, 16, 23), ("upscale", 16, 16, 9, 13), ("one_wide", 16, 16, 21, 1), ("rect_short", 24, 16, 30, 40)]
+
+
+def gen_lrn_crop(seed=109):          # (a seed at which channel 2 of mini_lrn's second conv -- the one its [normalization] never adds -- is of the tensor's own size; biases of N(0, 1) decide that)
+    """[normalization], [crop] and the classifier's validation fit through the compiled reference (normalization_layer.c, crop_layer.c; image.c
+    resize_min + crop_image).  mini_lrn.npz: mini_lrn_cfg, weights, three images, every layer's output for each of them (separate predicts).
+    lrn_crop_cases.npz: per LRN case a 1x1 linear conv + [normalization] on a 5 x 7 input -- the conv's output is lrn_C_size_x, the layer's lrn_C_size_y --;
+    per [crop] case cfg, weights, one image and every layer's output; per fit case a seeded uint8 image and the reference's float network input.
+    Asserted here: leaving the never-added channel out of the closed form (tests/test_lrn_crop_host.py lrn_ref) moves mini_lrn's second [normalization] by
+    more than twenty times the 5e-4 bound of the fp32 network test, and every stand-alone case that has such a channel by far more than fp32 rounding --
+    else the fixtures would not pin it."""
+    import ctypes as C
+    import importlib.util
+    from oracle import darknet_ref as D
+    from yolo_tensorflow_amd import darknet_io as IO
+    spec = importlib.util.spec_from_file_location("test_lrn_crop_host", os.path.join(ROOT, "tests", "test_lrn_crop_host.py"))
+    sys.path.insert(0, os.path.join(ROOT, "tests")); LH = importlib.util.module_from_spec(spec); spec.loader.exec_module(LH)
+
+    def run(cfg, flat, x):
+        net = D.RefNet(cfg, flat, 0, 2)
+        net.predict(x)
+        outs = [np.asarray(net.layer_output_nhwc(i), dtype=np.float32) for i in range(net.n)]
+        net.close()
+        return outs
+
+    def pins_ghost(x, y, size, alpha, beta, kappa):
+        with_g = LH.lrn_ref(x, size, alpha, beta, kappa); without = LH.lrn_ref(x, size, alpha, beta, kappa, ghost=False)
+        assert np.abs(with_g - y).max() < 1e-5 * np.abs(y).max(), "the closed form does not give the reference's output"
+        return float(np.abs(without - y).max() / np.abs(y).max())
+
+    # ---- mini_lrn ----
+    cfg = mini_lrn_cfg(); secs = IO.parse_cfg(cfg); shapes = IO.layer_shapes(secs)
+    flat = IO.synth_weights(secs, seed=seed)
+    last = IO.conv_specs(secs)[-1]
+    tail = last["filters"] * (1 + last["cin"] * last["size"] ** 2)
+    imgs = np.random.default_rng(seed + 1).integers(0, 256, (3, 20, 26, 3), dtype=np.uint8)
+    x = imgs.astype(np.float32) / np.float32(255.0)
+    logit_layer = len(secs) - 4
+    # the second conv (bias and filters; leaky is homogeneous), until its output's root mean square is 1.5: at alpha = 0.05 the never-added channel is then
+    # about a tenth of norms.  Then the class conv, until the logits reach +-5 (gen_mini_cls)
+    first, second = IO.conv_specs(secs)[:2]
+    lo = first["filters"] * (1 + first["cin"] * first["size"] ** 2); hi = lo + second["filters"] * (1 + second["cin"] * second["size"] ** 2)
+    flat[lo:hi] *= np.float32(round(1.5 / float(np.sqrt(np.mean(run(cfg, flat, x[0])[4].astype(np.float64) ** 2))), 2))
+    flat[-tail:] *= np.float32(round(5.0 / float(np.abs(run(cfg, flat, x[0])[logit_layer]).max()), 2))
+    per_image = [run(cfg, flat, x[b]) for b in range(3)]
+    data = {"cfg": np.array(cfg), "weights": flat, "images_u8": imgs, "logit_layer": np.int32(logit_layer)}
+    for i in range(len(shapes)):
+        data["layer_%02d" % i] = np.stack([o[i].reshape(shapes[i][1:4]) for o in per_image])
+        assert np.isfinite(data["layer_%02d" % i]).all()
+    data["max_abs_logit"] = np.float32(np.abs(data["layer_%02d" % logit_layer]).max())
+    pooled = data["layer_%02d" % (len(shapes) - 2)].reshape(3, -1)
+    top2 = np.sort(pooled, axis=-1)[:, -2:]
+    data["top1_margin"] = (top2[:, 1] - top2[:, 0]).astype(np.float32)
+    assert float(data["top1_margin"].min()) > 2 * TOL16_BF16 * float(np.abs(pooled).max()), "a top-1 margin below twice the bf16 bound: change the seed, not the rule"
+    gap = pins_ghost(data["layer_04"], data["layer_05"], 4, 0.05, 0.75, 1.5)
+    assert gap > 20 * MARGIN_TOL, "mini_lrn: the never-added channel moves the second [normalization] by %.2e of its scale only" % gap
+    pins_ghost(data["layer_01"], data["layer_02"], 5, 1e-4, 0.75, 1.0)
+    path = os.path.join(OUT, "mini_lrn.npz")
+    save_npz_reproducibly(path, data)
+    print("mini_lrn layers", len(shapes), "max|logit| %.2f" % float(data["max_abs_logit"]), "top-1 margins", data["top1_margin"], "ghost gap %.3f of the scale" % gap, os.path.getsize(path), "bytes")
+
+    # ---- stand-alone cases ----
+    data = {"lrn_alpha": np.float32(LRN_ALPHA), "lrn_kappa": np.float32(LRN_KAPPA)}
+    rng = np.random.default_rng(seed + 2)
+    for k, (ch, size, beta) in enumerate([(c, s, 0.75) for c, s in LRN_CASES] + [LRN_BETA_CASE]):
+        cfg = "[net]\nbatch=1\nwidth=7\nheight=5\nchannels=3\n\n" + _conv(ch, 1, bn=False, act="linear") + _lrn(size, LRN_ALPHA, beta, LRN_KAPPA)
+        secs = IO.parse_cfg(cfg)
+        outs = run(cfg, IO.synth_weights(secs, seed=seed + 10 + k), rng.random((5, 7, 3), dtype=np.float32))
+        tag = "lrn_%d_%d" % (ch, size) + ("" if beta == 0.75 else "_beta")
+        data[tag + "_x"], data[tag + "_y"] = outs[0][0], outs[1][0]
+        if beta != 0.75:
+            data[tag] = np.float32(beta)
+        gap = pins_ghost(outs[0][0], outs[1][0], size, LRN_ALPHA, beta, LRN_KAPPA)
+        assert (gap > 100 * 2.0 ** -20) == (size // 2 < ch), (tag, gap)
+        print(tag, "max|x| %.2f" % float(np.abs(outs[0]).max()), "ghost gap %.3g of the scale" % gap)
+    for name, h, w, ch_, cw_, noadjust, front in CROP_CASES:
+        cfg = ("[net]\nbatch=1\nwidth=%d\nheight=%d\nchannels=3\n\n" % (w, h) + (_conv(front, 3, bn=False) if front else "") + _crop(ch_, cw_, noadjust) +
+               _conv(6, 1, bn=False, act="linear"))
+        secs = IO.parse_cfg(cfg); shapes = IO.layer_shapes(secs)
+        flat = IO.synth_weights(secs, seed=seed + 40)
+        img = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
+        outs = run(cfg, flat, img.astype(np.float32) / np.float32(255.0))
+        data["crop_%s_cfg" % name], data["crop_%s_weights" % name], data["crop_%s_image_u8" % name] = np.array(cfg), flat, img
+        for i, o in enumerate(outs):
+            data["crop_%s_layer_%02d" % (name, i)] = o[0]
+            assert o[0].shape == shapes[i][1:4]
+    # the fit: darknet's `image` by value (DN/include/darknet.h: w, h, c, data), planar float
+    class IMAGE(C.Structure):
+        _fields_ = [("w", C.c_int), ("h", C.c_int), ("c", C.c_int), ("data", C.POINTER(C.c_float))]
+    lib = D.lib()
+    lib.resize_min.argtypes = [IMAGE, C.c_int]; lib.resize_min.restype = IMAGE
+    lib.crop_image.argtypes = [IMAGE, C.c_int, C.c_int, C.c_int, C.c_int]; lib.crop_image.restype = IMAGE
+    lib.free_image.argtypes = [IMAGE]
+    for name, nh, nw, h, w in FIT_CASES:
+        img = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
+        chw = np.ascontiguousarray((img.astype(np.float64) / 255.).astype(np.float32).transpose(2, 0, 1))          # darknet's loader: (float)p / 255.
+        im = IMAGE(w, h, 3, chw.ctypes.data_as(C.POINTER(C.c_float)))
+        resized = lib.resize_min(im, nw)
+        crop = lib.crop_image(resized, int((resized.w - nw) / 2), int((resized.h - nh) / 2), nw, nh)      # (C's division truncates toward zero: int() of the quotient, not //)
+        out = np.ctypeslib.as_array(crop.data, shape=(3, nh, nw)).copy().transpose(1, 2, 0)
+        data["fit_%s_image_u8" % name], data["fit_%s_net_hw" % name], data["fit_%s_input" % name] = img, np.array([nh, nw], np.int32), np.ascontiguousarray(out)
+        data["fit_%s_resized_hw" % name] = np.array([resized.h, resized.w], np.int32)
+        same = C.addressof(resized.data.contents) == chw.ctypes.data
+        print("fit", name, "image %dx%d -> resized %dx%d%s -> network %dx%d" % (h, w, resized.h, resized.w, " (no resize)" if same else "", nh, nw))
+        assert same == (name == "same")
+        if not same:
+            lib.free_image(resized)
+        lib.free_image(crop)
+    path = os.path.join(OUT, "lrn_crop_cases.npz")
+    save_npz_reproducibly(path, data)
+    print("lrn_crop_cases", len(data), "arrays", os.path.getsize(path), "bytes")
+
+
 def gen_rect():
     gen_mini_rect("mini_v3_rect", MINI_V3, 4, 64, 96, letterbox=True)
     gen_mini_rect("mini_v2_rect", MINI_V2, 5, 96, 64)
@@ -1210,6 +1349,8 @@ if __name__ == "__main__":
         gen_edges(); sys.exit(0)
     if sys.argv[1:] == ["recurrent"]:
         gen_recurrent(); sys.exit(0)
+    if sys.argv[1:] == ["lrn_crop"]:
+        gen_lrn_crop(); sys.exit(0)
     stub_modules()
     gen_nms_v3()
     gen_v2_post()
@@ -1225,6 +1366,7 @@ if __name__ == "__main__":
     gen_rect()
     gen_edges()
     gen_recurrent()
+    gen_lrn_crop()
     gen_bn_real()
     gen_known_answers()
     gen_darknet_py_symbols()

@@ -12,7 +12,9 @@ class Classifier:
         """cfg_or_name: a shipped topology ('darknet19', 'darknet53', 'resnet18', 'resnet50', 'resnext50', 'vgg-16'), a cfg file path, or cfg text
         (a ResNet's [shortcut] layers with fewer or larger `from` tensors and any of darknet's thirteen activations are served).  weights_file: a darknet
         `.weights` file; None loads darknet_io's seeded synthetic parameters (`seed`).  names: a list of class names or the path of a
-        file with one name per line; without it the class index stands in for the name.  hierarchy (a [softmax] with tree=): None
+        file with one name per line; without it the class index stands in for the name.  fit: how an image of any size becomes the network
+        input, a hip.FIT_* code -- hip.FIT_CENTER_CROP is darknet's validation preprocessing (resize_min to the network width, then the centred
+        crop), e.g. for 'alexnet-lrn'.  hierarchy (a [softmax] with tree=): None
         returns the conditional probabilities network_predict gives, "absolute" the products along the path to the root
         (hierarchy_predictions), "leaves" those with every inner node zeroed -- what darknet's classifier apps rank."""
         text = cfg_or_name if "[net]" in cfg_or_name or "[network]" in cfg_or_name else IO.cfg_text(cfg_or_name)

@@ -47,9 +47,9 @@ hipError_t launch_preprocess(const void *img, int fmt, int n, int hw, float scal
     return hipGetLastError();
 }
 
-// ---- per-pixel arithmetic of the three image fits, shared by the single-image kernels and the batched k_fit_images.  `at(y, x, c)`
+// ---- per-pixel arithmetic of the image fits, shared by the single-image kernels and the batched k_fit_images.  `at(y, x, c)`
 //      returns what the fit reads at a source pixel: the byte as a float for the stretch and cv2 forms, the 0..1 value for the letterbox
-//      (a planar float image, or a byte through fit_unit_value).  Restated operation for operation from the reference; this file is
+//      and the centre crop (a planar float image, or a byte through fit_unit_value).  Restated operation for operation from the reference; this file is
 //      compiled with -ffp-contract=off, so every caller rounds the same. ----
 
 // legacy TF bilinear (no half-pixel offset): src = dst * (in/out); value/255 first (D2T _input_process)
@@ -75,30 +75,50 @@ __device__ __forceinline__ void px_stretch(const At &at, int h, int w, int oh, i
     }
 }
 
-// darknet letterbox_image (DN/image.c:960-981) of one output pixel: aspect-preserving resize_image (DN/image.c:1347-1393: horizontal
-// pass then vertical pass, scales (in-1)/(out-1), last column / row copied) embedded at the centre of a 0.5-filled canvas.  Operation
-// order of the two passes is kept: part = (1-dx)*a + dx*b, then (1-dy)*p0 (+ dy*p1).
+// darknet resize_image (DN/image.c:1347-1393) of an iw x ih image to new_w x new_h, evaluated at ONE pixel (r, c) of the result: horizontal
+// pass then vertical pass, scales (in-1)/(out-1), last column / row copied.  Operation order of the two passes is kept:
+// part = (1-dx)*a + dx*b, then (1-dy)*p0 (+ dy*p1).  Where the size does not change the scales are 1, dx = dy = 0, and the value is the
+// source pixel itself, bit for bit: resize_min's `no resize` branch (DN/image.c:1008) needs no case of its own.
+template <class At>
+__device__ __forceinline__ void px_resize(const At &at, int iw, int ih, int new_w, int new_h, int r, int c, float *v)
+{
+    const float w_scale = (float)(iw - 1) / (float)(new_w - 1), h_scale = (float)(ih - 1) / (float)(new_h - 1);
+    const float sy = (float)r * h_scale; const int iy = (int)sy; const float dy = sy - (float)iy;
+    const bool last_c = c == new_w - 1 || iw == 1, last_r = r == new_h - 1 || ih == 1;
+    const float sx = (float)c * w_scale; const int ix = (int)sx; const float dx = sx - (float)ix;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        auto part = [&](int row) {
+            if (last_c) return at(row, iw - 1, k);
+            return (1 - dx) * at(row, ix, k) + dx * at(row, ix + 1, k);
+        };
+        float val = (1 - dy) * part(iy);
+        if (!last_r) val = val + dy * part(iy + 1);
+        v[k] = val;
+    }
+}
+
+// darknet letterbox_image (DN/image.c:960-981) of one output pixel: the aspect-preserving resize_image embedded at the centre of a
+// 0.5-filled canvas.
 template <class At>
 __device__ __forceinline__ void px_letterbox(const At &at, int iw, int ih, int new_w, int new_h, int off_x, int off_y, int oy, int ox, float *v)
 {
     const int r = oy - off_y, c = ox - off_x;
     v[0] = v[1] = v[2] = 0.5f;
-    if ((unsigned)r < (unsigned)new_h && (unsigned)c < (unsigned)new_w) {
-        const float w_scale = (float)(iw - 1) / (float)(new_w - 1), h_scale = (float)(ih - 1) / (float)(new_h - 1);
-        const float sy = (float)r * h_scale; const int iy = (int)sy; const float dy = sy - (float)iy;
-        const bool last_c = c == new_w - 1 || iw == 1, last_r = r == new_h - 1 || ih == 1;
-        const float sx = (float)c * w_scale; const int ix = (int)sx; const float dx = sx - (float)ix;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            auto part = [&](int row) {
-                if (last_c) return at(row, iw - 1, k);
-                return (1 - dx) * at(row, ix, k) + dx * at(row, ix + 1, k);
-            };
-            float val = (1 - dy) * part(iy);
-            if (!last_r) val = val + dy * part(iy + 1);
-            v[k] = val;
-        }
-    }
+    if ((unsigned)r < (unsigned)new_h && (unsigned)c < (unsigned)new_w) px_resize(at, iw, ih, new_w, new_h, r, c, v);
+}
+
+// darknet's classifier validation fit (DN/examples/classifier.c:635-636) of one output pixel: resize_min(im, net_w) -- the shorter side
+// becomes net_w, whatever net_h is -- then crop_image(resized, (rw - net_w) / 2, (rh - net_h) / 2, net_w, net_h) (DN/image.c:857-875).  The
+// offsets truncate toward zero and are negative where the resized image is smaller than the network (a non-square one); the coordinates
+// are CLAMPED to the resized image, so its edge is replicated: there is no fill value.
+template <class At>
+__device__ __forceinline__ void px_center_crop(const At &at, int iw, int ih, int net_w, int net_h, int oy, int ox, float *v)
+{
+    int rw, rh;
+    resize_min_dims(net_w, iw, ih, &rw, &rh);
+    const int r = min(max(oy + (rh - net_h) / 2, 0), rh - 1), c = min(max(ox + (rw - net_w) / 2, 0), rw - 1);
+    px_resize(at, iw, ih, rw, rh, r, c, v);
 }
 
 // `cv2.resize(image_float32, (ow, oh))` as V2/utils.py:13-27 calls it (INTER_LINEAR on a float32 image, after BGR -> RGB) followed by the
@@ -682,7 +702,7 @@ hipError_t launch_letterbox_chw(const float *img, int iw, int ih, int net_h, int
 // ---- ragged batch fit (yolo_forward_images_u8): native-size uint8 RGB images packed in one HWC buffer, described by a device table of
 //      {offset, h, w}, fitted into the network input [n][net_h][net_w][out_stride] by ONE launch: grid (pixel tiles) x (images), one output pixel
 //      per lane, the 16-byte output pixel (8 channels: 3 real + 5 zero) stored as one vector.  Per pixel, each fit is the single-image
-//      kernel's arithmetic (px_stretch / px_letterbox / px_cv2), so a batched image equals the same image run alone, bit for bit.
+//      kernel's arithmetic (px_stretch / px_letterbox / px_cv2; px_center_crop has no single-image kernel), so a batched image equals the same image run alone, bit for bit.
 //      Source bytes are read through a buffer descriptor whose size is the packed buffer's byte count: a descriptor that pointed past
 //      the end would read zeros, never another allocation (the host validates every descriptor before the launch anyway).
 struct AtPacked {
@@ -690,8 +710,8 @@ struct AtPacked {
     __device__ __forceinline__ float operator()(int y, int x, int c) const
     {
         const unsigned v = (unsigned)__builtin_amdgcn_raw_buffer_load_b8(rsrc, base + ((unsigned)y * (unsigned)w + (unsigned)x) * 3u + (unsigned)c, 0, 0);
-        // STRETCH and CV2 read the byte as a float (the /255 and /225 are part of px_stretch / px_cv2); LETTERBOX reads darknet's 0..1 value
-        return fit == FIT_LETTERBOX ? fit_unit_value(FIT_LETTERBOX, v) : (float)v;
+        // STRETCH and CV2 read the byte as a float (the /255 and /225 are part of px_stretch / px_cv2); LETTERBOX and CENTER_CROP read darknet's 0..1 value
+        return fit == FIT_LETTERBOX || fit == FIT_CENTER_CROP ? fit_unit_value(FIT_LETTERBOX, v) : (float)v;
     }
 };
 
@@ -712,7 +732,8 @@ __global__ __launch_bounds__(256) void k_fit_images(const uint8_t *pixels, unsig
             int new_w, new_h;
             letterbox_dims(net_w, net_h, d.w, d.h, &new_w, &new_h);
             px_letterbox(at, d.w, d.h, new_w, new_h, (net_w - new_w) / 2, (net_h - new_h) / 2, oy, ox, v);
-        } else px_cv2(at, d.h, d.w, net_h, net_w, oy, ox, FIT == FIT_CV2_BGR, 225.0f, v);
+        } else if (FIT == FIT_CENTER_CROP) px_center_crop(at, d.w, d.h, net_w, net_h, oy, ox, v);
+        else px_cv2(at, d.h, d.w, net_h, net_w, oy, ox, FIT == FIT_CV2_BGR, 225.0f, v);
         // YOLOv1's `x * 2 - 1` ([net] yolo_input_mul / yolo_input_add), as px_stretch applies it
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
@@ -726,13 +747,14 @@ __global__ __launch_bounds__(256) void k_fit_images(const uint8_t *pixels, unsig
 hipError_t launch_fit_images(const uint8_t *pixels, size_t bytes, const ImgDesc *d_descs, int n, int fit, int net_h, int net_w, void *out, int out_dt,
                              int out_stride, float post_mul, float post_add, hipStream_t s)
 {
-    if (n < 1 || net_h < 1 || net_w < 1 || (size_t)net_h * net_w > 0x7fffffffull || bytes > 0xffffffffull || fit < FIT_STRETCH || fit > FIT_CV2_BGR) return hipErrorInvalidValue;
+    if (n < 1 || net_h < 1 || net_w < 1 || (size_t)net_h * net_w > 0x7fffffffull || bytes > 0xffffffffull || fit < FIT_STRETCH || fit > FIT_CENTER_CROP) return hipErrorInvalidValue;
     const dim3 grid((unsigned)((net_h * net_w + 255) / 256), (unsigned)n);
 #define FIT_LAUNCH(F) WITH_DT(out_dt, hipLaunchKernelGGL((k_fit_images<T, F>), grid, dim3(256), 0, s, pixels, (unsigned)bytes, d_descs, net_h, net_w, (T *)out, out_stride, post_mul, post_add))
     if (fit == FIT_STRETCH) FIT_LAUNCH(FIT_STRETCH);
     else if (fit == FIT_LETTERBOX) FIT_LAUNCH(FIT_LETTERBOX);
     else if (fit == FIT_CV2) FIT_LAUNCH(FIT_CV2);
-    else FIT_LAUNCH(FIT_CV2_BGR);
+    else if (fit == FIT_CV2_BGR) FIT_LAUNCH(FIT_CV2_BGR);
+    else FIT_LAUNCH(FIT_CENTER_CROP);
 #undef FIT_LAUNCH
     return hipGetLastError();
 }

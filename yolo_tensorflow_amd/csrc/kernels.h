@@ -352,6 +352,13 @@ hipError_t launch_recur(const RecurArgs &a, hipStream_t s);
 // ---- the small layers of a dense-prediction network and the map outputs (map_ops.hip) ----------
 // [l2norm] (DN/blas.c:126-144): per pixel, over the channels, x / sqrtf(sum x^2); an all-zero pixel is 0 / 0 = NaN, as in the reference
 hipError_t launch_l2norm(const TView &in, const TView &out, hipStream_t s);
+// [normalization] / [lrn] (DN/normalization_layer.c:66-95), out of place: out[k] = x[k] * (kappa + alpha * (W(k) - g))^(-beta) over a pixel's channels, W(k) the
+// sum of x[j]^2 over k - (size - 1) / 2 <= j <= k + size / 2 inside the tensor, g = x[size / 2]^2 (0 where size / 2 == C): the reference's running sum never
+// adds that channel (map_ops.hip derives it).  1 <= size <= LRN_MAX_SIZE (a window reaches one 8-channel granule to either side) and size / 2 <= C
+enum { LRN_MAX_SIZE = 17 };
+hipError_t launch_lrn(const TView &in, const TView &out, int size, float alpha, float beta, float kappa, hipStream_t s);
+// [crop] at inference (DN/crop_layer.c:67-102): the centred out.h x out.w window of `in`, times 2 minus 1 where `adjust`; out.c channels (in.c >= out.c)
+hipError_t launch_crop(const TView &in, const TView &out, int adjust, hipStream_t s);
 // darknet's [upsample] (DN/blas.c:334-349): nearest, out[y][x] = scale * in[y / stride][x / stride]
 hipError_t launch_upsample_nearest(const TView &in, const TView &out, int stride, float scale, hipStream_t s);
 hipError_t launch_scale(const TView &x, float scale, hipStream_t s);          // x *= scale in place on the real channels
@@ -383,7 +390,7 @@ hipError_t launch_resize_cv2_u8(const uint8_t *img, int h, int w, int oh, int ow
 // ragged batch of native-size uint8 RGB images (yolo_forward_images_u8): one packed HWC buffer, one descriptor per image (the layout of
 // yolo_image_desc, include/yolo_hip.h), all fitted into the network input [n][net_h][net_w][out_stride] in ONE launch.  fit: FIT_* below.
 struct ImgDesc { unsigned long long offset; int h, w; };
-enum { FIT_STRETCH = 0, FIT_LETTERBOX = 1, FIT_CV2 = 2, FIT_CV2_BGR = 3 };
+enum { FIT_STRETCH = 0, FIT_LETTERBOX = 1, FIT_CV2 = 2, FIT_CV2_BGR = 3, FIT_CENTER_CROP = 4 };
 // source pixels are read through a buffer descriptor of `bytes` bytes (< 2^32, checked by the caller with every descriptor)
 hipError_t launch_fit_images(const uint8_t *pixels, size_t bytes, const ImgDesc *d_descs, int n, int fit, int net_h, int net_w, void *out, int out_dt,
                              int out_stride, float post_mul, float post_add, hipStream_t s);
@@ -392,12 +399,20 @@ __host__ __device__ inline void letterbox_dims(int netw, int neth, int w, int h,
 {
     if (((float)netw / w) < ((float)neth / h)) { *new_w = netw; *new_h = (h * netw) / w; } else { *new_h = neth; *new_w = (w * neth) / h; }
 }
-// the value one source byte contributes before any interpolation: STRETCH value / 255.0f (TF's convert_image_dtype), LETTERBOX darknet's
-// loader `(float)data / 255.` -- a DOUBLE division rounded to float (DN/image.c load_image_stb) --, CV2 the byte itself (/ 225 comes last)
+// darknet's resize_min geometry (DN/image.c:997-1011): the size of a w x h image whose SHORTER side becomes `min` (integer divisions).  The
+// classifier's validation fit (FIT_CENTER_CROP, DN/examples/classifier.c:635-636) crops netw x neth from the centre of that.  The caller refuses
+// an image whose longer side times `min` does not fit an int (resize_min_ok): the reference's own product overflows there
+__host__ __device__ inline void resize_min_dims(int min, int w, int h, int *new_w, int *new_h)
+{
+    if (w < h) { *new_h = (h * min) / w; *new_w = min; } else { *new_w = (w * min) / h; *new_h = min; }
+}
+inline bool resize_min_ok(int min, int w, int h) { return min >= 1 && w >= 1 && h >= 1 && (long long)(w > h ? w : h) * min <= 0x7fffffffLL; }
+// the value one source byte contributes before any interpolation: STRETCH value / 255.0f (TF's convert_image_dtype), LETTERBOX and CENTER_CROP
+// darknet's loader `(float)data / 255.` -- a DOUBLE division rounded to float (DN/image.c load_image_stb) --, CV2 the byte itself (/ 225 comes last)
 __host__ __device__ inline float fit_unit_value(int fit, unsigned v)
 {
     if (fit == FIT_STRETCH) return (float)v / 255.0f;
-    if (fit == FIT_LETTERBOX) return (float)((double)v / 255.);
+    if (fit == FIT_LETTERBOX || fit == FIT_CENTER_CROP) return (float)((double)v / 255.);
     return (float)v;
 }
 hipError_t launch_upsample2x(const TView &in, const TView &out, int bilinear, hipStream_t s);

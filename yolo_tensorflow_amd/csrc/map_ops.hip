@@ -33,6 +33,104 @@ hipError_t launch_l2norm(const TView &in, const TView &out, hipStream_t s)
     return hipGetLastError();
 }
 
+// ---- [normalization] / [lrn] (DN/normalization_layer.c:66-95): local response normalisation over the channels of a pixel.
+//      The reference keeps a RUNNING sum over the channels.  With sq[j] = x[j]^2, h = size / 2, lo = (size - 1) / 2:
+//        norms[0] = kappa + alpha * (sq[0] + .. + sq[h - 1])                          (:80-83, the initial loop stops BEFORE channel h)
+//        norms[k] = norms[k - 1] - alpha * sq[k - lo - 1] + alpha * sq[k + h]         (:85-91, each term only where its index is a channel)
+//      The loop over k adds the channels h + 1, h + 2, ..: channel h is never added, but it is subtracted once the window has passed it
+//      (k - lo - 1 == h).  Against the textbook window W(k) = sum of sq[j] over max(0, k - lo) <= j <= min(C - 1, k + h): while the window
+//      holds channel h the running sum lacks it, and afterwards the running sum has lost it once more than the window -- either way, for
+//      EVERY k,
+//        norms[k] = kappa + alpha * (W(k) - g),   g = sq[h] where h < C, 0 where h == C (no such channel),   out[k] = x[k] * norms[k]^(-beta)
+//      (pow_cpu + mul_cpu, :93-94).  A negative norms[k] is NaN there (pow of a negative base) and here; nothing is clamped.  size / 2 > C makes
+//      the reference's initial loop read past the image: the planner refuses it.
+//      One thread per 8-channel granule, consecutive lanes along a pixel's channels (then along the pixels): it squares its own granule and its
+//      two neighbours' (16-byte loads the neighbouring lanes issue as well: one trip to HBM), which hold every window of a size up to
+//      LRN_MAX_SIZE = 17 (h and lo at most 8).  W(k) is the direct sum of the window's squares in ascending channel order, fp32 -- a difference of
+//      prefix sums would cancel.  The window offsets are wave-uniform, so the loop over them branches on scalars and indexes registers with
+//      constants.  x^(-0.75), the default, is rsq(n) * sqrt(rsq(n)); any other beta is exp2(-beta * log2(n)) on the hardware's
+//      log2 / exp2 (docs/NOTEBOOK.md holds the measured error of both).  Channels C .. of the last granule are stored as zeros. ----
+template <typename T> __device__ __forceinline__ void store8_keep_nan(T *p, const float *v) { Elt<T>::store8(p, v); }
+template <> __device__ __forceinline__ void store8_keep_nan<f16_t>(f16_t *p, const float *v)
+{
+    Elt<f16_t>::store8(p, v);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) if (v[i] != v[i]) p[i].b = 0x7e00;          // (the encoder's clamp turns a NaN into -65504: see store1_keep_nan)
+}
+template <typename T>
+__global__ __launch_bounds__(256) void k_lrn(const T *in, int is, T *out, int os, size_t npix, int C, int c8, int lo, int h, float alpha, float beta, float kappa)
+{
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= npix * c8) return;
+    const size_t p = idx / c8; const int g = (int)(idx - p * c8);
+    const T *x = in + p * is;
+    float s[24], v[8];          // squares of the channels 8 (g - 1) .. 8 (g + 2), zero where there is no channel; v: this granule's values
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        const int gq = g + q - 1;
+        float t[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (gq >= 0 && gq * 8 < C) Elt<T>::load8(x + gq * 8, t);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) { if (q == 1) v[i] = t[i]; s[q * 8 + i] = gq * 8 + i < C ? t[i] * t[i] : 0.f; }
+    }
+    float ghost = 0.f;
+    if (h < C) { ghost = Elt<T>::load1(x + h); ghost *= ghost; }
+    float w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+    for (int d = -8; d <= 8; ++d)
+        if (d >= -lo && d <= h) {          // (uniform)
+#pragma unroll
+            for (int i = 0; i < 8; ++i) w[i] += s[8 + i + d];
+        }
+    float r[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const float n = kappa + alpha * (w[i] - ghost);
+        float pw;
+        if (beta == 0.75f) { const float t = __builtin_amdgcn_rsqf(n); pw = t * __builtin_amdgcn_sqrtf(t); }
+        else pw = __builtin_amdgcn_exp2f(-beta * __builtin_amdgcn_logf(n));
+        r[i] = g * 8 + i < C ? v[i] * pw : 0.f;
+    }
+    store8_keep_nan<T>(out + p * os + g * 8, r);
+}
+hipError_t launch_lrn(const TView &in, const TView &out, int size, float alpha, float beta, float kappa, hipStream_t s)
+{
+    const int c8 = (in.c + 7) / 8;
+    if (in.dt != out.dt || in.dt == DT_FP8 || in.c != out.c || in.c < 1 || out.h != in.h || out.w != in.w || size < 1 || size > LRN_MAX_SIZE || size / 2 > in.c ||
+        in.stride < c8 * 8 || out.stride < c8 * 8 || in.stride % 8 || out.stride % 8) return hipErrorInvalidValue;
+    const size_t npix = (size_t)in.n * in.h * in.w;
+    WITH_DT(in.dt, hipLaunchKernelGGL(k_lrn<T>, grid_for(npix * c8), dim3(256), 0, s, (const T *)in.ptr, in.stride, (T *)out.ptr, out.stride, npix, in.c, c8, (size - 1) / 2, size / 2, alpha, beta, kappa));
+    return hipGetLastError();
+}
+
+// ---- [crop] at inference (DN/crop_layer.c:67-102 with net.train == 0): the centred crop_h x crop_w window, dh = (H - crop_h) / 2, dw = (W - crop_w) / 2,
+//      out[y][x][c] = in[y + dh][x + dw][c] * 2 - 1 (a product, then a sum: fp32, no contraction), or the plain copy with noadjust=1.  One thread
+//      per granule; the channels C .. of the last granule stay zeros, whatever the adjustment does to a zero ----
+template <typename T>
+__global__ void k_crop(const T *in, int is, T *out, int os, int n, int h, int w, int ho, int wo, int dh, int dw, int C, int c8, int adjust)
+{
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (size_t)n * ho * wo * c8) return;
+    const int g = (int)(idx % c8); size_t p = idx / c8;
+    const int ox = (int)(p % wo); p /= wo;
+    const int oy = (int)(p % ho), b = (int)(p / ho);
+    float r[8];
+    Elt<T>::load8(in + (((size_t)b * h + oy + dh) * w + ox + dw) * is + g * 8, r);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) r[i] = g * 8 + i < C ? (adjust ? r[i] * 2.f + -1.f : r[i]) : 0.f;
+    Elt<T>::store8(out + (((size_t)b * ho + oy) * wo + ox) * os + g * 8, r);
+}
+hipError_t launch_crop(const TView &in, const TView &out, int adjust, hipStream_t s)
+{
+    const int c8 = (out.c + 7) / 8;          // (the network input's view counts its 8 padded channels: the layer's own count is the output's)
+    if (in.dt != out.dt || in.dt == DT_FP8 || out.c < 1 || in.c < out.c || out.h < 1 || out.w < 1 || out.h > in.h || out.w > in.w || in.n != out.n ||
+        in.stride < c8 * 8 || out.stride < c8 * 8 || in.stride % 8 || out.stride % 8) return hipErrorInvalidValue;
+    const size_t total = (size_t)in.n * out.h * out.w * c8;
+    WITH_DT(in.dt, hipLaunchKernelGGL(k_crop<T>, grid_for(total), dim3(256), 0, s, (const T *)in.ptr, in.stride, (T *)out.ptr, out.stride, in.n, in.h, in.w, out.h, out.w,
+                                      (in.h - out.h) / 2, (in.w - out.w) / 2, out.c, c8, adjust));
+    return hipGetLastError();
+}
+
 // ---- darknet's [upsample] (DN/blas.c:334-349 upsample_cpu, forward): out[y][x] = scale * in[y / stride][x / stride] ----
 template <typename T>
 __global__ void k_upsample_nearest(const T *in, int is, T *out, int os, int n, int h, int w, int c8, int stride, float scale)

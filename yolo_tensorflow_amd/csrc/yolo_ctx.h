@@ -23,7 +23,8 @@ enum LType { L_CONV, L_SHORTCUT, L_ROUTE, L_UPSAMPLE, L_MAXPOOL, L_REORG, L_YOLO
              L_DECONV, L_ACTIVATE, L_L2NORM,        // [deconvolutional]; [logistic] / [activation]: k_activate over the producer's tensor; [l2norm]
              L_GCONV,                               // [convolutional] with groups > 1 (gconv.hip); Layer::groups
              L_RECUR,                               // [rnn] / [gru] / [lstm] (rnn_ops.hip); Layer::rkind
-             L_CRNN };                              // [crnn]: three 3x3 convs around a state map, run by the dense conv kernels; Layer::sub
+             L_CRNN,                                // [crnn]: three 3x3 convs around a state map, run by the dense conv kernels; Layer::sub
+             L_LRN, L_CROP };                       // [normalization] / [lrn]: k_lrn, Layer::size / lrn_*; [crop] at inference: k_crop, the output geometry and Layer::crop_adjust
 enum ConvKernel { K_TILED, K_HALO, K_S2 };      // a conv's own kernel: the tiled family (fp32 / direct / pair form picked by dtype), conv_halo_c32_c64 (3x3/s1, 32 -> 64), conv_s2_c64_c128 (3x3/s2, 64 -> 128)
 // the fused launch a conv is a member of, {members} -> launcher: conv_stem.hip {0, 1, optionally the 1x1 conv 2} -> 1; conv_stem_pair.hip (split-fp16) {0, 1} -> 1; conv_block.hip {1x1 i, 3x3 i + 1} -> i + 1; conv_c3s2.hip {conv3 i, stride-2 conv i + 2} -> i + 2 (both keep K_HALO / K_S2, the fall-back)
 enum FuseKind { F_NONE, F_STEM, F_PSTEM, F_RESBLOCK, F_C3S2 };
@@ -68,6 +69,8 @@ struct Layer {
     // pool / upsample / reorg
     int psize = 0, pstride = 0, ppad = 0;
     float up_scale = 1.f;                // [upsample] scale= (DN/upsample_layer.c: out = scale * in)
+    float lrn_alpha = 1e-4f, lrn_beta = 0.75f, lrn_kappa = 1.f;      // [normalization] alpha= beta= kappa= (DN/parser.c:511-519); its size= is `size`
+    bool crop_adjust = true;             // [crop]: out = in * 2 - 1 (false with noadjust=1: the plain copy)
     // [logistic] / [activation] (L_ACTIVATE; the activation is L.act): `inplace` = the layer aliases its producer's tensor and is ONE k_activate launch over it (nobody
     // else reads that tensor and nobody asked to keep it); else it copies into a tensor of its own first
     bool inplace = false;

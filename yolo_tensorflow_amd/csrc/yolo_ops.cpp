@@ -337,6 +337,18 @@ int yolo_op_l2norm(const float *x, int n, int h, int w, int c, int dtype, float 
     return YOLO_OK;
 }
 
+int yolo_op_lrn(const float *x, int n, int h, int w, int c, int size, float alpha, float beta, float kappa, int dtype, float *out, int device)
+{
+    if (!x || !out || n < 1 || h < 1 || w < 1 || c < 1 || size < 1) { g_op_err = "lrn: bad arguments"; return YOLO_ERR_INVALID; }
+    if (size > LRN_MAX_SIZE) { g_op_err = "lrn: size (1.." + std::to_string((int)LRN_MAX_SIZE) + " are served)"; return YOLO_ERR_UNSUPPORTED; }
+    if (size / 2 > c) { g_op_err = "lrn: size / 2 must not exceed the channel count (the reference reads past the image)"; return YOLO_ERR_INVALID; }
+    if (dtype != YOLO_FP32 && dtype != YOLO_BF16 && dtype != YOLO_FP16) { g_op_err = "lrn: dtype (fp32, bf16 or fp16)"; return YOLO_ERR_UNSUPPORTED; }
+    OpScope S(device); if (S.rc) { g_op_err = "lrn: no HIP device"; return S.rc; }
+    OpTensor a, o;
+    if (!op_tensor(S, x, n, h, w, c, dtype, a) || !op_tensor(S, nullptr, n, h, w, c, dtype, o) || !S.ok(launch_lrn(a.v, o.v, size, alpha, beta, kappa, S.s)) || op_tensor_out(S, o, out)) { g_op_err = "lrn: " + (S.err.empty() ? std::string("allocation or copy failed") : S.err); return S.rc ? S.rc : YOLO_ERR_HIP; }
+    return YOLO_OK;
+}
+
 int yolo_op_upsample(const float *x, int n, int h, int w, int c, int stride, float scale, int dtype, float *out, int device)
 {
     if (!x || !out || n < 1 || h < 1 || w < 1 || c < 1) { g_op_err = "upsample: bad arguments"; return YOLO_ERR_INVALID; }

@@ -387,6 +387,35 @@ static int parse_l2norm(Cursor &k, const Section &, Layer &L)
     return YOLO_OK;
 }
 
+// [normalization] / [lrn] (DN/parser.c:511-519, DN/normalization_layer.c): local response normalisation over the channels, shape in = shape out, stored in its
+// input's type.  The reference's initial loop reads the channels 0 .. size / 2 - 1 whatever C is: size / 2 > C reads past the image there and is refused here
+static int parse_normalization(Cursor &k, const Section &s, Layer &L)
+{
+    yolo_ctx *c = k.c; const int i = k.i; const char *name = s.type.c_str();
+    if (c->dtype == YOLO_FP8 || c->split()) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [%s] is not served in the fp8 / split-fp16 configurations", i, name);
+    L.type = L_LRN; L.size = opt_i(s, "size", 5);
+    L.lrn_alpha = (float)atof(opt_s(s, "alpha", ".0001").c_str()); L.lrn_beta = (float)atof(opt_s(s, "beta", ".75").c_str()); L.lrn_kappa = (float)atof(opt_s(s, "kappa", "1").c_str());
+    if (L.size < 1) return fail(c, YOLO_ERR_INVALID, "layer %d: [%s] size=%d", i, name, L.size);
+    if (L.size > LRN_MAX_SIZE) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [%s] size=%d (1..%d are served)", i, name, L.size, LRN_MAX_SIZE);
+    if (L.size / 2 > k.C) return fail(c, YOLO_ERR_INVALID, "layer %d: [%s] size=%d over %d channels: size / 2 must not exceed the channel count (the reference reads past the image)", i, name, L.size, k.C);
+    return YOLO_OK;
+}
+
+// [crop] at inference (DN/parser.c:429-451, DN/crop_layer.c:67-102 with net.train == 0): the centred crop_height x crop_width window, times 2 minus 1 unless
+// noadjust=1.  flip / angle / saturation / exposure / shift act while training only: read by nobody.  It may be layer 0 (darknet's own classifier cfgs): the
+// conv behind it then reads a 3-channel layer tensor through the tiled kernel -- the fused stems ask for a conv at layer 0
+static int parse_crop(Cursor &k, const Section &s, Layer &L)
+{
+    yolo_ctx *c = k.c; const int i = k.i;
+    if (c->dtype == YOLO_FP8 || c->split()) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [crop] is not served in the fp8 / split-fp16 configurations", i);
+    const int ch = opt_i(s, "crop_height", 1), cw = opt_i(s, "crop_width", 1);
+    L.type = L_CROP; L.crop_adjust = opt_i(s, "noadjust", 0) == 0;
+    if (ch < 1 || cw < 1) return fail(c, YOLO_ERR_INVALID, "layer %d: [crop] crop_height=%d crop_width=%d", i, ch, cw);
+    if (ch > k.H || cw > k.W) return fail(c, YOLO_ERR_INVALID, "layer %d: [crop] to %d x %d is larger than its %d x %d input (the reference reads out of bounds)", i, cw, ch, k.W, k.H);
+    k.H = ch; k.W = cw;
+    return YOLO_OK;
+}
+
 static int parse_maxpool(Cursor &k, const Section &s, Layer &L)
 {
     yolo_ctx *c = k.c; const int i = k.i;
@@ -479,6 +508,7 @@ static const struct { const char *name; int (*parse)(Cursor &, const Section &, 
     {"logistic", parse_activate}, {"activation", parse_activate}, {"l2norm", parse_l2norm}, {"maxpool", parse_maxpool}, {"reorg", parse_reorg},
     {"yolo", parse_head}, {"region", parse_head}, {"avgpool", parse_avgpool}, {"softmax", parse_softmax}, {"cost", parse_identity},
     {"rnn", parse_recurrent}, {"gru", parse_recurrent}, {"lstm", parse_recurrent}, {"crnn", parse_crnn},
+    {"normalization", parse_normalization}, {"lrn", parse_normalization}, {"crop", parse_crop},
 };
 
 // After each section: a layer that moves data keeps the type and the pair form of what it moves, and its operands must agree.
@@ -750,7 +780,7 @@ static int decide_inplace(yolo_ctx *c, const std::vector<int> &uses)
         if (j < 0 || c->keep_layers || routed || uses[j] != 1) continue;
         const Layer &P = c->layers[j];
         L.inplace = (computes(P) || P.type == L_LOCAL || P.type == L_SHORTCUT || P.type == L_L2NORM || P.type == L_UPSAMPLE || P.type == L_MAXPOOL ||
-                     P.type == L_ACTIVATE) && !never_stored(P, j);
+                     P.type == L_ACTIVATE || P.type == L_LRN || P.type == L_CROP) && !never_stored(P, j);
     }
     return YOLO_OK;
 }
@@ -1175,6 +1205,8 @@ int yolo_plan_dump(const char *cfg_text, int dtype, int max_batch, int keep_laye
             for (int q = 0; q < g.launches; ++q) put(" launch%d=[mode=%d rows=%d kx=%d kh=%d]", q, g.mode[q], g.Mp[q], g.Kx[q], g.Kh[q]);
             put(" state=own(%s)\n", L.rkind == RECUR_LSTM ? "h,c" : "h");
         }
+        if (L.type == L_LRN) put("lrn %zu size=%d lo=%d h=%d alpha=%a beta=%a kappa=%a ghost=%d\n", i, L.size, (L.size - 1) / 2, L.size / 2, (double)L.lrn_alpha, (double)L.lrn_beta, (double)L.lrn_kappa, L.size / 2 < L.C ? L.size / 2 : -1);
+        if (L.type == L_CROP) { int h0, w0, c0; Cursor{&c, (int)i, 0, 0, 0}.dims(L.in[0], h0, w0, c0); put("crop %zu from=%dx%d to=%dx%d dh=%d dw=%d adjust=%d\n", i, h0, w0, L.H, L.W, (h0 - L.H) / 2, (w0 - L.W) / 2, (int)L.crop_adjust); }
         if (L.type == L_CRNN) {
             put("recurrent %zu kind=crnn hidden=%d output=%d shortcut=%d launches=3", i, L.cin, L.filters, L.rshortcut);
             for (int q = 0; q < 3; ++q) put(" conv%d=[cin=%d cin_pad=%d kpad=%d filters=%d cout_pad=%d bn=%d act=%d]", q, L.sub[q].cin, L.sub[q].cin_pad, L.sub[q].kpad, L.sub[q].filters, L.sub[q].cout_pad, L.sub[q].bn, L.sub[q].act);

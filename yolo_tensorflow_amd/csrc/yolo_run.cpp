@@ -390,6 +390,8 @@ int run_layer(yolo_ctx *c, int i, int n)
         HIPCK(c, launch_activate(out, L.pair, L.act, s));
         break; }
     case L_L2NORM: HIPCK(c, launch_l2norm(nview(n, view_of(c, L.in[0])), nview(n, L.out), s)); break;
+    case L_LRN: HIPCK(c, launch_lrn(nview(n, view_of(c, L.in[0])), nview(n, L.out), L.size, L.lrn_alpha, L.lrn_beta, L.lrn_kappa, s)); break;
+    case L_CROP: HIPCK(c, launch_crop(nview(n, view_of(c, L.in[0])), nview(n, L.out), L.crop_adjust, s)); break;          // (layer 0: the staged input, 3 of whose 8 channels are the image's)
     case L_UPSAMPLE:
         if (L.pstride != 2 || L.up_scale != 1.f) {          // (never pairs: the planner refuses these in the split-fp16 configuration)
             if (c->semantics == YOLO_SEM_DARKNET) { HIPCK(c, launch_upsample_nearest(nview(n, view_of(c, L.in[0])), nview(n, L.out), L.pstride, L.up_scale, s)); break; }
@@ -746,7 +748,7 @@ static int images_check(yolo_ctx *c, const void *pixels, size_t bytes, const yol
     if (!c->weights_loaded) return fail(c, YOLO_ERR_STATE, "forward of images before weights were loaded");
     if (n < 1 || n > c->max_batch) return fail(c, YOLO_ERR_INVALID, "batch %d outside 1..%d", n, c->max_batch);
     if (!pixels || !descs) return fail(c, YOLO_ERR_INVALID, "pixels / descs == NULL");
-    if (fit < YOLO_FIT_STRETCH || fit > YOLO_FIT_CV2_BGR) return fail(c, YOLO_ERR_INVALID, "bad fit %d", fit);
+    if (fit < YOLO_FIT_STRETCH || fit > YOLO_FIT_CENTER_CROP) return fail(c, YOLO_ERR_INVALID, "bad fit %d", fit);
     if (bytes < 3 || bytes > 0xffffffffull) return fail(c, YOLO_ERR_INVALID, "packed buffer of %zu bytes (3 .. 2^32 - 1)", bytes);
     for (int i = 0; i < n; ++i) {
         const yolo_image_desc &d = descs[i];
@@ -758,12 +760,22 @@ static int images_check(yolo_ctx *c, const void *pixels, size_t bytes, const yol
             int nw, nh; letterbox_dims(c->in_w, c->in_h, d.w, d.h, &nw, &nh);
             if (nw < 1 || nh < 1) return fail(c, YOLO_ERR_INVALID, "image %d: %d x %d letterboxes to less than one pixel", i, (int)d.h, (int)d.w);
         }
+        if (fit == YOLO_FIT_CENTER_CROP && !resize_min_ok(c->in_w, d.w, d.h))
+            return fail(c, YOLO_ERR_INVALID, "image %d: %d x %d: its longer side times the network width %d does not fit an int (darknet's resize_min)", i, (int)d.h, (int)d.w, c->in_w);
     }
     return YOLO_OK;
 }
 
+// the centre crop discards part of the image: it is a classifier's fit (and a plain forward's).  The entry points that map results back to the image refuse it
+static int crop_fit_refused(yolo_ctx *c, int fit, const char *who, const char *what)
+{
+    if (fit != YOLO_FIT_CENTER_CROP) return YOLO_OK;
+    return fail(c, YOLO_ERR_UNSUPPORTED, "%s: YOLO_FIT_CENTER_CROP is not served: %s cannot be mapped back through a crop that discards part of the image", who, what);
+}
+
 static int detect_images_check(yolo_ctx *c, int fit, int max_out, int nms_mode, int select_mode, int units)
 {
+    if (int r = crop_fit_refused(c, fit, "yolo_detect_images", "boxes")) return r;
     if (int r = post_args_ok(c, max_out, nms_mode, select_mode)) return r;
     if (units != YOLO_UNITS_NETWORK && units != YOLO_UNITS_SOURCE_PIXELS) return fail(c, YOLO_ERR_INVALID, "bad units %d", units);
     if (fit == YOLO_FIT_LETTERBOX)
@@ -894,6 +906,7 @@ int yolo_segment_images_u8(yolo_ctx *c, const uint8_t *pixels, const yolo_image_
 {
     if (!c) return YOLO_ERR_INVALID;
     if (int r = need_map(c, "yolo_segment_images_u8")) return r;
+    if (int r = crop_fit_refused(c, fit, "yolo_segment_images_u8", "labels")) return r;
     if (!labels_u8) return fail(c, YOLO_ERR_INVALID, "labels_u8 == NULL");
     const Layer &M = c->layers[c->map_layer];
     if (M.C > 255) return fail(c, YOLO_ERR_UNSUPPORTED, "yolo_segment_images_u8: a map of %d channels (uint8 labels hold at most 255 classes)", M.C);
@@ -921,7 +934,7 @@ int yolo_segment_images_u8(yolo_ctx *c, const uint8_t *pixels, const yolo_image_
 
 float yolo_fit_unit_value(int fit, int value)
 {
-    if (fit < YOLO_FIT_STRETCH || fit > YOLO_FIT_CV2_BGR || value < 0 || value > 255) return NAN;
+    if (fit < YOLO_FIT_STRETCH || fit > YOLO_FIT_CENTER_CROP || value < 0 || value > 255) return NAN;
     return fit_unit_value(fit, (unsigned)value);
 }
 

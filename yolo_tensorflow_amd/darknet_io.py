@@ -242,7 +242,9 @@ def layer_shapes(secs):
             H = W = int(s.get("side", 7))
         elif t == "avgpool":                 # always global (DN/avgpool_layer.c:40-55)
             H = W = 1
-        elif t not in ("shortcut", "yolo", "region", "dropout", "softmax", "cost", "logistic", "activation", "l2norm"):
+        elif t == "crop":                    # the centred window at inference (DN/crop_layer.c:67-102); the channels stay
+            H, W = int(s.get("crop_height", 1)), int(s.get("crop_width", 1))
+        elif t not in ("shortcut", "yolo", "region", "dropout", "softmax", "cost", "logistic", "activation", "l2norm", "normalization", "lrn"):
             raise ValueError("unsupported layer type [%s]" % t)
         shapes.append((t, H, W, C, cin))
     return shapes

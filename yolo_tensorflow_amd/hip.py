@@ -22,7 +22,7 @@ HOST, DEVICE = 0, 1
 IMG_U8, IMG_F32, IMG_F32_CHW = 0, 1, 2
 NMS_TF, NMS_PER_CLASS, NMS_DARKNET, NMS_NUMPY_V3, NMS_TF_V1 = 0, 1, 2, 3, 4
 SELECT_GT, SELECT_GE = 0, 1
-FIT_STRETCH, FIT_LETTERBOX, FIT_CV2, FIT_CV2_BGR = 0, 1, 2, 3
+FIT_STRETCH, FIT_LETTERBOX, FIT_CV2, FIT_CV2_BGR, FIT_CENTER_CROP = 0, 1, 2, 3, 4
 UNITS_NETWORK, UNITS_SOURCE_PIXELS = 0, 1
 
 BOX_DTYPE = np.dtype([("x0", "<f4"), ("y0", "<f4"), ("x1", "<f4"), ("y1", "<f4"), ("score", "<f4"), ("cls", "<i4")])
@@ -47,7 +47,7 @@ EXPORTS = [
     "yolo_set_hier_thresh", "yolo_set_hierarchy_mode", "yolo_darknet_boxes_map", "yolo_tree_geometry", "yolo_tree_read", "yolo_plan_check", "yolo_plan_table", "yolo_plan_dump",
     "yolo_op_tree_softmax", "yolo_op_tree_top", "yolo_activation_code", "yolo_op_activate", "yolo_op_shortcut",
     "yolo_output_map_geometry", "yolo_output_map", "yolo_label_map", "yolo_segment_images_u8", "yolo_op_deconv2d", "yolo_op_l2norm", "yolo_op_upsample", "yolo_op_label_map",
-    "yolo_op_conv2d_grouped", "yolo_op_conv2d_pad",
+    "yolo_op_conv2d_grouped", "yolo_op_conv2d_pad", "yolo_op_lrn",
     "yolo_num_state_tensors", "yolo_state_geometry", "yolo_get_state", "yolo_set_state", "yolo_reset_state",
 ]
 HIER_CONDITIONAL, HIER_ABSOLUTE, HIER_LEAVES = 0, 1, 2
@@ -164,6 +164,7 @@ def load_library():
     l.yolo_op_deconv2d.argtypes = [P, I, I, I, I, P, P, I, I, I, I, I, I, I, P, I]
     l.yolo_op_conv2d_grouped.argtypes = [P, I, I, I, I, P, P, I, I, I, I, I, I, I, I, P, I]
     l.yolo_op_l2norm.argtypes = [P, I, I, I, I, I, P, I]
+    l.yolo_op_lrn.argtypes = [P, I, I, I, I, I, C.c_float, C.c_float, C.c_float, I, P, I]
     l.yolo_op_upsample.argtypes = [P, I, I, I, I, I, F, I, P, I]
     l.yolo_op_label_map.argtypes = [P, I, I, I, I, F, P, I]
     l.yolo_num_state_tensors.argtypes = [P]
@@ -854,6 +855,15 @@ def op_l2norm(x, dtype=FP32, device=0):
     x = _f32(x); n, h, w, c = x.shape
     out = np.empty_like(x)
     _op_check(load_library().yolo_op_l2norm(x.ctypes.data, n, h, w, c, dtype, out.ctypes.data, device), "yolo_op_l2norm")
+    return out
+
+
+def op_lrn(x, size=5, alpha=1e-4, beta=0.75, kappa=1.0, dtype=FP32, device=0):
+    """[normalization] / [lrn] over the channels of every pixel of x [n, h, w, c], as darknet computes it: x * (kappa + alpha * (W - g)) ** -beta, W the
+    window's sum of squares, g the square of channel size // 2 (the one its running sum never adds) (yolo_op_lrn)."""
+    x = _f32(x); n, h, w, c = x.shape
+    out = np.empty_like(x)
+    _op_check(load_library().yolo_op_lrn(x.ctypes.data, n, h, w, c, int(size), float(alpha), float(beta), float(kappa), dtype, out.ctypes.data, device), "yolo_op_lrn")
     return out
 
 
