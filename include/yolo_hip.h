@@ -223,6 +223,38 @@ int yolo_detect_images_graph(yolo_ctx *ctx, const uint8_t *pixels, size_t bytes,
  * device evaluates the same expression. */
 float yolo_fit_unit_value(int fit, int value);
 
+/* ---- tiled detection of images larger than the network input ("Tiled detection"; no counterpart in the reference) ----
+ * One window of the grid an image is cut into: rows y0 .. y0 + h - 1, columns x0 .. x0 + w - 1 of the image (16 bytes). */
+typedef struct yolo_tile_window {
+    int32_t y0, x0, h, w;
+} yolo_tile_window;
+/* The window grid of an img_h x img_w image.  Per axis, with image extent L, tile extent T and overlap O (0 <= O < T): L <= T gives ONE
+ * window [0, L) -- the whole extent, smaller than the tile; otherwise the stride is S = T - O, there are ceil((L - T) / S) + 1 windows of
+ * extent T and window k starts at min(k * S, L - T): the last one is pulled back to the image's edge, so every window lies inside the
+ * image.  Windows are listed row-major, y outer and x inner.  *count is always written; at most `cap` windows are written to out (cap = 0 /
+ * out = NULL: the count only).  YOLO_ERR_INVALID for a non-positive extent, O < 0, O >= T, count == NULL or a grid of 2^31 windows or
+ * more.  Host-side: no context, no device. */
+int yolo_tile_windows(int img_h, int img_w, int tile_h, int tile_w, int overlap_h, int overlap_w, yolo_tile_window *out, int cap, int *count);
+/* Detection in images of any size at the resolution of their windows: every image of descs[n_images] (whole images in `pixels`, as for
+ * yolo_detect_images_u8; n_images is NOT bound by max_batch) is cut into the windows of yolo_tile_windows (tile_h = tile_w = 0: the
+ * network's own input size), each window is fitted into the network input straight from the image it lies in (`fit`: YOLO_FIT_STRETCH or
+ * YOLO_FIT_LETTERBOX; bit for bit the fit of the same crop handed over as an image of its own), the windows run max_batch at a time --
+ * ceil(windows / max_batch) network steps, images may share a step --, after every step the rows that pass `select_mode` against
+ * score_thr are mapped to SOURCE-IMAGE pixels and appended to their image's candidate list in (window, row) order, and after the last
+ * step ONE NMS launch (nms_mode: YOLO_NMS_TF or YOLO_NMS_DARKNET) runs over all images: duplicates across windows are suppressed like
+ * duplicates inside one.  boxes_out [n_images * max_out], counts_out [n_images] at out_loc.  The records are in the image's pixels
+ * (relative = 0) or divided by its width and height (relative = 1): corners for YOLO_NMS_TF, (cx, cy, w, h) for YOLO_NMS_DARKNET, as
+ * yolo_detect_images_u8 reports them.  Results do not depend on max_batch and are bit-reproducible from run to run.
+ * Every check runs before any launch.  YOLO_ERR_INVALID: a classifier or map context, a descriptor as yolo_forward_images_u8 refuses it,
+ * tile or overlap outside the rule above, an image too large for 32-bit sizes.  YOLO_ERR_UNSUPPORTED, naming what is refused: the CV2 and
+ * CENTER_CROP fits, YOLO_NMS_PER_CLASS / YOLO_NMS_TF_V1 / YOLO_NMS_NUMPY_V3, a softmax-tree head, a [detection] head with the letterbox.
+ * An image whose windows yield more than 32768 candidates in all: YOLO_ERR_UNSUPPORTED naming the image and the count, and nothing is
+ * written to boxes_out / counts_out.  There is no captured-graph form. */
+int yolo_detect_tiled_u8(yolo_ctx *ctx, const uint8_t *pixels, size_t bytes, const yolo_image_desc *descs, int n_images,
+                         int tile_h, int tile_w, int overlap_h, int overlap_w, int fit, int loc,
+                         float score_thr, float iou_thr, int max_out, int nms_mode, int select_mode, int relative,
+                         yolo_box *boxes_out, int32_t *counts_out, int out_loc);
+
 /* darknet's get_network_boxes on the device (DN/network.c:536-567 = num_detections + fill_network_boxes ->
  * get_yolo_detections DN/yolo_layer.c:316-343 / get_region_detections DN/region_layer.c:364-437 (softmax heads, no tree),
  * then correct_yolo_boxes DN/yolo_layer.c:247-273) over image 0 of the last forward: boxes above `thresh`, compacted in

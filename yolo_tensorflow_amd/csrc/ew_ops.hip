@@ -706,25 +706,28 @@ hipError_t launch_letterbox_chw(const float *img, int iw, int ih, int net_h, int
 //      Source bytes are read through a buffer descriptor whose size is the packed buffer's byte count: a descriptor that pointed past
 //      the end would read zeros, never another allocation (the host validates every descriptor before the launch anyway).
 struct AtPacked {
-    __amdgpu_buffer_rsrc_t rsrc; unsigned base; int w, fit;
+    __amdgpu_buffer_rsrc_t rsrc; unsigned base, pitch; int fit;      // pitch: bytes from one row to the next (a whole image: w * 3; a window: its image's)
     __device__ __forceinline__ float operator()(int y, int x, int c) const
     {
-        const unsigned v = (unsigned)__builtin_amdgcn_raw_buffer_load_b8(rsrc, base + ((unsigned)y * (unsigned)w + (unsigned)x) * 3u + (unsigned)c, 0, 0);
+        const unsigned v = (unsigned)__builtin_amdgcn_raw_buffer_load_b8(rsrc, base + (unsigned)y * pitch + (unsigned)x * 3u + (unsigned)c, 0, 0);
         // STRETCH and CV2 read the byte as a float (the /255 and /225 are part of px_stretch / px_cv2); LETTERBOX and CENTER_CROP read darknet's 0..1 value
         return fit == FIT_LETTERBOX || fit == FIT_CENTER_CROP ? fit_unit_value(FIT_LETTERBOX, v) : (float)v;
     }
 };
 
-template <typename T, int FIT>
-__global__ __launch_bounds__(256) void k_fit_images(const uint8_t *pixels, unsigned bytes, const ImgDesc *descs, int net_h, int net_w, T *out, int out_stride,
+__device__ __forceinline__ unsigned row_pitch(const ImgDesc &d) { return (unsigned)d.w * 3u; }
+__device__ __forceinline__ unsigned row_pitch(const WinDesc &d) { return (unsigned)d.pitch; }
+// Desc: ImgDesc (whole images) or WinDesc (windows of larger images, yolo_detect_tiled_u8): the same arithmetic over (h, w) pixels read at a row pitch
+template <typename T, int FIT, class Desc>
+__global__ __launch_bounds__(256) void k_fit_images(const uint8_t *pixels, unsigned bytes, const Desc *descs, int net_h, int net_w, T *out, int out_stride,
                                                     float post_mul, float post_add)
 {
     const int img = blockIdx.y;
     const int p = blockIdx.x * 256 + threadIdx.x;
     if (p >= net_h * net_w) return;
-    const ImgDesc d = descs[img];
+    const Desc d = descs[img];
     const int oy = p / net_w, ox = p - oy * net_w;
-    const AtPacked at{__builtin_amdgcn_make_buffer_rsrc((void *)pixels, 0, bytes, 0x00020000), (unsigned)d.offset, d.w, FIT};
+    const AtPacked at{__builtin_amdgcn_make_buffer_rsrc((void *)pixels, 0, bytes, 0x00020000), (unsigned)d.offset, row_pitch(d), FIT};
     float v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (FIT == FIT_STRETCH) px_stretch(at, d.h, d.w, net_h, net_w, oy, ox, post_mul, post_add, v);
     else {
@@ -749,12 +752,22 @@ hipError_t launch_fit_images(const uint8_t *pixels, size_t bytes, const ImgDesc 
 {
     if (n < 1 || net_h < 1 || net_w < 1 || (size_t)net_h * net_w > 0x7fffffffull || bytes > 0xffffffffull || fit < FIT_STRETCH || fit > FIT_CENTER_CROP) return hipErrorInvalidValue;
     const dim3 grid((unsigned)((net_h * net_w + 255) / 256), (unsigned)n);
-#define FIT_LAUNCH(F) WITH_DT(out_dt, hipLaunchKernelGGL((k_fit_images<T, F>), grid, dim3(256), 0, s, pixels, (unsigned)bytes, d_descs, net_h, net_w, (T *)out, out_stride, post_mul, post_add))
-    if (fit == FIT_STRETCH) FIT_LAUNCH(FIT_STRETCH);
-    else if (fit == FIT_LETTERBOX) FIT_LAUNCH(FIT_LETTERBOX);
-    else if (fit == FIT_CV2) FIT_LAUNCH(FIT_CV2);
-    else if (fit == FIT_CV2_BGR) FIT_LAUNCH(FIT_CV2_BGR);
-    else FIT_LAUNCH(FIT_CENTER_CROP);
+#define FIT_LAUNCH(F, D, descs) WITH_DT(out_dt, hipLaunchKernelGGL((k_fit_images<T, F, D>), grid, dim3(256), 0, s, pixels, (unsigned)bytes, descs, net_h, net_w, (T *)out, out_stride, post_mul, post_add))
+    if (fit == FIT_STRETCH) FIT_LAUNCH(FIT_STRETCH, ImgDesc, d_descs);
+    else if (fit == FIT_LETTERBOX) FIT_LAUNCH(FIT_LETTERBOX, ImgDesc, d_descs);
+    else if (fit == FIT_CV2) FIT_LAUNCH(FIT_CV2, ImgDesc, d_descs);
+    else if (fit == FIT_CV2_BGR) FIT_LAUNCH(FIT_CV2_BGR, ImgDesc, d_descs);
+    else FIT_LAUNCH(FIT_CENTER_CROP, ImgDesc, d_descs);
+    return hipGetLastError();
+}
+
+hipError_t launch_fit_windows(const uint8_t *pixels, size_t bytes, const WinDesc *d_wins, int n, int fit, int net_h, int net_w, void *out, int out_dt,
+                              int out_stride, float post_mul, float post_add, hipStream_t s)
+{
+    if (n < 1 || net_h < 1 || net_w < 1 || (size_t)net_h * net_w > 0x7fffffffull || bytes > 0xffffffffull || (fit != FIT_STRETCH && fit != FIT_LETTERBOX)) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((net_h * net_w + 255) / 256), (unsigned)n);
+    if (fit == FIT_STRETCH) FIT_LAUNCH(FIT_STRETCH, WinDesc, d_wins);
+    else FIT_LAUNCH(FIT_LETTERBOX, WinDesc, d_wins);
 #undef FIT_LAUNCH
     return hipGetLastError();
 }

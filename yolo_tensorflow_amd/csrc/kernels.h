@@ -394,6 +394,14 @@ enum { FIT_STRETCH = 0, FIT_LETTERBOX = 1, FIT_CV2 = 2, FIT_CV2_BGR = 3, FIT_CEN
 // source pixels are read through a buffer descriptor of `bytes` bytes (< 2^32, checked by the caller with every descriptor)
 hipError_t launch_fit_images(const uint8_t *pixels, size_t bytes, const ImgDesc *d_descs, int n, int fit, int net_h, int net_w, void *out, int out_dt,
                              int out_stride, float post_mul, float post_add, hipStream_t s);
+// One window of a larger image (yolo_detect_tiled_u8): h x w pixels whose first one lies at byte `offset` of the packed buffer, in an image
+// whose rows are `pitch` bytes apart; `image`: the descriptor it was cut from, (x0, y0): its first pixel in that image.  32 bytes.
+struct WinDesc { unsigned long long offset; int h, w, pitch, image, x0, y0; };
+static_assert(sizeof(WinDesc) == 32, "the window table's row");
+// the same launch over n windows: the fit clamps at the window's border and never reads the image around it, so a window is fitted
+// bit for bit as its crop would be as an image of its own.  FIT_STRETCH and FIT_LETTERBOX
+hipError_t launch_fit_windows(const uint8_t *pixels, size_t bytes, const WinDesc *d_wins, int n, int fit, int net_h, int net_w, void *out, int out_dt,
+                              int out_stride, float post_mul, float post_add, hipStream_t s);
 // darknet's letterbox_image geometry (DN/image.c:960-966): the aspect-preserving size of a w x h image inside netw x neth
 __host__ __device__ inline void letterbox_dims(int netw, int neth, int w, int h, int *new_w, int *new_h)
 {
@@ -574,6 +582,32 @@ struct PostArgs {
     int geom_net_pixels;                // 1: the decoded boxes are in network-input pixels (DECODE_PIXEL [yolo] heads), 0: normalised
 };
 hipError_t launch_postprocess(const PostArgs &a, hipStream_t s);
+// Cross-window merge of yolo_detect_tiled_u8 ("Tiled detection").  After a network step over the windows first .. first + nb - 1
+// of the window table (batch slot b holds window first + b), every row that passes select_mode against score_thr is mapped to its source
+// image's pixels and written to that image's merged list, ordered by (window, row) whatever the scheduling: launch 1 counts the passing rows
+// of every window; launch 2 places a window behind what its image held before the step (run_in) and behind the image's earlier windows of
+// the step, and writes its rows in row order.  run_in / run_out are two arrays the caller swaps between steps (a step never writes what it
+// reads); the block of an image's LAST window writes total[image] and, above `cap`, reports ((image << 32) | count) to *overflow by an
+// atomic minimum (the lowest such image wins; the word starts as all ones).  Rows beyond cap are counted, not written.
+#define TILE_MERGE_CAP 32768             // k_nms_image's limit: one image's merged candidates
+struct TileMergeArgs {
+    const WinDesc *wins; int nwin, first, nb;
+    int rows, attrs;                     // rows per window, attributes of a `det` row
+    const float *det, *box4;             // the step's boxes, as PostArgs: box4 non-null = the lean decode's [nb, rows, 4], det is not read
+    const float *scores; const int *labels;      // [nb, rows]
+    float score_thr; int select_mode;
+    int fit, netw, neth;                 // FIT_STRETCH / FIT_LETTERBOX of the windows into netw x neth
+    int net_pixels;                      // 1: the boxes are in network-input pixels (DECODE_PIXEL [yolo] heads): divided by the network size first
+    int centre;                          // 1: merged boxes are (cx, cy, w, h) (YOLO_NMS_DARKNET reads that form), 0: corners (x0, y0, x1, y1)
+    int cap;                             // merged rows per image (<= TILE_MERGE_CAP)
+    float *m_scores; int *m_labels; float4 *m_box;      // [images, cap]
+    int *wcount;                         // [nb]: passing rows per window of this step
+    const int *run_in; int *run_out; int *total;        // [images]
+    unsigned long long *overflow;
+};
+hipError_t launch_tile_merge(const TileMergeArgs &a, hipStream_t s);
+// the kept records of image i divided by that image's width (x0, x1) and height (y0, y1): relative = 1 of yolo_detect_tiled_u8
+hipError_t launch_tile_relative(void *boxes, const int *counts, int max_out, const ImgDesc *descs, int n, hipStream_t s);
 // row S on its own: score = max_k(obj * cls_k), label = first arg-max, of nrows decoded rows (objectness_mode: V3/yolo_v3.py:385,397)
 void launch_score_rows(const float *det, size_t nrows, int attrs, float *scores, int *labels, hipStream_t s, int objectness_mode = 0);
 hipError_t launch_letterbox_chw(const float *img, int iw, int ih, int net_h, int net_w, void *out, int out_dt, int out_stride, hipStream_t s);

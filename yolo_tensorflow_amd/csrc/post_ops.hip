@@ -917,6 +917,105 @@ hipError_t launch_postprocess(const PostArgs &a, hipStream_t s)
     return hipGetLastError();
 }
 
+// ---- cross-window merge of yolo_detect_tiled_u8 (TileMergeArgs, kernels.h; DESIGN.md "Tiled detection") ----
+// The box row `p` = (cx, cy, w, h) of a window enters its image's merged list with: in source-image pixels.  A DECODE_PIXEL head's numbers are
+// divided by the network size first.  STRETCH: the box in window units times the window's extent, plus the window's origin.  LETTERBOX:
+// correct_yolo_boxes for the window with relative = 0 (dn_correct, as cand_box applies it per image), plus the origin.  Corners are formed
+// from (cx, cy, w, h) in window units by cand_box's arithmetic (q - w * 0.5, q + w * 0.5) before the origin is added.  Every step is one
+// unfused fp32 operation (dn_correct: darknet's own mix of float and double), so a numpy float32 restatement reproduces it bit for bit.
+__device__ __forceinline__ float4 tile_box(const TileMergeArgs &a, const WinDesc &w, const float *p)
+{
+    float q0 = p[0], q1 = p[1], q2 = p[2], q3 = p[3];
+    if (a.net_pixels) { q0 = __fdiv_rn(q0, (float)a.netw); q1 = __fdiv_rn(q1, (float)a.neth); q2 = __fdiv_rn(q2, (float)a.netw); q3 = __fdiv_rn(q3, (float)a.neth); }
+    float sx = (float)w.w, sy = (float)w.h;          // what a window unit is in pixels
+    if (a.fit == FIT_LETTERBOX) {
+        int new_w, new_h;
+        letterbox_dims(a.netw, a.neth, w.w, w.h, &new_w, &new_h);
+        q0 = dn_correct(0, q0, a.netw, a.neth, new_w, new_h, w.w, w.h, 0); q1 = dn_correct(1, q1, a.netw, a.neth, new_w, new_h, w.w, w.h, 0);
+        q2 = dn_correct(2, q2, a.netw, a.neth, new_w, new_h, w.w, w.h, 0); q3 = dn_correct(3, q3, a.netw, a.neth, new_w, new_h, w.w, w.h, 0);
+        sx = sy = 1.f;                                // already pixels of the window (a product with 1 is exact)
+    }
+    const float X = (float)w.x0, Y = (float)w.y0;
+    if (a.centre) return float4{__fadd_rn(__fmul_rn(q0, sx), X), __fadd_rn(__fmul_rn(q1, sy), Y), __fmul_rn(q2, sx), __fmul_rn(q3, sy)};
+    const float w2 = __fmul_rn(q2, 0.5f), h2 = __fmul_rn(q3, 0.5f);
+    return float4{__fadd_rn(__fmul_rn(__fsub_rn(q0, w2), sx), X), __fadd_rn(__fmul_rn(__fsub_rn(q1, h2), sy), Y),
+                  __fadd_rn(__fmul_rn(__fadd_rn(q0, w2), sx), X), __fadd_rn(__fmul_rn(__fadd_rn(q1, h2), sy), Y)};
+}
+__device__ __forceinline__ bool tile_pass(const TileMergeArgs &a, float score) { return a.select_mode == 0 ? score > a.score_thr : score >= a.score_thr; }
+
+// launch 1: one workgroup per window of the step counts its passing rows
+__global__ __launch_bounds__(1024) void k_tile_count(const TileMergeArgs a)
+{
+    __shared__ int wcnt[16];
+    const int b = blockIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const float *sc = a.scores + (size_t)b * a.rows;
+    int cnt = 0;
+    for (int r = threadIdx.x; r < a.rows; r += 1024) cnt += tile_pass(a, sc[r]) ? 1 : 0;
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
+    if (lane == 0) wcnt[wv] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) { int t = 0; for (int k = 0; k < 16; ++k) t += wcnt[k]; a.wcount[b] = t; }
+}
+// launch 2: one workgroup per window of the step writes its passing rows, in row order, at its place in the image's list
+__global__ __launch_bounds__(1024) void k_tile_write(const TileMergeArgs a)
+{
+    __shared__ int wcnt[16]; __shared__ int s_before;
+    const int b = blockIdx.x, wi = a.first + b, tid = threadIdx.x;
+    const WinDesc w = a.wins[wi];
+    const int image = w.image;
+    // rows of this image ahead of the window: what earlier steps merged -- only where the image's windows began in an earlier step, i.e. the
+    // step's first window continues it -- plus the image's earlier windows of this step
+    if (tid == 0) s_before = (a.first > 0 && a.wins[a.first].image == image && a.wins[a.first - 1].image == image) ? a.run_in[image] : 0;
+    __syncthreads();
+    for (int t = tid; t < b; t += 1024) if (a.wins[a.first + t].image == image) atomicAdd(&s_before, a.wcount[t]);      // (integer sum: any order, one value)
+    __syncthreads();
+    int pos = s_before;
+    const int mine = a.wcount[b];
+    const size_t s0 = (size_t)b * a.rows, m0 = (size_t)image * a.cap;
+    for (int r0 = 0; r0 < a.rows; r0 += 1024) {          // (uniform trip count: barriers inside)
+        const int r = r0 + tid;
+        const bool f = r < a.rows && tile_pass(a, a.scores[s0 + r]);
+        int tot;
+        const int at = pos + block_rank(f, wcnt, tot);
+        if (f && at < a.cap) {
+            a.m_scores[m0 + at] = a.scores[s0 + r]; a.m_labels[m0 + at] = a.labels[s0 + r];
+            a.m_box[m0 + at] = tile_box(a, w, a.box4 ? a.box4 + (s0 + r) * 4 : a.det + (s0 + r) * a.attrs);
+        }
+        pos += tot;
+        __syncthreads();          // wcnt is rewritten by the next round
+    }
+    if (tid != 0) return;
+    const int after = s_before + mine;
+    const bool last_of_step = b == a.nb - 1 || a.wins[wi + 1].image != image, last_of_image = wi == a.nwin - 1 || a.wins[wi + 1].image != image;
+    if (last_of_step) a.run_out[image] = after;
+    if (last_of_image) {
+        a.total[image] = after;
+        if (after > a.cap) atomicMin(a.overflow, ((unsigned long long)(unsigned)image << 32) | (unsigned)after);
+    }
+}
+hipError_t launch_tile_merge(const TileMergeArgs &a, hipStream_t s)
+{
+    if (a.nb < 1 || a.first < 0 || a.first + a.nb > a.nwin || a.rows < 1 || a.cap < 1 || a.cap > TILE_MERGE_CAP || (a.fit != FIT_STRETCH && a.fit != FIT_LETTERBOX)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_tile_count, dim3(a.nb), dim3(1024), 0, s, a);
+    hipLaunchKernelGGL(k_tile_write, dim3(a.nb), dim3(1024), 0, s, a);
+    return hipGetLastError();
+}
+__global__ void k_tile_relative(BoxOut *out, const int *counts, int max_out, const ImgDesc *descs)
+{
+    const int img = blockIdx.x;
+    const int cnt = min(counts[img], max_out);
+    const float W = (float)descs[img].w, H = (float)descs[img].h;
+    for (int r = threadIdx.x; r < cnt; r += blockDim.x) {
+        BoxOut &b = out[(size_t)img * max_out + r];
+        b.x0 = __fdiv_rn(b.x0, W); b.y0 = __fdiv_rn(b.y0, H); b.x1 = __fdiv_rn(b.x1, W); b.y1 = __fdiv_rn(b.y1, H);
+    }
+}
+hipError_t launch_tile_relative(void *boxes, const int *counts, int max_out, const ImgDesc *descs, int n, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_tile_relative, dim3(n), dim3(64), 0, s, (BoxOut *)boxes, counts, max_out, descs);
+    return hipGetLastError();
+}
+
 // ---- X: `detections_boxes` (V3/yolo_v3.py:329-347): (cx, cy, w, h, rest...) -> (x0, y0, x1, y1, rest...), w/2 form ----
 __global__ void k_boxes_to_corners(const float *in, float *out, size_t nrows, int attrs)
 {

@@ -159,6 +159,9 @@ struct yolo_ctx {
     // geometry the last such forward ran with (what the box mapping of its postprocess reads)
     ImgDesc *d_descs = nullptr; void *d_pix = nullptr; size_t pix_cap = 0;
     int geom_fit = -1, geom_n = 0;
+    // tiled detection (yolo_detect_tiled_u8): ONE allocation, grown on demand and never shrunk, that holds the window table, the image table, every
+    // image's merged candidate list and k_nms_image's workspace over those lists (tile_slab, yolo_run.cpp)
+    void *d_tile = nullptr; size_t tile_cap = 0;
     // hierarchical softmax ("Softmax trees"): the trees of the cfg's tree= keys; tree_head: the [region] layer that has one
     // (-1: none); hier_thresh: yolo_set_hier_thresh; hierarchy_mode: yolo_set_hierarchy_mode; tree_full: YOLO_TREE_FULL forces the full
     // decode in yolo_detect*; lean_hier: the hier_thresh the last descent-form decode labelled its rows with

@@ -742,6 +742,16 @@ int yolo_detect_graph(yolo_ctx *c, const void *images, int n, int fmt, float sca
 //      postprocess reads the same table ("Ragged batches") ----
 static_assert(sizeof(ImgDesc) == sizeof(yolo_image_desc) && sizeof(yolo_image_desc) == 16, "yolo_image_desc is the device table's row");
 
+// one image's place in the packed buffer
+static int desc_check(yolo_ctx *c, int i, const yolo_image_desc &d, size_t bytes)
+{
+    if (d.h < 1 || d.w < 1) return fail(c, YOLO_ERR_INVALID, "image %d: %d x %d", i, (int)d.h, (int)d.w);
+    const uint64_t need = (uint64_t)d.h * (uint64_t)d.w * 3u;
+    if (d.offset > bytes || need > bytes - d.offset)
+        return fail(c, YOLO_ERR_INVALID, "image %d: %d x %d x 3 bytes at offset %llu end past the %zu-byte buffer", i, (int)d.h, (int)d.w, (unsigned long long)d.offset, bytes);
+    return YOLO_OK;
+}
+
 // everything a ragged batch is refused for, before any launch
 static int images_check(yolo_ctx *c, const void *pixels, size_t bytes, const yolo_image_desc *descs, int n, int fit)
 {
@@ -752,10 +762,7 @@ static int images_check(yolo_ctx *c, const void *pixels, size_t bytes, const yol
     if (bytes < 3 || bytes > 0xffffffffull) return fail(c, YOLO_ERR_INVALID, "packed buffer of %zu bytes (3 .. 2^32 - 1)", bytes);
     for (int i = 0; i < n; ++i) {
         const yolo_image_desc &d = descs[i];
-        if (d.h < 1 || d.w < 1) return fail(c, YOLO_ERR_INVALID, "image %d: %d x %d", i, (int)d.h, (int)d.w);
-        const uint64_t need = (uint64_t)d.h * (uint64_t)d.w * 3u;
-        if (d.offset > bytes || need > bytes - d.offset)
-            return fail(c, YOLO_ERR_INVALID, "image %d: %d x %d x 3 bytes at offset %llu end past the %zu-byte buffer", i, (int)d.h, (int)d.w, (unsigned long long)d.offset, bytes);
+        if (int r = desc_check(c, i, d, bytes)) return r;
         if (fit == YOLO_FIT_LETTERBOX) {
             int nw, nh; letterbox_dims(c->in_w, c->in_h, d.w, d.h, &nw, &nh);
             if (nw < 1 || nh < 1) return fail(c, YOLO_ERR_INVALID, "image %d: %d x %d letterboxes to less than one pixel", i, (int)d.h, (int)d.w);
@@ -794,22 +801,29 @@ static int images_step(yolo_ctx *c, const uint8_t *pixels, size_t bytes, const y
     return run_network(c, n, lean, fit);
 }
 
+// the packed buffer on the device: a host buffer is staged with one host-to-device copy (d_pix: grown, never shrunk)
+static int stage_pixels(yolo_ctx *c, const uint8_t *pixels, size_t bytes, int loc, const uint8_t **src)
+{
+    *src = pixels;
+    if (loc != YOLO_HOST) return YOLO_OK;
+    if (bytes > c->pix_cap) {
+        HIPCK(c, hipStreamSynchronize(c->stream));
+        if (c->d_pix) HIPCK(c, hipFree(c->d_pix));
+        c->d_pix = nullptr; c->pix_cap = 0;
+        HIPCK(c, hipMalloc(&c->d_pix, bytes)); c->pix_cap = bytes;
+    }
+    HIPCK(c, hipMemcpyAsync(c->d_pix, pixels, bytes, hipMemcpyHostToDevice, c->stream));
+    *src = (const uint8_t *)c->d_pix;
+    return YOLO_OK;
+}
+
 static int forward_images_impl(yolo_ctx *c, const uint8_t *pixels, size_t bytes, const yolo_image_desc *descs, int n, int fit, int loc,
                                float *det_out, int out_loc, bool lean, float score_thr)
 {
     if (int r = images_check(c, pixels, bytes, descs, n, fit)) return r;
     HIPCK(c, hipSetDevice(c->device));
-    const uint8_t *src = pixels;
-    if (loc == YOLO_HOST) {              // one host-to-device copy of the packed buffer (grown, never shrunk)
-        if (bytes > c->pix_cap) {
-            HIPCK(c, hipStreamSynchronize(c->stream));
-            if (c->d_pix) HIPCK(c, hipFree(c->d_pix));
-            c->d_pix = nullptr; c->pix_cap = 0;
-            HIPCK(c, hipMalloc(&c->d_pix, bytes)); c->pix_cap = bytes;
-        }
-        HIPCK(c, hipMemcpyAsync(c->d_pix, pixels, bytes, hipMemcpyHostToDevice, c->stream));
-        src = (const uint8_t *)c->d_pix;
-    }
+    const uint8_t *src = nullptr;
+    if (int r = stage_pixels(c, pixels, bytes, loc, &src)) return r;
     if (int r = images_step(c, src, bytes, descs, n, fit, true, lean && !det_out, score_thr)) return r;
     return det_out ? copy_out(c, det_out, c->d_det, (size_t)n * c->rows * c->attrs * 4, out_loc) : YOLO_OK;
 }
@@ -854,6 +868,160 @@ int yolo_detect_images_graph(yolo_ctx *c, const uint8_t *pixels, size_t bytes, c
     if (int r = graph_step(c, c->graph[1], k, eager, &replayed)) return r;
     if (replayed) { c->lean_thr = score_thr; c->stem_u8 = nullptr; forward_done(c, n, nms_mode != YOLO_NMS_NUMPY_V3, nms_mode == YOLO_NMS_NUMPY_V3 ? 1 : 0, fit); }
     return YOLO_OK;
+}
+
+// ---- tiled detection of images larger than the network input ("Tiled detection"): the window grid, then per chunk of max_batch windows one
+//      fit launch over the window table + the network + the cross-window merge, and ONE k_nms_image launch over every image's merged list ----
+namespace {
+// one axis of the grid: image extent L, tile extent T, overlap O
+struct TileAxis {
+    int L, T, S, n;
+    TileAxis(int L_, int T_, int O) : L(L_), T(T_), S(T_ - O), n(L_ <= T_ ? 1 : (int)(((long long)L_ - T_ + S - 1) / S) + 1) {}
+    int start(int k) const { return L <= T ? 0 : (int)std::min<long long>((long long)k * S, L - T); }
+    int extent() const { return L <= T ? L : T; }
+};
+bool tile_args_ok(int img_h, int img_w, int tile_h, int tile_w, int overlap_h, int overlap_w)
+{
+    return img_h >= 1 && img_w >= 1 && tile_h >= 1 && tile_w >= 1 && overlap_h >= 0 && overlap_w >= 0 && overlap_h < tile_h && overlap_w < tile_w;
+}
+// the carving of yolo_ctx::d_tile for a call of `images` images, `nwin` windows, `cap` merged rows per image and max_out records: every array 256-byte aligned
+struct TileSlab {
+    WinDesc *wins; ImgDesc *descs; unsigned long long *overflow; float *scores; int *labels; float4 *box; int *cand; unsigned long long *keys; float4 *sbox; int *slabel; float *sscore;
+    yolo_box *boxes; int *counts, *wcount, *run[2], *total; size_t bytes, nan_fill;      // nan_fill: bytes from `overflow` to the end of `scores`, set to all ones before the first step
+    TileSlab(char *base, size_t images, size_t nwin, size_t cap, size_t pow2, size_t max_out, size_t max_batch)
+    {
+        size_t off = 0;
+        auto take = [&](size_t n) { const uintptr_t p = (uintptr_t)base + off; off += (n + 255) & ~(size_t)255; return (void *)p; };      // (base == nullptr: the sizes only)
+        wins = (WinDesc *)take(nwin * sizeof(WinDesc)); descs = (ImgDesc *)take(images * sizeof(ImgDesc));
+        overflow = (unsigned long long *)take(8); scores = (float *)take(images * cap * 4); nan_fill = (size_t)((char *)scores - (char *)overflow) + images * cap * 4;
+        labels = (int *)take(images * cap * 4); box = (float4 *)take(images * cap * 16); cand = (int *)take(images * cap * 4); keys = (unsigned long long *)take(images * pow2 * 8);
+        sbox = (float4 *)take(images * cap * 16); slabel = (int *)take(images * cap * 4); sscore = (float *)take(images * cap * 4);
+        boxes = (yolo_box *)take(images * max_out * sizeof(yolo_box)); counts = (int *)take(images * 4); wcount = (int *)take(max_batch * 4);
+        run[0] = (int *)take(images * 4); run[1] = (int *)take(images * 4); total = (int *)take(images * 4);
+        bytes = off;
+    }
+};
+struct StreamDrain { yolo_ctx *c; ~StreamDrain() { hipStreamSynchronize(c->stream); } };      // host tables handed to asynchronous copies outlive them on every return path
+}
+
+int yolo_tile_windows(int img_h, int img_w, int tile_h, int tile_w, int overlap_h, int overlap_w, yolo_tile_window *out, int cap, int *count)
+{
+    if (!count) { g_op_err = "yolo_tile_windows: count == NULL"; return YOLO_ERR_INVALID; }
+    *count = 0;
+    if (!tile_args_ok(img_h, img_w, tile_h, tile_w, overlap_h, overlap_w) || cap < 0 || (cap > 0 && !out)) {
+        g_op_err = "yolo_tile_windows: image, tile extents >= 1 and 0 <= overlap < tile are needed (and out for cap > 0)"; return YOLO_ERR_INVALID;
+    }
+    const TileAxis ay(img_h, tile_h, overlap_h), ax(img_w, tile_w, overlap_w);
+    if ((long long)ay.n * ax.n > 0x7fffffffLL) { g_op_err = "yolo_tile_windows: 2^31 windows or more"; return YOLO_ERR_INVALID; }
+    *count = ay.n * ax.n;
+    for (int k = 0; k < std::min(cap, *count); ++k) out[k] = yolo_tile_window{ay.start(k / ax.n), ax.start(k % ax.n), ay.extent(), ax.extent()};
+    return YOLO_OK;
+}
+
+int yolo_detect_tiled_u8(yolo_ctx *c, const uint8_t *pixels, size_t bytes, const yolo_image_desc *descs, int n_images, int tile_h, int tile_w, int overlap_h,
+                         int overlap_w, int fit, int loc, float score_thr, float iou_thr, int max_out, int nms_mode, int select_mode, int relative,
+                         yolo_box *boxes_out, int32_t *counts_out, int out_loc)
+{
+    static const char *const who = "yolo_detect_tiled_u8";
+    if (!c) return YOLO_ERR_INVALID;
+    // ---- every refusal, before any launch ----
+    if (int r = need_detector(c, who)) return r;
+    if (!c->weights_loaded) return fail(c, YOLO_ERR_STATE, "%s before weights were loaded", who);
+    static const char *const fit_names[] = {"YOLO_FIT_STRETCH", "YOLO_FIT_LETTERBOX", "YOLO_FIT_CV2", "YOLO_FIT_CV2_BGR", "YOLO_FIT_CENTER_CROP"};
+    if (fit < YOLO_FIT_STRETCH || fit > YOLO_FIT_CENTER_CROP) return fail(c, YOLO_ERR_INVALID, "bad fit %d", fit);
+    if (fit != YOLO_FIT_STRETCH && fit != YOLO_FIT_LETTERBOX)
+        return fail(c, YOLO_ERR_UNSUPPORTED, "%s: %s is not served: a window is fitted by YOLO_FIT_STRETCH or YOLO_FIT_LETTERBOX", who, fit_names[fit]);
+    if (int r = post_args_ok(c, max_out, nms_mode, select_mode)) return r;
+    if (nms_mode != YOLO_NMS_TF && nms_mode != YOLO_NMS_DARKNET)
+        return fail(c, YOLO_ERR_UNSUPPORTED, "%s: %s is not served: the merged candidates of an image go through YOLO_NMS_TF or YOLO_NMS_DARKNET", who,
+                    nms_mode == YOLO_NMS_PER_CLASS ? "YOLO_NMS_PER_CLASS" : nms_mode == YOLO_NMS_TF_V1 ? "YOLO_NMS_TF_V1" : "YOLO_NMS_NUMPY_V3");
+    if (c->tree_head >= 0) return fail(c, YOLO_ERR_UNSUPPORTED, "%s: a softmax-tree head is not served", who);
+    if (fit == YOLO_FIT_LETTERBOX)
+        for (auto &L : c->layers) if (L.type == L_DETECT) return fail(c, YOLO_ERR_UNSUPPORTED, "%s: letterbox box mapping of a [detection] head (darknet v1 does not letterbox)", who);
+    if (relative != 0 && relative != 1) return fail(c, YOLO_ERR_INVALID, "bad relative %d", relative);
+    if (!boxes_out || !counts_out) return fail(c, YOLO_ERR_INVALID, "boxes_out / counts_out == NULL");
+    if (n_images < 1) return fail(c, YOLO_ERR_INVALID, "%d images", n_images);
+    if (!pixels || !descs) return fail(c, YOLO_ERR_INVALID, "pixels / descs == NULL");
+    if (bytes < 3 || bytes > 0xffffffffull) return fail(c, YOLO_ERR_INVALID, "packed buffer of %zu bytes (3 .. 2^32 - 1)", bytes);
+    if (tile_h == 0 && tile_w == 0) { tile_h = c->in_h; tile_w = c->in_w; }
+    if (!tile_args_ok(1, 1, tile_h, tile_w, overlap_h, overlap_w))
+        return fail(c, YOLO_ERR_INVALID, "%s: tile %d x %d with overlap %d x %d: extents >= 1 and 0 <= overlap < tile are needed", who, tile_h, tile_w, overlap_h, overlap_w);
+    std::vector<WinDesc> wins;
+    int most = 0;                                                          // windows of the image that has the most
+    try {
+        for (int i = 0; i < n_images; ++i) {
+            const yolo_image_desc &d = descs[i];
+            if (int r = desc_check(c, i, d, bytes)) return r;
+            if ((uint64_t)d.w * 3u > 0x7fffffffull) return fail(c, YOLO_ERR_INVALID, "image %d: a row of %d pixels does not fit a 32-bit pitch", i, (int)d.w);
+            const TileAxis ay(d.h, tile_h, overlap_h), ax(d.w, tile_w, overlap_w);
+            if ((long long)ay.n * ax.n + (long long)wins.size() > 0x7fffffffLL) return fail(c, YOLO_ERR_INVALID, "image %d: 2^31 windows or more", i);
+            most = std::max(most, ay.n * ax.n);
+            for (int k = 0; k < ay.n * ax.n; ++k) {
+                WinDesc w; w.y0 = ay.start(k / ax.n); w.x0 = ax.start(k % ax.n); w.h = ay.extent(); w.w = ax.extent(); w.pitch = d.w * 3; w.image = i;
+                w.offset = d.offset + (uint64_t)w.y0 * (uint64_t)w.pitch + (uint64_t)w.x0 * 3u;
+                if (fit == YOLO_FIT_LETTERBOX) {
+                    int nw, nh; letterbox_dims(c->in_w, c->in_h, w.w, w.h, &nw, &nh);
+                    if (nw < 1 || nh < 1) return fail(c, YOLO_ERR_INVALID, "image %d: its %d x %d window letterboxes to less than one pixel", i, w.h, w.w);
+                }
+                wins.push_back(w);
+            }
+        }
+    } catch (const std::bad_alloc &) { return fail(c, YOLO_ERR_NOMEM, "%s: the window table", who); }
+    const int nwin = (int)wins.size();
+    const size_t cap = (size_t)std::min<long long>(TILE_MERGE_CAP, (long long)most * c->rows);
+    size_t pow2 = 1; while (pow2 < cap) pow2 <<= 1;
+    const TileSlab need(nullptr, n_images, nwin, cap, pow2, max_out, c->max_batch);
+
+    // ---- device ----
+    HIPCK(c, hipSetDevice(c->device));
+    const uint8_t *src = nullptr;
+    if (int r = stage_pixels(c, pixels, bytes, loc, &src)) return r;
+    if (need.bytes > c->tile_cap) {
+        HIPCK(c, hipStreamSynchronize(c->stream));
+        if (c->d_tile) HIPCK(c, hipFree(c->d_tile));
+        c->d_tile = nullptr; c->tile_cap = 0;
+        HIPCK(c, hipMalloc(&c->d_tile, need.bytes)); c->tile_cap = need.bytes;
+    }
+    const TileSlab t((char *)c->d_tile, n_images, nwin, cap, pow2, max_out, c->max_batch);
+    StreamDrain drain{c};
+    HIPCK(c, hipMemcpyAsync(t.wins, wins.data(), (size_t)nwin * sizeof(WinDesc), hipMemcpyHostToDevice, c->stream));
+    HIPCK(c, hipMemcpyAsync(t.descs, descs, (size_t)n_images * sizeof(ImgDesc), hipMemcpyHostToDevice, c->stream));
+    // the overflow word starts as all ones; so does every merged score: a NaN, which neither `>` nor `>=` lets through the NMS's own threshold
+    HIPCK(c, hipMemsetAsync(t.overflow, 0xff, t.nan_fill, c->stream));
+    c->lean_thr = score_thr;
+    TileMergeArgs m; memset(&m, 0, sizeof m);
+    m.wins = t.wins; m.nwin = nwin; m.rows = c->rows; m.attrs = c->attrs; m.scores = c->d_scores; m.labels = c->d_labels; m.score_thr = score_thr; m.select_mode = select_mode;
+    m.fit = fit; m.netw = c->in_w; m.neth = c->in_h; m.centre = nms_mode == YOLO_NMS_DARKNET; m.cap = (int)cap;
+    m.net_pixels = c->decode == YOLO_DECODE_PIXEL;          // [region] / [detection] heads always decode normalised boxes
+    for (auto &L : c->layers) if (L.type == L_REGION || L.type == L_DETECT) m.net_pixels = 0;
+    m.m_scores = t.scores; m.m_labels = t.labels; m.m_box = t.box; m.wcount = t.wcount; m.total = t.total; m.overflow = t.overflow;
+    for (int first = 0, step = 0; first < nwin; first += c->max_batch, ++step) {
+        const int nb = std::min(c->max_batch, nwin - first);
+        auto [dst, dt] = input_fill_dst(c);
+        HIPCK(c, launch_fit_windows(src, bytes, t.wins + first, nb, fit, c->in_h, c->in_w, dst, dt, 8, c->in_mul, c->in_add, c->stream));
+        HIPCK(c, input_filled(c, (size_t)nb * c->in_h * c->in_w));
+        if (int r = run_network(c, nb, true)) return r;
+        m.first = first; m.nb = nb; m.det = c->d_det; m.box4 = c->det_valid ? nullptr : c->d_box4;
+        m.run_in = t.run[step & 1]; m.run_out = t.run[(step + 1) & 1];
+        HIPCK(c, launch_tile_merge(m, c->stream));
+    }
+    // one NMS launch over the merged lists: rows that hold the box in the form the flavour reads, scores and labels beside them
+    PostArgs p; memset(&p, 0, sizeof p);
+    p.box4 = (const float *)t.box; p.n = n_images; p.rows = (int)cap; p.attrs = 4; p.score_thr = score_thr; p.iou_thr = iou_thr; p.max_out = max_out;
+    p.nms_mode = nms_mode; p.select_mode = select_mode; p.scores_ready = 1; p.corners_in = 1;
+    p.scores = t.scores; p.labels = t.labels; p.cand = t.cand; p.keys = t.keys; p.rows_pow2 = (int)pow2; p.sbox = t.sbox; p.slabel = t.slabel; p.sscore = t.sscore;
+    p.boxes_out = t.boxes; p.counts_out = t.counts;
+    if (c->lean_cnt_dirty) p.zero_word = c->d_lean_cnt;
+    HIPCK(c, launch_postprocess(p, c->stream));
+    c->lean_cnt_dirty = false;
+    if (relative) HIPCK(c, launch_tile_relative(t.boxes, t.counts, max_out, t.descs, n_images, c->stream));
+    unsigned long long over = 0;
+    if (int r = copy_out(c, &over, t.overflow, 8, YOLO_HOST)) return r;          // (synchronises)
+    if (over != ~0ull)
+        return fail(c, YOLO_ERR_UNSUPPORTED, "%s: image %u yields %u candidates above the score threshold, more than the %zu one NMS launch serves; raise score_thr or enlarge the tile",
+                    who, (unsigned)(over >> 32), (unsigned)(over & 0xffffffffu), cap);
+    if (int r = copy_out(c, boxes_out, t.boxes, (size_t)n_images * max_out * sizeof(yolo_box), out_loc)) return r;
+    return copy_out(c, counts_out, t.counts, (size_t)n_images * 4, out_loc);
 }
 
 // ---- classifier contexts: forward + tail; the [softmax] launch of the output layer selects the top_k itself (run_layer) ----

@@ -74,6 +74,18 @@ class _Detector:
                 out.append((r["score"], np.stack([r["x0"], r["y0"], r["x1"], r["y1"]], -1).reshape(-1, 4), r["cls"]))
         return out
 
+    def detect_from_large_images(self, images, tile=None, overlap=64):
+        """Images much larger than the network input (a 4K frame, an aerial photo): each is cut into overlapping windows of `tile` (None:
+        the network's input size) that run max_batch at a time, the candidates of an image's windows are merged and ONE NMS per image
+        suppresses duplicates across windows (Engine.detect_tiled, stretch fit, the detector's thresholds and selection mode).
+        -> [(scores, boxes, classes)] per image, boxes normalised to the image like detect_from_image's."""
+        out = []
+        for r in self.engine.detect_tiled([np.ascontiguousarray(im, dtype=np.uint8) for im in images], tile=tile, overlap=overlap,
+                                          fit=hip.FIT_STRETCH, relative=True, score_thr=self.threshold, iou_thr=self.iou_threshold,
+                                          max_out=self.max_output_size, nms_mode=hip.NMS_TF, select_mode=self.select_mode):
+            out.append((r["score"], np.stack([r["x0"], r["y0"], r["x1"], r["y1"]], -1).reshape(-1, 4), r["cls"]))
+        return out
+
     def detect_from_file(self, image_file, imshow=False, deteted_boxes_file="boxes.txt", detected_image_file=None):
         """(sic: `deteted_boxes_file` is the reference's spelling.)  Reads the image with PIL instead of OpenCV and
         returns the predictions; with `detected_image_file` the boxes are drawn (draw.draw_detection) and the picture is saved."""

@@ -49,6 +49,7 @@ EXPORTS = [
     "yolo_output_map_geometry", "yolo_output_map", "yolo_label_map", "yolo_segment_images_u8", "yolo_op_deconv2d", "yolo_op_l2norm", "yolo_op_upsample", "yolo_op_label_map",
     "yolo_op_conv2d_grouped", "yolo_op_conv2d_pad", "yolo_op_lrn",
     "yolo_num_state_tensors", "yolo_state_geometry", "yolo_get_state", "yolo_set_state", "yolo_reset_state",
+    "yolo_tile_windows", "yolo_detect_tiled_u8",
 ]
 HIER_CONDITIONAL, HIER_ABSOLUTE, HIER_LEAVES = 0, 1, 2
 _HIER_MODES = {None: HIER_CONDITIONAL, "conditional": HIER_CONDITIONAL, "absolute": HIER_ABSOLUTE, "leaves": HIER_LEAVES}
@@ -172,6 +173,8 @@ def load_library():
     l.yolo_get_state.argtypes = [P, I, I, P, SZ]
     l.yolo_set_state.argtypes = [P, I, I, P, SZ]
     l.yolo_reset_state.argtypes = [P, I]
+    l.yolo_tile_windows.argtypes = [I, I, I, I, I, I, P, I, C.POINTER(I)]
+    l.yolo_detect_tiled_u8.argtypes = [P, P, SZ, P, I, I, I, I, I, I, I, F, F, I, I, I, I, P, P, I]
     l.yolo_shard_bounds.argtypes = [I, I, I, C.POINTER(I), C.POINTER(I)]
     l.yolo_dist_flat_words.argtypes = [I, I]; l.yolo_dist_flat_words.restype = C.c_size_t
     l.yolo_dist_split_records.argtypes = [P, I, I, I, P, P]
@@ -244,6 +247,29 @@ def fit_unit_value(fit, value):
     """What one source byte contributes to a fit's arithmetic before interpolation (yolo_fit_unit_value): host evaluation of the
     expression the fit kernel evaluates."""
     return load_library().yolo_fit_unit_value(fit, value)
+
+
+def _pair(v, what):
+    """an int, or an (h, w) pair -> (h, w) ints"""
+    if np.ndim(v) == 0:
+        return int(v), int(v)
+    if len(v) != 2:
+        raise YoloError("%s: an int or an (h, w) pair, got %r" % (what, v))
+    return int(v[0]), int(v[1])
+
+
+def tile_windows(img_hw, tile_hw, overlap_hw):
+    """yolo_tile_windows: the window grid an image of img_hw = (h, w) is cut into by tiles of tile_hw with overlap_hw pixels of overlap
+    (each an int or an (h, w) pair) -> int32 [count, 4] rows (y0, x0, h, w), row-major.  Per axis: an image no larger than the tile is
+    one window of its own extent; otherwise stride = tile - overlap, ceil((L - tile) / stride) + 1 windows of the tile's extent, the last
+    pulled back to the image's edge.  Host code: no device."""
+    l = load_library()
+    (ih, iw), (th, tw), (oh, ow) = _pair(img_hw, "img_hw"), _pair(tile_hw, "tile_hw"), _pair(overlap_hw, "overlap_hw")
+    n = C.c_int(0)
+    _op_check(l.yolo_tile_windows(ih, iw, th, tw, oh, ow, None, 0, C.byref(n)), "yolo_tile_windows")
+    out = np.zeros((n.value, 4), dtype=np.int32)
+    _op_check(l.yolo_tile_windows(ih, iw, th, tw, oh, ow, out.ctypes.data, n.value, C.byref(n)), "yolo_tile_windows")
+    return out
 
 
 def _stream_handle(stream):
@@ -525,6 +551,25 @@ class Engine:
         self._check(self.lib.yolo_detect_images_u8(self.ctx, p, nbytes, descs.ctypes.data, n, fit, loc, score_thr, iou_thr, max_out,
                                                    nms_mode, select_mode, units, boxes.ctypes.data, counts.ctypes.data, HOST),
                     "yolo_detect_images_u8")
+        return [boxes[i, :counts[i]].copy() for i in range(n)]
+
+    def detect_tiled(self, images, tile=None, overlap=(64, 64), fit=FIT_STRETCH, relative=False, score_thr=0.5, iou_thr=0.5, max_out=20,
+                     nms_mode=NMS_TF, select_mode=SELECT_GT):
+        """Detection in images larger than the network input (yolo_detect_tiled_u8): every image (a list of uint8 RGB [h, w, 3] arrays of any
+        sizes and any number, or a (buffer, descs) pair from pack_images) is cut into overlapping windows of `tile` (None: the network's
+        input size; an int or (h, w)) -- tile_windows states the grid --, the windows run max_batch at a time, their candidates are merged
+        per image in source-image pixels and ONE NMS per image suppresses duplicates across windows.  -> list of BOX_DTYPE arrays, at most
+        max_out records per image, in the image's pixels, or divided by its width and height with relative=True; NMS_DARKNET records hold
+        (cx, cy, w, h) as detect_images reports them.  fit: FIT_STRETCH or FIT_LETTERBOX; nms_mode: NMS_TF or NMS_DARKNET."""
+        buf, descs, p, loc, nbytes = self._packed(images)
+        n = len(descs)
+        th, tw = (0, 0) if tile is None else _pair(tile, "tile")
+        oh, ow = _pair(overlap, "overlap")
+        self._order_after_producer(buf)
+        boxes = np.zeros((n, max_out), dtype=BOX_DTYPE); counts = np.zeros(n, dtype=np.int32)
+        self._check(self.lib.yolo_detect_tiled_u8(self.ctx, p, nbytes, descs.ctypes.data, n, th, tw, oh, ow, fit, loc, score_thr, iou_thr, max_out,
+                                                  nms_mode, select_mode, 1 if relative else 0, boxes.ctypes.data, counts.ctypes.data, HOST),
+                    "yolo_detect_tiled_u8")
         return [boxes[i, :counts[i]].copy() for i in range(n)]
 
     def detect_images_graph(self, pixels_dev, descs, boxes_out, counts_out, fit=FIT_STRETCH, units=UNITS_NETWORK, score_thr=0.5,
