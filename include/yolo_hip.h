@@ -321,6 +321,41 @@ int yolo_get_state(yolo_ctx *ctx, int k, int stream, float *out, size_t out_floa
 int yolo_set_state(yolo_ctx *ctx, int k, int stream, const float *in, size_t in_floats);
 int yolo_reset_state(yolo_ctx *ctx, int stream);                 /* darknet's reset_network_state(net, b); stream < 0: every stream */
 
+/* ---- vector-input networks: char-rnn ([net] yolo_input=vector, inputs=N) ------------------------------------------
+ * A cfg whose [net] section says yolo_input=vector and inputs=N (1 .. 2^24, no height / width) reads one row of N values per
+ * stream instead of an image; darknet ignores the key, so the same cfg loads there.  Served sections: [connected], [rnn], [gru],
+ * [lstm], [dropout], [activation], [softmax], [cost]; configurations: bf16, fp16, fp32.  The output layer must be a [softmax].
+ * The image entry points (yolo_forward*, yolo_detect*, yolo_classify*, the tiled and map calls) refuse such a network and the
+ * calls below refuse an image network; yolo_input_size reports 1 x 1 x N; the state calls, yolo_layer_output and the timing
+ * calls work as on any recurrent network.
+ *
+ * yolo_forward_vectors: ONE step of streams 0 .. n-1 over x, fp32 [n][N] (loc: where x lies); out (may be NULL, host): the
+ * output layer's probabilities [n][classes].
+ *
+ * yolo_sequence: `steps` steps of streams 0 .. n-1 in one call, without a host synchronisation between them.  Step t < forced
+ * (1 <= forced <= steps) feeds the one-hot row of tokens[t][b]; a later step feeds the token sampled from step t - 1.  A token
+ * is sampled from the output of every step t >= forced - 1 as darknet's test_char_rnn samples it (rnn.c:290-293 and
+ * sample_array, in fp32 and in their order of operations: probabilities below `clip` become 0, the rest are divided by their
+ * sum, and the first class at which uniforms[t - forced + 1][b] minus the running sum reaches 0 is taken), into
+ * tokens_out[t - forced + 1][b]: tokens_out is [steps - forced + 1][n].  uniforms == NULL is allowed only with steps == forced:
+ * nothing is sampled (teacher forcing, valid_char_rnn's scoring form) and tokens_out is not written.  probs_out (may be NULL) is
+ * [steps][n][N]: every step's [softmax] row as the layer wrote it.  test_char_rnn(seed, num): forced = len, steps = len - 1 + num.
+ * loc: where tokens, uniforms, tokens_out and probs_out lie, all of them (YOLO_HOST: copied up once, back once at the end;
+ * YOLO_DEVICE: read and written in place, stream-ordered; a device token outside 0 .. N-1 feeds a row of zeros).  States carry
+ * over calls: 12 steps equal 5 steps, then 7 with forced = 1 on the last sampled token.  Every check stands in front of the
+ * first launch: a refused call changes no state.
+ *
+ * yolo_set_temperature: the temperature of every [softmax] layer (rnn.c:261), > 0, until it is set again; yolo_reset_temperature
+ * gives every [softmax] layer the temperature its cfg section names (valid_char_rnn sets none).
+ * yolo_op_sample: the sampler alone over host arrays: probs [n][len] (len <= 8192), uniforms [n] -> out [n]. */
+int yolo_vector_inputs(const yolo_ctx *ctx);                 /* N; 0: an image network */
+int yolo_forward_vectors(yolo_ctx *ctx, const float *x, int n, int loc, float *out, size_t out_floats);
+int yolo_sequence(yolo_ctx *ctx, int n, int steps, const int32_t *tokens, int forced, const float *uniforms, float clip,
+                  int32_t *tokens_out, float *probs_out, int loc);
+int yolo_set_temperature(yolo_ctx *ctx, float t);
+int yolo_reset_temperature(yolo_ctx *ctx);
+int yolo_op_sample(const float *probs, int n, int len, const float *uniforms, float clip, int32_t *out, int device);
+
 /* ---- introspection / measurement ------------------------------------------------------------ */
 /* Copies layer `index`'s output of the last forward as fp32 NHWC [n,H,W,C] to host (needs
  * keep_layers=1; without it only a conv layer's own tensor that still sits in its buffer after the

@@ -510,8 +510,22 @@ def unet(size=416, classes=21, base=32):
 HEADER = "# generated by tools/make_cfgs.py -- do not edit\n"
 
 
+def char_rnn(inputs=256, units=1024, layers=3):
+    """darknet's rnn.cfg (cfg/rnn.cfg of the reference): a one-hot byte in, three batch-normalised leaky [rnn] layers of 1024 units, a leaky
+    [connected] back to the 256 symbols, [softmax], [cost].  As darknet writes it: `inputs=` and no image size; CharRNN and the darknet veneer
+    add the [net] key yolo_input=vector that declares such an input here (darknet_io.with_vector_input)."""
+    rnn = "[rnn]\nbatch_normalize=1\noutput=%d\nactivation=leaky\n\n" % units
+    return "[net]\ninputs=%d\nbatch=1\ntime_steps=1\n\n" % inputs + rnn * layers + "[connected]\noutput=%d\nactivation=leaky\n\n[softmax]\n\n[cost]\n" % inputs
+
+
 def main():
     import sys
+    if len(sys.argv) > 2 and sys.argv[1] == "--char-rnn":      # python tools/make_cfgs.py --char-rnn DIR: char-rnn.cfg, darknet's rnn.cfg shape
+        os.makedirs(sys.argv[2], exist_ok=True)
+        with open(os.path.join(sys.argv[2], "char-rnn.cfg"), "w") as f:
+            f.write(char_rnn())
+        print("wrote char-rnn.cfg to", sys.argv[2])
+        return
     if len(sys.argv) > 2 and sys.argv[1] == "--unet":          # python tools/make_cfgs.py --unet DIR: unet.cfg at 416 x 416
         os.makedirs(sys.argv[2], exist_ok=True)
         with open(os.path.join(sys.argv[2], "unet.cfg"), "w") as f:

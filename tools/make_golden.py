@@ -1186,6 +1186,101 @@ def gen_mini_seq(seed=93):
           "drift bf16 %.3g fp16 %.3g" % (data["drift16_bf16"].max(), data["drift16_fp16"].max()), os.path.getsize(path), "bytes")
 
 
+def mini_char_rnn_cfg():
+    """darknet's rnn.cfg in miniature, one layer of each recurrent kind: a one-hot symbol of 37 in, a batch-normalised leaky [rnn] of 24, a [gru] of
+    20, an [lstm] of 12, a leaky [connected] back to 37, [softmax] at temperature 0.7, [cost].  37, 20 and 12 are ragged against the 8-element
+    granule and the 16-row MFMA tile.  yolo_input=vector: the key this project declares the input with; darknet ignores it."""
+    return ("[net]\ninputs=37\nyolo_input=vector\n\n[rnn]\nbatch_normalize=1\noutput=24\nactivation=leaky\n\n[gru]\noutput=20\n\n[lstm]\noutput=12\n\n"
+            "[connected]\noutput=37\nactivation=leaky\n\n[softmax]\ntemperature=0.7\n\n[cost]\n")
+
+
+def gen_mini_char_rnn(seed=131, logit_peak=6.0):
+    """mini_char_rnn_cfg through the compiled reference as examples/rnn.c test_char_rnn drives it: ONE live network, srand(rseed), a 4-token seed,
+    then 8 tokens the reference's own sample_array draws from its clipped output (rnn.c:290-293), each fed back.  Recorded: every layer's output at
+    each of the 11 steps (before the clip touches the output), the tokens, the uniforms sample_array consumed -- srand(rseed) again and
+    (float)rand() / RAND_MAX --, per sampled step the distance of the uniform from the nearest boundary of the row's running sums (`margin`), and
+    drift16_* as in mini_seq.npz.  The [connected] layer's rows are scaled until the logits peak near `logit_peak`, so that some probabilities fall
+    below the clip; rseed is the first of 0 .. 15 at which every margin is at least 1e-3 and the clip changes a sampled row."""
+    import ctypes as C
+    import importlib.util
+    from oracle import darknet_ref as D
+    from yolo_tensorflow_amd import darknet_io as IO
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    spec = importlib.util.spec_from_file_location("test_char_rnn_host", os.path.join(ROOT, "tests", "test_char_rnn_host.py"))
+    CH = importlib.util.module_from_spec(spec); spec.loader.exec_module(CH)
+    RH = CH.RH
+    name, cfg, n_in, seed_len, sampled = "mini_char_rnn", mini_char_rnn_cfg(), 37, 4, 8
+    secs = IO.parse_cfg(cfg)
+    flat = IO.synth_weights(secs, seed=seed)
+    seed_tokens = np.random.default_rng(seed + 1).integers(0, n_in, seed_len).astype(np.int32)
+    libc = C.CDLL(None); libc.rand.restype = C.c_int
+    l = D.lib(); l.sample_array.argtypes = [C.POINTER(C.c_float), C.c_int]; l.sample_array.restype = C.c_int
+    nl = len(secs) - 2          # ([cost] holds nothing at inference)
+
+    def run(weights, rseed):
+        net = D.RefNet(cfg, weights, 0, 2)
+        libc.srand(C.c_uint(rseed))
+        outs, fed, toks = [[] for _ in range(nl)], [], []
+        x = np.zeros(n_in, dtype=np.float32)
+        def predict(c):
+            x[:] = 0; x[c] = 1
+            out = l.network_predict(net.net, x.ctypes.data_as(C.POINTER(C.c_float)))
+            fed.append(c)
+            for i in range(nl):
+                outs[i].append(np.asarray(net.layer_output_nhwc(i), dtype=np.float32).reshape(-1))
+            return out
+        for c in seed_tokens[:-1]:
+            predict(int(c))
+        c = int(seed_tokens[-1])
+        for _ in range(sampled):
+            out = predict(c)
+            for j in range(n_in):
+                if out[j] < .0001:
+                    out[j] = 0
+            c = int(l.sample_array(out, n_in))
+            toks.append(c)
+        net.close()
+        return [np.stack(o) for o in outs], np.array(fed, dtype=np.int32), np.array(toks, dtype=np.int32)
+
+    # the [rnn] layer's self sublayer (the second of the stream: biases, then its rows) is damped: a leaky state that feeds itself through rows of
+    # unit gain doubles per step, and the gates behind it would saturate within the 11 steps
+    rnn = IO.recurrent_specs(secs)[0]
+    at = IO.connected_floats(rnn["subs"][0][0], rnn["subs"][0][1], rnn["bn"]) + rnn["outputs"]
+    flat[at:at + rnn["outputs"] * rnn["outputs"]] *= np.float32(0.25)
+    # the [connected] layer's rows, scaled until the logits of the seed steps peak near logit_peak
+    last = IO.conv_specs(secs)[-1]
+    nw = last["filters"] * last["cin"]
+    logits = run(flat, 0)[0][nl - 2]
+    flat[-nw:] *= np.float32(round(logit_peak / float(np.abs(logits).max()), 2))
+    for rseed in range(16):
+        outs, fed, toks = run(flat, rseed)
+        libc.srand(C.c_uint(rseed))
+        uniforms = (np.array([libc.rand() for _ in range(sampled)], dtype=np.int64).astype(np.float32) / np.float32(2147483647)).astype(np.float32)
+        probs = outs[nl - 1][seed_len - 1:]
+        margin = np.array([CH.cdf_margin(probs[k], uniforms[k]) for k in range(sampled)], dtype=np.float64)
+        own = [CH.sample_np(probs[k], uniforms[k]) for k in range(sampled)]
+        assert own == toks.tolist(), (rseed, own, toks.tolist())          # the numpy restatement of the sampler is the reference's
+        print("rseed", rseed, "tokens", toks.tolist(), "margin min %.2e" % margin.min(), "clipped", int(((probs > 0) & (probs < 1e-4)).sum()))
+        if margin.min() >= 1e-3 and ((probs > 0) & (probs < 1e-4)).any() and len(set(toks.tolist())) > 1:
+            break
+    else:
+        raise SystemExit("no rseed of 0 .. 15 meets the fixture's conditions")
+    shapes = IO.layer_shapes(secs)
+    data = {"cfg": np.array(cfg), "weights": flat, "seed_tokens": seed_tokens, "rseed": np.int32(rseed), "uniforms": uniforms, "tokens": toks, "fed": fed, "margin": margin}
+    for i, o in enumerate(outs):
+        assert np.isfinite(o).all()
+        data["layer_%02d" % i] = o.reshape((len(fed),) + tuple(shapes[i][1:4]))
+    for tag, store in (("bf16", RH.bf16), ("fp16", RH.fp16)):
+        sim = CH.run_tokens(cfg, flat, fed, store)
+        data["drift16_" + tag] = np.array([[RH.standoff(sim[t][i], data["layer_%02d" % i][t]) for i in range(nl)] for t in range(len(fed))], dtype=np.float64)
+    exact = CH.run_tokens(cfg, flat, fed)
+    worst = max(RH.standoff(exact[t][i], data["layer_%02d" % i][t]) for t in range(len(fed)) for i in range(nl))
+    path = os.path.join(OUT, name + ".npz")
+    save_npz_reproducibly(path, data)
+    print(name, "rseed", rseed, "seed", seed_tokens.tolist(), "tokens", toks.tolist(), "p max", np.round(probs.max(axis=1), 3).tolist(), "margin min %.2e" % margin.min(),
+          "restatement stand-off %.2e" % worst, "drift bf16 %.3g fp16 %.3g" % (data["drift16_bf16"].max(), data["drift16_fp16"].max()), os.path.getsize(path), "bytes")
+
+
 def _lrn(size=None, alpha=None, beta=None, kappa=None):
     keys = [("size", size), ("alpha", alpha), ("beta", beta), ("kappa", kappa)]
     return "[normalization]\n" + "".join("%s=%s\n" % (k, v) for k, v in keys if v is not None) + "\n"
@@ -1351,6 +1446,8 @@ if __name__ == "__main__":
         gen_recurrent(); sys.exit(0)
     if sys.argv[1:] == ["lrn_crop"]:
         gen_lrn_crop(); sys.exit(0)
+    if sys.argv[1:] == ["char_rnn"]:
+        gen_mini_char_rnn(); sys.exit(0)
     stub_modules()
     gen_nms_v3()
     gen_v2_post()
@@ -1367,6 +1464,7 @@ if __name__ == "__main__":
     gen_edges()
     gen_recurrent()
     gen_lrn_crop()
+    gen_mini_char_rnn()
     gen_bn_real()
     gen_known_answers()
     gen_darknet_py_symbols()

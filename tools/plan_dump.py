@@ -26,7 +26,8 @@ FIXTURE = os.path.join(ROOT, "tests", "golden", "plan_dumps.json")
 # 3): nothing recorded there could pin them, tests/test_wide_host.py pins their geometry instead
 # ... and [rnn] / [gru] / [lstm] / [crnn] sections, which it refused too: tests/test_recurrent_host.py pins what their plans hold
 # ... and [crop] / [normalization] sections, likewise: tests/test_lrn_crop_host.py
-UNPINNED = ("zoo/alexnet", "golden/mini_wide", "golden/mini_seq", "golden/mini_crnn", "zoo/alexnet-lrn", "golden/mini_lrn")
+# ... and a vector-input network ([net] yolo_input=vector), which it refused for its missing image size: tests/test_char_rnn_host.py
+UNPINNED = ("zoo/alexnet", "golden/mini_wide", "golden/mini_seq", "golden/mini_crnn", "zoo/alexnet-lrn", "golden/mini_lrn", "golden/mini_char_rnn")
 PLANNER_RC = (0, -1, -6)          # YOLO_OK, YOLO_ERR_INVALID, YOLO_ERR_UNSUPPORTED: all build_plan returns for a cfg whose tree file opens
 
 

@@ -45,6 +45,25 @@ std::string trim(const std::string &s)
     return s.substr(a, b - a);
 }
 
+// darknet's char-rnn cfgs name `inputs=` and no image size in [net] (examples/rnn.c over rnn.cfg): the library wants such a network declared
+// ([net] yolo_input=vector); the key is added behind the [net] line of a cfg that lacks it
+void declare_vector_input(std::string &cfg)
+{
+    bool in_net = false, inputs = false, sized = false, declared = false; size_t net_end = std::string::npos;
+    for (size_t pos = 0; pos < cfg.size();) {
+        size_t e = cfg.find('\n', pos); if (e == std::string::npos) e = cfg.size();
+        const std::string line = trim(cfg.substr(pos, e - pos));
+        if (!line.empty() && line[0] == '[') { if (in_net) break; in_net = true; net_end = e; }
+        else if (in_net && !line.empty() && line[0] != '#' && line[0] != ';') {
+            const size_t eq = line.find('=');
+            const std::string k = trim(line.substr(0, eq)), v = eq == std::string::npos ? "" : trim(line.substr(eq + 1));
+            inputs |= k == "inputs"; declared |= k == "yolo_input"; sized |= (k == "height" || k == "width") && atoi(v.c_str()) > 0;
+        }
+        pos = e + 1;
+    }
+    if (inputs && !sized && !declared && net_end != std::string::npos) cfg.insert(net_end, "\nyolo_input=vector");
+}
+
 bool open_ctx(network *net)
 {
     yolo_config yc; memset(&yc, 0, sizeof yc);
@@ -82,6 +101,7 @@ network *load_network(char *cfg, char *weights, int clear)
     (void)clear;                                   // `*net->seen = 0`: training state, nothing to clear here
     network *net = new network();
     if (!read_text(cfg, net->cfg_text)) { fprintf(stderr, "darknet_hip: cannot open cfg '%s'\n", cfg ? cfg : "(null)"); delete net; return nullptr; }
+    declare_vector_input(net->cfg_text);
     if (weights && weights[0]) net->weights_path = weights;
     if (!open_ctx(net)) { delete net; return nullptr; }
     return net;
@@ -113,7 +133,10 @@ void set_batch_network(network *net, int b)
 float *network_predict(network *net, float *input)
 {
     if (!net || !input) return nullptr;
-    if (yolo_forward(net->ctx, input, net->batch, YOLO_IMG_F32_CHW, YOLO_HOST, 1.0f, nullptr, YOLO_HOST) != YOLO_OK) {
+    // a vector-input network (char-rnn): `input` is batch x inputs values, one step of the streams 0 .. batch-1
+    const int rc = yolo_vector_inputs(net->ctx) > 0 ? yolo_forward_vectors(net->ctx, input, net->batch, YOLO_HOST, nullptr, 0)
+                                                    : yolo_forward(net->ctx, input, net->batch, YOLO_IMG_F32_CHW, YOLO_HOST, 1.0f, nullptr, YOLO_HOST);
+    if (rc != YOLO_OK) {
         net->have = false; fprintf(stderr, "darknet_hip: %s\n", yolo_last_error(net->ctx)); return nullptr;
     }
     net->fwd_n = net->batch;

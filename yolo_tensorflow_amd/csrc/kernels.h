@@ -472,6 +472,24 @@ hipError_t launch_softmax_topk(const SoftmaxArgs &a, hipStream_t s);
 bool avgpool_softmax_ok(const TView &in, const SoftmaxArgs &a);
 hipError_t launch_avgpool_softmax(const TView &in, float *pooled, int pooled_stride, const SoftmaxArgs &a, hipStream_t s);
 
+// ---- vector-input networks and sequences (seq_ops.hip; DN/examples/rnn.c test_char_rnn, DN/utils.c:592-603 sample_array) ----
+// x fp32 [n][len] -> rows [n][row_stride] of `dt` (bf16 / fp16 / fp32), the elements len .. row_stride - 1 of every row zero; row_stride a multiple of 8
+hipError_t launch_vector_in(const float *x, int n, int len, void *rows, int row_stride, int dt, hipStream_t s);
+// tokens int32 [n] -> one-hot rows of the same form, each written whole (a token outside 0 .. len - 1: a row of zeros)
+hipError_t launch_token_in(const int32_t *tokens, int n, int len, void *rows, int row_stride, int dt, hipStream_t s);
+// One workgroup per stream samples a token from its fp32 probability row (probs [n][p_stride], len <= CLS_SOFTMAX_MAX values) as rnn.c:290-293 and
+// sample_array do, in their order, in fp32: p < clip -> 0; the sum in index order; every element times (float)(1. / sum); r = u, r -= a[i] until r <= 0,
+// else len - 1 (a row that is clipped whole included: NaN compares false).  tokens_out [n]; next_rows (may be null): the stream's one-hot row as
+// launch_token_in writes it; probs_out (may be null): the row as it was read, dense [n][len]
+struct SampleArgs {
+    const float *probs; int p_stride, n, len;
+    const float *uniforms; float clip;
+    int32_t *tokens_out;
+    void *next_rows; int row_stride, dt;
+    float *probs_out;
+};
+hipError_t launch_sample(const SampleArgs &a, hipStream_t s);
+
 // ---- hierarchical softmax: darknet's softmax trees (tree_ops.hip; DN/tree.c, DN/softmax_layer.c:41-48, DN/region_layer.c:171-181) ----
 // A tree on the device.  parent / child / leaf [n], goff / gsize [groups] as DN/tree.c:83-139 builds them; order [groups]: the groups
 // sorted by depth (the root group first), lvl [levels + 1]: where each depth begins in `order`.  A group's parent node lies in a

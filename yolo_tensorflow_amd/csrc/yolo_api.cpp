@@ -7,6 +7,7 @@ namespace yolo_impl {
 
 int need_map(yolo_ctx *c, const char *what)
 {
+    if (int r = need_image(c, what)) return r;
     if (c->map_layer < 0) return fail(c, YOLO_ERR_INVALID, "%s: the network is not a map network (a %s; [net] yolo_output=map declares one)", what, c->cls_layer >= 0 ? "classifier" : "detector");
     return YOLO_OK;
 }
@@ -81,7 +82,7 @@ void yolo_destroy(yolo_ctx *c)
     for (auto &L : c->layers) for (auto &S : L.sub) { if (S.d_w) hipFree(S.d_w); if (S.d_b) hipFree(S.d_b); }
     if (c->d_state_keep) hipFree(c->d_state_keep);
     void *ptrs[] = {c->input.ptr, c->d_zeros, c->d_stage, c->d_det, c->d_scores, c->d_labels, c->d_cand, c->d_keys, c->d_sbox, c->d_slabel, c->d_sscore, c->d_boxes, c->d_counts,
-                    c->d_dn_rec, c->d_dn_src, c->d_dn_count, c->d_dn_last, c->d_box4, c->s2d.ptr, c->d_srow, c->d_rows, c->d_lean_list, c->d_lean_cnt, c->d_f32a, c->d_f32b, c->d_descs, c->d_pix, c->d_tile, c->d_cls_idx, c->d_cls_prob, c->d_map_f32, c->d_map_labels, c->d_label_off};
+                    c->d_seq, c->d_dn_rec, c->d_dn_src, c->d_dn_count, c->d_dn_last, c->d_box4, c->s2d.ptr, c->d_srow, c->d_rows, c->d_lean_list, c->d_lean_cnt, c->d_f32a, c->d_f32b, c->d_descs, c->d_pix, c->d_tile, c->d_cls_idx, c->d_cls_prob, c->d_map_f32, c->d_map_labels, c->d_label_off};
     for (void *p : ptrs) if (p) hipFree(p);
     for (auto &t : c->trees) free_tree(t);
     if (c->d_map200) hipFree(c->d_map200);

@@ -79,7 +79,7 @@ struct Layer {
     std::vector<float> anchors;          // masked, in reference units
     // classifier tail: [softmax] keys; an [avgpool] whose fp32 input is pooled inside the launch of the [softmax] behind it (cls_ops.hip);
     // `cost`: a [cost] section (inference identity, never the network's output)
-    int groups = 1; float temperature = 1.f; bool pool_fused = false; bool cost = false;
+    int groups = 1; float temperature = 1.f, cfg_temperature = 1.f; bool pool_fused = false; bool cost = false;
     int tree = -1;                       // [region] / [softmax] with tree=: index into yolo_ctx::trees (hierarchical softmax), else -1
     // [rnn] / [gru] / [lstm] (L_RECUR; DESIGN.md "Recurrent layers"): `filters` units over the flattened producer (fc_h / fc_w / fc_c its geometry, cin = their
     // product, as a [connected] layer reads it); act: an [rnn]'s activation, any code (its kernel applies it).  One stacked matrix per launch: d_w / d_b
@@ -122,6 +122,9 @@ struct yolo_ctx {
     hipStream_t stream = nullptr; bool own_stream = false;
     int max_batch = 1, dtype = YOLO_BF16, semantics = YOLO_SEM_TF, decode = YOLO_DECODE_RATIO, keep_layers = 0;
     int in_h = 0, in_w = 0, in_c = 0;
+    // vector-input network ([net] yolo_input=vector, inputs=N: char-rnn): vec_n = N (0: an image network), in_h = in_w = 1, in_c = N, `input` one row of roundup(N, 8) elements per
+    // stream.  d_seq: yolo_sequence's slab (forced tokens, uniforms, sampled tokens, probabilities), grown on demand and never shrunk
+    int vec_n = 0; void *d_seq = nullptr; size_t seq_cap = 0;
     std::vector<Layer> layers;
     std::vector<Storage> storages;
     std::vector<void *> phys; std::vector<size_t> phys_bytes;
@@ -266,6 +269,7 @@ int stage_in(yolo_ctx *c, const void *images, int n, int fmt, int loc, float sca
 int run_network(yolo_ctx *c, int n, bool lean = false, int fit = -1);      // fit >= 0: the input is a fitted ragged batch (forward_done records its geometry)
 int copy_out(yolo_ctx *c, void *dst, const void *src, size_t bytes, int loc);
 int output_layer(const yolo_ctx *c);      // the network's output: the last layer that is not [cost] (DN/network.c:699-706)
+int need_image(yolo_ctx *c, const char *what);         // YOLO_ERR_INVALID with a message for a vector-input context ([net] yolo_input=vector)
 int need_detector(yolo_ctx *c, const char *what);      // YOLO_ERR_INVALID with a message for a classifier or a map context
 int post_args_ok(yolo_ctx *c, int max_out, int nms_mode, int select_mode);
 struct PostGeom { int fit, pixels; };      // per-image box mapping of a ragged batch (yolo_box_units), over c->d_descs

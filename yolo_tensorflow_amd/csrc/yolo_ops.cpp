@@ -449,6 +449,19 @@ int yolo_op_softmax(const float *x, int n, int len, int groups, float temperatur
     return S.download(probs_out, a.probs, (size_t)n * len * 4);
 }
 
+int yolo_op_sample(const float *probs, int n, int len, const float *uniforms, float clip, int32_t *out, int device)
+{
+    if (!probs || !uniforms || !out || n < 1 || len < 1) { g_op_err = "sample: bad arguments"; return YOLO_ERR_INVALID; }
+    if (len > CLS_SOFTMAX_MAX) { g_op_err = "sample: more than 8192 probabilities in a row"; return YOLO_ERR_UNSUPPORTED; }
+    OpScope S(device); if (S.rc) { g_op_err = "sample: no HIP device"; return S.rc; }
+    SampleArgs a; memset(&a, 0, sizeof a);
+    a.probs = (const float *)S.upload(probs, (size_t)n * len * 4); a.p_stride = len; a.n = n; a.len = len;
+    a.uniforms = (const float *)S.upload(uniforms, (size_t)n * 4); a.clip = clip; a.tokens_out = (int32_t *)S.alloc((size_t)n * 4);
+    if (S.rc) { g_op_err = "sample: allocation failed"; return S.rc; }
+    if (!S.ok(launch_sample(a, S.s))) { g_op_err = "sample: " + S.err; return S.rc; }
+    return S.download(out, a.tokens_out, (size_t)n * 4);
+}
+
 int yolo_op_tree_softmax(const float *x, int n, int len, const char *tree_path, float temperature, int mode, float *out, int device)
 {
     if (!x || !out || n < 1 || len < 1 || !(temperature > 0.f) || mode < YOLO_HIER_CONDITIONAL || mode > YOLO_HIER_LEAVES) { g_op_err = "tree_softmax: bad arguments"; return YOLO_ERR_INVALID; }

@@ -472,6 +472,7 @@ struct ArtReader {
 int yolo_export(yolo_ctx *c, const char *path)
 {
     if (!c) return YOLO_ERR_INVALID;
+    if (c->vec_n) return fail(c, YOLO_ERR_UNSUPPORTED, "yolo_export: the export artifact of a vector-input network ([net] yolo_input=vector) is not built");
     if (!c->weights_loaded) return fail(c, YOLO_ERR_STATE, "yolo_export before weights were loaded");
     HIPCK(c, hipSetDevice(c->device)); HIPCK(c, hipStreamSynchronize(c->stream));
     FILE *f = path ? fopen(path, "wb") : nullptr;

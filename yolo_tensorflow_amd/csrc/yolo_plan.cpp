@@ -484,7 +484,7 @@ static int parse_softmax(Cursor &k, const Section &s, Layer &L)
     yolo_ctx *c = k.c; const int i = k.i;
     if (c->dtype == YOLO_FP8) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [softmax] is not served in the fp8 configuration", i);
     if (opt_i(s, "spatial", 0)) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [softmax] with spatial=1 is not served", i);
-    L.type = L_SOFTMAX; L.groups = opt_i(s, "groups", 1); L.temperature = (float)atof(opt_s(s, "temperature", "1").c_str());
+    L.type = L_SOFTMAX; L.groups = opt_i(s, "groups", 1); L.temperature = L.cfg_temperature = (float)atof(opt_s(s, "temperature", "1").c_str());          // (cfg_temperature: what yolo_reset_temperature hands back)
     if (k.H != 1 || k.W != 1) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [softmax] over a %d x %d map (it must follow an [avgpool] or a [connected] layer)", i, k.H, k.W);
     if (!(L.temperature > 0.f)) return fail(c, YOLO_ERR_INVALID, "layer %d: [softmax] temperature must be > 0", i);
     if (s.kv.count("tree")) {
@@ -537,13 +537,31 @@ static int parse_sections(yolo_ctx *c, const std::vector<Section> &secs)
 {
     const Section &net = secs[0];
     c->in_h = opt_i(net, "height", 0); c->in_w = opt_i(net, "width", 0); c->in_c = opt_i(net, "channels", 3);
-    if (c->in_h <= 0 || c->in_w <= 0 || c->in_c != 3)
-        return fail(c, YOLO_ERR_UNSUPPORTED, "cfg: need an input of positive height and width with 3 channels (got %dx%dx%d)", c->in_w, c->in_h, c->in_c);
+    // [net] yolo_input=vector with inputs=N (char-rnn: DN/parser.c:656 net->inputs where the cfg names no image size): the input is one row of N values per stream.
+    // Without the key a cfg without a size stays refused, as before
+    const std::string in_kind = opt_s(net, "yolo_input", "");
+    if (!in_kind.empty() && in_kind != "vector") return fail(c, YOLO_ERR_INVALID, "cfg: yolo_input=%s (the one value is `vector`)", in_kind.c_str());
+    c->vec_n = 0;
+    if (!in_kind.empty()) {
+        const int N = opt_i(net, "inputs", 0);
+        if (c->in_h > 0 || c->in_w > 0) return fail(c, YOLO_ERR_INVALID, "cfg: yolo_input=vector together with height=%d / width=%d: a vector network has no image size (inputs= alone gives its length)", c->in_h, c->in_w);
+        if (N <= 0 || N > (1 << 24)) return fail(c, YOLO_ERR_INVALID, "cfg: yolo_input=vector needs inputs= of 1..%d (got %d)", 1 << 24, N);
+        if (!opt_s(net, "yolo_output", "").empty()) return fail(c, YOLO_ERR_UNSUPPORTED, "cfg: yolo_input=vector together with yolo_output=map is not served");
+        c->vec_n = N; c->in_h = 1; c->in_w = 1; c->in_c = N;
+    } else if (c->in_h <= 0 || c->in_w <= 0 || c->in_c != 3)
+        return fail(c, YOLO_ERR_UNSUPPORTED, "cfg: need an input of positive height and width with 3 channels (got %dx%dx%d); a vector-input network ([net] inputs=N, no image size) is declared with [net] yolo_input=vector", c->in_w, c->in_h, c->in_c);
     const int NL = (int)secs.size() - 1;
     // a recurrent layer is served in the bf16, fp16 and fp32 configurations: refused here, by its own name, ahead of whatever else of such a network the
     // configuration refuses.  ([net] time_steps is read and ignored: one call is one step)
     for (int i = 0; i < NL && (c->dtype == YOLO_FP8 || c->split()); ++i)
         if (is_recurrent(secs[i + 1].type)) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [%s] is not served in the %s configuration", i, secs[i + 1].type.c_str(), c->split() ? "split-fp16" : "fp8");
+    if (c->vec_n && (c->dtype == YOLO_FP8 || c->split()))
+        return fail(c, YOLO_ERR_UNSUPPORTED, "cfg: a vector-input network (yolo_input=vector) is not served in the %s configuration (bf16, fp16 and fp32 are)", c->split() ? "split-fp16" : "fp8");
+    // ... and serves the sections that read a row of values; the others are refused here, by name
+    static const char *const vector_sections[] = {"connected", "rnn", "gru", "lstm", "dropout", "activation", "softmax", "cost"};
+    for (int i = 0; i < NL && c->vec_n; ++i)
+        if (std::none_of(std::begin(vector_sections), std::end(vector_sections), [&](const char *t) { return secs[i + 1].type == t; }))
+            return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [%s] needs an image-shaped input: a vector-input network (yolo_input=vector) serves [connected], [rnn], [gru], [lstm], [dropout], [activation], [softmax] and [cost]", i, secs[i + 1].type.c_str());
     c->layers.resize(NL);
     c->rows = 0; c->attrs = 0; c->conv_flops = 0; c->weights_count = 0;
     // split-fp16 networks: per-tensor storage form (mixed plans): pairs unless a [convolutional] section says yolo_pair=0
@@ -601,6 +619,7 @@ static int network_kind(yolo_ctx *c, const Section &net)
     int o = (int)c->layers.size() - 1;
     while (o >= 0 && c->layers[o].cost) --o;
     if (out_kind.empty()) {
+        if (c->vec_n && (o < 0 || c->layers[o].type != L_SOFTMAX)) return fail(c, YOLO_ERR_INVALID, "cfg: the output layer of a vector-input network (its last layer that is not [cost]) must be a [softmax]");
         if (o < 0 || c->layers[o].type != L_SOFTMAX) return fail(c, YOLO_ERR_INVALID, "cfg has no [yolo] / [region] / [detection] head");
         c->cls_layer = o;
         return YOLO_OK;
@@ -957,7 +976,7 @@ int recur_sublayers(const Layer &L, int subs[8])
 }
 
 // elements per pixel of the tensor layer idx's view lies in (-1: the network input); valid once create_storages ran
-static int stride_of(const yolo_ctx *c, int idx) { return idx < 0 ? (c->in_pair ? 24 : 8) : c->layers[idx].storage >= 0 ? c->storages[c->layers[idx].storage].stride : 0; }
+static int stride_of(const yolo_ctx *c, int idx) { return idx < 0 ? (c->vec_n ? roundup(c->vec_n, 8) : c->in_pair ? 24 : 8) : c->layers[idx].storage >= 0 ? c->storages[c->layers[idx].storage].stride : 0; }
 
 RecurGeom recur_geom(const yolo_ctx *c, const Layer &L)
 {
@@ -998,10 +1017,10 @@ int allocate(yolo_ctx *c)
     }
     // network input: 3 real channels padded to 8
     c->input.dt = c->dtype == YOLO_FP32 ? DT_F32 : (c->dtype == YOLO_FP16 || c->split()) ? DT_F16 : DT_BF16;            // fp8 mode keeps the image in bf16
-    const int in_stride = c->in_pair ? 24 : 8;                 // split fp16: hi | lo | hi blocks of the 8 padded channels
-    size_t in_bytes = (size_t)c->max_batch * c->in_h * c->in_w * in_stride * dt_size(c->input.dt);
+    const int in_stride = stride_of(c, -1);                    // split fp16: hi | lo | hi blocks of the 8 padded channels; a vector network: [max_batch][roundup(N, 8)], the padding zero
+    size_t in_bytes = (size_t)c->max_batch * c->in_h * c->in_w * in_stride * dt_size(c->input.dt) + (c->vec_n ? 256 : 0);      // (+ a tail the 16-byte pieces of a row's reader may touch, as the pool's buffers have)
     HIPCK(c, hipMalloc(&c->input.ptr, in_bytes)); HIPCK(c, hipMemsetAsync(c->input.ptr, 0, in_bytes, c->stream));      // defined even if a timing pass runs before any image was staged
-    c->input.n = c->max_batch; c->input.h = c->in_h; c->input.w = c->in_w; c->input.c = 8; c->input.stride = in_stride;
+    c->input.n = c->max_batch; c->input.h = c->in_h; c->input.w = c->in_w; c->input.c = c->vec_n ? c->vec_n : 8; c->input.stride = in_stride;
     if (c->split()) {
         // fp32 staging for the layers that run in fp32 between a join and a split (input conversion, upsample, pooling, reorg)
         size_t cap = (size_t)c->max_batch * c->in_h * c->in_w * 8;
@@ -1023,10 +1042,12 @@ int allocate(yolo_ctx *c)
         }
         if (L.fc) {             // the flattened producer must be dense: one pixel of fc_h * fc_w * fc_c contiguous elements per image
             const TView in = view_of(c, L.in[0]);
-            if (in.stride != in.c || in.c != L.fc_c) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %zu: [connected] needs a dense producer (channels a multiple of 8, not part of a concat)", i);
+            // ... or, where the producer is one pixel (a vector network's input, a recurrent or [connected] layer), that pixel with its granule's zero padding
+            const bool one_pixel = L.fc_h * L.fc_w == 1 && in.c == L.fc_c && in.stride == L.cin_pad && in.dt == L.in_dt && c->vec_n;
+            if (!one_pixel && (in.stride != in.c || in.c != L.fc_c)) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %zu: [connected] needs a dense producer (channels a multiple of 8, not part of a concat)", i);
         }
     }
-    c->stage_bytes = (size_t)c->max_batch * c->in_h * c->in_w * 3 * 4;
+    c->stage_bytes = (size_t)c->max_batch * c->in_h * c->in_w * (c->vec_n ? c->vec_n : 3) * 4;
     HIPCK(c, hipMalloc(&c->d_stage, c->stage_bytes));
     HIPCK(c, hipMalloc((void **)&c->d_descs, (size_t)c->max_batch * sizeof(ImgDesc)));      // ragged batches: one descriptor per image
     size_t nr = (size_t)c->max_batch * c->rows;
@@ -1217,6 +1238,8 @@ int yolo_plan_dump(const char *cfg_text, int dtype, int max_batch, int keep_laye
         const Storage &s = c.storages[k];
         put("storage %zu def=%d last=%d bytes=%zu phys=%d stride=%d dt=%d persistent=%d\n", k, s.def, s.last, s.bytes, s.phys, s.stride, s.dt, (int)s.persistent);
     }
+    if (r == YOLO_OK && c.vec_n)          // (a line of its own, for a vector network only: the dump of every other cfg is pinned byte for byte)
+        put("vector_input inputs=%d stride=%d dt=%d streams=%d\n", c.vec_n, roundup(c.vec_n, 8), c.act_dt(), c.max_batch);
     if (r == YOLO_OK) {
         put("context in_h=%d in_w=%d in_c=%d in_pair=%d rows=%d attrs=%d cls_layer=%d map_layer=%d tree_head=%d in_mul=%a in_add=%a weights_count=%zu conv_flops=%a phys_bytes=[",
             c.in_h, c.in_w, c.in_c, (int)c.in_pair, c.rows, c.attrs, c.cls_layer, c.map_layer, c.tree_head, (double)c.in_mul, (double)c.in_add, c.weights_count, c.conv_flops);

@@ -519,8 +519,16 @@ int output_layer(const yolo_ctx *c)
     return o;
 }
 
+// the entry points that read images refuse a vector-input network by name, and point at the two that serve it
+int need_image(yolo_ctx *c, const char *what)
+{
+    if (c->vec_n) return fail(c, YOLO_ERR_INVALID, "%s: the network is a vector-input network ([net] yolo_input=vector: its input is a row of %d values, not an image); use yolo_forward_vectors / yolo_sequence", what, c->vec_n);
+    return YOLO_OK;
+}
+
 int need_detector(yolo_ctx *c, const char *what)
 {
+    if (int r = need_image(c, what)) return r;
     if (c->map_layer >= 0) return fail(c, YOLO_ERR_INVALID, "%s: the network is a map network ([net] yolo_output=map: its output is an image-shaped tensor, it has no detection head); use yolo_output_map / yolo_label_map / yolo_segment_images_u8", what);
     if (c->cls_layer >= 0) return fail(c, YOLO_ERR_INVALID, "%s: the network is a classifier (its output layer is a [softmax], it has no detection head); use yolo_classify*", what);
     return YOLO_OK;
@@ -591,6 +599,7 @@ extern "C" {
 static int forward_impl(yolo_ctx *c, const void *images, int n, int fmt, int loc, float scale, float *det_out, int out_loc, bool lean, float score_thr = 0.f)
 {
     if (!c) return YOLO_ERR_INVALID;
+    if (int r = need_image(c, "yolo_forward")) return r;
     c->lean_thr = score_thr;
     if (!c->weights_loaded) return fail(c, YOLO_ERR_STATE, "yolo_forward before weights were loaded");
     if (fmt != YOLO_IMG_U8 && fmt != YOLO_IMG_F32 && fmt != YOLO_IMG_F32_CHW) return fail(c, YOLO_ERR_INVALID, "bad image format");
@@ -611,6 +620,7 @@ typedef hipError_t (*FillOne)(yolo_ctx *c, const void *src, int h, int w, void *
 static int forward_one(yolo_ctx *c, const char *name, const char *fill_name, FillOne fill, const void *image, int h, int w, size_t bytes, int loc, float *det_out, int out_loc)
 {
     if (!c) return YOLO_ERR_INVALID;
+    if (int r = need_image(c, name)) return r;
     if (!c->weights_loaded) return fail(c, YOLO_ERR_STATE, "%s before weights were loaded", name);
     if (!image || h < 1 || w < 1) return fail(c, YOLO_ERR_INVALID, "bad image");
     HIPCK(c, hipSetDevice(c->device));
@@ -755,6 +765,7 @@ static int desc_check(yolo_ctx *c, int i, const yolo_image_desc &d, size_t bytes
 // everything a ragged batch is refused for, before any launch
 static int images_check(yolo_ctx *c, const void *pixels, size_t bytes, const yolo_image_desc *descs, int n, int fit)
 {
+    if (int r = need_image(c, "forward of images")) return r;
     if (!c->weights_loaded) return fail(c, YOLO_ERR_STATE, "forward of images before weights were loaded");
     if (n < 1 || n > c->max_batch) return fail(c, YOLO_ERR_INVALID, "batch %d outside 1..%d", n, c->max_batch);
     if (!pixels || !descs) return fail(c, YOLO_ERR_INVALID, "pixels / descs == NULL");
@@ -1027,6 +1038,7 @@ int yolo_detect_tiled_u8(yolo_ctx *c, const uint8_t *pixels, size_t bytes, const
 // ---- classifier contexts: forward + tail; the [softmax] launch of the output layer selects the top_k itself (run_layer) ----
 static int classify_check(yolo_ctx *c, int top_k, const int32_t *classes_out, const float *probs_out)
 {
+    if (int r = need_image(c, "yolo_classify")) return r;
     if (c->map_layer >= 0) return fail(c, YOLO_ERR_INVALID, "yolo_classify: the network is a map network ([net] yolo_output=map); use yolo_output_map / yolo_label_map");
     if (c->cls_layer < 0) return fail(c, YOLO_ERR_INVALID, "yolo_classify: the network is a detector (its output layer is not a [softmax])");
     const Layer &L = c->layers[c->cls_layer];
@@ -1098,6 +1110,111 @@ int yolo_segment_images_u8(yolo_ctx *c, const uint8_t *pixels, const yolo_image_
     if (label_offsets) HIPCK(c, hipMemsetAsync(c->d_map_labels, 0, total, c->stream));          // (gaps a caller's placement leaves)
     HIPCK(c, launch_segment_labels(map, map_stride, M.H, M.W, M.C, thresh, c->d_descs, c->d_label_off, n, fit, c->in_h, c->in_w, c->d_map_labels, c->stream));
     return copy_out(c, labels_u8, c->d_map_labels, total, YOLO_HOST);          // (synchronises: `off` outlives its asynchronous copy)
+}
+
+// ---- vector-input networks: one step over fp32 rows; many steps over tokens, the sampler's token fed back on the device ----
+int yolo_vector_inputs(const yolo_ctx *c) { return c ? c->vec_n : YOLO_ERR_INVALID; }
+
+static int need_vector(yolo_ctx *c, const char *what)
+{
+    if (!c->vec_n) return fail(c, YOLO_ERR_INVALID, "%s: the network reads images, not vectors ([net] yolo_input=vector with inputs=N declares a vector-input network); use yolo_forward* / yolo_detect* / yolo_classify*", what);
+    return YOLO_OK;
+}
+
+int yolo_forward_vectors(yolo_ctx *c, const float *x, int n, int loc, float *out, size_t out_floats)
+{
+    if (!c) return YOLO_ERR_INVALID;
+    if (int r = need_vector(c, "yolo_forward_vectors")) return r;
+    if (!c->weights_loaded) return fail(c, YOLO_ERR_STATE, "yolo_forward_vectors before weights were loaded");
+    if (n < 1 || n > c->max_batch) return fail(c, YOLO_ERR_INVALID, "batch %d outside 1..%d", n, c->max_batch);
+    if (!x) return fail(c, YOLO_ERR_INVALID, "x == NULL");
+    const Layer &O = c->layers[c->cls_layer];          // (the planner asks for a [softmax] output layer: dense fp32 rows)
+    if (out && out_floats < (size_t)n * O.C) return fail(c, YOLO_ERR_INVALID, "output buffer too small (%zu < %zu floats)", out_floats, (size_t)n * O.C);
+    HIPCK(c, hipSetDevice(c->device));
+    const float *src = x;
+    if (loc == YOLO_HOST) { HIPCK(c, hipMemcpyAsync(c->d_stage, x, (size_t)n * c->vec_n * 4, hipMemcpyHostToDevice, c->stream)); src = (const float *)c->d_stage; }
+    HIPCK(c, launch_vector_in(src, n, c->vec_n, c->input.ptr, c->input.stride, c->input.dt, c->stream));
+    if (int r = run_network(c, n)) return r;
+    return out ? copy_out(c, out, O.out.ptr, (size_t)n * O.C * 4, YOLO_HOST) : YOLO_OK;
+}
+
+int yolo_set_temperature(yolo_ctx *c, float t)
+{
+    if (!c) return YOLO_ERR_INVALID;
+    if (!(t > 0.f) || !std::isfinite(t)) return fail(c, YOLO_ERR_INVALID, "yolo_set_temperature: the temperature must be finite and > 0");
+    for (Layer &L : c->layers) if (L.type == L_SOFTMAX) L.temperature = t;
+    drop_graph(c);          // a captured step holds the old value as a kernel argument
+    return YOLO_OK;
+}
+
+int yolo_reset_temperature(yolo_ctx *c)
+{
+    if (!c) return YOLO_ERR_INVALID;
+    for (Layer &L : c->layers) if (L.type == L_SOFTMAX) L.temperature = L.cfg_temperature;
+    drop_graph(c);
+    return YOLO_OK;
+}
+
+int yolo_sequence(yolo_ctx *c, int n, int steps, const int32_t *tokens, int forced, const float *uniforms, float clip,
+                  int32_t *tokens_out, float *probs_out, int loc)
+{
+    static const char *const who = "yolo_sequence";
+    if (!c) return YOLO_ERR_INVALID;
+    // ---- every refusal, before any launch: a refused call changes no state ----
+    if (int r = need_vector(c, who)) return r;
+    if (!c->weights_loaded) return fail(c, YOLO_ERR_STATE, "%s before weights were loaded", who);
+    const int N = c->vec_n;
+    const Layer &O = c->layers[c->cls_layer];
+    if (c->cls_layer != output_layer(c) || O.C != N || O.groups != 1 || O.tree >= 0)
+        return fail(c, YOLO_ERR_UNSUPPORTED, "%s: the output layer must be a plain [softmax] over as many classes as the network has inputs (%d): the sampled token is the next input", who, N);
+    if (N > CLS_SOFTMAX_MAX) return fail(c, YOLO_ERR_UNSUPPORTED, "%s: %d classes (the sampler stages at most %d)", who, N, CLS_SOFTMAX_MAX);
+    if (n < 1 || n > c->max_batch) return fail(c, YOLO_ERR_INVALID, "%s: %d streams outside 1..%d", who, n, c->max_batch);
+    if (steps < 1 || steps > (1 << 24)) return fail(c, YOLO_ERR_INVALID, "%s: %d steps outside 1..%d", who, steps, 1 << 24);
+    if (forced < 1 || forced > steps) return fail(c, YOLO_ERR_INVALID, "%s: forced = %d outside 1..steps (%d)", who, forced, steps);
+    if (!tokens) return fail(c, YOLO_ERR_INVALID, "%s: tokens == NULL", who);
+    if (!uniforms && steps > forced) return fail(c, YOLO_ERR_INVALID, "%s: uniforms == NULL with steps (%d) > forced (%d): the steps behind the forced ones feed sampled tokens", who, steps, forced);
+    if (uniforms && !tokens_out) return fail(c, YOLO_ERR_INVALID, "%s: tokens_out == NULL", who);
+    if (loc != YOLO_HOST && loc != YOLO_DEVICE) return fail(c, YOLO_ERR_INVALID, "%s: bad loc %d", who, loc);
+    if (loc == YOLO_HOST)
+        for (size_t k = 0; k < (size_t)forced * n; ++k)
+            if (tokens[k] < 0 || tokens[k] >= N) return fail(c, YOLO_ERR_INVALID, "%s: token %d (step %zu, stream %zu) outside 0..%d", who, (int)tokens[k], k / n, k % n, N - 1);
+    const size_t sampled = uniforms ? (size_t)(steps - forced + 1) * n : 0, row = (size_t)n * N;
+
+    // ---- device ----
+    HIPCK(c, hipSetDevice(c->device));
+    const int32_t *d_tok = tokens; const float *d_uni = uniforms; int32_t *d_out = tokens_out; float *d_probs = probs_out;
+    if (loc == YOLO_HOST) {          // the slab: forced tokens | uniforms | sampled tokens | probabilities, each 256-byte aligned
+        auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+        const size_t o_uni = up((size_t)forced * n * 4), o_out = o_uni + up(sampled * 4), o_probs = o_out + up(sampled * 4), need = o_probs + (probs_out ? (size_t)steps * row * 4 : 0);
+        if (need > c->seq_cap) {
+            HIPCK(c, hipStreamSynchronize(c->stream));
+            if (c->d_seq) HIPCK(c, hipFree(c->d_seq));
+            c->d_seq = nullptr; c->seq_cap = 0;
+            HIPCK(c, hipMalloc(&c->d_seq, need)); c->seq_cap = need;
+        }
+        char *base = (char *)c->d_seq;
+        HIPCK(c, hipMemcpyAsync(base, tokens, (size_t)forced * n * 4, hipMemcpyHostToDevice, c->stream));
+        if (uniforms) HIPCK(c, hipMemcpyAsync(base + o_uni, uniforms, sampled * 4, hipMemcpyHostToDevice, c->stream));
+        d_tok = (const int32_t *)base; d_uni = (const float *)(base + o_uni); d_out = (int32_t *)(base + o_out); d_probs = probs_out ? (float *)(base + o_probs) : nullptr;
+    }
+    c->lean = false;
+    for (int t = 0; t < steps; ++t) {
+        if (t < forced) HIPCK(c, launch_token_in(d_tok + (size_t)t * n, n, N, c->input.ptr, c->input.stride, c->input.dt, c->stream));
+        if (int r = run_layers(c, n)) return r;
+        float *pt = d_probs ? d_probs + (size_t)t * row : nullptr;
+        if (uniforms && t >= forced - 1) {
+            SampleArgs a; memset(&a, 0, sizeof a);
+            a.probs = (const float *)O.out.ptr; a.p_stride = O.out.stride; a.n = n; a.len = N; a.uniforms = d_uni + (size_t)(t - forced + 1) * n; a.clip = clip;
+            a.tokens_out = d_out + (size_t)(t - forced + 1) * n; a.next_rows = c->input.ptr; a.row_stride = c->input.stride; a.dt = c->input.dt; a.probs_out = pt;
+            HIPCK(c, launch_sample(a, c->stream));
+        } else if (pt) HIPCK(c, hipMemcpy2DAsync(pt, (size_t)N * 4, O.out.ptr, (size_t)O.out.stride * 4, (size_t)N * 4, (size_t)n, hipMemcpyDeviceToDevice, c->stream));
+    }
+    forward_done(c, n, false);
+    if (loc != YOLO_HOST) return YOLO_OK;
+    if (probs_out) HIPCK(c, hipMemcpyAsync(probs_out, d_probs, (size_t)steps * row * 4, hipMemcpyDeviceToHost, c->stream));
+    if (sampled) HIPCK(c, hipMemcpyAsync(tokens_out, d_out, sampled * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    return YOLO_OK;
 }
 
 float yolo_fit_unit_value(int fit, int value)

@@ -199,10 +199,33 @@ def read_tree(path):
                 group_offset=a(goff), group_size=a(gsize), leaf=a(leaf))
 
 
+def vector_inputs(secs):
+    """N of a vector-input network ([net] yolo_input=vector, inputs=N: char-rnn), 0 for an image network."""
+    net = secs[0]
+    return int(net.get("inputs", 0)) if net.get("yolo_input") == "vector" else 0
+
+
+def with_vector_input(text):
+    """darknet's own char-rnn cfg ([net] inputs=N and no height / width) with the key that declares it here, `yolo_input=vector`, added to its
+    [net] section; a cfg that has the key, or an image size, is returned as it is.  darknet ignores the key, so the result still loads there."""
+    net = parse_cfg(text)[0]
+    if "yolo_input" in net or "inputs" not in net or int(net.get("height", 0)) > 0 or int(net.get("width", 0)) > 0:
+        return text
+    out, done = [], False
+    for line in text.splitlines():
+        out.append(line)
+        if not done and line.strip().startswith("["):
+            out.append("yolo_input=vector"); done = True
+    return "\n".join(out) + "\n"
+
+
 def layer_shapes(secs):
     """[(type, H, W, C_out, C_in)] per layer, darknet shape rules (DN/parser.c:730-875)."""
     net = secs[0]
-    H, W, C = int(net["height"]), int(net["width"]), int(net["channels"])
+    if vector_inputs(secs):                  # a vector-input network: one "pixel" of inputs= values, no image size is read
+        H, W, C = 1, 1, vector_inputs(secs)
+    else:
+        H, W, C = int(net["height"]), int(net["width"]), int(net["channels"])
     shapes = []
     for i, s in enumerate(secs[1:]):
         t, cin = s["type"], C

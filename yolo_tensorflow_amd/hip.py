@@ -50,6 +50,7 @@ EXPORTS = [
     "yolo_op_conv2d_grouped", "yolo_op_conv2d_pad", "yolo_op_lrn",
     "yolo_num_state_tensors", "yolo_state_geometry", "yolo_get_state", "yolo_set_state", "yolo_reset_state",
     "yolo_tile_windows", "yolo_detect_tiled_u8",
+    "yolo_vector_inputs", "yolo_forward_vectors", "yolo_sequence", "yolo_set_temperature", "yolo_reset_temperature", "yolo_op_sample",
 ]
 HIER_CONDITIONAL, HIER_ABSOLUTE, HIER_LEAVES = 0, 1, 2
 _HIER_MODES = {None: HIER_CONDITIONAL, "conditional": HIER_CONDITIONAL, "absolute": HIER_ABSOLUTE, "leaves": HIER_LEAVES}
@@ -175,6 +176,12 @@ def load_library():
     l.yolo_reset_state.argtypes = [P, I]
     l.yolo_tile_windows.argtypes = [I, I, I, I, I, I, P, I, C.POINTER(I)]
     l.yolo_detect_tiled_u8.argtypes = [P, P, SZ, P, I, I, I, I, I, I, I, F, F, I, I, I, I, P, P, I]
+    l.yolo_vector_inputs.argtypes = [P]
+    l.yolo_forward_vectors.argtypes = [P, P, I, I, P, SZ]
+    l.yolo_sequence.argtypes = [P, I, I, P, I, P, F, P, P, I]
+    l.yolo_set_temperature.argtypes = [P, F]
+    l.yolo_reset_temperature.argtypes = [P]
+    l.yolo_op_sample.argtypes = [P, I, I, P, F, P, I]
     l.yolo_shard_bounds.argtypes = [I, I, I, C.POINTER(I), C.POINTER(I)]
     l.yolo_dist_flat_words.argtypes = [I, I]; l.yolo_dist_flat_words.restype = C.c_size_t
     l.yolo_dist_split_records.argtypes = [P, I, I, I, P, P]
@@ -704,6 +711,51 @@ class Engine:
         """zero the states of one stream, or of every stream (darknet's reset_network_state)"""
         self._check(self.lib.yolo_reset_state(self.ctx, -1 if stream is None else int(stream)), "yolo_reset_state")
 
+    # ---- vector-input networks ([net] yolo_input=vector, inputs=N: char-rnn; include/yolo_hip.h) ----
+    @property
+    def vector_inputs(self):
+        """N of a vector-input network, 0 for an image network"""
+        return self.lib.yolo_vector_inputs(self.ctx)
+
+    def forward_vectors(self, x):
+        """one step of streams 0 .. n-1 over x, float32 [n, N] -> the output layer's probabilities [n, classes]"""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        if x.ndim != 2 or x.shape[1] != self.vector_inputs:
+            raise YoloError("forward_vectors: need a float32 [n, %d] array, got %s" % (self.vector_inputs, x.shape))
+        out = np.empty((x.shape[0], self.lib.yolo_num_classes(self.ctx)), dtype=np.float32)
+        self._check(self.lib.yolo_forward_vectors(self.ctx, x.ctypes.data, x.shape[0], HOST, out.ctypes.data, out.size), "yolo_forward_vectors")
+        return out
+
+    def sequence(self, tokens, steps, uniforms=None, clip=1e-4, want_probs=False):
+        """yolo_sequence over host arrays.  tokens: int32 [forced, n] (or [forced]: one stream), fed at the steps 0 .. forced-1; uniforms: float32
+        [steps - forced + 1, n] (or one-dimensional for one stream), or None with steps == forced (teacher forcing: nothing is sampled).
+        -> sampled tokens int32 [steps - forced + 1, n] (None without uniforms), or (tokens, probs float32 [steps, n, N]) with want_probs.
+        clip: probabilities below it (p < clip, in floats) are not drawn.  The default is the float 1e-4; darknet's rnn.c:291 compares with the
+        DOUBLE .0001, which also removes p == 1e-4f: char_rnn.CharRNN.CLIP is the float bound that reproduces darknet exactly."""
+        tok = np.ascontiguousarray(tokens, dtype=np.int32)
+        if tok.ndim == 1:
+            tok = tok.reshape(-1, 1)
+        forced, n = tok.shape if tok.ndim == 2 else (0, 0)
+        uni = out = probs = None
+        if uniforms is not None:
+            uni = np.ascontiguousarray(uniforms, dtype=np.float32).reshape(-1, max(n, 1))
+            if uni.shape[0] != steps - forced + 1:
+                raise YoloError("sequence: %d steps with %d forced tokens need uniforms [%d, %d], got %s" % (steps, forced, steps - forced + 1, n, uni.shape))
+            out = np.full(uni.shape, -1, dtype=np.int32)
+        if want_probs:
+            probs = np.empty((max(steps, 0), n, self.vector_inputs), dtype=np.float32)
+        self._check(self.lib.yolo_sequence(self.ctx, n, steps, tok.ctypes.data, forced, uni.ctypes.data if uni is not None else None, float(clip),
+                                           out.ctypes.data if out is not None else None, probs.ctypes.data if probs is not None else None, HOST), "yolo_sequence")
+        return (out, probs) if want_probs else out
+
+    def set_temperature(self, t):
+        """the temperature of every [softmax] layer (darknet's rnn.c:261), until it is set again or reset_temperature is called"""
+        self._check(self.lib.yolo_set_temperature(self.ctx, float(t)), "yolo_set_temperature")
+
+    def reset_temperature(self):
+        """every [softmax] layer back to the temperature its cfg section names"""
+        self._check(self.lib.yolo_reset_temperature(self.ctx), "yolo_reset_temperature")
+
     # ---- introspection / measurement ----
     def layer_output(self, index, n):
         dims = (C.c_int * 3)()
@@ -937,6 +989,17 @@ def op_softmax(x, groups=1, temperature=1.0, top_k=0, device=0):
     _op_check(load_library().yolo_op_softmax(x.ctypes.data, n, ln, groups, float(temperature), top_k, probs.ctypes.data,
                                              cls.ctypes.data if top_k else None, tkp.ctypes.data if top_k else None, device), "yolo_op_softmax")
     return (probs, cls, tkp) if top_k else probs
+
+
+def op_sample(probs, uniforms, clip=1e-4, device=0):
+    """darknet's sampler (rnn.c:290-293 + sample_array) over probs float32 [n, len] and uniforms float32 [n] -> tokens int32 [n].  clip: as for
+    Engine.sequence (char_rnn.CharRNN.CLIP reproduces darknet's comparison with the double .0001)"""
+    probs = _f32(probs); uniforms = _f32(uniforms).reshape(-1); n, ln = probs.shape
+    if uniforms.size != n:
+        raise YoloError("op_sample: %d rows need %d uniforms, got %d" % (n, n, uniforms.size))
+    out = np.full(n, -1, dtype=np.int32)
+    _op_check(load_library().yolo_op_sample(probs.ctypes.data, n, ln, uniforms.ctypes.data, float(clip), out.ctypes.data, device), "yolo_op_sample")
+    return out
 
 
 def tree_read(path):
