@@ -76,6 +76,57 @@ def compared_layers(cfg):
     return [i for i, s in enumerate(IO.parse_cfg(cfg)[1:]) if s["type"] != "cost"]
 
 
+# ---- rows wider than one block of granules (shared with test_gpu_stream_tiles.py): the input kernels take one 8-element granule per thread and
+#      256 threads per block, the sampler writes the next row 256 granules per pass: element BLOCK is the first of a second block / pass ----
+BLOCK = 2048
+WIDE_N = (2085, 8192)          # 261 granules, the last one ragged; the sampler's limit
+LAST_U = np.float32(0.99999994)          # the largest float below 1
+# uniforms [10 sampled steps][3 streams]: tails (with near-uniform rows u > 2048 / 2085 = 0.9823 lands past BLOCK at the narrower width too) next to
+# heads, and LAST_U for the walk to the end of the row
+WIDE_U = np.array([[.30, .995, .10, LAST_U, .15, .99, .20, .999, .05, .70],
+                   [LAST_U, .12, .997, .40, LAST_U, .08, .993, .18, .60, .02],
+                   [.07, LAST_U, .19, .996, .03, LAST_U, .14, .55, .998, .11]], dtype=np.float32).T.copy()
+
+
+def wide_cfg(n):
+    return "[net]\ninputs=%d\nyolo_input=vector\n\n[lstm]\noutput=16\n\n[connected]\noutput=%d\nactivation=linear\n\n[softmax]\n" % (n, n)
+
+
+def wide_seed(n):
+    """the one forced token of each of the 3 streams: in the first block, just past it, the row's last element"""
+    return np.array([[5, BLOCK + 2, n - 1]], dtype=np.int32)
+
+
+def free_run(cfg, flat, seed, uniforms, store=None):
+    """the restatement free-running, as yolo_sequence runs: seed [forced][streams] fed, then the tokens sample_np draws with uniforms [sampled][streams]
+    -> tokens [sampled][streams]"""
+    n = IO.vector_inputs(IO.parse_cfg(cfg))
+    toks = np.zeros(uniforms.shape, dtype=np.int32)
+    for b in range(seed.shape[1]):
+        net = CharNet(cfg, flat, store)
+        for t in seed[:, b]:
+            probs = net.step(one_hot(t, n))[-1]
+        for k in range(uniforms.shape[0]):
+            toks[k, b] = sample_np(probs, uniforms[k, b])
+            if k + 1 < uniforms.shape[0]:
+                probs = net.step(one_hot(toks[k, b], n))[-1]
+    return toks
+
+
+def wide_coverage(toks, uniforms, n):
+    """what a free run over wide rows must have drawn for its self-consistency to say anything about the granules past BLOCK -> the list of what is
+    missing.  Only a token that is fed again (every one but the last of a stream) counts."""
+    fed = toks[:-1]
+    missing = []
+    if not (fed >= BLOCK).any() or not (fed < BLOCK).any():
+        missing.append("fed tokens on both sides of element %d" % BLOCK)
+    if not ((fed == n - 1) & (uniforms[:-1] == LAST_U)).any():
+        missing.append("a walk to the row's end (token %d under u = %.8f) that is fed again" % (n - 1, LAST_U))
+    if not ((fed[:-1] >= BLOCK) & (fed[1:] < BLOCK)).any():
+        missing.append("a fed token past element %d followed by a fed one below it (a stale granule would show)" % BLOCK)
+    return missing
+
+
 # ---- the tests ----
 @pytest.fixture(scope="module")
 def fx():
@@ -206,6 +257,25 @@ def test_sampler_edges():
     assert sample_np(np.array([5e-5, 0.9999, 5e-5], dtype=np.float32), 0.0) == 0
     assert sample_np(np.array([5e-5, 0.9999, 5e-5], dtype=np.float32), 0.5) == 1
     assert sample_np(np.full(7, 1e-5, dtype=np.float32), 0.3) == 6
+
+
+@pytest.mark.parametrize("n", WIDE_N)
+def test_wide_row_inputs_reach_both_sides_of_the_second_block(n):
+    """the inputs test_gpu_stream_tiles.py free-runs over rows wider than one block of granules, under the restatement alone (float64, and rounded
+    where a 16-bit device rounds): the tokens it draws and feeds again lie on both sides of element BLOCK, one walk ends at the row's last element,
+    one token past BLOCK is followed by one below it.  The device test asserts the same of the tokens the device returned."""
+    cfg = wide_cfg(n); secs = IO.parse_cfg(cfg)
+    for dt in (hip.BF16, hip.FP16, hip.FP32):
+        rc, msg = hip.plan_check(cfg, dtype=dt)
+        assert rc == 0, msg
+    flat = IO.synth_weights(secs, seed=n)
+    assert WIDE_U.shape == (10, 3) and (WIDE_U == LAST_U).sum() == 5 and LAST_U < 1 and np.nextafter(LAST_U, np.float32(2)) == 1
+    for store in (None, RH.bf16, RH.fp16):
+        toks = free_run(cfg, flat, wide_seed(n), WIDE_U, store)
+        print("N = %d %s: %s" % (n, store.__name__ if store else "float64", toks.T.tolist()))
+        assert wide_coverage(toks, WIDE_U, n) == []
+    none = np.full((10, 3), 7, dtype=np.int32)
+    assert len(wide_coverage(none, WIDE_U, n)) == 3
 
 
 def test_darknet_uniforms_are_the_fixtures(fx):
