@@ -39,7 +39,7 @@ int network_height(network *net);
 void set_batch_network(network *net, int b);                             /* DN/network.c:339 */
 void reset_network_state(network *net, int b);                           /* DN/network.c:69: the recurrent layers' state of batch index (stream) b back to zero */
 void reset_rnn(network *net);                                            /* DN/network.c:85: reset_network_state(net, 0) */
-float *network_predict(network *net, float *input);                      /* DN/network.c:497; batch x planar [3][h][w] at network size; a char-rnn cfg ([net] inputs=N, no image size): batch x N values, one time step */
+float *network_predict(network *net, float *input);                      /* DN/network.c:497; batch x planar [c][h][w] at network size, c the cfg's channels= (load_network declares a cfg whose channels != 3 itself: [net] yolo_input=planes); a char-rnn cfg ([net] inputs=N, no image size): batch x N values, one time step */
 float *network_predict_image(network *net, image im);                    /* DN/network.c:579-586 (letterbox + predict) */
 detection *make_network_boxes(network *net, float thresh, int *num);     /* DN/network.c:526 */
 detection *get_network_boxes(network *net, int w, int h, float thresh, float hier, int *map, int relative, int *num);   /* DN/network.c:562-567 */

@@ -180,7 +180,18 @@ double yolo_conv_flops(const yolo_ctx *ctx); /* 2*k*k*Cin*Cout*Ho*Wo summed (DN/
 double yolo_conv_bytes(const yolo_ctx *ctx, int n); /* algorithmic HBM bytes of the conv stack for n images */
 
 /* ---- hot path ------------------------------------------------------------------------------- */
-/* images: [n,H,W,3] ([net] height x width) in `fmt`, at `loc`; each value is multiplied by `scale` on the way in
+/* The image's channel count.  A cfg without a [net] yolo_input key reads RGB images: channels=3, anything else is refused.  With
+ * [net] yolo_input=planes the network reads images of C = [net] channels planes, 1 <= C <= 1024 (grey, thermal, RGB-D, multispectral,
+ * darknet's 19 x 19 x 1 go board); darknet ignores the key, so the same cfg loads there.  yolo_input_size reports C.  Wherever the
+ * entry points below say 3, read C: yolo_forward takes [n,H,W,C] (YOLO_IMG_F32_CHW: [n,C,H,W]), yolo_forward_letterbox_chw [C,h,w],
+ * yolo_forward_image_u8 and the yolo_*_images_u8 family packed [h,w,C] bytes, C bytes per pixel and w * C per row.  The channels
+ * C .. roundup(C, 8) - 1 of the staged input are zero (the letterbox's 0.5 fill and [net] yolo_input_mul / yolo_input_add belong to
+ * the C real channels).  With C = 3 the key changes nothing.  With C != 3: configurations bf16, fp16 and fp32 (fp8 and split-fp16
+ * are refused when the cfg is planned, by name); layer 0 runs the kernels every inner layer runs, no fused first-stage kernel; and,
+ * YOLO_ERR_UNSUPPORTED before any launch, naming the entry point and C: YOLO_FIT_CV2 / YOLO_FIT_CV2_BGR (their meaning is an RGB /
+ * BGR image) and yolo_detect_tiled_u8.
+ *
+ * images: [n,H,W,3] ([net] height x width) in `fmt`, at `loc`; each value is multiplied by `scale` on the way in
  * (1/255 for the `inputs / 255` of V3/yolo_v3.py:215, 1 for pre-normalised input).  Runs the conv stack
  * and the head decode; the decoded tensor [n, rows, attrs] (V3/yolo_v3.py:266) stays resident and, when
  * detections_out != NULL, is also copied there (fp32, at out_loc).  Asynchronous on the context stream
@@ -362,6 +373,11 @@ int yolo_op_sample(const float *probs, int n, int len, const float *uniforms, fl
  * forward -- launched, no folded shortcut, buffer not reused by a later layer -- is served, anything else is
  * YOLO_ERR_STATE).  dims_out receives H,W,C.  Head (yolo/region) layers return the raw conv tensor. */
 int yolo_layer_output(yolo_ctx *ctx, int index, int n, float *out, size_t out_floats, int *dims_out);
+/* The staged network input of images 0..n-1 of the last forward as fp32 [n,H,W,S] to host, EVERY stored channel of a pixel: S = 8 for
+ * an RGB network (3 real + 5 zero), roundup(C, 8) for C planes.  dims_out receives H,W,S; out == NULL: the dims only.
+ * YOLO_ERR_UNSUPPORTED: a vector-input network, a split-fp16 image stored as pairs.  YOLO_ERR_STATE: the last forward's uint8 batch was
+ * read in place by the fused first layers (nothing was staged). */
+int yolo_staged_input(yolo_ctx *ctx, int n, float *out, size_t out_floats, int *dims_out);
 /* Times `iters` forwards of batch n on the context stream with HIP events:
  * total_ms = wall per forward; conv_ms = the conv launches' share of it (all layers minus all-but-conv, bulk-timed)
  * (events around every conv launch, separate pass).  Either may be NULL.

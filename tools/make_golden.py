@@ -34,6 +34,10 @@ Runs only in the build container (it reads /root/reference and oracle/_ref); the
                     recurrent networks ([rnn], [gru], [lstm] behind a conv stack, a classifier; two [crnn] layers in front of a [yolo] head):
                     ONE live network of the compiled reference over 5 frames, every layer's output after each frame (mini_crnn: the boxes too), and
                     drift16_*: the stand-off of the 16-bit-rounded host restatement (tests/test_recurrent_host.py) per frame and layer
+  mini_planes_grey.npz / mini_planes_rgbd.npz / mini_planes_nine.npz / mini_planes_17.npz / planes_fit_cases.npz
+                    image networks of 1, 4, 9 and 17 planes (darknet's own cfg text, no yolo_input key), each opening with the shape of one fused first-stage
+                    kernel of the RGB path: one image, every layer's output (the grey one: get_network_boxes too); letterbox_image and resize_min +
+                    crop_image of images of 1, 4 and 9 planes; fixed member dates
   mini_lrn.npz / lrn_crop_cases.npz
                     [crop] and [normalization]: a classifier that opens with a [crop] and has two LRN layers (three images, every layer), eleven
                     stand-alone [normalization] shapes behind a 1x1 conv, four [crop] networks, and six uint8 images through the reference's
@@ -1416,6 +1420,88 @@ def gen_lrn_crop(seed=109):          # (a seed at which channel 2 of mini_lrn's 
     print("lrn_crop_cases", len(data), "arrays", os.path.getsize(path), "bytes")
 
 
+def _planes_net(width, height, channels, extra=""):
+    return "[net]\nbatch=1\nwidth=%d\nheight=%d\nchannels=%d\n%s\n" % (width, height, channels, extra)
+
+
+# Image networks whose channel count is not three, as darknet reads them: the cfgs carry NO yolo_input key (the library's loaders add it:
+# darknet_io.with_planes_input, the veneer's load_network).  Each opens with the shape of one fused first-stage kernel of the 3-channel path, which
+# must not be chosen for them: (name, cfg, (h, w, c), seed)
+PLANES_NETS = [
+    # the fused stem's shape: 3x3/1 -> 32, 3x3/2 -> 64, batch-normalised, leaky; a 1x1 head of 3 anchors x (5 + 2 classes) and [yolo]
+    ("mini_planes_grey", _planes_net(32, 32, 1) + _conv(32, 3) + _conv(64, 3, 2) + _conv(21, 1, bn=False, act="linear") +
+     "[yolo]\nmask=0,1,2\nanchors=4,5, 9,8, 14,17\nclasses=2\nnum=3\n", (32, 32, 1), 141),
+    # the space-to-depth 7x7 / stride 2 / pad 3 first conv (even extents), a max-pool, a conv to ten classes, [avgpool], [softmax]
+    ("mini_planes_rgbd", _planes_net(30, 22, 4) + "[convolutional]\nbatch_normalize=1\nfilters=16\nsize=7\nstride=2\npad=1\nactivation=leaky\n\n" +
+     "[maxpool]\nsize=2\nstride=2\n\n" + _conv(10, 3, bn=False, act="linear") + "[avgpool]\n\n[softmax]\ngroups=1\n", (22, 30, 4), 143),
+    # a first-layer [crop] of nine planes (two granules, the second with one real channel), a 5x5 conv, a stride-2 deconv, a linear 1x1: a map
+    ("mini_planes_nine", _planes_net(22, 15, 9, "yolo_output=map\n") + _crop(13, 20) + _conv(12, 5) + _deconv(8, 2, 2, 0) + _conv(5, 1, bn=False, act="linear"), (15, 22, 9), 145),
+    # seventeen planes (three granules) into a 1x1 first conv, then a linear 3x3: a map
+    ("mini_planes_17", _planes_net(11, 9, 17, "yolo_output=map\n") + _conv(12, 1) + _conv(8, 3, bn=False, act="linear"), (9, 11, 17), 147),
+]
+# (planes, image h, w) of the fit cases, network 16 x 16: one image wider and one taller than the network per plane count, odd sizes
+PLANES_FIT_NET = (16, 16)
+PLANES_FIT_CASES = [(1, 21, 37), (1, 35, 19), (4, 13, 29), (4, 27, 15), (9, 17, 23), (9, 31, 11)]
+
+
+def gen_planes(thresh=0.15):
+    """The networks of PLANES_NETS through the compiled reference: cfg text (darknet's own, without yolo_input), the seeded weight stream (filters
+    bf16-exact), one uint8 image [h, w, c] and every layer's output of network_predict on image / 255, `layer_%02d` [1, h, w, c]; mini_planes_grey also the
+    reference's get_network_boxes (boxes_raw / obj_raw / prob_raw at `thresh`, network-sized image: no letterbox correction).  planes_fit_cases.npz: the
+    reference's letterbox_image and resize_min + crop_image (the classifier's validation fit) of seeded images of 1, 4 and 9 planes."""
+    import ctypes as C
+    from oracle import darknet_ref as D
+    from yolo_tensorflow_amd import darknet_io as IO
+    for name, cfg, (h, w, ch), seed in PLANES_NETS:
+        secs = IO.parse_cfg(cfg); shapes = IO.layer_shapes(secs)
+        flat = IO.bf16_exact_filters(secs, IO.synth_weights(secs, seed=seed, obj_bias=0.5))
+        img = np.random.default_rng(seed + 1).integers(0, 256, (h, w, ch), dtype=np.uint8)
+        net = D.RefNet(cfg, flat, 0, 2)
+        assert (net.h, net.w) == (h, w)
+        net.predict(img.astype(np.float32) / np.float32(255.0))
+        data = {"cfg": np.array(cfg), "weights": flat, "image_u8": img}
+        for i in range(net.n):
+            o = np.asarray(net.layer_output_nhwc(i), dtype=np.float32)
+            data["layer_%02d" % i] = o.reshape((1,) + tuple(shapes[i][1:4])) if shapes[i][0] not in ("yolo",) else o
+            assert np.isfinite(o).all()
+        if name == "mini_planes_grey":
+            bb, obj, pr = net.boxes(thresh, None, 2)
+            assert len(bb) >= 8, "too few boxes above the threshold to pin anything: %d" % len(bb)
+            data["boxes_raw"], data["obj_raw"], data["prob_raw"], data["thresh"] = bb, obj, pr, np.float32(thresh)
+        net.close()
+        path = os.path.join(OUT, name + ".npz")
+        save_npz_reproducibly(path, data)
+        print(name, "layers", len(shapes), [tuple(data["layer_%02d" % i].shape[1:]) for i in range(len(shapes))], "boxes", len(data.get("boxes_raw", [])), os.path.getsize(path), "bytes")
+
+    class IMAGE(C.Structure):
+        _fields_ = [("w", C.c_int), ("h", C.c_int), ("c", C.c_int), ("data", C.POINTER(C.c_float))]
+    lib = D.lib()
+    lib.resize_min.argtypes = [IMAGE, C.c_int]; lib.resize_min.restype = IMAGE
+    lib.crop_image.argtypes = [IMAGE, C.c_int, C.c_int, C.c_int, C.c_int]; lib.crop_image.restype = IMAGE
+    lib.letterbox_image.argtypes = [IMAGE, C.c_int, C.c_int]; lib.letterbox_image.restype = IMAGE
+    lib.free_image.argtypes = [IMAGE]
+    nh, nw = PLANES_FIT_NET
+    rng = np.random.default_rng(149)
+    data = {"net_hw": np.array([nh, nw], np.int32), "cases": np.array(PLANES_FIT_CASES, np.int32)}
+    for ch, h, w in PLANES_FIT_CASES:
+        img = rng.integers(0, 256, (h, w, ch), dtype=np.uint8)
+        chw = np.ascontiguousarray((img.astype(np.float64) / 255.).astype(np.float32).transpose(2, 0, 1))          # darknet's loader: (float)p / 255.
+        im = IMAGE(w, h, ch, chw.ctypes.data_as(C.POINTER(C.c_float)))
+        boxed = lib.letterbox_image(im, nw, nh)
+        resized = lib.resize_min(im, nw)
+        crop = lib.crop_image(resized, int((resized.w - nw) / 2), int((resized.h - nh) / 2), nw, nh)
+        tag = "fit_%d_%dx%d" % (ch, h, w)
+        data[tag + "_image_u8"] = img
+        data[tag + "_letterbox"] = np.ctypeslib.as_array(boxed.data, shape=(ch, nh, nw)).copy().transpose(1, 2, 0)
+        data[tag + "_center_crop"] = np.ctypeslib.as_array(crop.data, shape=(ch, nh, nw)).copy().transpose(1, 2, 0)
+        if C.addressof(resized.data.contents) != chw.ctypes.data:
+            lib.free_image(resized)
+        lib.free_image(crop); lib.free_image(boxed)
+    path = os.path.join(OUT, "planes_fit_cases.npz")
+    save_npz_reproducibly(path, data)
+    print("planes_fit_cases", len(data), "arrays", os.path.getsize(path), "bytes")
+
+
 def gen_rect():
     gen_mini_rect("mini_v3_rect", MINI_V3, 4, 64, 96, letterbox=True)
     gen_mini_rect("mini_v2_rect", MINI_V2, 5, 96, 64)
@@ -1448,6 +1534,8 @@ if __name__ == "__main__":
         gen_lrn_crop(); sys.exit(0)
     if sys.argv[1:] == ["char_rnn"]:
         gen_mini_char_rnn(); sys.exit(0)
+    if sys.argv[1:] == ["planes"]:
+        gen_planes(); sys.exit(0)
     stub_modules()
     gen_nms_v3()
     gen_v2_post()
@@ -1465,6 +1553,7 @@ if __name__ == "__main__":
     gen_recurrent()
     gen_lrn_crop()
     gen_mini_char_rnn()
+    gen_planes()
     gen_bn_real()
     gen_known_answers()
     gen_darknet_py_symbols()

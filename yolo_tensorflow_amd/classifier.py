@@ -18,6 +18,7 @@ class Classifier:
         returns the conditional probabilities network_predict gives, "absolute" the products along the path to the root
         (hierarchy_predictions), "leaves" those with every inner node zeroed -- what darknet's classifier apps rank."""
         text = cfg_or_name if "[net]" in cfg_or_name or "[network]" in cfg_or_name else IO.cfg_text(cfg_or_name)
+        text = IO.with_planes_input(text)          # darknet's own grey / multi-plane cfgs ([net] channels != 3) load unchanged
         self.engine = hip.Engine(text, max_batch=max_batch, dtype=dtype, semantics=hip.SEM_DARKNET, device=device)
         if self.engine.rows != 0:
             self.engine.close()
@@ -39,7 +40,7 @@ class Classifier:
         return self.names[k] if self.names is not None and 0 <= k < len(self.names) else int(k)
 
     def classify_from_images(self, images, top=5):
-        """images: a list of RGB uint8 [h, w, 3] arrays of any sizes -> per image [(name_or_index, prob), ...], `top` entries,
+        """images: a list of uint8 [h, w, C] arrays of any sizes (RGB; a network of C planes: [h, w, C], one plane also [h, w]) -> per image [(name_or_index, prob), ...], `top` entries,
         probability descending."""
         out = []
         for lo in range(0, len(images), self.max_batch):

@@ -6,6 +6,7 @@
 #include "../../include/darknet_hip.h"
 #include "../../include/yolo_hip.h"
 
+#include <algorithm>
 #include <cctype>
 #include <cmath>
 #include <cstdio>
@@ -16,7 +17,7 @@
 
 struct network {
     yolo_ctx *ctx = nullptr;
-    int w = 0, h = 0, rows = 0, attrs = 0, batch = 1;
+    int w = 0, h = 0, c = 3, rows = 0, attrs = 0, batch = 1;
     std::string cfg_text, weights_path;
     std::vector<float> out;              // last layer's output in darknet layout (what network_predict returns)
     std::vector<float> rec;              // get_network_boxes staging: [count][5 + classes]
@@ -46,10 +47,11 @@ std::string trim(const std::string &s)
 }
 
 // darknet's char-rnn cfgs name `inputs=` and no image size in [net] (examples/rnn.c over rnn.cfg): the library wants such a network declared
-// ([net] yolo_input=vector); the key is added behind the [net] line of a cfg that lacks it
-void declare_vector_input(std::string &cfg)
+// ([net] yolo_input=vector); the key is added behind the [net] line of a cfg that lacks it.  Likewise an image network whose channels= is not 3 (grey,
+// RGB-D, the go board): [net] yolo_input=planes
+void declare_input_kind(std::string &cfg)
 {
-    bool in_net = false, inputs = false, sized = false, declared = false; size_t net_end = std::string::npos;
+    bool in_net = false, inputs = false, declared = false; int height = 0, width = 0, channels = 3; size_t net_end = std::string::npos;
     for (size_t pos = 0; pos < cfg.size();) {
         size_t e = cfg.find('\n', pos); if (e == std::string::npos) e = cfg.size();
         const std::string line = trim(cfg.substr(pos, e - pos));
@@ -57,11 +59,16 @@ void declare_vector_input(std::string &cfg)
         else if (in_net && !line.empty() && line[0] != '#' && line[0] != ';') {
             const size_t eq = line.find('=');
             const std::string k = trim(line.substr(0, eq)), v = eq == std::string::npos ? "" : trim(line.substr(eq + 1));
-            inputs |= k == "inputs"; declared |= k == "yolo_input"; sized |= (k == "height" || k == "width") && atoi(v.c_str()) > 0;
+            inputs |= k == "inputs"; declared |= k == "yolo_input";
+            if (k == "height") height = atoi(v.c_str());
+            if (k == "width") width = atoi(v.c_str());
+            if (k == "channels") channels = atoi(v.c_str());
         }
         pos = e + 1;
     }
-    if (inputs && !sized && !declared && net_end != std::string::npos) cfg.insert(net_end, "\nyolo_input=vector");
+    if (declared || net_end == std::string::npos) return;
+    if (inputs && height <= 0 && width <= 0) cfg.insert(net_end, "\nyolo_input=vector");
+    else if (height > 0 && width > 0 && channels != 3) cfg.insert(net_end, "\nyolo_input=planes");
 }
 
 bool open_ctx(network *net)
@@ -77,7 +84,7 @@ bool open_ctx(network *net)
     if (!net->weights_path.empty() && yolo_load_darknet_weights(net->ctx, net->weights_path.c_str(), 0) != YOLO_OK) {
         fprintf(stderr, "darknet_hip: %s\n", yolo_last_error(net->ctx)); yolo_destroy(net->ctx); net->ctx = nullptr; return false;
     }
-    yolo_input_size(net->ctx, &net->h, &net->w, nullptr);
+    yolo_input_size(net->ctx, &net->h, &net->w, &net->c);
     net->rows = yolo_num_rows(net->ctx); net->attrs = yolo_num_attrs(net->ctx);
     net->out.assign(yolo_last_layer_size(net->ctx) * (size_t)net->batch, 0.f);      // net->output: batch * outputs floats
     net->have = false;
@@ -101,7 +108,7 @@ network *load_network(char *cfg, char *weights, int clear)
     (void)clear;                                   // `*net->seen = 0`: training state, nothing to clear here
     network *net = new network();
     if (!read_text(cfg, net->cfg_text)) { fprintf(stderr, "darknet_hip: cannot open cfg '%s'\n", cfg ? cfg : "(null)"); delete net; return nullptr; }
-    declare_vector_input(net->cfg_text);
+    declare_input_kind(net->cfg_text);
     if (weights && weights[0]) net->weights_path = weights;
     if (!open_ctx(net)) { delete net; return nullptr; }
     return net;
@@ -127,7 +134,7 @@ void set_batch_network(network *net, int b)
     yolo_destroy(prev);
 }
 
-// `input`: batch x planar [3][h][w] at network size.  Returns net->output: the last layer's output of every image of the batch
+// `input`: batch x planar [c][h][w] at network size (c: the cfg's channels=).  Returns net->output: the last layer's output of every image of the batch
 // (a classifier cfg: the probabilities of its [softmax] layer, what darknet.py's classify() reads),
 // image after image (batch * outputs floats, DN/network.c:497-508), see include/darknet_hip.h.
 float *network_predict(network *net, float *input)
@@ -145,7 +152,8 @@ float *network_predict(network *net, float *input)
 
 float *network_predict_image(network *net, image im)
 {
-    if (!net || !im.data || im.c != 3) return nullptr;
+    if (!net || !im.data) return nullptr;
+    if (im.c != net->c) { net->have = false; fprintf(stderr, "darknet_hip: network_predict_image: an image of %d channels for a network of %d\n", im.c, net->c); return nullptr; }
     if (yolo_forward_letterbox_chw(net->ctx, im.data, im.w, im.h, YOLO_HOST, nullptr, YOLO_HOST) != YOLO_OK) {
         net->have = false; fprintf(stderr, "darknet_hip: %s\n", yolo_last_error(net->ctx)); return nullptr;
     }
@@ -233,8 +241,16 @@ void free_image(image m) { free(m.data); }
 image letterbox_image(image im, int w, int h)                                        /* DN/image.c:960-981, on the device */
 {
     image out = make_image(w, h, im.c);
-    if (!im.data || im.c != 3 || yolo_op_letterbox(im.data, im.w, im.h, w, h, 1, out.data, g_device) != YOLO_OK)
-        fprintf(stderr, "darknet_hip: letterbox_image: %s\n", im.c != 3 ? "3-channel images only" : yolo_last_error(NULL));
+    if (!im.data || im.c < 1) { fprintf(stderr, "darknet_hip: letterbox_image: no image\n"); return out; }
+    if (im.c == 3) { if (yolo_op_letterbox(im.data, im.w, im.h, w, h, 1, out.data, g_device) != YOLO_OK) fprintf(stderr, "darknet_hip: letterbox_image: %s\n", yolo_last_error(NULL)); return out; }
+    // any other plane count: the planes are independent, so they go through the three-plane operator three at a time (the last group padded with its own last plane)
+    const size_t ip = (size_t)im.w * im.h, op = (size_t)w * h;
+    std::vector<float> src(3 * ip), dst(3 * op);
+    for (int k0 = 0; k0 < im.c; k0 += 3) {
+        for (int k = 0; k < 3; ++k) memcpy(&src[k * ip], im.data + (size_t)std::min(k0 + k, im.c - 1) * ip, ip * sizeof(float));
+        if (yolo_op_letterbox(src.data(), im.w, im.h, w, h, 1, dst.data(), g_device) != YOLO_OK) { fprintf(stderr, "darknet_hip: letterbox_image: %s\n", yolo_last_error(NULL)); return out; }
+        for (int k = 0; k < 3 && k0 + k < im.c; ++k) memcpy(out.data + (size_t)(k0 + k) * op, &dst[k * op], op * sizeof(float));
+    }
     return out;
 }
 

@@ -16,45 +16,66 @@
 // do `c` channels fit both pixel strides as whole 8-channel granules?
 static inline bool granules_ok(int c, int stride_a, int stride_b) { const int c8 = (c + 7) / 8; return c >= 1 && stride_a >= c8 * 8 && stride_b >= c8 * 8; }
 
-// ---- row P: uint8/float image at network size -> 8-channel (3 real + 5 zero) activation ---------
-template <typename T>
-__global__ void k_preprocess(const void *img, int fmt, size_t npix, size_t hw, float scale, T *out, int out_stride, float post_mul, float post_add)
+// ---- The channel count of the staging kernels below.  NCH = 3: an RGB image, one lane per output pixel, its one granule 3 real + 5 zero channels.
+//      NCH = 0: `nch` planes ([net] yolo_input=planes), one lane per output pixel x 8-channel granule; the granule is the SLOW index of the
+//      folded grid, so the 64 lanes of a wave read 64 neighbouring pixels of one plane (a planar source: one coalesced run per channel; a packed
+//      one: bytes `nch` apart) and each stores its granule as one vector.  The channels nch .. of the last granule are stored as zeros. ----
+template <int NCH> struct Planes {
+    int c0, nc;          // the lane's channels [c0, c0 + nc)
+    __device__ __forceinline__ Planes(int g, int nch) : c0(NCH ? 0 : g * 8), nc(NCH ? NCH : min(8, nch - g * 8)) {}
+};
+
+// ---- row P: uint8/float image at network size -> whole granules of activation (RGB: 3 real + 5 zero channels) ---------
+template <typename T, int NCH>
+__global__ void k_preprocess(const void *img, int fmt, size_t npix, size_t hw, float scale, T *out, int out_stride, float post_mul, float post_add, int nch)
 {
-    size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= npix) return;
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t g = NCH ? 0 : idx / npix, p = NCH ? idx : idx - g * npix;
+    if (NCH ? p >= npix : g * 8 >= (size_t)nch) return;
+    const Planes<NCH> pl((int)g, nch);
+    const size_t N = NCH ? NCH : nch;
     float v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (fmt == 0) {
-        const uint8_t *s = (const uint8_t *)img + p * 3;
-        v[0] = (float)s[0] * scale; v[1] = (float)s[1] * scale; v[2] = (float)s[2] * scale;
+        const uint8_t *s = (const uint8_t *)img + p * N + pl.c0;
+#pragma unroll
+        for (int k = 0; k < (NCH ? NCH : 8); ++k) if (k < pl.nc) v[k] = (float)s[k] * scale;
     } else if (fmt == 1) {
-        const float *s = (const float *)img + p * 3;
-        v[0] = s[0] * scale; v[1] = s[1] * scale; v[2] = s[2] * scale;
-    } else {                                   // planar float [n][3][hw]: darknet's `image` layout (DN/image.c get_pixel)
+        const float *s = (const float *)img + p * N + pl.c0;
+#pragma unroll
+        for (int k = 0; k < (NCH ? NCH : 8); ++k) if (k < pl.nc) v[k] = s[k] * scale;
+    } else {                                   // planar float [n][N][hw]: darknet's `image` layout (DN/image.c get_pixel)
         const size_t b = p / hw, q = p - b * hw;
-        const float *s = (const float *)img + b * 3 * hw + q;
-        v[0] = s[0] * scale; v[1] = s[hw] * scale; v[2] = s[2 * hw] * scale;
+        const float *s = (const float *)img + (b * N + pl.c0) * hw + q;
+#pragma unroll
+        for (int k = 0; k < (NCH ? NCH : 8); ++k) if (k < pl.nc) v[k] = s[k * hw] * scale;
     }
-    // YOLOv1's input normalisation `(x / 255) * 2 - 1` (V1/YOLO_V1_Inference.py:67-71): an affine map of the three real channels
-    if (post_mul != 1.0f || post_add != 0.0f) { v[0] = v[0] * post_mul + post_add; v[1] = v[1] * post_mul + post_add; v[2] = v[2] * post_mul + post_add; }
-    Elt<T>::store8(out + p * out_stride, v);
+    // YOLOv1's input normalisation `(x / 255) * 2 - 1` (V1/YOLO_V1_Inference.py:67-71): an affine map of the real channels
+    if (post_mul != 1.0f || post_add != 0.0f) {
+#pragma unroll
+        for (int k = 0; k < (NCH ? NCH : 8); ++k) if (k < pl.nc) v[k] = v[k] * post_mul + post_add;
+    }
+    Elt<T>::store8(out + p * out_stride + pl.c0, v);
 }
 
 hipError_t launch_preprocess(const void *img, int fmt, int n, int hw, float scale, void *out, int out_dt,
-                             int out_stride, hipStream_t s, float post_mul, float post_add)
+                             int out_stride, hipStream_t s, float post_mul, float post_add, int nch)
 {
     size_t npix = (size_t)n * hw;
-    WITH_DT(out_dt, hipLaunchKernelGGL(k_preprocess<T>, grid_for(npix), dim3(256), 0, s, img, fmt, npix, (size_t)hw, scale, (T *)out, out_stride, post_mul, post_add));
+    if (nch < 1 || out_stride < (nch + 7) / 8 * 8) return hipErrorInvalidValue;
+    if (nch == 3) WITH_DT(out_dt, hipLaunchKernelGGL((k_preprocess<T, 3>), grid_for(npix), dim3(256), 0, s, img, fmt, npix, (size_t)hw, scale, (T *)out, out_stride, post_mul, post_add, 3));
+    else WITH_DT(out_dt, hipLaunchKernelGGL((k_preprocess<T, 0>), grid_for(npix * ((nch + 7) / 8)), dim3(256), 0, s, img, fmt, npix, (size_t)hw, scale, (T *)out, out_stride, post_mul, post_add, nch));
     return hipGetLastError();
 }
 
 // ---- per-pixel arithmetic of the image fits, shared by the single-image kernels and the batched k_fit_images.  `at(y, x, c)`
 //      returns what the fit reads at a source pixel: the byte as a float for the stretch and cv2 forms, the 0..1 value for the letterbox
 //      and the centre crop (a planar float image, or a byte through fit_unit_value).  Restated operation for operation from the reference; this file is
-//      compiled with -ffp-contract=off, so every caller rounds the same. ----
+//      compiled with -ffp-contract=off, so every caller rounds the same.  Coordinates and weights are computed once; then the channels
+//      [c0, c0 + nc) are interpolated into v[0 .. nc): NC = 3 is the RGB form (c0 = 0, nc = 3 at every call), NC = 8 one granule of an N-plane image. ----
 
 // legacy TF bilinear (no half-pixel offset): src = dst * (in/out); value/255 first (D2T _input_process)
-template <class At>
-__device__ __forceinline__ void px_stretch(const At &at, int h, int w, int oh, int ow, int oy, int ox, float post_scale, float post_add, float *v)
+template <int NC, class At>
+__device__ __forceinline__ void px_stretch(const At &at, int h, int w, int oh, int ow, int oy, int ox, float post_scale, float post_add, int c0, int nc, float *v)
 {
     const float hs = (float)h / (float)oh, ws = (float)w / (float)ow;
     float fy = (float)oy * hs, fx = (float)ox * ws;
@@ -62,16 +83,18 @@ __device__ __forceinline__ void px_stretch(const At &at, int h, int w, int oh, i
     int y1 = min(y0 + 1, h - 1), x1 = min(x0 + 1, w - 1);
     float yl = fy - (float)y0, xl = fx - (float)x0;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
+    for (int k = 0; k < NC; ++k) {
+        if (NC != 3 && k >= nc) break;
+        const int c = c0 + k;
         float tl = at(y0, x0, c) / 255.0f;
         float tr = at(y0, x1, c) / 255.0f;
         float bl = at(y1, x0, c) / 255.0f;
         float br = at(y1, x1, c) / 255.0f;
         float top = tl + (tr - tl) * xl;
         float bot = bl + (br - bl) * xl;
-        v[c] = top + (bot - top) * yl;
-        if (post_scale != 1.0f) v[c] *= post_scale;
-        if (post_add != 0.0f) v[c] += post_add;
+        v[k] = top + (bot - top) * yl;
+        if (post_scale != 1.0f) v[k] *= post_scale;
+        if (post_add != 0.0f) v[k] += post_add;
     }
 }
 
@@ -79,18 +102,20 @@ __device__ __forceinline__ void px_stretch(const At &at, int h, int w, int oh, i
 // pass then vertical pass, scales (in-1)/(out-1), last column / row copied.  Operation order of the two passes is kept:
 // part = (1-dx)*a + dx*b, then (1-dy)*p0 (+ dy*p1).  Where the size does not change the scales are 1, dx = dy = 0, and the value is the
 // source pixel itself, bit for bit: resize_min's `no resize` branch (DN/image.c:1008) needs no case of its own.
-template <class At>
-__device__ __forceinline__ void px_resize(const At &at, int iw, int ih, int new_w, int new_h, int r, int c, float *v)
+template <int NC, class At>
+__device__ __forceinline__ void px_resize(const At &at, int iw, int ih, int new_w, int new_h, int r, int c, int c0, int nc, float *v)
 {
     const float w_scale = (float)(iw - 1) / (float)(new_w - 1), h_scale = (float)(ih - 1) / (float)(new_h - 1);
     const float sy = (float)r * h_scale; const int iy = (int)sy; const float dy = sy - (float)iy;
     const bool last_c = c == new_w - 1 || iw == 1, last_r = r == new_h - 1 || ih == 1;
     const float sx = (float)c * w_scale; const int ix = (int)sx; const float dx = sx - (float)ix;
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
+    for (int k = 0; k < NC; ++k) {
+        if (NC != 3 && k >= nc) break;
+        const int ch = c0 + k;
         auto part = [&](int row) {
-            if (last_c) return at(row, iw - 1, k);
-            return (1 - dx) * at(row, ix, k) + dx * at(row, ix + 1, k);
+            if (last_c) return at(row, iw - 1, ch);
+            return (1 - dx) * at(row, ix, ch) + dx * at(row, ix + 1, ch);
         };
         float val = (1 - dy) * part(iy);
         if (!last_r) val = val + dy * part(iy + 1);
@@ -99,26 +124,27 @@ __device__ __forceinline__ void px_resize(const At &at, int iw, int ih, int new_
 }
 
 // darknet letterbox_image (DN/image.c:960-981) of one output pixel: the aspect-preserving resize_image embedded at the centre of a
-// 0.5-filled canvas.
-template <class At>
-__device__ __forceinline__ void px_letterbox(const At &at, int iw, int ih, int new_w, int new_h, int off_x, int off_y, int oy, int ox, float *v)
+// 0.5-filled canvas (the fill belongs to the real channels: a granule's padding stays zero).
+template <int NC, class At>
+__device__ __forceinline__ void px_letterbox(const At &at, int iw, int ih, int new_w, int new_h, int off_x, int off_y, int oy, int ox, int c0, int nc, float *v)
 {
     const int r = oy - off_y, c = ox - off_x;
-    v[0] = v[1] = v[2] = 0.5f;
-    if ((unsigned)r < (unsigned)new_h && (unsigned)c < (unsigned)new_w) px_resize(at, iw, ih, new_w, new_h, r, c, v);
+#pragma unroll
+    for (int k = 0; k < NC; ++k) if (NC == 3 || k < nc) v[k] = 0.5f;
+    if ((unsigned)r < (unsigned)new_h && (unsigned)c < (unsigned)new_w) px_resize<NC>(at, iw, ih, new_w, new_h, r, c, c0, nc, v);
 }
 
 // darknet's classifier validation fit (DN/examples/classifier.c:635-636) of one output pixel: resize_min(im, net_w) -- the shorter side
 // becomes net_w, whatever net_h is -- then crop_image(resized, (rw - net_w) / 2, (rh - net_h) / 2, net_w, net_h) (DN/image.c:857-875).  The
 // offsets truncate toward zero and are negative where the resized image is smaller than the network (a non-square one); the coordinates
 // are CLAMPED to the resized image, so its edge is replicated: there is no fill value.
-template <class At>
-__device__ __forceinline__ void px_center_crop(const At &at, int iw, int ih, int net_w, int net_h, int oy, int ox, float *v)
+template <int NC, class At>
+__device__ __forceinline__ void px_center_crop(const At &at, int iw, int ih, int net_w, int net_h, int oy, int ox, int c0, int nc, float *v)
 {
     int rw, rh;
     resize_min_dims(net_w, iw, ih, &rw, &rh);
     const int r = min(max(oy + (rh - net_h) / 2, 0), rh - 1), c = min(max(ox + (rw - net_w) / 2, 0), rw - 1);
-    px_resize(at, iw, ih, rw, rh, r, c, v);
+    px_resize<NC>(at, iw, ih, rw, rh, r, c, c0, nc, v);
 }
 
 // `cv2.resize(image_float32, (ow, oh))` as V2/utils.py:13-27 calls it (INTER_LINEAR on a float32 image, after BGR -> RGB) followed by the
@@ -151,34 +177,40 @@ __device__ __forceinline__ void px_cv2(const At &at, int h, int w, int oh, int o
     }
 }
 
-// source readers of the single-image kernels: a uint8 HWC image, a planar float [3][h][w] image
+// source readers of the single-image kernels: a uint8 HWC image of `px` channels, a planar float [C][h][w] image
 struct AtU8 {
-    const uint8_t *img; int w;
-    __device__ __forceinline__ float operator()(int y, int x, int c) const { return (float)img[((size_t)y * w + x) * 3 + c]; }
+    const uint8_t *img; int w, px;
+    __device__ __forceinline__ float operator()(int y, int x, int c) const { return (float)img[((size_t)y * w + x) * px + c]; }
 };
 struct AtPlanar {
     const float *img; int w, h;
     __device__ __forceinline__ float operator()(int y, int x, int k) const { return img[(size_t)k * w * h + (size_t)y * w + x]; }
 };
 
-template <typename T>
-__global__ void k_resize_u8(const uint8_t *img, int h, int w, int oh, int ow, T *out, int out_stride, int out_c, float post_scale, float post_add)
+template <typename T, int NCH>
+__global__ void k_resize_u8(const uint8_t *img, int h, int w, int oh, int ow, T *out, int out_stride, int out_c, float post_scale, float post_add, int nch)
 {
-    int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= oh * ow) return;
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    const int g = NCH ? 0 : idx / (oh * ow), p = NCH ? idx : idx - g * (oh * ow);
+    if (NCH ? p >= oh * ow : g * 8 >= nch) return;
+    const Planes<NCH> pl(g, nch);
     int oy = p / ow, ox = p - oy * ow;
     float v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    px_stretch(AtU8{img, w}, h, w, oh, ow, oy, ox, post_scale, post_add, v);
-    if (out_c >= 8) Elt<T>::store8(out + (size_t)p * out_stride, v);
+    px_stretch<NCH ? NCH : 8>(AtU8{img, w, NCH ? NCH : nch}, h, w, oh, ow, oy, ox, post_scale, post_add, pl.c0, pl.nc, v);
+    if (out_c >= 8) Elt<T>::store8(out + (size_t)p * out_stride + pl.c0, v);
     else
         for (int c = 0; c < out_c; ++c) Elt<T>::store1(out + (size_t)p * out_stride + c, v[c]);
 }
 
+// nch != 3: whole granules are stored (out_c >= nch, out_stride >= roundup(nch, 8))
 hipError_t launch_resize_u8(const uint8_t *img, int h, int w, int out_h, int out_w, void *out, int out_dt, int out_stride,
-                            int out_c, hipStream_t s, float post_scale, float post_add)
+                            int out_c, hipStream_t s, float post_scale, float post_add, int nch)
 {
     size_t np = (size_t)out_h * out_w;
-    WITH_DT(out_dt, hipLaunchKernelGGL(k_resize_u8<T>, grid_for(np), dim3(256), 0, s, img, h, w, out_h, out_w, (T *)out, out_stride, out_c, post_scale, post_add));
+    if (nch == 3) { WITH_DT(out_dt, hipLaunchKernelGGL((k_resize_u8<T, 3>), grid_for(np), dim3(256), 0, s, img, h, w, out_h, out_w, (T *)out, out_stride, out_c, post_scale, post_add, 3)); return hipGetLastError(); }
+    const int c8 = (nch + 7) / 8;
+    if (nch < 1 || out_c < 8 || out_stride < c8 * 8 || np * c8 > 0x7fffffffull) return hipErrorInvalidValue;
+    WITH_DT(out_dt, hipLaunchKernelGGL((k_resize_u8<T, 0>), grid_for(np * c8), dim3(256), 0, s, img, h, w, out_h, out_w, (T *)out, out_stride, out_c, post_scale, post_add, nch));
     return hipGetLastError();
 }
 
@@ -189,7 +221,7 @@ __global__ void k_resize_cv2_u8(const uint8_t *img, int h, int w, int oh, int ow
     if (p >= oh * ow) return;
     const int dy = p / ow, dx = p - dy * ow;
     float v[3];
-    px_cv2(AtU8{img, w}, h, w, oh, ow, dy, dx, swap_rb, divisor, v);
+    px_cv2(AtU8{img, w, 3}, h, w, oh, ow, dy, dx, swap_rb, divisor, v);
 #pragma unroll
     for (int c = 0; c < 3; ++c) out[(size_t)p * 3 + c] = v[c];
 }
@@ -679,80 +711,102 @@ hipError_t launch_shortcut(const TView &a, const TView &b, const TView &out, boo
 }
 
 // ---- darknet letterbox_image (DN/image.c:960-981) fused with the layout change: a planar float image of any size -> px_letterbox,
-//      written as the 8-channel network input ----
-template <typename T>
-__global__ void k_letterbox_chw(const float *img, int iw, int ih, int net_h, int net_w, int new_w, int new_h, int off_x, int off_y, T *out, int out_stride)
+//      written as the network input (whole granules per pixel) ----
+template <typename T, int NCH>
+__global__ void k_letterbox_chw(const float *img, int iw, int ih, int net_h, int net_w, int new_w, int new_h, int off_x, int off_y, T *out, int out_stride, int nch)
 {
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= net_h * net_w) return;
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    const int g = NCH ? 0 : idx / (net_h * net_w), p = NCH ? idx : idx - g * (net_h * net_w);
+    if (NCH ? p >= net_h * net_w : g * 8 >= nch) return;
+    const Planes<NCH> pl(g, nch);
     const int oy = p / net_w, ox = p - oy * net_w;
-    float v[8] = {0.5f, 0.5f, 0.5f, 0, 0, 0, 0, 0};
-    px_letterbox(AtPlanar{img, iw, ih}, iw, ih, new_w, new_h, off_x, off_y, oy, ox, v);
-    Elt<T>::store8(out + (size_t)p * out_stride, v);
+    float v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    px_letterbox<NCH ? NCH : 8>(AtPlanar{img, iw, ih}, iw, ih, new_w, new_h, off_x, off_y, oy, ox, pl.c0, pl.nc, v);
+    Elt<T>::store8(out + (size_t)p * out_stride + pl.c0, v);
 }
-hipError_t launch_letterbox_chw(const float *img, int iw, int ih, int net_h, int net_w, void *out, int out_dt, int out_stride, hipStream_t s)
+hipError_t launch_letterbox_chw(const float *img, int iw, int ih, int net_h, int net_w, void *out, int out_dt, int out_stride, hipStream_t s, int nch)
 {
     int new_w, new_h;
     letterbox_dims(net_w, net_h, iw, ih, &new_w, &new_h);
-    if (new_w < 1 || new_h < 1) return hipErrorInvalidValue;
-    WITH_DT(out_dt, hipLaunchKernelGGL(k_letterbox_chw<T>, grid_for((size_t)net_h * net_w), dim3(256), 0, s, img, iw, ih, net_h, net_w, new_w, new_h, (net_w - new_w) / 2, (net_h - new_h) / 2, (T *)out, out_stride));
+    const int c8 = (nch + 7) / 8;
+    if (new_w < 1 || new_h < 1 || nch < 1 || out_stride < c8 * 8 || (size_t)net_h * net_w * c8 > 0x7fffffffull) return hipErrorInvalidValue;
+    if (nch == 3) WITH_DT(out_dt, hipLaunchKernelGGL((k_letterbox_chw<T, 3>), grid_for((size_t)net_h * net_w), dim3(256), 0, s, img, iw, ih, net_h, net_w, new_w, new_h, (net_w - new_w) / 2, (net_h - new_h) / 2, (T *)out, out_stride, 3));
+    else WITH_DT(out_dt, hipLaunchKernelGGL((k_letterbox_chw<T, 0>), grid_for((size_t)net_h * net_w * c8), dim3(256), 0, s, img, iw, ih, net_h, net_w, new_w, new_h, (net_w - new_w) / 2, (net_h - new_h) / 2, (T *)out, out_stride, nch));
     return hipGetLastError();
 }
 
 // ---- ragged batch fit (yolo_forward_images_u8): native-size uint8 RGB images packed in one HWC buffer, described by a device table of
 //      {offset, h, w}, fitted into the network input [n][net_h][net_w][out_stride] by ONE launch: grid (pixel tiles) x (images), one output pixel
-//      per lane, the 16-byte output pixel (8 channels: 3 real + 5 zero) stored as one vector.  Per pixel, each fit is the single-image
+//      per lane, the 16-byte output pixel (8 channels: 3 real + 5 zero) stored as one vector; images of `nch` planes (NCH = 0): grid
+//      (pixel tiles x granules) x (images), one output pixel x granule per lane, source pixels `nch` bytes apart.  Per pixel, each fit is the single-image
 //      kernel's arithmetic (px_stretch / px_letterbox / px_cv2; px_center_crop has no single-image kernel), so a batched image equals the same image run alone, bit for bit.
 //      Source bytes are read through a buffer descriptor whose size is the packed buffer's byte count: a descriptor that pointed past
 //      the end would read zeros, never another allocation (the host validates every descriptor before the launch anyway).
 struct AtPacked {
-    __amdgpu_buffer_rsrc_t rsrc; unsigned base, pitch; int fit;      // pitch: bytes from one row to the next (a whole image: w * 3; a window: its image's)
+    __amdgpu_buffer_rsrc_t rsrc; unsigned base, pitch; int fit; unsigned px;      // pitch: bytes from one row to the next (a whole image: w * px; a window: its image's); px: bytes from one pixel to the next (the channel count)
     __device__ __forceinline__ float operator()(int y, int x, int c) const
     {
-        const unsigned v = (unsigned)__builtin_amdgcn_raw_buffer_load_b8(rsrc, base + (unsigned)y * pitch + (unsigned)x * 3u + (unsigned)c, 0, 0);
+        const unsigned v = (unsigned)__builtin_amdgcn_raw_buffer_load_b8(rsrc, base + (unsigned)y * pitch + (unsigned)x * px + (unsigned)c, 0, 0);
         // STRETCH and CV2 read the byte as a float (the /255 and /225 are part of px_stretch / px_cv2); LETTERBOX and CENTER_CROP read darknet's 0..1 value
         return fit == FIT_LETTERBOX || fit == FIT_CENTER_CROP ? fit_unit_value(FIT_LETTERBOX, v) : (float)v;
     }
 };
 
-__device__ __forceinline__ unsigned row_pitch(const ImgDesc &d) { return (unsigned)d.w * 3u; }
-__device__ __forceinline__ unsigned row_pitch(const WinDesc &d) { return (unsigned)d.pitch; }
+__device__ __forceinline__ unsigned row_pitch(const ImgDesc &d, unsigned px) { return (unsigned)d.w * px; }
+__device__ __forceinline__ unsigned row_pitch(const WinDesc &d, unsigned) { return (unsigned)d.pitch; }
 // Desc: ImgDesc (whole images) or WinDesc (windows of larger images, yolo_detect_tiled_u8): the same arithmetic over (h, w) pixels read at a row pitch
-template <typename T, int FIT, class Desc>
+template <typename T, int FIT, class Desc, int NCH>
 __global__ __launch_bounds__(256) void k_fit_images(const uint8_t *pixels, unsigned bytes, const Desc *descs, int net_h, int net_w, T *out, int out_stride,
-                                                    float post_mul, float post_add)
+                                                    float post_mul, float post_add, int nch, int tiles)
 {
+    static_assert(NCH == 3 || (FIT != FIT_CV2 && FIT != FIT_CV2_BGR), "the cv2 fits mean an RGB / BGR image");
+    constexpr int NC = NCH ? NCH : 8;
     const int img = blockIdx.y;
-    const int p = blockIdx.x * 256 + threadIdx.x;
+    const int g = NCH ? 0 : blockIdx.x / tiles;          // (tiles: pixel tiles per granule, the x extent of the RGB form's grid)
+    const int p = (NCH ? blockIdx.x : blockIdx.x - g * tiles) * 256 + threadIdx.x;
     if (p >= net_h * net_w) return;
+    const Planes<NCH> pl(g, nch);
     const Desc d = descs[img];
     const int oy = p / net_w, ox = p - oy * net_w;
-    const AtPacked at{__builtin_amdgcn_make_buffer_rsrc((void *)pixels, 0, bytes, 0x00020000), (unsigned)d.offset, row_pitch(d), FIT};
+    const unsigned px = NCH ? NCH : (unsigned)nch;
+    const AtPacked at{__builtin_amdgcn_make_buffer_rsrc((void *)pixels, 0, bytes, 0x00020000), (unsigned)d.offset, row_pitch(d, px), FIT, px};
     float v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (FIT == FIT_STRETCH) px_stretch(at, d.h, d.w, net_h, net_w, oy, ox, post_mul, post_add, v);
+    if (FIT == FIT_STRETCH) px_stretch<NC>(at, d.h, d.w, net_h, net_w, oy, ox, post_mul, post_add, pl.c0, pl.nc, v);
     else {
         if (FIT == FIT_LETTERBOX) {
             int new_w, new_h;
             letterbox_dims(net_w, net_h, d.w, d.h, &new_w, &new_h);
-            px_letterbox(at, d.w, d.h, new_w, new_h, (net_w - new_w) / 2, (net_h - new_h) / 2, oy, ox, v);
-        } else if (FIT == FIT_CENTER_CROP) px_center_crop(at, d.w, d.h, net_w, net_h, oy, ox, v);
-        else px_cv2(at, d.h, d.w, net_h, net_w, oy, ox, FIT == FIT_CV2_BGR, 225.0f, v);
+            px_letterbox<NC>(at, d.w, d.h, new_w, new_h, (net_w - new_w) / 2, (net_h - new_h) / 2, oy, ox, pl.c0, pl.nc, v);
+        } else if (FIT == FIT_CENTER_CROP) px_center_crop<NC>(at, d.w, d.h, net_w, net_h, oy, ox, pl.c0, pl.nc, v);
+        else if constexpr (NCH == 3) px_cv2(at, d.h, d.w, net_h, net_w, oy, ox, FIT == FIT_CV2_BGR, 225.0f, v);
         // YOLOv1's `x * 2 - 1` ([net] yolo_input_mul / yolo_input_add), as px_stretch applies it
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
+        for (int c = 0; c < NC; ++c) {
+            if (NCH != 3 && c >= pl.nc) break;
             if (post_mul != 1.0f) v[c] *= post_mul;
             if (post_add != 0.0f) v[c] += post_add;
         }
     }
-    Elt<T>::store8(out + ((size_t)img * net_h * net_w + p) * out_stride, v);
+    Elt<T>::store8(out + ((size_t)img * net_h * net_w + p) * out_stride + pl.c0, v);
 }
 
 hipError_t launch_fit_images(const uint8_t *pixels, size_t bytes, const ImgDesc *d_descs, int n, int fit, int net_h, int net_w, void *out, int out_dt,
-                             int out_stride, float post_mul, float post_add, hipStream_t s)
+                             int out_stride, float post_mul, float post_add, hipStream_t s, int nch)
 {
     if (n < 1 || net_h < 1 || net_w < 1 || (size_t)net_h * net_w > 0x7fffffffull || bytes > 0xffffffffull || fit < FIT_STRETCH || fit > FIT_CENTER_CROP) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)((net_h * net_w + 255) / 256), (unsigned)n);
-#define FIT_LAUNCH(F, D, descs) WITH_DT(out_dt, hipLaunchKernelGGL((k_fit_images<T, F, D>), grid, dim3(256), 0, s, pixels, (unsigned)bytes, descs, net_h, net_w, (T *)out, out_stride, post_mul, post_add))
+    const int tiles = (net_h * net_w + 255) / 256;
+#define FIT_LAUNCH_N(F, D, descs, NCH, grid) WITH_DT(out_dt, hipLaunchKernelGGL((k_fit_images<T, F, D, NCH>), grid, dim3(256), 0, s, pixels, (unsigned)bytes, descs, net_h, net_w, (T *)out, out_stride, post_mul, post_add, nch, tiles))
+    if (nch != 3) {          // N planes: the granule folded into the grid's x; the cv2 fits are the caller's to refuse
+        const int c8 = (nch + 7) / 8;
+        if (nch < 1 || out_stride < c8 * 8 || (size_t)tiles * c8 > 0x7fffffffull || fit == FIT_CV2 || fit == FIT_CV2_BGR) return hipErrorInvalidValue;
+        const dim3 grid_n((unsigned)(tiles * c8), (unsigned)n);
+        if (fit == FIT_STRETCH) FIT_LAUNCH_N(FIT_STRETCH, ImgDesc, d_descs, 0, grid_n);
+        else if (fit == FIT_LETTERBOX) FIT_LAUNCH_N(FIT_LETTERBOX, ImgDesc, d_descs, 0, grid_n);
+        else FIT_LAUNCH_N(FIT_CENTER_CROP, ImgDesc, d_descs, 0, grid_n);
+        return hipGetLastError();
+    }
+    const dim3 grid((unsigned)tiles, (unsigned)n);
+#define FIT_LAUNCH(F, D, descs) FIT_LAUNCH_N(F, D, descs, 3, grid)
     if (fit == FIT_STRETCH) FIT_LAUNCH(FIT_STRETCH, ImgDesc, d_descs);
     else if (fit == FIT_LETTERBOX) FIT_LAUNCH(FIT_LETTERBOX, ImgDesc, d_descs);
     else if (fit == FIT_CV2) FIT_LAUNCH(FIT_CV2, ImgDesc, d_descs);
@@ -765,10 +819,12 @@ hipError_t launch_fit_windows(const uint8_t *pixels, size_t bytes, const WinDesc
                               int out_stride, float post_mul, float post_add, hipStream_t s)
 {
     if (n < 1 || net_h < 1 || net_w < 1 || (size_t)net_h * net_w > 0x7fffffffull || bytes > 0xffffffffull || (fit != FIT_STRETCH && fit != FIT_LETTERBOX)) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)((net_h * net_w + 255) / 256), (unsigned)n);
+    const int tiles = (net_h * net_w + 255) / 256, nch = 3;
+    const dim3 grid((unsigned)tiles, (unsigned)n);
     if (fit == FIT_STRETCH) FIT_LAUNCH(FIT_STRETCH, WinDesc, d_wins);
     else FIT_LAUNCH(FIT_LETTERBOX, WinDesc, d_wins);
 #undef FIT_LAUNCH
+#undef FIT_LAUNCH_N
     return hipGetLastError();
 }
 
@@ -781,7 +837,7 @@ __global__ void k_letterbox_planar(const float *img, int iw, int ih, int W, int 
     if (p >= W * H) return;
     const int oy = p / W, ox = p - oy * W;
     float v[3];
-    px_letterbox(AtPlanar{img, iw, ih}, iw, ih, new_w, new_h, off_x, off_y, oy, ox, v);
+    px_letterbox<3>(AtPlanar{img, iw, ih}, iw, ih, new_w, new_h, off_x, off_y, oy, ox, 0, 3, v);
 #pragma unroll
     for (int k = 0; k < 3; ++k) out[(size_t)k * W * H + p] = v[k];
 }

@@ -381,10 +381,13 @@ hipError_t launch_segment_labels(const float *map, int stride, int map_h, int ma
 hipError_t launch_nhwc_to_chw(const float *in, float *out, int n, int hw, int c, hipStream_t s);      // dense fp32 [n][hw][c] -> [n][c][hw]
 
 // ---- memory-bound operators (ew_ops.hip) ------------------------------------------------------
-hipError_t launch_preprocess(const void *img, int fmt /*0 u8, 1 f32*/, int n, int hw, float scale,
-                             void *out, int out_dt, int out_stride, hipStream_t s, float post_mul = 1.0f, float post_add = 0.0f);
+// The kernels that write the network input take the image's channel count `nch` ([net] channels; 1..PLANES_MAX with yolo_input=planes): 3 runs the RGB
+// form (one lane per pixel, 3 real + 5 zero channels), any other count one lane per pixel x 8-channel granule, the padding of the last granule zero
+enum { PLANES_MAX = 1024 };
+hipError_t launch_preprocess(const void *img, int fmt /*0 u8 HWC, 1 f32 HWC, 2 f32 planar*/, int n, int hw, float scale,
+                             void *out, int out_dt, int out_stride, hipStream_t s, float post_mul = 1.0f, float post_add = 0.0f, int nch = 3);
 hipError_t launch_resize_u8(const uint8_t *img, int h, int w, int out_h, int out_w, void *out, int out_dt,
-                            int out_stride, int out_c, hipStream_t s, float post_scale = 1.0f, float post_add = 0.0f);
+                            int out_stride, int out_c, hipStream_t s, float post_scale = 1.0f, float post_add = 0.0f, int nch = 3);
 // cv2.resize (INTER_LINEAR, float32) of a uint8 [h,w,3] image to fp32 [oh,ow,3], optional BGR -> RGB, then / divisor (V2/utils.py:13-27)
 hipError_t launch_resize_cv2_u8(const uint8_t *img, int h, int w, int oh, int ow, int swap_rb, float divisor, float *out, hipStream_t s);
 // ragged batch of native-size uint8 RGB images (yolo_forward_images_u8): one packed HWC buffer, one descriptor per image (the layout of
@@ -393,7 +396,7 @@ struct ImgDesc { unsigned long long offset; int h, w; };
 enum { FIT_STRETCH = 0, FIT_LETTERBOX = 1, FIT_CV2 = 2, FIT_CV2_BGR = 3, FIT_CENTER_CROP = 4 };
 // source pixels are read through a buffer descriptor of `bytes` bytes (< 2^32, checked by the caller with every descriptor)
 hipError_t launch_fit_images(const uint8_t *pixels, size_t bytes, const ImgDesc *d_descs, int n, int fit, int net_h, int net_w, void *out, int out_dt,
-                             int out_stride, float post_mul, float post_add, hipStream_t s);
+                             int out_stride, float post_mul, float post_add, hipStream_t s, int nch = 3);
 // One window of a larger image (yolo_detect_tiled_u8): h x w pixels whose first one lies at byte `offset` of the packed buffer, in an image
 // whose rows are `pitch` bytes apart; `image`: the descriptor it was cut from, (x0, y0): its first pixel in that image.  32 bytes.
 struct WinDesc { unsigned long long offset; int h, w, pitch, image, x0, y0; };
@@ -628,7 +631,7 @@ hipError_t launch_tile_merge(const TileMergeArgs &a, hipStream_t s);
 hipError_t launch_tile_relative(void *boxes, const int *counts, int max_out, const ImgDesc *descs, int n, hipStream_t s);
 // row S on its own: score = max_k(obj * cls_k), label = first arg-max, of nrows decoded rows (objectness_mode: V3/yolo_v3.py:385,397)
 void launch_score_rows(const float *det, size_t nrows, int attrs, float *scores, int *labels, hipStream_t s, int objectness_mode = 0);
-hipError_t launch_letterbox_chw(const float *img, int iw, int ih, int net_h, int net_w, void *out, int out_dt, int out_stride, hipStream_t s);
+hipError_t launch_letterbox_chw(const float *img, int iw, int ih, int net_h, int net_w, void *out, int out_dt, int out_stride, hipStream_t s, int nch = 3);
 hipError_t launch_nms_dets(const float4 *boxes, float *prob, float *objectness, int n, int classes, float thresh, int by_obj, hipStream_t s);
 // darknet get_network_boxes on the device (post_ops.hip): ordered compaction + letterbox correction of one image's decoded rows
 struct DnBoxesArgs {

@@ -443,4 +443,27 @@ int yolo_layer_output(yolo_ctx *c, int index, int n, float *out, size_t out_floa
     return YOLO_OK;
 }
 
+// the staged network input of the last forward as fp32, every stored channel of a pixel: dims_out = {h, w, stored channels}, 8 for an RGB image (3 real + 5 zero),
+// roundup(N, 8) for N planes.  Introspection, like yolo_layer_output: a copy through a temporary buffer
+int yolo_staged_input(yolo_ctx *c, int n, float *out, size_t out_floats, int *dims_out)
+{
+    if (!c) return YOLO_ERR_INVALID;
+    if (c->vec_n || c->in_pair) return fail(c, YOLO_ERR_UNSUPPORTED, "yolo_staged_input: a vector-input network's row and a split-fp16 image stored as pairs are not served");
+    if (c->stem_u8) return fail(c, YOLO_ERR_STATE, "yolo_staged_input: the last forward's uint8 images were read by the fused first-stage kernel itself, nothing was staged");
+    if (n < 1 || n > c->last_n) return fail(c, YOLO_ERR_INVALID, "bad n");
+    TView v = c->input; v.n = n; v.c = v.stride;
+    if (dims_out) { dims_out[0] = v.h; dims_out[1] = v.w; dims_out[2] = v.c; }
+    const size_t need = (size_t)n * v.h * v.w * v.c;
+    if (!out) return YOLO_OK;
+    if (out_floats < need) return fail(c, YOLO_ERR_INVALID, "output buffer too small");
+    HIPCK(c, hipSetDevice(c->device));
+    float *tmp = nullptr; HIPCK(c, hipMalloc((void **)&tmp, need * 4));
+    hipError_t e = launch_to_f32(v, tmp, c->stream, 1.f);
+    if (e == hipSuccess) e = hipMemcpyAsync(out, tmp, need * 4, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    hipFree(tmp);
+    if (e != hipSuccess) return fail(c, YOLO_ERR_HIP, "staged_input: %s", hipGetErrorString(e));
+    return YOLO_OK;
+}
+
 }  // extern "C"

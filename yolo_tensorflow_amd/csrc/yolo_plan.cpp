@@ -540,16 +540,27 @@ static int parse_sections(yolo_ctx *c, const std::vector<Section> &secs)
     // [net] yolo_input=vector with inputs=N (char-rnn: DN/parser.c:656 net->inputs where the cfg names no image size): the input is one row of N values per stream.
     // Without the key a cfg without a size stays refused, as before
     const std::string in_kind = opt_s(net, "yolo_input", "");
-    if (!in_kind.empty() && in_kind != "vector") return fail(c, YOLO_ERR_INVALID, "cfg: yolo_input=%s (the one value is `vector`)", in_kind.c_str());
+    if (!in_kind.empty() && in_kind != "vector" && in_kind != "planes") return fail(c, YOLO_ERR_INVALID, "cfg: yolo_input=%s (the values are `vector` and `planes`)", in_kind.c_str());
     c->vec_n = 0;
-    if (!in_kind.empty()) {
+    if (in_kind == "vector") {
         const int N = opt_i(net, "inputs", 0);
         if (c->in_h > 0 || c->in_w > 0) return fail(c, YOLO_ERR_INVALID, "cfg: yolo_input=vector together with height=%d / width=%d: a vector network has no image size (inputs= alone gives its length)", c->in_h, c->in_w);
         if (N <= 0 || N > (1 << 24)) return fail(c, YOLO_ERR_INVALID, "cfg: yolo_input=vector needs inputs= of 1..%d (got %d)", 1 << 24, N);
         if (!opt_s(net, "yolo_output", "").empty()) return fail(c, YOLO_ERR_UNSUPPORTED, "cfg: yolo_input=vector together with yolo_output=map is not served");
         c->vec_n = N; c->in_h = 1; c->in_w = 1; c->in_c = N;
+    } else if (in_kind == "planes") {
+        // [net] yolo_input=planes with height, width and channels=N: an image network of N planes (grey, RGB-D, multispectral, darknet's go board).  With
+        // channels=3 the plan is the plan of the cfg without the key; any other count is staged as roundup(N, 8) channels per pixel and read by layer 0 as
+        // any inner layer reads a tensor of N channels
+        if (c->in_h <= 0 || c->in_w <= 0) {
+            if (net.kv.count("inputs")) return fail(c, YOLO_ERR_INVALID, "cfg: yolo_input=planes with inputs=%d and no image size: it needs positive height= and width= (got height=%d width=%d)", opt_i(net, "inputs", 0), c->in_h, c->in_w);
+            return fail(c, YOLO_ERR_INVALID, "cfg: yolo_input=planes needs positive height= and width= (got height=%d width=%d)", c->in_h, c->in_w);
+        }
+        if (c->in_c < 1 || c->in_c > PLANES_MAX) return fail(c, YOLO_ERR_INVALID, "cfg: yolo_input=planes needs channels= of 1..%d (got channels=%d)", PLANES_MAX, c->in_c);
+        if (c->in_c != 3 && (c->dtype == YOLO_FP8 || c->split()))
+            return fail(c, YOLO_ERR_UNSUPPORTED, "cfg: yolo_input=planes with channels=%d is not served in the %s configuration (bf16, fp16 and fp32 are)", c->in_c, c->split() ? "split-fp16" : "fp8");
     } else if (c->in_h <= 0 || c->in_w <= 0 || c->in_c != 3)
-        return fail(c, YOLO_ERR_UNSUPPORTED, "cfg: need an input of positive height and width with 3 channels (got %dx%dx%d); a vector-input network ([net] inputs=N, no image size) is declared with [net] yolo_input=vector", c->in_w, c->in_h, c->in_c);
+        return fail(c, YOLO_ERR_UNSUPPORTED, "cfg: need an input of positive height and width with 3 channels (got %dx%dx%d); a vector-input network ([net] inputs=N, no image size) is declared with [net] yolo_input=vector, an image network of another channel count with [net] yolo_input=planes", c->in_w, c->in_h, c->in_c);
     const int NL = (int)secs.size() - 1;
     // a recurrent layer is served in the bf16, fp16 and fp32 configurations: refused here, by its own name, ahead of whatever else of such a network the
     // configuration refuses.  ([net] time_steps is read and ignored: one call is one step)
@@ -976,7 +987,7 @@ int recur_sublayers(const Layer &L, int subs[8])
 }
 
 // elements per pixel of the tensor layer idx's view lies in (-1: the network input); valid once create_storages ran
-static int stride_of(const yolo_ctx *c, int idx) { return idx < 0 ? (c->vec_n ? roundup(c->vec_n, 8) : c->in_pair ? 24 : 8) : c->layers[idx].storage >= 0 ? c->storages[c->layers[idx].storage].stride : 0; }
+static int stride_of(const yolo_ctx *c, int idx) { return idx < 0 ? (c->vec_n ? roundup(c->vec_n, 8) : c->in_pair ? 24 : roundup(c->in_c, 8)) : c->layers[idx].storage >= 0 ? c->storages[c->layers[idx].storage].stride : 0; }
 
 RecurGeom recur_geom(const yolo_ctx *c, const Layer &L)
 {
@@ -1015,12 +1026,12 @@ int allocate(yolo_ctx *c)
         L.out.n = c->max_batch; L.out.h = L.H; L.out.w = L.W; L.out.c = L.C; L.out.stride = s.stride; L.out.dt = s.dt;
         L.out.ptr = (char *)c->phys[s.phys] + (size_t)L.ch_off * dt_size(s.dt);
     }
-    // network input: 3 real channels padded to 8
+    // network input: 3 real channels padded to 8; N planes ([net] yolo_input=planes) padded to whole granules
     c->input.dt = c->dtype == YOLO_FP32 ? DT_F32 : (c->dtype == YOLO_FP16 || c->split()) ? DT_F16 : DT_BF16;            // fp8 mode keeps the image in bf16
     const int in_stride = stride_of(c, -1);                    // split fp16: hi | lo | hi blocks of the 8 padded channels; a vector network: [max_batch][roundup(N, 8)], the padding zero
     size_t in_bytes = (size_t)c->max_batch * c->in_h * c->in_w * in_stride * dt_size(c->input.dt) + (c->vec_n ? 256 : 0);      // (+ a tail the 16-byte pieces of a row's reader may touch, as the pool's buffers have)
     HIPCK(c, hipMalloc(&c->input.ptr, in_bytes)); HIPCK(c, hipMemsetAsync(c->input.ptr, 0, in_bytes, c->stream));      // defined even if a timing pass runs before any image was staged
-    c->input.n = c->max_batch; c->input.h = c->in_h; c->input.w = c->in_w; c->input.c = c->vec_n ? c->vec_n : 8; c->input.stride = in_stride;
+    c->input.n = c->max_batch; c->input.h = c->in_h; c->input.w = c->in_w; c->input.c = c->vec_n ? c->vec_n : c->in_c == 3 ? 8 : c->in_c; c->input.stride = in_stride;
     if (c->split()) {
         // fp32 staging for the layers that run in fp32 between a join and a split (input conversion, upsample, pooling, reorg)
         size_t cap = (size_t)c->max_batch * c->in_h * c->in_w * 8;
@@ -1047,7 +1058,7 @@ int allocate(yolo_ctx *c)
             if (!one_pixel && (in.stride != in.c || in.c != L.fc_c)) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %zu: [connected] needs a dense producer (channels a multiple of 8, not part of a concat)", i);
         }
     }
-    c->stage_bytes = (size_t)c->max_batch * c->in_h * c->in_w * (c->vec_n ? c->vec_n : 3) * 4;
+    c->stage_bytes = (size_t)c->max_batch * c->in_h * c->in_w * (c->vec_n ? c->vec_n : c->in_c) * 4;
     HIPCK(c, hipMalloc(&c->d_stage, c->stage_bytes));
     HIPCK(c, hipMalloc((void **)&c->d_descs, (size_t)c->max_batch * sizeof(ImgDesc)));      // ragged batches: one descriptor per image
     size_t nr = (size_t)c->max_batch * c->rows;

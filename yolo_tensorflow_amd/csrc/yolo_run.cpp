@@ -454,7 +454,9 @@ int run_layer(yolo_ctx *c, int i, int n)
     return YOLO_OK;
 }
 
-// ---- input staging.  Every site that writes the network input does: auto [dst, dt] = input_fill_dst(c); its own fill launch into dst (8 channels per pixel); input_filled(c, pixels) ----
+// ---- input staging.  Every site that writes the network input does: auto [dst, dt] = input_fill_dst(c); its own fill launch into dst (c->input.stride channels per
+//      pixel: 8 for an RGB image, roundup(N, 8) for N planes; pairs: 8, in fp32); input_filled(c, pixels) ----
+static int fill_stride(const yolo_ctx *c) { return c->in_pair ? 8 : c->input.stride; }
 static std::pair<void *, int> input_fill_dst(yolo_ctx *c)      // (pointer, element type).  Split fp16: the fill writes the image in fp32 (exact for uint8 pixels x scale up to fp32 rounding), input_filled splits it into pairs
 {
     c->stem_u8 = nullptr;          // from here on the fused stem reads the filled input, not a caller's uint8 image: ahead of the fill launch, so also when that launch is refused
@@ -469,7 +471,7 @@ int stage_in(yolo_ctx *c, const void *images, int n, int fmt, int loc, float sca
     size_t npix = (size_t)n * c->in_h * c->in_w;
     const void *src = images;
     if (loc == YOLO_HOST) {
-        HIPCK(c, hipMemcpyAsync(c->d_stage, images, npix * 3 * (fmt == YOLO_IMG_U8 ? 1 : 4), hipMemcpyHostToDevice, c->stream));
+        HIPCK(c, hipMemcpyAsync(c->d_stage, images, npix * c->in_c * (fmt == YOLO_IMG_U8 ? 1 : 4), hipMemcpyHostToDevice, c->stream));
         src = c->d_stage;
     }
     // uint8 images of a network whose first layers run as the fused stem: the stem converts the pixels itself (conv_stem.hip, U8 form).
@@ -480,7 +482,7 @@ int stage_in(yolo_ctx *c, const void *images, int n, int fmt, int loc, float sca
         return YOLO_OK;
     }
     auto [dst, dt] = input_fill_dst(c);
-    HIPCK(c, launch_preprocess(src, fmt, n, c->in_h * c->in_w, scale, dst, dt, 8, c->stream, c->in_mul, c->in_add));
+    HIPCK(c, launch_preprocess(src, fmt, n, c->in_h * c->in_w, scale, dst, dt, fill_stride(c), c->stream, c->in_mul, c->in_add, c->in_c));
     HIPCK(c, input_filled(c, npix));
     return YOLO_OK;
 }
@@ -640,14 +642,14 @@ static int forward_one(yolo_ctx *c, const char *name, const char *fill_name, Fil
 
 int yolo_forward_image_u8(yolo_ctx *c, const uint8_t *image, int h, int w, int loc, float *det_out, int out_loc)
 {
-    const FillOne fill = [](yolo_ctx *c, const void *src, int h, int w, void *dst, int dt) { return launch_resize_u8((const uint8_t *)src, h, w, c->in_h, c->in_w, dst, dt, 8, 8, c->stream, c->in_mul, c->in_add); };
-    return forward_one(c, "yolo_forward_image_u8", "resize", fill, image, h, w, (size_t)h * w * 3, loc, det_out, out_loc);
+    const FillOne fill = [](yolo_ctx *c, const void *src, int h, int w, void *dst, int dt) { return launch_resize_u8((const uint8_t *)src, h, w, c->in_h, c->in_w, dst, dt, fill_stride(c), 8, c->stream, c->in_mul, c->in_add, c->in_c); };
+    return forward_one(c, "yolo_forward_image_u8", "resize", fill, image, h, w, (size_t)h * w * (c ? c->in_c : 3), loc, det_out, out_loc);
 }
 
 int yolo_forward_letterbox_chw(yolo_ctx *c, const float *image_chw, int w, int h, int loc, float *det_out, int out_loc)
 {
-    const FillOne fill = [](yolo_ctx *c, const void *src, int h, int w, void *dst, int dt) { return launch_letterbox_chw((const float *)src, w, h, c->in_h, c->in_w, dst, dt, 8, c->stream); };
-    return forward_one(c, "yolo_forward_letterbox_chw", "letterbox", fill, image_chw, h, w, (size_t)h * w * 3 * 4, loc, det_out, out_loc);
+    const FillOne fill = [](yolo_ctx *c, const void *src, int h, int w, void *dst, int dt) { return launch_letterbox_chw((const float *)src, w, h, c->in_h, c->in_w, dst, dt, fill_stride(c), c->stream, c->in_c); };
+    return forward_one(c, "yolo_forward_letterbox_chw", "letterbox", fill, image_chw, h, w, (size_t)h * w * (c ? c->in_c : 3) * 4, loc, det_out, out_loc);
 }
 
 static int postprocess_impl(yolo_ctx *c, int n, float score_thr, float iou_thr, int max_out, int nms_mode, int select_mode,
@@ -756,9 +758,9 @@ static_assert(sizeof(ImgDesc) == sizeof(yolo_image_desc) && sizeof(yolo_image_de
 static int desc_check(yolo_ctx *c, int i, const yolo_image_desc &d, size_t bytes)
 {
     if (d.h < 1 || d.w < 1) return fail(c, YOLO_ERR_INVALID, "image %d: %d x %d", i, (int)d.h, (int)d.w);
-    const uint64_t need = (uint64_t)d.h * (uint64_t)d.w * 3u;
+    const uint64_t need = (uint64_t)d.h * (uint64_t)d.w * (uint64_t)c->in_c;
     if (d.offset > bytes || need > bytes - d.offset)
-        return fail(c, YOLO_ERR_INVALID, "image %d: %d x %d x 3 bytes at offset %llu end past the %zu-byte buffer", i, (int)d.h, (int)d.w, (unsigned long long)d.offset, bytes);
+        return fail(c, YOLO_ERR_INVALID, "image %d: %d x %d x %d bytes at offset %llu end past the %zu-byte buffer", i, (int)d.h, (int)d.w, c->in_c, (unsigned long long)d.offset, bytes);
     return YOLO_OK;
 }
 
@@ -770,10 +772,14 @@ static int images_check(yolo_ctx *c, const void *pixels, size_t bytes, const yol
     if (n < 1 || n > c->max_batch) return fail(c, YOLO_ERR_INVALID, "batch %d outside 1..%d", n, c->max_batch);
     if (!pixels || !descs) return fail(c, YOLO_ERR_INVALID, "pixels / descs == NULL");
     if (fit < YOLO_FIT_STRETCH || fit > YOLO_FIT_CENTER_CROP) return fail(c, YOLO_ERR_INVALID, "bad fit %d", fit);
-    if (bytes < 3 || bytes > 0xffffffffull) return fail(c, YOLO_ERR_INVALID, "packed buffer of %zu bytes (3 .. 2^32 - 1)", bytes);
+    // the cv2 fits restate cv2.resize of an RGB / BGR image: an image of another channel count has no such meaning
+    if (c->in_c != 3 && (fit == YOLO_FIT_CV2 || fit == YOLO_FIT_CV2_BGR))
+        return fail(c, YOLO_ERR_UNSUPPORTED, "yolo_*_images_u8 / yolo_detect_images_graph: %s is not served for a network of %d planes ([net] yolo_input=planes): it fits an RGB / BGR image", fit == YOLO_FIT_CV2 ? "YOLO_FIT_CV2" : "YOLO_FIT_CV2_BGR", c->in_c);
+    if (bytes < (size_t)c->in_c || bytes > 0xffffffffull) return fail(c, YOLO_ERR_INVALID, "packed buffer of %zu bytes (%d .. 2^32 - 1)", bytes, c->in_c);
     for (int i = 0; i < n; ++i) {
         const yolo_image_desc &d = descs[i];
         if (int r = desc_check(c, i, d, bytes)) return r;
+        if ((uint64_t)d.w * (uint64_t)c->in_c > 0xffffffffull) return fail(c, YOLO_ERR_INVALID, "image %d: a row of %d pixels of %d bytes does not fit a 32-bit pitch", i, (int)d.w, c->in_c);
         if (fit == YOLO_FIT_LETTERBOX) {
             int nw, nh; letterbox_dims(c->in_w, c->in_h, d.w, d.h, &nw, &nh);
             if (nw < 1 || nh < 1) return fail(c, YOLO_ERR_INVALID, "image %d: %d x %d letterboxes to less than one pixel", i, (int)d.h, (int)d.w);
@@ -807,7 +813,7 @@ static int images_step(yolo_ctx *c, const uint8_t *pixels, size_t bytes, const y
     c->lean_thr = score_thr;
     if (upload) HIPCK(c, hipMemcpyAsync(c->d_descs, descs, (size_t)n * sizeof(ImgDesc), hipMemcpyHostToDevice, c->stream));
     auto [dst, dt] = input_fill_dst(c);
-    HIPCK(c, launch_fit_images(pixels, bytes, c->d_descs, n, fit, c->in_h, c->in_w, dst, dt, 8, c->in_mul, c->in_add, c->stream));
+    HIPCK(c, launch_fit_images(pixels, bytes, c->d_descs, n, fit, c->in_h, c->in_w, dst, dt, fill_stride(c), c->in_mul, c->in_add, c->stream, c->in_c));
     HIPCK(c, input_filled(c, (size_t)n * c->in_h * c->in_w));
     return run_network(c, n, lean, fit);
 }
@@ -937,6 +943,7 @@ int yolo_detect_tiled_u8(yolo_ctx *c, const uint8_t *pixels, size_t bytes, const
     if (!c) return YOLO_ERR_INVALID;
     // ---- every refusal, before any launch ----
     if (int r = need_detector(c, who)) return r;
+    if (c->in_c != 3) return fail(c, YOLO_ERR_UNSUPPORTED, "%s: a network of %d planes ([net] yolo_input=planes) is not served: windows are cut from RGB images", who, c->in_c);
     if (!c->weights_loaded) return fail(c, YOLO_ERR_STATE, "%s before weights were loaded", who);
     static const char *const fit_names[] = {"YOLO_FIT_STRETCH", "YOLO_FIT_LETTERBOX", "YOLO_FIT_CV2", "YOLO_FIT_CV2_BGR", "YOLO_FIT_CENTER_CROP"};
     if (fit < YOLO_FIT_STRETCH || fit > YOLO_FIT_CENTER_CROP) return fail(c, YOLO_ERR_INVALID, "bad fit %d", fit);
@@ -1097,7 +1104,7 @@ int yolo_segment_images_u8(yolo_ctx *c, const uint8_t *pixels, const yolo_image_
     for (int i = 0; i < n; ++i) {
         if (descs[i].h < 1 || descs[i].w < 1) return fail(c, YOLO_ERR_INVALID, "image %d: %d x %d", i, (int)descs[i].h, (int)descs[i].w);
         const size_t px = (size_t)descs[i].h * (size_t)descs[i].w;
-        bytes = std::max(bytes, (size_t)descs[i].offset + px * 3);
+        bytes = std::max(bytes, (size_t)descs[i].offset + px * c->in_c);
         off[i] = label_offsets ? label_offsets[i] : total;
         total = std::max(total, (size_t)off[i] + px);
     }

@@ -219,6 +219,21 @@ def with_vector_input(text):
     return "\n".join(out) + "\n"
 
 
+def with_planes_input(text):
+    """A darknet cfg of an image network whose channel count is not three (grey, RGB-D, multispectral, the go board) with the key that declares
+    it here, `yolo_input=planes`, added to its [net] section; a cfg that has a `yolo_input` key, three channels or no positive image size is
+    returned as it is.  darknet ignores the key, so the result still loads there."""
+    net = parse_cfg(text)[0]
+    if "yolo_input" in net or int(net.get("channels", 3)) == 3 or int(net.get("height", 0)) <= 0 or int(net.get("width", 0)) <= 0:
+        return text
+    out, done = [], False
+    for line in text.splitlines():
+        out.append(line)
+        if not done and line.strip().startswith("["):
+            out.append("yolo_input=planes"); done = True
+    return "\n".join(out) + "\n"
+
+
 def layer_shapes(secs):
     """[(type, H, W, C_out, C_in)] per layer, darknet shape rules (DN/parser.c:730-875)."""
     net = secs[0]

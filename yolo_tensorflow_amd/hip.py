@@ -37,7 +37,7 @@ EXPORTS = [
     "yolo_create", "yolo_destroy", "yolo_last_error", "yolo_load_darknet_weights", "yolo_set_weights",
     "yolo_weights_count", "yolo_set_act_scales", "yolo_export", "yolo_create_from_file", "yolo_input_size", "yolo_num_rows", "yolo_num_attrs", "yolo_num_layers", "yolo_head_geometry", "yolo_head_geometry_hw", "yolo_op_decode_hw", "yolo_op_resize_u8_hw",
     "yolo_conv_flops", "yolo_conv_bytes", "yolo_forward", "yolo_forward_image_u8", "yolo_postprocess",
-    "yolo_detect", "yolo_detect_graph", "yolo_synchronize", "yolo_layer_output", "yolo_time_forward", "yolo_time_layers",
+    "yolo_detect", "yolo_detect_graph", "yolo_synchronize", "yolo_layer_output", "yolo_staged_input", "yolo_time_forward", "yolo_time_layers",
     "yolo_autotune", "yolo_get_tile_configs", "yolo_set_tile_configs", "yolo_resolved_tile_configs", "yolo_op_conv2d", "yolo_op_conv_num_cfgs", "yolo_op_upsample2x", "yolo_op_reorg",
     "yolo_darknet_boxes", "yolo_last_layer_size", "yolo_last_layer_output", "yolo_op_letterbox",
     "yolo_op_maxpool", "yolo_op_resize_u8", "yolo_op_detections_boxes", "yolo_op_nms_detections", "yolo_forward_letterbox_chw", "yolo_op_decode", "yolo_op_postprocess",
@@ -105,6 +105,7 @@ def load_library():
     l.yolo_detect.argtypes = [P, P, I, I, I, F, F, F, I, I, I, P, P, I]
     l.yolo_detect_graph.argtypes = [P, P, I, I, F, F, F, I, I, I, P, P]
     l.yolo_layer_output.argtypes = [P, I, I, P, C.c_size_t, C.POINTER(I)]
+    l.yolo_staged_input.argtypes = [P, I, P, C.c_size_t, C.POINTER(I)]
     l.yolo_time_forward.argtypes = [P, I, I, FP, FP]
     l.yolo_time_layers.argtypes = [P, I, I, FP]
     l.yolo_autotune.argtypes = [P, I, I]
@@ -221,14 +222,23 @@ _warned_legacy = False
 HIP_STREAM_LEGACY = 1     # hipStreamLegacy: the explicit handle of the legacy NULL stream (hip_runtime_api.h)
 
 
-def pack_images(images):
-    """A list of uint8 RGB [h, w, 3] arrays of any sizes -> (packed uint8 buffer, DESC_DTYPE descriptors): the images back to back in
-    list order, each C-contiguous, offset = bytes of the images before it.  Pure host code; what yolo_*_images_* read."""
+class ChannelError(YoloError, ValueError):
+    """An image whose channel count is not the network's."""
+
+
+def pack_images(images, channels=3):
+    """A list of uint8 [h, w, channels] arrays of any sizes (RGB by default; a [h, w] array is one plane) -> (packed uint8 buffer,
+    DESC_DTYPE descriptors): the images back to back in list order, each C-contiguous, offset = bytes of the images before it.  Pure
+    host code; what yolo_*_images_* read.  ChannelError (a ValueError) for an image of another channel count."""
     arrs = []
     for i, im in enumerate(images):
         a = np.ascontiguousarray(im)
-        if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.shape[0] < 1 or a.shape[1] < 1:
-            raise YoloError("image %d: need a uint8 [h, w, 3] array, got %s %s" % (i, a.dtype, a.shape))
+        if a.ndim == 2 and channels != 3:
+            a = a[:, :, None]
+        if a.dtype == np.uint8 and a.ndim == 3 and a.shape[2] != channels and channels != 3:
+            raise ChannelError("image %d: %d channels, the network reads %d" % (i, a.shape[2], channels))
+        if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != channels or a.shape[0] < 1 or a.shape[1] < 1:
+            raise YoloError("image %d: need a uint8 [h, w, %d] array, got %s %s" % (i, channels, a.dtype, a.shape))
         arrs.append(a)
     if not arrs:
         raise YoloError("pack_images: no images")
@@ -319,6 +329,7 @@ class Engine:
         self.lib.yolo_input_size(self.ctx, C.byref(h), C.byref(w), C.byref(ch))
         self.size = h.value                        # the input's height; input_hw: both sides
         self.input_hw = (h.value, w.value)
+        self.input_channels = ch.value             # 3, or the N of [net] yolo_input=planes (a vector-input network: its inputs=)
         self.rows = self.lib.yolo_num_rows(self.ctx)
         self.attrs = self.lib.yolo_num_attrs(self.ctx)
         self.num_layers = self.lib.yolo_num_layers(self.ctx)
@@ -341,6 +352,7 @@ class Engine:
         self.lib.yolo_input_size(self.ctx, C.byref(h), C.byref(w), C.byref(ch))
         self.size = h.value
         self.input_hw = (h.value, w.value)
+        self.input_channels = ch.value
         self.rows = self.lib.yolo_num_rows(self.ctx); self.attrs = self.lib.yolo_num_attrs(self.ctx)
         self.num_layers = self.lib.yolo_num_layers(self.ctx); self.max_batch = max_batch; self.dtype = None
         self._own_stream = not stream
@@ -395,9 +407,22 @@ class Engine:
         self._check(self.lib.yolo_set_weights(self.ctx, flat.ctypes.data_as(C.POINTER(C.c_float)), flat.size), "yolo_set_weights")
 
     # ---- hot path ----
+    def _check_channels(self, images, fmt=None):
+        """[n, H, W, C] (IMG_F32_CHW: [n, C, H, W]) arrays of a network of another channel count: ChannelError, naming both counts"""
+        shape = getattr(images, "shape", None)
+        if shape is None or len(shape) != 4 or self.vector_inputs:          # (a vector-input network: the library refuses the call by name)
+            return
+        got = int(shape[1] if fmt == IMG_F32_CHW else shape[3])
+        if got != self.input_channels:
+            raise ChannelError("images of %d channels, the network reads %d" % (got, self.input_channels))
+
+    def _image_channels(self):
+        return 3 if self.vector_inputs else self.input_channels
+
     def forward(self, images, scale=1.0 / 255.0, want_detections=True, n=None, fmt=None, out=None):
-        """images: uint8 or float32 [n,in_h,in_w,3] (input_hw; numpy, torch host/device tensor, or raw device pointer with
+        """images: uint8 or float32 [n,in_h,in_w,C] (input_hw, input_channels; numpy, torch host/device tensor, or raw device pointer with
         n and fmt given).  Returns the decoded tensor [n, rows, attrs] (numpy) unless out/want_detections say otherwise."""
+        self._check_channels(images, fmt)
         p, loc = _ptr(images)
         # a device uint8 image may be read IN PLACE by the fused stem, also by a later time_forward / time_layers / autotune pass
         # (yolo_hip.h, yolo_forward): keep it alive until the next image replaces it (ADVICE r04)
@@ -418,8 +443,12 @@ class Engine:
         return det
 
     def forward_image(self, image_u8):
-        """One uint8 RGB image of any size: /255 + legacy bilinear stretch on the device, then forward."""
+        """One uint8 image of any size, [h, w, input_channels] (RGB; one plane: [h, w] too): /255 + legacy bilinear stretch on the device, then forward."""
         image_u8 = np.ascontiguousarray(image_u8, dtype=np.uint8)
+        if image_u8.ndim == 2 and self._image_channels() != 3:
+            image_u8 = image_u8[:, :, None]
+        if image_u8.ndim != 3 or image_u8.shape[2] != self._image_channels():
+            raise ChannelError("forward_image: an image of shape %s, the network reads %d channels" % (image_u8.shape, self.input_channels))
         det = np.empty((1, self.rows, self.attrs), dtype=np.float32)
         self._check(self.lib.yolo_forward_image_u8(self.ctx, image_u8.ctypes.data, image_u8.shape[0], image_u8.shape[1],
                                                    HOST, det.ctypes.data, HOST), "yolo_forward_image_u8")
@@ -529,14 +558,15 @@ class Engine:
         if isinstance(images, tuple):
             buf, descs = images
         else:
-            buf, descs = pack_images(images)
+            buf, descs = pack_images(images, self._image_channels())
         descs = _descs(descs)
         p, loc = _ptr(buf)
         nbytes = int(buf.numel()) if hasattr(buf, "numel") else int(buf.nbytes)
         return buf, descs, p, loc, nbytes
 
     def forward_images(self, images, fit=FIT_STRETCH, want_detections=True):
-        """A list of uint8 RGB [h, w, 3] images of any sizes (or a (buffer, descs) pair from pack_images, the buffer on the host or
+        """A list of uint8 RGB [h, w, 3] images of any sizes -- a network of planes ([net] yolo_input=planes): [h, w, input_channels], one plane also
+        [h, w]; ChannelError for another count -- (or a (buffer, descs) pair from pack_images, the buffer on the host or
         the device) -> fitted on the device in one launch (`fit`), then forward.  Returns the decoded tensor [n, rows, attrs]."""
         buf, descs, p, loc, nbytes = self._packed(images)
         n = len(descs)
@@ -611,6 +641,7 @@ class Engine:
         """images as for `forward`.  top_k > 0: -> (classes int32 [n, top_k], probs float32 [n, top_k]), probability descending, equal
         probabilities by ascending class -- selected on the device, only these records are copied; top_k == 0: -> the whole
         probability matrix float32 [n, num_classes]."""
+        self._check_channels(images)
         p, loc = _ptr(images)
         self._last_image = images if loc == DEVICE else None
         self._order_after_producer(images)
@@ -622,7 +653,7 @@ class Engine:
         return (cls, probs) if top_k else probs
 
     def classify_images(self, images, fit=FIT_STRETCH, top_k=5):
-        """`classify` over a list of uint8 RGB [h, w, 3] images of any sizes (or a (buffer, descs) pair from pack_images), fitted on
+        """`classify` over a list of uint8 [h, w, input_channels] images of any sizes, RGB unless the cfg says otherwise (or a (buffer, descs) pair from pack_images), fitted on
         the device in one launch (yolo_classify_images_u8)."""
         buf, descs, p, loc, nbytes = self._packed(images)
         n = len(descs)
@@ -656,7 +687,7 @@ class Engine:
     def segment_images(self, images, fit=FIT_LETTERBOX, thresh=0.5):
         """images: a list of uint8 RGB [h_i, w_i, 3] arrays of any sizes -> a list of [h_i, w_i] uint8 label arrays, each at its image's own
         size: one fit launch, one forward, one label kernel (yolo_segment_images_u8; include/yolo_hip.h states the pixel mapping)."""
-        buf, descs = pack_images(images)
+        buf, descs = pack_images(images, self._image_channels())
         d = _descs(descs)
         sizes = [int(q["h"]) * int(q["w"]) for q in d]
         labels = np.empty(sum(sizes), dtype=np.uint8)
@@ -762,6 +793,15 @@ class Engine:
         self._check(self.lib.yolo_layer_output(self.ctx, index, n, None, 0, dims), "yolo_layer_output")
         out = np.empty((n, dims[0], dims[1], dims[2]), dtype=np.float32)
         self._check(self.lib.yolo_layer_output(self.ctx, index, n, out.ctypes.data, out.size, dims), "yolo_layer_output")
+        return out
+
+    def staged_input(self, n):
+        """The staged network input of images 0..n-1 of the last forward, every stored channel of a pixel: [n, H, W, S] float32, S = 8 for an
+        RGB network, roundup(input_channels, 8) for a network of planes (yolo_staged_input)."""
+        dims = (C.c_int * 3)()
+        self._check(self.lib.yolo_staged_input(self.ctx, n, None, 0, dims), "yolo_staged_input")
+        out = np.empty((n, dims[0], dims[1], dims[2]), dtype=np.float32)
+        self._check(self.lib.yolo_staged_input(self.ctx, n, out.ctypes.data, out.size, dims), "yolo_staged_input")
         return out
 
     def conv_flops(self):

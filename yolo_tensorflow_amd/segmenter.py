@@ -16,7 +16,7 @@ class Segmenter:
         """cfg: a cfg file path or cfg text with `yolo_output=map` in its [net] section.  weights: a darknet `.weights` file or a flat
         float32 parameter stream; None loads darknet_io's seeded synthetic parameters (`seed`).  fit: "letterbox" (darknet's
         letterbox_image) or "stretch", or a hip.FIT_* code."""
-        text = cfg if "[net]" in cfg or "[network]" in cfg else IO.cfg_text(cfg)
+        text = IO.with_planes_input(cfg if "[net]" in cfg or "[network]" in cfg else IO.cfg_text(cfg))          # ([net] channels != 3: the key is added here)
         self.engine = hip.Engine(text, max_batch=max_batch, dtype=dtype, semantics=hip.SEM_DARKNET, device=device)
         try:
             self.map_hwc = self.engine.map_geometry()
@@ -34,7 +34,7 @@ class Segmenter:
         self.num_classes = self.map_hwc[2]
 
     def predict_from_images(self, images):
-        """images: a list of RGB uint8 [h, w, 3] arrays of any sizes -> a list of [map_h, map_w, c] float32 maps (of the fitted input)."""
+        """images: a list of uint8 [h, w, C] arrays of any sizes (RGB; a network of C planes: [h, w, C], one plane also [h, w]) -> a list of [map_h, map_w, c] float32 maps (of the fitted input)."""
         out = []
         for lo in range(0, len(images), self.max_batch):
             chunk = images[lo:lo + self.max_batch]
