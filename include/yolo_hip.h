@@ -332,6 +332,23 @@ int yolo_get_state(yolo_ctx *ctx, int k, int stream, float *out, size_t out_floa
 int yolo_set_state(yolo_ctx *ctx, int k, int stream, const float *in, size_t in_floats);
 int yolo_reset_state(yolo_ctx *ctx, int stream);                 /* darknet's reset_network_state(net, b); stream < 0: every stream */
 
+/* ---- frame-averaged detection on video streams (darknet's `detector demo`: remember_network + avg_predictions) -----
+ * frames = K in 1 .. 8; 1 (the default) is off.  With K >= 2 every yolo_forward* / yolo_detect* call with n images is one time
+ * step of the streams 0 .. n-1 (batch index b = stream b; the streams n .. max_batch-1 are untouched): per [yolo] / [region]
+ * head the step writes the layer's activated output -- darknet's l.output: logistic on x, y, objectness and a [yolo] head's
+ * classes, a [region] head's class softmax, w and h raw -- into slot pos[stream] of a ring of K slots, forms
+ * avg = 0; avg = avg + (float)(1. / K) * slot[j] for j = 0 .. K-1 (slot order, fp32), decodes the boxes from avg, and then
+ * moves pos[stream] on by one.  Everything behind the decode (scores, NMS, yolo_postprocess*, yolo_darknet_boxes*) reads the
+ * averaged rows.  The slots are ZERO when the setting is made and after yolo_reset_state, so a stream's first K-1 steps are
+ * attenuated by the empty slots, exactly as in darknet's demo (which callocs them).  yolo_detect* run the full decode while
+ * K >= 2.  Changing K empties the ring and drops the captured steps; yolo_reset_state(ctx, stream) also empties that stream's
+ * slots and position.  The timing calls and yolo_autotune are steps of no stream.  The setting is no part of the plan or of an
+ * export artifact.  Refused: K outside 1 .. 8; a classifier, map or vector-input network; a [detection] (YOLOv1) head; a
+ * [region] head with a softmax tree; more than 128 attributes per box; yolo_detect_tiled_u8 while K >= 2.
+ * Device memory: (K + 1) * max_batch * rows * attrs * 4 bytes. */
+int yolo_set_frame_average(yolo_ctx *ctx, int frames);
+int yolo_frame_average(const yolo_ctx *ctx);                     /* the current K */
+
 /* ---- vector-input networks: char-rnn ([net] yolo_input=vector, inputs=N) ------------------------------------------
  * A cfg whose [net] section says yolo_input=vector and inputs=N (1 .. 2^24, no height / width) reads one row of N values per
  * stream instead of an image; darknet ignores the key, so the same cfg loads there.  Served sections: [connected], [rnn], [gru],

@@ -42,6 +42,10 @@ Runs only in the build container (it reads /root/reference and oracle/_ref); the
                     [crop] and [normalization]: a classifier that opens with a [crop] and has two LRN layers (three images, every layer), eleven
                     stand-alone [normalization] shapes behind a 1x1 conv, four [crop] networks, and six uint8 images through the reference's
                     resize_min + crop_image (the classifier's validation preprocessing); fixed member dates
+  frame_average_cases.npz   (--frame-average)
+                    darknet's `detector demo` averaging (DN/examples/demo.c remember_network + avg_predictions) on three small detectors: per case
+                    cfg, weight seed, K, K + 2 uint8 frames, every [yolo] / [region] layer's l.output after each frame, and get_network_boxes of
+                    the compiled reference over the mean of the last K outputs (written back into l.output) after every step; fixed member dates
   yolov3_bn_real.npz / yolov2_bn_real.npz
                      the COMPLETE batch-norm vectors (beta, gamma, rolling mean, rolling variance) of every
                      batch-normalised conv of yolov3.weights / yolov2.weights, and the first l.n filter
@@ -1502,6 +1506,87 @@ def gen_planes(thresh=0.15):
     print("planes_fit_cases", len(data), "arrays", os.path.getsize(path), "bytes")
 
 
+def frame_average_cfgs():
+    """(name, cfg text, classes, K): a yolov3-tiny-shaped net 96 high x 128 wide with 7 classes (36 head channels: 3 x 4 and 6 x 8 cells), stock yolov3-tiny and
+    yolov2-tiny-voc at 96 x 96"""
+    from yolo_tensorflow_amd import darknet_io as IO
+    tiny = IO.cfg_text("yolov3-tiny")
+    rect = IO.with_input_size(tiny.replace("classes=80", "classes=7").replace("filters=255", "filters=36"), (96, 128))
+    return [("rect7", rect, 7, 3), ("tiny80", IO.with_input_size(tiny, 96), 80, 2), ("voc", IO.with_input_size(IO.cfg_text("yolov2-tiny-voc"), 96), 20, 5)]
+
+
+def frame_average_frames(seed, count, h, w):
+    """a fixed base image plus seeded noise of sigma 0.25 (of the 0 .. 1 range) per frame, uint8.  The noise is drawn per 8 x 8 block: white noise is
+    averaged away by the first convs and pools and would move the heads' outputs by a few hundredths only"""
+    rng = np.random.default_rng(seed)
+    base = rng.random((h, w, 3))
+    noise = lambda: np.repeat(np.repeat(rng.normal(0, 0.25, (h // 8, w // 8, 3)), 8, 0), 8, 1)
+    return np.stack([np.clip(np.rint((base + noise()) * 255), 0, 255).astype(np.uint8) for _ in range(count)])
+
+
+def gen_frame_average(weight_seed=21, src_wh=(200, 120)):
+    """demo.c's loop restated around the compiled reference: predict, remember every detection layer's l.output in ring slot (step % K), fill l.output with
+    avg = 0; avg += (float)(1. / K) * slot[j] in slot order (axpy_cpu, fp32), get_network_boxes at thresh 0 for relative 1 and 0 of a 200 x 120 source image."""
+    import ctypes as C
+    from oracle import darknet_ref as DR
+    from yolo_tensorflow_amd import darknet_io as IO
+    data = {"names": np.array([c[0] for c in frame_average_cfgs()])}
+    l = DR.lib()
+    for name, cfg, classes, K in frame_average_cfgs():
+        secs = IO.parse_cfg(cfg)
+        flat = IO.synth_weights(secs, weight_seed, obj_bias=0.0)
+        net = DR.RefNet(cfg, flat)
+        heads = [i for i, s in enumerate(secs[1:]) if s["type"] in ("yolo", "region")]
+        steps = K + 2
+        frames = frame_average_frames(1000 + K, steps, net.h, net.w)
+        ring = {i: np.zeros((K, l.ref_layer_outputs(net.net, i)), np.float32) for i in heads}
+        alpha = np.float32(1. / K)
+        data[name + "_cfg"] = np.array(cfg); data[name + "_weight_seed"] = np.array(weight_seed); data[name + "_K"] = np.array(K)
+        data[name + "_frames"] = frames; data[name + "_classes"] = np.array(classes); data[name + "_src_wh"] = np.array(src_wh)
+        # (float)netw / new_w and (float)neth / new_h as THIS build of the reference evaluates them in correct_*_boxes: -Ofast turns the float division
+        # into a reciprocal approximation (128 / 128 comes out as 0x3f7fffff) and folds `*= w` into the same factor, so the factors are recorded, read off a unit box
+        probe = (DR.DETECTION * 1)(); probe[0].bbox = DR.BOX(0.5, 0.5, 1.0, 1.0)
+        fn = l.correct_yolo_boxes if secs[1 + heads[0]]["type"] == "yolo" else l.correct_region_boxes
+        fn.argtypes = [C.POINTER(DR.DETECTION)] + [C.c_int] * 6; fn.restype = None
+        scale = np.zeros((2, 2), np.float32)          # [relative]: what a box's (w, h) are multiplied by in all (relative = 0: the source size included, as one factor)
+        for relative in (0, 1):
+            probe[0].bbox = DR.BOX(0.5, 0.5, 1.0, 1.0)
+            fn(probe, 1, src_wh[0], src_wh[1], net.w, net.h, relative)
+            scale[relative] = (probe[0].bbox.w, probe[0].bbox.h)
+        data[name + "_wh_scale"] = scale
+        for t in range(steps):
+            net.predict(frames[t].astype(np.float32) / np.float32(255))
+            for k, i in enumerate(heads):
+                out = np.ctypeslib.as_array(l.ref_layer_output(net.net, i), shape=(ring[i].shape[1],))      # a view of l.output: writable
+                ring[i][t % K] = out
+                data["%s_out_t%d_h%d" % (name, t, k)] = out.copy()
+                avg = np.zeros_like(out)
+                for j in range(K):
+                    avg = avg + alpha * ring[i][j]
+                out[:] = avg
+            for relative in (1, 0):
+                num = C.c_int(0)
+                dets = l.get_network_boxes(net.net, src_wh[0], src_wh[1], 0.0, .5, None, relative, C.byref(num))
+                n = num.value
+                bb = np.zeros((n, 4), np.float32); obj = np.zeros(n, np.float32); pr = np.zeros((n, classes), np.float32)
+                for d in range(n):
+                    bb[d] = (dets[d].bbox.x, dets[d].bbox.y, dets[d].bbox.w, dets[d].bbox.h); obj[d] = dets[d].objectness
+                    pr[d] = np.ctypeslib.as_array(dets[d].prob, shape=(classes,))
+                l.free_detections(dets, n)
+                data["%s_bbox_t%d_rel%d" % (name, t, relative)] = bb
+                if relative:
+                    data["%s_obj_t%d" % (name, t)] = obj; data["%s_prob_t%d" % (name, t)] = pr
+            # the gap the GPU test needs at every step: more than 20 boxes above a hole of 8e-3 in the reference's objectness
+            cand = np.sort(obj)[::-1]
+            gaps = [k for k in range(20, len(cand) - 1) if cand[k] - cand[k + 1] > 8e-3]
+            print("  %s step %d: %d boxes, objectness %.3f .. %.3f, first gap after %s" % (name, t, n, cand[-1], cand[0], gaps[:1]))
+            assert gaps, "no objectness gap wider than 8e-3 below the 21st box"
+        net.close()
+    path = os.path.join(OUT, "frame_average_cases.npz")
+    save_npz_reproducibly(path, data)
+    print("frame_average_cases", len(data), "arrays", os.path.getsize(path), "bytes")
+
+
 def gen_rect():
     gen_mini_rect("mini_v3_rect", MINI_V3, 4, 64, 96, letterbox=True)
     gen_mini_rect("mini_v2_rect", MINI_V2, 5, 96, 64)
@@ -1536,6 +1621,8 @@ if __name__ == "__main__":
         gen_mini_char_rnn(); sys.exit(0)
     if sys.argv[1:] == ["planes"]:
         gen_planes(); sys.exit(0)
+    if sys.argv[1:] == ["--frame-average"]:
+        gen_frame_average(); sys.exit(0)
     stub_modules()
     gen_nms_v3()
     gen_v2_post()
@@ -1554,6 +1641,7 @@ if __name__ == "__main__":
     gen_lrn_crop()
     gen_mini_char_rnn()
     gen_planes()
+    gen_frame_average()
     gen_bn_real()
     gen_known_answers()
     gen_darknet_py_symbols()

@@ -546,14 +546,21 @@ struct DecodeArgs {
 // twins; on a gh x gw grid DN/region_layer.c get_region_box): p the box's 5 + classes raw values, o (cx, cy, w, h, objectness), x and w
 // normalised by the grid's columns gw, y and h by its rows gh
 __device__ __forceinline__ float region_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
-__device__ __forceinline__ float region_box_attr(int k, const float *p, int cell, int gw, int gh, const float *anchor_wh)
+// In two steps: region_act, the value darknet's [region] layer holds in l.output for k < 5 (logistic on x, y and objectness, w and h raw), and
+// region_box_form, the box formula on such a value; the frame-averaged decode (k_decode_avg<true>) takes the mean between the two
+__device__ __forceinline__ float region_act(int k, float x) { return (k == 2 || k == 3) ? x : region_sigmoid(x); }
+__device__ __forceinline__ float region_box_form(int k, float v, int cell, int gw, int gh, const float *anchor_wh)
 {
     const float GW = (float)gw, GH = (float)gh;
-    if (k == 0) return ((float)(cell % gw) + region_sigmoid(p[0])) / GW;
-    if (k == 1) return ((float)(cell / gw) + region_sigmoid(p[1])) / GH;
-    if (k == 2) return (anchor_wh[0] * expf(p[2])) / GW;
-    if (k == 3) return (anchor_wh[1] * expf(p[3])) / GH;
-    return region_sigmoid(p[4]);
+    if (k == 0) return ((float)(cell % gw) + v) / GW;
+    if (k == 1) return ((float)(cell / gw) + v) / GH;
+    if (k == 2) return (anchor_wh[0] * expf(v)) / GW;
+    if (k == 3) return (anchor_wh[1] * expf(v)) / GH;
+    return v;
+}
+__device__ __forceinline__ float region_box_attr(int k, const float *p, int cell, int gw, int gh, const float *anchor_wh)
+{
+    return region_box_form(k, region_act(k, p[k < 4 ? k : 4]), cell, gw, gh, anchor_wh);
 }
 // Attribute k < 5 of a box in darknet's layer-output layout (DN/yolo_layer.c:143-152, DN/region_layer.c:163-173): the logistic,
 // 1. / (1. + exp(-x)) in double like DN/activations.h:38, on x, y and objectness; w and h stay raw
@@ -575,6 +582,18 @@ struct LeanArgs {
 hipError_t launch_decode_lean(const LeanArgs &a, float *scores, int *labels, hipStream_t s);
 // scores/labels (nullable): per-row max_k(obj*cls_k) and its first argmax, written alongside the decode
 hipError_t launch_decode(const DecodeArgs &a, float *scores, int *labels, hipStream_t s);
+// Frame averaging ("Frame averaging"; DN/examples/demo.c remember_network + avg_predictions): a ring of the last K ACTIVATED head tensors per
+// stream -- what darknet holds in l.output: logistic on x, y, objectness (and a [yolo] head's classes), a [region] head's class softmax, w and h raw.
+// ring [K][max_batch][E] fp32, E = sum over the heads of cells * na * (5 + classes), a head's part at `off` in its own [cell][anchor * attrs] order;
+// pos [max_batch]: the slot the stream's next step writes.  Both live in device memory: a captured step replays with these arguments.
+struct RingArgs { float *ring; const int *pos; int K, max_batch; size_t E, off; float alpha; };      // alpha = (float)(1. / K)
+// launch_decode's full form over the mean: per (stream, cell) one wave writes the activated values to slot pos[stream], forms avg = sum over the slots
+// j = 0 .. K - 1 (slot order) of alpha * slot[j], and applies the box arithmetic to it.  a.det, scores, labels non-null; a [yolo] head or a
+// [region] head without a tree, 5 + classes <= 128, raw_stride >= na * (5 + classes).  The positions are not advanced: launch_ring_advance, once all heads of the step are decoded
+hipError_t launch_decode_avg(const DecodeArgs &a, const RingArgs &g, float *scores, int *labels, hipStream_t s);
+hipError_t launch_ring_advance(int *pos, int n, int K, hipStream_t s);      // pos[b] = (pos[b] + 1) % K for the streams b < n
+// keep[b][e] <-> ring[pos[b]][b][e] for every stream: the one slot a step writes while the positions stand still (the timing entry points)
+hipError_t launch_ring_slot_move(float *ring, float *keep, const int *pos, int max_batch, size_t E, int restore, hipStream_t s);
 // YOLOv1 [detection] head (row D1): raw [n][raw_stride] fp32 = [cls S*S*C | conf S*S*B | box S*S*B*4] -> det rows (cx, cy, w, h, conf, cls...)
 hipError_t launch_decode_v1(const float *raw, int raw_stride, int n, int side, int num, int classes, int sqr, float *det, int rows_total,
                             int row_off, float *scores, int *labels, hipStream_t s);

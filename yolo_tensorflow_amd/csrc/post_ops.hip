@@ -30,11 +30,18 @@ __device__ __forceinline__ float sigmoid_fast(float x)
 // stride on the host, (GW, GH) grid columns and rows, (SX, SY) the strides along x and y: x and w take GW / SX, y and h GH / SY (one value
 // each on a square network).  mode 0 divides by G, the pixel mode multiplies by S: not interchangeable without contraction, and the
 // operand order is the reference's.
-__device__ __forceinline__ float yolo_box_attr(int k, float x, int cx, int cy, const float *anchor, float GW, float GH, float SX, float SY, int mode)
+// It is written in two steps: yolo_box_act, the value darknet's [yolo] layer holds in l.output (logistic on x and y, w and h raw), and yolo_box_form, the
+// box formula on such a value.  The frame-averaged decode (k_decode_avg<false>) takes the mean of activated values between the two.
+__device__ __forceinline__ float yolo_box_act(int k, float x) { return k < 2 ? sigmoidf_(x) : x; }
+__device__ __forceinline__ float yolo_box_form(int k, float v, int cx, int cy, const float *anchor, float GW, float GH, float SX, float SY, int mode)
 {
-    const float t = k < 2 ? sigmoidf_(x) + (float)(k == 0 ? cx : cy) : expf(x) * anchor[k - 2];
+    const float t = k < 2 ? v + (float)(k == 0 ? cx : cy) : expf(v) * anchor[k - 2];
     const float G = (k & 1) ? GH : GW, S = (k & 1) ? SY : SX;
     return mode == 0 ? t / G : t * S;
+}
+__device__ __forceinline__ float yolo_box_attr(int k, float x, int cx, int cy, const float *anchor, float GW, float GH, float SX, float SY, int mode)
+{
+    return yolo_box_form(k, yolo_box_act(k, x), cx, cy, anchor, GW, GH, SX, SY, mode);
 }
 
 // ---- D3 (+S): `_detection_layer` (V3/yolo_v3.py:111-159) / `_ratio_detection_layer` (V3/YOLOV3.py:168-238),
@@ -416,6 +423,112 @@ hipError_t launch_decode(const DecodeArgs &a, float *scores, int *labels, hipStr
         size_t blocks = (total + 15) / 16; if (blocks > (1u << 20)) blocks = 1u << 20;   // one step per wave: latency-bound otherwise
         hipLaunchKernelGGL(k_decode_yolo, dim3((unsigned)blocks), dim3(256), 0, s, a, scores, labels);
     }
+    return hipGetLastError();
+}
+
+// ---- Frame averaging (DN/examples/demo.c remember_network + avg_predictions; RingArgs, kernels.h): ring store + mean + decode + row score of
+//      one head in one launch.  One wave per (stream, cell), and nobody else touches that cell's ring entries: the wave takes the cell's
+//      anchors in turn, lanes along the 5 + C attributes of a box (two passes: attrs <= 128), so the raw tensor, every ring slot and the
+//      decoded rows are all read and written as contiguous runs of 5 + C floats.  Per element: the raw value is read once, its activated
+//      value -- darknet's l.output: yolo_box_act / sigmoid_fast exactly as k_decode_yolo_cell forms them, region_act and the class softmax
+//      as k_decode_region's -- goes to slot pos[stream], the other K - 1 slots are read (all loads issued before the first use), and
+//      avg = 0; avg = avg + alpha * slot[j] for j = 0 .. K - 1 in SLOT order, uncontracted, as avg_predictions adds them.  The box formula
+//      is applied to avg; objectness and classes are avg itself.  Score and label: k_score_rows' rule (first maximum of obj * class). ----
+template <bool REGION>
+__global__ __launch_bounds__(256) void k_decode_avg(const DecodeArgs a, const RingArgs g, float *scores, int *labels)
+{
+    const int attrs = 5 + a.classes, nch = a.na * attrs;
+    const int lane = threadIdx.x & 63;
+    const long wave = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const long nwaves = ((long)gridDim.x * blockDim.x) >> 6;
+    const int gg = a.gh * a.gw;
+    const long total = (long)a.n * gg;
+    const float GW = (float)a.gw, GH = (float)a.gh, SX = (float)(a.img_w / a.gw), SY = (float)(a.img_h / a.gh);
+    const size_t slot = (size_t)g.max_batch * g.E;          // floats between two slots of one element
+    for (long p = wave; p < total; p += nwaves) {
+        const unsigned up = (unsigned)__builtin_amdgcn_readfirstlane((int)p);
+        const int b = (int)(up / (unsigned)gg), cell = (int)(up - (unsigned)b * gg);
+        const int cy = cell / a.gw, cx = cell - cy * a.gw;
+        const int pos = g.pos[b];                           // wave-uniform, 0 .. K - 1; advanced by a later launch
+        const float *src = a.raw + (size_t)up * a.raw_stride;
+        float *mine = g.ring + (size_t)b * g.E + g.off + (size_t)cell * nch;      // this cell in slot 0
+        const size_t row0 = (size_t)b * a.rows_total + a.row_off + (size_t)cell * a.na;
+        for (int an = 0; an < a.na; ++an) {
+            float x[2], old[2][8], v[2];
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                const int k = lane + 64 * t;
+                x[t] = k < attrs ? src[an * attrs + k] : 0.f;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) old[t][j] = (j < g.K && j != pos && k < attrs) ? mine[j * slot + an * attrs + k] : 0.f;
+            }
+            float e[2] = {0.f, 0.f}, sum = 1.f;
+            if (REGION) {                                   // softmax over the box's classes (DN/blas.c:305-321 at temperature 1)
+                float mx = -INFINITY;
+#pragma unroll
+                for (int t = 0; t < 2; ++t) { const int k = lane + 64 * t; if (k >= 5 && k < attrs) mx = fmaxf(mx, x[t]); }
+                mx = wave_max(mx);
+#pragma unroll
+                for (int t = 0; t < 2; ++t) { const int k = lane + 64 * t; e[t] = (k >= 5 && k < attrs) ? expf(x[t] - mx) : 0.f; }
+                sum = wave_sum(e[0] + e[1]);
+            }
+            float *dst = a.det + (row0 + an) * attrs;
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                const int k = lane + 64 * t;
+                float act;
+                if (REGION) act = k < 5 ? region_act(k, x[t]) : e[t] / sum;
+                else act = k < 4 ? yolo_box_act(k, x[t]) : sigmoid_fast(x[t]);
+                if (k < attrs) mine[pos * slot + an * attrs + k] = act;
+                float avg = 0.f;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) if (j < g.K) avg = avg + g.alpha * (j == pos ? act : old[t][j]);
+                if (k >= 4) v[t] = avg;
+                else if (REGION) v[t] = region_box_form(k, avg, cell, a.gw, a.gh, a.anchors + 2 * an);
+                else v[t] = yolo_box_form(k, avg, cx, cy, a.anchors + 2 * an, GW, GH, SX, SY, a.mode);
+                if (k < attrs) dst[k] = v[t];
+            }
+            const float obj = __shfl(v[0], 4);
+            float best = -INFINITY; int bi = 0x7fffffff;
+            if (lane >= 5 && lane < attrs) { best = obj * v[0]; bi = lane - 5; }
+            if (lane + 64 < attrs) first_max(best, bi, obj * v[1], lane + 59);
+            wave_argmax(best, bi);
+            if (lane == 0) { scores[row0 + an] = best; labels[row0 + an] = bi; }
+        }
+    }
+}
+hipError_t launch_decode_avg(const DecodeArgs &a, const RingArgs &g, float *scores, int *labels, hipStream_t s)
+{
+    if (a.gh < 1 || a.gw < 1 || a.n < 1 || a.n > g.max_batch || !a.det || !scores || !labels || !g.ring || !g.pos || g.K < 2 || g.K > 8) return hipErrorInvalidValue;
+    if (5 + a.classes > 128 || a.raw_stride < a.na * (5 + a.classes)) return hipErrorInvalidValue;
+    const size_t cells = (size_t)a.n * a.gh * a.gw;
+    size_t blocks = (cells + 3) / 4; if (blocks > 256 * 8) blocks = 256 * 8;          // as k_decode_yolo_cell: persistent, 8 workgroups per CU
+    if (a.region) hipLaunchKernelGGL(k_decode_avg<true>, dim3((unsigned)blocks), dim3(256), 0, s, a, g, scores, labels);
+    else hipLaunchKernelGGL(k_decode_avg<false>, dim3((unsigned)blocks), dim3(256), 0, s, a, g, scores, labels);
+    return hipGetLastError();
+}
+__global__ void k_ring_advance(int *pos, int n, int K)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < n) pos[b] = (pos[b] + 1) % K;
+}
+hipError_t launch_ring_advance(int *pos, int n, int K, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_ring_advance, dim3((n + 63) / 64), dim3(64), 0, s, pos, n, K);
+    return hipGetLastError();
+}
+__global__ __launch_bounds__(256) void k_ring_slot_move(float *ring, float *keep, const int *pos, int max_batch, size_t E, int restore)
+{
+    const size_t total = (size_t)max_batch * E;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        float *r = ring + (size_t)pos[i / E] * total + i;
+        if (restore) *r = keep[i]; else keep[i] = *r;
+    }
+}
+hipError_t launch_ring_slot_move(float *ring, float *keep, const int *pos, int max_batch, size_t E, int restore, hipStream_t s)
+{
+    size_t blocks = ((size_t)max_batch * E + 255) / 256; if (blocks > 256 * 8) blocks = 256 * 8;
+    hipLaunchKernelGGL(k_ring_slot_move, dim3((unsigned)blocks), dim3(256), 0, s, ring, keep, pos, max_batch, E, restore);
     return hipGetLastError();
 }
 

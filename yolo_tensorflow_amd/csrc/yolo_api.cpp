@@ -81,6 +81,7 @@ void yolo_destroy(yolo_ctx *c)
     for (auto &L : c->layers) for (void *p : {L.d_w2, (void *)L.d_b2, L.d_h, L.d_hn, L.d_rh, (void *)L.d_h32, (void *)L.d_z, (void *)L.d_c}) if (p) hipFree(p);
     for (auto &L : c->layers) for (auto &S : L.sub) { if (S.d_w) hipFree(S.d_w); if (S.d_b) hipFree(S.d_b); }
     if (c->d_state_keep) hipFree(c->d_state_keep);
+    for (void *p : {(void *)c->d_ring, (void *)c->d_ring_keep, (void *)c->d_ring_pos}) if (p) hipFree(p);
     void *ptrs[] = {c->input.ptr, c->d_zeros, c->d_stage, c->d_det, c->d_scores, c->d_labels, c->d_cand, c->d_keys, c->d_sbox, c->d_slabel, c->d_sscore, c->d_boxes, c->d_counts,
                     c->d_seq, c->d_dn_rec, c->d_dn_src, c->d_dn_count, c->d_dn_last, c->d_box4, c->s2d.ptr, c->d_srow, c->d_rows, c->d_lean_list, c->d_lean_cnt, c->d_f32a, c->d_f32b, c->d_descs, c->d_pix, c->d_tile, c->d_cls_idx, c->d_cls_prob, c->d_map_f32, c->d_map_labels, c->d_label_off};
     for (void *p : ptrs) if (p) hipFree(p);
@@ -386,6 +387,16 @@ int yolo_set_state(yolo_ctx *c, int k, int stream, const float *in, size_t in_fl
     return YOLO_OK;
 }
 
+// the frame-average ring of one stream (or of all, stream < 0) back to empty: K slots of zeros, position 0
+static int ring_clear(yolo_ctx *c, int stream)
+{
+    const size_t E = c->ring_elems(), slot = (size_t)c->max_batch * E;
+    if (stream < 0) HIPCK(c, hipMemsetAsync(c->d_ring, 0, slot * c->avg_k * 4, c->stream));
+    else for (int j = 0; j < c->avg_k; ++j) HIPCK(c, hipMemsetAsync(c->d_ring + j * slot + (size_t)stream * E, 0, E * 4, c->stream));
+    HIPCK(c, hipMemsetAsync(c->d_ring_pos + (stream < 0 ? 0 : stream), 0, (size_t)(stream < 0 ? c->max_batch : 1) * 4, c->stream));
+    return YOLO_OK;
+}
+
 // reset_network_state(net, b) (DN/network.c:69): the states of one stream, or of all (stream < 0), back to zero
 int yolo_reset_state(yolo_ctx *c, int stream)
 {
@@ -398,7 +409,43 @@ int yolo_reset_state(yolo_ctx *c, int stream)
         HIPCK(c, hipMemsetAsync((char *)L.d_h + first * es, 0, ne * es, c->stream));
         for (float *p : {L.d_h32, L.d_c}) if (p) HIPCK(c, hipMemsetAsync(p + first, 0, ne * 4, c->stream));
     }
+    if (c->avg_k > 1) if (int r = ring_clear(c, stream)) return r;      // a new video on the stream starts with empty slots, as demo()'s calloc leaves them
     return YOLO_OK;
+}
+
+// ---- frame averaging ("Frame averaging"; DN/examples/demo.c) ----
+int yolo_frame_average(const yolo_ctx *c) { return c ? c->avg_k : YOLO_ERR_INVALID; }
+
+int yolo_set_frame_average(yolo_ctx *c, int frames)
+{
+    static const char *const who = "yolo_set_frame_average";
+    if (!c) return YOLO_ERR_INVALID;
+    if (frames < 1 || frames > 8) return fail(c, YOLO_ERR_INVALID, "%s: %d frames outside 1..8 (1: off)", who, frames);
+    if (frames > 1) {
+        if (int r = need_detector(c, who)) return r;
+        for (size_t i = 0; i < c->layers.size(); ++i) {
+            const Layer &L = c->layers[i];
+            if (L.type == L_DETECT) return fail(c, YOLO_ERR_UNSUPPORTED, "%s: layer %d is a [detection] (YOLOv1) head: its output is not averaged (darknet's demo averages it, its boxes take the square of the mean; not served)", who, (int)i);
+            if (is_head_layer(L) && L.tree >= 0) return fail(c, YOLO_ERR_UNSUPPORTED, "%s: layer %d is a [region] head with a softmax tree: the mean of per-group softmaxes is not served", who, (int)i);
+            if (is_head_layer(L) && 5 + L.classes > 128) return fail(c, YOLO_ERR_UNSUPPORTED, "%s: layer %d has %d attributes per box (at most 128)", who, (int)i, 5 + L.classes);
+        }
+    }
+    HIPCK(c, hipSetDevice(c->device));
+    if (frames == c->avg_k && frames == 1) return YOLO_OK;
+    // another launch sequence, other buffers: no captured step may be replayed; nothing in flight may still read the old ring
+    drop_graph(c);
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    for (void **p : {(void **)&c->d_ring, (void **)&c->d_ring_keep, (void **)&c->d_ring_pos}) { if (*p) HIPCK(c, hipFree(*p)); *p = nullptr; }
+    c->avg_k = 1; c->ring_frozen = false;
+    if (frames == 1) return YOLO_OK;
+    const size_t slot = (size_t)c->max_batch * c->ring_elems() * 4;
+    if (hipMalloc((void **)&c->d_ring, slot * frames) != hipSuccess || hipMalloc((void **)&c->d_ring_keep, slot) != hipSuccess || hipMalloc((void **)&c->d_ring_pos, (size_t)c->max_batch * 4) != hipSuccess) {
+        (void)hipGetLastError();
+        for (void **p : {(void **)&c->d_ring, (void **)&c->d_ring_keep, (void **)&c->d_ring_pos}) { if (*p) hipFree(*p); *p = nullptr; }
+        return fail(c, YOLO_ERR_HIP, "%s: no memory for %d + 1 slots of %zu bytes", who, frames, slot);
+    }
+    c->avg_k = frames;
+    return ring_clear(c, -1);
 }
 
 int yolo_synchronize(yolo_ctx *c) { if (!c) return YOLO_ERR_INVALID; HIPCK(c, hipStreamSynchronize(c->stream)); return YOLO_OK; }

@@ -177,6 +177,12 @@ struct yolo_ctx {
     int last_n = 0;
     std::vector<StateRef> states;         // the state tensors of the recurrent layers (empty: a pure function of the batch)
     void *d_state_keep = nullptr;         // the timing entry points' copy of every state, handed back when they return (state_keep / state_restore)
+    // frame averaging (yolo_set_frame_average; DESIGN.md "Frame averaging"): avg_k = K frames (1: off, nothing allocated).  d_ring [K][max_batch][rows * attrs] fp32:
+    // the last K activated head tensors of every stream, head h at row_off * attrs; d_ring_pos [max_batch]: the slot a stream's next step writes, advanced on
+    // the device after the step's last decode.  d_ring_keep [max_batch][rows * attrs]: the one slot per stream the timing entry points overwrite, which run
+    // with the positions standing still (ring_frozen) and hand that slot back (state_keep / state_restore).  Not recurrent states, no part of the plan
+    int avg_k = 1; float *d_ring = nullptr, *d_ring_keep = nullptr; int *d_ring_pos = nullptr; bool ring_frozen = false;
+    size_t ring_elems() const { return (size_t)rows * attrs; }
     // fp8 scheme: stored value = e4m3(real / scale).  user_scale[i] is what yolo_set_act_scales gave for
     // layer i (1 by default); eff_scale[i] is the scale of the tensor layer i's view holds (inherited through
     // upsample / maxpool / reorg / single-input route; NaN for multi-input routes, which are per channel).

@@ -272,8 +272,25 @@ static int state_move(yolo_ctx *c, bool restore)
     }
     return YOLO_OK;
 }
-int state_keep(yolo_ctx *c) { return c->states.empty() ? YOLO_OK : state_move(c, false); }
-int state_restore(yolo_ctx *c) { return c->states.empty() ? YOLO_OK : state_move(c, true); }
+// the frame-average ring: between keep and restore the positions stand still (run_decode issues no advance), so every pass writes the same one slot per stream
+static int ring_move(yolo_ctx *c, bool restore)
+{
+    HIPCK(c, launch_ring_slot_move(c->d_ring, c->d_ring_keep, c->d_ring_pos, c->max_batch, c->ring_elems(), restore, c->stream));
+    return YOLO_OK;
+}
+// ring_frozen is set only once everything is kept, and cleared by every restore whatever fails in it: no error path leaves the positions standing still
+int state_keep(yolo_ctx *c)
+{
+    if (!c->states.empty()) if (int r = state_move(c, false)) return r;
+    if (c->avg_k > 1) { if (int r = ring_move(c, false)) return r; c->ring_frozen = true; }
+    return YOLO_OK;
+}
+int state_restore(yolo_ctx *c)
+{
+    int r = c->states.empty() ? YOLO_OK : state_move(c, true);
+    if (c->avg_k > 1 && c->ring_frozen) { c->ring_frozen = false; const int r2 = ring_move(c, true); if (!r) r = r2; }
+    return r;
+}
 namespace { struct StateGuard { yolo_ctx *c; ~StateGuard() { state_restore(c); } }; }      // hands the states back on every return path
 
 static void yolo_anchors(const yolo_ctx *c, const Layer &Y, float *out)      // a [yolo] head's anchors in cells: pixels over the head's stride
@@ -320,6 +337,17 @@ static int run_decode(yolo_ctx *c, int i, int n)
     d.det = c->lean ? nullptr : c->d_det; d.box4 = c->lean ? c->d_box4 : nullptr; d.rows_total = c->rows; d.row_off = L.row_off;
     d.reject_below = c->lean ? c->lean_thr : -INFINITY;
     // [region] with a softmax tree.  Full form: the decoded tensor with absolute class probabilities (scored at postprocess time, with the hier_thresh of that moment); descent form (yolo_detect*): box4, scores, labels straight from the raw tensor
+    if (c->avg_k > 1) {
+        // frame averaging: this call is one time step of the streams 0 .. n - 1.  Ring store + mean + full decode per head; once the last head has read the
+        // positions they move on (not between the timing entry points' keep and restore: steps of no stream)
+        const float alpha = (float)(1. / c->avg_k);
+        const RingArgs g{c->d_ring, c->d_ring_pos, c->avg_k, c->max_batch, c->ring_elems(), (size_t)L.row_off * c->attrs, alpha};
+        HIPCK(c, launch_decode_avg(d, g, c->d_scores, c->d_labels, s));
+        bool later_head = false;
+        for (size_t k = i + 1; k < c->layers.size(); ++k) later_head |= is_head_layer(c->layers[k]);
+        if (!later_head && !c->ring_frozen) HIPCK(c, launch_ring_advance(c->d_ring_pos, n, c->avg_k, s));
+        return YOLO_OK;
+    }
     if (L.tree < 0) HIPCK(c, launch_decode(d, c->d_scores, c->d_labels, s));
     else if (c->lean) { HIPCK(c, launch_decode_region_tree_lean(d, c->trees[L.tree].dev, c->hier_thresh, c->d_scores, c->d_labels, s)); c->lean_hier = c->hier_thresh; }
     else HIPCK(c, launch_decode_region_tree(d, c->trees[L.tree].dev, s));
@@ -501,14 +529,14 @@ static int run_layers(yolo_ctx *c, int n, bool skip_conv = false, std::vector<hi
 // What a finished forward of n images leaves for yolo_postprocess* / yolo_darknet_boxes*.  lean: the decode wrote scores, labels and box4, not the tensor; scores_mode: what d_scores holds now (< 0: left as it is); fit >= 0: the input was a ragged batch fitted that way
 static void forward_done(yolo_ctx *c, int n, bool lean, int scores_mode = 0, int fit = -1)
 {
-    c->lean = lean && c->lean_ok; c->det_valid = !c->lean; c->last_n = n;
+    c->lean = lean && c->lean_ok && c->avg_k < 2; c->det_valid = !c->lean; c->last_n = n;          // (frame averaging: always the full decode, the lean one never forms what is averaged)
     if (scores_mode >= 0) c->scores_mode = scores_mode;
     if (fit >= 0) { c->geom_fit = fit; c->geom_n = n; }
 }
 
 int run_network(yolo_ctx *c, int n, bool lean, int fit)
 {
-    c->lean = lean && c->lean_ok;          // (run_decode reads it)
+    c->lean = lean && c->lean_ok && c->avg_k < 2;          // (run_decode reads it)
     if (int r = run_layers(c, n)) { c->lean = false; return r; }
     forward_done(c, n, lean, 0, fit);
     return YOLO_OK;
@@ -944,6 +972,7 @@ int yolo_detect_tiled_u8(yolo_ctx *c, const uint8_t *pixels, size_t bytes, const
     // ---- every refusal, before any launch ----
     if (int r = need_detector(c, who)) return r;
     if (c->in_c != 3) return fail(c, YOLO_ERR_UNSUPPORTED, "%s: a network of %d planes ([net] yolo_input=planes) is not served: windows are cut from RGB images", who, c->in_c);
+    if (c->avg_k > 1) return fail(c, YOLO_ERR_UNSUPPORTED, "%s: not served while frame averaging is on (yolo_set_frame_average(%d)): a batch slot holds a window, not a stream; set it to 1 first", who, c->avg_k);
     if (!c->weights_loaded) return fail(c, YOLO_ERR_STATE, "%s before weights were loaded", who);
     static const char *const fit_names[] = {"YOLO_FIT_STRETCH", "YOLO_FIT_LETTERBOX", "YOLO_FIT_CV2", "YOLO_FIT_CV2_BGR", "YOLO_FIT_CENTER_CROP"};
     if (fit < YOLO_FIT_STRETCH || fit > YOLO_FIT_CENTER_CROP) return fail(c, YOLO_ERR_INVALID, "bad fit %d", fit);

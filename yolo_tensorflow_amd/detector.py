@@ -22,7 +22,10 @@ class _Detector:
     flags = None
     select_mode = hip.SELECT_GT
 
-    def __init__(self, weights_file, verbose=False, dtype=hip.BF16, device=0, weights=None, max_output_size=None, max_batch=1):
+    def __init__(self, weights_file, verbose=False, dtype=hip.BF16, device=0, weights=None, max_output_size=None, max_batch=1, average_frames=1):
+        """average_frames = K >= 2: video mode, as darknet's `detector demo` -- the boxes come from the mean of the detection layers' outputs over
+        the last K frames (Engine.set_frame_average).  detect_from_image is then a time step of stream 0 and detect_from_images(images) one of the
+        streams 0 .. len(images) - 1 (at most max_batch); a stream's first K - 1 results are attenuated by the empty slots; reset_streams starts over."""
         f = self.flags
         self.verbose = verbose
         self.threshold, self.iou_threshold = f.conf_threshold, f.iou_threshold
@@ -39,6 +42,9 @@ class _Detector:
             self.engine.set_weights(weights)
         else:
             self.engine.load_weights(weights_file, self.header_ints)
+        self.average_frames = int(average_frames)
+        if self.average_frames != 1:
+            self.engine.set_frame_average(self.average_frames)
         try:
             self.class_names = self.load_coco_names(f.class_names)
         except OSError:
@@ -65,6 +71,9 @@ class _Detector:
         """A list of RGB uint8 [H,W,3] images of any sizes -> [(scores, boxes, classes)] per image, exactly what detect_from_image
         returns for each (normalised boxes, as `detected_boxes:0`); the images run max_batch at a time, each chunk as ONE device step
         (stretch fit, threshold and NMS of the whole chunk: Engine.detect_images)."""
+        if self.average_frames > 1 and len(images) > self.max_batch:
+            raise ValueError("detect_from_images: %d images, but with average_frames=%d a call is one time step of at most max_batch=%d streams"
+                             % (len(images), self.average_frames, self.max_batch))
         out = []
         for i in range(0, len(images), self.max_batch):
             chunk = [np.ascontiguousarray(im, dtype=np.uint8) for im in images[i:i + self.max_batch]]
@@ -73,6 +82,10 @@ class _Detector:
                                                select_mode=self.select_mode):
                 out.append((r["score"], np.stack([r["x0"], r["y0"], r["x1"], r["y1"]], -1).reshape(-1, 4), r["cls"]))
         return out
+
+    def reset_streams(self, stream=None):
+        """A new video on `stream` (None: on every stream): its frame-average slots, and the states of a recurrent network, back to zero."""
+        self.engine.reset_state(stream)
 
     def detect_from_large_images(self, images, tile=None, overlap=64):
         """Images much larger than the network input (a 4K frame, an aerial photo): each is cut into overlapping windows of `tile` (None:

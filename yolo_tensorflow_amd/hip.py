@@ -51,6 +51,7 @@ EXPORTS = [
     "yolo_num_state_tensors", "yolo_state_geometry", "yolo_get_state", "yolo_set_state", "yolo_reset_state",
     "yolo_tile_windows", "yolo_detect_tiled_u8",
     "yolo_vector_inputs", "yolo_forward_vectors", "yolo_sequence", "yolo_set_temperature", "yolo_reset_temperature", "yolo_op_sample",
+    "yolo_set_frame_average", "yolo_frame_average",
 ]
 HIER_CONDITIONAL, HIER_ABSOLUTE, HIER_LEAVES = 0, 1, 2
 _HIER_MODES = {None: HIER_CONDITIONAL, "conditional": HIER_CONDITIONAL, "absolute": HIER_ABSOLUTE, "leaves": HIER_LEAVES}
@@ -175,6 +176,8 @@ def load_library():
     l.yolo_get_state.argtypes = [P, I, I, P, SZ]
     l.yolo_set_state.argtypes = [P, I, I, P, SZ]
     l.yolo_reset_state.argtypes = [P, I]
+    l.yolo_set_frame_average.argtypes = [P, I]
+    l.yolo_frame_average.argtypes = [P]
     l.yolo_tile_windows.argtypes = [I, I, I, I, I, I, P, I, C.POINTER(I)]
     l.yolo_detect_tiled_u8.argtypes = [P, P, SZ, P, I, I, I, I, I, I, I, F, F, I, I, I, I, P, P, I]
     l.yolo_vector_inputs.argtypes = [P]
@@ -741,6 +744,17 @@ class Engine:
     def reset_state(self, stream=None):
         """zero the states of one stream, or of every stream (darknet's reset_network_state)"""
         self._check(self.lib.yolo_reset_state(self.ctx, -1 if stream is None else int(stream)), "yolo_reset_state")
+
+    # ---- frame-averaged detection on video streams (darknet's `detector demo`; include/yolo_hip.h) ----
+    def set_frame_average(self, frames):
+        """frames = K in 1 .. 8 (1: off).  With K >= 2 every forward* / detect* call with n images is one time step of the streams 0 .. n-1:
+        the boxes are decoded from the mean of the heads' activated outputs over the stream's last K steps.  The slots start as zeros (and
+        again after reset_state), so a stream's first K-1 results are attenuated, as in darknet's demo."""
+        self._check(self.lib.yolo_set_frame_average(self.ctx, int(frames)), "yolo_set_frame_average")
+
+    def frame_average(self):
+        """the current K (1: off)"""
+        return self.lib.yolo_frame_average(self.ctx)
 
     # ---- vector-input networks ([net] yolo_input=vector, inputs=N: char-rnn; include/yolo_hip.h) ----
     @property
