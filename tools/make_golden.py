@@ -46,6 +46,10 @@ Runs only in the build container (it reads /root/reference and oracle/_ref); the
                     darknet's `detector demo` averaging (DN/examples/demo.c remember_network + avg_predictions) on three small detectors: per case
                     cfg, weight seed, K, K + 2 uint8 frames, every [yolo] / [region] layer's l.output after each frame, and get_network_boxes of
                     the compiled reference over the mean of the last K outputs (written back into l.output) after every step; fixed member dates
+  mini_v1_edges.npz / mini_v1_stem.npz   (v1_edges)
+                    the YOLOv1 family at its kernels' edges: three [local] layers (72 granules per filter row, 13 filters, stride 2 under padding, tanh), two
+                    [connected] layers (the default logistic, K = 48) and [detection] with num=3, sqrt=0 on a 6 x 10 input; a 7x7 / 2 conv on 10 x 14,
+                    a [connected] over 5 x 7 x 8 and [detection] with side=1: three images, every layer, get_network_boxes per image; fixed member dates
   yolov3_bn_real.npz / yolov2_bn_real.npz
                      the COMPLETE batch-norm vectors (beta, gamma, rolling mean, rolling variance) of every
                      batch-normalised conv of yolov3.weights / yolov2.weights, and the first l.n filter
@@ -1587,6 +1591,92 @@ def gen_frame_average(weight_seed=21, src_wh=(200, 120)):
     print("frame_average_cases", len(data), "arrays", os.path.getsize(path), "bytes")
 
 
+def _local(filters, size, stride, pad, act):
+    return "[local]\nsize=%d\nstride=%d\npad=%d\nfilters=%d\nactivation=%s\n\n" % (size, stride, pad, filters, act)
+
+
+def _detection(side, num, classes, sqrt):
+    return "[detection]\nclasses=%d\ncoords=4\nrescore=1\nside=%d\nnum=%d\nsoftmax=0\nsqrt=%d\n" % (classes, side, num, sqrt)
+
+
+def mini_v1_edges_cfg(height=6, width=10):
+    """The YOLOv1 family at the edges of its kernels, 6 high x 10 wide.  Layer by layer (H x W x C):
+      0 conv 3x3 -> 64, bn, leaky                               6 x 10 x 64
+      1 conv 3x3 -> 64, bn, leaky                               6 x 10 x 64   (its im2col workspace, 60 * 9 * 64 floats, is the one the [local] layers lean on)
+      2 maxpool 2/2                                             3 x  5 x 64
+      3 [local] 3x3 / 1 / pad 1 -> 13, leaky                    3 x  5 x 13   72 granules per filter row: a ragged second pass of 64 lanes; 13 filters
+      4 conv 1x1 -> 16, bias, leaky                             3 x  5 x 16
+      5 [local] 3x3 / 2 / pad 1 -> 8, relu                      2 x  3 x  8   stride 2 under padding
+      6 [local] 2x2 / 1 / pad 0 -> 24, tanh                     1 x  2 x 24   even size, no padding, an activation outside the slope family
+      7 [connected] 37, no activation key (logistic)            K = 48
+      8 [connected] 68, linear                                  the head: 2 * 2 * (2 + 3 * 5)
+      9 [detection] side 2, num 3, classes 2, sqrt=0"""
+    return ("[net]\nbatch=1\nwidth=%d\nheight=%d\nchannels=3\n\n" % (width, height) + _econv(64, 3, pad=1, bn=True) + _econv(64, 3, pad=1, bn=True) + _pool(2, 2) +
+            _local(13, 3, 1, 1, "leaky") + _econv(16, 1, pad=0) + _local(8, 3, 2, 1, "relu") + _local(24, 2, 1, 0, "tanh") +
+            "[connected]\noutput=37\n\n[connected]\noutput=68\nactivation=linear\n\n" + _detection(2, 3, 2, 0))
+
+
+def mini_v1_stem_cfg(height=10, width=14):
+    """The 7x7 / 2 / pad 3 first conv where its space-to-depth form has odd extents below the 4 x 4 window's reach, 10 high x 14 wide:
+      0 conv 7x7 / 2 -> 20, bias, leaky                         5 x  7 x 20
+      1 conv 1x1 -> 8, bias, leaky                              5 x  7 x  8
+      2 [connected] 7, linear                                   K = 5 * 7 * 8 = 280: no multiple of 64, a rectangular CHW flatten
+      3 [detection] side 1, num 1, classes 2, sqrt=1"""
+    return ("[net]\nbatch=1\nwidth=%d\nheight=%d\nchannels=3\n\n" % (width, height) + _econv(20, 7, stride=2, pad=1) + _econv(8, 1, pad=0) +
+            "[connected]\noutput=7\nactivation=linear\n\n" + _detection(1, 1, 2, 1))
+
+
+V1_EDGES_NETS = [("mini_v1_edges", mini_v1_edges_cfg, (6, 10), 171, 2), ("mini_v1_stem", mini_v1_stem_cfg, (10, 14), 173, 2)]
+
+
+def gen_mini_v1_edges(out_dir=None, thresh=0.2):
+    """mini_v1_edges_cfg and mini_v1_stem_cfg through the compiled reference (local_layer.c, connected_layer.c, detection_layer.c), gen_mini_local's
+    recipe for three images: cfg text, the seeded weight stream, three uint8 images, every layer's output of network_predict on image / 255 (one predict per
+    image), and get_network_boxes -> get_detection_detections per image (boxes_raw [3, rows, 4] in network pixels, obj_raw, prob_raw at `thresh`).
+    Checked here: every [local] layer's im2col workspace (which the reference sizes in elements, DN/local_layer.c:64) fits in layer 1's, and the seed leaves
+    at most 5 % of the (box, class) scores within 1e-3 of the threshold.  Fixed member dates.  -> the paths written."""
+    from oracle import darknet_ref as D
+    from yolo_tensorflow_amd import darknet_io as IO
+    paths = []
+    for name, make, (h, w), seed, classes in V1_EDGES_NETS:
+        cfg = make(); secs = IO.parse_cfg(cfg); shapes = IO.layer_shapes(secs)
+        conv_ws = [sh[1] * sh[2] * int(s["size"]) ** 2 * sh[4] * 4 for s, sh in zip(secs[1:], shapes) if s["type"] == "convolutional"]
+        for s, sh in zip(secs[1:], shapes):
+            if s["type"] == "local":
+                need = sh[1] * sh[2] * int(s["size"]) ** 2 * sh[4] * 4
+                assert need < max(conv_ws), "[local] workspace of %d bytes, the largest conv's is %d" % (need, max(conv_ws))
+        flat = IO.synth_weights(secs, seed=seed)
+        imgs = np.random.default_rng(seed + 1).integers(0, 256, (3, h, w, 3), dtype=np.uint8)
+        net = D.RefNet(cfg, flat, 0, 2)
+        assert (net.h, net.w) == (h, w) and net.n == len(shapes)
+        outs = [[] for _ in range(net.n)]; bb, obj, pr = [], [], []
+        for b in range(3):
+            net.predict(imgs[b].astype(np.float32) / np.float32(255.0))
+            for i in range(net.n):
+                outs[i].append(np.asarray(net.layer_output_nhwc(i), dtype=np.float32).reshape(-1))
+            r = net.boxes(thresh, None, classes)
+            bb.append(r[0]); obj.append(r[1]); pr.append(r[2])
+        net.close()
+        data = {"cfg": np.array(cfg), "weights": flat, "images_u8": imgs, "thresh": np.float32(thresh)}
+        for i in range(net.n):
+            o = np.stack(outs[i])
+            data["layer_%02d" % i] = o.reshape((3,) + tuple(shapes[i][1:4])) if shapes[i][0] != "detection" else o
+            assert np.isfinite(o).all()
+        data["boxes_raw"], data["obj_raw"], data["prob_raw"] = np.stack(bb), np.stack(obj), np.stack(pr)
+        cells, num = int(secs[-1]["side"]) ** 2, int(secs[-1]["num"])
+        cls = np.repeat(data["layer_%02d" % (net.n - 1)][:, :cells * classes].reshape(3, cells, classes), num, axis=1)          # a cell's class scores, once per box
+        near = int((np.abs(data["obj_raw"][..., None] * cls - np.float32(thresh)) <= 1e-3).sum())
+        pairs = data["prob_raw"].size
+        assert near * 20 <= pairs, "%s: %d of %d (box, class) scores lie within 1e-3 of the threshold: choose another seed" % (name, near, pairs)
+        assert 0 < int((data["prob_raw"] > 0).sum()) < pairs, "%s: the threshold separates nothing" % name
+        path = os.path.join(out_dir or OUT, name + ".npz")
+        save_npz_reproducibly(path, data)
+        paths.append(path)
+        print(name, "layers", net.n, "boxes", data["boxes_raw"].shape, "scores above the threshold", int((data["prob_raw"] > 0).sum()), "of", pairs, "near it", near,
+              os.path.getsize(path), "bytes")
+    return paths
+
+
 def gen_rect():
     gen_mini_rect("mini_v3_rect", MINI_V3, 4, 64, 96, letterbox=True)
     gen_mini_rect("mini_v2_rect", MINI_V2, 5, 96, 64)
@@ -1621,6 +1711,8 @@ if __name__ == "__main__":
         gen_mini_char_rnn(); sys.exit(0)
     if sys.argv[1:] == ["planes"]:
         gen_planes(); sys.exit(0)
+    if sys.argv[1:] == ["v1_edges"]:
+        gen_mini_v1_edges(); sys.exit(0)
     if sys.argv[1:] == ["--frame-average"]:
         gen_frame_average(); sys.exit(0)
     stub_modules()
@@ -1642,6 +1734,7 @@ if __name__ == "__main__":
     gen_mini_char_rnn()
     gen_planes()
     gen_frame_average()
+    gen_mini_v1_edges()
     gen_bn_real()
     gen_known_answers()
     gen_darknet_py_symbols()

@@ -1053,8 +1053,12 @@ int allocate(yolo_ctx *c)
         }
         if (L.fc) {             // the flattened producer must be dense: one pixel of fc_h * fc_w * fc_c contiguous elements per image
             const TView in = view_of(c, L.in[0]);
-            // ... or, where the producer is one pixel (a vector network's input, a recurrent or [connected] layer), that pixel with its granule's zero padding
-            const bool one_pixel = L.fc_h * L.fc_w == 1 && in.c == L.fc_c && in.stride == L.cin_pad && in.dt == L.in_dt && c->vec_n;
+            // ... or, where the producer is one pixel, that pixel padded to whole granules: anything in a vector network (its input, a recurrent or
+            // [connected] layer), and in an image network a [connected] layer (YOLOv1's [connected] behind a [connected] of 37 outputs).  The pad
+            // lanes are finite -- the GEMM's epilogue writes act(0) there, a post-activation pass act(0) of that, logistic: 0.5 -- and meet zero
+            // filter rows, so they add nothing
+            const bool padded_row = c->vec_n || (L.in[0] >= 0 && c->layers[L.in[0]].fc);
+            const bool one_pixel = L.fc_h * L.fc_w == 1 && in.c == L.fc_c && in.stride == L.cin_pad && in.dt == L.in_dt && padded_row;
             if (!one_pixel && (in.stride != in.c || in.c != L.fc_c)) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %zu: [connected] needs a dense producer (channels a multiple of 8, not part of a concat)", i);
         }
     }
