@@ -411,7 +411,9 @@ int yolo_calibrate(int device, void *stream, int f16, double seconds, float *tfl
  * launched back to back for `seconds`.  The boxes of one pool differ in their matrix-pipe clock AND in what their memory system sustains;
  * bench.py prints both numbers (roofline.calib_tflops, roofline.calib_copy_gbs). */
 int yolo_calibrate_copy(int device, void *stream, double seconds, float *gbs);
-/* Per-layer kernel time (ms, averaged over iters) for batch n into ms_out[num_layers]. */
+/* Per-layer kernel time (ms, averaged over iters) for batch n into ms_out[num_layers].  A [convolutional] layer with xnor=1 is its k_xconv
+ * launch (xconv.hip: window staging as int8, the int8 MFMA, the epilogue) plus, for an activation outside the slope family, k_activate;
+ * yolo_time_forward counts it among the convs (conv_ms). */
 int yolo_time_layers(yolo_ctx *ctx, int n, int iters, float *ms_out);
 /* Tries every conv tile configuration on every conv layer at batch n and keeps the fastest. */
 int yolo_autotune(yolo_ctx *ctx, int n, int iters);
@@ -601,6 +603,17 @@ int yolo_op_deconv2d(const float *x, int n, int h, int w, int cin, const float *
  * against yolo_op_conv2d); dtype and out_f32 as for yolo_op_deconv2d; out [n, (h + 2 padding - size) / stride + 1, ..., cout] fp32 */
 int yolo_op_conv2d_grouped(const float *x, int n, int h, int w, int cin, const float *w_oihw, const float *bias, int size, int stride, int padding,
                            int cout, int groups, int act, int dtype, int out_f32, float *out, int device);
+/* darknet's [convolutional] with xnor=1 (XNOR-Net layers, DN/convolutional_layer.c:28-49, 451-485): the input becomes +1 where it is > 0 and -1
+ * elsewhere (+0, -0 and NaN give -1), a tap outside the image contributes 0; filter f becomes alpha_f * sign(w) with alpha_f = mean |w_f| (in float, added in the order
+ * the reference's build adds: DESIGN.md 3.20); out = act(alpha_f * sum of the sign products + bias).  The sum runs on the int8 MFMA (xconv.hip).
+ * x [n,h,w,cin] fp32 NHWC, stored as `dtype` before its sign is taken; w_oihw [cout][cin][size][size], bias [cout] or NULL; 1 <= size <= 11,
+ * stride >= 1, padding >= 0; dtype and out_f32 as for yolo_op_deconv2d; out [n, (h + 2 padding - size) / stride + 1, ..., cout] fp32.
+ * In a cfg: a [convolutional] section with xnor=1 plans a layer of this kind in the fp32, bf16 and fp16 configurations (yolo_plan_table prints
+ * kernel=- fused=none, as for a grouped section); the planner refuses (YOLO_ERR_UNSUPPORTED) xnor=1 in the fp8 and split-fp16 configurations,
+ * together with groups != 1, as the first layer, and directly in front of a [yolo] / [region] / [detection] head.  binary=1 without xnor, and
+ * flipped=1, are read by nobody. */
+int yolo_op_conv2d_xnor(const float *x, int n, int h, int w, int cin, const float *w_oihw, const float *bias, int size, int stride, int padding,
+                        int cout, int act, int dtype, int out_f32, float *out, int device);
 /* [l2norm]: per pixel x / sqrtf(sum over the channels of x^2); an all-zero pixel is NaN, as in the reference */
 int yolo_op_l2norm(const float *x, int n, int h, int w, int c, int dtype, float *out, int device);
 /* [normalization] / [lrn] (DN/normalization_layer.c:66-95) over the channels of every pixel: out[k] = x[k] * (kappa + alpha * (W(k) - g))^(-beta), W(k) the sum of

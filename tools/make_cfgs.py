@@ -43,13 +43,15 @@ class Cfg:
         self.n += 1
         return self.n - 1
 
-    def conv(self, filters, size, stride=1, bn=True, act="leaky", groups=1):
+    def conv(self, filters, size, stride=1, bn=True, act="leaky", groups=1, xnor=False):
         kv = {}
         if bn:
             kv["batch_normalize"] = 1
         kv.update(filters=filters, size=size, stride=stride, pad=1, activation=act)
         if groups != 1:
             kv["groups"] = groups            # DN/parser.c:184
+        if xnor:
+            kv["xnor"] = 1                   # DN/parser.c:198
         return self._sec("convolutional", **kv)
 
     def shortcut(self, frm, act="linear"):
@@ -268,6 +270,32 @@ def yolov2_tiny_voc(size=416, classes=20):
     c.conv(1024, 3)
     c.conv(len(V2_TINY_VOC_ANCHORS) * (5 + classes), 1, bn=False, act="linear")
     c.region(V2_TINY_VOC_ANCHORS, classes)
+    return c.text()
+
+
+def xnor_yolov2_tiny_voc(size=416, classes=20, xnor=True):
+    """yolov2-tiny-voc as an XNOR-Net detector (darknet's tiny-yolo-xnor): xnor=1 on every conv but the first and the last two"""
+    c = Cfg(size)
+    for f in (16, 32, 64, 128, 256):
+        c.conv(f, 3, xnor=xnor and f != 16); c.maxpool()
+    c.conv(512, 3, xnor=xnor); c.maxpool(2, 1)
+    c.conv(1024, 3, xnor=xnor)
+    c.conv(1024, 3)
+    c.conv(len(V2_TINY_VOC_ANCHORS) * (5 + classes), 1, bn=False, act="linear")
+    c.region(V2_TINY_VOC_ANCHORS, classes)
+    return c.text()
+
+
+def xnor_darknet_reference(size=256, classes=1000, xnor=True):
+    """darknet's reference classifier (darknet.cfg: 16 .. 1024 filters of 3x3 with a max-pool between them, a 1x1 conv to the classes, [avgpool],
+    [softmax]) written likewise: xnor=1 on every conv but the first and the last two"""
+    c = Cfg(size)
+    for f in (16, 32, 64, 128, 256, 512):
+        c.conv(f, 3, xnor=xnor and f != 16); c.maxpool()
+    c.conv(1024, 3)
+    c.conv(classes, 1, bn=False, act="linear")
+    c.avgpool()
+    c.softmax()
     return c.text()
 
 
@@ -540,6 +568,13 @@ def main():
             with open(os.path.join(sys.argv[2], name), "w") as f:
                 f.write(text + "\n")
         print("wrote", ", ".join(files), "to", sys.argv[2])
+        return
+    if len(sys.argv) > 2 and sys.argv[1] == "--xnor":          # python tools/make_cfgs.py --xnor DIR: the two XNOR-Net cfgs (tools/xnor_rate.py measures the first)
+        os.makedirs(sys.argv[2], exist_ok=True)
+        for name, text in (("yolov2-tiny-voc-xnor.cfg", xnor_yolov2_tiny_voc()), ("darknet-reference-xnor.cfg", xnor_darknet_reference())):
+            with open(os.path.join(sys.argv[2], name), "w") as f:
+                f.write(HEADER + text)
+        print("wrote yolov2-tiny-voc-xnor.cfg and darknet-reference-xnor.cfg to", sys.argv[2])
         return
     if len(sys.argv) > 2 and sys.argv[1] == "--dw-yolo":       # python tools/make_cfgs.py --dw-yolo DIR: dw-yolo.cfg, a depthwise-separable yolov3-tiny
         os.makedirs(sys.argv[2], exist_ok=True)

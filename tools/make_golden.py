@@ -50,6 +50,11 @@ Runs only in the build container (it reads /root/reference and oracle/_ref); the
                     the YOLOv1 family at its kernels' edges: three [local] layers (72 granules per filter row, 13 filters, stride 2 under padding, tanh), two
                     [connected] layers (the default logistic, K = 48) and [detection] with num=3, sqrt=0 on a 6 x 10 input; a 7x7 / 2 conv on 10 x 14,
                     a [connected] over 5 x 7 x 8 and [detection] with side=1: three images, every layer, get_network_boxes per image; fixed member dates
+  mini_xnor.npz / xnor_layer_cases.npz   (--xnor)
+                    XNOR-Net layers ([convolutional] with xnor=1, DN/convolutional_layer.c:28-49, 451-485): a [yolo] detector with xnor=1 on every conv but
+                    the first and the last two (one image, every layer's output, get_network_boxes), and a classifier whose xnor layers differ in shape (a
+                    5x5 with padding=1, a stride-2 3x3 with a bias, a 1x1 with tanh); the weight seed is the first at which no value entering an xnor
+                    layer is non-zero and within 5e-4 of its tensor's largest value of zero; fixed member dates
   yolov3_bn_real.npz / yolov2_bn_real.npz
                      the COMPLETE batch-norm vectors (beta, gamma, rolling mean, rolling variance) of every
                      batch-normalised conv of yolov3.weights / yolov2.weights, and the first l.n filter
@@ -1677,6 +1682,79 @@ def gen_mini_v1_edges(out_dir=None, thresh=0.2):
     return paths
 
 
+def _xconv(filters, size, stride=1, pad="pad=1", bn=True, act="leaky", xnor=True):
+    return "[convolutional]\n%sfilters=%d\nsize=%d\nstride=%d\n%s\n%sactivation=%s\n\n" % ("batch_normalize=1\n" if bn else "", filters, size, stride, pad, "xnor=1\n" if xnor else "", act)
+
+
+_XNOR_NET = "[net]\nbatch=1\nwidth=24\nheight=24\nchannels=3\n\n"
+_XNOR_STEM = _xconv(8, 3, 2, xnor=False) + "[maxpool]\nsize=2\nstride=2\n\n"          # 24 x 24 x 3 -> 12 x 12 x 8 -> 6 x 6 x 8: few values enter the first xnor layer
+# a tiny-YOLO in miniature: xnor=1 on every conv but the first and the last two
+MINI_XNOR = (_XNOR_NET + _XNOR_STEM + _xconv(16, 3) + _xconv(24, 3) + _xconv(16, 1) + _xconv(32, 3, xnor=False) + _xconv(16, 1, bn=False, act="linear", xnor=False) +
+             "[yolo]\nmask=0,1\nanchors=3,4,  8,6,  10,14\nclasses=3\nnum=3\n")
+# a classifier whose xnor layers differ in shape: 12 filters over 8 channels; a 5x5 with padding=1 over 12 channels; a stride-2 3x3 with a bias; a 1x1 with tanh (a post-activation)
+XNOR_LAYER_CASES = (_XNOR_NET + _XNOR_STEM + _xconv(12, 3) + _xconv(20, 5, pad="padding=1") + _xconv(16, 3, 2, bn=False) + _xconv(24, 1, act="tanh") +
+                    _xconv(32, 3, xnor=False) + _xconv(10, 1, bn=False, act="linear", xnor=False) + "[avgpool]\n\n[softmax]\ngroups=1\n")
+XNOR_MARGIN = 5e-4          # MARGIN_TOL of the fp32 network tests: a value this close to zero (as a share of its tensor's largest) may change sign on the device
+
+
+def xnor_inputs_clear(secs, layers):
+    """no value entering an xnor layer is non-zero and within XNOR_MARGIN * max|tensor| of zero (an exact zero is -1 on both sides)"""
+    for i, s in enumerate(secs[1:]):
+        if s["type"] == "convolutional" and int(s.get("xnor", 0)):
+            x = np.abs(layers[i - 1])
+            if ((x > 0) & (x <= XNOR_MARGIN * x.max())).any():
+                return False
+    return True
+
+
+def gen_xnor(first_seed=301, tries=4000, thresh=0.6):
+    """MINI_XNOR and XNOR_LAYER_CASES through the compiled reference (convolutional_layer.c with l.xnor: binarize_weights, binarize_cpu, im2col, gemm):
+    cfg text, weights, one image, every layer's output, the detector's get_network_boxes, and per xnor layer `alpha_NN`: the magnitude the reference's own
+    binarize_weights gives each filter.  The weight seed is the first from `first_seed` at which
+    xnor_inputs_clear holds in the reference's run: otherwise an fp32 device run may flip a sign and an end-to-end comparison means nothing."""
+    from oracle import darknet_ref as D
+    from yolo_tensorflow_amd import darknet_io as IO
+    for name, cfg, classes in (("mini_xnor", MINI_XNOR, 3), ("xnor_layer_cases", XNOR_LAYER_CASES, 0)):
+        secs = IO.parse_cfg(cfg)
+        img = np.random.default_rng(first_seed - 1).integers(0, 256, (24, 24, 3), dtype=np.uint8)
+        x = img.astype(np.float32) / np.float32(255.0)
+        for seed in range(first_seed, first_seed + tries):
+            flat = IO.synth_weights(secs, seed=seed, obj_bias=0.5)
+            net = D.RefNet(cfg, flat, 0, 2)
+            net.predict(x)
+            layers = [np.asarray(net.layer_output_nhwc(i), dtype=np.float32) for i in range(net.n)]
+            if xnor_inputs_clear(secs, layers):
+                break
+            net.close()
+        else:
+            raise SystemExit("%s: no seed in %d tries" % (name, tries))
+        data = {"cfg": np.array(cfg), "weights": flat, "image_u8": img, "seed": np.int32(seed)}
+        for i in range(net.n):
+            data["layer_%02d" % i] = layers[i].reshape(-1) if secs[i + 1]["type"] in ("avgpool", "softmax") else layers[i]
+        import ctypes as C
+        p = 0
+        for c in IO.conv_specs(secs):
+            nb, per = c["filters"] * (4 if c["bn"] else 1), c["cin"] * c["size"] ** 2
+            if int(secs[1 + c["index"]].get("xnor", 0)):
+                w = np.ascontiguousarray(flat[p + nb:p + nb + c["filters"] * per]); out = np.empty_like(w)
+                fp = C.POINTER(C.c_float)
+                D.lib().binarize_weights(w.ctypes.data_as(fp), C.c_int(c["filters"]), C.c_int(per), out.ctypes.data_as(fp))
+                out = out.reshape(c["filters"], per)
+                assert (np.abs(out) == np.abs(out[:, :1])).all() and ((out > 0) == (w.reshape(c["filters"], per) > 0)).all()
+                data["alpha_%02d" % c["index"]] = np.abs(out[:, 0]).copy()
+            p += nb + c["filters"] * per
+        assert p == flat.size
+        if classes:
+            bb, obj, pr = net.boxes(thresh, None, classes)
+            data["boxes_raw"], data["obj_raw"], data["prob_raw"] = bb, obj, pr
+            data["thresh"] = np.float32(thresh)
+            assert 3 <= len(bb) <= 60, "the threshold should cut the 72 candidates: %d pass" % len(bb)
+        net.close()
+        path = os.path.join(OUT, name + ".npz")
+        save_npz_reproducibly(path, data)
+        print(name, "seed", seed, "layers", len(layers), "boxes", len(data.get("boxes_raw", [])), os.path.getsize(path), "bytes")
+
+
 def gen_rect():
     gen_mini_rect("mini_v3_rect", MINI_V3, 4, 64, 96, letterbox=True)
     gen_mini_rect("mini_v2_rect", MINI_V2, 5, 96, 64)
@@ -1715,6 +1793,8 @@ if __name__ == "__main__":
         gen_mini_v1_edges(); sys.exit(0)
     if sys.argv[1:] == ["--frame-average"]:
         gen_frame_average(); sys.exit(0)
+    if sys.argv[1:] == ["--xnor"]:
+        gen_xnor(); sys.exit(0)
     stub_modules()
     gen_nms_v3()
     gen_v2_post()
@@ -1735,6 +1815,7 @@ if __name__ == "__main__":
     gen_planes()
     gen_frame_average()
     gen_mini_v1_edges()
+    gen_xnor()
     gen_bn_real()
     gen_known_answers()
     gen_darknet_py_symbols()

@@ -28,8 +28,9 @@ FIXTURE = os.path.join(ROOT, "tests", "golden", "plan_dumps.json")
 # ... and [crop] / [normalization] sections, likewise: tests/test_lrn_crop_host.py
 # ... and a vector-input network ([net] yolo_input=vector), which it refused for its missing image size: tests/test_char_rnn_host.py
 # ... and image networks of a channel count other than three ([net] yolo_input=planes), which it refused for their channels=: tests/test_planes_host.py
+# ... and [convolutional] sections with xnor=1, a key it read nowhere (it planned them as dense convs): tests/test_xnor_host.py pins their L_XCONV rows and refusals
 UNPINNED = ("zoo/alexnet", "golden/mini_wide", "golden/mini_seq", "golden/mini_crnn", "zoo/alexnet-lrn", "golden/mini_lrn", "golden/mini_char_rnn",
-            "golden/mini_planes_grey", "golden/mini_planes_rgbd", "golden/mini_planes_nine", "golden/mini_planes_17")
+            "golden/mini_planes_grey", "golden/mini_planes_rgbd", "golden/mini_planes_nine", "golden/mini_planes_17", "golden/mini_xnor", "golden/xnor_layer_cases")
 PLANNER_RC = (0, -1, -6)          # YOLO_OK, YOLO_ERR_INVALID, YOLO_ERR_UNSUPPORTED: all build_plan returns for a cfg whose tree file opens
 
 

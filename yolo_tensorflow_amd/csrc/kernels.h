@@ -313,6 +313,55 @@ inline bool gconv_served(int size, int stride, int pad, int h, int w)
 // 16-bit operands: v_mfma_f32_16x16x32_{bf16,f16} over the bundles, fp32 accumulators; fp32 operands: plain FMAs over the group's own channels
 hipError_t launch_gconv(const GConvArgs &a, hipStream_t s);
 
+// ---- XNOR convolution (xconv.hip; [convolutional] with xnor=1, DN/convolutional_layer.c:28-49, 451-485) ---------------------------
+// out = act(scale_f * sum(sign(x) * sign(w_f)) + bias_f): the input becomes +1 where the stored value is > 0 and -1 elsewhere (+0, -0 and NaN give
+// -1), a tap outside the image 0; filter f becomes +-1 with alpha_f = mean|w_f| in its scale.  The sum is an integer: v_mfma_i32_16x16x64_i8.
+// A workgroup computes a te x te block of output pixels (te = XCONV_TILE, or 4 where the larger block's window does not fit) of one image and
+// stages that block's input window into LDS once, as int8.  The window holds the rows and columns the block's taps read: with rs = min(stride,
+// size), window row r is input row iy0 + (r / rs) * stride + r % rs (for stride < size every row from the first to the last; for a larger
+// stride the rows between two pixels' taps are left out), ww = (te - 1) * rs + size rows and as many columns; tap (ty, tx) of block pixel
+// (y, x) is window position (y * rs + ty, x * rs + tx).  The channels are padded to 16 and cut into CHUNKS of cc channels so that a window of
+// one chunk fits XCONV_LDS_BYTES (every chunk but the last has cc channels, all are whole 16-channel granules).
+// K order: chunk by chunk, inside a chunk k = (tap * granules + granule) * 16 + channel, tap = ky * size + kx, each chunk's K rounded up to
+// 64: one lane's 16-byte MFMA fragment is one granule -- 16 consecutive channels of one tap.  The filters are int8 +1 / -1 (0 in every padded
+// channel, K position and row) in fragment order, [16-row tile][K step][lane][16]: xconv_pack_index.
+#define XCONV_TILE 8                 // edge of the block of output pixels of one workgroup: 64 pixels, four 16-pixel MFMA columns
+#define XCONV_CO_TILE 64             // filters of one workgroup pass: the four waves take 32 pixels x 32 filters each
+#define XCONV_LDS_BYTES (128 * 1024)
+struct XConvArgs {
+    const void *in; int in_stride, in_dt;      // the producer's tensor as stored (bf16, fp16 or fp32); the channels up to C rounded up to 8 are readable
+    const int8_t *wt;                    // [cout_pad / 16][kpad / 64][64][16]
+    const float *scale, *bias;           // [cout_pad] each: alpha_f (* the folded batch-norm scale), the folded shift; zeros past Cout
+    void *out; int out_stride, out_dt;   // out_dt: bf16 / fp16 / fp32
+    int N, H, W, C, Ho, Wo, Cout;
+    int Cstore;                          // channels written per pixel: Cout rounded up to the output's granule (zeros past Cout), a multiple of 4
+    int size, stride, pad, act;          // act: slope family only
+    int te, rs, ww, cc, nchunks, kpad, cout_pad;      // xconv_layout
+};
+// fills te .. cout_pad from (C, Cout, size, stride); returns the bytes of the filters
+inline size_t xconv_layout(XConvArgs &a)
+{
+    a.rs = a.stride < a.size ? a.stride : a.size;
+    a.te = XCONV_TILE; a.ww = (a.te - 1) * a.rs + a.size;
+    if ((size_t)a.ww * a.ww * 32 > XCONV_LDS_BYTES) { a.te = 4; a.ww = 3 * a.rs + a.size; }          // (at most 44 x 44 positions: size 11, stride >= 11)
+    const int cp = (a.C + 15) / 16 * 16, room = (int)(XCONV_LDS_BYTES / ((size_t)a.ww * a.ww) - 16) / 16 * 16;      // a window position holds cc + 16 bytes (xconv.hip: the pitch)
+    a.cc = cp < room ? cp : room;
+    a.nchunks = (cp + a.cc - 1) / a.cc;
+    const int taps = a.size * a.size, last = cp - (a.nchunks - 1) * a.cc;
+    a.kpad = (a.nchunks - 1) * ((taps * a.cc + 63) / 64 * 64) + (taps * last + 63) / 64 * 64;
+    a.cout_pad = (a.Cout + XCONV_CO_TILE - 1) / XCONV_CO_TILE * XCONV_CO_TILE;
+    return (size_t)a.cout_pad * a.kpad;
+}
+// where channel ci of tap `tap` lies in a filter row's K (the layout must be filled)
+inline int xconv_k(const XConvArgs &a, int tap, int ci)
+{
+    const int j = ci / a.cc, cp = (a.C + 15) / 16 * 16, ccj = j + 1 < a.nchunks ? a.cc : cp - j * a.cc;
+    return j * ((a.size * a.size * a.cc + 63) / 64 * 64) + tap * ccj + (ci - j * a.cc);
+}
+inline size_t xconv_pack_index(int row, int k, int ksteps) { return ((((size_t)(row >> 4) * ksteps + (k >> 6)) * 64 + (((k >> 4) & 3) << 4 | (row & 15))) << 4) | (size_t)(k & 15); }
+inline bool xconv_served(int size, int stride, int pad, int h, int w) { return conv_served(size, stride, pad, h, w); }
+hipError_t launch_xconv(const XConvArgs &a, hipStream_t s);
+
 // ---- recurrent layers [rnn] / [gru] / [lstm] (rnn_ops.hip): the stacked gate GEMM with the gate arithmetic in its epilogue ----------
 // One launch computes acc[row][stream] = W[row][:] . [x | h][stream][:] for every row of a layer's stacked weight matrix and every stream
 // (batch index) of the call, then the step arithmetic of `mode` on the accumulators.  The WEIGHTS are the MFMA A operand, the G gates of

@@ -24,7 +24,8 @@ enum LType { L_CONV, L_SHORTCUT, L_ROUTE, L_UPSAMPLE, L_MAXPOOL, L_REORG, L_YOLO
              L_GCONV,                               // [convolutional] with groups > 1 (gconv.hip); Layer::groups
              L_RECUR,                               // [rnn] / [gru] / [lstm] (rnn_ops.hip); Layer::rkind
              L_CRNN,                                // [crnn]: three 3x3 convs around a state map, run by the dense conv kernels; Layer::sub
-             L_LRN, L_CROP };                       // [normalization] / [lrn]: k_lrn, Layer::size / lrn_*; [crop] at inference: k_crop, the output geometry and Layer::crop_adjust
+             L_LRN, L_CROP,                         // [normalization] / [lrn]: k_lrn, Layer::size / lrn_*; [crop] at inference: k_crop, the output geometry and Layer::crop_adjust
+             L_XCONV };                             // [convolutional] with xnor=1 (xconv.hip): int8 signs in d_w, the per-filter scale in d_sc
 enum ConvKernel { K_TILED, K_HALO, K_S2 };      // a conv's own kernel: the tiled family (fp32 / direct / pair form picked by dtype), conv_halo_c32_c64 (3x3/s1, 32 -> 64), conv_s2_c64_c128 (3x3/s2, 64 -> 128)
 // the fused launch a conv is a member of, {members} -> launcher: conv_stem.hip {0, 1, optionally the 1x1 conv 2} -> 1; conv_stem_pair.hip (split-fp16) {0, 1} -> 1; conv_block.hip {1x1 i, 3x3 i + 1} -> i + 1; conv_c3s2.hip {conv3 i, stride-2 conv i + 2} -> i + 2 (both keep K_HALO / K_S2, the fall-back)
 enum FuseKind { F_NONE, F_STEM, F_PSTEM, F_RESBLOCK, F_C3S2 };
@@ -40,7 +41,7 @@ struct Layer {
     int post_act = ACT_LINEAR;           // conv / [connected] / [local] with an activation outside the slope family: applied in place on the output by k_activate after the layer's launch
     bool general = false;                // [shortcut]: a `from` tensor of another shape, or an activation -- runs as k_shortcut, never folded
     int cin = 0, cin_pad = 0, kpad = 0, cout_pad = 0;
-    void *d_w = nullptr; float *d_b = nullptr; float *d_sc = nullptr;   // filters, bias, fp8 per-channel dequant scale
+    void *d_w = nullptr; float *d_b = nullptr; float *d_sc = nullptr;   // filters, bias, fp8 per-channel dequant scale (an L_XCONV: the epilogue's per-filter scale)
     void *d_wf = nullptr;                   // bf16 1x1 conv that can ride in its producer's epilogue: its filters in MFMA-fragment order (tail_fragments)
     int in_dt = DT_BF16;                 // operand type of this conv's MFMA (filters are stored in it)
     int store_dt = DT_BF16;              // element type of this layer's output tensor (mixed plans: an fp8 network with bf16 islands, cfg key yolo_store)
@@ -215,7 +216,7 @@ inline void drop_graph(yolo_ctx *c)      // a plan / parameter / buffer change: 
 }
 
 // ---- layer kinds the planner asks for by more than one name ----
-inline bool computes(const Layer &L) { return L.type == L_CONV || L.type == L_DECONV || L.type == L_GCONV || L.type == L_RECUR || L.type == L_CRNN; }      // has filters and an MFMA kernel ([connected] is an L_CONV; [local] is not among them)
+inline bool computes(const Layer &L) { return L.type == L_CONV || L.type == L_DECONV || L.type == L_GCONV || L.type == L_XCONV || L.type == L_RECUR || L.type == L_CRNN; }      // has filters and an MFMA kernel ([connected] is an L_CONV; [local] is not among them)
 inline bool has_state(const Layer &L) { return L.type == L_RECUR || L.type == L_CRNN; }
 inline bool is_head_layer(const Layer &L) { return L.type == L_YOLO || L.type == L_REGION || L.type == L_DETECT; }      // a detection head: no tensor of its own, an alias of the conv in front of it
 
@@ -238,6 +239,10 @@ void pack_conv(const Layer &L, const float *bn_or_bias, const float *w_oihw, int
 void pack_deconv(const Layer &L, const float *bn_or_bias, const float *w_iohw, int wdt, std::vector<uint8_t> &wbuf, std::vector<float> &bias, int semantics = YOLO_SEM_TF);
 // [convolutional] with groups > 1: w_oihw [filters][cin / groups][k][k] -> the block-diagonal bundles of GConvArgs, batch norm folded as pack_conv folds it
 void pack_gconv(const Layer &L, const float *bn_or_bias, const float *w_oihw, int wdt, std::vector<uint8_t> &wbuf, std::vector<float> &bias, int semantics = YOLO_SEM_TF);
+// [convolutional] with xnor=1: w_oihw [filters][cin][k][k] -> int8 signs in the fragment order of XConvArgs (L.stride decides the channel chunks), the
+// per-filter scale alpha_f (* the folded batch-norm scale) and the folded shift, cout_pad entries each
+void pack_xconv(const Layer &L, const float *bn_or_bias, const float *w_oihw, std::vector<uint8_t> &wbuf, std::vector<float> &scale, std::vector<float> &bias, int semantics = YOLO_SEM_TF);
+inline size_t filter_bytes(const Layer &L) { return (size_t)L.cout_pad * L.kpad * (L.type == L_XCONV ? 1 : dt_size(L.in_dt)); }      // of d_w: a conv, deconv, grouped or xnor conv
 float h2f(uint16_t h);
 void resolve_scales(yolo_ctx *c);
 void channel_scales(const yolo_ctx *c, int idx, std::vector<float> &out);
@@ -270,6 +275,7 @@ TView view_of(const yolo_ctx *c, int idx);
 ConvArgs conv_args(const yolo_ctx *c, const Layer &L, int n);
 DeconvArgs deconv_geometry(int size, int stride, int pad, int h, int w, int cin_pad, int filters, int act, int in_dt);      // everything of DeconvArgs but pointers, strides, N, out_dt, Cstore
 GConvArgs gconv_geometry(int size, int stride, int pad, int h, int w, int cin, int filters, int groups, int act, int in_dt);      // the same of GConvArgs
+XConvArgs xconv_geometry(int size, int stride, int pad, int h, int w, int cin, int filters, int act);      // the same of XConvArgs
 int run_layer(yolo_ctx *c, int i, int n);
 int stage_in(yolo_ctx *c, const void *images, int n, int fmt, int loc, float scale);
 int run_network(yolo_ctx *c, int n, bool lean = false, int fit = -1);      // fit >= 0: the input is a fitted ragged batch (forward_done records its geometry)

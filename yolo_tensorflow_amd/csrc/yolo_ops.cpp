@@ -327,6 +327,39 @@ int yolo_op_conv2d_grouped(const float *x, int n, int h, int w, int cin, const f
     return S.rc;
 }
 
+// darknet's [convolutional] with xnor=1 on host tensors: x [n,h,w,cin] fp32 NHWC, w_oihw [cout][cin][size][size] (the order of darknet's weight files), bias
+// [cout] or NULL.  x is stored as `dtype` first and the sign is taken of the stored value; the filters become alpha_f * sign(w).  out_f32 != 0: the fp32
+// ("head") store of a 16-bit configuration.  An activation outside the slope family runs as the planner plans it: a linear epilogue, then k_activate
+int yolo_op_conv2d_xnor(const float *x, int n, int h, int w, int cin, const float *w_oihw, const float *bias, int size, int stride, int padding,
+                        int cout, int act, int dtype, int out_f32, float *out, int device)
+{
+    if (!x || !w_oihw || !out || n < 1 || h < 1 || w < 1 || cin < 1 || cout < 1 || act < 0 || act >= ACT_COUNT) { g_op_err = "conv2d_xnor: bad arguments"; return YOLO_ERR_INVALID; }
+    if (dtype != YOLO_FP32 && dtype != YOLO_BF16 && dtype != YOLO_FP16) { g_op_err = "conv2d_xnor: dtype (fp32, bf16 or fp16; the fp8 and split-fp16 configurations do not serve xnor=1)"; return YOLO_ERR_UNSUPPORTED; }
+    if (!xconv_served(size, stride, padding, h, w)) { g_op_err = "conv2d_xnor: served are 1 <= size <= 11, stride >= 1, padding >= 0 and a positive output"; return YOLO_ERR_UNSUPPORTED; }
+    OpScope S(device); if (S.rc) { g_op_err = "conv2d_xnor: no HIP device"; return S.rc; }
+    const int dt = dtype == YOLO_FP32 ? DT_F32 : dtype == YOLO_FP16 ? DT_F16 : DT_BF16, odt = (out_f32 || dt == DT_F32) ? DT_F32 : dt;
+    Layer L; L.type = L_XCONV; L.filters = cout; L.size = size; L.stride = stride; L.pad = padding; L.bn = 0; L.in_dt = dt;
+    L.cin = cin; L.cin_pad = roundup(cin, 8);
+    XConvArgs a = xconv_geometry(size, stride, padding, h, w, cin, cout, act_is_slope(act) ? act : ACT_LINEAR);
+    std::vector<float> b0(cout, 0.f); if (bias) memcpy(b0.data(), bias, (size_t)cout * 4);
+    std::vector<uint8_t> wbuf; std::vector<float> sv, bv; pack_xconv(L, b0.data(), w_oihw, wbuf, sv, bv);
+    const int cs = roundup(cout, odt == DT_F32 && dt != DT_F32 ? 4 : 8);
+    const size_t pin = (size_t)n * h * w, pout = (size_t)n * a.Ho * a.Wo;
+    void *d_w = S.upload(wbuf.data(), wbuf.size()); float *d_s = (float *)S.upload(sv.data(), sv.size() * 4), *d_b = (float *)S.upload(bv.data(), bv.size() * 4);
+    float *d_x32 = (float *)S.upload(x, pin * cin * 4);
+    void *d_x = S.alloc(pin * L.cin_pad * dt_size(dt)), *d_o = S.alloc(pout * cs * dt_size(odt)); float *d_o32 = (float *)S.alloc(pout * cout * 4);
+    if (S.rc) { g_op_err = "conv2d_xnor: allocation failed"; return S.rc; }
+    if (!S.ok(launch_from_f32(d_x32, make_view(d_x, n, h, w, cin, L.cin_pad, dt), S.s))) { g_op_err = S.err; return S.rc; }
+    a.in = d_x; a.in_stride = L.cin_pad; a.in_dt = dt; a.wt = (const int8_t *)d_w; a.scale = d_s; a.bias = d_b; a.out = d_o; a.out_stride = cs; a.out_dt = odt; a.N = n; a.Cstore = cs;
+    const TView vo = make_view(d_o, n, a.Ho, a.Wo, cout, cs, odt);
+    if (!S.ok(launch_xconv(a, S.s))) { g_op_err = "conv2d_xnor launch: " + S.err; return S.rc; }
+    if (!act_is_slope(act) && !S.ok(launch_activate(vo, false, act, S.s))) { g_op_err = "conv2d_xnor activation: " + S.err; return S.rc; }
+    if (!S.ok(launch_to_f32(vo, d_o32, S.s))) { g_op_err = S.err; return S.rc; }
+    S.download(out, d_o32, pout * cout * 4);
+    if (S.rc) g_op_err = "conv2d_xnor: " + std::string(hipGetErrorString(hipGetLastError()));
+    return S.rc;
+}
+
 int yolo_op_l2norm(const float *x, int n, int h, int w, int c, int dtype, float *out, int device)
 {
     if (!x || !out || n < 1 || h < 1 || w < 1 || c < 1) { g_op_err = "l2norm: bad arguments"; return YOLO_ERR_INVALID; }

@@ -180,6 +180,46 @@ void pack_gconv(const Layer &L, const float *bn_or_bias, const float *w_oihw, in
     }
 }
 
+// alpha_f = mean |w_f| of binarize_weights (DN/convolutional_layer.c:28-41) with the bits the reference's BUILD gives it.  The source reads as a float running
+// sum in index order and one division; the reference is compiled with -Ofast (its own Makefile's OPTS, and oracle/Makefile), under which the compiler keeps
+// four partial sums -- element j in sum j % 4 --, adds them as (s0 + s2) + (s1 + s3), then the elements past the last whole four in order, and multiplies
+// by the float reciprocal of the count.  That order is restated here (every one of the 128 filters of the fixtures matches bit for bit; the plain running
+// sum differs from it by up to 9 ulp in most of them: NOTEBOOK "XNOR layers")
+static float xnor_alpha(const float *w, int n)
+{
+    float lane[4] = {0.f, 0.f, 0.f, 0.f};
+    const int whole = n / 4 * 4;
+    for (int j = 0; j < whole; j += 4) for (int q = 0; q < 4; ++q) lane[q] += fabsf(w[j + q]);
+    float sum = (lane[0] + lane[2]) + (lane[1] + lane[3]);
+    for (int j = whole; j < n; ++j) sum += fabsf(w[j]);
+    return sum * (1.0f / (float)n);
+}
+
+// [convolutional] with xnor=1 (DN/convolutional_layer.c:28-41 binarize_weights): alpha_f = mean |w_f| as the reference forms it (xnor_alpha), the filters as
+// int8 signs (w > 0 ? 1 : -1) in the fragment order of
+// XConvArgs (kernels.h), every padded channel, K position and row 0.  The epilogue's scale is alpha_f times the batch-norm scale pack_conv folds
+// into the filters, the shift the one it folds into the bias
+void pack_xconv(const Layer &L, const float *bn_or_bias, const float *w_oihw, std::vector<uint8_t> &wbuf, std::vector<float> &scale, std::vector<float> &bias, int semantics)
+{
+    const int n = L.filters, k = L.size, cin = L.cin, per = cin * k * k;
+    XConvArgs g; memset(&g, 0, sizeof g); g.C = cin; g.Cout = n; g.size = k; g.stride = L.stride;
+    const size_t total = xconv_layout(g);
+    scale.assign(g.cout_pad, 0.f); bias.assign(g.cout_pad, 0.f);
+    wbuf.assign(total, 0);
+    const int ksteps = g.kpad / 64;
+    for (int o = 0; o < n; ++o) {
+        const float *w = w_oihw + (size_t)o * per;
+        const float mean = xnor_alpha(w, per);
+        if (L.bn) {
+            const float *beta = bn_or_bias, *gamma = beta + n, *mu = gamma + n, *var = mu + n;
+            const float sc = semantics == YOLO_SEM_DARKNET ? gamma[o] / (sqrtf(var[o]) + 1e-6f) : gamma[o] / sqrtf(var[o] + 1e-5f);
+            scale[o] = mean * sc; bias[o] = beta[o] - mu[o] * sc;
+        } else { scale[o] = mean; bias[o] = bn_or_bias[o]; }
+        for (int ci = 0; ci < cin; ++ci) for (int tap = 0; tap < k * k; ++tap)
+            wbuf[xconv_pack_index(o, xconv_k(g, tap, ci), ksteps)] = w[(size_t)ci * k * k + tap] > 0.f ? 1 : 0xff;
+    }
+}
+
 // one [connected] sublayer of the weight stream (DN/parser.c load_connected_weights: biases, weights [outputs][inputs], then scales, rolling mean,
 // rolling variance when batch-normalised) with its batch norm folded into the rows and the bias (DN/connected_layer.c:161 -> batchnorm_layer.c: the
 // rolling statistics, scale, then the biases), by pack_conv's rule.  Returns the stream behind it
@@ -374,6 +414,15 @@ int yolo_set_weights(yolo_ctx *c, const float *flat, size_t n)
             HIPCK(c, hipMemcpy(L.d_b, bias.data(), bias.size() * 4, hipMemcpyHostToDevice));
             continue;
         }
+        if (L.type == L_XCONV) {           // the file: as a conv's
+            const float *params = p; p += (size_t)L.filters * (L.bn ? 4 : 1);
+            const float *w = p; p += (size_t)L.filters * L.cin * L.size * L.size;
+            pack_xconv(L, params, w, wbuf, osc, bias, c->semantics);
+            HIPCK(c, hipMemcpy(L.d_w, wbuf.data(), wbuf.size(), hipMemcpyHostToDevice));
+            HIPCK(c, hipMemcpy(L.d_b, bias.data(), bias.size() * 4, hipMemcpyHostToDevice));
+            HIPCK(c, hipMemcpy(L.d_sc, osc.data(), osc.size() * 4, hipMemcpyHostToDevice));
+            continue;
+        }
         if (L.type == L_RECUR) { if (int rc = pack_recurrent(c, L, p)) return rc; continue; }
         if (L.type == L_CRNN) {          // input, self, output: three convs in a conv's own file layout
             for (Layer &S : L.sub) {
@@ -500,8 +549,8 @@ int yolo_export(yolo_ctx *c, const char *path)
             }
             continue;
         }
-        if (L.type != L_CONV && L.type != L_LOCAL && L.type != L_DECONV && L.type != L_GCONV) continue;
-        uint64_t sz[3] = {(uint64_t)L.cout_pad * L.kpad * dt_size(L.in_dt), (uint64_t)L.cout_pad, L.d_sc ? (uint64_t)L.cout_pad : 0};
+        if (L.type != L_CONV && L.type != L_LOCAL && L.type != L_DECONV && L.type != L_GCONV && L.type != L_XCONV) continue;
+        uint64_t sz[3] = {(uint64_t)filter_bytes(L), (uint64_t)L.cout_pad, L.d_sc ? (uint64_t)L.cout_pad : 0};
         if (L.type == L_LOCAL) { sz[0] = (uint64_t)L.H * L.W * L.filters * L.size * L.size * L.cin * dt_size(L.in_dt); sz[1] = (uint64_t)L.H * L.W * L.filters; sz[2] = 0; }
         w.put(sz, sizeof sz);
         const void *src[3] = {L.d_w, L.d_b, L.d_sc}; const size_t bytes[3] = {(size_t)sz[0], (size_t)sz[1] * 4, (size_t)sz[2] * 4};
@@ -567,9 +616,9 @@ yolo_ctx *yolo_create_from_file(const char *path, int max_batch, int device, voi
             }
             continue;
         }
-        if (L.type != L_CONV && L.type != L_LOCAL && L.type != L_DECONV && L.type != L_GCONV) continue;
+        if (L.type != L_CONV && L.type != L_LOCAL && L.type != L_DECONV && L.type != L_GCONV && L.type != L_XCONV) continue;
         uint64_t sz[3]; r.get(sz, sizeof sz);
-        uint64_t want[3] = {(uint64_t)L.cout_pad * L.kpad * dt_size(L.in_dt), (uint64_t)L.cout_pad, L.d_sc ? (uint64_t)L.cout_pad : 0};
+        uint64_t want[3] = {(uint64_t)filter_bytes(L), (uint64_t)L.cout_pad, L.d_sc ? (uint64_t)L.cout_pad : 0};
         if (L.type == L_LOCAL) { want[0] = (uint64_t)L.H * L.W * L.filters * L.size * L.size * L.cin * dt_size(L.in_dt); want[1] = (uint64_t)L.H * L.W * L.filters; want[2] = 0; }
         if (!r.ok || sz[0] != want[0] || sz[1] != want[1] || sz[2] != want[2]) { fclose(f); return bail(c, "artifact parameters do not fit the topology (truncated file or different packing)"); }
         void *dst[3] = {L.d_w, L.d_b, L.d_sc}; const size_t bytes[3] = {(size_t)sz[0], (size_t)sz[1] * 4, (size_t)sz[2] * 4};

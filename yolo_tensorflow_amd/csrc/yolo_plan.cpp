@@ -141,8 +141,34 @@ static int parse_grouped_conv(Cursor &k, const Section &s, Layer &L)
     return YOLO_OK;
 }
 
+// XNOR convolution (xnor=1, DN/parser.c:198, DN/convolutional_layer.c:451-456): a layer kind of its own with its own kernel (xconv.hip), the
+// sum of signs on the int8 MFMA.  Like the grouped conv it is never a member of a fused launch, neither end of a 1x1 tail, no host of a folded
+// [shortcut] and nothing for the tile tuner to choose -- every marking pass asks for L_CONV.  (binary=1 without xnor, and flipped=1, are read
+// by nobody: DESIGN.md 7)
+static int parse_xnor_conv(Cursor &k, const Section &s, Layer &L)
+{
+    yolo_ctx *c = k.c; const int i = k.i;
+    if (opt_i(s, "groups", 1) != 1) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [convolutional] with xnor=1 and groups=%d is not served (a grouped XNOR conv)", i, opt_i(s, "groups", 1));
+    if (c->dtype == YOLO_FP8) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [convolutional] with xnor=1 is not served in the fp8 configuration", i);
+    if (c->split()) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [convolutional] with xnor=1 is not served in the split-fp16 configuration", i);
+    if (i == 0) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [convolutional] with xnor=1 as the network's first layer is not served (the image is not negative anywhere, so its signs say nothing, and it is read by the dense kernels only)", i);
+    L.type = L_XCONV; read_conv_keys(s, L);
+    if (L.filters < 1) return fail(c, YOLO_ERR_INVALID, "layer %d: conv filters %d", i, L.filters);
+    if (L.size < 1 || L.size > CONV_MAX_SIZE) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: xnor conv size %d (1..%d are served)", i, L.size, CONV_MAX_SIZE);
+    if (L.stride < 1 || L.pad < 0) return fail(c, YOLO_ERR_INVALID, "layer %d: conv stride %d, padding %d", i, L.stride, L.pad);
+    if (k.H + 2 * L.pad < L.size || k.W + 2 * L.pad < L.size) return fail(c, YOLO_ERR_INVALID, "layer %d: conv larger than its padded input (%d x %d with padding %d under a size %d conv)", i, k.W, k.H, L.pad, L.size);
+    if (int r = plan_activation(c, i, s, "logistic", false)) return r;
+    L.in_dt = c->act_dt(); L.store_dt = c->act_dt();
+    L.cin = k.C; L.cin_pad = roundup(k.C, 8);
+    { XConvArgs g; memset(&g, 0, sizeof g); g.C = k.C; g.Cout = L.filters; g.size = L.size; g.stride = L.stride; xconv_layout(g); L.kpad = g.kpad; L.cout_pad = g.cout_pad; }      // cout_pad * kpad bytes of filters
+    conv_out(k, L);
+    conv_totals(c, L, L.cin, k.H, k.W);
+    return YOLO_OK;
+}
+
 static int parse_convolutional(Cursor &k, const Section &s, Layer &L)
 {
+    if (opt_i(s, "xnor", 0)) return parse_xnor_conv(k, s, L);
     if (opt_i(s, "groups", 1) != 1) return parse_grouped_conv(k, s, L);
     yolo_ctx *c = k.c; const int i = k.i;
     // (the variable: A/B of the dense kernels against the grouped kernel run with one group, tools/wide_conv_rate.py -- wherever that kernel serves the layer)
@@ -310,6 +336,7 @@ static int parse_detection(Cursor &k, const Section &s, Layer &L)
     L.type = L_DETECT; L.classes = opt_i(s, "classes", 1); L.na = opt_i(s, "num", 1); L.side = opt_i(s, "side", 7); L.sqr = opt_i(s, "sqrt", 0);
     if (opt_i(s, "coords", 4) != 4 || opt_i(s, "softmax", 0)) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [detection] with coords != 4 or softmax", i);
     if (i > 0 && c->layers[i - 1].type == L_GCONV) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: a [convolutional] with groups=%d directly in front of a [detection] head is not served ([detection] must follow a [connected] layer)", i - 1, c->layers[i - 1].groups);
+    if (i > 0 && c->layers[i - 1].type == L_XCONV) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: a [convolutional] with xnor=1 directly in front of a [detection] head is not served ([detection] must follow a [connected] layer)", i - 1);
     if (i == 0 || !c->layers[i - 1].fc) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [detection] must follow a [connected] layer", i);
     if (k.C != L.side * L.side * (L.classes + L.na * 5)) return fail(c, YOLO_ERR_INVALID, "layer %d: [detection] expects %d inputs, got %d", i, L.side * L.side * (L.classes + L.na * 5), k.C);
     if (c->attrs && c->attrs != 5 + L.classes) return fail(c, YOLO_ERR_UNSUPPORTED, "heads with different class counts");
@@ -452,6 +479,7 @@ static int parse_head(Cursor &k, const Section &s, Layer &L)
     L.na = (int)L.anchors.size() / 2;
     if (L.na > 16) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: more than 16 anchors", i);
     if (i > 0 && c->layers[i - 1].type == L_GCONV) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: a [convolutional] with groups=%d directly in front of a [%s] head is not served (the head's objectness plane and lean decode belong to the dense kernels; put a dense 1x1 conv in between)", i - 1, c->layers[i - 1].groups, s.type.c_str());
+    if (i > 0 && c->layers[i - 1].type == L_XCONV) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: a [convolutional] with xnor=1 directly in front of a [%s] head is not served (the head's fp32 store, objectness plane and lean decode belong to the dense kernels; put a dense 1x1 conv in between)", i - 1, s.type.c_str());
     if (i == 0 || c->layers[i - 1].type != L_CONV) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: head must follow a conv", i);
     if (k.C != L.na * (5 + L.classes)) return fail(c, YOLO_ERR_INVALID, "layer %d: head expects %d channels, conv gives %d", i, L.na * (5 + L.classes), k.C);
     if (c->attrs && c->attrs != 5 + L.classes) return fail(c, YOLO_ERR_UNSUPPORTED, "heads with different class counts");
@@ -498,7 +526,7 @@ static int parse_softmax(Cursor &k, const Section &s, Layer &L)
     // the logits are never rounded to 16 bits: the conv that reaches this layer directly, or through one [avgpool], writes fp32
     int p = i - 1;
     if (p >= 0 && c->layers[p].type == L_AVGPOOL) p = c->layers[p].in[0];
-    if (p >= 0 && (c->layers[p].type == L_CONV || c->layers[p].type == L_GCONV || c->layers[p].type == L_RECUR)) c->layers[p].head = true;      // (not L_DECONV)
+    if (p >= 0 && (c->layers[p].type == L_CONV || c->layers[p].type == L_GCONV || c->layers[p].type == L_XCONV || c->layers[p].type == L_RECUR)) c->layers[p].head = true;      // (not L_DECONV)
     return YOLO_OK;
 }
 
@@ -1095,11 +1123,11 @@ int allocate(yolo_ctx *c)
     HIPCK(c, hipMalloc((void **)&c->d_sbox, nr * 16)); HIPCK(c, hipMalloc((void **)&c->d_slabel, nr * 4)); HIPCK(c, hipMalloc((void **)&c->d_sscore, nr * 4));
     HIPCK(c, hipMalloc((void **)&c->d_counts, (size_t)c->max_batch * 4));
     // filters
-    for (auto &L : c->layers) if (L.type == L_CONV || L.type == L_DECONV || L.type == L_GCONV) {
-        size_t wb = (size_t)L.cout_pad * L.kpad * dt_size(L.in_dt);
+    for (auto &L : c->layers) if (L.type == L_CONV || L.type == L_DECONV || L.type == L_GCONV || L.type == L_XCONV) {
+        size_t wb = filter_bytes(L);
         HIPCK(c, hipMalloc(&L.d_w, wb)); HIPCK(c, hipMemsetAsync(L.d_w, 0, wb, c->stream));
         HIPCK(c, hipMalloc((void **)&L.d_b, (size_t)L.cout_pad * 4)); HIPCK(c, hipMemsetAsync(L.d_b, 0, (size_t)L.cout_pad * 4, c->stream));
-        if (L.in_dt == DT_FP8) { HIPCK(c, hipMalloc((void **)&L.d_sc, (size_t)L.cout_pad * 4)); HIPCK(c, hipMemsetAsync(L.d_sc, 0, (size_t)L.cout_pad * 4, c->stream)); }
+        if (L.in_dt == DT_FP8 || L.type == L_XCONV) { HIPCK(c, hipMalloc((void **)&L.d_sc, (size_t)L.cout_pad * 4)); HIPCK(c, hipMemsetAsync(L.d_sc, 0, (size_t)L.cout_pad * 4, c->stream)); }
     }
     size_t keep_bytes = 0;
     for (size_t i = 0; i < c->layers.size(); ++i) {

@@ -91,6 +91,26 @@ static GConvArgs gconv_args(const yolo_ctx *c, const Layer &L, int n)
     return a;
 }
 
+XConvArgs xconv_geometry(int size, int stride, int pad, int h, int w, int cin, int filters, int act)
+{
+    XConvArgs a; memset(&a, 0, sizeof a);
+    a.size = size; a.stride = stride; a.pad = pad; a.H = h; a.W = w; a.C = cin; a.Cout = filters; a.act = act;
+    a.Ho = (h + 2 * pad - size) / stride + 1; a.Wo = (w + 2 * pad - size) / stride + 1;
+    xconv_layout(a);
+    return a;
+}
+
+// (the input is read in the type its producer stored it in -- an fp32 tensor of a 16-bit network included: the sign needs no conversion)
+static XConvArgs xconv_args(const yolo_ctx *c, const Layer &L, int n)
+{
+    const TView in = view_of(c, L.in[0]);
+    XConvArgs a = xconv_geometry(L.size, L.stride, L.pad, in.h, in.w, L.cin, L.filters, L.act);
+    a.in = in.ptr; a.in_stride = in.stride; a.in_dt = in.dt; a.wt = (const int8_t *)L.d_w; a.scale = L.d_sc; a.bias = L.d_b;
+    a.out = L.out.ptr; a.out_stride = L.out.stride; a.out_dt = L.out.dt; a.N = n;
+    a.Cstore = store_width(L, L.filters);
+    return a;
+}
+
 // split fp16: a layer that moves or interpolates values runs in fp32 between a join (hi + lo) and a split
 static int via_f32(yolo_ctx *c, const Layer &L, int n)
 {
@@ -406,6 +426,10 @@ int run_layer(yolo_ctx *c, int i, int n)
         HIPCK(c, launch_gconv(gconv_args(c, L, n), s));
         if (L.post_act != ACT_LINEAR) HIPCK(c, launch_activate(nview(n, L.out), false, L.post_act, s));
         break;
+    case L_XCONV:
+        HIPCK(c, launch_xconv(xconv_args(c, L, n), s));
+        if (L.post_act != ACT_LINEAR) HIPCK(c, launch_activate(nview(n, L.out), false, L.post_act, s));
+        break;
     case L_ACTIVATE: {
         TView out = nview(n, L.out);
         if (!L.inplace) {          // a tensor of its own (keep_layers, a second reader of the producer, a concat window): copied first
@@ -515,12 +539,12 @@ int stage_in(yolo_ctx *c, const void *images, int n, int fmt, int loc, float sca
     return YOLO_OK;
 }
 
-// the layer sequence of one forward.  `skip_conv`: the timing pass that runs everything but the convs (dense and grouped: conv_flops counts both); `ev`: per-layer events (yolo_time_layers)
+// the layer sequence of one forward.  `skip_conv`: the timing pass that runs everything but the convs (dense, grouped and xnor: conv_flops counts them all); `ev`: per-layer events (yolo_time_layers)
 static int run_layers(yolo_ctx *c, int n, bool skip_conv = false, std::vector<hipEvent_t> *ev = nullptr)
 {
     const int NL = (int)c->layers.size();
     for (int i = 0; i < NL; ++i) {
-        if (!(skip_conv && (c->layers[i].type == L_CONV || c->layers[i].type == L_GCONV))) { int r = run_layer(c, i, n); if (r) return r; }
+        if (!(skip_conv && (c->layers[i].type == L_CONV || c->layers[i].type == L_GCONV || c->layers[i].type == L_XCONV))) { int r = run_layer(c, i, n); if (r) return r; }
         if (ev) HIPCK(c, hipEventRecord((*ev)[i + 1], c->stream));
     }
     return YOLO_OK;

@@ -47,7 +47,7 @@ EXPORTS = [
     "yolo_set_hier_thresh", "yolo_set_hierarchy_mode", "yolo_darknet_boxes_map", "yolo_tree_geometry", "yolo_tree_read", "yolo_plan_check", "yolo_plan_table", "yolo_plan_dump",
     "yolo_op_tree_softmax", "yolo_op_tree_top", "yolo_activation_code", "yolo_op_activate", "yolo_op_shortcut",
     "yolo_output_map_geometry", "yolo_output_map", "yolo_label_map", "yolo_segment_images_u8", "yolo_op_deconv2d", "yolo_op_l2norm", "yolo_op_upsample", "yolo_op_label_map",
-    "yolo_op_conv2d_grouped", "yolo_op_conv2d_pad", "yolo_op_lrn",
+    "yolo_op_conv2d_grouped", "yolo_op_conv2d_xnor", "yolo_op_conv2d_pad", "yolo_op_lrn",
     "yolo_num_state_tensors", "yolo_state_geometry", "yolo_get_state", "yolo_set_state", "yolo_reset_state",
     "yolo_tile_windows", "yolo_detect_tiled_u8",
     "yolo_vector_inputs", "yolo_forward_vectors", "yolo_sequence", "yolo_set_temperature", "yolo_reset_temperature", "yolo_op_sample",
@@ -167,6 +167,7 @@ def load_library():
     l.yolo_segment_images_u8.argtypes = [P, P, P, I, I, F, P, P]
     l.yolo_op_deconv2d.argtypes = [P, I, I, I, I, P, P, I, I, I, I, I, I, I, P, I]
     l.yolo_op_conv2d_grouped.argtypes = [P, I, I, I, I, P, P, I, I, I, I, I, I, I, I, P, I]
+    l.yolo_op_conv2d_xnor.argtypes = [P, I, I, I, I, P, P, I, I, I, I, I, I, I, P, I]
     l.yolo_op_l2norm.argtypes = [P, I, I, I, I, I, P, I]
     l.yolo_op_lrn.argtypes = [P, I, I, I, I, I, C.c_float, C.c_float, C.c_float, I, P, I]
     l.yolo_op_upsample.argtypes = [P, I, I, I, I, I, F, I, P, I]
@@ -998,6 +999,23 @@ def op_conv2d_grouped(x, w_oihw, bias=None, groups=1, stride=1, padding=0, activ
     out = np.empty((n, max(ho, 0), max(wo, 0), cout), dtype=np.float32)
     _op_check(load_library().yolo_op_conv2d_grouped(x.ctypes.data, n, h, w, cin, w_oihw.ctypes.data, b.ctypes.data if b is not None else None, size, stride, padding,
                                                     cout, groups, activation_code(activation), dtype, 1 if out_f32 else 0, out.ctypes.data, device), "yolo_op_conv2d_grouped")
+    return out
+
+
+def op_conv2d_xnor(x, w_oihw, bias=None, stride=1, padding=0, activation="linear", dtype=BF16, out_f32=False, device=0):
+    """darknet's [convolutional] with xnor=1 (yolo_op_conv2d_xnor): x [n, h, w, cin], rounded to `dtype` before its sign is taken (+1 where
+    > 0, else -1; a tap outside the image: 0), w_oihw [cout, cin, size, size] (the weight file's order), used as mean|w_f| * sign(w) ->
+    [n, (h + 2 padding - size) // stride + 1, ..., cout] float32.  out_f32: the fp32 store of a 16-bit configuration."""
+    x = _f32(x); w_oihw = _f32(w_oihw)
+    n, h, w, cin = x.shape
+    if w_oihw.ndim != 4 or w_oihw.shape[1] != cin or w_oihw.shape[2] != w_oihw.shape[3]:
+        raise YoloError("op_conv2d_xnor: filters must be [cout, cin, size, size]")
+    cout, size = w_oihw.shape[0], w_oihw.shape[2]
+    b = _f32(bias) if bias is not None else None
+    ho, wo = (h + 2 * padding - size) // stride + 1, (w + 2 * padding - size) // stride + 1
+    out = np.empty((n, max(ho, 0), max(wo, 0), cout), dtype=np.float32)
+    _op_check(load_library().yolo_op_conv2d_xnor(x.ctypes.data, n, h, w, cin, w_oihw.ctypes.data, b.ctypes.data if b is not None else None, size, stride, padding,
+                                                 cout, activation_code(activation), dtype, 1 if out_f32 else 0, out.ctypes.data, device), "yolo_op_conv2d_xnor")
     return out
 
 
