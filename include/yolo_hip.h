@@ -498,6 +498,43 @@ int yolo_classify(yolo_ctx *ctx, const void *images, int n, int fmt, int loc, fl
 /* ... over a ragged batch of native-size images through the one-launch fit of yolo_forward_images_u8 */
 int yolo_classify_images_u8(yolo_ctx *ctx, const uint8_t *pixels, size_t bytes, const yolo_image_desc *descs, int n, int fit, int loc,
                             int top_k, int32_t *classes_out, float *probs_out, int out_loc);
+/* ---- multi-view classification: darknet's ten-crop and flip averaging (DN/examples/classifier.c:234-301 validate_classifier_10,
+ * `classifier valid10`; DN/examples/cifar.c:101-128 test_cifar_multi).  Every image is predicted over K views and the K rows are added.
+ * YOLO_VIEWS_FLIP, K = 2: view 0 is the image fitted by `fit` (any fit yolo_classify_images_u8 takes), view 1 its mirror,
+ * view1[y][x][c] = view0[y][net_w - 1 - x][c] (flip_image on the network-sized image; [net] yolo_input_mul / yolo_input_add as in view 0).
+ * YOLO_VIEWS_TEN_CROP, K = 10, shift >= 0 (the reference's constant is 32): with W' = net_w + shift and H' = net_h + shift, R is darknet's
+ * (float)p/255. image put through resize_image(., W', H') -- the image itself where it already has that size --, and pixel (x, y) of view v
+ * is R[clamp(y + dy, 0, H' - 1)][cx] for v = 0..4 and R[..][W' - 1 - cx] for v = 5..9 (flip_image on R, then the same crops), with
+ * cx = clamp(x + dx, 0, W' - 1) and (dx, dy) = (-s,-s), (s,-s), (0,0), (-s,s), (s,s) indexed by v % 5.  The reference's quirks are kept: the
+ * (0,0) view is the top-left window, the -s views replicate the edge.  `fit` is not read.  No view is stored at W' x H'; the source bytes are
+ * uploaded once. */
+enum yolo_views { YOLO_VIEWS_FLIP = 1, YOLO_VIEWS_TEN_CROP = 2 };
+/* one view: the crop offsets in pixels and whether the image is mirrored (16 bytes) */
+typedef struct yolo_view { int32_t dy, dx, flip, pad; } yolo_view;
+/* The views of a mode, in view order: FLIP {0,0,0}, {0,0,1}; TEN_CROP the table above for `shift`.  *count is always written; at most `cap`
+ * views are written to out (cap = 0 / out = NULL: the count only).  YOLO_ERR_INVALID for an unknown `views`, shift < 0, count == NULL.
+ * Host-side: no context, no device. */
+int yolo_view_table(int views, int shift, yolo_view *out, int cap, int *count);
+/* descs[n_images] whole images in `pixels`, as for yolo_classify_images_u8; n_images is NOT bound by max_batch.  Slots are ordered
+ * image * K + view and run max_batch per network step, ceil(n_images * K / max_batch) steps: images may share a step, one image's views may
+ * span steps.  One launch per step fits that step's slots straight from the source bytes; every slot's row -- the context's classifier
+ * output, for a [softmax] with a tree in the context's hierarchy mode (classifier.c:287 is YOLO_HIER_LEAVES) -- is kept on the device, and
+ * after the last step ONE launch forms sum[i][c] = ((((0 + p_0) + p_1) + ..) + p_{K-1}) in fp32 in view order (axpy_cpu's order), multiplies it
+ * by `scale` once (1.0f leaves the bits alone, 1.0f / K gives the mean) and selects: top_k == 0: probs_out receives the n_images x classes
+ * sums; 0 < top_k <= min(32, classes): classes_out / probs_out [n_images][top_k], value descending, equal values by ascending class (the order
+ * of yolo_classify and of the reference's top_k), and only these records are copied.  The result does not depend on max_batch and is
+ * bit-reproducible from run to run.  Every check runs before any launch.  YOLO_ERR_INVALID: a detector, map or vector-input context; a
+ * descriptor yolo_forward_images_u8 refuses; an unknown `views`; shift < 0; top_k out of range; TEN_CROP with W' < 2 or H' < 2 (resize_image
+ * divides by W' - 1) or extents that do not fit an int.  YOLO_ERR_UNSUPPORTED, naming what is refused: a context with recurrent state
+ * (yolo_num_state_tensors > 0: a batch slot is a stream there), the cv2 fits on a network of C != 3 planes, fp8.  Planes networks are served
+ * in both modes.  There is no captured-graph form. */
+int yolo_classify_views_u8(yolo_ctx *ctx, const uint8_t *pixels, size_t bytes, const yolo_image_desc *descs, int n_images, int views, int fit,
+                           int shift, int loc, float scale, int top_k, int32_t *classes_out, float *probs_out, int out_loc);
+/* the reduction launch alone over host arrays: rows [n * views][len] fp32 (slot = image * views + view), 1 <= views <= 32, any len >= 1 ->
+ * sums_out [n][len]; top_k > 0 (<= min(32, len)): also classes_out / top_out [n][top_k] from the same launch (else NULL; NaN and -inf are
+ * never selected) */
+int yolo_op_view_reduce(const float *rows, int n, int views, int len, float scale, int top_k, float *sums_out, int32_t *classes_out,
+                        float *top_out, int device);
 /* darknet's [avgpool] on x [n,h,w,c] fp32 stored as `dtype` (YOLO_FP32 / BF16 / FP16 / FP16X2) first: out [n,c] fp32 */
 int yolo_op_avgpool(const float *x, int n, int h, int w, int c, int dtype, float *out, int device);
 /* Activations: the names DN/activations.c get_activation accepts.  YOLO_ACT_LINEAR .. YOLO_ACT_RELIE are the slope family, max(v, v * slope)

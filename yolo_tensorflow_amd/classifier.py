@@ -39,9 +39,19 @@ class Classifier:
     def _name(self, k):
         return self.names[k] if self.names is not None and 0 <= k < len(self.names) else int(k)
 
-    def classify_from_images(self, images, top=5):
+    VIEWS = {"flip": hip.VIEWS_FLIP, "ten_crop": hip.VIEWS_TEN_CROP}
+
+    def classify_from_images(self, images, top=5, views=None, shift=32):
         """images: a list of uint8 [h, w, C] arrays of any sizes (RGB; a network of C planes: [h, w, C], one plane also [h, w]) -> per image [(name_or_index, prob), ...], `top` entries,
-        probability descending."""
+        probability descending.  views: None predicts each image once; "flip" averages the image (fitted by the classifier's fit) and its mirror, as
+        darknet's test_cifar_multi adds them; "ten_crop" averages darknet's `classifier valid10` views, five crops of the image resized to the network
+        input + `shift` and the same five of its mirror (the fit is not used).  Both return the MEAN over the views, formed and ranked on the device."""
+        if views is not None:
+            if views not in self.VIEWS:
+                raise hip.YoloError("Classifier: views must be None, 'flip' or 'ten_crop', got %r" % (views,))
+            mode = self.VIEWS[views]
+            cls, probs = self.engine.classify_views(images, mode, fit=self.fit, shift=shift, scale=1.0 / len(hip.view_table(mode, shift)), top_k=top)
+            return [[(self._name(int(k)), float(q)) for k, q in zip(c, p)] for c, p in zip(cls, probs)]
         out = []
         for lo in range(0, len(images), self.max_batch):
             cls, probs = self.engine.classify_images(images[lo:lo + self.max_batch], fit=self.fit, top_k=top)

@@ -120,6 +120,25 @@ __device__ __forceinline__ float block_sum(float s, float *red)
     for (int w = 1; w < nw; ++w) r += red[w];
     return r;
 }
+// The top_k best of v[0 .. len) (value descending, equal values by ascending index) to cls / tkp; slots past len: index -1, value 0.  Thread t owns the
+// entries i = t, t + nt, ... and comes in with the best of them in (bp, bi) (bi < 0: none); a round takes the block's best, and only its owner looks for its
+// next one.  v (LDS or global memory) is consumed: a taken entry becomes -inf, which -- like a NaN met in a rescan -- is never selected.  Called by every
+// thread of the block; shared by the [softmax] launches and k_view_reduce.
+__device__ void block_topk(float *v, int len, float bp, int bi, int top_k, int *cls, float *tkp, float *red_p, int *red_i)
+{
+    const int t = threadIdx.x, nt = blockDim.x;
+    for (int r = 0; r < top_k; ++r) {
+        float p = bp; int i = bi;
+        block_best(p, i, red_p, red_i);
+        if (t == 0) { cls[r] = i; tkp[r] = i >= 0 ? p : 0.f; }
+        if (i >= 0 && i % nt == t) {
+            v[i] = -INFINITY;                // taken
+            bp = 0.f; bi = -1;
+            for (int j = t; j < len; j += nt) { const float q = v[j]; if (q > -INFINITY && ranks_before(q, j, bp, bi)) { bp = q; bi = j; } }
+        }
+    }
+    __syncthreads();
+}
 // softmax of the `len` logits in LDS at v (DN/blas.c:305-321: e = exp(x / temp - max / temp), p = e / sum), probabilities to
 // probs[0 .. len) and left in v; then, top_k > 0, the top_k best (probability descending, index ascending) to cls / tkp.
 // Called by every thread of the block.
@@ -138,19 +157,7 @@ __device__ void block_softmax_topk(float *v, int len, float temp, float *probs, 
         v[i] = p; probs[i] = p;
         if (ranks_before(p, i, bp, bi)) { bp = p; bi = i; }
     }
-    // selection: every thread keeps the best of the entries it owns (i = t, t + nt, ...); a round takes the block's best, and only
-    // its owner looks for its next one
-    for (int r = 0; r < top_k; ++r) {
-        float p = bp; int i = bi;
-        block_best(p, i, red_p, red_i);
-        if (t == 0) { cls[r] = i; tkp[r] = i >= 0 ? p : 0.f; }
-        if (i >= 0 && i % nt == t) {
-            v[i] = -1.f;                // taken (probabilities are >= 0)
-            bp = 0.f; bi = -1;
-            for (int j = t; j < len; j += nt) { const float q = v[j]; if (q >= 0.f && ranks_before(q, j, bp, bi)) { bp = q; bi = j; } }
-        }
-    }
-    __syncthreads();
+    block_topk(v, len, bp, bi, top_k, cls, tkp, red_p, red_i);
 }
 
 constexpr int SM_NT = 256, SM_MAX = CLS_SOFTMAX_MAX;
@@ -215,7 +222,38 @@ __global__ __launch_bounds__(FU_NT) void k_avgpool_softmax(const float *x, int x
         block_softmax_topk(v + g * len, len, temp, probs + (size_t)img * p_stride + (size_t)g * len, top_k, cls + (size_t)img * top_k, tkp + (size_t)img * top_k, red_p, red_i);
 }
 
+// ---- multi-view classification: the views' rows of every image added in view order, scaled, and the top-k of the result, one workgroup per image.
+//      rows [n * views][len]; lane t forms the classes t, t + 256, ...: s = 0; s = s + row_v[c] for v = 0 .. views - 1 (axpy_cpu's order, DN/blas.c), then
+//      s * scale.  The selection runs over a scratch copy of the scaled row in global memory (any len; a lane re-reads only what it wrote itself). ----
+constexpr int VR_NT = 256;
+
+__global__ __launch_bounds__(VR_NT) void k_view_reduce(const float *rows, int views, int len, float scale, float *sums, float *work, int top_k, int *cls, float *tkp)
+{
+    __shared__ float red_p[16];
+    __shared__ int red_i[16];
+    const int img = blockIdx.x, t = threadIdx.x;
+    const float *src = rows + (size_t)img * views * len;
+    float *dst = sums + (size_t)img * len, *w = top_k > 0 ? work + (size_t)img * len : nullptr;
+    float bp = 0.f; int bi = -1;
+    for (int i = t; i < len; i += VR_NT) {
+        float s = 0.f;
+        for (int v = 0; v < views; ++v) s = s + src[(size_t)v * len + i];
+        s = s * scale;
+        dst[i] = s;
+        if (top_k > 0) { w[i] = s; if (s > -INFINITY && ranks_before(s, i, bp, bi)) { bp = s; bi = i; } }
+    }
+    if (top_k > 0) block_topk(w, len, bp, bi, top_k, cls + (size_t)img * top_k, tkp + (size_t)img * top_k, red_p, red_i);
+}
+
 }  // namespace
+
+hipError_t launch_view_reduce(const ViewReduceArgs &a, hipStream_t s)
+{
+    if (!a.rows || !a.sums || a.n < 1 || a.views < 1 || a.views > VIEWS_MAX || a.len < 1 || a.top_k < 0 || a.top_k > CLS_TOPK_MAX || a.top_k > a.len) return hipErrorInvalidValue;
+    if (a.top_k > 0 && (!a.work || !a.cls || !a.topk)) return hipErrorInvalidValue;
+    k_view_reduce<<<a.n, VR_NT, 0, s>>>(a.rows, a.views, a.len, a.scale, a.sums, a.work, a.top_k, a.cls, a.topk);
+    return hipGetLastError();
+}
 
 hipError_t launch_avgpool(const TView &in, bool in_pair, const TView &out, hipStream_t s)
 {

@@ -147,6 +147,18 @@ __device__ __forceinline__ void px_center_crop(const At &at, int iw, int ih, int
     px_resize<NC>(at, iw, ih, rw, rh, r, c, c0, nc, v);
 }
 
+// One pixel of one of darknet's ten validation views (DN/examples/classifier.c:268-283, `classifier valid10`): the image resized to R = (net_w + shift) x
+// (net_h + shift) -- load_image_color's resize_image, the image itself where it has that size --, then crop_image(R, dx, dy, net_w, net_h) with dx, dy in
+// {-shift, 0, shift}: the coordinates are CLAMPED to R (the -shift views replicate its edge; the (0, 0) view is the top-left window, not the centre), and
+// the views 5..9 crop flip_image(R): column c of the mirrored image is column rw - 1 - c of R.  No R is ever stored: px_resize at that coordinate.
+template <int NC, class At>
+__device__ __forceinline__ void px_ten_crop(const At &at, int iw, int ih, int net_w, int net_h, int shift, int dy, int dx, int flip, int oy, int ox, int c0, int nc, float *v)
+{
+    const int rw = net_w + shift, rh = net_h + shift;
+    const int r = min(max(oy + dy, 0), rh - 1), c = min(max(ox + dx, 0), rw - 1);
+    px_resize<NC>(at, iw, ih, rw, rh, r, flip ? rw - 1 - c : c, c0, nc, v);
+}
+
 // `cv2.resize(image_float32, (ow, oh))` as V2/utils.py:13-27 calls it (INTER_LINEAR on a float32 image, after BGR -> RGB) followed by the
 // reference's `/ 225.0` -- restated from OpenCV's published resize (imgproc/resize.cpp, the CV_32F linear path): half-pixel centres,
 //   fx = (float)((dx + 0.5) * (double)(src_w / dst_w as 1 / (dst_w / src_w)) - 0.5); sx = floor(fx); fx -= sx;
@@ -747,14 +759,19 @@ struct AtPacked {
     __device__ __forceinline__ float operator()(int y, int x, int c) const
     {
         const unsigned v = (unsigned)__builtin_amdgcn_raw_buffer_load_b8(rsrc, base + (unsigned)y * pitch + (unsigned)x * px + (unsigned)c, 0, 0);
-        // STRETCH and CV2 read the byte as a float (the /255 and /225 are part of px_stretch / px_cv2); LETTERBOX and CENTER_CROP read darknet's 0..1 value
-        return fit == FIT_LETTERBOX || fit == FIT_CENTER_CROP ? fit_unit_value(FIT_LETTERBOX, v) : (float)v;
+        // STRETCH and CV2 read the byte as a float (the /255 and /225 are part of px_stretch / px_cv2); LETTERBOX, CENTER_CROP and TEN_CROP read darknet's 0..1 value
+        return fit == FIT_LETTERBOX || fit == FIT_CENTER_CROP || fit == FIT_TEN_CROP ? fit_unit_value(FIT_LETTERBOX, v) : (float)v;
     }
 };
 
 __device__ __forceinline__ unsigned row_pitch(const ImgDesc &d, unsigned px) { return (unsigned)d.w * px; }
 __device__ __forceinline__ unsigned row_pitch(const WinDesc &d, unsigned) { return (unsigned)d.pitch; }
-// Desc: ImgDesc (whole images) or WinDesc (windows of larger images, yolo_detect_tiled_u8): the same arithmetic over (h, w) pixels read at a row pitch
+__device__ __forceinline__ unsigned row_pitch(const ViewDesc &d, unsigned px) { return (unsigned)d.w * px; }
+// the column of the fitted image an output column shows: a mirrored view (flip_image on the network-sized image) reads the fit at net_w - 1 - ox
+template <class Desc> __device__ __forceinline__ int view_column(const Desc &, int ox, int) { return ox; }
+__device__ __forceinline__ int view_column(const ViewDesc &d, int ox, int net_w) { return d.flip ? net_w - 1 - ox : ox; }
+// Desc: ImgDesc (whole images), WinDesc (windows of larger images, yolo_detect_tiled_u8) or ViewDesc (one view of an image per slot, yolo_classify_views_u8):
+// the same arithmetic over (h, w) pixels read at a row pitch.  FIT_TEN_CROP (ViewDesc only) mirrors inside px_ten_crop, in the resized image's coordinates
 template <typename T, int FIT, class Desc, int NCH>
 __global__ __launch_bounds__(256) void k_fit_images(const uint8_t *pixels, unsigned bytes, const Desc *descs, int net_h, int net_w, T *out, int out_stride,
                                                     float post_mul, float post_add, int nch, int tiles)
@@ -767,7 +784,7 @@ __global__ __launch_bounds__(256) void k_fit_images(const uint8_t *pixels, unsig
     if (p >= net_h * net_w) return;
     const Planes<NCH> pl(g, nch);
     const Desc d = descs[img];
-    const int oy = p / net_w, ox = p - oy * net_w;
+    const int oy = p / net_w, ox = FIT == FIT_TEN_CROP ? p - oy * net_w : view_column(d, p - oy * net_w, net_w);
     const unsigned px = NCH ? NCH : (unsigned)nch;
     const AtPacked at{__builtin_amdgcn_make_buffer_rsrc((void *)pixels, 0, bytes, 0x00020000), (unsigned)d.offset, row_pitch(d, px), FIT, px};
     float v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -778,6 +795,7 @@ __global__ __launch_bounds__(256) void k_fit_images(const uint8_t *pixels, unsig
             letterbox_dims(net_w, net_h, d.w, d.h, &new_w, &new_h);
             px_letterbox<NC>(at, d.w, d.h, new_w, new_h, (net_w - new_w) / 2, (net_h - new_h) / 2, oy, ox, pl.c0, pl.nc, v);
         } else if (FIT == FIT_CENTER_CROP) px_center_crop<NC>(at, d.w, d.h, net_w, net_h, oy, ox, pl.c0, pl.nc, v);
+        else if constexpr (FIT == FIT_TEN_CROP) px_ten_crop<NC>(at, d.w, d.h, net_w, net_h, d.shift, d.dy, d.dx, d.flip, oy, ox, pl.c0, pl.nc, v);
         else if constexpr (NCH == 3) px_cv2(at, d.h, d.w, net_h, net_w, oy, ox, FIT == FIT_CV2_BGR, 225.0f, v);
         // YOLOv1's `x * 2 - 1` ([net] yolo_input_mul / yolo_input_add), as px_stretch applies it
 #pragma unroll
@@ -823,6 +841,32 @@ hipError_t launch_fit_windows(const uint8_t *pixels, size_t bytes, const WinDesc
     const dim3 grid((unsigned)tiles, (unsigned)n);
     if (fit == FIT_STRETCH) FIT_LAUNCH(FIT_STRETCH, WinDesc, d_wins);
     else FIT_LAUNCH(FIT_LETTERBOX, WinDesc, d_wins);
+    return hipGetLastError();
+}
+
+// the same launch over n views (yolo_classify_views_u8): slot i shows the image its descriptor names, mirrored where it says so; FIT_TEN_CROP: darknet's ten crops
+hipError_t launch_fit_views(const uint8_t *pixels, size_t bytes, const ViewDesc *d_views, int n, int fit, int net_h, int net_w, void *out, int out_dt,
+                            int out_stride, float post_mul, float post_add, hipStream_t s, int nch)
+{
+    if (n < 1 || net_h < 1 || net_w < 1 || (size_t)net_h * net_w > 0x7fffffffull || bytes > 0xffffffffull || fit < FIT_STRETCH || fit > FIT_TEN_CROP) return hipErrorInvalidValue;
+    const int tiles = (net_h * net_w + 255) / 256;
+    if (nch != 3) {
+        const int c8 = (nch + 7) / 8;
+        if (nch < 1 || out_stride < c8 * 8 || (size_t)tiles * c8 > 0x7fffffffull || fit == FIT_CV2 || fit == FIT_CV2_BGR) return hipErrorInvalidValue;
+        const dim3 grid_n((unsigned)(tiles * c8), (unsigned)n);
+        if (fit == FIT_STRETCH) FIT_LAUNCH_N(FIT_STRETCH, ViewDesc, d_views, 0, grid_n);
+        else if (fit == FIT_LETTERBOX) FIT_LAUNCH_N(FIT_LETTERBOX, ViewDesc, d_views, 0, grid_n);
+        else if (fit == FIT_CENTER_CROP) FIT_LAUNCH_N(FIT_CENTER_CROP, ViewDesc, d_views, 0, grid_n);
+        else FIT_LAUNCH_N(FIT_TEN_CROP, ViewDesc, d_views, 0, grid_n);
+        return hipGetLastError();
+    }
+    const dim3 grid((unsigned)tiles, (unsigned)n);
+    if (fit == FIT_STRETCH) FIT_LAUNCH(FIT_STRETCH, ViewDesc, d_views);
+    else if (fit == FIT_LETTERBOX) FIT_LAUNCH(FIT_LETTERBOX, ViewDesc, d_views);
+    else if (fit == FIT_CV2) FIT_LAUNCH(FIT_CV2, ViewDesc, d_views);
+    else if (fit == FIT_CV2_BGR) FIT_LAUNCH(FIT_CV2_BGR, ViewDesc, d_views);
+    else if (fit == FIT_CENTER_CROP) FIT_LAUNCH(FIT_CENTER_CROP, ViewDesc, d_views);
+    else FIT_LAUNCH(FIT_TEN_CROP, ViewDesc, d_views);
 #undef FIT_LAUNCH
 #undef FIT_LAUNCH_N
     return hipGetLastError();

@@ -454,6 +454,15 @@ static_assert(sizeof(WinDesc) == 32, "the window table's row");
 // bit for bit as its crop would be as an image of its own.  FIT_STRETCH and FIT_LETTERBOX
 hipError_t launch_fit_windows(const uint8_t *pixels, size_t bytes, const WinDesc *d_wins, int n, int fit, int net_h, int net_w, void *out, int out_dt,
                               int out_stride, float post_mul, float post_add, hipStream_t s);
+// One view of an image (yolo_classify_views_u8): the h x w image at byte `offset` of the packed buffer, shown mirrored when flip != 0.  FIT_TEN_CROP (a fit of
+// this launch only, not of the public enum): darknet's ten validation crops -- the image resized to (net_w + shift) x (net_h + shift), the window moved by
+// (dx, dy), coordinates clamped (px_ten_crop, ew_ops.hip).  32 bytes.
+struct ViewDesc { unsigned long long offset; int h, w, dy, dx, flip, shift; };
+static_assert(sizeof(ViewDesc) == 32, "the view table's row");
+enum { FIT_TEN_CROP = 5 };
+// the same launch over n views, one per batch slot; fit: FIT_STRETCH .. FIT_CENTER_CROP (shift, dy, dx unread) or FIT_TEN_CROP
+hipError_t launch_fit_views(const uint8_t *pixels, size_t bytes, const ViewDesc *d_views, int n, int fit, int net_h, int net_w, void *out, int out_dt,
+                            int out_stride, float post_mul, float post_add, hipStream_t s, int nch = 3);
 // darknet's letterbox_image geometry (DN/image.c:960-966): the aspect-preserving size of a w x h image inside netw x neth
 __host__ __device__ inline void letterbox_dims(int netw, int neth, int w, int h, int *new_w, int *new_h)
 {
@@ -523,6 +532,13 @@ hipError_t launch_softmax_topk(const SoftmaxArgs &a, hipStream_t s);
 // the pooled vector is also written to pooled [n][pooled_stride]
 bool avgpool_softmax_ok(const TView &in, const SoftmaxArgs &a);
 hipError_t launch_avgpool_softmax(const TView &in, float *pooled, int pooled_stride, const SoftmaxArgs &a, hipStream_t s);
+// Multi-view classification (yolo_classify_views_u8): rows [n * views][len] fp32, slot = image * views + view -> sums [n][len] with
+// sums[i][c] = ((((0 + p_0) + p_1) + ...) + p_{views-1}) * scale -- axpy_cpu's order, then one multiply --, and, top_k > 0, the top_k best of every scaled row to
+// cls / topk [n][top_k] in the order of launch_softmax_topk (the same device code), from the same launch.  work [n][len]: the selection's scratch (top_k > 0).
+// Any len >= 1; 1 <= views <= VIEWS_MAX.  Values of -inf are never selected.
+enum { VIEWS_MAX = 32 };
+struct ViewReduceArgs { const float *rows; int n, views, len; float scale; float *sums, *work; int top_k; int *cls; float *topk; };
+hipError_t launch_view_reduce(const ViewReduceArgs &a, hipStream_t s);
 
 // ---- vector-input networks and sequences (seq_ops.hip; DN/examples/rnn.c test_char_rnn, DN/utils.c:592-603 sample_array) ----
 // x fp32 [n][len] -> rows [n][row_stride] of `dt` (bf16 / fp16 / fp32), the elements len .. row_stride - 1 of every row zero; row_stride a multiple of 8

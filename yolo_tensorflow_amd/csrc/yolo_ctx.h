@@ -166,6 +166,9 @@ struct yolo_ctx {
     // tiled detection (yolo_detect_tiled_u8): ONE allocation, grown on demand and never shrunk, that holds the window table, the image table, every
     // image's merged candidate list and k_nms_image's workspace over those lists (tile_slab, yolo_run.cpp)
     void *d_tile = nullptr; size_t tile_cap = 0;
+    // multi-view classification (yolo_classify_views_u8): ONE allocation, grown on demand and never shrunk, that holds the view table, every slot's
+    // classifier row, the summed rows, the selection's scratch and the top-k records (ViewSlab, yolo_run.cpp)
+    void *d_views = nullptr; size_t views_cap = 0;
     // hierarchical softmax ("Softmax trees"): the trees of the cfg's tree= keys; tree_head: the [region] layer that has one
     // (-1: none); hier_thresh: yolo_set_hier_thresh; hierarchy_mode: yolo_set_hierarchy_mode; tree_full: YOLO_TREE_FULL forces the full
     // decode in yolo_detect*; lean_hier: the hier_thresh the last descent-form decode labelled its rows with

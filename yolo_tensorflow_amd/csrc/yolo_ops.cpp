@@ -482,6 +482,21 @@ int yolo_op_softmax(const float *x, int n, int len, int groups, float temperatur
     return S.download(probs_out, a.probs, (size_t)n * len * 4);
 }
 
+int yolo_op_view_reduce(const float *rows, int n, int views, int len, float scale, int top_k, float *sums_out, int32_t *classes_out, float *top_out, int device)
+{
+    if (!rows || !sums_out || n < 1 || len < 1 || views < 1 || views > VIEWS_MAX || (size_t)n * views > 0x7fffffffull) { g_op_err = "view_reduce: bad arguments (rows, sums_out, n >= 1, len >= 1, views 1..32)"; return YOLO_ERR_INVALID; }
+    if (top_k < 0 || top_k > CLS_TOPK_MAX || top_k > len || (top_k > 0 && (!classes_out || !top_out))) { g_op_err = "view_reduce: top_k needs 0..min(32, len) and both output arrays"; return YOLO_ERR_INVALID; }
+    OpScope S(device); if (S.rc) { g_op_err = "view_reduce: no HIP device"; return S.rc; }
+    ViewReduceArgs a; memset(&a, 0, sizeof a);
+    a.rows = (const float *)S.upload(rows, (size_t)n * views * len * 4); a.n = n; a.views = views; a.len = len; a.scale = scale; a.top_k = top_k;
+    a.sums = (float *)S.alloc((size_t)n * len * 4); a.work = (float *)S.alloc((size_t)n * len * 4);
+    a.cls = (int *)S.alloc((size_t)n * CLS_TOPK_MAX * 4); a.topk = (float *)S.alloc((size_t)n * CLS_TOPK_MAX * 4);
+    if (S.rc) { g_op_err = "view_reduce: allocation failed"; return S.rc; }
+    if (!S.ok(launch_view_reduce(a, S.s))) { g_op_err = "view_reduce: " + S.err; return S.rc; }
+    if (top_k > 0) { S.download(classes_out, a.cls, (size_t)n * top_k * 4); S.download(top_out, a.topk, (size_t)n * top_k * 4); }
+    return S.download(sums_out, a.sums, (size_t)n * len * 4);
+}
+
 int yolo_op_sample(const float *probs, int n, int len, const float *uniforms, float clip, int32_t *out, int device)
 {
     if (!probs || !uniforms || !out || n < 1 || len < 1) { g_op_err = "sample: bad arguments"; return YOLO_ERR_INVALID; }

@@ -816,6 +816,30 @@ static int desc_check(yolo_ctx *c, int i, const yolo_image_desc &d, size_t bytes
     return YOLO_OK;
 }
 
+// a fit the ragged entry points know, and one this network's images can take
+static int fit_check(yolo_ctx *c, int fit, const char *who)
+{
+    if (fit < YOLO_FIT_STRETCH || fit > YOLO_FIT_CENTER_CROP) return fail(c, YOLO_ERR_INVALID, "bad fit %d", fit);
+    // the cv2 fits restate cv2.resize of an RGB / BGR image: an image of another channel count has no such meaning
+    if (c->in_c != 3 && (fit == YOLO_FIT_CV2 || fit == YOLO_FIT_CV2_BGR))
+        return fail(c, YOLO_ERR_UNSUPPORTED, "%s: %s is not served for a network of %d planes ([net] yolo_input=planes): it fits an RGB / BGR image", who, fit == YOLO_FIT_CV2 ? "YOLO_FIT_CV2" : "YOLO_FIT_CV2_BGR", c->in_c);
+    return YOLO_OK;
+}
+
+// one image of a ragged batch: its place in the buffer, its pitch, and what `fit` needs of its size (fit < 0: no fit is asked)
+static int image_check(yolo_ctx *c, int i, const yolo_image_desc &d, size_t bytes, int fit)
+{
+    if (int r = desc_check(c, i, d, bytes)) return r;
+    if ((uint64_t)d.w * (uint64_t)c->in_c > 0xffffffffull) return fail(c, YOLO_ERR_INVALID, "image %d: a row of %d pixels of %d bytes does not fit a 32-bit pitch", i, (int)d.w, c->in_c);
+    if (fit == YOLO_FIT_LETTERBOX) {
+        int nw, nh; letterbox_dims(c->in_w, c->in_h, d.w, d.h, &nw, &nh);
+        if (nw < 1 || nh < 1) return fail(c, YOLO_ERR_INVALID, "image %d: %d x %d letterboxes to less than one pixel", i, (int)d.h, (int)d.w);
+    }
+    if (fit == YOLO_FIT_CENTER_CROP && !resize_min_ok(c->in_w, d.w, d.h))
+        return fail(c, YOLO_ERR_INVALID, "image %d: %d x %d: its longer side times the network width %d does not fit an int (darknet's resize_min)", i, (int)d.h, (int)d.w, c->in_w);
+    return YOLO_OK;
+}
+
 // everything a ragged batch is refused for, before any launch
 static int images_check(yolo_ctx *c, const void *pixels, size_t bytes, const yolo_image_desc *descs, int n, int fit)
 {
@@ -823,22 +847,9 @@ static int images_check(yolo_ctx *c, const void *pixels, size_t bytes, const yol
     if (!c->weights_loaded) return fail(c, YOLO_ERR_STATE, "forward of images before weights were loaded");
     if (n < 1 || n > c->max_batch) return fail(c, YOLO_ERR_INVALID, "batch %d outside 1..%d", n, c->max_batch);
     if (!pixels || !descs) return fail(c, YOLO_ERR_INVALID, "pixels / descs == NULL");
-    if (fit < YOLO_FIT_STRETCH || fit > YOLO_FIT_CENTER_CROP) return fail(c, YOLO_ERR_INVALID, "bad fit %d", fit);
-    // the cv2 fits restate cv2.resize of an RGB / BGR image: an image of another channel count has no such meaning
-    if (c->in_c != 3 && (fit == YOLO_FIT_CV2 || fit == YOLO_FIT_CV2_BGR))
-        return fail(c, YOLO_ERR_UNSUPPORTED, "yolo_*_images_u8 / yolo_detect_images_graph: %s is not served for a network of %d planes ([net] yolo_input=planes): it fits an RGB / BGR image", fit == YOLO_FIT_CV2 ? "YOLO_FIT_CV2" : "YOLO_FIT_CV2_BGR", c->in_c);
+    if (int r = fit_check(c, fit, "yolo_*_images_u8 / yolo_detect_images_graph")) return r;
     if (bytes < (size_t)c->in_c || bytes > 0xffffffffull) return fail(c, YOLO_ERR_INVALID, "packed buffer of %zu bytes (%d .. 2^32 - 1)", bytes, c->in_c);
-    for (int i = 0; i < n; ++i) {
-        const yolo_image_desc &d = descs[i];
-        if (int r = desc_check(c, i, d, bytes)) return r;
-        if ((uint64_t)d.w * (uint64_t)c->in_c > 0xffffffffull) return fail(c, YOLO_ERR_INVALID, "image %d: a row of %d pixels of %d bytes does not fit a 32-bit pitch", i, (int)d.w, c->in_c);
-        if (fit == YOLO_FIT_LETTERBOX) {
-            int nw, nh; letterbox_dims(c->in_w, c->in_h, d.w, d.h, &nw, &nh);
-            if (nw < 1 || nh < 1) return fail(c, YOLO_ERR_INVALID, "image %d: %d x %d letterboxes to less than one pixel", i, (int)d.h, (int)d.w);
-        }
-        if (fit == YOLO_FIT_CENTER_CROP && !resize_min_ok(c->in_w, d.w, d.h))
-            return fail(c, YOLO_ERR_INVALID, "image %d: %d x %d: its longer side times the network width %d does not fit an int (darknet's resize_min)", i, (int)d.h, (int)d.w, c->in_w);
-    }
+    for (int i = 0; i < n; ++i) if (int r = image_check(c, i, descs[i], bytes, fit)) return r;
     return YOLO_OK;
 }
 
@@ -1137,6 +1148,116 @@ int yolo_classify_images_u8(yolo_ctx *c, const uint8_t *pixels, size_t bytes, co
     c->cls_topk = 0; c->cls_mode = 0;
     if (r) return r;
     return classify_out(c, n, top_k, classes_out, probs_out, out_loc);
+}
+
+// ---- multi-view classification: darknet's `classifier valid10` (ten crops) and test_cifar_multi (the image and its mirror) on the
+//      device.  Slots are ordered image * K + view and run max_batch per step: one fit launch over the view table straight from the source bytes, the
+//      network, one device copy of the step's rows behind the rows of the steps before; after the last step ONE launch adds every image's K rows in view
+//      order, scales them and selects the top-k ----
+namespace {
+const yolo_view ten_crop_views[5] = {{-1, -1, 0, 0}, {-1, 1, 0, 0}, {0, 0, 0, 0}, {1, -1, 0, 0}, {1, 1, 0, 0}};      // (dy, dx) in units of `shift`: classifier.c:273-277
+int view_count(int views) { return views == YOLO_VIEWS_FLIP ? 2 : views == YOLO_VIEWS_TEN_CROP ? 10 : 0; }
+yolo_view view_at(int views, int shift, int v)
+{
+    if (views == YOLO_VIEWS_FLIP) return yolo_view{0, 0, v, 0};
+    const yolo_view u = ten_crop_views[v % 5];
+    return yolo_view{u.dy * shift, u.dx * shift, v / 5, 0};
+}
+// the carving of yolo_ctx::d_views for a call of `images` images of K views and `len` classes: every array 256-byte aligned
+struct ViewSlab {
+    ViewDesc *views; float *rows, *sums, *work, *topk; int *cls; size_t bytes;
+    ViewSlab(char *base, size_t images, size_t K, size_t len)
+    {
+        size_t off = 0;
+        auto take = [&](size_t n) { const uintptr_t p = (uintptr_t)base + off; off += (n + 255) & ~(size_t)255; return (void *)p; };      // (base == nullptr: the sizes only)
+        views = (ViewDesc *)take(images * K * sizeof(ViewDesc)); rows = (float *)take(images * K * len * 4); sums = (float *)take(images * len * 4);
+        work = (float *)take(images * len * 4); cls = (int *)take(images * CLS_TOPK_MAX * 4); topk = (float *)take(images * CLS_TOPK_MAX * 4);
+        bytes = off;
+    }
+};
+}
+
+int yolo_view_table(int views, int shift, yolo_view *out, int cap, int *count)
+{
+    if (!count) { g_op_err = "yolo_view_table: count == NULL"; return YOLO_ERR_INVALID; }
+    *count = 0;
+    const int K = view_count(views);
+    if (!K || shift < 0 || cap < 0 || (cap > 0 && !out)) { g_op_err = "yolo_view_table: views YOLO_VIEWS_FLIP or YOLO_VIEWS_TEN_CROP and shift >= 0 are needed (and out for cap > 0)"; return YOLO_ERR_INVALID; }
+    *count = K;
+    for (int v = 0; v < std::min(cap, K); ++v) out[v] = view_at(views, shift, v);
+    return YOLO_OK;
+}
+
+int yolo_classify_views_u8(yolo_ctx *c, const uint8_t *pixels, size_t bytes, const yolo_image_desc *descs, int n_images, int views, int fit, int shift, int loc,
+                           float scale, int top_k, int32_t *classes_out, float *probs_out, int out_loc)
+{
+    static const char *const who = "yolo_classify_views_u8";
+    if (!c) return YOLO_ERR_INVALID;
+    // ---- every refusal, before any launch ----
+    if (int r = classify_check(c, top_k, classes_out, probs_out)) return r;
+    if (!c->states.empty())
+        return fail(c, YOLO_ERR_UNSUPPORTED, "%s: a network with recurrent state (%d state tensors) is not served: a batch slot is a stream there, not a view of an image", who, (int)c->states.size());
+    if (c->dtype == YOLO_FP8) return fail(c, YOLO_ERR_UNSUPPORTED, "%s: the fp8 configuration is not served", who);
+    const int K = view_count(views);
+    if (!K) return fail(c, YOLO_ERR_INVALID, "%s: bad views %d (YOLO_VIEWS_FLIP or YOLO_VIEWS_TEN_CROP)", who, views);
+    if (shift < 0) return fail(c, YOLO_ERR_INVALID, "%s: shift %d < 0", who, shift);
+    const bool ten = views == YOLO_VIEWS_TEN_CROP;
+    if (!ten) { if (int r = fit_check(c, fit, who)) return r; }
+    else {
+        // resize_image divides by the resized extent - 1; the crop's coordinates y + shift, x + shift stay below the resized extents
+        if ((long long)c->in_w + shift > 0x7fffffffLL || (long long)c->in_h + shift > 0x7fffffffLL)
+            return fail(c, YOLO_ERR_INVALID, "%s: the network input %d x %d enlarged by shift %d does not fit an int", who, c->in_h, c->in_w, shift);
+        if (c->in_w + shift < 2 || c->in_h + shift < 2)
+            return fail(c, YOLO_ERR_INVALID, "%s: the resized image of %d x %d (network input + shift) is less than 2 pixels wide or high (darknet's resize_image divides by the extent - 1)", who, c->in_h + shift, c->in_w + shift);
+    }
+    if (!c->weights_loaded) return fail(c, YOLO_ERR_STATE, "%s before weights were loaded", who);
+    if (n_images < 1 || n_images > 0x7fffffff / K) return fail(c, YOLO_ERR_INVALID, "%s: %d images (1 .. %d)", who, n_images, 0x7fffffff / K);
+    if (!pixels || !descs) return fail(c, YOLO_ERR_INVALID, "pixels / descs == NULL");
+    if (bytes < (size_t)c->in_c || bytes > 0xffffffffull) return fail(c, YOLO_ERR_INVALID, "packed buffer of %zu bytes (%d .. 2^32 - 1)", bytes, c->in_c);
+    for (int i = 0; i < n_images; ++i) if (int r = image_check(c, i, descs[i], bytes, ten ? -1 : fit)) return r;
+    const Layer &L = c->layers[c->cls_layer];
+    const int nslots = n_images * K;
+    std::vector<ViewDesc> table;
+    try {
+        table.resize(nslots);
+    } catch (const std::bad_alloc &) { return fail(c, YOLO_ERR_NOMEM, "%s: the view table", who); }
+    for (int i = 0; i < nslots; ++i) {
+        const yolo_image_desc &d = descs[i / K];
+        const yolo_view v = view_at(views, shift, i % K);
+        table[i] = ViewDesc{d.offset, d.h, d.w, v.dy, v.dx, v.flip, shift};
+    }
+    const ViewSlab need(nullptr, n_images, K, L.C);
+
+    // ---- device ----
+    HIPCK(c, hipSetDevice(c->device));
+    const uint8_t *src = nullptr;
+    if (int r = stage_pixels(c, pixels, bytes, loc, &src)) return r;          // the source bytes go up once, whatever K is
+    if (need.bytes > c->views_cap) {
+        HIPCK(c, hipStreamSynchronize(c->stream));
+        if (c->d_views) HIPCK(c, hipFree(c->d_views));
+        c->d_views = nullptr; c->views_cap = 0;
+        HIPCK(c, hipMalloc(&c->d_views, need.bytes)); c->views_cap = need.bytes;
+    }
+    const ViewSlab t((char *)c->d_views, n_images, K, L.C);
+    StreamDrain drain{c};
+    HIPCK(c, hipMemcpyAsync(t.views, table.data(), (size_t)nslots * sizeof(ViewDesc), hipMemcpyHostToDevice, c->stream));
+    c->lean_thr = 0.f; c->cls_topk = 0; c->cls_mode = c->hierarchy_mode;
+    struct ModeReset { yolo_ctx *c; ~ModeReset() { c->cls_mode = 0; } } reset{c};
+    for (int first = 0; first < nslots; first += c->max_batch) {
+        const int nb = std::min(c->max_batch, nslots - first);
+        auto [dst, dt] = input_fill_dst(c);
+        HIPCK(c, launch_fit_views(src, bytes, t.views + first, nb, ten ? FIT_TEN_CROP : fit, c->in_h, c->in_w, dst, dt, fill_stride(c), c->in_mul, c->in_add, c->stream, c->in_c));
+        HIPCK(c, input_filled(c, (size_t)nb * c->in_h * c->in_w));
+        if (int r = run_network(c, nb, false)) return r;
+        // the step's rows behind those of the steps before: a device copy on the context stream, no host synchronisation
+        HIPCK(c, hipMemcpy2DAsync(t.rows + (size_t)first * L.C, (size_t)L.C * 4, L.out.ptr, (size_t)L.out.stride * 4, (size_t)L.C * 4, nb, hipMemcpyDeviceToDevice, c->stream));
+    }
+    ViewReduceArgs a; memset(&a, 0, sizeof a);
+    a.rows = t.rows; a.n = n_images; a.views = K; a.len = L.C; a.scale = scale; a.sums = t.sums; a.work = t.work; a.top_k = top_k; a.cls = t.cls; a.topk = t.topk;
+    HIPCK(c, launch_view_reduce(a, c->stream));
+    if (top_k == 0) return copy_out(c, probs_out, t.sums, (size_t)n_images * L.C * 4, out_loc);
+    if (int r = copy_out(c, classes_out, t.cls, (size_t)n_images * top_k * 4, out_loc)) return r;
+    return copy_out(c, probs_out, t.topk, (size_t)n_images * top_k * 4, out_loc);
 }
 
 // ---- map contexts: the ragged native-size path.  One fit launch and one forward, as yolo_detect_images_u8, then ONE kernel that writes every

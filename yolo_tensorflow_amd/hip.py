@@ -24,10 +24,13 @@ NMS_TF, NMS_PER_CLASS, NMS_DARKNET, NMS_NUMPY_V3, NMS_TF_V1 = 0, 1, 2, 3, 4
 SELECT_GT, SELECT_GE = 0, 1
 FIT_STRETCH, FIT_LETTERBOX, FIT_CV2, FIT_CV2_BGR, FIT_CENTER_CROP = 0, 1, 2, 3, 4
 UNITS_NETWORK, UNITS_SOURCE_PIXELS = 0, 1
+VIEWS_FLIP, VIEWS_TEN_CROP = 1, 2
 
 BOX_DTYPE = np.dtype([("x0", "<f4"), ("y0", "<f4"), ("x1", "<f4"), ("y1", "<f4"), ("score", "<f4"), ("cls", "<i4")])
 # yolo_image_desc: one image of a ragged batch, a uint8 RGB [h][w][3] image at byte `offset` of one packed buffer
 DESC_DTYPE = np.dtype([("offset", "<u8"), ("h", "<i4"), ("w", "<i4")])
+# yolo_view: one view of multi-view classification, the crop offsets in pixels and whether the image is mirrored
+VIEW_DTYPE = np.dtype([("dy", "<i4"), ("dx", "<i4"), ("flip", "<i4"), ("pad", "<i4")])
 
 
 class ImageDesc(C.Structure):
@@ -52,6 +55,7 @@ EXPORTS = [
     "yolo_tile_windows", "yolo_detect_tiled_u8",
     "yolo_vector_inputs", "yolo_forward_vectors", "yolo_sequence", "yolo_set_temperature", "yolo_reset_temperature", "yolo_op_sample",
     "yolo_set_frame_average", "yolo_frame_average",
+    "yolo_view_table", "yolo_classify_views_u8", "yolo_op_view_reduce",
 ]
 HIER_CONDITIONAL, HIER_ABSOLUTE, HIER_LEAVES = 0, 1, 2
 _HIER_MODES = {None: HIER_CONDITIONAL, "conditional": HIER_CONDITIONAL, "absolute": HIER_ABSOLUTE, "leaves": HIER_LEAVES}
@@ -181,6 +185,9 @@ def load_library():
     l.yolo_frame_average.argtypes = [P]
     l.yolo_tile_windows.argtypes = [I, I, I, I, I, I, P, I, C.POINTER(I)]
     l.yolo_detect_tiled_u8.argtypes = [P, P, SZ, P, I, I, I, I, I, I, I, F, F, I, I, I, I, P, P, I]
+    l.yolo_view_table.argtypes = [I, I, P, I, C.POINTER(I)]
+    l.yolo_classify_views_u8.argtypes = [P, P, SZ, P, I, I, I, I, I, F, I, P, P, I]
+    l.yolo_op_view_reduce.argtypes = [P, I, I, I, F, I, P, P, P, I]
     l.yolo_vector_inputs.argtypes = [P]
     l.yolo_forward_vectors.argtypes = [P, P, I, I, P, SZ]
     l.yolo_sequence.argtypes = [P, I, I, P, I, P, F, P, P, I]
@@ -290,6 +297,17 @@ def tile_windows(img_hw, tile_hw, overlap_hw):
     _op_check(l.yolo_tile_windows(ih, iw, th, tw, oh, ow, None, 0, C.byref(n)), "yolo_tile_windows")
     out = np.zeros((n.value, 4), dtype=np.int32)
     _op_check(l.yolo_tile_windows(ih, iw, th, tw, oh, ow, out.ctypes.data, n.value, C.byref(n)), "yolo_tile_windows")
+    return out
+
+
+def view_table(views, shift=32):
+    """yolo_view_table: the views of VIEWS_FLIP (the image and its mirror) or VIEWS_TEN_CROP (darknet's `classifier valid10`: five crop_image
+    windows of the image resized to network + shift, then the same five of its mirror) -> VIEW_DTYPE [K] in view order.  Host code: no device."""
+    l = load_library()
+    n = C.c_int(0)
+    _op_check(l.yolo_view_table(int(views), int(shift), None, 0, C.byref(n)), "yolo_view_table")
+    out = np.zeros(n.value, dtype=VIEW_DTYPE)
+    _op_check(l.yolo_view_table(int(views), int(shift), out.ctypes.data, n.value, C.byref(n)), "yolo_view_table")
     return out
 
 
@@ -665,6 +683,20 @@ class Engine:
         cls, probs = self._classify_result(n, top_k)
         self._check(self.lib.yolo_classify_images_u8(self.ctx, p, nbytes, descs.ctypes.data, n, fit, loc, top_k,
                                                      cls.ctypes.data if top_k else None, probs.ctypes.data, HOST), "yolo_classify_images_u8")
+        return (cls, probs) if top_k else probs
+
+    def classify_views(self, images, views, fit=FIT_STRETCH, shift=32, scale=1.0, top_k=0):
+        """yolo_classify_views_u8: every image (a list of uint8 [h, w, input_channels] arrays of any sizes and any number, or a (buffer, descs) pair
+        from pack_images) is predicted over the views of `views` -- VIEWS_FLIP: the image fitted by `fit` and its mirror; VIEWS_TEN_CROP: darknet's ten
+        crops of the image resized to network + shift (view_table states them; `fit` is not read) --, the slots image * K + view run max_batch at a
+        time, and one launch adds each image's rows in view order, multiplies by `scale` (1 / K: the mean) and selects.  top_k == 0: -> the sums
+        float32 [n, num_classes]; top_k > 0: -> (classes int32 [n, top_k], sums float32 [n, top_k]), value descending, equal values by ascending class."""
+        buf, descs, p, loc, nbytes = self._packed(images)
+        n = len(descs)
+        self._order_after_producer(buf)
+        cls, probs = self._classify_result(n, max(int(top_k), 0))          # (a negative top_k: the library refuses it)
+        self._check(self.lib.yolo_classify_views_u8(self.ctx, p, nbytes, descs.ctypes.data, n, int(views), int(fit), int(shift), loc, float(scale), int(top_k),
+                                                    cls.ctypes.data if cls is not None else None, probs.ctypes.data, HOST), "yolo_classify_views_u8")
         return (cls, probs) if top_k else probs
 
     # ---- map networks ([net] yolo_output=map): segmentation masks, heat maps ----
@@ -1061,6 +1093,21 @@ def op_softmax(x, groups=1, temperature=1.0, top_k=0, device=0):
     _op_check(load_library().yolo_op_softmax(x.ctypes.data, n, ln, groups, float(temperature), top_k, probs.ctypes.data,
                                              cls.ctypes.data if top_k else None, tkp.ctypes.data if top_k else None, device), "yolo_op_softmax")
     return (probs, cls, tkp) if top_k else probs
+
+
+def op_view_reduce(rows, views, scale=1.0, top_k=0, device=0):
+    """The reduction launch of multi-view classification alone (yolo_op_view_reduce): rows float32 [n * views, len], slot = image * views + view
+    -> sums [n, len] = (((0 + row_0) + row_1) + ...) * scale; top_k > 0: -> (sums, classes int32 [n, top_k], top sums [n, top_k]) from the same
+    launch, value descending, equal values by ascending class."""
+    rows = _f32(rows); views = int(views); top_k = int(top_k)
+    if rows.ndim != 2 or views < 1 or rows.shape[0] % views or rows.shape[0] < views:
+        raise YoloError("op_view_reduce: rows [n * views, len] with views >= 1, got %s and views %d" % (rows.shape, views))
+    n, ln = rows.shape[0] // views, rows.shape[1]
+    sums = np.empty((n, ln), dtype=np.float32)
+    cls = np.full((n, max(top_k, 1)), -1, dtype=np.int32); top = np.zeros((n, max(top_k, 1)), dtype=np.float32)
+    _op_check(load_library().yolo_op_view_reduce(rows.ctypes.data, n, views, ln, float(scale), top_k, sums.ctypes.data,
+                                                 cls.ctypes.data if top_k else None, top.ctypes.data if top_k else None, device), "yolo_op_view_reduce")
+    return (sums, cls, top) if top_k else sums
 
 
 def op_sample(probs, uniforms, clip=1e-4, device=0):
