@@ -396,3 +396,44 @@ def test_halo_form_on_rectangular_blocks_equals_tiled_form(hiplib, dtype):
         hiplib.op_conv2d(x, w, None, dtype=dt, tile_cfg=54)
     with pytest.raises(hiplib.YoloError):
         hiplib.op_conv2d(rng.standard_normal((1, 19, 19, 128)).astype(np.float32), w, None, dtype=hiplib.FP8, tile_cfg=56)
+
+
+def _bf16(x):
+    u = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32).astype(np.uint64)
+    u = (u + 0x7fff + ((u >> 16) & 1)) & 0xffff0000
+    return u.astype(np.uint32).view(np.float32)
+
+
+# the [deconvolutional], groups= and xnor=1 kernels share one store (side_epilogue.h).  (operator, filter shape, its keywords), each at batch 1 with
+# 20 filters: the stored width is 24 channels in 16-bit and fp32 tensors and 20 in the fp32 store of a 16-bit kernel, ragged in every type
+SIDE_STORE_CASES = {
+    "deconv": ("op_deconv2d", (1, 3, 3, 8), (8, 20, 1, 1), dict(stride=2, padding=0)),          # three of the four phases have no tap at all
+    "grouped": ("op_conv2d_grouped", (1, 4, 5, 16), (20, 4, 3, 3), dict(groups=4, stride=1, padding=1)),
+    "xnor": ("op_conv2d_xnor", (1, 4, 5, 16), (20, 16, 3, 3), dict(stride=1, padding=1)),          # mean|w| = 0: the scale is 0
+}
+
+
+@pytest.mark.parametrize("op", sorted(SIDE_STORE_CASES))
+def test_side_conv_store_edges(hiplib, op):
+    """All-zero filters and a bias that leaves fp16's range: every output pixel is exactly act(bias), rounded once to the storage type -- a closed
+    form.  fp16 saturates at +-65504 and stays finite; bf16 is the round-to-nearest-even of the value; the fp32 stores (fp32 operands, and
+    out_f32 of both 16-bit types) keep the bias as it is, unsaturated; leaky multiplies a negative value by float32(0.1) in fp32, relu makes it
+    zero (of either sign)."""
+    name, xs, ws, kw = SIDE_STORE_CASES[op]
+    x = np.random.default_rng(5).standard_normal(xs).astype(np.float32)
+    wt = np.zeros(ws, np.float32)
+    b = np.tile(np.array([1e5, -1e5, 65504, -8, 0.3, -0.3, 70000, 1], np.float32), 3)[:20]
+    for act in ("linear", "leaky", "relu"):
+        a = b if act == "linear" else np.where(b < 0, b * np.float32(0.1) if act == "leaky" else np.float32(0), b).astype(np.float32)
+        for dtype, out_f32 in ((hiplib.FP32, False), (hiplib.BF16, False), (hiplib.BF16, True), (hiplib.FP16, False), (hiplib.FP16, True)):
+            got = getattr(hiplib, name)(x, wt, b, activation=act, dtype=dtype, out_f32=out_f32, **kw)
+            assert got.dtype == np.float32 and got.shape[0] == 1 and got.shape[3] == 20 and got.shape[1] * got.shape[2] > 1
+            if dtype == hiplib.FP32 or out_f32:
+                want = a
+            elif dtype == hiplib.BF16:
+                want = _bf16(a)
+            else:
+                want = np.clip(a, -65504, 65504).astype(np.float16).astype(np.float32)
+                assert np.isfinite(got).all(), (op, act)
+            print("%s %s dtype %d out_f32 %d: %r" % (op, act, dtype, out_f32, got[0, 0, 0, :8].tolist()))
+            assert np.array_equal(got, np.broadcast_to(want, got.shape)), (op, act, dtype, out_f32, got[0, 0, 0], want)

@@ -10,20 +10,13 @@
 // fp32 operands (k_deconv_f32): plain FMAs, one thread per (output pixel, channel).
 #include "kernels.h"
 #include "device_common.h"
+#include "side_epilogue.h"
 
 namespace {
 
 // the output rows (or columns) of phase p along one axis: o = o0, o0 + s, ... < extent
 __device__ __forceinline__ int phase_first(int p, int pad, int s) { return ((p - pad) % s + s) % s; }
 __device__ __forceinline__ int phase_count(int o0, int extent, int s) { return o0 < extent ? (extent - o0 + s - 1) / s : 0; }
-
-template <bool H16> __device__ __forceinline__ uint32_t store_pack2(float lo, float hi)
-{
-    if constexpr (H16) {          // saturating, as the other fp16 stores of the library
-        lo = __builtin_amdgcn_fmed3f(lo, -65504.f, 65504.f); hi = __builtin_amdgcn_fmed3f(hi, -65504.f, 65504.f);
-        return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2_t{lo, hi}, f16x2_t));
-    } else return f32x2_to_bf16x2(lo, hi);
-}
 
 template <bool H16>
 __global__ __launch_bounds__(256) void k_deconv16(const DeconvArgs a)
@@ -61,17 +54,15 @@ __global__ __launch_bounds__(256) void k_deconv16(const DeconvArgs a)
     }
     if (!mv) return;
     const float slope = act_slope(a.act);
+    const int odt = a.out_dt == DT_F32 ? DT_F32 : H16 ? DT_F16 : DT_BF16;
     const long opix = ((long)n * a.Ho + oy) * a.Wo + ox;
 #pragma unroll
     for (int t = 0; t < DECONV_CO_TILE / 16; ++t) {
         const int co = c0 + t * 16 + lq * 4;
         if (co >= a.Cstore) continue;          // (co and Cstore are multiples of 4: the four channels are in or out together)
         const float4 bv = *(const float4 *)(a.bias + co);
-        float v[4] = {acc[t][0] + bv.x, acc[t][1] + bv.y, acc[t][2] + bv.z, acc[t][3] + bv.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = fmaxf(v[j], v[j] * slope);
-        if (a.out_dt == DT_F32) *(float4 *)((float *)a.out + opix * a.out_stride + co) = float4{v[0], v[1], v[2], v[3]};
-        else *(uint2 *)((uint16_t *)a.out + opix * a.out_stride + co) = uint2{store_pack2<H16>(v[0], v[1]), store_pack2<H16>(v[2], v[3])};
+        const float v[4] = {acc[t][0] + bv.x, acc[t][1] + bv.y, acc[t][2] + bv.z, acc[t][3] + bv.w};
+        side_store4(a.out, opix * a.out_stride + co, odt, slope, v);
     }
 }
 
@@ -103,8 +94,7 @@ __global__ __launch_bounds__(256) void k_deconv_f32(const DeconvArgs a)
 
 hipError_t launch_deconv(const DeconvArgs &a, hipStream_t s)
 {
-    if (!deconv_served(a.size, a.stride, a.pad, a.H, a.W) || a.N < 1 || a.Cin_pad < 8 || a.Cin_pad % 8 || a.in_stride % 8 || a.in_stride < a.Cin_pad ||
-        a.cout_pad % DECONV_CO_TILE || a.Cstore % 4 || a.Cstore > a.cout_pad || a.Cstore > a.out_stride || a.out_stride % 4 || !act_is_slope(a.act) ||
+    if (!side_conv_args_ok(a, a.cout_pad) || !deconv_served(a.size, a.stride, a.pad, a.H, a.W) || a.Cin_pad < 8 || a.Cin_pad % 8 || a.in_stride < a.Cin_pad || a.cout_pad % DECONV_CO_TILE ||
         a.Ho != (a.H - 1) * a.stride + a.size - 2 * a.pad || a.Wo != (a.W - 1) * a.stride + a.size - 2 * a.pad) return hipErrorInvalidValue;
     if (a.in_dt == DT_F32) {
         if (a.out_dt != DT_F32) return hipErrorInvalidValue;
@@ -113,8 +103,6 @@ hipError_t launch_deconv(const DeconvArgs &a, hipStream_t s)
         return hipGetLastError();
     }
     if ((a.in_dt != DT_BF16 && a.in_dt != DT_F16) || (a.out_dt != a.in_dt && a.out_dt != DT_F32)) return hipErrorInvalidValue;
-    // 16-byte fragment loads and 8- / 16-byte stores: channel windows begin on whole granules
-    if (((uintptr_t)a.in & 15) || ((uintptr_t)a.wt & 15) || ((uintptr_t)a.bias & 15) || ((uintptr_t)a.out & (a.out_dt == DT_F32 ? 15 : 7))) return hipErrorInvalidValue;
     // the largest phase decides the grid: phase p of an axis holds ceil((extent - first) / stride) <= ceil(extent / stride) outputs
     const long mmax = (long)a.N * ((a.Ho + a.stride - 1) / a.stride) * ((a.Wo + a.stride - 1) / a.stride);
     const dim3 grid((unsigned)((mmax + 63) / 64), (unsigned)(a.cout_pad / DECONV_CO_TILE), (unsigned)(a.stride * a.stride));

@@ -18,16 +18,9 @@
 // fp32 operands (k_gconv_f32): plain FMAs, one thread per (output pixel, channel), over the group's own cg channels only.
 #include "kernels.h"
 #include "device_common.h"
+#include "side_epilogue.h"
 
 namespace {
-
-template <bool H16> __device__ __forceinline__ uint32_t store_pack2(float lo, float hi)
-{
-    if constexpr (H16) {          // saturating, as the other fp16 stores of the library
-        lo = __builtin_amdgcn_fmed3f(lo, -65504.f, 65504.f); hi = __builtin_amdgcn_fmed3f(hi, -65504.f, 65504.f);
-        return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2_t{lo, hi}, f16x2_t));
-    } else return f32x2_to_bf16x2(lo, hi);
-}
 
 template <bool H16>
 __global__ __launch_bounds__(256) void k_gconv16(const GConvArgs a)
@@ -75,6 +68,7 @@ __global__ __launch_bounds__(256) void k_gconv16(const GConvArgs a)
         while (c >= a.kc) { c -= a.kc; if (++tx == a.size) { tx = 0; ++ty; } }
     }
     const float slope = act_slope(a.act);
+    const int odt = a.out_dt == DT_F32 ? DT_F32 : H16 ? DT_F16 : DT_BF16;
 #pragma unroll
     for (int p = 0; p < GCONV_PT; ++p) {
         if (!mv[p]) continue;
@@ -84,11 +78,8 @@ __global__ __launch_bounds__(256) void k_gconv16(const GConvArgs a)
             const int co = b * a.mb + c0 + t * 16 + lq * 4;
             if (t >= nt || co >= a.Cstore) continue;          // (co and Cstore are multiples of 4: the four channels are in or out together)
             const float4 bv = *(const float4 *)(a.bias + co);
-            float v[4] = {acc[p][t][0] + bv.x, acc[p][t][1] + bv.y, acc[p][t][2] + bv.z, acc[p][t][3] + bv.w};
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v[j] = fmaxf(v[j], v[j] * slope);
-            if (a.out_dt == DT_F32) *(float4 *)((float *)a.out + opix * a.out_stride + co) = float4{v[0], v[1], v[2], v[3]};
-            else *(uint2 *)((uint16_t *)a.out + opix * a.out_stride + co) = uint2{store_pack2<H16>(v[0], v[1]), store_pack2<H16>(v[2], v[3])};
+            const float v[4] = {acc[p][t][0] + bv.x, acc[p][t][1] + bv.y, acc[p][t][2] + bv.z, acc[p][t][3] + bv.w};
+            side_store4(a.out, opix * a.out_stride + co, odt, slope, v);
         }
     }
 }
@@ -125,8 +116,7 @@ hipError_t launch_gconv(const GConvArgs &a, hipStream_t s)
     GConvArgs g = a;
     if (a.groups < 1 || a.C < 1 || a.Cout < 1 || a.C % a.groups || a.Cout % a.groups) return hipErrorInvalidValue;
     gconv_layout(g);
-    if (!gconv_served(a.size, a.stride, a.pad, a.H, a.W) || a.N < 1 || g.t != a.t || g.kp != a.kp || g.nb != a.nb || g.kc != a.kc || g.mb != a.mb || a.in_stride % 8 || a.in_stride < (a.C + 7) / 8 * 8 ||
-        a.Cstore % 4 || a.Cstore < a.Cout || a.Cstore > a.nb * a.mb || a.Cstore > a.out_stride || a.out_stride % 4 || !act_is_slope(a.act) ||
+    if (!gconv_served(a.size, a.stride, a.pad, a.H, a.W) || g.t != a.t || g.kp != a.kp || g.nb != a.nb || g.kc != a.kc || g.mb != a.mb || !side_conv_args_ok(a, a.nb * a.mb) || a.in_stride < (a.C + 7) / 8 * 8 ||
         a.Ho != (a.H + 2 * a.pad - a.size) / a.stride + 1 || a.Wo != (a.W + 2 * a.pad - a.size) / a.stride + 1) return hipErrorInvalidValue;
     if (a.in_dt == DT_F32) {
         if (a.out_dt != DT_F32) return hipErrorInvalidValue;
@@ -135,8 +125,6 @@ hipError_t launch_gconv(const GConvArgs &a, hipStream_t s)
         return hipGetLastError();
     }
     if ((a.in_dt != DT_BF16 && a.in_dt != DT_F16) || (a.out_dt != a.in_dt && a.out_dt != DT_F32)) return hipErrorInvalidValue;
-    // 16-byte fragment loads and 8- / 16-byte stores: channel windows begin on whole granules
-    if (((uintptr_t)a.in & 15) || ((uintptr_t)a.wt & 15) || ((uintptr_t)a.bias & 15) || ((uintptr_t)a.out & (a.out_dt == DT_F32 ? 15 : 7))) return hipErrorInvalidValue;
     const long M = (long)a.N * a.Ho * a.Wo;
     const int units = a.nb * ((a.mb + GCONV_CO_TILE - 1) / GCONV_CO_TILE);
     if ((units + 3) / 4 > 65535 || (M + 16 * GCONV_PT - 1) / (16 * GCONV_PT) > 0x7fffffffL) return hipErrorInvalidValue;

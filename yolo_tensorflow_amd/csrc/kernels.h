@@ -230,6 +230,28 @@ hipError_t launch_conv_resblock(const BlockArgs &a, hipStream_t s);
 // exact-fp32 MFMA conv (config 2); same argument meaning, in/wt/res are float
 hipError_t launch_conv_f32(const ConvArgs &a, hipStream_t s);
 
+// ---- the side convs: [deconvolutional], [convolutional] with groups > 1, [convolutional] with xnor=1 -----------------------------------
+// Three conv kinds with a filter layout and a K loop of their own (deconv.hip, gconv.hip, xconv.hip) and everything else in common: these
+// fields, the accumulator mapping and the store of their MFMA kernels (side_epilogue.h), the launch sequence's case (yolo_run.cpp), the
+// single-operator body (yolo_ops.cpp).  Each kind's struct adds its layout fields and says which channels of `in` it reads.
+struct SideConvArgs {
+    const void *in; int in_stride;       // elements per input pixel
+    const void *wt;                      // the packed filters, in the kind's own layout
+    const float *bias;                   // fp32 (BN folded), one entry per filter row of the layout
+    void *out; int out_stride; int out_dt, in_dt;      // out_dt: the operand type, or DT_F32 (a "head": logits, a map network's output)
+    int N, H, W, Ho, Wo, Cout;
+    int Cstore;                          // channels written per pixel: Cout rounded up to the output's granule (zeros past Cout), a multiple of 4
+    int size, stride, pad, act;          // act: slope family only
+};
+// what every launcher asks of those fields; `rows`: the filter rows of the kind's layout (the bias has as many entries).  16-byte fragment loads
+// and 8- / 16-byte stores: pixels and channel windows begin on whole granules
+inline bool side_conv_args_ok(const SideConvArgs &a, int rows)
+{
+    if (a.N < 1 || a.in_stride % 8 || a.out_stride % 4 || !act_is_slope(a.act)) return false;
+    if (a.Cstore % 4 || a.Cstore < a.Cout || a.Cstore > rows || a.Cstore > a.out_stride) return false;
+    return !(((uintptr_t)a.in & 15) || ((uintptr_t)a.wt & 15) || ((uintptr_t)a.bias & 15) || ((uintptr_t)a.out & (a.out_dt == DT_F32 ? 15 : 7)));
+}
+
 // ---- transposed convolution (deconv.hip; DN/deconvolutional_layer.c) ------------------------------------------------------------
 // out[f, iy * s - p + kh, ix * s - p + kw] += sum_ci w[ci, f, kh, kw] * in[ci, iy, ix], computed as a GATHER: the output splits into s x s
 // PHASES ((oy + p) mod s, (ox + p) mod s); phase (py, px) is an implicit GEMM over the taps kh = py + ty * s < size, kw = px + tx * s < size,
@@ -239,15 +261,8 @@ hipError_t launch_conv_f32(const ConvArgs &a, hipStream_t s);
 #define DECONV_MAX_SIZE 7
 #define DECONV_MAX_STRIDE 4
 #define DECONV_CO_TILE 32            // output channels per workgroup: cout_pad is a multiple of it
-struct DeconvArgs {
-    const void *in; int in_stride;       // elements per input pixel; Cin_pad channels are readable
-    const void *wt;                      // the phases' filter blocks back to back, in the operand type (in_dt)
-    const float *bias;                   // [cout_pad] fp32 (BN folded)
-    void *out; int out_stride; int out_dt, in_dt;      // out_dt: in_dt, or DT_F32 (a "head": the map network's output)
-    int N, H, W, Cin_pad, Ho, Wo, Cout;
-    int Cstore;                          // channels written per pixel: Cout rounded up to the output's granule (zeros past Cout), a multiple of 4
-    int size, stride, pad, act;          // act: slope family only
-    int cout_pad;
+struct DeconvArgs : SideConvArgs {      // in: Cin_pad channels are readable; wt: the phases' filter blocks back to back, in the operand type (in_dt); bias: [cout_pad]
+    int Cin_pad, cout_pad;
     int woff[DECONV_MAX_STRIDE * DECONV_MAX_STRIDE], kp[DECONV_MAX_STRIDE * DECONV_MAX_STRIDE];      // per phase py * stride + px: element offset of its block in wt, its padded K
 };
 __host__ __device__ inline int deconv_taps(int p, int size, int stride) { return p < size ? (size - p + stride - 1) / stride : 0; }
@@ -282,14 +297,8 @@ hipError_t launch_deconv(const DeconvArgs &a, hipStream_t s);
 #define GCONV_MAX_STRIDE 4
 #define GCONV_CO_TILE 32             // output channels of a bundle per wave: a bundle of more is cut into pieces of this size
 #define GCONV_PT 2                   // 16-pixel tiles per wave: one filter fragment feeds this many MFMAs
-struct GConvArgs {
-    const void *in; int in_stride;       // elements per input pixel; the channels up to C rounded up to 8 are readable and finite
-    const void *wt;                      // the bundles' filter blocks back to back, in the operand type (in_dt)
-    const float *bias;                   // [nb * mb] fp32 (BN folded)
-    void *out; int out_stride; int out_dt, in_dt;      // out_dt: in_dt, or DT_F32 (a "head": logits, a map network's output)
-    int N, H, W, C, Ho, Wo, Cout;
-    int Cstore;                          // channels written per pixel: Cout rounded up to the output's granule (zeros past Cout), a multiple of 4
-    int size, stride, pad, act;          // act: slope family only
+struct GConvArgs : SideConvArgs {       // in: the channels up to C rounded up to 8 are readable and finite; wt: the bundles' filter blocks back to back, in the operand type (in_dt); bias: [nb * mb]
+    int C;
     int groups, cg, m, t, nb, kc, mb, kp;      // the bundle layout (gconv_layout)
 };
 // fills cg .. kp from (C, Cout, groups, size, in_dt); returns the elements of all blocks together
@@ -328,14 +337,10 @@ hipError_t launch_gconv(const GConvArgs &a, hipStream_t s);
 #define XCONV_TILE 8                 // edge of the block of output pixels of one workgroup: 64 pixels, four 16-pixel MFMA columns
 #define XCONV_CO_TILE 64             // filters of one workgroup pass: the four waves take 32 pixels x 32 filters each
 #define XCONV_LDS_BYTES (128 * 1024)
-struct XConvArgs {
-    const void *in; int in_stride, in_dt;      // the producer's tensor as stored (bf16, fp16 or fp32); the channels up to C rounded up to 8 are readable
-    const int8_t *wt;                    // [cout_pad / 16][kpad / 64][64][16]
-    const float *scale, *bias;           // [cout_pad] each: alpha_f (* the folded batch-norm scale), the folded shift; zeros past Cout
-    void *out; int out_stride, out_dt;   // out_dt: bf16 / fp16 / fp32
-    int N, H, W, C, Ho, Wo, Cout;
-    int Cstore;                          // channels written per pixel: Cout rounded up to the output's granule (zeros past Cout), a multiple of 4
-    int size, stride, pad, act;          // act: slope family only
+struct XConvArgs : SideConvArgs {       // in: the producer's tensor as stored (in_dt: bf16, fp16 or fp32, whatever out_dt is), the channels up to C rounded up to 8 are readable;
+                                        // wt: int8 [cout_pad / 16][kpad / 64][64][16]; bias: [cout_pad], the folded shift, zeros past Cout
+    const float *scale;                  // [cout_pad]: alpha_f (* the folded batch-norm scale), zeros past Cout
+    int C;
     int te, rs, ww, cc, nchunks, kpad, cout_pad;      // xconv_layout
 };
 // fills te .. cout_pad from (C, Cout, size, stride); returns the bytes of the filters

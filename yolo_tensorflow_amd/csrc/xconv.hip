@@ -13,10 +13,10 @@
 // takes granule 4 * step + (lane >> 4) -- so the sum does not depend on the order of the 16 bytes inside a fragment.  The A fragments come
 // straight from global memory in fragment order (one contiguous KiB per wave and load), the B fragments from the window with ds_read_b128;
 // a window position is cc + 16 bytes apart from the next, which spreads the sixteen pixels of a fragment load over the banks.
-// The epilogue is float(acc) * scale + bias, the slope activation, and the store encoders of elt.h.
+// The epilogue is float(acc) * scale + bias, then the side convs' store (side_epilogue.h).
 #include "kernels.h"
 #include "device_common.h"
-#include "elt.h"
+#include "side_epilogue.h"
 #include <algorithm>
 
 namespace {
@@ -96,7 +96,7 @@ __global__ __launch_bounds__(256) void k_xconv(const XConvArgs a, const int fper
                 __syncthreads();
             }
             const int ccg = ccj >> 4, ng = taps * ccg, nsteps = (ng + 3) >> 2;
-            const int8_t *wt = a.wt + ((((long)(ft * 4 + wf * 2) * KS + ch * chunk_steps) * 64 + lane) << 4);
+            const int8_t *wt = (const int8_t *)a.wt + ((((long)(ft * 4 + wf * 2) * KS + ch * chunk_steps) * 64 + lane) << 4);
             // this lane's granule 4 * step + lq as (tap row, tap column, granule of the chunk), advanced by 4 per step without a division
             int gi = lq, ty = 0, tx = 0;
             while (gi >= ccg) { gi -= ccg; if (++tx == a.size) { tx = 0; ++ty; } }
@@ -123,12 +123,8 @@ __global__ __launch_bounds__(256) void k_xconv(const XConvArgs a, const int fper
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 if (!pv[j]) continue;
-                float v[4] = {(float)acc[i][j][0] * sc.x + bv.x, (float)acc[i][j][1] * sc.y + bv.y, (float)acc[i][j][2] * sc.z + bv.z, (float)acc[i][j][3] * sc.w + bv.w};
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], v[e] * slope);
-                if (a.out_dt == DT_F32) *(float4 *)((float *)a.out + opix[j] * a.out_stride + co) = float4{v[0], v[1], v[2], v[3]};
-                else if (a.out_dt == DT_F16) *(uint2 *)((uint16_t *)a.out + opix[j] * a.out_stride + co) = uint2{Elt<f16_t>::pk(v[0], v[1]), Elt<f16_t>::pk(v[2], v[3])};
-                else *(uint2 *)((uint16_t *)a.out + opix[j] * a.out_stride + co) = uint2{Elt<bf16_t>::cvt(v[0]) | (Elt<bf16_t>::cvt(v[1]) << 16), Elt<bf16_t>::cvt(v[2]) | (Elt<bf16_t>::cvt(v[3]) << 16)};
+                const float v[4] = {(float)acc[i][j][0] * sc.x + bv.x, (float)acc[i][j][1] * sc.y + bv.y, (float)acc[i][j][2] * sc.z + bv.z, (float)acc[i][j][3] * sc.w + bv.w};
+                side_store4(a.out, opix[j] * a.out_stride + co, a.out_dt, slope, v);
             }
         }
     }
@@ -145,15 +141,13 @@ template <typename T> hipError_t launch_t(const XConvArgs &a, const dim3 grid, i
 
 hipError_t launch_xconv(const XConvArgs &a, hipStream_t s)
 {
-    if (a.C < 1 || a.Cout < 1 || a.N < 1 || !xconv_served(a.size, a.stride, a.pad, a.H, a.W)) return hipErrorInvalidValue;
+    if (a.C < 1 || a.Cout < 1 || !xconv_served(a.size, a.stride, a.pad, a.H, a.W)) return hipErrorInvalidValue;
     XConvArgs g = a; xconv_layout(g);
     if (g.te != a.te || g.rs != a.rs || g.ww != a.ww || g.cc != a.cc || g.nchunks != a.nchunks || g.kpad != a.kpad || g.cout_pad != a.cout_pad) return hipErrorInvalidValue;
-    if (a.in_stride % 8 || a.in_stride < (a.C + 7) / 8 * 8 || a.Cstore % 4 || a.Cstore < a.Cout || a.Cstore > a.cout_pad || a.Cstore > a.out_stride || a.out_stride % 4 || !act_is_slope(a.act) ||
+    if (!side_conv_args_ok(a, a.cout_pad) || ((uintptr_t)a.scale & 15) || a.in_stride < (a.C + 7) / 8 * 8 ||
         a.Ho != (a.H + 2 * a.pad - a.size) / a.stride + 1 || a.Wo != (a.W + 2 * a.pad - a.size) / a.stride + 1) return hipErrorInvalidValue;
     if (a.in_dt != DT_BF16 && a.in_dt != DT_F16 && a.in_dt != DT_F32) return hipErrorInvalidValue;
     if (a.out_dt != DT_BF16 && a.out_dt != DT_F16 && a.out_dt != DT_F32) return hipErrorInvalidValue;
-    // 16-byte loads of the window's pieces and of the fragments, 8- / 16-byte stores
-    if (((uintptr_t)a.in & 15) || ((uintptr_t)a.wt & 15) || ((uintptr_t)a.scale & 15) || ((uintptr_t)a.bias & 15) || ((uintptr_t)a.out & (a.out_dt == DT_F32 ? 15 : 7))) return hipErrorInvalidValue;
     const size_t lds = (size_t)a.ww * a.ww * (a.cc + 16);
     if (lds > XCONV_LDS_BYTES) return hipErrorInvalidValue;
     const long blocks = (long)a.N * ((a.Ho + a.te - 1) / a.te) * ((a.Wo + a.te - 1) / a.te);

@@ -1,8 +1,9 @@
 // Private to libyolo_hip.so's host side: the planned network (layers, storage pool, context) and the functions its translation
-// units share.  yolo_plan.cpp: darknet-cfg parser, planner, buffer pool, the plan queries that need no device.  yolo_pack.cpp: BN fold, filter packing, fp8 scales, weight
-// stream / export artifact.  yolo_run.cpp: launch sequence, input staging (input_fill_dst / input_filled), the two captured detect steps (graph_step over
+// units share.  yolo_plan.cpp: darknet-cfg parser, planner, buffer pool, the plan queries that need no device.  yolo_pack.cpp: BN fold (fold_bn), filter packing
+// (put_elt), fp8 scales, weight stream / export artifact.  yolo_run.cpp: launch sequence, input staging (input_fill_dst / input_filled), the two captured detect steps (graph_step over
 // yolo_ctx::graph), what a forward leaves (forward_done), timing.  yolo_tune.cpp: tile selection rule, autotuner, tile plan.  yolo_api.cpp: create / destroy,
-// introspection, darknet-flavoured views.  yolo_ops.cpp: single-operator entry points.
+// introspection, darknet-flavoured views.  yolo_ops.cpp: single-operator entry points.  The side convs ([deconvolutional], groups=, xnor=1: is_side_conv below) share
+// their argument fields and launch checks (SideConvArgs, kernels.h), their store (side_epilogue.h), one run_layer case and one operator body.
 #pragma once
 #include "../../include/yolo_hip.h"
 #include "kernels.h"
@@ -20,12 +21,12 @@
 namespace yolo_impl {
 
 enum LType { L_CONV, L_SHORTCUT, L_ROUTE, L_UPSAMPLE, L_MAXPOOL, L_REORG, L_YOLO, L_REGION, L_DETECT, L_LOCAL, L_AVGPOOL, L_SOFTMAX,
-             L_DECONV, L_ACTIVATE, L_L2NORM,        // [deconvolutional]; [logistic] / [activation]: k_activate over the producer's tensor; [l2norm]
-             L_GCONV,                               // [convolutional] with groups > 1 (gconv.hip); Layer::groups
+             L_DECONV, L_ACTIVATE, L_L2NORM,        // [deconvolutional] (deconv.hip), a side conv: is_side_conv; [logistic] / [activation]: k_activate over the producer's tensor; [l2norm]
+             L_GCONV,                               // [convolutional] with groups > 1 (gconv.hip), a side conv; Layer::groups
              L_RECUR,                               // [rnn] / [gru] / [lstm] (rnn_ops.hip); Layer::rkind
              L_CRNN,                                // [crnn]: three 3x3 convs around a state map, run by the dense conv kernels; Layer::sub
              L_LRN, L_CROP,                         // [normalization] / [lrn]: k_lrn, Layer::size / lrn_*; [crop] at inference: k_crop, the output geometry and Layer::crop_adjust
-             L_XCONV };                             // [convolutional] with xnor=1 (xconv.hip): int8 signs in d_w, the per-filter scale in d_sc
+             L_XCONV };                             // [convolutional] with xnor=1 (xconv.hip), a side conv: int8 signs in d_w, the per-filter scale in d_sc
 enum ConvKernel { K_TILED, K_HALO, K_S2 };      // a conv's own kernel: the tiled family (fp32 / direct / pair form picked by dtype), conv_halo_c32_c64 (3x3/s1, 32 -> 64), conv_s2_c64_c128 (3x3/s2, 64 -> 128)
 // the fused launch a conv is a member of, {members} -> launcher: conv_stem.hip {0, 1, optionally the 1x1 conv 2} -> 1; conv_stem_pair.hip (split-fp16) {0, 1} -> 1; conv_block.hip {1x1 i, 3x3 i + 1} -> i + 1; conv_c3s2.hip {conv3 i, stride-2 conv i + 2} -> i + 2 (both keep K_HALO / K_S2, the fall-back)
 enum FuseKind { F_NONE, F_STEM, F_PSTEM, F_RESBLOCK, F_C3S2 };
@@ -219,7 +220,9 @@ inline void drop_graph(yolo_ctx *c)      // a plan / parameter / buffer change: 
 }
 
 // ---- layer kinds the planner asks for by more than one name ----
-inline bool computes(const Layer &L) { return L.type == L_CONV || L.type == L_DECONV || L.type == L_GCONV || L.type == L_XCONV || L.type == L_RECUR || L.type == L_CRNN; }      // has filters and an MFMA kernel ([connected] is an L_CONV; [local] is not among them)
+inline bool is_side_conv(const Layer &L) { return L.type == L_DECONV || L.type == L_GCONV || L.type == L_XCONV; }      // SideConvArgs (kernels.h): a kernel of its own, never a member of a fused launch, neither end of a 1x1 tail, nothing for the tile tuner
+inline bool has_packed_filters(const Layer &L) { return L.type == L_CONV || L.type == L_LOCAL || is_side_conv(L); }      // d_w / d_b [/ d_sc] blobs of an export artifact
+inline bool computes(const Layer &L) { return L.type == L_CONV || is_side_conv(L) || L.type == L_RECUR || L.type == L_CRNN; }      // has filters and an MFMA kernel ([connected] is an L_CONV; [local] is not among them)
 inline bool has_state(const Layer &L) { return L.type == L_RECUR || L.type == L_CRNN; }
 inline bool is_head_layer(const Layer &L) { return L.type == L_YOLO || L.type == L_REGION || L.type == L_DETECT; }      // a detection head: no tensor of its own, an alias of the conv in front of it
 
@@ -279,6 +282,7 @@ ConvArgs conv_args(const yolo_ctx *c, const Layer &L, int n);
 DeconvArgs deconv_geometry(int size, int stride, int pad, int h, int w, int cin_pad, int filters, int act, int in_dt);      // everything of DeconvArgs but pointers, strides, N, out_dt, Cstore
 GConvArgs gconv_geometry(int size, int stride, int pad, int h, int w, int cin, int filters, int groups, int act, int in_dt);      // the same of GConvArgs
 XConvArgs xconv_geometry(int size, int stride, int pad, int h, int w, int cin, int filters, int act);      // the same of XConvArgs
+void side_layout(const Layer &L, int &kpad, int &cout_pad);      // a side conv's cout_pad * kpad filter elements, from its kind's geometry; reads type, size, stride, pad, filters, groups, cin, cin_pad, in_dt
 int run_layer(yolo_ctx *c, int i, int n);
 int stage_in(yolo_ctx *c, const void *images, int n, int fmt, int loc, float scale);
 int run_network(yolo_ctx *c, int n, bool lean = false, int fit = -1);      // fit >= 0: the input is a fitted ragged batch (forward_done records its geometry)

@@ -41,6 +41,51 @@ int act_from_name(const char *name)
     return -1;
 }
 
+// The body behind the three side-conv operators (SideConvArgs, kernels.h): x [n,h,w,cin] fp32 NHWC, the filters in the order of darknet's weight files, bias [cout]
+// or NULL.  The operands are stored as `dtype` first; out_f32 != 0: the fp32 ("head") store of a 16-bit kernel.  An activation outside the slope family runs
+// as the planner plans it: a linear epilogue, then k_activate on the output.  What a kind brings: its name and the phrases of its messages, `invalid` (a
+// message of its own for arguments it alone checks, or NULL), `served` (its size / stride / padding rule), and two callables --
+//   pack(dt, act, b0, wbuf, bv, sv) -> its argument struct with the geometry filled, the filters packed into wbuf, the bias into bv and, an xnor conv, the scale into sv
+//   launch(a, d_sv, stream): its launcher (d_sv: the uploaded sv, NULL where sv stayed empty)
+struct SideOp { const char *name, *kind, *invalid; bool served; const char *served_text; };
+template <class Pack, class Launch>
+static int op_side_conv(const SideOp &op, const float *x, int n, int h, int w, int cin, const float *filters, const float *bias, int cout, int act, int dtype, int out_f32,
+                        float *out, int device, Pack pack, Launch launch)
+{
+    const std::string name = op.name;
+    if (!x || !filters || !out || n < 1 || h < 1 || w < 1 || cin < 1 || cout < 1 || act < 0 || act >= ACT_COUNT) { g_op_err = name + ": bad arguments"; return YOLO_ERR_INVALID; }
+    if (op.invalid) { g_op_err = name + ": " + op.invalid; return YOLO_ERR_INVALID; }
+    if (dtype != YOLO_FP32 && dtype != YOLO_BF16 && dtype != YOLO_FP16) { g_op_err = name + ": dtype (fp32, bf16 or fp16; the fp8 and split-fp16 configurations do not serve " + op.kind + ")"; return YOLO_ERR_UNSUPPORTED; }
+    if (!op.served) { g_op_err = name + ": served are " + op.served_text; return YOLO_ERR_UNSUPPORTED; }
+    OpScope S(device); if (S.rc) { g_op_err = name + ": no HIP device"; return S.rc; }
+    const int dt = dtype == YOLO_FP32 ? DT_F32 : dtype == YOLO_FP16 ? DT_F16 : DT_BF16, odt = (out_f32 || dt == DT_F32) ? DT_F32 : dt;
+    std::vector<float> b0(cout, 0.f); if (bias) memcpy(b0.data(), bias, (size_t)cout * 4);
+    std::vector<uint8_t> wbuf; std::vector<float> bv, sv;
+    auto a = pack(dt, act_is_slope(act) ? act : ACT_LINEAR, b0.data(), wbuf, bv, sv);
+    const int cin_pad = roundup(cin, 8), cs = roundup(cout, odt == DT_F32 && dt != DT_F32 ? 4 : 8);
+    const size_t pin = (size_t)n * h * w, pout = (size_t)n * a.Ho * a.Wo;
+    void *d_w = S.upload(wbuf.data(), wbuf.size()); float *d_s = sv.empty() ? nullptr : (float *)S.upload(sv.data(), sv.size() * 4), *d_b = (float *)S.upload(bv.data(), bv.size() * 4);
+    float *d_x32 = (float *)S.upload(x, pin * cin * 4);
+    void *d_x = S.alloc(pin * cin_pad * dt_size(dt)), *d_o = S.alloc(pout * cs * dt_size(odt)); float *d_o32 = (float *)S.alloc(pout * cout * 4);
+    if (S.rc) { g_op_err = name + ": allocation failed"; return S.rc; }
+    if (!S.ok(launch_from_f32(d_x32, make_view(d_x, n, h, w, cin, cin_pad, dt), S.s))) { g_op_err = S.err; return S.rc; }
+    a.in = d_x; a.in_stride = cin_pad; a.in_dt = dt; a.wt = d_w; a.bias = d_b; a.out = d_o; a.out_stride = cs; a.out_dt = odt; a.N = n; a.Cstore = cs;
+    const TView vo = make_view(d_o, n, a.Ho, a.Wo, cout, cs, odt);
+    if (!S.ok(launch(a, d_s, S.s))) { g_op_err = name + " launch: " + S.err; return S.rc; }
+    if (!act_is_slope(act) && !S.ok(launch_activate(vo, false, act, S.s))) { g_op_err = name + " activation: " + S.err; return S.rc; }
+    if (!S.ok(launch_to_f32(vo, d_o32, S.s))) { g_op_err = S.err; return S.rc; }
+    S.download(out, d_o32, pout * cout * 4);
+    if (S.rc) g_op_err = name + ": " + std::string(hipGetErrorString(hipGetLastError()));
+    return S.rc;
+}
+// the Layer the packers read
+static Layer side_op_layer(LType type, int cin, int cout, int size, int stride, int padding, int groups, int dt)
+{
+    Layer L; L.type = type; L.filters = cout; L.size = size; L.stride = stride; L.pad = padding; L.bn = 0; L.in_dt = dt; L.groups = groups;
+    L.cin = cin; L.cin_pad = roundup(cin, 8);
+    return L;
+}
+
 extern "C" {
 
 int yolo_activation_code(const char *name) { return act_from_name(name); }
@@ -260,104 +305,41 @@ int yolo_op_conv2d_pad(const float *x, int n, int h, int w, int cin, const float
     return op_conv2d_any(x, n, h, w, cin, w_hwio, bias, k, stride, padding, cout, act, residual, out, dtype, tile_cfg, device);
 }
 
-// darknet's [deconvolutional] on host tensors: x [n,h,w,cin] fp32 NHWC, w_iohw [cin][cout][size][size] (the order of darknet's weight files), bias
-// [cout] or NULL.  The operands are stored as `dtype` first; out_f32 != 0: the fp32 ("head") store of a 16-bit kernel.  An activation
-// outside the slope family runs as the planner plans it: a linear epilogue, then k_activate on the output.
+// darknet's [deconvolutional]: w_iohw [cin][cout][size][size]
 int yolo_op_deconv2d(const float *x, int n, int h, int w, int cin, const float *w_iohw, const float *bias, int size, int stride, int padding,
                      int cout, int act, int dtype, int out_f32, float *out, int device)
 {
-    if (!x || !w_iohw || !out || n < 1 || h < 1 || w < 1 || cin < 1 || cout < 1 || act < 0 || act >= ACT_COUNT) { g_op_err = "deconv2d: bad arguments"; return YOLO_ERR_INVALID; }
-    if (dtype != YOLO_FP32 && dtype != YOLO_BF16 && dtype != YOLO_FP16) { g_op_err = "deconv2d: dtype (fp32, bf16 or fp16; the fp8 and split-fp16 configurations do not serve [deconvolutional])"; return YOLO_ERR_UNSUPPORTED; }
-    if (!deconv_served(size, stride, padding, h, w)) { g_op_err = "deconv2d: served are 1 <= size <= 7, 1 <= stride <= 4, 0 <= padding < size and a positive output"; return YOLO_ERR_UNSUPPORTED; }
-    OpScope S(device); if (S.rc) { g_op_err = "deconv2d: no HIP device"; return S.rc; }
-    const int dt = dtype == YOLO_FP32 ? DT_F32 : dtype == YOLO_FP16 ? DT_F16 : DT_BF16, odt = (out_f32 || dt == DT_F32) ? DT_F32 : dt;
-    Layer L; L.type = L_DECONV; L.filters = cout; L.size = size; L.stride = stride; L.pad = padding; L.bn = 0; L.in_dt = dt;
-    L.cin = cin; L.cin_pad = roundup(cin, 8); L.cout_pad = roundup(cout, DECONV_CO_TILE);
-    DeconvArgs a = deconv_geometry(size, stride, padding, h, w, L.cin_pad, cout, act_is_slope(act) ? act : ACT_LINEAR, dt);
-    std::vector<float> b0(cout, 0.f); if (bias) memcpy(b0.data(), bias, (size_t)cout * 4);
-    std::vector<uint8_t> wbuf; std::vector<float> bv; pack_deconv(L, b0.data(), w_iohw, dt, wbuf, bv);
-    const int cs = roundup(cout, odt == DT_F32 && dt != DT_F32 ? 4 : 8);
-    const size_t pin = (size_t)n * h * w, pout = (size_t)n * a.Ho * a.Wo;
-    void *d_w = S.upload(wbuf.data(), wbuf.size()); float *d_b = (float *)S.upload(bv.data(), bv.size() * 4);
-    float *d_x32 = (float *)S.upload(x, pin * cin * 4);
-    void *d_x = S.alloc(pin * L.cin_pad * dt_size(dt)), *d_o = S.alloc(pout * cs * dt_size(odt)); float *d_o32 = (float *)S.alloc(pout * cout * 4);
-    if (S.rc) { g_op_err = "deconv2d: allocation failed"; return S.rc; }
-    if (!S.ok(launch_from_f32(d_x32, make_view(d_x, n, h, w, cin, L.cin_pad, dt), S.s))) { g_op_err = S.err; return S.rc; }
-    a.in = d_x; a.in_stride = L.cin_pad; a.wt = d_w; a.bias = d_b; a.out = d_o; a.out_stride = cs; a.out_dt = odt; a.N = n; a.Cstore = cs;
-    const TView vo = make_view(d_o, n, a.Ho, a.Wo, cout, cs, odt);
-    if (!S.ok(launch_deconv(a, S.s))) { g_op_err = "deconv2d launch: " + S.err; return S.rc; }
-    if (!act_is_slope(act) && !S.ok(launch_activate(vo, false, act, S.s))) { g_op_err = "deconv2d activation: " + S.err; return S.rc; }
-    if (!S.ok(launch_to_f32(vo, d_o32, S.s))) { g_op_err = S.err; return S.rc; }
-    S.download(out, d_o32, pout * cout * 4);
-    if (S.rc) g_op_err = "deconv2d: " + std::string(hipGetErrorString(hipGetLastError()));
-    return S.rc;
+    const SideOp op = {"deconv2d", "[deconvolutional]", nullptr, deconv_served(size, stride, padding, h, w), "1 <= size <= 7, 1 <= stride <= 4, 0 <= padding < size and a positive output"};
+    return op_side_conv(op, x, n, h, w, cin, w_iohw, bias, cout, act, dtype, out_f32, out, device,
+        [&](int dt, int a, const float *b0, std::vector<uint8_t> &wbuf, std::vector<float> &bv, std::vector<float> &) {
+            pack_deconv(side_op_layer(L_DECONV, cin, cout, size, stride, padding, 1, dt), b0, w_iohw, dt, wbuf, bv);
+            return deconv_geometry(size, stride, padding, h, w, roundup(cin, 8), cout, a, dt); },
+        [](const DeconvArgs &a, const float *, hipStream_t s) { return launch_deconv(a, s); });
 }
 
-// darknet's [convolutional] with groups= on host tensors: x [n,h,w,cin] fp32 NHWC, w_oihw [cout][cin / groups][size][size] (the order of darknet's weight
-// files), bias [cout] or NULL.  groups == 1 runs the same kernel with one group.  The operands are stored as `dtype` first; out_f32 != 0: the
-// fp32 ("head") store of a 16-bit kernel.  An activation outside the slope family runs as the planner plans it: a linear epilogue, then k_activate
+// darknet's [convolutional] with groups=: w_oihw [cout][cin / groups][size][size].  groups == 1 runs the same kernel with one group
 int yolo_op_conv2d_grouped(const float *x, int n, int h, int w, int cin, const float *w_oihw, const float *bias, int size, int stride, int padding,
                            int cout, int groups, int act, int dtype, int out_f32, float *out, int device)
 {
-    if (!x || !w_oihw || !out || n < 1 || h < 1 || w < 1 || cin < 1 || cout < 1 || act < 0 || act >= ACT_COUNT) { g_op_err = "conv2d_grouped: bad arguments"; return YOLO_ERR_INVALID; }
-    if (groups < 1 || cin % groups || cout % groups) { g_op_err = "conv2d_grouped: groups must be >= 1 and divide cin and cout"; return YOLO_ERR_INVALID; }
-    if (dtype != YOLO_FP32 && dtype != YOLO_BF16 && dtype != YOLO_FP16) { g_op_err = "conv2d_grouped: dtype (fp32, bf16 or fp16; the fp8 and split-fp16 configurations do not serve groups=)"; return YOLO_ERR_UNSUPPORTED; }
-    if (!gconv_served(size, stride, padding, h, w)) { g_op_err = "conv2d_grouped: served are 1 <= size <= 7, 1 <= stride <= 4, 0 <= padding < size and a positive output"; return YOLO_ERR_UNSUPPORTED; }
-    OpScope S(device); if (S.rc) { g_op_err = "conv2d_grouped: no HIP device"; return S.rc; }
-    const int dt = dtype == YOLO_FP32 ? DT_F32 : dtype == YOLO_FP16 ? DT_F16 : DT_BF16, odt = (out_f32 || dt == DT_F32) ? DT_F32 : dt;
-    Layer L; L.type = L_GCONV; L.filters = cout; L.size = size; L.stride = stride; L.pad = padding; L.bn = 0; L.in_dt = dt; L.groups = groups;
-    L.cin = cin; L.cin_pad = roundup(cin, 8);
-    GConvArgs a = gconv_geometry(size, stride, padding, h, w, cin, cout, groups, act_is_slope(act) ? act : ACT_LINEAR, dt);
-    std::vector<float> b0(cout, 0.f); if (bias) memcpy(b0.data(), bias, (size_t)cout * 4);
-    std::vector<uint8_t> wbuf; std::vector<float> bv; pack_gconv(L, b0.data(), w_oihw, dt, wbuf, bv);
-    const int cs = roundup(cout, odt == DT_F32 && dt != DT_F32 ? 4 : 8);
-    const size_t pin = (size_t)n * h * w, pout = (size_t)n * a.Ho * a.Wo;
-    void *d_w = S.upload(wbuf.data(), wbuf.size()); float *d_b = (float *)S.upload(bv.data(), bv.size() * 4);
-    float *d_x32 = (float *)S.upload(x, pin * cin * 4);
-    void *d_x = S.alloc(pin * L.cin_pad * dt_size(dt)), *d_o = S.alloc(pout * cs * dt_size(odt)); float *d_o32 = (float *)S.alloc(pout * cout * 4);
-    if (S.rc) { g_op_err = "conv2d_grouped: allocation failed"; return S.rc; }
-    if (!S.ok(launch_from_f32(d_x32, make_view(d_x, n, h, w, cin, L.cin_pad, dt), S.s))) { g_op_err = S.err; return S.rc; }
-    a.in = d_x; a.in_stride = L.cin_pad; a.wt = d_w; a.bias = d_b; a.out = d_o; a.out_stride = cs; a.out_dt = odt; a.N = n; a.Cstore = cs;
-    const TView vo = make_view(d_o, n, a.Ho, a.Wo, cout, cs, odt);
-    if (!S.ok(launch_gconv(a, S.s))) { g_op_err = "conv2d_grouped launch: " + S.err; return S.rc; }
-    if (!act_is_slope(act) && !S.ok(launch_activate(vo, false, act, S.s))) { g_op_err = "conv2d_grouped activation: " + S.err; return S.rc; }
-    if (!S.ok(launch_to_f32(vo, d_o32, S.s))) { g_op_err = S.err; return S.rc; }
-    S.download(out, d_o32, pout * cout * 4);
-    if (S.rc) g_op_err = "conv2d_grouped: " + std::string(hipGetErrorString(hipGetLastError()));
-    return S.rc;
+    const SideOp op = {"conv2d_grouped", "groups=", (groups < 1 || cin % groups || cout % groups) ? "groups must be >= 1 and divide cin and cout" : nullptr,
+                       gconv_served(size, stride, padding, h, w), "1 <= size <= 7, 1 <= stride <= 4, 0 <= padding < size and a positive output"};
+    return op_side_conv(op, x, n, h, w, cin, w_oihw, bias, cout, act, dtype, out_f32, out, device,
+        [&](int dt, int a, const float *b0, std::vector<uint8_t> &wbuf, std::vector<float> &bv, std::vector<float> &) {
+            pack_gconv(side_op_layer(L_GCONV, cin, cout, size, stride, padding, groups, dt), b0, w_oihw, dt, wbuf, bv);
+            return gconv_geometry(size, stride, padding, h, w, cin, cout, groups, a, dt); },
+        [](const GConvArgs &a, const float *, hipStream_t s) { return launch_gconv(a, s); });
 }
 
-// darknet's [convolutional] with xnor=1 on host tensors: x [n,h,w,cin] fp32 NHWC, w_oihw [cout][cin][size][size] (the order of darknet's weight files), bias
-// [cout] or NULL.  x is stored as `dtype` first and the sign is taken of the stored value; the filters become alpha_f * sign(w).  out_f32 != 0: the fp32
-// ("head") store of a 16-bit configuration.  An activation outside the slope family runs as the planner plans it: a linear epilogue, then k_activate
+// darknet's [convolutional] with xnor=1: w_oihw [cout][cin][size][size].  The sign is taken of x as stored; the filters become alpha_f * sign(w)
 int yolo_op_conv2d_xnor(const float *x, int n, int h, int w, int cin, const float *w_oihw, const float *bias, int size, int stride, int padding,
                         int cout, int act, int dtype, int out_f32, float *out, int device)
 {
-    if (!x || !w_oihw || !out || n < 1 || h < 1 || w < 1 || cin < 1 || cout < 1 || act < 0 || act >= ACT_COUNT) { g_op_err = "conv2d_xnor: bad arguments"; return YOLO_ERR_INVALID; }
-    if (dtype != YOLO_FP32 && dtype != YOLO_BF16 && dtype != YOLO_FP16) { g_op_err = "conv2d_xnor: dtype (fp32, bf16 or fp16; the fp8 and split-fp16 configurations do not serve xnor=1)"; return YOLO_ERR_UNSUPPORTED; }
-    if (!xconv_served(size, stride, padding, h, w)) { g_op_err = "conv2d_xnor: served are 1 <= size <= 11, stride >= 1, padding >= 0 and a positive output"; return YOLO_ERR_UNSUPPORTED; }
-    OpScope S(device); if (S.rc) { g_op_err = "conv2d_xnor: no HIP device"; return S.rc; }
-    const int dt = dtype == YOLO_FP32 ? DT_F32 : dtype == YOLO_FP16 ? DT_F16 : DT_BF16, odt = (out_f32 || dt == DT_F32) ? DT_F32 : dt;
-    Layer L; L.type = L_XCONV; L.filters = cout; L.size = size; L.stride = stride; L.pad = padding; L.bn = 0; L.in_dt = dt;
-    L.cin = cin; L.cin_pad = roundup(cin, 8);
-    XConvArgs a = xconv_geometry(size, stride, padding, h, w, cin, cout, act_is_slope(act) ? act : ACT_LINEAR);
-    std::vector<float> b0(cout, 0.f); if (bias) memcpy(b0.data(), bias, (size_t)cout * 4);
-    std::vector<uint8_t> wbuf; std::vector<float> sv, bv; pack_xconv(L, b0.data(), w_oihw, wbuf, sv, bv);
-    const int cs = roundup(cout, odt == DT_F32 && dt != DT_F32 ? 4 : 8);
-    const size_t pin = (size_t)n * h * w, pout = (size_t)n * a.Ho * a.Wo;
-    void *d_w = S.upload(wbuf.data(), wbuf.size()); float *d_s = (float *)S.upload(sv.data(), sv.size() * 4), *d_b = (float *)S.upload(bv.data(), bv.size() * 4);
-    float *d_x32 = (float *)S.upload(x, pin * cin * 4);
-    void *d_x = S.alloc(pin * L.cin_pad * dt_size(dt)), *d_o = S.alloc(pout * cs * dt_size(odt)); float *d_o32 = (float *)S.alloc(pout * cout * 4);
-    if (S.rc) { g_op_err = "conv2d_xnor: allocation failed"; return S.rc; }
-    if (!S.ok(launch_from_f32(d_x32, make_view(d_x, n, h, w, cin, L.cin_pad, dt), S.s))) { g_op_err = S.err; return S.rc; }
-    a.in = d_x; a.in_stride = L.cin_pad; a.in_dt = dt; a.wt = (const int8_t *)d_w; a.scale = d_s; a.bias = d_b; a.out = d_o; a.out_stride = cs; a.out_dt = odt; a.N = n; a.Cstore = cs;
-    const TView vo = make_view(d_o, n, a.Ho, a.Wo, cout, cs, odt);
-    if (!S.ok(launch_xconv(a, S.s))) { g_op_err = "conv2d_xnor launch: " + S.err; return S.rc; }
-    if (!act_is_slope(act) && !S.ok(launch_activate(vo, false, act, S.s))) { g_op_err = "conv2d_xnor activation: " + S.err; return S.rc; }
-    if (!S.ok(launch_to_f32(vo, d_o32, S.s))) { g_op_err = S.err; return S.rc; }
-    S.download(out, d_o32, pout * cout * 4);
-    if (S.rc) g_op_err = "conv2d_xnor: " + std::string(hipGetErrorString(hipGetLastError()));
-    return S.rc;
+    const SideOp op = {"conv2d_xnor", "xnor=1", nullptr, xconv_served(size, stride, padding, h, w), "1 <= size <= 11, stride >= 1, padding >= 0 and a positive output"};
+    return op_side_conv(op, x, n, h, w, cin, w_oihw, bias, cout, act, dtype, out_f32, out, device,
+        [&](int dt, int a, const float *b0, std::vector<uint8_t> &wbuf, std::vector<float> &bv, std::vector<float> &sv) {
+            pack_xconv(side_op_layer(L_XCONV, cin, cout, size, stride, padding, 1, dt), b0, w_oihw, wbuf, sv, bv);
+            return xconv_geometry(size, stride, padding, h, w, cin, cout, a); },
+        [](XConvArgs &a, const float *d_sv, hipStream_t s) { a.scale = d_sv; return launch_xconv(a, s); });
 }
 
 int yolo_op_l2norm(const float *x, int n, int h, int w, int c, int dtype, float *out, int device)

@@ -62,23 +62,38 @@ float h2f(uint16_t h)
     return (h & 0x8000) ? -v : v;
 }
 
+// Batch norm as a per-filter scale (folded into the filters, or an xnor conv's epilogue scale) and bias.  TF: epsilon inside the sqrt
+// (V3/yolo_v3.py:9).  darknet semantics follow the reference's CPU normalize (DN/blas.c:154: (x - mean) / (sqrt(var) + .000001f)), the code
+// oracle/_ref is compiled from
+static void fold_bn(int n, const float *beta, const float *gamma, const float *mean, const float *var, int semantics, float *scale, float *bias)
+{
+    for (int o = 0; o < n; ++o) {
+        const float s = semantics == YOLO_SEM_DARKNET ? gamma[o] / (sqrtf(var[o]) + 1e-6f) : gamma[o] / sqrtf(var[o] + 1e-5f);
+        scale[o] = s; bias[o] = beta[o] - mean[o] * s;
+    }
+}
+// ... of a conv's parameter block [beta gamma mean var], or (bn == 0) its [bias]: scale 1
+static void fold_bn(int bn, int n, const float *bn_or_bias, int semantics, float *scale, float *bias)
+{
+    if (bn) return fold_bn(n, bn_or_bias, bn_or_bias + n, bn_or_bias + 2 * (size_t)n, bn_or_bias + 3 * (size_t)n, semantics, scale, bias);
+    for (int o = 0; o < n; ++o) { scale[o] = 1.f; bias[o] = bn_or_bias[o]; }
+}
+
+// filter element idx of a buffer of fp32 / fp16 / bf16 filters
+static void put_elt(std::vector<uint8_t> &wbuf, size_t idx, float v, int dt)
+{
+    if (dt == DT_F32) { memcpy(&wbuf[idx * 4], &v, 4); return; }
+    const uint16_t b = dt == DT_F16 ? f2h(v) : f2bf(v);
+    memcpy(&wbuf[idx * 2], &b, 2);
+}
+
 void pack_conv(const Layer &L, const float *bn_or_bias, const float *w_oihw, int wdt, const float *in_scale,
                std::vector<uint8_t> &wbuf, std::vector<float> &bias, std::vector<float> &osc, int semantics, int split)
 {
     const int n = L.filters, k = L.size, cin = L.cin;
     bias.assign(L.cout_pad, 0.f); osc.assign(L.cout_pad, 1.f);
-    std::vector<float> scale(n, 1.f);
-    if (L.bn) {
-        const float *beta = bn_or_bias, *gamma = beta + n, *mean = gamma + n, *var = mean + n;
-        for (int o = 0; o < n; ++o) {
-            // TF: epsilon inside the sqrt (V3/yolo_v3.py:9).  darknet semantics follow the reference's CPU normalize
-            // (DN/blas.c:154: (x - mean) / (sqrt(var) + .000001f)), the code oracle/_ref is compiled from
-            float s = semantics == YOLO_SEM_DARKNET ? gamma[o] / (sqrtf(var[o]) + 1e-6f) : gamma[o] / sqrtf(var[o] + 1e-5f);
-            scale[o] = s; bias[o] = beta[o] - mean[o] * s;
-        }
-    } else {
-        for (int o = 0; o < n; ++o) bias[o] = bn_or_bias[o];
-    }
+    std::vector<float> scale(n);
+    fold_bn(L.bn, n, bn_or_bias, semantics, scale.data(), bias.data());
     const size_t es = dt_size(wdt);
     wbuf.assign((size_t)L.cout_pad * L.kpad * es, 0);
     std::vector<float> row((size_t)cin * k * k);
@@ -116,9 +131,8 @@ void pack_conv(const Layer &L, const float *bn_or_bias, const float *w_oihw, int
                     continue;
                 }
                 const size_t idx = (size_t)o * L.kpad + ((size_t)(ci / kc) * k * k + t) * kc + ci % kc;     // t = kh * k + kw
-                if (wdt == DT_F32) memcpy(&wbuf[idx * 4], &v, 4);
-                else if (wdt == DT_FP8) wbuf[idx] = f2e4m3(v / osc[o]);
-                else { uint16_t b = wdt == DT_F16 ? f2h(v) : f2bf(v); memcpy(&wbuf[idx * 2], &b, 2); }
+                if (wdt == DT_FP8) wbuf[idx] = f2e4m3(v / osc[o]);
+                else put_elt(wbuf, idx, v, wdt);
             }
     }
 }
@@ -128,25 +142,16 @@ void pack_conv(const Layer &L, const float *bn_or_bias, const float *w_oihw, int
 void pack_deconv(const Layer &L, const float *bn_or_bias, const float *w_iohw, int wdt, std::vector<uint8_t> &wbuf, std::vector<float> &bias, int semantics)
 {
     const int n = L.filters, k = L.size, cin = L.cin, st = L.stride;
-    bias.assign(L.cout_pad, 0.f);
-    std::vector<float> scale(n, 1.f);
-    if (L.bn) {
-        const float *beta = bn_or_bias, *gamma = beta + n, *mean = gamma + n, *var = mean + n;
-        for (int o = 0; o < n; ++o) {
-            const float s = semantics == YOLO_SEM_DARKNET ? gamma[o] / (sqrtf(var[o]) + 1e-6f) : gamma[o] / sqrtf(var[o] + 1e-5f);
-            scale[o] = s; bias[o] = beta[o] - mean[o] * s;
-        }
-    } else for (int o = 0; o < n; ++o) bias[o] = bn_or_bias[o];
-    DeconvArgs g; memset(&g, 0, sizeof g); g.size = k; g.stride = st; g.Cin_pad = L.cin_pad; g.cout_pad = L.cout_pad;
-    const size_t es = dt_size(wdt), total = deconv_layout(g);
-    wbuf.assign(total * es, 0);
+    DeconvArgs g = deconv_geometry(k, st, L.pad, 1, 1, L.cin_pad, n, ACT_LINEAR, wdt);
+    bias.assign(g.cout_pad, 0.f);
+    std::vector<float> scale(n);
+    fold_bn(L.bn, n, bn_or_bias, semantics, scale.data(), bias.data());
+    wbuf.assign(deconv_layout(g) * dt_size(wdt), 0);
     for (int kh = 0; kh < k; ++kh) for (int kw = 0; kw < k; ++kw) {
         const int py = kh % st, px = kw % st, phase = py * st + px, tap = (kh / st) * deconv_taps(px, k, st) + kw / st;
         for (int o = 0; o < n; ++o) for (int ci = 0; ci < cin; ++ci) {
             const float v = w_iohw[(((size_t)ci * n + o) * k + kh) * k + kw] * scale[o];
-            const size_t idx = (size_t)g.woff[phase] + (size_t)o * g.kp[phase] + (size_t)tap * L.cin_pad + ci;
-            if (wdt == DT_F32) memcpy(&wbuf[idx * 4], &v, 4);
-            else { const uint16_t b = wdt == DT_F16 ? f2h(v) : f2bf(v); memcpy(&wbuf[idx * 2], &b, 2); }
+            put_elt(wbuf, (size_t)g.woff[phase] + (size_t)o * g.kp[phase] + (size_t)tap * L.cin_pad + ci, v, wdt);
         }
     }
 }
@@ -157,25 +162,16 @@ void pack_deconv(const Layer &L, const float *bn_or_bias, const float *w_iohw, i
 void pack_gconv(const Layer &L, const float *bn_or_bias, const float *w_oihw, int wdt, std::vector<uint8_t> &wbuf, std::vector<float> &bias, int semantics)
 {
     const int n = L.filters, k = L.size;
-    GConvArgs g; memset(&g, 0, sizeof g); g.C = L.cin; g.Cout = n; g.groups = L.groups; g.size = k; g.in_dt = wdt;
-    const size_t es = dt_size(wdt), total = gconv_layout(g);
+    GConvArgs g = gconv_geometry(k, L.stride, L.pad, 1, 1, L.cin, n, L.groups, ACT_LINEAR, wdt);
     bias.assign((size_t)g.nb * g.mb, 0.f);
-    std::vector<float> scale(n, 1.f);
-    if (L.bn) {
-        const float *beta = bn_or_bias, *gamma = beta + n, *mean = gamma + n, *var = mean + n;
-        for (int o = 0; o < n; ++o) {
-            const float s = semantics == YOLO_SEM_DARKNET ? gamma[o] / (sqrtf(var[o]) + 1e-6f) : gamma[o] / sqrtf(var[o] + 1e-5f);
-            scale[o] = s; bias[o] = beta[o] - mean[o] * s;
-        }
-    } else for (int o = 0; o < n; ++o) bias[o] = bn_or_bias[o];
-    wbuf.assign(total * es, 0);
+    std::vector<float> scale(n);
+    fold_bn(L.bn, n, bn_or_bias, semantics, scale.data(), bias.data());
+    wbuf.assign(gconv_layout(g) * dt_size(wdt), 0);
     for (int o = 0; o < n; ++o) {
         const int gi = wdt == DT_F32 ? 0 : (o / g.m) % g.t;          // (fp32 rows hold the group's own channels only)
         for (int ci = 0; ci < g.cg; ++ci) for (int tap = 0; tap < k * k; ++tap) {
             const float v = w_oihw[((size_t)o * g.cg + ci) * k * k + tap] * scale[o];
-            const size_t idx = (size_t)o * g.kp + (size_t)tap * g.kc + gi * g.cg + ci;
-            if (wdt == DT_F32) memcpy(&wbuf[idx * 4], &v, 4);
-            else { const uint16_t b = wdt == DT_F16 ? f2h(v) : f2bf(v); memcpy(&wbuf[idx * 2], &b, 2); }
+            put_elt(wbuf, (size_t)o * g.kp + (size_t)tap * g.kc + gi * g.cg + ci, v, wdt);
         }
     }
 }
@@ -202,19 +198,15 @@ static float xnor_alpha(const float *w, int n)
 void pack_xconv(const Layer &L, const float *bn_or_bias, const float *w_oihw, std::vector<uint8_t> &wbuf, std::vector<float> &scale, std::vector<float> &bias, int semantics)
 {
     const int n = L.filters, k = L.size, cin = L.cin, per = cin * k * k;
-    XConvArgs g; memset(&g, 0, sizeof g); g.C = cin; g.Cout = n; g.size = k; g.stride = L.stride;
-    const size_t total = xconv_layout(g);
+    XConvArgs g = xconv_geometry(k, L.stride, L.pad, 1, 1, cin, n, ACT_LINEAR);
     scale.assign(g.cout_pad, 0.f); bias.assign(g.cout_pad, 0.f);
-    wbuf.assign(total, 0);
+    wbuf.assign(xconv_layout(g), 0);
     const int ksteps = g.kpad / 64;
+    std::vector<float> sc(n);
+    fold_bn(L.bn, n, bn_or_bias, semantics, sc.data(), bias.data());
     for (int o = 0; o < n; ++o) {
         const float *w = w_oihw + (size_t)o * per;
-        const float mean = xnor_alpha(w, per);
-        if (L.bn) {
-            const float *beta = bn_or_bias, *gamma = beta + n, *mu = gamma + n, *var = mu + n;
-            const float sc = semantics == YOLO_SEM_DARKNET ? gamma[o] / (sqrtf(var[o]) + 1e-6f) : gamma[o] / sqrtf(var[o] + 1e-5f);
-            scale[o] = mean * sc; bias[o] = beta[o] - mu[o] * sc;
-        } else { scale[o] = mean; bias[o] = bn_or_bias[o]; }
+        scale[o] = xnor_alpha(w, per) * sc[o];
         for (int ci = 0; ci < cin; ++ci) for (int tap = 0; tap < k * k; ++tap)
             wbuf[xconv_pack_index(o, xconv_k(g, tap, ci), ksteps)] = w[(size_t)ci * k * k + tap] > 0.f ? 1 : 0xff;
     }
@@ -230,11 +222,9 @@ static const float *read_connected(const float *p, int inputs, int outputs, int 
     w.assign(wf, wf + (size_t)outputs * inputs); b.assign(bias, bias + outputs);
     if (!bn) return p;
     const float *gamma = p, *mean = p + outputs, *var = p + 2 * (size_t)outputs;
-    for (int o = 0; o < outputs; ++o) {
-        const float sc = semantics == YOLO_SEM_DARKNET ? gamma[o] / (sqrtf(var[o]) + 1e-6f) : gamma[o] / sqrtf(var[o] + 1e-5f);
-        for (int j = 0; j < inputs; ++j) w[(size_t)o * inputs + j] *= sc;
-        b[o] = bias[o] - mean[o] * sc;
-    }
+    std::vector<float> sc(outputs);
+    fold_bn(outputs, bias, gamma, mean, var, semantics, sc.data(), b.data());
+    for (int o = 0; o < outputs; ++o) for (int j = 0; j < inputs; ++j) w[(size_t)o * inputs + j] *= sc[o];
     return p + 3 * (size_t)outputs;
 }
 
@@ -257,11 +247,7 @@ static int pack_recurrent(yolo_ctx *c, Layer &L, const float *&p)
     for (int q = 0; q < g.launches; ++q) {
         const int K = g.Kx[q] + g.Kh[q], KS = K / 32;
         std::vector<uint8_t> wbuf((size_t)g.Mp[q] * K * es, 0); std::vector<float> bias((size_t)2 * g.Mp[q], 0.f);
-        auto put = [&](int row, int k, float v) {
-            const size_t idx = recur_pack_index(row, k, KS);
-            if (L.in_dt == DT_F32) memcpy(&wbuf[idx * 4], &v, 4);
-            else { const uint16_t h = L.in_dt == DT_F16 ? f2h(v) : f2bf(v); memcpy(&wbuf[idx * 2], &h, 2); }
-        };
+        auto put = [&](int row, int k, float v) { put_elt(wbuf, recur_pack_index(row, k, KS), v, L.in_dt); };
         const bool x_is_input = !(L.rkind == RECUR_RNN && q == 1);
         for (int u = 0; u < U; ++u) for (int t = 0; t < G[q]; ++t) {
             const int row = u * G[q] + t, a = sx[q][t], hpart = sh[q][t];
@@ -388,39 +374,20 @@ int yolo_set_weights(yolo_ctx *c, const float *flat, size_t n)
             std::vector<uint8_t> wb((size_t)loc * F * k * k * C * es);
             for (size_t lf = 0; lf < (size_t)loc * F; ++lf)
                 for (int ch = 0; ch < C; ++ch)
-                    for (int t = 0; t < k * k; ++t) {
-                        const float v = wfile[(lf * C + ch) * k * k + t];
-                        const size_t idx = (lf * k * k + t) * C + ch;
-                        if (L.in_dt == DT_F32) memcpy(&wb[idx * 4], &v, 4);
-                        else { uint16_t h = L.in_dt == DT_F16 ? f2h(v) : f2bf(v); memcpy(&wb[idx * 2], &h, 2); }
-                    }
+                    for (int t = 0; t < k * k; ++t) put_elt(wb, (lf * k * k + t) * C + ch, wfile[(lf * C + ch) * k * k + t], L.in_dt);
             HIPCK(c, hipMemcpy(L.d_w, wb.data(), wb.size(), hipMemcpyHostToDevice));
             HIPCK(c, hipMemcpy(L.d_b, b.data(), b.size() * 4, hipMemcpyHostToDevice));
             continue;
         }
-        if (L.type == L_DECONV) {          // the file: as a conv's, [bias | beta gamma mean var] then cin * filters * size^2 filters (DN/parser.c load_convolutional_weights)
-            const float *params = p; p += (size_t)L.filters * (L.bn ? 4 : 1);
-            const float *w = p; p += (size_t)L.cin * L.filters * L.size * L.size;
-            pack_deconv(L, params, w, L.in_dt, wbuf, bias, c->semantics);
-            HIPCK(c, hipMemcpy(L.d_w, wbuf.data(), wbuf.size(), hipMemcpyHostToDevice));
-            HIPCK(c, hipMemcpy(L.d_b, bias.data(), bias.size() * 4, hipMemcpyHostToDevice));
-            continue;
-        }
-        if (L.type == L_GCONV) {           // the file: [bias | beta gamma mean var] then filters * (cin / groups) * size^2 filters (DN/parser.c load_convolutional_weights: l.nweights)
+        if (is_side_conv(L)) {          // the file: as a conv's, [bias | beta gamma mean var] then the filters (DN/parser.c load_convolutional_weights: l.nweights, cin / groups channels per filter)
             const float *params = p; p += (size_t)L.filters * (L.bn ? 4 : 1);
             const float *w = p; p += (size_t)L.filters * (L.cin / L.groups) * L.size * L.size;
-            pack_gconv(L, params, w, L.in_dt, wbuf, bias, c->semantics);
+            if (L.type == L_DECONV) pack_deconv(L, params, w, L.in_dt, wbuf, bias, c->semantics);
+            else if (L.type == L_GCONV) pack_gconv(L, params, w, L.in_dt, wbuf, bias, c->semantics);
+            else pack_xconv(L, params, w, wbuf, osc, bias, c->semantics);
             HIPCK(c, hipMemcpy(L.d_w, wbuf.data(), wbuf.size(), hipMemcpyHostToDevice));
             HIPCK(c, hipMemcpy(L.d_b, bias.data(), bias.size() * 4, hipMemcpyHostToDevice));
-            continue;
-        }
-        if (L.type == L_XCONV) {           // the file: as a conv's
-            const float *params = p; p += (size_t)L.filters * (L.bn ? 4 : 1);
-            const float *w = p; p += (size_t)L.filters * L.cin * L.size * L.size;
-            pack_xconv(L, params, w, wbuf, osc, bias, c->semantics);
-            HIPCK(c, hipMemcpy(L.d_w, wbuf.data(), wbuf.size(), hipMemcpyHostToDevice));
-            HIPCK(c, hipMemcpy(L.d_b, bias.data(), bias.size() * 4, hipMemcpyHostToDevice));
-            HIPCK(c, hipMemcpy(L.d_sc, osc.data(), osc.size() * 4, hipMemcpyHostToDevice));
+            if (L.d_sc) HIPCK(c, hipMemcpy(L.d_sc, osc.data(), osc.size() * 4, hipMemcpyHostToDevice));
             continue;
         }
         if (L.type == L_RECUR) { if (int rc = pack_recurrent(c, L, p)) return rc; continue; }
@@ -549,7 +516,7 @@ int yolo_export(yolo_ctx *c, const char *path)
             }
             continue;
         }
-        if (L.type != L_CONV && L.type != L_LOCAL && L.type != L_DECONV && L.type != L_GCONV && L.type != L_XCONV) continue;
+        if (!has_packed_filters(L)) continue;
         uint64_t sz[3] = {(uint64_t)filter_bytes(L), (uint64_t)L.cout_pad, L.d_sc ? (uint64_t)L.cout_pad : 0};
         if (L.type == L_LOCAL) { sz[0] = (uint64_t)L.H * L.W * L.filters * L.size * L.size * L.cin * dt_size(L.in_dt); sz[1] = (uint64_t)L.H * L.W * L.filters; sz[2] = 0; }
         w.put(sz, sizeof sz);
@@ -616,7 +583,7 @@ yolo_ctx *yolo_create_from_file(const char *path, int max_batch, int device, voi
             }
             continue;
         }
-        if (L.type != L_CONV && L.type != L_LOCAL && L.type != L_DECONV && L.type != L_GCONV && L.type != L_XCONV) continue;
+        if (!has_packed_filters(L)) continue;
         uint64_t sz[3]; r.get(sz, sizeof sz);
         uint64_t want[3] = {(uint64_t)filter_bytes(L), (uint64_t)L.cout_pad, L.d_sc ? (uint64_t)L.cout_pad : 0};
         if (L.type == L_LOCAL) { want[0] = (uint64_t)L.H * L.W * L.filters * L.size * L.size * L.cin * dt_size(L.in_dt); want[1] = (uint64_t)L.H * L.W * L.filters; want[2] = 0; }

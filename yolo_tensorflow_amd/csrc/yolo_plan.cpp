@@ -113,18 +113,46 @@ static void conv_totals(yolo_ctx *c, const Layer &L, int cin_g, int h, int w)
     c->weights_count += (size_t)L.filters * (L.bn ? 4 : 1) + (size_t)L.filters * cin_g * L.size * L.size;
 }
 
-// grouped convolution (DN/parser.c:184, DN/convolutional_layer.c:458-471): a layer kind of its own with its own kernel (gconv.hip).  Like
-// [deconvolutional] it is never a member of a fused launch, neither end of a 1x1 tail, no host of a folded [shortcut] and nothing for
-// the tile tuner to choose -- every marking pass asks for L_CONV
+// ---- the side convs (is_side_conv): layer kinds of their own with their own kernels, never a member of a fused launch, neither end of a 1x1 tail,
+// no host of a folded [shortcut] and nothing for the tile tuner to choose -- every marking pass asks for L_CONV.  Size, stride and padding limits
+// are each kind's own; what they plan alike is here
+static std::string side_conv_name(const Layer &L)      // as the messages name the kind
+{
+    return L.type == L_DECONV ? "[deconvolutional]" : L.type == L_GCONV ? "[convolutional] with groups=" + std::to_string(L.groups) : "[convolutional] with xnor=1";
+}
+static int side_conv_dtype(yolo_ctx *c, int i, const Layer &L)
+{
+    if (c->dtype == YOLO_FP8) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: %s is not served in the fp8 configuration", i, side_conv_name(L).c_str());
+    if (c->split()) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: %s is not served in the split-fp16 configuration", i, side_conv_name(L).c_str());
+    return YOLO_OK;
+}
+// activation, operand and storage type, channels, the filter layout's kpad / cout_pad (cout_pad * kpad elements of filters; an xnor conv: bytes)
+static int side_conv_tail(Cursor &k, const Section &s, Layer &L)
+{
+    yolo_ctx *c = k.c;
+    if (int r = plan_activation(c, k.i, s, "logistic", false)) return r;
+    L.in_dt = c->act_dt(); L.store_dt = c->act_dt();
+    L.cin = k.C; L.cin_pad = roundup(k.C, 8);
+    side_layout(L, L.kpad, L.cout_pad);
+    return YOLO_OK;
+}
+// a grouped or xnor conv as the layer in front of head i (a [deconvolutional] there gets the head's own "must follow" message)
+static int side_conv_before_head(yolo_ctx *c, int i, const char *head, const char *why_grouped, const char *why_xnor)
+{
+    if (i == 0 || !is_side_conv(c->layers[i - 1]) || c->layers[i - 1].type == L_DECONV) return YOLO_OK;
+    const Layer &P = c->layers[i - 1];
+    return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: a %s directly in front of a [%s] head is not served (%s)", i - 1, side_conv_name(P).c_str(), head, P.type == L_XCONV ? why_xnor : why_grouped);
+}
+
+// grouped convolution (DN/parser.c:184, DN/convolutional_layer.c:458-471), gconv.hip
 static int parse_grouped_conv(Cursor &k, const Section &s, Layer &L)
 {
     yolo_ctx *c = k.c; const int i = k.i;
-    L.groups = opt_i(s, "groups", 1);
+    L.type = L_GCONV; L.groups = opt_i(s, "groups", 1);
     if (L.groups < 1) return fail(c, YOLO_ERR_INVALID, "layer %d: [convolutional] groups=%d", i, L.groups);
-    if (c->dtype == YOLO_FP8) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [convolutional] with groups=%d is not served in the fp8 configuration", i, L.groups);
-    if (c->split()) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [convolutional] with groups=%d is not served in the split-fp16 configuration", i, L.groups);
+    if (int r = side_conv_dtype(c, i, L)) return r;
     if (i == 0) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [convolutional] with groups=%d as the network's first layer is not served (the image is read by the dense kernels only)", i, L.groups);
-    L.type = L_GCONV; read_conv_keys(s, L);
+    read_conv_keys(s, L);
     if (L.filters < 1) return fail(c, YOLO_ERR_INVALID, "layer %d: conv filters %d", i, L.filters);
     if (k.C % L.groups) return fail(c, YOLO_ERR_INVALID, "layer %d: groups=%d does not divide the %d input channels", i, L.groups, k.C);
     if (L.filters % L.groups) return fail(c, YOLO_ERR_INVALID, "layer %d: groups=%d does not divide filters=%d", i, L.groups, L.filters);
@@ -132,35 +160,27 @@ static int parse_grouped_conv(Cursor &k, const Section &s, Layer &L)
     if (L.stride < 1 || L.stride > GCONV_MAX_STRIDE) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: grouped conv stride %d (1..%d are served)", i, L.stride, GCONV_MAX_STRIDE);
     if (L.pad < 0 || L.pad >= L.size) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: grouped conv padding %d must be below its size %d", i, L.pad, L.size);
     if (k.H + 2 * L.pad < L.size || k.W + 2 * L.pad < L.size) return fail(c, YOLO_ERR_INVALID, "layer %d: grouped conv larger than its padded input", i);
-    if (int r = plan_activation(c, i, s, "logistic", false)) return r;
-    L.in_dt = c->act_dt(); L.store_dt = c->act_dt();
-    L.cin = k.C; L.cin_pad = roundup(k.C, 8);
-    { GConvArgs g; memset(&g, 0, sizeof g); g.C = k.C; g.Cout = L.filters; g.groups = L.groups; g.size = L.size; g.in_dt = L.in_dt; gconv_layout(g); L.kpad = g.kp; L.cout_pad = g.nb * g.mb; }      // cout_pad * kpad elements of filters
+    if (int r = side_conv_tail(k, s, L)) return r;
     conv_out(k, L);
     conv_totals(c, L, L.cin / L.groups, k.H, k.W);      // DN/convolutional_layer.c:201, :325: c / groups
     return YOLO_OK;
 }
 
-// XNOR convolution (xnor=1, DN/parser.c:198, DN/convolutional_layer.c:451-456): a layer kind of its own with its own kernel (xconv.hip), the
-// sum of signs on the int8 MFMA.  Like the grouped conv it is never a member of a fused launch, neither end of a 1x1 tail, no host of a folded
-// [shortcut] and nothing for the tile tuner to choose -- every marking pass asks for L_CONV.  (binary=1 without xnor, and flipped=1, are read
-// by nobody: DESIGN.md 7)
+// XNOR convolution (xnor=1, DN/parser.c:198, DN/convolutional_layer.c:451-456), xconv.hip: the sum of signs on the int8 MFMA.  (binary=1 without
+// xnor, and flipped=1, are read by nobody: DESIGN.md 7)
 static int parse_xnor_conv(Cursor &k, const Section &s, Layer &L)
 {
     yolo_ctx *c = k.c; const int i = k.i;
+    L.type = L_XCONV;
     if (opt_i(s, "groups", 1) != 1) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [convolutional] with xnor=1 and groups=%d is not served (a grouped XNOR conv)", i, opt_i(s, "groups", 1));
-    if (c->dtype == YOLO_FP8) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [convolutional] with xnor=1 is not served in the fp8 configuration", i);
-    if (c->split()) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [convolutional] with xnor=1 is not served in the split-fp16 configuration", i);
+    if (int r = side_conv_dtype(c, i, L)) return r;
     if (i == 0) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [convolutional] with xnor=1 as the network's first layer is not served (the image is not negative anywhere, so its signs say nothing, and it is read by the dense kernels only)", i);
-    L.type = L_XCONV; read_conv_keys(s, L);
+    read_conv_keys(s, L);
     if (L.filters < 1) return fail(c, YOLO_ERR_INVALID, "layer %d: conv filters %d", i, L.filters);
     if (L.size < 1 || L.size > CONV_MAX_SIZE) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: xnor conv size %d (1..%d are served)", i, L.size, CONV_MAX_SIZE);
     if (L.stride < 1 || L.pad < 0) return fail(c, YOLO_ERR_INVALID, "layer %d: conv stride %d, padding %d", i, L.stride, L.pad);
     if (k.H + 2 * L.pad < L.size || k.W + 2 * L.pad < L.size) return fail(c, YOLO_ERR_INVALID, "layer %d: conv larger than its padded input (%d x %d with padding %d under a size %d conv)", i, k.W, k.H, L.pad, L.size);
-    if (int r = plan_activation(c, i, s, "logistic", false)) return r;
-    L.in_dt = c->act_dt(); L.store_dt = c->act_dt();
-    L.cin = k.C; L.cin_pad = roundup(k.C, 8);
-    { XConvArgs g; memset(&g, 0, sizeof g); g.C = k.C; g.Cout = L.filters; g.size = L.size; g.stride = L.stride; xconv_layout(g); L.kpad = g.kpad; L.cout_pad = g.cout_pad; }      // cout_pad * kpad bytes of filters
+    if (int r = side_conv_tail(k, s, L)) return r;
     conv_out(k, L);
     conv_totals(c, L, L.cin, k.H, k.W);
     return YOLO_OK;
@@ -210,24 +230,20 @@ static int parse_convolutional(Cursor &k, const Section &s, Layer &L)
     return YOLO_OK;
 }
 
-// transposed convolution (DN/deconvolutional_layer.c, DN/parser.c:151-174): its own kernel (deconv.hip), never a member of a fused
-// launch, neither end of a 1x1 tail, and a [shortcut] behind it is not folded into it -- every marking pass asks for L_CONV
+// transposed convolution (DN/deconvolutional_layer.c, DN/parser.c:151-174), deconv.hip
 static int parse_deconvolutional(Cursor &k, const Section &s, Layer &L)
 {
     yolo_ctx *c = k.c; const int i = k.i;
-    if (c->dtype == YOLO_FP8) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [deconvolutional] is not served in the fp8 configuration", i);
-    if (c->split()) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [deconvolutional] is not served in the split-fp16 configuration", i);
-    L.type = L_DECONV; read_conv_keys(s, L);
+    L.type = L_DECONV;
+    if (int r = side_conv_dtype(c, i, L)) return r;
+    read_conv_keys(s, L);
     if (L.size < 1 || L.size > DECONV_MAX_SIZE) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: deconv size %d (1..%d are served)", i, L.size, DECONV_MAX_SIZE);
     if (L.stride < 1 || L.stride > DECONV_MAX_STRIDE) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: deconv stride %d (1..%d are served)", i, L.stride, DECONV_MAX_STRIDE);
     if (L.pad < 0 || L.pad >= L.size) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: deconv padding %d must be below its size %d", i, L.pad, L.size);
     if (L.filters < 1) return fail(c, YOLO_ERR_INVALID, "layer %d: deconv filters %d", i, L.filters);
     const int ho = (k.H - 1) * L.stride + L.size - 2 * L.pad, wo = (k.W - 1) * L.stride + L.size - 2 * L.pad;
     if (ho < 1 || wo < 1) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: deconv output %d x %d is not positive", i, wo, ho);
-    if (int r = plan_activation(c, i, s, "logistic", false)) return r;
-    L.in_dt = c->act_dt(); L.store_dt = c->act_dt();
-    L.cin = k.C; L.cin_pad = roundup(k.C, 8); L.cout_pad = roundup(L.filters, DECONV_CO_TILE);
-    { DeconvArgs g; memset(&g, 0, sizeof g); g.size = L.size; g.stride = L.stride; g.Cin_pad = L.cin_pad; g.cout_pad = L.cout_pad; L.kpad = (int)(deconv_layout(g) / L.cout_pad); }      // (the K of all phases together: cout_pad * kpad elements of filters)
+    if (int r = side_conv_tail(k, s, L)) return r;
     conv_totals(c, L, L.cin, k.H, k.W);      // (over the INPUT grid: every input pixel meets every tap)
     k.H = ho; k.W = wo; k.C = L.filters;
     return YOLO_OK;
@@ -335,8 +351,7 @@ static int parse_detection(Cursor &k, const Section &s, Layer &L)
     yolo_ctx *c = k.c; const int i = k.i;
     L.type = L_DETECT; L.classes = opt_i(s, "classes", 1); L.na = opt_i(s, "num", 1); L.side = opt_i(s, "side", 7); L.sqr = opt_i(s, "sqrt", 0);
     if (opt_i(s, "coords", 4) != 4 || opt_i(s, "softmax", 0)) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [detection] with coords != 4 or softmax", i);
-    if (i > 0 && c->layers[i - 1].type == L_GCONV) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: a [convolutional] with groups=%d directly in front of a [detection] head is not served ([detection] must follow a [connected] layer)", i - 1, c->layers[i - 1].groups);
-    if (i > 0 && c->layers[i - 1].type == L_XCONV) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: a [convolutional] with xnor=1 directly in front of a [detection] head is not served ([detection] must follow a [connected] layer)", i - 1);
+    if (int r = side_conv_before_head(c, i, "detection", "[detection] must follow a [connected] layer", "[detection] must follow a [connected] layer")) return r;
     if (i == 0 || !c->layers[i - 1].fc) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: [detection] must follow a [connected] layer", i);
     if (k.C != L.side * L.side * (L.classes + L.na * 5)) return fail(c, YOLO_ERR_INVALID, "layer %d: [detection] expects %d inputs, got %d", i, L.side * L.side * (L.classes + L.na * 5), k.C);
     if (c->attrs && c->attrs != 5 + L.classes) return fail(c, YOLO_ERR_UNSUPPORTED, "heads with different class counts");
@@ -478,8 +493,8 @@ static int parse_head(Cursor &k, const Section &s, Layer &L)
     else L.anchors.assign(an.begin(), an.begin() + 2 * total);
     L.na = (int)L.anchors.size() / 2;
     if (L.na > 16) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: more than 16 anchors", i);
-    if (i > 0 && c->layers[i - 1].type == L_GCONV) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: a [convolutional] with groups=%d directly in front of a [%s] head is not served (the head's objectness plane and lean decode belong to the dense kernels; put a dense 1x1 conv in between)", i - 1, c->layers[i - 1].groups, s.type.c_str());
-    if (i > 0 && c->layers[i - 1].type == L_XCONV) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: a [convolutional] with xnor=1 directly in front of a [%s] head is not served (the head's fp32 store, objectness plane and lean decode belong to the dense kernels; put a dense 1x1 conv in between)", i - 1, s.type.c_str());
+    if (int r = side_conv_before_head(c, i, s.type.c_str(), "the head's objectness plane and lean decode belong to the dense kernels; put a dense 1x1 conv in between",
+                                      "the head's fp32 store, objectness plane and lean decode belong to the dense kernels; put a dense 1x1 conv in between")) return r;
     if (i == 0 || c->layers[i - 1].type != L_CONV) return fail(c, YOLO_ERR_UNSUPPORTED, "layer %d: head must follow a conv", i);
     if (k.C != L.na * (5 + L.classes)) return fail(c, YOLO_ERR_INVALID, "layer %d: head expects %d channels, conv gives %d", i, L.na * (5 + L.classes), k.C);
     if (c->attrs && c->attrs != 5 + L.classes) return fail(c, YOLO_ERR_UNSUPPORTED, "heads with different class counts");
@@ -526,7 +541,7 @@ static int parse_softmax(Cursor &k, const Section &s, Layer &L)
     // the logits are never rounded to 16 bits: the conv that reaches this layer directly, or through one [avgpool], writes fp32
     int p = i - 1;
     if (p >= 0 && c->layers[p].type == L_AVGPOOL) p = c->layers[p].in[0];
-    if (p >= 0 && (c->layers[p].type == L_CONV || c->layers[p].type == L_GCONV || c->layers[p].type == L_XCONV || c->layers[p].type == L_RECUR)) c->layers[p].head = true;      // (not L_DECONV)
+    if (p >= 0 && (c->layers[p].type == L_CONV || (is_side_conv(c->layers[p]) && c->layers[p].type != L_DECONV) || c->layers[p].type == L_RECUR)) c->layers[p].head = true;      // (not L_DECONV)
     return YOLO_OK;
 }
 
@@ -1123,7 +1138,7 @@ int allocate(yolo_ctx *c)
     HIPCK(c, hipMalloc((void **)&c->d_sbox, nr * 16)); HIPCK(c, hipMalloc((void **)&c->d_slabel, nr * 4)); HIPCK(c, hipMalloc((void **)&c->d_sscore, nr * 4));
     HIPCK(c, hipMalloc((void **)&c->d_counts, (size_t)c->max_batch * 4));
     // filters
-    for (auto &L : c->layers) if (L.type == L_CONV || L.type == L_DECONV || L.type == L_GCONV || L.type == L_XCONV) {
+    for (auto &L : c->layers) if (L.type == L_CONV || is_side_conv(L)) {
         size_t wb = filter_bytes(L);
         HIPCK(c, hipMalloc(&L.d_w, wb)); HIPCK(c, hipMemsetAsync(L.d_w, 0, wb, c->stream));
         HIPCK(c, hipMalloc((void **)&L.d_b, (size_t)L.cout_pad * 4)); HIPCK(c, hipMemsetAsync(L.d_b, 0, (size_t)L.cout_pad * 4, c->stream));

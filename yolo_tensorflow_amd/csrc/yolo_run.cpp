@@ -64,12 +64,19 @@ static TView nview(int n, TView v) { v.n = n; return v; }      // a tensor's vie
 // channels a layer that computes `ch` of them stores: zeros in the channels past them, up to the granule of the output's type (a window of a concat buffer holds whole granules)
 static int store_width(const Layer &L, int ch) { return std::min(L.out.stride, roundup(ch, L.out.dt == DT_F32 && L.head ? 4 : 8)); }
 
+// the fields of a side conv's arguments its geometry leaves open: tensors, parameters, batch, the stored width
+static void side_bind(SideConvArgs &a, const yolo_ctx *c, const Layer &L, int n)
+{
+    const TView in = view_of(c, L.in[0]);
+    a.in = in.ptr; a.in_stride = in.stride; a.wt = L.d_w; a.bias = L.d_b; a.out = L.out.ptr; a.out_stride = L.out.stride; a.out_dt = L.out.dt; a.N = n;
+    a.Cstore = store_width(L, L.filters);
+}
+
 static DeconvArgs deconv_args(const yolo_ctx *c, const Layer &L, int n)
 {
     const TView in = view_of(c, L.in[0]);
     DeconvArgs a = deconv_geometry(L.size, L.stride, L.pad, in.h, in.w, L.cin_pad, L.filters, L.act, L.in_dt);
-    a.in = in.ptr; a.in_stride = in.stride; a.wt = L.d_w; a.bias = L.d_b; a.out = L.out.ptr; a.out_stride = L.out.stride; a.out_dt = L.out.dt; a.N = n;
-    a.Cstore = store_width(L, L.filters);
+    side_bind(a, c, L, n);
     return a;
 }
 
@@ -86,8 +93,7 @@ static GConvArgs gconv_args(const yolo_ctx *c, const Layer &L, int n)
 {
     const TView in = view_of(c, L.in[0]);
     GConvArgs a = gconv_geometry(L.size, L.stride, L.pad, in.h, in.w, L.cin, L.filters, L.groups, L.act, L.in_dt);
-    a.in = in.ptr; a.in_stride = in.stride; a.wt = L.d_w; a.bias = L.d_b; a.out = L.out.ptr; a.out_stride = L.out.stride; a.out_dt = L.out.dt; a.N = n;
-    a.Cstore = store_width(L, L.filters);
+    side_bind(a, c, L, n);
     return a;
 }
 
@@ -105,10 +111,31 @@ static XConvArgs xconv_args(const yolo_ctx *c, const Layer &L, int n)
 {
     const TView in = view_of(c, L.in[0]);
     XConvArgs a = xconv_geometry(L.size, L.stride, L.pad, in.h, in.w, L.cin, L.filters, L.act);
-    a.in = in.ptr; a.in_stride = in.stride; a.in_dt = in.dt; a.wt = (const int8_t *)L.d_w; a.scale = L.d_sc; a.bias = L.d_b;
-    a.out = L.out.ptr; a.out_stride = L.out.stride; a.out_dt = L.out.dt; a.N = n;
-    a.Cstore = store_width(L, L.filters);
+    side_bind(a, c, L, n);
+    a.in_dt = in.dt; a.scale = L.d_sc;
     return a;
+}
+
+static hipError_t launch_side_conv(const yolo_ctx *c, const Layer &L, int n, hipStream_t s)
+{
+    if (L.type == L_DECONV) return launch_deconv(deconv_args(c, L, n), s);
+    if (L.type == L_GCONV) return launch_gconv(gconv_args(c, L, n), s);
+    return launch_xconv(xconv_args(c, L, n), s);
+}
+
+void side_layout(const Layer &L, int &kpad, int &cout_pad)
+{
+    if (L.type == L_DECONV) {          // (the K of all phases together)
+        const DeconvArgs g = deconv_geometry(L.size, L.stride, L.pad, 1, 1, L.cin_pad, L.filters, ACT_LINEAR, L.in_dt);
+        cout_pad = g.cout_pad; kpad = 0;
+        for (int p = 0; p < L.stride * L.stride; ++p) kpad += g.kp[p];
+    } else if (L.type == L_GCONV) {
+        const GConvArgs g = gconv_geometry(L.size, L.stride, L.pad, 1, 1, L.cin, L.filters, L.groups, ACT_LINEAR, L.in_dt);
+        kpad = g.kp; cout_pad = g.nb * g.mb;
+    } else {
+        const XConvArgs g = xconv_geometry(L.size, L.stride, L.pad, 1, 1, L.cin, L.filters, ACT_LINEAR);
+        kpad = g.kpad; cout_pad = g.cout_pad;          // (bytes: int8 filters)
+    }
 }
 
 // split fp16: a layer that moves or interpolates values runs in fp32 between a join (hi + lo) and a split
@@ -418,16 +445,8 @@ int run_layer(yolo_ctx *c, int i, int n)
         HIPCK(c, launch_local(nview(n, view_of(c, L.in[0])), nview(n, L.out), L.d_w, L.d_b, L.size, L.stride, L.pad, L.act, s));
         if (L.post_act != ACT_LINEAR) HIPCK(c, launch_activate(nview(n, L.out), false, L.post_act, s));
         break;
-    case L_DECONV:
-        HIPCK(c, launch_deconv(deconv_args(c, L, n), s));
-        if (L.post_act != ACT_LINEAR) HIPCK(c, launch_activate(nview(n, L.out), false, L.post_act, s));
-        break;
-    case L_GCONV:
-        HIPCK(c, launch_gconv(gconv_args(c, L, n), s));
-        if (L.post_act != ACT_LINEAR) HIPCK(c, launch_activate(nview(n, L.out), false, L.post_act, s));
-        break;
-    case L_XCONV:
-        HIPCK(c, launch_xconv(xconv_args(c, L, n), s));
+    case L_DECONV: case L_GCONV: case L_XCONV:
+        HIPCK(c, launch_side_conv(c, L, n, s));
         if (L.post_act != ACT_LINEAR) HIPCK(c, launch_activate(nview(n, L.out), false, L.post_act, s));
         break;
     case L_ACTIVATE: {
@@ -539,12 +558,12 @@ int stage_in(yolo_ctx *c, const void *images, int n, int fmt, int loc, float sca
     return YOLO_OK;
 }
 
-// the layer sequence of one forward.  `skip_conv`: the timing pass that runs everything but the convs (dense, grouped and xnor: conv_flops counts them all); `ev`: per-layer events (yolo_time_layers)
+// the layer sequence of one forward.  `skip_conv`: the timing pass that runs everything but the convs (dense, grouped and xnor, not [deconvolutional]; conv_flops counts them all); `ev`: per-layer events (yolo_time_layers)
 static int run_layers(yolo_ctx *c, int n, bool skip_conv = false, std::vector<hipEvent_t> *ev = nullptr)
 {
     const int NL = (int)c->layers.size();
     for (int i = 0; i < NL; ++i) {
-        if (!(skip_conv && (c->layers[i].type == L_CONV || c->layers[i].type == L_GCONV || c->layers[i].type == L_XCONV))) { int r = run_layer(c, i, n); if (r) return r; }
+        if (!(skip_conv && (c->layers[i].type == L_CONV || (is_side_conv(c->layers[i]) && c->layers[i].type != L_DECONV)))) { int r = run_layer(c, i, n); if (r) return r; }
         if (ev) HIPCK(c, hipEventRecord((*ev)[i + 1], c->stream));
     }
     return YOLO_OK;

@@ -1002,6 +1002,17 @@ def op_shortcut(x, frm, activation="linear", dtype=FP32, device=0):
     return out
 
 
+def _op_side_conv(entry, x, filters, bias, cout, geometry, out_hw, activation, dtype, out_f32, device):
+    """The call behind op_deconv2d / op_conv2d_grouped / op_conv2d_xnor: C entry point `entry` over x [n, h, w, cin] and checked float32 filters of `cout`
+    filters [., ., size, size]; `geometry`: the integers between `size` and the activation; out_hw: the output's height and width."""
+    n, h, w, cin = x.shape
+    b = _f32(bias) if bias is not None else None
+    out = np.empty((n, max(out_hw[0], 0), max(out_hw[1], 0), cout), dtype=np.float32)
+    _op_check(getattr(load_library(), entry)(x.ctypes.data, n, h, w, cin, filters.ctypes.data, b.ctypes.data if b is not None else None, filters.shape[2], *geometry,
+                                             activation_code(activation), dtype, 1 if out_f32 else 0, out.ctypes.data, device), entry)
+    return out
+
+
 def op_deconv2d(x, w_iohw, bias=None, stride=1, padding=0, activation="linear", dtype=BF16, out_f32=False, device=0):
     """darknet's [deconvolutional] (yolo_op_deconv2d): x [n, h, w, cin], w_iohw [cin, cout, size, size] (the weight file's order) ->
     [n, (h - 1) stride + size - 2 padding, ..., cout] float32.  out_f32: the fp32 store of a 16-bit kernel."""
@@ -1010,12 +1021,8 @@ def op_deconv2d(x, w_iohw, bias=None, stride=1, padding=0, activation="linear", 
     if w_iohw.ndim != 4 or w_iohw.shape[0] != cin or w_iohw.shape[2] != w_iohw.shape[3]:
         raise YoloError("op_deconv2d: filters must be [cin, cout, size, size]")
     cout, size = w_iohw.shape[1], w_iohw.shape[2]
-    b = _f32(bias) if bias is not None else None
-    ho, wo = (h - 1) * stride + size - 2 * padding, (w - 1) * stride + size - 2 * padding
-    out = np.empty((n, max(ho, 0), max(wo, 0), cout), dtype=np.float32)
-    _op_check(load_library().yolo_op_deconv2d(x.ctypes.data, n, h, w, cin, w_iohw.ctypes.data, b.ctypes.data if b is not None else None, size, stride, padding,
-                                              cout, activation_code(activation), dtype, 1 if out_f32 else 0, out.ctypes.data, device), "yolo_op_deconv2d")
-    return out
+    return _op_side_conv("yolo_op_deconv2d", x, w_iohw, bias, cout, (stride, padding, cout), [(d - 1) * stride + size - 2 * padding for d in (h, w)],
+                         activation, dtype, out_f32, device)
 
 
 def op_conv2d_grouped(x, w_oihw, bias=None, groups=1, stride=1, padding=0, activation="linear", dtype=BF16, out_f32=False, device=0):
@@ -1026,12 +1033,8 @@ def op_conv2d_grouped(x, w_oihw, bias=None, groups=1, stride=1, padding=0, activ
     if w_oihw.ndim != 4 or groups < 1 or cin % groups or w_oihw.shape[1] != cin // groups or w_oihw.shape[2] != w_oihw.shape[3]:
         raise YoloError("op_conv2d_grouped: filters must be [cout, cin / groups, size, size]")
     cout, size = w_oihw.shape[0], w_oihw.shape[2]
-    b = _f32(bias) if bias is not None else None
-    ho, wo = (h + 2 * padding - size) // stride + 1, (w + 2 * padding - size) // stride + 1
-    out = np.empty((n, max(ho, 0), max(wo, 0), cout), dtype=np.float32)
-    _op_check(load_library().yolo_op_conv2d_grouped(x.ctypes.data, n, h, w, cin, w_oihw.ctypes.data, b.ctypes.data if b is not None else None, size, stride, padding,
-                                                    cout, groups, activation_code(activation), dtype, 1 if out_f32 else 0, out.ctypes.data, device), "yolo_op_conv2d_grouped")
-    return out
+    return _op_side_conv("yolo_op_conv2d_grouped", x, w_oihw, bias, cout, (stride, padding, cout, groups), [(d + 2 * padding - size) // stride + 1 for d in (h, w)],
+                         activation, dtype, out_f32, device)
 
 
 def op_conv2d_xnor(x, w_oihw, bias=None, stride=1, padding=0, activation="linear", dtype=BF16, out_f32=False, device=0):
@@ -1043,12 +1046,8 @@ def op_conv2d_xnor(x, w_oihw, bias=None, stride=1, padding=0, activation="linear
     if w_oihw.ndim != 4 or w_oihw.shape[1] != cin or w_oihw.shape[2] != w_oihw.shape[3]:
         raise YoloError("op_conv2d_xnor: filters must be [cout, cin, size, size]")
     cout, size = w_oihw.shape[0], w_oihw.shape[2]
-    b = _f32(bias) if bias is not None else None
-    ho, wo = (h + 2 * padding - size) // stride + 1, (w + 2 * padding - size) // stride + 1
-    out = np.empty((n, max(ho, 0), max(wo, 0), cout), dtype=np.float32)
-    _op_check(load_library().yolo_op_conv2d_xnor(x.ctypes.data, n, h, w, cin, w_oihw.ctypes.data, b.ctypes.data if b is not None else None, size, stride, padding,
-                                                 cout, activation_code(activation), dtype, 1 if out_f32 else 0, out.ctypes.data, device), "yolo_op_conv2d_xnor")
-    return out
+    return _op_side_conv("yolo_op_conv2d_xnor", x, w_oihw, bias, cout, (stride, padding, cout), [(d + 2 * padding - size) // stride + 1 for d in (h, w)],
+                         activation, dtype, out_f32, device)
 
 
 def op_l2norm(x, dtype=FP32, device=0):
