@@ -266,6 +266,67 @@ int yolo_detect_tiled_u8(yolo_ctx *ctx, const uint8_t *pixels, size_t bytes, con
                          float score_thr, float iou_thr, int max_out, int nms_mode, int select_mode, int relative,
                          yolo_box *boxes_out, int32_t *counts_out, int out_loc);
 
+/* ---- decoded video frames: NV12, I420 and pitched RGB / BGR surfaces (no counterpart in the reference) ----
+ * A frame is h x w pixels (odd sizes are served) as a video decoder or a capture leaves them, described in place:
+ *   YOLO_PIX_NV12   plane 0: Y, h rows of w bytes; plane 1: interleaved U,V, ceil(h/2) rows of 2 * ceil(w/2) bytes
+ *   YOLO_PIX_I420   plane 0: Y; planes 1 and 2: U and V, each ceil(h/2) rows of ceil(w/2) bytes
+ *   YOLO_PIX_RGB24 / YOLO_PIX_BGR24   plane 0: h rows of 3 * w bytes
+ * Every plane has its own byte offset into the packed buffer and its own row pitch (at least the row's bytes; any larger value is
+ * allowed); the planes a format does not have are not read.  Pixel (y, x) takes its chroma sample from (y >> 1, x >> 1): nearest, no
+ * chroma interpolation.  The RGB bytes of a YUV pixel are, with m the frame's matrix, in int32 with an arithmetic `>>`:
+ *   y' = max(0, Y - yoff[m]) * CY[m];   u = U - 128;   v = V - 128
+ *   R = clamp8((y' + CVR[m] * v                 + 2^19) >> 20)
+ *   G = clamp8((y' - CUG[m] * u - CVG[m] * v    + 2^19) >> 20)
+ *   B = clamp8((y' + CUB[m] * u                 + 2^19) >> 20)
+ *   matrix                               yoff  CY       CVR      CUG     CVG     CUB       round(k * 2^20) of
+ *   YOLO_MATRIX_BT601 (limited range)    16    1220542  1673527  409993  852492  2116026   1.164, 1.596, 0.391, 0.813, 2.018
+ *   YOLO_MATRIX_BT709 (limited range)    16    1220542  1880097  223347  558891  2214593   1.164, 1.793, 0.213, 0.533, 2.112
+ *   YOLO_MATRIX_BT601_FULL (JFIF)        0     1048576  1470104  360853  748826  1858077   1, 1.402, 0.344136, 0.714136, 1.772
+ * (every intermediate lies in -282 943 616 .. +573 487 137).  The BT.601 limited row is believed to be what OpenCV's COLOR_YUV2RGB_NV12
+ * evaluates; cv2 is absent where this was written: that equality is unpinned, the rule above is what is promised.  RGB24 bytes are the
+ * image's own, BGR24 swaps channels 0 and 2; the matrix of such a frame must still be a valid one.
+ * From there on a frame IS the h x w x 3 byte image this rule yields: every fit reads it exactly as it reads a packed RGB image
+ * (yolo_fit_unit_value, the /255, darknet's two-pass resize_image, the cv2 rule, [net] yolo_input_mul / yolo_input_add), host and device
+ * evaluate the rule identically, and no RGB copy of the frame is ever stored.  64 bytes. */
+enum yolo_pix_format { YOLO_PIX_NV12 = 0, YOLO_PIX_I420 = 1, YOLO_PIX_RGB24 = 2, YOLO_PIX_BGR24 = 3 };
+enum yolo_color_matrix { YOLO_MATRIX_BT601 = 0, YOLO_MATRIX_BT709 = 1, YOLO_MATRIX_BT601_FULL = 2 };
+typedef struct yolo_frame_desc {
+    uint64_t offset[3];        /* where each plane begins in the packed buffer */
+    uint64_t pitch[3];         /* bytes from one row of the plane to the next */
+    int32_t h, w;
+    int32_t format;            /* enum yolo_pix_format */
+    int32_t matrix;            /* enum yolo_color_matrix */
+} yolo_frame_desc;
+/* The rule on the host: the frame `desc` describes inside pixels[bytes] -> rgb_out [h][w][3] uint8.  The counterpart of
+ * yolo_fit_unit_value: no context, no device.  YOLO_ERR_INVALID (text in yolo_last_error(NULL)): a NULL pointer, and what every
+ * yolo_*_frames_* entry point refuses for a descriptor: an unknown format or matrix, h or w below 1, a pitch below the plane's row
+ * bytes, a pitch or a plane that passes 32 bits, a plane that ends past `bytes`. */
+int yolo_frame_to_rgb_host(const yolo_frame_desc *desc, const uint8_t *pixels, size_t bytes, uint8_t *rgb_out);
+/* The same on the device, by one kernel of its own (host buffers, in the style of the other yolo_op_*): pins the rule there. */
+int yolo_op_frame_to_rgb(const yolo_frame_desc *desc, const uint8_t *pixels, size_t bytes, uint8_t *rgb_out, int device);
+/* yolo_forward_images_u8, yolo_detect_images_u8, yolo_detect_images_graph and yolo_detect_tiled_u8 over frames, argument for argument:
+ * yolo_frame_desc in the place of yolo_image_desc, everything else as documented there -- the fit launch converts while it fits, one
+ * batch may mix formats and matrices, boxes come back in the frame's own pixels (YOLO_UNITS_SOURCE_PIXELS / the tiled form), frame
+ * averaging and recurrent state advance as for images.  The graph form keeps a captured step of its own: a caller that alternates
+ * yolo_detect_images_graph and yolo_detect_frames_graph recaptures neither; the frame table is copied on the context stream before
+ * every replay.  A tiled window indexes chroma by the pixel's position in the FRAME: a window may start on an odd row or column.
+ * Every refusal comes before any launch and names the frame.  YOLO_ERR_INVALID: a descriptor as yolo_frame_to_rgb_host refuses it, and
+ * everything the image form refuses with that code.  YOLO_ERR_UNSUPPORTED: a network of other than 3 channels ([net]
+ * yolo_input=planes); YOLO_FIT_CV2_BGR (the frame's format states its channel order); whatever the image form of the same entry point
+ * refuses (the centre crop where boxes are mapped back, tiling's list). */
+int yolo_forward_frames_u8(yolo_ctx *ctx, const uint8_t *pixels, size_t bytes, const yolo_frame_desc *descs, int n, int fit, int loc,
+                           float *detections_out, int out_loc);
+int yolo_detect_frames_u8(yolo_ctx *ctx, const uint8_t *pixels, size_t bytes, const yolo_frame_desc *descs, int n, int fit, int loc,
+                          float score_thr, float iou_thr, int max_out, int nms_mode, int select_mode, int units,
+                          yolo_box *boxes_out, int32_t *counts_out, int out_loc);
+int yolo_detect_frames_graph(yolo_ctx *ctx, const uint8_t *pixels, size_t bytes, const yolo_frame_desc *descs, int n, int fit,
+                             float score_thr, float iou_thr, int max_out, int nms_mode, int select_mode, int units,
+                             yolo_box *boxes_out, int32_t *counts_out);
+int yolo_detect_tiled_frames_u8(yolo_ctx *ctx, const uint8_t *pixels, size_t bytes, const yolo_frame_desc *descs, int n_images,
+                                int tile_h, int tile_w, int overlap_h, int overlap_w, int fit, int loc,
+                                float score_thr, float iou_thr, int max_out, int nms_mode, int select_mode, int relative,
+                                yolo_box *boxes_out, int32_t *counts_out, int out_loc);
+
 /* darknet's get_network_boxes on the device (DN/network.c:536-567 = num_detections + fill_network_boxes ->
  * get_yolo_detections DN/yolo_layer.c:316-343 / get_region_detections DN/region_layer.c:364-437 (softmax heads, no tree),
  * then correct_yolo_boxes DN/yolo_layer.c:247-273) over image 0 of the last forward: boxes above `thresh`, compacted in

@@ -872,6 +872,113 @@ hipError_t launch_fit_views(const uint8_t *pixels, size_t bytes, const ViewDesc 
     return hipGetLastError();
 }
 
+// ---- decoded video frames (yolo_*_frames_*; kernels.h FrameDesc): the source reader of a frame.  at(y, x, c) is byte c of the h x w x 3 image the colour rule
+//      yields at pixel (y0 + y, x0 + x) of the frame -- (y0, x0): where a window begins, 0 for a whole frame; chroma is indexed in the FRAME -- as AtPacked returns it
+//      for a packed RGB image, so every px_* fit above runs over it unchanged.  The conversion is integer-exact: how often a tap's three channels evaluate it cannot
+//      change a bit, and the compiler folds the three evaluations of one tap into one (the loads are the same addresses; NOTEBOOK 2026-10-21).  Format and matrix
+//      are the frame's: uniform over a workgroup (blockIdx.y is the frame), so one batch may mix them.
+struct AtFrame {
+    __amdgpu_buffer_rsrc_t rsrc; FrameDesc f; ColorMatrix m; int y0, x0, fit;
+    __device__ __forceinline__ unsigned byte_at(unsigned off) const { return (unsigned)__builtin_amdgcn_raw_buffer_load_b8(rsrc, off, 0, 0); }
+    __device__ __forceinline__ void rgb(int y, int x, int *v) const
+    {
+        unsigned o[3];
+        frame_sample_offsets(f, y0 + y, x0 + x, o);
+        const int a = (int)byte_at(o[0]), b = (int)byte_at(o[1]), c = (int)byte_at(o[2]);
+        if (f.format >= PIX_RGB24) { v[0] = a; v[1] = b; v[2] = c; }
+        else yuv_to_rgb(m, a, b, c, v);
+    }
+    __device__ __forceinline__ float operator()(int y, int x, int c) const
+    {
+        int v[3];
+        rgb(y, x, v);
+        const unsigned b = (unsigned)(c == 0 ? v[0] : c == 1 ? v[1] : v[2]);
+        return fit == FIT_LETTERBOX || fit == FIT_CENTER_CROP ? fit_unit_value(FIT_LETTERBOX, b) : (float)b;
+    }
+};
+
+// k_fit_images over frames.  WIN: slot i is window wins[i] of frame wins[i].image, else frame i itself
+template <typename T, int FIT, bool WIN>
+__global__ __launch_bounds__(256) void k_fit_frames(const uint8_t *pixels, unsigned bytes, const FrameDesc *frames, const WinDesc *wins, int net_h, int net_w, T *out,
+                                                    int out_stride, float post_mul, float post_add)
+{
+    const int img = blockIdx.y;
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= net_h * net_w) return;
+    int h = 0, w = 0, y0 = 0, x0 = 0, fi = img;
+    if (WIN) { const WinDesc d = wins[img]; h = d.h; w = d.w; y0 = d.y0; x0 = d.x0; fi = d.image; }
+    const FrameDesc f = frames[fi];
+    if (!WIN) { h = f.h; w = f.w; }
+    const int oy = p / net_w, ox = p - oy * net_w;
+    const AtFrame at{__builtin_amdgcn_make_buffer_rsrc((void *)pixels, 0, bytes, 0x00020000), f, color_matrix(f.matrix), y0, x0, FIT};
+    float v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (FIT == FIT_STRETCH) px_stretch<3>(at, h, w, net_h, net_w, oy, ox, post_mul, post_add, 0, 3, v);
+    else {
+        if (FIT == FIT_LETTERBOX) {
+            int new_w, new_h;
+            letterbox_dims(net_w, net_h, w, h, &new_w, &new_h);
+            px_letterbox<3>(at, w, h, new_w, new_h, (net_w - new_w) / 2, (net_h - new_h) / 2, oy, ox, 0, 3, v);
+        } else if (FIT == FIT_CENTER_CROP) px_center_crop<3>(at, w, h, net_w, net_h, oy, ox, 0, 3, v);
+        else px_cv2(at, h, w, net_h, net_w, oy, ox, 0, 225.0f, v);
+        // [net] yolo_input_mul / yolo_input_add, as k_fit_images applies them
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            if (post_mul != 1.0f) v[c] *= post_mul;
+            if (post_add != 0.0f) v[c] += post_add;
+        }
+    }
+    Elt<T>::store8(out + ((size_t)img * net_h * net_w + p) * out_stride, v);
+}
+
+static hipError_t fit_frames(const uint8_t *pixels, size_t bytes, const FrameDesc *d_frames, const WinDesc *d_wins, int n, int fit, int net_h, int net_w, void *out,
+                             int out_dt, int out_stride, float post_mul, float post_add, hipStream_t s)
+{
+    if (n < 1 || net_h < 1 || net_w < 1 || (size_t)net_h * net_w > 0x7fffffffull || bytes > 0xffffffffull || out_stride < 8) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((net_h * net_w + 255) / 256), (unsigned)n);
+#define FRAMES_LAUNCH(F, WIN) WITH_DT(out_dt, hipLaunchKernelGGL((k_fit_frames<T, F, WIN>), grid, dim3(256), 0, s, pixels, (unsigned)bytes, d_frames, d_wins, net_h, net_w, (T *)out, out_stride, post_mul, post_add))
+    if (d_wins) {
+        if (fit == FIT_STRETCH) FRAMES_LAUNCH(FIT_STRETCH, true);
+        else if (fit == FIT_LETTERBOX) FRAMES_LAUNCH(FIT_LETTERBOX, true);
+        else return hipErrorInvalidValue;
+    } else if (fit == FIT_STRETCH) FRAMES_LAUNCH(FIT_STRETCH, false);
+    else if (fit == FIT_LETTERBOX) FRAMES_LAUNCH(FIT_LETTERBOX, false);
+    else if (fit == FIT_CV2) FRAMES_LAUNCH(FIT_CV2, false);
+    else if (fit == FIT_CENTER_CROP) FRAMES_LAUNCH(FIT_CENTER_CROP, false);
+    else return hipErrorInvalidValue;
+#undef FRAMES_LAUNCH
+    return hipGetLastError();
+}
+hipError_t launch_fit_frames(const uint8_t *pixels, size_t bytes, const FrameDesc *d_frames, int n, int fit, int net_h, int net_w, void *out, int out_dt,
+                             int out_stride, float post_mul, float post_add, hipStream_t s)
+{
+    return fit_frames(pixels, bytes, d_frames, nullptr, n, fit, net_h, net_w, out, out_dt, out_stride, post_mul, post_add, s);
+}
+hipError_t launch_fit_frame_windows(const uint8_t *pixels, size_t bytes, const FrameDesc *d_frames, const WinDesc *d_wins, int n, int fit, int net_h, int net_w,
+                                    void *out, int out_dt, int out_stride, float post_mul, float post_add, hipStream_t s)
+{
+    if (!d_wins) return hipErrorInvalidValue;
+    return fit_frames(pixels, bytes, d_frames, d_wins, n, fit, net_h, net_w, out, out_dt, out_stride, post_mul, post_add, s);
+}
+
+// one frame -> [h][w][3] uint8: the colour rule by itself (yolo_op_frame_to_rgb); one pixel per lane
+__global__ __launch_bounds__(256) void k_frame_to_rgb(const uint8_t *pixels, unsigned bytes, FrameDesc f, uint8_t *out)
+{
+    const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= (size_t)f.h * f.w) return;
+    const int y = (int)(p / f.w), x = (int)(p - (size_t)y * f.w);
+    const AtFrame at{__builtin_amdgcn_make_buffer_rsrc((void *)pixels, 0, bytes, 0x00020000), f, color_matrix(f.matrix), 0, 0, FIT_CV2};
+    int v[3];
+    at.rgb(y, x, v);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) out[p * 3 + c] = (uint8_t)v[c];
+}
+hipError_t launch_frame_to_rgb(const uint8_t *pixels, size_t bytes, const FrameDesc &frame, uint8_t *out, hipStream_t s)
+{
+    if (frame.h < 1 || frame.w < 1 || bytes > 0xffffffffull || frame.format < 0 || frame.format >= PIX_COUNT || frame.matrix < 0 || frame.matrix >= MATRIX_COUNT) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_frame_to_rgb, grid_for((size_t)frame.h * frame.w), dim3(256), 0, s, pixels, (unsigned)bytes, frame, out);
+    return hipGetLastError();
+}
+
 // ---- darknet letterbox_image (DN/image.c:960-981: resize_image to the aspect-preserving size, embedded in a 0.5-grey w x h
 //      canvas) and resize_image itself (DN/image.c:1347-1389; embed == 0: the image is stretched to w x h), planar float in,
 //      planar float out.  Same two-pass operation order as k_letterbox_chw above. ----

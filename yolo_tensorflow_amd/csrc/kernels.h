@@ -489,6 +489,55 @@ __host__ __device__ inline float fit_unit_value(int fit, unsigned v)
     if (fit == FIT_LETTERBOX || fit == FIT_CENTER_CROP) return (float)((double)v / 255.);
     return (float)v;
 }
+// ---- decoded video frames (yolo_*_frames_*): a frame is h x w pixels stored as NV12, I420 or pitched RGB / BGR rows, every plane at its own
+// byte offset of the packed buffer and its own row pitch (the layout of yolo_frame_desc, include/yolo_hip.h; offsets and pitches < 2^32, checked by the
+// caller).  The fits read a frame as the h x w x 3 byte image the colour rule below yields; no such image is stored.  64 bytes.
+struct FrameDesc { unsigned long long offset[3], pitch[3]; int h, w, format, matrix; };
+static_assert(sizeof(FrameDesc) == 64, "the frame table's row: a power of two");
+enum { PIX_NV12 = 0, PIX_I420 = 1, PIX_RGB24 = 2, PIX_BGR24 = 3, PIX_COUNT = 4 };
+enum { MATRIX_BT601 = 0, MATRIX_BT709 = 1, MATRIX_BT601_FULL = 2, MATRIX_COUNT = 3 };
+// The colour rule, in int32 (every intermediate lies in -282 943 616 .. +573 487 137): the integers are round(k * 2^20) of the classic decimal constants
+//   BT.601 limited 1.164, 1.596, 0.391, 0.813, 2.018;  BT.709 limited 1.164, 1.793, 0.213, 0.533, 2.112;  BT.601 full (JFIF) 1, 1.402, 0.344136, 0.714136, 1.772.
+// The BT.601 limited row is believed to be what OpenCV's COLOR_YUV2RGB_NV12 evaluates; cv2 is absent here: parity unpinned.
+struct ColorMatrix { int yoff, cy, cvr, cug, cvg, cub; };
+__host__ __device__ inline ColorMatrix color_matrix(int m)
+{
+    if (m == MATRIX_BT709) return ColorMatrix{16, 1220542, 1880097, 223347, 558891, 2214593};
+    if (m == MATRIX_BT601_FULL) return ColorMatrix{0, 1048576, 1470104, 360853, 748826, 1858077};
+    return ColorMatrix{16, 1220542, 1673527, 409993, 852492, 2116026};
+}
+__host__ __device__ inline int clamp8(int v) { return v < 0 ? 0 : v > 255 ? 255 : v; }
+// R, G, B bytes of one (Y, U, V) sample; `>>` on a negative sum is the arithmetic shift
+__host__ __device__ inline void yuv_to_rgb(const ColorMatrix &m, int Y, int U, int V, int *rgb)
+{
+    const int y = (Y - m.yoff > 0 ? Y - m.yoff : 0) * m.cy, u = U - 128, v = V - 128;
+    rgb[0] = clamp8((y + m.cvr * v + (1 << 19)) >> 20);
+    rgb[1] = clamp8((y - m.cug * u - m.cvg * v + (1 << 19)) >> 20);
+    rgb[2] = clamp8((y + m.cub * u + (1 << 19)) >> 20);
+}
+// byte offsets of the samples of pixel (y, x) of a frame: chroma is taken from (y >> 1, x >> 1) of the FRAME (nearest, no interpolation).  NV12 / I420: o[0] Y, o[1] U,
+// o[2] V; RGB24 / BGR24: o[c] the byte of output channel c (BGR swaps 0 and 2)
+__host__ __device__ inline void frame_sample_offsets(const FrameDesc &f, int y, int x, unsigned *o)
+{
+    if (f.format >= PIX_RGB24) {
+        const unsigned p = (unsigned)f.offset[0] + (unsigned)y * (unsigned)f.pitch[0] + (unsigned)x * 3u, sw = f.format == PIX_BGR24 ? 2u : 0u;
+        o[0] = p + sw; o[1] = p + 1u; o[2] = p + 2u - sw;
+        return;
+    }
+    o[0] = (unsigned)f.offset[0] + (unsigned)y * (unsigned)f.pitch[0] + (unsigned)x;
+    const unsigned cy = (unsigned)y >> 1, cx = (unsigned)x >> 1;
+    if (f.format == PIX_NV12) { o[1] = (unsigned)f.offset[1] + cy * (unsigned)f.pitch[1] + 2u * cx; o[2] = o[1] + 1u; }
+    else { o[1] = (unsigned)f.offset[1] + cy * (unsigned)f.pitch[1] + cx; o[2] = (unsigned)f.offset[2] + cy * (unsigned)f.pitch[2] + cx; }
+}
+// whole frames, one per batch slot, fitted as launch_fit_images fits RGB images; fit: FIT_STRETCH, FIT_LETTERBOX, FIT_CV2 or FIT_CENTER_CROP.  One batch may mix formats
+hipError_t launch_fit_frames(const uint8_t *pixels, size_t bytes, const FrameDesc *d_frames, int n, int fit, int net_h, int net_w, void *out, int out_dt,
+                             int out_stride, float post_mul, float post_add, hipStream_t s);
+// windows of frames (yolo_detect_tiled_frames_u8): window i is rows y0 .., columns x0 .. of frame d_wins[i].image (its offset and pitch are not read); chroma is
+// indexed by the pixel's position in the FRAME, so a window may start on an odd row or column.  FIT_STRETCH and FIT_LETTERBOX
+hipError_t launch_fit_frame_windows(const uint8_t *pixels, size_t bytes, const FrameDesc *d_frames, const WinDesc *d_wins, int n, int fit, int net_h, int net_w,
+                                    void *out, int out_dt, int out_stride, float post_mul, float post_add, hipStream_t s);
+// one frame -> the [h][w][3] uint8 image of the colour rule (yolo_op_frame_to_rgb)
+hipError_t launch_frame_to_rgb(const uint8_t *pixels, size_t bytes, const FrameDesc &frame, uint8_t *out, hipStream_t s);
 hipError_t launch_upsample2x(const TView &in, const TView &out, int bilinear, hipStream_t s);
 hipError_t launch_maxpool(const TView &in, const TView &out, int size, int stride, int pad, hipStream_t s);
 hipError_t launch_reorg(const TView &in, const TView &out, int stride, int darknet, hipStream_t s);

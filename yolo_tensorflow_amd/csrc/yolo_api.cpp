@@ -83,7 +83,7 @@ void yolo_destroy(yolo_ctx *c)
     if (c->d_state_keep) hipFree(c->d_state_keep);
     for (void *p : {(void *)c->d_ring, (void *)c->d_ring_keep, (void *)c->d_ring_pos}) if (p) hipFree(p);
     void *ptrs[] = {c->input.ptr, c->d_zeros, c->d_stage, c->d_det, c->d_scores, c->d_labels, c->d_cand, c->d_keys, c->d_sbox, c->d_slabel, c->d_sscore, c->d_boxes, c->d_counts,
-                    c->d_seq, c->d_dn_rec, c->d_dn_src, c->d_dn_count, c->d_dn_last, c->d_box4, c->s2d.ptr, c->d_srow, c->d_rows, c->d_lean_list, c->d_lean_cnt, c->d_f32a, c->d_f32b, c->d_descs, c->d_pix, c->d_tile, c->d_views, c->d_cls_idx, c->d_cls_prob, c->d_map_f32, c->d_map_labels, c->d_label_off};
+                    c->d_seq, c->d_dn_rec, c->d_dn_src, c->d_dn_count, c->d_dn_last, c->d_box4, c->s2d.ptr, c->d_srow, c->d_rows, c->d_lean_list, c->d_lean_cnt, c->d_f32a, c->d_f32b, c->d_descs, c->d_frames, c->d_pix, c->d_tile, c->d_views, c->d_cls_idx, c->d_cls_prob, c->d_map_f32, c->d_map_labels, c->d_label_off};
     for (void *p : ptrs) if (p) hipFree(p);
     for (auto &t : c->trees) free_tree(t);
     if (c->d_map200) hipFree(c->d_map200);

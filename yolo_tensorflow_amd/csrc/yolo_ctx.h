@@ -159,11 +159,14 @@ struct yolo_ctx {
     // the captured detect steps (graph_step, yolo_run.cpp): graph[0] yolo_detect_graph's, graph[1] yolo_detect_images_graph's -- one each: a caller that alternates the two recaptures neither.
     // key: every argument the captured launches hold, both entry points' in one struct (memset to zero before it is filled: memcmp compares it; no image size or offset: those live in d_descs, rewritten before every launch)
     struct GraphKey { const void *src; size_t bytes; int n, fmt, fit, units; float scale, st, it; int mo, nm, sm; void *bo, *co; };
-    struct GraphStep { GraphKey key; hipGraphExec_t exec; int state; } graph[2] = {};      // state 0: next call eager, 1: next call captures, 2: replay, -1: capture unsupported (sticky)
+    struct GraphStep { GraphKey key; hipGraphExec_t exec; int state; } graph[3] = {};      // state 0: next call eager, 1: next call captures, 2: replay, -1: capture unsupported (sticky).  graph[2]: yolo_detect_frames_graph's
     // ragged batches of native-size images (yolo_*_images_*): descriptor table [max_batch] (device), staging of a host packed buffer, the
     // geometry the last such forward ran with (what the box mapping of its postprocess reads)
     ImgDesc *d_descs = nullptr; void *d_pix = nullptr; size_t pix_cap = 0;
     int geom_fit = -1, geom_n = 0;
+    // decoded video frames (yolo_*_frames_*): the frame table [max_batch] (device) the fit launch reads; d_descs then holds {plane 0's offset, h, w} of the same
+    // frames, so the box mapping reads what it reads for images.  h_geom: the host side of that copy, kept here so that it outlives the asynchronous upload
+    FrameDesc *d_frames = nullptr; std::vector<ImgDesc> h_geom;
     // tiled detection (yolo_detect_tiled_u8): ONE allocation, grown on demand and never shrunk, that holds the window table, the image table, every
     // image's merged candidate list and k_nms_image's workspace over those lists (tile_slab, yolo_run.cpp)
     void *d_tile = nullptr; size_t tile_cap = 0;
@@ -295,6 +298,8 @@ struct PostGeom { int fit, pixels; };      // per-image box mapping of a ragged 
 int post(yolo_ctx *c, const float *det, int n, int rows, int attrs, float score_thr, float iou_thr, int max_out,
          int nms_mode, int select_mode, int img_h, int img_w, int scores_ready, yolo_box *boxes_out, int32_t *counts_out, int out_loc, int32_t *rows_out = nullptr,
          const PostGeom *geom = nullptr);
+// decoded video frames: YOLO_OK, or YOLO_ERR_INVALID with what is wrong with frame `i`'s descriptor inside a packed buffer of `bytes` bytes in `msg` (yolo_run.cpp)
+int frame_desc_check(const yolo_frame_desc &d, size_t bytes, int i, std::string &msg);
 // yolo_api.cpp: map networks
 int need_map(yolo_ctx *c, const char *what);      // YOLO_ERR_INVALID with a message for a detector or a classifier context
 int map_to_f32(yolo_ctx *c, int n);

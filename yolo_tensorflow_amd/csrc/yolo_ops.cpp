@@ -541,6 +541,19 @@ int yolo_op_resize_cv2(const uint8_t *img, int h, int w, int oh, int ow, int swa
     return S.download(out, d_o, (size_t)oh * ow * 3 * 4);
 }
 
+int yolo_op_frame_to_rgb(const yolo_frame_desc *desc, const uint8_t *pixels, size_t bytes, uint8_t *rgb_out, int device)
+{
+    if (!desc || !pixels || !rgb_out) { g_op_err = "frame_to_rgb: desc / pixels / rgb_out == NULL"; return YOLO_ERR_INVALID; }
+    if (int r = frame_desc_check(*desc, bytes, 0, g_op_err)) { g_op_err = "frame_to_rgb: " + g_op_err; return r; }
+    OpScope S(device); if (S.rc) { g_op_err = "frame_to_rgb: no HIP device"; return S.rc; }
+    FrameDesc f; memcpy(&f, desc, sizeof f);
+    const size_t out_bytes = (size_t)f.h * f.w * 3;
+    uint8_t *d_i = (uint8_t *)S.upload(pixels, bytes), *d_o = (uint8_t *)S.alloc(out_bytes);
+    if (S.rc) { g_op_err = "frame_to_rgb: allocation failed"; return S.rc; }
+    if (!S.ok(launch_frame_to_rgb(d_i, bytes, f, d_o, S.s))) { g_op_err = "frame_to_rgb: " + S.err; return S.rc; }
+    return S.download(rgb_out, d_o, out_bytes);
+}
+
 int yolo_op_letterbox(const float *image_chw, int iw, int ih, int w, int h, int embed, float *out_chw, int device)
 {
     if (!image_chw || !out_chw || iw < 1 || ih < 1 || w < 1 || h < 1) { g_op_err = "letterbox: bad arguments"; return YOLO_ERR_INVALID; }

@@ -1108,6 +1108,7 @@ int allocate(yolo_ctx *c)
     c->stage_bytes = (size_t)c->max_batch * c->in_h * c->in_w * (c->vec_n ? c->vec_n : c->in_c) * 4;
     HIPCK(c, hipMalloc(&c->d_stage, c->stage_bytes));
     HIPCK(c, hipMalloc((void **)&c->d_descs, (size_t)c->max_batch * sizeof(ImgDesc)));      // ragged batches: one descriptor per image
+    HIPCK(c, hipMalloc((void **)&c->d_frames, (size_t)c->max_batch * sizeof(FrameDesc)));      // ... and one per decoded video frame
     size_t nr = (size_t)c->max_batch * c->rows;
     if (c->rows == 0) nr = 1;            // a classifier or a map network has no candidate rows: the detection workspace is one element each
     if (c->cls_layer >= 0) {

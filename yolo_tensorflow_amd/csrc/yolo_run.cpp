@@ -664,6 +664,31 @@ int post(yolo_ctx *c, const float *det, int n, int rows, int attrs, float score_
     return YOLO_OK;
 }
 
+// decoded video frames: what is wrong with frame `i`'s descriptor inside a packed buffer of `bytes` bytes, before anything reads it
+int frame_desc_check(const yolo_frame_desc &d, size_t bytes, int i, std::string &msg)
+{
+    char b[256];
+    auto bad = [&](const char *fmt, auto... a) { snprintf(b, sizeof b, fmt, a...); msg = "frame " + std::to_string(i) + ": " + b; return (int)YOLO_ERR_INVALID; };
+    if (d.format < YOLO_PIX_NV12 || d.format > YOLO_PIX_BGR24) return bad("unknown format %d", (int)d.format);
+    if (d.matrix < YOLO_MATRIX_BT601 || d.matrix > YOLO_MATRIX_BT601_FULL) return bad("unknown matrix %d", (int)d.matrix);
+    if (d.h < 1 || d.w < 1) return bad("%d x %d", (int)d.h, (int)d.w);
+    const uint64_t ch = ((uint64_t)d.h + 1) / 2, cw = ((uint64_t)d.w + 1) / 2;
+    // the planes the format has: rows and bytes per row
+    const int planes = d.format == YOLO_PIX_NV12 ? 2 : d.format == YOLO_PIX_I420 ? 3 : 1;
+    for (int p = 0; p < planes; ++p) {
+        const uint64_t rows = p == 0 ? (uint64_t)d.h : ch;
+        const uint64_t row = d.format >= YOLO_PIX_RGB24 ? 3 * (uint64_t)d.w : p == 0 ? (uint64_t)d.w : d.format == YOLO_PIX_NV12 ? 2 * cw : cw;
+        if (d.pitch[p] < row) return bad("plane %d: pitch %llu below the row's %llu bytes", p, (unsigned long long)d.pitch[p], (unsigned long long)row);
+        if (d.pitch[p] > 0xffffffffull) return bad("plane %d: pitch %llu does not fit 32 bits", p, (unsigned long long)d.pitch[p]);
+        if (d.offset[p] > 0xffffffffull || (rows - 1) * d.pitch[p] + row > 0xffffffffull - d.offset[p])
+            return bad("plane %d: %llu rows of pitch %llu at offset %llu pass 32 bits", p, (unsigned long long)rows, (unsigned long long)d.pitch[p], (unsigned long long)d.offset[p]);
+        if (d.offset[p] + (rows - 1) * d.pitch[p] + row > (uint64_t)bytes)
+            return bad("plane %d: %llu rows of pitch %llu (%llu bytes each) at offset %llu end past the %zu-byte buffer", p, (unsigned long long)rows, (unsigned long long)d.pitch[p],
+                       (unsigned long long)row, (unsigned long long)d.offset[p], bytes);
+    }
+    return YOLO_OK;
+}
+
 }  // namespace yolo_impl
 
 extern "C" {
@@ -969,6 +994,137 @@ int yolo_detect_images_graph(yolo_ctx *c, const uint8_t *pixels, size_t bytes, c
     return YOLO_OK;
 }
 
+// ---- decoded video frames: NV12 / I420 / pitched RGB / BGR surfaces described in place by yolo_frame_desc.  The fit launch reads the frame table
+//      and converts while it fits; d_descs receives {plane 0's offset, h, w} of the same frames, so everything behind the fit -- run_network, frame averaging,
+//      recurrent state, the box mapping of the postprocess -- is the image path's ----
+static_assert(sizeof(FrameDesc) == sizeof(yolo_frame_desc) && offsetof(FrameDesc, pitch) == offsetof(yolo_frame_desc, pitch) && offsetof(FrameDesc, h) == offsetof(yolo_frame_desc, h) &&
+              offsetof(FrameDesc, w) == offsetof(yolo_frame_desc, w) && offsetof(FrameDesc, format) == offsetof(yolo_frame_desc, format) && offsetof(FrameDesc, matrix) == offsetof(yolo_frame_desc, matrix),
+              "yolo_frame_desc is the frame table's row");
+static_assert(PIX_NV12 == YOLO_PIX_NV12 && PIX_I420 == YOLO_PIX_I420 && PIX_RGB24 == YOLO_PIX_RGB24 && PIX_BGR24 == YOLO_PIX_BGR24 && MATRIX_BT601 == YOLO_MATRIX_BT601 &&
+              MATRIX_BT709 == YOLO_MATRIX_BT709 && MATRIX_BT601_FULL == YOLO_MATRIX_BT601_FULL, "the kernels' format and matrix codes are the public ones");
+
+int yolo_frame_to_rgb_host(const yolo_frame_desc *desc, const uint8_t *pixels, size_t bytes, uint8_t *rgb_out)
+{
+    if (!desc || !pixels || !rgb_out) { g_op_err = "yolo_frame_to_rgb_host: desc / pixels / rgb_out == NULL"; return YOLO_ERR_INVALID; }
+    if (int r = frame_desc_check(*desc, bytes, 0, g_op_err)) { g_op_err = "yolo_frame_to_rgb_host: " + g_op_err; return r; }
+    FrameDesc f; memcpy(&f, desc, sizeof f);
+    const ColorMatrix m = color_matrix(f.matrix);
+    for (int y = 0; y < f.h; ++y)
+        for (int x = 0; x < f.w; ++x) {
+            unsigned o[3]; int v[3];
+            frame_sample_offsets(f, y, x, o);
+            if (f.format >= PIX_RGB24) for (int k = 0; k < 3; ++k) v[k] = pixels[o[k]];
+            else yuv_to_rgb(m, pixels[o[0]], pixels[o[1]], pixels[o[2]], v);
+            uint8_t *q = rgb_out + ((size_t)y * f.w + x) * 3;
+            q[0] = (uint8_t)v[0]; q[1] = (uint8_t)v[1]; q[2] = (uint8_t)v[2];
+        }
+    return YOLO_OK;
+}
+
+// one frame of a batch: its descriptor, and what `fit` needs of its size (fit < 0: no fit is asked), as image_check
+static int frame_check(yolo_ctx *c, int i, const yolo_frame_desc &d, size_t bytes, int fit)
+{
+    std::string msg;
+    if (int r = frame_desc_check(d, bytes, i, msg)) return fail(c, r, "%s", msg.c_str());
+    if (fit == YOLO_FIT_LETTERBOX) {
+        int nw, nh; letterbox_dims(c->in_w, c->in_h, d.w, d.h, &nw, &nh);
+        if (nw < 1 || nh < 1) return fail(c, YOLO_ERR_INVALID, "frame %d: %d x %d letterboxes to less than one pixel", i, (int)d.h, (int)d.w);
+    }
+    if (fit == YOLO_FIT_CENTER_CROP && !resize_min_ok(c->in_w, d.w, d.h))
+        return fail(c, YOLO_ERR_INVALID, "frame %d: %d x %d: its longer side times the network width %d does not fit an int (darknet's resize_min)", i, (int)d.h, (int)d.w, c->in_w);
+    return YOLO_OK;
+}
+
+// everything a batch of frames is refused for, before any launch: images_check's list, the frame descriptors, and what a frame cannot mean
+static int frames_check(yolo_ctx *c, const void *pixels, size_t bytes, const yolo_frame_desc *descs, int n, int fit)
+{
+    static const char *const who = "yolo_*_frames_u8 / yolo_detect_frames_graph";
+    if (int r = need_image(c, "forward of frames")) return r;
+    if (c->in_c != 3) return fail(c, YOLO_ERR_UNSUPPORTED, "%s: a network of %d planes ([net] yolo_input=planes) is not served: a frame is an RGB image after its conversion", who, c->in_c);
+    if (!c->weights_loaded) return fail(c, YOLO_ERR_STATE, "forward of frames before weights were loaded");
+    if (n < 1 || n > c->max_batch) return fail(c, YOLO_ERR_INVALID, "batch %d outside 1..%d", n, c->max_batch);
+    if (!pixels || !descs) return fail(c, YOLO_ERR_INVALID, "pixels / descs == NULL");
+    if (int r = fit_check(c, fit, who)) return r;
+    if (fit == YOLO_FIT_CV2_BGR) return fail(c, YOLO_ERR_UNSUPPORTED, "%s: YOLO_FIT_CV2_BGR is not served for frames: a frame's format states its channel order (YOLO_PIX_BGR24 with YOLO_FIT_CV2)", who);
+    if (bytes < 1 || bytes > 0xffffffffull) return fail(c, YOLO_ERR_INVALID, "packed buffer of %zu bytes (1 .. 2^32 - 1)", bytes);
+    for (int i = 0; i < n; ++i) if (int r = frame_check(c, i, descs[i], bytes, fit)) return r;
+    return YOLO_OK;
+}
+
+// this call's frame table and the {offset, h, w} table the box mapping reads: onto the device, on the context stream
+static int frames_upload(yolo_ctx *c, const yolo_frame_desc *descs, int n)
+{
+    c->h_geom.resize((size_t)c->max_batch);
+    for (int i = 0; i < n; ++i) c->h_geom[i] = ImgDesc{descs[i].offset[0], descs[i].h, descs[i].w};
+    HIPCK(c, hipMemcpyAsync(c->d_frames, descs, (size_t)n * sizeof(FrameDesc), hipMemcpyHostToDevice, c->stream));
+    HIPCK(c, hipMemcpyAsync(c->d_descs, c->h_geom.data(), (size_t)n * sizeof(ImgDesc), hipMemcpyHostToDevice, c->stream));
+    return YOLO_OK;
+}
+
+// the device step of a checked batch of frames whose tables are on the device: fit, network.  pixels: device memory
+static int frames_step(yolo_ctx *c, const uint8_t *pixels, size_t bytes, int n, int fit, bool lean, float score_thr)
+{
+    c->lean_thr = score_thr;
+    auto [dst, dt] = input_fill_dst(c);
+    HIPCK(c, launch_fit_frames(pixels, bytes, c->d_frames, n, fit, c->in_h, c->in_w, dst, dt, fill_stride(c), c->in_mul, c->in_add, c->stream));
+    HIPCK(c, input_filled(c, (size_t)n * c->in_h * c->in_w));
+    return run_network(c, n, lean, fit);
+}
+
+static int forward_frames_impl(yolo_ctx *c, const uint8_t *pixels, size_t bytes, const yolo_frame_desc *descs, int n, int fit, int loc,
+                               float *det_out, int out_loc, bool lean, float score_thr)
+{
+    if (int r = frames_check(c, pixels, bytes, descs, n, fit)) return r;
+    HIPCK(c, hipSetDevice(c->device));
+    const uint8_t *src = nullptr;
+    if (int r = stage_pixels(c, pixels, bytes, loc, &src)) return r;
+    if (int r = frames_upload(c, descs, n)) return r;
+    if (int r = frames_step(c, src, bytes, n, fit, lean && !det_out, score_thr)) return r;
+    return det_out ? copy_out(c, det_out, c->d_det, (size_t)n * c->rows * c->attrs * 4, out_loc) : YOLO_OK;
+}
+
+int yolo_forward_frames_u8(yolo_ctx *c, const uint8_t *pixels, size_t bytes, const yolo_frame_desc *descs, int n, int fit, int loc,
+                           float *det_out, int out_loc)
+{
+    if (!c) return YOLO_ERR_INVALID;
+    return forward_frames_impl(c, pixels, bytes, descs, n, fit, loc, det_out, out_loc, false, 0.f);
+}
+
+int yolo_detect_frames_u8(yolo_ctx *c, const uint8_t *pixels, size_t bytes, const yolo_frame_desc *descs, int n, int fit, int loc,
+                          float score_thr, float iou_thr, int max_out, int nms_mode, int select_mode, int units,
+                          yolo_box *boxes_out, int32_t *counts_out, int out_loc)
+{
+    if (!c) return YOLO_ERR_INVALID;
+    if (int r = detect_images_check(c, fit, max_out, nms_mode, select_mode, units)) return r;
+    if (int r = forward_frames_impl(c, pixels, bytes, descs, n, fit, loc, nullptr, YOLO_DEVICE, nms_mode != YOLO_NMS_NUMPY_V3, score_thr)) return r;
+    const PostGeom g{fit, units == YOLO_UNITS_SOURCE_PIXELS};
+    return postprocess_impl(c, n, score_thr, iou_thr, max_out, nms_mode, select_mode, boxes_out, counts_out, nullptr, out_loc, &g);
+}
+
+int yolo_detect_frames_graph(yolo_ctx *c, const uint8_t *pixels, size_t bytes, const yolo_frame_desc *descs, int n, int fit,
+                             float score_thr, float iou_thr, int max_out, int nms_mode, int select_mode, int units,
+                             yolo_box *boxes_out, int32_t *counts_out)
+{
+    if (!c) return YOLO_ERR_INVALID;
+    if (!pixels || !boxes_out || !counts_out) return fail(c, YOLO_ERR_INVALID, "yolo_detect_frames_graph needs device pointers for pixels, boxes_out and counts_out");
+    if (int r = detect_images_check(c, fit, max_out, nms_mode, select_mode, units)) return r;
+    if (int r = frames_check(c, pixels, bytes, descs, n, fit)) return r;
+    GraphKey k; memset(&k, 0, sizeof k);
+    k.src = pixels; k.bytes = bytes; k.n = n; k.fit = fit; k.units = units; k.st = score_thr; k.it = iou_thr; k.mo = max_out; k.nm = nms_mode; k.sm = select_mode; k.bo = boxes_out; k.co = counts_out;
+    HIPCK(c, hipSetDevice(c->device));
+    // this call's frames: into the device tables, on the context stream, ahead of the step that reads them (never captured)
+    if (int r = frames_upload(c, descs, n)) return r;
+    const GraphEager eager = [](yolo_ctx *c, const GraphKey &k) -> int {
+        if (int r = frames_step(c, (const uint8_t *)k.src, k.bytes, k.n, k.fit, k.nm != YOLO_NMS_NUMPY_V3, k.st)) return r;
+        const PostGeom g{k.fit, k.units == YOLO_UNITS_SOURCE_PIXELS};
+        return postprocess_impl(c, k.n, k.st, k.it, k.mo, k.nm, k.sm, (yolo_box *)k.bo, (int32_t *)k.co, nullptr, YOLO_DEVICE, &g);
+    };
+    bool replayed = false;
+    if (int r = graph_step(c, c->graph[2], k, eager, &replayed)) return r;
+    if (replayed) { c->lean_thr = score_thr; c->stem_u8 = nullptr; forward_done(c, n, nms_mode != YOLO_NMS_NUMPY_V3, nms_mode == YOLO_NMS_NUMPY_V3 ? 1 : 0, fit); }
+    return YOLO_OK;
+}
+
 // ---- tiled detection of images larger than the network input ("Tiled detection"): the window grid, then per chunk of max_batch windows one
 //      fit launch over the window table + the network + the cross-window merge, and ONE k_nms_image launch over every image's merged list ----
 namespace {
@@ -986,8 +1142,8 @@ bool tile_args_ok(int img_h, int img_w, int tile_h, int tile_w, int overlap_h, i
 // the carving of yolo_ctx::d_tile for a call of `images` images, `nwin` windows, `cap` merged rows per image and max_out records: every array 256-byte aligned
 struct TileSlab {
     WinDesc *wins; ImgDesc *descs; unsigned long long *overflow; float *scores; int *labels; float4 *box; int *cand; unsigned long long *keys; float4 *sbox; int *slabel; float *sscore;
-    yolo_box *boxes; int *counts, *wcount, *run[2], *total; size_t bytes, nan_fill;      // nan_fill: bytes from `overflow` to the end of `scores`, set to all ones before the first step
-    TileSlab(char *base, size_t images, size_t nwin, size_t cap, size_t pow2, size_t max_out, size_t max_batch)
+    yolo_box *boxes; int *counts, *wcount, *run[2], *total; FrameDesc *frames; size_t bytes, nan_fill;      // nan_fill: bytes from `overflow` to the end of `scores`, set to all ones before the first step
+    TileSlab(char *base, size_t images, size_t nwin, size_t cap, size_t pow2, size_t max_out, size_t max_batch, size_t nframes)      // nframes: rows of the frame table (yolo_detect_tiled_frames_u8), 0 for images
     {
         size_t off = 0;
         auto take = [&](size_t n) { const uintptr_t p = (uintptr_t)base + off; off += (n + 255) & ~(size_t)255; return (void *)p; };      // (base == nullptr: the sizes only)
@@ -997,6 +1153,7 @@ struct TileSlab {
         sbox = (float4 *)take(images * cap * 16); slabel = (int *)take(images * cap * 4); sscore = (float *)take(images * cap * 4);
         boxes = (yolo_box *)take(images * max_out * sizeof(yolo_box)); counts = (int *)take(images * 4); wcount = (int *)take(max_batch * 4);
         run[0] = (int *)take(images * 4); run[1] = (int *)take(images * 4); total = (int *)take(images * 4);
+        frames = (FrameDesc *)take(nframes * sizeof(FrameDesc));
         bytes = off;
     }
 };
@@ -1017,15 +1174,18 @@ int yolo_tile_windows(int img_h, int img_w, int tile_h, int tile_w, int overlap_
     return YOLO_OK;
 }
 
-int yolo_detect_tiled_u8(yolo_ctx *c, const uint8_t *pixels, size_t bytes, const yolo_image_desc *descs, int n_images, int tile_h, int tile_w, int overlap_h,
-                         int overlap_w, int fit, int loc, float score_thr, float iou_thr, int max_out, int nms_mode, int select_mode, int relative,
-                         yolo_box *boxes_out, int32_t *counts_out, int out_loc)
+static int frame_check(yolo_ctx *c, int i, const yolo_frame_desc &d, size_t bytes, int fit);
+
+// yolo_detect_tiled_u8 (descs: packed RGB images) and yolo_detect_tiled_frames_u8 (frames: decoded video frames, descs == NULL): the same steps over windows of either
+static int detect_tiled_impl(yolo_ctx *c, const char *who, const uint8_t *pixels, size_t bytes, const yolo_image_desc *descs, const yolo_frame_desc *frames, int n_images,
+                             int tile_h, int tile_w, int overlap_h, int overlap_w, int fit, int loc, float score_thr, float iou_thr, int max_out, int nms_mode,
+                             int select_mode, int relative, yolo_box *boxes_out, int32_t *counts_out, int out_loc)
 {
-    static const char *const who = "yolo_detect_tiled_u8";
     if (!c) return YOLO_ERR_INVALID;
     // ---- every refusal, before any launch ----
     if (int r = need_detector(c, who)) return r;
     if (c->in_c != 3) return fail(c, YOLO_ERR_UNSUPPORTED, "%s: a network of %d planes ([net] yolo_input=planes) is not served: windows are cut from RGB images", who, c->in_c);
+    if (frames && fit == YOLO_FIT_CV2_BGR) return fail(c, YOLO_ERR_UNSUPPORTED, "%s: YOLO_FIT_CV2_BGR is not served for frames: a frame's format states its channel order", who);
     if (c->avg_k > 1) return fail(c, YOLO_ERR_UNSUPPORTED, "%s: not served while frame averaging is on (yolo_set_frame_average(%d)): a batch slot holds a window, not a stream; set it to 1 first", who, c->avg_k);
     if (!c->weights_loaded) return fail(c, YOLO_ERR_STATE, "%s before weights were loaded", who);
     static const char *const fit_names[] = {"YOLO_FIT_STRETCH", "YOLO_FIT_LETTERBOX", "YOLO_FIT_CV2", "YOLO_FIT_CV2_BGR", "YOLO_FIT_CENTER_CROP"};
@@ -1042,17 +1202,25 @@ int yolo_detect_tiled_u8(yolo_ctx *c, const uint8_t *pixels, size_t bytes, const
     if (relative != 0 && relative != 1) return fail(c, YOLO_ERR_INVALID, "bad relative %d", relative);
     if (!boxes_out || !counts_out) return fail(c, YOLO_ERR_INVALID, "boxes_out / counts_out == NULL");
     if (n_images < 1) return fail(c, YOLO_ERR_INVALID, "%d images", n_images);
-    if (!pixels || !descs) return fail(c, YOLO_ERR_INVALID, "pixels / descs == NULL");
+    if (!pixels || (!descs && !frames)) return fail(c, YOLO_ERR_INVALID, "pixels / descs == NULL");
     if (bytes < 3 || bytes > 0xffffffffull) return fail(c, YOLO_ERR_INVALID, "packed buffer of %zu bytes (3 .. 2^32 - 1)", bytes);
     if (tile_h == 0 && tile_w == 0) { tile_h = c->in_h; tile_w = c->in_w; }
     if (!tile_args_ok(1, 1, tile_h, tile_w, overlap_h, overlap_w))
         return fail(c, YOLO_ERR_INVALID, "%s: tile %d x %d with overlap %d x %d: extents >= 1 and 0 <= overlap < tile are needed", who, tile_h, tile_w, overlap_h, overlap_w);
     std::vector<WinDesc> wins;
+    std::vector<yolo_image_desc> geom;                                     // frames: {plane 0's offset, h, w} of every frame, what the relative form divides by
     int most = 0;                                                          // windows of the image that has the most
     try {
+        if (frames) {
+            for (int i = 0; i < n_images; ++i) {
+                if (int r = frame_check(c, i, frames[i], bytes, -1)) return r;
+                geom.push_back(yolo_image_desc{frames[i].offset[0], frames[i].h, frames[i].w});
+            }
+            descs = geom.data();
+        }
         for (int i = 0; i < n_images; ++i) {
             const yolo_image_desc &d = descs[i];
-            if (int r = desc_check(c, i, d, bytes)) return r;
+            if (!frames) if (int r = desc_check(c, i, d, bytes)) return r;
             if ((uint64_t)d.w * 3u > 0x7fffffffull) return fail(c, YOLO_ERR_INVALID, "image %d: a row of %d pixels does not fit a 32-bit pitch", i, (int)d.w);
             const TileAxis ay(d.h, tile_h, overlap_h), ax(d.w, tile_w, overlap_w);
             if ((long long)ay.n * ax.n + (long long)wins.size() > 0x7fffffffLL) return fail(c, YOLO_ERR_INVALID, "image %d: 2^31 windows or more", i);
@@ -1060,6 +1228,7 @@ int yolo_detect_tiled_u8(yolo_ctx *c, const uint8_t *pixels, size_t bytes, const
             for (int k = 0; k < ay.n * ax.n; ++k) {
                 WinDesc w; w.y0 = ay.start(k / ax.n); w.x0 = ax.start(k % ax.n); w.h = ay.extent(); w.w = ax.extent(); w.pitch = d.w * 3; w.image = i;
                 w.offset = d.offset + (uint64_t)w.y0 * (uint64_t)w.pitch + (uint64_t)w.x0 * 3u;
+                if (frames) { w.offset = 0; w.pitch = 0; }          // a frame's window is (y0, x0, h, w) of frame `image`: the fit reads the frame table
                 if (fit == YOLO_FIT_LETTERBOX) {
                     int nw, nh; letterbox_dims(c->in_w, c->in_h, w.w, w.h, &nw, &nh);
                     if (nw < 1 || nh < 1) return fail(c, YOLO_ERR_INVALID, "image %d: its %d x %d window letterboxes to less than one pixel", i, w.h, w.w);
@@ -1071,7 +1240,7 @@ int yolo_detect_tiled_u8(yolo_ctx *c, const uint8_t *pixels, size_t bytes, const
     const int nwin = (int)wins.size();
     const size_t cap = (size_t)std::min<long long>(TILE_MERGE_CAP, (long long)most * c->rows);
     size_t pow2 = 1; while (pow2 < cap) pow2 <<= 1;
-    const TileSlab need(nullptr, n_images, nwin, cap, pow2, max_out, c->max_batch);
+    const TileSlab need(nullptr, n_images, nwin, cap, pow2, max_out, c->max_batch, frames ? n_images : 0);
 
     // ---- device ----
     HIPCK(c, hipSetDevice(c->device));
@@ -1083,10 +1252,11 @@ int yolo_detect_tiled_u8(yolo_ctx *c, const uint8_t *pixels, size_t bytes, const
         c->d_tile = nullptr; c->tile_cap = 0;
         HIPCK(c, hipMalloc(&c->d_tile, need.bytes)); c->tile_cap = need.bytes;
     }
-    const TileSlab t((char *)c->d_tile, n_images, nwin, cap, pow2, max_out, c->max_batch);
+    const TileSlab t((char *)c->d_tile, n_images, nwin, cap, pow2, max_out, c->max_batch, frames ? n_images : 0);
     StreamDrain drain{c};
     HIPCK(c, hipMemcpyAsync(t.wins, wins.data(), (size_t)nwin * sizeof(WinDesc), hipMemcpyHostToDevice, c->stream));
     HIPCK(c, hipMemcpyAsync(t.descs, descs, (size_t)n_images * sizeof(ImgDesc), hipMemcpyHostToDevice, c->stream));
+    if (frames) HIPCK(c, hipMemcpyAsync(t.frames, frames, (size_t)n_images * sizeof(FrameDesc), hipMemcpyHostToDevice, c->stream));
     // the overflow word starts as all ones; so does every merged score: a NaN, which neither `>` nor `>=` lets through the NMS's own threshold
     HIPCK(c, hipMemsetAsync(t.overflow, 0xff, t.nan_fill, c->stream));
     c->lean_thr = score_thr;
@@ -1099,7 +1269,8 @@ int yolo_detect_tiled_u8(yolo_ctx *c, const uint8_t *pixels, size_t bytes, const
     for (int first = 0, step = 0; first < nwin; first += c->max_batch, ++step) {
         const int nb = std::min(c->max_batch, nwin - first);
         auto [dst, dt] = input_fill_dst(c);
-        HIPCK(c, launch_fit_windows(src, bytes, t.wins + first, nb, fit, c->in_h, c->in_w, dst, dt, 8, c->in_mul, c->in_add, c->stream));
+        if (frames) HIPCK(c, launch_fit_frame_windows(src, bytes, t.frames, t.wins + first, nb, fit, c->in_h, c->in_w, dst, dt, 8, c->in_mul, c->in_add, c->stream));
+        else HIPCK(c, launch_fit_windows(src, bytes, t.wins + first, nb, fit, c->in_h, c->in_w, dst, dt, 8, c->in_mul, c->in_add, c->stream));
         HIPCK(c, input_filled(c, (size_t)nb * c->in_h * c->in_w));
         if (int r = run_network(c, nb, true)) return r;
         m.first = first; m.nb = nb; m.det = c->d_det; m.box4 = c->det_valid ? nullptr : c->d_box4;
@@ -1123,6 +1294,23 @@ int yolo_detect_tiled_u8(yolo_ctx *c, const uint8_t *pixels, size_t bytes, const
                     who, (unsigned)(over >> 32), (unsigned)(over & 0xffffffffu), cap);
     if (int r = copy_out(c, boxes_out, t.boxes, (size_t)n_images * max_out * sizeof(yolo_box), out_loc)) return r;
     return copy_out(c, counts_out, t.counts, (size_t)n_images * 4, out_loc);
+}
+
+int yolo_detect_tiled_u8(yolo_ctx *c, const uint8_t *pixels, size_t bytes, const yolo_image_desc *descs, int n_images, int tile_h, int tile_w, int overlap_h,
+                         int overlap_w, int fit, int loc, float score_thr, float iou_thr, int max_out, int nms_mode, int select_mode, int relative,
+                         yolo_box *boxes_out, int32_t *counts_out, int out_loc)
+{
+    return detect_tiled_impl(c, "yolo_detect_tiled_u8", pixels, bytes, descs, nullptr, n_images, tile_h, tile_w, overlap_h, overlap_w, fit, loc, score_thr, iou_thr, max_out,
+                             nms_mode, select_mode, relative, boxes_out, counts_out, out_loc);
+}
+
+int yolo_detect_tiled_frames_u8(yolo_ctx *c, const uint8_t *pixels, size_t bytes, const yolo_frame_desc *descs, int n_images, int tile_h, int tile_w, int overlap_h,
+                                int overlap_w, int fit, int loc, float score_thr, float iou_thr, int max_out, int nms_mode, int select_mode, int relative,
+                                yolo_box *boxes_out, int32_t *counts_out, int out_loc)
+{
+    if (c && !descs) return fail(c, YOLO_ERR_INVALID, "pixels / descs == NULL");
+    return detect_tiled_impl(c, "yolo_detect_tiled_frames_u8", pixels, bytes, nullptr, descs, n_images, tile_h, tile_w, overlap_h, overlap_w, fit, loc, score_thr, iou_thr, max_out,
+                             nms_mode, select_mode, relative, boxes_out, counts_out, out_loc);
 }
 
 // ---- classifier contexts: forward + tail; the [softmax] launch of the output layer selects the top_k itself (run_layer) ----

@@ -99,6 +99,32 @@ class _Detector:
             out.append((r["score"], np.stack([r["x0"], r["y0"], r["x1"], r["y1"]], -1).reshape(-1, 4), r["cls"]))
         return out
 
+    def detect_from_frames(self, frames):
+        """detect_from_images over decoded video frames (a list of hip.Frame: NV12, I420 or pitched RGB / BGR surfaces as the decoder left
+        them): each chunk of max_batch frames is converted, fitted and detected in ONE device step (Engine.detect_frames) -> what
+        detect_from_images returns for the RGB images the frames' colour rule yields."""
+        frames = list(frames)
+        if self.average_frames > 1 and len(frames) > self.max_batch:
+            raise ValueError("detect_from_frames: %d frames, but with average_frames=%d a call is one time step of at most max_batch=%d streams"
+                             % (len(frames), self.average_frames, self.max_batch))
+        out = []
+        for i in range(0, len(frames), self.max_batch):
+            for r in self.engine.detect_frames(frames[i:i + self.max_batch], fit=hip.FIT_STRETCH, units=hip.UNITS_NETWORK, score_thr=self.threshold,
+                                               iou_thr=self.iou_threshold, max_out=self.max_output_size, nms_mode=hip.NMS_TF,
+                                               select_mode=self.select_mode):
+                out.append((r["score"], np.stack([r["x0"], r["y0"], r["x1"], r["y1"]], -1).reshape(-1, 4), r["cls"]))
+        return out
+
+    def detect_from_large_frames(self, frames, tile=None, overlap=64):
+        """detect_from_large_images over decoded video frames (a list of hip.Frame; Engine.detect_tiled_frames): a 4K NV12 surface is cut
+        into windows where it lies -> [(scores, boxes, classes)] per frame, boxes normalised to the frame."""
+        out = []
+        for r in self.engine.detect_tiled_frames(list(frames), tile=tile, overlap=overlap, fit=hip.FIT_STRETCH, relative=True, score_thr=self.threshold,
+                                                 iou_thr=self.iou_threshold, max_out=self.max_output_size, nms_mode=hip.NMS_TF,
+                                                 select_mode=self.select_mode):
+            out.append((r["score"], np.stack([r["x0"], r["y0"], r["x1"], r["y1"]], -1).reshape(-1, 4), r["cls"]))
+        return out
+
     def detect_from_file(self, image_file, imshow=False, deteted_boxes_file="boxes.txt", detected_image_file=None):
         """(sic: `deteted_boxes_file` is the reference's spelling.)  Reads the image with PIL instead of OpenCV and
         returns the predictions; with `detected_image_file` the boxes are drawn (draw.draw_detection) and the picture is saved."""

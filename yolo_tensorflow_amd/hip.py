@@ -25,10 +25,14 @@ SELECT_GT, SELECT_GE = 0, 1
 FIT_STRETCH, FIT_LETTERBOX, FIT_CV2, FIT_CV2_BGR, FIT_CENTER_CROP = 0, 1, 2, 3, 4
 UNITS_NETWORK, UNITS_SOURCE_PIXELS = 0, 1
 VIEWS_FLIP, VIEWS_TEN_CROP = 1, 2
+PIX_NV12, PIX_I420, PIX_RGB24, PIX_BGR24 = 0, 1, 2, 3
+MATRIX_BT601, MATRIX_BT709, MATRIX_BT601_FULL = 0, 1, 2
 
 BOX_DTYPE = np.dtype([("x0", "<f4"), ("y0", "<f4"), ("x1", "<f4"), ("y1", "<f4"), ("score", "<f4"), ("cls", "<i4")])
 # yolo_image_desc: one image of a ragged batch, a uint8 RGB [h][w][3] image at byte `offset` of one packed buffer
 DESC_DTYPE = np.dtype([("offset", "<u8"), ("h", "<i4"), ("w", "<i4")])
+# yolo_frame_desc: one decoded video frame, every plane at its own byte offset of one packed buffer and its own row pitch
+FRAME_DTYPE = np.dtype([("offset", "<u8", (3,)), ("pitch", "<u8", (3,)), ("h", "<i4"), ("w", "<i4"), ("format", "<i4"), ("matrix", "<i4")])
 # yolo_view: one view of multi-view classification, the crop offsets in pixels and whether the image is mirrored
 VIEW_DTYPE = np.dtype([("dy", "<i4"), ("dx", "<i4"), ("flip", "<i4"), ("pad", "<i4")])
 
@@ -56,6 +60,7 @@ EXPORTS = [
     "yolo_vector_inputs", "yolo_forward_vectors", "yolo_sequence", "yolo_set_temperature", "yolo_reset_temperature", "yolo_op_sample",
     "yolo_set_frame_average", "yolo_frame_average",
     "yolo_view_table", "yolo_classify_views_u8", "yolo_op_view_reduce",
+    "yolo_frame_to_rgb_host", "yolo_op_frame_to_rgb", "yolo_forward_frames_u8", "yolo_detect_frames_u8", "yolo_detect_frames_graph", "yolo_detect_tiled_frames_u8",
 ]
 HIER_CONDITIONAL, HIER_ABSOLUTE, HIER_LEAVES = 0, 1, 2
 _HIER_MODES = {None: HIER_CONDITIONAL, "conditional": HIER_CONDITIONAL, "absolute": HIER_ABSOLUTE, "leaves": HIER_LEAVES}
@@ -188,6 +193,12 @@ def load_library():
     l.yolo_view_table.argtypes = [I, I, P, I, C.POINTER(I)]
     l.yolo_classify_views_u8.argtypes = [P, P, SZ, P, I, I, I, I, I, F, I, P, P, I]
     l.yolo_op_view_reduce.argtypes = [P, I, I, I, F, I, P, P, P, I]
+    l.yolo_frame_to_rgb_host.argtypes = [P, P, SZ, P]
+    l.yolo_op_frame_to_rgb.argtypes = [P, P, SZ, P, I]
+    l.yolo_forward_frames_u8.argtypes = l.yolo_forward_images_u8.argtypes
+    l.yolo_detect_frames_u8.argtypes = l.yolo_detect_images_u8.argtypes
+    l.yolo_detect_frames_graph.argtypes = l.yolo_detect_images_graph.argtypes
+    l.yolo_detect_tiled_frames_u8.argtypes = l.yolo_detect_tiled_u8.argtypes
     l.yolo_vector_inputs.argtypes = [P]
     l.yolo_forward_vectors.argtypes = [P, P, I, I, P, SZ]
     l.yolo_sequence.argtypes = [P, I, I, P, I, P, F, P, P, I]
@@ -269,6 +280,99 @@ def _descs(descs):
     if d.dtype != DESC_DTYPE:
         d = np.ascontiguousarray(np.asarray(descs), dtype=DESC_DTYPE)
     return d
+
+
+def frame_plane_rows(h, w, format):
+    """(rows, bytes per row) of every plane a frame of `format` has, in plane order"""
+    ch, cw = (int(h) + 1) // 2, (int(w) + 1) // 2
+    if format == PIX_NV12:
+        return [(int(h), int(w)), (ch, 2 * cw)]
+    if format == PIX_I420:
+        return [(int(h), int(w)), (ch, cw), (ch, cw)]
+    if format in (PIX_RGB24, PIX_BGR24):
+        return [(int(h), 3 * int(w))]
+    raise YoloError("unknown pixel format %r" % (format,))
+
+
+class Frame(object):
+    """One decoded video frame as a decoder or a capture leaves it (yolo_frame_desc): `data` a uint8 buffer (host numpy array of any shape,
+    read flat) that holds the planes of an h x w frame in `format` (PIX_NV12, PIX_I420, PIX_RGB24, PIX_BGR24), plane p beginning at byte
+    offsets[p] of it with rows pitch[p] bytes apart.  pitch: one int for every plane or one per plane; None: the rows' own bytes.  offsets:
+    None: the planes back to back in plane order, each rows * pitch bytes.  matrix: MATRIX_BT601 / MATRIX_BT709 (limited range) or
+    MATRIX_BT601_FULL (JFIF); not read for the RGB formats."""
+
+    def __init__(self, data, h, w, format, matrix=MATRIX_BT601, pitch=None, offsets=None):
+        self.data = np.ascontiguousarray(data).reshape(-1)
+        if self.data.dtype != np.uint8:
+            raise YoloError("Frame: need uint8 data, got %s" % self.data.dtype)
+        self.h, self.w, self.format, self.matrix = int(h), int(w), int(format), int(matrix)
+        planes = frame_plane_rows(h, w, self.format)
+        if pitch is None:
+            pitch = [row for _, row in planes]
+        elif np.ndim(pitch) == 0:
+            pitch = [int(pitch)] * len(planes)
+        if offsets is None:
+            offsets, off = [], 0
+            for (rows, _), pt in zip(planes, pitch):
+                offsets.append(off)
+                off += rows * int(pt)
+        if len(pitch) != len(planes) or len(offsets) != len(planes):
+            raise YoloError("Frame: format %d has %d planes, got %d pitches and %d offsets" % (self.format, len(planes), len(pitch), len(offsets)))
+        self.pitch = [int(p) for p in pitch]
+        self.offsets = [int(o) for o in offsets]
+
+    def desc(self, base=0):
+        """the FRAME_DTYPE record of this frame with its data at byte `base` of a packed buffer"""
+        d = np.zeros(1, dtype=FRAME_DTYPE)
+        n = len(self.offsets)
+        d["offset"][0, :n] = [base + o for o in self.offsets]
+        d["pitch"][0, :n] = self.pitch
+        d["h"], d["w"], d["format"], d["matrix"] = self.h, self.w, self.format, self.matrix
+        return d
+
+
+def pack_frames(frames):
+    """A list of Frame -> (packed uint8 buffer, FRAME_DTYPE descriptors): every frame's data back to back in list order, its plane offsets
+    moved by the bytes in front of it; pitches, sizes, formats and matrices as the frames state them.  Pure host code; what
+    yolo_*_frames_* read."""
+    frames = list(frames)
+    if not frames:
+        raise YoloError("pack_frames: no frames")
+    for i, f in enumerate(frames):
+        if not isinstance(f, Frame):
+            raise YoloError("pack_frames: frame %d is %r, not a hip.Frame" % (i, type(f)))
+    descs = np.zeros(len(frames), dtype=FRAME_DTYPE)
+    off = 0
+    for i, f in enumerate(frames):
+        descs[i] = f.desc(off)[0]
+        off += f.data.size
+    return np.concatenate([f.data for f in frames]), descs
+
+
+def _frame_descs(descs):
+    d = np.ascontiguousarray(descs)
+    if d.dtype != FRAME_DTYPE:
+        raise YoloError("frame descriptors: need a FRAME_DTYPE array (pack_frames), got %s" % d.dtype)
+    return d.reshape(-1)
+
+
+def frame_to_rgb(frame, device=None):
+    """The uint8 [h, w, 3] RGB image the colour rule yields for a frame (a Frame, or a (buffer, FRAME_DTYPE record) pair): on the host
+    (yolo_frame_to_rgb_host; no device is touched) or, with `device` an ordinal, by the device operator (yolo_op_frame_to_rgb).  The two
+    agree bit for bit; every fit reads a frame as this image."""
+    l = load_library()
+    if isinstance(frame, Frame):
+        buf, d = frame.data, frame.desc()
+    else:
+        buf, d = frame
+        buf = np.ascontiguousarray(buf).reshape(-1)
+        d = _frame_descs(d)[:1].copy()
+    out = np.zeros((max(int(d["h"][0]), 0), max(int(d["w"][0]), 0), 3), dtype=np.uint8)
+    if device is None:
+        _op_check(l.yolo_frame_to_rgb_host(d.ctypes.data, buf.ctypes.data, buf.size, out.ctypes.data), "yolo_frame_to_rgb_host")
+    else:
+        _op_check(l.yolo_op_frame_to_rgb(d.ctypes.data, buf.ctypes.data, buf.size, out.ctypes.data, int(device)), "yolo_op_frame_to_rgb")
+    return out
 
 
 def fit_unit_value(fit, value):
@@ -647,6 +751,75 @@ class Engine:
         self._order_after_producer(pixels_dev, boxes_out, counts_out)
         self._check(self.lib.yolo_detect_images_graph(self.ctx, p, nbytes, descs.ctypes.data, len(descs), fit, score_thr, iou_thr,
                                                       max_out, nms_mode, select_mode, units, bp, cp), "yolo_detect_images_graph")
+
+    # ---- decoded video frames: NV12 / I420 / pitched RGB / BGR surfaces, converted while they are fitted ----
+    def _packed_frames(self, frames):
+        if isinstance(frames, tuple):
+            buf, descs = frames
+        else:
+            buf, descs = pack_frames(frames)
+        descs = _frame_descs(descs)
+        p, loc = _ptr(buf)
+        nbytes = int(buf.numel()) if hasattr(buf, "numel") else int(buf.nbytes)
+        return buf, descs, p, loc, nbytes
+
+    def forward_frames(self, frames, fit=FIT_STRETCH, want_detections=True):
+        """forward_images over a list of Frame (or a (buffer, descs) pair from pack_frames, the buffer on the host or the device): one
+        launch converts and fits every frame (`fit`: any but FIT_CV2_BGR), then forward.  One batch may mix formats and matrices.  Returns the
+        decoded tensor [n, rows, attrs]."""
+        buf, descs, p, loc, nbytes = self._packed_frames(frames)
+        n = len(descs)
+        self._order_after_producer(buf)
+        det = np.empty((n, self.rows, self.attrs), dtype=np.float32) if want_detections else None
+        self._check(self.lib.yolo_forward_frames_u8(self.ctx, p, nbytes, descs.ctypes.data, n, fit, loc,
+                                                    det.ctypes.data if det is not None else None, HOST), "yolo_forward_frames_u8")
+        return det
+
+    def detect_frames(self, frames, fit=FIT_STRETCH, units=UNITS_NETWORK, score_thr=0.5, iou_thr=0.5, max_out=20, nms_mode=NMS_TF,
+                      select_mode=SELECT_GT, hier_thresh=None):
+        """detect_images over frames (yolo_detect_frames_u8) -> list of BOX_DTYPE arrays; UNITS_SOURCE_PIXELS: in the frame's own pixels."""
+        if hier_thresh is not None:
+            self.set_hier_thresh(hier_thresh)
+        buf, descs, p, loc, nbytes = self._packed_frames(frames)
+        n = len(descs)
+        self._order_after_producer(buf)
+        boxes = np.zeros((n, max_out), dtype=BOX_DTYPE); counts = np.zeros(n, dtype=np.int32)
+        self._check(self.lib.yolo_detect_frames_u8(self.ctx, p, nbytes, descs.ctypes.data, n, fit, loc, score_thr, iou_thr, max_out,
+                                                   nms_mode, select_mode, units, boxes.ctypes.data, counts.ctypes.data, HOST),
+                    "yolo_detect_frames_u8")
+        return [boxes[i, :counts[i]].copy() for i in range(n)]
+
+    def detect_tiled_frames(self, frames, tile=None, overlap=(64, 64), fit=FIT_STRETCH, relative=False, score_thr=0.5, iou_thr=0.5, max_out=20,
+                            nms_mode=NMS_TF, select_mode=SELECT_GT):
+        """detect_tiled over frames (yolo_detect_tiled_frames_u8): every window is converted and fitted straight from the frame it lies in,
+        chroma indexed by the pixel's position in the frame.  Arguments and records as detect_tiled."""
+        buf, descs, p, loc, nbytes = self._packed_frames(frames)
+        n = len(descs)
+        th, tw = (0, 0) if tile is None else _pair(tile, "tile")
+        oh, ow = _pair(overlap, "overlap")
+        self._order_after_producer(buf)
+        boxes = np.zeros((n, max_out), dtype=BOX_DTYPE); counts = np.zeros(n, dtype=np.int32)
+        self._check(self.lib.yolo_detect_tiled_frames_u8(self.ctx, p, nbytes, descs.ctypes.data, n, th, tw, oh, ow, fit, loc, score_thr, iou_thr,
+                                                         max_out, nms_mode, select_mode, 1 if relative else 0, boxes.ctypes.data,
+                                                         counts.ctypes.data, HOST), "yolo_detect_tiled_frames_u8")
+        return [boxes[i, :counts[i]].copy() for i in range(n)]
+
+    def detect_frames_graph(self, pixels_dev, descs, boxes_out, counts_out, fit=FIT_STRETCH, units=UNITS_NETWORK, score_thr=0.5,
+                            iou_thr=0.5, max_out=20, nms_mode=NMS_TF, select_mode=SELECT_GT, nbytes=None, hier_thresh=None):
+        """yolo_detect_frames_graph: detect_images_graph over frames -- pixels_dev a device uint8 tensor holding the surfaces, descs (host,
+        FRAME_DTYPE) where each frame's planes lie this call.  One captured graph, kept apart from detect_images_graph's, serves every
+        call with the same buffers and modes, whatever the frames' sizes, formats and pitches."""
+        if hier_thresh is not None:
+            self.set_hier_thresh(hier_thresh)
+        p, loc = _ptr(pixels_dev); bp, bl = _ptr(boxes_out); cp, cl = _ptr(counts_out)
+        if loc != DEVICE or bl != DEVICE or cl != DEVICE:
+            raise YoloError("detect_frames_graph needs device-resident buffers")
+        descs = _frame_descs(descs)
+        if nbytes is None:
+            nbytes = int(pixels_dev.numel())
+        self._order_after_producer(pixels_dev, boxes_out, counts_out)
+        self._check(self.lib.yolo_detect_frames_graph(self.ctx, p, nbytes, descs.ctypes.data, len(descs), fit, score_thr, iou_thr,
+                                                      max_out, nms_mode, select_mode, units, bp, cp), "yolo_detect_frames_graph")
 
     # ---- classifier networks (a cfg whose output layer is a [softmax]) ----
     @property
