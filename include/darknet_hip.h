@@ -8,7 +8,9 @@
  * through the C ABI of include/yolo_hip.h; this layer marshals darknet's structs and parses its small text files.
  *
  * Differences a caller can observe:
- *   - load_image_color decodes binary PPM / PGM only (the reference uses the vendored stb_image for JPEG / PNG);
+ *   - load_image_color decodes JPEG files bit-equal to the reference's vendored stb_image (sequential Huffman, 8-bit, grey or YCbCr:
+ *     include/yolo_hip.h "JPEG files") and binary PPM / PGM; PNG and the refused JPEG kinds (progressive, CMYK, ...) print why and
+ *     return the empty image;
  *   - do_nms_* leave the array order unchanged (the reference qsorts it in place);
  *   - [region] heads are served in their softmax form or with a softmax tree (`tree=`, YOLO9000): get_network_boxes honours
  *     hier_thresh and map for the latter (no mask coefficients, no background=1).  A tree head follows the reference's GPU path,
@@ -50,7 +52,7 @@ void do_nms_obj(detection *dets, int total, int classes, float thresh);  /* DN/b
 image make_image(int w, int h, int c);                                   /* DN/image.c:798 */
 void free_image(image m);
 image letterbox_image(image im, int w, int h);                           /* DN/image.c:960-981 */
-image load_image_color(char *filename, int w, int h);                    /* DN/image.c:1482 (PPM / PGM) */
+image load_image_color(char *filename, int w, int h);                    /* DN/image.c:1482 (JPEG / PPM / PGM) */
 void rgbgr_image(image im);                                              /* DN/image.c:527 */
 metadata get_metadata(char *file);                                       /* DN/option_list.c:35 */
 

@@ -288,7 +288,9 @@ int yolo_detect_tiled_u8(yolo_ctx *ctx, const uint8_t *pixels, size_t bytes, con
  * From there on a frame IS the h x w x 3 byte image this rule yields: every fit reads it exactly as it reads a packed RGB image
  * (yolo_fit_unit_value, the /255, darknet's two-pass resize_image, the cv2 rule, [net] yolo_input_mul / yolo_input_add), host and device
  * evaluate the rule identically, and no RGB copy of the frame is ever stored.  64 bytes. */
-enum yolo_pix_format { YOLO_PIX_NV12 = 0, YOLO_PIX_I420 = 1, YOLO_PIX_RGB24 = 2, YOLO_PIX_BGR24 = 3 };
+enum yolo_pix_format { YOLO_PIX_NV12 = 0, YOLO_PIX_I420 = 1, YOLO_PIX_RGB24 = 2, YOLO_PIX_BGR24 = 3,
+                       /* the component planes of a decoded JPEG file (below, "JPEG files"); 4 .. 15 are no format */
+                       YOLO_PIX_JPEG_GREY = 16, YOLO_PIX_JPEG_444 = 17, YOLO_PIX_JPEG_422 = 18, YOLO_PIX_JPEG_420 = 19, YOLO_PIX_JPEG_440 = 20 };
 enum yolo_color_matrix { YOLO_MATRIX_BT601 = 0, YOLO_MATRIX_BT709 = 1, YOLO_MATRIX_BT601_FULL = 2 };
 typedef struct yolo_frame_desc {
     uint64_t offset[3];        /* where each plane begins in the packed buffer */
@@ -326,6 +328,70 @@ int yolo_detect_tiled_frames_u8(yolo_ctx *ctx, const uint8_t *pixels, size_t byt
                                 int tile_h, int tile_w, int overlap_h, int overlap_w, int fit, int loc,
                                 float score_thr, float iou_thr, int max_out, int nms_mode, int select_mode, int relative,
                                 yolo_box *boxes_out, int32_t *counts_out, int out_loc);
+
+/* ---- JPEG files: what darknet's load_image reads through its vendored stb_image (DN/image.c load_image_stb) ----
+ * The host parses the file and Huffman-decodes it to dequantised coefficient blocks; the device does the rest: one IDCT launch per
+ * batch writes the component planes (uint8, whole MCUs: plane_w x plane_h) into a surface the context owns, and a decoded file is
+ * then a FRAME over those planes, in one of five formats that carry the reference's integer rule with them:
+ *   YOLO_PIX_JPEG_GREY  plane 0: Y, h rows of w bytes; R = G = B = Y
+ *   YOLO_PIX_JPEG_444   planes 0, 1, 2: Y, Cb, Cr, each h rows of w bytes
+ *   YOLO_PIX_JPEG_422   Y as above; Cb, Cr: h rows of ceil(w / 2) bytes
+ *   YOLO_PIX_JPEG_420   Y as above; Cb, Cr: ceil(h / 2) rows of ceil(w / 2) bytes
+ *   YOLO_PIX_JPEG_440   Y as above; Cb, Cr: ceil(h / 2) rows of w bytes
+ * (any pitch at least the row's bytes, as for the other formats).  Pixel (y, x) takes its chroma through the reference's upsamplers
+ * (stbi__resample_row_h_2 / _hv_2 / _v_2: 3:1 linear interpolation with their edge cases, rows clamped to the component's own), indexed by
+ * the pixel's position in the frame, and its colour through stbi__YCbCr_to_RGB_row; kernels.h states both as closed forms.  The
+ * `matrix` field of such a frame must be 0: it selects nothing.  The result is bit-equal to load_image's bytes.
+ * Served: baseline and extended sequential Huffman (SOF0, SOF1), 8-bit, one scan; 1 component, or 3 components as YCbCr with luma
+ * sampled 1x1, 2x1, 2x2 or 1x2 and chroma 1x1; any size, any restart interval, 8- and 16-bit quantisation tables.  APPn / COM segments
+ * are skipped, EXIF orientation is ignored as the reference ignores it.  YOLO_ERR_UNSUPPORTED, naming the file's index and the
+ * feature: progressive, arithmetic-coded, lossless, hierarchical or 12-bit files, 4 components (CMYK / YCCK), 3 components stored
+ * as RGB (component ids R, G, B, or Adobe APP14 transform 0 without JFIF), any other sampling, several scans.
+ * YOLO_ERR_INVALID, naming the file's index and the byte offset: anything malformed or truncated (the reference decodes a truncated
+ * file as if zero bits followed; this library refuses it). */
+struct yolo_jpeg_info {        /* (a tag, no typedef: the function below has the name, as stat(2) and struct stat share theirs) */
+    int32_t h, w;
+    int32_t components;        /* 1 or 3 */
+    int32_t hs, vs;            /* the luma sampling factors; chroma is 1 x 1 */
+    int32_t format;            /* the YOLO_PIX_JPEG_* of its frame */
+    int32_t restart_interval;  /* MCUs, 0: none */
+    int32_t mcus_w, mcus_h;
+    int32_t plane_w[3], plane_h[3];   /* the padded component planes the IDCT writes: whole MCUs (0 for the planes a grey file lacks) */
+    int32_t blocks[3];         /* 8 x 8 blocks of every plane */
+};
+/* The headers of one file: host only; the text of a refusal in yolo_last_error(NULL), "file 0: ...". */
+int yolo_jpeg_info(const uint8_t *file, size_t bytes, struct yolo_jpeg_info *out);
+/* The host stage by itself: the dequantised coefficient blocks of the file, coef_out [blocks[0] + blocks[1] + blocks[2]][64] int16 in
+ * natural (de-zigzagged) order, plane by plane, each plane's blocks in raster order -- what the IDCT kernel reads, and what the
+ * reference hands to its IDCT (the wrap to 16 bits of its dequantising multiply included).  cap_blocks: the room in coef_out. */
+int yolo_jpeg_coefficients(const uint8_t *file, size_t bytes, int16_t *coef_out, size_t cap_blocks);
+/* The whole decode on the host, no context and no device: rgb_out [h][w][3] uint8, cap its size in bytes (YOLO_ERR_INVALID when
+ * below h * w * 3).  The CPU anchor of the rule, and what libdarknet_hip.so's load_image reads JPEG files with. */
+int yolo_jpeg_to_rgb_host(const uint8_t *file, size_t bytes, uint8_t *rgb_out, size_t cap);
+/* The same through the device (host buffers; rgb_out holds h * w * 3 bytes): host entropy stage, the IDCT kernel, then the
+ * frame-to-RGB operator over its planes. */
+int yolo_op_jpeg_to_rgb(const uint8_t *file, size_t bytes, uint8_t *rgb_out, int device);
+/* files[i] of bytes[i] bytes, i < n (any n >= 1) -> a frame table over the context's surface.  The batch is entropy-decoded by
+ * min(n, 8) host threads into pinned memory, uploaded once and transformed by one launch on the context stream.  descs_out[n]
+ * (host) describes every file's planes inside *device_pixels (device memory) of *device_bytes bytes -- the surface's capacity, so
+ * that batches of different sizes present the same buffer to yolo_detect_frames_graph --: pass the three to any yolo_*_frames_*
+ * entry point with loc = YOLO_DEVICE.  Table and surface are valid until the next decode on this context; a decode that needs a
+ * larger surface moves it.  Every refusal comes before the first launch and names the file. */
+int yolo_decode_jpegs(yolo_ctx *ctx, const uint8_t *const *files, const size_t *bytes, int n, yolo_frame_desc *descs_out,
+                      const uint8_t **device_pixels, size_t *device_bytes);
+/* What the last decode on this context cost (waits for its IDCT): the host's entropy stage in wall-clock ms, the upload and the IDCT
+ * launch in device ms between events on the context stream, and the bytes uploaded.  Any pointer may be NULL.  tools/jpeg_rate.py. */
+int yolo_jpeg_decode_times(yolo_ctx *ctx, double *entropy_ms, double *upload_ms, double *idct_ms, size_t *upload_bytes);
+/* yolo_decode_jpegs, then yolo_forward_frames_u8 / yolo_detect_frames_u8 / yolo_detect_tiled_frames_u8 over its table: the
+ * arguments of those, with (files, bytes, n) in the place of the packed buffer, its descriptors and its location. */
+int yolo_forward_jpegs(yolo_ctx *ctx, const uint8_t *const *files, const size_t *bytes, int n, int fit, float *detections_out, int out_loc);
+int yolo_detect_jpegs(yolo_ctx *ctx, const uint8_t *const *files, const size_t *bytes, int n, int fit,
+                      float score_thr, float iou_thr, int max_out, int nms_mode, int select_mode, int units,
+                      yolo_box *boxes_out, int32_t *counts_out, int out_loc);
+int yolo_detect_tiled_jpegs(yolo_ctx *ctx, const uint8_t *const *files, const size_t *bytes, int n_images,
+                            int tile_h, int tile_w, int overlap_h, int overlap_w, int fit,
+                            float score_thr, float iou_thr, int max_out, int nms_mode, int select_mode, int relative,
+                            yolo_box *boxes_out, int32_t *counts_out, int out_loc);
 
 /* darknet's get_network_boxes on the device (DN/network.c:536-567 = num_detections + fill_network_boxes ->
  * get_yolo_detections DN/yolo_layer.c:316-343 / get_region_detections DN/region_layer.c:364-437 (softmax heads, no tree),

@@ -261,12 +261,42 @@ void rgbgr_image(image im)                                                      
     for (size_t i = 0; i < n; ++i) { const float t = im.data[i]; im.data[i] = im.data[i + 2 * n]; im.data[i + 2 * n] = t; }
 }
 
-// DN/image.c:1442-1485 (load_image_stb + optional resize_image).  Binary PPM (P6) and PGM (P5) only, 8 bits per sample.
+// the bytes / 255. as darknet's planar image (DN/image.c:1458), resized by darknet's resize_image on the device when a size is given (DN/image.c:1475-1479)
+static image planar_image(const unsigned char *raw, int iw, int ih, int ch, int w, int h)
+{
+    image im = make_image(iw, ih, 3);
+    const size_t n = (size_t)iw * ih;
+    for (int k = 0; k < 3; ++k)
+        for (size_t i = 0; i < n; ++i) im.data[k * n + i] = (float)raw[i * ch + (ch == 3 ? k : 0)] / 255.;       /* DN/image.c:1458 */
+    if (h && w && (h != im.h || w != im.w)) {
+        image r = make_image(w, h, 3);
+        if (yolo_op_letterbox(im.data, im.w, im.h, w, h, 0, r.data, g_device) != YOLO_OK) fprintf(stderr, "darknet_hip: resize: %s\n", yolo_last_error(NULL));
+        free_image(im); im = r;
+    }
+    return im;
+}
+
+// DN/image.c:1442-1485 (load_image_stb + optional resize_image).  JPEG files of the kinds yolo_jpeg_to_rgb_host serves (bit-equal to the reference's stb decode),
+// binary PPM (P6) and PGM (P5) of 8 bits per sample.  Anything else -- PNG, the refused JPEG kinds -- prints why and returns the empty image.
 image load_image_color(char *filename, int w, int h)
 {
     image bad = {0, 0, 0, nullptr};
     FILE *f = filename ? fopen(filename, "rb") : nullptr;
     if (!f) { fprintf(stderr, "darknet_hip: cannot load image \"%s\"\n", filename ? filename : "(null)"); return bad; }
+    unsigned char soi[2] = {0, 0};
+    const bool jpeg = fread(soi, 1, 2, f) == 2 && soi[0] == 0xff && soi[1] == 0xd8;
+    rewind(f);
+    if (jpeg) {
+        std::vector<unsigned char> file;
+        unsigned char chunk[65536];
+        for (size_t got; (got = fread(chunk, 1, sizeof chunk, f)) > 0;) file.insert(file.end(), chunk, chunk + got);
+        fclose(f);
+        struct yolo_jpeg_info info;
+        if (yolo_jpeg_info(file.data(), file.size(), &info) != YOLO_OK) { fprintf(stderr, "darknet_hip: \"%s\": %s\n", filename, yolo_last_error(NULL)); return bad; }
+        std::vector<unsigned char> rgb((size_t)info.h * info.w * 3);
+        if (yolo_jpeg_to_rgb_host(file.data(), file.size(), rgb.data(), rgb.size()) != YOLO_OK) { fprintf(stderr, "darknet_hip: \"%s\": %s\n", filename, yolo_last_error(NULL)); return bad; }
+        return planar_image(rgb.data(), info.w, info.h, 3, w, h);
+    }
     auto token = [&](std::string &t) {
         t.clear(); int ch;
         for (;;) {
@@ -279,7 +309,7 @@ image load_image_color(char *filename, int w, int h)
     };
     std::string magic, sw, sh, smax;
     if (!token(magic) || (magic != "P6" && magic != "P5") || !token(sw) || !token(sh) || !token(smax) || atoi(smax.c_str()) != 255) {
-        fclose(f); fprintf(stderr, "darknet_hip: \"%s\" is not an 8-bit binary PPM/PGM (JPEG/PNG decoding is outside the inference path: convert the image first)\n", filename); return bad;
+        fclose(f); fprintf(stderr, "darknet_hip: \"%s\" is neither a JPEG file nor an 8-bit binary PPM/PGM (PNG decoding is outside the inference path: convert the image first)\n", filename); return bad;
     }
     const int iw = atoi(sw.c_str()), ih = atoi(sh.c_str()), ch = magic == "P6" ? 3 : 1;
     if (iw < 1 || ih < 1 || (long)iw * ih > (1L << 28)) { fclose(f); return bad; }
@@ -287,16 +317,7 @@ image load_image_color(char *filename, int w, int h)
     const bool ok = fread(raw.data(), 1, raw.size(), f) == raw.size();
     fclose(f);
     if (!ok) { fprintf(stderr, "darknet_hip: short read on \"%s\"\n", filename); return bad; }
-    image im = make_image(iw, ih, 3);
-    const size_t n = (size_t)iw * ih;
-    for (int k = 0; k < 3; ++k)
-        for (size_t i = 0; i < n; ++i) im.data[k * n + i] = (float)raw[i * ch + (ch == 3 ? k : 0)] / 255.;       /* DN/image.c:1458 */
-    if (h && w && (h != im.h || w != im.w)) {
-        image r = make_image(w, h, 3);
-        if (yolo_op_letterbox(im.data, im.w, im.h, w, h, 0, r.data, g_device) != YOLO_OK) fprintf(stderr, "darknet_hip: resize: %s\n", yolo_last_error(NULL));
-        free_image(im); im = r;
-    }
-    return im;
+    return planar_image(raw.data(), iw, ih, ch, w, h);
 }
 
 // DN/option_list.c:35-50 + get_labels DN/data.c:618: `classes = N`, `names = path` (or `labels = path`); one class name per line

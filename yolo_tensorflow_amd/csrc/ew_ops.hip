@@ -882,6 +882,8 @@ struct AtFrame {
     __device__ __forceinline__ unsigned byte_at(unsigned off) const { return (unsigned)__builtin_amdgcn_raw_buffer_load_b8(rsrc, off, 0, 0); }
     __device__ __forceinline__ void rgb(int y, int x, int *v) const
     {
+        // a decoded JPEG file: luma direct, chroma through the reference's upsampler at the pixel's position in the frame, the reference's colour step (kernels.h)
+        if (pix_is_jpeg(f.format)) { jpeg_frame_rgb(f, y0 + y, x0 + x, [&](unsigned off) { return (int)byte_at(off); }, v); return; }
         unsigned o[3];
         frame_sample_offsets(f, y0 + y, x0 + x, o);
         const int a = (int)byte_at(o[0]), b = (int)byte_at(o[1]), c = (int)byte_at(o[2]);
@@ -974,7 +976,7 @@ __global__ __launch_bounds__(256) void k_frame_to_rgb(const uint8_t *pixels, uns
 }
 hipError_t launch_frame_to_rgb(const uint8_t *pixels, size_t bytes, const FrameDesc &frame, uint8_t *out, hipStream_t s)
 {
-    if (frame.h < 1 || frame.w < 1 || bytes > 0xffffffffull || frame.format < 0 || frame.format >= PIX_COUNT || frame.matrix < 0 || frame.matrix >= MATRIX_COUNT) return hipErrorInvalidValue;
+    if (frame.h < 1 || frame.w < 1 || bytes > 0xffffffffull || frame.format < 0 || (frame.format >= PIX_COUNT && !pix_is_jpeg(frame.format)) || frame.matrix < 0 || frame.matrix >= MATRIX_COUNT) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_frame_to_rgb, grid_for((size_t)frame.h * frame.w), dim3(256), 0, s, pixels, (unsigned)bytes, frame, out);
     return hipGetLastError();
 }

@@ -515,6 +515,104 @@ __host__ __device__ inline void yuv_to_rgb(const ColorMatrix &m, int Y, int U, i
     rgb[1] = clamp8((y - m.cug * u - m.cvg * v + (1 << 19)) >> 20);
     rgb[2] = clamp8((y + m.cub * u + (1 << 19)) >> 20);
 }
+// ---- JPEG files (yolo_*_jpegs, yolo_decode_jpegs): the reference reads a JPEG through its vendored stb_image (DN/image.c load_image_stb), whose
+// IDCT, chroma upsampling and colour step are integer arithmetic.  The three are restated here, once, for the host twin (yolo_jpeg_to_rgb_host), the IDCT kernel
+// (k_jpeg_idct, jpeg_ops.hip) and the frame reader (AtFrame, ew_ops.hip): the bar is bit equality with the compiled reference.  A decoded file is a frame whose
+// planes are the component planes the IDCT writes: Y, then Cb and Cr at full size (444), half width (422), half width and height (420) or half height (440); GREY
+// has Y alone.
+// The formats carry their colour rule with them: the matrix of such a frame must be 0 and selects nothing.
+enum { PIX_JPEG_GREY = 16, PIX_JPEG_444 = 17, PIX_JPEG_422 = 18, PIX_JPEG_420 = 19, PIX_JPEG_440 = 20 };
+__host__ __device__ inline bool pix_is_jpeg(int format) { return format >= PIX_JPEG_GREY && format <= PIX_JPEG_440; }
+// rows and bytes per row the chroma planes of an h x w JPEG frame must have (the component's own size, T.81 A.1.1: ceil(h * v / v_max) x ceil(w * h / h_max))
+__host__ __device__ inline int jpeg_chroma_rows(int format, int h) { return format == PIX_JPEG_420 || format == PIX_JPEG_440 ? (h + 1) >> 1 : h; }
+__host__ __device__ inline int jpeg_chroma_cols(int format, int w) { return format == PIX_JPEG_444 || format == PIX_JPEG_440 ? w : (w + 1) >> 1; }
+// One 8-point pass of the reference's IDCT (stb_image.h:2163-2202 STBI__IDCT_1D, "derived from jidctint"; the constants are its stbi__f2f(k) = (int)(k * 4096 + 0.5)).
+// With x0..x3 the even part plus the pass's rounding `bias` and t0..t3 the odd part: out[k] = (x[k] + t[3 - k]) >> shift, out[7 - k] = (x[k] - t[3 - k]) >> shift.
+// Evaluated in unsigned so that coefficients no encoder writes wrap as on the reference's machine instead of overflowing an int.
+__host__ __device__ inline void jpeg_idct_1d(const int *s, int bias, int shift, int *out)
+{
+    typedef unsigned U;
+    U p2 = (U)s[2], p3 = (U)s[6];
+    U p1 = (p2 + p3) * (U)2217;
+    U t2 = p1 + p3 * (U)-7567, t3 = p1 + p2 * (U)3135;
+    p2 = (U)s[0]; p3 = (U)s[4];
+    U t0 = (p2 + p3) * 4096u, t1 = (p2 - p3) * 4096u;
+    const U x0 = t0 + t3 + (U)bias, x3 = t0 - t3 + (U)bias, x1 = t1 + t2 + (U)bias, x2 = t1 - t2 + (U)bias;
+    t0 = (U)s[7]; t1 = (U)s[5]; t2 = (U)s[3]; t3 = (U)s[1];
+    p3 = t0 + t2;
+    U p4 = t1 + t3;
+    p1 = t0 + t3; p2 = t1 + t2;
+    const U p5 = (p3 + p4) * (U)4816;
+    t0 *= (U)1223; t1 *= (U)8410; t2 *= (U)12586; t3 *= (U)6149;
+    p1 = p5 + p1 * (U)-3685; p2 = p5 + p2 * (U)-10497; p3 *= (U)-8034; p4 *= (U)-1597;
+    t3 += p1 + p4; t2 += p2 + p3; t1 += p2 + p4; t0 += p1 + p3;
+    out[0] = (int)(x0 + t3) >> shift; out[7] = (int)(x0 - t3) >> shift;
+    out[1] = (int)(x1 + t2) >> shift; out[6] = (int)(x1 - t2) >> shift;
+    out[2] = (int)(x2 + t1) >> shift; out[5] = (int)(x2 - t1) >> shift;
+    out[3] = (int)(x3 + t0) >> shift; out[4] = (int)(x3 - t0) >> shift;
+}
+// the column pass keeps two extra bits (+512, >> 10); the row pass removes 17 bits, rounds, and adds the level shift 128 before it (stb_image.h:2225-2259).  The
+// reference's all-zero-AC shortcut of the column pass (d[0] * 4) is what the general form yields for such a column: no special case is needed
+enum { JPEG_IDCT_COL_BIAS = 512, JPEG_IDCT_COL_SHIFT = 10, JPEG_IDCT_ROW_BIAS = 65536 + (128 << 17), JPEG_IDCT_ROW_SHIFT = 17 };
+// one dequantised block (natural order) -> 8 rows of 8 samples at `stride`
+__host__ __device__ inline void jpeg_idct_block(const int16_t *d, uint8_t *out, size_t stride)
+{
+    int v[64], s[8], o[8];
+    for (int c = 0; c < 8; ++c) {
+        for (int r = 0; r < 8; ++r) s[r] = d[8 * r + c];
+        jpeg_idct_1d(s, JPEG_IDCT_COL_BIAS, JPEG_IDCT_COL_SHIFT, o);
+        for (int r = 0; r < 8; ++r) v[8 * r + c] = o[r];
+    }
+    for (int r = 0; r < 8; ++r) {
+        jpeg_idct_1d(v + 8 * r, JPEG_IDCT_ROW_BIAS, JPEG_IDCT_ROW_SHIFT, o);
+        for (int c = 0; c < 8; ++c) out[r * stride + c] = (uint8_t)clamp8(o[c]);
+    }
+}
+// The chroma sample of pixel (y, x) of an h x w frame, from a component plane read through at(row, col) (stb_image.h:3183-3235 stbi__resample_row_h_2 and
+// stbi__resample_row_hv_2, and the row bookkeeping of load_jpeg_image :3611-3645, as closed forms).  With wl = ceil(w / 2) samples in a plane row:
+//   422  wl == 1: s[0].  x == 0: s[0];  x == 2 wl - 1: s[wl - 1];  x == 2 wl - 2: (3 s[wl - 2] + s[wl - 1] + 2) >> 2 -- the reference's last pair weighs the
+//        NEIGHBOUR by 3 --;  else, i = x >> 1: (3 s[i] + s[x odd ? i + 1 : i - 1] + 2) >> 2
+//   420  the near row is y >> 1, the far row (y >> 1) + 1 for odd y, - 1 for even y, clamped to 0 .. ceil(h / 2) - 1 (the component's rows, not the padded plane's);
+//        t[i] = 3 near[i] + far[i].  wl == 1, x == 0 or x == 2 wl - 1: (t[x >> 1] + 2) >> 2;  else, i = x >> 1: (3 t[i] + t[x odd ? i + 1 : i - 1] + 8) >> 4
+//   440  (stbi__resample_row_v_2, :3173-3181) the same near and far rows at full width: (3 near[x] + far[x] + 2) >> 2
+template <typename At>
+__host__ __device__ inline int jpeg_chroma(int format, int h, int w, int y, int x, const At &at)
+{
+    if (format == PIX_JPEG_444) return at(y, x);
+    const int wl = (w + 1) >> 1, i = x >> 1, o = (x & 1) ? i + 1 : i - 1;
+    if (format == PIX_JPEG_422) {
+        if (wl == 1 || x == 0) return at(y, 0);
+        if (i == wl - 1) return (x & 1) ? at(y, i) : (3 * at(y, i - 1) + at(y, i) + 2) >> 2;
+        return (3 * at(y, i) + at(y, o) + 2) >> 2;
+    }
+    const int rows = (h + 1) >> 1, near = y >> 1, f = (y & 1) ? near + 1 : near - 1, far = f < 0 ? 0 : f > rows - 1 ? rows - 1 : f;
+    if (format == PIX_JPEG_440) return (3 * at(near, x) + at(far, x) + 2) >> 2;
+    const int t = 3 * at(near, i) + at(far, i);
+    if (wl == 1 || x == 0 || x == 2 * wl - 1) return (t + 2) >> 2;
+    return (3 * t + 3 * at(near, o) + at(far, o) + 8) >> 4;
+}
+// R, G, B of one (Y, Cb, Cr) sample (stb_image.h:3367-3391 stbi__YCbCr_to_RGB_row): 12-bit constants (int)(k * 4096 + 0.5) of 1.402, 0.71414, 0.34414, 1.772 shifted
+// left by 8, and the Cb term of green with its low 16 bits masked off (how the reference's SIMD and scalar paths are kept equal)
+__host__ __device__ inline void jpeg_ycc_to_rgb(int Y, int Cb, int Cr, int *rgb)
+{
+    const int yf = (Y << 20) + (1 << 19), cr = Cr - 128, cb = Cb - 128;
+    rgb[0] = clamp8((yf + cr * 1470208) >> 20);
+    rgb[1] = clamp8((yf + cr * -748800 + (int)((unsigned)(cb * -360960) & 0xffff0000u)) >> 20);
+    rgb[2] = clamp8((yf + cb * 1858048) >> 20);
+}
+// R, G, B of pixel (y, x) of a JPEG frame whose bytes are read through byte(offset); GREY repeats Y (stb_image.h:3683-3685)
+template <typename Byte>
+__host__ __device__ inline void jpeg_frame_rgb(const FrameDesc &f, int y, int x, const Byte &byte, int *rgb)
+{
+    const int Y = byte((unsigned)f.offset[0] + (unsigned)y * (unsigned)f.pitch[0] + (unsigned)x);
+    if (f.format == PIX_JPEG_GREY) { rgb[0] = rgb[1] = rgb[2] = Y; return; }
+    int c[2];
+    for (int p = 1; p <= 2; ++p) {
+        const unsigned base = (unsigned)f.offset[p], pitch = (unsigned)f.pitch[p];
+        c[p - 1] = jpeg_chroma(f.format, f.h, f.w, y, x, [&](int r, int col) { return byte(base + (unsigned)r * pitch + (unsigned)col); });
+    }
+    jpeg_ycc_to_rgb(Y, c[0], c[1], rgb);
+}
 // byte offsets of the samples of pixel (y, x) of a frame: chroma is taken from (y >> 1, x >> 1) of the FRAME (nearest, no interpolation).  NV12 / I420: o[0] Y, o[1] U,
 // o[2] V; RGB24 / BGR24: o[c] the byte of output channel c (BGR swaps 0 and 2)
 __host__ __device__ inline void frame_sample_offsets(const FrameDesc &f, int y, int x, unsigned *o)
@@ -538,6 +636,11 @@ hipError_t launch_fit_frame_windows(const uint8_t *pixels, size_t bytes, const F
                                     void *out, int out_dt, int out_stride, float post_mul, float post_add, hipStream_t s);
 // one frame -> the [h][w][3] uint8 image of the colour rule (yolo_op_frame_to_rgb)
 hipError_t launch_frame_to_rgb(const uint8_t *pixels, size_t bytes, const FrameDesc &frame, uint8_t *out, hipStream_t s);
+// JPEG files: one component plane of one file of a batch -- blocks block0 .. of the batch's coefficient array are its 8 x 8 blocks in raster order, bw across; the
+// plane begins at byte `offset` of the surface (a multiple of 8) with rows `pitch` bytes apart (a multiple of 8, >= 8 bw).  The table is sorted by block0
+struct JpegPlane { unsigned block0, bw, offset, pitch; };
+// the IDCT of a whole batch in one launch (jpeg_ops.hip): coef [blocks][64] int16, dequantised, natural order (16-byte aligned) -> every plane of the table
+hipError_t launch_jpeg_idct(const int16_t *coef, const JpegPlane *d_planes, int nplanes, size_t blocks, uint8_t *out, size_t out_bytes, hipStream_t s);
 hipError_t launch_upsample2x(const TView &in, const TView &out, int bilinear, hipStream_t s);
 hipError_t launch_maxpool(const TView &in, const TView &out, int size, int stride, int pad, hipStream_t s);
 hipError_t launch_reorg(const TView &in, const TView &out, int stride, int darknet, hipStream_t s);

@@ -87,6 +87,10 @@ void yolo_destroy(yolo_ctx *c)
     for (void *p : ptrs) if (p) hipFree(p);
     for (auto &t : c->trees) free_tree(t);
     if (c->d_map200) hipFree(c->d_map200);
+    for (void *p : {c->d_jin, (void *)c->d_jpeg}) if (p) hipFree(p);
+    if (c->h_jin) hipHostFree(c->h_jin);
+    if (c->jpeg_up) hipEventDestroy(c->jpeg_up);
+    for (hipEvent_t ev : c->jpeg_t) if (ev) hipEventDestroy(ev);
     drop_graph(c);
     if (c->own_stream && c->stream) hipStreamDestroy(c->stream);
     delete c;

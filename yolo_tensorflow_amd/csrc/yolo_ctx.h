@@ -7,6 +7,7 @@
 #pragma once
 #include "../../include/yolo_hip.h"
 #include "kernels.h"
+#include "yolo_jpeg.h"
 
 #include <algorithm>
 #include <cmath>
@@ -167,6 +168,17 @@ struct yolo_ctx {
     // decoded video frames (yolo_*_frames_*): the frame table [max_batch] (device) the fit launch reads; d_descs then holds {plane 0's offset, h, w} of the same
     // frames, so the box mapping reads what it reads for images.  h_geom: the host side of that copy, kept here so that it outlives the asynchronous upload
     FrameDesc *d_frames = nullptr; std::vector<ImgDesc> h_geom;
+    // JPEG files (yolo_decode_jpegs): the batch being decoded -- parsed headers, its frame table over the surface, the IDCT's plane table, where
+    // each file's blocks begin --; h_jin: pinned staging of {plane table, coefficients}, d_jin: its device copy, d_jpeg: the surface of component planes the
+    // frame table describes (all three grown on demand, never shrunk; the surface in steps of 4 MiB, so that batches of like size present one buffer to the captured
+    // frames step).  jpeg_up: recorded behind the upload; the next decode waits for it before it overwrites the staging
+    struct JpegBatch {
+        std::vector<yolo_impl::JpegFile> files; std::vector<yolo_frame_desc> descs; std::vector<JpegPlane> planes; std::vector<size_t> first_block;
+        size_t blocks = 0, surface = 0, view_bytes = 0;
+    } jpeg;
+    void *h_jin = nullptr, *d_jin = nullptr; size_t jin_cap = 0; uint8_t *d_jpeg = nullptr; size_t jpeg_cap = 0; hipEvent_t jpeg_up = nullptr; bool jpeg_up_pending = false;
+    // what the last decode cost (yolo_jpeg_decode_times): wall time of the entropy stage, bytes uploaded, events in front of the upload, behind it, behind the IDCT
+    hipEvent_t jpeg_t[3] = {nullptr, nullptr, nullptr}; double jpeg_entropy_ms = 0; size_t jpeg_upload_bytes = 0;
     // tiled detection (yolo_detect_tiled_u8): ONE allocation, grown on demand and never shrunk, that holds the window table, the image table, every
     // image's merged candidate list and k_nms_image's workspace over those lists (tile_slab, yolo_run.cpp)
     void *d_tile = nullptr; size_t tile_cap = 0;
@@ -300,6 +312,9 @@ int post(yolo_ctx *c, const float *det, int n, int rows, int attrs, float score_
          const PostGeom *geom = nullptr);
 // decoded video frames: YOLO_OK, or YOLO_ERR_INVALID with what is wrong with frame `i`'s descriptor inside a packed buffer of `bytes` bytes in `msg` (yolo_run.cpp)
 int frame_desc_check(const yolo_frame_desc &d, size_t bytes, int i, std::string &msg);
+// JPEG files: a parsed file's planes behind `surface` bytes of a surface and its blocks behind `block` blocks of a coefficient array -> its frame descriptor and
+// its f.comps rows of the IDCT's table; both ends advance (yolo_run.cpp)
+void jpeg_place(const JpegFile &f, size_t &surface, size_t &block, yolo_frame_desc *desc, JpegPlane *rows);
 // yolo_api.cpp: map networks
 int need_map(yolo_ctx *c, const char *what);      // YOLO_ERR_INVALID with a message for a detector or a classifier context
 int map_to_f32(yolo_ctx *c, int n);

@@ -1,0 +1,47 @@
+// JPEG files, host stage: marker parsing and Huffman entropy decoding of sequential 8-bit JPEG (ITU-T T.81), down to the
+// DEQUANTISED coefficient blocks.  Everything behind that -- IDCT, chroma upsampling, colour -- is the rule of kernels.h, evaluated by
+// the device (k_jpeg_idct, AtFrame) and by the host twin alike.  Plain C++: no HIP, no context; compiles alone for the sanitizer run
+// of tests/c/jpeg_malformed.cpp.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+#include <string>
+
+namespace yolo_impl {
+
+// a canonical Huffman table (T.81 annex C) with a 9-bit first-level lookup
+struct JpegHuff {
+    bool set = false;
+    uint8_t vals[256];
+    uint16_t look[512];        // (length << 8) | symbol of every code of at most 9 bits, 0: longer
+    int32_t maxcode[18];       // largest code of each length, left-aligned to 16 bits, + 1; [17] ends every search
+    int32_t delta[17];         // index of the first value of a length minus its first code
+};
+
+// one file after its headers: geometry, tables, where the entropy-coded segment begins
+struct JpegFile {
+    int h = 0, w = 0, comps = 0, hs = 1, vs = 1;     // (hs, vs): the luma sampling; chroma is 1 x 1.  Grey: 1 x 1 whatever the file states
+    int format = 0;                                  // YOLO_PIX_JPEG_*
+    int restart = 0;                                 // MCUs per restart interval, 0: none
+    int mcux = 0, mcuy = 0;                          // MCUs across and down
+    int bw[3] = {0, 0, 0}, bh[3] = {0, 0, 0};        // blocks across and down every component plane (whole MCUs); the plane is 8 bw x 8 bh bytes
+    size_t block0[3] = {0, 0, 0}, blocks = 0;        // first block of every plane in the coefficient array (plane by plane, row-major), and their count
+    size_t scan = 0;                                 // byte offset of the entropy-coded segment
+    int tq[3] = {0, 0, 0}, td[3] = {0, 0, 0}, ta[3] = {0, 0, 0};
+    uint16_t quant[4][64];                           // natural (de-zigzagged) order
+    bool qset[4] = {false, false, false, false};
+    JpegHuff dc[4], ac[4];
+};
+
+// headers of file `index` of a batch: YOLO_OK, YOLO_ERR_UNSUPPORTED (a kind of JPEG that is not served: msg names the file and the feature) or
+// YOLO_ERR_INVALID (malformed or truncated: msg names the file and the byte offset)
+int jpeg_parse(const uint8_t *file, size_t bytes, int index, JpegFile *out, std::string &msg);
+// the entropy-coded segment of a parsed file -> coef[f.blocks][64] int16, dequantised, natural order: exactly what the reference hands to its IDCT,
+// its wrap to 16 bits on the dequantising multiply included (stb_image.h stbi__jpeg_decode_block).  YOLO_OK or YOLO_ERR_INVALID
+int jpeg_decode(const uint8_t *file, size_t bytes, int index, const JpegFile &f, int16_t *coef, std::string &msg);
+
+// a parsed batch: file i into coef + first_block[i] * 64, by min(n, 8) threads that take one file at a time each (one thread, the caller's, when n == 1; the
+// pool is never sized from the machine's processor count).  The failure of the lowest index is the one reported
+int jpeg_decode_batch(const uint8_t *const *files, const size_t *bytes, int n, const JpegFile *parsed, const size_t *first_block, int16_t *coef, std::string &msg);
+
+}  // namespace yolo_impl

@@ -554,6 +554,31 @@ int yolo_op_frame_to_rgb(const yolo_frame_desc *desc, const uint8_t *pixels, siz
     return S.download(rgb_out, d_o, out_bytes);
 }
 
+// one JPEG file through the device stages: host entropy decode, k_jpeg_idct into a surface of its planes, k_frame_to_rgb over the frame those planes are
+int yolo_op_jpeg_to_rgb(const uint8_t *file, size_t bytes, uint8_t *rgb_out, int device)
+{
+    if (!file || !rgb_out) { g_op_err = "jpeg_to_rgb: file / rgb_out == NULL"; return YOLO_ERR_INVALID; }
+    JpegFile jf;
+    if (int r = jpeg_parse(file, bytes, 0, &jf, g_op_err)) return r;
+    yolo_frame_desc d; JpegPlane rows[3]; size_t surface = 0, block = 0;
+    jpeg_place(jf, surface, block, &d, rows);
+    if (surface > 0xffffffffull) { g_op_err = "jpeg_to_rgb: file 0: its component planes pass 2^32 - 1 bytes"; return YOLO_ERR_UNSUPPORTED; }
+    std::vector<int16_t> coef;
+    try { coef.resize(jf.blocks * 64); } catch (const std::bad_alloc &) { g_op_err = "jpeg_to_rgb: file 0: no memory for its blocks"; return YOLO_ERR_NOMEM; }
+    if (int r = jpeg_decode(file, bytes, 0, jf, coef.data(), g_op_err)) return r;
+    if (int r = frame_desc_check(d, surface, 0, g_op_err)) { g_op_err = "jpeg_to_rgb: " + g_op_err; return r; }
+    OpScope S(device); if (S.rc) { g_op_err = "jpeg_to_rgb: no HIP device"; return S.rc; }
+    FrameDesc f; memcpy(&f, &d, sizeof f);
+    const size_t out_bytes = (size_t)f.h * f.w * 3;
+    const int16_t *d_c = (const int16_t *)S.upload(coef.data(), coef.size() * 2);
+    const JpegPlane *d_t = (const JpegPlane *)S.upload(rows, (size_t)jf.comps * sizeof(JpegPlane));
+    uint8_t *d_p = (uint8_t *)S.alloc(surface), *d_o = (uint8_t *)S.alloc(out_bytes);
+    if (S.rc) { g_op_err = "jpeg_to_rgb: allocation failed"; return S.rc; }
+    if (!S.ok(launch_jpeg_idct(d_c, d_t, jf.comps, jf.blocks, d_p, surface, S.s))) { g_op_err = "jpeg_to_rgb: IDCT: " + S.err; return S.rc; }
+    if (!S.ok(launch_frame_to_rgb(d_p, surface, f, d_o, S.s))) { g_op_err = "jpeg_to_rgb: " + S.err; return S.rc; }
+    return S.download(rgb_out, d_o, out_bytes);
+}
+
 int yolo_op_letterbox(const float *image_chw, int iw, int ih, int w, int h, int embed, float *out_chw, int device)
 {
     if (!image_chw || !out_chw || iw < 1 || ih < 1 || w < 1 || h < 1) { g_op_err = "letterbox: bad arguments"; return YOLO_ERR_INVALID; }

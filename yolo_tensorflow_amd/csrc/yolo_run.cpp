@@ -1,5 +1,6 @@
 // Launch sequence of libyolo_hip.so: layer -> kernel launch, input staging, threshold + NMS, the captured detect steps and layer timing.
 #include "yolo_ctx.h"
+#include <chrono>
 
 namespace yolo_impl {
 
@@ -669,15 +670,17 @@ int frame_desc_check(const yolo_frame_desc &d, size_t bytes, int i, std::string 
 {
     char b[256];
     auto bad = [&](const char *fmt, auto... a) { snprintf(b, sizeof b, fmt, a...); msg = "frame " + std::to_string(i) + ": " + b; return (int)YOLO_ERR_INVALID; };
-    if (d.format < YOLO_PIX_NV12 || d.format > YOLO_PIX_BGR24) return bad("unknown format %d", (int)d.format);
+    const bool jpeg = pix_is_jpeg(d.format);
+    if ((d.format < YOLO_PIX_NV12 || d.format > YOLO_PIX_BGR24) && !jpeg) return bad("unknown format %d", (int)d.format);
     if (d.matrix < YOLO_MATRIX_BT601 || d.matrix > YOLO_MATRIX_BT601_FULL) return bad("unknown matrix %d", (int)d.matrix);
+    if (jpeg && d.matrix != 0) return bad("matrix %d with a JPEG format: the format carries its colour rule, the matrix must be 0", (int)d.matrix);
     if (d.h < 1 || d.w < 1) return bad("%d x %d", (int)d.h, (int)d.w);
-    const uint64_t ch = ((uint64_t)d.h + 1) / 2, cw = ((uint64_t)d.w + 1) / 2;
+    const uint64_t ch = jpeg ? (uint64_t)jpeg_chroma_rows(d.format, d.h) : ((uint64_t)d.h + 1) / 2, cw = jpeg ? (uint64_t)jpeg_chroma_cols(d.format, d.w) : ((uint64_t)d.w + 1) / 2;
     // the planes the format has: rows and bytes per row
-    const int planes = d.format == YOLO_PIX_NV12 ? 2 : d.format == YOLO_PIX_I420 ? 3 : 1;
+    const int planes = d.format == YOLO_PIX_NV12 ? 2 : d.format == YOLO_PIX_I420 || (jpeg && d.format != YOLO_PIX_JPEG_GREY) ? 3 : 1;
     for (int p = 0; p < planes; ++p) {
         const uint64_t rows = p == 0 ? (uint64_t)d.h : ch;
-        const uint64_t row = d.format >= YOLO_PIX_RGB24 ? 3 * (uint64_t)d.w : p == 0 ? (uint64_t)d.w : d.format == YOLO_PIX_NV12 ? 2 * cw : cw;
+        const uint64_t row = d.format == YOLO_PIX_RGB24 || d.format == YOLO_PIX_BGR24 ? 3 * (uint64_t)d.w : p == 0 ? (uint64_t)d.w : d.format == YOLO_PIX_NV12 ? 2 * cw : cw;
         if (d.pitch[p] < row) return bad("plane %d: pitch %llu below the row's %llu bytes", p, (unsigned long long)d.pitch[p], (unsigned long long)row);
         if (d.pitch[p] > 0xffffffffull) return bad("plane %d: pitch %llu does not fit 32 bits", p, (unsigned long long)d.pitch[p]);
         if (d.offset[p] > 0xffffffffull || (rows - 1) * d.pitch[p] + row > 0xffffffffull - d.offset[p])
@@ -1001,7 +1004,8 @@ static_assert(sizeof(FrameDesc) == sizeof(yolo_frame_desc) && offsetof(FrameDesc
               offsetof(FrameDesc, w) == offsetof(yolo_frame_desc, w) && offsetof(FrameDesc, format) == offsetof(yolo_frame_desc, format) && offsetof(FrameDesc, matrix) == offsetof(yolo_frame_desc, matrix),
               "yolo_frame_desc is the frame table's row");
 static_assert(PIX_NV12 == YOLO_PIX_NV12 && PIX_I420 == YOLO_PIX_I420 && PIX_RGB24 == YOLO_PIX_RGB24 && PIX_BGR24 == YOLO_PIX_BGR24 && MATRIX_BT601 == YOLO_MATRIX_BT601 &&
-              MATRIX_BT709 == YOLO_MATRIX_BT709 && MATRIX_BT601_FULL == YOLO_MATRIX_BT601_FULL, "the kernels' format and matrix codes are the public ones");
+              MATRIX_BT709 == YOLO_MATRIX_BT709 && MATRIX_BT601_FULL == YOLO_MATRIX_BT601_FULL && PIX_JPEG_GREY == YOLO_PIX_JPEG_GREY && PIX_JPEG_444 == YOLO_PIX_JPEG_444 &&
+              PIX_JPEG_422 == YOLO_PIX_JPEG_422 && PIX_JPEG_420 == YOLO_PIX_JPEG_420 && PIX_JPEG_440 == YOLO_PIX_JPEG_440, "the kernels' format and matrix codes are the public ones");
 
 int yolo_frame_to_rgb_host(const yolo_frame_desc *desc, const uint8_t *pixels, size_t bytes, uint8_t *rgb_out)
 {
@@ -1012,9 +1016,12 @@ int yolo_frame_to_rgb_host(const yolo_frame_desc *desc, const uint8_t *pixels, s
     for (int y = 0; y < f.h; ++y)
         for (int x = 0; x < f.w; ++x) {
             unsigned o[3]; int v[3];
-            frame_sample_offsets(f, y, x, o);
-            if (f.format >= PIX_RGB24) for (int k = 0; k < 3; ++k) v[k] = pixels[o[k]];
-            else yuv_to_rgb(m, pixels[o[0]], pixels[o[1]], pixels[o[2]], v);
+            if (pix_is_jpeg(f.format)) jpeg_frame_rgb(f, y, x, [&](unsigned off) { return (int)pixels[off]; }, v);
+            else {
+                frame_sample_offsets(f, y, x, o);
+                if (f.format >= PIX_RGB24) for (int k = 0; k < 3; ++k) v[k] = pixels[o[k]];
+                else yuv_to_rgb(m, pixels[o[0]], pixels[o[1]], pixels[o[2]], v);
+            }
             uint8_t *q = rgb_out + ((size_t)y * f.w + x) * 3;
             q[0] = (uint8_t)v[0]; q[1] = (uint8_t)v[1]; q[2] = (uint8_t)v[2];
         }
@@ -1036,14 +1043,17 @@ static int frame_check(yolo_ctx *c, int i, const yolo_frame_desc &d, size_t byte
 }
 
 // everything a batch of frames is refused for, before any launch: images_check's list, the frame descriptors, and what a frame cannot mean
-static int frames_check(yolo_ctx *c, const void *pixels, size_t bytes, const yolo_frame_desc *descs, int n, int fit)
+static int frames_refusals(yolo_ctx *c, bool have_pixels, size_t bytes, const yolo_frame_desc *descs, int n, int fit);
+static int frames_check(yolo_ctx *c, const void *pixels, size_t bytes, const yolo_frame_desc *descs, int n, int fit) { return frames_refusals(c, pixels != nullptr, bytes, descs, n, fit); }
+// the same for a buffer of `bytes` bytes that is not read here (have_pixels: the caller holds one) -- the JPEG forms ask before their surface holds anything
+static int frames_refusals(yolo_ctx *c, bool have_pixels, size_t bytes, const yolo_frame_desc *descs, int n, int fit)
 {
     static const char *const who = "yolo_*_frames_u8 / yolo_detect_frames_graph";
     if (int r = need_image(c, "forward of frames")) return r;
     if (c->in_c != 3) return fail(c, YOLO_ERR_UNSUPPORTED, "%s: a network of %d planes ([net] yolo_input=planes) is not served: a frame is an RGB image after its conversion", who, c->in_c);
     if (!c->weights_loaded) return fail(c, YOLO_ERR_STATE, "forward of frames before weights were loaded");
     if (n < 1 || n > c->max_batch) return fail(c, YOLO_ERR_INVALID, "batch %d outside 1..%d", n, c->max_batch);
-    if (!pixels || !descs) return fail(c, YOLO_ERR_INVALID, "pixels / descs == NULL");
+    if (!have_pixels || !descs) return fail(c, YOLO_ERR_INVALID, "pixels / descs == NULL");
     if (int r = fit_check(c, fit, who)) return r;
     if (fit == YOLO_FIT_CV2_BGR) return fail(c, YOLO_ERR_UNSUPPORTED, "%s: YOLO_FIT_CV2_BGR is not served for frames: a frame's format states its channel order (YOLO_PIX_BGR24 with YOLO_FIT_CV2)", who);
     if (bytes < 1 || bytes > 0xffffffffull) return fail(c, YOLO_ERR_INVALID, "packed buffer of %zu bytes (1 .. 2^32 - 1)", bytes);
@@ -1176,13 +1186,20 @@ int yolo_tile_windows(int img_h, int img_w, int tile_h, int tile_w, int overlap_
 
 static int frame_check(yolo_ctx *c, int i, const yolo_frame_desc &d, size_t bytes, int fit);
 
-// yolo_detect_tiled_u8 (descs: packed RGB images) and yolo_detect_tiled_frames_u8 (frames: decoded video frames, descs == NULL): the same steps over windows of either
-static int detect_tiled_impl(yolo_ctx *c, const char *who, const uint8_t *pixels, size_t bytes, const yolo_image_desc *descs, const yolo_frame_desc *frames, int n_images,
-                             int tile_h, int tile_w, int overlap_h, int overlap_w, int fit, int loc, float score_thr, float iou_thr, int max_out, int nms_mode,
-                             int select_mode, int relative, yolo_box *boxes_out, int32_t *counts_out, int out_loc)
+// what tiled_refusals leaves for the device part: the window table, {plane 0's offset, h, w} of every frame (frames only: what the relative form divides by),
+// the windows of the image that has the most
+struct TiledWindows { std::vector<WinDesc> wins; std::vector<yolo_image_desc> geom; int most = 0; };
+
+// Every refusal of tiled detection, and the window table: no device work.  `bytes`: the size of the packed buffer the windows will be cut from -- the buffer
+// itself is not read, so yolo_detect_tiled_jpegs asks before its surface holds anything
+static int tiled_refusals(yolo_ctx *c, const char *who, size_t bytes, const yolo_image_desc *descs, const yolo_frame_desc *frames, int n_images, int tile_h, int tile_w,
+                          int overlap_h, int overlap_w, int fit, int max_out, int nms_mode, int select_mode, int relative, const void *boxes_out, const void *counts_out,
+                          TiledWindows &out)
 {
-    if (!c) return YOLO_ERR_INVALID;
-    // ---- every refusal, before any launch ----
+    std::vector<WinDesc> &wins = out.wins;
+    std::vector<yolo_image_desc> &geom = out.geom;
+    int &most = out.most;
+    wins.clear(); geom.clear(); most = 0;
     if (int r = need_detector(c, who)) return r;
     if (c->in_c != 3) return fail(c, YOLO_ERR_UNSUPPORTED, "%s: a network of %d planes ([net] yolo_input=planes) is not served: windows are cut from RGB images", who, c->in_c);
     if (frames && fit == YOLO_FIT_CV2_BGR) return fail(c, YOLO_ERR_UNSUPPORTED, "%s: YOLO_FIT_CV2_BGR is not served for frames: a frame's format states its channel order", who);
@@ -1202,14 +1219,11 @@ static int detect_tiled_impl(yolo_ctx *c, const char *who, const uint8_t *pixels
     if (relative != 0 && relative != 1) return fail(c, YOLO_ERR_INVALID, "bad relative %d", relative);
     if (!boxes_out || !counts_out) return fail(c, YOLO_ERR_INVALID, "boxes_out / counts_out == NULL");
     if (n_images < 1) return fail(c, YOLO_ERR_INVALID, "%d images", n_images);
-    if (!pixels || (!descs && !frames)) return fail(c, YOLO_ERR_INVALID, "pixels / descs == NULL");
+    if (!descs && !frames) return fail(c, YOLO_ERR_INVALID, "pixels / descs == NULL");
     if (bytes < 3 || bytes > 0xffffffffull) return fail(c, YOLO_ERR_INVALID, "packed buffer of %zu bytes (3 .. 2^32 - 1)", bytes);
     if (tile_h == 0 && tile_w == 0) { tile_h = c->in_h; tile_w = c->in_w; }
     if (!tile_args_ok(1, 1, tile_h, tile_w, overlap_h, overlap_w))
         return fail(c, YOLO_ERR_INVALID, "%s: tile %d x %d with overlap %d x %d: extents >= 1 and 0 <= overlap < tile are needed", who, tile_h, tile_w, overlap_h, overlap_w);
-    std::vector<WinDesc> wins;
-    std::vector<yolo_image_desc> geom;                                     // frames: {plane 0's offset, h, w} of every frame, what the relative form divides by
-    int most = 0;                                                          // windows of the image that has the most
     try {
         if (frames) {
             for (int i = 0; i < n_images; ++i) {
@@ -1237,6 +1251,18 @@ static int detect_tiled_impl(yolo_ctx *c, const char *who, const uint8_t *pixels
             }
         }
     } catch (const std::bad_alloc &) { return fail(c, YOLO_ERR_NOMEM, "%s: the window table", who); }
+    return YOLO_OK;
+}
+
+// the device part of tiled detection over a window table that passed tiled_refusals: pixels[bytes] holds the images (descs) or the frames (frames, descs == NULL)
+static int tiled_run(yolo_ctx *c, const char *who, const TiledWindows &tw, const uint8_t *pixels, size_t bytes, const yolo_image_desc *descs, const yolo_frame_desc *frames,
+                     int n_images, int fit, int loc, float score_thr, float iou_thr, int max_out, int nms_mode, int select_mode, int relative, yolo_box *boxes_out,
+                     int32_t *counts_out, int out_loc)
+{
+    if (!pixels) return fail(c, YOLO_ERR_INVALID, "pixels / descs == NULL");
+    const std::vector<WinDesc> &wins = tw.wins;
+    const int most = tw.most;
+    if (frames) descs = tw.geom.data();
     const int nwin = (int)wins.size();
     const size_t cap = (size_t)std::min<long long>(TILE_MERGE_CAP, (long long)most * c->rows);
     size_t pow2 = 1; while (pow2 < cap) pow2 <<= 1;
@@ -1296,6 +1322,17 @@ static int detect_tiled_impl(yolo_ctx *c, const char *who, const uint8_t *pixels
     return copy_out(c, counts_out, t.counts, (size_t)n_images * 4, out_loc);
 }
 
+// yolo_detect_tiled_u8 (descs: packed RGB images) and yolo_detect_tiled_frames_u8 (frames: decoded video frames, descs == NULL): the same steps over windows of either
+static int detect_tiled_impl(yolo_ctx *c, const char *who, const uint8_t *pixels, size_t bytes, const yolo_image_desc *descs, const yolo_frame_desc *frames, int n_images,
+                             int tile_h, int tile_w, int overlap_h, int overlap_w, int fit, int loc, float score_thr, float iou_thr, int max_out, int nms_mode,
+                             int select_mode, int relative, yolo_box *boxes_out, int32_t *counts_out, int out_loc)
+{
+    if (!c) return YOLO_ERR_INVALID;
+    TiledWindows tw;
+    if (int r = tiled_refusals(c, who, bytes, descs, frames, n_images, tile_h, tile_w, overlap_h, overlap_w, fit, max_out, nms_mode, select_mode, relative, boxes_out, counts_out, tw)) return r;
+    return tiled_run(c, who, tw, pixels, bytes, descs, frames, n_images, fit, loc, score_thr, iou_thr, max_out, nms_mode, select_mode, relative, boxes_out, counts_out, out_loc);
+}
+
 int yolo_detect_tiled_u8(yolo_ctx *c, const uint8_t *pixels, size_t bytes, const yolo_image_desc *descs, int n_images, int tile_h, int tile_w, int overlap_h,
                          int overlap_w, int fit, int loc, float score_thr, float iou_thr, int max_out, int nms_mode, int select_mode, int relative,
                          yolo_box *boxes_out, int32_t *counts_out, int out_loc)
@@ -1311,6 +1348,199 @@ int yolo_detect_tiled_frames_u8(yolo_ctx *c, const uint8_t *pixels, size_t bytes
     if (c && !descs) return fail(c, YOLO_ERR_INVALID, "pixels / descs == NULL");
     return detect_tiled_impl(c, "yolo_detect_tiled_frames_u8", pixels, bytes, nullptr, descs, n_images, tile_h, tile_w, overlap_h, overlap_w, fit, loc, score_thr, iou_thr, max_out,
                              nms_mode, select_mode, relative, boxes_out, counts_out, out_loc);
+}
+
+// ---- JPEG files: host entropy stage (yolo_jpeg.cpp) -> one upload -> one IDCT launch (jpeg_ops.hip) -> a frame table over the context's surface,
+//      which the frames entry points above read as they read any frame ----
+}  // extern "C"
+namespace yolo_impl {
+
+// where a parsed file's planes lie in a surface that has `surface` bytes in front of them, and its blocks in a coefficient array that has `block` blocks: the
+// frame descriptor, the IDCT's table rows (f.comps of them), the surface's and the array's new ends.  Planes begin at multiples of 256 bytes
+void jpeg_place(const JpegFile &f, size_t &surface, size_t &block, yolo_frame_desc *desc, JpegPlane *rows)
+{
+    memset(desc, 0, sizeof *desc);
+    desc->h = f.h; desc->w = f.w; desc->format = f.format; desc->matrix = 0;
+    for (int p = 0; p < f.comps; ++p) {
+        surface = (surface + 255) & ~(size_t)255;
+        desc->offset[p] = surface; desc->pitch[p] = (uint64_t)f.bw[p] * 8;
+        rows[p] = JpegPlane{(unsigned)(block + f.block0[p]), (unsigned)f.bw[p], (unsigned)surface, (unsigned)f.bw[p] * 8u};
+        surface += (size_t)f.bw[p] * 8 * (size_t)f.bh[p] * 8;
+    }
+    block += f.blocks;
+}
+
+// the whole decode of one parsed file on the host: entropy stage, the IDCT of every block into a surface, the frame rule over it
+static int jpeg_to_rgb_host(const uint8_t *file, size_t bytes, const JpegFile &f, uint8_t *rgb_out, std::string &msg)
+{
+    yolo_frame_desc d; JpegPlane rows[3]; size_t surface = 0, block = 0;
+    jpeg_place(f, surface, block, &d, rows);
+    std::vector<int16_t> coef; std::vector<uint8_t> planes;
+    try { coef.resize(f.blocks * 64); planes.resize(surface); } catch (const std::bad_alloc &) { msg = "file 0: no memory for its " + std::to_string(f.blocks) + " blocks"; return YOLO_ERR_NOMEM; }
+    if (int r = jpeg_decode(file, bytes, 0, f, coef.data(), msg)) return r;
+    for (int p = 0; p < f.comps; ++p)
+        for (size_t i = 0; i < (size_t)f.bw[p] * f.bh[p]; ++i)
+            jpeg_idct_block(coef.data() + (f.block0[p] + i) * 64, planes.data() + rows[p].offset + (i / f.bw[p]) * 8 * rows[p].pitch + (i % f.bw[p]) * 8, rows[p].pitch);
+    return yolo_frame_to_rgb_host(&d, planes.data(), planes.size(), rgb_out);
+}
+
+// headers and layout of a batch, into c->jpeg: no device work.  view_bytes: the surface's capacity once this batch fits it
+static int jpegs_plan(yolo_ctx *c, const uint8_t *const *files, const size_t *bytes, int n)
+{
+    if (!files || !bytes) return fail(c, YOLO_ERR_INVALID, "files / bytes == NULL");
+    if (n < 1 || n > 65536) return fail(c, YOLO_ERR_INVALID, "%d files (1 .. 65536)", n);
+    yolo_ctx::JpegBatch &J = c->jpeg;
+    try { J.files.resize((size_t)n); J.descs.resize((size_t)n); J.planes.clear(); J.planes.reserve(3 * (size_t)n); J.first_block.resize((size_t)n); }
+    catch (const std::bad_alloc &) { return fail(c, YOLO_ERR_NOMEM, "the table of %d files", n); }
+    J.blocks = 0; J.surface = 0;
+    std::string msg;
+    for (int i = 0; i < n; ++i) {
+        if (int r = jpeg_parse(files[i], bytes[i], i, &J.files[i], msg)) return fail(c, r, "%s", msg.c_str());
+        JpegPlane rows[3];
+        J.first_block[i] = J.blocks;
+        jpeg_place(J.files[i], J.surface, J.blocks, &J.descs[i], rows);
+        for (int p = 0; p < J.files[i].comps; ++p) J.planes.push_back(rows[p]);
+        if (J.surface > 0xffffffffull || J.blocks > 0xfffffff0ull) return fail(c, YOLO_ERR_UNSUPPORTED, "file %d: the component planes of files 0 .. %d pass 2^32 - 1 bytes; decode fewer files per call", i, i);
+    }
+    const size_t step = (size_t)4 << 20;
+    J.view_bytes = std::max(c->jpeg_cap, std::min<size_t>((J.surface + step - 1) / step * step, 0xffffffffull));
+    return YOLO_OK;
+}
+
+// the planned batch onto the device: buffers, entropy stage into pinned memory, one upload, one launch
+static int jpegs_run(yolo_ctx *c, const uint8_t *const *files, const size_t *bytes, int n)
+{
+    yolo_ctx::JpegBatch &J = c->jpeg;
+    HIPCK(c, hipSetDevice(c->device));
+    const size_t table = (J.planes.size() * sizeof(JpegPlane) + 255) & ~(size_t)255, need = table + J.blocks * 128;
+    if (c->jpeg_up_pending) { HIPCK(c, hipEventSynchronize(c->jpeg_up)); c->jpeg_up_pending = false; }          // the staging is free again
+    if (need > c->jin_cap || J.view_bytes > c->jpeg_cap) HIPCK(c, hipStreamSynchronize(c->stream));             // nothing in flight reads what moves
+    if (need > c->jin_cap) {
+        if (c->h_jin) HIPCK(c, hipHostFree(c->h_jin));
+        if (c->d_jin) HIPCK(c, hipFree(c->d_jin));
+        c->h_jin = c->d_jin = nullptr; c->jin_cap = 0;
+        const size_t cap = need + need / 4;
+        HIPCK(c, hipHostMalloc(&c->h_jin, cap, hipHostMallocDefault));
+        HIPCK(c, hipMalloc(&c->d_jin, cap));
+        c->jin_cap = cap;
+    }
+    if (J.view_bytes > c->jpeg_cap) {
+        if (c->d_jpeg) HIPCK(c, hipFree(c->d_jpeg));
+        c->d_jpeg = nullptr; c->jpeg_cap = 0;
+        HIPCK(c, hipMalloc((void **)&c->d_jpeg, J.view_bytes));
+        c->jpeg_cap = J.view_bytes;
+    }
+    if (!c->jpeg_up) HIPCK(c, hipEventCreateWithFlags(&c->jpeg_up, hipEventDisableTiming));
+    if (!c->jpeg_t[0]) for (auto &ev : c->jpeg_t) HIPCK(c, hipEventCreate(&ev));
+    memcpy(c->h_jin, J.planes.data(), J.planes.size() * sizeof(JpegPlane));
+    std::string msg;
+    const auto t0 = std::chrono::steady_clock::now();
+    if (int r = jpeg_decode_batch(files, bytes, n, J.files.data(), J.first_block.data(), (int16_t *)((char *)c->h_jin + table), msg)) return fail(c, r, "%s", msg.c_str());
+    c->jpeg_entropy_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    c->jpeg_upload_bytes = need;
+    HIPCK(c, hipEventRecord(c->jpeg_t[0], c->stream));
+    HIPCK(c, hipMemcpyAsync(c->d_jin, c->h_jin, need, hipMemcpyHostToDevice, c->stream));
+    HIPCK(c, hipEventRecord(c->jpeg_up, c->stream));
+    HIPCK(c, hipEventRecord(c->jpeg_t[1], c->stream));
+    c->jpeg_up_pending = true;
+    HIPCK(c, launch_jpeg_idct((const int16_t *)((const char *)c->d_jin + table), (const JpegPlane *)c->d_jin, (int)J.planes.size(), J.blocks, c->d_jpeg, c->jpeg_cap, c->stream));
+    HIPCK(c, hipEventRecord(c->jpeg_t[2], c->stream));
+    return YOLO_OK;
+}
+
+}  // namespace yolo_impl
+extern "C" {
+
+int yolo_jpeg_info(const uint8_t *file, size_t bytes, struct yolo_jpeg_info *out)
+{
+    if (!file || !out) { g_op_err = "yolo_jpeg_info: file / out == NULL"; return YOLO_ERR_INVALID; }
+    JpegFile f;
+    if (int r = jpeg_parse(file, bytes, 0, &f, g_op_err)) return r;
+    memset(out, 0, sizeof *out);
+    out->h = f.h; out->w = f.w; out->components = f.comps; out->hs = f.hs; out->vs = f.vs; out->format = f.format; out->restart_interval = f.restart;
+    out->mcus_w = f.mcux; out->mcus_h = f.mcuy;
+    for (int p = 0; p < f.comps; ++p) { out->plane_w[p] = f.bw[p] * 8; out->plane_h[p] = f.bh[p] * 8; out->blocks[p] = f.bw[p] * f.bh[p]; }
+    return YOLO_OK;
+}
+
+int yolo_jpeg_coefficients(const uint8_t *file, size_t bytes, int16_t *coef_out, size_t cap_blocks)
+{
+    if (!file || !coef_out) { g_op_err = "yolo_jpeg_coefficients: file / coef_out == NULL"; return YOLO_ERR_INVALID; }
+    JpegFile f;
+    if (int r = jpeg_parse(file, bytes, 0, &f, g_op_err)) return r;
+    if (cap_blocks < f.blocks) { g_op_err = "yolo_jpeg_coefficients: file 0: its " + std::to_string(f.blocks) + " blocks do not fit coef_out's " + std::to_string(cap_blocks); return YOLO_ERR_INVALID; }
+    return jpeg_decode(file, bytes, 0, f, coef_out, g_op_err);
+}
+
+int yolo_jpeg_to_rgb_host(const uint8_t *file, size_t bytes, uint8_t *rgb_out, size_t cap)
+{
+    if (!file || !rgb_out) { g_op_err = "yolo_jpeg_to_rgb_host: file / rgb_out == NULL"; return YOLO_ERR_INVALID; }
+    JpegFile f;
+    if (int r = jpeg_parse(file, bytes, 0, &f, g_op_err)) return r;
+    if (cap < (size_t)f.h * f.w * 3) { g_op_err = "yolo_jpeg_to_rgb_host: file 0: " + std::to_string(f.h) + " x " + std::to_string(f.w) + " x 3 bytes do not fit rgb_out's " + std::to_string(cap); return YOLO_ERR_INVALID; }
+    return jpeg_to_rgb_host(file, bytes, f, rgb_out, g_op_err);
+}
+
+int yolo_decode_jpegs(yolo_ctx *c, const uint8_t *const *files, const size_t *bytes, int n, yolo_frame_desc *descs_out, const uint8_t **device_pixels, size_t *device_bytes)
+{
+    if (!c) return YOLO_ERR_INVALID;
+    if (!descs_out || !device_pixels || !device_bytes) return fail(c, YOLO_ERR_INVALID, "yolo_decode_jpegs: descs_out / device_pixels / device_bytes == NULL");
+    if (int r = jpegs_plan(c, files, bytes, n)) return r;
+    if (int r = jpegs_run(c, files, bytes, n)) return r;
+    memcpy(descs_out, c->jpeg.descs.data(), (size_t)n * sizeof(yolo_frame_desc));
+    *device_pixels = c->d_jpeg; *device_bytes = c->jpeg_cap;
+    return YOLO_OK;
+}
+
+int yolo_jpeg_decode_times(yolo_ctx *c, double *entropy_ms, double *upload_ms, double *idct_ms, size_t *upload_bytes)
+{
+    if (!c) return YOLO_ERR_INVALID;
+    if (!c->jpeg_t[0] || !c->jpeg_upload_bytes) return fail(c, YOLO_ERR_STATE, "yolo_jpeg_decode_times before any decode on this context");
+    HIPCK(c, hipSetDevice(c->device));
+    HIPCK(c, hipEventSynchronize(c->jpeg_t[2]));
+    float up = 0.f, idct = 0.f;
+    HIPCK(c, hipEventElapsedTime(&up, c->jpeg_t[0], c->jpeg_t[1]));
+    HIPCK(c, hipEventElapsedTime(&idct, c->jpeg_t[1], c->jpeg_t[2]));
+    if (entropy_ms) *entropy_ms = c->jpeg_entropy_ms;
+    if (upload_ms) *upload_ms = up;
+    if (idct_ms) *idct_ms = idct;
+    if (upload_bytes) *upload_bytes = c->jpeg_upload_bytes;
+    return YOLO_OK;
+}
+
+int yolo_forward_jpegs(yolo_ctx *c, const uint8_t *const *files, const size_t *bytes, int n, int fit, float *det_out, int out_loc)
+{
+    if (!c) return YOLO_ERR_INVALID;
+    if (int r = jpegs_plan(c, files, bytes, n)) return r;
+    // what the frames form would refuse, asked before the IDCT launch
+    if (int r = frames_refusals(c, true, c->jpeg.view_bytes, c->jpeg.descs.data(), n, fit)) return r;
+    if (int r = jpegs_run(c, files, bytes, n)) return r;
+    return yolo_forward_frames_u8(c, c->d_jpeg, c->jpeg_cap, c->jpeg.descs.data(), n, fit, YOLO_DEVICE, det_out, out_loc);
+}
+
+int yolo_detect_jpegs(yolo_ctx *c, const uint8_t *const *files, const size_t *bytes, int n, int fit, float score_thr, float iou_thr, int max_out, int nms_mode,
+                      int select_mode, int units, yolo_box *boxes_out, int32_t *counts_out, int out_loc)
+{
+    if (!c) return YOLO_ERR_INVALID;
+    if (int r = jpegs_plan(c, files, bytes, n)) return r;
+    if (int r = detect_images_check(c, fit, max_out, nms_mode, select_mode, units)) return r;
+    if (int r = frames_refusals(c, true, c->jpeg.view_bytes, c->jpeg.descs.data(), n, fit)) return r;
+    if (int r = jpegs_run(c, files, bytes, n)) return r;
+    return yolo_detect_frames_u8(c, c->d_jpeg, c->jpeg_cap, c->jpeg.descs.data(), n, fit, YOLO_DEVICE, score_thr, iou_thr, max_out, nms_mode, select_mode, units, boxes_out, counts_out, out_loc);
+}
+
+int yolo_detect_tiled_jpegs(yolo_ctx *c, const uint8_t *const *files, const size_t *bytes, int n_images, int tile_h, int tile_w, int overlap_h, int overlap_w, int fit,
+                            float score_thr, float iou_thr, int max_out, int nms_mode, int select_mode, int relative, yolo_box *boxes_out, int32_t *counts_out, int out_loc)
+{
+    if (!c) return YOLO_ERR_INVALID;
+    if (int r = jpegs_plan(c, files, bytes, n_images)) return r;
+    static const char *const who = "yolo_detect_tiled_jpegs";
+    TiledWindows tw;          // every refusal of the tiled form and its window table before the IDCT launch, the device part after it
+    if (int r = tiled_refusals(c, who, c->jpeg.view_bytes, nullptr, c->jpeg.descs.data(), n_images, tile_h, tile_w, overlap_h, overlap_w, fit, max_out, nms_mode, select_mode,
+                               relative, boxes_out, counts_out, tw)) return r;
+    if (int r = jpegs_run(c, files, bytes, n_images)) return r;
+    return tiled_run(c, who, tw, c->d_jpeg, c->jpeg_cap, nullptr, c->jpeg.descs.data(), n_images, fit, YOLO_DEVICE, score_thr, iou_thr, max_out, nms_mode, select_mode, relative,
+                     boxes_out, counts_out, out_loc);
 }
 
 // ---- classifier contexts: forward + tail; the [softmax] launch of the output layer selects the top_k itself (run_layer) ----

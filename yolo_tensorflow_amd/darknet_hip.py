@@ -4,9 +4,10 @@ declarations (BOX, DETECTION, IMAGE, METADATA) and every name that file binds (`
 `letterbox_image`, `rgbgr_image`, `set_gpu`, `reset_rnn`, `classify`, `detect`), bound to `libdarknet_hip.so` (include/darknet_hip.h)
 instead of `./libdarknet.so`.
 
-Differences a caller sees: `load_image` decodes binary PPM / PGM only (the reference's stb JPEG decoding, D2T/darknet.py:105,
-is outside the inference path), so `detect` also takes the image as an array (RGB, HWC uint8 or float 0..1) or a ready IMAGE, and
-the class names as a METADATA or a plain list."""
+Differences a caller sees: `load_image` decodes JPEG files -- `detect(net, meta, "data/dog.jpg")` runs as in the reference, on the
+same pixels bit for bit -- and binary PPM / PGM; PNG and the refused JPEG kinds (progressive, CMYK, ...: include/yolo_hip.h "JPEG
+files") are not decoded.  `detect` also takes the image as an array (RGB, HWC uint8 or float 0..1) or a ready IMAGE, and the class
+names as a METADATA or a plain list."""
 import ctypes as C
 import os
 import numpy as np
@@ -93,7 +94,7 @@ def load_meta(path):
 
 
 def load_image(path, w=0, h=0):
-    """D2T/darknet.py:105-107 (binary PPM / PGM files)."""
+    """D2T/darknet.py:105-107 (JPEG and binary PPM / PGM files)."""
     im = _load().load_image_color(os.fsencode(path), w, h)
     if not im.data:
         raise YoloError("load_image_color failed for %s" % path)

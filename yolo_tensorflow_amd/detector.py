@@ -125,6 +125,32 @@ class _Detector:
             out.append((r["score"], np.stack([r["x0"], r["y0"], r["x1"], r["y1"]], -1).reshape(-1, 4), r["cls"]))
         return out
 
+    def detect_from_files(self, paths):
+        """detect_from_frames over JPEG files (paths or bytes objects): each chunk of max_batch files is entropy-decoded on the host and
+        transformed, fitted and detected on the device (Engine.detect_jpegs) -> what detect_from_images returns for the images darknet's
+        load_image reads from the same files (hip.jpeg_to_rgb).  detect_from_file, which reads with PIL, is not the same pixels."""
+        paths = list(paths)
+        if self.average_frames > 1 and len(paths) > self.max_batch:
+            raise ValueError("detect_from_files: %d files, but with average_frames=%d a call is one time step of at most max_batch=%d streams"
+                             % (len(paths), self.average_frames, self.max_batch))
+        out = []
+        for i in range(0, len(paths), self.max_batch):
+            for r in self.engine.detect_jpegs(paths[i:i + self.max_batch], fit=hip.FIT_STRETCH, units=hip.UNITS_NETWORK, score_thr=self.threshold,
+                                              iou_thr=self.iou_threshold, max_out=self.max_output_size, nms_mode=hip.NMS_TF,
+                                              select_mode=self.select_mode):
+                out.append((r["score"], np.stack([r["x0"], r["y0"], r["x1"], r["y1"]], -1).reshape(-1, 4), r["cls"]))
+        return out
+
+    def detect_from_large_files(self, paths, tile=None, overlap=64):
+        """detect_from_large_frames over JPEG files (Engine.detect_tiled_jpegs) -> [(scores, boxes, classes)] per file, boxes normalised to
+        the picture."""
+        out = []
+        for r in self.engine.detect_tiled_jpegs(list(paths), tile=tile, overlap=overlap, fit=hip.FIT_STRETCH, relative=True, score_thr=self.threshold,
+                                                iou_thr=self.iou_threshold, max_out=self.max_output_size, nms_mode=hip.NMS_TF,
+                                                select_mode=self.select_mode):
+            out.append((r["score"], np.stack([r["x0"], r["y0"], r["x1"], r["y1"]], -1).reshape(-1, 4), r["cls"]))
+        return out
+
     def detect_from_file(self, image_file, imshow=False, deteted_boxes_file="boxes.txt", detected_image_file=None):
         """(sic: `deteted_boxes_file` is the reference's spelling.)  Reads the image with PIL instead of OpenCV and
         returns the predictions; with `detected_image_file` the boxes are drawn (draw.draw_detection) and the picture is saved."""

@@ -26,6 +26,7 @@ FIT_STRETCH, FIT_LETTERBOX, FIT_CV2, FIT_CV2_BGR, FIT_CENTER_CROP = 0, 1, 2, 3, 
 UNITS_NETWORK, UNITS_SOURCE_PIXELS = 0, 1
 VIEWS_FLIP, VIEWS_TEN_CROP = 1, 2
 PIX_NV12, PIX_I420, PIX_RGB24, PIX_BGR24 = 0, 1, 2, 3
+PIX_JPEG_GREY, PIX_JPEG_444, PIX_JPEG_422, PIX_JPEG_420, PIX_JPEG_440 = 16, 17, 18, 19, 20      # the component planes of a decoded JPEG file
 MATRIX_BT601, MATRIX_BT709, MATRIX_BT601_FULL = 0, 1, 2
 
 BOX_DTYPE = np.dtype([("x0", "<f4"), ("y0", "<f4"), ("x1", "<f4"), ("y1", "<f4"), ("score", "<f4"), ("cls", "<i4")])
@@ -61,6 +62,7 @@ EXPORTS = [
     "yolo_set_frame_average", "yolo_frame_average",
     "yolo_view_table", "yolo_classify_views_u8", "yolo_op_view_reduce",
     "yolo_frame_to_rgb_host", "yolo_op_frame_to_rgb", "yolo_forward_frames_u8", "yolo_detect_frames_u8", "yolo_detect_frames_graph", "yolo_detect_tiled_frames_u8",
+    "yolo_jpeg_info", "yolo_jpeg_coefficients", "yolo_jpeg_to_rgb_host", "yolo_op_jpeg_to_rgb", "yolo_decode_jpegs", "yolo_jpeg_decode_times", "yolo_forward_jpegs", "yolo_detect_jpegs", "yolo_detect_tiled_jpegs",
 ]
 HIER_CONDITIONAL, HIER_ABSOLUTE, HIER_LEAVES = 0, 1, 2
 _HIER_MODES = {None: HIER_CONDITIONAL, "conditional": HIER_CONDITIONAL, "absolute": HIER_ABSOLUTE, "leaves": HIER_LEAVES}
@@ -199,6 +201,15 @@ def load_library():
     l.yolo_detect_frames_u8.argtypes = l.yolo_detect_images_u8.argtypes
     l.yolo_detect_frames_graph.argtypes = l.yolo_detect_images_graph.argtypes
     l.yolo_detect_tiled_frames_u8.argtypes = l.yolo_detect_tiled_u8.argtypes
+    l.yolo_jpeg_info.argtypes = [P, SZ, P]
+    l.yolo_jpeg_to_rgb_host.argtypes = [P, SZ, P, SZ]
+    l.yolo_jpeg_coefficients.argtypes = [P, SZ, P, SZ]
+    l.yolo_op_jpeg_to_rgb.argtypes = [P, SZ, P, I]
+    l.yolo_decode_jpegs.argtypes = [P, P, P, I, P, C.POINTER(P), C.POINTER(SZ)]
+    l.yolo_jpeg_decode_times.argtypes = [P, C.POINTER(D), C.POINTER(D), C.POINTER(D), C.POINTER(SZ)]
+    l.yolo_forward_jpegs.argtypes = [P, P, P, I, I, P, I]
+    l.yolo_detect_jpegs.argtypes = [P, P, P, I, I, F, F, I, I, I, I, P, P, I]
+    l.yolo_detect_tiled_jpegs.argtypes = [P, P, P, I, I, I, I, I, I, F, F, I, I, I, I, P, P, I]
     l.yolo_vector_inputs.argtypes = [P]
     l.yolo_forward_vectors.argtypes = [P, P, I, I, P, SZ]
     l.yolo_sequence.argtypes = [P, I, I, P, I, P, F, P, P, I]
@@ -291,6 +302,12 @@ def frame_plane_rows(h, w, format):
         return [(int(h), int(w)), (ch, cw), (ch, cw)]
     if format in (PIX_RGB24, PIX_BGR24):
         return [(int(h), 3 * int(w))]
+    if format == PIX_JPEG_GREY:
+        return [(int(h), int(w))]
+    if format in (PIX_JPEG_444, PIX_JPEG_422, PIX_JPEG_420, PIX_JPEG_440):
+        rows = ch if format in (PIX_JPEG_420, PIX_JPEG_440) else int(h)
+        cols = cw if format in (PIX_JPEG_422, PIX_JPEG_420) else int(w)
+        return [(int(h), int(w)), (rows, cols), (rows, cols)]
     raise YoloError("unknown pixel format %r" % (format,))
 
 
@@ -299,7 +316,8 @@ class Frame(object):
     read flat) that holds the planes of an h x w frame in `format` (PIX_NV12, PIX_I420, PIX_RGB24, PIX_BGR24), plane p beginning at byte
     offsets[p] of it with rows pitch[p] bytes apart.  pitch: one int for every plane or one per plane; None: the rows' own bytes.  offsets:
     None: the planes back to back in plane order, each rows * pitch bytes.  matrix: MATRIX_BT601 / MATRIX_BT709 (limited range) or
-    MATRIX_BT601_FULL (JFIF); not read for the RGB formats."""
+    MATRIX_BT601_FULL (JFIF); not read for the RGB formats.  The PIX_JPEG_* formats -- the component planes of a decoded JPEG file, what
+    Engine.decode_jpegs describes -- carry their own rule: their matrix must be 0 (the default)."""
 
     def __init__(self, data, h, w, format, matrix=MATRIX_BT601, pitch=None, offsets=None):
         self.data = np.ascontiguousarray(data).reshape(-1)
@@ -373,6 +391,92 @@ def frame_to_rgb(frame, device=None):
     else:
         _op_check(l.yolo_op_frame_to_rgb(d.ctypes.data, buf.ctypes.data, buf.size, out.ctypes.data, int(device)), "yolo_op_frame_to_rgb")
     return out
+
+
+# ---- JPEG files (include/yolo_hip.h "JPEG files"): host entropy decode, IDCT and colour on the device; bit-equal to darknet's load_image ----
+class _JpegInfo(C.Structure):
+    _fields_ = [("h", C.c_int32), ("w", C.c_int32), ("components", C.c_int32), ("hs", C.c_int32), ("vs", C.c_int32), ("format", C.c_int32),
+                ("restart_interval", C.c_int32), ("mcus_w", C.c_int32), ("mcus_h", C.c_int32), ("plane_w", C.c_int32 * 3), ("plane_h", C.c_int32 * 3),
+                ("blocks", C.c_int32 * 3)]
+
+
+def _jpeg_bytes(f):
+    """one file as a bytes object: bytes-like as they are, anything else is a path"""
+    if isinstance(f, (bytes, bytearray, memoryview)):
+        return bytes(f)
+    with open(os.fspath(f), "rb") as fh:
+        return fh.read()
+
+
+class _JpegFiles(object):
+    """files (bytes objects or paths) as the (files, bytes, n) triple of the C entry points; holds the buffers alive"""
+
+    def __init__(self, files):
+        if isinstance(files, (bytes, bytearray, memoryview, str)) or hasattr(files, "__fspath__"):
+            raise YoloError("JPEG files: need a list of bytes objects or paths, got one %s" % type(files).__name__)
+        self.data = [_jpeg_bytes(f) for f in files]
+        self.n = len(self.data)
+        if not self.n:
+            raise YoloError("JPEG files: no files")
+        self.ptrs = (C.c_char_p * self.n)(*self.data)
+        self.sizes = (C.c_size_t * self.n)(*[len(d) for d in self.data])
+
+
+def jpeg_info(file):
+    """The headers of one JPEG file (bytes or a path) as a dict (yolo_jpeg_info): h, w, components, the luma sampling hs x vs, the PIX_JPEG_* format of
+    its frame, restart_interval, mcus (w, h), the padded component planes and their blocks.  Host only.  A file of a kind that is not served
+    (progressive, CMYK, ...) or a malformed one raises YoloError with the library's text: code -6 (unsupported) or -1 (invalid)."""
+    data = _jpeg_bytes(file)
+    info = _JpegInfo()
+    _op_check(load_library().yolo_jpeg_info(data, len(data), C.byref(info)), "yolo_jpeg_info")
+    n = info.components
+    return {"h": info.h, "w": info.w, "components": n, "hs": info.hs, "vs": info.vs, "format": info.format, "restart_interval": info.restart_interval,
+            "mcus": (info.mcus_w, info.mcus_h), "planes": [(info.plane_h[p], info.plane_w[p]) for p in range(n)], "blocks": [info.blocks[p] for p in range(n)]}
+
+
+def jpeg_coefficients(file):
+    """The host stage by itself (yolo_jpeg_coefficients): the dequantised coefficient blocks of a JPEG file, one int16 array
+    [blocks down, blocks across, 8, 8] per component plane (natural order: [..., v, u] is row v, column u of the block)."""
+    data = _jpeg_bytes(file)
+    l = load_library()
+    info = _JpegInfo()
+    _op_check(l.yolo_jpeg_info(data, len(data), C.byref(info)), "yolo_jpeg_info")
+    n = info.components
+    coef = np.zeros((sum(info.blocks[p] for p in range(n)), 8, 8), dtype=np.int16)
+    _op_check(l.yolo_jpeg_coefficients(data, len(data), coef.ctypes.data, coef.shape[0]), "yolo_jpeg_coefficients")
+    out, at = [], 0
+    for p in range(n):
+        out.append(coef[at:at + info.blocks[p]].reshape(info.plane_h[p] // 8, info.plane_w[p] // 8, 8, 8))
+        at += info.blocks[p]
+    return out
+
+
+def jpeg_to_rgb(file, device=None):
+    """The uint8 [h, w, 3] image of a JPEG file (bytes or a path), bit-equal to what darknet's load_image reads: wholly on the host
+    (yolo_jpeg_to_rgb_host; no device is touched) or, with `device` an ordinal, entropy stage on the host and IDCT, upsampling and colour by the
+    device kernels (yolo_op_jpeg_to_rgb)."""
+    data = _jpeg_bytes(file)
+    l = load_library()
+    info = _JpegInfo()
+    _op_check(l.yolo_jpeg_info(data, len(data), C.byref(info)), "yolo_jpeg_info")
+    out = np.zeros((info.h, info.w, 3), dtype=np.uint8)
+    if device is None:
+        _op_check(l.yolo_jpeg_to_rgb_host(data, len(data), out.ctypes.data, out.size), "yolo_jpeg_to_rgb_host")
+    else:
+        _op_check(l.yolo_op_jpeg_to_rgb(data, len(data), out.ctypes.data, int(device)), "yolo_op_jpeg_to_rgb")
+    return out
+
+
+class JpegFrames(object):
+    """What Engine.decode_jpegs returns: the frame table (`descs`, FRAME_DTYPE) of a decoded batch over the engine's surface -- `pixels`, a raw device
+    pointer, `nbytes` its capacity.  Pass it wherever frames are taken (forward_frames, detect_frames, detect_tiled_frames; detect_frames_graph:
+    pixels_dev=handle.pixels, descs=handle.descs, nbytes=handle.nbytes).  Valid until the engine's next decode."""
+
+    def __init__(self, pixels, nbytes, descs):
+        self.pixels, self.nbytes, self.descs = int(pixels), int(nbytes), descs
+
+    def __len__(self):
+        return len(self.descs)
 
 
 def fit_unit_value(fit, value):
@@ -754,6 +858,8 @@ class Engine:
 
     # ---- decoded video frames: NV12 / I420 / pitched RGB / BGR surfaces, converted while they are fitted ----
     def _packed_frames(self, frames):
+        if isinstance(frames, JpegFrames):          # a decoded batch of JPEG files: the engine's own surface
+            return frames.pixels, _frame_descs(frames.descs), C.c_void_p(frames.pixels), DEVICE, frames.nbytes
         if isinstance(frames, tuple):
             buf, descs = frames
         else:
@@ -820,6 +926,52 @@ class Engine:
         self._order_after_producer(pixels_dev, boxes_out, counts_out)
         self._check(self.lib.yolo_detect_frames_graph(self.ctx, p, nbytes, descs.ctypes.data, len(descs), fit, score_thr, iou_thr,
                                                       max_out, nms_mode, select_mode, units, bp, cp), "yolo_detect_frames_graph")
+
+    # ---- JPEG files: entropy-decoded on the host, IDCT on the device, read as frames (chroma upsampling and colour inside the fit launch) ----
+    def decode_jpegs(self, files):
+        """files: a list of JPEG files, each a bytes object or a path -> a JpegFrames handle over this engine's surface (yolo_decode_jpegs): one
+        upload and one IDCT launch for the batch.  The handle goes wherever frames go; it is valid until the next decode on this engine."""
+        f = _JpegFiles(files)
+        descs = np.zeros(f.n, dtype=FRAME_DTYPE)
+        pixels, nbytes = C.c_void_p(), C.c_size_t()
+        self._check(self.lib.yolo_decode_jpegs(self.ctx, f.ptrs, f.sizes, f.n, descs.ctypes.data, C.byref(pixels), C.byref(nbytes)), "yolo_decode_jpegs")
+        return JpegFrames(pixels.value, nbytes.value, descs)
+
+    def jpeg_decode_times(self):
+        """What this engine's last decode cost (yolo_jpeg_decode_times): {"entropy_ms": host wall time of the entropy stage, "upload_ms" and
+        "idct_ms": device time of the upload and of the IDCT launch, "upload_bytes"}.  Waits for the IDCT."""
+        e, u, i, b = C.c_double(), C.c_double(), C.c_double(), C.c_size_t()
+        self._check(self.lib.yolo_jpeg_decode_times(self.ctx, C.byref(e), C.byref(u), C.byref(i), C.byref(b)), "yolo_jpeg_decode_times")
+        return {"entropy_ms": e.value, "upload_ms": u.value, "idct_ms": i.value, "upload_bytes": b.value}
+
+    def forward_jpegs(self, files, fit=FIT_STRETCH, want_detections=True):
+        """forward_frames over JPEG files (yolo_forward_jpegs): decode, fit, forward.  Returns the decoded tensor [n, rows, attrs]."""
+        f = _JpegFiles(files)
+        det = np.empty((f.n, self.rows, self.attrs), dtype=np.float32) if want_detections else None
+        self._check(self.lib.yolo_forward_jpegs(self.ctx, f.ptrs, f.sizes, f.n, fit, det.ctypes.data if det is not None else None, HOST), "yolo_forward_jpegs")
+        return det
+
+    def detect_jpegs(self, files, fit=FIT_STRETCH, units=UNITS_NETWORK, score_thr=0.5, iou_thr=0.5, max_out=20, nms_mode=NMS_TF, select_mode=SELECT_GT,
+                     hier_thresh=None):
+        """detect_frames over JPEG files (yolo_detect_jpegs) -> list of BOX_DTYPE arrays; UNITS_SOURCE_PIXELS: in the picture's own pixels."""
+        if hier_thresh is not None:
+            self.set_hier_thresh(hier_thresh)
+        f = _JpegFiles(files)
+        boxes = np.zeros((f.n, max_out), dtype=BOX_DTYPE); counts = np.zeros(f.n, dtype=np.int32)
+        self._check(self.lib.yolo_detect_jpegs(self.ctx, f.ptrs, f.sizes, f.n, fit, score_thr, iou_thr, max_out, nms_mode, select_mode, units,
+                                               boxes.ctypes.data, counts.ctypes.data, HOST), "yolo_detect_jpegs")
+        return [boxes[i, :counts[i]].copy() for i in range(f.n)]
+
+    def detect_tiled_jpegs(self, files, tile=None, overlap=(64, 64), fit=FIT_STRETCH, relative=False, score_thr=0.5, iou_thr=0.5, max_out=20,
+                           nms_mode=NMS_TF, select_mode=SELECT_GT):
+        """detect_tiled_frames over JPEG files (yolo_detect_tiled_jpegs).  Arguments and records as detect_tiled."""
+        f = _JpegFiles(files)
+        th, tw = (0, 0) if tile is None else _pair(tile, "tile")
+        oh, ow = _pair(overlap, "overlap")
+        boxes = np.zeros((f.n, max_out), dtype=BOX_DTYPE); counts = np.zeros(f.n, dtype=np.int32)
+        self._check(self.lib.yolo_detect_tiled_jpegs(self.ctx, f.ptrs, f.sizes, f.n, th, tw, oh, ow, fit, score_thr, iou_thr, max_out, nms_mode,
+                                                     select_mode, 1 if relative else 0, boxes.ctypes.data, counts.ctypes.data, HOST), "yolo_detect_tiled_jpegs")
+        return [boxes[i, :counts[i]].copy() for i in range(f.n)]
 
     # ---- classifier networks (a cfg whose output layer is a [softmax]) ----
     @property
