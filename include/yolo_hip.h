@@ -625,6 +625,19 @@ int yolo_classify(yolo_ctx *ctx, const void *images, int n, int fmt, int loc, fl
 /* ... over a ragged batch of native-size images through the one-launch fit of yolo_forward_images_u8 */
 int yolo_classify_images_u8(yolo_ctx *ctx, const uint8_t *pixels, size_t bytes, const yolo_image_desc *descs, int n, int fit, int loc,
                             int top_k, int32_t *classes_out, float *probs_out, int out_loc);
+/* ... over decoded video frames: yolo_forward_frames_u8's arguments (one launch converts and fits every frame; chroma upsampling and colour happen inside
+ * it, no RGB copy of a frame is stored), then the tail.  Every fit yolo_classify_images_u8 takes except YOLO_FIT_CV2_BGR, which is refused for frames
+ * (YOLO_ERR_UNSUPPORTED); YOLO_FIT_CENTER_CROP over a frame is darknet's `classifier predict` preprocessing.  The staged input, the probabilities and the
+ * top_k records equal, bit for bit, those of yolo_classify_images_u8 over the RGB image yolo_frame_to_rgb_host yields.  Refused before any launch: what
+ * yolo_classify_images_u8 refuses of a context and of top_k, what yolo_forward_frames_u8 refuses of descriptors (naming the frame), a network of other
+ * than 3 planes (YOLO_ERR_UNSUPPORTED). */
+int yolo_classify_frames_u8(yolo_ctx *ctx, const uint8_t *pixels, size_t bytes, const yolo_frame_desc *descs, int n, int fit, int loc,
+                            int top_k, int32_t *classes_out, float *probs_out, int out_loc);
+/* ... over JPEG files (files[i], bytes[i]: file i, host): yolo_decode_jpegs of the batch, then yolo_classify_frames_u8 over its frame table on the device.
+ * The pixels are the reference's load_image pixels, so with YOLO_FIT_CENTER_CROP this is `darknet classifier predict cfg weights file.jpg`.  Refused before
+ * the IDCT launch: everything above, and every file yolo_decode_jpegs refuses (naming the file). */
+int yolo_classify_jpegs(yolo_ctx *ctx, const uint8_t *const *files, const size_t *bytes, int n, int fit, int top_k, int32_t *classes_out,
+                        float *probs_out, int out_loc);
 /* ---- multi-view classification: darknet's ten-crop and flip averaging (DN/examples/classifier.c:234-301 validate_classifier_10,
  * `classifier valid10`; DN/examples/cifar.c:101-128 test_cifar_multi).  Every image is predicted over K views and the K rows are added.
  * YOLO_VIEWS_FLIP, K = 2: view 0 is the image fitted by `fit` (any fit yolo_classify_images_u8 takes), view 1 its mirror,
@@ -657,6 +670,20 @@ int yolo_view_table(int views, int shift, yolo_view *out, int cap, int *count);
  * in both modes.  There is no captured-graph form. */
 int yolo_classify_views_u8(yolo_ctx *ctx, const uint8_t *pixels, size_t bytes, const yolo_image_desc *descs, int n_images, int views, int fit,
                            int shift, int loc, float scale, int top_k, int32_t *classes_out, float *probs_out, int out_loc);
+/* ... over decoded video frames, argument for argument: descs[n_images] frames in `pixels` (host or device), n_images NOT bound by max_batch (the call
+ * carries a frame table of its own to the device).  Slot image * K + view is one view of frame `image`, fitted straight from the frame's planes by the
+ * step's one launch: YOLO_VIEWS_FLIP under any fit yolo_classify_frames_u8 takes, YOLO_VIEWS_TEN_CROP as above.  The mirror and the crops act on
+ * coordinates of the fitted / resized image; chroma is always indexed by the pixel's position in the FRAME (the nearest chroma of NV12 / I420, the JPEG
+ * formats' upsamplers with their edge cases), so every staged slot, every sum and every top_k record equals, bit for bit, yolo_classify_views_u8 over the
+ * RGB images yolo_frame_to_rgb_host yields.  Steps, the device-resident rows, the one reduction launch, `scale`, `top_k` and the independence from
+ * max_batch are yolo_classify_views_u8's; so are its refusals, with yolo_forward_frames_u8's of descriptors (naming the frame), YOLO_FIT_CV2_BGR and a
+ * network of other than 3 planes (YOLO_ERR_UNSUPPORTED).  No RGB copy of a frame or a view is stored; the source bytes are uploaded once. */
+int yolo_classify_views_frames_u8(yolo_ctx *ctx, const uint8_t *pixels, size_t bytes, const yolo_frame_desc *descs, int n_images, int views, int fit,
+                                  int shift, int loc, float scale, int top_k, int32_t *classes_out, float *probs_out, int out_loc);
+/* ... over JPEG files: ONE decode batch for all n_images files (n_images <= 65536 and the planes of the batch < 2^32 bytes, as yolo_decode_jpegs), then
+ * the frame form over its table on the device -- `classifier valid10` over files.  Every refusal comes before the IDCT launch. */
+int yolo_classify_views_jpegs(yolo_ctx *ctx, const uint8_t *const *files, const size_t *bytes, int n_images, int views, int fit, int shift,
+                              float scale, int top_k, int32_t *classes_out, float *probs_out, int out_loc);
 /* the reduction launch alone over host arrays: rows [n * views][len] fp32 (slot = image * views + view), 1 <= views <= 32, any len >= 1 ->
  * sums_out [n][len]; top_k > 0 (<= min(32, len)): also classes_out / top_out [n][top_k] from the same launch (else NULL; NaN and -inf are
  * never selected) */
@@ -756,6 +783,16 @@ int yolo_label_map(yolo_ctx *ctx, int n, float thresh, uint8_t *labels_u8);
  * same for y.  YOLO_FIT_LETTERBOX: new_w, new_h, dx, dy are darknet's letterbox_image integers; every other fit: new_w = net_w, dx = 0. */
 int yolo_segment_images_u8(yolo_ctx *ctx, const uint8_t *pixels, const yolo_image_desc *descs, int n, int fit, float thresh,
                            uint8_t *labels_u8, const uint64_t *label_offsets);
+/* ... over decoded video frames: `pixels` (bytes; host or device, `loc`) and descs[n] as for yolo_forward_frames_u8 -- one launch converts and fits, one
+ * forward, then the same label kernel: frame i's labels at THAT FRAME'S OWN h_i x w_i, placed as above, equal byte for byte to yolo_segment_images_u8
+ * over the RGB images yolo_frame_to_rgb_host yields.  Refused before any launch: a detector or a classifier, YOLO_FIT_CENTER_CROP, more than 255 channels,
+ * and what yolo_forward_frames_u8 refuses (a bad descriptor, naming the frame; YOLO_FIT_CV2_BGR; a network of other than 3 planes). */
+int yolo_segment_frames_u8(yolo_ctx *ctx, const uint8_t *pixels, size_t bytes, const yolo_frame_desc *descs, int n, int fit, int loc, float thresh,
+                           uint8_t *labels_u8, const uint64_t *label_offsets);
+/* ... over JPEG files: yolo_decode_jpegs of the batch, then the frame form on the device (the reference's `segmenter test` takes a file).  Every refusal,
+ * those of the files included, comes before the IDCT launch. */
+int yolo_segment_jpegs(yolo_ctx *ctx, const uint8_t *const *files, const size_t *bytes, int n, int fit, float thresh, uint8_t *labels_u8,
+                       const uint64_t *label_offsets);
 /* single operators.  deconv2d: x [n,h,w,cin] fp32 NHWC, w_iohw [cin][cout][size][size] (the order of darknet's weight files), bias [cout]
  * or NULL, act a yolo_activation, dtype YOLO_FP32 / BF16 / FP16 (the operands are stored as it first), out_f32 != 0: the fp32 store of a
  * 16-bit kernel (a map network's output layer); out [n, (h-1) stride + size - 2 padding, ..., cout] fp32 */

@@ -46,21 +46,36 @@ class Classifier:
         probability descending.  views: None predicts each image once; "flip" averages the image (fitted by the classifier's fit) and its mirror, as
         darknet's test_cifar_multi adds them; "ten_crop" averages darknet's `classifier valid10` views, five crops of the image resized to the network
         input + `shift` and the same five of its mirror (the fit is not used).  Both return the MEAN over the views, formed and ranked on the device."""
+        return self._classify(images, top, views, shift, self.engine.classify_images, self.engine.classify_views)
+
+    def _classify(self, items, top, views, shift, once, multi):
+        """classify_from_*: `once` the engine's single-view call over a chunk of max_batch items, `multi` its multi-view call over all of them"""
         if views is not None:
             if views not in self.VIEWS:
                 raise hip.YoloError("Classifier: views must be None, 'flip' or 'ten_crop', got %r" % (views,))
             mode = self.VIEWS[views]
-            cls, probs = self.engine.classify_views(images, mode, fit=self.fit, shift=shift, scale=1.0 / len(hip.view_table(mode, shift)), top_k=top)
+            cls, probs = multi(items, mode, fit=self.fit, shift=shift, scale=1.0 / len(hip.view_table(mode, shift)), top_k=top)
             return [[(self._name(int(k)), float(q)) for k, q in zip(c, p)] for c, p in zip(cls, probs)]
         out = []
-        for lo in range(0, len(images), self.max_batch):
-            cls, probs = self.engine.classify_images(images[lo:lo + self.max_batch], fit=self.fit, top_k=top)
+        for lo in range(0, len(items), self.max_batch):
+            cls, probs = once(items[lo:lo + self.max_batch], fit=self.fit, top_k=top)
             for c, p in zip(cls, probs):
                 out.append([(self._name(int(k)), float(q)) for k, q in zip(c, p)])
         return out
 
     def classify_from_image(self, image, top=5):
         return self.classify_from_images([np.ascontiguousarray(image, dtype=np.uint8)], top=top)[0]
+
+    def classify_from_files(self, paths, top=5, views=None, shift=32):
+        """paths: a list of JPEG files (paths or bytes objects) -> what classify_from_images returns, over the pixels darknet's load_image reads from them:
+        entropy decode on the host, IDCT, chroma upsampling, colour and the fit on the device.  With fit=hip.FIT_CENTER_CROP this is `darknet classifier
+        predict cfg weights file.jpg`; views="ten_crop" is `classifier valid10` over files."""
+        return self._classify(list(paths), top, views, shift, self.engine.classify_jpegs, self.engine.classify_views_jpegs)
+
+    def classify_from_frames(self, frames, top=5, views=None, shift=32):
+        """frames: a list of hip.Frame (NV12, I420, pitched RGB / BGR surfaces) -> what classify_from_images returns; every frame is converted while it is
+        fitted, no RGB copy of it is made."""
+        return self._classify(list(frames), top, views, shift, self.engine.classify_frames, self.engine.classify_views_frames)
 
     def close(self):
         self.engine.close()

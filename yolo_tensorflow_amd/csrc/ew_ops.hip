@@ -895,23 +895,30 @@ struct AtFrame {
         int v[3];
         rgb(y, x, v);
         const unsigned b = (unsigned)(c == 0 ? v[0] : c == 1 ? v[1] : v[2]);
-        return fit == FIT_LETTERBOX || fit == FIT_CENTER_CROP ? fit_unit_value(FIT_LETTERBOX, b) : (float)b;
+        return fit == FIT_LETTERBOX || fit == FIT_CENTER_CROP || fit == FIT_TEN_CROP ? fit_unit_value(FIT_LETTERBOX, b) : (float)b;
     }
 };
 
-// k_fit_images over frames.  WIN: slot i is window wins[i] of frame wins[i].image, else frame i itself
-template <typename T, int FIT, bool WIN>
-__global__ __launch_bounds__(256) void k_fit_frames(const uint8_t *pixels, unsigned bytes, const FrameDesc *frames, const WinDesc *wins, int net_h, int net_w, T *out,
+// k_fit_images over frames.  What a batch slot shows: frame i itself; window wins[i] of frame wins[i].image (slots: the WinDesc table); or one view of frame
+// views[i].offset (slots: the ViewDesc table, whose `offset` field holds the FRAME INDEX here, h and w the frame's), with k_fit_images<.., ViewDesc, 3>'s meaning:
+// a mirrored view reads the fit at view_column, FIT_TEN_CROP crops and mirrors in the resized image's coordinates.  A view's pixels are pixels of the whole frame
+// (y0 = x0 = 0), so its chroma is indexed in the frame whatever the mirror or the crop does
+enum { SLOT_FRAME = 0, SLOT_WINDOW = 1, SLOT_VIEW = 2 };
+template <typename T, int FIT, int SLOT>
+__global__ __launch_bounds__(256) void k_fit_frames(const uint8_t *pixels, unsigned bytes, const FrameDesc *frames, const void *slots, int net_h, int net_w, T *out,
                                                     int out_stride, float post_mul, float post_add)
 {
+    static_assert(FIT != FIT_TEN_CROP || SLOT == SLOT_VIEW, "the ten crops are views");
     const int img = blockIdx.y;
     const int p = blockIdx.x * 256 + threadIdx.x;
     if (p >= net_h * net_w) return;
     int h = 0, w = 0, y0 = 0, x0 = 0, fi = img;
-    if (WIN) { const WinDesc d = wins[img]; h = d.h; w = d.w; y0 = d.y0; x0 = d.x0; fi = d.image; }
+    ViewDesc view = {};
+    if (SLOT == SLOT_WINDOW) { const WinDesc d = ((const WinDesc *)slots)[img]; h = d.h; w = d.w; y0 = d.y0; x0 = d.x0; fi = d.image; }
+    if (SLOT == SLOT_VIEW) { view = ((const ViewDesc *)slots)[img]; fi = (int)view.offset; }
     const FrameDesc f = frames[fi];
-    if (!WIN) { h = f.h; w = f.w; }
-    const int oy = p / net_w, ox = p - oy * net_w;
+    if (SLOT != SLOT_WINDOW) { h = f.h; w = f.w; }
+    const int oy = p / net_w, ox = SLOT == SLOT_VIEW && FIT != FIT_TEN_CROP ? view_column(view, p - oy * net_w, net_w) : p - oy * net_w;
     const AtFrame at{__builtin_amdgcn_make_buffer_rsrc((void *)pixels, 0, bytes, 0x00020000), f, color_matrix(f.matrix), y0, x0, FIT};
     float v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (FIT == FIT_STRETCH) px_stretch<3>(at, h, w, net_h, net_w, oy, ox, post_mul, post_add, 0, 3, v);
@@ -921,6 +928,7 @@ __global__ __launch_bounds__(256) void k_fit_frames(const uint8_t *pixels, unsig
             letterbox_dims(net_w, net_h, w, h, &new_w, &new_h);
             px_letterbox<3>(at, w, h, new_w, new_h, (net_w - new_w) / 2, (net_h - new_h) / 2, oy, ox, 0, 3, v);
         } else if (FIT == FIT_CENTER_CROP) px_center_crop<3>(at, w, h, net_w, net_h, oy, ox, 0, 3, v);
+        else if constexpr (FIT == FIT_TEN_CROP) px_ten_crop<3>(at, w, h, net_w, net_h, view.shift, view.dy, view.dx, view.flip, oy, ox, 0, 3, v);
         else px_cv2(at, h, w, net_h, net_w, oy, ox, 0, 225.0f, v);
         // [net] yolo_input_mul / yolo_input_add, as k_fit_images applies them
 #pragma unroll
@@ -932,20 +940,28 @@ __global__ __launch_bounds__(256) void k_fit_frames(const uint8_t *pixels, unsig
     Elt<T>::store8(out + ((size_t)img * net_h * net_w + p) * out_stride, v);
 }
 
-static hipError_t fit_frames(const uint8_t *pixels, size_t bytes, const FrameDesc *d_frames, const WinDesc *d_wins, int n, int fit, int net_h, int net_w, void *out,
+// slots: the WinDesc table (SLOT_WINDOW: FIT_STRETCH, FIT_LETTERBOX), the ViewDesc table (SLOT_VIEW: every fit of whole frames, and FIT_TEN_CROP), NULL for whole frames
+static hipError_t fit_frames(const uint8_t *pixels, size_t bytes, const FrameDesc *d_frames, const void *slots, int slot, int n, int fit, int net_h, int net_w, void *out,
                              int out_dt, int out_stride, float post_mul, float post_add, hipStream_t s)
 {
-    if (n < 1 || net_h < 1 || net_w < 1 || (size_t)net_h * net_w > 0x7fffffffull || bytes > 0xffffffffull || out_stride < 8) return hipErrorInvalidValue;
+    if (n < 1 || net_h < 1 || net_w < 1 || (size_t)net_h * net_w > 0x7fffffffull || bytes > 0xffffffffull || out_stride < 8 || (slot != SLOT_FRAME) != (slots != nullptr)) return hipErrorInvalidValue;
     const dim3 grid((unsigned)((net_h * net_w + 255) / 256), (unsigned)n);
-#define FRAMES_LAUNCH(F, WIN) WITH_DT(out_dt, hipLaunchKernelGGL((k_fit_frames<T, F, WIN>), grid, dim3(256), 0, s, pixels, (unsigned)bytes, d_frames, d_wins, net_h, net_w, (T *)out, out_stride, post_mul, post_add))
-    if (d_wins) {
-        if (fit == FIT_STRETCH) FRAMES_LAUNCH(FIT_STRETCH, true);
-        else if (fit == FIT_LETTERBOX) FRAMES_LAUNCH(FIT_LETTERBOX, true);
+#define FRAMES_LAUNCH(F, SLOT) WITH_DT(out_dt, hipLaunchKernelGGL((k_fit_frames<T, F, SLOT>), grid, dim3(256), 0, s, pixels, (unsigned)bytes, d_frames, slots, net_h, net_w, (T *)out, out_stride, post_mul, post_add))
+    if (slot == SLOT_WINDOW) {
+        if (fit == FIT_STRETCH) FRAMES_LAUNCH(FIT_STRETCH, SLOT_WINDOW);
+        else if (fit == FIT_LETTERBOX) FRAMES_LAUNCH(FIT_LETTERBOX, SLOT_WINDOW);
         else return hipErrorInvalidValue;
-    } else if (fit == FIT_STRETCH) FRAMES_LAUNCH(FIT_STRETCH, false);
-    else if (fit == FIT_LETTERBOX) FRAMES_LAUNCH(FIT_LETTERBOX, false);
-    else if (fit == FIT_CV2) FRAMES_LAUNCH(FIT_CV2, false);
-    else if (fit == FIT_CENTER_CROP) FRAMES_LAUNCH(FIT_CENTER_CROP, false);
+    } else if (slot == SLOT_VIEW) {
+        if (fit == FIT_STRETCH) FRAMES_LAUNCH(FIT_STRETCH, SLOT_VIEW);
+        else if (fit == FIT_LETTERBOX) FRAMES_LAUNCH(FIT_LETTERBOX, SLOT_VIEW);
+        else if (fit == FIT_CV2) FRAMES_LAUNCH(FIT_CV2, SLOT_VIEW);
+        else if (fit == FIT_CENTER_CROP) FRAMES_LAUNCH(FIT_CENTER_CROP, SLOT_VIEW);
+        else if (fit == FIT_TEN_CROP) FRAMES_LAUNCH(FIT_TEN_CROP, SLOT_VIEW);
+        else return hipErrorInvalidValue;
+    } else if (fit == FIT_STRETCH) FRAMES_LAUNCH(FIT_STRETCH, SLOT_FRAME);
+    else if (fit == FIT_LETTERBOX) FRAMES_LAUNCH(FIT_LETTERBOX, SLOT_FRAME);
+    else if (fit == FIT_CV2) FRAMES_LAUNCH(FIT_CV2, SLOT_FRAME);
+    else if (fit == FIT_CENTER_CROP) FRAMES_LAUNCH(FIT_CENTER_CROP, SLOT_FRAME);
     else return hipErrorInvalidValue;
 #undef FRAMES_LAUNCH
     return hipGetLastError();
@@ -953,13 +969,17 @@ static hipError_t fit_frames(const uint8_t *pixels, size_t bytes, const FrameDes
 hipError_t launch_fit_frames(const uint8_t *pixels, size_t bytes, const FrameDesc *d_frames, int n, int fit, int net_h, int net_w, void *out, int out_dt,
                              int out_stride, float post_mul, float post_add, hipStream_t s)
 {
-    return fit_frames(pixels, bytes, d_frames, nullptr, n, fit, net_h, net_w, out, out_dt, out_stride, post_mul, post_add, s);
+    return fit_frames(pixels, bytes, d_frames, nullptr, SLOT_FRAME, n, fit, net_h, net_w, out, out_dt, out_stride, post_mul, post_add, s);
 }
 hipError_t launch_fit_frame_windows(const uint8_t *pixels, size_t bytes, const FrameDesc *d_frames, const WinDesc *d_wins, int n, int fit, int net_h, int net_w,
                                     void *out, int out_dt, int out_stride, float post_mul, float post_add, hipStream_t s)
 {
-    if (!d_wins) return hipErrorInvalidValue;
-    return fit_frames(pixels, bytes, d_frames, d_wins, n, fit, net_h, net_w, out, out_dt, out_stride, post_mul, post_add, s);
+    return fit_frames(pixels, bytes, d_frames, d_wins, SLOT_WINDOW, n, fit, net_h, net_w, out, out_dt, out_stride, post_mul, post_add, s);
+}
+hipError_t launch_fit_frame_views(const uint8_t *pixels, size_t bytes, const FrameDesc *d_frames, const ViewDesc *d_views, int n, int fit, int net_h, int net_w,
+                                  void *out, int out_dt, int out_stride, float post_mul, float post_add, hipStream_t s)
+{
+    return fit_frames(pixels, bytes, d_frames, d_views, SLOT_VIEW, n, fit, net_h, net_w, out, out_dt, out_stride, post_mul, post_add, s);
 }
 
 // one frame -> [h][w][3] uint8: the colour rule by itself (yolo_op_frame_to_rgb); one pixel per lane

@@ -634,6 +634,11 @@ hipError_t launch_fit_frames(const uint8_t *pixels, size_t bytes, const FrameDes
 // indexed by the pixel's position in the FRAME, so a window may start on an odd row or column.  FIT_STRETCH and FIT_LETTERBOX
 hipError_t launch_fit_frame_windows(const uint8_t *pixels, size_t bytes, const FrameDesc *d_frames, const WinDesc *d_wins, int n, int fit, int net_h, int net_w,
                                     void *out, int out_dt, int out_stride, float post_mul, float post_add, hipStream_t s);
+// views of frames (yolo_classify_views_frames_u8): slot i is one view of frame d_views[i].offset -- the field holds the FRAME INDEX here, not a byte offset; h, w: the
+// frame's -- with launch_fit_views' meaning: fit FIT_STRETCH, FIT_LETTERBOX, FIT_CV2 or FIT_CENTER_CROP, mirrored where flip != 0, or FIT_TEN_CROP.  A mirror or a
+// crop moves coordinates of the fitted / resized image only: chroma stays indexed by the pixel's position in the frame
+hipError_t launch_fit_frame_views(const uint8_t *pixels, size_t bytes, const FrameDesc *d_frames, const ViewDesc *d_views, int n, int fit, int net_h, int net_w,
+                                  void *out, int out_dt, int out_stride, float post_mul, float post_add, hipStream_t s);
 // one frame -> the [h][w][3] uint8 image of the colour rule (yolo_op_frame_to_rgb)
 hipError_t launch_frame_to_rgb(const uint8_t *pixels, size_t bytes, const FrameDesc &frame, uint8_t *out, hipStream_t s);
 // JPEG files: one component plane of one file of a batch -- blocks block0 .. of the batch's coefficient array are its 8 x 8 blocks in raster order, bw across; the

@@ -1587,6 +1587,30 @@ int yolo_classify_images_u8(yolo_ctx *c, const uint8_t *pixels, size_t bytes, co
     return classify_out(c, n, top_k, classes_out, probs_out, out_loc);
 }
 
+// ... over decoded video frames: the frame fit of yolo_forward_frames_u8, the same tail
+int yolo_classify_frames_u8(yolo_ctx *c, const uint8_t *pixels, size_t bytes, const yolo_frame_desc *descs, int n, int fit, int loc, int top_k,
+                            int32_t *classes_out, float *probs_out, int out_loc)
+{
+    if (!c) return YOLO_ERR_INVALID;
+    if (int r = classify_check(c, top_k, classes_out, probs_out)) return r;
+    c->cls_topk = top_k; c->cls_mode = c->hierarchy_mode;
+    const int r = forward_frames_impl(c, pixels, bytes, descs, n, fit, loc, nullptr, YOLO_DEVICE, false, 0.f);
+    c->cls_topk = 0; c->cls_mode = 0;
+    if (r) return r;
+    return classify_out(c, n, top_k, classes_out, probs_out, out_loc);
+}
+
+// ... and over JPEG files: every refusal before the IDCT launch, then the frame form over the context's surface
+int yolo_classify_jpegs(yolo_ctx *c, const uint8_t *const *files, const size_t *bytes, int n, int fit, int top_k, int32_t *classes_out, float *probs_out, int out_loc)
+{
+    if (!c) return YOLO_ERR_INVALID;
+    if (int r = classify_check(c, top_k, classes_out, probs_out)) return r;
+    if (int r = jpegs_plan(c, files, bytes, n)) return r;
+    if (int r = frames_refusals(c, true, c->jpeg.view_bytes, c->jpeg.descs.data(), n, fit)) return r;
+    if (int r = jpegs_run(c, files, bytes, n)) return r;
+    return yolo_classify_frames_u8(c, c->d_jpeg, c->jpeg_cap, c->jpeg.descs.data(), n, fit, YOLO_DEVICE, top_k, classes_out, probs_out, out_loc);
+}
+
 // ---- multi-view classification: darknet's `classifier valid10` (ten crops) and test_cifar_multi (the image and its mirror) on the
 //      device.  Slots are ordered image * K + view and run max_batch per step: one fit launch over the view table straight from the source bytes, the
 //      network, one device copy of the step's rows behind the rows of the steps before; after the last step ONE launch adds every image's K rows in view
@@ -1602,13 +1626,14 @@ yolo_view view_at(int views, int shift, int v)
 }
 // the carving of yolo_ctx::d_views for a call of `images` images of K views and `len` classes: every array 256-byte aligned
 struct ViewSlab {
-    ViewDesc *views; float *rows, *sums, *work, *topk; int *cls; size_t bytes;
-    ViewSlab(char *base, size_t images, size_t K, size_t len)
+    ViewDesc *views; float *rows, *sums, *work, *topk; int *cls; FrameDesc *frames; size_t bytes;
+    ViewSlab(char *base, size_t images, size_t K, size_t len, size_t nframes)      // nframes: rows of the frame table (yolo_classify_views_frames_u8), 0 for images
     {
         size_t off = 0;
         auto take = [&](size_t n) { const uintptr_t p = (uintptr_t)base + off; off += (n + 255) & ~(size_t)255; return (void *)p; };      // (base == nullptr: the sizes only)
         views = (ViewDesc *)take(images * K * sizeof(ViewDesc)); rows = (float *)take(images * K * len * 4); sums = (float *)take(images * len * 4);
         work = (float *)take(images * len * 4); cls = (int *)take(images * CLS_TOPK_MAX * 4); topk = (float *)take(images * CLS_TOPK_MAX * 4);
+        frames = (FrameDesc *)take(nframes * sizeof(FrameDesc));
         bytes = off;
     }
 };
@@ -1625,13 +1650,17 @@ int yolo_view_table(int views, int shift, yolo_view *out, int cap, int *count)
     return YOLO_OK;
 }
 
-int yolo_classify_views_u8(yolo_ctx *c, const uint8_t *pixels, size_t bytes, const yolo_image_desc *descs, int n_images, int views, int fit, int shift, int loc,
-                           float scale, int top_k, int32_t *classes_out, float *probs_out, int out_loc)
+// what views_refusals leaves for the device part: the view table in slot order, K
+struct ViewPlan { std::vector<ViewDesc> table; int K = 0; bool ten = false; };
+
+// Every refusal of multi-view classification, and the view table: no device work.  descs: packed images; frames (descs == NULL): decoded video frames, whose view
+// rows name their frame by its index.  `bytes`: the size of the buffer the views will be read from -- the buffer itself is not read, so the JPEG form asks before
+// its surface holds anything (have_pixels: the caller holds one)
+static int views_refusals(yolo_ctx *c, const char *who, bool have_pixels, size_t bytes, const yolo_image_desc *descs, const yolo_frame_desc *frames, int n_images, int views,
+                          int fit, int shift, int top_k, const int32_t *classes_out, const float *probs_out, ViewPlan &out)
 {
-    static const char *const who = "yolo_classify_views_u8";
-    if (!c) return YOLO_ERR_INVALID;
-    // ---- every refusal, before any launch ----
     if (int r = classify_check(c, top_k, classes_out, probs_out)) return r;
+    if (frames && c->in_c != 3) return fail(c, YOLO_ERR_UNSUPPORTED, "%s: a network of %d planes ([net] yolo_input=planes) is not served: a frame is an RGB image after its conversion", who, c->in_c);
     if (!c->states.empty())
         return fail(c, YOLO_ERR_UNSUPPORTED, "%s: a network with recurrent state (%d state tensors) is not served: a batch slot is a stream there, not a view of an image", who, (int)c->states.size());
     if (c->dtype == YOLO_FP8) return fail(c, YOLO_ERR_UNSUPPORTED, "%s: the fp8 configuration is not served", who);
@@ -1639,8 +1668,10 @@ int yolo_classify_views_u8(yolo_ctx *c, const uint8_t *pixels, size_t bytes, con
     if (!K) return fail(c, YOLO_ERR_INVALID, "%s: bad views %d (YOLO_VIEWS_FLIP or YOLO_VIEWS_TEN_CROP)", who, views);
     if (shift < 0) return fail(c, YOLO_ERR_INVALID, "%s: shift %d < 0", who, shift);
     const bool ten = views == YOLO_VIEWS_TEN_CROP;
-    if (!ten) { if (int r = fit_check(c, fit, who)) return r; }
-    else {
+    if (!ten) {
+        if (int r = fit_check(c, fit, who)) return r;
+        if (frames && fit == YOLO_FIT_CV2_BGR) return fail(c, YOLO_ERR_UNSUPPORTED, "%s: YOLO_FIT_CV2_BGR is not served for frames: a frame's format states its channel order (YOLO_PIX_BGR24 with YOLO_FIT_CV2)", who);
+    } else {
         // resize_image divides by the resized extent - 1; the crop's coordinates y + shift, x + shift stay below the resized extents
         if ((long long)c->in_w + shift > 0x7fffffffLL || (long long)c->in_h + shift > 0x7fffffffLL)
             return fail(c, YOLO_ERR_INVALID, "%s: the network input %d x %d enlarged by shift %d does not fit an int", who, c->in_h, c->in_w, shift);
@@ -1649,23 +1680,37 @@ int yolo_classify_views_u8(yolo_ctx *c, const uint8_t *pixels, size_t bytes, con
     }
     if (!c->weights_loaded) return fail(c, YOLO_ERR_STATE, "%s before weights were loaded", who);
     if (n_images < 1 || n_images > 0x7fffffff / K) return fail(c, YOLO_ERR_INVALID, "%s: %d images (1 .. %d)", who, n_images, 0x7fffffff / K);
-    if (!pixels || !descs) return fail(c, YOLO_ERR_INVALID, "pixels / descs == NULL");
-    if (bytes < (size_t)c->in_c || bytes > 0xffffffffull) return fail(c, YOLO_ERR_INVALID, "packed buffer of %zu bytes (%d .. 2^32 - 1)", bytes, c->in_c);
-    for (int i = 0; i < n_images; ++i) if (int r = image_check(c, i, descs[i], bytes, ten ? -1 : fit)) return r;
-    const Layer &L = c->layers[c->cls_layer];
+    if (!have_pixels || (!descs && !frames)) return fail(c, YOLO_ERR_INVALID, "pixels / descs == NULL");
+    if (frames) {
+        if (bytes < 1 || bytes > 0xffffffffull) return fail(c, YOLO_ERR_INVALID, "packed buffer of %zu bytes (1 .. 2^32 - 1)", bytes);
+        for (int i = 0; i < n_images; ++i) if (int r = frame_check(c, i, frames[i], bytes, ten ? -1 : fit)) return r;
+    } else {
+        if (bytes < (size_t)c->in_c || bytes > 0xffffffffull) return fail(c, YOLO_ERR_INVALID, "packed buffer of %zu bytes (%d .. 2^32 - 1)", bytes, c->in_c);
+        for (int i = 0; i < n_images; ++i) if (int r = image_check(c, i, descs[i], bytes, ten ? -1 : fit)) return r;
+    }
     const int nslots = n_images * K;
-    std::vector<ViewDesc> table;
     try {
-        table.resize(nslots);
+        out.table.resize(nslots);
     } catch (const std::bad_alloc &) { return fail(c, YOLO_ERR_NOMEM, "%s: the view table", who); }
     for (int i = 0; i < nslots; ++i) {
-        const yolo_image_desc &d = descs[i / K];
         const yolo_view v = view_at(views, shift, i % K);
-        table[i] = ViewDesc{d.offset, d.h, d.w, v.dy, v.dx, v.flip, shift};
+        // a frame's view names its frame by index: the fit reads the frame table
+        if (frames) out.table[i] = ViewDesc{(unsigned long long)(i / K), frames[i / K].h, frames[i / K].w, v.dy, v.dx, v.flip, shift};
+        else out.table[i] = ViewDesc{descs[i / K].offset, descs[i / K].h, descs[i / K].w, v.dy, v.dx, v.flip, shift};
     }
-    const ViewSlab need(nullptr, n_images, K, L.C);
+    out.K = K; out.ten = ten;
+    return YOLO_OK;
+}
 
-    // ---- device ----
+// the device part over a view table that passed views_refusals: pixels[bytes] holds the images, or the frames (frames != NULL: the call's own frame table goes
+// into the slab -- n_images is not bound by max_batch, which is what the context's d_frames holds)
+static int views_run(yolo_ctx *c, const ViewPlan &plan, const uint8_t *pixels, size_t bytes, const yolo_frame_desc *frames, int n_images, int fit, int loc, float scale,
+                     int top_k, int32_t *classes_out, float *probs_out, int out_loc)
+{
+    const Layer &L = c->layers[c->cls_layer];
+    const int K = plan.K, nslots = n_images * K;
+    const ViewSlab need(nullptr, n_images, K, L.C, frames ? n_images : 0);
+
     HIPCK(c, hipSetDevice(c->device));
     const uint8_t *src = nullptr;
     if (int r = stage_pixels(c, pixels, bytes, loc, &src)) return r;          // the source bytes go up once, whatever K is
@@ -1675,15 +1720,18 @@ int yolo_classify_views_u8(yolo_ctx *c, const uint8_t *pixels, size_t bytes, con
         c->d_views = nullptr; c->views_cap = 0;
         HIPCK(c, hipMalloc(&c->d_views, need.bytes)); c->views_cap = need.bytes;
     }
-    const ViewSlab t((char *)c->d_views, n_images, K, L.C);
+    const ViewSlab t((char *)c->d_views, n_images, K, L.C, frames ? n_images : 0);
     StreamDrain drain{c};
-    HIPCK(c, hipMemcpyAsync(t.views, table.data(), (size_t)nslots * sizeof(ViewDesc), hipMemcpyHostToDevice, c->stream));
+    HIPCK(c, hipMemcpyAsync(t.views, plan.table.data(), (size_t)nslots * sizeof(ViewDesc), hipMemcpyHostToDevice, c->stream));
+    if (frames) HIPCK(c, hipMemcpyAsync(t.frames, frames, (size_t)n_images * sizeof(FrameDesc), hipMemcpyHostToDevice, c->stream));
     c->lean_thr = 0.f; c->cls_topk = 0; c->cls_mode = c->hierarchy_mode;
     struct ModeReset { yolo_ctx *c; ~ModeReset() { c->cls_mode = 0; } } reset{c};
+    const int kfit = plan.ten ? FIT_TEN_CROP : fit;
     for (int first = 0; first < nslots; first += c->max_batch) {
         const int nb = std::min(c->max_batch, nslots - first);
         auto [dst, dt] = input_fill_dst(c);
-        HIPCK(c, launch_fit_views(src, bytes, t.views + first, nb, ten ? FIT_TEN_CROP : fit, c->in_h, c->in_w, dst, dt, fill_stride(c), c->in_mul, c->in_add, c->stream, c->in_c));
+        if (frames) HIPCK(c, launch_fit_frame_views(src, bytes, t.frames, t.views + first, nb, kfit, c->in_h, c->in_w, dst, dt, fill_stride(c), c->in_mul, c->in_add, c->stream));
+        else HIPCK(c, launch_fit_views(src, bytes, t.views + first, nb, kfit, c->in_h, c->in_w, dst, dt, fill_stride(c), c->in_mul, c->in_add, c->stream, c->in_c));
         HIPCK(c, input_filled(c, (size_t)nb * c->in_h * c->in_w));
         if (int r = run_network(c, nb, false)) return r;
         // the step's rows behind those of the steps before: a device copy on the context stream, no host synchronisation
@@ -1697,17 +1745,68 @@ int yolo_classify_views_u8(yolo_ctx *c, const uint8_t *pixels, size_t bytes, con
     return copy_out(c, probs_out, t.topk, (size_t)n_images * top_k * 4, out_loc);
 }
 
+int yolo_classify_views_u8(yolo_ctx *c, const uint8_t *pixels, size_t bytes, const yolo_image_desc *descs, int n_images, int views, int fit, int shift, int loc,
+                           float scale, int top_k, int32_t *classes_out, float *probs_out, int out_loc)
+{
+    if (!c) return YOLO_ERR_INVALID;
+    ViewPlan plan;
+    if (int r = views_refusals(c, "yolo_classify_views_u8", pixels != nullptr, bytes, descs, nullptr, n_images, views, fit, shift, top_k, classes_out, probs_out, plan)) return r;
+    return views_run(c, plan, pixels, bytes, nullptr, n_images, fit, loc, scale, top_k, classes_out, probs_out, out_loc);
+}
+
+int yolo_classify_views_frames_u8(yolo_ctx *c, const uint8_t *pixels, size_t bytes, const yolo_frame_desc *descs, int n_images, int views, int fit, int shift, int loc,
+                                  float scale, int top_k, int32_t *classes_out, float *probs_out, int out_loc)
+{
+    if (!c) return YOLO_ERR_INVALID;
+    if (!descs) return fail(c, YOLO_ERR_INVALID, "pixels / descs == NULL");
+    ViewPlan plan;
+    if (int r = views_refusals(c, "yolo_classify_views_frames_u8", pixels != nullptr, bytes, nullptr, descs, n_images, views, fit, shift, top_k, classes_out, probs_out, plan)) return r;
+    return views_run(c, plan, pixels, bytes, descs, n_images, fit, loc, scale, top_k, classes_out, probs_out, out_loc);
+}
+
+// one decode batch for all n_images files, every refusal before the IDCT launch
+int yolo_classify_views_jpegs(yolo_ctx *c, const uint8_t *const *files, const size_t *bytes, int n_images, int views, int fit, int shift, float scale, int top_k,
+                              int32_t *classes_out, float *probs_out, int out_loc)
+{
+    if (!c) return YOLO_ERR_INVALID;
+    if (int r = jpegs_plan(c, files, bytes, n_images)) return r;
+    ViewPlan plan;
+    if (int r = views_refusals(c, "yolo_classify_views_jpegs", true, c->jpeg.view_bytes, nullptr, c->jpeg.descs.data(), n_images, views, fit, shift, top_k, classes_out, probs_out, plan)) return r;
+    if (int r = jpegs_run(c, files, bytes, n_images)) return r;
+    return views_run(c, plan, c->d_jpeg, c->jpeg_cap, c->jpeg.descs.data(), n_images, fit, YOLO_DEVICE, scale, top_k, classes_out, probs_out, out_loc);
+}
+
 // ---- map contexts: the ragged native-size path.  One fit launch and one forward, as yolo_detect_images_u8, then ONE kernel that writes every
 //      image's labels at that image's own size (launch_segment_labels) ----
+// what a segment entry point is refused for before it looks at its images: no device work
+static int segment_refusals(yolo_ctx *c, const char *who, int fit, const uint8_t *labels_u8)
+{
+    if (int r = need_map(c, who)) return r;
+    if (int r = crop_fit_refused(c, fit, who, "labels")) return r;
+    if (!labels_u8) return fail(c, YOLO_ERR_INVALID, "labels_u8 == NULL");
+    if (c->layers[c->map_layer].C > 255) return fail(c, YOLO_ERR_UNSUPPORTED, "%s: a map of %d channels (uint8 labels hold at most 255 classes)", who, c->layers[c->map_layer].C);
+    return YOLO_OK;
+}
+
+// behind the forward of n images whose {offset, h, w} lie in d_descs: image i's labels at its own size at off[i] of a `total`-byte label buffer, to the host
+static int segment_labels_out(yolo_ctx *c, int n, int fit, float thresh, const std::vector<unsigned long long> &off, size_t total, bool placed, uint8_t *labels_u8)
+{
+    const Layer &M = c->layers[c->map_layer];
+    if (!c->d_label_off) HIPCK(c, hipMalloc((void **)&c->d_label_off, (size_t)c->max_batch * 8));
+    HIPCK(c, hipMemcpyAsync(c->d_label_off, off.data(), (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+    const float *map = nullptr; int map_stride = 0;
+    if (int r = map_f32_view(c, n, &map, &map_stride)) return r;
+    if (int r = map_labels_room(c, total)) return r;
+    if (placed) HIPCK(c, hipMemsetAsync(c->d_map_labels, 0, total, c->stream));          // (gaps a caller's placement leaves)
+    HIPCK(c, launch_segment_labels(map, map_stride, M.H, M.W, M.C, thresh, c->d_descs, c->d_label_off, n, fit, c->in_h, c->in_w, c->d_map_labels, c->stream));
+    return copy_out(c, labels_u8, c->d_map_labels, total, YOLO_HOST);          // (synchronises: `off` outlives its asynchronous copy)
+}
+
 int yolo_segment_images_u8(yolo_ctx *c, const uint8_t *pixels, const yolo_image_desc *descs, int n, int fit, float thresh, uint8_t *labels_u8,
                            const uint64_t *label_offsets)
 {
     if (!c) return YOLO_ERR_INVALID;
-    if (int r = need_map(c, "yolo_segment_images_u8")) return r;
-    if (int r = crop_fit_refused(c, fit, "yolo_segment_images_u8", "labels")) return r;
-    if (!labels_u8) return fail(c, YOLO_ERR_INVALID, "labels_u8 == NULL");
-    const Layer &M = c->layers[c->map_layer];
-    if (M.C > 255) return fail(c, YOLO_ERR_UNSUPPORTED, "yolo_segment_images_u8: a map of %d channels (uint8 labels hold at most 255 classes)", M.C);
+    if (int r = segment_refusals(c, "yolo_segment_images_u8", fit, labels_u8)) return r;
     if (!descs || n < 1 || n > c->max_batch) return fail(c, YOLO_ERR_INVALID, "batch %d outside 1..%d", n, c->max_batch);
     // the packed buffer ends where its last image ends; the labels lie back to back in image order unless the caller places them
     size_t bytes = 0, total = 0;
@@ -1720,14 +1819,41 @@ int yolo_segment_images_u8(yolo_ctx *c, const uint8_t *pixels, const yolo_image_
         total = std::max(total, (size_t)off[i] + px);
     }
     if (int r = forward_images_impl(c, pixels, bytes, descs, n, fit, YOLO_HOST, nullptr, YOLO_DEVICE, false, 0.f)) return r;
-    if (!c->d_label_off) HIPCK(c, hipMalloc((void **)&c->d_label_off, (size_t)c->max_batch * 8));
-    HIPCK(c, hipMemcpyAsync(c->d_label_off, off.data(), (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
-    const float *map = nullptr; int map_stride = 0;
-    if (int r = map_f32_view(c, n, &map, &map_stride)) return r;
-    if (int r = map_labels_room(c, total)) return r;
-    if (label_offsets) HIPCK(c, hipMemsetAsync(c->d_map_labels, 0, total, c->stream));          // (gaps a caller's placement leaves)
-    HIPCK(c, launch_segment_labels(map, map_stride, M.H, M.W, M.C, thresh, c->d_descs, c->d_label_off, n, fit, c->in_h, c->in_w, c->d_map_labels, c->stream));
-    return copy_out(c, labels_u8, c->d_map_labels, total, YOLO_HOST);          // (synchronises: `off` outlives its asynchronous copy)
+    return segment_labels_out(c, n, fit, thresh, off, total, label_offsets != nullptr, labels_u8);
+}
+
+// ... over decoded video frames: the frame fit, the forward, then the same label kernel over the {plane 0's offset, h, w} table frames_upload
+// leaves in d_descs -- labels at each FRAME's own h x w.  pixels: host or device (loc)
+int yolo_segment_frames_u8(yolo_ctx *c, const uint8_t *pixels, size_t bytes, const yolo_frame_desc *descs, int n, int fit, int loc, float thresh, uint8_t *labels_u8,
+                           const uint64_t *label_offsets)
+{
+    if (!c) return YOLO_ERR_INVALID;
+    if (int r = segment_refusals(c, "yolo_segment_frames_u8", fit, labels_u8)) return r;
+    if (int r = frames_check(c, pixels, bytes, descs, n, fit)) return r;
+    size_t total = 0;
+    std::vector<unsigned long long> off(n);
+    for (int i = 0; i < n; ++i) {
+        const size_t px = (size_t)descs[i].h * (size_t)descs[i].w;
+        off[i] = label_offsets ? label_offsets[i] : total;
+        total = std::max(total, (size_t)off[i] + px);
+    }
+    HIPCK(c, hipSetDevice(c->device));
+    const uint8_t *src = nullptr;
+    if (int r = stage_pixels(c, pixels, bytes, loc, &src)) return r;
+    if (int r = frames_upload(c, descs, n)) return r;
+    if (int r = frames_step(c, src, bytes, n, fit, false, 0.f)) return r;
+    return segment_labels_out(c, n, fit, thresh, off, total, label_offsets != nullptr, labels_u8);
+}
+
+// ... and over JPEG files: every refusal before the IDCT launch, then the frame form over the context's surface
+int yolo_segment_jpegs(yolo_ctx *c, const uint8_t *const *files, const size_t *bytes, int n, int fit, float thresh, uint8_t *labels_u8, const uint64_t *label_offsets)
+{
+    if (!c) return YOLO_ERR_INVALID;
+    if (int r = segment_refusals(c, "yolo_segment_jpegs", fit, labels_u8)) return r;
+    if (int r = jpegs_plan(c, files, bytes, n)) return r;
+    if (int r = frames_refusals(c, true, c->jpeg.view_bytes, c->jpeg.descs.data(), n, fit)) return r;
+    if (int r = jpegs_run(c, files, bytes, n)) return r;
+    return yolo_segment_frames_u8(c, c->d_jpeg, c->jpeg_cap, c->jpeg.descs.data(), n, fit, YOLO_DEVICE, thresh, labels_u8, label_offsets);
 }
 
 // ---- vector-input networks: one step over fp32 rows; many steps over tokens, the sampler's token fed back on the device ----

@@ -63,6 +63,7 @@ EXPORTS = [
     "yolo_view_table", "yolo_classify_views_u8", "yolo_op_view_reduce",
     "yolo_frame_to_rgb_host", "yolo_op_frame_to_rgb", "yolo_forward_frames_u8", "yolo_detect_frames_u8", "yolo_detect_frames_graph", "yolo_detect_tiled_frames_u8",
     "yolo_jpeg_info", "yolo_jpeg_coefficients", "yolo_jpeg_to_rgb_host", "yolo_op_jpeg_to_rgb", "yolo_decode_jpegs", "yolo_jpeg_decode_times", "yolo_forward_jpegs", "yolo_detect_jpegs", "yolo_detect_tiled_jpegs",
+    "yolo_classify_frames_u8", "yolo_classify_views_frames_u8", "yolo_segment_frames_u8", "yolo_classify_jpegs", "yolo_classify_views_jpegs", "yolo_segment_jpegs",
 ]
 HIER_CONDITIONAL, HIER_ABSOLUTE, HIER_LEAVES = 0, 1, 2
 _HIER_MODES = {None: HIER_CONDITIONAL, "conditional": HIER_CONDITIONAL, "absolute": HIER_ABSOLUTE, "leaves": HIER_LEAVES}
@@ -210,6 +211,12 @@ def load_library():
     l.yolo_forward_jpegs.argtypes = [P, P, P, I, I, P, I]
     l.yolo_detect_jpegs.argtypes = [P, P, P, I, I, F, F, I, I, I, I, P, P, I]
     l.yolo_detect_tiled_jpegs.argtypes = [P, P, P, I, I, I, I, I, I, F, F, I, I, I, I, P, P, I]
+    l.yolo_classify_frames_u8.argtypes = l.yolo_classify_images_u8.argtypes
+    l.yolo_classify_views_frames_u8.argtypes = l.yolo_classify_views_u8.argtypes
+    l.yolo_segment_frames_u8.argtypes = [P, P, SZ, P, I, I, I, F, P, P]
+    l.yolo_classify_jpegs.argtypes = [P, P, P, I, I, I, P, P, I]
+    l.yolo_classify_views_jpegs.argtypes = [P, P, P, I, I, I, I, F, I, P, P, I]
+    l.yolo_segment_jpegs.argtypes = [P, P, P, I, I, F, P, P]
     l.yolo_vector_inputs.argtypes = [P]
     l.yolo_forward_vectors.argtypes = [P, P, I, I, P, SZ]
     l.yolo_sequence.argtypes = [P, I, I, P, I, P, F, P, P, I]
@@ -469,7 +476,7 @@ def jpeg_to_rgb(file, device=None):
 
 class JpegFrames(object):
     """What Engine.decode_jpegs returns: the frame table (`descs`, FRAME_DTYPE) of a decoded batch over the engine's surface -- `pixels`, a raw device
-    pointer, `nbytes` its capacity.  Pass it wherever frames are taken (forward_frames, detect_frames, detect_tiled_frames; detect_frames_graph:
+    pointer, `nbytes` its capacity.  Pass it wherever frames are taken (forward_frames, detect_frames, detect_tiled_frames, classify_frames, classify_views_frames, segment_frames; detect_frames_graph:
     pixels_dev=handle.pixels, descs=handle.descs, nbytes=handle.nbytes).  Valid until the engine's next decode."""
 
     def __init__(self, pixels, nbytes, descs):
@@ -1024,6 +1031,47 @@ class Engine:
                                                     cls.ctypes.data if cls is not None else None, probs.ctypes.data, HOST), "yolo_classify_views_u8")
         return (cls, probs) if top_k else probs
 
+    # ---- classifiers over decoded video frames and JPEG files: the frame fit, no RGB copy of a frame anywhere ----
+    def classify_frames(self, frames, fit=FIT_STRETCH, top_k=5):
+        """`classify_images` over a list of Frame (or a (buffer, descs) pair from pack_frames, the buffer on the host or the device; or a decode_jpegs
+        handle): one launch converts and fits every frame (`fit`: any but FIT_CV2_BGR), then the classifier tail (yolo_classify_frames_u8).  Bit-equal
+        to classify_images over frame_to_rgb of the frames."""
+        buf, descs, p, loc, nbytes = self._packed_frames(frames)
+        n = len(descs)
+        self._order_after_producer(buf)
+        cls, probs = self._classify_result(n, top_k)
+        self._check(self.lib.yolo_classify_frames_u8(self.ctx, p, nbytes, descs.ctypes.data, n, fit, loc, top_k,
+                                                     cls.ctypes.data if top_k else None, probs.ctypes.data, HOST), "yolo_classify_frames_u8")
+        return (cls, probs) if top_k else probs
+
+    def classify_views_frames(self, frames, views, fit=FIT_STRETCH, shift=32, scale=1.0, top_k=0):
+        """`classify_views` over frames (yolo_classify_views_frames_u8): any number of them; every view is fitted straight from its frame's planes, chroma
+        indexed by the pixel's position in the frame.  Arguments and results as classify_views."""
+        buf, descs, p, loc, nbytes = self._packed_frames(frames)
+        n = len(descs)
+        self._order_after_producer(buf)
+        cls, probs = self._classify_result(n, max(int(top_k), 0))          # (a negative top_k: the library refuses it)
+        self._check(self.lib.yolo_classify_views_frames_u8(self.ctx, p, nbytes, descs.ctypes.data, n, int(views), int(fit), int(shift), loc, float(scale), int(top_k),
+                                                           cls.ctypes.data if cls is not None else None, probs.ctypes.data, HOST), "yolo_classify_views_frames_u8")
+        return (cls, probs) if top_k else probs
+
+    def classify_jpegs(self, files, fit=FIT_STRETCH, top_k=5):
+        """classify_frames over JPEG files (bytes objects or paths; yolo_classify_jpegs): decode, fit, classify.  fit=FIT_CENTER_CROP: darknet's
+        `classifier predict` from a file."""
+        f = _JpegFiles(files)
+        cls, probs = self._classify_result(f.n, top_k)
+        self._check(self.lib.yolo_classify_jpegs(self.ctx, f.ptrs, f.sizes, f.n, fit, top_k, cls.ctypes.data if top_k else None, probs.ctypes.data, HOST),
+                    "yolo_classify_jpegs")
+        return (cls, probs) if top_k else probs
+
+    def classify_views_jpegs(self, files, views, fit=FIT_STRETCH, shift=32, scale=1.0, top_k=0):
+        """classify_views_frames over JPEG files (yolo_classify_views_jpegs): one decode batch for all the files -- darknet's `classifier valid10` over files."""
+        f = _JpegFiles(files)
+        cls, probs = self._classify_result(f.n, max(int(top_k), 0))
+        self._check(self.lib.yolo_classify_views_jpegs(self.ctx, f.ptrs, f.sizes, f.n, int(views), int(fit), int(shift), float(scale), int(top_k),
+                                                       cls.ctypes.data if cls is not None else None, probs.ctypes.data, HOST), "yolo_classify_views_jpegs")
+        return (cls, probs) if top_k else probs
+
     # ---- map networks ([net] yolo_output=map): segmentation masks, heat maps ----
     def map_geometry(self):
         """(h, w, c) of the output map (yolo_output_map_geometry); YoloError on a detector or a classifier."""
@@ -1057,6 +1105,36 @@ class Engine:
         for q, sz in zip(d, sizes):
             out.append(labels[lo:lo + sz].reshape(int(q["h"]), int(q["w"])).copy()); lo += sz
         return out
+
+    @staticmethod
+    def _split_labels(labels, hw):
+        out, lo = [], 0
+        for h, w in hw:
+            out.append(labels[lo:lo + h * w].reshape(h, w).copy()); lo += h * w
+        return out
+
+    def segment_frames(self, frames, fit=FIT_LETTERBOX, thresh=0.5):
+        """segment_images over frames (a list of Frame, a (buffer, descs) pair with the buffer on the host or the device, or a decode_jpegs handle) -> a
+        list of [h_i, w_i] uint8 label arrays, each at its frame's own size (yolo_segment_frames_u8)."""
+        buf, descs, p, loc, nbytes = self._packed_frames(frames)
+        hw = [(max(int(q["h"]), 0), max(int(q["w"]), 0)) for q in descs]
+        self._order_after_producer(buf)
+        labels = np.empty(sum(h * w for h, w in hw), dtype=np.uint8)
+        self._check(self.lib.yolo_segment_frames_u8(self.ctx, p, nbytes, descs.ctypes.data, len(descs), fit, loc, float(thresh), labels.ctypes.data, None),
+                    "yolo_segment_frames_u8")
+        return self._split_labels(labels, hw)
+
+    def segment_jpegs(self, files, fit=FIT_LETTERBOX, thresh=0.5):
+        """segment_frames over JPEG files (bytes objects or paths; yolo_segment_jpegs): labels at each picture's own size."""
+        f = _JpegFiles(files)
+        hw = []
+        for d in f.data:
+            info = _JpegInfo()
+            ok = self.lib.yolo_jpeg_info(d, len(d), C.byref(info)) == 0          # (a file that is not served: the entry point refuses it, by its index)
+            hw.append((info.h, info.w) if ok else (0, 0))
+        labels = np.empty(sum(h * w for h, w in hw), dtype=np.uint8)
+        self._check(self.lib.yolo_segment_jpegs(self.ctx, f.ptrs, f.sizes, f.n, fit, float(thresh), labels.ctypes.data, None), "yolo_segment_jpegs")
+        return self._split_labels(labels, hw)
 
     def darknet_boxes(self, image, w, h, thresh=0.5, relative=1, cap=None, hier_thresh=None, map200=None):
         """darknet's get_network_boxes over image `image` of the last forward (yolo_darknet_boxes_at) -> records [count, 5 + classes]

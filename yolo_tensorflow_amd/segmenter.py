@@ -50,5 +50,20 @@ class Segmenter:
             out.extend(self.engine.segment_images(images[lo:lo + self.max_batch], fit=self.fit, thresh=thresh))
         return out
 
+    def segment_from_files(self, paths, thresh=0.5):
+        """paths: a list of JPEG files (paths or bytes objects) -> segment_from_images over the pixels darknet's load_image reads from them (the
+        reference's `segmenter test` takes a file), decoded and fitted on the device; labels at each picture's own size."""
+        paths, out = list(paths), []
+        for lo in range(0, len(paths), self.max_batch):
+            out.extend(self.engine.segment_jpegs(paths[lo:lo + self.max_batch], fit=self.fit, thresh=thresh))
+        return out
+
+    def segment_from_frames(self, frames, thresh=0.5):
+        """frames: a list of hip.Frame -> segment_from_images over them, each converted while it is fitted; labels at each frame's own size."""
+        frames, out = list(frames), []
+        for lo in range(0, len(frames), self.max_batch):
+            out.extend(self.engine.segment_frames(frames[lo:lo + self.max_batch], fit=self.fit, thresh=thresh))
+        return out
+
     def close(self):
         self.engine.close()
