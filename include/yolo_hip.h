@@ -382,6 +382,34 @@ int yolo_decode_jpegs(yolo_ctx *ctx, const uint8_t *const *files, const size_t *
 /* What the last decode on this context cost (waits for its IDCT): the host's entropy stage in wall-clock ms, the upload and the IDCT
  * launch in device ms between events on the context stream, and the bytes uploaded.  Any pointer may be NULL.  tools/jpeg_rate.py. */
 int yolo_jpeg_decode_times(yolo_ctx *ctx, double *entropy_ms, double *upload_ms, double *idct_ms, size_t *upload_bytes);
+/* ---- the entropy stage on the device, over restart intervals ----
+ * A restart interval (DRI) is byte-aligned, begins with zeroed DC predictors and ends at a marker: the intervals of a file are independent
+ * streams, and k_jpeg_entropy Huffman-decodes one per lane, a whole batch per launch, from the uploaded file bytes into the coefficient
+ * array the IDCT reads.  YOLO_JPEG_ENTROPY_HOST (the default) is the host stage above for every file.  Under YOLO_JPEG_ENTROPY_AUTO,
+ * yolo_decode_jpegs and every yolo_*_jpegs entry point send the ELIGIBLE files of a batch to the device and the others through the
+ * host stage, in one call, with one IDCT launch over all.  Eligible: the file has a DRI and a scan of its entropy-coded segment finds
+ * exactly the expected RSTm markers (fill bytes 0xFF allowed in front, nothing else between).  The results are bit-equal, and so are
+ * the verdicts: a file of which any interval fails on the device, or leaves whole bytes unread in front of its marker, is decoded
+ * again by the host stage, and what that returns -- its coefficients, or its code and message -- is what the call returns.  Such a
+ * refusal comes after the first launch; refusals of header kinds still come before it.  After it the contents of the context's surface
+ * and what the two *_times calls report are undefined until the next successful decode (a batch refused under HOST leaves the
+ * previous surface as it was).  A decode under AUTO that ran the device stage has waited for it when it returns. */
+enum { YOLO_JPEG_ENTROPY_HOST = 0, YOLO_JPEG_ENTROPY_AUTO = 1 };
+int yolo_set_jpeg_entropy(yolo_ctx *ctx, int mode);          /* any other mode: YOLO_ERR_INVALID */
+int yolo_jpeg_entropy(yolo_ctx *ctx);                        /* the mode; a fresh context: YOLO_JPEG_ENTROPY_HOST */
+/* What the entropy stage of the last decode on this context did: files decoded on the device and by the host stage (a file handed
+ * back counts as the host's, its intervals are not counted), restart intervals decoded on the device and served, the interval scan in wall-clock ms, the device stage
+ * (k_jpeg_entropy and what zeroes its blocks) in device ms, and the bytes of the uploaded files.  Any pointer may be NULL.
+ * yolo_jpeg_decode_times keeps its meaning: the host stage's wall clock, all uploads, the IDCT launch. */
+int yolo_jpeg_entropy_times(yolo_ctx *ctx, int *device_files, int *host_files, int *intervals, double *scan_ms, double *device_ms,
+                            size_t *stream_bytes);
+/* The interval scan by itself, host only: the restart intervals of an eligible file, interval i the bytes begin_out[i] .. end_out[i] - 1
+ * of it, *n_out their count (cap: the room in the two arrays, either of which may be NULL).  A file that is not eligible: YOLO_OK and
+ * *n_out = 0.  A file whose headers are refused: that refusal. */
+int yolo_jpeg_intervals(const uint8_t *file, size_t bytes, uint32_t *begin_out, uint32_t *end_out, size_t cap, size_t *n_out);
+/* One file through scan, upload, k_jpeg_entropy and read-back: coef_out as yolo_jpeg_coefficients.  YOLO_ERR_UNSUPPORTED ("no restart
+ * interval") for a file without DRI; for a file that is not eligible, or that the device hands back, the host stage's result. */
+int yolo_op_jpeg_entropy(const uint8_t *file, size_t bytes, int16_t *coef_out, size_t cap_blocks, int device);
 /* yolo_decode_jpegs, then yolo_forward_frames_u8 / yolo_detect_frames_u8 / yolo_detect_tiled_frames_u8 over its table: the
  * arguments of those, with (files, bytes, n) in the place of the packed buffer, its descriptors and its location. */
 int yolo_forward_jpegs(yolo_ctx *ctx, const uint8_t *const *files, const size_t *bytes, int n, int fit, float *detections_out, int out_loc);

@@ -12,7 +12,9 @@ weights, max_batch 32, one process.
           (d) classify_views over the same pictures as host RGB (hip.frame_to_rgb of the frames: the same answer, which the tool checks): 3 bytes per pixel
 Host clock around each call (each ends in the copy of the records to the host), median per round, median over rounds, rounds alternating.
 
-  python tools/classify_files_rate.py [--host-steps 6] [--rounds 5] [--out JSON] [--only both | views] [--kernel-stats STATS_CSV]
+          --entropy both | host | auto: (a) under each entropy mode, alternating within every round; "auto" decodes dog.jpg's 36 restart
+          intervals per file on the device from the uploaded file bytes; its split adds Engine.jpeg_entropy_times.
+  python tools/classify_files_rate.py [--host-steps 6] [--rounds 5] [--out JSON] [--only both | views] [--entropy both | host | auto] [--kernel-stats STATS_CSV]
 
 --only views: run (c) and (d) alone (the process to run under `rocprofv3 --kernel-trace --stats`); --kernel-stats: read that run's kernel_stats.csv and add
 the per-step view-fit launches' own average times (k_fit_frames over the view table, k_fit_images over the view table).  Prints one JSON line."""
@@ -48,6 +50,7 @@ def main():
     ap.add_argument("--host-steps", type=int, default=6)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--only", choices=["both", "views"], default="both")
+    ap.add_argument("--entropy", choices=["both", "host", "auto"], default="both")
     ap.add_argument("--kernel-stats", default=None)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
@@ -96,10 +99,19 @@ def main():
         def pil_decode():
             return [np.asarray(Image.open(io.BytesIO(f)).convert("RGB")) for f in files]
         pictures = pil_decode()
+        modes = ["host", "auto"] if args.entropy == "both" else [args.entropy]
         ta, tp, ti, split = [], [], [], []
+        auto_ms, auto_split, auto_equal = [], [], None
         for _ in range(args.rounds):
-            ta.append(host_timed(lambda: eng.classify_jpegs(files, fit=fit, top_k=top)))
-            split.append(eng.jpeg_decode_times())
+            for m in modes:
+                eng.set_jpeg_entropy(m)
+                t = host_timed(lambda: eng.classify_jpegs(files, fit=fit, top_k=top))
+                if m == modes[0]:
+                    ta.append(t); split.append(eng.jpeg_decode_times())
+                else:
+                    auto_ms.append(t); auto_split.append(dict(eng.jpeg_decode_times(), **eng.jpeg_entropy_times()))
+                    auto_equal = same(eng.classify_jpegs(files, fit=fit, top_k=top), eng.classify_images([twin] * B, fit=fit, top_k=top))
+            eng.set_jpeg_entropy("host")
             tp.append(host_timed(pil_decode))
             ti.append(host_timed(lambda: eng.classify_images(pictures, fit=fit, top_k=top)))
         med = lambda k: float(np.median([s[k] for s in split]))
@@ -112,7 +124,17 @@ def main():
             "pil_plus_classify_images_ms": float(np.median(tp) + np.median(ti)),
             "jpegs_over_pil_path": float(np.median(ta) / (np.median(tp) + np.median(ti))),
             "split": {"entropy_ms": med("entropy_ms"), "upload_ms": med("upload_ms"), "upload_bytes": int(split[-1]["upload_bytes"]), "idct_ms": med("idct_ms")},
+            "entropy_mode": modes[0],
         }
+        if auto_ms:
+            amed = lambda k: float(np.median([s[k] for s in auto_split]))
+            out["files"]["auto"] = {
+                "classify_jpegs_call_ms": float(np.median(auto_ms)), "classify_jpegs_rounds_ms": auto_ms, "records_equal_host_twin": auto_equal,
+                "auto_over_host": float(np.median(auto_ms) / np.median(ta)),
+                "split": {"entropy_ms": amed("entropy_ms"), "upload_ms": amed("upload_ms"), "upload_bytes": int(auto_split[-1]["upload_bytes"]), "idct_ms": amed("idct_ms"),
+                          "scan_ms": amed("scan_ms"), "device_entropy_ms": amed("device_ms"), "stream_bytes": int(auto_split[-1]["stream_bytes"]),
+                          "device_files": auto_split[-1]["device_files"], "intervals": auto_split[-1]["intervals"]},
+            }
 
     distinct = FR.nv12_pictures(hip, 4)
     rgb_distinct = [hip.frame_to_rgb(f) for f in distinct]

@@ -8,7 +8,7 @@ from . import hip, darknet_io as IO
 
 
 class Classifier:
-    def __init__(self, cfg_or_name, weights_file=None, dtype=hip.BF16, max_batch=1, names=None, device=0, fit=hip.FIT_STRETCH, seed=0, hierarchy=None):
+    def __init__(self, cfg_or_name, weights_file=None, dtype=hip.BF16, max_batch=1, names=None, device=0, fit=hip.FIT_STRETCH, seed=0, hierarchy=None, jpeg_entropy="host"):
         """cfg_or_name: a shipped topology ('darknet19', 'darknet53', 'resnet18', 'resnet50', 'resnext50', 'vgg-16'), a cfg file path, or cfg text
         (a ResNet's [shortcut] layers with fewer or larger `from` tensors and any of darknet's thirteen activations are served).  weights_file: a darknet
         `.weights` file; None loads darknet_io's seeded synthetic parameters (`seed`).  names: a list of class names or the path of a
@@ -16,7 +16,8 @@ class Classifier:
         input, a hip.FIT_* code -- hip.FIT_CENTER_CROP is darknet's validation preprocessing (resize_min to the network width, then the centred
         crop), e.g. for 'alexnet-lrn'.  hierarchy (a [softmax] with tree=): None
         returns the conditional probabilities network_predict gives, "absolute" the products along the path to the root
-        (hierarchy_predictions), "leaves" those with every inner node zeroed -- what darknet's classifier apps rank."""
+        (hierarchy_predictions), "leaves" those with every inner node zeroed -- what darknet's classifier apps rank.  jpeg_entropy: "host" or "auto" --
+        who Huffman-decodes the files of classify_from_files (Engine.set_jpeg_entropy); the results are the same."""
         text = cfg_or_name if "[net]" in cfg_or_name or "[network]" in cfg_or_name else IO.cfg_text(cfg_or_name)
         text = IO.with_planes_input(text)          # darknet's own grey / multi-plane cfgs ([net] channels != 3) load unchanged
         self.engine = hip.Engine(text, max_batch=max_batch, dtype=dtype, semantics=hip.SEM_DARKNET, device=device)
@@ -27,6 +28,8 @@ class Classifier:
             self.engine.load_weights(weights_file)
         else:
             self.engine.set_weights(IO.synth_weights(IO.parse_cfg(text), seed=seed))
+        if jpeg_entropy != "host":
+            self.engine.set_jpeg_entropy(jpeg_entropy)
         if hierarchy is not None:
             self.engine.set_hierarchy_mode(hierarchy)
         self.max_batch, self.fit = max_batch, fit

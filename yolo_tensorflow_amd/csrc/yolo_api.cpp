@@ -87,8 +87,8 @@ void yolo_destroy(yolo_ctx *c)
     for (void *p : ptrs) if (p) hipFree(p);
     for (auto &t : c->trees) free_tree(t);
     if (c->d_map200) hipFree(c->d_map200);
-    for (void *p : {c->d_jin, (void *)c->d_jpeg}) if (p) hipFree(p);
-    if (c->h_jin) hipHostFree(c->h_jin);
+    for (void *p : {c->d_jin, (void *)c->d_jpeg, c->d_jst, (void *)c->d_jstream}) if (p) hipFree(p);
+    for (void *p : {c->h_jin, c->h_jst}) if (p) hipHostFree(p);
     if (c->jpeg_up) hipEventDestroy(c->jpeg_up);
     for (hipEvent_t ev : c->jpeg_t) if (ev) hipEventDestroy(ev);
     drop_graph(c);

@@ -178,7 +178,16 @@ struct yolo_ctx {
     } jpeg;
     void *h_jin = nullptr, *d_jin = nullptr; size_t jin_cap = 0; uint8_t *d_jpeg = nullptr; size_t jpeg_cap = 0; hipEvent_t jpeg_up = nullptr; bool jpeg_up_pending = false;
     // what the last decode cost (yolo_jpeg_decode_times): wall time of the entropy stage, bytes uploaded, events in front of the upload, behind it, behind the IDCT
-    hipEvent_t jpeg_t[3] = {nullptr, nullptr, nullptr}; double jpeg_entropy_ms = 0; size_t jpeg_upload_bytes = 0;
+    // ([3]: behind k_jpeg_entropy, in front of the IDCT, recorded by a decode that ran the device's entropy stage)
+    hipEvent_t jpeg_t[4] = {nullptr, nullptr, nullptr, nullptr}; double jpeg_entropy_ms = 0; size_t jpeg_upload_bytes = 0;
+    // the entropy stage over restart intervals (yolo_set_jpeg_entropy).  jpeg_entropy_mode: YOLO_JPEG_ENTROPY_*; jent: the eligible files of the
+    // batch being decoded as k_jpeg_entropy reads them; h_jst: pinned staging of {file records, workgroup table, interval table} and, behind them, of the status
+    // words that come back; d_jst: its device copy; d_jstream: the eligible files' bytes (all grown on demand, never shrunk).  je_*: what the last decode did
+    // (yolo_jpeg_entropy_times)
+    int jpeg_entropy_mode = 0;
+    yolo_impl::JpegEntropyPlan jent; std::vector<std::vector<yolo_impl::JpegInterval>> jpeg_iv;
+    void *h_jst = nullptr, *d_jst = nullptr; size_t jst_cap = 0; uint8_t *d_jstream = nullptr; size_t jstream_cap = 0;
+    int je_dev_files = 0, je_host_files = 0, je_intervals = 0; double je_scan_ms = 0; size_t je_stream_bytes = 0;
     // tiled detection (yolo_detect_tiled_u8): ONE allocation, grown on demand and never shrunk, that holds the window table, the image table, every
     // image's merged candidate list and k_nms_image's workspace over those lists (tile_slab, yolo_run.cpp)
     void *d_tile = nullptr; size_t tile_cap = 0;

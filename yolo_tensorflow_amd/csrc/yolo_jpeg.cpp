@@ -6,6 +6,7 @@
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
+#include <algorithm>
 #include <atomic>
 #include <mutex>
 #include <new>
@@ -280,14 +281,16 @@ int jpeg_decode(const uint8_t *p, size_t n, int index, const JpegFile &f, int16_
     return YOLO_OK;
 }
 
-int jpeg_decode_batch(const uint8_t *const *files, const size_t *bytes, int n, const JpegFile *parsed, const size_t *first_block, int16_t *coef, std::string &msg)
+int jpeg_decode_some(const uint8_t *const *files, const size_t *bytes, const int *which, int count, const JpegFile *parsed, const size_t *first_block, int16_t *coef, std::string &msg)
 {
-    if (n == 1) return jpeg_decode(files[0], bytes[0], 0, parsed[0], coef + first_block[0] * 64, msg);
+    const auto file_of = [&](int k) { return which ? which[k] : k; };
+    if (count == 1) { const int i = file_of(0); return jpeg_decode(files[i], bytes[i], i, parsed[i], coef + first_block[i] * 64, msg); }
     std::atomic<int> next{0};
     std::mutex mu;
-    int bad = n, bad_rc = YOLO_OK;
+    int bad = 0x7fffffff, bad_rc = YOLO_OK;
     auto work = [&]() {
-        for (int i; (i = next.fetch_add(1)) < n;) {
+        for (int k; (k = next.fetch_add(1)) < count;) {
+            const int i = file_of(k);
             std::string m;
             const int r = jpeg_decode(files[i], bytes[i], i, parsed[i], coef + first_block[i] * 64, m);
             if (r) { std::lock_guard<std::mutex> lock(mu); if (i < bad) { bad = i; bad_rc = r; msg = m; } }
@@ -295,10 +298,74 @@ int jpeg_decode_batch(const uint8_t *const *files, const size_t *bytes, int n, c
     };
     std::vector<std::thread> pool;
     // a thread the system will not start (or a table it will not allocate) is done without: the threads that did start and the caller share the files
-    try { for (int t = 1; t < (n < 8 ? n : 8); ++t) pool.emplace_back(work); } catch (const std::system_error &) {} catch (const std::bad_alloc &) {}
+    try { for (int t = 1; t < (count < 8 ? count : 8); ++t) pool.emplace_back(work); } catch (const std::system_error &) {} catch (const std::bad_alloc &) {}
     work();
     for (auto &t : pool) t.join();
     return bad_rc;
+}
+
+int jpeg_decode_batch(const uint8_t *const *files, const size_t *bytes, int n, const JpegFile *parsed, const size_t *first_block, int16_t *coef, std::string &msg)
+{
+    return jpeg_decode_some(files, bytes, nullptr, n, parsed, first_block, coef, msg);
+}
+
+bool jpeg_intervals(const uint8_t *p, size_t n, const JpegFile &f, std::vector<JpegInterval> &out)
+{
+    out.clear();
+    const size_t mcus = (size_t)f.mcux * f.mcuy;
+    if (!p || f.restart < 1 || n > 0xffffffffull || f.scan > n || mcus < 1 || mcus > 0xffffffffull || f.blocks > 0xffffffffull) return false;
+    const size_t count = (mcus + (size_t)f.restart - 1) / (size_t)f.restart;
+    if (count > (n - f.scan) / 2 + 1) return false;          // every marker takes two bytes: the file cannot hold them (and the table is not sized from a header alone)
+    out.reserve(count);
+    // where Bits::restart() would find a marker at `at`: behind any fill bytes.  0: none
+    const auto marker = [&](size_t at) -> size_t {
+        while (at + 1 < n && p[at] == 0xff && p[at + 1] == 0xff) ++at;
+        return at + 1 < n && p[at] == 0xff && p[at + 1] >= 0xd0 && p[at + 1] <= 0xd7 ? at + 2 : 0;
+    };
+    size_t pos = f.scan;
+    for (size_t i = 0; i < count; ++i) {
+        const size_t begin = pos;
+        while (pos < n) {
+            const uint8_t *ff = (const uint8_t *)memchr(p + pos, 0xff, n - pos);
+            if (!ff) { pos = n; break; }
+            pos = (size_t)(ff - p);
+            if (pos + 1 < n && p[pos + 1] == 0) pos += 2; else break;
+        }
+        out.push_back(JpegInterval{(uint32_t)begin, (uint32_t)pos, (uint32_t)(i * (size_t)f.restart), (uint32_t)std::min<size_t>((size_t)f.restart, mcus - i * (size_t)f.restart)});
+        const size_t next = marker(pos);
+        if ((i + 1 < count) != (next != 0)) { out.clear(); return false; }          // a marker missing, something else in its place, or one marker too many
+        pos = next;
+    }
+    return true;
+}
+
+void jpeg_entropy_tables(const JpegFile &f, JpegEntropyTables *t, JpegGeom *g)
+{
+    memset(t, 0, sizeof *t); memset(g, 0, sizeof *g);
+    const auto put = [](JpegHuffTable &d, const JpegHuff &s) {
+        memcpy(d.look, s.look, sizeof d.look); memcpy(d.vals, s.vals, sizeof d.vals);
+        memcpy(d.maxcode, s.maxcode, sizeof d.maxcode); memcpy(d.delta, s.delta, sizeof d.delta);
+        d.delta[0] = 0; d.maxcode[0] = 0;          // (never read, and never set by build_huffman)
+    };
+    g->comps = f.comps; g->hs = f.hs; g->vs = f.vs; g->mcux = f.mcux;
+    for (int c = 0; c < f.comps; ++c) {
+        put(t->dc[c], f.dc[f.td[c]]); put(t->ac[c], f.ac[f.ta[c]]);
+        memcpy(t->quant[c], f.quant[f.tq[c]], sizeof t->quant[c]);
+        g->bw[c] = (uint32_t)f.bw[c]; g->block0[c] = (uint32_t)f.block0[c];
+    }
+}
+
+void JpegEntropyPlan::add(const JpegFile &f, size_t bytes, const std::vector<JpegInterval> &intervals, size_t block0)
+{
+    files.emplace_back();
+    JpegDevFile &d = files.back();
+    jpeg_entropy_tables(f, &d.t, &d.g);
+    d.stream0 = stream_bytes; d.block0 = block0; d.bytes = (uint32_t)bytes; d.blocks = (uint32_t)f.blocks;
+    stream_bytes += (bytes + 15) & ~(size_t)15;
+    iv.insert(iv.end(), intervals.begin(), intervals.end());
+    iv.resize((iv.size() + JPEG_ENTROPY_LANES - 1) / JPEG_ENTROPY_LANES * JPEG_ENTROPY_LANES, JpegInterval{0, 0, 0, 0});
+    wg_file.resize(iv.size() / JPEG_ENTROPY_LANES, (uint32_t)(files.size() - 1));
+    first_slot.push_back(iv.size());
 }
 
 }  // namespace yolo_impl

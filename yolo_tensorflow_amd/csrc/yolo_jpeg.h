@@ -6,6 +6,8 @@
 #include <stddef.h>
 #include <stdint.h>
 #include <string>
+#include <vector>
+#include "jpeg_entropy.h"
 
 namespace yolo_impl {
 
@@ -43,5 +45,26 @@ int jpeg_decode(const uint8_t *file, size_t bytes, int index, const JpegFile &f,
 // a parsed batch: file i into coef + first_block[i] * 64, by min(n, 8) threads that take one file at a time each (one thread, the caller's, when n == 1; the
 // pool is never sized from the machine's processor count).  The failure of the lowest index is the one reported
 int jpeg_decode_batch(const uint8_t *const *files, const size_t *bytes, int n, const JpegFile *parsed, const size_t *first_block, int16_t *coef, std::string &msg);
+// the same for files which[0 .. count) of the batch alone (ascending indices; each keeps its index in the batch, in its messages too)
+int jpeg_decode_some(const uint8_t *const *files, const size_t *bytes, const int *which, int count, const JpegFile *parsed, const size_t *first_block, int16_t *coef, std::string &msg);
+
+// ---- the entropy stage over restart intervals (jpeg_entropy.h) ----
+// One pass over the entropy-coded segment of a parsed file: its ceil(mcus / restart) restart intervals, `begin` the byte behind the preceding RSTm marker (f.scan
+// for the first), `end` the offset of the first 0xFF that no 0x00 follows, or the file's end.  true: the file is ELIGIBLE for the interval decoder -- it has a DRI,
+// its offsets fit 32 bits, and behind every interval but the last lies exactly what Bits::restart() accepts (fill bytes 0xFF, then one of 0xFF 0xD0 .. 0xD7) and
+// behind the last no further such marker.  false is no error: the file goes to jpeg_decode, whose verdict stands; `out` is then left empty
+bool jpeg_intervals(const uint8_t *file, size_t bytes, const JpegFile &f, std::vector<JpegInterval> &out);
+// the tables and the geometry of a parsed file as the interval decoder reads them
+void jpeg_entropy_tables(const JpegFile &f, JpegEntropyTables *t, JpegGeom *g);
+// the eligible files of a batch as k_jpeg_entropy reads them (launch_jpeg_entropy, jpeg_entropy.h): one record per file, the interval table with every file's
+// intervals padded to whole workgroups by idle slots, the file of every workgroup.  Entry k's slots are first_slot[k] .. first_slot[k + 1] - 1; its bytes begin at
+// files[k].stream0 of a stream buffer of stream_bytes bytes
+struct JpegEntropyPlan {
+    std::vector<JpegDevFile> files; std::vector<uint32_t> wg_file; std::vector<JpegInterval> iv; std::vector<size_t> first_slot{0};
+    size_t stream_bytes = 0;
+    void clear() { files.clear(); wg_file.clear(); iv.clear(); first_slot.assign(1, 0); stream_bytes = 0; }
+    // one more file: parsed, `bytes` long, with the intervals jpeg_intervals found, its blocks at block0 of the batch's coefficient array
+    void add(const JpegFile &f, size_t bytes, const std::vector<JpegInterval> &intervals, size_t block0);
+};
 
 }  // namespace yolo_impl

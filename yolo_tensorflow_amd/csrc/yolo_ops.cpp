@@ -579,6 +579,35 @@ int yolo_op_jpeg_to_rgb(const uint8_t *file, size_t bytes, uint8_t *rgb_out, int
     return S.download(rgb_out, d_o, out_bytes);
 }
 
+// one JPEG file through the device's entropy stage: interval scan, upload, k_jpeg_entropy, read-back.  A file the scan does not find eligible, or
+// one with a failed or doubtful interval, is the host stage's: its coefficients, or its refusal
+int yolo_op_jpeg_entropy(const uint8_t *file, size_t bytes, int16_t *coef_out, size_t cap_blocks, int device)
+{
+    if (!file || !coef_out) { g_op_err = "jpeg_entropy: file / coef_out == NULL"; return YOLO_ERR_INVALID; }
+    JpegFile jf;
+    if (int r = jpeg_parse(file, bytes, 0, &jf, g_op_err)) return r;
+    if (!jf.restart) { g_op_err = "jpeg_entropy: file 0: no restart interval (DRI): the device's entropy stage decodes restart intervals"; return YOLO_ERR_UNSUPPORTED; }
+    if (cap_blocks < jf.blocks) { g_op_err = "jpeg_entropy: file 0: its " + std::to_string(jf.blocks) + " blocks do not fit coef_out's " + std::to_string(cap_blocks); return YOLO_ERR_INVALID; }
+    std::vector<JpegInterval> iv; JpegEntropyPlan P; std::vector<uint32_t> status;
+    bool eligible = false;
+    try { eligible = jpeg_intervals(file, bytes, jf, iv); if (eligible) { P.add(jf, bytes, iv, 0); status.resize(P.iv.size()); } }
+    catch (const std::bad_alloc &) { g_op_err = "jpeg_entropy: file 0: no memory for its intervals"; return YOLO_ERR_NOMEM; }
+    if (!eligible) return jpeg_decode(file, bytes, 0, jf, coef_out, g_op_err);
+    OpScope S(device); if (S.rc) { g_op_err = "jpeg_entropy: no HIP device"; return S.rc; }
+    const size_t slots = P.iv.size();
+    uint8_t *d_s = (uint8_t *)S.alloc(P.stream_bytes);
+    const JpegDevFile *d_f = (const JpegDevFile *)S.upload(P.files.data(), sizeof(JpegDevFile));
+    const uint32_t *d_w = (const uint32_t *)S.upload(P.wg_file.data(), P.wg_file.size() * 4);
+    const JpegInterval *d_i = (const JpegInterval *)S.upload(P.iv.data(), slots * sizeof(JpegInterval));
+    int16_t *d_c = (int16_t *)S.alloc(jf.blocks * 128); uint32_t *d_st = (uint32_t *)S.alloc(slots * 4);
+    if (S.rc) { g_op_err = "jpeg_entropy: allocation failed"; return S.rc; }
+    if (!S.ok(hipMemcpyAsync(d_s, file, bytes, hipMemcpyHostToDevice, S.s))) { g_op_err = "jpeg_entropy: " + S.err; return S.rc; }
+    if (!S.ok(launch_jpeg_entropy(d_s, P.stream_bytes, d_f, 1, d_w, d_i, slots, d_c, jf.blocks, d_st, S.s))) { g_op_err = "jpeg_entropy: " + S.err; return S.rc; }
+    if (S.download(status.data(), d_st, slots * 4) || S.download(coef_out, d_c, jf.blocks * 128)) { g_op_err = "jpeg_entropy: " + std::string(hipGetErrorString(hipGetLastError())); return S.rc; }
+    for (uint32_t st : status) if (st) return jpeg_decode(file, bytes, 0, jf, coef_out, g_op_err);
+    return YOLO_OK;
+}
+
 int yolo_op_letterbox(const float *image_chw, int iw, int ih, int w, int h, int embed, float *out_chw, int device)
 {
     if (!image_chw || !out_chw || iw < 1 || ih < 1 || w < 1 || h < 1) { g_op_err = "letterbox: bad arguments"; return YOLO_ERR_INVALID; }

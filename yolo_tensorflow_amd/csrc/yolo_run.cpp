@@ -1407,12 +1407,11 @@ static int jpegs_plan(yolo_ctx *c, const uint8_t *const *files, const size_t *by
     return YOLO_OK;
 }
 
-// the planned batch onto the device: buffers, entropy stage into pinned memory, one upload, one launch
-static int jpegs_run(yolo_ctx *c, const uint8_t *const *files, const size_t *bytes, int n)
+// what every decode needs before its entropy stage: the staging of {plane table, coefficients} and its device copy (`need` bytes), the surface, the events; the
+// plane table at the staging's head
+static int jpegs_buffers(yolo_ctx *c, size_t need)
 {
     yolo_ctx::JpegBatch &J = c->jpeg;
-    HIPCK(c, hipSetDevice(c->device));
-    const size_t table = (J.planes.size() * sizeof(JpegPlane) + 255) & ~(size_t)255, need = table + J.blocks * 128;
     if (c->jpeg_up_pending) { HIPCK(c, hipEventSynchronize(c->jpeg_up)); c->jpeg_up_pending = false; }          // the staging is free again
     if (need > c->jin_cap || J.view_bytes > c->jpeg_cap) HIPCK(c, hipStreamSynchronize(c->stream));             // nothing in flight reads what moves
     if (need > c->jin_cap) {
@@ -1433,6 +1432,126 @@ static int jpegs_run(yolo_ctx *c, const uint8_t *const *files, const size_t *byt
     if (!c->jpeg_up) HIPCK(c, hipEventCreateWithFlags(&c->jpeg_up, hipEventDisableTiming));
     if (!c->jpeg_t[0]) for (auto &ev : c->jpeg_t) HIPCK(c, hipEventCreate(&ev));
     memcpy(c->h_jin, J.planes.data(), J.planes.size() * sizeof(JpegPlane));
+    return YOLO_OK;
+}
+
+// YOLO_JPEG_ENTROPY_AUTO with at least one eligible file (c->jpeg_iv[i] non-empty: file i's intervals).  The others go through the host stage into their ranges of
+// the staging; the eligible ones are decoded by k_jpeg_entropy into theirs of the device array; one IDCT launch; the status words come back and are waited for.
+// A file with a non-zero word is decoded again by the host stage, whose verdict stands
+static int jpegs_run_device(yolo_ctx *c, const uint8_t *const *files, const size_t *bytes, int n)
+{
+    yolo_ctx::JpegBatch &J = c->jpeg;
+    JpegEntropyPlan &P = c->jent;
+    const size_t table = (J.planes.size() * sizeof(JpegPlane) + 255) & ~(size_t)255, need = table + J.blocks * 128;
+    if (int r = jpegs_buffers(c, need)) return r;
+    std::vector<int> host, dev;
+    try {
+        P.clear();
+        for (int i = 0; i < n; ++i)
+            if (c->jpeg_iv[i].empty()) host.push_back(i);
+            else { dev.push_back(i); P.add(J.files[i], bytes[i], c->jpeg_iv[i], J.first_block[i]); }
+    } catch (const std::bad_alloc &) { return fail(c, YOLO_ERR_NOMEM, "the interval table of %d files", n); }
+    const size_t slots = P.iv.size(), at_wg = (P.files.size() * sizeof(JpegDevFile) + 15) & ~(size_t)15, at_iv = (at_wg + P.wg_file.size() * 4 + 15) & ~(size_t)15,
+                 at_status = at_iv + slots * sizeof(JpegInterval), jst = at_status + slots * 4;
+    if (slots > 0x7fffffc0ull) return fail(c, YOLO_ERR_UNSUPPORTED, "%zu restart intervals in one batch; decode fewer files per call", slots);
+    if (jst > c->jst_cap || P.stream_bytes > c->jstream_cap) HIPCK(c, hipStreamSynchronize(c->stream));
+    if (jst > c->jst_cap) {
+        if (c->h_jst) HIPCK(c, hipHostFree(c->h_jst));
+        if (c->d_jst) HIPCK(c, hipFree(c->d_jst));
+        c->h_jst = c->d_jst = nullptr; c->jst_cap = 0;
+        const size_t cap = jst + jst / 4;
+        HIPCK(c, hipHostMalloc(&c->h_jst, cap, hipHostMallocDefault));
+        HIPCK(c, hipMalloc(&c->d_jst, cap));
+        c->jst_cap = cap;
+    }
+    if (P.stream_bytes > c->jstream_cap) {
+        if (c->d_jstream) HIPCK(c, hipFree(c->d_jstream));
+        c->d_jstream = nullptr; c->jstream_cap = 0;
+        const size_t cap = P.stream_bytes + P.stream_bytes / 4;
+        HIPCK(c, hipMalloc((void **)&c->d_jstream, cap));
+        c->jstream_cap = cap;
+    }
+    memcpy(c->h_jst, P.files.data(), P.files.size() * sizeof(JpegDevFile));
+    memcpy((char *)c->h_jst + at_wg, P.wg_file.data(), P.wg_file.size() * 4);
+    memcpy((char *)c->h_jst + at_iv, P.iv.data(), slots * sizeof(JpegInterval));
+    int16_t *const h_coef = (int16_t *)((char *)c->h_jin + table), *const d_coef = (int16_t *)((char *)c->d_jin + table);
+    std::string msg;
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!host.empty() && jpeg_decode_some(files, bytes, host.data(), (int)host.size(), J.files.data(), J.first_block.data(), h_coef, msg)) {
+        // the batch has a malformed file: the verdict is the host stage's over the WHOLE batch, which names the lowest index that fails
+        const int r = jpeg_decode_batch(files, bytes, n, J.files.data(), J.first_block.data(), h_coef, msg);
+        return fail(c, r ? r : YOLO_ERR_INVALID, "%s", msg.c_str());
+    }
+    c->jpeg_entropy_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    // files i .. j - 1 of a list that are neighbours in the batch share one copy of their blocks
+    const auto runs = [&](const std::vector<int> &list, const auto &each) -> hipError_t {
+        for (size_t i = 0; i < list.size();) {
+            size_t j = i + 1;
+            while (j < list.size() && list[j] == list[j - 1] + 1) ++j;
+            const size_t b0 = J.first_block[list[i]], b1 = J.first_block[list[j - 1]] + J.files[list[j - 1]].blocks;
+            if (hipError_t e = each(b0 * 64, (b1 - b0) * 128)) return e;
+            i = j;
+        }
+        return hipSuccess;
+    };
+    size_t up = table + jst - slots * 4 + P.stream_bytes;
+    for (int i : host) up += J.files[i].blocks * 128;
+    c->jpeg_upload_bytes = up;
+    HIPCK(c, hipEventRecord(c->jpeg_t[0], c->stream));
+    HIPCK(c, hipMemcpyAsync(c->d_jin, c->h_jin, table, hipMemcpyHostToDevice, c->stream));
+    HIPCK(c, runs(host, [&](size_t at, size_t len) { return hipMemcpyAsync(d_coef + at, h_coef + at, len, hipMemcpyHostToDevice, c->stream); }));
+    HIPCK(c, hipMemcpyAsync(c->d_jst, c->h_jst, at_status, hipMemcpyHostToDevice, c->stream));
+    HIPCK(c, hipEventRecord(c->jpeg_up, c->stream));
+    c->jpeg_up_pending = true;
+    // (the files' bytes come from the caller's pageable memory: the runtime stages them, and the call waits for the stream below before it returns)
+    for (size_t k = 0; k < dev.size(); ++k) HIPCK(c, hipMemcpyAsync(c->d_jstream + P.files[k].stream0, files[dev[k]], bytes[dev[k]], hipMemcpyHostToDevice, c->stream));
+    HIPCK(c, hipEventRecord(c->jpeg_t[1], c->stream));
+    uint32_t *const d_status = (uint32_t *)((char *)c->d_jst + at_status);
+    const uint32_t *const h_status = (const uint32_t *)((const char *)c->h_jst + at_status);
+    HIPCK(c, launch_jpeg_entropy(c->d_jstream, c->jstream_cap, (const JpegDevFile *)c->d_jst, (int)P.files.size(), (const uint32_t *)((const char *)c->d_jst + at_wg),
+                                 (const JpegInterval *)((const char *)c->d_jst + at_iv), slots, d_coef, J.blocks, d_status, c->stream));
+    HIPCK(c, hipEventRecord(c->jpeg_t[3], c->stream));
+    HIPCK(c, launch_jpeg_idct(d_coef, (const JpegPlane *)c->d_jin, (int)J.planes.size(), J.blocks, c->d_jpeg, c->jpeg_cap, c->stream));
+    HIPCK(c, hipEventRecord(c->jpeg_t[2], c->stream));
+    HIPCK(c, hipMemcpyAsync((char *)c->h_jst + at_status, d_status, slots * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    c->jpeg_up_pending = false;
+    c->je_dev_files = (int)dev.size(); c->je_host_files = (int)host.size(); c->je_stream_bytes = P.stream_bytes;
+    std::vector<int> again;
+    for (size_t k = 0; k < dev.size(); ++k) {
+        bool clean = true;
+        for (size_t i = P.first_slot[k]; clean && i < P.first_slot[k + 1]; ++i) clean = h_status[i] == 0;
+        if (clean) c->je_intervals += (int)c->jpeg_iv[dev[k]].size(); else again.push_back(dev[k]);          // (a file handed back counts as the host's, its intervals too)
+    }
+    if (again.empty()) return YOLO_OK;
+    // failed or doubtful intervals: those files again, in full, by the host stage -- served, or refused in its words --, and the IDCT again over the batch
+    if (int r = jpeg_decode_some(files, bytes, again.data(), (int)again.size(), J.files.data(), J.first_block.data(), h_coef, msg)) return fail(c, r, "%s", msg.c_str());
+    HIPCK(c, runs(again, [&](size_t at, size_t len) { return hipMemcpyAsync(d_coef + at, h_coef + at, len, hipMemcpyHostToDevice, c->stream); }));
+    HIPCK(c, hipEventRecord(c->jpeg_up, c->stream));
+    c->jpeg_up_pending = true;
+    HIPCK(c, launch_jpeg_idct(d_coef, (const JpegPlane *)c->d_jin, (int)J.planes.size(), J.blocks, c->d_jpeg, c->jpeg_cap, c->stream));
+    c->je_dev_files -= (int)again.size(); c->je_host_files += (int)again.size();
+    return YOLO_OK;
+}
+
+// the planned batch onto the device: buffers, entropy stage into pinned memory, one upload, one launch
+static int jpegs_run(yolo_ctx *c, const uint8_t *const *files, const size_t *bytes, int n)
+{
+    yolo_ctx::JpegBatch &J = c->jpeg;
+    HIPCK(c, hipSetDevice(c->device));
+    c->je_dev_files = 0; c->je_host_files = n; c->je_intervals = 0; c->je_scan_ms = 0; c->je_stream_bytes = 0;
+    if (c->jpeg_entropy_mode == YOLO_JPEG_ENTROPY_AUTO) {
+        const auto t0 = std::chrono::steady_clock::now();
+        bool any = false;
+        try {
+            c->jpeg_iv.resize((size_t)n);
+            for (int i = 0; i < n; ++i) any |= jpeg_intervals(files[i], bytes[i], J.files[i], c->jpeg_iv[i]);
+        } catch (const std::bad_alloc &) { return fail(c, YOLO_ERR_NOMEM, "the interval table of %d files", n); }
+        c->je_scan_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        if (any) return jpegs_run_device(c, files, bytes, n);
+    }
+    const size_t table = (J.planes.size() * sizeof(JpegPlane) + 255) & ~(size_t)255, need = table + J.blocks * 128;
+    if (int r = jpegs_buffers(c, need)) return r;
     std::string msg;
     const auto t0 = std::chrono::steady_clock::now();
     if (int r = jpeg_decode_batch(files, bytes, n, J.files.data(), J.first_block.data(), (int16_t *)((char *)c->h_jin + table), msg)) return fail(c, r, "%s", msg.c_str());
@@ -1500,11 +1619,55 @@ int yolo_jpeg_decode_times(yolo_ctx *c, double *entropy_ms, double *upload_ms, d
     HIPCK(c, hipEventSynchronize(c->jpeg_t[2]));
     float up = 0.f, idct = 0.f;
     HIPCK(c, hipEventElapsedTime(&up, c->jpeg_t[0], c->jpeg_t[1]));
-    HIPCK(c, hipEventElapsedTime(&idct, c->jpeg_t[1], c->jpeg_t[2]));
+    HIPCK(c, hipEventElapsedTime(&idct, c->jpeg_t[c->je_stream_bytes ? 3 : 1], c->jpeg_t[2]));          // (behind the device's entropy stage where the decode ran one)
     if (entropy_ms) *entropy_ms = c->jpeg_entropy_ms;
     if (upload_ms) *upload_ms = up;
     if (idct_ms) *idct_ms = idct;
     if (upload_bytes) *upload_bytes = c->jpeg_upload_bytes;
+    return YOLO_OK;
+}
+
+int yolo_set_jpeg_entropy(yolo_ctx *c, int mode)
+{
+    if (!c) return YOLO_ERR_INVALID;
+    if (mode != YOLO_JPEG_ENTROPY_HOST && mode != YOLO_JPEG_ENTROPY_AUTO) return fail(c, YOLO_ERR_INVALID, "yolo_set_jpeg_entropy: mode %d (YOLO_JPEG_ENTROPY_HOST or YOLO_JPEG_ENTROPY_AUTO)", mode);
+    c->jpeg_entropy_mode = mode;
+    return YOLO_OK;
+}
+
+int yolo_jpeg_entropy(yolo_ctx *c) { return c ? c->jpeg_entropy_mode : YOLO_ERR_INVALID; }
+
+int yolo_jpeg_entropy_times(yolo_ctx *c, int *device_files, int *host_files, int *intervals, double *scan_ms, double *device_ms, size_t *stream_bytes)
+{
+    if (!c) return YOLO_ERR_INVALID;
+    if (!c->jpeg_t[0] || !c->jpeg_upload_bytes) return fail(c, YOLO_ERR_STATE, "yolo_jpeg_entropy_times before any decode on this context");
+    float dev = 0.f;
+    if (c->je_stream_bytes) {
+        HIPCK(c, hipSetDevice(c->device));
+        HIPCK(c, hipEventSynchronize(c->jpeg_t[3]));
+        HIPCK(c, hipEventElapsedTime(&dev, c->jpeg_t[1], c->jpeg_t[3]));
+    }
+    if (device_files) *device_files = c->je_dev_files;
+    if (host_files) *host_files = c->je_host_files;
+    if (intervals) *intervals = c->je_intervals;
+    if (scan_ms) *scan_ms = c->je_scan_ms;
+    if (device_ms) *device_ms = dev;
+    if (stream_bytes) *stream_bytes = c->je_stream_bytes;
+    return YOLO_OK;
+}
+
+int yolo_jpeg_intervals(const uint8_t *file, size_t bytes, uint32_t *begin_out, uint32_t *end_out, size_t cap, size_t *n_out)
+{
+    if (!file || !n_out) { g_op_err = "yolo_jpeg_intervals: file / n_out == NULL"; return YOLO_ERR_INVALID; }
+    *n_out = 0;
+    JpegFile f;
+    if (int r = jpeg_parse(file, bytes, 0, &f, g_op_err)) return r;
+    std::vector<JpegInterval> iv;
+    try { if (!jpeg_intervals(file, bytes, f, iv)) return YOLO_OK; } catch (const std::bad_alloc &) { g_op_err = "yolo_jpeg_intervals: file 0: no memory for its intervals"; return YOLO_ERR_NOMEM; }
+    *n_out = iv.size();
+    if (!begin_out && !end_out) return YOLO_OK;
+    if (cap < iv.size()) { g_op_err = "yolo_jpeg_intervals: file 0: its " + std::to_string(iv.size()) + " intervals do not fit the " + std::to_string(cap) + " of begin_out / end_out"; return YOLO_ERR_INVALID; }
+    for (size_t i = 0; i < iv.size(); ++i) { if (begin_out) begin_out[i] = iv[i].begin; if (end_out) end_out[i] = iv[i].end; }
     return YOLO_OK;
 }
 

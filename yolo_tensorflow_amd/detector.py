@@ -22,10 +22,11 @@ class _Detector:
     flags = None
     select_mode = hip.SELECT_GT
 
-    def __init__(self, weights_file, verbose=False, dtype=hip.BF16, device=0, weights=None, max_output_size=None, max_batch=1, average_frames=1):
+    def __init__(self, weights_file, verbose=False, dtype=hip.BF16, device=0, weights=None, max_output_size=None, max_batch=1, average_frames=1, jpeg_entropy="host"):
         """average_frames = K >= 2: video mode, as darknet's `detector demo` -- the boxes come from the mean of the detection layers' outputs over
         the last K frames (Engine.set_frame_average).  detect_from_image is then a time step of stream 0 and detect_from_images(images) one of the
-        streams 0 .. len(images) - 1 (at most max_batch); a stream's first K - 1 results are attenuated by the empty slots; reset_streams starts over."""
+        streams 0 .. len(images) - 1 (at most max_batch); a stream's first K - 1 results are attenuated by the empty slots; reset_streams starts over.
+        jpeg_entropy: "host" or "auto" -- who Huffman-decodes the files of detect_from_files (Engine.set_jpeg_entropy); the results are the same."""
         f = self.flags
         self.verbose = verbose
         self.threshold, self.iou_threshold = f.conf_threshold, f.iou_threshold
@@ -42,6 +43,8 @@ class _Detector:
             self.engine.set_weights(weights)
         else:
             self.engine.load_weights(weights_file, self.header_ints)
+        if jpeg_entropy != "host":
+            self.engine.set_jpeg_entropy(jpeg_entropy)
         self.average_frames = int(average_frames)
         if self.average_frames != 1:
             self.engine.set_frame_average(self.average_frames)

@@ -64,6 +64,7 @@ EXPORTS = [
     "yolo_frame_to_rgb_host", "yolo_op_frame_to_rgb", "yolo_forward_frames_u8", "yolo_detect_frames_u8", "yolo_detect_frames_graph", "yolo_detect_tiled_frames_u8",
     "yolo_jpeg_info", "yolo_jpeg_coefficients", "yolo_jpeg_to_rgb_host", "yolo_op_jpeg_to_rgb", "yolo_decode_jpegs", "yolo_jpeg_decode_times", "yolo_forward_jpegs", "yolo_detect_jpegs", "yolo_detect_tiled_jpegs",
     "yolo_classify_frames_u8", "yolo_classify_views_frames_u8", "yolo_segment_frames_u8", "yolo_classify_jpegs", "yolo_classify_views_jpegs", "yolo_segment_jpegs",
+    "yolo_set_jpeg_entropy", "yolo_jpeg_entropy", "yolo_jpeg_entropy_times", "yolo_jpeg_intervals", "yolo_op_jpeg_entropy",
 ]
 HIER_CONDITIONAL, HIER_ABSOLUTE, HIER_LEAVES = 0, 1, 2
 _HIER_MODES = {None: HIER_CONDITIONAL, "conditional": HIER_CONDITIONAL, "absolute": HIER_ABSOLUTE, "leaves": HIER_LEAVES}
@@ -208,6 +209,11 @@ def load_library():
     l.yolo_op_jpeg_to_rgb.argtypes = [P, SZ, P, I]
     l.yolo_decode_jpegs.argtypes = [P, P, P, I, P, C.POINTER(P), C.POINTER(SZ)]
     l.yolo_jpeg_decode_times.argtypes = [P, C.POINTER(D), C.POINTER(D), C.POINTER(D), C.POINTER(SZ)]
+    l.yolo_set_jpeg_entropy.argtypes = [P, I]
+    l.yolo_jpeg_entropy.argtypes = [P]
+    l.yolo_jpeg_entropy_times.argtypes = [P, C.POINTER(I), C.POINTER(I), C.POINTER(I), C.POINTER(D), C.POINTER(D), C.POINTER(SZ)]
+    l.yolo_jpeg_intervals.argtypes = [P, SZ, P, P, SZ, C.POINTER(SZ)]
+    l.yolo_op_jpeg_entropy.argtypes = [P, SZ, P, SZ, I]
     l.yolo_forward_jpegs.argtypes = [P, P, P, I, I, P, I]
     l.yolo_detect_jpegs.argtypes = [P, P, P, I, I, F, F, I, I, I, I, P, P, I]
     l.yolo_detect_tiled_jpegs.argtypes = [P, P, P, I, I, I, I, I, I, F, F, I, I, I, I, P, P, I]
@@ -451,6 +457,41 @@ def jpeg_coefficients(file):
     n = info.components
     coef = np.zeros((sum(info.blocks[p] for p in range(n)), 8, 8), dtype=np.int16)
     _op_check(l.yolo_jpeg_coefficients(data, len(data), coef.ctypes.data, coef.shape[0]), "yolo_jpeg_coefficients")
+    out, at = [], 0
+    for p in range(n):
+        out.append(coef[at:at + info.blocks[p]].reshape(info.plane_h[p] // 8, info.plane_w[p] // 8, 8, 8))
+        at += info.blocks[p]
+    return out
+
+
+JPEG_ENTROPY_HOST, JPEG_ENTROPY_AUTO = 0, 1          # YOLO_JPEG_ENTROPY_*: who Huffman-decodes the files of a batch (Engine.set_jpeg_entropy)
+_JPEG_ENTROPY = {"host": JPEG_ENTROPY_HOST, "auto": JPEG_ENTROPY_AUTO}
+
+
+def jpeg_intervals(file):
+    """The restart intervals of a JPEG file (bytes or a path) that the device's entropy stage would decode (yolo_jpeg_intervals): a uint32 array [n, 2],
+    interval i the bytes [i, 0] .. [i, 1] - 1 of the file.  Empty for a file that is not eligible -- no DRI segment, or a marker missing or out of place --:
+    such a file is the host stage's.  Host only."""
+    data = _jpeg_bytes(file)
+    l = load_library()
+    n = C.c_size_t()
+    _op_check(l.yolo_jpeg_intervals(data, len(data), None, None, 0, C.byref(n)), "yolo_jpeg_intervals")
+    begin, end = np.zeros(n.value, dtype=np.uint32), np.zeros(n.value, dtype=np.uint32)
+    if n.value:
+        _op_check(l.yolo_jpeg_intervals(data, len(data), begin.ctypes.data, end.ctypes.data, n.value, C.byref(n)), "yolo_jpeg_intervals")
+    return np.stack([begin, end], axis=1)
+
+
+def jpeg_coefficients_device(file, device=0):
+    """jpeg_coefficients through the device's entropy stage (yolo_op_jpeg_entropy): scan, upload, k_jpeg_entropy, read-back; the same arrays, bit for bit.
+    A file without a restart interval raises YoloError (-6); one the device hands back is decoded, or refused, by the host stage."""
+    data = _jpeg_bytes(file)
+    l = load_library()
+    info = _JpegInfo()
+    _op_check(l.yolo_jpeg_info(data, len(data), C.byref(info)), "yolo_jpeg_info")
+    n = info.components
+    coef = np.zeros((sum(info.blocks[p] for p in range(n)), 8, 8), dtype=np.int16)
+    _op_check(l.yolo_op_jpeg_entropy(data, len(data), coef.ctypes.data, coef.shape[0], int(device)), "yolo_op_jpeg_entropy")
     out, at = [], 0
     for p in range(n):
         out.append(coef[at:at + info.blocks[p]].reshape(info.plane_h[p] // 8, info.plane_w[p] // 8, 8, 8))
@@ -950,6 +991,25 @@ class Engine:
         e, u, i, b = C.c_double(), C.c_double(), C.c_double(), C.c_size_t()
         self._check(self.lib.yolo_jpeg_decode_times(self.ctx, C.byref(e), C.byref(u), C.byref(i), C.byref(b)), "yolo_jpeg_decode_times")
         return {"entropy_ms": e.value, "upload_ms": u.value, "idct_ms": i.value, "upload_bytes": b.value}
+
+    def set_jpeg_entropy(self, mode):
+        """Who Huffman-decodes the files of decode_jpegs and every *_jpegs method (yolo_set_jpeg_entropy): "host" (the default) -- host threads, every file --
+        or "auto" -- files with restart intervals on the device, one lane per interval, the others on the host, in one call.  Same results, same refusals."""
+        if mode not in _JPEG_ENTROPY and mode not in _JPEG_ENTROPY.values():
+            raise YoloError("set_jpeg_entropy: mode %r (\"host\" or \"auto\")" % (mode,))
+        self._check(self.lib.yolo_set_jpeg_entropy(self.ctx, _JPEG_ENTROPY.get(mode, mode)), "yolo_set_jpeg_entropy")
+
+    @property
+    def jpeg_entropy(self):
+        """"host" or "auto": the mode set_jpeg_entropy set"""
+        return "auto" if self.lib.yolo_jpeg_entropy(self.ctx) == JPEG_ENTROPY_AUTO else "host"
+
+    def jpeg_entropy_times(self):
+        """What the entropy stage of this engine's last decode did (yolo_jpeg_entropy_times): {"device_files", "host_files", "intervals" decoded on the
+        device, "scan_ms": host wall time of the interval scan, "device_ms": device time of k_jpeg_entropy, "stream_bytes": file bytes uploaded}."""
+        d, h, i, s, k, b = C.c_int(), C.c_int(), C.c_int(), C.c_double(), C.c_double(), C.c_size_t()
+        self._check(self.lib.yolo_jpeg_entropy_times(self.ctx, C.byref(d), C.byref(h), C.byref(i), C.byref(s), C.byref(k), C.byref(b)), "yolo_jpeg_entropy_times")
+        return {"device_files": d.value, "host_files": h.value, "intervals": i.value, "scan_ms": s.value, "device_ms": k.value, "stream_bytes": b.value}
 
     def forward_jpegs(self, files, fit=FIT_STRETCH, want_detections=True):
         """forward_frames over JPEG files (yolo_forward_jpegs): decode, fit, forward.  Returns the decoded tensor [n, rows, attrs]."""

@@ -12,10 +12,11 @@ _FITS = {"letterbox": hip.FIT_LETTERBOX, "stretch": hip.FIT_STRETCH}
 
 
 class Segmenter:
-    def __init__(self, cfg, weights=None, max_batch=1, dtype=hip.BF16, fit="letterbox", device=0, seed=0):
+    def __init__(self, cfg, weights=None, max_batch=1, dtype=hip.BF16, fit="letterbox", device=0, seed=0, jpeg_entropy="host"):
         """cfg: a cfg file path or cfg text with `yolo_output=map` in its [net] section.  weights: a darknet `.weights` file or a flat
         float32 parameter stream; None loads darknet_io's seeded synthetic parameters (`seed`).  fit: "letterbox" (darknet's
-        letterbox_image) or "stretch", or a hip.FIT_* code."""
+        letterbox_image) or "stretch", or a hip.FIT_* code.  jpeg_entropy: "host" or "auto" -- who Huffman-decodes the files of the *_from_files methods
+        (Engine.set_jpeg_entropy); the results are the same."""
         text = IO.with_planes_input(cfg if "[net]" in cfg or "[network]" in cfg else IO.cfg_text(cfg))          # ([net] channels != 3: the key is added here)
         self.engine = hip.Engine(text, max_batch=max_batch, dtype=dtype, semantics=hip.SEM_DARKNET, device=device)
         try:
@@ -29,6 +30,8 @@ class Segmenter:
             self.engine.load_weights(weights)
         else:
             self.engine.set_weights(weights)
+        if jpeg_entropy != "host":
+            self.engine.set_jpeg_entropy(jpeg_entropy)
         self.max_batch = max_batch
         self.fit = _FITS[fit] if isinstance(fit, str) else int(fit)
         self.num_classes = self.map_hwc[2]
