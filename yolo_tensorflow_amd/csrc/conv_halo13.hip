@@ -28,18 +28,18 @@ static bool halo_ok(const ConvArgs &a, int bh, int bw)
     return (double)a.N * a.H * a.W * a.in_stride * dt_size(a.in_dt) < 2147483648.0;
 }
 
-template <int WC, int TC, int NL, int EB, bool FREE = false, int NS = 2, bool H16 = false, bool SPLIT = false, int BH = HALO_B, int BW = HALO_B, bool HEADT = false, bool PAIRK = false>
+template <int WC, int TC, int NL, int EB, bool FREE = false, int NS = 2, bool H16 = false, bool SPLIT = false, int BH = HALO_B, int BW = HALO_B, bool HEADT = false, bool PAIRK = false, bool FRAGW = false>
 static hipError_t launch_h(const ConvArgs &a, hipStream_t s)
 {
     if (a.tail_f32 && !HEADT) return hipErrorInvalidValue;        // a head as the tail runs on the HEADT instantiations (head_tail in the table)
     constexpr int WP = 1, TP = (BH * BW + 15) / 16, BK = 64, BC = WC * TC * 16;
     const long blocks = (long)a.N * ((a.H + BH - 1) / BH) * ((a.W + BW - 1) / BW);
     const long tiles = blocks * ((a.Cout + BC - 1) / BC);
-    constexpr size_t lds = conv_lds_bytes<WP, WC, TP, TC, NS, BK, NL, true, BH, BW>();
+    constexpr size_t lds = conv_lds_bytes<WP, WC, TP, TC, NS, BK, NL, true, BH, BW, FRAGW>();
     static_assert(lds <= 160 * 1024, "halo form: LDS");
-    hipError_t e = conv_opt_in_lds((const void *)conv_igemm<WP, WC, TP, TC, NS, BK, true, NL, false, EB, true, FREE, H16, SPLIT, BH, BW, HEADT, PAIRK>, lds);
+    hipError_t e = conv_opt_in_lds((const void *)conv_igemm<WP, WC, TP, TC, NS, BK, true, NL, false, EB, true, FREE, H16, SPLIT, BH, BW, HEADT, PAIRK, false, FRAGW>, lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((conv_igemm<WP, WC, TP, TC, NS, BK, true, NL, false, EB, true, FREE, H16, SPLIT, BH, BW, HEADT, PAIRK>), dim3((unsigned)((tiles + 7) / 8 * 8)), dim3(64 * (WP * WC + NL)), lds, s, conv_tile_magic(a, BC, BH, BW));
+    hipLaunchKernelGGL((conv_igemm<WP, WC, TP, TC, NS, BK, true, NL, false, EB, true, FREE, H16, SPLIT, BH, BW, HEADT, PAIRK, false, FRAGW>), dim3((unsigned)((tiles + 7) / 8 * 8)), dim3(64 * (WP * WC + NL)), lds, s, conv_tile_magic(a, BC, BH, BW));
     return hipGetLastError();
 }
 
@@ -69,6 +69,10 @@ static hipError_t launch_hid(const ConvArgs &a, hipStream_t s)
 {
     constexpr ConvCfg c = kCfgs[ID];
     static_assert(c.halo && c.wp == 1 && c.bk == 64 && c.tp == (c.bh * c.bw + 15) / 16, "halo form: one wave row over the block's sub-tiles");
+    // the free-running 16-bit forms take their filters as fragments from the fragment-order image when the arguments carry one (FRAGW;
+    // the planner and the operator leave a.wf null under YOLO_NO_FRAGW=1: the filter stages in LDS, the same id)
+    if constexpr (c.free && EB == 2 && !SPLIT && !PAIRK)
+        if (a.wf) return launch_h<c.wc, c.tc, c.nl, EB, c.free, c.ns, H16, SPLIT, c.bh, c.bw, HEADT, PAIRK, true>(a, s);
     return launch_h<c.wc, c.tc, c.nl, EB, c.free, c.ns, H16, SPLIT, c.bh, c.bw, HEADT, PAIRK>(a, s);
 }
 // 16-bit storage: a detection head as the fused tail has its own instantiation where the table says so

@@ -150,7 +150,14 @@ constexpr bool halo_div_ok(int bw) { for (unsigned r = 0; r < 256; ++r) if (((r 
 // masks instead: bits 0..15 the rows, bits 16..31 the columns (sizes up to 16).  A K-step asks for the two bits of its tap at once,
 // (mask & need) == need; a K-step past the last tap (K padding) asks for bit 15, which no mask of a size up to CONV_MAX_SIZE holds.
 // The per-lane cursor carries (kh, kw) along with the tap instead of dividing.  Every other instantiation is untouched by the switch.
-template <int WP, int WC, int TP, int TC, int NS, int BK, bool UNI, int NL = 0, bool DIAG = false, int EB = 2, bool HALO = false, bool FREE = false, bool H16 = false, bool SPLIT = false, int BH = HALO_B, int BW = HALO_B, bool HEADT = false, bool PAIRK = false, bool WIDE = false>
+// FRAGW (free-running 16-bit halo form only): the filters never enter LDS.  A free-running wave is the only reader of its own TC * 16 filter
+// rows, so it takes them as MFMA fragments straight from a second image of the packed filters in FRAGMENT order (a.wf, filter_fragments in
+// yolo_pack.cpp: [row / 16][k / 32][64 lanes][8], the 16 bytes lane (l15, lq) gets from the LDS path through wrow(i) + sw0 / sw1): TC * 2
+// buffer loads of one contiguous KiB each per K-step, issued one K-step ahead where the LDS path issues its filter DMA, into a second set of
+// registers.  (The same path on the ROW-major image lost in round 2, see LA / LB below: that was the layout.)  No filter stages, no filter
+// DMA, no filter ds_read; LDS is the two halo tiles, or the epilogue's tile.  The halo tile, the barrier per chunk, the stagger, K order and
+// every rounding point are the LDS path's: bit-identical.  Both forms are built; the launcher takes this one when the arguments carry a.wf.
+template <int WP, int WC, int TP, int TC, int NS, int BK, bool UNI, int NL = 0, bool DIAG = false, int EB = 2, bool HALO = false, bool FREE = false, bool H16 = false, bool SPLIT = false, int BH = HALO_B, int BW = HALO_B, bool HEADT = false, bool PAIRK = false, bool WIDE = false, bool FRAGW = false>
 __global__ __launch_bounds__(64 * (WP * WC + NL)) void conv_igemm(const ConvArgs a)
 {
 #if defined(__HIP_DEVICE_COMPILE__)   // the host pass only needs the launch stub (hipcc drops the stub of a
@@ -177,7 +184,7 @@ __global__ __launch_bounds__(64 * (WP * WC + NL)) void conv_igemm(const ConvArgs
     // (Tried and dropped: with WP == 1 no filter row is shared between waves, so the filter fragments could go
     // global -> VGPR directly and skip LDS.  Measured SLOWER, K-step 2114 -> 2900 cycles for p176c128: a
     // fragment-shaped load touches 16 rows x 64 B per instruction, which the texture addresser handles far worse than
-    // the 8 x 128-B rows of an LDS-DMA piece.)
+    // the 8 x 128-B rows of an LDS-DMA piece.  From an image in fragment order the same path wins: FRAGW, above the template.)
     constexpr int LA = (GP + NW - 1) / NW, LB = (GC + NW - 1) / NW;
     constexpr int L = LA + LB;
     constexpr int BPL = LA * NW * RG, BCL = LB * NW * RG;    // rows of the LDS images
@@ -191,6 +198,7 @@ __global__ __launch_bounds__(64 * (WP * WC + NL)) void conv_igemm(const ConvArgs
     static_assert(!HALO || LAH <= 9, "a halo tile is fetched during the nine taps of the previous chunk");
     static_assert(!FREE || (HALO && NL == 0 && LB * RG == TC * 16), "free-running form: every wave fetches its own filter rows");
     static_assert(!WIDE || (!HALO && !PAIRK && !SPLIT && !DIAG && EB == 2), "row / column tap masks: the tiled 16-bit form");
+    static_assert(!FRAGW || (HALO && FREE && EB == 2 && !SPLIT && !PAIRK), "filter fragments from global memory: the free-running 16-bit halo form");
 
     if constexpr (H16) fp16_saturating_mode();
     extern __shared__ __attribute__((aligned(16))) char smem[];   // [NS][ BP rows | BC rows ][128 B]
@@ -259,11 +267,32 @@ __global__ __launch_bounds__(64 * (WP * WC + NL)) void conv_igemm(const ConvArgs
 #pragma unroll
     for (int i = 0; i < LB; ++i) {
         const int crow = (FREE ? wid * LB + i : wid + i * NW) * RG + rl;
-        woff[i] = crow < BC ? (unsigned)((ct * BC + crow) * a.Kpad + chunk * EPC) * (unsigned)EB : OOB_OFFSET;
+        woff[i] = FRAGW ? 0u : crow < BC ? (unsigned)((ct * BC + crow) * a.Kpad + chunk * EPC) * (unsigned)EB : OOB_OFFSET;
+    }
+    // FRAGW: this lane's 16 bytes of K-half 0 of K-step 0 of the wave's channel sub-tile i in the fragment-order image (K-half 1: + 1 KiB,
+    // the next K-step: + 2 KiB); fwq: the fragments in flight, those of the K-step after the one being multiplied
+    __amdgpu_buffer_rsrc_t rwf = buf_rsrc(FRAGW ? a.wf : nullptr);
+    unsigned fwoff[FRAGW ? TC : 1];
+    bf16x8 fwq[FRAGW ? 2 : 1][FRAGW ? TC : 1];
+    int s_wf = 0;                              // byte offset of the K-step in a sub-tile's run of fragments
+    auto load_fwq = [&]() {
+        if constexpr (FRAGW) {
+#pragma unroll
+            for (int i = 0; i < TC; ++i)
+#pragma unroll
+                for (int kk = 0; kk < 2; ++kk) fwq[kk][i] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rwf, fwoff[i] + kk * 1024u, s_wf, 0));
+            s_wf += 2048;
+        }
+    };
+    if constexpr (FRAGW) {
+#pragma unroll
+        for (int i = 0; i < TC; ++i) fwoff[i] = ((unsigned)((ct * (BC / 16) + wci * TC + i) * (a.Kpad / 32)) * 64u + (unsigned)lane) * 16u;
     }
     // K-step 0's filter rows are requested first -- their offsets are the cheapest to form, and the pixel addressing below (halo form:
     // ~130 instructions; tiled form: ~55 per row group) then runs while they are in flight.  Order in the vmcnt queue: filters of step 0,
     // activations of step 0, later stages: the counted waits of the K loop only rely on whole K-steps retiring in order.
+    if constexpr (FRAGW) load_fwq();
+    else
     if (is_loader && 0 < a.Kpad / BKE) {
         char *const f0 = smem + (HALO ? 2 * ACT_BYTES : BPL * RB);
 #pragma unroll
@@ -453,7 +482,7 @@ __global__ __launch_bounds__(64 * (WP * WC + NL)) void conv_igemm(const ConvArgs
             for (int i = 0; i < LAH; ++i)
                 if (wid + i * NW < APIECES) __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (lds_void *)(smem + (wid + i * NW) * 1024), 16, aoff[i], 0, 0, HALO_LOAD_AUX);
 #pragma unroll
-            for (int t = 1; t < (FREE ? NS - 1 : 1); ++t)        // (stage 0 was requested ahead of the halo addressing)
+            for (int t = 1; t < (FRAGW ? 1 : FREE ? NS - 1 : 1); ++t)        // (stage 0 was requested ahead of the halo addressing)
                 if (t < KT) {
 #pragma unroll
                     for (int i = 0; i < LB; ++i)
@@ -505,7 +534,8 @@ __global__ __launch_bounds__(64 * (WP * WC + NL)) void conv_igemm(const ConvArgs
     // of an inlined function are what produces that metadata.
     // MFMA phase of one K-step.  xrow(j) / wrow(i): LDS address of this lane's row of pixel sub-tile j / channel sub-tile i;
     // xs0 / xs1: byte offsets of the lane's 16-B piece of a pixel row in the two K-halves (filter rows: sw0 / sw1).
-    auto mma_phase = [&](auto xrow, auto wrow, const int xs0, const int xs1) {
+    // fwr (FRAGW): the step's filter fragments, already in registers -- no filter ds_read, and none in the pinned order
+    auto mma_phase = [&](auto xrow, auto wrow, const int xs0, const int xs1, const bf16x8 (*fwr)[FRAGW ? TC : 1] = nullptr) {
         // Fragment reads are software-pipelined PD MFMA groups ahead and PINNED there with sched_group_barrier: left
         // alone the scheduler hoists every ds_read of the (half) step above the first MFMA and waits lgkmcnt(0), so
         // the LDS pipe and the MFMA pipe take turns instead of overlapping (all four waves are in the same phase).
@@ -606,7 +636,10 @@ __global__ __launch_bounds__(64 * (WP * WC + NL)) void conv_igemm(const ConvArgs
             bf16x8 fw[KH][TC], fx[NG];
             auto rdw = [&](int kk) {
 #pragma unroll
-                for (int i = 0; i < TC; ++i) fw[kk][i] = *(const bf16x8 *)(wrow(i) + (kk ? sw1 : sw0));
+                for (int i = 0; i < TC; ++i) {
+                    if constexpr (FRAGW) fw[kk][i] = fwr[kk][i]; else
+                    fw[kk][i] = *(const bf16x8 *)(wrow(i) + (kk ? sw1 : sw0));
+                }
             };
             auto rdx = [&](int g) {
                 const int kk = g / TP, j = g - kk * TP;
@@ -629,11 +662,11 @@ __global__ __launch_bounds__(64 * (WP * WC + NL)) void conv_igemm(const ConvArgs
                 for (int i = 0; i < TC; ++i)
                     acc[i][j] = mma16<H16>(fw[kk][i], fx[g], acc[i][j]);
             }
-            __builtin_amdgcn_sched_group_barrier(0x100, TC + (W1_UPFRONT ? TC : 0) + PD, 0);
+            __builtin_amdgcn_sched_group_barrier(0x100, (FRAGW ? 0 : TC + (W1_UPFRONT ? TC : 0)) + PD, 0);
 #pragma unroll
             for (int g = 0; g < NG; ++g) {
                 if (g + PD < NG) {
-                    if (KH == 2 && !W1_UPFRONT && g + PD == TP) __builtin_amdgcn_sched_group_barrier(0x100, TC, 0);
+                    if (KH == 2 && !W1_UPFRONT && g + PD == TP && !FRAGW) __builtin_amdgcn_sched_group_barrier(0x100, TC, 0);
                     __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
                 }
                 __builtin_amdgcn_sched_group_barrier(0x008, TC, 0);
@@ -693,9 +726,18 @@ __global__ __launch_bounds__(64 * (WP * WC + NL)) void conv_igemm(const ConvArgs
         // LDS-DMA instructions this wave issues in this step; f_ops1 / f_ops2: in the previous step / the one before (the filters of
         // K-step kt were issued NS - 1 steps ago: everything issued since may still be in flight when they are waited for)
         const int ops_now = (do_a ? 1 : 0) + (load_f ? LB : 0);
+        // FRAGW: this step's fragments were requested one step ago into fwq, which the loads issued now overwrite.  They land in order behind
+        // what was issued since (at most one halo piece and the next step's loads): the compiler's own counted wait in front of the first MFMA
+        bf16x8 fwc[FRAGW ? 2 : 1][FRAGW ? TC : 1];
+        if constexpr (FRAGW) {
+#pragma unroll
+            for (int i = 0; i < TC; ++i) { fwc[0][i] = fwq[0][i]; fwc[1][i] = fwq[1][i]; }
+        }
         auto issue = [&]() {
             if constexpr (ATAP)
                 if (do_a) __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (lds_void *)(fill_a + (wid + TAP * NW) * 1024), 16, aoff[TAP < LAH ? TAP : 0], next_chunk * RB, 0, HALO_LOAD_AUX);
+            if constexpr (FRAGW) { if (load_f) load_fwq(); }
+            else
             if (load_f) {
 #pragma unroll
                 for (int i = 0; i < LB; ++i)
@@ -708,7 +750,7 @@ __global__ __launch_bounds__(64 * (WP * WC + NL)) void conv_igemm(const ConvArgs
         if constexpr (TAP == 0) {
             // chunk boundary: this wave's filters of the step and its pieces of this chunk's halo tile have landed; after the barrier
             // everybody's have, and nobody reads the previous chunk's halo tile any more (the next chunk's pieces overwrite it)
-            if constexpr (NS == 2) wait_vmcnt<0>(); else wait_vmcnt_rt<(NS - 2) * (LB + 1)>(NS == 3 ? f_ops1 : f_ops1 + f_ops2);
+            if constexpr (NS == 2 || FRAGW) wait_vmcnt<0>(); else wait_vmcnt_rt<(NS - 2) * (LB + 1)>(NS == 3 ? f_ops1 : f_ops1 + f_ops2);
             block_barrier();
             if (NC == 8 && wave_id >= NC / 2) __builtin_amdgcn_s_sleep(TP * TC * (PAIRK ? PAIR_SLEEP : 32) / 64);      // half a K-step behind the SIMD's other wave (eight-wave forms: two waves per SIMD)
             s1 = stamp();
@@ -718,7 +760,8 @@ __global__ __launch_bounds__(64 * (WP * WC + NL)) void conv_igemm(const ConvArgs
         } else {
             issue();
             s1 = stamp();
-            if constexpr (NS == 2) {
+            if constexpr (FRAGW) { }           // (nothing in LDS to wait for inside a chunk: the fragments are register loads)
+            else if constexpr (NS == 2) {
                 if (load_f) { if (do_a) wait_vmcnt<LB + 1>(); else wait_vmcnt<LB>(); }
                 else { if (do_a) wait_vmcnt<1>(); else wait_vmcnt<0>(); }
             } else wait_vmcnt_rt<(NS - 1) * (LB + 1)>(ops_now + f_ops1 + (NS == 4 ? f_ops2 : 0));
@@ -727,7 +770,7 @@ __global__ __launch_bounds__(64 * (WP * WC + NL)) void conv_igemm(const ConvArgs
         }
         f_ops2 = f_ops1; f_ops1 = ops_now;
         __builtin_amdgcn_s_setprio(2);
-        mma_phase([&](int j) { return sb_a + abase[j] + ((TAP / 3) * HPW + TAP % 3) * APIX; }, [&](int i) { return sb_f + offw + i * 16 * RB; }, 0, 64);
+        mma_phase([&](int j) { return sb_a + abase[j] + ((TAP / 3) * HPW + TAP % 3) * APIX; }, [&](int i) { return sb_f + offw + i * 16 * RB; }, 0, 64, fwc);
         __builtin_amdgcn_s_setprio(0);
         if (DIAG) { if (!a.dbg_light) asm volatile("s_nop 7\n\ts_nop 7" ::: "memory"); t_mma += stamp() - s2; }
     };
@@ -739,7 +782,8 @@ __global__ __launch_bounds__(64 * (WP * WC + NL)) void conv_igemm(const ConvArgs
             char *const sa = (c & 1) ? act1 : act0, *const fa = (c & 1) ? act0 : act1;
             const bool la = c + 1 < NCH;
             static_for<9>([&](auto tapc) {
-                if constexpr (FREE && NS > 2) {
+                if constexpr (FRAGW) fstep(tapc, (char *)nullptr, fa, (const char *)nullptr, sa, kt + 1 < KT, la, c + 1);      // (no filter stages, whatever NS)
+                else if constexpr (FREE && NS > 2) {
                     // ring of NS private filter stages: K-step kt multiplies stage kt % NS and refills the stage it read one step ago
                     fstep(tapc, flt0 + fill_i * FSTAGE, fa, flt0 + cur_i * FSTAGE, sa, kt + NS - 1 < KT, la, c + 1);
                     cur_i = cur_i + 1 == NS ? 0 : cur_i + 1; fill_i = fill_i + 1 == NS ? 0 : fill_i + 1;
@@ -1271,7 +1315,7 @@ __global__ __launch_bounds__(64 * (WP * WC + NL)) void conv_igemm(const ConvArgs
 }
 
 // dynamic LDS of one instantiation: NS staging buffers, re-used by the epilogue's padded output tile
-template <int WP, int WC, int TP, int TC, int NS, int BK, int NL = 0, bool HALO = false, int BH = HALO_B, int BW = HALO_B>
+template <int WP, int WC, int TP, int TC, int NS, int BK, int NL = 0, bool HALO = false, int BH = HALO_B, int BW = HALO_B, bool FRAGW = false>
 constexpr size_t conv_lds_bytes()
 {
     constexpr int NW = NL > 0 ? NL : WP * WC, BP = WP * TP * 16, BC = WC * TC * 16;
@@ -1279,6 +1323,6 @@ constexpr size_t conv_lds_bytes()
     constexpr int LA = ((BP + RG - 1) / RG + NW - 1) / NW, LB = ((BC + RG - 1) / RG + NW - 1) / NW;
     constexpr size_t stage = (size_t)(LA + LB) * NW * RG * (BK * 2);
     constexpr bool tail = conv_tail_shape(WP, WC, BC, 0, 2);      // tail shapes also stage the tail's [BP][BC/2] tile (one LDS size per tile shape: sized by the 16-bit rule, loader waves or not)
-    constexpr size_t lds0 = HALO ? (size_t)2 * halo_apieces(BH, BW) * 1024 + (size_t)NS * LB * NW * RG * (BK * 2) : (size_t)NS * stage, ldso = (size_t)BP * (BC * 2 + 16) + (tail ? (size_t)BP * (BC + 16) : 0);
+    constexpr size_t lds0 = HALO ? (size_t)2 * halo_apieces(BH, BW) * 1024 + (FRAGW ? 0 : (size_t)NS * LB * NW * RG * (BK * 2)) : (size_t)NS * stage, ldso = (size_t)BP * (BC * 2 + 16) + (tail ? (size_t)BP * (BC + 16) : 0);
     return lds0 > ldso ? lds0 : ldso;
 }

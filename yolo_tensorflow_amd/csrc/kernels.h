@@ -80,6 +80,8 @@ struct ConvArgs {
     const void *w2; const float *b2; void *out2; int out2_stride, K2pad, act2;
     const void *w2f;                     // bf16 tail: W2 in MFMA-fragment order [C2 / 16][K2 / 32][64 lanes][8] (yolo_api.cpp tail_fragments)
     const float *oscale2; float out2_inv_scale;      // fp8 tail: per-channel dequantisation scale of W2, 1 / scale of out2
+    const void *wf;                      // 16-bit 3x3 / stride 1 conv: `wt` in MFMA-fragment order [Cout_pad / 16][Kpad / 32][64 lanes][8] (yolo_pack.cpp filter_fragments), or nullptr.
+                                         // With it the free-running halo forms read their filters as fragments from global memory (conv_igemm_kernel.h FRAGW), without it through LDS
     int N, H, W, Cin_pad;
     int Ho, Wo, Cout;
     int ksize, stride, pad;

@@ -77,7 +77,7 @@ void yolo_destroy(yolo_ctx *c)
     hipSetDevice(c->device);
     if (c->stream) hipStreamSynchronize(c->stream);
     for (void *p : c->phys) if (p) hipFree(p);
-    for (auto &L : c->layers) { if (L.d_w) hipFree(L.d_w); if (L.d_b) hipFree(L.d_b); if (L.d_sc) hipFree(L.d_sc); if (L.d_wf) hipFree(L.d_wf); if (L.d_obj) hipFree(L.d_obj); }
+    for (auto &L : c->layers) { if (L.d_w) hipFree(L.d_w); if (L.d_b) hipFree(L.d_b); if (L.d_sc) hipFree(L.d_sc); if (L.d_wf) hipFree(L.d_wf); if (L.d_wfrag) hipFree(L.d_wfrag); if (L.d_obj) hipFree(L.d_obj); }
     for (auto &L : c->layers) for (void *p : {L.d_w2, (void *)L.d_b2, L.d_h, L.d_hn, L.d_rh, (void *)L.d_h32, (void *)L.d_z, (void *)L.d_c}) if (p) hipFree(p);
     for (auto &L : c->layers) for (auto &S : L.sub) { if (S.d_w) hipFree(S.d_w); if (S.d_b) hipFree(S.d_b); }
     if (c->d_state_keep) hipFree(c->d_state_keep);

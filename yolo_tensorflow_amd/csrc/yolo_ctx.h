@@ -45,6 +45,7 @@ struct Layer {
     int cin = 0, cin_pad = 0, kpad = 0, cout_pad = 0;
     void *d_w = nullptr; float *d_b = nullptr; float *d_sc = nullptr;   // filters, bias, fp8 per-channel dequant scale (an L_XCONV: the epilogue's per-filter scale)
     void *d_wf = nullptr;                   // bf16 1x1 conv that can ride in its producer's epilogue: its filters in MFMA-fragment order (tail_fragments)
+    void *d_wfrag = nullptr;                // 16-bit 3x3 / stride 1 conv a free-running halo id can run: d_w in MFMA-fragment order (filter_fragments)
     int in_dt = DT_BF16;                 // operand type of this conv's MFMA (filters are stored in it)
     int store_dt = DT_BF16;              // element type of this layer's output tensor (mixed plans: an fp8 network with bf16 islands, cfg key yolo_store)
     bool pair = false;                   // YOLO_FP16X2 networks: this layer's output tensor is split-fp16 PAIRS (interleaved per 32-channel group, 2 x the channels); false there:
@@ -198,6 +199,7 @@ struct yolo_ctx {
     // (-1: none); hier_thresh: yolo_set_hier_thresh; hierarchy_mode: yolo_set_hierarchy_mode; tree_full: YOLO_TREE_FULL forces the full
     // decode in yolo_detect*; lean_hier: the hier_thresh the last descent-form decode labelled its rows with
     std::vector<Tree> trees; int tree_head = -1; float hier_thresh = 0.5f, lean_hier = 0.f; int hierarchy_mode = 0; bool tree_full = false;
+    bool fragw = true;                    // the free-running halo forms read their filters as fragments from global memory (Layer::d_wfrag); false under YOLO_NO_FRAGW=1: through LDS
     int *d_map200 = nullptr;
     bool weights_loaded = false;
     int scores_mode = -1;                 // what d_scores/d_labels hold: 0 max(obj*cls) from the decode, 1 objectness, -1 nothing
@@ -277,6 +279,8 @@ float h2f(uint16_t h);
 void resolve_scales(yolo_ctx *c);
 void channel_scales(const yolo_ctx *c, int idx, std::vector<float> &out);
 int tail_fragments(yolo_ctx *c);
+void fragment_order(const uint16_t *src, int rows, int K, uint16_t *dst);      // [row][K] 16-bit filters -> [row / 16][K / 32][64 lanes][8]
+int filter_fragments(yolo_ctx *c);      // Layer::d_wfrag of every conv a free-running halo id can run (none under YOLO_NO_FRAGW)
 // recurrent layers: the sublayers of layer L in file order -- {inputs, 1 for a sublayer over the state} per sublayer -- and the floats one holds
 int recur_sublayers(const Layer &L, int subs[8]);
 inline size_t connected_floats(int inputs, int outputs, int bn) { return (size_t)outputs * (1 + (size_t)inputs + (bn ? 3 : 0)); }

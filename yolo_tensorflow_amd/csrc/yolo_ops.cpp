@@ -248,6 +248,12 @@ static int op_conv2d_any(const float *x, int n, int h, int w, int cin, const flo
     a.res = d_r; a.res_stride = cstride; a.N = n; a.H = h; a.W = w; a.Cin_pad = L.cin_pad; a.Ho = ho; a.Wo = wo; a.Cout = cout;
     a.ksize = k; a.stride = stride; a.pad = L.pad; a.Kpad = L.kpad; a.kchunk = conv_kchunk(L.cin_pad, dt); a.act = act; a.zeros = d_z;
     conv_finalize(a);
+    // what filter_fragments gives such a layer of a network: the packed filters once more, in fragment order (YOLO_NO_FRAGW=1: not, as there)
+    if ((dt == DT_BF16 || dt == DT_F16) && k == 3 && stride == 1 && padding == 1 && L.cin_pad % 64 == 0 && L.kpad == 9 * L.cin_pad && !getenv("YOLO_NO_FRAGW")) {
+        std::vector<uint16_t> wfrag(wbuf.size() / 2);
+        fragment_order((const uint16_t *)wbuf.data(), L.cout_pad, L.kpad, wfrag.data());
+        a.wf = S.upload(wfrag.data(), wfrag.size() * 2);
+    }
     const int cfg = tile_cfg >= 0 ? tile_cfg : conv_default_cfg(a);
     if (conv_cfg_is_halo(cfg) && (f32 || !conv_cfg_runs(a, cfg))) { g_op_err = "conv2d: tile config not applicable to this shape (halo-staged form: 3x3, stride 1, size a multiple of 13, whole channel chunks)"; return YOLO_ERR_UNSUPPORTED; }
     if (!f32 && conv_is_wide(a) && !conv_cfg_runs(a, cfg)) { g_op_err = "conv2d: tile config " + std::to_string(cfg) + " has no form for convs of more than 25 taps (row / column tap masks)"; return YOLO_ERR_UNSUPPORTED; }

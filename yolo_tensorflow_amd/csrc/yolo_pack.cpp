@@ -311,6 +311,39 @@ void channel_scales(const yolo_ctx *c, int idx, std::vector<float> &out)
 // 64-byte pieces 2 * K bytes apart, and every workgroup of the layer asks for the same 64 KB at the same moment; a copy in fragment
 // order -- [channel tile][K step][lane][8 bf16] -- makes each wave-load one contiguous KiB.  Built from the packed filters already on
 // the device, so both ways of loading parameters (weight stream, export artifact) share it.
+// rows [0, rows) of a 16-bit [row][K] filter image in fragment order: [row / 16][K / 32][64 lanes][8 elements] (rows a multiple of 16, K of 32)
+void fragment_order(const uint16_t *src, int rows, int K, uint16_t *dst)
+{
+    const int K2S = K / 32;
+    for (int ct2 = 0; ct2 < rows / 16; ++ct2)
+        for (int kk = 0; kk < K2S; ++kk)
+            for (int lane = 0; lane < 64; ++lane)
+                memcpy(&dst[(((size_t)ct2 * K2S + kk) * 64 + lane) * 8], &src[(size_t)(ct2 * 16 + (lane & 15)) * K + (kk * 4 + (lane >> 4)) * 8], 16);
+}
+
+// The free-running halo forms (conv_igemm_kernel.h FRAGW) read the filters of their main K loop the same way: every 16-bit 3x3 / stride 1 /
+// pad 1 conv over whole 64-channel chunks -- what such an id can run (conv_halo13.hip halo_ok; the spatial size is the launch's business) --
+// gets a second image of ALL its packed rows in fragment order.  The rows past the filters are the packed image's own zero rows, the K order
+// is the packed image's (chunk-major), so fragment (ct, kt, kk) holds exactly what the LDS path reads at wrow(i) + sw0 / sw1 of K-step kt.
+bool wants_filter_fragments(const yolo_ctx *c, const Layer &L)
+{
+    return c->fragw && !c->split() && L.type == L_CONV && (L.in_dt == DT_BF16 || L.in_dt == DT_F16) && !L.head && !L.fc && !L.s2d7 &&
+           L.size == 3 && L.stride == 1 && L.pad == 1 && L.cin_pad % 64 == 0 && L.kpad == 9 * L.cin_pad && L.cout_pad % 16 == 0;
+}
+int filter_fragments(yolo_ctx *c)
+{
+    std::vector<uint16_t> src, dst;
+    for (auto &L : c->layers) {
+        if (!wants_filter_fragments(c, L)) continue;
+        src.resize((size_t)L.cout_pad * L.kpad); dst.resize(src.size());
+        HIPCK(c, hipMemcpy(src.data(), L.d_w, src.size() * 2, hipMemcpyDeviceToHost));
+        fragment_order(src.data(), L.cout_pad, L.kpad, dst.data());
+        if (!L.d_wfrag) HIPCK(c, hipMalloc(&L.d_wfrag, dst.size() * 2));
+        HIPCK(c, hipMemcpy(L.d_wfrag, dst.data(), dst.size() * 2, hipMemcpyHostToDevice));
+    }
+    return YOLO_OK;
+}
+
 int tail_fragments(yolo_ctx *c)
 {
     std::vector<uint16_t> src, dst;
@@ -324,11 +357,7 @@ int tail_fragments(yolo_ctx *c)
         if (C2 > T.cout_pad || K % 32 || (T.head && T.cout_pad < 256)) continue;
         src.resize((size_t)T.cout_pad * K); dst.assign((size_t)C2 * K, 0);
         HIPCK(c, hipMemcpy(src.data(), T.d_w, src.size() * 2, hipMemcpyDeviceToHost));
-        const int K2S = K / 32;
-        for (int ct2 = 0; ct2 < C2 / 16; ++ct2)
-            for (int kk = 0; kk < K2S; ++kk)
-                for (int lane = 0; lane < 64; ++lane)
-                    memcpy(&dst[(((size_t)ct2 * K2S + kk) * 64 + lane) * 8], &src[(size_t)(ct2 * 16 + (lane & 15)) * K + (kk * 4 + (lane >> 4)) * 8], 16);
+        fragment_order(src.data(), C2, K, dst.data());
         if (!T.d_wf) HIPCK(c, hipMalloc(&T.d_wf, dst.size() * 2));
         HIPCK(c, hipMemcpy(T.d_wf, dst.data(), dst.size() * 2, hipMemcpyHostToDevice));
     }
@@ -443,6 +472,7 @@ int yolo_set_weights(yolo_ctx *c, const float *flat, size_t n)
         if (L.d_sc) HIPCK(c, hipMemcpy(L.d_sc, osc.data(), osc.size() * 4, hipMemcpyHostToDevice));
     }
     if (int rc = tail_fragments(c)) return rc;
+    if (int rc = filter_fragments(c)) return rc;
     c->weights_loaded = true;
     return YOLO_OK;
 }
@@ -598,7 +628,7 @@ yolo_ctx *yolo_create_from_file(const char *path, int max_batch, int device, voi
     }
     uint64_t sum = 0; const bool got = fread(&sum, 1, 8, f) == 8; fclose(f);
     if (!got || sum != r.h) return bail(c, "artifact checksum mismatch");
-    if (tail_fragments(c) != YOLO_OK) return bail(c, c->err);
+    if (tail_fragments(c) != YOLO_OK || filter_fragments(c) != YOLO_OK) return bail(c, c->err);
     c->weights_loaded = true;
     // the tile plan is only meaningful for the tile table it was tuned with and for a plan that fuses nothing it cannot
     if (hd.num_cfgs == (uint32_t)conv_num_cfgs() && !keep_layers) { if (yolo_set_tile_configs(c, plan.data()) != YOLO_OK) { std::vector<int32_t> none(hd.n_layers, -1); yolo_set_tile_configs(c, none.data()); } }

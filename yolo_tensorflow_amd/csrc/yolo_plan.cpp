@@ -1125,6 +1125,7 @@ int allocate(yolo_ctx *c)
     }
     // ... or the one [region] head with a tree: its descent form writes scores, labels and box4.  Which form yolo_detect* takes:
     // YOLO_TREE_FULL forces the full decode, YOLO_TREE_DESCENT the descent; otherwise TREE_DESCENT_DEFAULT (NOTEBOOK, "Softmax trees")
+    c->fragw = !getenv("YOLO_NO_FRAGW");      // (A/B and the identity tests: the same ids with their filter stages in LDS)
     c->tree_full = getenv("YOLO_TREE_FULL") ? true : getenv("YOLO_TREE_DESCENT") ? false : !TREE_DESCENT_DEFAULT;
     if (c->tree_head >= 0) c->lean_ok = !c->tree_full;
     c->lean_heads = 0;

@@ -23,6 +23,7 @@ ConvArgs conv_args(const yolo_ctx *c, const Layer &L, int n)
     if (L.pair || (c->split() && L.out.dt == DT_F32)) a.split = 1;
     a.pairk = L.in[0] >= 0 && c->pair_of(L.in[0]) ? 1 : 0;          // the input is an interleaved pair tensor: the pair K loop (the network input's three blocks: the plain one)
     a.out_inv_scale = 1.f; a.res_scale = 1.f; a.mid_scale = 1.f; a.mid_inv_scale = 1.f;
+    if (c->fragw) a.wf = L.d_wfrag;          // (null for every conv but those filter_fragments serves)
     const int li = (int)(&L - c->layers.data());
     if (L.residual_from >= -1) { TView r = view_of(c, L.residual_from); a.res = r.ptr; a.res_stride = r.stride; }
     // the tail runs on the producer's operand type: bf16 needs the fragment-order copy of the 1x1 filters (tail_fragments), e4m3 an
